@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — image+text embeddings/sec of the MI355X-native CLIP encoder (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config NAME]
+    python bench.py --gpus N --steps K --warmup W [--config NAME] [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
 
 One "step" = one pass of the hot path over one batch of synthetic input that is ALREADY resident in HBM:
@@ -14,11 +14,15 @@ Default workload = the configuration BASELINE.json's metric is quoted on: ViT-B/
 `--config` selects the other rows of the north_star target matrix (ViT-B/32 q4_0 and ViT-L/14 f16 at batch 1 / 32 / 256)
 and the BASELINE configs 2-5 in their single-GPU forms; see CONFIGS.
 
-Prints ONE JSON line (rank 0) with the driver's contract keys plus
-  "roofline"            — dominant kernel (the GEMM instantiation with the largest total time), timed live with HIP events
-                          on the launch stream in a second pass of the same K steps
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the driver's contract keys
+(`ms_per_step` = wall clock of the K steps / K), the per-step event statistics and
   "whole_step_roofline" — EXECUTED FLOPs (SURVEY 8(d) figure minus the last layer's pruned rows) / algorithmic bytes of the whole step
                           against ms_per_step; the SURVEY-figure view of the same time under frac_survey_flops
+`--dump-outputs DIR` writes the embeddings of the last timed step as DIR/<name>.npy (float32).  `--full` adds what takes runs of its
+own, each behind every timed region:
+  "images_per_s_per_gpu" / "texts_per_s_per_gpu" — one tower at a time
+  "roofline"            — dominant kernel (the GEMM instantiation with the largest total time), timed live with HIP events
+                          on the launch stream in a second pass of the same K steps
   "matrix"              — the other north_star cells, each with gpu_vs_cpu_1_minus_cos_max of rows kept from its timed call
   "cpu_baseline"        — the CPU oracle (restatement of the ggml path; ggml itself is absent) on a bounded sample, all host
                           cores and the reference harness's chunk-of-4 / 4-thread form (tests/benchmark.cpp:50-51), with the
@@ -57,6 +61,20 @@ CONFIGS = {
     "b32_q4_0_b256_img": dict(model="b32", ftype="q4_0", batch=256, texts=0, steps=100),
 }
 BITS_PER_WEIGHT = {"f32": 32.0, "f16": 16.0, "q4_0": 4.5, "q4_1": 5.0, "q5_0": 5.5, "q5_1": 6.0, "q8_0": 8.5}
+DUMP_CAP_BYTES = 64 << 20      # --dump-outputs: all files together
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array as dirname/<name>.npy in float32.  Above DUMP_CAP_BYTES in all, every array keeps the same fixed, seeded
+    sample of rows (sorted), so that two builds of the project still compare row for row."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_CAP_BYTES and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * DUMP_CAP_BYTES // total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def parse():
@@ -91,6 +109,12 @@ def parse():
     ap.add_argument("--matrix", action="store_true", help="run the matrix cells also with a non-default --config")
     ap.add_argument("--json-out", default=None)
     ap.add_argument("--no-rates", action="store_true", help="skip the separate image-only / text-only passes (PMC collection: every launch of the process then belongs to a W + K step)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: single-tower rates, the per-kernel roofline pass, the host-pointer API, "
+                         "the CPU-oracle baseline and (default config) the north_star matrix; the --no-* options above deselect parts of it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the embeddings the last timed step produced as DIR/<name>.npy (float32; a seeded "
+                         "sample of rows above %d MB in all); the inputs depend on the arguments only" % (DUMP_CAP_BYTES >> 20))
     ap.add_argument("--stub-encoder", action="store_true",
                     help="CPU test tier only (tests/test_bench_launch.py): torch CPU tensors, the gloo backend and a trivial stand-in for the two "
                          "towers, so that the launcher, the collective skeleton and the JSON contract of this file run without a GPU; the line says so in `data`")
@@ -372,6 +396,14 @@ def single_process_main(args, cfg, steps, batch, n_texts, torch, clip_cpp_amd, s
     for _ in range(steps):
         step()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:       # the step's calls return nothing to the host: one more call of the last step, with host outputs
+        outs = {"image_embeddings": np.empty((N * batch, proj), dtype=np.float32)}
+        if n_texts:
+            outs["text_embeddings"] = np.empty((N * n_texts, proj), dtype=np.float32)
+            clip.encode_pair_device_multi(img_ptrs, N * batch, id_ptrs, offsets, True, outs["image_embeddings"], outs["text_embeddings"])
+        else:
+            clip.encode_images_device_multi(img_ptrs, N * batch, True, outs["image_embeddings"])
+        dump_outputs(args.dump_outputs, outs)
     out_i = np.empty((N * batch, proj), dtype=np.float32)
     clip.encode_images_device_multi(img_ptrs, N * batch, True, out_i)
     assert np.all(np.isfinite(out_i)), "non-finite embeddings"
@@ -477,6 +509,13 @@ def stub_main(args, cfg, steps, batch, n_texts, torch, dist, rank, world, N):
         per = batch + n_texts
         for r in range(world if N > 1 else 1):
             assert torch.allclose(gathered[r * per:(r + 1) * per], towers(inputs(r)), atol=1e-6), "all-gather block %d is not rank %d's embeddings" % (r, r)
+    if args.dump_outputs and rank == 0:
+        outs = {"image_embeddings": emb[:batch].numpy()}
+        if n_texts:
+            outs["text_embeddings"] = emb[batch:].numpy()
+        if use_dist:
+            outs["gathered_embeddings"] = gathered.numpy()
+        dump_outputs(args.dump_outputs, outs)
     if rank == 0:
         out = {"metric": "image+text embeddings/sec", "value": round(N * (batch + n_texts) * steps / dt, 1), "unit": "embeddings/s", "n_gpus": N,
                "steps": steps, "warmup": args.warmup, "preheat_s": args.preheat, "ms_per_step": round(dt / steps * 1e3, 4), "higher_is_better": True,
@@ -495,6 +534,8 @@ def stub_main(args, cfg, steps, batch, n_texts, torch, dist, rank, world, N):
 
 def main():
     args = parse()
+    if not args.full:      # a plain run measures the headline only
+        args.no_rates = args.no_roofline = args.no_host_api = args.no_cpu_baseline = args.no_matrix = True
     import torch
     import torch.distributed as dist
 
@@ -628,6 +669,13 @@ def main():
     per_step_units = N * (batch + n_texts)
     value = per_step_units * steps / dt
     assert bool(torch.isfinite(emb).all()), "non-finite embeddings"
+    if args.dump_outputs and rank == 0:     # before anything else writes into emb
+        outs = {"image_embeddings": img_out.cpu().numpy()}
+        if n_texts:
+            outs["text_embeddings"] = txt_out.cpu().numpy()
+        if use_dist:
+            outs["gathered_embeddings"] = gathered.cpu().numpy()
+        dump_outputs(args.dump_outputs, outs)
 
     # separate image-only / text-only rates (rank-local, informative): one tower at a time = the device is not shared
     def rate(fn, units):
@@ -639,7 +687,7 @@ def main():
         torch.cuda.synchronize()
         return units * n / (time.perf_counter() - t)
 
-    img_rate = txt_rate = 0.0
+    img_rate = txt_rate = None
     if not args.no_rates:
         share(False)
         img_rate = rate(lambda: clip.encode_images_device(imgs.data_ptr(), batch, img_out.data_ptr(), True), batch)
@@ -878,7 +926,7 @@ def main():
                        "last_layer": ("every row (CLIP_AMD_PRUNE_LAST=0)" if os.environ.get("CLIP_AMD_PRUNE_LAST", "1") == "0" else
                                       "out-projection + FFN of the LAST layer computed for the pooled row of each sequence only — the rows the embeddings are taken from "
                                       "(class token / last token, reference clip.cpp:1426-1431, 1154-1155); identical embeddings; whole_step_roofline.executed_flops_per_step")},
-            "images_per_s_per_gpu": round(img_rate, 1), "texts_per_s_per_gpu": round(txt_rate, 1),
+            "images_per_s_per_gpu": img_rate and round(img_rate, 1), "texts_per_s_per_gpu": txt_rate and round(txt_rate, 1),
             "host_api_images_per_s": host_api,
             "host_api_images_per_s_4x_batch_per_call": host_api_x4,
             "host_api_u8_images_per_s": host_api_u8,

@@ -1,19 +1,19 @@
 #!/bin/bash
-# One gpurun call: GPU test tier + smoke + bench + rocprofv3 kernel trace (+ PMC HBM traffic / MFMA busy). Logs under gpurun_out/.
+# One GPU session: GPU test tier + smoke + bench --full + rocprofv3 kernel trace (+ PMC HBM traffic / MFMA busy). Logs under $OUT (default gpu_logs/).
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-mkdir -p gpurun_out
+OUT=${OUT:-gpu_logs}; mkdir -p "$OUT"
 export TMPDIR=/tmp
 TAG=${1:-r02}
 R="${GRAFT_REPO_ROOT:-/root/repo}"
 if [ "${PROFILE_ONLY:-0}" != "1" ]; then
-echo "== GPU tests" ; timeout 2400 python -m pytest tests/ -m gpu -q -p no:cacheprovider 2>&1 | grep -E " passed| failed| error|FAILED|ERROR|max .* mean|1-cos" | tail -24 | tee gpurun_out/${TAG}_tests.log
-echo "== smoke" ; timeout 300 python __graft_entry__.py --smoke 2>&1 | tail -3 | tee gpurun_out/${TAG}_smoke.log
-echo "== bench" ; timeout 900 python bench.py --json-out gpurun_out/${TAG}_bench.json 2>&1 | tail -2 | cut -c1-4000 | tee gpurun_out/${TAG}_bench.log
+echo "== GPU tests" ; timeout 2400 python -m pytest tests/ -m gpu -q -p no:cacheprovider 2>&1 | grep -E " passed| failed| error|FAILED|ERROR|max .* mean|1-cos" | tail -24 | tee $OUT/${TAG}_tests.log
+echo "== smoke" ; timeout 300 python __graft_entry__.py --smoke 2>&1 | tail -3 | tee $OUT/${TAG}_smoke.log
+echo "== bench" ; timeout 900 python bench.py --full --json-out $OUT/${TAG}_bench.json 2>&1 | tail -2 | cut -c1-4000 | tee $OUT/${TAG}_bench.log
 fi
 echo "== rocprof kernel trace (default config)" ; (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_${TAG} -o ${TAG} -- python "$R/bench.py" --steps 10 --warmup 3 --preheat 0.3 --no-matrix --no-cpu-baseline --no-roofline --no-host-api > /tmp/prof_${TAG}.log 2>&1; tail -1 /tmp/prof_${TAG}.log | cut -c1-300)
-for f in $(find /tmp/prof_${TAG} -name "*kernel_stats*.csv"); do grep -v "at::native\|__amd_rocclr" $f | cut -c1-400 > gpurun_out/${TAG}_kernel_stats_b32_q4_0_b256.csv; done
-head -8 gpurun_out/${TAG}_kernel_stats_b32_q4_0_b256.csv | cut -c1-200
+for f in $(find /tmp/prof_${TAG} -name "*kernel_stats*.csv"); do grep -v "at::native\|__amd_rocclr" $f | cut -c1-400 > $OUT/${TAG}_kernel_stats_b32_q4_0_b256.csv; done
+head -8 $OUT/${TAG}_kernel_stats_b32_q4_0_b256.csv | cut -c1-200
 # the same trace split by (kernel name, grid): one instantiation serves several GEMM shapes (both towers), a per-name average mixes them
 python - <<PY
 import csv, glob, collections
@@ -26,7 +26,7 @@ for f in glob.glob("/tmp/prof_${TAG}/**/*kernel_trace.csv", recursive=True):
         gy = int(r.get("Grid_Size_Y") or 1); wy = int(r.get("Workgroup_Size_Y") or 1)
         acc[(k.replace("void clipamd::(anonymous namespace)::", "").split("(")[0], (gx // max(1, wx)) * max(1, gy // max(1, wy)))].append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
 rows = sorted(((sum(v), k, v) for k, v in acc.items()), reverse=True)
-with open("gpurun_out/${TAG}_kernel_stats_by_grid_b32_q4_0_b256.csv", "w") as o:
+with open("$OUT/${TAG}_kernel_stats_by_grid_b32_q4_0_b256.csv", "w") as o:
     o.write('"Name","Workgroups","Calls","TotalDurationNs","AverageNs","MinNs","MaxNs"\n')
     for tot, (name, wgs), v in rows:
         o.write('"%s",%d,%d,%d,%.1f,%d,%d\n' % (name, wgs, len(v), tot, tot / len(v), min(v), max(v)))
@@ -34,17 +34,17 @@ for tot, (name, wgs), v in rows[:10]: print("%-48s grid %5d WGs  x%5d  avg %8.1f
 PY
 echo "== rocprof kernel trace (batch 1, L/14 f16 batch 256)"
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_${TAG}_b1 -o b1 -- python "$R/bench.py" --config b32_q4_0_b1 --vision-only --steps 50 --no-cpu-baseline --no-roofline --no-host-api > /tmp/prof_b1.log 2>&1)
-for f in $(find /tmp/prof_${TAG}_b1 -name "*kernel_stats*.csv"); do grep -v "at::native\|__amd_rocclr" $f | cut -c1-400 > gpurun_out/${TAG}_kernel_stats_b32_q4_0_b1.csv; done
+for f in $(find /tmp/prof_${TAG}_b1 -name "*kernel_stats*.csv"); do grep -v "at::native\|__amd_rocclr" $f | cut -c1-400 > $OUT/${TAG}_kernel_stats_b32_q4_0_b1.csv; done
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_${TAG}_l14 -o l14 -- python "$R/bench.py" --config cfg3_l14_f16_b256_img --steps 3 --warmup 1 --preheat 0.3 --no-cpu-baseline --no-roofline --no-host-api > /tmp/prof_l14.log 2>&1)
-for f in $(find /tmp/prof_${TAG}_l14 -name "*kernel_stats*.csv"); do grep -v "at::native\|__amd_rocclr" $f | cut -c1-400 > gpurun_out/${TAG}_kernel_stats_l14_f16_b256.csv; done
-head -6 gpurun_out/${TAG}_kernel_stats_b32_q4_0_b1.csv | cut -c1-160; head -6 gpurun_out/${TAG}_kernel_stats_l14_f16_b256.csv | cut -c1-160
-echo "== launch-boundary micro-benchmark"; [ -x scripts/ubench/launch_chain ] && timeout 300 ./scripts/ubench/launch_chain | tee gpurun_out/${TAG}_launch_chain.txt | tail -18
+for f in $(find /tmp/prof_${TAG}_l14 -name "*kernel_stats*.csv"); do grep -v "at::native\|__amd_rocclr" $f | cut -c1-400 > $OUT/${TAG}_kernel_stats_l14_f16_b256.csv; done
+head -6 $OUT/${TAG}_kernel_stats_b32_q4_0_b1.csv | cut -c1-160; head -6 $OUT/${TAG}_kernel_stats_l14_f16_b256.csv | cut -c1-160
+echo "== launch-boundary micro-benchmark"; [ -x scripts/ubench/launch_chain ] && timeout 300 ./scripts/ubench/launch_chain | tee $OUT/${TAG}_launch_chain.txt | tail -18
 echo "== rocprof PMC (HBM traffic, MFMA busy)"
 for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE"; do
   n=$(echo $set | cut -d' ' -f1)
   (cd /tmp && timeout 600 rocprofv3 --pmc $set --kernel-trace --output-format csv -d /tmp/pmc_${TAG}_$n -o pmc -- python "$R/bench.py" --steps 3 --warmup 1 --preheat 0 --no-matrix --no-cpu-baseline --no-roofline --no-host-api --no-rates > /tmp/pmc_${TAG}_$n.log 2>&1)
 done
-python - <<PY | tee gpurun_out/${TAG}_pmc_traffic_and_mfma_busy.txt
+python - <<PY | tee $OUT/${TAG}_pmc_traffic_and_mfma_busy.txt
 import csv, glob, collections, json, sys
 sys.path.insert(0, "$R")
 acc = collections.defaultdict(lambda: collections.defaultdict(float)); cnt = collections.Counter()
@@ -72,7 +72,7 @@ out["_whole_step_hbm_bytes"] = tot / 4.0
 print("whole step: %.3e HBM bytes (sum over every launch of a step; 4 steps in the PMC run)" % out["_whole_step_hbm_bytes"])
 out["_kernel_src_sha16"] = bench.kernel_source_sha16()      # bench.py reports roofline.traffic only while the kernel sources are these
 out["_config"] = "b32_q4_0_b256"
-json.dump(out, open("gpurun_out/${TAG}_pmc_traffic.json", "w"), indent=1)
+json.dump(out, open("$OUT/${TAG}_pmc_traffic.json", "w"), indent=1)
 print("-- MFMA busy (SQ_VALU_MFMA_BUSY_CYCLES summed over all SIMDs; 16 cycles per v_mfma_f32_16x16x32_f16; GRBM_GUI_ACTIVE = GPU-active cycles of the dispatch)")
 for k in acc:
     a = {c: acc[k][c] / max(1, cnt[(k, c)]) for c in acc[k]}

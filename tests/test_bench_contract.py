@@ -1,9 +1,10 @@
-"""bench.py prints ONE JSON line with the contract's fields (incl. `roofline` and `cpu_baseline`); smoke() runs."""
+"""bench.py prints ONE JSON line with the contract's fields (with --full incl. `roofline` and `cpu_baseline`); smoke() runs."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--preheat", "0.2", "--model", "tiny",
-                        "--ftype", "q4_0", "--batch", "16", "--cpu-sample", "4"], cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        "--ftype", "q4_0", "--batch", "16", "--cpu-sample", "4", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines                          # exactly one line on stdout
@@ -41,6 +42,32 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert ws["executed_flops_per_step"] <= ws["algorithmic_flops_per_step"] and ws["frac"] <= ws["frac_survey_flops"]
     if ws["bound"] == "mfma":
         assert abs(ws["frac"] - ws["executed_flops_per_step"] / 2.5e15 / (d["ms_per_step"] * 1e-3)) < 2e-3
+
+
+def test_bench_plain_run_times_the_steps_only_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run (no --full) prints the contract line without the legs that take runs of their own; --dump-outputs writes the
+    embeddings of the last timed step, and two runs with the same arguments write the same arrays."""
+    dumps = []
+    for i in range(2):
+        d_out = tmp_path / ("run%d" % i)
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1", "--preheat", "0.2", "--model", "tiny",
+                            "--ftype", "q4_0", "--batch", "16", "--texts", "8", "--dump-outputs", str(d_out)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f16"
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["matrix"] is None and d["host_api_images_per_s"] is None
+        assert d["images_per_s_per_gpu"] is None and d["kernels"] is None
+        img, txt = np.load(d_out / "image_embeddings.npy"), np.load(d_out / "text_embeddings.npy")
+        assert sorted(os.listdir(d_out)) == ["image_embeddings.npy", "text_embeddings.npy"]
+        assert img.dtype == np.float32 and img.shape[0] == 16 and txt.dtype == np.float32 and txt.shape[0] == 8
+        assert np.all(np.isfinite(img)) and np.allclose(np.linalg.norm(img, axis=1), 1.0, atol=1e-3)
+        assert np.allclose(np.linalg.norm(txt, axis=1), 1.0, atol=1e-3)
+        dumps.append((img, txt))
+    for a, b in zip(dumps[0], dumps[1]):        # same seeded inputs: same embeddings (up to the order of a split-K fix-up)
+        np.testing.assert_allclose(a, b, rtol=0, atol=1e-6)
 
 
 def test_bench_collective_path_runs_with_one_rank():

@@ -55,6 +55,35 @@ def test_bench_stub_single_rank():
     assert d["n_gpus"] == 1 and d["self_launched"] is False
 
 
+def test_bench_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: the last timed step's embeddings as DIR/<name>.npy in float32; the same arguments give the same arrays."""
+    import numpy as np
+    got = []
+    for i, steps in enumerate((2, 5)):
+        d = one_line(run(["--gpus", "1", "--steps", str(steps), "--warmup", "1", "--preheat", "0", "--batch", "8", "--texts", "3",
+                          "--stub-encoder", "--dump-outputs", str(tmp_path / str(i))]))
+        assert d["steps"] == steps and d["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / str(i))) == ["image_embeddings.npy", "text_embeddings.npy"]
+        img, txt = np.load(tmp_path / str(i) / "image_embeddings.npy"), np.load(tmp_path / str(i) / "text_embeddings.npy")
+        assert img.dtype == np.float32 and img.shape == (8, 64) and txt.shape == (3, 64)
+        got.append((img, txt))
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
+
+
+def test_bench_dump_outputs_keeps_a_seeded_sample_above_the_cap(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 4096)
+    a = np.arange(64 * 32, dtype=np.float64).reshape(64, 32)       # 16 KB as float64, 8 KB as float32
+    b = np.ones((16, 32), dtype=np.float32)
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d), {"a": a, "b": b})
+    sa, sb = np.load(tmp_path / "x" / "a.npy"), np.load(tmp_path / "x" / "b.npy")
+    assert sa.dtype == np.float32 and sa.nbytes + sb.nbytes <= 4096 and sa.shape[1] == 32
+    assert np.all(np.diff(sa[:, 0]) > 0)                           # rows of the original, in order
+    assert np.array_equal(sa, np.load(tmp_path / "y" / "a.npy"))
+
+
 def test_algorithmic_work_is_the_survey_8d_figure():
     """`roofline.achieved` must use SURVEY 8(d)'s per-unit figures: FLOPs per image 8.818 G (ViT-B/32), 162.03 G (ViT-L/14), 334.59 G (ViT-H/14);
     FLOPs per text 2 L N (4 h^2 + 2 h ff) + 4 L N^2 h + 2 h proj (0.606 G at N = 8 for ViT-B/32); weight bytes per vision forward 53.2 MB
