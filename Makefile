@@ -11,7 +11,7 @@ SRC     := clip_cpp_amd/csrc
 OUT     := clip_cpp_amd/build
 CXXFLAGS := -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -Wno-unused-result -Wno-inline-asm -Wno-bitwise-instead-of-logical -Iinclude --offload-arch=$(ARCH) -DCLIPAMD_TEST_HOOKS=$(hooks)
 HOST    := gguf quant load forward tokenizer preprocess image_io image_formats jpeg_decode host_pipeline api
-KERNELS := k_attn k_attn_f32 k_misc k_preproc k_gemm k_gemm8 k_gemm4 k_gemm32 k_gemm_f32 k_skinny k_gemm_ring k_fold
+KERNELS := k_attn k_attn_long k_attn_f32 k_misc k_preproc k_gemm k_gemm8 k_gemm4 k_gemm32 k_gemm_f32 k_skinny k_gemm_ring k_fold
 WTS     := 0 1 2 3 4 5
 OBJS    := $(HOST:%=$(OUT)/%.cpp.o) $(KERNELS:%=$(OUT)/%.hip.o) $(WTS:%=$(OUT)/k_gemm_wt%.o) $(WTS:%=$(OUT)/k_skinny_wt%.o) $(WTS:%=$(OUT)/k_gemm_ring_wt%.o)
 
@@ -22,8 +22,8 @@ $(OUT):
 # (-fwrapv: the file decoders run integer transforms over untrusted coefficients; same flag as clip_cpp_amd/build.py)
 $(OUT)/%.cpp.o: $(SRC)/%.cpp $(wildcard $(SRC)/*.h) include/clip.h include/clip_amd.h | $(OUT)
 	$(HIPCC) -x hip -fwrapv $(CXXFLAGS) -c $< -o $@
-# (the f32-file kernels without the SLP vectoriser: same per-file flags as clip_cpp_amd/build.py EXTRA_FLAGS, which says why)
-$(OUT)/k_attn_f32.hip.o $(OUT)/k_gemm_f32.hip.o: CXXFLAGS += -fno-slp-vectorize
+# (the online-softmax attention kernels and the f32-file GEMM without the SLP vectoriser: same per-file flags as clip_cpp_amd/build.py EXTRA_FLAGS, which says why)
+$(OUT)/k_attn_f32.hip.o $(OUT)/k_attn_long.hip.o $(OUT)/k_gemm_f32.hip.o: CXXFLAGS += -fno-slp-vectorize
 $(OUT)/%.hip.o: $(SRC)/%.hip $(wildcard $(SRC)/*.h) | $(OUT)
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@
 $(OUT)/k_gemm_wt%.o: $(SRC)/k_gemm.hip $(wildcard $(SRC)/*.h) | $(OUT)

@@ -67,6 +67,7 @@ AMD_SYMBOLS = [
     "clip_amd_zero_shot_score_device", "clip_amd_zero_shot_label_images",
     "clip_amd_synchronize", "clip_amd_profile_enable", "clip_amd_profile_read", "clip_amd_profile_report",
     "clip_amd_test_gemm", "clip_amd_test_gemm_ex", "clip_amd_test_gemm_tile", "clip_amd_test_gemm_tile_ex", "clip_amd_test_skinny", "clip_amd_test_layernorm", "clip_amd_test_attention", "clip_amd_bench_gemm",
+    "clip_amd_test_attention_ex", "clip_amd_bench_attention",
 ]
 
 _lib = None
@@ -183,6 +184,10 @@ def lib():
     L.clip_amd_test_layernorm.argtypes = [f32p, f32p, f32p, C.c_float, C.c_int64, C.c_int64, f32p, i32]
     L.clip_amd_test_attention.restype = i32
     L.clip_amd_test_attention.argtypes = [f32p, i32, i32, i32, i32, i32, f32p]
+    L.clip_amd_test_attention_ex.restype = i32
+    L.clip_amd_test_attention_ex.argtypes = [f32p, i32, i32, i32, i32, i32, f32p, i32]
+    L.clip_amd_bench_attention.restype = C.c_float
+    L.clip_amd_bench_attention.argtypes = [i32, i32, i32, i32, i32, i32, i32]
     _lib = L
     return L
 

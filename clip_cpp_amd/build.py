@@ -23,12 +23,13 @@ ARCH = "gfx950"
 
 HOST_SOURCES = ["gguf.cpp", "quant.cpp", "load.cpp", "forward.cpp", "tokenizer.cpp", "preprocess.cpp", "image_io.cpp", "image_formats.cpp",
                 "jpeg_decode.cpp", "host_pipeline.cpp", "api.cpp"]
-HIP_SOURCES = ["k_attn.hip", "k_attn_f32.hip", "k_misc.hip", "k_preproc.hip", "k_gemm.hip", "k_gemm8.hip", "k_gemm4.hip", "k_gemm32.hip", "k_gemm_f32.hip", "k_skinny.hip", "k_gemm_ring.hip", "k_fold.hip"]
+HIP_SOURCES = ["k_attn.hip", "k_attn_long.hip", "k_attn_f32.hip", "k_misc.hip", "k_preproc.hip", "k_gemm.hip", "k_gemm8.hip", "k_gemm4.hip", "k_gemm32.hip", "k_gemm_f32.hip", "k_skinny.hip", "k_gemm_ring.hip", "k_fold.hip"]
 GEMM_WTYPES = [0, 1, 2, 3, 4, 5]
 # Per-file flags.  The f32-file kernels (a correctness path, not a tuned one) are built without the SLP vectoriser: packed f32 instructions that
 # consume a transcendental's result one wait state later are the suspect of the round-6 epilogue hazard (gemm_common.h GELU_SCALAR_FENCE,
 # profiles/r06_experiments.txt section 8), and hipcc forms exactly those around the online softmax of k_attn_f32.hip when it may.
-EXTRA_FLAGS = {"k_attn_f32.hip": ["-fno-slp-vectorize"], "k_gemm_f32.hip": ["-fno-slp-vectorize"]}
+# The streaming fp16 attention (k_attn_long.hip) has the same online softmax: same flag.
+EXTRA_FLAGS = {"k_attn_f32.hip": ["-fno-slp-vectorize"], "k_attn_long.hip": ["-fno-slp-vectorize"], "k_gemm_f32.hip": ["-fno-slp-vectorize"]}
 
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-Wno-inline-asm", "-Wno-bitwise-instead-of-logical",
           "-I" + os.path.join(os.path.dirname(HERE), "include")]

@@ -1047,18 +1047,65 @@ int clip_amd_test_layernorm(const float * x, const float * w, const float * b, f
     return 0;
 }
 
-int clip_amd_test_attention(const float * qkv, int nseq, int T, int h, int n_head, int causal, float * out) {
+// kernel: 0 = launch_attention (what the layers run), 1 = the whole-row kernel (k_attn.hip), 2 = the streaming kernel (k_attn_long.hip)
+static bool launch_attention_kernel(int kernel, const half_t * qkv, half_t * out, int nseq, int T, int h, int n_head, bool causal) {
+    switch (kernel) {
+    case 0: return launch_attention(qkv, out, nseq, T, nullptr, T, h, n_head, causal, nullptr);
+    case 1: return launch_attention_whole_row(qkv, out, nseq, T, nullptr, T, h, n_head, causal, nullptr);
+    case 2: return launch_attention_long(qkv, out, nseq, T, nullptr, T, h, n_head, causal, nullptr);
+    }
+    return false;
+}
+
+int clip_amd_test_attention_ex(const float * qkv, int nseq, int T, int h, int n_head, int causal, float * out, int kernel) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return -1; }
+    if (nseq <= 0 || T <= 0 || h <= 0 || n_head <= 0 || h % n_head) return -3;
     const size_t rows = (size_t)nseq * T;
     DBuf d32(rows * 3 * h * 4), d16(rows * 3 * h * 2), o16(rows * h * 2), o32(rows * h * 4);
     (void)hipMemcpy(d32.p, qkv, rows * 3 * h * 4, hipMemcpyHostToDevice);
     launch_f32_to_f16((const float *)d32.p, 3 * h, (half_t *)d16.p, 3 * h, (int)rows, 3 * h, 3 * h, nullptr);
-    if (!launch_attention((const half_t *)d16.p, (half_t *)o16.p, nseq, T, nullptr, T, h, n_head, causal != 0, nullptr)) return -2;
+    if (!launch_attention_kernel(kernel, (const half_t *)d16.p, (half_t *)o16.p, nseq, T, h, n_head, causal != 0)) return -2;
     launch_f16_to_f32((const half_t *)o16.p, h, (float *)o32.p, h, (int)rows, h, nullptr);
     if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return -4;
     (void)hipMemcpy(out, o32.p, rows * h * 4, hipMemcpyDeviceToHost);
     return 0;
+}
+
+int clip_amd_test_attention(const float * qkv, int nseq, int T, int h, int n_head, int causal, float * out) {
+    return clip_amd_test_attention_ex(qkv, nseq, T, h, n_head, causal, out, 0);
+}
+
+// Micro-benchmark of one attention shape (seeded random q / k / v, q at the scale of a pre-scaled projection): average kernel time in
+// microseconds over `iters` launches (HIP events, after one warm-up launch), < 0 on error (-2: the chosen kernel does not take the shape).
+float clip_amd_bench_attention(int nseq, int T, int h, int n_head, int causal, int kernel, int iters) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return -1.f; }
+    if (nseq <= 0 || T <= 0 || h <= 0 || n_head <= 0 || h % n_head || iters <= 0) return -3.f;
+    const size_t rows = (size_t)nseq * T;
+    std::vector<uint16_t> hx(rows * 3 * h);
+    uint32_t st = 12345u;
+    const float qs = 1.0f / sqrtf((float)(h / n_head));
+    for (size_t i = 0; i < hx.size(); i++) {
+        st = st * 1664525u + 1013904223u;
+        const float v = ((int)(st >> 9) % 2001 - 1000) * 1e-3f;
+        hx[i] = f32_to_f16_bits((int)(i % (3 * h)) < h ? v * qs : v);
+    }
+    DBuf d16(hx.size() * 2), o16(rows * h * 2);
+    (void)hipMemcpy(d16.p, hx.data(), hx.size() * 2, hipMemcpyHostToDevice);
+    if (!launch_attention_kernel(kernel, (const half_t *)d16.p, (half_t *)o16.p, nseq, T, h, n_head, causal != 0)) return -2.f;
+    if (hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); return -4.f; }
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    (void)hipEventRecord(e0, nullptr);
+    for (int i = 0; i < iters; i++) launch_attention_kernel(kernel, (const half_t *)d16.p, (half_t *)o16.p, nseq, T, h, n_head, causal != 0);
+    (void)hipEventRecord(e1, nullptr);
+    float ms = -1.f;
+    if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { (void)hipGetLastError(); ms = -1.f; }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return ms < 0 ? -4.f : ms * 1000.f / iters;
 }
 
 #endif  // CLIPAMD_TEST_HOOKS

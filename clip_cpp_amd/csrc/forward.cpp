@@ -1111,7 +1111,8 @@ bool text_forward_device(clip_ctx * ctx, const int32_t * d_ids, const int32_t * 
     };
     // Small token counts are launch-bound (~90 dependent launches): capture the chain on the second sighting of a signature and
     // replay it afterwards.  The kernels read the sequence offsets from device memory (uploaded above), so a graph only depends on
-    // (texts, token rows, attention key-tile bucket, pointers) — not on the individual lengths.
+    // (texts, token rows, attention key-tile bucket, pointers) — not on the individual lengths.  The bucket also fixes which attention
+    // kernel runs (the whole-row limits 592 / 288 are whole tiles) and the streaming kernel's grid (whole blocks of 64 / 128 queries).
     const int nt_bucket = (max_len + 15) / 16;
     if (ctx->graphs_enabled && !ctx->profiling && rows <= 1024 && !guard_mode()) {
         clip_ctx::TextGraphEntry * e = nullptr;

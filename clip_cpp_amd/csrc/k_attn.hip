@@ -19,8 +19,9 @@
 // Scores are never materialised in HBM (the reference materialises [T,T,n_head*B] f32).
 // Everything that indexes registers (key tiles NT, head-dim k-steps DKS, output d tiles DT) is a template
 // parameter and the MFMA chains are unconditional: padded keys are masked to -inf / multiplied by zero.
-// T <= 288 for every d_head in {32,64,80,88,96,104} (all 224-px models and every text length); T <= 592 for d_head <= 64
-// (ViT-L/14 at 336 px: T = 577, 154.6 KB of LDS); longer sequences are rejected by the launcher.
+// T <= 288 for every d_head in {32,64,80,88,96,104} (all 224-px models and every text length); T <= 592 for d_head 64
+// (ViT-L/14 at 336 px: T = 577, 154.6 KB of LDS).  launch_attention sends longer sequences to the streaming kernel of
+// k_attn_long.hip (K / V chunks through LDS, online softmax), which has no length bound.
 
 #include <cstdlib>
 
@@ -366,8 +367,12 @@ bool launch_nt(const AttnParams & p, int nseq, int nt, hipStream_t stream) {
 
 }  // namespace
 
-bool launch_attention(const half_t * qkv, half_t * out, int nseq, int T_uniform, const int * seq_start, int max_len,
-                      int h, int n_head, bool causal, hipStream_t stream) {
+int attention_whole_row_max_len(int d_head) {
+    return d_head == 64 ? 592 : 288;     // NT = 37 is instantiated for the 2-k-step head only (swizzled K rows of exactly 128 B)
+}
+
+bool launch_attention_whole_row(const half_t * qkv, half_t * out, int nseq, int T_uniform, const int * seq_start, int max_len,
+                                int h, int n_head, bool causal, hipStream_t stream) {
     if (nseq <= 0) return true;
     const int dh = h / n_head;
     if (max_len > 592 || max_len <= 0) return false;
@@ -392,6 +397,14 @@ bool launch_attention(const half_t * qkv, half_t * out, int nseq, int T_uniform,
     case 104: return launch_nt<4, 7, 104>(p, nseq, nt, stream);    // ViT-bigG/14 (hidden 1664, 16 heads)
     }
     return false;
+}
+
+bool launch_attention(const half_t * qkv, half_t * out, int nseq, int T_uniform, const int * seq_start, int max_len,
+                      int h, int n_head, bool causal, hipStream_t stream) {
+    // past what the whole-row kernel holds in LDS and registers: the streaming kernel (k_attn_long.hip); every shorter shape stays here
+    if (max_len > attention_whole_row_max_len(h / n_head))
+        return launch_attention_long(qkv, out, nseq, T_uniform, seq_start, max_len, h, n_head, causal, stream);
+    return launch_attention_whole_row(qkv, out, nseq, T_uniform, seq_start, max_len, h, n_head, causal, stream);
 }
 
 }  // namespace clipamd

@@ -224,8 +224,16 @@ void launch_layernorm_prep(const float * x, int ldx, const float * w, const floa
 // Multi-head self-attention softmax(QK^T)V (reference clip.cpp:1382-1388; causal for text :1101).
 // qkv: [rows][3h] fp16 with Q pre-scaled; sequences given by seq_start[nseq+1] (device) or, when
 // seq_start == nullptr, uniform length T.  out: [rows][h] fp16.
+// Sequences up to attention_whole_row_max_len(d_head) (592 for d_head 64, 288 otherwise) run the whole-row kernel of k_attn.hip,
+// longer ones the streaming kernel of k_attn_long.hip; the two are also callable on their own (test / measurement hooks), and
+// launch_attention_whole_row returns false past its limit.
 bool launch_attention(const half_t * qkv, half_t * out, int nseq, int T_uniform, const int * seq_start, int max_len,
                       int h, int n_head, bool causal, hipStream_t stream);
+int attention_whole_row_max_len(int d_head);
+bool launch_attention_whole_row(const half_t * qkv, half_t * out, int nseq, int T_uniform, const int * seq_start, int max_len,
+                                int h, int n_head, bool causal, hipStream_t stream);
+bool launch_attention_long(const half_t * qkv, half_t * out, int nseq, int T_uniform, const int * seq_start, int max_len,
+                           int h, int n_head, bool causal, hipStream_t stream);
 
 // The same attention in f32 for f32 GGUF files (k_attn_f32.hip; the reference's KQ, soft_max and KQV are f32 for every file type): qkv float [rows][3h]
 // with Q pre-scaled, out float [rows][h]; any sequence length, d_head <= 128 and a multiple of 4.

@@ -183,6 +183,12 @@ int clip_amd_test_layernorm(const float * x, const float * w, const float * b, f
                             float * y, int out_f16);
 /* Multi-head attention over nseq sequences of length T each: qkv [nseq*T][3h] (q pre-scaled), out [nseq*T][h]. */
 int clip_amd_test_attention(const float * qkv, int nseq, int T, int h, int n_head, int causal, float * out);
+/* ... with the kernel chosen: 0 = automatic (what the layers run), 1 = the whole-row kernel (d_head 64: T <= 592, other head sizes:
+ * T <= 288), 2 = the streaming kernel (any T).  Returns -2 when the chosen kernel does not take the shape. */
+int clip_amd_test_attention_ex(const float * qkv, int nseq, int T, int h, int n_head, int causal, float * out, int kernel);
+/* Average device time (microseconds, HIP events) of one attention launch on seeded random q / k / v, kernel as
+ * clip_amd_test_attention_ex; < 0 on error (-2: the kernel does not take the shape).  Used by scripts/attn_bench.py. */
+float clip_amd_bench_attention(int nseq, int T, int h, int n_head, int causal, int kernel, int iters);
 
 #ifdef __cplusplus
 }
