@@ -10,6 +10,7 @@ GPU is missing the encoders raise.
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -68,6 +69,9 @@ AMD_SYMBOLS = [
     "clip_amd_synchronize", "clip_amd_profile_enable", "clip_amd_profile_read", "clip_amd_profile_report",
     "clip_amd_test_gemm", "clip_amd_test_gemm_ex", "clip_amd_test_gemm_tile", "clip_amd_test_gemm_tile_ex", "clip_amd_test_skinny", "clip_amd_test_layernorm", "clip_amd_test_attention", "clip_amd_bench_gemm",
     "clip_amd_test_attention_ex", "clip_amd_bench_attention",
+    "clip_amd_index_create", "clip_amd_index_add", "clip_amd_index_add_device", "clip_amd_index_size", "clip_amd_index_dim",
+    "clip_amd_index_search", "clip_amd_index_search_device", "clip_amd_index_save", "clip_amd_index_load", "clip_amd_index_free",
+    "clip_amd_bench_search",
 ]
 
 _lib = None
@@ -188,6 +192,29 @@ def lib():
     L.clip_amd_test_attention_ex.argtypes = [f32p, i32, i32, i32, i32, i32, f32p, i32]
     L.clip_amd_bench_attention.restype = C.c_float
     L.clip_amd_bench_attention.argtypes = [i32, i32, i32, i32, i32, i32, i32]
+    i64, i64p = C.c_int64, C.POINTER(C.c_int64)
+    L.clip_amd_index_create.restype = vp
+    L.clip_amd_index_create.argtypes = [vp, i32, i32]
+    L.clip_amd_index_add.restype = C.c_bool
+    L.clip_amd_index_add.argtypes = [vp, f32p, i64]
+    L.clip_amd_index_add_device.restype = C.c_bool
+    L.clip_amd_index_add_device.argtypes = [vp, vp, i64]
+    L.clip_amd_index_size.restype = i64
+    L.clip_amd_index_size.argtypes = [vp]
+    L.clip_amd_index_dim.restype = i32
+    L.clip_amd_index_dim.argtypes = [vp]
+    L.clip_amd_index_search.restype = C.c_bool
+    L.clip_amd_index_search.argtypes = [vp, f32p, i32, i32, f32p, i64p]
+    L.clip_amd_index_search_device.restype = C.c_bool
+    L.clip_amd_index_search_device.argtypes = [vp, vp, i32, i32, vp, vp]
+    L.clip_amd_index_save.restype = C.c_bool
+    L.clip_amd_index_save.argtypes = [vp, C.c_char_p]
+    L.clip_amd_index_load.restype = vp
+    L.clip_amd_index_load.argtypes = [vp, C.c_char_p]
+    L.clip_amd_index_free.restype = None
+    L.clip_amd_index_free.argtypes = [vp]
+    L.clip_amd_bench_search.restype = C.c_float
+    L.clip_amd_bench_search.argtypes = [i32, i64, i32, i32, i32, i32]
     _lib = L
     return L
 
@@ -465,6 +492,8 @@ class Clip:
 
     def close(self):
         if getattr(self, "ctx", None):
+            for ix in list(getattr(self, "_indexes", ())):     # an index lives on this context: free it first
+                ix.close()
             lib().clip_free(self.ctx)
             self.ctx = None
 
@@ -473,6 +502,92 @@ class Clip:
             self.close()
         except Exception:
             pass
+
+
+class Index:
+    """Exact cosine nearest-neighbour index on the GPU of a `Clip` (clip_amd_index_*, include/clip_amd.h): rows are L2-normalised and
+    stored in f16 (default) or f32; search returns (distances f32 [nq, k], ids int64 [nq, k]) sorted by ascending 1 - cosine, equal
+    distances lower id first, -1 / +inf past the index size.  Keep the `Clip` alive while the index is in use."""
+
+    DTYPES = {"f32": 0, "f16": 1}
+
+    def __init__(self, clip, dim, dtype="f16", _handle=None):
+        self.clip = clip
+        if _handle is None:
+            if dtype not in self.DTYPES:
+                raise ValueError("dtype must be 'f16' or 'f32', not %r" % (dtype,))
+            _handle = lib().clip_amd_index_create(clip.ctx, int(dim), self.DTYPES[dtype])
+            if not _handle:
+                raise RuntimeError("clip_amd_index_create failed (see stderr)")
+        self.handle = _handle
+        self.dim = lib().clip_amd_index_dim(self.handle)
+        if not hasattr(clip, "_indexes"):
+            clip._indexes = weakref.WeakSet()
+        clip._indexes.add(self)
+
+    @classmethod
+    def load(cls, clip, path):
+        h = lib().clip_amd_index_load(clip.ctx, os.fsencode(path))
+        if not h:
+            raise RuntimeError("clip_amd_index_load failed for %r (see stderr)" % (path,))
+        return cls(clip, 0, _handle=h)
+
+    def __len__(self):
+        return int(lib().clip_amd_index_size(self.handle))
+
+    def len(self):
+        return len(self)
+
+    def add(self, vecs):
+        """float32 [n, dim] rows (host); they get the next n ids."""
+        v = np.ascontiguousarray(vecs, dtype=np.float32).reshape(-1, self.dim)
+        if not lib().clip_amd_index_add(self._live(), _fp(v), v.shape[0]):
+            raise RuntimeError("clip_amd_index_add failed (see stderr)")
+
+    def add_device(self, ptr, n):
+        """n float32 rows of dim values at device address ptr (asynchronous on the context's stream)."""
+        if not lib().clip_amd_index_add_device(self._live(), C.c_void_p(ptr), int(n)):
+            raise RuntimeError("clip_amd_index_add_device failed (see stderr)")
+
+    def search(self, queries, k):
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        nq = q.shape[0]
+        dist = np.empty((nq, k), dtype=np.float32)
+        ids = np.empty((nq, k), dtype=np.int64)
+        if not lib().clip_amd_index_search(self._live(), _fp(q), nq, int(k), _fp(dist), ids.ctypes.data_as(C.POINTER(C.c_int64))):
+            raise RuntimeError("clip_amd_index_search failed (see stderr)")
+        return dist, ids
+
+    def search_device(self, d_queries, n_queries, k, d_distances, d_ids):
+        """Device pointers (ints): queries [n, dim] f32 -> distances [n, k] f32, ids [n, k] int64; asynchronous on the context's stream."""
+        if not lib().clip_amd_index_search_device(self._live(), C.c_void_p(d_queries), int(n_queries), int(k), C.c_void_p(d_distances),
+                                                  C.c_void_p(d_ids)):
+            raise RuntimeError("clip_amd_index_search_device failed (see stderr)")
+
+    def save(self, path):
+        if not lib().clip_amd_index_save(self._live(), os.fsencode(path)):
+            raise RuntimeError("clip_amd_index_save failed for %r (see stderr)" % (path,))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib().clip_amd_index_free(self.handle)
+            self.handle = None
+
+    def _live(self):
+        if not getattr(self, "handle", None):
+            raise RuntimeError("the index is closed")
+        return self.handle
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bench_search(dtype, n, dim, n_queries, k, iters=10):
+    """Microseconds per clip_amd_index_search_device on seeded random data (clip_amd_bench_search); < 0 on error."""
+    return float(lib().clip_amd_bench_search(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(k), int(iters)))
 
 
 def gguf_inspect(path):

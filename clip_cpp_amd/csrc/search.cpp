@@ -1,0 +1,376 @@
+// search.cpp — the exact nearest-neighbour index of include/clip_amd.h (clip_amd_index_*): device-resident rows, argument checking,
+// query chunking, the scan -> merge tree -> finish launch sequence of k_search.hip, and the CLIPIDX1 file format.
+// Replaces the usearch index of the reference's examples/image-search (build.cpp / search.cpp) with an exact search on the GPU.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <exception>
+#include <vector>
+
+#include "../../include/clip_amd.h"
+#include "kernels.h"
+#include "model.h"
+
+using namespace clipamd;
+
+struct clip_amd_index {
+    clip_ctx * ctx = nullptr;      // NULL: benchmark index on the default stream
+    int device = 0;
+    int dim = 0, Dpad = 0, dtype = 1;
+    size_t es = 2;                 // bytes per stored value
+    int64_t n = 0, cap = 0;        // rows stored / allocated
+    void * rows = nullptr;         // [cap][Dpad]
+    // device workspaces, grown on demand
+    void * stage = nullptr; size_t stage_bytes = 0;     // f32 rows / queries copied from the host
+    void * qbuf = nullptr;  size_t qbuf_bytes = 0;      // normalised queries [nq_pad][Dpad]
+    void * cand = nullptr;  size_t cand_bytes = 0;      // [n_chunks][nq][C] candidates
+    void * mbuf[2] = {nullptr, nullptr}; size_t mbuf_bytes = 0;   // merge levels
+    void * outs = nullptr;  size_t outs_bytes = 0;      // distances + ids of the host search form
+};
+
+namespace {
+
+constexpr char MAGIC[8] = {'C', 'L', 'I', 'P', 'I', 'D', 'X', '1'};
+constexpr uint32_t VERSION = 1;
+constexpr int MAX_K = 1024;
+constexpr int64_t MAX_ROWS = 2147483647;
+constexpr size_t CAND_BUDGET = (size_t)512 << 20;       // bytes of candidate workspace per scan launch
+constexpr int64_t HOST_CHUNK_ROWS = 65536;              // rows per staging copy (add, save, load)
+
+hipStream_t stream_of(const clip_amd_index * ix) { return ix->ctx ? ix->ctx->stream : nullptr; }
+
+bool ensure(const clip_amd_index * ix, void *& p, size_t & have, size_t need) {
+    if (need <= have && p) return true;
+    if (p) {
+        (void)hipStreamSynchronize(stream_of(ix));
+        (void)hipFree(p);
+        p = nullptr;
+        have = 0;
+    }
+    if (hipMalloc(&p, need ? need : 16) != hipSuccess) {
+        (void)hipGetLastError();
+        p = nullptr;
+        fprintf(stderr, "clip_amd_index: device allocation of %zu bytes failed\n", need);
+        return false;
+    }
+    have = need;
+    return true;
+}
+
+bool reserve_rows(clip_amd_index * ix, int64_t need) {
+    if (need <= ix->cap) return true;
+    int64_t cap = std::max<int64_t>({need, ix->cap * 2, 1024});
+    cap = std::min<int64_t>(cap, std::max<int64_t>(need, MAX_ROWS));
+    void * p = nullptr;
+    if (hipMalloc(&p, (size_t)cap * ix->Dpad * ix->es) != hipSuccess) {
+        (void)hipGetLastError();
+        fprintf(stderr, "clip_amd_index: cannot allocate %lld rows of %d values\n", (long long)cap, ix->Dpad);
+        return false;
+    }
+    hipStream_t st = stream_of(ix);
+    if (ix->rows) {
+        (void)hipMemcpyAsync(p, ix->rows, (size_t)ix->n * ix->Dpad * ix->es, hipMemcpyDeviceToDevice, st);
+        (void)hipStreamSynchronize(st);
+        (void)hipFree(ix->rows);
+    }
+    ix->rows = p;
+    ix->cap = cap;
+    return true;
+}
+
+bool valid_dim(int dim) { return dim >= 4 && dim <= 4096 && dim % 4 == 0; }
+
+clip_amd_index * make_index(clip_ctx * ctx, int device, int dim, int dtype) {
+    clip_amd_index * ix = new clip_amd_index;
+    ix->ctx = ctx;
+    ix->device = device;
+    ix->dim = dim;
+    ix->Dpad = (dim + 31) / 32 * 32;
+    ix->dtype = dtype;
+    ix->es = dtype == 1 ? 2 : 4;
+    return ix;
+}
+
+void free_index(clip_amd_index * ix) {
+    (void)hipSetDevice(ix->device);
+    (void)hipStreamSynchronize(stream_of(ix));
+    for (void * p : {ix->rows, ix->stage, ix->qbuf, ix->cand, ix->mbuf[0], ix->mbuf[1], ix->outs})
+        if (p) (void)hipFree(p);
+    delete ix;
+}
+
+// rows of a search: every chunk at least 256 rows and 4 k (its k best are a small part of it), at most ~1024 chunks
+int64_t rows_per_chunk(int64_t n, int k) {
+    int64_t r = std::max<int64_t>({256, 4 * (int64_t)k, (n + 1023) / 1024});
+    return (r + 63) / 64 * 64;
+}
+
+bool search_device_impl(clip_amd_index * ix, const float * d_q, int nq, int k, float * d_dist, int64_t * d_ids) {
+    hipStream_t st = stream_of(ix);
+    if (nq == 0) return true;
+    if (ix->n == 0) {
+        launch_search_finish(nullptr, 0, nq, k, d_dist, d_ids, st);
+        return hipGetLastError() == hipSuccess;
+    }
+    const bool f16 = ix->dtype == 1;
+    const int64_t rpc = rows_per_chunk(ix->n, k);
+    const int n_chunks = (int)((ix->n + rpc - 1) / rpc);
+    const int C = search_candidate_capacity(k);
+    int max_q = (int)std::min<size_t>(1024, CAND_BUDGET / ((size_t)n_chunks * C * sizeof(float) * 2));
+    max_q = std::max(16, max_q / 16 * 16);
+    for (int q0 = 0; q0 < nq; q0 += max_q) {
+        const int m = std::min(max_q, nq - q0);
+        const int qt = m >= 64 ? 4 : (m > 16 ? 2 : 1);
+        const int64_t m_pad = (m + 16 * qt - 1) / (16 * qt) * (16 * qt);
+        if (!ensure(ix, ix->qbuf, ix->qbuf_bytes, (size_t)m_pad * ix->Dpad * ix->es)) return false;
+        if (!ensure(ix, ix->cand, ix->cand_bytes, (size_t)n_chunks * m * C * 8)) return false;
+        const size_t mb = (size_t)((n_chunks + 1) / 2) * m * k * 8;
+        if (n_chunks > 1 && mb > ix->mbuf_bytes) {
+            size_t have0 = ix->mbuf_bytes, have1 = ix->mbuf_bytes;
+            if (!ensure(ix, ix->mbuf[0], have0, mb) || !ensure(ix, ix->mbuf[1], have1, mb)) return false;
+            ix->mbuf_bytes = mb;
+        }
+        launch_search_normalize(d_q + (size_t)q0 * ix->dim, m, m_pad, ix->dim, ix->Dpad, ix->qbuf, f16, st);
+        if (!launch_search_scan(ix->rows, ix->n, ix->Dpad, f16, ix->qbuf, m, qt, k, ix->cand, n_chunks, rpc, st)) {
+            fprintf(stderr, "clip_amd_index_search: scan launch failed\n");
+            return false;
+        }
+        const void * in = ix->cand;
+        int64_t stride = C;
+        int lists = n_chunks, t = 0;
+        while (lists > 1) {
+            launch_search_merge(in, stride, lists, ix->mbuf[t], m, k, st);
+            in = ix->mbuf[t];
+            t ^= 1;
+            stride = k;
+            lists = (lists + 1) / 2;
+        }
+        launch_search_finish(in, stride, m, k, d_dist + (size_t)q0 * k, d_ids + (size_t)q0 * k, st);
+        if (hipGetLastError() != hipSuccess) {
+            fprintf(stderr, "clip_amd_index_search: launch failed\n");
+            return false;
+        }
+    }
+    return true;
+}
+
+bool check_search_args(const clip_amd_index * ix, const void * q, int nq, int k, const void * dist, const void * ids, const char * fn) {
+    if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+    if (nq < 0) { fprintf(stderr, "%s: n_queries %d < 0\n", fn, nq); return false; }
+    if (k < 1 || k > MAX_K) { fprintf(stderr, "%s: k = %d outside 1 ... %d\n", fn, k, MAX_K); return false; }
+    if (nq > 0 && (!q || !dist || !ids)) { fprintf(stderr, "%s: NULL queries or result pointer\n", fn); return false; }
+    return true;
+}
+
+bool add_device_impl(clip_amd_index * ix, const float * d_vecs, int64_t n) {
+    if (!reserve_rows(ix, ix->n + n)) return false;
+    launch_search_normalize(d_vecs, n, n, ix->dim, ix->Dpad, (char *)ix->rows + (size_t)ix->n * ix->Dpad * ix->es, ix->dtype == 1, stream_of(ix));
+    if (hipGetLastError() != hipSuccess) { fprintf(stderr, "clip_amd_index_add: launch failed\n"); return false; }
+    ix->n += n;
+    return true;
+}
+
+bool check_add_args(const clip_amd_index * ix, const float * v, int64_t n, const char * fn) {
+    if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+    if (n < 0 || n > MAX_ROWS - ix->n) { fprintf(stderr, "%s: %lld rows would take the index past %lld rows\n", fn, (long long)n, (long long)MAX_ROWS); return false; }
+    if (n > 0 && !v) { fprintf(stderr, "%s: NULL rows\n", fn); return false; }
+    return true;
+}
+
+struct File {
+    FILE * f;
+    explicit File(const char * p, const char * mode) : f(fopen(p, mode)) {}
+    ~File() { if (f) fclose(f); }
+};
+
+}  // namespace
+
+extern "C" {
+
+struct clip_amd_index * clip_amd_index_create(struct clip_ctx * ctx, int dim, int dtype) try {
+    if (!ctx) { fprintf(stderr, "clip_amd_index_create: ctx is NULL\n"); return nullptr; }
+    if (ctx->device < 0) { fprintf(stderr, "clip_amd_index_create: host-only context: the index lives on a HIP device\n"); return nullptr; }
+    if (!valid_dim(dim)) { fprintf(stderr, "clip_amd_index_create: dim %d not in 4 ... 4096 or not a multiple of 4\n", dim); return nullptr; }
+    if (dtype != 0 && dtype != 1) { fprintf(stderr, "clip_amd_index_create: dtype %d is neither 0 (f32) nor 1 (f16)\n", dtype); return nullptr; }
+    (void)hipSetDevice(ctx->device);
+    return make_index(ctx, ctx->device, dim, dtype);
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_index_create: %s\n", e.what()); return nullptr; }
+
+bool clip_amd_index_add_device(struct clip_amd_index * ix, const float * d_vecs, int64_t n) try {
+    if (!check_add_args(ix, d_vecs, n, "clip_amd_index_add_device")) return false;
+    if (n == 0) return true;
+    (void)hipSetDevice(ix->device);
+    return add_device_impl(ix, d_vecs, n);
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_index_add_device: %s\n", e.what()); return false; }
+
+bool clip_amd_index_add(struct clip_amd_index * ix, const float * vecs, int64_t n) try {
+    if (!check_add_args(ix, vecs, n, "clip_amd_index_add")) return false;
+    if (n == 0) return true;
+    (void)hipSetDevice(ix->device);
+    hipStream_t st = stream_of(ix);
+    for (int64_t r0 = 0; r0 < n; r0 += HOST_CHUNK_ROWS) {
+        const int64_t m = std::min(HOST_CHUNK_ROWS, n - r0);
+        if (!ensure(ix, ix->stage, ix->stage_bytes, (size_t)std::min(HOST_CHUNK_ROWS, n) * ix->dim * 4)) return false;
+        (void)hipMemcpyAsync(ix->stage, vecs + (size_t)r0 * ix->dim, (size_t)m * ix->dim * 4, hipMemcpyHostToDevice, st);
+        if (!add_device_impl(ix, (const float *)ix->stage, m)) return false;
+        (void)hipStreamSynchronize(st);      // the staging buffer is reused by the next piece
+    }
+    return hipStreamSynchronize(st) == hipSuccess;
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_index_add: %s\n", e.what()); return false; }
+
+int64_t clip_amd_index_size(const struct clip_amd_index * ix) { return ix ? ix->n : 0; }
+int clip_amd_index_dim(const struct clip_amd_index * ix) { return ix ? ix->dim : 0; }
+
+bool clip_amd_index_search_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int k, float * d_distances,
+                                  int64_t * d_ids) try {
+    if (!check_search_args(ix, d_queries, n_queries, k, d_distances, d_ids, "clip_amd_index_search_device")) return false;
+    (void)hipSetDevice(ix->device);
+    return search_device_impl(ix, d_queries, n_queries, k, d_distances, d_ids);
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_index_search_device: %s\n", e.what()); return false; }
+
+bool clip_amd_index_search(struct clip_amd_index * ix, const float * queries, int n_queries, int k, float * distances, int64_t * ids) try {
+    if (!check_search_args(ix, queries, n_queries, k, distances, ids, "clip_amd_index_search")) return false;
+    if (n_queries == 0) return true;
+    (void)hipSetDevice(ix->device);
+    hipStream_t st = stream_of(ix);
+    const size_t qb = (size_t)n_queries * ix->dim * 4, db = (size_t)n_queries * k * 4, ib = (size_t)n_queries * k * 8;
+    if (!ensure(ix, ix->stage, ix->stage_bytes, std::max(qb, ix->stage_bytes))) return false;
+    if (!ensure(ix, ix->outs, ix->outs_bytes, std::max(ib + db, ix->outs_bytes))) return false;
+    int64_t * d_ids = (int64_t *)ix->outs;
+    float * d_dist = (float *)((char *)ix->outs + ib);
+    (void)hipMemcpyAsync(ix->stage, queries, qb, hipMemcpyHostToDevice, st);
+    if (!search_device_impl(ix, (const float *)ix->stage, n_queries, k, d_dist, d_ids)) return false;
+    (void)hipMemcpyAsync(distances, d_dist, db, hipMemcpyDeviceToHost, st);
+    (void)hipMemcpyAsync(ids, d_ids, ib, hipMemcpyDeviceToHost, st);
+    if (hipStreamSynchronize(st) != hipSuccess) {
+        fprintf(stderr, "clip_amd_index_search: %s\n", hipGetErrorString(hipGetLastError()));
+        return false;
+    }
+    return true;
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_index_search: %s\n", e.what()); return false; }
+
+bool clip_amd_index_save(struct clip_amd_index * ix, const char * path) try {
+    if (!ix || !path) { fprintf(stderr, "clip_amd_index_save: NULL index or path\n"); return false; }
+    (void)hipSetDevice(ix->device);
+    hipStream_t st = stream_of(ix);
+    File out(path, "wb");
+    if (!out.f) { fprintf(stderr, "clip_amd_index_save: cannot open '%s' for writing\n", path); return false; }
+    const uint32_t hdr[3] = {VERSION, (uint32_t)ix->dim, (uint32_t)ix->dtype};
+    const uint64_t n = (uint64_t)ix->n;
+    bool ok = fwrite(MAGIC, 1, 8, out.f) == 8 && fwrite(hdr, 4, 3, out.f) == 3 && fwrite(&n, 8, 1, out.f) == 1;
+    const size_t row_bytes = (size_t)ix->dim * ix->es;
+    std::vector<unsigned char> buf((size_t)std::min<int64_t>(HOST_CHUNK_ROWS, std::max<int64_t>(ix->n, 1)) * row_bytes);
+    for (int64_t r0 = 0; ok && r0 < ix->n; r0 += HOST_CHUNK_ROWS) {
+        const int64_t m = std::min(HOST_CHUNK_ROWS, ix->n - r0);
+        ok = hipMemcpy2DAsync(buf.data(), row_bytes, (const char *)ix->rows + (size_t)r0 * ix->Dpad * ix->es, (size_t)ix->Dpad * ix->es, row_bytes,
+                              (size_t)m, hipMemcpyDeviceToHost, st) == hipSuccess &&
+             hipStreamSynchronize(st) == hipSuccess && fwrite(buf.data(), row_bytes, (size_t)m, out.f) == (size_t)m;
+    }
+    if (!ok) fprintf(stderr, "clip_amd_index_save: writing '%s' failed\n", path);
+    return ok;
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_index_save: %s\n", e.what()); return false; }
+
+struct clip_amd_index * clip_amd_index_load(struct clip_ctx * ctx, const char * path) try {
+    if (!ctx || !path) { fprintf(stderr, "clip_amd_index_load: NULL ctx or path\n"); return nullptr; }
+    if (ctx->device < 0) { fprintf(stderr, "clip_amd_index_load: host-only context: the index lives on a HIP device\n"); return nullptr; }
+    File in(path, "rb");
+    if (!in.f) { fprintf(stderr, "clip_amd_index_load: cannot open '%s'\n", path); return nullptr; }
+    char magic[8];
+    uint32_t hdr[3];
+    uint64_t n = 0;
+    if (fread(magic, 1, 8, in.f) != 8 || fread(hdr, 4, 3, in.f) != 3 || fread(&n, 8, 1, in.f) != 1) {
+        fprintf(stderr, "clip_amd_index_load: '%s' is shorter than the header\n", path);
+        return nullptr;
+    }
+    if (memcmp(magic, MAGIC, 8) != 0) { fprintf(stderr, "clip_amd_index_load: '%s' is not an index file (bad magic)\n", path); return nullptr; }
+    if (hdr[0] != VERSION) { fprintf(stderr, "clip_amd_index_load: '%s' has version %u, expected %u\n", path, hdr[0], VERSION); return nullptr; }
+    const uint32_t dim = hdr[1], dtype = hdr[2];
+    if (dim > 4096 || !valid_dim((int)dim)) { fprintf(stderr, "clip_amd_index_load: '%s': dim %u not in 4 ... 4096 or not a multiple of 4\n", path, dim); return nullptr; }
+    if (dtype > 1) { fprintf(stderr, "clip_amd_index_load: '%s': unknown dtype %u\n", path, dtype); return nullptr; }
+    const uint64_t es = dtype == 1 ? 2 : 4;
+    if (n > (uint64_t)MAX_ROWS || n > UINT64_MAX / (dim * es)) {
+        fprintf(stderr, "clip_amd_index_load: '%s': %llu rows of %u values overflow the index\n", path, (unsigned long long)n, dim);
+        return nullptr;
+    }
+    const uint64_t payload = n * dim * es;
+    if (fseek(in.f, 0, SEEK_END) != 0) { fprintf(stderr, "clip_amd_index_load: cannot seek in '%s'\n", path); return nullptr; }
+    const long long fsize = ftell(in.f);
+    if (fsize < 0 || (uint64_t)fsize != 28 + payload) {
+        fprintf(stderr, "clip_amd_index_load: '%s' holds %lld bytes, its header says %llu\n", path, fsize, (unsigned long long)(28 + payload));
+        return nullptr;
+    }
+    fseek(in.f, 28, SEEK_SET);
+    (void)hipSetDevice(ctx->device);
+    clip_amd_index * ix = make_index(ctx, ctx->device, (int)dim, (int)dtype);
+    hipStream_t st = stream_of(ix);
+    bool ok = reserve_rows(ix, (int64_t)n);
+    if (ok && n) ok = hipMemsetAsync(ix->rows, 0, (size_t)n * ix->Dpad * es, st) == hipSuccess;
+    const size_t row_bytes = (size_t)dim * es;
+    std::vector<unsigned char> buf((size_t)std::min<uint64_t>(HOST_CHUNK_ROWS, std::max<uint64_t>(n, 1)) * row_bytes);
+    for (int64_t r0 = 0; ok && r0 < (int64_t)n; r0 += HOST_CHUNK_ROWS) {
+        const int64_t m = std::min<int64_t>(HOST_CHUNK_ROWS, (int64_t)n - r0);
+        ok = fread(buf.data(), row_bytes, (size_t)m, in.f) == (size_t)m &&
+             hipMemcpy2DAsync((char *)ix->rows + (size_t)r0 * ix->Dpad * es, (size_t)ix->Dpad * es, buf.data(), row_bytes, row_bytes, (size_t)m,
+                              hipMemcpyHostToDevice, st) == hipSuccess &&
+             hipStreamSynchronize(st) == hipSuccess;
+    }
+    if (!ok) {
+        fprintf(stderr, "clip_amd_index_load: reading '%s' failed\n", path);
+        free_index(ix);
+        return nullptr;
+    }
+    ix->n = (int64_t)n;
+    return ix;
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_index_load: %s\n", e.what()); return nullptr; }
+
+void clip_amd_index_free(struct clip_amd_index * ix) {
+    if (ix) free_index(ix);
+}
+
+float clip_amd_bench_search(int dtype, int64_t n, int dim, int n_queries, int k, int iters) try {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return -1.f; }
+    if ((dtype != 0 && dtype != 1) || !valid_dim(dim) || n < 1 || n > MAX_ROWS || n_queries < 1 || k < 1 || k > MAX_K || iters < 1) return -3.f;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    clip_amd_index * ix = make_index(nullptr, dev, dim, dtype);
+    float * src = nullptr;
+    float * d_dist = nullptr;
+    int64_t * d_ids = nullptr;
+    const int64_t piece = HOST_CHUNK_ROWS;
+    float us = -4.f;
+    if (hipMalloc(&src, (size_t)std::max<int64_t>(piece, n_queries) * dim * 4) == hipSuccess &&
+        hipMalloc(&d_dist, (size_t)n_queries * k * 4) == hipSuccess && hipMalloc(&d_ids, (size_t)n_queries * k * 8) == hipSuccess &&
+        reserve_rows(ix, n)) {
+        bool ok = true;
+        for (int64_t r0 = 0; ok && r0 < n; r0 += piece) {
+            const int64_t m = std::min(piece, n - r0);
+            launch_search_fill_random(src, m * dim, 0x5EEDull + (uint64_t)r0 * dim, nullptr);
+            ok = add_device_impl(ix, src, m);
+        }
+        launch_search_fill_random(src, (int64_t)n_queries * dim, 0xC0FFEEull, nullptr);
+        ok = ok && search_device_impl(ix, src, n_queries, k, d_dist, d_ids) && hipDeviceSynchronize() == hipSuccess;
+        if (ok) {
+            hipEvent_t e0, e1;
+            (void)hipEventCreate(&e0);
+            (void)hipEventCreate(&e1);
+            (void)hipEventRecord(e0, nullptr);
+            for (int i = 0; ok && i < iters; i++) ok = search_device_impl(ix, src, n_queries, k, d_dist, d_ids);
+            (void)hipEventRecord(e1, nullptr);
+            float ms = -1.f;
+            if (ok && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) us = ms * 1000.f / iters;
+            (void)hipEventDestroy(e0);
+            (void)hipEventDestroy(e1);
+        }
+    }
+    (void)hipGetLastError();
+    (void)hipDeviceSynchronize();
+    if (src) (void)hipFree(src);
+    if (d_dist) (void)hipFree(d_dist);
+    if (d_ids) (void)hipFree(d_ids);
+    free_index(ix);
+    return us;
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_bench_search: %s\n", e.what()); return -4.f; }
+
+}  // extern "C"

@@ -1,0 +1,281 @@
+"""Semantic image search over a directory tree: the reference's examples/image-search (`image-search-build` / `image-search`,
+build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.Index`) instead of usearch's approximate one.
+
+    python -m clip_cpp_amd.image_search build  [-m MODEL] [-v N] [-t N] [--db DIR] [--dtype f16|f32] dir [more dirs]
+    python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N] [--db DIR] <search text or /path/to/query/image>
+
+`build` writes DIR/images.index (the CLIPIDX1 file of clip_amd_index_save) and DIR/images.paths (the reference's layout: the model path
+on the first line, then one image path per id).  `search` prints the reference's output: "search results:" / "distance path" at
+verbosity > 0, then "  %f %s" per hit, nearest first.
+"""
+import ctypes as C
+import os
+import struct
+import sys
+
+import numpy as np
+
+IMAGE_EXTENSIONS = (".jpg", ".JPG", ".jpeg", ".JPEG", ".gif", ".GIF", ".png", ".PNG")
+INDEX_FILE = "images.index"
+PATHS_FILE = "images.paths"
+BATCH = 64          # images decoded and encoded per call
+MAX_K = 1024
+
+
+def is_image_file_extension(path):
+    """The reference's is_image_file_extension (examples/common-clip.cpp): the text after the last '.' is one of eight spellings."""
+    pos = path.rfind(".")
+    return pos >= 0 and path[pos:] in IMAGE_EXTENSIONS
+
+
+def classify_query(args):
+    """(image_path, search_text) from the positional arguments the way the reference's parser reads them: a last argument with an image
+    extension is an image query; otherwise the arguments from the first one on are joined with spaces into the search text."""
+    if not args:
+        return "", ""
+    if len(args) == 1 and is_image_file_extension(args[0]):
+        return args[0], ""
+    return "", " ".join(args)
+
+
+def _err(msg):
+    print(msg, file=sys.stderr, flush=True)
+
+
+def _parse(argv, build):
+    """Reference-style option parsing (examples/image-search/{build,search}.cpp my_app_params_parse)."""
+    p = dict(threads=4, verbose=1, db=".", dtype="f16", results=5, model="../models/ggml-model-f16.bin" if build else "", rest=[])
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        takes = {"-m": "model", "--model": "model", "-t": "threads", "--threads": "threads", "-v": "verbose", "--verbose": "verbose",
+                 "--db": "db"}
+        if build:
+            takes["--dtype"] = "dtype"
+        else:
+            takes.update({"-n": "results", "--results": "results"})
+        if a in takes:
+            i += 1
+            if i >= len(argv):
+                return None
+            key = takes[a]
+            try:
+                p[key] = int(argv[i]) if key in ("threads", "verbose", "results") else argv[i]
+            except ValueError:
+                return None
+        elif a in ("-h", "--help"):
+            _help(build, p)
+            sys.exit(0)
+        elif a.startswith("-"):
+            print("main: unrecognized argument: %s" % a)
+            return None
+        elif build:
+            p["rest"].append(a)
+        else:
+            p["rest"] = argv[i:]     # the query: everything from here on
+            break
+        i += 1
+    if not p["rest"] or (build and p["dtype"] not in ("f16", "f32")):
+        return None
+    return p
+
+
+def _help(build, p):
+    if build:
+        print("Usage: python -m clip_cpp_amd.image_search build [options] dir/with/pictures [more/dirs]")
+        print("\nOptions:")
+        print("  -h, --help: Show this message and exit")
+        print("  -m <path>, --model <path>: path to model. Default: %s" % p["model"])
+        print("  -t N, --threads N: Number of threads to use for inference. Default: %d" % p["threads"])
+        print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
+        print("  --db <dir>: directory that receives %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
+        print("  --dtype f16|f32: stored precision of the index. Default: %s" % p["dtype"])
+    else:
+        print("Usage: python -m clip_cpp_amd.image_search search [options] <search string or /path/to/query/image>")
+        print("\nOptions:")
+        print("  -h, --help: Show this message and exit")
+        print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default.")
+        print("  -t N, --threads N: Number of threads to use for inference. Default: %d" % p["threads"])
+        print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
+        print("  -n N, --results N: Number of results to display. Default: %d" % p["results"])
+        print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
+
+
+def image_files(base_dir):
+    """Every file under base_dir (recursively, in sorted order) whose extension passes is_image_file_extension."""
+    out = []
+    for root, dirs, files in os.walk(base_dir):
+        dirs.sort()
+        for name in sorted(files):
+            if is_image_file_extension(name):
+                out.append(os.path.join(root, name))
+    return out
+
+
+def _encode_batch(clip, L, imgs):
+    """embeddings [n, proj] of decoded clip_image_u8 structs through clip_amd_image_batch_encode_u8, normalised"""
+    import clip_cpp_amd
+    arr = (clip_cpp_amd.ClipImageU8 * len(imgs))(*[im.contents for im in imgs])
+    out = np.empty((len(imgs), clip.vision_config["projection_dim"]), dtype=np.float32)
+    if not L.clip_amd_image_batch_encode_u8(clip.ctx, arr, len(imgs), out.ctypes.data_as(C.POINTER(C.c_float)), True):
+        raise RuntimeError("clip_amd_image_batch_encode_u8 failed (see stderr)")
+    return out
+
+
+def build(argv):
+    import clip_cpp_amd
+    p = _parse(argv, build=True)
+    if p is None:
+        _help(True, dict(threads=4, verbose=1, db=".", dtype="f16", model="../models/ggml-model-f16.bin"))
+        return 1
+    L = clip_cpp_amd.lib()
+    try:
+        clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])
+    except RuntimeError:
+        print("main: Unable  to load model from %s" % p["model"])
+        return 1
+    if clip.vision_config["n_layer"] <= 0:
+        _err("main: the model at %s has no vision encoder: an image index needs a vision or two-tower model" % p["model"])
+        return 1
+    index = clip_cpp_amd.Index(clip, clip.vision_config["projection_dim"], dtype=p["dtype"])
+    paths = []
+
+    def flush(batch):
+        if not batch:
+            return
+        try:
+            index.add(_encode_batch(clip, L, [im for _, im in batch]))
+            paths.extend(path for path, _ in batch)
+        finally:
+            for _, im in batch:
+                L.clip_image_u8_free(im)
+            batch.clear()
+        if p["verbose"] == 1:
+            print(".", end="", flush=True)
+
+    batch = []
+    for base in p["rest"]:
+        print("main: starting base dir scan of '%s'" % base, flush=True)
+        files = image_files(base)
+        print("\nmain: processing %d files in '%s'" % (len(files), base), flush=True)
+        for path in files:
+            if p["verbose"] >= 2:
+                print("main: found image file '%s'" % path, flush=True)
+            im = L.clip_image_u8_make()
+            if not L.clip_image_load_from_file(os.fsencode(path), im):
+                L.clip_image_u8_free(im)
+                _err("main: failed to load image from '%s'" % path)
+                continue           # (no slot: the failed file gets no id and no line in images.paths)
+            batch.append((path, im))
+            if len(batch) == BATCH:
+                flush(batch)
+    flush(batch)
+    os.makedirs(p["db"], exist_ok=True)
+    index.save(os.path.join(p["db"], INDEX_FILE))
+    with open(os.path.join(p["db"], PATHS_FILE), "w") as f:
+        f.write(p["model"] + "\n")
+        for path in paths:
+            f.write(path + "\n")
+    index.close()
+    clip.close()
+    print("main: %d images processed and indexed" % len(paths), flush=True)
+    return 0
+
+
+def read_index_header(path):
+    """(version, dim, dtype, n) of a CLIPIDX1 file, or None when it is not one."""
+    try:
+        with open(path, "rb") as f:
+            h = f.read(28)
+    except OSError:
+        return None
+    if len(h) != 28 or h[:8] != b"CLIPIDX1":
+        return None
+    return struct.unpack("<IIIQ", h[8:])
+
+
+def search(argv):
+    import clip_cpp_amd
+    p = _parse(argv, build=False)
+    if p is None:
+        _help(False, dict(threads=4, verbose=1, db=".", results=5))
+        return 1
+    img_path, text = classify_query(p["rest"])
+    paths_file = os.path.join(p["db"], PATHS_FILE)
+    lines = []
+    if os.path.exists(paths_file):
+        with open(paths_file) as f:
+            lines = f.read().split("\n")
+    model_line = lines[0] if lines else ""
+    image_paths = []
+    for line in lines[1:]:
+        if not line:
+            break
+        image_paths.append(line)
+    if not p["model"]:
+        p["model"] = model_line
+    else:
+        print("main: using alternative model from %s. Make sure you use the same model you used for indexing, or the embeddings wont work."
+              % p["model"])
+    if not p["model"]:
+        print("main: Unable to load model from %s" % p["model"])
+        _err("main: no database in '%s' (%s is missing or empty): run `python -m clip_cpp_amd.image_search build` first" % (p["db"], PATHS_FILE))
+        return 1
+    hdr = read_index_header(os.path.join(p["db"], INDEX_FILE))
+    if hdr is None:
+        _err("main: '%s' is missing or not an index file" % os.path.join(p["db"], INDEX_FILE))
+        return 1
+    if hdr[3] != len(image_paths):
+        print("main: index files size missmatch")
+        return 1
+    try:
+        clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])
+    except RuntimeError:
+        print("main: Unable to load model from %s" % p["model"])
+        return 1
+    if img_path:
+        if clip.vision_config["n_layer"] <= 0:
+            _err("main: the model at %s has no vision encoder: image queries need a vision or two-tower model" % p["model"])
+            return 1
+        L = clip_cpp_amd.lib()
+        im = L.clip_image_u8_make()
+        try:
+            if not L.clip_image_load_from_file(os.fsencode(img_path), im):
+                _err("main: failed to load image from '%s'" % img_path)
+                return 1
+            vec = _encode_batch(clip, L, [im])[0]
+        finally:
+            L.clip_image_u8_free(im)
+    else:
+        if clip.text_config["n_layer"] <= 0:
+            _err("main: the model at %s has no text encoder: text queries need a two-tower model" % p["model"])
+            return 1
+        vec = np.asarray(clip.encode_text(clip.tokenize(text), n_threads=p["threads"], normalize=True), dtype=np.float32)
+    index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
+    if index.dim != vec.size:
+        _err("main: the index holds %d-dimensional embeddings, the model makes %d" % (index.dim, vec.size))
+        return 1
+    k = max(1, min(p["results"], MAX_K))
+    dist, ids = index.search(vec[None, :], k)
+    if p["verbose"] > 0:
+        print("search results:")
+        print("distance path")
+    for d, i in zip(dist[0], ids[0]):
+        if i >= 0 and p["results"] > 0:
+            print("  %f %s" % (d, image_paths[i]))
+    sys.stdout.flush()
+    index.close()
+    clip.close()
+    return 0
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else argv
+    if not argv or argv[0] not in ("build", "search"):
+        print("Usage: python -m clip_cpp_amd.image_search {build|search} [options] ...  (-h after the command for its options)")
+        return 1
+    return build(argv[1:]) if argv[0] == "build" else search(argv[1:])
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -136,6 +136,35 @@ int clip_amd_profile_read(struct clip_ctx * ctx, float * ms, int64_t * launches,
  * Returns the number of bytes needed (call with buf == NULL to size the buffer). */
 int clip_amd_profile_report(struct clip_ctx * ctx, char * buf, int cap, bool reset);
 
+/* ---- exact nearest-neighbour index (semantic image search; the reference's examples/image-search uses an approximate usearch
+ * index for the same job) ----
+ * Cosine distance d = 1 - <q/|q|, g/|g|>: rows are L2-normalised in f32 when added, queries when searched (a zero vector stays zero:
+ * distance exactly 1), both stored in the index dtype (0 = f32, 1 = f16: the normalised values rounded to fp16), dot products in f32.
+ * Rows get ids 0 ... n-1 in the order they were added; appending after a search is allowed, deletion is not.  Results per query sorted
+ * by ascending distance, equal distances lower id first; with k > size the tail holds id -1 / distance +INFINITY.  1 <= k <= 1024,
+ * 4 <= dim <= 4096 with dim % 4 == 0, any number of queries, up to 2^31 - 1 rows.  Results are bit-identical run to run, however queries
+ * are split across calls, however rows were split across add calls, and across save / load.
+ * The index lives on ctx's device and launches on ctx's stream (clip_amd_set_stream applies); free it before the ctx.  NULL on a
+ * host-only ctx.  Bad arguments make a call return false (NULL) with a message on stderr, without launching anything.
+ * File format (little-endian): "CLIPIDX1", u32 version (1), u32 dim, u32 dtype, u64 n, then n rows of dim stored values (unpadded). */
+struct clip_amd_index;
+struct clip_amd_index * clip_amd_index_create(struct clip_ctx * ctx, int dim, int dtype);
+bool clip_amd_index_add(struct clip_amd_index * ix, const float * vecs, int64_t n);            /* host rows [n][dim], synchronous */
+bool clip_amd_index_add_device(struct clip_amd_index * ix, const float * d_vecs, int64_t n);   /* HBM rows, asynchronous on the ctx stream */
+int64_t clip_amd_index_size(const struct clip_amd_index * ix);
+int clip_amd_index_dim(const struct clip_amd_index * ix);
+/* queries [n_queries][dim] -> distances [n_queries][k], ids [n_queries][k]; host pointers, synchronous */
+bool clip_amd_index_search(struct clip_amd_index * ix, const float * queries, int n_queries, int k, float * distances, int64_t * ids);
+/* the same on HBM pointers, asynchronous on the ctx stream */
+bool clip_amd_index_search_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int k, float * d_distances,
+                                  int64_t * d_ids);
+bool clip_amd_index_save(struct clip_amd_index * ix, const char * path);
+struct clip_amd_index * clip_amd_index_load(struct clip_ctx * ctx, const char * path);
+void clip_amd_index_free(struct clip_amd_index * ix);
+/* Average device time (microseconds, HIP events) of one clip_amd_index_search_device of n_queries seeded random queries against n seeded
+ * random rows on the current device; < 0 on error.  Used by scripts/search_bench.py. */
+float clip_amd_bench_search(int dtype, int64_t n, int dim, int n_queries, int k, int iters);
+
 /* ---- kernel-level test hooks (used by tests/ only; host pointers, synchronous) ----
  * Y[M,N] = X[M,K] . W[N,K]^T (+bias) through the production dequant-GEMM kernel.
  * w_raw is the tensor in its GGUF/ggml block layout (type: ggml type id 0,1,2,3,6,7,8).
