@@ -507,15 +507,21 @@ class Clip:
 class Index:
     """Exact cosine nearest-neighbour index on the GPU of a `Clip` (clip_amd_index_*, include/clip_amd.h): rows are L2-normalised and
     stored in f16 (default) or f32; search returns (distances f32 [nq, k], ids int64 [nq, k]) sorted by ascending 1 - cosine, equal
-    distances lower id first, -1 / +inf past the index size.  Keep the `Clip` alive while the index is in use."""
+    distances lower id first, -1 / +inf past the index size.  Keep the `Clip` alive while the index is in use.
 
-    DTYPES = {"f32": 0, "f16": 1}
+    "i8" (dtype code 3) stores each row as int8, a quarter of f32's bytes: in f32, amax = max |x|, q = rint((x / amax) * 127) (half to
+    even; numpy: np.rint((x / amax).astype(np.float32) * np.float32(127))), no L2 normalisation first (the mapping is scale-invariant).
+    Queries are quantised the same way at search time.  A vector with amax 0 or any NaN / inf is stored as the zero vector (distance
+    exactly 1 to everything).  Distance = 1 - (float)dot * inv_q * inv_r with dot the exact int32 sum q_i r_i and inv = 1 / sqrtf(sum
+    v_i^2) (0 for the zero vector): the cosine distance of the stored integer vectors, bit-reproducible like the other dtypes."""
+
+    DTYPES = {"f32": 0, "f16": 1, "i8": 3}
 
     def __init__(self, clip, dim, dtype="f16", _handle=None):
         self.clip = clip
         if _handle is None:
             if dtype not in self.DTYPES:
-                raise ValueError("dtype must be 'f16' or 'f32', not %r" % (dtype,))
+                raise ValueError("dtype must be 'f16', 'f32' or 'i8', not %r" % (dtype,))
             _handle = lib().clip_amd_index_create(clip.ctx, int(dim), self.DTYPES[dtype])
             if not _handle:
                 raise RuntimeError("clip_amd_index_create failed (see stderr)")

@@ -1,13 +1,20 @@
 // k_search.hip — exact cosine nearest-neighbour search over a device-resident gallery (the semantic image search of the reference's
 // examples/image-search, which uses an approximate usearch HNSW index; this one is exact).
 //
-//   rows      [cap][Dpad] in the stored dtype (fp16 or f32), each row L2-normalised in f32 at add time, zero padded to Dpad = 32 m
-//   queries   normalised the same way into [nq_pad][Dpad] of the stored dtype at search time
+//   rows      [cap][Dpad] in the stored dtype (fp16 or f32), each row L2-normalised in f32 at add time, zero padded to Dpad = 32 m;
+//             i8: each row quantised in f32 at add time (q = rint(x / max|x| * 127)), zero padded to Dpad = 64 m, plus rinv [cap] f32 =
+//             1 / sqrt(sum q^2) (0 for the zero row)
+//   queries   normalised (quantised) the same way into [nq_pad][Dpad] of the stored dtype at search time (i8: and qinv [nq_pad])
 //   score     <q, g> accumulated in f32 on the MFMA (fp16: v_mfma_f32_16x16x32_f16, f32: v_mfma_f32_16x16x4_f32); distance = 1 - score (f32)
+//             i8: the exact i32 dot on v_mfma_i32_16x16x64_i8, score = (float)dot * qinv * rinv
 //
 // Kernels:
 //   search_normalize_kernel  one wave per row: f32 sum of squares (fixed lane order + butterfly), x / sqrt(ss) (zero rows stay zero),
 //                            written in the stored dtype with the zero padding; rows past the source count are written as zeros.
+//   search_quantize_kernel   the i8 form: one wave per row: max |x| and a non-finite flag (a row with amax 0 or any NaN / inf is the zero
+//                            row), rint(x / amax * 127) packed 4 per lane store with the zero padding, the exact integer sum of squares
+//                            -> inv; rows past the source count are written as zeros (inv 0).
+//   search_row_inv_kernel    inv of stored i8 rows (index load: the file holds the rows only).
 //   search_scan_kernel       workgroup = one contiguous chunk of rows x one block of 16 QT queries, 4 waves.  Each wave takes 16 rows per
 //                            iteration (the MFMA "A" operand, read straight from HBM, 16 bytes per lane per k-step) against QT query tiles
 //                            (the "B" operand, L2-resident); a lane ends up with, for ONE query (lane & 15), 4 consecutive rows.
@@ -36,6 +43,11 @@ namespace {
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef int i4 __attribute__((ext_vector_type(4)));
+
+// accumulator of the scan per stored dtype: f32 for fp16 / f32 rows, the exact i32 dot for i8 rows
+template <typename T> struct ScanAcc { typedef f4 type; };
+template <> struct ScanAcc<int8_t> { typedef i4 type; };
 
 struct Cand {
     float s;
@@ -72,6 +84,71 @@ __global__ void __launch_bounds__(256) search_normalize_kernel(const float * __r
     }
 }
 
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// 1 / |q| of an i8 vector from its exact sum of squares (<= 127^2 * 4096 < 2^31); 0 for the zero vector
+__device__ __forceinline__ float i8_inv_norm(int ss) { return ss > 0 ? 1.0f / sqrtf((float)ss) : 0.f; }
+
+__global__ void __launch_bounds__(256) search_quantize_kernel(const float * __restrict__ src, int64_t n_src, int64_t n_rows, int dim, int Dpad,
+                                                              int8_t * __restrict__ dst, float * __restrict__ inv) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n_rows) return;
+    unsigned * d = (unsigned *)(dst + row * Dpad);            // 4 values per store (Dpad = 64 m)
+    const float * s = src + row * dim;
+    float amax = 0.f;
+    int bad = row >= n_src;
+    if (!bad) {
+        for (int i = lane; i < dim; i += 64) {
+            const float a = fabsf(s[i]);
+            bad |= !(a <= FLT_MAX);                            // NaN or inf (fmaxf alone would skip a NaN)
+            amax = fmaxf(amax, a);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        amax = fmaxf(amax, __shfl_xor(amax, off, 64));
+        bad |= __shfl_xor(bad, off, 64);
+    }
+    const bool zero = bad || !(amax > 0.f);
+    int ss = 0;
+    for (int g = lane; g < Dpad / 4; g += 64) {
+        unsigned w = 0;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int i = 4 * g + t;
+            const int q = (!zero && i < dim) ? (int)rintf((s[i] / amax) * 127.0f) : 0;   // |x / amax| <= 1: no clamp
+            ss += q * q;
+            w |= (unsigned)(q & 255) << (8 * t);
+        }
+        d[g] = w;
+    }
+    ss = wave_sum_i(ss);
+    if (lane == 0) inv[row] = i8_inv_norm(ss);
+}
+
+__global__ void __launch_bounds__(256) search_row_inv_kernel(const int8_t * __restrict__ rows, int64_t n, int Dpad, float * __restrict__ inv) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const unsigned * r = (const unsigned *)(rows + row * Dpad);
+    int ss = 0;
+    for (int g = lane; g < Dpad / 4; g += 64) {
+        const unsigned w = r[g];
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int q = (int)(signed char)(w >> (8 * t));
+            ss += q * q;
+        }
+    }
+    ss = wave_sum_i(ss);
+    if (lane == 0) inv[row] = i8_inv_norm(ss);
+}
+
 struct ScanParams {
     const void * rows;     // [>= n][Dpad]
     const void * q;        // [nq_pad][Dpad]
@@ -81,6 +158,8 @@ struct ScanParams {
     int nq;
     int k, C, P;           // P = power of two >= C (sort buffer)
     int64_t rows_per_chunk;
+    const float * rinv;    // i8: [>= n rounded up to 64] row inverse norms
+    const float * qinv;    // i8: [nq_pad] query inverse norms
 };
 
 // bitonic sort of a wave's LDS buffer (P pairs, better first).  The buffer is private to the wave and LDS operations of one wave are
@@ -124,15 +203,19 @@ __device__ int wave_select(Cand * buf, int cnt, int k, int P, bool final, float 
 }
 
 // One k-step of a row (or query) for lane group fgrp: fp16 — 32 k per step, the lane's 8 consecutive k (16 bytes); f32 — 16 k per step,
-// the lane's 4 consecutive k, consumed by four MFMAs (MFMA s multiplies k = 4 fgrp + s on both operands: a permuted but fixed order).
+// the lane's 4 consecutive k, consumed by four MFMAs (MFMA s multiplies k = 4 fgrp + s on both operands: a permuted but fixed order);
+// i8 — 64 k per step, the lane's 16 consecutive k (16 bytes), one MFMA (both operands take the same lane -> k map, so the dot is the same
+// whatever order the instruction gives the 16 bytes).
 template <typename T>
 __device__ __forceinline__ u32x4 ld_step(const T * row, int kk, int fgrp) {
-    return *(const u32x4 *)(row + kk * (sizeof(T) == 2 ? 32 : 16) + fgrp * (sizeof(T) == 2 ? 8 : 4));
+    return *(const u32x4 *)(row + kk * (64 / (int)sizeof(T)) + fgrp * (16 / (int)sizeof(T)));
 }
 
 template <typename T>
-__device__ __forceinline__ f4 mfma_step(u32x4 a, u32x4 b, f4 acc) {
-    if constexpr (sizeof(T) == 2) {
+__device__ __forceinline__ typename ScanAcc<T>::type mfma_step(u32x4 a, u32x4 b, typename ScanAcc<T>::type acc) {
+    if constexpr (sizeof(T) == 1) {
+        return __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i4, a), __builtin_bit_cast(i4, b), acc, 0, 0, 0);
+    } else if constexpr (sizeof(T) == 2) {
         return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), acc, 0, 0, 0);
     } else {
         const f4 af = __builtin_bit_cast(f4, a), bf = __builtin_bit_cast(f4, b);
@@ -174,11 +257,11 @@ __global__ void __launch_bounds__(SCAN_THREADS) search_scan_kernel(const ScanPar
             int64_t gr = r0 + frow;
             gr = gr < p.n ? gr : p.n - 1;                                     // rows past the end compute on the last row, never pushed
             const T * grow = (const T *)p.rows + gr * p.Dpad;
-            f4 acc[QT];
+            typename ScanAcc<T>::type acc[QT];
 #pragma unroll
-            for (int j = 0; j < QT; j++) acc[j] = (f4){0.f, 0.f, 0.f, 0.f};
+            for (int j = 0; j < QT; j++) acc[j] = {};
             // the k-steps in order, four row loads in flight at a time (the same chain for every (query, row) pair)
-            const int nk = sizeof(T) == 2 ? p.Dpad / 32 : p.Dpad / 16;
+            const int nk = p.Dpad / (64 / (int)sizeof(T));
             int kk = 0;
             for (; kk + 4 <= nk; kk += 4) {
                 u32x4 a[4];
@@ -195,16 +278,22 @@ __global__ void __launch_bounds__(SCAN_THREADS) search_scan_kernel(const ScanPar
                 for (int j = 0; j < QT; j++) acc[j] = mfma_step<T>(a, ld_step<T>(qrow[j], kk, fgrp), acc[j]);
             }
             // lane holds query q0 + 16 j + frow against rows r0 + 4 fgrp + r
+            f4 rinv = {};
+            if constexpr (sizeof(T) == 1) rinv = *(const f4 *)(p.rinv + r0 + fgrp * 4);   // r0 + 4 fgrp < n rounded up to 16: allocated
 #pragma unroll
             for (int j = 0; j < QT; j++) {
                 const int ql = j * 16 + frow;
                 if (q0 + ql >= p.nq) continue;
                 const float t = thr[ql];
                 Cand * buf = p.cand + ((size_t)chunk * p.nq + q0 + ql) * p.C;
+                float qinv = 0.f;
+                if constexpr (sizeof(T) == 1) qinv = p.qinv[q0 + ql];
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     const int64_t row = r0 + fgrp * 4 + r;
-                    const float d = 1.0f - acc[j][r];
+                    float d;
+                    if constexpr (sizeof(T) == 1) d = 1.0f - (float)acc[j][r] * qinv * rinv[r];
+                    else d = 1.0f - acc[j][r];
                     if (row < hi && d < t) {
                         const int slot = atomicAdd(&cnt[ql], 1);
                         buf[slot] = Cand{d, (int)row};
@@ -314,18 +403,31 @@ int search_sort_size(int k) {
     return P;
 }
 
-void launch_search_normalize(const float * src, int64_t n_src, int64_t n_rows, int dim, int Dpad, void * dst, bool f16, hipStream_t stream) {
+void launch_search_normalize(const float * src, int64_t n_src, int64_t n_rows, int dim, int Dpad, void * dst, int dtype, hipStream_t stream) {
     if (n_rows <= 0) return;
     const unsigned blocks = (unsigned)((n_rows + 3) / 4);
-    if (f16) hipLaunchKernelGGL(search_normalize_kernel<half_t>, dim3(blocks), dim3(256), 0, stream, src, n_src, n_rows, dim, Dpad, (half_t *)dst);
+    if (dtype == SEARCH_F16) hipLaunchKernelGGL(search_normalize_kernel<half_t>, dim3(blocks), dim3(256), 0, stream, src, n_src, n_rows, dim, Dpad, (half_t *)dst);
     else hipLaunchKernelGGL(search_normalize_kernel<float>, dim3(blocks), dim3(256), 0, stream, src, n_src, n_rows, dim, Dpad, (float *)dst);
 }
 
-bool launch_search_scan(const void * rows, int64_t n, int Dpad, bool f16, const void * q, int nq, int qt, int k, void * cand, int n_chunks,
-                        int64_t rows_per_chunk, hipStream_t stream) {
+void launch_search_quantize(const float * src, int64_t n_src, int64_t n_rows, int dim, int Dpad, void * dst, float * inv, hipStream_t stream) {
+    if (n_rows <= 0) return;
+    hipLaunchKernelGGL(search_quantize_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, stream, src, n_src, n_rows, dim, Dpad,
+                       (int8_t *)dst, inv);
+}
+
+void launch_search_row_inv(const void * rows, int64_t n, int Dpad, float * inv, hipStream_t stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(search_row_inv_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, (const int8_t *)rows, n, Dpad, inv);
+}
+
+bool launch_search_scan(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq, int qt,
+                        int k, void * cand, int n_chunks, int64_t rows_per_chunk, hipStream_t stream) {
     ScanParams p;
     p.rows = rows;
     p.q = q;
+    p.rinv = rinv;
+    p.qinv = qinv;
     p.cand = (Cand *)cand;
     p.n = n;
     p.Dpad = Dpad;
@@ -334,7 +436,12 @@ bool launch_search_scan(const void * rows, int64_t n, int Dpad, bool f16, const 
     p.C = search_candidate_capacity(k);
     p.P = search_sort_size(k);
     p.rows_per_chunk = rows_per_chunk;
-    if (f16) {
+    if (dtype == SEARCH_I8) {
+        if (qt == 4) return launch_scan_t<int8_t, 4>(p, n_chunks, stream);
+        if (qt == 2) return launch_scan_t<int8_t, 2>(p, n_chunks, stream);
+        return launch_scan_t<int8_t, 1>(p, n_chunks, stream);
+    }
+    if (dtype == SEARCH_F16) {
         if (qt == 4) return launch_scan_t<half_t, 4>(p, n_chunks, stream);
         if (qt == 2) return launch_scan_t<half_t, 2>(p, n_chunks, stream);
         return launch_scan_t<half_t, 1>(p, n_chunks, stream);

@@ -284,15 +284,21 @@ void launch_f32_to_f16(const float * src, int lds, half_t * dst, int ldd, int ro
                        hipStream_t stream);
 void launch_f16_to_f32(const half_t * src, int lds, float * dst, int ldd, int rows, int cols, hipStream_t stream);
 
-// Exact nearest-neighbour search (k_search.hip).  Stored rows / queries: [rows][Dpad] fp16 (f16) or f32, Dpad = 32 m, L2-normalised.
+// Exact nearest-neighbour search (k_search.hip).  Stored dtypes (the codes of clip_amd_index_create; 2 is reserved):
+enum { SEARCH_F32 = 0, SEARCH_F16 = 1, SEARCH_I8 = 3 };
+// f32 / fp16: stored rows / queries [rows][Dpad], Dpad = 32 m, L2-normalised (launch_search_normalize).  i8: [rows][Dpad] int8, Dpad = 64 m, quantised rint(x / max|x| * 127) with inv = 1 / sqrt(sum q^2) per
+// vector (launch_search_quantize; launch_search_row_inv recomputes inv of stored rows); the scan reads rinv as 16-byte groups, so a row
+// inv array holds at least n rounded up to 64 floats.
 // Candidate workspace of a scan: [n_chunks][nq][search_candidate_capacity(k)] (score f32, id i32) pairs; each chunk's best k, sorted, ends
 // at the head of its (chunk, query) slot.  Merge: lists 2i, 2i + 1 -> list i ([n_out][nq][k] pairs).  Finish: one list per query ->
 // distances (1 - score) and int64 ids, empty slots -1 / +inf.
 int search_candidate_capacity(int k);
 int search_sort_size(int k);
-void launch_search_normalize(const float * src, int64_t n_src, int64_t n_rows, int dim, int Dpad, void * dst, bool f16, hipStream_t stream);
-bool launch_search_scan(const void * rows, int64_t n, int Dpad, bool f16, const void * q, int nq, int qt, int k, void * cand, int n_chunks,
-                        int64_t rows_per_chunk, hipStream_t stream);
+void launch_search_normalize(const float * src, int64_t n_src, int64_t n_rows, int dim, int Dpad, void * dst, int dtype, hipStream_t stream);
+void launch_search_quantize(const float * src, int64_t n_src, int64_t n_rows, int dim, int Dpad, void * dst, float * inv, hipStream_t stream);
+void launch_search_row_inv(const void * rows, int64_t n, int Dpad, float * inv, hipStream_t stream);
+bool launch_search_scan(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq, int qt,
+                        int k, void * cand, int n_chunks, int64_t rows_per_chunk, hipStream_t stream);
 void launch_search_merge(const void * in, int64_t in_stride, int n_in, void * out, int nq, int k, hipStream_t stream);
 void launch_search_finish(const void * in, int64_t in_stride, int nq, int k, float * dist, int64_t * ids, hipStream_t stream);
 void launch_search_fill_random(float * x, int64_t n, uint64_t seed, hipStream_t stream);

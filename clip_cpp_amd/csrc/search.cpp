@@ -21,9 +21,11 @@ struct clip_amd_index {
     size_t es = 2;                 // bytes per stored value
     int64_t n = 0, cap = 0;        // rows stored / allocated
     void * rows = nullptr;         // [cap][Dpad]
+    float * rinv = nullptr;        // i8: [cap rounded up to 64] row inverse norms (the scan reads them 4 at a time)
     // device workspaces, grown on demand
     void * stage = nullptr; size_t stage_bytes = 0;     // f32 rows / queries copied from the host
     void * qbuf = nullptr;  size_t qbuf_bytes = 0;      // normalised queries [nq_pad][Dpad]
+    void * qinv = nullptr;  size_t qinv_bytes = 0;      // i8: query inverse norms [nq_pad]
     void * cand = nullptr;  size_t cand_bytes = 0;      // [n_chunks][nq][C] candidates
     void * mbuf[2] = {nullptr, nullptr}; size_t mbuf_bytes = 0;   // merge levels
     void * outs = nullptr;  size_t outs_bytes = 0;      // distances + ids of the host search form
@@ -63,39 +65,54 @@ bool reserve_rows(clip_amd_index * ix, int64_t need) {
     int64_t cap = std::max<int64_t>({need, ix->cap * 2, 1024});
     cap = std::min<int64_t>(cap, std::max<int64_t>(need, MAX_ROWS));
     void * p = nullptr;
-    if (hipMalloc(&p, (size_t)cap * ix->Dpad * ix->es) != hipSuccess) {
+    float * inv = nullptr;
+    const bool i8 = ix->dtype == SEARCH_I8;
+    if (hipMalloc(&p, (size_t)cap * ix->Dpad * ix->es) != hipSuccess ||
+        (i8 && hipMalloc((void **)&inv, (size_t)(cap + 63) / 64 * 64 * sizeof(float)) != hipSuccess)) {
         (void)hipGetLastError();
+        if (p) (void)hipFree(p);
         fprintf(stderr, "clip_amd_index: cannot allocate %lld rows of %d values\n", (long long)cap, ix->Dpad);
         return false;
     }
     hipStream_t st = stream_of(ix);
     if (ix->rows) {
         (void)hipMemcpyAsync(p, ix->rows, (size_t)ix->n * ix->Dpad * ix->es, hipMemcpyDeviceToDevice, st);
+        if (i8) (void)hipMemcpyAsync(inv, ix->rinv, (size_t)ix->n * sizeof(float), hipMemcpyDeviceToDevice, st);
         (void)hipStreamSynchronize(st);
         (void)hipFree(ix->rows);
+        if (ix->rinv) (void)hipFree(ix->rinv);
     }
     ix->rows = p;
+    ix->rinv = inv;
     ix->cap = cap;
     return true;
 }
 
 bool valid_dim(int dim) { return dim >= 4 && dim <= 4096 && dim % 4 == 0; }
+bool valid_dtype(int64_t dtype) { return dtype == SEARCH_F32 || dtype == SEARCH_F16 || dtype == SEARCH_I8; }
+size_t elem_size(int dtype) { return dtype == SEARCH_I8 ? 1 : dtype == SEARCH_F16 ? 2 : 4; }
 
 clip_amd_index * make_index(clip_ctx * ctx, int device, int dim, int dtype) {
     clip_amd_index * ix = new clip_amd_index;
     ix->ctx = ctx;
     ix->device = device;
     ix->dim = dim;
-    ix->Dpad = (dim + 31) / 32 * 32;
+    ix->Dpad = dtype == SEARCH_I8 ? (dim + 63) / 64 * 64 : (dim + 31) / 32 * 32;      // one k-step: 64 i8 / 32 fp16 / 16 f32 values
     ix->dtype = dtype;
-    ix->es = dtype == 1 ? 2 : 4;
+    ix->es = elem_size(dtype);
     return ix;
+}
+
+// rows [n_rows][Dpad] of the stored dtype (and, i8, their inverse norms) from f32 [n_src][dim]; rows past n_src are zeros
+void prepare_rows(const clip_amd_index * ix, const float * src, int64_t n_src, int64_t n_rows, void * dst, float * inv) {
+    if (ix->dtype == SEARCH_I8) launch_search_quantize(src, n_src, n_rows, ix->dim, ix->Dpad, dst, inv, stream_of(ix));
+    else launch_search_normalize(src, n_src, n_rows, ix->dim, ix->Dpad, dst, ix->dtype, stream_of(ix));
 }
 
 void free_index(clip_amd_index * ix) {
     (void)hipSetDevice(ix->device);
     (void)hipStreamSynchronize(stream_of(ix));
-    for (void * p : {ix->rows, ix->stage, ix->qbuf, ix->cand, ix->mbuf[0], ix->mbuf[1], ix->outs})
+    for (void * p : {ix->rows, (void *)ix->rinv, ix->stage, ix->qbuf, ix->qinv, ix->cand, ix->mbuf[0], ix->mbuf[1], ix->outs})
         if (p) (void)hipFree(p);
     delete ix;
 }
@@ -113,7 +130,6 @@ bool search_device_impl(clip_amd_index * ix, const float * d_q, int nq, int k, f
         launch_search_finish(nullptr, 0, nq, k, d_dist, d_ids, st);
         return hipGetLastError() == hipSuccess;
     }
-    const bool f16 = ix->dtype == 1;
     const int64_t rpc = rows_per_chunk(ix->n, k);
     const int n_chunks = (int)((ix->n + rpc - 1) / rpc);
     const int C = search_candidate_capacity(k);
@@ -124,6 +140,7 @@ bool search_device_impl(clip_amd_index * ix, const float * d_q, int nq, int k, f
         const int qt = m >= 64 ? 4 : (m > 16 ? 2 : 1);
         const int64_t m_pad = (m + 16 * qt - 1) / (16 * qt) * (16 * qt);
         if (!ensure(ix, ix->qbuf, ix->qbuf_bytes, (size_t)m_pad * ix->Dpad * ix->es)) return false;
+        if (ix->dtype == SEARCH_I8 && !ensure(ix, ix->qinv, ix->qinv_bytes, (size_t)m_pad * sizeof(float))) return false;
         if (!ensure(ix, ix->cand, ix->cand_bytes, (size_t)n_chunks * m * C * 8)) return false;
         const size_t mb = (size_t)((n_chunks + 1) / 2) * m * k * 8;
         if (n_chunks > 1 && mb > ix->mbuf_bytes) {
@@ -131,8 +148,9 @@ bool search_device_impl(clip_amd_index * ix, const float * d_q, int nq, int k, f
             if (!ensure(ix, ix->mbuf[0], have0, mb) || !ensure(ix, ix->mbuf[1], have1, mb)) return false;
             ix->mbuf_bytes = mb;
         }
-        launch_search_normalize(d_q + (size_t)q0 * ix->dim, m, m_pad, ix->dim, ix->Dpad, ix->qbuf, f16, st);
-        if (!launch_search_scan(ix->rows, ix->n, ix->Dpad, f16, ix->qbuf, m, qt, k, ix->cand, n_chunks, rpc, st)) {
+        prepare_rows(ix, d_q + (size_t)q0 * ix->dim, m, m_pad, ix->qbuf, (float *)ix->qinv);
+        if (!launch_search_scan(ix->rows, ix->rinv, ix->n, ix->Dpad, ix->dtype, ix->qbuf, (const float *)ix->qinv, m, qt, k, ix->cand, n_chunks,
+                                rpc, st)) {
             fprintf(stderr, "clip_amd_index_search: scan launch failed\n");
             return false;
         }
@@ -165,7 +183,7 @@ bool check_search_args(const clip_amd_index * ix, const void * q, int nq, int k,
 
 bool add_device_impl(clip_amd_index * ix, const float * d_vecs, int64_t n) {
     if (!reserve_rows(ix, ix->n + n)) return false;
-    launch_search_normalize(d_vecs, n, n, ix->dim, ix->Dpad, (char *)ix->rows + (size_t)ix->n * ix->Dpad * ix->es, ix->dtype == 1, stream_of(ix));
+    prepare_rows(ix, d_vecs, n, n, (char *)ix->rows + (size_t)ix->n * ix->Dpad * ix->es, ix->rinv ? ix->rinv + ix->n : nullptr);
     if (hipGetLastError() != hipSuccess) { fprintf(stderr, "clip_amd_index_add: launch failed\n"); return false; }
     ix->n += n;
     return true;
@@ -192,7 +210,7 @@ struct clip_amd_index * clip_amd_index_create(struct clip_ctx * ctx, int dim, in
     if (!ctx) { fprintf(stderr, "clip_amd_index_create: ctx is NULL\n"); return nullptr; }
     if (ctx->device < 0) { fprintf(stderr, "clip_amd_index_create: host-only context: the index lives on a HIP device\n"); return nullptr; }
     if (!valid_dim(dim)) { fprintf(stderr, "clip_amd_index_create: dim %d not in 4 ... 4096 or not a multiple of 4\n", dim); return nullptr; }
-    if (dtype != 0 && dtype != 1) { fprintf(stderr, "clip_amd_index_create: dtype %d is neither 0 (f32) nor 1 (f16)\n", dtype); return nullptr; }
+    if (!valid_dtype(dtype)) { fprintf(stderr, "clip_amd_index_create: dtype %d is not 0 (f32), 1 (f16) or 3 (i8)\n", dtype); return nullptr; }
     (void)hipSetDevice(ctx->device);
     return make_index(ctx, ctx->device, dim, dtype);
 } catch (const std::exception & e) { fprintf(stderr, "clip_amd_index_create: %s\n", e.what()); return nullptr; }
@@ -287,8 +305,8 @@ struct clip_amd_index * clip_amd_index_load(struct clip_ctx * ctx, const char * 
     if (hdr[0] != VERSION) { fprintf(stderr, "clip_amd_index_load: '%s' has version %u, expected %u\n", path, hdr[0], VERSION); return nullptr; }
     const uint32_t dim = hdr[1], dtype = hdr[2];
     if (dim > 4096 || !valid_dim((int)dim)) { fprintf(stderr, "clip_amd_index_load: '%s': dim %u not in 4 ... 4096 or not a multiple of 4\n", path, dim); return nullptr; }
-    if (dtype > 1) { fprintf(stderr, "clip_amd_index_load: '%s': unknown dtype %u\n", path, dtype); return nullptr; }
-    const uint64_t es = dtype == 1 ? 2 : 4;
+    if (!valid_dtype(dtype)) { fprintf(stderr, "clip_amd_index_load: '%s': unknown dtype %u (known: 0 f32, 1 f16, 3 i8)\n", path, dtype); return nullptr; }
+    const uint64_t es = elem_size((int)dtype);
     if (n > (uint64_t)MAX_ROWS || n > UINT64_MAX / (dim * es)) {
         fprintf(stderr, "clip_amd_index_load: '%s': %llu rows of %u values overflow the index\n", path, (unsigned long long)n, dim);
         return nullptr;
@@ -315,6 +333,10 @@ struct clip_amd_index * clip_amd_index_load(struct clip_ctx * ctx, const char * 
                               hipMemcpyHostToDevice, st) == hipSuccess &&
              hipStreamSynchronize(st) == hipSuccess;
     }
+    if (ok && ix->dtype == SEARCH_I8) {          // the file holds the rows only: their inverse norms again, the same integer arithmetic
+        launch_search_row_inv(ix->rows, (int64_t)n, ix->Dpad, ix->rinv, st);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+    }
     if (!ok) {
         fprintf(stderr, "clip_amd_index_load: reading '%s' failed\n", path);
         free_index(ix);
@@ -331,7 +353,7 @@ void clip_amd_index_free(struct clip_amd_index * ix) {
 float clip_amd_bench_search(int dtype, int64_t n, int dim, int n_queries, int k, int iters) try {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return -1.f; }
-    if ((dtype != 0 && dtype != 1) || !valid_dim(dim) || n < 1 || n > MAX_ROWS || n_queries < 1 || k < 1 || k > MAX_K || iters < 1) return -3.f;
+    if (!valid_dtype(dtype) || !valid_dim(dim) || n < 1 || n > MAX_ROWS || n_queries < 1 || k < 1 || k > MAX_K || iters < 1) return -3.f;
     int dev = 0;
     (void)hipGetDevice(&dev);
     clip_amd_index * ix = make_index(nullptr, dev, dim, dtype);

@@ -1,7 +1,7 @@
 """Semantic image search over a directory tree: the reference's examples/image-search (`image-search-build` / `image-search`,
 build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.Index`) instead of usearch's approximate one.
 
-    python -m clip_cpp_amd.image_search build  [-m MODEL] [-v N] [-t N] [--db DIR] [--dtype f16|f32] dir [more dirs]
+    python -m clip_cpp_amd.image_search build  [-m MODEL] [-v N] [-t N] [--db DIR] [--dtype f16|f32|i8] dir [more dirs]
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N] [--db DIR] <search text or /path/to/query/image>
 
 `build` writes DIR/images.index (the CLIPIDX1 file of clip_amd_index_save) and DIR/images.paths (the reference's layout: the model path
@@ -75,7 +75,7 @@ def _parse(argv, build):
             p["rest"] = argv[i:]     # the query: everything from here on
             break
         i += 1
-    if not p["rest"] or (build and p["dtype"] not in ("f16", "f32")):
+    if not p["rest"] or (build and p["dtype"] not in ("f16", "f32", "i8")):
         return None
     return p
 
@@ -89,7 +89,7 @@ def _help(build, p):
         print("  -t N, --threads N: Number of threads to use for inference. Default: %d" % p["threads"])
         print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
         print("  --db <dir>: directory that receives %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
-        print("  --dtype f16|f32: stored precision of the index. Default: %s" % p["dtype"])
+        print("  --dtype f16|f32|i8: stored precision of the index (i8: int8 rows, half of f16's memory). Default: %s" % p["dtype"])
     else:
         print("Usage: python -m clip_cpp_amd.image_search search [options] <search string or /path/to/query/image>")
         print("\nOptions:")

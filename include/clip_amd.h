@@ -140,13 +140,20 @@ int clip_amd_profile_report(struct clip_ctx * ctx, char * buf, int cap, bool res
  * index for the same job) ----
  * Cosine distance d = 1 - <q/|q|, g/|g|>: rows are L2-normalised in f32 when added, queries when searched (a zero vector stays zero:
  * distance exactly 1), both stored in the index dtype (0 = f32, 1 = f16: the normalised values rounded to fp16), dot products in f32.
+ * dtype 3 = i8 (2 is reserved): each row when added and each query when searched is quantised in f32, in this order, without FMA
+ * contraction: amax = max_i |x_i|, q_i = (int8) rintf((x_i / amax) * 127.0f) (half to even; |x_i / amax| <= 1, no clamp); no L2
+ * normalisation first (the mapping is scale-invariant).  A vector with amax == 0 or any NaN / inf is stored as the zero vector
+ * (distance exactly 1).  d = 1 - (float)dot * inv_q * inv_r, dot = sum_i q_i r_i an exact int32 (|dot| <= 127^2 * 4096 < 2^31),
+ * inv = 1.0f / sqrtf((float)sum_i v_i^2), 0 for the zero vector: the cosine distance of the stored integer vectors.  1 byte per value
+ * (rows padded to 64 values in HBM) + 4 bytes per row for inv_r.
  * Rows get ids 0 ... n-1 in the order they were added; appending after a search is allowed, deletion is not.  Results per query sorted
  * by ascending distance, equal distances lower id first; with k > size the tail holds id -1 / distance +INFINITY.  1 <= k <= 1024,
  * 4 <= dim <= 4096 with dim % 4 == 0, any number of queries, up to 2^31 - 1 rows.  Results are bit-identical run to run, however queries
  * are split across calls, however rows were split across add calls, and across save / load.
  * The index lives on ctx's device and launches on ctx's stream (clip_amd_set_stream applies); free it before the ctx.  NULL on a
  * host-only ctx.  Bad arguments make a call return false (NULL) with a message on stderr, without launching anything.
- * File format (little-endian): "CLIPIDX1", u32 version (1), u32 dim, u32 dtype, u64 n, then n rows of dim stored values (unpadded). */
+ * File format (little-endian): "CLIPIDX1", u32 version (1), u32 dim, u32 dtype, u64 n, then n rows of dim stored values (unpadded;
+ * i8: 1-byte values, inv_r is not stored but recomputed on the device at load, so a loaded index searches and re-saves identically). */
 struct clip_amd_index;
 struct clip_amd_index * clip_amd_index_create(struct clip_ctx * ctx, int dim, int dtype);
 bool clip_amd_index_add(struct clip_amd_index * ix, const float * vecs, int64_t n);            /* host rows [n][dim], synchronous */
@@ -162,7 +169,7 @@ bool clip_amd_index_save(struct clip_amd_index * ix, const char * path);
 struct clip_amd_index * clip_amd_index_load(struct clip_ctx * ctx, const char * path);
 void clip_amd_index_free(struct clip_amd_index * ix);
 /* Average device time (microseconds, HIP events) of one clip_amd_index_search_device of n_queries seeded random queries against n seeded
- * random rows on the current device; < 0 on error.  Used by scripts/search_bench.py. */
+ * random rows on the current device (dtype as clip_amd_index_create: 0, 1 or 3); < 0 on error.  Used by scripts/search_bench.py. */
 float clip_amd_bench_search(int dtype, int64_t n, int dim, int n_queries, int k, int iters);
 
 /* ---- kernel-level test hooks (used by tests/ only; host pointers, synchronous) ----

@@ -1,11 +1,12 @@
 """Exact nearest-neighbour search (k_search.hip through clip_amd_bench_search) against the vendor yardstick on the same shapes:
 torch.mm (the score matrix written out) + torch.topk.
 
-    python scripts/search_bench.py [--quick] [--iters N]
+    python scripts/search_bench.py [--quick] [--iters N] [--dtypes f16,f32,i8] [--no-torch]
 
 Per configuration: microseconds per search, the gallery bytes read once per search divided by that time (GB/s), its fraction of the HBM
 rate measured here with a device-to-device copy, and the torch time.  Seeded random data (the torch gallery is its own seeded
-random tensor of the same shape and dtype: only the timing is compared, not the results).
+random tensor of the same shape and dtype: only the timing is compared, not the results).  i8 rows count N x Dpad (dim rounded up to
+64) bytes plus the 4-byte inverse norm per row; torch has no int8 mm + topk here, so their yardstick is the f16 one of the same shape.
 """
 import argparse
 import json
@@ -40,7 +41,7 @@ def hbm_rate():
 
 
 def torch_us(dtype, n, dim, nq, k, iters):
-    dt = torch.float16 if dtype == "f16" else torch.float32
+    dt = torch.float32 if dtype == "f32" else torch.float16
     g = torch.Generator(device="cuda").manual_seed(5)
     rows = torch.randn((n, dim), generator=g, device="cuda", dtype=dt)
     q = torch.randn((nq, dim), generator=g, device="cuda", dtype=dt)
@@ -59,9 +60,15 @@ def torch_us(dtype, n, dim, nq, k, iters):
     return us
 
 
-def configs(quick):
+def gallery_bytes(dtype, n, dim):
+    if dtype == "i8":
+        return n * ((dim + 63) // 64 * 64 + 4)
+    return n * ((dim + 31) // 32 * 32) * (2 if dtype == "f16" else 4)
+
+
+def configs(quick, dtypes):
     out = []
-    for dtype in ("f16", "f32"):
+    for dtype in dtypes:
         for nq in (1, 16, 64, 256, 1024):
             for k in (5, 100, 1024):
                 out.append((dtype, 1 << 20, 512, nq, k))
@@ -69,7 +76,7 @@ def configs(quick):
             for dim in (512, 768, 1024):
                 out.append((dtype, n, dim, 16, 100))
     if quick:
-        out = [c for c in out if c[3] in (1, 64) and c[4] in (5, 100) and c[1] == 1 << 20] + [("f16", 1 << 22, 512, 16, 100)]
+        out = [c for c in out if c[3] in (1, 64) and c[4] in (5, 100) and c[1] == 1 << 20] + [(d, 1 << 22, 512, 16, 100) for d in dtypes]
     return out
 
 
@@ -78,15 +85,16 @@ def main():
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--dtypes", default="f16,f32,i8")
     a = ap.parse_args()
     torch.cuda.init()
     rate = hbm_rate()
     print("HBM copy rate: %.0f GB/s" % rate)
     print("%-4s %8s %5s %5s %5s %10s %8s %6s %10s %7s" % ("dt", "N", "dim", "nq", "k", "us", "GB/s", "frac", "torch_us", "speedup"))
     rows = []
-    for dtype, n, dim, nq, k in configs(a.quick):
+    for dtype, n, dim, nq, k in configs(a.quick, a.dtypes.split(",")):
         us = clip_cpp_amd.bench_search(dtype, n, dim, nq, k, a.iters)
-        gb = n * ((dim + 31) // 32 * 32) * (2 if dtype == "f16" else 4) / 1e9
+        gb = gallery_bytes(dtype, n, dim) / 1e9
         tu = -1.0 if a.no_torch else torch_us(dtype, n, dim, nq, k, a.iters)
         r = dict(dtype=dtype, n=n, dim=dim, nq=nq, k=k, us=round(us, 1), gbs=round(gb / (us * 1e-6), 0) if us > 0 else None,
                  frac=round(gb / (us * 1e-6) / rate, 3) if us > 0 else None, torch_us=round(tu, 1))
