@@ -71,7 +71,7 @@ AMD_SYMBOLS = [
     "clip_amd_test_attention_ex", "clip_amd_bench_attention",
     "clip_amd_index_create", "clip_amd_index_add", "clip_amd_index_add_device", "clip_amd_index_size", "clip_amd_index_dim",
     "clip_amd_index_search", "clip_amd_index_search_device", "clip_amd_index_save", "clip_amd_index_load", "clip_amd_index_free",
-    "clip_amd_bench_search",
+    "clip_amd_bench_search", "clip_amd_index_range_search", "clip_amd_index_pairs", "clip_amd_bench_range",
 ]
 
 _lib = None
@@ -215,6 +215,12 @@ def lib():
     L.clip_amd_index_free.argtypes = [vp]
     L.clip_amd_bench_search.restype = C.c_float
     L.clip_amd_bench_search.argtypes = [i32, i64, i32, i32, i32, i32]
+    L.clip_amd_index_range_search.restype = i64
+    L.clip_amd_index_range_search.argtypes = [vp, f32p, i32, C.c_float, i64p, f32p, i64p, i64]
+    L.clip_amd_index_pairs.restype = i64
+    L.clip_amd_index_pairs.argtypes = [vp, C.c_float, i64p, f32p, i64p, i64]
+    L.clip_amd_bench_range.restype = C.c_float
+    L.clip_amd_bench_range.argtypes = [i32, i64, i32, i32, C.c_float, i32]
     _lib = L
     return L
 
@@ -507,7 +513,8 @@ class Clip:
 class Index:
     """Exact cosine nearest-neighbour index on the GPU of a `Clip` (clip_amd_index_*, include/clip_amd.h): rows are L2-normalised and
     stored in f16 (default) or f32; search returns (distances f32 [nq, k], ids int64 [nq, k]) sorted by ascending 1 - cosine, equal
-    distances lower id first, -1 / +inf past the index size.  Keep the `Clip` alive while the index is in use.
+    distances lower id first, -1 / +inf past the index size.  range_search (every row within a radius of each query) and pairs (every pair
+    of rows within a radius: near-duplicates) report the same distances, bit for bit.  Keep the `Clip` alive while the index is in use.
 
     "i8" (dtype code 3) stores each row as int8, a quarter of f32's bytes: in f32, amax = max |x|, q = rint((x / amax) * 127) (half to
     even; numpy: np.rint((x / amax).astype(np.float32) * np.float32(127))), no L2 normalisation first (the mapping is scale-invariant).
@@ -564,6 +571,39 @@ class Index:
             raise RuntimeError("clip_amd_index_search failed (see stderr)")
         return dist, ids
 
+    def range_search(self, queries, radius):
+        """Every stored row within `radius` of each query (distance <= radius in f32, the distance `search` reports): (lims int64 [nq + 1],
+        distances f32 [total], ids int64 [total]); query q's results are [lims[q], lims[q + 1]), nearest first, equal distances lower id
+        first."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        nq = q.shape[0]
+        call = lambda lims, d, i, cap: lib().clip_amd_index_range_search(self._live(), _fp(q), nq, float(radius), lims, d, i, cap)
+        return self._join(call, nq + 1, 64 * nq + 1024, "clip_amd_index_range_search")
+
+    def pairs(self, radius):
+        """Every pair of rows i < j at distance <= radius, d(i, j) being what `search` reports for row j when queried with the vector added
+        as row i: (i int64 [P], j int64 [P], distances f32 [P]), grouped by ascending i, within one i nearest first, equal distances lower j
+        first."""
+        n = len(self)
+        call = lambda lims, d, i, cap: lib().clip_amd_index_pairs(self._live(), float(radius), lims, d, i, cap)
+        lims, dist, j = self._join(call, n + 1, 4 * n + 1024, "clip_amd_index_pairs")
+        return np.repeat(np.arange(n, dtype=np.int64), np.diff(lims)), j, dist
+
+    @staticmethod
+    def _join(call, n_lims, guess, name):
+        """(lims, distances, ids) of a range-search / pairs call: a guessed capacity first, the exact total again when it did not fit"""
+        lims = np.zeros(n_lims, dtype=np.int64)
+        cap = guess
+        while True:
+            dist = np.empty(cap, dtype=np.float32)
+            ids = np.empty(cap, dtype=np.int64)
+            total = call(lims.ctypes.data_as(C.POINTER(C.c_int64)), _fp(dist), ids.ctypes.data_as(C.POINTER(C.c_int64)), cap)
+            if total < 0:
+                raise RuntimeError("%s failed (see stderr)" % name)
+            if total <= cap:
+                return lims, dist[:total], ids[:total]
+            cap = int(total)
+
     def search_device(self, d_queries, n_queries, k, d_distances, d_ids):
         """Device pointers (ints): queries [n, dim] f32 -> distances [n, k] f32, ids [n, k] int64; asynchronous on the context's stream."""
         if not lib().clip_amd_index_search_device(self._live(), C.c_void_p(d_queries), int(n_queries), int(k), C.c_void_p(d_distances),
@@ -594,6 +634,12 @@ class Index:
 def bench_search(dtype, n, dim, n_queries, k, iters=10):
     """Microseconds per clip_amd_index_search_device on seeded random data (clip_amd_bench_search); < 0 on error."""
     return float(lib().clip_amd_bench_search(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(k), int(iters)))
+
+
+def bench_range(dtype, n, dim, n_queries, radius, iters=10):
+    """Microseconds per clip_amd_index_range_search of n_queries queries, or per clip_amd_index_pairs when n_queries == 0, on seeded random
+    rows with planted near-duplicates (clip_amd_bench_range); < 0 on error."""
+    return float(lib().clip_amd_bench_range(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), float(radius), int(iters)))
 
 
 def gguf_inspect(path):

@@ -29,37 +29,20 @@
 //   search_merge_kernel      pairwise merge of two sorted k-lists per query keeping the best k (rank by binary search: a strict total order
 //                            — distance ascending, id ascending — so each element's output slot is unique); log2(chunks) launches.
 //   search_finish_kernel     ids widened to int64; empty slots -> id -1, distance +inf.
-// Plain launches on the caller's stream, no LDS past 64 KB but the sort buffers of k > 512, no scratch.
+// Plain launches on the caller's stream, no LDS past 64 KB but the sort buffers of k > 512, no scratch.  The score chain (ld_step, mfma_step,
+// scan_distance), the candidate order and wave_sort live in search_common.h, shared with k_join.hip (range search / pairs).
 
 #include <cfloat>
 #include <climits>
 
-#include "kernels.h"
+#include "search_common.h"
 
 namespace clipamd {
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef int i4 __attribute__((ext_vector_type(4)));
-
-// accumulator of the scan per stored dtype: f32 for fp16 / f32 rows, the exact i32 dot for i8 rows
-template <typename T> struct ScanAcc { typedef f4 type; };
-template <> struct ScanAcc<int8_t> { typedef i4 type; };
-
-struct Cand {
-    float s;
-    int id;
-};
-
 constexpr int SCAN_THREADS = 256;
 constexpr int ROWS_PER_ITER = 64;     // 4 waves x 16 rows
-
-// strict total order of candidates: smaller distance first, then lower id (empty slots: +inf / INT_MAX, last).  Candidates carry the
-// distance 1 - score (f32) itself, so "equal distances lower id first" holds for the distances the caller sees.
-__device__ __forceinline__ bool better(float da, int ia, float db, int ib) { return da < db || (da == db && ia < ib); }
 
 template <typename T>
 __global__ void __launch_bounds__(256) search_normalize_kernel(const float * __restrict__ src, int64_t n_src, int64_t n_rows, int dim, int Dpad,
@@ -162,29 +145,6 @@ struct ScanParams {
     const float * qinv;    // i8: [nq_pad] query inverse norms
 };
 
-// bitonic sort of a wave's LDS buffer (P pairs, better first).  The buffer is private to the wave and LDS operations of one wave are
-// processed in order, so a wave-level barrier (compiler ordering) separates the stages.
-__device__ void wave_sort(float * bs, int * bi, int P, int lane) {
-    for (int kk = 2; kk <= P; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int t = lane; t < (P >> 1); t += 64) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i + j;   // (j is a power of two)
-                const float sa = bs[i], sb = bs[l];
-                const int ia = bi[i], ib = bi[l];
-                const bool first_half = (i & kk) == 0;
-                const bool sw = first_half ? better(sb, ib, sa, ia) : better(sa, ia, sb, ib);
-                if (sw) {
-                    bs[i] = sb; bi[i] = ib;
-                    bs[l] = sa; bi[l] = ia;
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-    }
-}
-
 // keep the best min(k, cnt) of a query's candidates (sorted, at the head of its buffer); returns the new count.  `final`: write all k
 // slots (empty ones as +inf / INT_MAX) so the merge reads k sorted entries.
 __device__ int wave_select(Cand * buf, int cnt, int k, int P, bool final, float * bs, int * bi, int lane) {
@@ -200,29 +160,6 @@ __device__ int wave_select(Cand * buf, int cnt, int k, int P, bool final, float 
     const int keep = final ? k : (cnt < k ? cnt : k);
     for (int i = lane; i < keep; i += 64) buf[i] = Cand{bs[i], bi[i]};
     return cnt < k ? cnt : k;
-}
-
-// One k-step of a row (or query) for lane group fgrp: fp16 — 32 k per step, the lane's 8 consecutive k (16 bytes); f32 — 16 k per step,
-// the lane's 4 consecutive k, consumed by four MFMAs (MFMA s multiplies k = 4 fgrp + s on both operands: a permuted but fixed order);
-// i8 — 64 k per step, the lane's 16 consecutive k (16 bytes), one MFMA (both operands take the same lane -> k map, so the dot is the same
-// whatever order the instruction gives the 16 bytes).
-template <typename T>
-__device__ __forceinline__ u32x4 ld_step(const T * row, int kk, int fgrp) {
-    return *(const u32x4 *)(row + kk * (64 / (int)sizeof(T)) + fgrp * (16 / (int)sizeof(T)));
-}
-
-template <typename T>
-__device__ __forceinline__ typename ScanAcc<T>::type mfma_step(u32x4 a, u32x4 b, typename ScanAcc<T>::type acc) {
-    if constexpr (sizeof(T) == 1) {
-        return __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i4, a), __builtin_bit_cast(i4, b), acc, 0, 0, 0);
-    } else if constexpr (sizeof(T) == 2) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), acc, 0, 0, 0);
-    } else {
-        const f4 af = __builtin_bit_cast(f4, a), bf = __builtin_bit_cast(f4, b);
-#pragma unroll
-        for (int s = 0; s < 4; s++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s], bf[s], acc, 0, 0, 0);
-        return acc;
-    }
 }
 
 template <typename T, int QT>
@@ -291,9 +228,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) search_scan_kernel(const ScanPar
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     const int64_t row = r0 + fgrp * 4 + r;
-                    float d;
-                    if constexpr (sizeof(T) == 1) d = 1.0f - (float)acc[j][r] * qinv * rinv[r];
-                    else d = 1.0f - acc[j][r];
+                    const float d = scan_distance(acc[j][r], qinv, rinv[r]);
                     if (row < hi && d < t) {
                         const int slot = atomicAdd(&cnt[ql], 1);
                         buf[slot] = Cand{d, (int)row};

@@ -303,4 +303,19 @@ void launch_search_merge(const void * in, int64_t in_stride, int n_in, void * ou
 void launch_search_finish(const void * in, int64_t in_stride, int nq, int k, float * dist, int64_t * ids, hipStream_t stream);
 void launch_search_fill_random(float * x, int64_t n, uint64_t seed, hipStream_t stream);
 
+// Range search and pairs (k_join.hip): every (query, row) at distance <= radius, scored exactly as launch_search_scan scores it (rows and
+// queries in the stored form above).  pairs: the queries are the rows themselves (q = rows, qinv = rinv, nq = n) and only row > query
+// counts.  count [nq] and *total accumulate (zero them first); hit slot s < hit_cap of the hit list receives (distance f32, row i32,
+// query i32), JOIN_HIT_BYTES each.  Scatter: hits -> (distance, row) pairs at offs[q] + cursor[q]++ (cursor [nq] zeroed first).  Sort:
+// every segment [offs[s], offs[s + 1]) of buf by distance, then row (tmp: a second buffer of the same size; longest: the longest
+// segment); returns the buffer that holds the result.  Finish: pairs -> distances f32 and int64 ids.  Plant: benchmark rows, every 64th
+// row of x [rows][dim] a small perturbation of the row 37 before it.
+constexpr int JOIN_HIT_BYTES = 12;
+bool launch_join(const void * rows, const float * rinv, int64_t n, const void * q, const float * qinv, int64_t nq, int Dpad, int dtype, bool pairs,
+                 float radius, int * count, unsigned long long * total, void * hits, int64_t hit_cap, hipStream_t stream);
+void launch_join_scatter(const void * hits, int64_t total, const int64_t * offs, int * cursor, void * out, hipStream_t stream);
+void * launch_join_sort(void * buf, void * tmp, const int64_t * offs, int64_t nseg, int64_t total, int64_t longest, hipStream_t stream);
+void launch_join_finish(const void * in, int64_t total, float * dist, int64_t * ids, hipStream_t stream);
+void launch_join_plant(float * x, int64_t rows, int dim, uint64_t seed, hipStream_t stream);
+
 }  // namespace clipamd

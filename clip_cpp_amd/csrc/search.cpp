@@ -1,7 +1,9 @@
 // search.cpp — the exact nearest-neighbour index of include/clip_amd.h (clip_amd_index_*): device-resident rows, argument checking,
-// query chunking, the scan -> merge tree -> finish launch sequence of k_search.hip, and the CLIPIDX1 file format.
+// query chunking, the scan -> merge tree -> finish launch sequence of k_search.hip, the count -> lims -> scatter -> sort -> finish sequence of
+// range search and pairs (k_join.hip), and the CLIPIDX1 file format.
 // Replaces the usearch index of the reference's examples/image-search (build.cpp / search.cpp) with an exact search on the GPU.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -29,6 +31,12 @@ struct clip_amd_index {
     void * cand = nullptr;  size_t cand_bytes = 0;      // [n_chunks][nq][C] candidates
     void * mbuf[2] = {nullptr, nullptr}; size_t mbuf_bytes = 0;   // merge levels
     void * outs = nullptr;  size_t outs_bytes = 0;      // distances + ids of the host search form
+    // range search / pairs
+    void * jcnt = nullptr;  size_t jcnt_bytes = 0;      // total (u64) + per-segment counts, reused as the scatter cursors
+    void * hits = nullptr;  size_t hits_bytes = 0;      // hit list
+    void * joffs = nullptr; size_t joffs_bytes = 0;     // segment offsets (= lims) on the device
+    void * jsort = nullptr; size_t jsort_bytes = 0;     // two (distance, id) buffers of the results
+    void * jouts = nullptr; size_t jouts_bytes = 0;     // ids (int64) + distances of the results
 };
 
 namespace {
@@ -39,6 +47,7 @@ constexpr int MAX_K = 1024;
 constexpr int64_t MAX_ROWS = 2147483647;
 constexpr size_t CAND_BUDGET = (size_t)512 << 20;       // bytes of candidate workspace per scan launch
 constexpr int64_t HOST_CHUNK_ROWS = 65536;              // rows per staging copy (add, save, load)
+constexpr int64_t JOIN_HIT_BUDGET = (int64_t)1 << 21;    // hits the first scoring pass keeps (24 MB); more only when the caller's capacity asks
 
 hipStream_t stream_of(const clip_amd_index * ix) { return ix->ctx ? ix->ctx->stream : nullptr; }
 
@@ -112,7 +121,8 @@ void prepare_rows(const clip_amd_index * ix, const float * src, int64_t n_src, i
 void free_index(clip_amd_index * ix) {
     (void)hipSetDevice(ix->device);
     (void)hipStreamSynchronize(stream_of(ix));
-    for (void * p : {ix->rows, (void *)ix->rinv, ix->stage, ix->qbuf, ix->qinv, ix->cand, ix->mbuf[0], ix->mbuf[1], ix->outs})
+    for (void * p : {ix->rows, (void *)ix->rinv, ix->stage, ix->qbuf, ix->qinv, ix->cand, ix->mbuf[0], ix->mbuf[1], ix->outs, ix->jcnt, ix->hits,
+                     ix->joffs, ix->jsort, ix->jouts})
         if (p) (void)hipFree(p);
     delete ix;
 }
@@ -178,6 +188,89 @@ bool check_search_args(const clip_amd_index * ix, const void * q, int nq, int k,
     if (nq < 0) { fprintf(stderr, "%s: n_queries %d < 0\n", fn, nq); return false; }
     if (k < 1 || k > MAX_K) { fprintf(stderr, "%s: k = %d outside 1 ... %d\n", fn, k, MAX_K); return false; }
     if (nq > 0 && (!q || !dist || !ids)) { fprintf(stderr, "%s: NULL queries or result pointer\n", fn); return false; }
+    return true;
+}
+
+// Range search (d_q: nq f32 queries on the device) or pairs (d_q NULL, the rows against the rows, row > query): one scoring pass counts
+// every segment and keeps up to min(capacity, JOIN_HIT_BUDGET) hits; a second pass runs only when the total fits the caller's capacity
+// but not that list.  lims [segments + 1] is always written; when total <= capacity the hits are placed in their segments, sorted and
+// copied out.  Returns the total or -1.
+int64_t join_impl(clip_amd_index * ix, const float * d_q, int nq, bool pairs, float radius, int64_t * lims, float * distances, int64_t * ids,
+                  int64_t capacity, const char * fn) {
+    hipStream_t st = stream_of(ix);
+    const int64_t nseg = pairs ? ix->n : nq;
+    const void * q = ix->rows;
+    const float * qinv = ix->rinv;
+    if (!pairs && nq > 0) {
+        const int64_t nq_pad = (nq + 15) / 16 * 16;
+        if (!ensure(ix, ix->qbuf, ix->qbuf_bytes, (size_t)nq_pad * ix->Dpad * ix->es)) return -1;
+        if (ix->dtype == SEARCH_I8 && !ensure(ix, ix->qinv, ix->qinv_bytes, (size_t)nq_pad * sizeof(float))) return -1;
+        prepare_rows(ix, d_q, nq, nq_pad, ix->qbuf, (float *)ix->qinv);
+        q = ix->qbuf;
+        qinv = (const float *)ix->qinv;
+    }
+    if (!ensure(ix, ix->jcnt, ix->jcnt_bytes, 8 + (size_t)nseg * 4)) return -1;
+    unsigned long long * d_total = (unsigned long long *)ix->jcnt;
+    int * d_count = (int *)((char *)ix->jcnt + 8);
+    std::vector<int> cnt((size_t)nseg);
+    int64_t hit_cap = std::min(capacity, JOIN_HIT_BUDGET);
+    unsigned long long total = 0;
+    for (;;) {
+        if (!ensure(ix, ix->hits, ix->hits_bytes, (size_t)std::max<int64_t>(hit_cap, 1) * JOIN_HIT_BYTES)) return -1;
+        (void)hipMemsetAsync(ix->jcnt, 0, 8 + (size_t)nseg * 4, st);
+        if (ix->n > 0 && nseg > 0 &&
+            !launch_join(ix->rows, ix->rinv, ix->n, q, qinv, pairs ? ix->n : nq, ix->Dpad, ix->dtype, pairs, radius, d_count, d_total, ix->hits,
+                         hit_cap, st)) {
+            fprintf(stderr, "%s: join launch failed\n", fn);
+            return -1;
+        }
+        (void)hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st);
+        if (nseg > 0) (void)hipMemcpyAsync(cnt.data(), d_count, (size_t)nseg * 4, hipMemcpyDeviceToHost, st);
+        if (hipStreamSynchronize(st) != hipSuccess) {
+            fprintf(stderr, "%s: %s\n", fn, hipGetErrorString(hipGetLastError()));
+            return -1;
+        }
+        if ((int64_t)total <= hit_cap || (int64_t)total > capacity) break;
+        hit_cap = (int64_t)total;           // the list of the first pass was full: score again into one that holds every hit
+    }
+    lims[0] = 0;
+    int64_t longest = 0;
+    for (int64_t s = 0; s < nseg; s++) {
+        lims[s + 1] = lims[s] + cnt[(size_t)s];
+        longest = std::max<int64_t>(longest, cnt[(size_t)s]);
+    }
+    const int64_t tot = lims[nseg];
+    if (tot > capacity || tot == 0) return tot;
+    if (!ensure(ix, ix->joffs, ix->joffs_bytes, (size_t)(nseg + 1) * 8) || !ensure(ix, ix->jsort, ix->jsort_bytes, (size_t)tot * 16) ||
+        !ensure(ix, ix->jouts, ix->jouts_bytes, (size_t)tot * 12))
+        return -1;
+    (void)hipMemcpyAsync(ix->joffs, lims, (size_t)(nseg + 1) * 8, hipMemcpyHostToDevice, st);
+    (void)hipMemsetAsync(d_count, 0, (size_t)nseg * 4, st);
+    launch_join_scatter(ix->hits, tot, (const int64_t *)ix->joffs, d_count, ix->jsort, st);
+    const void * sorted = launch_join_sort(ix->jsort, (char *)ix->jsort + (size_t)tot * 8, (const int64_t *)ix->joffs, nseg, tot, longest, st);
+    int64_t * d_ids = (int64_t *)ix->jouts;
+    float * d_dist = (float *)((char *)ix->jouts + (size_t)tot * 8);
+    launch_join_finish(sorted, tot, d_dist, d_ids, st);
+    if (hipGetLastError() != hipSuccess) {
+        fprintf(stderr, "%s: launch failed\n", fn);
+        return -1;
+    }
+    (void)hipMemcpyAsync(distances, d_dist, (size_t)tot * 4, hipMemcpyDeviceToHost, st);
+    (void)hipMemcpyAsync(ids, d_ids, (size_t)tot * 8, hipMemcpyDeviceToHost, st);
+    if (hipStreamSynchronize(st) != hipSuccess) {
+        fprintf(stderr, "%s: %s\n", fn, hipGetErrorString(hipGetLastError()));
+        return -1;
+    }
+    return tot;
+}
+
+bool check_join_args(const clip_amd_index * ix, float radius, const int64_t * lims, const void * dist, const void * ids, int64_t capacity,
+                     const char * fn) {
+    if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+    if (!lims) { fprintf(stderr, "%s: lims is NULL\n", fn); return false; }
+    if (std::isnan(radius)) { fprintf(stderr, "%s: radius is NaN\n", fn); return false; }
+    if (capacity < 0) { fprintf(stderr, "%s: capacity %lld < 0\n", fn, (long long)capacity); return false; }
+    if (capacity > 0 && (!dist || !ids)) { fprintf(stderr, "%s: NULL result pointer with capacity %lld\n", fn, (long long)capacity); return false; }
     return true;
 }
 
@@ -350,6 +443,28 @@ void clip_amd_index_free(struct clip_amd_index * ix) {
     if (ix) free_index(ix);
 }
 
+int64_t clip_amd_index_range_search(struct clip_amd_index * ix, const float * queries, int n_queries, float radius, int64_t * lims, float * distances,
+                                    int64_t * ids, int64_t capacity) try {
+    const char * fn = "clip_amd_index_range_search";
+    if (!check_join_args(ix, radius, lims, distances, ids, capacity, fn)) return -1;
+    if (n_queries < 0) { fprintf(stderr, "%s: n_queries %d < 0\n", fn, n_queries); return -1; }
+    if (n_queries > 0 && !queries) { fprintf(stderr, "%s: NULL queries\n", fn); return -1; }
+    lims[0] = 0;
+    if (n_queries == 0) return 0;
+    (void)hipSetDevice(ix->device);
+    const size_t qb = (size_t)n_queries * ix->dim * 4;
+    if (!ensure(ix, ix->stage, ix->stage_bytes, std::max(qb, ix->stage_bytes))) return -1;
+    (void)hipMemcpyAsync(ix->stage, queries, qb, hipMemcpyHostToDevice, stream_of(ix));
+    return join_impl(ix, (const float *)ix->stage, n_queries, false, radius, lims, distances, ids, capacity, fn);
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_index_range_search: %s\n", e.what()); return -1; }
+
+int64_t clip_amd_index_pairs(struct clip_amd_index * ix, float radius, int64_t * lims, float * distances, int64_t * ids, int64_t capacity) try {
+    const char * fn = "clip_amd_index_pairs";
+    if (!check_join_args(ix, radius, lims, distances, ids, capacity, fn)) return -1;
+    (void)hipSetDevice(ix->device);
+    return join_impl(ix, nullptr, 0, true, radius, lims, distances, ids, capacity, fn);
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_index_pairs: %s\n", e.what()); return -1; }
+
 float clip_amd_bench_search(int dtype, int64_t n, int dim, int n_queries, int k, int iters) try {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return -1.f; }
@@ -394,5 +509,48 @@ float clip_amd_bench_search(int dtype, int64_t n, int dim, int n_queries, int k,
     free_index(ix);
     return us;
 } catch (const std::exception & e) { fprintf(stderr, "clip_amd_bench_search: %s\n", e.what()); return -4.f; }
+
+float clip_amd_bench_range(int dtype, int64_t n, int dim, int n_queries, float radius, int iters) try {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return -1.f; }
+    if (!valid_dtype(dtype) || !valid_dim(dim) || n < 1 || n > MAX_ROWS || n_queries < 0 || std::isnan(radius) || iters < 1) return -3.f;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    clip_amd_index * ix = make_index(nullptr, dev, dim, dtype);
+    const char * fn = "clip_amd_bench_range";
+    const bool pairs = n_queries == 0;
+    float * src = nullptr;
+    const int64_t piece = HOST_CHUNK_ROWS;                // a multiple of 64: a planted row and its original share a piece
+    float us = -4.f;
+    std::vector<int64_t> lims((size_t)(pairs ? n : n_queries) + 1);
+    if (hipMalloc(&src, (size_t)std::max<int64_t>(piece, n_queries) * dim * 4) == hipSuccess && reserve_rows(ix, n)) {
+        bool ok = true;
+        for (int64_t r0 = 0; ok && r0 < n; r0 += piece) {
+            const int64_t m = std::min(piece, n - r0);
+            launch_search_fill_random(src, m * dim, 0x5EEDull + (uint64_t)r0 * dim, nullptr);
+            launch_join_plant(src, m, dim, 0xD0Bull + (uint64_t)r0, nullptr);
+            ok = add_device_impl(ix, src, m);
+        }
+        // queries: the gallery's first rows before planting (each finds itself, some a planted copy as well)
+        launch_search_fill_random(src, (int64_t)n_queries * dim, 0x5EEDull, nullptr);
+        ok = ok && hipDeviceSynchronize() == hipSuccess;
+        int64_t tot = ok ? join_impl(ix, pairs ? nullptr : src, n_queries, pairs, radius, lims.data(), nullptr, nullptr, 0, fn) : -1;
+        std::vector<float> dist((size_t)std::max<int64_t>(tot, 1));
+        std::vector<int64_t> ids(dist.size());
+        if (tot >= 0) tot = join_impl(ix, pairs ? nullptr : src, n_queries, pairs, radius, lims.data(), dist.data(), ids.data(), tot, fn);
+        if (tot >= 0) {
+            const auto t0 = std::chrono::steady_clock::now();
+            for (int i = 0; tot >= 0 && i < iters; i++)
+                tot = join_impl(ix, pairs ? nullptr : src, n_queries, pairs, radius, lims.data(), dist.data(), ids.data(), (int64_t)dist.size(), fn);
+            const auto t1 = std::chrono::steady_clock::now();
+            if (tot >= 0) us = (float)(std::chrono::duration<double, std::micro>(t1 - t0).count() / iters);
+        }
+    }
+    (void)hipGetLastError();
+    (void)hipDeviceSynchronize();
+    if (src) (void)hipFree(src);
+    free_index(ix);
+    return us;
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_bench_range: %s\n", e.what()); return -4.f; }
 
 }  // extern "C"

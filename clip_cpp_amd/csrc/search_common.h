@@ -1,0 +1,87 @@
+// search_common.h — the score chain of the exact index, shared by k_search.hip (top-k scan) and k_join.hip (range search / pairs).
+//
+// A (query, row) score is bit-identical in both files because both take it from here: the same 16-byte lane loads (ld_step), the same
+// MFMA per stored dtype in the same k order (mfma_step), the same f32 distance expression (scan_distance), with the gallery row as the
+// MFMA "A" operand and the query as "B", one accumulator per pair starting at zero.  Candidates are ordered by the strict total order
+// `better` (distance ascending, then id ascending); wave_sort sorts a wave's LDS buffer in that order.
+#pragma once
+
+#include <climits>
+
+#include "kernels.h"
+
+namespace clipamd {
+
+namespace {
+
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef float f4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef int i4 __attribute__((ext_vector_type(4)));
+
+// accumulator of the scan per stored dtype: f32 for fp16 / f32 rows, the exact i32 dot for i8 rows
+template <typename T> struct ScanAcc { typedef f4 type; };
+template <> struct ScanAcc<int8_t> { typedef i4 type; };
+
+struct Cand {
+    float s;
+    int id;
+};
+
+// strict total order of candidates: smaller distance first, then lower id (empty slots: +inf / INT_MAX, last).  Candidates carry the
+// distance 1 - score (f32) itself, so "equal distances lower id first" holds for the distances the caller sees.
+__device__ __forceinline__ bool better(float da, int ia, float db, int ib) { return da < db || (da == db && ia < ib); }
+
+// bitonic sort of a wave's LDS buffer (P pairs, P a power of two >= 2, better first).  The buffer is private to the wave and LDS operations
+// of one wave are processed in order, so a wave-level barrier (compiler ordering) separates the stages.
+__device__ void wave_sort(float * bs, int * bi, int P, int lane) {
+    for (int kk = 2; kk <= P; kk <<= 1) {
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            for (int t = lane; t < (P >> 1); t += 64) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i + j;   // (j is a power of two)
+                const float sa = bs[i], sb = bs[l];
+                const int ia = bi[i], ib = bi[l];
+                const bool first_half = (i & kk) == 0;
+                const bool sw = first_half ? better(sb, ib, sa, ia) : better(sa, ia, sb, ib);
+                if (sw) {
+                    bs[i] = sb; bi[i] = ib;
+                    bs[l] = sa; bi[l] = ia;
+                }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+    }
+}
+
+// One k-step of a row (or query) for lane group fgrp: fp16 — 32 k per step, the lane's 8 consecutive k (16 bytes); f32 — 16 k per step,
+// the lane's 4 consecutive k, consumed by four MFMAs (MFMA s multiplies k = 4 fgrp + s on both operands: a permuted but fixed order);
+// i8 — 64 k per step, the lane's 16 consecutive k (16 bytes), one MFMA (both operands take the same lane -> k map, so the dot is the same
+// whatever order the instruction gives the 16 bytes).  Every dtype: a k-step is 64 bytes of a row, lane group fgrp takes bytes 16 fgrp ...
+template <typename T>
+__device__ __forceinline__ u32x4 ld_step(const T * row, int kk, int fgrp) {
+    return *(const u32x4 *)(row + kk * (64 / (int)sizeof(T)) + fgrp * (16 / (int)sizeof(T)));
+}
+
+template <typename T>
+__device__ __forceinline__ typename ScanAcc<T>::type mfma_step(u32x4 a, u32x4 b, typename ScanAcc<T>::type acc) {
+    if constexpr (sizeof(T) == 1) {
+        return __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i4, a), __builtin_bit_cast(i4, b), acc, 0, 0, 0);
+    } else if constexpr (sizeof(T) == 2) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, a), __builtin_bit_cast(h8, b), acc, 0, 0, 0);
+    } else {
+        const f4 af = __builtin_bit_cast(f4, a), bf = __builtin_bit_cast(f4, b);
+#pragma unroll
+        for (int s = 0; s < 4; s++) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s], bf[s], acc, 0, 0, 0);
+        return acc;
+    }
+}
+
+// distance of one accumulator entry: fp16 / f32 1 - score (qinv, rinv unused); i8 1 - (float)dot * inv_q * inv_r
+__device__ __forceinline__ float scan_distance(float acc, float, float) { return 1.0f - acc; }
+__device__ __forceinline__ float scan_distance(int dot, float qinv, float rinv) { return 1.0f - (float)dot * qinv * rinv; }
+
+}  // namespace
+
+}  // namespace clipamd

@@ -2,11 +2,15 @@
 build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.Index`) instead of usearch's approximate one.
 
     python -m clip_cpp_amd.image_search build  [-m MODEL] [-v N] [-t N] [--db DIR] [--dtype f16|f32|i8] dir [more dirs]
-    python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N] [--db DIR] <search text or /path/to/query/image>
+    python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N | -d R] [--db DIR] <search text or /path/to/query/image>
+    python -m clip_cpp_amd.image_search dedup  [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R]
 
 `build` writes DIR/images.index (the CLIPIDX1 file of clip_amd_index_save) and DIR/images.paths (the reference's layout: the model path
 on the first line, then one image path per id).  `search` prints the reference's output: "search results:" / "distance path" at
-verbosity > 0, then "  %f %s" per hit, nearest first.
+verbosity > 0, then "  %f %s" per hit, nearest first: the -n nearest, or with -d R every indexed image within distance R.  `dedup` prints
+the groups of near-duplicate images (connected components of the pairs within distance R, clip_amd_index_pairs): "duplicate groups:" at
+verbosity > 0, then per group, in order of its lowest id, "  %f %s" per member in id order (the distance to its nearest other member),
+groups separated by a blank line, and "main: %d groups, %d images".
 """
 import ctypes as C
 import os
@@ -20,6 +24,7 @@ INDEX_FILE = "images.index"
 PATHS_FILE = "images.paths"
 BATCH = 64          # images decoded and encoded per call
 MAX_K = 1024
+DEDUP_RADIUS = 0.05
 
 
 def is_image_file_extension(path):
@@ -42,32 +47,44 @@ def _err(msg):
     print(msg, file=sys.stderr, flush=True)
 
 
-def _parse(argv, build):
-    """Reference-style option parsing (examples/image-search/{build,search}.cpp my_app_params_parse)."""
-    p = dict(threads=4, verbose=1, db=".", dtype="f16", results=5, model="../models/ggml-model-f16.bin" if build else "", rest=[])
+def _parse(argv, build, dedup=False):
+    """Reference-style option parsing (examples/image-search/{build,search}.cpp my_app_params_parse); `dedup` takes no positional
+    arguments."""
+    p = dict(threads=4, verbose=1, db=".", dtype="f16", results=5, max_distance=DEDUP_RADIUS if dedup else None,
+             model="../models/ggml-model-f16.bin" if build else "", rest=[])
+    seen = set()
     i = 0
     while i < len(argv):
         a = argv[i]
-        takes = {"-m": "model", "--model": "model", "-t": "threads", "--threads": "threads", "-v": "verbose", "--verbose": "verbose",
-                 "--db": "db"}
+        takes = {"-m": "model", "--model": "model", "-v": "verbose", "--verbose": "verbose", "--db": "db"}
+        if not dedup:
+            takes.update({"-t": "threads", "--threads": "threads"})
         if build:
             takes["--dtype"] = "dtype"
         else:
-            takes.update({"-n": "results", "--results": "results"})
+            takes.update({"-d": "max_distance", "--max-distance": "max_distance"})
+            if not dedup:
+                takes.update({"-n": "results", "--results": "results"})
         if a in takes:
             i += 1
             if i >= len(argv):
                 return None
             key = takes[a]
+            seen.add(key)
             try:
-                p[key] = int(argv[i]) if key in ("threads", "verbose", "results") else argv[i]
+                p[key] = int(argv[i]) if key in ("threads", "verbose", "results") else float(argv[i]) if key == "max_distance" else argv[i]
             except ValueError:
                 return None
+            if key == "max_distance" and p[key] != p[key]:      # NaN
+                return None
         elif a in ("-h", "--help"):
-            _help(build, p)
+            _help(build, p, dedup)
             sys.exit(0)
         elif a.startswith("-"):
             print("main: unrecognized argument: %s" % a)
+            return None
+        elif dedup:
+            print("main: unexpected argument: %s" % a)
             return None
         elif build:
             p["rest"].append(a)
@@ -75,13 +92,27 @@ def _parse(argv, build):
             p["rest"] = argv[i:]     # the query: everything from here on
             break
         i += 1
-    if not p["rest"] or (build and p["dtype"] not in ("f16", "f32", "i8")):
+    if (not p["rest"] and not dedup) or (build and p["dtype"] not in ("f16", "f32", "i8")):
+        return None
+    if {"results", "max_distance"} <= seen:
+        print("main: -n and -d cannot be combined: -n N prints the N nearest, -d R every image within R")
         return None
     return p
 
 
-def _help(build, p):
-    if build:
+def _help(build, p, dedup=False):
+    radius = ("  -d R, --max-distance R: %s within cosine distance R (<= R). Default: %s. %g is a starting point for embeddings of near-identical"
+              " images, not a tuned value: check a few groups of your collection and adjust R")
+    if dedup:
+        print("Usage: python -m clip_cpp_amd.image_search dedup [options]")
+        print("\nPrints the groups of near-duplicate images of an index built by `build` (connected components of the image pairs within R).")
+        print("\nOptions:")
+        print("  -h, --help: Show this message and exit")
+        print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default (loaded only to place the index on its device).")
+        print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
+        print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
+        print(radius % ("pair images", DEDUP_RADIUS, DEDUP_RADIUS))
+    elif build:
         print("Usage: python -m clip_cpp_amd.image_search build [options] dir/with/pictures [more/dirs]")
         print("\nOptions:")
         print("  -h, --help: Show this message and exit")
@@ -98,6 +129,7 @@ def _help(build, p):
         print("  -t N, --threads N: Number of threads to use for inference. Default: %d" % p["threads"])
         print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
         print("  -n N, --results N: Number of results to display. Default: %d" % p["results"])
+        print("  -d R, --max-distance R: display every indexed image within cosine distance R (<= R), nearest first, instead of the -n nearest (not with -n)")
         print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
 
 
@@ -194,13 +226,9 @@ def read_index_header(path):
     return struct.unpack("<IIIQ", h[8:])
 
 
-def search(argv):
-    import clip_cpp_amd
-    p = _parse(argv, build=False)
-    if p is None:
-        _help(False, dict(threads=4, verbose=1, db=".", results=5))
-        return 1
-    img_path, text = classify_query(p["rest"])
+def _read_db(p):
+    """The image paths of DIR/images.paths after the database checks `search` and `dedup` share (the model path from its first line unless
+    -m gave one); None, with the message printed, when a check fails."""
     paths_file = os.path.join(p["db"], PATHS_FILE)
     lines = []
     if os.path.exists(paths_file):
@@ -220,13 +248,26 @@ def search(argv):
     if not p["model"]:
         print("main: Unable to load model from %s" % p["model"])
         _err("main: no database in '%s' (%s is missing or empty): run `python -m clip_cpp_amd.image_search build` first" % (p["db"], PATHS_FILE))
-        return 1
+        return None
     hdr = read_index_header(os.path.join(p["db"], INDEX_FILE))
     if hdr is None:
         _err("main: '%s' is missing or not an index file" % os.path.join(p["db"], INDEX_FILE))
-        return 1
+        return None
     if hdr[3] != len(image_paths):
         print("main: index files size missmatch")
+        return None
+    return image_paths
+
+
+def search(argv):
+    import clip_cpp_amd
+    p = _parse(argv, build=False)
+    if p is None:
+        _help(False, dict(threads=4, verbose=1, db=".", results=5))
+        return 1
+    img_path, text = classify_query(p["rest"])
+    image_paths = _read_db(p)
+    if image_paths is None:
         return 1
     try:
         clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])
@@ -255,14 +296,74 @@ def search(argv):
     if index.dim != vec.size:
         _err("main: the index holds %d-dimensional embeddings, the model makes %d" % (index.dim, vec.size))
         return 1
-    k = max(1, min(p["results"], MAX_K))
-    dist, ids = index.search(vec[None, :], k)
+    if p["max_distance"] is not None:
+        _, dist, ids = index.range_search(vec[None, :], p["max_distance"])
+        hits = list(zip(dist, ids))
+    else:
+        k = max(1, min(p["results"], MAX_K))
+        dist, ids = index.search(vec[None, :], k)
+        hits = [(d, i) for d, i in zip(dist[0], ids[0]) if i >= 0 and p["results"] > 0]
     if p["verbose"] > 0:
         print("search results:")
         print("distance path")
-    for d, i in zip(dist[0], ids[0]):
-        if i >= 0 and p["results"] > 0:
+    for d, i in hits:
+        print("  %f %s" % (d, image_paths[i]))
+    sys.stdout.flush()
+    index.close()
+    clip.close()
+    return 0
+
+
+def duplicate_groups(i, j, d):
+    """Connected components of the graph whose edges are the pairs (i[t], j[t]) at distance d[t]: a list, in order of each group's lowest
+    id, of [(id, distance to its nearest other member), ...] in id order.  Every id on an edge is in exactly one group of two or more."""
+    parent = {}
+
+    def find(x):
+        parent.setdefault(x, x)
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+
+    nearest = {}
+    for a, b, dd in zip(np.asarray(i).tolist(), np.asarray(j).tolist(), np.asarray(d, dtype=np.float64).tolist()):
+        ra, rb = find(a), find(b)
+        if ra != rb:
+            parent[max(ra, rb)] = min(ra, rb)       # the root is the lowest id of the group
+        for x in (a, b):
+            if x not in nearest or dd < nearest[x]:
+                nearest[x] = dd
+    groups = {}
+    for x in sorted(nearest):
+        groups.setdefault(find(x), []).append((x, nearest[x]))
+    return [groups[r] for r in sorted(groups)]
+
+
+def dedup(argv):
+    import clip_cpp_amd
+    p = _parse(argv, build=False, dedup=True)
+    if p is None:
+        _help(False, dict(verbose=1, db="."), dedup=True)
+        return 1
+    image_paths = _read_db(p)
+    if image_paths is None:
+        return 1
+    try:
+        clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])      # only the index's device: no image is encoded
+    except RuntimeError:
+        print("main: Unable to load model from %s" % p["model"])
+        return 1
+    index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
+    groups = duplicate_groups(*index.pairs(p["max_distance"]))
+    if p["verbose"] > 0:
+        print("duplicate groups:")
+    for g, members in enumerate(groups):
+        if g:
+            print()
+        for i, d in members:
             print("  %f %s" % (d, image_paths[i]))
+    print("main: %d groups, %d images" % (len(groups), sum(len(m) for m in groups)))
     sys.stdout.flush()
     index.close()
     clip.close()
@@ -271,10 +372,11 @@ def search(argv):
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
-    if not argv or argv[0] not in ("build", "search"):
-        print("Usage: python -m clip_cpp_amd.image_search {build|search} [options] ...  (-h after the command for its options)")
+    commands = {"build": build, "search": search, "dedup": dedup}
+    if not argv or argv[0] not in commands:
+        print("Usage: python -m clip_cpp_amd.image_search {build|search|dedup} [options] ...  (-h after the command for its options)")
         return 1
-    return build(argv[1:]) if argv[0] == "build" else search(argv[1:])
+    return commands[argv[0]](argv[1:])
 
 
 if __name__ == "__main__":

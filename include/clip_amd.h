@@ -171,6 +171,28 @@ void clip_amd_index_free(struct clip_amd_index * ix);
 /* Average device time (microseconds, HIP events) of one clip_amd_index_search_device of n_queries seeded random queries against n seeded
  * random rows on the current device (dtype as clip_amd_index_create: 0, 1 or 3); < 0 on error.  Used by scripts/search_bench.py. */
 float clip_amd_bench_search(int dtype, int64_t n, int dim, int n_queries, int k, int iters);
+/* Range search and near-duplicate pairs.
+ * Distance: exactly what clip_amd_index_search reports for the same (query, row) pair (the same stored values, the same MFMA chain per
+ * dtype, the same f32 expression); a row is a result when d <= radius, compared in f32.
+ * range_search: for each query every stored row with d <= radius, sorted by ascending distance, equal distances lower id first (search's
+ * order: for a query with c <= 1024 results, search with any k >= c begins with exactly those c (id, distance) pairs, bit for bit).
+ * pairs: every (i, j) with i < j < size and d(i, j) <= radius, d(i, j) being the distance search reports for row j when the query is the
+ * vector that was added as row i (row i's stored values are exactly that query's normalised / quantised form); grouped by ascending i,
+ * within one i in range-search order, so the pairs of row i are range_search(vector of row i) without the ids <= i, bit for bit.
+ * Results are bit-identical run to run, however queries are split across calls, however rows were split across add calls, and across
+ * save / load.  Zero vectors (i8: also rows with amax 0, NaN or inf) are at distance exactly 1 from everything: results only at radius >= 1.
+ * Host pointers, synchronous, on the ctx stream.  lims has n_queries + 1 (range_search) / size + 1 (pairs) entries and is written on every
+ * successful call: segment q is [lims[q], lims[q + 1]).  Returns the total lims[last]; distances / ids (capacity entries) are written only
+ * when total <= capacity, otherwise only lims (call again with a larger buffer); capacity 0 with NULL outputs is a count-only call.
+ * -1 with a message on stderr, nothing launched, for a NULL index or lims, a NaN radius, n_queries < 0, capacity < 0, NULL outputs with
+ * capacity > 0 or NULL queries with n_queries > 0.  Device memory: O(size + n_queries + min(total, capacity)) plus a fixed workspace. */
+int64_t clip_amd_index_range_search(struct clip_amd_index * ix, const float * queries, int n_queries, float radius,
+                                    int64_t * lims, float * distances, int64_t * ids, int64_t capacity);
+int64_t clip_amd_index_pairs(struct clip_amd_index * ix, float radius, int64_t * lims, float * distances, int64_t * ids, int64_t capacity);
+/* Average wall time (microseconds) of one clip_amd_index_range_search of n_queries seeded queries (n_queries == 0: clip_amd_index_pairs)
+ * against n seeded random rows of which every 64th is a small perturbation of an earlier one (sparse, non-empty output at small radii), on
+ * the current device (dtype as clip_amd_index_create); < 0 on error.  Used by scripts/pairs_bench.py. */
+float clip_amd_bench_range(int dtype, int64_t n, int dim, int n_queries, float radius, int iters);
 
 /* ---- kernel-level test hooks (used by tests/ only; host pointers, synchronous) ----
  * Y[M,N] = X[M,K] . W[N,K]^T (+bias) through the production dequant-GEMM kernel.
