@@ -255,238 +255,6 @@ bool layers_fit_skinny(const DevTower & tw, int rows, int h, int ff) {
     return l.qkv.K == l.qkv.Kpad && l.ff1.K == l.ff1.Kpad && l.o.N == h && l.ff2.N == h && l.ff1.N == ff;
 }
 
-// precondition: slot 0 of ctx->sk_stats holds the row statistics of x (launch_row_stats)
-bool run_layers_skinny(clip_ctx * ctx, const DevTower & tw, int rows, int h, int nh, int ff, float eps, int nseq, int T_uniform,
-                       const int * d_seq_start, int max_len, bool causal, float * x, half_t * qkv, half_t * att, half_t * mid) {
-    hipStream_t s = ctx->stream;
-    const int dh = h / nh;
-    const float qscale = 1.0f / sqrtf((float)dh);
-    const int act = ctx->use_gelu ? EPI_GELU_F16 : EPI_QGELU_F16;
-    float2 * stA = ctx->sk_stats, * stB = ctx->sk_stats + (size_t)SKINNY_MAX_ROWS * 128;
-    int slotsA = 1;
-    for (const DevLayer & l : tw.layers) {
-        SkinnyParams q;   // LN1 + q/k/v projection (+ Q scale after the bias, clip.cpp:1363)
-        q.x32 = x; q.ldx = h; q.ln_w = l.ln1_w; q.ln_b = l.ln1_b; q.eps = eps; q.stats_in = stA; q.stats_slots = slotsA;
-        q.M = rows; q.W = l.qkv; q.bias = l.qkv_b; q.out = qkv; q.ldc = 3 * h; q.qscale = qscale; q.qcols = h;
-        skinny(ctx, "ln1_qkv", q, EPI_F16);
-        {
-            const double afl = 4.0 * (double)nseq * nh * (double)max_len * max_len * dh;
-            ProfScope ps(ctx, "attention", nseq * nh, max_len, dh, afl, (double)rows * h * 8);
-            if (!launch_attention(qkv, att, nseq, T_uniform, d_seq_start, max_len, h, nh, causal, s)) {
-                fprintf(stderr, "clip (hip): attention kernel does not support T=%d d_head=%d\n", max_len, dh);
-                return false;
-            }
-        }
-        SkinnyParams o;   // out-projection + residual; leaves the statistics of the new rows for LN2
-        o.A16 = att; o.lda = h; o.M = rows; o.W = l.o; o.bias = l.o_b; o.out = x; o.ldc = h; o.resid = x; o.stats_out = stB;
-        skinny(ctx, "out_resid", o, EPI_RESID_F32);
-        SkinnyParams u;   // LN2 + FFN-up + activation
-        u.x32 = x; u.ldx = h; u.ln_w = l.ln2_w; u.ln_b = l.ln2_b; u.eps = eps; u.stats_in = stB; u.stats_slots = h / 16;
-        u.M = rows; u.W = l.ff1; u.bias = l.ff1_b; u.out = mid; u.ldc = ff;
-        skinny(ctx, "ln2_ffn_up", u, act);
-        SkinnyParams d;   // FFN-down + residual; statistics for the next layer's LN1
-        d.A16 = mid; d.lda = ff; d.M = rows; d.W = l.ff2; d.bias = l.ff2_b; d.out = x; d.ldc = h; d.resid = x; d.stats_out = stA;
-        skinny(ctx, "ffn_down_resid", d, EPI_RESID_F32);
-        slotsA = h / 16;
-    }
-    return true;
-}
-
-// The small-M chain with the LayerNorm folded (kernels.h SkinnyParams::ln_c / xg_out): 5 launches per layer as above, but the q/k/v and
-// FFN-up kernels read the fp16 operand xn = fp16(x gamma) the residual epilogues leave (half the bytes of the f32 rows, no gamma / beta
-// staging, no normalisation in registers) and finish the LayerNorm in their epilogue.  r03 stamps: the LayerNorm prologue was 2.7 us of
-// the 6-7 us these two kernels live.  Precondition as run_layers_fold: xn and ONE statistics slot per row from the entry kernel.
-bool run_layers_skinny_fold(clip_ctx * ctx, const DevTower & tw, int rows, int h, int nh, int ff, float eps, int nseq, int T_uniform,
-                            const int * d_seq_start, int max_len, bool causal, float * x, half_t * xn, half_t * qkv, half_t * att, half_t * mid,
-                            float2 * stats, int stats_stride, float * mu) {
-    hipStream_t s = ctx->stream;
-    const int dh = h / nh;
-    const float qscale = 1.0f / sqrtf((float)dh);
-    const int act = ctx->use_gelu ? EPI_GELU_F16 : EPI_QGELU_F16;
-    int slots = 1, slotw = h;
-    // centring offsets (kernels.h GemmParams::xg_mu): two [stats_stride] buffers; every consumer reads the one its operand was centred on
-    // and leaves its own row means in the other, which the next producer centres on.  mu == null: the uncentred form.
-    float * mu_cur = mu, * mu_alt = mu ? mu + stats_stride : nullptr;
-    auto consume = [&](SkinnyParams & p, const float * c, const float * bf) {
-        p.A16 = xn; p.lda = h; p.bias = bf; p.ln_c = c; p.fstats = stats; p.fslots = slots; p.fslotw = slotw; p.fstride = stats_stride; p.eps = eps;
-        if (mu) { p.ln_mu = mu_cur; p.mu_out = mu_alt; std::swap(mu_cur, mu_alt); }
-    };
-    auto produce = [&](SkinnyParams & p, const float * gamma_next) {
-        if (!gamma_next) return;
-        p.xg_mu = mu_cur;
-        p.xg_out = xn; p.ldxg = h; p.xg_gamma = gamma_next; p.fstats_out = stats; p.fstride_out = stats_stride;
-        slots = h / 16; slotw = 16;
-    };
-    for (size_t li = 0; li < tw.layers.size(); li++) {
-        const DevLayer & l = tw.layers[li];
-        SkinnyParams q;   // q/k/v projection of the folded LN1 (+ Q scale after the bias, clip.cpp:1363)
-        q.M = rows; q.W = l.qkv; q.out = qkv; q.ldc = 3 * h; q.qscale = qscale; q.qcols = h;
-        consume(q, l.qkv_c, l.qkv_bf);
-        skinny(ctx, "ln1_qkv", q, EPI_F16);
-        {
-            const double afl = 4.0 * (double)nseq * nh * (double)max_len * max_len * dh;
-            ProfScope ps(ctx, "attention", nseq * nh, max_len, dh, afl, (double)rows * h * 8);
-            if (!launch_attention(qkv, att, nseq, T_uniform, d_seq_start, max_len, h, nh, causal, s)) {
-                fprintf(stderr, "clip (hip): attention kernel does not support T=%d d_head=%d\n", max_len, dh);
-                return false;
-            }
-        }
-        SkinnyParams o;   // out-projection + residual; leaves xn = fp16(x ln2_w) and the 16-column statistics for LN2
-        o.A16 = att; o.lda = h; o.M = rows; o.W = l.o; o.bias = l.o_b; o.out = x; o.ldc = h; o.resid = x;
-        produce(o, l.ln2_w);
-        skinny(ctx, "out_resid", o, EPI_RESID_F32);
-        SkinnyParams u;   // FFN-up of the folded LN2 + activation
-        u.M = rows; u.W = l.ff1; u.out = mid; u.ldc = ff;
-        consume(u, l.ff1_c, l.ff1_bf);
-        skinny(ctx, "ln2_ffn_up", u, act);
-        SkinnyParams d;   // FFN-down + residual; operand and statistics for the next layer's LN1
-        d.A16 = mid; d.lda = ff; d.M = rows; d.W = l.ff2; d.bias = l.ff2_b; d.out = x; d.ldc = h; d.resid = x;
-        produce(d, li + 1 < tw.layers.size() ? tw.layers[li + 1].ln1_w : nullptr);
-        skinny(ctx, "ffn_down_resid", d, EPI_RESID_F32);
-    }
-    return true;
-}
-
-// L x { LN1, QKV, attention, out-proj(+res), LN2, FFN-up(+act), FFN-down(+res) }   (clip.cpp:1342-1423 / :1064-1143)
-bool run_layers(clip_ctx * ctx, const DevTower & tw, int rows, int h, int nh, int ff, float eps, int nseq, int T_uniform,
-                const int * d_seq_start, int max_len, bool causal, float * x, half_t * xn, half_t * qkv, half_t * att, half_t * mid, bool prune_last,
-                const half_t * const * resp = nullptr) {
-    hipStream_t s = ctx->stream;
-    const int dh = h / nh;
-    const float qscale = 1.0f / sqrtf((float)dh);
-    const int act = ctx->use_gelu ? EPI_GELU_F16 : EPI_QGELU_F16;
-    const bool f32 = acts_f32(ctx, tw);                       // f32 file: xn / qkv / att / mid hold float rows
-    for (size_t li = 0; li < tw.layers.size(); li++) {
-        const DevLayer & l = tw.layers[li];
-        const LayerPanels lp = dequant_layer(ctx, l, rows, resp ? resp + 4 * li : nullptr);
-        {
-            ProfScope ps(ctx, "layernorm", rows, h, 0, 0, (double)rows * h * 6);
-            layernorm_act(f32, x, h, nullptr, 1, l.ln1_w, l.ln1_b, eps, rows, h, xn, s);
-        }
-        GemmParams p;
-        p.A = xn; p.lda = h; p.M = rows; p.W = l.qkv; p.bias = l.qkv_b; p.out = qkv; p.ldc = 3 * h; p.w16_pre = lp.qkv;
-        p.qscale = qscale; p.qcols = h;   // Q = (W_q x + b_q) / sqrt(d_head): scale after bias (clip.cpp:1363)
-        p.act_f32 = f32;
-        gemm(ctx, "gemm_qkv", p, EPI_F16);
-        {
-            const double afl = 4.0 * (double)nseq * nh * (double)max_len * max_len * dh;
-            ProfScope ps(ctx, "attention", nseq * nh, max_len, dh, afl, (double)rows * h * 8);
-            if (!(f32 ? launch_attention_f32((const float *)qkv, (float *)att, nseq, T_uniform, d_seq_start, max_len, h, nh, causal, s)
-                      : launch_attention(qkv, att, nseq, T_uniform, d_seq_start, max_len, h, nh, causal, s))) {
-                fprintf(stderr, "clip (hip): attention kernel does not support T=%d d_head=%d\n", max_len, dh);
-                return false;
-            }
-        }
-        if (prune_last && li + 1 == tw.layers.size()) break;     // the rest of the last layer runs on the pooled rows only (pooled_tail)
-        GemmParams po;
-        po.A = att; po.lda = h; po.M = rows; po.W = l.o; po.bias = l.o_b; po.out = x; po.ldc = h; po.resid = x; po.w16_pre = lp.o; po.act_f32 = f32;
-        gemm(ctx, "gemm_out", po, EPI_RESID_F32);
-        {
-            ProfScope ps(ctx, "layernorm", rows, h, 0, 0, (double)rows * h * 6);
-            layernorm_act(f32, x, h, nullptr, 1, l.ln2_w, l.ln2_b, eps, rows, h, xn, s);
-        }
-        GemmParams p1;
-        p1.A = xn; p1.lda = h; p1.M = rows; p1.W = l.ff1; p1.bias = l.ff1_b; p1.out = mid; p1.ldc = ff; p1.w16_pre = lp.ff1; p1.act_f32 = f32;
-        gemm(ctx, "gemm_ffn_up", p1, act);
-        GemmParams p2;
-        p2.A = mid; p2.lda = ff; p2.M = rows; p2.W = l.ff2; p2.bias = l.ff2_b; p2.out = x; p2.ldc = h; p2.resid = x; p2.w16_pre = lp.ff2; p2.act_f32 = f32;
-        gemm(ctx, "gemm_ffn_down", p2, EPI_RESID_F32);
-    }
-    return true;
-}
-
-// The same chain with every LayerNorm folded into the GEMMs around it (gemm_common.h; reference ops clip.cpp:1350-1355,1400-1405 and
-// text :1071-1076,1121-1126): 5 launches per layer.  The residual epilogues (out-projection, FFN-down) leave xg = fp16(x gamma_next)
-// in xn and the partial row statistics in `stats`; the q/k/v and FFN-up epilogues apply rstd (acc - mean c) + b'.
-// Precondition: xn = fp16(x * ln1_w of layer 0) and stats = ONE slot per row over all h columns (launch_layernorm_prep / launch_text_embed).
-bool run_layers_fold(clip_ctx * ctx, const DevTower & tw, int rows, int h, int nh, int ff, float eps, int nseq, int T_uniform,
-                     const int * d_seq_start, int max_len, bool causal, float * x, half_t * xn, half_t * qkv, half_t * att, half_t * mid,
-                     float2 * stats, int stats_stride, float * mu, bool prune_last, const half_t * const * ff2p = nullptr) {
-    hipStream_t s = ctx->stream;
-    const int dh = h / nh;
-    const float qscale = 1.0f / sqrtf((float)dh);
-    const int act = ctx->use_gelu ? EPI_GELU_F16 : EPI_QGELU_F16;
-    int slots = 1, slotw = h;
-    float * mu_cur = mu, * mu_alt = mu ? mu + stats_stride : nullptr;      // centring offsets, as run_layers_skinny_fold
-    auto consume = [&](GemmParams & p, const float * c, const float * bf) {
-        p.A = xn; p.lda = h; p.bias = bf; p.ln_c = c; p.ln_stats = stats; p.ln_slots = slots; p.ln_slotw = slotw; p.ln_stride = stats_stride; p.ln_eps = eps;
-        if (mu) { p.ln_mu = mu_cur; p.mu_out = mu_alt; std::swap(mu_cur, mu_alt); }
-    };
-    auto produce = [&](GemmParams & p, const float * gamma_next) {
-        if (!gamma_next) return;                              // last layer: the pooled rows go through the post-LN launch
-        p.xg_mu = mu_cur;
-        p.xg_out = xn; p.ldxg = h; p.xg_gamma = gamma_next; p.stats_out = stats; p.stats_stride = stats_stride;
-        const bool quant = !p.w16_pre && p.W.wtype != W_F16;
-        slotw = gemm_fold_slotw_for(p.M, p.W.N, p.W.Kpad, quant, device_shared(ctx));
-        slots = h / slotw;
-    };
-    for (size_t li = 0; li < tw.layers.size(); li++) {
-        const DevLayer & l = tw.layers[li];
-        const LayerPanels lp = dequant_layer(ctx, l, rows, ff2p ? ff2p + 4 * li : nullptr);
-        GemmParams p;
-        p.M = rows; p.W = l.qkv; p.out = qkv; p.ldc = 3 * h; p.w16_pre = lp.qkv;
-        p.qscale = qscale; p.qcols = h;   // Q = (W_q LN(x) + b_q) / sqrt(d_head): scale after bias (clip.cpp:1363)
-        consume(p, l.qkv_c, l.qkv_bf);
-        gemm(ctx, "gemm_qkv", p, EPI_F16);
-        {
-            const double afl = 4.0 * (double)nseq * nh * (double)max_len * max_len * dh;
-            ProfScope ps(ctx, "attention", nseq * nh, max_len, dh, afl, (double)rows * h * 8);
-            if (!launch_attention(qkv, att, nseq, T_uniform, d_seq_start, max_len, h, nh, causal, s)) {
-                fprintf(stderr, "clip (hip): attention kernel does not support T=%d d_head=%d\n", max_len, dh);
-                return false;
-            }
-        }
-        if (prune_last && li + 1 == tw.layers.size()) break;     // the rest of the last layer runs on the pooled rows only (pooled_tail)
-        GemmParams po;
-        po.A = att; po.lda = h; po.M = rows; po.W = l.o; po.bias = l.o_b; po.out = x; po.ldc = h; po.resid = x; po.w16_pre = lp.o;
-        produce(po, l.ln2_w);
-        gemm(ctx, "gemm_out", po, EPI_RESID_F32);
-        GemmParams p1;
-        p1.M = rows; p1.W = l.ff1; p1.out = mid; p1.ldc = ff; p1.w16_pre = lp.ff1;
-        consume(p1, l.ff1_c, l.ff1_bf);
-        gemm(ctx, "gemm_ffn_up", p1, act);
-        GemmParams p2;
-        p2.A = mid; p2.lda = ff; p2.M = rows; p2.W = l.ff2; p2.bias = l.ff2_b; p2.out = x; p2.ldc = h; p2.resid = x; p2.w16_pre = lp.ff2;
-        produce(p2, li + 1 < tw.layers.size() ? tw.layers[li + 1].ln1_w : nullptr);
-        gemm(ctx, "gemm_ffn_down", p2, EPI_RESID_F32);
-    }
-    return true;
-}
-
-// Only ONE row per sequence leaves the tower — the class-token row of an image (reference clip.cpp:1426-1431), the last token of a text
-// (:1154-1155) — and a row of the last layer's out-projection / FFN depends on no other row.  So the last layer runs q/k/v and attention on
-// every row (keys and values of all tokens feed the pooled query) and everything behind the attention on the `n` pooled rows only:
-// 1 / T of the out-projection and of both FFN GEMMs, i.e. ~(9 / 12) / L of the tower's linear FLOPs for free (ViT-B/32 batch 256: three
-// GEMMs of 12800 rows become three of 256).  Same arithmetic per row as the full-row layer (LayerNorm launch form), different tiles.
-// xp [n][h] f32 (out: the pooled rows of the final residual stream), ap / xnp [n][h] fp16, midp [n][ff] fp16: workspace of the caller.
-bool pooled_tail(clip_ctx * ctx, const DevLayer & l, int n, int h, int ff, float eps, const float * x, const half_t * att, const int * in_rows,
-                 int in_row_mul, float * xp, half_t * ap, half_t * xnp, half_t * midp) {
-    hipStream_t s = ctx->stream;
-    const int act = ctx->use_gelu ? EPI_GELU_F16 : EPI_QGELU_F16;
-    const bool f32 = ctx->f32_acts && l.o.wtype == W_F32 && l.ff1.wtype == W_F32 && l.ff2.wtype == W_F32;     // f32 file: att / ap / xnp / midp hold float rows
-    {
-        ProfScope ps(ctx, "gather_pooled", n, h, 0, 0, (double)n * h * 12);
-        if (f32) {
-            launch_gather_rows(x, nullptr, in_rows, in_row_mul, n, h, xp, nullptr, s);
-            launch_gather_rows((const float *)att, nullptr, in_rows, in_row_mul, n, h, (float *)ap, nullptr, s);
-        } else launch_gather_rows(x, att, in_rows, in_row_mul, n, h, xp, ap, s);
-    }
-    GemmParams po;
-    po.A = ap; po.lda = h; po.M = n; po.W = l.o; po.bias = l.o_b; po.out = xp; po.ldc = h; po.resid = xp; po.act_f32 = f32;
-    gemm(ctx, "gemm_out_pooled", po, EPI_RESID_F32);
-    {
-        ProfScope ps(ctx, "layernorm", n, h, 0, 0, (double)n * h * 6);
-        layernorm_act(f32, xp, h, nullptr, 1, l.ln2_w, l.ln2_b, eps, n, h, xnp, s);
-    }
-    GemmParams p1;
-    p1.A = xnp; p1.lda = h; p1.M = n; p1.W = l.ff1; p1.bias = l.ff1_b; p1.out = midp; p1.ldc = ff; p1.act_f32 = f32;
-    gemm(ctx, "gemm_ffn_up_pooled", p1, act);
-    GemmParams p2;
-    p2.A = midp; p2.lda = ff; p2.M = n; p2.W = l.ff2; p2.bias = l.ff2_b; p2.out = xp; p2.ldc = h; p2.resid = xp; p2.act_f32 = f32;
-    gemm(ctx, "gemm_ffn_down_pooled", p2, EPI_RESID_F32);
-    return true;
-}
-
 // RESIDENT fp16 panels of block-quantised weights (round 4; profiles/r04_experiments.txt section 9): the FFN-down weight where the 8-wave
 // kernel on a panel beats the fused-dequant 4-wave kernel but a per-layer dequantisation launch would cost more than it gains (K >= 2048
 // and >= 200 tiles of 160 x 256 — ViT-B/32 at batch 256: 75.9 -> 71.7 us per launch, +1.0 ... +1.5 % on the BASELINE configuration on four
@@ -562,6 +330,183 @@ bool fold_pays(const DevTower & tw, int rows, bool shared) {
     return true;
 }
 
+// One pass of one tower, filled once per call (vision_stage_finish, text_forward_device): shapes, sequences, workspace, and which of the
+// four forms of the layer chain carries it (choose_form).
+struct TowerPass {
+    const DevTower * tw = nullptr;
+    int which = 0;                              // 0 vision, 1 text: the tower's resident-panel table (resident_panels)
+    int rows = 0, h = 0, nh = 0, ff = 0, proj = 0;
+    float eps = 0.f;
+    int nseq = 0, T_uniform = 0;                // sequences: uniform length T_uniform, or (T_uniform = 0) the device offsets seq_start [nseq + 1]
+    const int * seq_start = nullptr;
+    int max_len = 0;
+    bool causal = false;
+    const int * in_rows = nullptr;              // the row of sequence i that leaves the tower: in_rows[i], or i * in_row_mul where in_rows is null
+    int in_row_mul = 1;
+    TowerBufs b;
+    // the form of the layer chain:
+    bool skinny = false;                        // small-M kernels (k_skinny.hip, rows <= 64): SkinnyParams; else GemmParams
+    bool fold = false;                          // both LayerNorms of a layer folded into the GEMMs around them; else fused on the A operand (skinny) / launched
+    bool prune = false;                         // behind the last layer's attention only the pooled rows are computed (pooled_tail)
+    bool f32 = false;                           // f32 file: xn / qkv / att / mid (and the pooled buffers) hold float rows.  Only the plain GEMM form sees it
+    float * mu = nullptr;                       // b.mu, or null: the uncentred fold (CLIP_AMD_LNFOLD_CENTRE=0)
+    const half_t * const * resp = nullptr;      // resident-panel table (run_tower), or null
+};
+
+// needs tw, rows, h, ff, nseq and b
+void choose_form(const clip_ctx * ctx, TowerPass & P) {
+    const DevTower & tw = *P.tw;
+    P.skinny = layers_fit_skinny(tw, P.rows, P.h, P.ff);
+    P.fold = ctx->ln_fold && !tw.layers.empty() && (ctx->ln_fold_force || fold_pays(tw, P.rows, device_shared(ctx)));
+    // rows beyond the small-M path: the last layer's out-projection and FFN run on the nseq pooled rows only (pooled_tail)
+    P.prune = ctx->prune_last && !P.skinny && !tw.layers.empty() && P.rows > P.nseq;
+    P.f32 = acts_f32(ctx, tw);                  // (load.cpp turns ln_fold off for f32 files and layers_fit_skinny refuses them)
+    P.mu = ctx->ln_fold_centre ? P.b.mu : nullptr;
+}
+
+// Where the next normalised linear finds its row statistics, stepped by the linears in launch order.
+struct LnState {
+    // folded forms: the partial statistics in TowerBufs::stats.  Entry kernel: ONE slot over all h columns
+    int slots = 1, slotw = 0;
+    // centring offsets (kernels.h GemmParams::xg_mu): two [st_stride] buffers; every consumer reads the one its operand was centred on
+    // and leaves its own row means in the other, which the next producer centres on.  Both null: the uncentred form.
+    float * mu_cur = nullptr, * mu_alt = nullptr;
+    // small-M form with the LayerNorm fused on the A operand: the two halves of ctx->sk_stats.  Precondition: slot 0 of the first half
+    // holds the row statistics of x (launch_row_stats); the residual kernels leave h / 16 slots
+    float2 * st_cur = nullptr, * st_alt = nullptr;
+    int st_slots = 1;
+    LnState(const clip_ctx * ctx, const TowerPass & P) : slotw(P.h), mu_cur(P.mu), mu_alt(P.mu ? P.mu + P.b.st_stride : nullptr),
+                                                         st_cur(ctx->sk_stats), st_alt(ctx->sk_stats + (size_t)SKINNY_MAX_ROWS * 128) {}
+};
+
+struct Linear { const char * gemm_tag, * skinny_tag; const DevWeight & W; const float * bias; const half_t * panel; };   // panel: LayerPanels entry, or null
+struct Norm { const float * w, * b, * c, * bf; };     // a LayerNorm's weight and bias; folded into the linear behind it: c and the bias b' (DevLayer::qkv_c ...)
+
+// LayerNorm of the residual stream -> linear (q/k/v, FFN-up) -> out [rows][W.N], in the form of the pass:
+//   GEMM            : a LayerNorm launch into xn, then the GEMM
+//   GEMM, folded    : the GEMM reads xn = fp16(x gamma) that the kernel before it left and its epilogue applies rstd (acc - mean c) + b'
+//   small-M         : the kernel normalises the f32 rows of x on the fly
+//   small-M, folded : as the folded GEMM (half the bytes of the f32 rows, no gamma / beta staging, no normalisation in registers; r03
+//                     stamps: the LayerNorm prologue was 2.7 us of the 6-7 us these two kernels live)
+void norm_linear(clip_ctx * ctx, const TowerPass & P, LnState & ln, const Linear & L, const Norm & N, half_t * out, int epi, float qscale = 1.0f, int qcols = 0) {
+    const TowerBufs & B = P.b;
+    if (P.skinny) {
+        SkinnyParams p;
+        p.M = P.rows; p.W = L.W; p.out = out; p.ldc = L.W.N; p.qscale = qscale; p.qcols = qcols; p.eps = P.eps;
+        if (P.fold) {
+            p.A16 = B.xn; p.lda = P.h; p.bias = N.bf; p.ln_c = N.c; p.fstats = B.stats; p.fslots = ln.slots; p.fslotw = ln.slotw; p.fstride = B.st_stride;
+            if (ln.mu_cur) { p.ln_mu = ln.mu_cur; p.mu_out = ln.mu_alt; std::swap(ln.mu_cur, ln.mu_alt); }
+        } else {
+            p.x32 = B.x; p.ldx = P.h; p.ln_w = N.w; p.ln_b = N.b; p.stats_in = ln.st_cur; p.stats_slots = ln.st_slots; p.bias = L.bias;
+        }
+        skinny(ctx, L.skinny_tag, p, epi);
+        return;
+    }
+    GemmParams p;
+    p.A = B.xn; p.lda = P.h; p.M = P.rows; p.W = L.W; p.out = out; p.ldc = L.W.N; p.w16_pre = L.panel; p.qscale = qscale; p.qcols = qcols; p.act_f32 = P.f32;
+    if (P.fold) {
+        p.bias = N.bf; p.ln_c = N.c; p.ln_stats = B.stats; p.ln_slots = ln.slots; p.ln_slotw = ln.slotw; p.ln_stride = B.st_stride; p.ln_eps = P.eps;
+        if (ln.mu_cur) { p.ln_mu = ln.mu_cur; p.mu_out = ln.mu_alt; std::swap(ln.mu_cur, ln.mu_alt); }
+    } else {
+        ProfScope ps(ctx, "layernorm", P.rows, P.h, 0, 0, (double)P.rows * P.h * 6);
+        layernorm_act(P.f32, B.x, P.h, nullptr, 1, N.w, N.b, P.eps, P.rows, P.h, B.xn, ctx->stream);
+        p.bias = L.bias;
+    }
+    gemm(ctx, L.gemm_tag, p, epi);
+}
+
+// x += A W^T + bias (out-projection, FFN-down).  gamma_next: weight of the LayerNorm that the next norm_linear applies to the new rows,
+// null where none follows (the last layer's FFN-down: the pooled rows go through the post-LN launch).  The folded forms leave
+// xn = fp16((x - mu) gamma_next) and the partial row statistics for it; the un-folded small-M form leaves the statistics alone.
+void resid_linear(clip_ctx * ctx, const TowerPass & P, LnState & ln, const Linear & L, const half_t * A, const float * gamma_next) {
+    const TowerBufs & B = P.b;
+    if (P.skinny) {
+        SkinnyParams p;
+        p.A16 = A; p.lda = L.W.K; p.M = P.rows; p.W = L.W; p.bias = L.bias; p.out = B.x; p.ldc = P.h; p.resid = B.x;
+        if (!P.fold) {
+            p.stats_out = ln.st_alt;
+            std::swap(ln.st_cur, ln.st_alt);
+            ln.st_slots = P.h / 16;
+        } else if (gamma_next) {
+            p.xg_mu = ln.mu_cur;
+            p.xg_out = B.xn; p.ldxg = P.h; p.xg_gamma = gamma_next; p.fstats_out = B.stats; p.fstride_out = B.st_stride;
+            ln.slots = P.h / 16; ln.slotw = 16;
+        }
+        skinny(ctx, L.skinny_tag, p, EPI_RESID_F32);
+        return;
+    }
+    GemmParams p;
+    p.A = A; p.lda = L.W.K; p.M = P.rows; p.W = L.W; p.bias = L.bias; p.out = B.x; p.ldc = P.h; p.resid = B.x; p.w16_pre = L.panel; p.act_f32 = P.f32;
+    if (P.fold && gamma_next) {
+        p.xg_mu = ln.mu_cur;
+        p.xg_out = B.xn; p.ldxg = P.h; p.xg_gamma = gamma_next; p.stats_out = B.stats; p.stats_stride = B.st_stride;
+        const bool quant = !p.w16_pre && p.W.wtype != W_F16;
+        ln.slotw = gemm_fold_slotw_for(p.M, p.W.N, p.W.Kpad, quant, device_shared(ctx));
+        ln.slots = P.h / ln.slotw;
+    }
+    gemm(ctx, L.gemm_tag, p, EPI_RESID_F32);
+}
+
+// L x { LN1, QKV, attention, out-proj(+res), LN2, FFN-up(+act), FFN-down(+res) }   (clip.cpp:1342-1423 / :1064-1143): 7 launches per
+// layer, 5 in the folded and the small-M forms (reference ops of the fold: clip.cpp:1350-1355,1400-1405 and text :1071-1076,1121-1126).
+// Precondition of the folded forms: xn = fp16(x * ln1_w of layer 0) and stats = ONE slot per row over all h columns
+// (launch_layernorm_prep / launch_text_embed); of the un-folded small-M form: launch_row_stats.
+bool run_layers(clip_ctx * ctx, const TowerPass & P) {
+    const DevTower & tw = *P.tw;
+    const TowerBufs & B = P.b;
+    const int h = P.h, dh = h / P.nh;
+    const float qscale = 1.0f / sqrtf((float)dh);
+    const int act = ctx->use_gelu ? EPI_GELU_F16 : EPI_QGELU_F16;
+    LnState ln(ctx, P);
+    for (size_t li = 0; li < tw.layers.size(); li++) {
+        const DevLayer & l = tw.layers[li];
+        const bool last = li + 1 == tw.layers.size();
+        const LayerPanels lp = P.skinny ? LayerPanels() : dequant_layer(ctx, l, P.rows, P.resp ? P.resp + 4 * li : nullptr);
+        // Q = (W_q LN1(x) + b_q) / sqrt(d_head): scale after bias (clip.cpp:1363)
+        norm_linear(ctx, P, ln, {"gemm_qkv", "ln1_qkv", l.qkv, l.qkv_b, lp.qkv}, {l.ln1_w, l.ln1_b, l.qkv_c, l.qkv_bf}, B.qkv, EPI_F16, qscale, h);
+        {
+            const double afl = 4.0 * (double)P.nseq * P.nh * (double)P.max_len * P.max_len * dh;
+            ProfScope ps(ctx, "attention", P.nseq * P.nh, P.max_len, dh, afl, (double)P.rows * h * 8);
+            if (!(P.f32 ? launch_attention_f32((const float *)B.qkv, (float *)B.att, P.nseq, P.T_uniform, P.seq_start, P.max_len, h, P.nh, P.causal, ctx->stream)
+                        : launch_attention(B.qkv, B.att, P.nseq, P.T_uniform, P.seq_start, P.max_len, h, P.nh, P.causal, ctx->stream))) {
+                fprintf(stderr, "clip (hip): attention kernel does not support T=%d d_head=%d\n", P.max_len, dh);
+                return false;
+            }
+        }
+        if (P.prune && last) break;                          // the rest of the last layer runs on the pooled rows only (pooled_tail)
+        resid_linear(ctx, P, ln, {"gemm_out", "out_resid", l.o, l.o_b, lp.o}, B.att, l.ln2_w);
+        norm_linear(ctx, P, ln, {"gemm_ffn_up", "ln2_ffn_up", l.ff1, l.ff1_b, lp.ff1}, {l.ln2_w, l.ln2_b, l.ff1_c, l.ff1_bf}, B.mid, act);
+        resid_linear(ctx, P, ln, {"gemm_ffn_down", "ffn_down_resid", l.ff2, l.ff2_b, lp.ff2}, B.mid, last ? nullptr : tw.layers[li + 1].ln1_w);
+    }
+    return true;
+}
+
+// Only ONE row per sequence leaves the tower — the class-token row of an image (reference clip.cpp:1426-1431), the last token of a text
+// (:1154-1155) — and a row of the last layer's out-projection / FFN depends on no other row.  So the last layer runs q/k/v and attention on
+// every row (keys and values of all tokens feed the pooled query) and everything behind the attention on the nseq pooled rows only:
+// 1 / T of the out-projection and of both FFN GEMMs, i.e. ~(9 / 12) / L of the tower's linear FLOPs for free (ViT-B/32 batch 256: three
+// GEMMs of 12800 rows become three of 256).  Same arithmetic per row as the full-row layer (LayerNorm launch form), different tiles.
+// Out: xp [nseq][h], the pooled rows of the final residual stream.
+void pooled_tail(clip_ctx * ctx, const TowerPass & P) {
+    const DevLayer & l = P.tw->layers.back();
+    const TowerBufs & B = P.b;
+    const int n = P.nseq, h = P.h;
+    {
+        ProfScope ps(ctx, "gather_pooled", n, h, 0, 0, (double)n * h * 12);
+        if (P.f32) {
+            launch_gather_rows(B.x, nullptr, P.in_rows, P.in_row_mul, n, h, B.xp, nullptr, ctx->stream);
+            launch_gather_rows((const float *)B.att, nullptr, P.in_rows, P.in_row_mul, n, h, (float *)B.ap, nullptr, ctx->stream);
+        } else launch_gather_rows(B.x, B.att, P.in_rows, P.in_row_mul, n, h, B.xp, B.ap, ctx->stream);
+    }
+    TowerPass T = P;                                        // the second half of a layer in the plain GEMM form, on the pooled buffers
+    T.rows = n; T.skinny = T.fold = false;
+    T.b.x = B.xp; T.b.att = B.ap; T.b.xn = B.xnp; T.b.mid = B.midp;
+    LnState ln(ctx, T);
+    resid_linear(ctx, T, ln, {"gemm_out_pooled", "", l.o, l.o_b, nullptr}, T.b.att, nullptr);
+    norm_linear(ctx, T, ln, {"gemm_ffn_up_pooled", "", l.ff1, l.ff1_b, nullptr}, {l.ln2_w, l.ln2_b, nullptr, nullptr}, T.b.mid, ctx->use_gelu ? EPI_GELU_F16 : EPI_QGELU_F16);
+    resid_linear(ctx, T, ln, {"gemm_ffn_down_pooled", "", l.ff2, l.ff2_b, nullptr}, T.b.mid, nullptr);
+}
+
 bool check_device(clip_ctx * ctx, const char * who) {
     if (!ctx || ctx->device < 0) {
         fprintf(stderr, "%s: no HIP device bound to this context — the encoders have no CPU fallback\n", who);
@@ -580,6 +525,59 @@ bool launch_ok(const char * who) {
         fprintf(stderr, "%s: HIP launch error: %s\n", who, hipGetErrorString(e));
         return false;
     }
+    return true;
+}
+
+// The buffers both towers need, for `rows` token rows of `n` sequences
+void carve_tower(Carver & c, TowerBufs & b, int rows, int n, int h, int ff, int proj, bool f32) {
+    b.st_stride = (rows + 63) & ~63;
+    b.stats = c.take<float2>((size_t)(h / 16) * b.st_stride);
+    b.mu = c.take<float>((size_t)2 * b.st_stride);
+    b.x = c.take<float>((size_t)rows * h);
+    const size_t aw = f32 ? 2 : 1;                            // f32 file: the activation buffers hold float rows
+    b.xn = c.take<half_t>(aw * rows * h);
+    b.qkv = c.take<half_t>(aw * rows * 3 * h);
+    b.att = c.take<half_t>(aw * rows * h);
+    b.mid = c.take<half_t>(aw * rows * ff);
+    b.pooled = c.take<half_t>(aw * n * h);
+    b.emb = c.take<float>((size_t)n * proj);
+    b.xp = c.take<float>((size_t)n * h);
+    b.ap = c.take<half_t>(aw * n * h);
+    b.xnp = c.take<half_t>(aw * n * h);
+    b.midp = c.take<half_t>(aw * n * ff);
+}
+
+// carve(Carver &) runs twice: over a null base to size the workspace, then over the workspace itself
+template <typename F> bool carve_workspace(clip_ctx * ctx, F carve) {
+    Carver sizer(nullptr);
+    carve(sizer);
+    if (!ensure_workspace(ctx, sizer.off + 4096)) return false;
+    Carver c(ctx->ws.base, &ctx->guard_gaps);
+    carve(c);
+    return guard_arm(ctx);
+}
+
+// What both towers run behind their entry step (vision: class-token rows + pre-LN, text: embedding), which has left x — and, where P.fold,
+// xn and the whole-row statistics: the layers, pool + post-LN, projection, L2 norm into d_out [nseq][proj]
+bool run_tower(clip_ctx * ctx, TowerPass & P, float * d_out, bool normalize) {
+    const DevTower & tw = *P.tw;
+    const TowerBufs & B = P.b;
+    hipStream_t s = ctx->stream;
+    if (P.skinny && !P.fold) launch_row_stats(B.x, P.h, P.rows, P.h, ctx->sk_stats, s);
+    P.resp = P.skinny ? nullptr : resident_panels(ctx, tw, P.which, P.rows);
+    if (!run_layers(ctx, P)) return false;
+    // pool + post-LN (vision :1426-1438: the class-token rows b * T; text :1146-1155: the last-token rows) — LayerNorm is row-wise, so
+    // LN-then-gather == gather-then-LN: one LayerNorm launch with a row gather
+    if (P.prune) {    // ... and so is everything behind the last layer's attention
+        pooled_tail(ctx, P);
+        layernorm_act(P.f32, B.xp, P.h, nullptr, 1, tw.post_ln_w, tw.post_ln_b, P.eps, P.nseq, P.h, B.pooled, s);
+    } else {
+        layernorm_act(P.f32, B.x, P.h, P.in_rows, P.in_row_mul, tw.post_ln_w, tw.post_ln_b, P.eps, P.nseq, P.h, B.pooled, s);
+    }
+    GemmParams pj;
+    pj.A = B.pooled; pj.lda = P.h; pj.M = P.nseq; pj.W = tw.proj; pj.out = B.emb; pj.ldc = P.proj; pj.act_f32 = P.f32;
+    gemm(ctx, "gemm_proj", pj, EPI_F32);                        // projection, no bias (:1443 / :1160)
+    launch_l2norm(B.emb, d_out, P.nseq, P.proj, normalize, s);  // (:1446-1455 / :1163-1166)
     return true;
 }
 
@@ -832,30 +830,10 @@ bool vision_stage_begin(clip_ctx * ctx, int Bc, VisionStage & st) {
     const int h = hp.hidden_size, ff = hp.n_intermediate, proj = hp.projection_dim;
     const int rows = Bc * T;
     st.Bc = Bc;
-    st.st_stride = (rows + 63) & ~63;                      // LayerNorm-fold statistics: [<= h / 16 slots][st_stride rows] float2
-    auto carve = [&](Carver & c) {
-        st.stats = c.take<float2>((size_t)(h / 16) * st.st_stride);
-        st.mu = c.take<float>((size_t)2 * st.st_stride);      // centring offsets of the folded LayerNorms (two buffers, ping-pong)
-        st.x = c.take<float>((size_t)rows * h);
-        const size_t aw = acts_f32(ctx, V) ? 2 : 1;                // f32 file: the activation buffers hold float rows
-        st.xn = c.take<half_t>(aw * rows * h);
-        st.qkv = c.take<half_t>(aw * rows * 3 * h);
-        st.att = c.take<half_t>(aw * rows * h);
-        st.mid = c.take<half_t>(aw * rows * ff);
+    return carve_workspace(ctx, [&](Carver & c) {
+        carve_tower(c, st.b, rows, Bc, h, ff, proj, acts_f32(ctx, V));
         st.col = c.take<half_t>((size_t)Bc * Np * V.patch.Kpad);
-        st.pooled = c.take<half_t>(aw * Bc * h);
-        st.emb = c.take<float>((size_t)Bc * proj);
-        st.xp = c.take<float>((size_t)Bc * h);                // pooled rows of the last layer (pooled_tail)
-        st.ap = c.take<half_t>(aw * Bc * h);
-        st.xnp = c.take<half_t>(aw * Bc * h);
-        st.midp = c.take<half_t>(aw * Bc * ff);
-    };
-    Carver sizer(nullptr);
-    carve(sizer);
-    if (!ensure_workspace(ctx, sizer.off + 4096)) return false;
-    Carver c(ctx->ws.base, &ctx->guard_gaps);
-    carve(c);
-    return guard_arm(ctx);
+    });
 }
 
 // imgs: the n images themselves (f32, or fp16 when ctx->input_f16), i0: their index inside the chunk
@@ -866,7 +844,7 @@ bool vision_stage_patch(clip_ctx * ctx, const VisionStage & st, const void * img
     const int S = hp.image_size, P = hp.patch_size, G = S / P, Np = G * G, T = Np + 1, h = hp.hidden_size;
     hipStream_t s = ctx->stream;
     half_t * col = st.col + (size_t)i0 * Np * V.patch.Kpad;
-    float * x = st.x + (size_t)i0 * T * h;
+    float * x = st.b.x + (size_t)i0 * T * h;
     // patch embedding = im2col + GEMM (ggml_conv_2d, clip.cpp:1309-1312); epilogue scatters to token rows + pos
     {
         ProfScope ps(ctx, "im2col", n * Np, V.patch.Kpad, 0, 0, (double)n * S * S * 3 * (ctx->input_f16 ? 2 : 4) + (double)n * Np * V.patch.Kpad * 2);
@@ -883,45 +861,26 @@ bool vision_stage_patch(clip_ctx * ctx, const VisionStage & st, const void * img
 bool vision_stage_finish(clip_ctx * ctx, const VisionStage & st, float * d_out, bool normalize) {
     const auto & hp = ctx->vision_hparams;
     const DevTower & V = ctx->vision;
-    const int S = hp.image_size, P = hp.patch_size, G = S / P, Np = G * G, T = Np + 1;
-    const int h = hp.hidden_size, ff = hp.n_intermediate, nh = hp.n_head, proj = hp.projection_dim;
-    hipStream_t s = ctx->stream;
-    const int Bc = st.Bc, rows = Bc * T;
-    float * x = st.x;
-    const bool skinny = layers_fit_skinny(V, rows, h, ff);
-    const bool fold = ctx->ln_fold && !V.layers.empty() && (ctx->ln_fold_force || fold_pays(V, rows, device_shared(ctx)));
+    const int G = hp.image_size / hp.patch_size, T = G * G + 1;
+    TowerPass P;
+    P.tw = &V; P.which = 0;
+    P.rows = st.Bc * T; P.h = hp.hidden_size; P.nh = hp.n_head; P.ff = hp.n_intermediate; P.proj = hp.projection_dim; P.eps = hp.eps;
+    P.nseq = st.Bc; P.T_uniform = T; P.max_len = T; P.causal = false;
+    P.in_row_mul = T;                                          // CLS pool: row b * T
+    P.b = st.b;
+    choose_form(ctx, P);
+    float * x = P.b.x;
     {
-        ProfScope ps(ctx, "layernorm", rows, h, 0, 0, (double)rows * h * (fold ? 10 : 8));
-        if (fold)   // class-token rows (:1315-1331) + pre-LN (:1334-1339) + entry of the folded chain: xn = fp16(x ln1_w[0]), whole-row statistics
-            launch_layernorm_prep(x, h, V.pre_ln_w, V.pre_ln_b, hp.eps, rows, h, x, h, V.layers[0].ln1_w, st.xn, h, st.stats, s, ctx->ln_fold_centre ? st.mu : nullptr,
+        ProfScope ps(ctx, "layernorm", P.rows, P.h, 0, 0, (double)P.rows * P.h * (P.fold ? 10 : 8));
+        if (P.fold)   // class-token rows (:1315-1331) + pre-LN (:1334-1339) + entry of the folded chain: xn = fp16(x ln1_w[0]), whole-row statistics
+            launch_layernorm_prep(x, P.h, V.pre_ln_w, V.pre_ln_b, hp.eps, P.rows, P.h, x, P.h, V.layers[0].ln1_w, P.b.xn, P.h, P.b.stats, ctx->stream, P.mu,
                                   V.class_embd, V.pos, T);
         else {
-            launch_cls_rows(x, V.class_embd, V.pos, Bc, T, h, s);   // class token + pos[0] (clip.cpp:1315-1331)
-            launch_layernorm(x, h, nullptr, 1, V.pre_ln_w, V.pre_ln_b, hp.eps, rows, h, nullptr, 0, x, h, s);
+            launch_cls_rows(x, V.class_embd, V.pos, st.Bc, T, P.h, ctx->stream);   // class token + pos[0] (clip.cpp:1315-1331)
+            launch_layernorm(x, P.h, nullptr, 1, V.pre_ln_w, V.pre_ln_b, hp.eps, P.rows, P.h, nullptr, 0, x, P.h, ctx->stream);
         }
     }
-    // rows beyond the small-M path: the last layer's out-projection and FFN run on the Bc class-token rows only (pooled_tail)
-    const bool prune = ctx->prune_last && !skinny && !V.layers.empty() && T > 1;
-    if (skinny && fold) {
-        if (!run_layers_skinny_fold(ctx, V, rows, h, nh, ff, hp.eps, Bc, T, nullptr, T, false, x, st.xn, st.qkv, st.att, st.mid, st.stats, st.st_stride, ctx->ln_fold_centre ? st.mu : nullptr)) return false;
-    } else if (skinny) {
-        launch_row_stats(x, h, rows, h, ctx->sk_stats, s);
-        if (!run_layers_skinny(ctx, V, rows, h, nh, ff, hp.eps, Bc, T, nullptr, T, false, x, st.qkv, st.att, st.mid)) return false;
-    } else if (fold) {
-        if (!run_layers_fold(ctx, V, rows, h, nh, ff, hp.eps, Bc, T, nullptr, T, false, x, st.xn, st.qkv, st.att, st.mid, st.stats, st.st_stride, ctx->ln_fold_centre ? st.mu : nullptr, prune, resident_panels(ctx, V, 0, rows))) return false;
-    } else if (!run_layers(ctx, V, rows, h, nh, ff, hp.eps, Bc, T, nullptr, T, false, x, st.xn, st.qkv, st.att, st.mid, prune, resident_panels(ctx, V, 0, rows))) return false;
-    // CLS pool + post-LN (:1426-1438): LayerNorm with a strided row gather (row b*T)
-    const bool f32 = acts_f32(ctx, V);
-    if (prune) {
-        if (!pooled_tail(ctx, V.layers.back(), Bc, h, ff, hp.eps, x, st.att, nullptr, T, st.xp, st.ap, st.xnp, st.midp)) return false;
-        layernorm_act(f32, st.xp, h, nullptr, 1, V.post_ln_w, V.post_ln_b, hp.eps, Bc, h, st.pooled, s);
-    } else {
-        layernorm_act(f32, x, h, nullptr, T, V.post_ln_w, V.post_ln_b, hp.eps, Bc, h, st.pooled, s);
-    }
-    GemmParams pj;
-    pj.A = st.pooled; pj.lda = h; pj.M = Bc; pj.W = V.proj; pj.out = st.emb; pj.ldc = proj; pj.act_f32 = f32;
-    gemm(ctx, "gemm_proj", pj, EPI_F32);   // projection, no bias (:1443)
-    launch_l2norm(st.emb, d_out, Bc, proj, normalize, s);  // (:1446-1455)
+    if (!run_tower(ctx, P, d_out, normalize)) return false;
     return launch_ok("clip_image_batch_encode") && guard_check(ctx, "clip_image_batch_encode");
 }
 
@@ -966,10 +925,11 @@ bool text_forward_device(clip_ctx * ctx, const int32_t * d_ids, const int32_t * 
     if (n_texts <= 0) return true;
     const auto & hp = ctx->text_hparams;
     const DevTower & Tw = ctx->text;
-    const int h = hp.hidden_size, ff = hp.n_intermediate, nh = hp.n_head, proj = hp.projection_dim;
     hipStream_t s = ctx->stream;
-    const int rows = h_offsets[n_texts] - h_offsets[0];
-    int max_len = 0;
+    TowerPass P;
+    P.tw = &Tw; P.which = 1;
+    P.rows = h_offsets[n_texts] - h_offsets[0]; P.h = hp.hidden_size; P.nh = hp.n_head; P.ff = hp.n_intermediate; P.proj = hp.projection_dim; P.eps = hp.eps;
+    P.nseq = n_texts; P.causal = true;
     for (int i = 0; i < n_texts; i++) {
         const int len = h_offsets[i + 1] - h_offsets[i];
         if (len <= 0 || len > hp.num_positions) {
@@ -977,41 +937,17 @@ bool text_forward_device(clip_ctx * ctx, const int32_t * d_ids, const int32_t * 
             fprintf(stderr, "clip_text_encode: %d tokens is outside [1, %d]\n", len, hp.num_positions);
             return false;
         }
-        max_len = std::max(max_len, len);
+        P.max_len = std::max(P.max_len, len);
     }
-    const int st_stride = (rows + 63) & ~63;                   // LayerNorm-fold statistics: [<= h / 16 slots][st_stride rows] float2
-    float2 * stats = nullptr;
-    float * mu = nullptr;                                      // centring offsets of the folded LayerNorms: [2][st_stride]
-    float * xp = nullptr;                                      // pooled rows of the last layer (pooled_tail)
-    half_t * ap = nullptr, * xnp = nullptr, * midp = nullptr;
-    auto carve = [&](Carver & c, float *& x, half_t *& xn, half_t *& qkv, half_t *& att, half_t *& mid, half_t *& pooled,
-                     float *& emb, int *& seq, int *& last) {
-        stats = c.take<float2>((size_t)(h / 16) * st_stride);
-        mu = c.take<float>((size_t)2 * st_stride);
-        x = c.take<float>((size_t)rows * h);
-        const size_t aw = acts_f32(ctx, Tw) ? 2 : 1;               // f32 file: the activation buffers hold float rows
-        xn = c.take<half_t>(aw * rows * h);
-        qkv = c.take<half_t>(aw * rows * 3 * h);
-        att = c.take<half_t>(aw * rows * h);
-        mid = c.take<half_t>(aw * rows * ff);
-        pooled = c.take<half_t>(aw * n_texts * h);
-        emb = c.take<float>((size_t)n_texts * proj);
-        seq = c.take<int>((size_t)n_texts + 1);
-        last = c.take<int>((size_t)n_texts);
-        xp = c.take<float>((size_t)n_texts * h);
-        ap = c.take<half_t>(aw * n_texts * h);
-        xnp = c.take<half_t>(aw * n_texts * h);
-        midp = c.take<half_t>(aw * n_texts * ff);
-    };
-    float *x, *emb;
-    half_t *xn, *qkv, *att, *mid, *pooled;
-    int *seq, *last;
-    Carver sizer(nullptr);
-    carve(sizer, x, xn, qkv, att, mid, pooled, emb, seq, last);
-    if (!ensure_workspace(ctx, sizer.off + 4096)) return false;
-    Carver c(ctx->ws.base, &ctx->guard_gaps);
-    carve(c, x, xn, qkv, att, mid, pooled, emb, seq, last);
-    if (!guard_arm(ctx)) return false;
+    const int rows = P.rows, h = P.h;
+    int * seq = nullptr, * last = nullptr;                     // device copies of the sequence offsets [n_texts + 1] and the last-token rows [n_texts]
+    if (!carve_workspace(ctx, [&](Carver & c) {
+            carve_tower(c, P.b, rows, n_texts, h, P.ff, P.proj, acts_f32(ctx, Tw));
+            seq = c.take<int>((size_t)n_texts + 1);
+            last = c.take<int>((size_t)n_texts);
+        })) return false;
+    P.seq_start = seq;
+    P.in_rows = last;                                          // EOS pool (clip.cpp:1154-1155)
     {
         // sequence offsets + last-token rows (EOS, clip.cpp:1154-1155): written into a slot of a pinned ring and uploaded
         // asynchronously by a one-workgroup launch that reads the (device-mapped) slot — the host does not wait for the stream; a slot is
@@ -1082,38 +1018,17 @@ bool text_forward_device(clip_ctx * ctx, const int32_t * d_ids, const int32_t * 
         }
     }
     auto launch_all = [&]() -> bool {
-        const bool skinny = layers_fit_skinny(Tw, rows, h, ff);
-        const bool fold = ctx->ln_fold && !Tw.layers.empty() && (ctx->ln_fold_force || fold_pays(Tw, rows, device_shared(ctx)));
-        const bool prune = ctx->prune_last && !skinny && !Tw.layers.empty() && rows > n_texts;
-        if (fold)   // embedding (:1059-1061) + entry of the folded chain: xn = fp16(x ln1_w[0]), whole-row statistics
-            launch_text_embed(d_ids + h_offsets[0], seq, n_texts, rows, Tw.tok_raw, Tw.tok_type, Tw.pos, h, x, s, Tw.layers[0].ln1_w, xn, h, stats, ctx->ln_fold_centre ? mu : nullptr);
-        else launch_text_embed(d_ids + h_offsets[0], seq, n_texts, rows, Tw.tok_raw, Tw.tok_type, Tw.pos, h, x, s);  // (:1059-1061)
-        if (skinny && fold) {
-            if (!run_layers_skinny_fold(ctx, Tw, rows, h, nh, ff, hp.eps, n_texts, 0, seq, max_len, true, x, xn, qkv, att, mid, stats, st_stride, ctx->ln_fold_centre ? mu : nullptr)) return false;
-        } else if (skinny) {
-            launch_row_stats(x, h, rows, h, ctx->sk_stats, s);
-            if (!run_layers_skinny(ctx, Tw, rows, h, nh, ff, hp.eps, n_texts, 0, seq, max_len, true, x, qkv, att, mid)) return false;
-        } else if (fold) {
-            if (!run_layers_fold(ctx, Tw, rows, h, nh, ff, hp.eps, n_texts, 0, seq, max_len, true, x, xn, qkv, att, mid, stats, st_stride, ctx->ln_fold_centre ? mu : nullptr, prune, resident_panels(ctx, Tw, 1, rows))) return false;
-        } else if (!run_layers(ctx, Tw, rows, h, nh, ff, hp.eps, n_texts, 0, seq, max_len, true, x, xn, qkv, att, mid, prune, resident_panels(ctx, Tw, 1, rows))) return false;
-        // final LN on the pooled (last) row only — LayerNorm is row-wise, so LN-then-gather == gather-then-LN (:1146-1155)
-        if (prune) {    // ... and so is everything behind the last layer's attention: out-projection + FFN on the n_texts last-token rows only
-            if (!pooled_tail(ctx, Tw.layers.back(), n_texts, h, ff, hp.eps, x, att, last, 1, xp, ap, xnp, midp)) return false;
-            layernorm_act(acts_f32(ctx, Tw), xp, h, nullptr, 1, Tw.post_ln_w, Tw.post_ln_b, hp.eps, n_texts, h, pooled, s);
-        } else {
-            layernorm_act(acts_f32(ctx, Tw), x, h, last, 1, Tw.post_ln_w, Tw.post_ln_b, hp.eps, n_texts, h, pooled, s);
-        }
-        GemmParams pj;
-        pj.A = pooled; pj.lda = h; pj.M = n_texts; pj.W = Tw.proj; pj.out = emb; pj.ldc = proj; pj.act_f32 = acts_f32(ctx, Tw);
-        gemm(ctx, "gemm_proj", pj, EPI_F32);     // (:1160)
-        launch_l2norm(emb, d_out, n_texts, proj, normalize, s);  // (:1163-1166)
-        return true;
+        choose_form(ctx, P);                                   // (not needed where a captured graph is replayed)
+        if (P.fold)   // embedding (:1059-1061) + entry of the folded chain: xn = fp16(x ln1_w[0]), whole-row statistics
+            launch_text_embed(d_ids + h_offsets[0], seq, n_texts, rows, Tw.tok_raw, Tw.tok_type, Tw.pos, h, P.b.x, ctx->stream, Tw.layers[0].ln1_w, P.b.xn, h, P.b.stats, P.mu);
+        else launch_text_embed(d_ids + h_offsets[0], seq, n_texts, rows, Tw.tok_raw, Tw.tok_type, Tw.pos, h, P.b.x, ctx->stream);  // (:1059-1061)
+        return run_tower(ctx, P, d_out, normalize);
     };
     // Small token counts are launch-bound (~90 dependent launches): capture the chain on the second sighting of a signature and
     // replay it afterwards.  The kernels read the sequence offsets from device memory (uploaded above), so a graph only depends on
     // (texts, token rows, attention key-tile bucket, pointers) — not on the individual lengths.  The bucket also fixes which attention
     // kernel runs (the whole-row limits 592 / 288 are whole tiles) and the streaming kernel's grid (whole blocks of 64 / 128 queries).
-    const int nt_bucket = (max_len + 15) / 16;
+    const int nt_bucket = (P.max_len + 15) / 16;
     if (ctx->graphs_enabled && !ctx->profiling && rows <= 1024 && !guard_mode()) {
         clip_ctx::TextGraphEntry * e = nullptr;
         const void * ids_key = d_ids + h_offsets[0];

@@ -226,14 +226,20 @@ bool vision_forward_device(clip_ctx * ctx, const float * d_imgs, int B, float * 
 bool text_forward_device(clip_ctx * ctx, const int32_t * d_ids, const int32_t * h_offsets, int n_texts, float * d_out,
                          bool normalize);
 // the vision tower of one workspace chunk in stages (forward.cpp): the host pipeline runs the patch stage per copy piece
-struct VisionStage {
-    int Bc = 0, st_stride = 0;
+// activation buffers of one tower pass, carved out of the workspace (forward.cpp carve_tower)
+struct TowerBufs {
+    int st_stride = 0;
+    float2 * stats = nullptr;        // LayerNorm-fold statistics: [<= h / 16 slots][st_stride rows]
+    float * mu = nullptr;            // centring offsets of the folded LayerNorms: [2][st_stride] (two buffers, ping-pong)
     float * x = nullptr, * emb = nullptr;
-    half_t * xn = nullptr, * qkv = nullptr, * att = nullptr, * mid = nullptr, * col = nullptr, * pooled = nullptr;
-    float2 * stats = nullptr;
-    float * mu = nullptr;
+    half_t * xn = nullptr, * qkv = nullptr, * att = nullptr, * mid = nullptr, * pooled = nullptr;
     float * xp = nullptr;            // pooled rows of the last layer (forward.cpp pooled_tail)
     half_t * ap = nullptr, * xnp = nullptr, * midp = nullptr;
+};
+struct VisionStage {
+    TowerBufs b;
+    int Bc = 0;
+    half_t * col = nullptr;
 };
 bool vision_stage_begin(clip_ctx * ctx, int Bc, VisionStage & st);
 bool vision_stage_patch(clip_ctx * ctx, const VisionStage & st, const void * imgs, int i0, int n);
