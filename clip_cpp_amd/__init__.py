@@ -69,6 +69,7 @@ AMD_SYMBOLS = [
     "clip_amd_synchronize", "clip_amd_profile_enable", "clip_amd_profile_read", "clip_amd_profile_report",
     "clip_amd_test_gemm", "clip_amd_test_gemm_ex", "clip_amd_test_gemm_tile", "clip_amd_test_gemm_tile_ex", "clip_amd_test_skinny", "clip_amd_test_layernorm", "clip_amd_test_attention", "clip_amd_bench_gemm",
     "clip_amd_test_attention_ex", "clip_amd_bench_attention",
+    "clip_amd_test_layernorm_ex", "clip_amd_test_text_embed", "clip_amd_test_im2col", "clip_amd_test_layernorm_prep", "clip_amd_test_rows",
     "clip_amd_index_create", "clip_amd_index_add", "clip_amd_index_add_device", "clip_amd_index_size", "clip_amd_index_dim",
     "clip_amd_index_search", "clip_amd_index_search_device", "clip_amd_index_save", "clip_amd_index_load", "clip_amd_index_free",
     "clip_amd_bench_search", "clip_amd_index_range_search", "clip_amd_index_pairs", "clip_amd_bench_range",
@@ -186,6 +187,17 @@ def lib():
     L.clip_amd_bench_gemm.argtypes = [i32, C.c_int64, C.c_int64, C.c_int64, i32, i32, i32]
     L.clip_amd_test_layernorm.restype = i32
     L.clip_amd_test_layernorm.argtypes = [f32p, f32p, f32p, C.c_float, C.c_int64, C.c_int64, f32p, i32]
+    u16p, i32p = C.POINTER(C.c_uint16), C.POINTER(C.c_int32)
+    L.clip_amd_test_layernorm_ex.restype = i32
+    L.clip_amd_test_layernorm_ex.argtypes = [f32p, C.c_int64, i32, i32p, i32, f32p, f32p, C.c_float, i32, i32, u16p, i32, f32p, i32]
+    L.clip_amd_test_text_embed.restype = i32
+    L.clip_amd_test_text_embed.argtypes = [i32, vp, C.c_int64, i32, i32p, i32p, i32, i32, f32p, i32, f32p, i32, f32p, u16p, i32, f32p, f32p]
+    L.clip_amd_test_im2col.restype = i32
+    L.clip_amd_test_im2col.argtypes = [f32p, i32, i32, i32, i32, i32, u16p]
+    L.clip_amd_test_layernorm_prep.restype = i32
+    L.clip_amd_test_layernorm_prep.argtypes = [f32p, i32, f32p, f32p, C.c_float, i32, i32, f32p, i32, f32p, f32p, i32, i32, f32p, i32, u16p, i32, f32p, f32p]
+    L.clip_amd_test_rows.restype = i32
+    L.clip_amd_test_rows.argtypes = [i32, vp, vp, i32p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, vp]
     L.clip_amd_test_attention.restype = i32
     L.clip_amd_test_attention.argtypes = [f32p, i32, i32, i32, i32, i32, f32p]
     L.clip_amd_test_attention_ex.restype = i32

@@ -1029,22 +1029,225 @@ int clip_amd_test_skinny(int type, const void * w_raw, int64_t N, int64_t K, con
     return rc;
 }
 
-int clip_amd_test_layernorm(const float * x, const float * w, const float * b, float eps, int64_t rows, int64_t h, float * y, int out_f16) {
+// ---- the memory-bound kernels at the two ends of each tower (k_misc.hip, row_stats_kernel of k_skinny.hip) ----
+// Every hook: host pointers in, ONE launch through the launch_* entry point forward.cpp calls, synchronise, host pointers out.  Output buffers are
+// filled with a poison pattern first (f32: quiet NaN, fp16: 0x7e00), so padding and rows the kernel must not write can be checked afterwards.
+static bool test_device() {
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return -1; }
-    DBuf dx((size_t)rows * h * 4), dw((size_t)h * 4), db((size_t)h * 4), dy((size_t)rows * h * 4), dh_((size_t)rows * h * 2);
-    (void)hipMemcpy(dx.p, x, (size_t)rows * h * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(dw.p, w, (size_t)h * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(db.p, b, (size_t)h * 4, hipMemcpyHostToDevice);
-    if (out_f16) {
-        launch_layernorm((const float *)dx.p, (int)h, nullptr, 1, (const float *)dw.p, (const float *)db.p, eps, (int)rows, (int)h, (half_t *)dh_.p, (int)h, nullptr, 0, nullptr);
-        launch_f16_to_f32((const half_t *)dh_.p, (int)h, (float *)dy.p, (int)h, (int)rows, (int)h, nullptr);
-    } else {
-        launch_layernorm((const float *)dx.p, (int)h, nullptr, 1, (const float *)dw.p, (const float *)db.p, eps, (int)rows, (int)h, nullptr, 0, (float *)dy.p, (int)h, nullptr);
-    }
-    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) return -4;
-    (void)hipMemcpy(y, dy.p, (size_t)rows * h * 4, hipMemcpyDeviceToHost);
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return false; }
+    return true;
+}
+static void poison32(const DBuf & d, size_t n) { if (n) (void)hipMemsetD32((hipDeviceptr_t)d.p, 0x7fc00000, n); }
+static void poison16(const DBuf & d, size_t n) { if (n) (void)hipMemsetD16((hipDeviceptr_t)d.p, 0x7e00, n); }
+static void upload(const DBuf & d, const void * src, size_t bytes) { if (src && bytes) (void)hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice); }
+static void download(void * dst, const DBuf & d, size_t bytes) { if (dst && bytes) (void)hipMemcpy(dst, d.p, bytes, hipMemcpyDeviceToHost); }
+// the source rows of a gather (in_rows[r], or r * in_row_mul) stay inside [0, n_src)
+static bool test_rows_ok(const int32_t * in_rows, int64_t in_row_mul, int64_t rows, int64_t n_src) {
+    if (!in_rows) return in_row_mul >= 0 && (rows - 1) * in_row_mul < n_src;
+    for (int64_t r = 0; r < rows; r++)
+        if (in_rows[r] < 0 || in_rows[r] >= n_src) return false;
+    return true;
+}
+static bool test_sync() { return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess; }
+
+int clip_amd_test_layernorm_ex(const float * x, int64_t x_rows, int ldx, const int32_t * in_rows, int in_row_mul, const float * w, const float * b, float eps,
+                               int rows, int h, uint16_t * out16, int ld16, float * out32, int ld32) {
+    if (!test_device()) return -1;
+    if (rows <= 0 || x_rows <= 0 || h <= 0 || h % 4 || ldx < h || (out16 && ld16 < h) || (out32 && ld32 < h) || ldx % 4 || ld16 % 4 || ld32 % 4 ||
+        !test_rows_ok(in_rows, in_row_mul, rows, x_rows)) return -3;
+    const size_t n16 = out16 ? (size_t)rows * ld16 : 0, n32 = out32 ? (size_t)rows * ld32 : 0;
+    DBuf dx((size_t)x_rows * ldx * 4), dr((size_t)rows * 4), dw((size_t)h * 4), db((size_t)h * 4), d16(n16 * 2), d32(n32 * 4);
+    upload(dx, x, (size_t)x_rows * ldx * 4);
+    upload(dr, in_rows, (size_t)rows * 4);
+    upload(dw, w, (size_t)h * 4);
+    upload(db, b, (size_t)h * 4);
+    poison16(d16, n16);
+    poison32(d32, n32);
+    launch_layernorm((const float *)dx.p, ldx, in_rows ? (const int *)dr.p : nullptr, in_row_mul, (const float *)dw.p, (const float *)db.p, eps, rows, h,
+                     out16 ? (half_t *)d16.p : nullptr, ld16, out32 ? (float *)d32.p : nullptr, ld32, nullptr);
+    if (!test_sync()) return -4;
+    download(out16, d16, n16 * 2);
+    download(out32, d32, n32 * 4);
     return 0;
+}
+
+int clip_amd_test_layernorm(const float * x, const float * w, const float * b, float eps, int64_t rows, int64_t h, float * y, int out_f16) {
+    if (!out_f16) return clip_amd_test_layernorm_ex(x, rows, (int)h, nullptr, 1, w, b, eps, (int)rows, (int)h, nullptr, 0, y, (int)h);
+    std::vector<uint16_t> y16((size_t)rows * h);
+    const int rc = clip_amd_test_layernorm_ex(x, rows, (int)h, nullptr, 1, w, b, eps, (int)rows, (int)h, y16.data(), (int)h, nullptr, 0);
+    if (rc == 0)
+        for (size_t i = 0; i < y16.size(); i++) y[i] = f16_bits_to_f32(y16[i]);
+    return rc;
+}
+
+int clip_amd_test_text_embed(int type, const void * tok_raw, int64_t tok_bytes, int h, const int32_t * ids, const int32_t * seq_start, int nseq, int rows,
+                             const float * pos, int n_pos, const float * gamma_next, int centred, float * x, uint16_t * xg, int ldxg, float * stats, float * mu) {
+    if (!test_device()) return -1;
+    if (rows <= 0 || nseq <= 0 || n_pos <= 0 || tok_bytes <= 0 || h <= 0 || h % 64 || h > 2048 || ldxg < h || ldxg % 4) return -3;
+    size_t row_bytes = 0;
+    switch (type) {
+    case 0: row_bytes = (size_t)h * 4; break;
+    case 1: row_bytes = (size_t)h * 2; break;
+    case 2: row_bytes = (size_t)(h / 32) * 18; break;
+    case 3: row_bytes = (size_t)(h / 32) * 20; break;
+    case 6: row_bytes = (size_t)(h / 32) * 22; break;
+    case 7: row_bytes = (size_t)(h / 32) * 24; break;
+    case 8: row_bytes = (size_t)(h / 32) * 34; break;
+    default: return -3;
+    }
+    if (seq_start[0] != 0 || seq_start[nseq] != rows) return -3;
+    for (int i = 0; i < nseq; i++)
+        if (seq_start[i + 1] <= seq_start[i] || seq_start[i + 1] - seq_start[i] > n_pos) return -3;
+    for (int r = 0; r < rows; r++)
+        if (ids[r] < 0 || ((size_t)ids[r] + 1) * row_bytes > (size_t)tok_bytes) return -3;
+    const size_t nx = (size_t)rows * h, ng = (size_t)rows * ldxg;
+    DBuf dt((size_t)tok_bytes), di((size_t)rows * 4), ds((size_t)(nseq + 1) * 4), dp((size_t)n_pos * h * 4), dg((size_t)h * 4), dx(nx * 4), dxg(ng * 2),
+        dst((size_t)rows * 8), dmu((size_t)rows * 4);
+    upload(dt, tok_raw, (size_t)tok_bytes);
+    upload(di, ids, (size_t)rows * 4);
+    upload(ds, seq_start, (size_t)(nseq + 1) * 4);
+    upload(dp, pos, (size_t)n_pos * h * 4);
+    upload(dg, gamma_next, (size_t)h * 4);
+    poison32(dx, nx);
+    poison16(dxg, ng);
+    poison32(dst, (size_t)rows * 2);
+    poison32(dmu, (size_t)rows);
+    if (gamma_next)
+        launch_text_embed((const int32_t *)di.p, (const int *)ds.p, nseq, rows, dt.p, type, (const float *)dp.p, h, (float *)dx.p, nullptr, (const float *)dg.p,
+                          (half_t *)dxg.p, ldxg, (float2 *)dst.p, centred ? (float *)dmu.p : nullptr);
+    else
+        launch_text_embed((const int32_t *)di.p, (const int *)ds.p, nseq, rows, dt.p, type, (const float *)dp.p, h, (float *)dx.p, nullptr);
+    if (!test_sync()) return -4;
+    download(x, dx, nx * 4);
+    download(xg, dxg, ng * 2);
+    download(stats, dst, (size_t)rows * 8);
+    download(mu, dmu, (size_t)rows * 4);
+    return 0;
+}
+
+int clip_amd_test_im2col(const float * imgs, int imgs_f16, int B, int S, int P, int Kpad, uint16_t * col) {
+    if (!test_device()) return -1;
+    if (B <= 0 || S <= 0 || P <= 0 || S % P || Kpad < 3 * P * P || Kpad % 2) return -3;
+    const size_t n_in = (size_t)B * S * S * 3, n_col = (size_t)B * (S / P) * (S / P) * Kpad;
+    DBuf d32(n_in * 4), d16(n_in * 2), dc(n_col * 2);
+    upload(d32, imgs, n_in * 4);
+    poison16(dc, n_col);
+    if (imgs_f16) launch_f32_to_f16((const float *)d32.p, (int)n_in, (half_t *)d16.p, (int)n_in, 1, (int)n_in, (int)n_in, nullptr);
+    launch_im2col(imgs_f16 ? d16.p : d32.p, imgs_f16 != 0, (half_t *)dc.p, B, S, P, Kpad, nullptr);
+    if (!test_sync()) return -4;
+    download(col, dc, n_col * 2);
+    return 0;
+}
+
+int clip_amd_test_layernorm_prep(const float * x, int ldx, const float * w, const float * b, float eps, int rows, int h, const float * gamma_next, int centred,
+                                 const float * class_embd, const float * pos0, int T, int in_place, float * out32, int ld32, uint16_t * xg, int ldxg,
+                                 float * stats, float * mu) {
+    if (!test_device()) return -1;
+    if (in_place) ld32 = ldx;
+    if (rows <= 0 || h <= 0 || h % 64 || h > 2048 || ldx < h || ld32 < h || ldx % 4 || ld32 % 4 || ldxg < h || ldxg % 4 || !gamma_next || (w != nullptr) != (b != nullptr) ||
+        (class_embd != nullptr) != (pos0 != nullptr) || (class_embd && T <= 0)) return -3;
+    const size_t nx = (size_t)rows * ldx, no = (size_t)rows * ld32, ng = (size_t)rows * ldxg;
+    DBuf dx(nx * 4), dw((size_t)h * 4), db((size_t)h * 4), dg((size_t)h * 4), dc((size_t)h * 4), dp((size_t)h * 4), dout(in_place ? 0 : no * 4), dxg(ng * 2),
+        dst((size_t)rows * 8), dmu((size_t)rows * 4);
+    upload(dx, x, nx * 4);
+    upload(dw, w, (size_t)h * 4);
+    upload(db, b, (size_t)h * 4);
+    upload(dg, gamma_next, (size_t)h * 4);
+    upload(dc, class_embd, (size_t)h * 4);
+    upload(dp, pos0, (size_t)h * 4);
+    if (!in_place) poison32(dout, no);
+    poison16(dxg, ng);
+    poison32(dst, (size_t)rows * 2);
+    poison32(dmu, (size_t)rows);
+    launch_layernorm_prep((const float *)dx.p, ldx, w ? (const float *)dw.p : nullptr, w ? (const float *)db.p : nullptr, eps, rows, h,
+                          (float *)(in_place ? dx.p : dout.p), ld32, (const float *)dg.p, (half_t *)dxg.p, ldxg, (float2 *)dst.p, nullptr,
+                          centred ? (float *)dmu.p : nullptr, class_embd ? (const float *)dc.p : nullptr, class_embd ? (const float *)dp.p : nullptr, T);
+    if (!test_sync()) return -4;
+    download(out32, in_place ? dx : dout, no * 4);
+    download(xg, dxg, ng * 2);
+    download(stats, dst, (size_t)rows * 8);
+    download(mu, dmu, (size_t)rows * 4);
+    return 0;
+}
+
+int clip_amd_test_rows(int op, const void * in0, const void * in1, const int32_t * idx, int64_t n0, int64_t n1, int64_t n2, int64_t n3, int64_t n4,
+                       void * out0, void * out1) {
+    if (!test_device()) return -1;
+    if (!in0 || !out0 || n0 <= 0 || n1 <= 0) return -3;
+    switch (op) {
+    case 0: {   // cls_rows: in0 class_embd [h], in1 pos [h] (row 0 of the table), n0 = B, n1 = T, n2 = h; out0 = x [B T][h] f32, in / out
+        const size_t B = (size_t)n0, T = (size_t)n1, h = (size_t)n2;
+        if (!in1 || n2 <= 0) return -3;
+        DBuf dc(h * 4), dp(h * 4), dx(B * T * h * 4);
+        upload(dc, in0, h * 4);
+        upload(dp, in1, h * 4);
+        upload(dx, out0, B * T * h * 4);
+        launch_cls_rows((float *)dx.p, (const float *)dc.p, (const float *)dp.p, (int)B, (int)T, (int)h, nullptr);
+        if (!test_sync()) return -4;
+        download(out0, dx, B * T * h * 4);
+        return 0;
+    }
+    case 1: {   // gather_rows: in0 x f32 [n3][h], in1 a fp16 [n3][h] or NULL, idx in_rows [rows] or NULL, n0 = rows, n1 = in_row_mul, n2 = h; out0 xp f32, out1 ap fp16 [rows][h]
+        const size_t rows = (size_t)n0, h = (size_t)n2, src = (size_t)n3;
+        if (n2 <= 0 || n2 % 4 || n3 <= 0 || !out1 || !test_rows_ok(idx, n1, n0, n3)) return -3;
+        DBuf dx(src * h * 4), da(src * h * 2), dr(rows * 4), dxp(rows * h * 4), dap(rows * h * 2);
+        upload(dx, in0, src * h * 4);
+        upload(da, in1, src * h * 2);
+        upload(dr, idx, rows * 4);
+        poison32(dxp, rows * h);
+        poison16(dap, rows * h);
+        launch_gather_rows((const float *)dx.p, in1 ? (const half_t *)da.p : nullptr, idx ? (const int *)dr.p : nullptr, (int)n1, (int)rows, (int)h, (float *)dxp.p,
+                           in1 ? (half_t *)dap.p : nullptr, nullptr);
+        if (!test_sync()) return -4;
+        download(out0, dxp, rows * h * 4);
+        download(out1, dap, rows * h * 2);
+        return 0;
+    }
+    case 2: {   // l2norm: in0 v [rows][n] f32, n0 = rows, n1 = n, n2 = normalize; out0 [rows][n] f32
+        const size_t n = (size_t)n0 * n1;
+        DBuf dv(n * 4), dout(n * 4);
+        upload(dv, in0, n * 4);
+        poison32(dout, n);
+        launch_l2norm((const float *)dv.p, (float *)dout.p, (int)n0, (int)n1, n2 != 0, nullptr);
+        if (!test_sync()) return -4;
+        download(out0, dout, n * 4);
+        return 0;
+    }
+    case 3: {   // row_stats: in0 x [rows][ldx] f32, n0 = rows, n1 = h, n2 = ldx; out0 = [rows][128 slots][2] f32 (slot 0 := (sum, sum of squares))
+        const size_t rows = (size_t)n0, ldx = (size_t)n2;
+        if (n1 % 4 || n2 < n1 || n2 % 4) return -3;
+        DBuf dx(rows * ldx * 4), dst(rows * 128 * 8);
+        upload(dx, in0, rows * ldx * 4);
+        poison32(dst, rows * 128 * 2);
+        launch_row_stats((const float *)dx.p, (int)ldx, (int)rows, (int)n1, (float2 *)dst.p, nullptr);
+        if (!test_sync()) return -4;
+        download(out0, dst, rows * 128 * 8);
+        return 0;
+    }
+    case 4: {   // f32_to_f16: in0 [rows][lds] f32, n0 = rows, n1 = cols, n2 = cols_pad, n3 = lds, n4 = ldd; out0 [rows][ldd] fp16
+        const size_t rows = (size_t)n0, lds = (size_t)n3, ldd = (size_t)n4;
+        if (n2 < n1 || n3 < n1 || n4 < n2) return -3;
+        DBuf dsrc(rows * lds * 4), ddst(rows * ldd * 2);
+        upload(dsrc, in0, rows * lds * 4);
+        poison16(ddst, rows * ldd);
+        launch_f32_to_f16((const float *)dsrc.p, (int)lds, (half_t *)ddst.p, (int)ldd, (int)rows, (int)n1, (int)n2, nullptr);
+        if (!test_sync()) return -4;
+        download(out0, ddst, rows * ldd * 2);
+        return 0;
+    }
+    case 5: {   // f16_to_f32: in0 [rows][lds] fp16, n0 = rows, n1 = cols, n3 = lds, n4 = ldd; out0 [rows][ldd] f32
+        const size_t rows = (size_t)n0, lds = (size_t)n3, ldd = (size_t)n4;
+        if (n3 < n1 || n4 < n1) return -3;
+        DBuf dsrc(rows * lds * 2), ddst(rows * ldd * 4);
+        upload(dsrc, in0, rows * lds * 2);
+        poison32(ddst, rows * ldd);
+        launch_f16_to_f32((const half_t *)dsrc.p, (int)lds, (float *)ddst.p, (int)ldd, (int)rows, (int)n1, nullptr);
+        if (!test_sync()) return -4;
+        download(out0, ddst, rows * ldd * 4);
+        return 0;
+    }
+    }
+    return -3;
 }
 
 // kernel: 0 = launch_attention (what the layers run), 1 = the whole-row kernel (k_attn.hip), 2 = the streaming kernel (k_attn_long.hip)

@@ -239,6 +239,36 @@ int clip_amd_test_skinny(int type, const void * w_raw, int64_t N, int64_t K, con
 /* y = LayerNorm(x)*w + b, rows x h. out_f16 != 0 rounds the result through fp16. */
 int clip_amd_test_layernorm(const float * x, const float * w, const float * b, float eps, int64_t rows, int64_t h,
                             float * y, int out_f16);
+/* The general form: row r reads x[in_rows[r]] (in_rows != NULL) or x[r * in_row_mul] of x [x_rows][ldx]; out16 (raw fp16 bits, [rows][ld16]) and
+ * out32 ([rows][ld32]), either may be NULL, come out of ONE launch.  Both are filled with a poison pattern first (f32: quiet NaN, fp16: 0x7e00):
+ * whatever the kernel does not write, the padding ld > h included, still holds it.  -3: bad arguments. */
+int clip_amd_test_layernorm_ex(const float * x, int64_t x_rows, int ldx, const int32_t * in_rows, int in_row_mul, const float * w, const float * b,
+                               float eps, int rows, int h, uint16_t * out16, int ld16, float * out32, int ld32);
+/* Text embedding (launch_text_embed): x[r] = dequant(tok_raw[ids[r]]) + pos[r - start of r's sequence], tok_raw a table of ggml type `type`
+ * (tok_bytes bytes), seq_start [nseq + 1] ascending from 0 to rows, pos [n_pos][h].  gamma_next != NULL: also the fold entry, xg [rows][ldxg] raw fp16
+ * bits, stats [rows][2] = (sum, sum of squared deviations), and with centred != 0 mu [rows].  All outputs are poisoned first as above. */
+int clip_amd_test_text_embed(int type, const void * tok_raw, int64_t tok_bytes, int h, const int32_t * ids, const int32_t * seq_start, int nseq, int rows,
+                             const float * pos, int n_pos, const float * gamma_next, int centred, float * x, uint16_t * xg, int ldxg, float * stats,
+                             float * mu);
+/* im2col of the patch convolution (launch_im2col): imgs [B][S][S][3] f32 -> col [B (S/P)^2][Kpad] raw fp16 bits (poisoned first).  imgs_f16 != 0: the
+ * images are first rounded to fp16 on the device (launch_f32_to_f16) and the fp16-input kernel runs. */
+int clip_amd_test_im2col(const float * imgs, int imgs_f16, int B, int S, int P, int Kpad, uint16_t * col);
+/* Entry of the folded layer chain with the pre-LayerNorm (launch_layernorm_prep): y = LayerNorm(x) w + b (w == b == NULL: y = x) -> out32 [rows][ld32];
+ * xg, stats, mu of y as for clip_amd_test_text_embed (gamma_next required).  class_embd / pos0 != NULL: rows r % T == 0 are class_embd + pos0 and are
+ * never read from x.  in_place != 0: out32 aliases x on the device (ld32 := ldx) and returns the x buffer as the launch left it; else out32 is poisoned first. */
+int clip_amd_test_layernorm_prep(const float * x, int ldx, const float * w, const float * b, float eps, int rows, int h, const float * gamma_next,
+                                 int centred, const float * class_embd, const float * pos0, int T, int in_place, float * out32, int ld32,
+                                 uint16_t * xg, int ldxg, float * stats, float * mu);
+/* The small row kernels, one launch each; outputs are poisoned first unless stated.
+ *   op 0 cls_rows:   in0 class_embd [h], in1 pos [h]; n0 = B, n1 = T, n2 = h; out0 = x [B T][h] f32, uploaded first (in / out)
+ *   op 1 gather_rows: in0 x f32 [n3][h], in1 a fp16 [n3][h] or NULL, idx = in_rows [rows] or NULL; n0 = rows, n1 = in_row_mul, n2 = h;
+ *                    out0 = xp f32 [rows][h], out1 = ap fp16 [rows][h]
+ *   op 2 l2norm:     in0 v [rows][n]; n0 = rows, n1 = n, n2 = normalize; out0 [rows][n] f32
+ *   op 3 row_stats:  in0 x [rows][ldx]; n0 = rows, n1 = h, n2 = ldx; out0 [rows][128][2] f32 (slot 0 := (sum, sum of squares))
+ *   op 4 f32_to_f16: in0 [rows][lds] f32; n0 = rows, n1 = cols, n2 = cols_pad, n3 = lds, n4 = ldd; out0 [rows][ldd] fp16
+ *   op 5 f16_to_f32: in0 [rows][lds] fp16; n0 = rows, n1 = cols, n3 = lds, n4 = ldd; out0 [rows][ldd] f32 */
+int clip_amd_test_rows(int op, const void * in0, const void * in1, const int32_t * idx, int64_t n0, int64_t n1, int64_t n2, int64_t n3, int64_t n4,
+                       void * out0, void * out1);
 /* Multi-head attention over nseq sequences of length T each: qkv [nseq*T][3h] (q pre-scaled), out [nseq*T][h]. */
 int clip_amd_test_attention(const float * qkv, int nseq, int T, int h, int n_head, int causal, float * out);
 /* ... with the kernel chosen: 0 = automatic (what the layers run), 1 = the whole-row kernel (d_head 64: T <= 592, other head sizes:

@@ -1,5 +1,6 @@
-"""GPU tier, kernel level: every HIP kernel of the hot path against the oracle / numpy on seeded inputs,
-called through the C ABI test hooks (include/clip_amd.h).  All tests need a real MI355X."""
+"""GPU tier, kernel level: the GEMMs, the small-M kernels, the LayerNorm fold and attention against the oracle / numpy on seeded inputs,
+called through the C ABI test hooks (include/clip_amd.h).  The memory-bound kernels at the two ends of each tower (text embedding, im2col,
+LayerNorm and its fold entry, row copies, L2 normalisation, conversions) are in test_gpu_entry_kernels.py.  All tests need a real MI355X."""
 import ctypes as C
 import os
 
