@@ -73,6 +73,8 @@ AMD_SYMBOLS = [
     "clip_amd_index_create", "clip_amd_index_add", "clip_amd_index_add_device", "clip_amd_index_size", "clip_amd_index_dim",
     "clip_amd_index_search", "clip_amd_index_search_device", "clip_amd_index_save", "clip_amd_index_load", "clip_amd_index_free",
     "clip_amd_bench_search", "clip_amd_index_range_search", "clip_amd_index_pairs", "clip_amd_bench_range",
+    "clip_amd_index_remove", "clip_amd_index_live", "clip_amd_index_live_mask", "clip_amd_index_compact", "clip_amd_index_search_subset",
+    "clip_amd_index_search_subset_device", "clip_amd_index_range_search_subset", "clip_amd_bench_search_subset",
 ]
 
 _lib = None
@@ -233,6 +235,23 @@ def lib():
     L.clip_amd_index_pairs.argtypes = [vp, C.c_float, i64p, f32p, i64p, i64]
     L.clip_amd_bench_range.restype = C.c_float
     L.clip_amd_bench_range.argtypes = [i32, i64, i32, i32, C.c_float, i32]
+    u64p = C.POINTER(C.c_uint64)
+    L.clip_amd_index_remove.restype = i64
+    L.clip_amd_index_remove.argtypes = [vp, i64p, i64]
+    L.clip_amd_index_live.restype = i64
+    L.clip_amd_index_live.argtypes = [vp]
+    L.clip_amd_index_live_mask.restype = C.c_bool
+    L.clip_amd_index_live_mask.argtypes = [vp, u64p]
+    L.clip_amd_index_compact.restype = i64
+    L.clip_amd_index_compact.argtypes = [vp, i64p]
+    L.clip_amd_index_search_subset.restype = C.c_bool
+    L.clip_amd_index_search_subset.argtypes = [vp, f32p, i32, i32, u64p, f32p, i64p]
+    L.clip_amd_index_search_subset_device.restype = C.c_bool
+    L.clip_amd_index_search_subset_device.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+    L.clip_amd_index_range_search_subset.restype = i64
+    L.clip_amd_index_range_search_subset.argtypes = [vp, f32p, i32, C.c_float, u64p, i64p, f32p, i64p, i64]
+    L.clip_amd_bench_search_subset.restype = C.c_float
+    L.clip_amd_bench_search_subset.argtypes = [i32, i64, i32, i32, i32, C.c_float, i32, i32]
     _lib = L
     return L
 
@@ -522,6 +541,28 @@ class Clip:
             pass
 
 
+def allow_words(allow, n):
+    """The uint64 words [(n + 63) // 64] of an allowed set over ids 0 ... n - 1 (the layout of clip_amd_index_search_subset: bit id & 63 of
+    word id >> 6): `allow` is a bool array of length n or an integer array of ids (any order, duplicates allowed).  ValueError for a bool
+    array of another length or an id outside [0, n).  Pure numpy: needs no device."""
+    a = np.asarray(allow)
+    if a.dtype == np.bool_:
+        if a.ndim != 1 or a.shape[0] != n:
+            raise ValueError("a bool allow mask must have one entry per id: shape (%d,), not %r" % (n, a.shape))
+        bits = a
+    else:
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("allow must be a bool mask or an integer array of ids, not %s" % a.dtype)
+        ids = a.reshape(-1).astype(np.int64)
+        if ids.size and (int(ids.min()) < 0 or int(ids.max()) >= n):
+            raise ValueError("allow holds an id outside 0 ... %d" % (n - 1))
+        bits = np.zeros(n, dtype=np.bool_)
+        bits[ids] = True
+    padded = np.zeros((n + 63) // 64 * 64, dtype=np.uint8)
+    padded[:n] = bits
+    return np.packbits(padded, bitorder="little").view("<u8").astype(np.uint64)
+
+
 class Index:
     """Exact cosine nearest-neighbour index on the GPU of a `Clip` (clip_amd_index_*, include/clip_amd.h): rows are L2-normalised and
     stored in f16 (default) or f32; search returns (distances f32 [nq, k], ids int64 [nq, k]) sorted by ascending 1 - cosine, equal
@@ -532,7 +573,13 @@ class Index:
     even; numpy: np.rint((x / amax).astype(np.float32) * np.float32(127))), no L2 normalisation first (the mapping is scale-invariant).
     Queries are quantised the same way at search time.  A vector with amax 0 or any NaN / inf is stored as the zero vector (distance
     exactly 1 to everything).  Distance = 1 - (float)dot * inv_q * inv_r with dot the exact int32 sum q_i r_i and inv = 1 / sqrtf(sum
-    v_i^2) (0 for the zero vector): the cosine distance of the stored integer vectors, bit-reproducible like the other dtypes."""
+    v_i^2) (0 for the zero vector): the cosine distance of the stored integer vectors, bit-reproducible like the other dtypes.
+
+    remove(ids) marks rows as removed: no search, range_search or pairs returns them again, ids are not renumbered and len() keeps
+    counting every id ever given (`live` = len minus the removed rows); compact() drops them from device memory and renumbers the
+    survivors.  search and range_search take `allow`, a bool mask of length len(index) or an array of ids: only those rows (and of those
+    only the live ones) are eligible.  Either way the result is, bit for bit, that of an index that only ever held the eligible rows.
+    save() refuses an index that holds removed rows: compact() first."""
 
     DTYPES = {"f32": 0, "f16": 1, "i8": 3}
 
@@ -574,23 +621,63 @@ class Index:
         if not lib().clip_amd_index_add_device(self._live(), C.c_void_p(ptr), int(n)):
             raise RuntimeError("clip_amd_index_add_device failed (see stderr)")
 
-    def search(self, queries, k):
+    def remove(self, ids):
+        """Mark the rows `ids` (each in [0, len)) as removed; duplicates and rows removed before are fine.  Returns how many rows this call
+        took from live to removed."""
+        a = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        r = int(lib().clip_amd_index_remove(self._live(), a.ctypes.data_as(C.POINTER(C.c_int64)), a.size))
+        if r < 0:
+            raise RuntimeError("clip_amd_index_remove failed (see stderr)")
+        return r
+
+    @property
+    def live(self):
+        """rows that are not removed: len(index) minus the removed ones"""
+        return int(lib().clip_amd_index_live(self._live()))
+
+    def live_mask(self):
+        """bool [len]: True for a live row"""
+        n = len(self)
+        words = np.zeros((n + 63) // 64, dtype=np.uint64)
+        if not lib().clip_amd_index_live_mask(self._live(), words.ctypes.data_as(C.POINTER(C.c_uint64))):
+            raise RuntimeError("clip_amd_index_live_mask failed (see stderr)")
+        return np.unpackbits(words.astype("<u8").view(np.uint8), bitorder="little")[:n].astype(np.bool_)
+
+    def compact(self):
+        """Drop the removed rows; the survivors keep their order and become ids 0 ... live - 1.  Returns new_ids int64 [old len]: each old
+        id's new id, -1 for a removed row."""
+        new_ids = np.empty(len(self), dtype=np.int64)
+        if lib().clip_amd_index_compact(self._live(), new_ids.ctypes.data_as(C.POINTER(C.c_int64))) < 0:
+            raise RuntimeError("clip_amd_index_compact failed (see stderr)")
+        return new_ids
+
+    def _allow(self, allow):
+        """(keep-alive array, pointer) of an allowed set; (None, NULL) for None"""
+        if allow is None:
+            return None, None
+        words = allow_words(allow, len(self))
+        return words, words.ctypes.data_as(C.POINTER(C.c_uint64))
+
+    def search(self, queries, k, allow=None):
+        """(distances f32 [nq, k], ids int64 [nq, k]); `allow` (bool mask [len] or ids): only those rows are eligible"""
         q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
         nq = q.shape[0]
+        words, wp = self._allow(allow)
         dist = np.empty((nq, k), dtype=np.float32)
         ids = np.empty((nq, k), dtype=np.int64)
-        if not lib().clip_amd_index_search(self._live(), _fp(q), nq, int(k), _fp(dist), ids.ctypes.data_as(C.POINTER(C.c_int64))):
-            raise RuntimeError("clip_amd_index_search failed (see stderr)")
+        if not lib().clip_amd_index_search_subset(self._live(), _fp(q), nq, int(k), wp, _fp(dist), ids.ctypes.data_as(C.POINTER(C.c_int64))):
+            raise RuntimeError("clip_amd_index_search%s failed (see stderr)" % ("" if allow is None else "_subset"))
         return dist, ids
 
-    def range_search(self, queries, radius):
+    def range_search(self, queries, radius, allow=None):
         """Every stored row within `radius` of each query (distance <= radius in f32, the distance `search` reports): (lims int64 [nq + 1],
         distances f32 [total], ids int64 [total]); query q's results are [lims[q], lims[q + 1]), nearest first, equal distances lower id
-        first."""
+        first.  `allow` (bool mask [len] or ids): only those rows are eligible."""
         q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
         nq = q.shape[0]
-        call = lambda lims, d, i, cap: lib().clip_amd_index_range_search(self._live(), _fp(q), nq, float(radius), lims, d, i, cap)
-        return self._join(call, nq + 1, 64 * nq + 1024, "clip_amd_index_range_search")
+        words, wp = self._allow(allow)
+        call = lambda lims, d, i, cap: lib().clip_amd_index_range_search_subset(self._live(), _fp(q), nq, float(radius), wp, lims, d, i, cap)
+        return self._join(call, nq + 1, 64 * nq + 1024, "clip_amd_index_range_search" + ("" if allow is None else "_subset"))
 
     def pairs(self, radius):
         """Every pair of rows i < j at distance <= radius, d(i, j) being what `search` reports for row j when queried with the vector added
@@ -622,6 +709,12 @@ class Index:
                                                   C.c_void_p(d_ids)):
             raise RuntimeError("clip_amd_index_search_device failed (see stderr)")
 
+    def search_subset_device(self, d_queries, n_queries, k, d_allow, d_distances, d_ids):
+        """search_device over the rows allowed by the uint64 words at device address d_allow (0 / None: every row)"""
+        if not lib().clip_amd_index_search_subset_device(self._live(), C.c_void_p(d_queries), int(n_queries), int(k), C.c_void_p(d_allow or None),
+                                                         C.c_void_p(d_distances), C.c_void_p(d_ids)):
+            raise RuntimeError("clip_amd_index_search_subset_device failed (see stderr)")
+
     def save(self, path):
         if not lib().clip_amd_index_save(self._live(), os.fsencode(path)):
             raise RuntimeError("clip_amd_index_save failed for %r (see stderr)" % (path,))
@@ -646,6 +739,13 @@ class Index:
 def bench_search(dtype, n, dim, n_queries, k, iters=10):
     """Microseconds per clip_amd_index_search_device on seeded random data (clip_amd_bench_search); < 0 on error."""
     return float(lib().clip_amd_bench_search(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(k), int(iters)))
+
+
+def bench_search_subset(dtype, n, dim, n_queries, k, allowed_fraction, contiguous, iters=10):
+    """Microseconds per clip_amd_index_search_subset_device on the data of bench_search with a seeded allowed set: a random selection of
+    `allowed_fraction` of the ids or, `contiguous`, one id range of that size (clip_amd_bench_search_subset); < 0 on error."""
+    return float(lib().clip_amd_bench_search_subset(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(k), float(allowed_fraction),
+                                                    int(bool(contiguous)), int(iters)))
 
 
 def bench_range(dtype, n, dim, n_queries, radius, iters=10):

@@ -13,6 +13,12 @@
 //                             The score matrix never leaves the registers.  Tiles: range search — row tiles fastest; pairs — only row
 //                             tile >= query tile, in 8 x 8 super-tiles, each group of workgroups that shares an L2 (blockIdx % 8) working
 //                             through its own super-tiles, so 8 row and 8 query tiles serve 64 tiles from one L2.
+//                             Masked instantiation (template parameter MASKED; the unmasked one runs when nothing was removed and no
+//                             subset was given): p.rmask holds one bit per row (the live bitmap ANDed with the allowed set; bit row & 31
+//                             of 32-bit word row >> 5, zeros past n up to a multiple of 128).  A row tile whose 128 bits are all zero is
+//                             skipped before anything is loaded, and the emit condition tests the row's bit; pairs test the same mask
+//                             on the query side too (p.qmask: a removed row is neither i nor j) and skip a query tile without a set bit.
+//                             The distances still come from the same chain.
 //   join_scatter_kernel       hit list -> segment q = [offs[q], offs[q + 1]) through a per-query cursor (any order inside a segment)
 //   join_sort_kernel          one wave per segment: runs of <= 1024 sorted in LDS with wave_sort (strict order: distance, then id)
 //   join_merge_kernel         one pass of the merge of sorted runs of width w inside every segment longer than w: an element's slot is
@@ -60,6 +66,8 @@ struct JoinParams {
     unsigned long long * total;
     Hit * hits;
     int64_t hit_cap;
+    const uint32_t * rmask;       // masked: one bit per row, [ceil(n / 128) * 4] words
+    const uint32_t * qmask;       // masked pairs: the same bitmap for the query side, else NULL
 };
 
 // lower-triangle index t = a (a + 1) / 2 + b, 0 <= b <= a
@@ -71,7 +79,7 @@ __device__ __forceinline__ void tri_index(int64_t t, int64_t & a, int64_t & b) {
     b = t - x * (x + 1) / 2;
 }
 
-template <typename T, int WR, int WQ, int WQS>
+template <typename T, int WR, int WQ, int WQS, bool MASKED>
 __global__ void __launch_bounds__(JOIN_THREADS) join_kernel(const JoinParams p) {
     constexpr int WRS = 4 / WQS;
     static_assert(WRS * WQS == 4 && WRS * WR * 16 == JOIN_BM, "four waves cover 128 rows");
@@ -106,6 +114,14 @@ __global__ void __launch_bounds__(JOIN_THREADS) join_kernel(const JoinParams p) 
             ti = u - tj * p.row_tiles;
         }
         const int64_t r0 = ti * JOIN_BM, q0 = tj * BN;
+        if constexpr (MASKED) {                                // a tile without an eligible row (pairs: or query): nothing to emit
+            const u32x4 mr = *(const u32x4 *)(p.rmask + ti * 4);
+            if ((mr[0] | mr[1] | mr[2] | mr[3]) == 0) continue;
+            if (p.qmask) {                                     // pairs: BN = 128 queries, four words again
+                const u32x4 mq = *(const u32x4 *)(p.qmask + tj * 4);
+                if ((mq[0] | mq[1] | mq[2] | mq[3]) == 0) continue;
+            }
+        }
         Acc acc[WR][WQ];
 #pragma unroll
         for (int i = 0; i < WR; i++)
@@ -163,10 +179,17 @@ __global__ void __launch_bounds__(JOIN_THREADS) join_kernel(const JoinParams p) 
             if constexpr (sizeof(T) == 1) qv = p.qinv[qi < p.nq ? qi : p.nq - 1];
 #pragma unroll
             for (int i = 0; i < WR; i++) {
+                unsigned mbits = 0xffffu;                      // the 16 rows of this fragment: 16 aligned bits of one mask word
+                if constexpr (MASKED) {
+                    const int64_t rb = r0 + (wr * WR + i) * 16;
+                    mbits = (p.rmask[rb >> 5] >> (int)(rb & 16)) & 0xffffu;
+                    if (p.qmask && qi < p.nq && !((p.qmask[qi >> 5] >> (int)(qi & 31)) & 1u)) mbits = 0;
+                }
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     const int64_t row = r0 + (wr * WR + i) * 16 + fgrp * 4 + r;
                     if (qi >= p.nq || row >= p.n || (p.pairs && row <= qi)) continue;
+                    if (!((mbits >> (fgrp * 4 + r)) & 1u)) continue;
                     float rv = 0.f;
                     if constexpr (sizeof(T) == 1) rv = p.rinv[row];
                     const float d = scan_distance(acc[i][j][r], qv, rv);
@@ -265,16 +288,16 @@ __global__ void __launch_bounds__(256) join_plant_kernel(float * __restrict__ x,
     x[i] = x[i - 37 * (int64_t)dim] + 0.01f * ((float)(z >> 40) * (1.0f / 8388608.0f) - 1.0f);
 }
 
-template <typename T, int WR, int WQ, int WQS>
-bool launch_join_t(JoinParams p, hipStream_t stream) {
+template <typename T, int WR, int WQ, int WQS, bool MASKED>
+bool launch_join_m(JoinParams p, hipStream_t stream) {
     constexpr int BN = WQS * WQ * 16;
     static unsigned long long lds_done = 0;
     const size_t lds = (size_t)(JOIN_BM + BN) * JOIN_LROW;
-    if (lds > 65536) opt_in_dynamic_lds(join_kernel<T, WR, WQ, WQS>, lds, lds_done);
+    if (lds > 65536) opt_in_dynamic_lds(join_kernel<T, WR, WQ, WQS, MASKED>, lds, lds_done);
     int dev = 0, cus = 0, per_cu = 0;
     (void)hipGetDevice(&dev);
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, join_kernel<T, WR, WQ, WQS>, JOIN_THREADS, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, join_kernel<T, WR, WQ, WQS, MASKED>, JOIN_THREADS, lds) != hipSuccess || per_cu < 1) per_cu = 1;
     (void)hipGetLastError();
     const int64_t resident = (int64_t)cus * per_cu;
     p.row_tiles = (p.n + JOIN_BM - 1) / JOIN_BM;
@@ -287,8 +310,13 @@ bool launch_join_t(JoinParams p, hipStream_t stream) {
         p.n_slots = p.row_tiles * ((p.nq + BN - 1) / BN);
         grid = std::min(resident, p.n_slots);
     }
-    hipLaunchKernelGGL((join_kernel<T, WR, WQ, WQS>), dim3((unsigned)grid), dim3(JOIN_THREADS), lds, stream, p);
+    hipLaunchKernelGGL((join_kernel<T, WR, WQ, WQS, MASKED>), dim3((unsigned)grid), dim3(JOIN_THREADS), lds, stream, p);
     return hipGetLastError() == hipSuccess;
+}
+
+template <typename T, int WR, int WQ, int WQS>
+bool launch_join_t(const JoinParams & p, hipStream_t stream) {
+    return p.rmask ? launch_join_m<T, WR, WQ, WQS, true>(p, stream) : launch_join_m<T, WR, WQ, WQS, false>(p, stream);
 }
 
 unsigned grid_of(int64_t items) { return (unsigned)std::min<int64_t>((items + 255) / 256, 65536); }
@@ -296,8 +324,10 @@ unsigned grid_of(int64_t items) { return (unsigned)std::min<int64_t>((items + 25
 }  // namespace
 
 bool launch_join(const void * rows, const float * rinv, int64_t n, const void * q, const float * qinv, int64_t nq, int Dpad, int dtype, bool pairs,
-                 float radius, int * count, unsigned long long * total, void * hits, int64_t hit_cap, hipStream_t stream) {
+                 float radius, int * count, unsigned long long * total, void * hits, int64_t hit_cap, const uint32_t * mask, hipStream_t stream) {
     JoinParams p = {};
+    p.rmask = mask;
+    p.qmask = pairs ? mask : nullptr;
     p.rows = (const unsigned char *)rows;
     p.rinv = rinv;
     p.q = (const unsigned char *)q;

@@ -26,12 +26,36 @@
 //                            of any of its queries that could overflow in the next iteration (bitonic sort in LDS, one buffer per wave),
 //                            keeps the best k and raises the threshold.  At the end every query's best k, sorted, is left at the head
 //                            of its buffer.
+//                            Masked instantiation (template parameter MASKED; the unmasked one is what runs when nothing was removed and no
+//                            subset was given): p.mask holds one bit per row (bit row & 31 of 32-bit word row >> 5), the live bitmap ANDed
+//                            with the caller's allowed set.  A wave's 16 rows start at a multiple of 16, so their bits are 16 aligned bits
+//                            of one word: all zero — the wave skips the row loads and the MFMA chain of that iteration (those rows are never
+//                            read from HBM); otherwise the same chain runs and a distance is pushed only if its row's bit is set as well.
+//                            Rows are still visited in ascending id, so the tie rule holds; a chunk without an eligible row leaves k
+//                            sorted empty slots.
 //   search_merge_kernel      pairwise merge of two sorted k-lists per query keeping the best k (rank by binary search: a strict total order
 //                            — distance ascending, id ascending — so each element's output slot is unique); log2(chunks) launches.
 //   search_finish_kernel     ids widened to int64; empty slots -> id -1, distance +inf.
-// Plain launches on the caller's stream, no LDS past 64 KB but the sort buffers of k > 512, no scratch.  The score chain (ld_step, mfma_step,
+//   live_set_kernel          row bitmap: sets the bits of rows [lo, hi) (add, load, compact), one thread per 32-bit word.
+//   live_remove_kernel       one thread per id: integer atomic AND clears the row's bit; the bits that were still set are counted (integer
+//                            atomic add), so the count does not depend on the order and a duplicate id counts once.
+//   mask_and_kernel          effective mask = live & allow, word by word; allow words past (n + 63) / 64 * 2 read as zero, and live holds
+//                            zeros at positions >= n, so stray allow bits never reach the scan.
+//   compact_ids_kernel       new id of every row: workgroup b owns 2048 bitmap words (65536 rows).  Its base is the popcount of every word
+//                            before them (each workgroup sums them itself, 16 bytes per lane per load: no workgroup waits for another),
+//                            the words' exclusive prefix inside the workgroup comes from a shuffle scan, and new_ids[row] = base + prefix
+//                            + popcount of the lower bits of its word, -1 for a cleared bit.  The workgroup of the last word writes the
+//                            survivor count.  Known limit: the recount grows with the square of the workgroup count (n^2 / 2^22 words
+//                            read in all: 1 M rows 1 MB, 2^31 rows ~4 TB) and a 1 M-row index gets 16 workgroups; a first pass of one
+//                            popcount per workgroup would make it linear at the price of a second launch.
+//   compact_gather_kernel    survivor rows (16 bytes per thread) and, i8, their inverse norms, copied bit for bit from the old allocation
+//                            to row new_ids[row] of a fresh one: source and destination never alias.
+//   search_fill_allow_kernel benchmark data: an allowed set of a given fraction, seeded random or one contiguous id range.
+// Plain launches on the caller's stream, no LDS past 64 KB but the sort buffers of k > 512 (compact_ids_kernel: 16 KB static; the mask needs
+// none), no scratch.  The score chain (ld_step, mfma_step,
 // scan_distance), the candidate order and wave_sort live in search_common.h, shared with k_join.hip (range search / pairs).
 
+#include <algorithm>
 #include <cfloat>
 #include <climits>
 
@@ -143,6 +167,7 @@ struct ScanParams {
     int64_t rows_per_chunk;
     const float * rinv;    // i8: [>= n rounded up to 64] row inverse norms
     const float * qinv;    // i8: [nq_pad] query inverse norms
+    const uint32_t * mask; // masked scan: one bit per row, at least n rounded up to 32 bits
 };
 
 // keep the best min(k, cnt) of a query's candidates (sorted, at the head of its buffer); returns the new count.  `final`: write all k
@@ -162,7 +187,7 @@ __device__ int wave_select(Cand * buf, int cnt, int k, int P, bool final, float 
     return cnt < k ? cnt : k;
 }
 
-template <typename T, int QT>
+template <typename T, int QT, bool MASKED>
 __global__ void __launch_bounds__(SCAN_THREADS) search_scan_kernel(const ScanParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int QB = 16 * QT;
@@ -190,7 +215,9 @@ __global__ void __launch_bounds__(SCAN_THREADS) search_scan_kernel(const ScanPar
 
     for (int it = 0; it < nit; it++) {
         const int64_t r0 = lo + (int64_t)it * ROWS_PER_ITER + wave * 16;
-        if (r0 < hi) {
+        unsigned mbits = 0xffffu;                                             // the wave's 16 rows: 16 aligned bits of one mask word
+        if constexpr (MASKED) mbits = r0 < hi ? (p.mask[r0 >> 5] >> (int)(r0 & 16)) & 0xffffu : 0u;
+        if (r0 < hi && mbits != 0) {
             int64_t gr = r0 + frow;
             gr = gr < p.n ? gr : p.n - 1;                                     // rows past the end compute on the last row, never pushed
             const T * grow = (const T *)p.rows + gr * p.Dpad;
@@ -229,7 +256,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) search_scan_kernel(const ScanPar
                 for (int r = 0; r < 4; r++) {
                     const int64_t row = r0 + fgrp * 4 + r;
                     const float d = scan_distance(acc[j][r], qinv, rinv[r]);
-                    if (row < hi && d < t) {
+                    if (row < hi && d < t && ((mbits >> (fgrp * 4 + r)) & 1u)) {
                         const int slot = atomicAdd(&cnt[ql], 1);
                         buf[slot] = Cand{d, (int)row};
                     }
@@ -315,14 +342,153 @@ __global__ void __launch_bounds__(256) search_fill_random_kernel(float * __restr
     x[i] = (float)(z >> 40) * (1.0f / 8388608.0f) - 1.0f;
 }
 
-template <typename T, int QT>
-bool launch_scan_t(const ScanParams & p, int n_chunks, hipStream_t stream) {
+template <typename T, int QT, bool MASKED>
+bool launch_scan_m(const ScanParams & p, int n_chunks, hipStream_t stream) {
     static unsigned long long lds_done = 0;
     const size_t lds = (size_t)2 * 16 * QT * 4 + (size_t)4 * 2 * p.P * 4;
-    if (lds > 65536) opt_in_dynamic_lds(search_scan_kernel<T, QT>, lds, lds_done);
+    if (lds > 65536) opt_in_dynamic_lds(search_scan_kernel<T, QT, MASKED>, lds, lds_done);
     const dim3 grid(n_chunks, (p.nq + 16 * QT - 1) / (16 * QT));
-    hipLaunchKernelGGL((search_scan_kernel<T, QT>), grid, dim3(SCAN_THREADS), lds, stream, p);
+    hipLaunchKernelGGL((search_scan_kernel<T, QT, MASKED>), grid, dim3(SCAN_THREADS), lds, stream, p);
     return hipGetLastError() == hipSuccess;
+}
+
+template <typename T, int QT>
+bool launch_scan_t(const ScanParams & p, int n_chunks, hipStream_t stream) {
+    return p.mask ? launch_scan_m<T, QT, true>(p, n_chunks, stream) : launch_scan_m<T, QT, false>(p, n_chunks, stream);
+}
+
+__global__ void __launch_bounds__(256) live_set_kernel(uint32_t * __restrict__ live, int64_t lo, int64_t hi) {
+    const int64_t w = (lo >> 5) + (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w > ((hi - 1) >> 5)) return;
+    const int64_t b0 = w * 32;
+    uint32_t m = 0xffffffffu;
+    if (lo > b0) m &= 0xffffffffu << (int)(lo - b0);
+    if (hi < b0 + 32) m &= 0xffffffffu >> (int)(b0 + 32 - hi);
+    atomicOr(live + w, m);
+}
+
+__global__ void __launch_bounds__(256) live_remove_kernel(uint32_t * __restrict__ live, const int64_t * __restrict__ ids, int64_t n,
+                                                          unsigned long long * __restrict__ removed) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t id = ids[i];
+    const uint32_t bit = 1u << (int)(id & 31);
+    if (atomicAnd(live + (id >> 5), ~bit) & bit) atomicAdd(removed, 1ull);
+}
+
+__global__ void __launch_bounds__(256) mask_and_kernel(const uint32_t * __restrict__ live, const uint32_t * __restrict__ allow, int64_t allow_words,
+                                                       uint32_t * __restrict__ out, int64_t words) {
+    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w < words) out[w] = w < allow_words ? live[w] & allow[w] : 0u;
+}
+
+constexpr int COMPACT_WORDS = 2048;           // bitmap words per workgroup (8 per thread)
+
+__device__ __forceinline__ int block_sum_256(int v, int * red) {
+    v = wave_sum_i(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const int s = red[0] + red[1] + red[2] + red[3];
+    __syncthreads();
+    return s;
+}
+
+// live: [words rounded up to 4] (zeros past n); new_ids [n]
+__global__ void __launch_bounds__(256) compact_ids_kernel(const uint32_t * __restrict__ live, int64_t n, int64_t * __restrict__ new_ids,
+                                                          unsigned long long * __restrict__ total) {
+    __shared__ uint32_t sw[COMPACT_WORDS];
+    __shared__ int sp[COMPACT_WORDS];
+    __shared__ int red[4];
+    __shared__ int wtot[4];
+    const int64_t words = (n + 31) >> 5;
+    const int64_t w0 = (int64_t)blockIdx.x * COMPACT_WORDS;
+    // popcount of every word before this workgroup's (w0 is a multiple of 4: whole 16-byte groups)
+    unsigned long long before = 0;
+    const u32x4 * l4 = (const u32x4 *)live;
+    for (int64_t g0 = 0; g0 < w0 / 4; g0 += 256 * 1024) {        // pieces of 2^20 words: an int holds a piece's count
+        const int64_t g1 = g0 + 256 * 1024 < w0 / 4 ? g0 + 256 * 1024 : w0 / 4;
+        int c = 0;
+        for (int64_t g = g0 + threadIdx.x; g < g1; g += 256) {
+            const u32x4 v = l4[g];
+            c += __popc(v[0]) + __popc(v[1]) + __popc(v[2]) + __popc(v[3]);
+        }
+        before += (unsigned long long)block_sum_256(c, red);
+    }
+    // this workgroup's words: thread t takes words 8 t ... 8 t + 7
+    int mine = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const int64_t w = w0 + threadIdx.x * 8 + j;
+        const uint32_t v = w < words ? live[w] : 0u;
+        sw[threadIdx.x * 8 + j] = v;
+        mine += __popc(v);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = mine;                                              // inclusive scan of `mine` over the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int o = __shfl_up(incl, off, 64);
+        if (lane >= off) incl += o;
+    }
+    if (lane == 63) wtot[wave] = incl;
+    __syncthreads();
+    int excl = incl - mine;
+    for (int u = 0; u < wave; u++) excl += wtot[u];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        sp[threadIdx.x * 8 + j] = excl;
+        excl += __popc(sw[threadIdx.x * 8 + j]);
+    }
+    __syncthreads();
+    const int64_t row0 = w0 * 32;
+    for (int i = threadIdx.x; i < COMPACT_WORDS * 32; i += 256) {
+        const int64_t row = row0 + i;
+        if (row >= n) break;
+        const uint32_t v = sw[i >> 5];
+        const int b = i & 31;
+        new_ids[row] = (v >> b) & 1u ? (int64_t)(before + (unsigned long long)(sp[i >> 5] + __popc(v & ((1u << b) - 1u)))) : (int64_t)-1;
+    }
+    if (w0 + COMPACT_WORDS >= words && threadIdx.x == 255) *total = before + (unsigned long long)excl;
+}
+
+__global__ void __launch_bounds__(256) compact_gather_kernel(const u32x4 * __restrict__ src, u32x4 * __restrict__ dst, const float * __restrict__ sinv,
+                                                             float * __restrict__ dinv, const int64_t * __restrict__ new_ids, int64_t n,
+                                                             int pieces) {
+    const int64_t items = n * pieces;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < items; i += (int64_t)gridDim.x * 256) {
+        const int64_t row = i / pieces;
+        const int piece = (int)(i - row * pieces);
+        const int64_t to = new_ids[row];
+        if (to < 0) continue;
+        dst[to * pieces + piece] = src[i];
+        if (sinv && piece == 0) dinv[to] = sinv[row];
+    }
+}
+
+__global__ void __launch_bounds__(256) search_fill_allow_kernel(uint32_t * __restrict__ allow, int64_t n, int64_t words, float fraction,
+                                                                int contiguous, uint64_t seed) {
+    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= words) return;
+    int64_t cnt = (int64_t)((double)fraction * (double)n + 0.5);
+    cnt = cnt < 0 ? 0 : (cnt > n ? n : cnt);
+    const int64_t start = (n - cnt) / 2;
+    uint32_t v = 0;
+    for (int b = 0; b < 32; b++) {
+        const int64_t id = w * 32 + b;
+        if (id >= n) break;
+        bool on;
+        if (contiguous) {
+            on = id >= start && id < start + cnt;
+        } else {
+            uint64_t z = seed + (uint64_t)id * 0x9E3779B97F4A7C15ull;
+            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+            z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+            z ^= z >> 31;
+            on = (float)(z >> 40) * (1.0f / 16777216.0f) < fraction;
+        }
+        v |= (uint32_t)on << b;
+    }
+    allow[w] = v;
 }
 
 }  // namespace
@@ -357,8 +523,9 @@ void launch_search_row_inv(const void * rows, int64_t n, int Dpad, float * inv, 
 }
 
 bool launch_search_scan(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq, int qt,
-                        int k, void * cand, int n_chunks, int64_t rows_per_chunk, hipStream_t stream) {
+                        int k, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask, hipStream_t stream) {
     ScanParams p;
+    p.mask = mask;
     p.rows = rows;
     p.q = q;
     p.rinv = rinv;
@@ -398,6 +565,45 @@ void launch_search_finish(const void * in, int64_t in_stride, int nq, int k, flo
 void launch_search_fill_random(float * x, int64_t n, uint64_t seed, hipStream_t stream) {
     if (n <= 0) return;
     hipLaunchKernelGGL(search_fill_random_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, n, seed);
+}
+
+void launch_live_set(uint32_t * live, int64_t lo, int64_t hi, hipStream_t stream) {
+    if (hi <= lo) return;
+    const int64_t words = ((hi - 1) >> 5) - (lo >> 5) + 1;
+    hipLaunchKernelGGL(live_set_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, live, lo, hi);
+}
+
+void launch_live_remove(uint32_t * live, const int64_t * ids, int64_t n, unsigned long long * removed, hipStream_t stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(live_remove_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, live, ids, n, removed);
+}
+
+void launch_mask_and(const uint32_t * live, const uint32_t * allow, int64_t allow_words, uint32_t * out, int64_t words, hipStream_t stream) {
+    if (words <= 0) return;
+    hipLaunchKernelGGL(mask_and_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, live, allow, allow_words, out, words);
+}
+
+void launch_compact_ids(const uint32_t * live, int64_t n, int64_t * new_ids, unsigned long long * total, hipStream_t stream) {
+    if (n <= 0) return;
+    const int64_t words = (n + 31) >> 5;
+    hipLaunchKernelGGL(compact_ids_kernel, dim3((unsigned)((words + COMPACT_WORDS - 1) / COMPACT_WORDS)), dim3(256), 0, stream, live, n, new_ids,
+                       total);
+}
+
+void launch_compact_gather(const void * src, void * dst, const float * sinv, float * dinv, const int64_t * new_ids, int64_t n, int64_t row_bytes,
+                           hipStream_t stream) {
+    if (n <= 0) return;
+    const int pieces = (int)(row_bytes / 16);
+    const int64_t blocks = std::min<int64_t>((n * pieces + 255) / 256, 1 << 20);
+    hipLaunchKernelGGL(compact_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const u32x4 *)src, (u32x4 *)dst, sinv, dinv, new_ids, n,
+                       pieces);
+}
+
+void launch_search_fill_allow(uint32_t * allow, int64_t n, float fraction, bool contiguous, uint64_t seed, hipStream_t stream) {
+    const int64_t words = (n + 63) / 64 * 2;
+    if (words <= 0) return;
+    hipLaunchKernelGGL(search_fill_allow_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, allow, n, words, fraction,
+                       contiguous ? 1 : 0, seed);
 }
 
 }  // namespace clipamd

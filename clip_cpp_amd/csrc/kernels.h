@@ -289,6 +289,9 @@ enum { SEARCH_F32 = 0, SEARCH_F16 = 1, SEARCH_I8 = 3 };
 // f32 / fp16: stored rows / queries [rows][Dpad], Dpad = 32 m, L2-normalised (launch_search_normalize).  i8: [rows][Dpad] int8, Dpad = 64 m, quantised rint(x / max|x| * 127) with inv = 1 / sqrt(sum q^2) per
 // vector (launch_search_quantize; launch_search_row_inv recomputes inv of stored rows); the scan reads rinv as 16-byte groups, so a row
 // inv array holds at least n rounded up to 64 floats.
+// mask (scan and join; NULL: every row): one bit per row, bit row & 31 of 32-bit word row >> 5 (little-endian halves of the 64-bit words of
+// clip_amd.h), the live bitmap ANDed with the caller's allowed set, zeros at positions >= n up to a multiple of 128 rows.  A row whose bit
+// is 0 is never a candidate; an aligned group of 16 such rows is not read.
 // Candidate workspace of a scan: [n_chunks][nq][search_candidate_capacity(k)] (score f32, id i32) pairs; each chunk's best k, sorted, ends
 // at the head of its (chunk, query) slot.  Merge: lists 2i, 2i + 1 -> list i ([n_out][nq][k] pairs).  Finish: one list per query ->
 // distances (1 - score) and int64 ids, empty slots -1 / +inf.
@@ -298,10 +301,22 @@ void launch_search_normalize(const float * src, int64_t n_src, int64_t n_rows, i
 void launch_search_quantize(const float * src, int64_t n_src, int64_t n_rows, int dim, int Dpad, void * dst, float * inv, hipStream_t stream);
 void launch_search_row_inv(const void * rows, int64_t n, int Dpad, float * inv, hipStream_t stream);
 bool launch_search_scan(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq, int qt,
-                        int k, void * cand, int n_chunks, int64_t rows_per_chunk, hipStream_t stream);
+                        int k, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask, hipStream_t stream);
 void launch_search_merge(const void * in, int64_t in_stride, int n_in, void * out, int nq, int k, hipStream_t stream);
 void launch_search_finish(const void * in, int64_t in_stride, int nq, int k, float * dist, int64_t * ids, hipStream_t stream);
 void launch_search_fill_random(float * x, int64_t n, uint64_t seed, hipStream_t stream);
+// Row bitmap (layout as mask above).  set: bits [lo, hi) := 1.  remove: clears the bit of every ids[i] (device, each in range) and adds the
+// number of bits that were set to *removed.  mask_and: out[w] = live[w] & allow[w], allow words at w >= allow_words read as 0.
+// compact_ids: new_ids[row] = rank of the row among the set bits, -1 for a cleared bit; *total = the number of set bits (live: words
+// rounded up to 4, zeros past n).  compact_gather: rows (row_bytes each, a multiple of 16) and, sinv != NULL, inverse norms of the set
+// rows -> row new_ids[row] of dst / dinv, which must not alias src / sinv.  fill_allow: benchmark allowed set of (n + 63) / 64 * 2 words.
+void launch_live_set(uint32_t * live, int64_t lo, int64_t hi, hipStream_t stream);
+void launch_live_remove(uint32_t * live, const int64_t * ids, int64_t n, unsigned long long * removed, hipStream_t stream);
+void launch_mask_and(const uint32_t * live, const uint32_t * allow, int64_t allow_words, uint32_t * out, int64_t words, hipStream_t stream);
+void launch_compact_ids(const uint32_t * live, int64_t n, int64_t * new_ids, unsigned long long * total, hipStream_t stream);
+void launch_compact_gather(const void * src, void * dst, const float * sinv, float * dinv, const int64_t * new_ids, int64_t n, int64_t row_bytes,
+                           hipStream_t stream);
+void launch_search_fill_allow(uint32_t * allow, int64_t n, float fraction, bool contiguous, uint64_t seed, hipStream_t stream);
 
 // Range search and pairs (k_join.hip): every (query, row) at distance <= radius, scored exactly as launch_search_scan scores it (rows and
 // queries in the stored form above).  pairs: the queries are the rows themselves (q = rows, qinv = rinv, nq = n) and only row > query
@@ -312,7 +327,7 @@ void launch_search_fill_random(float * x, int64_t n, uint64_t seed, hipStream_t 
 // row of x [rows][dim] a small perturbation of the row 37 before it.
 constexpr int JOIN_HIT_BYTES = 12;
 bool launch_join(const void * rows, const float * rinv, int64_t n, const void * q, const float * qinv, int64_t nq, int Dpad, int dtype, bool pairs,
-                 float radius, int * count, unsigned long long * total, void * hits, int64_t hit_cap, hipStream_t stream);
+                 float radius, int * count, unsigned long long * total, void * hits, int64_t hit_cap, const uint32_t * mask, hipStream_t stream);
 void launch_join_scatter(const void * hits, int64_t total, const int64_t * offs, int * cursor, void * out, hipStream_t stream);
 void * launch_join_sort(void * buf, void * tmp, const int64_t * offs, int64_t nseg, int64_t total, int64_t longest, hipStream_t stream);
 void launch_join_finish(const void * in, int64_t total, float * dist, int64_t * ids, hipStream_t stream);

@@ -2,12 +2,18 @@
 build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.Index`) instead of usearch's approximate one.
 
     python -m clip_cpp_amd.image_search build  [-m MODEL] [-v N] [-t N] [--db DIR] [--dtype f16|f32|i8] dir [more dirs]
-    python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N | -d R] [--db DIR] <search text or /path/to/query/image>
+    python -m clip_cpp_amd.image_search update [-m MODEL] [-v N] [-t N] [--db DIR] dir [more dirs]
+    python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N | -d R] [--in PREFIX]... [--db DIR] <search text or /path/to/query/image>
     python -m clip_cpp_amd.image_search dedup  [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R]
 
 `build` writes DIR/images.index (the CLIPIDX1 file of clip_amd_index_save) and DIR/images.paths (the reference's layout: the model path
 on the first line, then one image path per id).  `search` prints the reference's output: "search results:" / "distance path" at
-verbosity > 0, then "  %f %s" per hit, nearest first: the -n nearest, or with -d R every indexed image within distance R.  `dedup` prints
+verbosity > 0, then "  %f %s" per hit, nearest first: the -n nearest, or with -d R every indexed image within distance R; with --in PREFIX
+(repeatable) only among the images whose path starts with one of the prefixes (the index's subset search: the other rows are not ranked).
+`update` brings an existing database in line with the disk without encoding anything twice: every indexed path that no longer exists is
+removed from the index (Index.remove + Index.compact), the files under the given dirs that are not indexed yet are encoded and appended,
+and both files are rewritten: the survivors in their old order, then the new files in scan order; it prints "main: %d added, %d removed,
+%d kept".  `dedup` prints
 the groups of near-duplicate images (connected components of the pairs within distance R, clip_amd_index_pairs): "duplicate groups:" at
 verbosity > 0, then per group, in order of its lowest id, "  %f %s" per member in id order (the distance to its nearest other member),
 groups separated by a blank line, and "main: %d groups, %d images".
@@ -47,11 +53,13 @@ def _err(msg):
     print(msg, file=sys.stderr, flush=True)
 
 
-def _parse(argv, build, dedup=False):
+def _parse(argv, build, dedup=False, update=False):
     """Reference-style option parsing (examples/image-search/{build,search}.cpp my_app_params_parse); `dedup` takes no positional
-    arguments."""
+    arguments; `update` takes build's directories, but neither a default model nor --dtype (both come from the database)."""
     p = dict(threads=4, verbose=1, db=".", dtype="f16", results=5, max_distance=DEDUP_RADIUS if dedup else None,
              model="../models/ggml-model-f16.bin" if build else "", rest=[])
+    p["in"] = []
+    search = not (build or dedup or update)
     seen = set()
     i = 0
     while i < len(argv):
@@ -61,16 +69,22 @@ def _parse(argv, build, dedup=False):
             takes.update({"-t": "threads", "--threads": "threads"})
         if build:
             takes["--dtype"] = "dtype"
-        else:
+        elif not update:
             takes.update({"-d": "max_distance", "--max-distance": "max_distance"})
             if not dedup:
                 takes.update({"-n": "results", "--results": "results"})
+        if search:
+            takes["--in"] = "in"
         if a in takes:
             i += 1
             if i >= len(argv):
                 return None
             key = takes[a]
             seen.add(key)
+            if key == "in":
+                p["in"].append(argv[i])
+                i += 1
+                continue
             try:
                 p[key] = int(argv[i]) if key in ("threads", "verbose", "results") else float(argv[i]) if key == "max_distance" else argv[i]
             except ValueError:
@@ -78,7 +92,7 @@ def _parse(argv, build, dedup=False):
             if key == "max_distance" and p[key] != p[key]:      # NaN
                 return None
         elif a in ("-h", "--help"):
-            _help(build, p, dedup)
+            _help(build, p, dedup, update)
             sys.exit(0)
         elif a.startswith("-"):
             print("main: unrecognized argument: %s" % a)
@@ -86,7 +100,7 @@ def _parse(argv, build, dedup=False):
         elif dedup:
             print("main: unexpected argument: %s" % a)
             return None
-        elif build:
+        elif build or update:
             p["rest"].append(a)
         else:
             p["rest"] = argv[i:]     # the query: everything from here on
@@ -100,7 +114,7 @@ def _parse(argv, build, dedup=False):
     return p
 
 
-def _help(build, p, dedup=False):
+def _help(build, p, dedup=False, update=False):
     radius = ("  -d R, --max-distance R: %s within cosine distance R (<= R). Default: %s. %g is a starting point for embeddings of near-identical"
               " images, not a tuned value: check a few groups of your collection and adjust R")
     if dedup:
@@ -112,6 +126,18 @@ def _help(build, p, dedup=False):
         print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
         print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
         print(radius % ("pair images", DEDUP_RADIUS, DEDUP_RADIUS))
+    elif update:
+        print("Usage: python -m clip_cpp_amd.image_search update [options] dir/with/pictures [more/dirs]")
+        print("\nBrings a database made by `build` in line with the disk: indexed paths that no longer exist are removed, image files under the")
+        print("given dirs that are not indexed yet are encoded and appended, nothing already indexed is encoded again.")
+        print("\nOptions:")
+        print("  -h, --help: Show this message and exit")
+        print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default. When the database is rewritten, the"
+              " given path replaces the one stored on the first line of images.paths: later commands load this model.")
+        print("  -t N, --threads N: Number of threads to use for inference. Default: %d" % p["threads"])
+        print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
+        print("  --db <dir>: directory holding %s and %s; both are written under temporary names and renamed into place. Default: %s"
+              % (INDEX_FILE, PATHS_FILE, p["db"]))
     elif build:
         print("Usage: python -m clip_cpp_amd.image_search build [options] dir/with/pictures [more/dirs]")
         print("\nOptions:")
@@ -130,6 +156,8 @@ def _help(build, p, dedup=False):
         print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
         print("  -n N, --results N: Number of results to display. Default: %d" % p["results"])
         print("  -d R, --max-distance R: display every indexed image within cosine distance R (<= R), nearest first, instead of the -n nearest (not with -n)")
+        print("  --in <prefix>: only images whose indexed path starts with <prefix> are eligible (one directory, one album); may be repeated:"
+              " a path matching any prefix is eligible. Works with -n and with -d")
         print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
 
 
@@ -171,7 +199,31 @@ def build(argv):
         return 1
     index = clip_cpp_amd.Index(clip, clip.vision_config["projection_dim"], dtype=p["dtype"])
     paths = []
+    _encode_dirs(clip, L, index, p, paths)
+    os.makedirs(p["db"], exist_ok=True)
+    _write_db(p, index, paths)
+    index.close()
+    clip.close()
+    print("main: %d images processed and indexed" % len(paths), flush=True)
+    return 0
 
+
+def _write_db(p, index, paths):
+    """Both files under temporary names first, then renamed into place one after the other: an interruption while they are written
+    leaves the old database as it was."""
+    index_file, paths_file = os.path.join(p["db"], INDEX_FILE), os.path.join(p["db"], PATHS_FILE)
+    index.save(index_file + ".tmp")
+    with open(paths_file + ".tmp", "w") as f:
+        f.write(p["model"] + "\n")
+        for path in paths:
+            f.write(path + "\n")
+    os.replace(index_file + ".tmp", index_file)
+    os.replace(paths_file + ".tmp", paths_file)
+
+
+def _encode_dirs(clip, L, index, p, paths, scans=None):
+    """Decode and encode the image files of the directories p["rest"] in batches and append them to `index` and `paths`.  scans: the
+    [(dir, files)] to take when the caller has scanned already (`update`), else every file found under each dir."""
     def flush(batch):
         if not batch:
             return
@@ -186,9 +238,10 @@ def build(argv):
             print(".", end="", flush=True)
 
     batch = []
-    for base in p["rest"]:
-        print("main: starting base dir scan of '%s'" % base, flush=True)
-        files = image_files(base)
+    for base, files in scans if scans is not None else [(base, None) for base in p["rest"]]:
+        if files is None:
+            print("main: starting base dir scan of '%s'" % base, flush=True)
+            files = image_files(base)
         print("\nmain: processing %d files in '%s'" % (len(files), base), flush=True)
         for path in files:
             if p["verbose"] >= 2:
@@ -202,15 +255,66 @@ def build(argv):
             if len(batch) == BATCH:
                 flush(batch)
     flush(batch)
-    os.makedirs(p["db"], exist_ok=True)
-    index.save(os.path.join(p["db"], INDEX_FILE))
-    with open(os.path.join(p["db"], PATHS_FILE), "w") as f:
-        f.write(p["model"] + "\n")
-        for path in paths:
-            f.write(path + "\n")
+
+
+def reconcile(old_paths, found, exists=os.path.exists):
+    """What `update` does to a database: (kept, removed, to_add).  kept: the ids of old_paths that still exist, ascending; removed: the ids
+    that do not; to_add: the files of `found` (scan order) that are not indexed, each once."""
+    kept = [i for i, path in enumerate(old_paths) if exists(path)]
+    kept_set = set(kept)
+    removed = [i for i in range(len(old_paths)) if i not in kept_set]
+    known = set(old_paths[i] for i in kept)
+    to_add = []
+    for path in found:
+        if path not in known:
+            known.add(path)
+            to_add.append(path)
+    return kept, removed, to_add
+
+
+def update(argv):
+    import clip_cpp_amd
+    p = _parse(argv, build=False, update=True)
+    if p is None:
+        _help(False, dict(threads=4, verbose=1, db="."), update=True)
+        return 1
+    old_paths = _read_db(p)
+    if old_paths is None:
+        return 1
+    scans = []
+    for base in p["rest"]:                          # every directory is scanned once
+        print("main: starting base dir scan of '%s'" % base, flush=True)
+        scans.append((base, image_files(base)))
+    kept, removed, to_add = reconcile(old_paths, [f for _, files in scans for f in files])
+    L = clip_cpp_amd.lib()
+    try:
+        clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])
+    except RuntimeError:
+        print("main: Unable to load model from %s" % p["model"])
+        return 1
+    if to_add and clip.vision_config["n_layer"] <= 0:
+        _err("main: the model at %s has no vision encoder: an image index needs a vision or two-tower model" % p["model"])
+        return 1
+    index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
+    if to_add and index.dim != clip.vision_config["projection_dim"]:
+        _err("main: the index holds %d-dimensional embeddings, the model makes %d" % (index.dim, clip.vision_config["projection_dim"]))
+        return 1
+    paths = [old_paths[i] for i in kept]
+    if removed:
+        index.remove(removed)
+        index.compact()
+    n_kept = len(paths)
+    if to_add:
+        todo = set(to_add)
+        for i, (base, files) in enumerate(scans):   # each new file under the first directory that holds it
+            scans[i] = (base, [f for f in files if f in todo])
+            todo -= set(scans[i][1])
+        _encode_dirs(clip, L, index, p, paths, scans)
+    if removed or len(paths) > n_kept:
+        _write_db(p, index, paths)
     index.close()
     clip.close()
-    print("main: %d images processed and indexed" % len(paths), flush=True)
+    print("main: %d added, %d removed, %d kept" % (len(paths) - n_kept, len(removed), n_kept), flush=True)
     return 0
 
 
@@ -296,12 +400,15 @@ def search(argv):
     if index.dim != vec.size:
         _err("main: the index holds %d-dimensional embeddings, the model makes %d" % (index.dim, vec.size))
         return 1
+    allow = None
+    if p["in"]:                                    # the index ranks only these rows: no host-side filtering of a longer list
+        allow = np.array([path.startswith(tuple(p["in"])) for path in image_paths], dtype=np.bool_)
     if p["max_distance"] is not None:
-        _, dist, ids = index.range_search(vec[None, :], p["max_distance"])
+        _, dist, ids = index.range_search(vec[None, :], p["max_distance"], allow=allow)
         hits = list(zip(dist, ids))
     else:
         k = max(1, min(p["results"], MAX_K))
-        dist, ids = index.search(vec[None, :], k)
+        dist, ids = index.search(vec[None, :], k, allow=allow)
         hits = [(d, i) for d, i in zip(dist[0], ids[0]) if i >= 0 and p["results"] > 0]
     if p["verbose"] > 0:
         print("search results:")
@@ -372,9 +479,10 @@ def dedup(argv):
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
-    commands = {"build": build, "search": search, "dedup": dedup}
+    commands = {"build": build, "update": update, "search": search, "dedup": dedup}
     if not argv or argv[0] not in commands:
         print("Usage: python -m clip_cpp_amd.image_search {build|search|dedup} [options] ...  (-h after the command for its options)")
+        print("       python -m clip_cpp_amd.image_search update [options] dir [more dirs]  (an existing database brought in line with the disk)")
         return 1
     return commands[argv[0]](argv[1:])
 

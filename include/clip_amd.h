@@ -146,14 +146,25 @@ int clip_amd_profile_report(struct clip_ctx * ctx, char * buf, int cap, bool res
  * (distance exactly 1).  d = 1 - (float)dot * inv_q * inv_r, dot = sum_i q_i r_i an exact int32 (|dot| <= 127^2 * 4096 < 2^31),
  * inv = 1.0f / sqrtf((float)sum_i v_i^2), 0 for the zero vector: the cosine distance of the stored integer vectors.  1 byte per value
  * (rows padded to 64 values in HBM) + 4 bytes per row for inv_r.
- * Rows get ids 0 ... n-1 in the order they were added; appending after a search is allowed, deletion is not.  Results per query sorted
- * by ascending distance, equal distances lower id first; with k > size the tail holds id -1 / distance +INFINITY.  1 <= k <= 1024,
+ * Rows get ids 0 ... n-1 in the order they were added; appending after a search is allowed, and so is removal: clip_amd_index_remove marks
+ * rows in a device-resident bitmap (one bit per row) that the scan and join kernels honour, so search, search_device, range_search and
+ * pairs never return a removed row (pairs neither as i nor as j; its lims keeps size + 1 entries, a removed row's segment is empty) and
+ * an aligned group of 16 rows without a live row is not read from HBM.  Removal never reuses or renumbers ids: size still counts every id
+ * ever given, live = size minus the removed rows, add after remove appends live rows with the next ids.  clip_amd_index_compact drops the
+ * removed rows from device memory and renumbers the survivors 0 ... live - 1 in their old order.  The *_subset forms restrict a search to
+ * the rows whose bit is set in a caller's bitmap (one directory, one album, everything not yet dismissed); a row is eligible when it is
+ * live and allowed.  Results per query sorted
+ * by ascending distance, equal distances lower id first; with k > the number of eligible rows the tail holds id -1 / distance +INFINITY.
+ * A result over the eligible rows is, bit for bit, the result of an index to which only those rows were ever added (ids mapped in
+ * order).  An index without removed rows searched without a subset runs the unmasked kernels.  1 <= k <= 1024,
  * 4 <= dim <= 4096 with dim % 4 == 0, any number of queries, up to 2^31 - 1 rows.  Results are bit-identical run to run, however queries
  * are split across calls, however rows were split across add calls, and across save / load.
  * The index lives on ctx's device and launches on ctx's stream (clip_amd_set_stream applies); free it before the ctx.  NULL on a
  * host-only ctx.  Bad arguments make a call return false (NULL) with a message on stderr, without launching anything.
  * File format (little-endian): "CLIPIDX1", u32 version (1), u32 dim, u32 dtype, u64 n, then n rows of dim stored values (unpadded;
- * i8: 1-byte values, inv_r is not stored but recomputed on the device at load, so a loaded index searches and re-saves identically). */
+ * i8: 1-byte values, inv_r is not stored but recomputed on the device at load, so a loaded index searches and re-saves identically).
+ * The file has no place for removed rows: save on an index that holds any returns false with a message that says to compact first;
+ * after compact, or when nothing was removed, save writes what it always wrote. */
 struct clip_amd_index;
 struct clip_amd_index * clip_amd_index_create(struct clip_ctx * ctx, int dim, int dtype);
 bool clip_amd_index_add(struct clip_amd_index * ix, const float * vecs, int64_t n);            /* host rows [n][dim], synchronous */
@@ -168,15 +179,37 @@ bool clip_amd_index_search_device(struct clip_amd_index * ix, const float * d_qu
 bool clip_amd_index_save(struct clip_amd_index * ix, const char * path);
 struct clip_amd_index * clip_amd_index_load(struct clip_ctx * ctx, const char * path);
 void clip_amd_index_free(struct clip_amd_index * ix);
+/* Mark rows as removed.  ids: n host values, each in [0, size); duplicates and already-removed ids are allowed.
+ * Returns how many rows went from live to removed in this call; -1 (nothing changed) for a NULL index, n < 0, NULL ids with n > 0 or any id
+ * outside [0, size).  Ids are never reused or renumbered by removal: clip_amd_index_size still counts every id ever given. */
+int64_t clip_amd_index_remove(struct clip_amd_index * ix, const int64_t * ids, int64_t n);
+int64_t clip_amd_index_live(const struct clip_amd_index * ix);            /* size minus removed rows */
+/* bits: (size + 63) / 64 host words; bit (id & 63) of word id >> 6 is 1 for a live row; bits at positions >= size are written as 0. */
+bool clip_amd_index_live_mask(struct clip_amd_index * ix, uint64_t * bits);
+/* Drop the removed rows from device memory; survivors keep their order and get ids 0 ... live - 1.  new_ids (host, old size entries, may be
+ * NULL) receives each old id's new id, -1 for a removed row.  Returns the new size, -1 on error.  Stored values (i8: and inverse norms) are
+ * moved bit for bit: afterwards the index searches and saves exactly like one to which only the survivors were ever added.
+ * Device memory at the peak: the old rows, the fresh allocation of the survivors and 8 bytes per old row for the new ids (also with
+ * new_ids NULL); the old rows are freed before the call returns.  No removed rows: nothing is allocated or moved. */
+int64_t clip_amd_index_compact(struct clip_amd_index * ix, int64_t * new_ids);
+/* search / range_search restricted to the rows whose bit is set in allow (layout as live_mask; host words for the host forms, HBM for the
+ * _device form; NULL = every row; bits at positions >= size are ignored, whatever they hold).  A removed row is never a result even if allowed. */
+bool clip_amd_index_search_subset(struct clip_amd_index * ix, const float * queries, int n_queries, int k, const uint64_t * allow,
+                                  float * distances, int64_t * ids);
+bool clip_amd_index_search_subset_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int k, const uint64_t * d_allow,
+                                         float * d_distances, int64_t * d_ids);
 /* Average device time (microseconds, HIP events) of one clip_amd_index_search_device of n_queries seeded random queries against n seeded
  * random rows on the current device (dtype as clip_amd_index_create: 0, 1 or 3); < 0 on error.  Used by scripts/search_bench.py. */
 float clip_amd_bench_search(int dtype, int64_t n, int dim, int n_queries, int k, int iters);
+/* The same with an allowed set over the same seeded rows and queries (clip_amd_index_search_subset_device): allowed_fraction in [0, 1] of
+ * the ids, a seeded random selection or, contiguous != 0, one id range in the middle of the index.  Used by scripts/subset_bench.py. */
+float clip_amd_bench_search_subset(int dtype, int64_t n, int dim, int n_queries, int k, float allowed_fraction, int contiguous, int iters);
 /* Range search and near-duplicate pairs.
  * Distance: exactly what clip_amd_index_search reports for the same (query, row) pair (the same stored values, the same MFMA chain per
  * dtype, the same f32 expression); a row is a result when d <= radius, compared in f32.
- * range_search: for each query every stored row with d <= radius, sorted by ascending distance, equal distances lower id first (search's
+ * range_search: for each query every stored (live) row with d <= radius, sorted by ascending distance, equal distances lower id first (search's
  * order: for a query with c <= 1024 results, search with any k >= c begins with exactly those c (id, distance) pairs, bit for bit).
- * pairs: every (i, j) with i < j < size and d(i, j) <= radius, d(i, j) being the distance search reports for row j when the query is the
+ * pairs: every (i, j) of live rows with i < j < size and d(i, j) <= radius, d(i, j) being the distance search reports for row j when the query is the
  * vector that was added as row i (row i's stored values are exactly that query's normalised / quantised form); grouped by ascending i,
  * within one i in range-search order, so the pairs of row i are range_search(vector of row i) without the ids <= i, bit for bit.
  * Results are bit-identical run to run, however queries are split across calls, however rows were split across add calls, and across
@@ -189,6 +222,9 @@ float clip_amd_bench_search(int dtype, int64_t n, int dim, int n_queries, int k,
 int64_t clip_amd_index_range_search(struct clip_amd_index * ix, const float * queries, int n_queries, float radius,
                                     int64_t * lims, float * distances, int64_t * ids, int64_t capacity);
 int64_t clip_amd_index_pairs(struct clip_amd_index * ix, float radius, int64_t * lims, float * distances, int64_t * ids, int64_t capacity);
+/* range_search over the allowed rows only (allow as for clip_amd_index_search_subset, host words) */
+int64_t clip_amd_index_range_search_subset(struct clip_amd_index * ix, const float * queries, int n_queries, float radius, const uint64_t * allow,
+                                           int64_t * lims, float * distances, int64_t * ids, int64_t capacity);
 /* Average wall time (microseconds) of one clip_amd_index_range_search of n_queries seeded queries (n_queries == 0: clip_amd_index_pairs)
  * against n seeded random rows of which every 64th is a small perturbation of an earlier one (sparse, non-empty output at small radii), on
  * the current device (dtype as clip_amd_index_create); < 0 on error.  Used by scripts/pairs_bench.py. */
