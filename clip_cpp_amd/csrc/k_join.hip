@@ -334,7 +334,7 @@ bool launch_join(const void * rows, const float * rinv, int64_t n, const void * 
     p.qinv = qinv;
     p.n = n;
     p.nq = nq;
-    p.row_bytes = (int64_t)Dpad * (dtype == SEARCH_I8 ? 1 : dtype == SEARCH_F16 ? 2 : 4);
+    p.row_bytes = (int64_t)Dpad * (int64_t)search_elem_size(dtype);
     p.nk = (int)(p.row_bytes / 64);
     p.radius = radius;
     p.pairs = pairs;
@@ -343,9 +343,10 @@ bool launch_join(const void * rows, const float * rinv, int64_t n, const void * 
     p.hits = (Hit *)hits;
     p.hit_cap = hit_cap;
     const bool wide = pairs || nq > 16;        // pairs need square tiles; few queries: a 16-query tile, the gallery read once
-    if (dtype == SEARCH_I8) return wide ? launch_join_t<int8_t, 4, 4, 2>(p, stream) : launch_join_t<int8_t, 2, 1, 1>(p, stream);
-    if (dtype == SEARCH_F16) return wide ? launch_join_t<half_t, 4, 4, 2>(p, stream) : launch_join_t<half_t, 2, 1, 1>(p, stream);
-    return wide ? launch_join_t<float, 4, 4, 2>(p, stream) : launch_join_t<float, 2, 1, 1>(p, stream);
+    return with_search_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        return wide ? launch_join_t<T, 4, 4, 2>(p, stream) : launch_join_t<T, 2, 1, 1>(p, stream);
+    });
 }
 
 void launch_join_scatter(const void * hits, int64_t total, const int64_t * offs, int * cursor, void * out, hipStream_t stream) {

@@ -504,17 +504,15 @@ int search_sort_size(int k) {
     return P;
 }
 
-void launch_search_normalize(const float * src, int64_t n_src, int64_t n_rows, int dim, int Dpad, void * dst, int dtype, hipStream_t stream) {
+void launch_search_prepare(const float * src, int64_t n_src, int64_t n_rows, int dim, int Dpad, int dtype, void * dst, float * inv,
+                           hipStream_t stream) {
     if (n_rows <= 0) return;
-    const unsigned blocks = (unsigned)((n_rows + 3) / 4);
-    if (dtype == SEARCH_F16) hipLaunchKernelGGL(search_normalize_kernel<half_t>, dim3(blocks), dim3(256), 0, stream, src, n_src, n_rows, dim, Dpad, (half_t *)dst);
-    else hipLaunchKernelGGL(search_normalize_kernel<float>, dim3(blocks), dim3(256), 0, stream, src, n_src, n_rows, dim, Dpad, (float *)dst);
-}
-
-void launch_search_quantize(const float * src, int64_t n_src, int64_t n_rows, int dim, int Dpad, void * dst, float * inv, hipStream_t stream) {
-    if (n_rows <= 0) return;
-    hipLaunchKernelGGL(search_quantize_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, stream, src, n_src, n_rows, dim, Dpad,
-                       (int8_t *)dst, inv);
+    const dim3 grid((unsigned)((n_rows + 3) / 4));
+    with_search_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        if constexpr (sizeof(T) == 1) hipLaunchKernelGGL(search_quantize_kernel, grid, dim3(256), 0, stream, src, n_src, n_rows, dim, Dpad, (T *)dst, inv);
+        else hipLaunchKernelGGL(search_normalize_kernel<T>, grid, dim3(256), 0, stream, src, n_src, n_rows, dim, Dpad, (T *)dst);
+    });
 }
 
 void launch_search_row_inv(const void * rows, int64_t n, int Dpad, float * inv, hipStream_t stream) {
@@ -538,19 +536,12 @@ bool launch_search_scan(const void * rows, const float * rinv, int64_t n, int Dp
     p.C = search_candidate_capacity(k);
     p.P = search_sort_size(k);
     p.rows_per_chunk = rows_per_chunk;
-    if (dtype == SEARCH_I8) {
-        if (qt == 4) return launch_scan_t<int8_t, 4>(p, n_chunks, stream);
-        if (qt == 2) return launch_scan_t<int8_t, 2>(p, n_chunks, stream);
-        return launch_scan_t<int8_t, 1>(p, n_chunks, stream);
-    }
-    if (dtype == SEARCH_F16) {
-        if (qt == 4) return launch_scan_t<half_t, 4>(p, n_chunks, stream);
-        if (qt == 2) return launch_scan_t<half_t, 2>(p, n_chunks, stream);
-        return launch_scan_t<half_t, 1>(p, n_chunks, stream);
-    }
-    if (qt == 4) return launch_scan_t<float, 4>(p, n_chunks, stream);
-    if (qt == 2) return launch_scan_t<float, 2>(p, n_chunks, stream);
-    return launch_scan_t<float, 1>(p, n_chunks, stream);
+    return with_search_type(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (qt == 4) return launch_scan_t<T, 4>(p, n_chunks, stream);
+        if (qt == 2) return launch_scan_t<T, 2>(p, n_chunks, stream);
+        return launch_scan_t<T, 1>(p, n_chunks, stream);
+    });
 }
 
 void launch_search_merge(const void * in, int64_t in_stride, int n_in, void * out, int nq, int k, hipStream_t stream) {
@@ -600,7 +591,7 @@ void launch_compact_gather(const void * src, void * dst, const float * sinv, flo
 }
 
 void launch_search_fill_allow(uint32_t * allow, int64_t n, float fraction, bool contiguous, uint64_t seed, hipStream_t stream) {
-    const int64_t words = (n + 63) / 64 * 2;
+    const int64_t words = search_allow_words(n);
     if (words <= 0) return;
     hipLaunchKernelGGL(search_fill_allow_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, stream, allow, n, words, fraction,
                        contiguous ? 1 : 0, seed);

@@ -286,19 +286,26 @@ void launch_f16_to_f32(const half_t * src, int lds, float * dst, int ldd, int ro
 
 // Exact nearest-neighbour search (k_search.hip).  Stored dtypes (the codes of clip_amd_index_create; 2 is reserved):
 enum { SEARCH_F32 = 0, SEARCH_F16 = 1, SEARCH_I8 = 3 };
-// f32 / fp16: stored rows / queries [rows][Dpad], Dpad = 32 m, L2-normalised (launch_search_normalize).  i8: [rows][Dpad] int8, Dpad = 64 m, quantised rint(x / max|x| * 127) with inv = 1 / sqrt(sum q^2) per
-// vector (launch_search_quantize; launch_search_row_inv recomputes inv of stored rows); the scan reads rinv as 16-byte groups, so a row
-// inv array holds at least n rounded up to 64 floats.
+// What a stored dtype implies: bytes per value, and Dpad, a row's length: dim rounded up to whole k-steps of the scan (64 i8 values; 32 for
+// fp16 and, two 16-value steps, f32).  search_common.h maps the code to the element type (with_search_type).
+inline size_t search_elem_size(int dtype) { return dtype == SEARCH_I8 ? 1 : dtype == SEARCH_F16 ? 2 : 4; }
+inline int search_dpad(int dtype, int dim) { return dtype == SEARCH_I8 ? (dim + 63) / 64 * 64 : (dim + 31) / 32 * 32; }
+// f32 / fp16: stored rows / queries [rows][Dpad], L2-normalised.  i8: [rows][Dpad] int8, quantised rint(x / max|x| * 127) with
+// inv = 1 / sqrt(sum q^2) per vector (launch_search_row_inv recomputes inv of stored rows); the scan reads rinv as 16-byte groups, so a row
+// inv array holds at least n rounded up to 64 floats.  launch_search_prepare writes either form from f32 [n_src][dim] (inv: i8 only); rows
+// past n_src are zeros.
 // mask (scan and join; NULL: every row): one bit per row, bit row & 31 of 32-bit word row >> 5 (little-endian halves of the 64-bit words of
 // clip_amd.h), the live bitmap ANDed with the caller's allowed set, zeros at positions >= n up to a multiple of 128 rows.  A row whose bit
-// is 0 is never a candidate; an aligned group of 16 such rows is not read.
+// is 0 is never a candidate; an aligned group of 16 such rows is not read.  An allowed set of n rows is search_allow_words(n) such words
+// (whole 64-bit words of clip_amd.h).
+inline int64_t search_allow_words(int64_t n) { return (n + 63) / 64 * 2; }
 // Candidate workspace of a scan: [n_chunks][nq][search_candidate_capacity(k)] (score f32, id i32) pairs; each chunk's best k, sorted, ends
 // at the head of its (chunk, query) slot.  Merge: lists 2i, 2i + 1 -> list i ([n_out][nq][k] pairs).  Finish: one list per query ->
 // distances (1 - score) and int64 ids, empty slots -1 / +inf.
 int search_candidate_capacity(int k);
 int search_sort_size(int k);
-void launch_search_normalize(const float * src, int64_t n_src, int64_t n_rows, int dim, int Dpad, void * dst, int dtype, hipStream_t stream);
-void launch_search_quantize(const float * src, int64_t n_src, int64_t n_rows, int dim, int Dpad, void * dst, float * inv, hipStream_t stream);
+void launch_search_prepare(const float * src, int64_t n_src, int64_t n_rows, int dim, int Dpad, int dtype, void * dst, float * inv,
+                           hipStream_t stream);
 void launch_search_row_inv(const void * rows, int64_t n, int Dpad, float * inv, hipStream_t stream);
 bool launch_search_scan(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq, int qt,
                         int k, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask, hipStream_t stream);
@@ -309,7 +316,7 @@ void launch_search_fill_random(float * x, int64_t n, uint64_t seed, hipStream_t 
 // number of bits that were set to *removed.  mask_and: out[w] = live[w] & allow[w], allow words at w >= allow_words read as 0.
 // compact_ids: new_ids[row] = rank of the row among the set bits, -1 for a cleared bit; *total = the number of set bits (live: words
 // rounded up to 4, zeros past n).  compact_gather: rows (row_bytes each, a multiple of 16) and, sinv != NULL, inverse norms of the set
-// rows -> row new_ids[row] of dst / dinv, which must not alias src / sinv.  fill_allow: benchmark allowed set of (n + 63) / 64 * 2 words.
+// rows -> row new_ids[row] of dst / dinv, which must not alias src / sinv.  fill_allow: benchmark allowed set of search_allow_words(n) words.
 void launch_live_set(uint32_t * live, int64_t lo, int64_t hi, hipStream_t stream);
 void launch_live_remove(uint32_t * live, const int64_t * ids, int64_t n, unsigned long long * removed, hipStream_t stream);
 void launch_mask_and(const uint32_t * live, const uint32_t * allow, int64_t allow_words, uint32_t * out, int64_t words, hipStream_t stream);

@@ -3,7 +3,8 @@
 // A (query, row) score is bit-identical in both files because both take it from here: the same 16-byte lane loads (ld_step), the same
 // MFMA per stored dtype in the same k order (mfma_step), the same f32 distance expression (scan_distance), with the gallery row as the
 // MFMA "A" operand and the query as "B", one accumulator per pair starting at zero.  Candidates are ordered by the strict total order
-// `better` (distance ascending, then id ascending); wave_sort sorts a wave's LDS buffer in that order.
+// `better` (distance ascending, then id ascending); wave_sort sorts a wave's LDS buffer in that order.  The launchers of both files pick
+// the element type of a stored dtype through with_search_type.
 #pragma once
 
 #include <climits>
@@ -22,6 +23,15 @@ typedef int i4 __attribute__((ext_vector_type(4)));
 // accumulator of the scan per stored dtype: f32 for fp16 / f32 rows, the exact i32 dot for i8 rows
 template <typename T> struct ScanAcc { typedef f4 type; };
 template <> struct ScanAcc<int8_t> { typedef i4 type; };
+
+// The one place a stored dtype code becomes an element type: calls f with a value of int8_t, half_t or float.  Every launcher with a kernel
+// per dtype goes through it, in this order (the order in which the kernels are instantiated and emitted).
+template <typename F>
+auto with_search_type(int dtype, F && f) {
+    if (dtype == SEARCH_I8) return f(int8_t());
+    if (dtype == SEARCH_F16) return f(half_t());
+    return f(float());
+}
 
 struct Cand {
     float s;

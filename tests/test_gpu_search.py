@@ -32,9 +32,21 @@ def stored_rows(index, tmp_path, name="rows.index"):
 
 
 def stored_queries(q, dtype):
+    """the queries as search_normalize_kernel stores them: the f32 sum of squares in the kernel's own order (lane i % 64 adds its values in
+    ascending i, then the xor butterfly 32 ... 1 over the 64 lanes), x / sqrt(ss) in f32, rounded to the stored dtype.  Any other
+    summation order gives another f32 norm now and then, which flips the fp16 rounding of a value: at a small dim, where the values are
+    large, one flip moves a distance by more than check's tolerance (seen with numpy's own sum: dim 36, 2 of 37080 values, 3.9e-5)."""
     q = np.asarray(q, dtype=np.float32)
-    nrm = np.sqrt((q * q).sum(1, dtype=np.float32)).astype(np.float32)[:, None]
-    qn = np.where(nrm > 0, q / np.where(nrm > 0, nrm, 1), 0).astype(np.float32)
+    m, dim = q.shape
+    sq = np.zeros((m, (dim + 63) // 64 * 64), dtype=np.float32)
+    sq[:, :dim] = q * q
+    lanes = np.zeros((m, 64), dtype=np.float32)
+    for c in range(0, sq.shape[1], 64):
+        lanes = lanes + sq[:, c:c + 64]
+    for off in (32, 16, 8, 4, 2, 1):
+        lanes = lanes + lanes[:, np.arange(64) ^ off]
+    ss = lanes[:, :1]
+    qn = np.where(ss > 0, q / np.where(ss > 0, np.sqrt(ss), 1), 0).astype(np.float32)
     return qn.astype(NP_DT[dtype]).astype(np.float64)
 
 
@@ -73,6 +85,7 @@ CASES = [  # dtype, dim, N, nq, k
     ("f16", 512, 1000, 64, 100), ("f32", 512, 1000, 5, 1024), ("f16", 768, 1000, 300, 5), ("f32", 1280, 1000, 1, 1),
     ("f16", 1024, 65537, 5, 100), ("f32", 768, 65537, 64, 5), ("f16", 1280, 65537, 1, 1024), ("f16", 512, 65537, 300, 1),
     ("f32", 1024, 65537, 5, 1024), ("f16", 512, 300000, 5, 100), ("f32", 512, 300000, 1, 5), ("f16", 768, 300000, 64, 1024),
+    ("f16", 36, 300, 1030, 3), ("f32", 36, 300, 1030, 3),      # two passes over the query chunks, workspaces reused
 ]
 
 
