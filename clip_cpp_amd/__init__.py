@@ -75,6 +75,7 @@ AMD_SYMBOLS = [
     "clip_amd_bench_search", "clip_amd_index_range_search", "clip_amd_index_pairs", "clip_amd_bench_range",
     "clip_amd_index_remove", "clip_amd_index_live", "clip_amd_index_live_mask", "clip_amd_index_compact", "clip_amd_index_search_subset",
     "clip_amd_index_search_subset_device", "clip_amd_index_range_search_subset", "clip_amd_bench_search_subset",
+    "clip_amd_index_search_ids", "clip_amd_index_search_ids_device", "clip_amd_index_knn_graph", "clip_amd_test_index_knn_route", "clip_amd_bench_knn",
 ]
 
 _lib = None
@@ -252,6 +253,16 @@ def lib():
     L.clip_amd_index_range_search_subset.argtypes = [vp, f32p, i32, C.c_float, u64p, i64p, f32p, i64p, i64]
     L.clip_amd_bench_search_subset.restype = C.c_float
     L.clip_amd_bench_search_subset.argtypes = [i32, i64, i32, i32, i32, C.c_float, i32, i32]
+    L.clip_amd_index_search_ids.restype = C.c_bool
+    L.clip_amd_index_search_ids.argtypes = [vp, i64p, i32, i32, i32, u64p, f32p, i64p]
+    L.clip_amd_index_search_ids_device.restype = C.c_bool
+    L.clip_amd_index_search_ids_device.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
+    L.clip_amd_index_knn_graph.restype = C.c_bool
+    L.clip_amd_index_knn_graph.argtypes = [vp, i32, f32p, i64p]
+    L.clip_amd_test_index_knn_route.restype = i32
+    L.clip_amd_test_index_knn_route.argtypes = [vp, i32]
+    L.clip_amd_bench_knn.restype = C.c_float
+    L.clip_amd_bench_knn.argtypes = [i32, i64, i32, i32, i32, i32]
     _lib = L
     return L
 
@@ -579,7 +590,12 @@ class Index:
     counting every id ever given (`live` = len minus the removed rows); compact() drops them from device memory and renumbers the
     survivors.  search and range_search take `allow`, a bool mask of length len(index) or an array of ids: only those rows (and of those
     only the live ones) are eligible.  Either way the result is, bit for bit, that of an index that only ever held the eligible rows.
-    save() refuses an index that holds removed rows: compact() first."""
+    save() refuses an index that holds removed rows: compact() first.
+
+    search_ids(ids, k) finds the neighbours of rows that are already stored ("more like this one"): the query is the row's stored values,
+    bit for bit, so no vector and no model is needed; with exclude_self (the default) the row itself is not a candidate, and the result is
+    what search gives for the added vector with that row's bit cleared in `allow`.  knn_graph(k) is the same for every row at once: its k
+    nearest other live rows (an all -1 / +inf row for a removed id), from a tiled kernel on larger indexes."""
 
     DTYPES = {"f32": 0, "f16": 1, "i8": 3}
 
@@ -703,6 +719,36 @@ class Index:
                 return lims, dist[:total], ids[:total]
             cap = int(total)
 
+    def search_ids(self, ids, k, exclude_self=True, allow=None):
+        """Neighbours of the stored rows `ids` (each a live id; duplicates are fine): (distances f32 [n_ids, k], ids int64 [n_ids, k]) as
+        `search` gives them for the vectors that were added as those rows; exclude_self: a row is not its own neighbour.  `allow` (bool mask
+        [len] or ids) restricts the candidates only."""
+        a = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        words, wp = self._allow(allow)
+        dist = np.empty((a.size, k), dtype=np.float32)
+        out = np.empty((a.size, k), dtype=np.int64)
+        if not lib().clip_amd_index_search_ids(self._live(), a.ctypes.data_as(C.POINTER(C.c_int64)), a.size, int(k), int(bool(exclude_self)), wp,
+                                               _fp(dist), out.ctypes.data_as(C.POINTER(C.c_int64))):
+            raise RuntimeError("clip_amd_index_search_ids failed (see stderr)")
+        return dist, out
+
+    def search_ids_device(self, d_ids, n_ids, k, d_distances, d_out_ids, exclude_self=True, d_allow=None):
+        """search_ids on device pointers (ints): ids [n] int64 -> distances [n, k] f32, ids [n, k] int64; asynchronous on the context's
+        stream.  An id out of range or removed gives an all-empty row (-1 / +inf); d_allow: uint64 words on the device (0 / None: every row)."""
+        if not lib().clip_amd_index_search_ids_device(self._live(), C.c_void_p(d_ids), int(n_ids), int(k), int(bool(exclude_self)),
+                                                      C.c_void_p(d_allow or None), C.c_void_p(d_distances), C.c_void_p(d_out_ids)):
+            raise RuntimeError("clip_amd_index_search_ids_device failed (see stderr)")
+
+    def knn_graph(self, k):
+        """(distances f32 [n, k], ids int64 [n, k]): for every id its k nearest other live rows, nearest first, equal distances lower id
+        first, -1 / +inf where there are fewer (and in the whole row of a removed id); row i equals search_ids([i], k) bit for bit."""
+        n = len(self)
+        dist = np.empty((n, k), dtype=np.float32)
+        ids = np.empty((n, k), dtype=np.int64)
+        if not lib().clip_amd_index_knn_graph(self._live(), int(k), _fp(dist), ids.ctypes.data_as(C.POINTER(C.c_int64))):
+            raise RuntimeError("clip_amd_index_knn_graph failed (see stderr)")
+        return dist, ids
+
     def search_device(self, d_queries, n_queries, k, d_distances, d_ids):
         """Device pointers (ints): queries [n, dim] f32 -> distances [n, k] f32, ids [n, k] int64; asynchronous on the context's stream."""
         if not lib().clip_amd_index_search_device(self._live(), C.c_void_p(d_queries), int(n_queries), int(k), C.c_void_p(d_distances),
@@ -752,6 +798,12 @@ def bench_range(dtype, n, dim, n_queries, radius, iters=10):
     """Microseconds per clip_amd_index_range_search of n_queries queries, or per clip_amd_index_pairs when n_queries == 0, on seeded random
     rows with planted near-duplicates (clip_amd_bench_range); < 0 on error."""
     return float(lib().clip_amd_bench_range(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), float(radius), int(iters)))
+
+
+def bench_knn(dtype, n, dim, k, route=0, iters=3):
+    """Microseconds (wall) per clip_amd_index_knn_graph over n seeded random rows; route 0 automatic, 1 the scan route, 2 the tiled kernel
+    (clip_amd_bench_knn); < 0 on error."""
+    return float(lib().clip_amd_bench_knn(Index.DTYPES[dtype], int(n), int(dim), int(k), int(route), int(iters)))
 
 
 def gguf_inspect(path):

@@ -37,10 +37,6 @@ namespace clipamd {
 
 namespace {
 
-constexpr int JOIN_THREADS = 256;
-constexpr int JOIN_BM = 128;                  // rows per tile
-constexpr int JOIN_KC = 4;                    // k-steps (64 bytes of a row each) per LDS chunk
-constexpr int JOIN_LROW = JOIN_KC * 64 + 32;  // LDS bytes per staged row
 constexpr int JOIN_RUN = 1024;                // segment run one wave sorts in LDS
 constexpr int JOIN_SUPER = 8;                 // pairs: super-tile edge in tiles
 

@@ -33,9 +33,16 @@
 //                            read from HBM); otherwise the same chain runs and a distance is pushed only if its row's bit is set as well.
 //                            Rows are still visited in ascending id, so the tie rule holds; a chunk without an eligible row leaves k
 //                            sorted empty slots.
+//                            Self-excluding instantiation (template parameter SELF: searches by id, clip_amd_index_search_ids with
+//                            exclude_self and the scan route of clip_amd_index_knn_graph): p.qself holds, per query, the stored row the
+//                            query is a copy of; that row is never pushed for that query, everything else is the same text.
+//   search_gather_kernel     queries of a search by id: query t = stored row ids[t] copied bit for bit (16 bytes per thread; i8: qinv :=
+//                            rinv) and qself[t] = that id; an id out of range or removed is tested before anything is read there and
+//                            gives the zero row and qself -1, which search_finish_kernel turns into an all-empty result; so do the
+//                            padding queries.
 //   search_merge_kernel      pairwise merge of two sorted k-lists per query keeping the best k (rank by binary search: a strict total order
 //                            — distance ascending, id ascending — so each element's output slot is unique); log2(chunks) launches.
-//   search_finish_kernel     ids widened to int64; empty slots -> id -1, distance +inf.
+//   search_finish_kernel     ids widened to int64; empty slots -> id -1, distance +inf; a query flagged qself < 0: every slot empty.
 //   live_set_kernel          row bitmap: sets the bits of rows [lo, hi) (add, load, compact), one thread per 32-bit word.
 //   live_remove_kernel       one thread per id: integer atomic AND clears the row's bit; the bits that were still set are counted (integer
 //                            atomic add), so the count does not depend on the order and a duplicate id counts once.
@@ -168,26 +175,10 @@ struct ScanParams {
     const float * rinv;    // i8: [>= n rounded up to 64] row inverse norms
     const float * qinv;    // i8: [nq_pad] query inverse norms
     const uint32_t * mask; // masked scan: one bit per row, at least n rounded up to 32 bits
+    const int * qself;     // self-excluding scan: [nq] the stored row a query is, or -1
 };
 
-// keep the best min(k, cnt) of a query's candidates (sorted, at the head of its buffer); returns the new count.  `final`: write all k
-// slots (empty ones as +inf / INT_MAX) so the merge reads k sorted entries.
-__device__ int wave_select(Cand * buf, int cnt, int k, int P, bool final, float * bs, int * bi, int lane) {
-    for (int i = lane; i < P; i += 64) {
-        Cand c = i < cnt ? buf[i] : Cand{INFINITY, INT_MAX};
-        bs[i] = c.s;
-        bi[i] = c.id;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    wave_sort(bs, bi, P, lane);
-    const int keep = final ? k : (cnt < k ? cnt : k);
-    for (int i = lane; i < keep; i += 64) buf[i] = Cand{bs[i], bi[i]};
-    return cnt < k ? cnt : k;
-}
-
-template <typename T, int QT, bool MASKED>
+template <typename T, int QT, bool MASKED, bool SELF = false>
 __global__ void __launch_bounds__(SCAN_THREADS) search_scan_kernel(const ScanParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int QB = 16 * QT;
@@ -252,11 +243,15 @@ __global__ void __launch_bounds__(SCAN_THREADS) search_scan_kernel(const ScanPar
                 Cand * buf = p.cand + ((size_t)chunk * p.nq + q0 + ql) * p.C;
                 float qinv = 0.f;
                 if constexpr (sizeof(T) == 1) qinv = p.qinv[q0 + ql];
+                int self = -1;
+                if constexpr (SELF) self = p.qself[q0 + ql];
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     const int64_t row = r0 + fgrp * 4 + r;
                     const float d = scan_distance(acc[j][r], qinv, rinv[r]);
-                    if (row < hi && d < t && ((mbits >> (fgrp * 4 + r)) & 1u)) {
+                    bool push = row < hi && d < t && ((mbits >> (fgrp * 4 + r)) & 1u);
+                    if constexpr (SELF) push = push && row != self;
+                    if (push) {
                         const int slot = atomicAdd(&cnt[ql], 1);
                         buf[slot] = Cand{d, (int)row};
                     }
@@ -321,10 +316,11 @@ __global__ void __launch_bounds__(256) search_merge_kernel(const Cand * __restri
 }
 
 __global__ void __launch_bounds__(256) search_finish_kernel(const Cand * __restrict__ in, int64_t in_stride, int nq, int k, float * __restrict__ dist,
-                                                            int64_t * __restrict__ ids) {
+                                                            int64_t * __restrict__ ids, const int * __restrict__ qself) {
     const int q = blockIdx.x;
+    const bool none = !in || (qself && qself[q] < 0);      // by-id query of an id that is out of range or removed
     for (int t = threadIdx.x; t < k; t += 256) {
-        Cand c = in ? in[(size_t)q * in_stride + t] : Cand{INFINITY, INT_MAX};
+        Cand c = none ? Cand{INFINITY, INT_MAX} : in[(size_t)q * in_stride + t];
         const bool empty = c.id == INT_MAX;
         dist[(size_t)q * k + t] = empty ? INFINITY : c.s;
         ids[(size_t)q * k + t] = empty ? (int64_t)-1 : (int64_t)c.id;
@@ -342,19 +338,20 @@ __global__ void __launch_bounds__(256) search_fill_random_kernel(float * __restr
     x[i] = (float)(z >> 40) * (1.0f / 8388608.0f) - 1.0f;
 }
 
-template <typename T, int QT, bool MASKED>
+template <typename T, int QT, bool MASKED, bool SELF>
 bool launch_scan_m(const ScanParams & p, int n_chunks, hipStream_t stream) {
     static unsigned long long lds_done = 0;
     const size_t lds = (size_t)2 * 16 * QT * 4 + (size_t)4 * 2 * p.P * 4;
-    if (lds > 65536) opt_in_dynamic_lds(search_scan_kernel<T, QT, MASKED>, lds, lds_done);
+    if (lds > 65536) opt_in_dynamic_lds(search_scan_kernel<T, QT, MASKED, SELF>, lds, lds_done);
     const dim3 grid(n_chunks, (p.nq + 16 * QT - 1) / (16 * QT));
-    hipLaunchKernelGGL((search_scan_kernel<T, QT, MASKED>), grid, dim3(SCAN_THREADS), lds, stream, p);
+    hipLaunchKernelGGL((search_scan_kernel<T, QT, MASKED, SELF>), grid, dim3(SCAN_THREADS), lds, stream, p);
     return hipGetLastError() == hipSuccess;
 }
 
 template <typename T, int QT>
 bool launch_scan_t(const ScanParams & p, int n_chunks, hipStream_t stream) {
-    return p.mask ? launch_scan_m<T, QT, true>(p, n_chunks, stream) : launch_scan_m<T, QT, false>(p, n_chunks, stream);
+    if (p.qself) return p.mask ? launch_scan_m<T, QT, true, true>(p, n_chunks, stream) : launch_scan_m<T, QT, false, true>(p, n_chunks, stream);
+    return p.mask ? launch_scan_m<T, QT, true, false>(p, n_chunks, stream) : launch_scan_m<T, QT, false, false>(p, n_chunks, stream);
 }
 
 __global__ void __launch_bounds__(256) live_set_kernel(uint32_t * __restrict__ live, int64_t lo, int64_t hi) {
@@ -465,6 +462,26 @@ __global__ void __launch_bounds__(256) compact_gather_kernel(const u32x4 * __res
     }
 }
 
+// query workspace of a by-id search: query t is stored row ids[t] (ids NULL: row first + t), 16 bytes per thread
+__global__ void __launch_bounds__(256) search_gather_kernel(const u32x4 * __restrict__ rows, const float * __restrict__ rinv,
+                                                            const uint32_t * __restrict__ live, int64_t n, const int64_t * __restrict__ ids,
+                                                            int64_t first, int n_ids, int64_t n_rows, int pieces, u32x4 * __restrict__ q,
+                                                            float * __restrict__ qinv, int * __restrict__ qself) {
+    const int64_t items = n_rows * pieces;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < items; i += (int64_t)gridDim.x * 256) {
+        const int64_t t = i / pieces;
+        const int piece = (int)(i - t * pieces);
+        int64_t id = -1;
+        if (t < n_ids) id = ids ? ids[t] : first + t;
+        const bool ok = id >= 0 && id < n && ((live[id >> 5] >> (int)(id & 31)) & 1u);      // tested before anything is read at id
+        q[i] = ok ? rows[id * pieces + piece] : u32x4{0, 0, 0, 0};
+        if (piece == 0) {
+            if (qinv) qinv[t] = ok ? rinv[id] : 0.f;
+            qself[t] = ok ? (int)id : -1;
+        }
+    }
+}
+
 __global__ void __launch_bounds__(256) search_fill_allow_kernel(uint32_t * __restrict__ allow, int64_t n, int64_t words, float fraction,
                                                                 int contiguous, uint64_t seed) {
     const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -521,9 +538,10 @@ void launch_search_row_inv(const void * rows, int64_t n, int Dpad, float * inv, 
 }
 
 bool launch_search_scan(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq, int qt,
-                        int k, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask, hipStream_t stream) {
+                        int k, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask, const int * qself, hipStream_t stream) {
     ScanParams p;
     p.mask = mask;
+    p.qself = qself;
     p.rows = rows;
     p.q = q;
     p.rinv = rinv;
@@ -549,8 +567,17 @@ void launch_search_merge(const void * in, int64_t in_stride, int n_in, void * ou
     hipLaunchKernelGGL(search_merge_kernel, grid, dim3(256), 0, stream, (const Cand *)in, in_stride, n_in, (Cand *)out, nq, k);
 }
 
-void launch_search_finish(const void * in, int64_t in_stride, int nq, int k, float * dist, int64_t * ids, hipStream_t stream) {
-    hipLaunchKernelGGL(search_finish_kernel, dim3(nq), dim3(256), 0, stream, (const Cand *)in, in_stride, nq, k, dist, ids);
+void launch_search_finish(const void * in, int64_t in_stride, int nq, int k, float * dist, int64_t * ids, const int * qself, hipStream_t stream) {
+    hipLaunchKernelGGL(search_finish_kernel, dim3(nq), dim3(256), 0, stream, (const Cand *)in, in_stride, nq, k, dist, ids, qself);
+}
+
+void launch_search_gather(const void * rows, const float * rinv, const uint32_t * live, int64_t n, const int64_t * ids, int64_t first, int n_ids,
+                          int64_t n_rows, int64_t row_bytes, void * q, float * qinv, int * qself, hipStream_t stream) {
+    if (n_rows <= 0) return;
+    const int pieces = (int)(row_bytes / 16);
+    const int64_t blocks = std::min<int64_t>((n_rows * pieces + 255) / 256, 1 << 20);
+    hipLaunchKernelGGL(search_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const u32x4 *)rows, rinv, live, n, ids, first, n_ids,
+                       n_rows, pieces, (u32x4 *)q, qinv, qself);
 }
 
 void launch_search_fill_random(float * x, int64_t n, uint64_t seed, hipStream_t stream) {

@@ -308,9 +308,20 @@ void launch_search_prepare(const float * src, int64_t n_src, int64_t n_rows, int
                            hipStream_t stream);
 void launch_search_row_inv(const void * rows, int64_t n, int Dpad, float * inv, hipStream_t stream);
 bool launch_search_scan(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq, int qt,
-                        int k, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask, hipStream_t stream);
+                        int k, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask, const int * qself, hipStream_t stream);
 void launch_search_merge(const void * in, int64_t in_stride, int n_in, void * out, int nq, int k, hipStream_t stream);
-void launch_search_finish(const void * in, int64_t in_stride, int nq, int k, float * dist, int64_t * ids, hipStream_t stream);
+void launch_search_finish(const void * in, int64_t in_stride, int nq, int k, float * dist, int64_t * ids, const int * qself, hipStream_t stream);
+// Searches by id.  gather: query t of n_rows (the padded count) := stored row ids[t] (device; NULL: row first + t) for t < n_ids, bit for bit
+// (i8: qinv[t] := rinv of that row), qself[t] := that id; an id outside [0, n) or with a cleared bit in live, and every t >= n_ids, gives the
+// zero row and qself -1.  launch_search_scan with qself != NULL never makes row qself[query] a candidate of that query; launch_search_finish
+// with qself != NULL writes every slot of a query with qself < 0 as empty.
+void launch_search_gather(const void * rows, const float * rinv, const uint32_t * live, int64_t n, const int64_t * ids, int64_t first, int n_ids,
+                          int64_t n_rows, int64_t row_bytes, void * q, float * qinv, int * qself, hipStream_t stream);
+// k-NN graph (k_graph.hip): for the nq stored rows from q_first on, the candidates of their k nearest other rows from the tile engine of
+// k_join.hip with the selection of the scan: cand [n_chunks][nq][search_candidate_capacity(k)] as launch_search_scan leaves it (rows_per_chunk
+// a multiple of 128), for the same merge tree and finish.  mask (NULL: every row): the live bitmap; a removed query keeps no candidate.
+bool launch_graph(const void * rows, const float * rinv, int64_t n, int64_t q_first, int nq, int Dpad, int dtype, int k, void * cand, int n_chunks,
+                  int64_t rows_per_chunk, const uint32_t * mask, hipStream_t stream);
 void launch_search_fill_random(float * x, int64_t n, uint64_t seed, hipStream_t stream);
 // Row bitmap (layout as mask above).  set: bits [lo, hi) := 1.  remove: clears the bit of every ids[i] (device, each in range) and adds the
 // number of bits that were set to *removed.  mask_and: out[w] = live[w] & allow[w], allow words at w >= allow_words read as 0.

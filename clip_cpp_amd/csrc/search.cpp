@@ -1,5 +1,6 @@
 // search.cpp — the exact nearest-neighbour index of include/clip_amd.h (clip_amd_index_*): device-resident rows, argument checking,
-// query chunking, the scan -> merge tree -> finish launch sequence of k_search.hip, the count -> lims -> scatter -> sort -> finish sequence of
+// query chunking, the scan -> merge tree -> finish launch sequence of k_search.hip, searches by id and the k-NN graph (the gather kernel in
+// front of the same sequence, or the tiled kernel of k_graph.hip in the scan's place), the count -> lims -> scatter -> sort -> finish sequence of
 // range search and pairs (k_join.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
 // Replaces the usearch index of the reference's examples/image-search (build.cpp / search.cpp) with an exact search on the GPU.
 #include <algorithm>
@@ -54,7 +55,10 @@ struct clip_amd_index {
     Buf qinv;                      // i8: query inverse norms [nq_pad]
     Buf cand;                      // [n_chunks][nq][C] candidates
     Buf mbuf[2];                   // merge levels
-    Buf outs;                      // distances + ids of the host search form
+    Buf outs;                      // distances + ids of the host search form / of one query block of the k-NN graph
+    Buf idbuf;                     // ids of a search by id copied from the host
+    Buf qself;                     // searches by id: [nq_pad] the stored row each query is, -1 for a flagged one
+    int knn_route = 0;             // clip_amd_test_index_knn_route: 0 automatic, 1 scan, 2 tiled
     // range search / pairs
     Buf jcnt;                      // total (u64) + per-segment counts, reused as the scatter cursors
     Buf hits;                      // hit list
@@ -72,6 +76,8 @@ constexpr int64_t MAX_ROWS = 2147483647;
 constexpr size_t CAND_BUDGET = (size_t)512 << 20;       // bytes of candidate workspace per scan launch
 constexpr int64_t HOST_CHUNK_ROWS = 65536;              // rows per staging copy (add, save, load)
 constexpr int64_t JOIN_HIT_BUDGET = (int64_t)1 << 21;    // hits the first scoring pass keeps (24 MB); more only when the caller's capacity asks
+constexpr size_t GRAPH_OUT_BUDGET = (size_t)128 << 20;  // bytes of results one query block of the k-NN graph leaves on the device
+constexpr int64_t GRAPH_BLOCK_MAX = 65408;              // queries per block: 511 tiles of 128 (the merge and graph grids count them in 16 bits)
 
 hipStream_t stream_of(const clip_amd_index * ix) { return ix->ctx ? ix->ctx->stream : nullptr; }
 size_t row_stride(const clip_amd_index * ix) { return (size_t)ix->Dpad * ix->es; }      // bytes from one stored row to the next
@@ -241,11 +247,49 @@ int64_t rows_per_chunk(int64_t n, int k) {
     return (r + 63) / 64 * 64;
 }
 
-bool search_device_impl(clip_amd_index * ix, const float * d_q, int nq, int k, const uint32_t * d_allow, float * d_dist, int64_t * d_ids) {
+// Where the queries of a search come from: f32 vectors on the device (normalised / quantised into the query workspace), or stored rows by
+// id (gathered bit for bit): d_ids on the device or, NULL, the rows first, first + 1, ...
+struct QuerySource {
+    const float * d_q = nullptr;
+    bool by_id = false;
+    const int64_t * d_ids = nullptr;
+    int64_t first = 0;
+    bool exclude_self = false;
+};
+
+// n_src stored rows by id -> the query workspaces, n_rows (the padded count) rows, and qself
+bool gather_queries(clip_amd_index * ix, const QuerySource & src, int q0, int64_t n_src, int64_t n_rows) {
+    if (!ensure(ix, ix->qbuf, (size_t)n_rows * row_stride(ix)) || !ensure(ix, ix->qself, (size_t)n_rows * sizeof(int))) return false;
+    if (ix->dtype == SEARCH_I8 && !ensure(ix, ix->qinv, (size_t)n_rows * sizeof(float))) return false;
+    launch_search_gather(ix->store.rows, ix->store.rinv, ix->store.live, ix->n, src.d_ids ? src.d_ids + q0 : nullptr, src.first + q0, (int)n_src, n_rows,
+                         (int64_t)row_stride(ix), ix->qbuf.p, ix->dtype == SEARCH_I8 ? (float *)ix->qinv.p : nullptr, (int *)ix->qself.p, stream_of(ix));
+    return true;
+}
+
+// the merge tree over the chunks' lists of m queries and the finish into d_dist / d_ids ([m][k])
+bool merge_and_finish(clip_amd_index * ix, int n_chunks, int m, int k, const int * qself, float * d_dist, int64_t * d_ids) {
+    hipStream_t st = stream_of(ix);
+    const size_t mb = (size_t)((n_chunks + 1) / 2) * m * k * 8;
+    if (n_chunks > 1 && (!ensure(ix, ix->mbuf[0], mb) || !ensure(ix, ix->mbuf[1], mb))) return false;
+    const void * in = ix->cand.p;
+    int64_t stride = search_candidate_capacity(k);
+    int lists = n_chunks, t = 0;
+    while (lists > 1) {
+        launch_search_merge(in, stride, lists, ix->mbuf[t].p, m, k, st);
+        in = ix->mbuf[t].p;
+        t ^= 1;
+        stride = k;
+        lists = (lists + 1) / 2;
+    }
+    launch_search_finish(in, stride, m, k, d_dist, d_ids, qself, st);
+    return true;
+}
+
+bool search_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, int k, const uint32_t * d_allow, float * d_dist, int64_t * d_ids) {
     hipStream_t st = stream_of(ix);
     if (nq == 0) return true;
     if (ix->n == 0) {
-        launch_search_finish(nullptr, 0, nq, k, d_dist, d_ids, st);
+        launch_search_finish(nullptr, 0, nq, k, d_dist, d_ids, nullptr, st);
         return hipGetLastError() == hipSuccess;
     }
     const uint32_t * mask = nullptr;
@@ -259,30 +303,87 @@ bool search_device_impl(clip_amd_index * ix, const float * d_q, int nq, int k, c
         const int m = std::min(max_q, nq - q0);
         const int qt = m >= 64 ? 4 : (m > 16 ? 2 : 1);
         const int64_t m_pad = (m + 16 * qt - 1) / (16 * qt) * (16 * qt);
-        if (!prepare_queries(ix, d_q + (size_t)q0 * ix->dim, m, m_pad)) return false;
+        if (!(src.by_id ? gather_queries(ix, src, q0, m, m_pad) : prepare_queries(ix, src.d_q + (size_t)q0 * ix->dim, m, m_pad))) return false;
         if (!ensure(ix, ix->cand, (size_t)n_chunks * m * C * 8)) return false;
-        const size_t mb = (size_t)((n_chunks + 1) / 2) * m * k * 8;
-        if (n_chunks > 1 && (!ensure(ix, ix->mbuf[0], mb) || !ensure(ix, ix->mbuf[1], mb))) return false;
+        const int * qself = src.by_id ? (const int *)ix->qself.p : nullptr;
         if (!launch_search_scan(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, ix->qbuf.p, (const float *)ix->qinv.p, m, qt, k,
-                                ix->cand.p, n_chunks, rpc, mask, st)) {
+                                ix->cand.p, n_chunks, rpc, mask, src.exclude_self ? qself : nullptr, st)) {
             fprintf(stderr, "clip_amd_index_search: scan launch failed\n");
             return false;
         }
-        const void * in = ix->cand.p;
-        int64_t stride = C;
-        int lists = n_chunks, t = 0;
-        while (lists > 1) {
-            launch_search_merge(in, stride, lists, ix->mbuf[t].p, m, k, st);
-            in = ix->mbuf[t].p;
-            t ^= 1;
-            stride = k;
-            lists = (lists + 1) / 2;
-        }
-        launch_search_finish(in, stride, m, k, d_dist + (size_t)q0 * k, d_ids + (size_t)q0 * k, st);
+        if (!merge_and_finish(ix, n_chunks, m, k, qself, d_dist + (size_t)q0 * k, d_ids + (size_t)q0 * k)) return false;
         if (hipGetLastError() != hipSuccess) {
             fprintf(stderr, "clip_amd_index_search: launch failed\n");
             return false;
         }
+    }
+    return true;
+}
+
+QuerySource vectors(const float * d_q) {
+    QuerySource s;
+    s.d_q = d_q;
+    return s;
+}
+
+QuerySource stored_rows(const int64_t * d_ids, int64_t first, bool exclude_self) {
+    QuerySource s;
+    s.by_id = true;
+    s.d_ids = d_ids;
+    s.first = first;
+    s.exclude_self = exclude_self;
+    return s;
+}
+
+// Rows from which the automatic route of clip_amd_index_knn_graph takes the tiled kernel of k_graph.hip; below, the scan route.
+// NOT MEASURED YET (profiles/knn_bench.txt says why; scripts/knn_bench.py has a "crossover" section for it).  Until then the value comes
+// from the launch arithmetic alone: at 4096 rows the tiled route has 32 query tiles x 8 row chunks = one workgroup for every CU of an
+// MI355X, below that it leaves CUs idle while the scan's 64-row steps still fill them.
+constexpr int64_t KNN_TILED_MIN_ROWS = 4096;
+
+// The k-NN graph on the host: query blocks of a fixed size, one after another, each scored (scan route: the self-excluding scan over the
+// gathered rows; tiled route: graph_kernel straight from the store), merged, finished into the block's result workspace and copied out.
+bool knn_graph_impl(clip_amd_index * ix, int k, float * distances, int64_t * ids, const char * fn) {
+    hipStream_t st = stream_of(ix);
+    const int64_t n = ix->n;
+    if (n == 0) return true;
+    const bool tiled = ix->knn_route ? ix->knn_route == 2 : n >= KNN_TILED_MIN_ROWS;
+    const uint32_t * mask = ix->removed > 0 ? ix->store.live : nullptr;
+    const int C = search_candidate_capacity(k);
+    int64_t block = std::min<int64_t>({(n + 127) / 128 * 128, GRAPH_BLOCK_MAX, (int64_t)(GRAPH_OUT_BUDGET / ((size_t)k * 12)) / 128 * 128,
+                                       (int64_t)(CAND_BUDGET / ((size_t)C * 8)) / 128 * 128});
+    // tiled route: a query tile's rows are split across workgroups until the device is full (a chunk at least 4 k rows, as in the scan)
+    int n_chunks = 1;
+    int64_t rpc = (n + 127) / 128 * 128;
+    if (tiled) {
+        int dev = 0, cus = 0;
+        (void)hipGetDevice(&dev);
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
+        (void)hipGetLastError();
+        const int64_t q_tiles = (std::min(block, n) + 127) / 128;
+        const int64_t min_rpc = (std::max<int64_t>(256, 4 * (int64_t)k) + 127) / 128 * 128;
+        int64_t want = std::max<int64_t>(1, std::min<int64_t>({(cus + q_tiles - 1) / q_tiles, (n + min_rpc - 1) / min_rpc,
+                                                                (int64_t)(CAND_BUDGET / ((size_t)block * C * 8))}));
+        rpc = ((n + want - 1) / want + 127) / 128 * 128;
+        n_chunks = (int)((n + rpc - 1) / rpc);
+    }
+    if (!ensure(ix, ix->outs, (size_t)block * k * 12)) return false;
+    int64_t * d_ids = (int64_t *)ix->outs.p;
+    float * d_dist = (float *)((char *)ix->outs.p + (size_t)block * k * 8);
+    for (int64_t q0 = 0; q0 < n; q0 += block) {
+        const int m = (int)std::min(block, n - q0);
+        if (!tiled) {
+            if (!search_device_impl(ix, stored_rows(nullptr, q0, true), m, k, nullptr, d_dist, d_ids)) return false;
+        } else {
+            if (!ensure(ix, ix->cand, (size_t)n_chunks * m * C * 8)) return false;
+            if (!launch_graph(ix->store.rows, ix->store.rinv, n, q0, m, ix->Dpad, ix->dtype, k, ix->cand.p, n_chunks, rpc, mask, st)) {
+                fprintf(stderr, "%s: graph launch failed\n", fn);
+                return false;
+            }
+            if (!merge_and_finish(ix, n_chunks, m, k, nullptr, d_dist, d_ids)) return false;
+            if (hipGetLastError() != hipSuccess) { fprintf(stderr, "%s: launch failed\n", fn); return false; }
+        }
+        if (!copy_results(ix, d_dist, d_ids, (size_t)m * k, distances + (size_t)q0 * k, ids + (size_t)q0 * k, fn)) return false;
     }
     return true;
 }
@@ -436,14 +537,14 @@ float bench_search_impl(int dtype, int64_t n, int dim, int n_queries, int k, flo
         if (ok) {
             launch_search_fill_random(src, (int64_t)n_queries * dim, 0xC0FFEEull, nullptr);
             if (d_allow) launch_search_fill_allow(d_allow, n, fraction, contiguous, 0xA110ull, nullptr);
-            ok = search_device_impl(ix, src, n_queries, k, d_allow, d_dist, d_ids) && hipDeviceSynchronize() == hipSuccess;
+            ok = search_device_impl(ix, vectors(src), n_queries, k, d_allow, d_dist, d_ids) && hipDeviceSynchronize() == hipSuccess;
         }
         if (ok) {
             hipEvent_t e0, e1;
             (void)hipEventCreate(&e0);
             (void)hipEventCreate(&e1);
             (void)hipEventRecord(e0, nullptr);
-            for (int i = 0; ok && i < iters; i++) ok = search_device_impl(ix, src, n_queries, k, d_allow, d_dist, d_ids);
+            for (int i = 0; ok && i < iters; i++) ok = search_device_impl(ix, vectors(src), n_queries, k, d_allow, d_dist, d_ids);
             (void)hipEventRecord(e1, nullptr);
             float ms = -1.f;
             if (ok && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) us = ms * 1000.f / iters;
@@ -506,7 +607,7 @@ static bool search_device_call(struct clip_amd_index * ix, const float * d_queri
     return guarded(name, false, [&](const char * fn) {
         if (!check_search_args(ix, d_queries, n_queries, k, d_distances, d_ids, fn)) return false;
         (void)hipSetDevice(ix->device);
-        return search_device_impl(ix, d_queries, n_queries, k, (const uint32_t *)d_allow, d_distances, d_ids);
+        return search_device_impl(ix, vectors(d_queries), n_queries, k, (const uint32_t *)d_allow, d_distances, d_ids);
     });
 }
 
@@ -532,7 +633,7 @@ static bool search_call(struct clip_amd_index * ix, const float * queries, int n
         if (!stage_inputs(ix, queries, n_queries, allow, d_q, d_allow) || !ensure(ix, ix->outs, count * 12)) return false;
         int64_t * d_ids = (int64_t *)ix->outs.p;
         float * d_dist = (float *)((char *)ix->outs.p + count * 8);
-        return search_device_impl(ix, d_q, n_queries, k, d_allow, d_dist, d_ids) && copy_results(ix, d_dist, d_ids, count, distances, ids, fn);
+        return search_device_impl(ix, vectors(d_q), n_queries, k, d_allow, d_dist, d_ids) && copy_results(ix, d_dist, d_ids, count, distances, ids, fn);
     });
 }
 
@@ -748,6 +849,90 @@ int64_t clip_amd_index_pairs(struct clip_amd_index * ix, float radius, int64_t *
         if (!check_join_args(ix, radius, lims, distances, ids, capacity, fn)) return -1;
         (void)hipSetDevice(ix->device);
         return join_impl(ix, nullptr, 0, true, radius, nullptr, lims, distances, ids, capacity, fn);
+    });
+}
+
+bool clip_amd_index_search_ids_device(struct clip_amd_index * ix, const int64_t * d_ids, int n_ids, int k, int exclude_self,
+                                      const uint64_t * d_allow, float * d_distances, int64_t * d_out_ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_search_args(ix, d_ids, n_ids, k, d_distances, d_out_ids, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return search_device_impl(ix, stored_rows(d_ids, 0, exclude_self != 0), n_ids, k, (const uint32_t *)d_allow, d_distances, d_out_ids);
+    });
+}
+
+bool clip_amd_index_search_ids(struct clip_amd_index * ix, const int64_t * ids, int n_ids, int k, int exclude_self, const uint64_t * allow,
+                               float * distances, int64_t * out_ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_search_args(ix, ids, n_ids, k, distances, out_ids, fn)) return false;
+        if (n_ids == 0) return true;
+        (void)hipSetDevice(ix->device);
+        hipStream_t st = stream_of(ix);
+        std::vector<uint32_t> live;                        // only when rows were removed: every in-range id is live otherwise
+        if (ix->removed > 0) {
+            live.resize(live_bytes(ix->n) / 4);
+            if (!stream_done(ix, fn, hipMemcpyAsync(live.data(), ix->store.live, live.size() * 4, hipMemcpyDeviceToHost, st))) return false;
+        }
+        for (int t = 0; t < n_ids; t++) {
+            const int64_t id = ids[t];
+            if (id < 0 || id >= ix->n) {
+                fprintf(stderr, "%s: id %lld (entry %d) outside 0 ... %lld: nothing searched\n", fn, (long long)id, t, (long long)ix->n - 1);
+                return false;
+            }
+            if (!live.empty() && !((live[(size_t)(id >> 5)] >> (int)(id & 31)) & 1u)) {
+                fprintf(stderr, "%s: id %lld (entry %d) was removed: nothing searched\n", fn, (long long)id, t);
+                return false;
+            }
+        }
+        const size_t count = (size_t)n_ids * k, ab = (size_t)search_allow_words(ix->n) * 4;
+        const uint32_t * d_allow = nullptr;
+        if (!ensure(ix, ix->idbuf, (size_t)n_ids * 8) || !ensure(ix, ix->outs, count * 12)) return false;
+        (void)hipMemcpyAsync(ix->idbuf.p, ids, (size_t)n_ids * 8, hipMemcpyHostToDevice, st);
+        if (allow) {
+            if (!ensure(ix, ix->abuf, ab)) return false;
+            (void)hipMemcpyAsync(ix->abuf.p, allow, ab, hipMemcpyHostToDevice, st);
+            d_allow = (const uint32_t *)ix->abuf.p;
+        }
+        int64_t * d_out = (int64_t *)ix->outs.p;
+        float * d_dist = (float *)((char *)ix->outs.p + count * 8);
+        return search_device_impl(ix, stored_rows((const int64_t *)ix->idbuf.p, 0, exclude_self != 0), n_ids, k, d_allow, d_dist, d_out) &&
+               copy_results(ix, d_dist, d_out, count, distances, out_ids, fn);
+    });
+}
+
+bool clip_amd_index_knn_graph(struct clip_amd_index * ix, int k, float * distances, int64_t * ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+        if (k < 1 || k > MAX_K) { fprintf(stderr, "%s: k = %d outside 1 ... %d\n", fn, k, MAX_K); return false; }
+        if (ix->n > 0 && (!distances || !ids)) { fprintf(stderr, "%s: NULL result pointer\n", fn); return false; }
+        (void)hipSetDevice(ix->device);
+        return knn_graph_impl(ix, k, distances, ids, fn);
+    });
+}
+
+int clip_amd_test_index_knn_route(struct clip_amd_index * ix, int route) {
+    if (!ix || route < 0 || route > 2) return -1;
+    ix->knn_route = route;
+    return route;
+}
+
+float clip_amd_bench_knn(int dtype, int64_t n, int dim, int k, int route, int iters) {
+    return guarded(__func__, -4.f, [&](const char * fn) {
+        const bool args_ok = k >= 1 && k <= MAX_K && route >= 0 && route <= 2;
+        return bench_on_gallery(dtype, n, dim, 0, iters, args_ok, false, [&](clip_amd_index * ix, float *) {
+            std::vector<float> dist((size_t)n * k);
+            std::vector<int64_t> ids((size_t)n * k);
+            ix->knn_route = route;
+            float us = -4.f;
+            bool ok = hipDeviceSynchronize() == hipSuccess && knn_graph_impl(ix, k, dist.data(), ids.data(), fn);      // a warm call
+            if (ok) {
+                const auto t0 = std::chrono::steady_clock::now();
+                for (int i = 0; ok && i < iters; i++) ok = knn_graph_impl(ix, k, dist.data(), ids.data(), fn);
+                const auto t1 = std::chrono::steady_clock::now();
+                if (ok) us = (float)(std::chrono::duration<double, std::micro>(t1 - t0).count() / iters);
+            }
+            return us;
+        });
     });
 }
 

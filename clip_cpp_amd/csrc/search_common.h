@@ -92,6 +92,29 @@ __device__ __forceinline__ typename ScanAcc<T>::type mfma_step(u32x4 a, u32x4 b,
 __device__ __forceinline__ float scan_distance(float acc, float, float) { return 1.0f - acc; }
 __device__ __forceinline__ float scan_distance(int dot, float qinv, float rinv) { return 1.0f - (float)dot * qinv * rinv; }
 
+// The tile engine's staging scheme, shared by k_join.hip (range search / pairs) and k_graph.hip (k-NN graph)
+constexpr int JOIN_THREADS = 256;
+constexpr int JOIN_BM = 128;                  // rows per tile
+constexpr int JOIN_KC = 4;                    // k-steps (64 bytes of a row each) per LDS chunk
+constexpr int JOIN_LROW = JOIN_KC * 64 + 32;  // LDS bytes per staged row
+
+// keep the best min(k, cnt) of a query's candidates (sorted, at the head of its buffer); returns the new count.  `final`: write all k
+// slots (empty ones as +inf / INT_MAX) so the merge reads k sorted entries.
+__device__ int wave_select(Cand * buf, int cnt, int k, int P, bool final, float * bs, int * bi, int lane) {
+    for (int i = lane; i < P; i += 64) {
+        Cand c = i < cnt ? buf[i] : Cand{INFINITY, INT_MAX};
+        bs[i] = c.s;
+        bi[i] = c.id;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sort(bs, bi, P, lane);
+    const int keep = final ? k : (cnt < k ? cnt : k);
+    for (int i = lane; i < keep; i += 64) buf[i] = Cand{bs[i], bi[i]};
+    return cnt < k ? cnt : k;
+}
+
 }  // namespace
 
 }  // namespace clipamd

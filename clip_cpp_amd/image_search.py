@@ -4,7 +4,9 @@ build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.In
     python -m clip_cpp_amd.image_search build  [-m MODEL] [-v N] [-t N] [--db DIR] [--dtype f16|f32|i8] dir [more dirs]
     python -m clip_cpp_amd.image_search update [-m MODEL] [-v N] [-t N] [--db DIR] dir [more dirs]
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N | -d R] [--in PREFIX]... [--db DIR] <search text or /path/to/query/image>
+    python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-n N] [--in PREFIX]... [--db DIR] --like INDEXED/IMAGE/PATH
     python -m clip_cpp_amd.image_search dedup  [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R]
+    python -m clip_cpp_amd.image_search neighbors [-m MODEL] [-v N] [--db DIR] [-n N]
 
 `build` writes DIR/images.index (the CLIPIDX1 file of clip_amd_index_save) and DIR/images.paths (the reference's layout: the model path
 on the first line, then one image path per id).  `search` prints the reference's output: "search results:" / "distance path" at
@@ -17,6 +19,11 @@ and both files are rewritten: the survivors in their old order, then the new fil
 the groups of near-duplicate images (connected components of the pairs within distance R, clip_amd_index_pairs): "duplicate groups:" at
 verbosity > 0, then per group, in order of its lowest id, "  %f %s" per member in id order (the distance to its nearest other member),
 groups separated by a blank line, and "main: %d groups, %d images".
+`search --like PATH` asks for "more like this one": the query is the indexed image whose line in images.paths equals PATH as written
+(Index.search_ids: its stored row, nothing is decoded or encoded, so a text-only or vision-less model is enough); the image itself is not
+listed.  It composes with -n and --in, not with a positional query or -d.  `neighbors` prints the k-NN graph (Index.knn_graph, one call):
+"neighbours:" at verbosity > 0, then per image, in id order, its path on a line of its own and "  %f %s" per neighbour, the -n (default 5)
+nearest other images, nearest first; images separated by a blank line, and "main: %d images, %d neighbours each".
 """
 import ctypes as C
 import os
@@ -53,33 +60,38 @@ def _err(msg):
     print(msg, file=sys.stderr, flush=True)
 
 
-def _parse(argv, build, dedup=False, update=False):
-    """Reference-style option parsing (examples/image-search/{build,search}.cpp my_app_params_parse); `dedup` takes no positional
-    arguments; `update` takes build's directories, but neither a default model nor --dtype (both come from the database)."""
+def _parse(argv, build, dedup=False, update=False, neighbors=False):
+    """Reference-style option parsing (examples/image-search/{build,search}.cpp my_app_params_parse); `dedup` and `neighbors` take no
+    positional arguments; `update` takes build's directories, but neither a default model nor --dtype (both come from the database)."""
     p = dict(threads=4, verbose=1, db=".", dtype="f16", results=5, max_distance=DEDUP_RADIUS if dedup else None,
-             model="../models/ggml-model-f16.bin" if build else "", rest=[])
+             model="../models/ggml-model-f16.bin" if build else "", rest=[], like=None)
     p["in"] = []
-    search = not (build or dedup or update)
+    search = not (build or dedup or update or neighbors)
     seen = set()
     i = 0
     while i < len(argv):
         a = argv[i]
         takes = {"-m": "model", "--model": "model", "-v": "verbose", "--verbose": "verbose", "--db": "db"}
-        if not dedup:
+        if not (dedup or neighbors):
             takes.update({"-t": "threads", "--threads": "threads"})
         if build:
             takes["--dtype"] = "dtype"
+        elif neighbors:
+            takes.update({"-n": "results", "--results": "results"})
         elif not update:
             takes.update({"-d": "max_distance", "--max-distance": "max_distance"})
             if not dedup:
                 takes.update({"-n": "results", "--results": "results"})
         if search:
-            takes["--in"] = "in"
+            takes.update({"--in": "in", "--like": "like"})
         if a in takes:
             i += 1
             if i >= len(argv):
                 return None
             key = takes[a]
+            if key == "like" and "like" in seen:
+                print("main: --like takes one indexed image: it cannot be given twice")
+                return None
             seen.add(key)
             if key == "in":
                 p["in"].append(argv[i])
@@ -92,12 +104,12 @@ def _parse(argv, build, dedup=False, update=False):
             if key == "max_distance" and p[key] != p[key]:      # NaN
                 return None
         elif a in ("-h", "--help"):
-            _help(build, p, dedup, update)
+            _help(build, p, dedup, update, neighbors)
             sys.exit(0)
         elif a.startswith("-"):
             print("main: unrecognized argument: %s" % a)
             return None
-        elif dedup:
+        elif dedup or neighbors:
             print("main: unexpected argument: %s" % a)
             return None
         elif build or update:
@@ -106,7 +118,11 @@ def _parse(argv, build, dedup=False, update=False):
             p["rest"] = argv[i:]     # the query: everything from here on
             break
         i += 1
-    if (not p["rest"] and not dedup) or (build and p["dtype"] not in ("f16", "f32", "i8")):
+    if p["like"] is not None:
+        if p["rest"] or "max_distance" in seen:
+            print("main: --like cannot be combined with a query or with -d: it lists the -n nearest images of an indexed one")
+            return None
+    elif (not p["rest"] and not (dedup or neighbors)) or (build and p["dtype"] not in ("f16", "f32", "i8")):
         return None
     if {"results", "max_distance"} <= seen:
         print("main: -n and -d cannot be combined: -n N prints the N nearest, -d R every image within R")
@@ -114,10 +130,19 @@ def _parse(argv, build, dedup=False, update=False):
     return p
 
 
-def _help(build, p, dedup=False, update=False):
+def _help(build, p, dedup=False, update=False, neighbors=False):
     radius = ("  -d R, --max-distance R: %s within cosine distance R (<= R). Default: %s. %g is a starting point for embeddings of near-identical"
               " images, not a tuned value: check a few groups of your collection and adjust R")
-    if dedup:
+    if neighbors:
+        print("Usage: python -m clip_cpp_amd.image_search neighbors [options]")
+        print("\nPrints, for every image of an index built by `build`, its nearest other images (the k-NN graph of the index).")
+        print("\nOptions:")
+        print("  -h, --help: Show this message and exit")
+        print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default (loaded only to place the index on its device).")
+        print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
+        print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
+        print("  -n N, --results N: Number of neighbours per image (at most %d). Default: %d" % (MAX_K, p["results"]))
+    elif dedup:
         print("Usage: python -m clip_cpp_amd.image_search dedup [options]")
         print("\nPrints the groups of near-duplicate images of an index built by `build` (connected components of the image pairs within R).")
         print("\nOptions:")
@@ -149,6 +174,7 @@ def _help(build, p, dedup=False, update=False):
         print("  --dtype f16|f32|i8: stored precision of the index (i8: int8 rows, half of f16's memory). Default: %s" % p["dtype"])
     else:
         print("Usage: python -m clip_cpp_amd.image_search search [options] <search string or /path/to/query/image>")
+        print("       python -m clip_cpp_amd.image_search search [options] --like <indexed/image/path>")
         print("\nOptions:")
         print("  -h, --help: Show this message and exit")
         print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default.")
@@ -158,6 +184,8 @@ def _help(build, p, dedup=False, update=False):
         print("  -d R, --max-distance R: display every indexed image within cosine distance R (<= R), nearest first, instead of the -n nearest (not with -n)")
         print("  --in <prefix>: only images whose indexed path starts with <prefix> are eligible (one directory, one album); may be repeated:"
               " a path matching any prefix is eligible. Works with -n and with -d")
+        print("  --like <path>: more like this one: the query is the indexed image whose line in %s equals <path> as written; nothing is"
+              " decoded or encoded and the image itself is not listed. Works with -n and --in, not with a query or -d" % PATHS_FILE)
         print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
 
 
@@ -373,12 +401,21 @@ def search(argv):
     image_paths = _read_db(p)
     if image_paths is None:
         return 1
+    like_id = None
+    if p["like"] is not None:
+        if p["like"] not in image_paths:
+            _err("main: '%s' is not in the database (paths are compared as written in %s)" % (p["like"], PATHS_FILE))
+            return 1
+        like_id = image_paths.index(p["like"])
     try:
         clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])
     except RuntimeError:
         print("main: Unable to load model from %s" % p["model"])
         return 1
-    if img_path:
+    vec = None
+    if like_id is not None:
+        pass                                       # the query is a stored row: no tower is needed
+    elif img_path:
         if clip.vision_config["n_layer"] <= 0:
             _err("main: the model at %s has no vision encoder: image queries need a vision or two-tower model" % p["model"])
             return 1
@@ -397,7 +434,7 @@ def search(argv):
             return 1
         vec = np.asarray(clip.encode_text(clip.tokenize(text), n_threads=p["threads"], normalize=True), dtype=np.float32)
     index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
-    if index.dim != vec.size:
+    if vec is not None and index.dim != vec.size:
         _err("main: the index holds %d-dimensional embeddings, the model makes %d" % (index.dim, vec.size))
         return 1
     allow = None
@@ -408,7 +445,7 @@ def search(argv):
         hits = list(zip(dist, ids))
     else:
         k = max(1, min(p["results"], MAX_K))
-        dist, ids = index.search(vec[None, :], k, allow=allow)
+        dist, ids = index.search_ids([like_id], k, allow=allow) if like_id is not None else index.search(vec[None, :], k, allow=allow)
         hits = [(d, i) for d, i in zip(dist[0], ids[0]) if i >= 0 and p["results"] > 0]
     if p["verbose"] > 0:
         print("search results:")
@@ -477,12 +514,46 @@ def dedup(argv):
     return 0
 
 
+def neighbors(argv):
+    import clip_cpp_amd
+    p = _parse(argv, build=False, neighbors=True)
+    if p is None:
+        _help(False, dict(verbose=1, db=".", results=5), neighbors=True)
+        return 1
+    image_paths = _read_db(p)
+    if image_paths is None:
+        return 1
+    try:
+        clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])      # only the index's device: no image is encoded
+    except RuntimeError:
+        print("main: Unable to load model from %s" % p["model"])
+        return 1
+    index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
+    k = max(1, min(p["results"], MAX_K))
+    dist, ids = index.knn_graph(k)
+    if p["verbose"] > 0:
+        print("neighbours:")
+    for i, path in enumerate(image_paths):
+        if i:
+            print()
+        print(path)
+        for d, j in zip(dist[i], ids[i]):
+            if j >= 0 and p["results"] > 0:
+                print("  %f %s" % (d, image_paths[j]))
+    print("main: %d images, %d neighbours each" % (len(image_paths), k if p["results"] > 0 else 0))
+    sys.stdout.flush()
+    index.close()
+    clip.close()
+    return 0
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
-    commands = {"build": build, "update": update, "search": search, "dedup": dedup}
+    commands = {"build": build, "update": update, "search": search, "dedup": dedup, "neighbors": neighbors}
     if not argv or argv[0] not in commands:
         print("Usage: python -m clip_cpp_amd.image_search {build|search|dedup} [options] ...  (-h after the command for its options)")
         print("       python -m clip_cpp_amd.image_search update [options] dir [more dirs]  (an existing database brought in line with the disk)")
+        print("       python -m clip_cpp_amd.image_search neighbors [options]  (every indexed image's nearest other images; search --like PATH for one)")
         return 1
     return commands[argv[0]](argv[1:])
 

@@ -204,6 +204,38 @@ float clip_amd_bench_search(int dtype, int64_t n, int dim, int n_queries, int k,
 /* The same with an allowed set over the same seeded rows and queries (clip_amd_index_search_subset_device): allowed_fraction in [0, 1] of
  * the ids, a seeded random selection or, contiguous != 0, one id range in the middle of the index.  Used by scripts/subset_bench.py. */
 float clip_amd_bench_search_subset(int dtype, int64_t n, int dim, int n_queries, int k, float allowed_fraction, int contiguous, int iters);
+/* Neighbours of stored rows and the k-NN graph: searches whose queries are rows of the index itself ("more like this one", the related
+ * images of every image), without the vectors that were added and without a model.
+ * The query for ids[t] is that row's stored values copied bit for bit (i8: inv_q := inv_r of the row); it is never renormalised or
+ * requantised, so with exclude_self == 0 the result for ids[t] is, bit for bit (distances, ids, order, tail), what
+ * clip_amd_index_search_subset returns for the vector that was added as that row with the same allow.  With exclude_self != 0 row ids[t]
+ * is not eligible for query t (other queries still see it): the result is, bit for bit, search_subset with that row's bit cleared in
+ * allow, the result of an index that never held the row; equal distances still come lower id first and the tail holds -1 / +INFINITY.
+ * allow (layout as live_mask) restricts the candidates only: the query row itself need not be allowed; NULL = every live row.
+ * 1 <= k <= 1024; duplicate ids are fine; n_ids == 0 succeeds and launches nothing.
+ * Host form: an id outside [0, size) or a removed id makes the call return false with a message on stderr that names the id; nothing is
+ * launched and the outputs are untouched (the discipline of clip_amd_index_remove).  Device form: the ids cannot be checked without a
+ * round trip, so an out-of-range or removed id yields an all-empty result row (-1 / +INFINITY); the gather tests the id before it reads
+ * anything there, so such an id never causes an out-of-bounds read.
+ * knn_graph: for every id in [0, size) its k nearest OTHER live rows; distances / ids are host [size][k].  Row i is search_ids(i, k,
+ * exclude_self = 1, allow = NULL) for a live row i, bit for bit; the row of a removed id is all -1 / +INFINITY; size == 0 succeeds and
+ * writes nothing.  Small indexes run the self-excluding scan over blocks of gathered rows, larger ones the tiled kernel of k_graph.hip
+ * (128 stored rows x 128 stored rows per workgroup step, the top-k selection of the scan behind it); both give the same bits.  Device
+ * memory beyond the index is a fixed workspace (candidates <= 512 MB, one query block's results <= 128 MB): query blocks are processed
+ * and copied out one after another, nothing grows with size x k.
+ * Results are bit-identical run to run, across both graph routes, however rows were split across add calls, across save / load, and
+ * across compact (ids mapped through new_ids) as long as no removed row was among a survivor's neighbours. */
+bool clip_amd_index_search_ids(struct clip_amd_index * ix, const int64_t * ids, int n_ids, int k, int exclude_self, const uint64_t * allow,
+                               float * distances, int64_t * out_ids);                                       /* host, synchronous */
+bool clip_amd_index_search_ids_device(struct clip_amd_index * ix, const int64_t * d_ids, int n_ids, int k, int exclude_self,
+                                      const uint64_t * d_allow, float * d_distances, int64_t * d_out_ids);  /* HBM, asynchronous */
+bool clip_amd_index_knn_graph(struct clip_amd_index * ix, int k, float * distances, int64_t * ids);
+/* test hook: the route of clip_amd_index_knn_graph on this index from now on: 0 automatic, 1 the scan route, 2 the tiled kernel.  Returns
+ * the route set, -1 for a NULL index or another value. */
+int clip_amd_test_index_knn_route(struct clip_amd_index * ix, int route);
+/* Average wall time (microseconds) of one clip_amd_index_knn_graph over n seeded random rows on the current device (results copied to the
+ * host included), route as above; < 0 on error.  Used by scripts/knn_bench.py. */
+float clip_amd_bench_knn(int dtype, int64_t n, int dim, int k, int route, int iters);
 /* Range search and near-duplicate pairs.
  * Distance: exactly what clip_amd_index_search reports for the same (query, row) pair (the same stored values, the same MFMA chain per
  * dtype, the same f32 expression); a row is a result when d <= radius, compared in f32.
