@@ -76,6 +76,7 @@ AMD_SYMBOLS = [
     "clip_amd_index_remove", "clip_amd_index_live", "clip_amd_index_live_mask", "clip_amd_index_compact", "clip_amd_index_search_subset",
     "clip_amd_index_search_subset_device", "clip_amd_index_range_search_subset", "clip_amd_bench_search_subset",
     "clip_amd_index_search_ids", "clip_amd_index_search_ids_device", "clip_amd_index_knn_graph", "clip_amd_test_index_knn_route", "clip_amd_bench_knn",
+    "clip_amd_index_search_index", "clip_amd_index_append", "clip_amd_test_index_cross_route", "clip_amd_bench_cross",
 ]
 
 _lib = None
@@ -263,6 +264,14 @@ def lib():
     L.clip_amd_test_index_knn_route.argtypes = [vp, i32]
     L.clip_amd_bench_knn.restype = C.c_float
     L.clip_amd_bench_knn.argtypes = [i32, i64, i32, i32, i32, i32]
+    L.clip_amd_index_search_index.restype = C.c_bool
+    L.clip_amd_index_search_index.argtypes = [vp, vp, i64p, i64, i32, u64p, f32p, i64p]
+    L.clip_amd_index_append.restype = i64
+    L.clip_amd_index_append.argtypes = [vp, vp, i64p]
+    L.clip_amd_test_index_cross_route.restype = i32
+    L.clip_amd_test_index_cross_route.argtypes = [vp, i32]
+    L.clip_amd_bench_cross.restype = C.c_float
+    L.clip_amd_bench_cross.argtypes = [i32, i64, i64, i32, i32, i32, i32]
     _lib = L
     return L
 
@@ -595,7 +604,12 @@ class Index:
     search_ids(ids, k) finds the neighbours of rows that are already stored ("more like this one"): the query is the row's stored values,
     bit for bit, so no vector and no model is needed; with exclude_self (the default) the row itself is not a candidate, and the result is
     what search gives for the added vector with that row's bit cleared in `allow`.  knn_graph(k) is the same for every row at once: its k
-    nearest other live rows (an all -1 / +inf row for a removed id), from a tiled kernel on larger indexes."""
+    nearest other live rows (an all -1 / +inf row for a removed id), from a tiled kernel on larger indexes.
+
+    search_index(src, k) searches this index with the stored rows of another one of the same Clip, dim and dtype (every row, or `ids` of
+    them): row t of the result is what search gives for the vector that was added to `src` as that row, bit for bit.  append(src) copies
+    src's rows, bit for bit, to the end of this index.  Neither needs the vectors that were added, or a model; `src` must hold no removed
+    rows (compact() it first)."""
 
     DTYPES = {"f32": 0, "f16": 1, "i8": 3}
 
@@ -749,6 +763,32 @@ class Index:
             raise RuntimeError("clip_amd_index_knn_graph failed (see stderr)")
         return dist, ids
 
+    def search_index(self, src, k, ids=None, allow=None):
+        """This index searched with the stored rows of `src` (an Index of the same Clip, dim and dtype without removed rows): every row in
+        id order, or the rows `ids` (duplicates and any order are fine).  (distances f32 [n, k], ids int64 [n, k]) as `search` gives them
+        for the vectors that were added to `src` as those rows; `allow` (bool mask [len(self)] or ids) restricts the candidates.
+        `src is self` equals search_ids(..., exclude_self=False)."""
+        a, ap = None, None
+        n = len(src)
+        if ids is not None:
+            a = np.zeros(np.size(ids) + 1, dtype=np.int64)[:np.size(ids)]      # (no ids is still an array, not the NULL of "every row")
+            a[:] = np.asarray(ids, dtype=np.int64).reshape(-1)
+            ap, n = a.ctypes.data_as(C.POINTER(C.c_int64)), a.size
+        words, wp = self._allow(allow)
+        dist = np.empty((n, k), dtype=np.float32)
+        out = np.empty((n, k), dtype=np.int64)
+        if not lib().clip_amd_index_search_index(self._live(), src._live(), ap, n, int(k), wp, _fp(dist), out.ctypes.data_as(C.POINTER(C.c_int64))):
+            raise RuntimeError("clip_amd_index_search_index failed (see stderr)")
+        return dist, out
+
+    def append(self, src):
+        """Append every row of `src` (same Clip, dim and dtype, no removed rows, not this index) bit for bit; `src` is unchanged.  Returns
+        new_ids int64 [len(src)]: each src id's id in this index."""
+        new_ids = np.empty(len(src), dtype=np.int64)
+        if lib().clip_amd_index_append(self._live(), src._live(), new_ids.ctypes.data_as(C.POINTER(C.c_int64))) < 0:
+            raise RuntimeError("clip_amd_index_append failed (see stderr)")
+        return new_ids
+
     def search_device(self, d_queries, n_queries, k, d_distances, d_ids):
         """Device pointers (ints): queries [n, dim] f32 -> distances [n, k] f32, ids [n, k] int64; asynchronous on the context's stream."""
         if not lib().clip_amd_index_search_device(self._live(), C.c_void_p(d_queries), int(n_queries), int(k), C.c_void_p(d_distances),
@@ -804,6 +844,12 @@ def bench_knn(dtype, n, dim, k, route=0, iters=3):
     """Microseconds (wall) per clip_amd_index_knn_graph over n seeded random rows; route 0 automatic, 1 the scan route, 2 the tiled kernel
     (clip_amd_bench_knn); < 0 on error."""
     return float(lib().clip_amd_bench_knn(Index.DTYPES[dtype], int(n), int(dim), int(k), int(route), int(iters)))
+
+
+def bench_cross(dtype, n_rows, n_queries, dim, k, route=0, iters=3):
+    """Microseconds (wall) per clip_amd_index_search_index of an index of n_rows seeded random rows with every one of the n_queries rows of a
+    second one; route 0 automatic, 1 the scan route, 2 the tiled kernel (clip_amd_bench_cross); < 0 on error."""
+    return float(lib().clip_amd_bench_cross(Index.DTYPES[dtype], int(n_rows), int(n_queries), int(dim), int(k), int(route), int(iters)))
 
 
 def gguf_inspect(path):

@@ -322,6 +322,11 @@ void launch_search_gather(const void * rows, const float * rinv, const uint32_t 
 // a multiple of 128), for the same merge tree and finish.  mask (NULL: every row): the live bitmap; a removed query keeps no candidate.
 bool launch_graph(const void * rows, const float * rinv, int64_t n, int64_t q_first, int nq, int Dpad, int dtype, int k, void * cand, int n_chunks,
                   int64_t rows_per_chunk, const uint32_t * mask, hipStream_t stream);
+// The same tile loop with the queries taken from a second store of the same dim and dtype (clip_amd_index_search_index): the nq rows from
+// q_first on of qrows / qrinv (qn rows, q_first + nq <= qn) against the n rows of rows / rinv.  No row is excluded as "self"; mask (NULL:
+// every row) is the candidate side's effective mask (live & allow) and says nothing about the queries, which are all scored.
+bool launch_graph_cross(const void * rows, const float * rinv, int64_t n, const void * qrows, const float * qrinv, int64_t qn, int64_t q_first, int nq,
+                        int Dpad, int dtype, int k, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask, hipStream_t stream);
 void launch_search_fill_random(float * x, int64_t n, uint64_t seed, hipStream_t stream);
 // Row bitmap (layout as mask above).  set: bits [lo, hi) := 1.  remove: clears the bit of every ids[i] (device, each in range) and adds the
 // number of bits that were set to *removed.  mask_and: out[w] = live[w] & allow[w], allow words at w >= allow_words read as 0.

@@ -1,6 +1,7 @@
 // search.cpp — the exact nearest-neighbour index of include/clip_amd.h (clip_amd_index_*): device-resident rows, argument checking,
-// query chunking, the scan -> merge tree -> finish launch sequence of k_search.hip, searches by id and the k-NN graph (the gather kernel in
-// front of the same sequence, or the tiled kernel of k_graph.hip in the scan's place), the count -> lims -> scatter -> sort -> finish sequence of
+// query chunking, the scan -> merge tree -> finish launch sequence of k_search.hip, searches by id, the k-NN graph and the search of one
+// index with the rows of another (the gather kernel in front of the same sequence, or the tiled kernel of k_graph.hip in the scan's place),
+// appending one index to another, the count -> lims -> scatter -> sort -> finish sequence of
 // range search and pairs (k_join.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
 // Replaces the usearch index of the reference's examples/image-search (build.cpp / search.cpp) with an exact search on the GPU.
 #include <algorithm>
@@ -59,6 +60,7 @@ struct clip_amd_index {
     Buf idbuf;                     // ids of a search by id copied from the host
     Buf qself;                     // searches by id: [nq_pad] the stored row each query is, -1 for a flagged one
     int knn_route = 0;             // clip_amd_test_index_knn_route: 0 automatic, 1 scan, 2 tiled
+    int cross_route = 0;           // clip_amd_test_index_cross_route: the same for clip_amd_index_search_index
     // range search / pairs
     Buf jcnt;                      // total (u64) + per-segment counts, reused as the scatter cursors
     Buf hits;                      // hit list
@@ -248,10 +250,12 @@ int64_t rows_per_chunk(int64_t n, int k) {
 }
 
 // Where the queries of a search come from: f32 vectors on the device (normalised / quantised into the query workspace), or stored rows by
-// id (gathered bit for bit): d_ids on the device or, NULL, the rows first, first + 1, ...
+// id (gathered bit for bit): d_ids on the device or, NULL, the rows first, first + 1, ...; rows of `from` (same dim, dtype and stream),
+// NULL: of the searched index itself
 struct QuerySource {
     const float * d_q = nullptr;
     bool by_id = false;
+    const clip_amd_index * from = nullptr;
     const int64_t * d_ids = nullptr;
     int64_t first = 0;
     bool exclude_self = false;
@@ -261,7 +265,8 @@ struct QuerySource {
 bool gather_queries(clip_amd_index * ix, const QuerySource & src, int q0, int64_t n_src, int64_t n_rows) {
     if (!ensure(ix, ix->qbuf, (size_t)n_rows * row_stride(ix)) || !ensure(ix, ix->qself, (size_t)n_rows * sizeof(int))) return false;
     if (ix->dtype == SEARCH_I8 && !ensure(ix, ix->qinv, (size_t)n_rows * sizeof(float))) return false;
-    launch_search_gather(ix->store.rows, ix->store.rinv, ix->store.live, ix->n, src.d_ids ? src.d_ids + q0 : nullptr, src.first + q0, (int)n_src, n_rows,
+    const clip_amd_index * from = src.from ? src.from : ix;      // the id test uses this store's size and live bitmap
+    launch_search_gather(from->store.rows, from->store.rinv, from->store.live, from->n, src.d_ids ? src.d_ids + q0 : nullptr, src.first + q0, (int)n_src, n_rows,
                          (int64_t)row_stride(ix), ix->qbuf.p, ix->dtype == SEARCH_I8 ? (float *)ix->qinv.p : nullptr, (int *)ix->qself.p, stream_of(ix));
     return true;
 }
@@ -326,9 +331,10 @@ QuerySource vectors(const float * d_q) {
     return s;
 }
 
-QuerySource stored_rows(const int64_t * d_ids, int64_t first, bool exclude_self) {
+QuerySource stored_rows(const int64_t * d_ids, int64_t first, bool exclude_self, const clip_amd_index * from = nullptr) {
     QuerySource s;
     s.by_id = true;
+    s.from = from;
     s.d_ids = d_ids;
     s.first = first;
     s.exclude_self = exclude_self;
@@ -341,6 +347,22 @@ QuerySource stored_rows(const int64_t * d_ids, int64_t first, bool exclude_self)
 // MI355X, below that it leaves CUs idle while the scan's 64-row steps still fill them.
 constexpr int64_t KNN_TILED_MIN_ROWS = 4096;
 
+// The grid of the tiled kernel for `block` queries (a multiple of 128) per launch over n candidate rows: a query tile's rows are split
+// across workgroups until the device is full (a chunk at least 4 k rows and 256, in whole tiles of 128, as in the scan), within the candidate budget.
+void tiled_chunks(int64_t n, int64_t block, int k, int64_t & rpc, int & n_chunks) {
+    int dev = 0, cus = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
+    (void)hipGetLastError();
+    const int C = search_candidate_capacity(k);
+    const int64_t q_tiles = (block + 127) / 128;
+    const int64_t min_rpc = (std::max<int64_t>(256, 4 * (int64_t)k) + 127) / 128 * 128;
+    const int64_t want = std::max<int64_t>(1, std::min<int64_t>({(cus + q_tiles - 1) / q_tiles, (n + min_rpc - 1) / min_rpc,
+                                                                  (int64_t)(CAND_BUDGET / ((size_t)block * C * 8))}));
+    rpc = ((n + want - 1) / want + 127) / 128 * 128;
+    n_chunks = (int)((n + rpc - 1) / rpc);
+}
+
 // The k-NN graph on the host: query blocks of a fixed size, one after another, each scored (scan route: the self-excluding scan over the
 // gathered rows; tiled route: graph_kernel straight from the store), merged, finished into the block's result workspace and copied out.
 bool knn_graph_impl(clip_amd_index * ix, int k, float * distances, int64_t * ids, const char * fn) {
@@ -352,21 +374,9 @@ bool knn_graph_impl(clip_amd_index * ix, int k, float * distances, int64_t * ids
     const int C = search_candidate_capacity(k);
     int64_t block = std::min<int64_t>({(n + 127) / 128 * 128, GRAPH_BLOCK_MAX, (int64_t)(GRAPH_OUT_BUDGET / ((size_t)k * 12)) / 128 * 128,
                                        (int64_t)(CAND_BUDGET / ((size_t)C * 8)) / 128 * 128});
-    // tiled route: a query tile's rows are split across workgroups until the device is full (a chunk at least 4 k rows, as in the scan)
     int n_chunks = 1;
     int64_t rpc = (n + 127) / 128 * 128;
-    if (tiled) {
-        int dev = 0, cus = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
-        (void)hipGetLastError();
-        const int64_t q_tiles = (std::min(block, n) + 127) / 128;
-        const int64_t min_rpc = (std::max<int64_t>(256, 4 * (int64_t)k) + 127) / 128 * 128;
-        int64_t want = std::max<int64_t>(1, std::min<int64_t>({(cus + q_tiles - 1) / q_tiles, (n + min_rpc - 1) / min_rpc,
-                                                                (int64_t)(CAND_BUDGET / ((size_t)block * C * 8))}));
-        rpc = ((n + want - 1) / want + 127) / 128 * 128;
-        n_chunks = (int)((n + rpc - 1) / rpc);
-    }
+    if (tiled) tiled_chunks(n, block, k, rpc, n_chunks);
     if (!ensure(ix, ix->outs, (size_t)block * k * 12)) return false;
     int64_t * d_ids = (int64_t *)ix->outs.p;
     float * d_dist = (float *)((char *)ix->outs.p + (size_t)block * k * 8);
@@ -384,6 +394,75 @@ bool knn_graph_impl(clip_amd_index * ix, int k, float * distances, int64_t * ids
             if (hipGetLastError() != hipSuccess) { fprintf(stderr, "%s: launch failed\n", fn); return false; }
         }
         if (!copy_results(ix, d_dist, d_ids, (size_t)m * k, distances + (size_t)q0 * k, ids + (size_t)q0 * k, fn)) return false;
+    }
+    return true;
+}
+
+// Queries from which the automatic route of clip_amd_index_search_index takes the tiled kernel (ids == NULL only); below, the scan route.
+// Measured (profiles/cross_bench.txt, "crossover"; MI355X, dim 512): the smallest swept query count from which on the tiled route's median
+// wall time is below the scan route's on every dtype is 2048 over an index of 256 and of 1024 rows (a call of the tiled route costs about
+// 1.2 ms however few the queries, the scan route 0.65 ms per pass of 1024 queries) and 128, the smallest count swept, over 10^6 rows; the
+// constant is the largest of the three, so the automatic route never takes the slower kernel of a label-sized index.
+constexpr int64_t CROSS_TILED_MIN_QUERIES = 2048;
+
+// clip_amd_index_search_index on the host: the nq queries are the rows ids[0 ... nq) of src (host ids) or, ids NULL, its rows 0 ... nq - 1.
+// Query blocks as in knn_graph_impl, one after another: scored (scan route: the scan over rows gathered from src's store; tiled route:
+// the CROSS graph_kernel straight from both stores), merged, finished into the block's result workspace and copied out.
+bool search_index_impl(clip_amd_index * ix, const clip_amd_index * src, const int64_t * ids, int64_t nq, int k, const uint64_t * allow,
+                       float * distances, int64_t * out_ids, const char * fn) {
+    hipStream_t st = stream_of(ix);
+    if (nq == 0) return true;
+    const bool tiled = !ids && ix->n > 0 && (ix->cross_route ? ix->cross_route == 2 : nq >= CROSS_TILED_MIN_QUERIES);
+    const int C = search_candidate_capacity(k);
+    const int64_t block = std::min<int64_t>({(nq + 127) / 128 * 128, GRAPH_BLOCK_MAX, (int64_t)(GRAPH_OUT_BUDGET / ((size_t)k * 12)) / 128 * 128,
+                                             (int64_t)(CAND_BUDGET / ((size_t)C * 8)) / 128 * 128});
+    const uint32_t * d_allow = nullptr;
+    if (allow && ix->n > 0) {
+        const size_t ab = (size_t)search_allow_words(ix->n) * 4;
+        if (!ensure(ix, ix->abuf, ab)) return false;
+        (void)hipMemcpyAsync(ix->abuf.p, allow, ab, hipMemcpyHostToDevice, st);
+        d_allow = (const uint32_t *)ix->abuf.p;
+    }
+    const uint32_t * mask = nullptr;
+    int n_chunks = 1;
+    int64_t rpc = 128;
+    if (tiled) {
+        if (!effective_mask(ix, d_allow, mask)) return false;
+        tiled_chunks(ix->n, block, k, rpc, n_chunks);
+    }
+    if (!ensure(ix, ix->outs, (size_t)block * k * 12) || (ids && !ensure(ix, ix->idbuf, (size_t)block * 8))) return false;
+    int64_t * d_out = (int64_t *)ix->outs.p;
+    float * d_dist = (float *)((char *)ix->outs.p + (size_t)block * k * 8);
+    for (int64_t q0 = 0; q0 < nq; q0 += block) {
+        const int m = (int)std::min(block, nq - q0);
+        if (!tiled) {
+            if (ids) (void)hipMemcpyAsync(ix->idbuf.p, ids + q0, (size_t)m * 8, hipMemcpyHostToDevice, st);
+            const QuerySource qs = stored_rows(ids ? (const int64_t *)ix->idbuf.p : nullptr, ids ? 0 : q0, false, src);
+            if (!search_device_impl(ix, qs, m, k, d_allow, d_dist, d_out)) return false;
+        } else {
+            if (!ensure(ix, ix->cand, (size_t)n_chunks * m * C * 8)) return false;
+            if (!launch_graph_cross(ix->store.rows, ix->store.rinv, ix->n, src->store.rows, src->store.rinv, src->n, q0, m, ix->Dpad, ix->dtype, k,
+                                    ix->cand.p, n_chunks, rpc, mask, st)) {
+                fprintf(stderr, "%s: graph launch failed\n", fn);
+                return false;
+            }
+            if (!merge_and_finish(ix, n_chunks, m, k, nullptr, d_dist, d_out)) return false;
+            if (hipGetLastError() != hipSuccess) { fprintf(stderr, "%s: launch failed\n", fn); return false; }
+        }
+        if (!copy_results(ix, d_dist, d_out, (size_t)m * k, distances + (size_t)q0 * k, out_ids + (size_t)q0 * k, fn)) return false;
+    }
+    return true;
+}
+
+// what clip_amd_index_search_index and clip_amd_index_append ask of their two indexes
+bool check_pair(const clip_amd_index * ix, const clip_amd_index * src, const char * fn) {
+    if (!ix || !src) { fprintf(stderr, "%s: %s is NULL\n", fn, ix ? "src" : "index"); return false; }
+    if (ix->ctx != src->ctx) { fprintf(stderr, "%s: the two indexes belong to different contexts (%p and %p)\n", fn, (void *)ix->ctx, (void *)src->ctx); return false; }
+    if (ix->dim != src->dim) { fprintf(stderr, "%s: src holds %d-dimensional rows, the index %d-dimensional ones\n", fn, src->dim, ix->dim); return false; }
+    if (ix->dtype != src->dtype) { fprintf(stderr, "%s: src has dtype %d, the index dtype %d\n", fn, src->dtype, ix->dtype); return false; }
+    if (src->removed > 0) {
+        fprintf(stderr, "%s: src holds %lld removed rows: call clip_amd_index_compact on it first\n", fn, (long long)src->removed);
+        return false;
     }
     return true;
 }
@@ -907,6 +986,86 @@ bool clip_amd_index_knn_graph(struct clip_amd_index * ix, int k, float * distanc
         if (ix->n > 0 && (!distances || !ids)) { fprintf(stderr, "%s: NULL result pointer\n", fn); return false; }
         (void)hipSetDevice(ix->device);
         return knn_graph_impl(ix, k, distances, ids, fn);
+    });
+}
+
+bool clip_amd_index_search_index(struct clip_amd_index * ix, struct clip_amd_index * src, const int64_t * ids, int64_t n_ids, int k,
+                                 const uint64_t * allow, float * distances, int64_t * out_ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_pair(ix, src, fn)) return false;
+        if (k < 1 || k > MAX_K) { fprintf(stderr, "%s: k = %d outside 1 ... %d\n", fn, k, MAX_K); return false; }
+        if (ids && n_ids < 0) { fprintf(stderr, "%s: n_ids %lld < 0\n", fn, (long long)n_ids); return false; }
+        const int64_t nq = ids ? n_ids : src->n;
+        if (nq > 0 && (!distances || !out_ids)) { fprintf(stderr, "%s: NULL result pointer\n", fn); return false; }
+        for (int64_t t = 0; ids && t < nq; t++)
+            if (ids[t] < 0 || ids[t] >= src->n) {
+                fprintf(stderr, "%s: id %lld (entry %lld) outside 0 ... %lld of src: nothing searched\n", fn, (long long)ids[t], (long long)t,
+                        (long long)src->n - 1);
+                return false;
+            }
+        (void)hipSetDevice(ix->device);
+        return search_index_impl(ix, src, ids, nq, k, allow, distances, out_ids, fn);
+    });
+}
+
+int64_t clip_amd_index_append(struct clip_amd_index * ix, struct clip_amd_index * src, int64_t * new_ids) {
+    return guarded(__func__, (int64_t)-1, [&](const char * fn) -> int64_t {
+        if (!check_pair(ix, src, fn)) return -1;
+        if (ix == src) { fprintf(stderr, "%s: an index cannot be appended to itself\n", fn); return -1; }
+        const int64_t m = src->n, n = ix->n;
+        if (m > MAX_ROWS - n) { fprintf(stderr, "%s: %lld rows would take the index past %lld rows\n", fn, (long long)m, (long long)MAX_ROWS); return -1; }
+        if (m > 0) {
+            (void)hipSetDevice(ix->device);
+            hipStream_t st = stream_of(ix);
+            if (!reserve_rows(ix, n + m)) return -1;
+            const RowStore & d = ix->store;
+            (void)hipMemcpyAsync((char *)d.rows + (size_t)n * row_stride(ix), src->store.rows, (size_t)m * row_stride(ix), hipMemcpyDeviceToDevice, st);
+            if (d.rinv) (void)hipMemcpyAsync(d.rinv + n, src->store.rinv, (size_t)m * sizeof(float), hipMemcpyDeviceToDevice, st);
+            if (!stream_done(ix, fn, hipGetLastError())) return -1;      // no bit set, no row counted: the index is as it was
+            launch_live_set(d.live, n, n + m, st);
+            if (!stream_done(ix, fn, hipGetLastError())) return -1;
+            ix->n = n + m;
+        }
+        for (int64_t i = 0; new_ids && i < m; i++) new_ids[i] = n + i;
+        return m;
+    });
+}
+
+int clip_amd_test_index_cross_route(struct clip_amd_index * ix, int route) {
+    if (!ix || route < 0 || route > 2) return -1;
+    ix->cross_route = route;
+    return route;
+}
+
+float clip_amd_bench_cross(int dtype, int64_t n_rows, int64_t n_queries, int dim, int k, int route, int iters) {
+    return guarded(__func__, -4.f, [&](const char * fn) {
+        const bool args_ok = k >= 1 && k <= MAX_K && route >= 0 && route <= 2 && n_queries >= 1 && n_queries <= MAX_ROWS;
+        return bench_on_gallery(dtype, n_rows, dim, 0, iters, args_ok, false, [&](clip_amd_index * ix, float * scratch) {
+            // the second index: n_queries rows from seeds of their own, filled in the pieces the gallery was filled in
+            clip_amd_index * src = make_index(nullptr, ix->device, dim, dtype);
+            bool ok = reserve_rows(src, n_queries);
+            for (int64_t r0 = 0; ok && r0 < n_queries; r0 += HOST_CHUNK_ROWS) {
+                const int64_t m = std::min(HOST_CHUNK_ROWS, n_queries - r0);
+                launch_search_fill_random(scratch, m * dim, 0xC0FFEEull + (uint64_t)r0 * dim, nullptr);
+                ok = add_device_impl(src, scratch, m);
+            }
+            float us = -4.f;
+            if (ok) {
+                std::vector<float> dist((size_t)n_queries * k);
+                std::vector<int64_t> out((size_t)n_queries * k);
+                ix->cross_route = route;
+                ok = hipDeviceSynchronize() == hipSuccess && search_index_impl(ix, src, nullptr, n_queries, k, nullptr, dist.data(), out.data(), fn);   // a warm call
+                if (ok) {
+                    const auto t0 = std::chrono::steady_clock::now();
+                    for (int i = 0; ok && i < iters; i++) ok = search_index_impl(ix, src, nullptr, n_queries, k, nullptr, dist.data(), out.data(), fn);
+                    const auto t1 = std::chrono::steady_clock::now();
+                    if (ok) us = (float)(std::chrono::duration<double, std::micro>(t1 - t0).count() / iters);
+                }
+            }
+            (void)hipDeviceSynchronize();
+            free_index(src);
+            return us;
+        });
     });
 }
 

@@ -7,6 +7,8 @@ build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.In
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-n N] [--in PREFIX]... [--db DIR] --like INDEXED/IMAGE/PATH
     python -m clip_cpp_amd.image_search dedup  [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R]
     python -m clip_cpp_amd.image_search neighbors [-m MODEL] [-v N] [--db DIR] [-n N]
+    python -m clip_cpp_amd.image_search label  [-m MODEL] [-v N] [-t N] [--db DIR] [-n N] LABEL [LABEL ...]
+    python -m clip_cpp_amd.image_search merge  [-m MODEL] [-v N] --db DIR --from DIR2 [--from DIR3 ...] [-d R]
 
 `build` writes DIR/images.index (the CLIPIDX1 file of clip_amd_index_save) and DIR/images.paths (the reference's layout: the model path
 on the first line, then one image path per id).  `search` prints the reference's output: "search results:" / "distance path" at
@@ -24,6 +26,14 @@ groups separated by a blank line, and "main: %d groups, %d images".
 listed.  It composes with -n and --in, not with a positional query or -d.  `neighbors` prints the k-NN graph (Index.knn_graph, one call):
 "neighbours:" at verbosity > 0, then per image, in id order, its path on a line of its own and "  %f %s" per neighbour, the -n (default 5)
 nearest other images, nearest first; images separated by a blank line, and "main: %d images, %d neighbours each".
+`label` labels the whole database (the reference's zsl example applied to a collection): the labels are encoded as written, in one batch,
+into a temporary index of the database's dim and dtype, which is searched once with every stored row of the database
+(Index.search_index: no image is decoded or encoded again); "labels:" at verbosity > 0, then per image, in id order, its path on a line of
+its own and "  %f %s" (distance, label) for its -n (default 1) nearest labels, nearest first; images separated by a blank line, and
+"main: %d images, %d labels each".  `merge` appends the databases given with --from to the one at --db without encoding anything
+(Index.append): an image whose path the target already holds is skipped and, with -d R, so is one whose nearest target image is within
+R (one Index.search_index per source; listed as "  %f %s ~ %s" at verbosity > 0); it prints "main: %d added, %d already present, %d near
+duplicates skipped".  A source built with another model (unless -m is given), dim or dtype is refused before any model is loaded.
 """
 import ctypes as C
 import os
@@ -60,24 +70,29 @@ def _err(msg):
     print(msg, file=sys.stderr, flush=True)
 
 
-def _parse(argv, build, dedup=False, update=False, neighbors=False):
-    """Reference-style option parsing (examples/image-search/{build,search}.cpp my_app_params_parse); `dedup` and `neighbors` take no
-    positional arguments; `update` takes build's directories, but neither a default model nor --dtype (both come from the database)."""
-    p = dict(threads=4, verbose=1, db=".", dtype="f16", results=5, max_distance=DEDUP_RADIUS if dedup else None,
+def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False, merge=False):
+    """Reference-style option parsing (examples/image-search/{build,search}.cpp my_app_params_parse); `dedup`, `neighbors` and `merge` take
+    no positional arguments; `update` takes build's directories, but neither a default model nor --dtype (both come from the database);
+    `label` takes the labels; `merge` needs --from at least once."""
+    p = dict(threads=4, verbose=1, db=".", dtype="f16", results=1 if label else 5, max_distance=DEDUP_RADIUS if dedup else None,
              model="../models/ggml-model-f16.bin" if build else "", rest=[], like=None)
     p["in"] = []
-    search = not (build or dedup or update or neighbors)
+    if merge:
+        p["from"] = []
+    search = not (build or dedup or update or neighbors or label or merge)
     seen = set()
     i = 0
     while i < len(argv):
         a = argv[i]
         takes = {"-m": "model", "--model": "model", "-v": "verbose", "--verbose": "verbose", "--db": "db"}
-        if not (dedup or neighbors):
+        if not (dedup or neighbors or merge):
             takes.update({"-t": "threads", "--threads": "threads"})
         if build:
             takes["--dtype"] = "dtype"
-        elif neighbors:
+        elif neighbors or label:
             takes.update({"-n": "results", "--results": "results"})
+        elif merge:
+            takes.update({"-d": "max_distance", "--max-distance": "max_distance", "--from": "from"})
         elif not update:
             takes.update({"-d": "max_distance", "--max-distance": "max_distance"})
             if not dedup:
@@ -93,8 +108,8 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False):
                 print("main: --like takes one indexed image: it cannot be given twice")
                 return None
             seen.add(key)
-            if key == "in":
-                p["in"].append(argv[i])
+            if key in ("in", "from"):
+                p[key].append(argv[i])
                 i += 1
                 continue
             try:
@@ -104,15 +119,15 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False):
             if key == "max_distance" and p[key] != p[key]:      # NaN
                 return None
         elif a in ("-h", "--help"):
-            _help(build, p, dedup, update, neighbors)
+            _help(build, p, dedup, update, neighbors, label, merge)
             sys.exit(0)
         elif a.startswith("-"):
             print("main: unrecognized argument: %s" % a)
             return None
-        elif dedup or neighbors:
+        elif dedup or neighbors or merge:
             print("main: unexpected argument: %s" % a)
             return None
-        elif build or update:
+        elif build or update or label:
             p["rest"].append(a)
         else:
             p["rest"] = argv[i:]     # the query: everything from here on
@@ -122,7 +137,9 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False):
         if p["rest"] or "max_distance" in seen:
             print("main: --like cannot be combined with a query or with -d: it lists the -n nearest images of an indexed one")
             return None
-    elif (not p["rest"] and not (dedup or neighbors)) or (build and p["dtype"] not in ("f16", "f32", "i8")):
+    elif (not p["rest"] and not (dedup or neighbors or merge)) or (build and p["dtype"] not in ("f16", "f32", "i8")):
+        return None
+    if merge and not p["from"]:
         return None
     if {"results", "max_distance"} <= seen:
         print("main: -n and -d cannot be combined: -n N prints the N nearest, -d R every image within R")
@@ -130,10 +147,35 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False):
     return p
 
 
-def _help(build, p, dedup=False, update=False, neighbors=False):
+def _help(build, p, dedup=False, update=False, neighbors=False, label=False, merge=False):
     radius = ("  -d R, --max-distance R: %s within cosine distance R (<= R). Default: %s. %g is a starting point for embeddings of near-identical"
               " images, not a tuned value: check a few groups of your collection and adjust R")
-    if neighbors:
+    if label:
+        print("Usage: python -m clip_cpp_amd.image_search label [options] LABEL [LABEL ...]")
+        print("\nPrints, for every image of an index built by `build`, the labels that fit it best. The labels are encoded as written (no prompt")
+        print("template); no image is decoded or encoded again.")
+        print("\nOptions:")
+        print("  -h, --help: Show this message and exit")
+        print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default. The model needs a text encoder.")
+        print("  -t N, --threads N: Number of threads to use for inference. Default: %d" % p["threads"])
+        print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
+        print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
+        print("  -n N, --results N: Number of labels per image, nearest first (at most %d). Default: %d" % (MAX_K, p["results"]))
+    elif merge:
+        print("Usage: python -m clip_cpp_amd.image_search merge [options] --db <dir> --from <dir2> [--from <dir3> ...]")
+        print("\nAppends the databases given with --from to the one at --db without encoding anything twice. Images whose path the target")
+        print("already holds are skipped. Every database must have been built with the same model, dim and dtype.")
+        print("\nOptions:")
+        print("  -h, --help: Show this message and exit")
+        print("  -m <path>, --model <path>: overwrite path to model (loaded only to place the indexes on its device); the model lines of the"
+              " databases are then not compared, and the given path is the one stored in the merged %s." % PATHS_FILE)
+        print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
+        print("  --db <dir>: the target: directory holding %s and %s; both are written under temporary names and renamed into place."
+              " Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
+        print("  --from <dir>: a source database to append; may be repeated. Sources are not changed")
+        print("  -d R, --max-distance R: also skip a source image whose nearest target image is within cosine distance R (<= R): an import"
+              " without near duplicates. Default: off. %g is a starting point for near-identical images, not a tuned value" % DEDUP_RADIUS)
+    elif neighbors:
         print("Usage: python -m clip_cpp_amd.image_search neighbors [options]")
         print("\nPrints, for every image of an index built by `build`, its nearest other images (the k-NN graph of the index).")
         print("\nOptions:")
@@ -358,10 +400,9 @@ def read_index_header(path):
     return struct.unpack("<IIIQ", h[8:])
 
 
-def _read_db(p):
-    """The image paths of DIR/images.paths after the database checks `search` and `dedup` share (the model path from its first line unless
-    -m gave one); None, with the message printed, when a check fails."""
-    paths_file = os.path.join(p["db"], PATHS_FILE)
+def _read_paths(db):
+    """(model line, image paths) of db/images.paths; ("", []) when the file is missing or empty."""
+    paths_file = os.path.join(db, PATHS_FILE)
     lines = []
     if os.path.exists(paths_file):
         with open(paths_file) as f:
@@ -372,6 +413,13 @@ def _read_db(p):
         if not line:
             break
         image_paths.append(line)
+    return model_line, image_paths
+
+
+def _read_db(p):
+    """The image paths of DIR/images.paths after the database checks `search` and `dedup` share (the model path from its first line unless
+    -m gave one); None, with the message printed, when a check fails."""
+    model_line, image_paths = _read_paths(p["db"])
     if not p["model"]:
         p["model"] = model_line
     else:
@@ -547,13 +595,142 @@ def neighbors(argv):
     return 0
 
 
+DTYPE_NAMES = {0: "f32", 1: "f16", 3: "i8"}       # the dtype codes of a CLIPIDX1 header
+
+
+def label(argv):
+    import clip_cpp_amd
+    p = _parse(argv, build=False, label=True)
+    if p is None:
+        _help(False, dict(threads=4, verbose=1, db=".", results=1), label=True)
+        return 1
+    image_paths = _read_db(p)
+    if image_paths is None:
+        return 1
+    _, dim, dtype, _ = read_index_header(os.path.join(p["db"], INDEX_FILE))
+    try:
+        clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])
+    except RuntimeError:
+        print("main: Unable to load model from %s" % p["model"])
+        return 1
+    if clip.text_config["n_layer"] <= 0:
+        _err("main: the model at %s has no text encoder: text queries need a two-tower model" % p["model"])
+        return 1
+    if dim != clip.text_config["projection_dim"]:
+        _err("main: the index holds %d-dimensional embeddings, the model makes %d" % (dim, clip.text_config["projection_dim"]))
+        return 1
+    names = p["rest"]
+    labels = clip_cpp_amd.Index(clip, dim, dtype=DTYPE_NAMES[dtype])
+    labels.add(clip.encode_texts([clip.tokenize(t) for t in names], normalize=True))      # as written: no prompt template
+    index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
+    k = max(1, min(p["results"], len(names), MAX_K))
+    dist, ids = labels.search_index(index, k)      # every image's stored row against the labels
+    if p["verbose"] > 0:
+        print("labels:")
+    for i, path in enumerate(image_paths):
+        if i:
+            print()
+        print(path)
+        for d, j in zip(dist[i], ids[i]):
+            if j >= 0 and p["results"] > 0:
+                print("  %f %s" % (d, names[j]))
+    print("main: %d images, %d labels each" % (len(image_paths), k if p["results"] > 0 else 0))
+    sys.stdout.flush()
+    index.close()
+    labels.close()
+    clip.close()
+    return 0
+
+
+def merge_refusal(target_model, target_hdr, source_dir, model_given):
+    """Why the database in source_dir cannot be merged into a target with that model line and index header (version, dim, dtype, n), or
+    None; read from the source's two files alone: no model and no device is needed."""
+    model_line, paths = _read_paths(source_dir)
+    hdr = read_index_header(os.path.join(source_dir, INDEX_FILE))
+    if not model_line or hdr is None:
+        return "no database in '%s' (%s or %s is missing or not a database file)" % (source_dir, PATHS_FILE, INDEX_FILE)
+    if hdr[3] != len(paths):
+        return "'%s': index files size missmatch" % source_dir
+    if not model_given and model_line != target_model:
+        return ("'%s' was built with the model %s, the target with %s: embeddings of two models cannot be compared (-m MODEL overrides "
+                "this check when both paths name the same model)" % (source_dir, model_line, target_model))
+    if hdr[1] != target_hdr[1]:
+        return "'%s' holds %d-dimensional embeddings, the target %d-dimensional ones" % (source_dir, hdr[1], target_hdr[1])
+    if hdr[2] != target_hdr[2]:
+        return ("'%s' is stored as %s, the target as %s: build both with the same --dtype"
+                % (source_dir, DTYPE_NAMES.get(hdr[2], hdr[2]), DTYPE_NAMES.get(target_hdr[2], target_hdr[2])))
+    return None
+
+
+def merge(argv):
+    import clip_cpp_amd
+    p = _parse(argv, build=False, merge=True)
+    if p is None:
+        _help(False, dict(verbose=1, db="."), merge=True)
+        return 1
+    model_given = bool(p["model"])
+    paths = _read_db(p)
+    if paths is None:
+        return 1
+    target_model = _read_paths(p["db"])[0]
+    target_hdr = read_index_header(os.path.join(p["db"], INDEX_FILE))
+    for source_dir in p["from"]:
+        why = merge_refusal(target_model, target_hdr, source_dir, model_given)
+        if why:
+            _err("main: " + why)
+            return 1
+    try:
+        clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])      # only the indexes' device: no image is encoded
+    except RuntimeError:
+        print("main: Unable to load model from %s" % p["model"])
+        return 1
+    target = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
+    known = set(paths)
+    added = present = near = 0
+    for source_dir in p["from"]:
+        source_paths = _read_paths(source_dir)[1]
+        source = clip_cpp_amd.Index.load(clip, os.path.join(source_dir, INDEX_FILE))
+        nearest = None
+        if p["max_distance"] is not None and len(target) and len(source):
+            nearest = target.search_index(source, 1)      # before anything of this source is appended
+        drop, keep = [], []
+        for i, path in enumerate(source_paths):
+            if path in known:
+                present += 1
+                drop.append(i)
+            elif nearest is not None and nearest[1][i, 0] >= 0 and nearest[0][i, 0] <= np.float32(p["max_distance"]):
+                near += 1
+                drop.append(i)
+                if p["verbose"] > 0:
+                    print("  %f %s ~ %s" % (nearest[0][i, 0], path, paths[nearest[1][i, 0]]))
+            else:
+                known.add(path)
+                keep.append(path)
+        if drop:
+            source.remove(drop)
+            source.compact()
+        if keep:
+            target.append(source)
+            paths.extend(keep)
+            added += len(keep)
+        source.close()
+    if added:
+        _write_db(p, target, paths)
+    target.close()
+    clip.close()
+    print("main: %d added, %d already present, %d near duplicates skipped" % (added, present, near), flush=True)
+    return 0
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
-    commands = {"build": build, "update": update, "search": search, "dedup": dedup, "neighbors": neighbors}
+    commands = {"build": build, "update": update, "search": search, "dedup": dedup, "neighbors": neighbors, "label": label, "merge": merge}
     if not argv or argv[0] not in commands:
         print("Usage: python -m clip_cpp_amd.image_search {build|search|dedup} [options] ...  (-h after the command for its options)")
         print("       python -m clip_cpp_amd.image_search update [options] dir [more dirs]  (an existing database brought in line with the disk)")
         print("       python -m clip_cpp_amd.image_search neighbors [options]  (every indexed image's nearest other images; search --like PATH for one)")
+        print("       python -m clip_cpp_amd.image_search label [options] LABEL [LABEL ...]  (every indexed image's best-fitting labels)")
+        print("       python -m clip_cpp_amd.image_search merge [options] --db DIR --from DIR2 [--from DIR3 ...]  (append databases, nothing encoded twice)")
         return 1
     return commands[argv[0]](argv[1:])
 

@@ -236,6 +236,34 @@ int clip_amd_test_index_knn_route(struct clip_amd_index * ix, int route);
 /* Average wall time (microseconds) of one clip_amd_index_knn_graph over n seeded random rows on the current device (results copied to the
  * host included), route as above; < 0 on error.  Used by scripts/knn_bench.py. */
 float clip_amd_bench_knn(int dtype, int64_t n, int dim, int k, int route, int iters);
+/* One index searched with the rows of another, and one index appended to another: label every image of a database with a small index of
+ * captions, find which images of B a database A already holds (k = 1), merge two databases without encoding anything twice.
+ * search_index: the queries are stored rows of src: ids[0 ... n_ids) (host), or with ids == NULL every row 0 ... size(src) - 1 (n_ids is
+ * then ignored); the candidates are the rows of ix that are live and set in allow (layout as live_mask, (size(ix) + 63) / 64 host words;
+ * NULL = every live row).  distances / out_ids are host [n][k], laid out as search lays them out.  Result row t is, bit for bit, what
+ * clip_amd_index_search_subset(ix, v, 1, k, allow, ...) returns for the vector v that was added to src as row ids[t]: the stored row is
+ * the prepared query (i8: inv_q := its inv_r) and is copied, never renormalised or requantised.  ix == src is allowed and equals
+ * search_ids(..., exclude_self = 0, allow).  Requirements, checked before anything is launched: both indexes non-NULL, of the same ctx,
+ * dim and dtype; src holds no removed rows (compact it first: a query-side mask stays out of the kernel, and databases on disk never
+ * hold removed rows); every id in [0, size(src)); 1 <= k <= 1024; result pointers non-NULL when there is a query.  A failed check returns
+ * false with a message on stderr that names the offending value and leaves the outputs untouched.  No queries: succeeds, launches
+ * nothing; size(ix) == 0: every row all -1 / +INFINITY.  With ids, and for few queries, the rows are gathered from src's store and
+ * scanned like any query; with ids == NULL and many queries the tiled kernel of k_graph.hip reads both stores directly; both give the same
+ * bits.  Synchronous on the ctx stream; device memory beyond the two indexes is the fixed workspace of knn_graph (query blocks are
+ * processed and copied out one after another).
+ * append: copies every row of src, in order and bit for bit (stored values, i8 inverse norms), to the end of ix, where they are live rows
+ * with the next ids; new_ids (host, size(src) entries, may be NULL) receives each src id's id in ix.  Returns the number of rows appended
+ * (0 for an empty src), or -1 with nothing changed: the requirements above, ix != src and size(ix) + size(src) <= 2^31 - 1.  Afterwards ix
+ * searches and saves exactly like an index to which src's vectors had been added with clip_amd_index_add; src is unchanged. */
+bool clip_amd_index_search_index(struct clip_amd_index * ix, struct clip_amd_index * src, const int64_t * ids, int64_t n_ids, int k,
+                                 const uint64_t * allow, float * distances, int64_t * out_ids);             /* host pointers, synchronous */
+int64_t clip_amd_index_append(struct clip_amd_index * ix, struct clip_amd_index * src, int64_t * new_ids);
+/* test hook: the route of clip_amd_index_search_index with ids == NULL on this index (as ix) from now on: 0 automatic, 1 the scan route,
+ * 2 the tiled kernel.  Returns the route set, -1 for a NULL index or another value. */
+int clip_amd_test_index_cross_route(struct clip_amd_index * ix, int route);
+/* Average wall time (microseconds) of one clip_amd_index_search_index of an index of n_rows seeded random rows with all n_queries seeded
+ * random rows of a second one (results copied to the host included), route as above; < 0 on error.  Used by scripts/cross_bench.py. */
+float clip_amd_bench_cross(int dtype, int64_t n_rows, int64_t n_queries, int dim, int k, int route, int iters);
 /* Range search and near-duplicate pairs.
  * Distance: exactly what clip_amd_index_search reports for the same (query, row) pair (the same stored values, the same MFMA chain per
  * dtype, the same f32 expression); a row is a result when d <= radius, compared in f32.
