@@ -77,6 +77,8 @@ AMD_SYMBOLS = [
     "clip_amd_index_search_subset_device", "clip_amd_index_range_search_subset", "clip_amd_bench_search_subset",
     "clip_amd_index_search_ids", "clip_amd_index_search_ids_device", "clip_amd_index_knn_graph", "clip_amd_test_index_knn_route", "clip_amd_bench_knn",
     "clip_amd_index_search_index", "clip_amd_index_append", "clip_amd_test_index_cross_route", "clip_amd_bench_cross",
+    "clip_amd_image_batch_encode_files", "clip_amd_image_batch_encode_memory", "clip_amd_test_jpeg_plan", "clip_amd_test_jpeg_decode_device",
+    "clip_amd_bench_jpeg_kernels", "clip_amd_test_jpeg_device_count",
 ]
 
 _lib = None
@@ -272,6 +274,19 @@ def lib():
     L.clip_amd_test_index_cross_route.argtypes = [vp, i32]
     L.clip_amd_bench_cross.restype = C.c_float
     L.clip_amd_bench_cross.argtypes = [i32, i64, i64, i32, i32, i32, i32]
+    u8p, szp = C.POINTER(C.c_uint8), C.POINTER(C.c_size_t)
+    L.clip_amd_image_batch_encode_files.restype = i32
+    L.clip_amd_image_batch_encode_files.argtypes = [vp, C.POINTER(C.c_char_p), i32, i32, i32, C.c_bool, f32p, C.POINTER(i32), u8p]
+    L.clip_amd_image_batch_encode_memory.restype = i32
+    L.clip_amd_image_batch_encode_memory.argtypes = [vp, C.POINTER(C.c_char_p), szp, i32, i32, i32, C.c_bool, f32p, C.POINTER(i32), u8p]
+    L.clip_amd_test_jpeg_plan.restype = i32
+    L.clip_amd_test_jpeg_plan.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(i32)]
+    L.clip_amd_test_jpeg_decode_device.restype = i32
+    L.clip_amd_test_jpeg_decode_device.argtypes = [C.c_char_p, C.c_size_t, u8p, C.c_size_t, C.POINTER(i32), C.POINTER(i32)]
+    L.clip_amd_test_jpeg_device_count.restype = C.c_longlong
+    L.clip_amd_test_jpeg_device_count.argtypes = []
+    L.clip_amd_bench_jpeg_kernels.restype = i32
+    L.clip_amd_bench_jpeg_kernels.argtypes = [C.c_char_p, C.c_size_t, i32, i32, f32p, C.POINTER(C.c_double)]
     _lib = L
     return L
 
@@ -425,6 +440,51 @@ class Clip:
         if not lib().clip_amd_image_batch_encode_u8(self.ctx, arr, n, _fp(out), normalize):
             raise RuntimeError("clip_amd_image_batch_encode_u8 failed (see stderr)")
         return out
+
+    class ImageFileList:
+        """Paths prepared once for repeated Clip.encode_image_files(..., start=pos) calls over one long list: the encoded names and the
+        C arrays are built here, each call then costs what its window costs."""
+
+        def __init__(self, paths):
+            self.paths = list(paths)
+            self.n = len(self.paths)
+            self.arr = (C.c_char_p * max(self.n, 1))(*[os.fsencode(p) for p in self.paths])
+            self.ok = np.zeros(max(self.n, 1), dtype=np.uint8)
+
+        def __len__(self):
+            return self.n
+
+    def _encode_encoded(self, call, arr, sizes, ok, n, normalize, n_threads, max_images):
+        cap = n if max_images is None else max(0, min(int(max_images), n))
+        out = np.empty((cap, self.vision_config["projection_dim"]), dtype=np.float32)
+        consumed = C.c_int(0)
+        if n == 0 or cap == 0:
+            return out[:0], ok[:0].astype(bool), 0
+        args = (arr,) if sizes is None else (arr, sizes)
+        rows = call(self.ctx, *args, n, cap, int(n_threads), normalize, _fp(out), C.byref(consumed), ok.ctypes.data_as(C.POINTER(C.c_uint8)))
+        if rows < 0:
+            raise RuntimeError("%s failed (see stderr)" % call.__name__)
+        return out[:rows], ok[:consumed.value].astype(bool), consumed.value
+
+    def encode_image_files(self, paths, normalize=True, n_threads=4, max_images=None, start=0):
+        """Image files -> (embeddings float32 [rows, proj], ok bool [consumed], consumed): the files are read and decoded on n_threads host
+        threads, in every format clip_image_load_from_file reads, and the loadable ones encoded as ONE batch, bit-identical to
+        clip_image_load_from_file + encode_images_u8.  Only a JPEG's entropy decoding stays on those threads: its IDCT / up-sampling / colour
+        conversion run on the GPU (CLIP_AMD_JPEG_DEVICE=0 in the environment: on the host threads as well; same rows).  max_images: stop after that many loadable files; `consumed` paths were looked at, ok[i] says whether path i
+        produced a row (clip_amd_image_batch_encode_files).  paths: a list, or a Clip.ImageFileList with `start` = the first path to
+        look at, for walking a long list in windows without preparing the rest of it again for every call."""
+        fl = paths if isinstance(paths, Clip.ImageFileList) else Clip.ImageFileList(paths)
+        start = max(0, min(int(start), fl.n))
+        arr = C.cast(C.byref(fl.arr, start * C.sizeof(C.c_char_p)), C.POINTER(C.c_char_p))
+        return self._encode_encoded(lib().clip_amd_image_batch_encode_files, arr, None, fl.ok[start:], fl.n - start, normalize, n_threads, max_images)
+
+    def encode_image_bytes(self, blobs, normalize=True, n_threads=4, max_images=None):
+        """The same for encoded images held in memory (a list of bytes objects): clip_amd_image_batch_encode_memory."""
+        blobs = [bytes(b) for b in blobs]
+        n = len(blobs)
+        arr = (C.c_char_p * max(n, 1))(*blobs)
+        sizes = (C.c_size_t * max(n, 1))(*[len(b) for b in blobs])
+        return self._encode_encoded(lib().clip_amd_image_batch_encode_memory, arr, sizes, np.zeros(max(n, 1), dtype=np.uint8)[:n], n, normalize, n_threads, max_images)
 
     def zero_shot_label_images(self, images, labels):
         """Batched clip_zero_shot_label_image on the GPU: list of uint8 [ny,nx,3] images x list of label strings ->

@@ -223,11 +223,15 @@ bool clip_amd_image_batch_preprocess_device(struct clip_ctx * ctx, const struct 
     return preprocess_batch_device(ctx, imgs, n, d_out);
 }
 
+}  // extern "C"
+
 // raw u8 images -> embeddings with the resize/crop/normalise on the GPU (bit-identical to clip_image_preprocess):
 // ships <= 3 B/pixel of the ORIGINAL image instead of 12 B/pixel of the resized one and takes the double-precision
 // resampling (the dominant host cost of benchmark.cpp / zsl.cpp style callers) off the CPU.
 // n raw images -> d_out [n][proj] on ctx's device, queued on ctx->stream.
-static bool encode_u8_to_device(clip_ctx * ctx, const clip_image_u8 * imgs, int n, float * d_out, bool normalize) {
+// (the images as PreSrc: decoded pixels, or JPEGs whose pixel half runs on the device — clip_amd_image_batch_encode_files; both kinds count
+// 3 bytes per pixel towards the chunk limits, so a list of files is cut into the same forward batches as its decoded pixels)
+bool clipamd::encode_sources_to_device(clip_ctx * ctx, const PreSrc * imgs, int n, float * d_out, bool normalize) {
     const int S = ctx->vision_hparams.image_size, proj = ctx->vision_hparams.projection_dim;
     const size_t per = (size_t)S * S * 3;
     (void)hipSetDevice(ctx->device);
@@ -258,7 +262,7 @@ static bool encode_u8_to_device(clip_ctx * ctx, const clip_image_u8 * imgs, int 
                 pbytes += (size_t)3 * (size_t)std::max(0, imgs[b0 + p0 + pn].nx) * (size_t)std::max(0, imgs[b0 + p0 + pn].ny);
                 pn++;
             }
-            ok = ok && preprocess_batch_device(ctx, imgs + b0 + p0, pn, (float *)ctx->io_in + (size_t)p0 * per, pipelined ? piece_idx : -1);
+            ok = ok && preprocess_sources_device(ctx, imgs + b0 + p0, pn, (float *)ctx->io_in + (size_t)p0 * per, pipelined ? piece_idx : -1);
             p0 += pn;
             piece_idx++;
         }
@@ -266,6 +270,14 @@ static bool encode_u8_to_device(clip_ctx * ctx, const clip_image_u8 * imgs, int 
         b0 += bc;
     }
     return ok;
+}
+
+extern "C" {
+
+static bool encode_u8_to_device(clip_ctx * ctx, const clip_image_u8 * imgs, int n, float * d_out, bool normalize) {
+    std::vector<PreSrc> src((size_t)std::max(n, 0));
+    for (int i = 0; i < n; i++) { src[i].nx = imgs[i].nx; src[i].ny = imgs[i].ny; src[i].rgb = imgs[i].data; }
+    return encode_sources_to_device(ctx, src.data(), n, d_out, normalize);
 }
 
 bool clip_amd_image_batch_encode_u8(struct clip_ctx * ctx, const struct clip_image_u8 * imgs, int n, float * vec, bool normalize) try {
@@ -298,6 +310,20 @@ bool clip_amd_image_batch_encode_u8(struct clip_ctx * ctx, const struct clip_ima
     if (ctx->profiling) prof_collect(ctx);
     return ok;
 } catch (const std::exception & e) { fprintf(stderr, "clip_amd_image_batch_encode_u8: %s\n", e.what()); return false; } catch (...) { fprintf(stderr, "clip_amd_image_batch_encode_u8: unknown exception\n"); return false; }
+
+// encoded images (files, or buffers in memory) -> embeddings: threaded decode, JPEG pixel half on the GPU (files_pipeline.cpp)
+int clip_amd_image_batch_encode_files(struct clip_ctx * ctx, const char * const * paths, int n, int max_images, int n_threads, bool normalize, float * vec,
+                                      int * consumed, uint8_t * ok) try {
+    RelaxCapture relax_capture;     // (model.h: this thread may allocate while another thread of the process captures)
+    if (n > 0 && !paths) { fprintf(stderr, "clip_amd_image_batch_encode_files: bad arguments\n"); return -1; }
+    return encode_encoded_images(ctx, paths, nullptr, nullptr, n, max_images, n_threads, normalize, vec, consumed, ok, "clip_amd_image_batch_encode_files");
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_image_batch_encode_files: %s\n", e.what()); return -1; } catch (...) { fprintf(stderr, "clip_amd_image_batch_encode_files: unknown exception\n"); return -1; }
+int clip_amd_image_batch_encode_memory(struct clip_ctx * ctx, const uint8_t * const * data, const size_t * sizes, int n, int max_images, int n_threads,
+                                       bool normalize, float * vec, int * consumed, uint8_t * ok) try {
+    RelaxCapture relax_capture;     // (model.h: this thread may allocate while another thread of the process captures)
+    if (n > 0 && (!data || !sizes)) { fprintf(stderr, "clip_amd_image_batch_encode_memory: bad arguments\n"); return -1; }
+    return encode_encoded_images(ctx, nullptr, data, sizes, n, max_images, n_threads, normalize, vec, consumed, ok, "clip_amd_image_batch_encode_memory");
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_image_batch_encode_memory: %s\n", e.what()); return -1; } catch (...) { fprintf(stderr, "clip_amd_image_batch_encode_memory: unknown exception\n"); return -1; }
 
 // Device-resident sharded image encode on a clip_amd_model_load_multi context (the measured form of SURVEY 8e: bench.py --single-process).
 // d_imgs[g]: the preprocessed f32 images of shard g ([hi - lo][S][S][3], clip_amd_shard_bounds(total, G, g)) ON device g.
@@ -1311,6 +1337,110 @@ float clip_amd_bench_attention(int nseq, int T, int h, int n_head, int causal, i
     return ms < 0 ? -4.f : ms * 1000.f / iters;
 }
 
+
+// ---- JPEG stages (jpeg_stages.h) ----
+// info[16]: route (0 host, 1 device), width, height, ncomp, progressive, colour rule, complete, then (h, v) of the components.  No device needed.
+int clip_amd_test_jpeg_plan(const uint8_t * data, size_t size, int * info) try {
+    if (!info) return -3;
+    for (int i = 0; i < 16; i++) info[i] = 0;
+    if (!data) return 0;
+    JpegCoefImage im;
+    std::string err;
+    if (!jpeg_entropy_stage(data, size, im, err)) return 0;
+    info[0] = jpeg_plan(im); info[1] = im.width; info[2] = im.height; info[3] = im.ncomp; info[4] = im.progressive ? 1 : 0; info[5] = im.colour;
+    info[6] = im.complete ? 1 : 0;
+    for (int k = 0; k < im.ncomp; k++) { info[7 + 2 * k] = im.comp[k].h; info[8 + 2 * k] = im.comp[k].v; }
+    return 1;
+} catch (...) { return 0; }
+
+long long clip_amd_test_jpeg_device_count(void) { return jpeg_device_images(); }
+
+// entropy stage on the host, jpeg_idct_kernel + jpeg_rgb_kernel, D2H of the [ny][nx][3] block.  -2: not a JPEG or planned "host" (refused, nothing runs)
+int clip_amd_test_jpeg_decode_device(const uint8_t * data, size_t size, uint8_t * rgb, size_t cap, int * nx, int * ny) try {
+    if (!data || !rgb || !nx || !ny) return -3;
+    JpegCoefImage im;
+    std::string err;
+    if (!jpeg_entropy_stage(data, size, im, err) || jpeg_plan(im) != JPEG_ROUTE_DEVICE) return -2;
+    *nx = im.width; *ny = im.height;
+    const size_t out_bytes = (size_t)3 * im.width * im.height;
+    if (cap < out_bytes) return -3;
+    if (!test_device()) return -1;
+    const JpegCoefImage * one = &im;
+    const long long off = 0;
+    JpegTables jt;
+    if (!jpeg_build_tables(&one, &off, 1, jt) || !jpeg_tables_in_bounds(jt, 0, (long long)out_bytes)) return -3;
+    std::vector<int16_t> coef(jt.coef_values);
+    for (int c = 0; c < im.ncomp; c++) memcpy(&coef[(size_t)jt.planes[c].coef_off], im.comp[c].coef.data(), (size_t)jt.planes[c].nblocks * 64 * sizeof(int16_t));
+    const size_t guard = 64;     // behind the pixels: must come back untouched
+    DBuf dp(jt.planes.size() * sizeof(JpegPlaneDesc)), di(sizeof(JpegImgDesc)), dc(coef.size() * 2), ds(jt.plane_bytes), dout(out_bytes + guard);
+    if (!dp.p || !di.p || !dc.p || !ds.p || !dout.p) return -1;
+    upload(dp, jt.planes.data(), jt.planes.size() * sizeof(JpegPlaneDesc));
+    upload(di, jt.imgs.data(), sizeof(JpegImgDesc));
+    upload(dc, coef.data(), coef.size() * 2);
+    (void)hipMemset(dout.p, 0xA5, out_bytes + guard);
+    launch_jpeg_idct((const JpegPlaneDesc *)dp.p, (int)jt.planes.size(), jt.max_blocks, (const int16_t *)dc.p, (uint8_t *)ds.p, nullptr);
+    launch_jpeg_rgb((const JpegPlaneDesc *)dp.p, (const JpegImgDesc *)di.p, 1, jt.max_pixels, (const uint8_t *)ds.p, (uint8_t *)dout.p, nullptr);
+    if (!test_sync()) return -4;
+    std::vector<uint8_t> back(out_bytes + guard);
+    download(back.data(), dout, back.size());
+    for (size_t i = 0; i < guard; i++)
+        if (back[out_bytes + i] != 0xA5) return -5;
+    memcpy(rgb, back.data(), out_bytes);
+    return 0;
+} catch (...) { return -3; }
+
+// kernel times of the two JPEG kernels over `reps` runs of one device-planned image replicated `copies` times (scripts/files_bench.py):
+// ms[0] = idct, ms[1] = rgb (medians); bytes[0], bytes[1] = what each must move per run.  Same return codes as above.
+int clip_amd_bench_jpeg_kernels(const uint8_t * data, size_t size, int copies, int reps, float * ms, double * bytes) try {
+    if (!data || !ms || !bytes || copies < 1 || copies > 256 || reps < 1 || reps > 1000) return -3;
+    JpegCoefImage im;
+    std::string err;
+    if (!jpeg_entropy_stage(data, size, im, err) || jpeg_plan(im) != JPEG_ROUTE_DEVICE) return -2;
+    if (!test_device()) return -1;
+    const size_t pix = (((size_t)3 * im.width * im.height) + 15) & ~(size_t)15;
+    std::vector<const JpegCoefImage *> imgs((size_t)copies, &im);
+    std::vector<long long> offs((size_t)copies);
+    for (int i = 0; i < copies; i++) offs[i] = (long long)(pix * i);
+    JpegTables jt;
+    if (!jpeg_build_tables(imgs.data(), offs.data(), copies, jt) || !jpeg_tables_in_bounds(jt, 0, (long long)(pix * copies))) return -3;
+    std::vector<int16_t> coef(jt.coef_values);
+    for (int i = 0; i < copies; i++)
+        for (int c = 0; c < im.ncomp; c++) {
+            const JpegPlaneDesc & pd = jt.planes[jt.imgs[i].plane[c]];
+            memcpy(&coef[(size_t)pd.coef_off], im.comp[c].coef.data(), (size_t)pd.nblocks * 64 * sizeof(int16_t));
+        }
+    DBuf dp(jt.planes.size() * sizeof(JpegPlaneDesc)), di(jt.imgs.size() * sizeof(JpegImgDesc)), dc(coef.size() * 2), ds(jt.plane_bytes), dout(pix * copies);
+    if (!dp.p || !di.p || !dc.p || !ds.p || !dout.p) return -1;
+    upload(dp, jt.planes.data(), jt.planes.size() * sizeof(JpegPlaneDesc));
+    upload(di, jt.imgs.data(), jt.imgs.size() * sizeof(JpegImgDesc));
+    upload(dc, coef.data(), coef.size() * 2);
+    hipEvent_t e0, e1, e2;
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventCreate(&e2) != hipSuccess) return -1;
+    std::vector<float> t0, t1;
+    bool good = true;
+    for (int r = 0; r < reps + 2 && good; r++) {         // (two warm-up runs)
+        (void)hipEventRecord(e0, nullptr);
+        launch_jpeg_idct((const JpegPlaneDesc *)dp.p, (int)jt.planes.size(), jt.max_blocks, (const int16_t *)dc.p, (uint8_t *)ds.p, nullptr);
+        (void)hipEventRecord(e1, nullptr);
+        launch_jpeg_rgb((const JpegPlaneDesc *)dp.p, (const JpegImgDesc *)di.p, copies, jt.max_pixels, (const uint8_t *)ds.p, (uint8_t *)dout.p, nullptr);
+        (void)hipEventRecord(e2, nullptr);
+        good = hipEventSynchronize(e2) == hipSuccess;
+        float a = 0, b = 0;
+        good = good && hipEventElapsedTime(&a, e0, e1) == hipSuccess && hipEventElapsedTime(&b, e1, e2) == hipSuccess;
+        if (r >= 2) { t0.push_back(a); t1.push_back(b); }
+    }
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2);
+    if (!good || !test_sync()) return -4;
+    std::sort(t0.begin(), t0.end());
+    std::sort(t1.begin(), t1.end());
+    ms[0] = t0[t0.size() / 2];
+    ms[1] = t1[t1.size() / 2];
+    double samples = 0;
+    for (int c = 0; c < im.ncomp; c++) samples += (double)im.comp[c].bw * im.comp[c].bh * 64;
+    bytes[0] = copies * samples * 3.0;                                                       // 2 B of coefficients in, 1 B of samples out
+    bytes[1] = copies * (samples + 3.0 * im.width * im.height);                              // every sample in once, 3 B per pixel out
+    return 0;
+} catch (...) { return -3; }
 #endif  // CLIPAMD_TEST_HOOKS
 
 }  // extern "C"

@@ -12,10 +12,10 @@
 #include <zlib.h>
 
 #include "model.h"
+#include "jpeg_stages.h"
 
 namespace clipamd {
 
-bool decode_jpeg(const uint8_t * data, size_t size, std::vector<uint8_t> & rgb, int & nx, int & ny, std::string & err);  // jpeg_decode.cpp
 // image_formats.cpp
 bool decode_bmp(const std::vector<uint8_t> & d, std::vector<uint8_t> & rgb, int & nx, int & ny);
 bool decode_gif(const std::vector<uint8_t> & d, std::vector<uint8_t> & rgb, int & nx, int & ny);
@@ -25,9 +25,7 @@ bool decode_tga(const std::vector<uint8_t> & d, std::vector<uint8_t> & rgb, int 
 bool decode_pic(const std::vector<uint8_t> & d, std::vector<uint8_t> & rgb, int & nx, int & ny);
 bool decode_hdr(const std::vector<uint8_t> & d, std::vector<uint8_t> & rgb, int & nx, int & ny);
 
-namespace {
-
-bool read_file(const char * fname, std::vector<uint8_t> & out) {
+bool read_image_file(const char * fname, std::vector<uint8_t> & out) {
     FILE * f = fopen(fname, "rb");
     if (!f) return false;
     fseek(f, 0, SEEK_END);
@@ -39,6 +37,8 @@ bool read_file(const char * fname, std::vector<uint8_t> & out) {
     fclose(f);
     return ok;
 }
+
+namespace {
 
 // ---- PNG ----
 inline uint32_t be32(const uint8_t * p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
@@ -185,17 +185,33 @@ bool decode_png(const std::vector<uint8_t> & d, std::vector<uint8_t> & rgb, int 
 
 }  // namespace
 
+// The format dispatch, in the order of the reference's decoder: formats with a magic number first, TGA — which has none — last.
+// staged == nullptr: pixels in rgb.  Otherwise a JPEG that jpeg_plan() gives to the device stops after the entropy stage: *staged holds its
+// coefficients, *is_staged is set and rgb stays empty (files_pipeline.cpp); every other file is decoded to pixels as before.
+bool decode_image_bytes(const std::vector<uint8_t> & d, std::vector<uint8_t> & rgb, int & nx, int & ny, std::string & err, JpegCoefImage * staged,
+                        bool * is_staged) {
+    if (is_staged) *is_staged = false;
+    if (decode_png(d, rgb, nx, ny) || decode_bmp(d, rgb, nx, ny) || decode_gif(d, rgb, nx, ny) || decode_psd(d, rgb, nx, ny) || decode_pic(d, rgb, nx, ny))
+        return true;
+    {
+        JpegCoefImage local;
+        JpegCoefImage & j = staged ? *staged : local;
+        if (jpeg_entropy_stage(d.data(), d.size(), j, err)) {
+            nx = j.width;
+            ny = j.height;
+            if (staged && jpeg_plan(j) == JPEG_ROUTE_DEVICE) *is_staged = true;
+            else jpeg_pixel_stage(j, rgb);
+            return true;
+        }
+    }
+    return decode_pnm(d, rgb, nx, ny) || decode_hdr(d, rgb, nx, ny) || decode_tga(d, rgb, nx, ny);
+}
+
 bool load_image_file(const char * fname, clip_image_u8 * img) {
     std::vector<uint8_t> d, rgb;
     int nx = 0, ny = 0;
     std::string err;
-    bool ok = read_file(fname, d);
-    if (ok) {
-        // (the order of the reference's decoder: formats with a magic number first, TGA — which has none — last)
-        ok = decode_png(d, rgb, nx, ny) || decode_bmp(d, rgb, nx, ny) || decode_gif(d, rgb, nx, ny) || decode_psd(d, rgb, nx, ny) ||
-             decode_pic(d, rgb, nx, ny) || decode_jpeg(d.data(), d.size(), rgb, nx, ny, err) || decode_pnm(d, rgb, nx, ny) || decode_hdr(d, rgb, nx, ny) ||
-             decode_tga(d, rgb, nx, ny);
-    }
+    const bool ok = read_image_file(fname, d) && decode_image_bytes(d, rgb, nx, ny, err, nullptr, nullptr);
     if (!ok) {
         fprintf(stderr, "%s: failed to load '%s'%s%s\n", "clip_image_load_from_file", fname, err.empty() ? "" : ": ", err.c_str());
         return false;

@@ -9,10 +9,16 @@
 //   * chroma up-sampling: 2x horizontal / vertical / both with the 3:1 "triangle" filter, nearest for other factors,
 //   * YCbCr -> RGB in 20-bit fixed point (1.40200, 0.34414 (truncated to 16 bits), 0.71414, 1.77200),
 //   * grey-scale -> RGB replication; four-component files: CMYK / YCCK per the Adobe APP14 transform (else YCbCr + ignored channel).
+//
+// Two stages (jpeg_stages.h): the ENTROPY stage below (struct Decoder) parses the markers and decodes every scan into dequantised 16-bit
+// coefficients; the PIXEL stage (jpeg_pixel_stage) runs the IDCT, the up-sampling and the colour conversion over them.  decode_jpeg() is
+// the one after the other.  jpeg_plan() says whether the device kernels of k_jpeg.hip may stand in for the host pixel stage.
 #include <cstdint>
 #include <cstring>
 #include <string>
 #include <vector>
+
+#include "jpeg_stages.h"
 
 namespace clipamd {
 
@@ -73,9 +79,8 @@ struct Component {
     int td = 0, ta = 0;           // current scan's tables
     int dc_pred = 0;
     int bw = 0, bh = 0;           // blocks per row / column (padded to MCU)
-    int pw = 0, ph = 0;           // plane size in pixels (bw*8, bh*8)
-    std::vector<int16_t> coef;    // progressive: bw*bh*64
-    std::vector<uint8_t> plane;   // decoded samples
+    std::vector<int16_t> coef;    // bw*bh*64.  baseline: dequantised as each block is decoded; progressive: raw until the last scan has ended
+    std::vector<uint8_t> done;    // baseline: bw*bh, 1 where a scan decoded the block
 };
 
 struct Decoder {
@@ -100,6 +105,8 @@ struct Decoder {
     int marker = 0;      // pending marker hit inside entropy data
     bool nomore = false;
     int eobrun = 0;
+    int pad_bits = 0;    // zero bits the reader made up behind a marker or the end of the data, since the last reset
+    bool complete = true;   // no scan ended early, none consumed made-up bits
     // scan params
     int ss = 0, se = 63, ah = 0, al = 0;
 
@@ -110,6 +117,7 @@ struct Decoder {
 
     void fill() {
         while (bitcnt <= 24) {
+            bool made_up = nomore || p >= end;
             int b = nomore ? 0 : get8();
             if (b == 0xFF) {
                 int c = get8();
@@ -118,8 +126,12 @@ struct Decoder {
                     marker = c;
                     nomore = true;
                     b = 0;
+                    made_up = true;
                 }
             }
+            // made-up bytes only ever follow real ones, so they sit at the tail of bitbuf: a scan has consumed some of them exactly when
+            // bitcnt < pad_bits (ate_padding)
+            if (made_up) pad_bits += 8;
             bitbuf |= (uint32_t)b << (24 - bitcnt);
             bitcnt += 8;
         }
@@ -161,7 +173,10 @@ struct Decoder {
         bitcnt -= l;
         return h.sym[idx];
     }
+    bool ate_padding() const { return bitcnt < pad_bits; }
     void reset_entropy() {
+        if (ate_padding()) complete = false;
+        pad_bits = 0;
         bitbuf = 0;
         bitcnt = 0;
         nomore = false;
@@ -283,60 +298,6 @@ struct Decoder {
         return true;
     }
 
-    // ---- IDCT (LL&M, 12-bit constants) ----
-    static inline uint8_t clamp8(int x) { return (uint8_t)((unsigned)x > 255 ? (x < 0 ? 0 : 255) : x); }
-    static inline int fx(double v) { return (int)(v * 4096 + 0.5); }
-
-    // One 1-D pass over eight 16-bit inputs.  The arithmetic is the scalar LL&M flow regrouped the way the reference's SSE2 kernel groups it
-    // (the same integers for every valid stream): the four input sums s0 +- s4, s1 + s7, s3 + s5 are formed in 16 bits and WRAP, every
-    // product and sum behind them is 32-bit (wrapping), and the eight results are shifted and SATURATED back to 16 bits.  Only corrupt
-    // streams (coefficients x quantisers beyond 16 bits) ever reach the wrap / saturation; with them the pixels still equal that decoder's.
-    static inline int sat16(int x) { return x > 32767 ? 32767 : (x < -32768 ? -32768 : x); }
-    static inline int32_t wrap_mul(int a, int b) { return (int32_t)((uint32_t)a * (uint32_t)b); }
-    static inline int32_t wrap_add(int32_t a, int32_t b) { return (int32_t)((uint32_t)a + (uint32_t)b); }
-    static inline int32_t wrap_sub(int32_t a, int32_t b) { return (int32_t)((uint32_t)a - (uint32_t)b); }
-    static void idct1d(const int s[8], int32_t bias, int shift, int out[8]) {
-        const int c0541 = fx(0.5411961), cm1847 = fx(-1.847759065), c0765 = fx(0.765366865), c1175 = fx(1.175875602), cm0899 = fx(-0.899976223),
-                  cm2562 = fx(-2.562915447), cm1961 = fx(-1.961570560), c0298 = fx(0.298631336), c3072 = fx(3.072711026), cm0390 = fx(-0.390180644),
-                  c2053 = fx(2.053119869), c1501 = fx(1.501321110);
-        const int e04 = (int16_t)(s[0] + s[4]), d04 = (int16_t)(s[0] - s[4]), a17 = (int16_t)(s[1] + s[7]), a35 = (int16_t)(s[3] + s[5]);
-        // even part
-        const int32_t t2e = wrap_add(wrap_mul(s[2], c0541), wrap_mul(s[6], c0541 + cm1847));
-        const int32_t t3e = wrap_add(wrap_mul(s[2], c0541 + c0765), wrap_mul(s[6], c0541));
-        const int32_t t0e = wrap_mul(e04, 4096), t1e = wrap_mul(d04, 4096);
-        const int32_t x0 = wrap_add(t0e, t3e), x3 = wrap_sub(t0e, t3e), x1 = wrap_add(t1e, t2e), x2 = wrap_sub(t1e, t2e);
-        // odd part
-        const int32_t y0 = wrap_add(wrap_mul(s[7], cm1961 + c0298), wrap_mul(s[3], cm1961));
-        const int32_t y2 = wrap_add(wrap_mul(s[7], cm1961), wrap_mul(s[3], cm1961 + c3072));
-        const int32_t y1 = wrap_add(wrap_mul(s[5], cm0390 + c2053), wrap_mul(s[1], cm0390));
-        const int32_t y3 = wrap_add(wrap_mul(s[5], cm0390), wrap_mul(s[1], cm0390 + c1501));
-        const int32_t y4 = wrap_add(wrap_mul(a17, c1175 + cm0899), wrap_mul(a35, c1175));
-        const int32_t y5 = wrap_add(wrap_mul(a17, c1175), wrap_mul(a35, c1175 + cm2562));
-        const int32_t x4 = wrap_add(y0, y4), x5 = wrap_add(y1, y5), x6 = wrap_add(y2, y5), x7 = wrap_add(y3, y4);
-        const int32_t xe[4] = {x0, x1, x2, x3}, xo[4] = {x7, x6, x5, x4};
-        for (int k = 0; k < 4; k++) {
-            const int32_t a = wrap_add(xe[k], bias);
-            out[k] = sat16(wrap_add(a, xo[k]) >> shift);
-            out[7 - k] = sat16(wrap_sub(a, xo[k]) >> shift);
-        }
-    }
-
-    static void idct_block(uint8_t * out, int stride, const int16_t * d) {
-        int val[64];
-        for (int i = 0; i < 8; i++) {                      // columns: 2 extra bits of precision kept (>> 10 of 12)
-            const int col[8] = {d[i], d[8 + i], d[16 + i], d[24 + i], d[32 + i], d[40 + i], d[48 + i], d[56 + i]};
-            int o[8];
-            idct1d(col, 512, 10, o);
-            for (int k = 0; k < 8; k++) val[k * 8 + i] = o[k];
-        }
-        for (int i = 0; i < 8; i++) {                      // rows: >> 17 with the rounding and the +128 level shift in the bias
-            int o[8];
-            idct1d(val + i * 8, 65536 + (128 << 17), 17, o);
-            uint8_t * q = out + i * stride;
-            for (int k = 0; k < 8; k++) q[k] = clamp8(o[k]);
-        }
-    }
-
     // ---- segments ----
     bool read_dqt(int len) {
         while (len > 0) {
@@ -396,10 +357,9 @@ struct Decoder {
             Component & c = comp[i];
             c.bw = mcux * c.h;
             c.bh = mcuy * c.v;
-            c.pw = c.bw * 8;
-            c.ph = c.bh * 8;
-            c.plane.assign((size_t)c.pw * c.ph, 0);
-            if (progressive) c.coef.assign((size_t)c.bw * c.bh * 64, 0);
+            // (a second SOF starts over: what the scans before it decoded is dropped, whichever process they belonged to)
+            c.coef.assign((size_t)c.bw * c.bh * 64, 0);
+            c.done.assign(progressive ? 0 : (size_t)c.bw * c.bh, 0);
         }
         return true;
     }
@@ -466,13 +426,14 @@ struct Decoder {
                     } else {
                         if (!hdc[c.td].present || !hac[c.ta].present) return fail("missing huffman table");
                         if (!block_baseline(tmp, c)) return false;
-                        for (int i = 0; i < 64; i++) tmp[i] = (int16_t)(tmp[i] * qt[c.tq][i]);
-                        idct_block(&c.plane[(size_t)by * 8 * c.pw + bx * 8], c.pw, tmp);
+                        int16_t * d = &c.coef[((size_t)by * c.bw + bx) * 64];
+                        for (int i = 0; i < 64; i++) d[i] = (int16_t)(tmp[i] * qt[c.tq][i]);
+                        c.done[(size_t)by * c.bw + bx] = 1;
                     }
                     if (restart_interval) {
                         if (--todo <= 0) {
                             if (bitcnt < 24) fill();
-                            if (!(marker >= 0xD0 && marker <= 0xD7)) return true;
+                            if (!(marker >= 0xD0 && marker <= 0xD7)) return end_scan(by == h - 1 && bx == w - 1);
                             reset_entropy();
                             todo = restart_interval;
                         }
@@ -492,34 +453,41 @@ struct Decoder {
                                 } else {
                                     if (!hdc[c.td].present || !hac[c.ta].present) return fail("missing huffman table");
                                     if (!block_baseline(tmp, c)) return false;
-                                    for (int k = 0; k < 64; k++) tmp[k] = (int16_t)(tmp[k] * qt[c.tq][k]);
-                                    idct_block(&c.plane[(size_t)by * 8 * c.pw + bx * 8], c.pw, tmp);
+                                    int16_t * d = &c.coef[((size_t)by * c.bw + bx) * 64];
+                                    for (int k = 0; k < 64; k++) d[k] = (int16_t)(tmp[k] * qt[c.tq][k]);
+                                    c.done[(size_t)by * c.bw + bx] = 1;
                                 }
                             }
                     }
                     if (restart_interval) {
                         if (--todo <= 0) {
                             if (bitcnt < 24) fill();
-                            if (!(marker >= 0xD0 && marker <= 0xD7)) return true;
+                            if (!(marker >= 0xD0 && marker <= 0xD7)) return end_scan(my == mcuy - 1 && mx == mcux - 1);
                             reset_entropy();
                             todo = restart_interval;
                         }
                     }
                 }
         }
+        return end_scan(true);
+    }
+    // A scan is over: after its last block, or early where a restart marker is missing (what it did not reach keeps its zeros).  Either
+    // way the file still decodes; `complete` remembers whether every block came from bits that the file holds.
+    bool end_scan(bool all_blocks) {
+        if (!all_blocks || ate_padding()) complete = false;
         return true;
     }
 
+    // progressive: the coefficients are complete once the last scan has ended — multiply by the quantisers that hold NOW, over the blocks
+    // that carry image samples (the pixel stage transforms exactly those)
     void finish_progressive() {
-        int16_t tmp[64];
         for (int i = 0; i < ncomp; i++) {
             Component & c = comp[i];
             const int w = ceil_div(ceil_div(width * c.h, hmax), 8), h = ceil_div(ceil_div(height * c.v, vmax), 8);
             for (int by = 0; by < h; by++)
                 for (int bx = 0; bx < w; bx++) {
-                    const int16_t * d = &c.coef[((size_t)by * c.bw + bx) * 64];
-                    for (int k = 0; k < 64; k++) tmp[k] = (int16_t)(d[k] * qt[c.tq][k]);
-                    idct_block(&c.plane[(size_t)by * 8 * c.pw + bx * 8], c.pw, tmp);
+                    int16_t * d = &c.coef[((size_t)by * c.bw + bx) * 64];
+                    for (int k = 0; k < 64; k++) d[k] = (int16_t)(d[k] * qt[c.tq][k]);
                 }
         }
     }
@@ -582,136 +550,284 @@ struct Decoder {
         return true;
     }
 
-    // ---- up-sampling + colour conversion ----
-    static inline uint8_t div4(int x) { return (uint8_t)(x >> 2); }
-    static inline uint8_t div16(int x) { return (uint8_t)(x >> 4); }
-
-    static void row_h2(uint8_t * out, const uint8_t * in, int w) {
-        if (w == 1) { out[0] = out[1] = in[0]; return; }
-        out[0] = in[0];
-        out[1] = div4(in[0] * 3 + in[1] + 2);
-        int i;
-        for (i = 1; i < w - 1; i++) {
-            const int n = 3 * in[i] + 2;
-            out[i * 2 + 0] = div4(n + in[i - 1]);
-            out[i * 2 + 1] = div4(n + in[i + 1]);
+    // what the scans left, handed to the pixel stage
+    void export_to(JpegCoefImage & o) {
+        o.width = width; o.height = height; o.ncomp = ncomp;
+        o.hmax = hmax; o.vmax = vmax;
+        o.progressive = progressive;
+        o.complete = complete;
+        if (ncomp == 1) o.colour = JPEG_GREY;
+        else if (ncomp == 3)   // stored as R, G, B when the component ids say so, or under an Adobe marker with transform 0 in a file that is not JFIF
+            o.colour = (rgb_ids == 3 || (saw_adobe && adobe_transform == 0 && !saw_jfif)) ? JPEG_RGB : JPEG_YCC;
+        else {                 // four components: Adobe transform 0 = CMYK, 2 = YCCK, anything else: YCbCr + an ignored fourth channel
+            const int tr = saw_adobe ? adobe_transform : -1;
+            o.colour = tr == 0 ? JPEG_CMYK : tr == 2 ? JPEG_YCCK : JPEG_YCC_X;
         }
-        out[i * 2 + 0] = div4(in[w - 2] * 3 + in[w - 1] + 2);
-        out[i * 2 + 1] = in[w - 1];
-    }
-    static void row_v2(uint8_t * out, const uint8_t * near, const uint8_t * far, int w) {
-        for (int i = 0; i < w; i++) out[i] = div4(3 * near[i] + far[i] + 2);
-    }
-    static void row_hv2(uint8_t * out, const uint8_t * near, const uint8_t * far, int w) {
-        if (w == 1) { out[0] = out[1] = div4(3 * near[0] + far[0] + 2); return; }
-        int t1 = 3 * near[0] + far[0];
-        out[0] = div4(t1 + 2);
-        for (int i = 1; i < w; i++) {
-            const int t0 = t1;
-            t1 = 3 * near[i] + far[i];
-            out[i * 2 - 1] = div16(3 * t0 + t1 + 8);
-            out[i * 2] = div16(3 * t1 + t0 + 8);
-        }
-        out[w * 2 - 1] = div4(t1 + 2);
-    }
-    static void row_generic(uint8_t * out, const uint8_t * near, int w, int hs) {
-        for (int i = 0; i < w; i++)
-            for (int j = 0; j < hs; j++) out[i * hs + j] = near[i];
-    }
-
-    void to_rgb(std::vector<uint8_t> & rgb) {
-        rgb.resize((size_t)width * height * 3);
-        struct Res { int hs, vs, ystep, ypos, wl; const uint8_t *l0, *l1; std::vector<uint8_t> buf; };
-        Res rs[4];
-        for (int k = 0; k < ncomp; k++) {
-            Component & c = comp[k];
-            Res & r = rs[k];
-            r.hs = hmax / c.h;
-            r.vs = vmax / c.v;
-            r.ystep = r.vs >> 1;
-            r.wl = (width + r.hs - 1) / r.hs;
-            r.ypos = 0;
-            r.l0 = r.l1 = c.plane.data();
-            r.buf.resize((size_t)width + 8 * hmax + 16);
-        }
-        const int cy = (height * 1);
-        (void)cy;
-        for (int j = 0; j < height; j++) {
-            const uint8_t * line[4];
-            for (int k = 0; k < ncomp; k++) {
-                Component & c = comp[k];
-                Res & r = rs[k];
-                const bool bot = r.ystep >= (r.vs >> 1);
-                const uint8_t * near = bot ? r.l1 : r.l0;
-                const uint8_t * far = bot ? r.l0 : r.l1;
-                if (r.hs == 1 && r.vs == 1) line[k] = near;
-                else if (r.hs == 1 && r.vs == 2) { row_v2(r.buf.data(), near, far, r.wl); line[k] = r.buf.data(); }
-                else if (r.hs == 2 && r.vs == 1) { row_h2(r.buf.data(), near, r.wl); line[k] = r.buf.data(); }
-                else if (r.hs == 2 && r.vs == 2) { row_hv2(r.buf.data(), near, far, r.wl); line[k] = r.buf.data(); }
-                else { row_generic(r.buf.data(), near, r.wl, r.hs); line[k] = r.buf.data(); }
-                if (++r.ystep >= r.vs) {
-                    r.ystep = 0;
-                    r.l0 = r.l1;
-                    const int rows = (height * c.v + vmax - 1) / vmax;   // component height in samples
-                    if (++r.ypos < rows) r.l1 += c.pw;
-                }
-            }
-            uint8_t * o = &rgb[(size_t)j * width * 3];
-            // x * y / 255 rounded, for 0 <= x, y <= 255 (the multiply the reference's decoder uses for the K channel)
-            auto mul255 = [](int x, int y) { const unsigned t = (unsigned)(x * y) + 128u; return (uint8_t)((t + (t >> 8)) >> 8); };
-            auto ycc = [&](int i, uint8_t * px) {
-                const int yf = (line[0][i] << 20) + (1 << 19);
-                const int cb = line[1][i] - 128, cr = line[2][i] - 128;
-                int r = yf + cr * (((int)(1.40200f * 4096.0f + 0.5f)) << 8);
-                int g = yf + cr * -(((int)(0.71414f * 4096.0f + 0.5f)) << 8) + ((cb * -(((int)(0.34414f * 4096.0f + 0.5f)) << 8)) & 0xffff0000);
-                int b = yf + cb * (((int)(1.77200f * 4096.0f + 0.5f)) << 8);
-                r >>= 20; g >>= 20; b >>= 20;
-                px[0] = clamp8(r); px[1] = clamp8(g); px[2] = clamp8(b);
-            };
-            if (ncomp == 1) {
-                for (int i = 0; i < width; i++) o[3 * i] = o[3 * i + 1] = o[3 * i + 2] = line[0][i];
-            } else if (ncomp == 3) {
-                // stored as R, G, B when the component ids say so, or under an Adobe marker with transform 0 in a file that is not JFIF
-                const bool is_rgb = rgb_ids == 3 || (saw_adobe && adobe_transform == 0 && !saw_jfif);
-                for (int i = 0; i < width; i++) {
-                    if (is_rgb) { o[3 * i] = line[0][i]; o[3 * i + 1] = line[1][i]; o[3 * i + 2] = line[2][i]; }
-                    else ycc(i, o + 3 * i);
-                }
-            } else {
-                // four components: Adobe transform 0 = CMYK (stored inverted: sample * K / 255), 2 = YCCK ((255 - RGB) * K / 255),
-                // anything else: YCbCr + an ignored fourth channel
-                const int tr = saw_adobe ? adobe_transform : -1;
-                for (int i = 0; i < width; i++) {
-                    uint8_t * px = o + 3 * i;
-                    const int k = line[3][i];
-                    if (tr == 0) { px[0] = mul255(line[0][i], k); px[1] = mul255(line[1][i], k); px[2] = mul255(line[2][i], k); }
-                    else {
-                        ycc(i, px);
-                        if (tr == 2) { px[0] = mul255(255 - px[0], k); px[1] = mul255(255 - px[1], k); px[2] = mul255(255 - px[2], k); }
-                    }
-                }
-            }
+        for (int i = 0; i < ncomp; i++) {
+            Component & c = comp[i];
+            JpegCoefPlane & q = o.comp[i];
+            q.h = c.h; q.v = c.v; q.bw = c.bw; q.bh = c.bh;
+            q.cw = ceil_div(ceil_div(width * c.h, hmax), 8);
+            q.ch = ceil_div(ceil_div(height * c.v, vmax), 8);
+            q.coef = std::move(c.coef);
+            q.done = std::move(c.done);
         }
     }
 };
 
+// ---- pixel stage, host ----
+using namespace jpegmath;
+
+void idct_block(uint8_t * out, int stride, const int16_t * d) {
+    int val[64];
+    for (int i = 0; i < 8; i++) {                      // columns
+        const int col[8] = {d[i], d[8 + i], d[16 + i], d[24 + i], d[32 + i], d[40 + i], d[48 + i], d[56 + i]};
+        int o[8];
+        idct1d(col, IDCT_COL_BIAS, IDCT_COL_SHIFT, o);
+        for (int k = 0; k < 8; k++) val[k * 8 + i] = o[k];
+    }
+    for (int i = 0; i < 8; i++) {                      // rows
+        int o[8];
+        idct1d(val + i * 8, IDCT_ROW_BIAS, IDCT_ROW_SHIFT, o);
+        uint8_t * q = out + i * stride;
+        for (int k = 0; k < 8; k++) q[k] = clamp8(o[k]);
+    }
+}
+
+// Sample planes [bh*8][bw*8] of every component.  A baseline block that no scan decoded keeps samples of 0; a progressive file is
+// transformed over every block that carries image samples, decoded or not.
+void idct_planes(const JpegCoefImage & im, std::vector<uint8_t> plane[4]) {
+    for (int i = 0; i < im.ncomp; i++) {
+        const JpegCoefPlane & c = im.comp[i];
+        const int pw = c.bw * 8;
+        plane[i].assign((size_t)pw * c.bh * 8, 0);
+        const int w = im.progressive ? c.cw : c.bw, h = im.progressive ? c.ch : c.bh;
+        for (int by = 0; by < h; by++)
+            for (int bx = 0; bx < w; bx++) {
+                const size_t b = (size_t)by * c.bw + bx;
+                if (!im.progressive && !c.done[b]) continue;
+                idct_block(&plane[i][(size_t)by * 8 * pw + bx * 8], pw, &c.coef[b * 64]);
+            }
+    }
+}
+
+// ---- up-sampling + colour conversion ----
+inline uint8_t div4(int x) { return (uint8_t)(x >> 2); }
+inline uint8_t div16(int x) { return (uint8_t)(x >> 4); }
+
+void row_h2(uint8_t * out, const uint8_t * in, int w) {
+    if (w == 1) { out[0] = out[1] = in[0]; return; }
+    out[0] = in[0];
+    out[1] = div4(in[0] * 3 + in[1] + 2);
+    int i;
+    for (i = 1; i < w - 1; i++) {
+        const int n = 3 * in[i] + 2;
+        out[i * 2 + 0] = div4(n + in[i - 1]);
+        out[i * 2 + 1] = div4(n + in[i + 1]);
+    }
+    out[i * 2 + 0] = div4(in[w - 2] * 3 + in[w - 1] + 2);
+    out[i * 2 + 1] = in[w - 1];
+}
+void row_v2(uint8_t * out, const uint8_t * near, const uint8_t * far, int w) {
+    for (int i = 0; i < w; i++) out[i] = div4(3 * near[i] + far[i] + 2);
+}
+void row_hv2(uint8_t * out, const uint8_t * near, const uint8_t * far, int w) {
+    if (w == 1) { out[0] = out[1] = div4(3 * near[0] + far[0] + 2); return; }
+    int t1 = 3 * near[0] + far[0];
+    out[0] = div4(t1 + 2);
+    for (int i = 1; i < w; i++) {
+        const int t0 = t1;
+        t1 = 3 * near[i] + far[i];
+        out[i * 2 - 1] = div16(3 * t0 + t1 + 8);
+        out[i * 2] = div16(3 * t1 + t0 + 8);
+    }
+    out[w * 2 - 1] = div4(t1 + 2);
+}
+void row_generic(uint8_t * out, const uint8_t * near, int w, int hs) {
+    for (int i = 0; i < w; i++)
+        for (int j = 0; j < hs; j++) out[i * hs + j] = near[i];
+}
+
+void to_rgb(const JpegCoefImage & im, const std::vector<uint8_t> plane[4], std::vector<uint8_t> & rgb) {
+    const int width = im.width, height = im.height, ncomp = im.ncomp, hmax = im.hmax, vmax = im.vmax;
+    rgb.resize((size_t)width * height * 3);
+    struct Res { int hs, vs, ystep, ypos, wl, pw; const uint8_t *l0, *l1; std::vector<uint8_t> buf; };
+    Res rs[4];
+    for (int k = 0; k < ncomp; k++) {
+        const JpegCoefPlane & c = im.comp[k];
+        Res & r = rs[k];
+        r.hs = hmax / c.h;
+        r.vs = vmax / c.v;
+        r.ystep = r.vs >> 1;
+        r.wl = (width + r.hs - 1) / r.hs;
+        r.ypos = 0;
+        r.pw = c.bw * 8;
+        r.l0 = r.l1 = plane[k].data();
+        r.buf.resize((size_t)width + 8 * hmax + 16);
+    }
+    for (int j = 0; j < height; j++) {
+        const uint8_t * line[4];
+        for (int k = 0; k < ncomp; k++) {
+            const JpegCoefPlane & c = im.comp[k];
+            Res & r = rs[k];
+            const bool bot = r.ystep >= (r.vs >> 1);
+            const uint8_t * near = bot ? r.l1 : r.l0;
+            const uint8_t * far = bot ? r.l0 : r.l1;
+            if (r.hs == 1 && r.vs == 1) line[k] = near;
+            else if (r.hs == 1 && r.vs == 2) { row_v2(r.buf.data(), near, far, r.wl); line[k] = r.buf.data(); }
+            else if (r.hs == 2 && r.vs == 1) { row_h2(r.buf.data(), near, r.wl); line[k] = r.buf.data(); }
+            else if (r.hs == 2 && r.vs == 2) { row_hv2(r.buf.data(), near, far, r.wl); line[k] = r.buf.data(); }
+            else { row_generic(r.buf.data(), near, r.wl, r.hs); line[k] = r.buf.data(); }
+            if (++r.ystep >= r.vs) {
+                r.ystep = 0;
+                r.l0 = r.l1;
+                const int rows = (height * c.v + vmax - 1) / vmax;   // component height in samples
+                if (++r.ypos < rows) r.l1 += r.pw;
+            }
+        }
+        uint8_t * o = &rgb[(size_t)j * width * 3];
+        // x * y / 255 rounded, for 0 <= x, y <= 255 (the multiply the reference's decoder uses for the K channel)
+        auto mul255 = [](int x, int y) { const unsigned t = (unsigned)(x * y) + 128u; return (uint8_t)((t + (t >> 8)) >> 8); };
+        switch (im.colour) {
+        case JPEG_GREY:
+            for (int i = 0; i < width; i++) o[3 * i] = o[3 * i + 1] = o[3 * i + 2] = line[0][i];
+            break;
+        case JPEG_RGB:
+            for (int i = 0; i < width; i++) { o[3 * i] = line[0][i]; o[3 * i + 1] = line[1][i]; o[3 * i + 2] = line[2][i]; }
+            break;
+        case JPEG_YCC:
+            for (int i = 0; i < width; i++) ycc_to_rgb(line[0][i], line[1][i], line[2][i], o + 3 * i);
+            break;
+        default:
+            // four components: CMYK (stored inverted: sample * K / 255), YCCK ((255 - RGB) * K / 255), or YCbCr + an ignored fourth channel
+            for (int i = 0; i < width; i++) {
+                uint8_t * px = o + 3 * i;
+                const int k = line[3][i];
+                if (im.colour == JPEG_CMYK) { px[0] = mul255(line[0][i], k); px[1] = mul255(line[1][i], k); px[2] = mul255(line[2][i], k); }
+                else {
+                    ycc_to_rgb(line[0][i], line[1][i], line[2][i], px);
+                    if (im.colour == JPEG_YCCK) { px[0] = mul255(255 - px[0], k); px[1] = mul255(255 - px[1], k); px[2] = mul255(255 - px[2], k); }
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
 
-bool decode_jpeg(const uint8_t * data, size_t size, std::vector<uint8_t> & rgb, int & nx, int & ny, std::string & err) {
+bool jpeg_entropy_stage(const uint8_t * data, size_t size, JpegCoefImage & img, std::string & err) {
     if (size < 4 || data[0] != 0xFF || data[1] != 0xD8) return false;
     Decoder * d = new Decoder();
     d->p = data;
     d->end = data + size;
-    bool ok = d->decode();
-    if (ok) {
-        d->to_rgb(rgb);
-        nx = d->width;
-        ny = d->height;
-    } else {
-        err = d->err.empty() ? "JPEG decode failed" : d->err;
-    }
+    const bool ok = d->decode();
+    if (ok) d->export_to(img);
+    else err = d->err.empty() ? "JPEG decode failed" : d->err;
     delete d;
     return ok;
+}
+
+void jpeg_pixel_stage(const JpegCoefImage & img, std::vector<uint8_t> & rgb) {
+    std::vector<uint8_t> plane[4];
+    idct_planes(img, plane);
+    to_rgb(img, plane, rgb);
+}
+
+// "device" only where the kernels provably give the host's pixels:
+//   * every scan ran to its end on bits of the file, and (baseline) every block that carries image samples was decoded — a block that no
+//     scan reached keeps samples of 0 on the host, which no IDCT of stored coefficients gives;
+//   * one or three components (grey, YCbCr, stored RGB); four-component files stay on the host;
+//   * every component is stretched by 1 or 2 in each direction (the filters of jpegmath::upsampled); other ratios stay on the host.
+// Coefficients beyond 16 bits (corrupt but decodable streams) need no rule: the kernel runs jpegmath::idct1d itself, wrap and
+// saturation included, on the same 16-bit values.
+int jpeg_plan(const JpegCoefImage & im) {
+    if (!im.complete) return JPEG_ROUTE_HOST;
+    if (im.ncomp != 1 && im.ncomp != 3) return JPEG_ROUTE_HOST;
+    if (im.colour != JPEG_GREY && im.colour != JPEG_YCC && im.colour != JPEG_RGB) return JPEG_ROUTE_HOST;
+    if (im.width <= 0 || im.height <= 0) return JPEG_ROUTE_HOST;
+    for (int i = 0; i < im.ncomp; i++) {
+        const JpegCoefPlane & c = im.comp[i];
+        if (c.h < 1 || c.v < 1 || im.hmax % c.h || im.vmax % c.v) return JPEG_ROUTE_HOST;
+        const int hs = im.hmax / c.h, vs = im.vmax / c.v;
+        if ((hs != 1 && hs != 2) || (vs != 1 && vs != 2)) return JPEG_ROUTE_HOST;
+        if (c.cw < 1 || c.ch < 1 || c.cw > c.bw || c.ch > c.bh || c.coef.size() != (size_t)c.bw * c.bh * 64) return JPEG_ROUTE_HOST;
+        if (!im.progressive) {
+            if (c.done.size() != (size_t)c.bw * c.bh) return JPEG_ROUTE_HOST;
+            for (int by = 0; by < c.ch; by++)
+                for (int bx = 0; bx < c.cw; bx++)
+                    if (!c.done[(size_t)by * c.bw + bx]) return JPEG_ROUTE_HOST;
+        }
+    }
+    return JPEG_ROUTE_DEVICE;
+}
+
+bool jpeg_build_tables(const JpegCoefImage * const * imgs, const long long * rgb_off, int n, JpegTables & t) {
+    t = JpegTables();
+    for (int i = 0; i < n; i++) {
+        const JpegCoefImage & im = *imgs[i];
+        if (jpeg_plan(im) != JPEG_ROUTE_DEVICE) return false;
+        JpegImgDesc d = {};
+        d.rgb_off = rgb_off[i];
+        d.width = im.width;
+        d.height = im.height;
+        d.colour = im.colour;
+        for (int k = 0; k < im.ncomp; k++) {
+            const JpegCoefPlane & c = im.comp[k];
+            JpegPlaneDesc pd;
+            pd.coef_off = (long long)t.coef_values;
+            pd.plane_off = (long long)t.plane_bytes;
+            pd.bw = c.bw;
+            pd.nblocks = c.bw * c.bh;
+            t.coef_values += (size_t)pd.nblocks * 64;
+            t.plane_bytes += (size_t)pd.nblocks * 64;
+            t.max_blocks = pd.nblocks > t.max_blocks ? pd.nblocks : t.max_blocks;
+            d.plane[k] = (int)t.planes.size();
+            d.hs[k] = im.hmax / c.h;
+            d.vs[k] = im.vmax / c.v;
+            d.wl[k] = (im.width + d.hs[k] - 1) / d.hs[k];
+            d.rows[k] = (im.height * c.v + im.vmax - 1) / im.vmax;
+            t.planes.push_back(pd);
+        }
+        const long long npix = (long long)im.width * im.height;
+        t.max_pixels = npix > t.max_pixels ? npix : t.max_pixels;
+        t.imgs.push_back(d);
+    }
+    return true;
+}
+
+bool jpeg_tables_in_bounds(const JpegTables & t, long long raw_lo, long long raw_hi) {
+    for (const JpegPlaneDesc & pd : t.planes) {
+        if (pd.bw < 1 || pd.nblocks < pd.bw || pd.nblocks % pd.bw || pd.nblocks > t.max_blocks) return false;
+        if (pd.coef_off < 0 || pd.coef_off % 8 || (size_t)pd.coef_off + (size_t)pd.nblocks * 64 > t.coef_values) return false;
+        if (pd.plane_off < 0 || pd.plane_off % 16 || (size_t)pd.plane_off + (size_t)pd.nblocks * 64 > t.plane_bytes) return false;
+    }
+    long long prev_end = raw_lo;
+    for (const JpegImgDesc & d : t.imgs) {
+        if (d.width < 1 || d.height < 1) return false;
+        const long long npix = (long long)d.width * d.height;
+        if (npix > t.max_pixels || d.rgb_off % 16 || d.rgb_off < prev_end || d.rgb_off + 3 * npix > raw_hi) return false;
+        prev_end = d.rgb_off + 3 * npix;
+        if (d.colour != JPEG_GREY && d.colour != JPEG_YCC && d.colour != JPEG_RGB) return false;
+        for (int k = 0; k < (d.colour == JPEG_GREY ? 1 : 3); k++) {
+            if (d.plane[k] < 0 || d.plane[k] >= (int)t.planes.size()) return false;
+            const JpegPlaneDesc & pd = t.planes[d.plane[k]];
+            const int pw = pd.bw * 8, ph = pd.nblocks / pd.bw * 8;
+            if ((d.hs[k] != 1 && d.hs[k] != 2) || (d.vs[k] != 1 && d.vs[k] != 2)) return false;
+            // the samples upsampled() touches: columns [0, wl), rows [0, rows); and x >> (hs - 1) < wl, j >> (vs - 1) < rows for every pixel
+            if (d.wl[k] < 1 || d.wl[k] > pw || d.rows[k] < 1 || d.rows[k] > ph) return false;
+            if ((d.width + d.hs[k] - 1) / d.hs[k] > d.wl[k] || (d.height + d.vs[k] - 1) / d.vs[k] > d.rows[k]) return false;
+        }
+    }
+    return true;
+}
+
+bool decode_jpeg(const uint8_t * data, size_t size, std::vector<uint8_t> & rgb, int & nx, int & ny, std::string & err) {
+    JpegCoefImage img;
+    if (!jpeg_entropy_stage(data, size, img, err)) return false;
+    jpeg_pixel_stage(img, rgb);
+    nx = img.width;
+    ny = img.height;
+    return true;
 }
 
 }  // namespace clipamd

@@ -8,6 +8,8 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "jpeg_stages.h"
+
 namespace clipamd {
 
 typedef _Float16 half_t;
@@ -274,6 +276,16 @@ struct PreImg {            // one per image
 struct PreTaps { long long w_off; int first_off, count_off, ksize; };   // weights [out][ksize] in wpool; first/count [out] in ipool
 void launch_preprocess(const uint8_t * raw, const PreImg * imgs, const PreTaps * taps, const double * wpool, const int * ipool, float * hbuf,
                        float * out, int n_imgs, int S, int max_rows, const float * mean, const float * stdv, hipStream_t stream);
+
+// GPU pixel half of the JPEG decoder (k_jpeg.hip; host twin and the shared arithmetic: jpeg_stages.h; reference clip.cpp:709-726 -> stbi_load):
+// dequantised coefficients -> u8 sample planes -> [ny][nx][3] u8 at raw + rgb_off, i.e. where launch_preprocess reads an image
+// (PreImg::src_off).  The tables (JpegPlaneDesc, JpegImgDesc: jpeg_stages.h) are built on the host from headers the entropy stage has
+// validated (jpeg_build_tables).
+// jpeg_idct_kernel: every 8x8 block of every plane; max_blocks = the largest nblocks
+void launch_jpeg_idct(const JpegPlaneDesc * planes_desc, int n_planes, int max_blocks, const int16_t * coef, uint8_t * planes, hipStream_t stream);
+// jpeg_rgb_kernel: every pixel of every image; max_pixels = the largest width*height
+void launch_jpeg_rgb(const JpegPlaneDesc * planes_desc, const JpegImgDesc * imgs, int n_imgs, long long max_pixels, const uint8_t * planes, uint8_t * raw,
+                     hipStream_t stream);
 
 // Zero-shot scoring: per image, softmax_with_sorting (reference clip.cpp:1591-1622) of its similarities with n text
 // embeddings.  img [B][dim], txt [n][dim] -> scores [B][n] (descending), indices [B][n].  false if n > 8192 or dim > 4096.

@@ -275,6 +275,19 @@ bool preprocess_image(const clip_ctx * ctx, const clip_image_u8 * img, clip_imag
 bool preprocess_batch_device(clip_ctx * ctx, const clip_image_u8 * imgs, int n, float * d_out, int slot = -1);   // preprocess.cpp + k_preproc.hip; slot 0 / 1: pipelined staging
 void free_preprocess_slots(clip_ctx * ctx);
 bool load_image_file(const char * fname, clip_image_u8 * img);                                      // image_io.cpp
+bool read_image_file(const char * fname, std::vector<uint8_t> & out);
+struct JpegCoefImage;                                                                               // jpeg_stages.h
+bool decode_image_bytes(const std::vector<uint8_t> & d, std::vector<uint8_t> & rgb, int & nx, int & ny, std::string & err, JpegCoefImage * staged,
+                        bool * is_staged);
+// One image of a device preprocessing batch: decoded pixels ([ny][nx][3] u8 at rgb), or a JPEG that stopped after its entropy stage
+// (jpeg != nullptr, planned "device"): its pixels are made on the GPU, in the place the pixels of the others are copied to.
+struct PreSrc { int nx = 0, ny = 0; const uint8_t * rgb = nullptr; const JpegCoefImage * jpeg = nullptr; };
+bool preprocess_sources_device(clip_ctx * ctx, const PreSrc * src, int n, float * d_out, int slot = -1);        // preprocess.cpp + k_jpeg.hip + k_preproc.hip
+long long jpeg_device_images();                                                                     // preprocess.cpp: device-planned JPEGs launched so far
+bool encode_sources_to_device(clip_ctx * ctx, const PreSrc * src, int n, float * d_out, bool normalize);        // api.cpp: the chunking of clip_amd_image_batch_encode_u8
+// files_pipeline.cpp: threaded decode of encoded images (paths, or data + sizes) + the above; the body of clip_amd_image_batch_encode_files / _memory
+int encode_encoded_images(clip_ctx * ctx, const char * const * paths, const uint8_t * const * data, const size_t * sizes, int n, int max_images,
+                          int n_threads, bool normalize, float * vec, int * consumed, uint8_t * ok, const char * who);
 
 // quant.cpp — host codecs for the ggml block formats
 void dequantize_row(int type, const void * src, float * dst, int64_t k);

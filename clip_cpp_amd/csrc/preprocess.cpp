@@ -6,6 +6,7 @@
 // reference so that results are bit-identical: accumulate in double over the taps in increasing
 // source index, round to float, clamp.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -140,6 +141,11 @@ bool preprocess_image(const clip_ctx * ctx, const clip_image_u8 * img, clip_imag
 // tables (one per distinct (source size, target size) pair), packs {descriptors, tables, raw u8 pixels} into one pinned
 // blob, ships it with a single H2D copy and launches the two passes.  d_out: [n][S][S][3] f32 in HBM.
 // ---------------------------------------------------------------------------------------------
+// JPEGs whose pixel half was launched on the device since the process started (clip_amd_test_jpeg_device_count): the rows are the same
+// on both routes, so only a count can show that the device route was taken
+static std::atomic<long long> g_jpeg_device_images(0);
+long long jpeg_device_images() { return g_jpeg_device_images.load(); }
+
 void free_preprocess_slots(clip_ctx * ctx) {
     for (auto & sl : ctx->pre_slot) {
         if (sl.pin) (void)hipHostFree(sl.pin);
@@ -158,6 +164,15 @@ void free_preprocess_slots(clip_ctx * ctx) {
 // pass), and the only waits are events (this slot's previous H2D before the host overwrites the pinned blob; its previous kernels before
 // the copy overwrites the device blob).  d_out regions of one buffer: the kernels writing them are stream-ordered behind the forward reading it.
 bool preprocess_batch_device(clip_ctx * ctx, const clip_image_u8 * imgs, int n, float * d_out, int slot) {
+    std::vector<PreSrc> src((size_t)std::max(n, 0));
+    for (int i = 0; i < n; i++) { src[i].nx = imgs[i].nx; src[i].ny = imgs[i].ny; src[i].rgb = imgs[i].data; }
+    return preprocess_sources_device(ctx, src.data(), n, d_out, slot);
+}
+
+// The same for sources of two kinds (model.h PreSrc).  A device-planned JPEG adds its coefficients and descriptor tables to the uploaded
+// blob; jpeg_idct_kernel and jpeg_rgb_kernel (k_jpeg.hip) then write its pixels into a device-only region that its PreImg::src_off names,
+// ahead of the preprocessing kernels on the same stream.
+bool preprocess_sources_device(clip_ctx * ctx, const PreSrc * imgs, int n, float * d_out, int slot) {
     if (!ctx->has_vision_encoder) {
         printf("This gguf file seems to have no vision encoder\n");
         return false;
@@ -192,11 +207,14 @@ bool preprocess_batch_device(clip_ctx * ctx, const clip_image_u8 * imgs, int n, 
         seen[{in_size, out_size}] = idx;
         return idx;
     };
-    size_t raw_bytes = 0, hbuf_floats = 0;
+    size_t raw_bytes = 0, rawj_bytes = 0, hbuf_floats = 0;
     int max_rows = 0;
+    std::vector<const JpegCoefImage *> jimgs;     // the device-planned JPEGs of this batch, in order ...
+    std::vector<long long> joff;                  // ... and where their pixels go, relative to the start of the device-only pixel region
+    std::vector<int> jidx((size_t)n, -1);         // image -> its place among them, -1 for decoded pixels
     for (int i = 0; i < n; i++) {
-        const clip_image_u8 & im = imgs[i];
-        if (im.nx <= 0 || im.ny <= 0 || !im.data) {
+        const PreSrc & im = imgs[i];
+        if (im.nx <= 0 || im.ny <= 0 || (!im.rgb && !im.jpeg) || (im.jpeg && (im.jpeg->width != im.nx || im.jpeg->height != im.ny))) {
             fprintf(stderr, "clip_amd_image_batch_preprocess_device: image %d is empty\n", i);
             return false;
         }
@@ -217,16 +235,45 @@ bool preprocess_batch_device(clip_ctx * ctx, const clip_image_u8 * imgs, int n, 
         for (int o = d.y0; o < d.y0 + S; o++) yhi = std::max(yhi, tv.first[o] + tv.count[o]);
         d.nrows = yhi - d.ylo;
         max_rows = std::max(max_rows, d.nrows);
-        d.src_off = (long long)raw_bytes;
-        raw_bytes += ((size_t)3 * im.nx * im.ny + 15) & ~(size_t)15;
+        const size_t pix_bytes = ((size_t)3 * im.nx * im.ny + 15) & ~(size_t)15;
+        if (im.jpeg) {
+            jimgs.push_back(im.jpeg);
+            joff.push_back((long long)rawj_bytes);
+            jidx[i] = (int)jimgs.size() - 1;
+            rawj_bytes += pix_bytes;
+        } else {
+            d.src_off = (long long)raw_bytes;
+            raw_bytes += pix_bytes;
+        }
         d.hbuf_off = (long long)hbuf_floats;
         hbuf_floats += (size_t)d.nrows * S * 3;
     }
-    // blob layout (all 16-byte aligned): descriptors | directory | ipool | wpool | raw pixels ; then (device only) hbuf
+    // blob layout (all 16-byte aligned): descriptors | directory | ipool | wpool | raw pixels | JPEG plane table | JPEG image table | JPEG
+    // coefficients ; then (device only) hbuf | pixels of the device-planned JPEGs | their sample planes
     auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t o_desc = 0, o_dir = up(o_desc + desc.size() * sizeof(PreImg)), o_ip = up(o_dir + dir.size() * sizeof(PreTaps));
     const size_t o_wp = up(o_ip + ipool.size() * sizeof(int)), o_raw = up(o_wp + wpool.size() * sizeof(double));
-    const size_t host_bytes = up(o_raw + raw_bytes), total = host_bytes + hbuf_floats * sizeof(float);
+    JpegTables jt;
+    size_t o_jp = up(o_raw + raw_bytes), o_ji = o_jp, o_coef = o_jp, host_bytes = o_jp;
+    if (!jimgs.empty()) {
+        if (!jpeg_build_tables(jimgs.data(), joff.data(), (int)jimgs.size(), jt)) {
+            fprintf(stderr, "clip (hip): a JPEG that is not planned for the device reached the device pixel stage\n");
+            return false;
+        }
+        o_ji = up(o_jp + jt.planes.size() * sizeof(JpegPlaneDesc));
+        o_coef = up(o_ji + jt.imgs.size() * sizeof(JpegImgDesc));
+        host_bytes = up(o_coef + jt.coef_values * sizeof(int16_t));
+    }
+    const size_t o_rawj = up(host_bytes + hbuf_floats * sizeof(float)), o_planes = o_rawj + rawj_bytes, total = o_planes + jt.plane_bytes;
+    for (int i = 0; i < n; i++) {                       // offsets relative to `raw` (= blob + o_raw), as every PreImg::src_off
+        if (jidx[i] < 0) continue;
+        desc[i].src_off = (long long)(o_rawj - o_raw) + joff[jidx[i]];
+        jt.imgs[jidx[i]].rgb_off = desc[i].src_off;
+    }
+    if (!jimgs.empty() && !jpeg_tables_in_bounds(jt, (long long)(o_rawj - o_raw), (long long)(o_planes - o_raw))) {
+        fprintf(stderr, "clip (hip): JPEG descriptor tables leave their buffers\n");
+        return false;
+    }
     (void)hipSetDevice(ctx->device);
     uint8_t * h = nullptr, * dv = nullptr;
     clip_ctx::PreSlot * sl = slot >= 0 ? &ctx->pre_slot[slot % clip_ctx::PRE_SLOTS] : nullptr;
@@ -272,13 +319,24 @@ bool preprocess_batch_device(clip_ctx * ctx, const clip_image_u8 * imgs, int n, 
     memcpy(h + o_dir, dir.data(), dir.size() * sizeof(PreTaps));
     memcpy(h + o_ip, ipool.data(), ipool.size() * sizeof(int));
     memcpy(h + o_wp, wpool.data(), wpool.size() * sizeof(double));
+    if (!jimgs.empty()) {
+        memcpy(h + o_jp, jt.planes.data(), jt.planes.size() * sizeof(JpegPlaneDesc));
+        memcpy(h + o_ji, jt.imgs.data(), jt.imgs.size() * sizeof(JpegImgDesc));
+    }
     {
         static const int max_thr = [] { const char * e = getenv("CLIP_AMD_U8_THREADS"); const int v = e ? atoi(e) : 8; return v < 1 ? 1 : v > 64 ? 64 : v; }();
         const int nthr = std::max(1, std::min(max_thr, n));     // the pixel copy into pinned memory is the host cost of this path
         std::vector<std::thread> pool;
         for (int t = 0; t < nthr; t++)
             pool.emplace_back([&, t]() {
-                for (int i = t; i < n; i += nthr) memcpy(h + o_raw + desc[i].src_off, imgs[i].data, (size_t)3 * imgs[i].nx * imgs[i].ny);
+                for (int i = t; i < n; i += nthr) {
+                    if (!imgs[i].jpeg) { memcpy(h + o_raw + desc[i].src_off, imgs[i].rgb, (size_t)3 * imgs[i].nx * imgs[i].ny); continue; }
+                    const JpegImgDesc & jd = jt.imgs[jidx[i]];
+                    for (int c = 0; c < imgs[i].jpeg->ncomp; c++) {
+                        const JpegPlaneDesc & pd = jt.planes[jd.plane[c]];
+                        memcpy(h + o_coef + (size_t)pd.coef_off * sizeof(int16_t), imgs[i].jpeg->comp[c].coef.data(), (size_t)pd.nblocks * 64 * sizeof(int16_t));
+                    }
+                }
             });
         for (auto & th : pool) th.join();
     }
@@ -289,6 +347,12 @@ bool preprocess_batch_device(clip_ctx * ctx, const clip_image_u8 * imgs, int n, 
         if (sl->used && hipStreamWaitEvent(cs, sl->ev_done, 0) != hipSuccess) return false;      // the kernels that read this device blob two chunks ago
         if (hipMemcpyAsync(dv, h, host_bytes, hipMemcpyHostToDevice, cs) != hipSuccess) return false;
         if (hipEventRecord(sl->ev_h2d, cs) != hipSuccess || hipStreamWaitEvent(ctx->stream, sl->ev_h2d, 0) != hipSuccess) return false;
+    }
+    if (!jimgs.empty()) {
+        const JpegPlaneDesc * d_planes = (const JpegPlaneDesc *)(dv + o_jp);
+        launch_jpeg_idct(d_planes, (int)jt.planes.size(), jt.max_blocks, (const int16_t *)(dv + o_coef), dv + o_planes, ctx->stream);
+        launch_jpeg_rgb(d_planes, (const JpegImgDesc *)(dv + o_ji), (int)jt.imgs.size(), jt.max_pixels, dv + o_planes, dv + o_raw, ctx->stream);
+        g_jpeg_device_images += (long long)jt.imgs.size();
     }
     launch_preprocess(dv + o_raw, (const PreImg *)(dv + o_desc), (const PreTaps *)(dv + o_dir), (const double *)(dv + o_wp), (const int *)(dv + o_ip),
                       (float *)(dv + host_bytes), d_out, n, S, max_rows, ctx->image_mean, ctx->image_std, ctx->stream);

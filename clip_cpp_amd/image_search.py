@@ -201,7 +201,7 @@ def _help(build, p, dedup=False, update=False, neighbors=False, label=False, mer
         print("  -h, --help: Show this message and exit")
         print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default. When the database is rewritten, the"
               " given path replaces the one stored on the first line of images.paths: later commands load this model.")
-        print("  -t N, --threads N: Number of threads to use for inference. Default: %d" % p["threads"])
+        print("  -t N, --threads N: Number of host threads that read and decode the image files. Default: %d" % p["threads"])
         print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
         print("  --db <dir>: directory holding %s and %s; both are written under temporary names and renamed into place. Default: %s"
               % (INDEX_FILE, PATHS_FILE, p["db"]))
@@ -210,7 +210,7 @@ def _help(build, p, dedup=False, update=False, neighbors=False, label=False, mer
         print("\nOptions:")
         print("  -h, --help: Show this message and exit")
         print("  -m <path>, --model <path>: path to model. Default: %s" % p["model"])
-        print("  -t N, --threads N: Number of threads to use for inference. Default: %d" % p["threads"])
+        print("  -t N, --threads N: Number of host threads that read and decode the image files. Default: %d" % p["threads"])
         print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
         print("  --db <dir>: directory that receives %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
         print("  --dtype f16|f32|i8: stored precision of the index (i8: int8 rows, half of f16's memory). Default: %s" % p["dtype"])
@@ -293,38 +293,44 @@ def _write_db(p, index, paths):
 
 def _encode_dirs(clip, L, index, p, paths, scans=None):
     """Decode and encode the image files of the directories p["rest"] in batches and append them to `index` and `paths`.  scans: the
-    [(dir, files)] to take when the caller has scanned already (`update`), else every file found under each dir."""
-    def flush(batch):
-        if not batch:
-            return
-        try:
-            index.add(_encode_batch(clip, L, [im for _, im in batch]))
-            paths.extend(path for path, _ in batch)
-        finally:
-            for _, im in batch:
-                L.clip_image_u8_free(im)
-            batch.clear()
-        if p["verbose"] == 1:
-            print(".", end="", flush=True)
-
-    batch = []
+    [(dir, files)] to take when the caller has scanned already (`update`), else every file found under each dir.
+    The files of all directories form one list that goes through Clip.encode_image_files in windows of BATCH loadable images:
+    p["threads"] host threads read and decode (the GPU does the JPEG pixel work unless CLIP_AMD_JPEG_DEVICE=0), and every encoder call
+    sees BATCH consecutive loadable images, across directory boundaries too.  The directories are scanned first and each is announced
+    when its first file is reported, so the lines come out in the order of a file-by-file pass; the list is prepared for the library
+    once (Clip.ImageFileList), each call starts where the last one stopped and no file is decoded twice."""
+    stream, heads = [], []                            # heads: (index of the directory's first file in stream, dir, files, scanned here)
     for base, files in scans if scans is not None else [(base, None) for base in p["rest"]]:
-        if files is None:
-            print("main: starting base dir scan of '%s'" % base, flush=True)
-            files = image_files(base)
-        print("\nmain: processing %d files in '%s'" % (len(files), base), flush=True)
-        for path in files:
+        heads.append((len(stream), base, image_files(base) if files is None else files, files is None))
+        stream.extend(heads[-1][2])
+
+    def announce(upto):
+        while heads and heads[0][0] <= upto:
+            _, base, files, here = heads.pop(0)
+            if here:
+                print("main: starting base dir scan of '%s'" % base, flush=True)
+            print("\nmain: processing %d files in '%s'" % (len(files), base), flush=True)
+
+    prepared, pos = clip.ImageFileList(stream), 0
+    while pos < len(stream):
+        vecs, ok, consumed = clip.encode_image_files(prepared, normalize=True, n_threads=p["threads"], max_images=BATCH, start=pos)
+        if consumed <= 0:
+            break
+        window = stream[pos:pos + consumed]
+        for i, (path, good) in enumerate(zip(window, ok)):
+            announce(pos + i)
             if p["verbose"] >= 2:
                 print("main: found image file '%s'" % path, flush=True)
-            im = L.clip_image_u8_make()
-            if not L.clip_image_load_from_file(os.fsencode(path), im):
-                L.clip_image_u8_free(im)
-                _err("main: failed to load image from '%s'" % path)
-                continue           # (no slot: the failed file gets no id and no line in images.paths)
-            batch.append((path, im))
-            if len(batch) == BATCH:
-                flush(batch)
-    flush(batch)
+            if not good:
+                _err("main: failed to load image from '%s'" % path)      # (no slot: the failed file gets no id and no line in images.paths)
+        pos += consumed
+        loaded = [path for path, good in zip(window, ok) if good]
+        if loaded:
+            index.add(vecs)
+            paths.extend(loaded)
+            if p["verbose"] == 1:
+                print(".", end="", flush=True)
+    announce(len(stream))
 
 
 def reconcile(old_paths, found, exists=os.path.exists):

@@ -99,6 +99,24 @@ bool clip_amd_image_batch_preprocess_device(struct clip_ctx * ctx, const struct 
  * vec: [n][projection_dim] on the host.  Same results as the two-step host path. */
 bool clip_amd_image_batch_encode_u8(struct clip_ctx * ctx, const struct clip_image_u8 * imgs, int n, float * vec, bool normalize);
 
+/* Encoded images in, embeddings out.  The files are read and decoded on n_threads host threads (every format clip_image_load_from_file
+ * reads).  Only the entropy decoding of a JPEG stays on those threads: its IDCT, chroma up-sampling and colour conversion run on the GPU,
+ * where that provably gives the host decoder's pixels.  CLIP_AMD_JPEG_DEVICE=0 keeps them on the host threads as well (same rows); the
+ * comparison that made the device the default: profiles/files_bench.txt.  The rows are bit-identical to
+ * clip_image_load_from_file + ONE clip_amd_image_batch_encode_u8 call over the loadable images.
+ *
+ * Encode the first max_images loadable files of paths[0..n): returns the number of rows written to vec ([rows][proj], in path order),
+ * -1 on a device or argument error. *consumed = paths looked at; ok[i] (i < *consumed) = 1 when path i produced a row.  When some of the
+ * first max_images paths do not load, as many further paths as are missing are looked at, until max_images have loaded or the list ends:
+ * walking a long list with paths + consumed gives max_images consecutive loadable images per call.  vec holds max_images rows, ok n
+ * entries; host memory grows with max_images (every decoded image of a call is held until it is encoded).  Not for
+ * clip_amd_model_load_multi contexts. */
+int clip_amd_image_batch_encode_files(struct clip_ctx * ctx, const char * const * paths, int n, int max_images, int n_threads,
+                                      bool normalize, float * vec, int * consumed, uint8_t * ok);
+/* the same for encoded images held in memory (uploads, archives): data[i], sizes[i] */
+int clip_amd_image_batch_encode_memory(struct clip_ctx * ctx, const uint8_t * const * data, const size_t * sizes, int n, int max_images,
+                                       int n_threads, bool normalize, float * vec, int * consumed, uint8_t * ok);
+
 /* Batched text encoding ("next" row §8f-2; per-text semantics identical to
  * clip_text_encode, reference clip.cpp:1016-1233).  Texts are ragged:
  * tokens[i].data holds tokens[i].size ids incl. BOS/EOS.  vec: [n_texts][projection_dim]. */
@@ -365,6 +383,19 @@ int clip_amd_test_layernorm_prep(const float * x, int ldx, const float * w, cons
  *   op 5 f16_to_f32: in0 [rows][lds] fp16; n0 = rows, n1 = cols, n3 = lds, n4 = ldd; out0 [rows][ldd] f32 */
 int clip_amd_test_rows(int op, const void * in0, const void * in1, const int32_t * idx, int64_t n0, int64_t n1, int64_t n2, int64_t n3, int64_t n4,
                        void * out0, void * out1);
+/* The JPEG decoder's stages.  plan: runs the entropy stage on the host and says where the pixel stage may run; needs no device.  Returns 1 for a
+ * decodable JPEG, else 0.  info[16]: route (0 host, 1 device), width, height, number of components, progressive, colour rule (0 grey,
+ * 1 YCbCr, 2 stored RGB, 3 CMYK, 4 YCCK, 5 YCbCr + ignored channel), every scan complete, then (h, v) sampling factors per component. */
+int clip_amd_test_jpeg_plan(const uint8_t * data, size_t size, int * info);
+/* JPEGs whose pixel half clip_amd_image_batch_encode_files / _memory have run on the device since the process started (the rows do not tell). */
+long long clip_amd_test_jpeg_device_count(void);
+/* decode_device: the entropy stage, then jpeg_idct_kernel and jpeg_rgb_kernel, then the [ny][nx][3] block copied into rgb (cap bytes).
+ * 0 ok; -1 no device; -2 not a JPEG, or one that is planned "host": refused, no kernel runs; -3 bad arguments / cap too small;
+ * -4 kernel error; -5 a byte behind the pixels was written. */
+int clip_amd_test_jpeg_decode_device(const uint8_t * data, size_t size, uint8_t * rgb, size_t cap, int * nx, int * ny);
+/* Median HIP-event times (ms[0] jpeg_idct_kernel, ms[1] jpeg_rgb_kernel) over reps runs on `copies` copies of one device-planned JPEG, and
+ * the bytes each kernel must move per run (bytes[0], bytes[1]).  Return codes as above.  Used by scripts/files_bench.py. */
+int clip_amd_bench_jpeg_kernels(const uint8_t * data, size_t size, int copies, int reps, float * ms, double * bytes);
 /* Multi-head attention over nseq sequences of length T each: qkv [nseq*T][3h] (q pre-scaled), out [nseq*T][h]. */
 int clip_amd_test_attention(const float * qkv, int nseq, int T, int h, int n_head, int causal, float * out);
 /* ... with the kernel chosen: 0 = automatic (what the layers run), 1 = the whole-row kernel (d_head 64: T <= 592, other head sizes:

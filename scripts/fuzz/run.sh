@@ -10,10 +10,11 @@ W=${FUZZ_DIR:-/tmp/clip_amd_fuzz}; IT=${1:-2000}; SEED=${2:-1}
 CL=/opt/rocm/lib/llvm/bin/clang++
 FL="-std=c++17 -g -O1 -fwrapv -fPIC -fsanitize=address,undefined -fno-sanitize-recover=undefined -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I$ROOT/include -I$ROOT/clip_cpp_amd/csrc"
 mkdir -p "$W/obj" "$W/seeds"
-for f in gguf quant load forward tokenizer preprocess image_io image_formats jpeg_decode host_pipeline api; do
+for f in gguf quant load forward tokenizer preprocess image_io image_formats jpeg_decode host_pipeline files_pipeline api; do
     $CL $FL -c "$ROOT/clip_cpp_amd/csrc/$f.cpp" -o "$W/obj/$f.o" &
 done; wait
 $CL $FL "$ROOT/scripts/fuzz/fuzz_images.cpp" "$W/obj/image_io.o" "$W/obj/image_formats.o" "$W/obj/jpeg_decode.o" -lz -o "$W/fuzz_images"
+$CL $FL "$ROOT/scripts/fuzz/jpeg_stage_check.cpp" "$W/obj/jpeg_decode.o" -o "$W/jpeg_stage_check"
 $CL $FL "$ROOT/scripts/fuzz/fuzz_model.cpp" "$W"/obj/*.o $(ls "$ROOT"/clip_cpp_amd/build/*.o | grep -E "/k_") -L/opt/rocm/lib -lamdhip64 -lz -lpthread -ldl -Wl,-rpath,/opt/rocm/lib -o "$W/fuzz_model"
 python3 - "$W/seeds" <<'PY'
 import sys, numpy as np, PIL.Image as I
@@ -50,6 +51,24 @@ open(d + "/z.psd", "wb").write(b"8BPS" + struct.pack(">H6xHIIHH", 1, 4, 37, 53, 
 PY
 export ASAN_OPTIONS=detect_leaks=0:allocator_may_return_null=1:max_allocation_size_mb=4096
 "$W/fuzz_images" "$IT" "$W/t.bin" "$SEED" "$W"/seeds/* 2>&1 | grep -E "runtime error|ERROR|SUMMARY|decoded$|#[0-9]" | tail -20
+# the JPEG decoder's stages: the same mutation cut over the JPEG seeds plus small files of every sampling layout and edge size (partial MCUs,
+# one-sample rows, the last-row clamp), where the device plan and the kernels' closed-form addressing are compared with the host pixel stage
+mkdir -p "$W/jseeds"
+python3 - "$W/jseeds" <<'PY'
+import sys, numpy as np, PIL.Image as I
+d = sys.argv[1]; rng = np.random.default_rng(2)
+k = 0
+for (h, w) in [(1, 1), (8, 8), (7, 9), (16, 16), (17, 13), (33, 31), (2, 65), (65, 2)]:
+    im = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    for kw in [dict(subsampling=0), dict(subsampling=1), dict(subsampling=2), dict(subsampling=2, progressive=True), dict(subsampling=1, restart_marker_blocks=1)]:
+        I.fromarray(im).save("%s/s%03d.jpg" % (d, k), quality=80, **kw); k += 1
+    I.fromarray(im).convert("L").save("%s/s%03d.jpg" % (d, k), quality=80); k += 1
+    # 4:4:0 (luma 1x2), which PIL does not write: a 4:2:2 file with the sampling byte changed and width / height exchanged in its frame header
+    b = bytearray(open("%s/s%03d.jpg" % (d, k - 5), "rb").read()); i = b.find(b"\xff\xc0")
+    b[i + 5:i + 7], b[i + 7:i + 9] = bytes(b[i + 7:i + 9]), bytes(b[i + 5:i + 7]); b[i + 11] = 0x12
+    open("%s/s%03d.jpg" % (d, k), "wb").write(bytes(b)); k += 1
+PY
+"$W/jpeg_stage_check" "$(( IT / 4 + 1 ))" "$SEED" "$W"/seeds/*.jpg "$W"/jseeds/*.jpg 2>&1 | grep -E "runtime error|ERROR|SUMMARY|closed form$|#[0-9]" | tail -20
 CACHE=${CLIP_AMD_FIXTURE_CACHE:-/tmp/clip_amd_fixtures}
 PYTHONPATH="$ROOT" python3 -c "from oracle import fixtures as f; [f.cached_model('$CACHE', 'tiny', t, text=tx, vision=True) for t, tx in (('q4_1', False), ('f32', False), ('q4_1', True))]"
 "$W/fuzz_model" "$IT" "$W/m.gguf" "$SEED" "$CACHE"/tiny_q4_1_v_s1234.gguf "$CACHE"/tiny_f32_v_s1234.gguf "$CACHE"/tiny_q4_1_tv_s1234.gguf 2>&1 | grep -E "runtime error|ERROR|SUMMARY|loaded$|#[0-9]" | tail -20
