@@ -79,6 +79,9 @@ AMD_SYMBOLS = [
     "clip_amd_index_search_index", "clip_amd_index_append", "clip_amd_test_index_cross_route", "clip_amd_bench_cross",
     "clip_amd_image_batch_encode_files", "clip_amd_image_batch_encode_memory", "clip_amd_test_jpeg_plan", "clip_amd_test_jpeg_decode_device",
     "clip_amd_bench_jpeg_kernels", "clip_amd_test_jpeg_device_count",
+    "clip_amd_index_search_grouped", "clip_amd_index_search_grouped_device", "clip_amd_bench_search_grouped",
+    "clip_amd_image_batch_encode_regions", "clip_amd_image_batch_preprocess_regions_device", "clip_amd_image_batch_encode_files_grid",
+    "clip_amd_image_batch_encode_memory_grid",
 ]
 
 _lib = None
@@ -254,6 +257,12 @@ def lib():
     L.clip_amd_index_search_subset_device.argtypes = [vp, vp, i32, i32, vp, vp, vp]
     L.clip_amd_index_range_search_subset.restype = i64
     L.clip_amd_index_range_search_subset.argtypes = [vp, f32p, i32, C.c_float, u64p, i64p, f32p, i64p, i64]
+    L.clip_amd_index_search_grouped.restype = C.c_bool
+    L.clip_amd_index_search_grouped.argtypes = [vp, f32p, i32, i32, C.POINTER(C.c_int32), u64p, f32p, i64p]
+    L.clip_amd_index_search_grouped_device.restype = C.c_bool
+    L.clip_amd_index_search_grouped_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
+    L.clip_amd_bench_search_grouped.restype = C.c_float
+    L.clip_amd_bench_search_grouped.argtypes = [i32, i64, i32, i32, i32, i32, i32]
     L.clip_amd_bench_search_subset.restype = C.c_float
     L.clip_amd_bench_search_subset.argtypes = [i32, i64, i32, i32, i32, C.c_float, i32, i32]
     L.clip_amd_index_search_ids.restype = C.c_bool
@@ -277,6 +286,15 @@ def lib():
     u8p, szp = C.POINTER(C.c_uint8), C.POINTER(C.c_size_t)
     L.clip_amd_image_batch_encode_files.restype = i32
     L.clip_amd_image_batch_encode_files.argtypes = [vp, C.POINTER(C.c_char_p), i32, i32, i32, C.c_bool, f32p, C.POINTER(i32), u8p]
+    i32p = C.POINTER(C.c_int32)
+    L.clip_amd_image_batch_encode_regions.restype = C.c_bool
+    L.clip_amd_image_batch_encode_regions.argtypes = [vp, C.POINTER(ClipImageU8), i32, i32p, i32, f32p, C.c_bool]
+    L.clip_amd_image_batch_preprocess_regions_device.restype = C.c_bool
+    L.clip_amd_image_batch_preprocess_regions_device.argtypes = [vp, C.POINTER(ClipImageU8), i32, i32p, i32, vp]
+    L.clip_amd_image_batch_encode_files_grid.restype = i32
+    L.clip_amd_image_batch_encode_files_grid.argtypes = [vp, C.POINTER(C.c_char_p), i32, i32, i32, i32, C.c_bool, f32p, i32p, C.POINTER(i32), u8p]
+    L.clip_amd_image_batch_encode_memory_grid.restype = i32
+    L.clip_amd_image_batch_encode_memory_grid.argtypes = [vp, C.POINTER(C.c_char_p), szp, i32, i32, i32, i32, C.c_bool, f32p, i32p, C.POINTER(i32), u8p]
     L.clip_amd_image_batch_encode_memory.restype = i32
     L.clip_amd_image_batch_encode_memory.argtypes = [vp, C.POINTER(C.c_char_p), szp, i32, i32, i32, C.c_bool, f32p, C.POINTER(i32), u8p]
     L.clip_amd_test_jpeg_plan.restype = i32
@@ -441,6 +459,33 @@ class Clip:
             raise RuntimeError("clip_amd_image_batch_encode_u8 failed (see stderr)")
         return out
 
+    @staticmethod
+    def _boxes_array(boxes):
+        b = np.ascontiguousarray(np.asarray(boxes, dtype=np.int64).reshape(-1, 5))
+        if b.size and (int(b.min()) < -2 ** 31 or int(b.max()) > 2 ** 31 - 1):
+            raise ValueError("a box value does not fit 32 bits")
+        return np.ascontiguousarray(b, dtype=np.int32)
+
+    def encode_image_regions(self, images, boxes, normalize=True):
+        """Boxes of raw images -> float32 [n_boxes, proj]: images is a list of uint8 [ny,nx,3] arrays, boxes an int array [n_boxes, 5] =
+        image number, x, y, w, h (inside the image, w, h >= 1, any order, an image any number of times).  Row b is, bit for bit, row b of
+        encode_images_u8 over the host crops images[i][y:y+h, x:x+w]; each image is uploaded once per staging piece, not once per box
+        (clip_amd_image_batch_encode_regions)."""
+        keep, arr, n = self._u8_array(images)
+        b = self._boxes_array(boxes)
+        out = np.empty((len(b), self.vision_config["projection_dim"]), dtype=np.float32)
+        if not lib().clip_amd_image_batch_encode_regions(self.ctx, arr, n, b.ctypes.data_as(C.POINTER(C.c_int32)), len(b), _fp(out), normalize):
+            raise RuntimeError("clip_amd_image_batch_encode_regions failed (see stderr)")
+        return out
+
+    def preprocess_regions_device(self, images, boxes, d_out_ptr):
+        """preprocess_device for boxes of the images (boxes as encode_image_regions): [n_boxes,S,S,3] float32 at device address d_out_ptr"""
+        keep, arr, n = self._u8_array(images)
+        b = self._boxes_array(boxes)
+        if not lib().clip_amd_image_batch_preprocess_regions_device(self.ctx, arr, n, b.ctypes.data_as(C.POINTER(C.c_int32)), len(b), C.c_void_p(d_out_ptr)):
+            raise RuntimeError("clip_amd_image_batch_preprocess_regions_device failed (see stderr)")
+        self.synchronize()
+
     class ImageFileList:
         """Paths prepared once for repeated Clip.encode_image_files(..., start=pos) calls over one long list: the encoded names and the
         C arrays are built here, each call then costs what its window costs."""
@@ -454,37 +499,54 @@ class Clip:
         def __len__(self):
             return self.n
 
-    def _encode_encoded(self, call, arr, sizes, ok, n, normalize, n_threads, max_images):
+    def _encode_encoded(self, call, arr, sizes, ok, n, normalize, n_threads, max_images, grid=1, grid_call=None):
         cap = n if max_images is None else max(0, min(int(max_images), n))
-        out = np.empty((cap, self.vision_config["projection_dim"]), dtype=np.float32)
+        grid = int(grid)
+        if grid < 1 or grid > 8:
+            raise ValueError("grid must be 1 ... 8, not %d" % grid)
+        R = 1 if grid == 1 else 1 + grid * grid
+        out = np.empty((cap * R, self.vision_config["projection_dim"]), dtype=np.float32)
         consumed = C.c_int(0)
         if n == 0 or cap == 0:
-            return out[:0], ok[:0].astype(bool), 0
+            return (out[:0], ok[:0].astype(bool), 0) + ((np.zeros((0, 4), dtype=np.int32),) if grid > 1 else ())
         args = (arr,) if sizes is None else (arr, sizes)
-        rows = call(self.ctx, *args, n, cap, int(n_threads), normalize, _fp(out), C.byref(consumed), ok.ctypes.data_as(C.POINTER(C.c_uint8)))
-        if rows < 0:
-            raise RuntimeError("%s failed (see stderr)" % call.__name__)
-        return out[:rows], ok[:consumed.value].astype(bool), consumed.value
+        if grid == 1:
+            rows = call(self.ctx, *args, n, cap, int(n_threads), normalize, _fp(out), C.byref(consumed), ok.ctypes.data_as(C.POINTER(C.c_uint8)))
+            if rows < 0:
+                raise RuntimeError("%s failed (see stderr)" % call.__name__)
+            return out[:rows], ok[:consumed.value].astype(bool), consumed.value
+        boxes = np.zeros((cap * R, 4), dtype=np.int32)
+        imgs = grid_call(self.ctx, *args, n, cap, int(n_threads), grid, normalize, _fp(out), boxes.ctypes.data_as(C.POINTER(C.c_int32)),
+                         C.byref(consumed), ok.ctypes.data_as(C.POINTER(C.c_uint8)))
+        if imgs < 0:
+            raise RuntimeError("%s failed (see stderr)" % grid_call.__name__)
+        return out[:imgs * R], ok[:consumed.value].astype(bool), consumed.value, boxes[:imgs * R]
 
-    def encode_image_files(self, paths, normalize=True, n_threads=4, max_images=None, start=0):
+    def encode_image_files(self, paths, normalize=True, n_threads=4, max_images=None, start=0, grid=1):
         """Image files -> (embeddings float32 [rows, proj], ok bool [consumed], consumed): the files are read and decoded on n_threads host
         threads, in every format clip_image_load_from_file reads, and the loadable ones encoded as ONE batch, bit-identical to
         clip_image_load_from_file + encode_images_u8.  Only a JPEG's entropy decoding stays on those threads: its IDCT / up-sampling / colour
         conversion run on the GPU (CLIP_AMD_JPEG_DEVICE=0 in the environment: on the host threads as well; same rows).  max_images: stop after that many loadable files; `consumed` paths were looked at, ok[i] says whether path i
         produced a row (clip_amd_image_batch_encode_files).  paths: a list, or a Clip.ImageFileList with `start` = the first path to
-        look at, for walking a long list in windows without preparing the rest of it again for every call."""
+        look at, for walking a long list in windows without preparing the rest of it again for every call.
+        grid = G > 1 (up to 8): every loadable image gives 1 + G * G consecutive rows, the whole image and then the tiles of grid_boxes(nx,
+        ny, G), and a fourth value is returned: boxes int32 [rows, 4] = x, y, w, h of every row.  max_images, ok and consumed keep counting
+        images; an image with a side shorter than G counts as not loadable.  Bit-identical to loading each file and one
+        encode_image_regions call over those boxes; a JPEG decoded on the GPU is decoded once for all its regions."""
         fl = paths if isinstance(paths, Clip.ImageFileList) else Clip.ImageFileList(paths)
         start = max(0, min(int(start), fl.n))
         arr = C.cast(C.byref(fl.arr, start * C.sizeof(C.c_char_p)), C.POINTER(C.c_char_p))
-        return self._encode_encoded(lib().clip_amd_image_batch_encode_files, arr, None, fl.ok[start:], fl.n - start, normalize, n_threads, max_images)
+        return self._encode_encoded(lib().clip_amd_image_batch_encode_files, arr, None, fl.ok[start:], fl.n - start, normalize, n_threads, max_images,
+                                    grid, lib().clip_amd_image_batch_encode_files_grid)
 
-    def encode_image_bytes(self, blobs, normalize=True, n_threads=4, max_images=None):
-        """The same for encoded images held in memory (a list of bytes objects): clip_amd_image_batch_encode_memory."""
+    def encode_image_bytes(self, blobs, normalize=True, n_threads=4, max_images=None, grid=1):
+        """The same for encoded images held in memory (a list of bytes objects): clip_amd_image_batch_encode_memory[_grid]."""
         blobs = [bytes(b) for b in blobs]
         n = len(blobs)
         arr = (C.c_char_p * max(n, 1))(*blobs)
         sizes = (C.c_size_t * max(n, 1))(*[len(b) for b in blobs])
-        return self._encode_encoded(lib().clip_amd_image_batch_encode_memory, arr, sizes, np.zeros(max(n, 1), dtype=np.uint8)[:n], n, normalize, n_threads, max_images)
+        return self._encode_encoded(lib().clip_amd_image_batch_encode_memory, arr, sizes, np.zeros(max(n, 1), dtype=np.uint8)[:n], n, normalize, n_threads, max_images,
+                                    grid, lib().clip_amd_image_batch_encode_memory_grid)
 
     def zero_shot_label_images(self, images, labels):
         """Batched clip_zero_shot_label_image on the GPU: list of uint8 [ny,nx,3] images x list of label strings ->
@@ -621,6 +683,25 @@ class Clip:
             pass
 
 
+def grid_boxes(nx, ny, G):
+    """int32 [R, 4] = x, y, w, h: the regions of an nx x ny image under a grid of G (1 ... 8), as clip_amd_image_batch_encode_files_grid
+    makes them: the whole image alone for G = 1, else the whole image and then tile (i, j) = x in [i nx // G, (i + 1) nx // G), y in
+    [j ny // G, (j + 1) ny // G), j outer and i inner (R = 1 + G * G).  ValueError for G outside 1 ... 8 or an image with a side shorter
+    than G.  Pure arithmetic: needs no device."""
+    nx, ny, G = int(nx), int(ny), int(G)
+    if G < 1 or G > 8:
+        raise ValueError("grid must be 1 ... 8, not %d" % G)
+    if nx < 1 or ny < 1 or (G > 1 and min(nx, ny) < G):
+        raise ValueError("a %dx%d image is too small for a grid of %d" % (nx, ny, G))
+    rows = [(0, 0, nx, ny)]
+    if G > 1:
+        for j in range(G):
+            for i in range(G):
+                x, y = i * nx // G, j * ny // G
+                rows.append((x, y, (i + 1) * nx // G - x, (j + 1) * ny // G - y))
+    return np.array(rows, dtype=np.int32)
+
+
 def allow_words(allow, n):
     """The uint64 words [(n + 63) // 64] of an allowed set over ids 0 ... n - 1 (the layout of clip_amd_index_search_subset: bit id & 63 of
     word id >> 6): `allow` is a bool array of length n or an integer array of ids (any order, duplicates allowed).  ValueError for a bool
@@ -669,7 +750,11 @@ class Index:
     search_index(src, k) searches this index with the stored rows of another one of the same Clip, dim and dtype (every row, or `ids` of
     them): row t of the result is what search gives for the vector that was added to `src` as that row, bit for bit.  append(src) copies
     src's rows, bit for bit, to the end of this index.  Neither needs the vectors that were added, or a model; `src` must hold no removed
-    rows (compact() it first)."""
+    rows (compact() it first).
+
+    search_grouped(queries, k, groups) ranks groups of rows instead of rows (several crops of one image, ranked by image): `groups` names
+    every row's group and a result holds each group at most once, represented by its best row.  Groups are an argument of the call, not
+    state of the index."""
 
     DTYPES = {"f32": 0, "f16": 1, "i8": 3}
 
@@ -758,6 +843,38 @@ class Index:
         if not lib().clip_amd_index_search_subset(self._live(), _fp(q), nq, int(k), wp, _fp(dist), ids.ctypes.data_as(C.POINTER(C.c_int64))):
             raise RuntimeError("clip_amd_index_search%s failed (see stderr)" % ("" if allow is None else "_subset"))
         return dist, ids
+
+    def search_grouped(self, queries, k, groups, allow=None):
+        """search with each group at most once in a result: `groups` (int [len], each >= 0) is every row's group, any numbering.  With L the
+        eligible rows in search's order, a query's result is the rows of L whose group has not appeared earlier in L, cut to k: (distances
+        f32 [nq, k], ids int64 [nq, k]) hold the best row of each of the k best groups and that row's distance, the bits `search` reports
+        for it; -1 / +inf where there are fewer groups.  All groups distinct: search's result.  ValueError for a wrong length or a
+        negative group."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        nq = q.shape[0]
+        g = np.asarray(groups)
+        if g.size and not np.issubdtype(g.dtype, np.integer):
+            raise ValueError("groups must be integers, not %s" % g.dtype)
+        g = g.reshape(-1)
+        if g.size != len(self):
+            raise ValueError("groups must have one entry per row: %d, not %d" % (len(self), g.size))
+        if g.size and (int(g.min()) < 0 or int(g.max()) > 2 ** 31 - 1):
+            raise ValueError("groups must lie in 0 ... 2^31 - 1")
+        g = np.zeros(g.size + 1, dtype=np.int32)[:g.size] if g.size == 0 else np.ascontiguousarray(g, dtype=np.int32)
+        words, wp = self._allow(allow)
+        dist = np.empty((nq, k), dtype=np.float32)
+        ids = np.empty((nq, k), dtype=np.int64)
+        if not lib().clip_amd_index_search_grouped(self._live(), _fp(q), nq, int(k), g.ctypes.data_as(C.POINTER(C.c_int32)), wp, _fp(dist),
+                                                   ids.ctypes.data_as(C.POINTER(C.c_int64))):
+            raise RuntimeError("clip_amd_index_search_grouped failed (see stderr)")
+        return dist, ids
+
+    def search_grouped_device(self, d_queries, n_queries, k, d_groups, d_allow, d_distances, d_ids):
+        """search_grouped on device pointers (ints): queries [n, dim] f32, groups [len] int32 (trusted: each >= 0), d_allow uint64 words
+        (0 / None: every row) -> distances [n, k] f32, ids [n, k] int64; asynchronous on the context's stream."""
+        if not lib().clip_amd_index_search_grouped_device(self._live(), C.c_void_p(d_queries), int(n_queries), int(k), C.c_void_p(d_groups or None),
+                                                          C.c_void_p(d_allow or None), C.c_void_p(d_distances), C.c_void_p(d_ids)):
+            raise RuntimeError("clip_amd_index_search_grouped_device failed (see stderr)")
 
     def range_search(self, queries, radius, allow=None):
         """Every stored row within `radius` of each query (distance <= radius in f32, the distance `search` reports): (lims int64 [nq + 1],
@@ -885,6 +1002,12 @@ class Index:
 def bench_search(dtype, n, dim, n_queries, k, iters=10):
     """Microseconds per clip_amd_index_search_device on seeded random data (clip_amd_bench_search); < 0 on error."""
     return float(lib().clip_amd_bench_search(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(k), int(iters)))
+
+
+def bench_search_grouped(dtype, n, dim, n_queries, k, group_size, iters=10):
+    """Microseconds per clip_amd_index_search_grouped_device on the data of bench_search, row r in group r // group_size
+    (clip_amd_bench_search_grouped); < 0 on error."""
+    return float(lib().clip_amd_bench_search_grouped(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(k), int(group_size), int(iters)))
 
 
 def bench_search_subset(dtype, n, dim, n_queries, k, allowed_fraction, contiguous, iters=10):

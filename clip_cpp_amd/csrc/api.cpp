@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <set>
 #include <thread>
 #include <vector>
 
@@ -230,7 +231,9 @@ bool clip_amd_image_batch_preprocess_device(struct clip_ctx * ctx, const struct 
 // resampling (the dominant host cost of benchmark.cpp / zsl.cpp style callers) off the CPU.
 // n raw images -> d_out [n][proj] on ctx's device, queued on ctx->stream.
 // (the images as PreSrc: decoded pixels, or JPEGs whose pixel half runs on the device — clip_amd_image_batch_encode_files; both kinds count
-// 3 bytes per pixel towards the chunk limits, so a list of files is cut into the same forward batches as its decoded pixels)
+// 3 bytes per pixel towards the chunk limits, so a list of files is cut into the same forward batches as its decoded pixels; a row that
+// is a box of its source counts the box's pixels, so a list of regions is cut into the same forward batches as its host crops.  Rows of
+// one staging piece that share a source, PreSrc::src_id, upload it once; a piece boundary inside them uploads it in both pieces)
 bool clipamd::encode_sources_to_device(clip_ctx * ctx, const PreSrc * imgs, int n, float * d_out, bool normalize) {
     const int S = ctx->vision_hparams.image_size, proj = ctx->vision_hparams.projection_dim;
     const size_t per = (size_t)S * S * 3;
@@ -248,7 +251,7 @@ bool clipamd::encode_sources_to_device(clip_ctx * ctx, const PreSrc * imgs, int 
         int bc = 0;
         size_t bytes = 0;
         while (b0 + bc < n && bc < 256 && (bc == 0 || bytes < ((size_t)512 << 20))) {
-            bytes += (size_t)3 * (size_t)std::max(0, imgs[b0 + bc].nx) * (size_t)std::max(0, imgs[b0 + bc].ny);
+            bytes += (size_t)3 * (size_t)std::max(0, imgs[b0 + bc].out_nx()) * (size_t)std::max(0, imgs[b0 + bc].out_ny());
             bc++;
         }
         if (!ensure_io(ctx, per * 4 * std::min(n, 256), 16)) {
@@ -256,10 +259,14 @@ bool clipamd::encode_sources_to_device(clip_ctx * ctx, const PreSrc * imgs, int 
             return false;
         }
         for (int p0 = 0; p0 < bc && ok;) {
+            // (the piece budget counts what a piece uploads: every distinct source once, whole, however small its boxes are; only the
+            // forward chunks above must follow the host crops, the piece split does not change a bit)
             int pn = 0;
             size_t pbytes = 0;
+            std::set<int> in_piece;
             while (p0 + pn < bc && pn < (pipelined ? piece_max : bc) && (pn == 0 || pbytes < ((size_t)128 << 20))) {
-                pbytes += (size_t)3 * (size_t)std::max(0, imgs[b0 + p0 + pn].nx) * (size_t)std::max(0, imgs[b0 + p0 + pn].ny);
+                const PreSrc & s = imgs[b0 + p0 + pn];
+                if (s.src_id < 0 || in_piece.insert(s.src_id).second) pbytes += (size_t)3 * (size_t)std::max(0, s.nx) * (size_t)std::max(0, s.ny);
                 pn++;
             }
             ok = ok && preprocess_sources_device(ctx, imgs + b0 + p0, pn, (float *)ctx->io_in + (size_t)p0 * per, pipelined ? piece_idx : -1);
@@ -311,6 +318,72 @@ bool clip_amd_image_batch_encode_u8(struct clip_ctx * ctx, const struct clip_ima
     return ok;
 } catch (const std::exception & e) { fprintf(stderr, "clip_amd_image_batch_encode_u8: %s\n", e.what()); return false; } catch (...) { fprintf(stderr, "clip_amd_image_batch_encode_u8: unknown exception\n"); return false; }
 
+// boxes [n_boxes][5] = image, x, y, w, h over imgs -> one PreSrc per box (src_id = the image); false with a message naming the first bad box
+static bool regions_to_sources(const char * who, const clip_image_u8 * imgs, int n_imgs, const int32_t * boxes, int n_boxes, std::vector<PreSrc> & src) {
+    if (n_boxes < 0 || n_imgs < 0 || (n_boxes > 0 && (!boxes || !imgs))) {
+        fprintf(stderr, "%s: bad arguments (%d images%s, %d boxes%s)\n", who, n_imgs, imgs ? "" : " at NULL", n_boxes, boxes ? "" : " at NULL");
+        return false;
+    }
+    src.resize((size_t)n_boxes);
+    for (int b = 0; b < n_boxes; b++) {
+        const int32_t * bx = boxes + (size_t)5 * b;
+        if (bx[0] < 0 || bx[0] >= n_imgs) { fprintf(stderr, "%s: box %d names image %d of %d\n", who, b, (int)bx[0], n_imgs); return false; }
+        const clip_image_u8 & im = imgs[bx[0]];
+        if (im.nx <= 0 || im.ny <= 0 || !im.data) { fprintf(stderr, "%s: box %d names image %d, which is empty\n", who, b, (int)bx[0]); return false; }
+        if (bx[3] < 1 || bx[4] < 1 || bx[1] < 0 || bx[2] < 0 || bx[1] > im.nx - bx[3] || bx[2] > im.ny - bx[4]) {
+            fprintf(stderr, "%s: box %d (x %d, y %d, %dx%d) is empty or leaves image %d (%dx%d)\n", who, b, (int)bx[1], (int)bx[2], (int)bx[3], (int)bx[4], (int)bx[0], im.nx, im.ny);
+            return false;
+        }
+        PreSrc & s = src[(size_t)b];
+        s.nx = im.nx; s.ny = im.ny; s.rgb = im.data;
+        s.bx = bx[1]; s.by = bx[2]; s.bw = bx[3]; s.bh = bx[4];
+        s.src_id = bx[0];
+    }
+    return true;
+}
+
+static bool regions_ctx_ok(const char * who, const clip_ctx * ctx) {
+    if (!ctx) { fprintf(stderr, "%s: ctx is NULL\n", who); return false; }
+    if (!ctx->has_vision_encoder) { printf("This gguf file seems to have no vision encoder\n"); return false; }
+    if (ctx->device < 0) { fprintf(stderr, "%s: no HIP device bound to this context — the encoders have no CPU fallback\n", who); return false; }
+    return true;
+}
+
+bool clip_amd_image_batch_preprocess_regions_device(struct clip_ctx * ctx, const struct clip_image_u8 * imgs, int n_imgs, const int32_t * boxes,
+                                                    int n_boxes, float * d_out) try {
+    RelaxCapture relax_capture;     // (model.h: this thread may allocate while another thread of the process captures)
+    const char * who = "clip_amd_image_batch_preprocess_regions_device";
+    std::vector<PreSrc> src;
+    if (!regions_ctx_ok(who, ctx) || !regions_to_sources(who, imgs, n_imgs, boxes, n_boxes, src)) return false;
+    if (n_boxes == 0) return true;
+    if (!d_out) { fprintf(stderr, "%s: d_out is NULL\n", who); return false; }
+    return preprocess_sources_device(ctx, src.data(), n_boxes, d_out);
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_image_batch_preprocess_regions_device: %s\n", e.what()); return false; } catch (...) { fprintf(stderr, "clip_amd_image_batch_preprocess_regions_device: unknown exception\n"); return false; }
+
+bool clip_amd_image_batch_encode_regions(struct clip_ctx * ctx, const struct clip_image_u8 * imgs, int n_imgs, const int32_t * boxes, int n_boxes,
+                                         float * vec, bool normalize) try {
+    RelaxCapture relax_capture;     // (model.h: this thread may allocate while another thread of the process captures)
+    const char * who = "clip_amd_image_batch_encode_regions";
+    std::vector<PreSrc> src;
+    if (!regions_ctx_ok(who, ctx)) return false;
+    if (ctx->multi) {
+        fprintf(stderr, "%s: not available on a clip_amd_model_load_multi context (crop on the host and shard the pixels with clip_amd_image_batch_encode_u8)\n", who);
+        return false;
+    }
+    if (!regions_to_sources(who, imgs, n_imgs, boxes, n_boxes, src)) return false;
+    if (n_boxes == 0) return true;
+    if (!vec) { fprintf(stderr, "%s: vec is NULL\n", who); return false; }
+    const int proj = ctx->vision_hparams.projection_dim;
+    (void)hipSetDevice(ctx->device);
+    bool ok = ensure_io(ctx, 16, (size_t)proj * 4 * n_boxes);
+    ok = ok && encode_sources_to_device(ctx, src.data(), n_boxes, (float *)ctx->io_out, normalize);
+    ok = ok && hipMemcpyAsync(vec, ctx->io_out, (size_t)proj * 4 * n_boxes, hipMemcpyDeviceToHost, ctx->stream) == hipSuccess;
+    ok = hipStreamSynchronize(ctx->stream) == hipSuccess && ok;
+    if (!ok) fprintf(stderr, "%s: failed (%s)\n", who, hipGetErrorString(hipGetLastError()));
+    if (ctx->profiling) prof_collect(ctx);
+    return ok;
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_image_batch_encode_regions: %s\n", e.what()); return false; } catch (...) { fprintf(stderr, "clip_amd_image_batch_encode_regions: unknown exception\n"); return false; }
+
 // encoded images (files, or buffers in memory) -> embeddings: threaded decode, JPEG pixel half on the GPU (files_pipeline.cpp)
 int clip_amd_image_batch_encode_files(struct clip_ctx * ctx, const char * const * paths, int n, int max_images, int n_threads, bool normalize, float * vec,
                                       int * consumed, uint8_t * ok) try {
@@ -324,6 +397,24 @@ int clip_amd_image_batch_encode_memory(struct clip_ctx * ctx, const uint8_t * co
     if (n > 0 && (!data || !sizes)) { fprintf(stderr, "clip_amd_image_batch_encode_memory: bad arguments\n"); return -1; }
     return encode_encoded_images(ctx, nullptr, data, sizes, n, max_images, n_threads, normalize, vec, consumed, ok, "clip_amd_image_batch_encode_memory");
 } catch (const std::exception & e) { fprintf(stderr, "clip_amd_image_batch_encode_memory: %s\n", e.what()); return -1; } catch (...) { fprintf(stderr, "clip_amd_image_batch_encode_memory: unknown exception\n"); return -1; }
+
+// The same with a grid of regions per image (files_pipeline.cpp): 1 + grid^2 rows per loadable image; returns the IMAGES that loaded
+int clip_amd_image_batch_encode_files_grid(struct clip_ctx * ctx, const char * const * paths, int n, int max_images, int n_threads, int grid,
+                                           bool normalize, float * vec, int32_t * boxes_out, int * consumed, uint8_t * ok) try {
+    RelaxCapture relax_capture;     // (model.h: this thread may allocate while another thread of the process captures)
+    if (n > 0 && !paths) { fprintf(stderr, "clip_amd_image_batch_encode_files_grid: bad arguments\n"); return -1; }
+    if (grid < 1 || grid > 8) { fprintf(stderr, "clip_amd_image_batch_encode_files_grid: grid = %d outside 1 ... 8\n", grid); if (consumed) *consumed = 0; return -1; }
+    return encode_encoded_images(ctx, paths, nullptr, nullptr, n, max_images, n_threads, normalize, vec, consumed, ok, "clip_amd_image_batch_encode_files_grid",
+                                 grid, boxes_out);
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_image_batch_encode_files_grid: %s\n", e.what()); return -1; } catch (...) { fprintf(stderr, "clip_amd_image_batch_encode_files_grid: unknown exception\n"); return -1; }
+int clip_amd_image_batch_encode_memory_grid(struct clip_ctx * ctx, const uint8_t * const * data, const size_t * sizes, int n, int max_images,
+                                            int n_threads, int grid, bool normalize, float * vec, int32_t * boxes_out, int * consumed, uint8_t * ok) try {
+    RelaxCapture relax_capture;     // (model.h: this thread may allocate while another thread of the process captures)
+    if (n > 0 && (!data || !sizes)) { fprintf(stderr, "clip_amd_image_batch_encode_memory_grid: bad arguments\n"); return -1; }
+    if (grid < 1 || grid > 8) { fprintf(stderr, "clip_amd_image_batch_encode_memory_grid: grid = %d outside 1 ... 8\n", grid); if (consumed) *consumed = 0; return -1; }
+    return encode_encoded_images(ctx, nullptr, data, sizes, n, max_images, n_threads, normalize, vec, consumed, ok, "clip_amd_image_batch_encode_memory_grid",
+                                 grid, boxes_out);
+} catch (const std::exception & e) { fprintf(stderr, "clip_amd_image_batch_encode_memory_grid: %s\n", e.what()); return -1; } catch (...) { fprintf(stderr, "clip_amd_image_batch_encode_memory_grid: unknown exception\n"); return -1; }
 
 // Device-resident sharded image encode on a clip_amd_model_load_multi context (the measured form of SURVEY 8e: bench.py --single-process).
 // d_imgs[g]: the preprocessed f32 images of shard g ([hi - lo][S][S][3], clip_amd_shard_bounds(total, G, g)) ON device g.

@@ -7,6 +7,9 @@
 // build uses -ffp-contract=off, and HIP's f32 division is correctly rounded), so the results match bit for bit.
 // Only what the centre crop needs is computed: S output columns of the horizontal pass and the source rows the S output
 // rows of the vertical pass touch.  HBM-bound on the u8 source (3 B/pixel read once).
+// A box of an uploaded image is the same computation with the box's origin in src_off, the box's size in nx / ny and the image's width
+// as the row stride: the taps are those of a (box size -> target size) resize, so a filter's support stops at the box edge exactly as it
+// stops at an image edge, and nothing outside the box is read.
 #include "kernels.h"
 
 namespace clipamd {
@@ -26,7 +29,7 @@ __global__ void __launch_bounds__(256) preproc_h_kernel(const uint8_t * raw, con
     const int o = im.x0 + xo;
     const double * k = wpool + t.w_off + (size_t)o * t.ksize;
     const int lo = ipool[t.first_off + o], n = ipool[t.count_off + o];
-    const uint8_t * srow = raw + im.src_off + (size_t)3 * (im.ylo + r) * im.nx + (size_t)3 * lo;
+    const uint8_t * srow = raw + im.src_off + (size_t)3 * (im.ylo + r) * im.stride + (size_t)3 * lo;
     double a0 = 0.0, a1 = 0.0, a2 = 0.0;
     for (int x = 0; x < n; x++) {
         const double w = k[x];

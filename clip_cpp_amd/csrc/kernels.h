@@ -265,13 +265,15 @@ void launch_l2norm(const float * v, float * out, int rows, int n, bool normalize
 // GPU image preprocessing (k_preproc.hip; reference clip.cpp:728-1008): separable antialiased bicubic resize of the
 // shorter side to S, centre crop, normalise.  Tap tables come from the host (preprocess.cpp) so that the result is
 // bit-identical to the host path.
-struct PreImg {            // one per image
-    long long src_off;     // byte offset of the [ny][nx][3] u8 pixels in `raw`
-    int nx, ny;            // source size
+struct PreImg {            // one per output image: a whole source image or a box of one
+    long long src_off;     // byte offset in `raw` of the first u8 pixel of the [ny] rows of [nx][3] (a box: its top-left pixel)
+    int nx, ny;            // size of what is resized: the image, or the box
     int x0, y0;            // crop origin in the resized image
     int ylo, nrows;        // first source row the vertical pass needs / number of such rows
     long long hbuf_off;    // float offset of this image's horizontal-pass rows [nrows][S][3] in `hbuf`
     int th, tv;            // tap-table indices (horizontal, vertical)
+    int stride;            // pixels from one source row to the next: nx for a whole image, the image's width for a box of it
+    int reserved;
 };
 struct PreTaps { long long w_off; int first_off, count_off, ksize; };   // weights [out][ksize] in wpool; first/count [out] in ipool
 void launch_preprocess(const uint8_t * raw, const PreImg * imgs, const PreTaps * taps, const double * wpool, const int * ipool, float * hbuf,
@@ -323,6 +325,13 @@ bool launch_search_scan(const void * rows, const float * rinv, int64_t n, int Dp
                         int k, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask, const int * qself, hipStream_t stream);
 void launch_search_merge(const void * in, int64_t in_stride, int n_in, void * out, int nq, int k, hipStream_t stream);
 void launch_search_finish(const void * in, int64_t in_stride, int nq, int k, float * dist, int64_t * ids, const int * qself, hipStream_t stream);
+// Grouped search (k_group.hip): groups [n] (device, each >= 0) names every row's group; the scan leaves, per (chunk, query), the best row of
+// each of the chunk's best k distinct groups, sorted, in the layout of launch_search_scan (same cand workspace, chunks and mask), and the
+// merge runs the same selection over two lists.  launch_search_finish ends the tree.
+bool launch_search_scan_grouped(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq,
+                                int qt, int k, const int * groups, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask,
+                                hipStream_t stream);
+void launch_search_merge_grouped(const void * in, int64_t in_stride, int n_in, void * out, int nq, int k, const int * groups, hipStream_t stream);
 // Searches by id.  gather: query t of n_rows (the padded count) := stored row ids[t] (device; NULL: row first + t) for t < n_ids, bit for bit
 // (i8: qinv[t] := rinv of that row), qself[t] := that id; an id outside [0, n) or with a cleared bit in live, and every t >= n_ids, gives the
 // zero row and qself -1.  launch_search_scan with qself != NULL never makes row qself[query] a candidate of that query; launch_search_finish

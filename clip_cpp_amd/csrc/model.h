@@ -281,13 +281,23 @@ bool decode_image_bytes(const std::vector<uint8_t> & d, std::vector<uint8_t> & r
                         bool * is_staged);
 // One image of a device preprocessing batch: decoded pixels ([ny][nx][3] u8 at rgb), or a JPEG that stopped after its entropy stage
 // (jpeg != nullptr, planned "device"): its pixels are made on the GPU, in the place the pixels of the others are copied to.
-struct PreSrc { int nx = 0, ny = 0; const uint8_t * rgb = nullptr; const JpegCoefImage * jpeg = nullptr; };
+struct PreSrc {
+    int nx = 0, ny = 0; const uint8_t * rgb = nullptr; const JpegCoefImage * jpeg = nullptr;
+    // Regions (clip_amd_image_batch_encode_regions): the row is the box [bx, bx + bw) x [by, by + bh) of the source; bw == 0: the whole
+    // source.  Entries of one preprocess_sources_device call with the same src_id >= 0 name the same source, whose pixels (or JPEG
+    // coefficients) are uploaded (decoded) once for all of them; -1: a source of its own.
+    int bx = 0, by = 0, bw = 0, bh = 0;
+    int src_id = -1;
+    int out_nx() const { return bw ? bw : nx; }
+    int out_ny() const { return bw ? bh : ny; }
+};
 bool preprocess_sources_device(clip_ctx * ctx, const PreSrc * src, int n, float * d_out, int slot = -1);        // preprocess.cpp + k_jpeg.hip + k_preproc.hip
 long long jpeg_device_images();                                                                     // preprocess.cpp: device-planned JPEGs launched so far
 bool encode_sources_to_device(clip_ctx * ctx, const PreSrc * src, int n, float * d_out, bool normalize);        // api.cpp: the chunking of clip_amd_image_batch_encode_u8
 // files_pipeline.cpp: threaded decode of encoded images (paths, or data + sizes) + the above; the body of clip_amd_image_batch_encode_files / _memory
 int encode_encoded_images(clip_ctx * ctx, const char * const * paths, const uint8_t * const * data, const size_t * sizes, int n, int max_images,
-                          int n_threads, bool normalize, float * vec, int * consumed, uint8_t * ok, const char * who);
+                          int n_threads, bool normalize, float * vec, int * consumed, uint8_t * ok, const char * who, int grid = 0,
+                          int32_t * boxes_out = nullptr);      // grid >= 1: the _grid forms (1 + grid^2 rows per image from 2 on, boxes_out [rows][4])
 
 // quant.cpp — host codecs for the ggml block formats
 void dequantize_row(int type, const void * src, float * dst, int64_t k);

@@ -172,6 +172,9 @@ bool preprocess_batch_device(clip_ctx * ctx, const clip_image_u8 * imgs, int n, 
 // The same for sources of two kinds (model.h PreSrc).  A device-planned JPEG adds its coefficients and descriptor tables to the uploaded
 // blob; jpeg_idct_kernel and jpeg_rgb_kernel (k_jpeg.hip) then write its pixels into a device-only region that its PreImg::src_off names,
 // ahead of the preprocessing kernels on the same stream.
+// A row may be a box of its source (PreSrc::bw != 0) and rows may share a source (PreSrc::src_id): the source is placed in the blob once,
+// by the first row that names it, and every row's descriptor points into it (origin of the box, the source's width as the row stride).
+// Tap tables, the rows of the horizontal pass and the hbuf accounting are per row, from the box's size.
 bool preprocess_sources_device(clip_ctx * ctx, const PreSrc * imgs, int n, float * d_out, int slot) {
     if (!ctx->has_vision_encoder) {
         printf("This gguf file seems to have no vision encoder\n");
@@ -211,24 +214,45 @@ bool preprocess_sources_device(clip_ctx * ctx, const PreSrc * imgs, int n, float
     int max_rows = 0;
     std::vector<const JpegCoefImage *> jimgs;     // the device-planned JPEGs of this batch, in order ...
     std::vector<long long> joff;                  // ... and where their pixels go, relative to the start of the device-only pixel region
-    std::vector<int> jidx((size_t)n, -1);         // image -> its place among them, -1 for decoded pixels
+    std::vector<int> jidx((size_t)n, -1);         // row -> its source's place among them, -1 for decoded pixels
+    std::vector<long long> src_base((size_t)n, 0); // row that places decoded pixels -> their offset in `raw`
+    std::vector<int> owner((size_t)n);            // row -> the first row of this call with the same source (itself: it places the source)
+    std::map<int, int> first_of;                  // src_id -> that row
     for (int i = 0; i < n; i++) {
         const PreSrc & im = imgs[i];
         if (im.nx <= 0 || im.ny <= 0 || (!im.rgb && !im.jpeg) || (im.jpeg && (im.jpeg->width != im.nx || im.jpeg->height != im.ny))) {
             fprintf(stderr, "clip_amd_image_batch_preprocess_device: image %d is empty\n", i);
             return false;
         }
-        const float scale = std::min((float)im.nx, (float)im.ny) / (float)S;   // same arithmetic as preprocess_image above
-        const int rx = (int)(im.nx / scale + 0.5f), ry = (int)(im.ny / scale + 0.5f);
+        const int bnx = im.out_nx(), bny = im.out_ny();
+        if (im.bw && (im.bx < 0 || im.by < 0 || im.bw < 1 || im.bh < 1 || im.bx > im.nx - im.bw || im.by > im.ny - im.bh)) {
+            fprintf(stderr, "clip_amd_image_batch_preprocess_device: row %d: box %d,%d %dx%d leaves its %dx%d image\n", i, im.bx, im.by, im.bw, im.bh, im.nx, im.ny);
+            return false;
+        }
+        owner[i] = i;
+        if (im.src_id >= 0) {
+            auto f = first_of.find(im.src_id);
+            if (f == first_of.end()) first_of[im.src_id] = i;
+            else owner[i] = f->second;
+            const PreSrc & o = imgs[owner[i]];
+            if (o.nx != im.nx || o.ny != im.ny || o.rgb != im.rgb || o.jpeg != im.jpeg) {
+                fprintf(stderr, "clip_amd_image_batch_preprocess_device: rows %d and %d name source %d differently\n", owner[i], i, im.src_id);
+                return false;
+            }
+        }
+        const float scale = std::min((float)bnx, (float)bny) / (float)S;   // same arithmetic as preprocess_image above
+        const int rx = (int)(bnx / scale + 0.5f), ry = (int)(bny / scale + 0.5f);
         if (rx < S || ry < S) {
-            fprintf(stderr, "clip_amd_image_batch_preprocess_device: image %d (%dx%d) resizes below %d\n", i, im.nx, im.ny, S);
+            fprintf(stderr, "clip_amd_image_batch_preprocess_device: image %d (%dx%d) resizes below %d\n", i, bnx, bny, S);
             return false;
         }
         PreImg & d = desc[i];
-        d.nx = im.nx; d.ny = im.ny;
+        d.nx = bnx; d.ny = bny;
+        d.stride = im.nx;
+        d.reserved = 0;
         d.x0 = (rx - S) / 2; d.y0 = (ry - S) / 2;
-        d.th = table(im.nx, rx);
-        d.tv = table(im.ny, ry);
+        d.th = table(bnx, rx);
+        d.tv = table(bny, ry);
         const Taps & tv = tabs[d.tv];
         d.ylo = tv.first[d.y0];
         int yhi = 0;
@@ -236,13 +260,18 @@ bool preprocess_sources_device(clip_ctx * ctx, const PreSrc * imgs, int n, float
         d.nrows = yhi - d.ylo;
         max_rows = std::max(max_rows, d.nrows);
         const size_t pix_bytes = ((size_t)3 * im.nx * im.ny + 15) & ~(size_t)15;
-        if (im.jpeg) {
+        const long long box_off = (long long)3 * ((long long)im.by * im.nx + im.bx);      // the box's first pixel inside its source
+        if (owner[i] != i) {                                   // the source is in the blob already
+            jidx[i] = jidx[owner[i]];
+            if (!im.jpeg) d.src_off = src_base[owner[i]] + box_off;
+        } else if (im.jpeg) {
             jimgs.push_back(im.jpeg);
             joff.push_back((long long)rawj_bytes);
             jidx[i] = (int)jimgs.size() - 1;
             rawj_bytes += pix_bytes;
         } else {
-            d.src_off = (long long)raw_bytes;
+            src_base[i] = (long long)raw_bytes;
+            d.src_off = src_base[i] + box_off;
             raw_bytes += pix_bytes;
         }
         d.hbuf_off = (long long)hbuf_floats;
@@ -267,8 +296,9 @@ bool preprocess_sources_device(clip_ctx * ctx, const PreSrc * imgs, int n, float
     const size_t o_rawj = up(host_bytes + hbuf_floats * sizeof(float)), o_planes = o_rawj + rawj_bytes, total = o_planes + jt.plane_bytes;
     for (int i = 0; i < n; i++) {                       // offsets relative to `raw` (= blob + o_raw), as every PreImg::src_off
         if (jidx[i] < 0) continue;
-        desc[i].src_off = (long long)(o_rawj - o_raw) + joff[jidx[i]];
-        jt.imgs[jidx[i]].rgb_off = desc[i].src_off;
+        const long long base = (long long)(o_rawj - o_raw) + joff[jidx[i]];
+        desc[i].src_off = base + (long long)3 * ((long long)imgs[i].by * imgs[i].nx + imgs[i].bx);
+        jt.imgs[jidx[i]].rgb_off = base;
     }
     if (!jimgs.empty() && !jpeg_tables_in_bounds(jt, (long long)(o_rawj - o_raw), (long long)(o_planes - o_raw))) {
         fprintf(stderr, "clip (hip): JPEG descriptor tables leave their buffers\n");
@@ -330,7 +360,8 @@ bool preprocess_sources_device(clip_ctx * ctx, const PreSrc * imgs, int n, float
         for (int t = 0; t < nthr; t++)
             pool.emplace_back([&, t]() {
                 for (int i = t; i < n; i += nthr) {
-                    if (!imgs[i].jpeg) { memcpy(h + o_raw + desc[i].src_off, imgs[i].rgb, (size_t)3 * imgs[i].nx * imgs[i].ny); continue; }
+                    if (owner[i] != i) continue;
+                    if (!imgs[i].jpeg) { memcpy(h + o_raw + src_base[i], imgs[i].rgb, (size_t)3 * imgs[i].nx * imgs[i].ny); continue; }   // (the source's place, not the row's box)
                     const JpegImgDesc & jd = jt.imgs[jidx[i]];
                     for (int c = 0; c < imgs[i].jpeg->ncomp; c++) {
                         const JpegPlaneDesc & pd = jt.planes[jd.plane[c]];

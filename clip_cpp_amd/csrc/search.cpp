@@ -59,6 +59,7 @@ struct clip_amd_index {
     Buf outs;                      // distances + ids of the host search form / of one query block of the k-NN graph
     Buf idbuf;                     // ids of a search by id copied from the host
     Buf qself;                     // searches by id: [nq_pad] the stored row each query is, -1 for a flagged one
+    Buf gbuf;                      // groups of a grouped search copied from the host
     int knn_route = 0;             // clip_amd_test_index_knn_route: 0 automatic, 1 scan, 2 tiled
     int cross_route = 0;           // clip_amd_test_index_cross_route: the same for clip_amd_index_search_index
     // range search / pairs
@@ -271,8 +272,9 @@ bool gather_queries(clip_amd_index * ix, const QuerySource & src, int q0, int64_
     return true;
 }
 
-// the merge tree over the chunks' lists of m queries and the finish into d_dist / d_ids ([m][k])
-bool merge_and_finish(clip_amd_index * ix, int n_chunks, int m, int k, const int * qself, float * d_dist, int64_t * d_ids) {
+// the merge tree over the chunks' lists of m queries and the finish into d_dist / d_ids ([m][k]); d_groups: the grouped merge of k_group.hip
+bool merge_and_finish(clip_amd_index * ix, int n_chunks, int m, int k, const int * qself, float * d_dist, int64_t * d_ids,
+                      const int * d_groups = nullptr) {
     hipStream_t st = stream_of(ix);
     const size_t mb = (size_t)((n_chunks + 1) / 2) * m * k * 8;
     if (n_chunks > 1 && (!ensure(ix, ix->mbuf[0], mb) || !ensure(ix, ix->mbuf[1], mb))) return false;
@@ -280,7 +282,8 @@ bool merge_and_finish(clip_amd_index * ix, int n_chunks, int m, int k, const int
     int64_t stride = search_candidate_capacity(k);
     int lists = n_chunks, t = 0;
     while (lists > 1) {
-        launch_search_merge(in, stride, lists, ix->mbuf[t].p, m, k, st);
+        if (d_groups) launch_search_merge_grouped(in, stride, lists, ix->mbuf[t].p, m, k, d_groups, st);
+        else launch_search_merge(in, stride, lists, ix->mbuf[t].p, m, k, st);
         in = ix->mbuf[t].p;
         t ^= 1;
         stride = k;
@@ -290,7 +293,9 @@ bool merge_and_finish(clip_amd_index * ix, int n_chunks, int m, int k, const int
     return true;
 }
 
-bool search_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, int k, const uint32_t * d_allow, float * d_dist, int64_t * d_ids) {
+// d_groups (vector queries only): one group per stored row, the grouped scan and merge in the place of the plain ones
+bool search_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, int k, const uint32_t * d_allow, float * d_dist, int64_t * d_ids,
+                        const int * d_groups = nullptr) {
     hipStream_t st = stream_of(ix);
     if (nq == 0) return true;
     if (ix->n == 0) {
@@ -311,12 +316,16 @@ bool search_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, in
         if (!(src.by_id ? gather_queries(ix, src, q0, m, m_pad) : prepare_queries(ix, src.d_q + (size_t)q0 * ix->dim, m, m_pad))) return false;
         if (!ensure(ix, ix->cand, (size_t)n_chunks * m * C * 8)) return false;
         const int * qself = src.by_id ? (const int *)ix->qself.p : nullptr;
-        if (!launch_search_scan(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, ix->qbuf.p, (const float *)ix->qinv.p, m, qt, k,
-                                ix->cand.p, n_chunks, rpc, mask, src.exclude_self ? qself : nullptr, st)) {
+        const bool launched =
+            d_groups ? launch_search_scan_grouped(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, ix->qbuf.p, (const float *)ix->qinv.p, m,
+                                                  qt, k, d_groups, ix->cand.p, n_chunks, rpc, mask, st)
+                     : launch_search_scan(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, ix->qbuf.p, (const float *)ix->qinv.p, m, qt, k,
+                                          ix->cand.p, n_chunks, rpc, mask, src.exclude_self ? qself : nullptr, st);
+        if (!launched) {
             fprintf(stderr, "clip_amd_index_search: scan launch failed\n");
             return false;
         }
-        if (!merge_and_finish(ix, n_chunks, m, k, qself, d_dist + (size_t)q0 * k, d_ids + (size_t)q0 * k)) return false;
+        if (!merge_and_finish(ix, n_chunks, m, k, qself, d_dist + (size_t)q0 * k, d_ids + (size_t)q0 * k, d_groups)) return false;
         if (hipGetLastError() != hipSuccess) {
             fprintf(stderr, "clip_amd_index_search: launch failed\n");
             return false;
@@ -603,34 +612,41 @@ float bench_on_gallery(int dtype, int64_t n, int dim, int n_queries, int iters, 
     return us;
 }
 
-// the body of clip_amd_bench_search (fraction < 0: no allowed set) and clip_amd_bench_search_subset
-float bench_search_impl(int dtype, int64_t n, int dim, int n_queries, int k, float fraction, bool contiguous, int iters) {
-    const bool args_ok = n_queries >= 1 && k >= 1 && k <= MAX_K && fraction <= 1.0f;
+// the body of clip_amd_bench_search (fraction < 0: no allowed set), clip_amd_bench_search_subset and, group_size >= 1,
+// clip_amd_bench_search_grouped (row r in group r / group_size)
+float bench_search_impl(int dtype, int64_t n, int dim, int n_queries, int k, float fraction, bool contiguous, int iters, int group_size = 0) {
+    const bool args_ok = n_queries >= 1 && k >= 1 && k <= MAX_K && fraction <= 1.0f && group_size >= 0;
     return bench_on_gallery(dtype, n, dim, n_queries, iters, args_ok, false, [&](clip_amd_index * ix, float * src) {
         float * d_dist = nullptr;
         int64_t * d_ids = nullptr;
         uint32_t * d_allow = nullptr;
+        int * d_groups = nullptr;
         float us = -4.f;
         bool ok = (fraction < 0.f || hipMalloc((void **)&d_allow, (size_t)search_allow_words(n) * 4) == hipSuccess) &&
-                  hipMalloc(&d_dist, (size_t)n_queries * k * 4) == hipSuccess && hipMalloc(&d_ids, (size_t)n_queries * k * 8) == hipSuccess;
+                  (group_size < 1 || hipMalloc((void **)&d_groups, (size_t)n * 4) == hipSuccess) && hipMalloc(&d_dist, (size_t)n_queries * k * 4) == hipSuccess && hipMalloc(&d_ids, (size_t)n_queries * k * 8) == hipSuccess;
         if (ok) {
             launch_search_fill_random(src, (int64_t)n_queries * dim, 0xC0FFEEull, nullptr);
             if (d_allow) launch_search_fill_allow(d_allow, n, fraction, contiguous, 0xA110ull, nullptr);
-            ok = search_device_impl(ix, vectors(src), n_queries, k, d_allow, d_dist, d_ids) && hipDeviceSynchronize() == hipSuccess;
+            if (d_groups) {
+                std::vector<int> g((size_t)n);
+                for (int64_t r = 0; r < n; r++) g[(size_t)r] = (int)(r / group_size);
+                ok = hipMemcpy(d_groups, g.data(), (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess;
+            }
+            ok = ok && search_device_impl(ix, vectors(src), n_queries, k, d_allow, d_dist, d_ids, d_groups) && hipDeviceSynchronize() == hipSuccess;
         }
         if (ok) {
             hipEvent_t e0, e1;
             (void)hipEventCreate(&e0);
             (void)hipEventCreate(&e1);
             (void)hipEventRecord(e0, nullptr);
-            for (int i = 0; ok && i < iters; i++) ok = search_device_impl(ix, vectors(src), n_queries, k, d_allow, d_dist, d_ids);
+            for (int i = 0; ok && i < iters; i++) ok = search_device_impl(ix, vectors(src), n_queries, k, d_allow, d_dist, d_ids, d_groups);
             (void)hipEventRecord(e1, nullptr);
             float ms = -1.f;
             if (ok && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) us = ms * 1000.f / iters;
             (void)hipEventDestroy(e0);
             (void)hipEventDestroy(e1);
         }
-        for (void * p : {(void *)d_dist, (void *)d_ids, (void *)d_allow})
+        for (void * p : {(void *)d_dist, (void *)d_ids, (void *)d_allow, (void *)d_groups})
             if (p) (void)hipFree(p);
         return us;
     });
@@ -723,6 +739,42 @@ bool clip_amd_index_search_subset(struct clip_amd_index * ix, const float * quer
 
 bool clip_amd_index_search(struct clip_amd_index * ix, const float * queries, int n_queries, int k, float * distances, int64_t * ids) {
     return search_call(ix, queries, n_queries, k, nullptr, distances, ids, __func__);
+}
+
+bool clip_amd_index_search_grouped_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int k, const int32_t * d_groups,
+                                          const uint64_t * d_allow, float * d_distances, int64_t * d_ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_search_args(ix, d_queries, n_queries, k, d_distances, d_ids, fn)) return false;
+        if (!d_groups && ix->n > 0) { fprintf(stderr, "%s: groups is NULL\n", fn); return false; }
+        (void)hipSetDevice(ix->device);
+        return search_device_impl(ix, vectors(d_queries), n_queries, k, (const uint32_t *)d_allow, d_distances, d_ids, (const int *)d_groups);
+    });
+}
+
+bool clip_amd_index_search_grouped(struct clip_amd_index * ix, const float * queries, int n_queries, int k, const int32_t * groups,
+                                   const uint64_t * allow, float * distances, int64_t * ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_search_args(ix, queries, n_queries, k, distances, ids, fn)) return false;
+        if (!groups && ix->n > 0) { fprintf(stderr, "%s: groups is NULL\n", fn); return false; }
+        for (int64_t r = 0; r < ix->n; r++)
+            if (groups[r] < 0) { fprintf(stderr, "%s: groups[%lld] = %d is negative\n", fn, (long long)r, (int)groups[r]); return false; }
+        if (n_queries == 0) return true;
+        (void)hipSetDevice(ix->device);
+        const float * d_q = nullptr;
+        const uint32_t * d_allow = nullptr;
+        const size_t count = (size_t)n_queries * k;
+        if (!stage_inputs(ix, queries, n_queries, allow, d_q, d_allow) || !ensure(ix, ix->outs, count * 12) ||
+            !ensure(ix, ix->gbuf, (size_t)ix->n * sizeof(int32_t)))
+            return false;
+        if (ix->n > 0 && hipMemcpyAsync(ix->gbuf.p, groups, (size_t)ix->n * sizeof(int32_t), hipMemcpyHostToDevice, stream_of(ix)) != hipSuccess) {
+            fprintf(stderr, "%s: the upload of groups failed: %s\n", fn, hipGetErrorString(hipGetLastError()));
+            return false;
+        }
+        int64_t * d_ids = (int64_t *)ix->outs.p;
+        float * d_dist = (float *)((char *)ix->outs.p + count * 8);
+        return search_device_impl(ix, vectors(d_q), n_queries, k, d_allow, d_dist, d_ids, (const int *)ix->gbuf.p) &&
+               copy_results(ix, d_dist, d_ids, count, distances, ids, fn);
+    });
 }
 
 int64_t clip_amd_index_live(const struct clip_amd_index * ix) { return ix ? ix->n - ix->removed : 0; }
@@ -1097,6 +1149,13 @@ float clip_amd_bench_knn(int dtype, int64_t n, int dim, int k, int route, int it
 
 float clip_amd_bench_search(int dtype, int64_t n, int dim, int n_queries, int k, int iters) {
     return guarded(__func__, -4.f, [&](const char *) { return bench_search_impl(dtype, n, dim, n_queries, k, -1.f, false, iters); });
+}
+
+float clip_amd_bench_search_grouped(int dtype, int64_t n, int dim, int n_queries, int k, int group_size, int iters) {
+    return guarded(__func__, -4.f, [&](const char *) {
+        if (group_size < 1) return -3.f;
+        return bench_search_impl(dtype, n, dim, n_queries, k, -1.0f, false, iters, group_size);
+    });
 }
 
 float clip_amd_bench_search_subset(int dtype, int64_t n, int dim, int n_queries, int k, float allowed_fraction, int contiguous, int iters) {

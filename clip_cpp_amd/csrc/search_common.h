@@ -42,6 +42,13 @@ struct Cand {
 // distance 1 - score (f32) itself, so "equal distances lower id first" holds for the distances the caller sees.
 __device__ __forceinline__ bool better(float da, int ia, float db, int ib) { return da < db || (da == db && ia < ib); }
 
+// LDS writes of this wave before, LDS reads of this wave after (buffers private to the wave: a wave-level barrier is enough)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // bitonic sort of a wave's LDS buffer (P pairs, P a power of two >= 2, better first).  The buffer is private to the wave and LDS operations
 // of one wave are processed in order, so a wave-level barrier (compiler ordering) separates the stages.
 __device__ void wave_sort(float * bs, int * bi, int P, int lane) {
@@ -58,9 +65,7 @@ __device__ void wave_sort(float * bs, int * bi, int P, int lane) {
                     bs[l] = sa; bi[l] = ia;
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_sync();
         }
     }
 }
@@ -106,9 +111,7 @@ __device__ int wave_select(Cand * buf, int cnt, int k, int P, bool final, float 
         bs[i] = c.s;
         bi[i] = c.id;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     wave_sort(bs, bi, P, lane);
     const int keep = final ? k : (cnt < k ? cnt : k);
     for (int i = lane; i < keep; i += 64) buf[i] = Cand{bs[i], bi[i]};

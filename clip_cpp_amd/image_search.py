@@ -1,7 +1,7 @@
 """Semantic image search over a directory tree: the reference's examples/image-search (`image-search-build` / `image-search`,
 build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.Index`) instead of usearch's approximate one.
 
-    python -m clip_cpp_amd.image_search build  [-m MODEL] [-v N] [-t N] [--db DIR] [--dtype f16|f32|i8] dir [more dirs]
+    python -m clip_cpp_amd.image_search build  [-m MODEL] [-v N] [-t N] [--db DIR] [--dtype f16|f32|i8] [--grid G] dir [more dirs]
     python -m clip_cpp_amd.image_search update [-m MODEL] [-v N] [-t N] [--db DIR] dir [more dirs]
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N | -d R] [--in PREFIX]... [--db DIR] <search text or /path/to/query/image>
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-n N] [--in PREFIX]... [--db DIR] --like INDEXED/IMAGE/PATH
@@ -34,6 +34,13 @@ its own and "  %f %s" (distance, label) for its -n (default 1) nearest labels, n
 (Index.append): an image whose path the target already holds is skipped and, with -d R, so is one whose nearest target image is within
 R (one Index.search_index per source; listed as "  %f %s ~ %s" at verbosity > 0); it prints "main: %d added, %d already present, %d near
 duplicates skipped".  A source built with another model (unless -m is given), dim or dtype is refused before any model is loaded.
+
+`build --grid G` (2 ... 8; 1 is a plain build) indexes regions: every image gives 1 + G * G rows, the whole image and the tiles of a G x G
+grid (Clip.encode_image_files(grid=G)), so a small object that hardly moves the embedding of the whole frame still has a row of its own.
+images.paths keeps one line per image; DIR/images.regions holds "grid G" and then one line "image x y w h" per index row.  `search` on
+such a database ranks images by their best row (Index.search_grouped with group = image): each image is printed once, with its best row's
+distance and, when that row is a tile, " [x,y,w,h]" behind the path; a query image is encoded whole; --in selects the rows of the matching
+images.  update, merge, dedup, neighbors, label and search --like / -d do not support a database built with --grid yet and say so.
 """
 import ctypes as C
 import os
@@ -45,6 +52,8 @@ import numpy as np
 IMAGE_EXTENSIONS = (".jpg", ".JPG", ".jpeg", ".JPEG", ".gif", ".GIF", ".png", ".PNG")
 INDEX_FILE = "images.index"
 PATHS_FILE = "images.paths"
+REGIONS_FILE = "images.regions"
+MAX_GRID = 8
 BATCH = 64          # images decoded and encoded per call
 MAX_K = 1024
 DEDUP_RADIUS = 0.05
@@ -89,6 +98,7 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
             takes.update({"-t": "threads", "--threads": "threads"})
         if build:
             takes["--dtype"] = "dtype"
+            takes["--grid"] = "grid"
         elif neighbors or label:
             takes.update({"-n": "results", "--results": "results"})
         elif merge:
@@ -113,10 +123,13 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
                 i += 1
                 continue
             try:
-                p[key] = int(argv[i]) if key in ("threads", "verbose", "results") else float(argv[i]) if key == "max_distance" else argv[i]
+                p[key] = int(argv[i]) if key in ("threads", "verbose", "results", "grid") else float(argv[i]) if key == "max_distance" else argv[i]
             except ValueError:
                 return None
             if key == "max_distance" and p[key] != p[key]:      # NaN
+                return None
+            if key == "grid" and not 1 <= p[key] <= MAX_GRID:
+                print("main: --grid takes 1 ... %d (1: whole images only), not %d" % (MAX_GRID, p[key]))
                 return None
         elif a in ("-h", "--help"):
             _help(build, p, dedup, update, neighbors, label, merge)
@@ -214,6 +227,9 @@ def _help(build, p, dedup=False, update=False, neighbors=False, label=False, mer
         print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
         print("  --db <dir>: directory that receives %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
         print("  --dtype f16|f32|i8: stored precision of the index (i8: int8 rows, half of f16's memory). Default: %s" % p["dtype"])
+        print("  --grid G: index regions as well: every image gives 1 + G*G rows, the whole image and the tiles of a G x G grid, and `search`"
+              " ranks images by their best row (2 ... %d; update, merge, dedup, neighbors, label and search --like / -d do not support such"
+              " a database yet). Default: 1, whole images only" % MAX_GRID)
     else:
         print("Usage: python -m clip_cpp_amd.image_search search [options] <search string or /path/to/query/image>")
         print("       python -m clip_cpp_amd.image_search search [options] --like <indexed/image/path>")
@@ -269,36 +285,84 @@ def build(argv):
         return 1
     index = clip_cpp_amd.Index(clip, clip.vision_config["projection_dim"], dtype=p["dtype"])
     paths = []
-    _encode_dirs(clip, L, index, p, paths)
+    p.setdefault("grid", 1)                        # (the key exists only when --grid was given)
+    regions = [] if p["grid"] > 1 else None
+    _encode_dirs(clip, L, index, p, paths, regions=regions)
     os.makedirs(p["db"], exist_ok=True)
-    _write_db(p, index, paths)
+    _write_db(p, index, paths, regions)
     index.close()
     clip.close()
     print("main: %d images processed and indexed" % len(paths), flush=True)
     return 0
 
 
-def _write_db(p, index, paths):
+def _write_db(p, index, paths, regions=None):
     """Both files under temporary names first, then renamed into place one after the other: an interruption while they are written
-    leaves the old database as it was."""
+    leaves the old database as it was.  regions (a build with --grid): the (image, x, y, w, h) of every index row, written the same way
+    as the third file; without them a regions file left by an earlier gridded build of the same directory goes away."""
     index_file, paths_file = os.path.join(p["db"], INDEX_FILE), os.path.join(p["db"], PATHS_FILE)
+    regions_file = os.path.join(p["db"], REGIONS_FILE)
     index.save(index_file + ".tmp")
     with open(paths_file + ".tmp", "w") as f:
         f.write(p["model"] + "\n")
         for path in paths:
             f.write(path + "\n")
+    if regions is not None:
+        with open(regions_file + ".tmp", "w") as f:
+            f.write("grid %d\n" % p["grid"])
+            for row in regions:
+                f.write("%d %d %d %d %d\n" % tuple(row))
     os.replace(index_file + ".tmp", index_file)
     os.replace(paths_file + ".tmp", paths_file)
+    if regions is not None:
+        os.replace(regions_file + ".tmp", regions_file)
+    elif os.path.exists(regions_file):
+        os.remove(regions_file)
 
 
-def _encode_dirs(clip, L, index, p, paths, scans=None):
+def read_regions(db):
+    """(grid, int array [rows, 5] = image, x, y, w, h) of db/images.regions; None when the database has none (a plain build); ValueError
+    when the file is not a regions file as `build --grid` writes it: the rows of an image together, images in ascending order, 1 + G * G
+    rows each (`search` takes an image's first row for the whole image and the others for tiles)."""
+    regions_file = os.path.join(db, REGIONS_FILE)
+    if not os.path.exists(regions_file):
+        return None
+    with open(regions_file) as f:
+        lines = f.read().split("\n")
+    head = lines[0].split()
+    if len(head) != 2 or head[0] != "grid":
+        raise ValueError("'%s' does not start with 'grid G'" % regions_file)
+    rows = [[int(v) for v in line.split()] for line in lines[1:] if line]
+    if any(len(r) != 5 for r in rows):
+        raise ValueError("'%s' holds a line that is not 'image x y w h'" % regions_file)
+    grid, rows = int(head[1]), np.array(rows, dtype=np.int64).reshape(-1, 5)
+    per = 1 + grid * grid
+    if not 2 <= grid <= MAX_GRID or len(rows) % per or not np.array_equal(rows[:, 0], np.repeat(rows[::per, 0], per)) or \
+            (len(rows) > per and np.any(np.diff(rows[::per, 0]) <= 0)):
+        raise ValueError("'%s' does not hold %s rows per image, each image's rows together and the images in ascending order"
+                         % (regions_file, "1 + G * G" if not 2 <= grid <= MAX_GRID else per))
+    return grid, rows
+
+
+def _refuse_gridded(db, command):
+    """True, with the message printed, when the database in db was built with --grid: `command` does not handle regions"""
+    if not os.path.exists(os.path.join(db, REGIONS_FILE)):
+        return False
+    _err("main: the database in '%s' was built with --grid (it holds %s): `%s` does not support such a database yet"
+         % (db, REGIONS_FILE, command))
+    return True
+
+
+def _encode_dirs(clip, L, index, p, paths, scans=None, regions=None):
     """Decode and encode the image files of the directories p["rest"] in batches and append them to `index` and `paths`.  scans: the
     [(dir, files)] to take when the caller has scanned already (`update`), else every file found under each dir.
     The files of all directories form one list that goes through Clip.encode_image_files in windows of BATCH loadable images:
     p["threads"] host threads read and decode (the GPU does the JPEG pixel work unless CLIP_AMD_JPEG_DEVICE=0), and every encoder call
     sees BATCH consecutive loadable images, across directory boundaries too.  The directories are scanned first and each is announced
     when its first file is reported, so the lines come out in the order of a file-by-file pass; the list is prepared for the library
-    once (Clip.ImageFileList), each call starts where the last one stopped and no file is decoded twice."""
+    once (Clip.ImageFileList), each call starts where the last one stopped and no file is decoded twice.
+    regions (a list, build --grid): every image is encoded as the 1 + G * G rows of Clip.encode_image_files(grid=p["grid"]) and the list
+    receives (image id, x, y, w, h) per row."""
     stream, heads = [], []                            # heads: (index of the directory's first file in stream, dir, files, scanned here)
     for base, files in scans if scans is not None else [(base, None) for base in p["rest"]]:
         heads.append((len(stream), base, image_files(base) if files is None else files, files is None))
@@ -313,7 +377,11 @@ def _encode_dirs(clip, L, index, p, paths, scans=None):
 
     prepared, pos = clip.ImageFileList(stream), 0
     while pos < len(stream):
-        vecs, ok, consumed = clip.encode_image_files(prepared, normalize=True, n_threads=p["threads"], max_images=BATCH, start=pos)
+        if regions is None:
+            vecs, ok, consumed = clip.encode_image_files(prepared, normalize=True, n_threads=p["threads"], max_images=BATCH, start=pos)
+        else:
+            vecs, ok, consumed, boxes = clip.encode_image_files(prepared, normalize=True, n_threads=p["threads"], max_images=BATCH, start=pos,
+                                                                grid=p["grid"])
         if consumed <= 0:
             break
         window = stream[pos:pos + consumed]
@@ -327,6 +395,10 @@ def _encode_dirs(clip, L, index, p, paths, scans=None):
         loaded = [path for path, good in zip(window, ok) if good]
         if loaded:
             index.add(vecs)
+            if regions is not None:
+                per = len(boxes) // len(loaded)
+                for r, box in enumerate(boxes.tolist()):
+                    regions.append([len(paths) + r // per] + box)
             paths.extend(loaded)
             if p["verbose"] == 1:
                 print(".", end="", flush=True)
@@ -353,6 +425,8 @@ def update(argv):
     p = _parse(argv, build=False, update=True)
     if p is None:
         _help(False, dict(threads=4, verbose=1, db="."), update=True)
+        return 1
+    if _refuse_gridded(p["db"], "update"):
         return 1
     old_paths = _read_db(p)
     if old_paths is None:
@@ -422,9 +496,10 @@ def _read_paths(db):
     return model_line, image_paths
 
 
-def _read_db(p):
+def _read_db(p, regions=None):
     """The image paths of DIR/images.paths after the database checks `search` and `dedup` share (the model path from its first line unless
-    -m gave one); None, with the message printed, when a check fails."""
+    -m gave one); None, with the message printed, when a check fails.  regions (read_regions, a gridded database): the index holds one
+    row per region, each naming one of the paths."""
     model_line, image_paths = _read_paths(p["db"])
     if not p["model"]:
         p["model"] = model_line
@@ -439,6 +514,12 @@ def _read_db(p):
     if hdr is None:
         _err("main: '%s' is missing or not an index file" % os.path.join(p["db"], INDEX_FILE))
         return None
+    if regions is not None:
+        rows = regions[1]
+        if hdr[3] != len(rows) or (len(rows) and (rows[:, 0].min() < 0 or rows[:, 0].max() >= len(image_paths))):
+            print("main: index files size missmatch")
+            return None
+        return image_paths
     if hdr[3] != len(image_paths):
         print("main: index files size missmatch")
         return None
@@ -452,7 +533,14 @@ def search(argv):
         _help(False, dict(threads=4, verbose=1, db=".", results=5))
         return 1
     img_path, text = classify_query(p["rest"])
-    image_paths = _read_db(p)
+    if (p["like"] is not None or p["max_distance"] is not None) and _refuse_gridded(p["db"], "search --like" if p["like"] is not None else "search -d"):
+        return 1
+    try:
+        regions = read_regions(p["db"])
+    except ValueError as e:
+        _err("main: %s" % e)
+        return 1
+    image_paths = _read_db(p, regions)
     if image_paths is None:
         return 1
     like_id = None
@@ -494,7 +582,21 @@ def search(argv):
     allow = None
     if p["in"]:                                    # the index ranks only these rows: no host-side filtering of a longer list
         allow = np.array([path.startswith(tuple(p["in"])) for path in image_paths], dtype=np.bool_)
-    if p["max_distance"] is not None:
+    boxes = {}
+    if regions is not None:                        # images ranked by their best row: group = image, each image once
+        rows = regions[1]
+        groups = rows[:, 0]
+        k = max(1, min(p["results"], MAX_K))
+        dist, ids = index.search_grouped(vec[None, :], k, groups, allow=None if allow is None else allow[groups])
+        whole = np.ones(len(rows), dtype=np.bool_)
+        whole[1:] = groups[1:] != groups[:-1]      # an image's first row is the whole image, the tiles follow
+        hits = []
+        for d, r in zip(dist[0], ids[0]):
+            if r >= 0 and p["results"] > 0:
+                hits.append((d, int(groups[r])))
+                if not whole[r]:
+                    boxes[int(groups[r])] = " [%d,%d,%d,%d]" % tuple(rows[r, 1:])
+    elif p["max_distance"] is not None:
         _, dist, ids = index.range_search(vec[None, :], p["max_distance"], allow=allow)
         hits = list(zip(dist, ids))
     else:
@@ -505,7 +607,7 @@ def search(argv):
         print("search results:")
         print("distance path")
     for d, i in hits:
-        print("  %f %s" % (d, image_paths[i]))
+        print("  %f %s%s" % (d, image_paths[i], boxes.get(i, "")))
     sys.stdout.flush()
     index.close()
     clip.close()
@@ -544,6 +646,8 @@ def dedup(argv):
     if p is None:
         _help(False, dict(verbose=1, db="."), dedup=True)
         return 1
+    if _refuse_gridded(p["db"], "dedup"):
+        return 1
     image_paths = _read_db(p)
     if image_paths is None:
         return 1
@@ -573,6 +677,8 @@ def neighbors(argv):
     p = _parse(argv, build=False, neighbors=True)
     if p is None:
         _help(False, dict(verbose=1, db=".", results=5), neighbors=True)
+        return 1
+    if _refuse_gridded(p["db"], "neighbors"):
         return 1
     image_paths = _read_db(p)
     if image_paths is None:
@@ -609,6 +715,8 @@ def label(argv):
     p = _parse(argv, build=False, label=True)
     if p is None:
         _help(False, dict(threads=4, verbose=1, db=".", results=1), label=True)
+        return 1
+    if _refuse_gridded(p["db"], "label"):
         return 1
     image_paths = _read_db(p)
     if image_paths is None:
@@ -673,6 +781,8 @@ def merge(argv):
     p = _parse(argv, build=False, merge=True)
     if p is None:
         _help(False, dict(verbose=1, db="."), merge=True)
+        return 1
+    if any(_refuse_gridded(db, "merge") for db in [p["db"]] + p["from"]):
         return 1
     model_given = bool(p["model"])
     paths = _read_db(p)

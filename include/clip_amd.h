@@ -117,6 +117,31 @@ int clip_amd_image_batch_encode_files(struct clip_ctx * ctx, const char * const 
 int clip_amd_image_batch_encode_memory(struct clip_ctx * ctx, const uint8_t * const * data, const size_t * sizes, int n, int max_images,
                                        int n_threads, bool normalize, float * vec, int * consumed, uint8_t * ok);
 
+/* Regions: several boxes of uploaded images, one row each (crops per image for a region index; see clip_amd_index_search_grouped).
+ * boxes: [n_boxes][5] = image number (0 ... n_imgs - 1), x, y, w, h with w, h >= 1 and the box inside its image; any order, an image may
+ * be named any number of times or not at all.  Row b is, bit for bit, row b of ONE clip_amd_image_batch_encode_u8 call over the n_boxes
+ * images obtained by copying each box out on the host: the resize treats the box as the whole picture, nothing outside it is read.  An
+ * image's pixels are uploaded once per staging piece (at most 128 rows, CLIP_AMD_U8_PIECE) that holds one of its boxes, not once per
+ * box.  A bad box (or NULL boxes with n_boxes > 0) returns false before anything is launched, with a message that names the box, and
+ * leaves vec untouched.  Not for clip_amd_model_load_multi contexts. */
+bool clip_amd_image_batch_encode_regions(struct clip_ctx * ctx, const struct clip_image_u8 * imgs, int n_imgs, const int32_t * boxes, int n_boxes,
+                                         float * vec, bool normalize);
+/* the preprocessing half alone, as clip_amd_image_batch_preprocess_device: d_out [n_boxes][S][S][3] float32 in HBM (one staging piece) */
+bool clip_amd_image_batch_preprocess_regions_device(struct clip_ctx * ctx, const struct clip_image_u8 * imgs, int n_imgs, const int32_t * boxes,
+                                                    int n_boxes, float * d_out);
+/* clip_amd_image_batch_encode_files / _memory with a grid of regions per image, 1 <= grid <= 8.  grid == 1: the same rows as the call
+ * without a grid.  grid = G >= 2: every loadable image yields R = 1 + G * G consecutive rows: the whole image, then the tiles row by row,
+ * tile (i, j) = x in [i nx / G, (i + 1) nx / G), y in [j ny / G, (j + 1) ny / G) in integer division, j outer and i inner.  max_images,
+ * the return value, *consumed and ok keep counting IMAGES; vec holds max_images * R rows and boxes_out [max_images * R][4] receives each
+ * row's x, y, w, h.  An image with min(nx, ny) < G counts as not loadable (ok 0, a message on stderr).  The rows are bit-identical to
+ * clip_image_load_from_file for each loadable file followed by ONE clip_amd_image_batch_encode_regions call over those boxes.  A JPEG
+ * whose pixel half runs on the device is decoded there once per staging piece; all its regions read those pixels, which never exist on
+ * the host. */
+int clip_amd_image_batch_encode_files_grid(struct clip_ctx * ctx, const char * const * paths, int n, int max_images, int n_threads, int grid,
+                                           bool normalize, float * vec, int32_t * boxes_out, int * consumed, uint8_t * ok);
+int clip_amd_image_batch_encode_memory_grid(struct clip_ctx * ctx, const uint8_t * const * data, const size_t * sizes, int n, int max_images,
+                                            int n_threads, int grid, bool normalize, float * vec, int32_t * boxes_out, int * consumed, uint8_t * ok);
+
 /* Batched text encoding ("next" row §8f-2; per-text semantics identical to
  * clip_text_encode, reference clip.cpp:1016-1233).  Texts are ragged:
  * tokens[i].data holds tokens[i].size ids incl. BOS/EOS.  vec: [n_texts][projection_dim]. */
@@ -216,9 +241,26 @@ bool clip_amd_index_search_subset(struct clip_amd_index * ix, const float * quer
                                   float * distances, int64_t * ids);
 bool clip_amd_index_search_subset_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int k, const uint64_t * d_allow,
                                          float * d_distances, int64_t * d_ids);
+/* Grouped search: every row belongs to a group and a result holds each group at most once, represented by its best row (several crops or
+ * views per image, ranked by image).  groups: size entries, each >= 0, groups[id] = the group of row id; any numbering, rows of a group need
+ * not be adjacent.  Groups are an argument of the call, not index state: add, remove, compact, append and save know nothing of them.
+ * With L = every eligible row (live and allowed, allow as for search_subset, NULL = every row) in search's order (distance ascending, equal
+ * distances lower id first), the result of a query is the rows of L whose group has not appeared earlier in L, cut to k; the tail is -1 /
+ * +INFINITY.  ids are row ids and distances the bits clip_amd_index_search reports for the same (query, row) pair, so with all groups
+ * distinct the result is search_subset's, bit for bit.  1 <= k <= 1024; the result does not depend on how queries are split across calls.
+ * Host form: groups and allow are host arrays (groups is uploaded for the call); a negative group, NULL groups with size > 0 or any bad
+ * argument of search returns false with a message and launches nothing.  Device form: d_groups (int32) and d_allow are read from HBM and
+ * trusted. */
+bool clip_amd_index_search_grouped(struct clip_amd_index * ix, const float * queries, int n_queries, int k, const int32_t * groups,
+                                   const uint64_t * allow, float * distances, int64_t * ids);
+bool clip_amd_index_search_grouped_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int k, const int32_t * d_groups,
+                                          const uint64_t * d_allow, float * d_distances, int64_t * d_ids);
 /* Average device time (microseconds, HIP events) of one clip_amd_index_search_device of n_queries seeded random queries against n seeded
  * random rows on the current device (dtype as clip_amd_index_create: 0, 1 or 3); < 0 on error.  Used by scripts/search_bench.py. */
 float clip_amd_bench_search(int dtype, int64_t n, int dim, int n_queries, int k, int iters);
+/* The same for clip_amd_index_search_grouped_device over the same seeded rows and queries, row r in group r / group_size (group_size >= 1).
+ * Used by scripts/regions_bench.py. */
+float clip_amd_bench_search_grouped(int dtype, int64_t n, int dim, int n_queries, int k, int group_size, int iters);
 /* The same with an allowed set over the same seeded rows and queries (clip_amd_index_search_subset_device): allowed_fraction in [0, 1] of
  * the ids, a seeded random selection or, contiguous != 0, one id range in the middle of the index.  Used by scripts/subset_bench.py. */
 float clip_amd_bench_search_subset(int dtype, int64_t n, int dim, int n_queries, int k, float allowed_fraction, int contiguous, int iters);
