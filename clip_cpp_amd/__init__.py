@@ -82,6 +82,8 @@ AMD_SYMBOLS = [
     "clip_amd_index_search_grouped", "clip_amd_index_search_grouped_device", "clip_amd_bench_search_grouped",
     "clip_amd_image_batch_encode_regions", "clip_amd_image_batch_preprocess_regions_device", "clip_amd_image_batch_encode_files_grid",
     "clip_amd_image_batch_encode_memory_grid",
+    "clip_amd_index_search_sets", "clip_amd_index_search_sets_device", "clip_amd_index_search_ids_sets", "clip_amd_test_index_sets_block",
+    "clip_amd_bench_search_sets",
 ]
 
 _lib = None
@@ -263,6 +265,16 @@ def lib():
     L.clip_amd_index_search_grouped_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp]
     L.clip_amd_bench_search_grouped.restype = C.c_float
     L.clip_amd_bench_search_grouped.argtypes = [i32, i64, i32, i32, i32, i32, i32]
+    L.clip_amd_index_search_sets.restype = C.c_bool
+    L.clip_amd_index_search_sets.argtypes = [vp, f32p, i32, i64p, i64, i32, C.POINTER(C.c_int32), u64p, f32p, i64p, C.POINTER(C.c_int32)]
+    L.clip_amd_index_search_sets_device.restype = C.c_bool
+    L.clip_amd_index_search_sets_device.argtypes = [vp, vp, i32, i64p, i64, i32, vp, vp, vp, vp, vp]
+    L.clip_amd_index_search_ids_sets.restype = C.c_bool
+    L.clip_amd_index_search_ids_sets.argtypes = [vp, i64p, i64, i64p, i64, i32, i32, C.POINTER(C.c_int32), u64p, f32p, i64p, C.POINTER(C.c_int32)]
+    L.clip_amd_test_index_sets_block.restype = i64
+    L.clip_amd_test_index_sets_block.argtypes = [vp, i64]
+    L.clip_amd_bench_search_sets.restype = C.c_float
+    L.clip_amd_bench_search_sets.argtypes = [i32, i64, i32, i32, i32, i32, i32, i32]
     L.clip_amd_bench_search_subset.restype = C.c_float
     L.clip_amd_bench_search_subset.argtypes = [i32, i64, i32, i32, i32, C.c_float, i32, i32]
     L.clip_amd_index_search_ids.restype = C.c_bool
@@ -754,7 +766,13 @@ class Index:
 
     search_grouped(queries, k, groups) ranks groups of rows instead of rows (several crops of one image, ranked by image): `groups` names
     every row's group and a result holds each group at most once, represented by its best row.  Groups are an argument of the call, not
-    state of the index."""
+    state of the index.
+
+    search_sets(queries, set_lims, k, groups) searches with query sets: the rows set_lims[s] ... set_lims[s + 1] - 1 stand for one thing (the
+    regions of one image) and the result of a set holds the best stored rows over all of its rows, each group (without groups: each row)
+    at most once, with the query row that matched.  search_ids_sets does the same with stored rows as the queries and can leave a set's
+    own group out (two gridded images match through their best pair of regions, and no image matches itself); knn_graph_grouped is that
+    for every group of the index at once."""
 
     DTYPES = {"f32": 0, "f16": 1, "i8": 3}
 
@@ -852,19 +870,13 @@ class Index:
         negative group."""
         q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
         nq = q.shape[0]
-        g = np.asarray(groups)
-        if g.size and not np.issubdtype(g.dtype, np.integer):
-            raise ValueError("groups must be integers, not %s" % g.dtype)
-        g = g.reshape(-1)
-        if g.size != len(self):
-            raise ValueError("groups must have one entry per row: %d, not %d" % (len(self), g.size))
-        if g.size and (int(g.min()) < 0 or int(g.max()) > 2 ** 31 - 1):
-            raise ValueError("groups must lie in 0 ... 2^31 - 1")
-        g = np.zeros(g.size + 1, dtype=np.int32)[:g.size] if g.size == 0 else np.ascontiguousarray(g, dtype=np.int32)
+        if groups is None:
+            raise ValueError("groups must be integers, not None")
+        g, gp = self._groups(groups)
         words, wp = self._allow(allow)
         dist = np.empty((nq, k), dtype=np.float32)
         ids = np.empty((nq, k), dtype=np.int64)
-        if not lib().clip_amd_index_search_grouped(self._live(), _fp(q), nq, int(k), g.ctypes.data_as(C.POINTER(C.c_int32)), wp, _fp(dist),
+        if not lib().clip_amd_index_search_grouped(self._live(), _fp(q), nq, int(k), gp, wp, _fp(dist),
                                                    ids.ctypes.data_as(C.POINTER(C.c_int64))):
             raise RuntimeError("clip_amd_index_search_grouped failed (see stderr)")
         return dist, ids
@@ -875,6 +887,102 @@ class Index:
         if not lib().clip_amd_index_search_grouped_device(self._live(), C.c_void_p(d_queries), int(n_queries), int(k), C.c_void_p(d_groups or None),
                                                           C.c_void_p(d_allow or None), C.c_void_p(d_distances), C.c_void_p(d_ids)):
             raise RuntimeError("clip_amd_index_search_grouped_device failed (see stderr)")
+
+    @staticmethod
+    def _set_lims(set_lims, n_rows):
+        """set_lims as a contiguous int64 array after the checks of the library (ValueError): it starts at 0, never decreases and ends at
+        n_rows.  Pure numpy: needs no device."""
+        a = np.asarray(set_lims)
+        if a.ndim != 1 or a.size < 1 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("set_lims must be a one-dimensional integer array of n_sets + 1 entries")
+        a = np.ascontiguousarray(a, dtype=np.int64)
+        if int(a[0]) != 0:
+            raise ValueError("set_lims must start at 0, not at %d" % int(a[0]))
+        if a.size > 1 and bool(np.any(np.diff(a) < 0)):
+            raise ValueError("set_lims must not decrease (entry %d)" % (int(np.argmax(np.diff(a) < 0)) + 1))
+        if int(a[-1]) != n_rows:
+            raise ValueError("set_lims must end at the %d query rows, not at %d" % (n_rows, int(a[-1])))
+        return a
+
+    def _groups(self, groups):
+        """(keep-alive int32 array, pointer) of one group per row (ValueError for a wrong length, a non-integer or a group outside 0 ...
+        2^31 - 1); (None, NULL) for None"""
+        if groups is None:
+            return None, None
+        g = np.asarray(groups)
+        if g.size and not np.issubdtype(g.dtype, np.integer):
+            raise ValueError("groups must be integers, not %s" % g.dtype)
+        g = g.reshape(-1)
+        if g.size != len(self):
+            raise ValueError("groups must have one entry per row: %d, not %d" % (len(self), g.size))
+        if g.size and (int(g.min()) < 0 or int(g.max()) > 2 ** 31 - 1):
+            raise ValueError("groups must lie in 0 ... 2^31 - 1")
+        g = np.zeros(g.size + 1, dtype=np.int32)[:g.size] if g.size == 0 else np.ascontiguousarray(g, dtype=np.int32)
+        return g, g.ctypes.data_as(C.POINTER(C.c_int32))
+
+    def search_sets(self, queries, set_lims, k, groups=None, allow=None):
+        """Search with query sets: set s is the query rows set_lims[s] ... set_lims[s + 1] - 1 (set_lims int [n_sets + 1], from 0 to the
+        number of rows, non-decreasing; an empty set gives an all-empty result).  Per set, every pair (query row q, eligible stored row r)
+        in the order distance ascending, then r, then q, keeping a pair when the group of r (`groups`, int [len]; None: r itself) has not
+        appeared earlier, cut to k: (distances f32 [n_sets, k], ids int64 [n_sets, k], qrows int32 [n_sets, k]), the stored row and the
+        query row (its index in `queries`) of each kept pair and the distance `search` reports for the two; +inf / -1 / -1 where there
+        are fewer.  Sets of one row: search_grouped's result (search's without groups).  ValueError for a malformed set_lims or groups."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        lims = self._set_lims(set_lims, q.shape[0])
+        g, gp = self._groups(groups)
+        words, wp = self._allow(allow)
+        ns = lims.size - 1
+        dist = np.empty((ns, k), dtype=np.float32)
+        ids = np.empty((ns, k), dtype=np.int64)
+        qrows = np.empty((ns, k), dtype=np.int32)
+        if not lib().clip_amd_index_search_sets(self._live(), _fp(q), q.shape[0], lims.ctypes.data_as(C.POINTER(C.c_int64)), ns, int(k), gp, wp,
+                                                _fp(dist), ids.ctypes.data_as(C.POINTER(C.c_int64)), qrows.ctypes.data_as(C.POINTER(C.c_int32))):
+            raise RuntimeError("clip_amd_index_search_sets failed (see stderr)")
+        return dist, ids, qrows
+
+    def search_ids_sets(self, ids, set_lims, k, groups=None, exclude_own=True, allow=None):
+        """search_sets with the stored rows `ids` (each a live id; duplicates are fine) as the query rows, bit for bit as search_ids takes
+        them (a row is not excluded as itself).  exclude_own (needs `groups`): a stored row of the group of the query row is not eligible
+        for that query row, so a group never matches itself.  Returns (distances, ids, qrows) as search_sets, qrows indexing `ids`."""
+        a = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        lims = self._set_lims(set_lims, a.size)
+        g, gp = self._groups(groups)
+        if exclude_own and g is None:
+            raise ValueError("exclude_own needs groups")
+        words, wp = self._allow(allow)
+        ns = lims.size - 1
+        dist = np.empty((ns, k), dtype=np.float32)
+        out = np.empty((ns, k), dtype=np.int64)
+        qrows = np.empty((ns, k), dtype=np.int32)
+        if not lib().clip_amd_index_search_ids_sets(self._live(), a.ctypes.data_as(C.POINTER(C.c_int64)), a.size, lims.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    ns, int(k), int(bool(exclude_own)), gp, wp, _fp(dist), out.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    qrows.ctypes.data_as(C.POINTER(C.c_int32))):
+            raise RuntimeError("clip_amd_index_search_ids_sets failed (see stderr)")
+        return dist, out, qrows
+
+    def search_sets_device(self, d_queries, n_queries, set_lims, k, d_groups, d_allow, d_distances, d_ids, d_qrows):
+        """search_sets on device pointers (ints): queries [n, dim] f32, groups [len] int32 (trusted; 0 / None: no groups), d_allow uint64
+        words (0 / None: every row) -> distances [n_sets, k] f32, ids [n_sets, k] int64, qrows [n_sets, k] int32; set_lims is a host array
+        (it shapes the launches); asynchronous on the context's stream."""
+        lims = self._set_lims(set_lims, int(n_queries))
+        if not lib().clip_amd_index_search_sets_device(self._live(), C.c_void_p(d_queries or None), int(n_queries), lims.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                       lims.size - 1, int(k), C.c_void_p(d_groups or None), C.c_void_p(d_allow or None),
+                                                       C.c_void_p(d_distances or None), C.c_void_p(d_ids or None), C.c_void_p(d_qrows or None)):
+            raise RuntimeError("clip_amd_index_search_sets_device failed (see stderr)")
+
+    def knn_graph_grouped(self, k, groups):
+        """The k-NN graph of the groups (images of a gridded index): (labels, distances, ids, qids).  labels int64 [G]: the distinct groups
+        of the live rows, ascending, one result row each; distances f32 / ids int64 / qids int64 [G, k]: the label's k nearest OTHER
+        groups by their best pair of rows, ids the other group's row and qids the label's own row of that pair; +inf / -1 / -1 where
+        there are fewer other groups.  One search_ids_sets(exclude_own=True) over the live rows stably sorted by group."""
+        g, _ = self._groups(groups)
+        rows = np.flatnonzero(self.live_mask()).astype(np.int64)
+        order = rows[np.argsort(g[rows], kind="stable")]
+        labels, counts = np.unique(g[order], return_counts=True)
+        lims = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        dist, ids, qrows = self.search_ids_sets(order, lims, k, groups=g, exclude_own=True)
+        qids = np.where(qrows >= 0, order[np.maximum(qrows, 0)] if order.size else -1, -1).astype(np.int64)
+        return labels.astype(np.int64), dist, ids, qids
 
     def range_search(self, queries, radius, allow=None):
         """Every stored row within `radius` of each query (distance <= radius in f32, the distance `search` reports): (lims int64 [nq + 1],
@@ -1008,6 +1116,13 @@ def bench_search_grouped(dtype, n, dim, n_queries, k, group_size, iters=10):
     """Microseconds per clip_amd_index_search_grouped_device on the data of bench_search, row r in group r // group_size
     (clip_amd_bench_search_grouped); < 0 on error."""
     return float(lib().clip_amd_bench_search_grouped(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(k), int(group_size), int(iters)))
+
+
+def bench_search_sets(dtype, n, dim, n_sets, set_size, k, group_size, iters=10):
+    """Microseconds per clip_amd_index_search_sets_device of n_sets sets of set_size query rows on the data of bench_search, row r in group
+    r // group_size, 0: no groups (clip_amd_bench_search_sets); < 0 on error."""
+    return float(lib().clip_amd_bench_search_sets(Index.DTYPES[dtype], int(n), int(dim), int(n_sets), int(set_size), int(k), int(group_size),
+                                                  int(iters)))
 
 
 def bench_search_subset(dtype, n, dim, n_queries, k, allowed_fraction, contiguous, iters=10):

@@ -12,7 +12,11 @@
 //                         groups.  The threshold is the distance of the k-th distinct group and stays +inf while fewer than k groups are
 //                         known; the strict push rule d < threshold stays exact because a later row (higher id) at the threshold's distance
 //                         loses the tie to the row that set it, and a group's best row only ever improves, so the threshold only falls.
-//                         Masked and unmasked instantiations as in k_search.hip.
+//                         Masked and unmasked instantiations as in k_search.hip.  OWN (query sets of stored rows with exclude_own,
+//                         k_sets.hip): a row of the query's own group (groups[row] == qgroup[query]) is not eligible.  The group is
+//                         read only for a row that passed d < threshold, and the threshold argument above still holds because an
+//                         ineligible row is never pushed: it neither sets a threshold nor takes a slot.  A compile-time flag: the
+//                         instantiations without it are the kernels they were.
 //   group_merge_kernel    one wave per (list pair, query): the same selection over the 2 k entries of two sorted lists.  (The rank merge of
 //                         k_search.hip cannot drop a group that both lists hold.)  A chunk's list is enough: if the best row of group g is
 //                         among the k best groups overall, fewer than k groups rank above it inside its own chunk too.
@@ -119,9 +123,10 @@ struct GroupScanParams {
     const float * rinv;    // i8: [>= n rounded up to 64] row inverse norms
     const float * qinv;    // i8: [nq_pad] query inverse norms
     const uint32_t * mask; // masked scan: one bit per row, at least n rounded up to 32 bits
+    const int * qgroup;    // OWN: [nq] the group each query belongs to (-1: none)
 };
 
-template <typename T, int QT, bool MASKED>
+template <typename T, int QT, bool MASKED, bool OWN>
 __global__ void __launch_bounds__(GSCAN_THREADS) group_scan_kernel(const GroupScanParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int QB = 16 * QT;
@@ -187,11 +192,14 @@ __global__ void __launch_bounds__(GSCAN_THREADS) group_scan_kernel(const GroupSc
                 Cand * buf = p.cand + ((size_t)chunk * p.nq + q0 + ql) * p.C;
                 float qinv = 0.f;
                 if constexpr (sizeof(T) == 1) qinv = p.qinv[q0 + ql];
+                int own = -1;
+                if constexpr (OWN) own = p.qgroup[q0 + ql];
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     const int64_t row = r0 + fgrp * 4 + r;
                     const float d = scan_distance(acc[j][r], qinv, rinv[r]);
-                    const bool push = row < hi && d < t && ((mbits >> (fgrp * 4 + r)) & 1u);
+                    bool push = row < hi && d < t && ((mbits >> (fgrp * 4 + r)) & 1u);
+                    if constexpr (OWN) push = push && p.groups[row] != own;      // (row < hi <= n here)
                     if (push) {
                         const int slot = atomicAdd(&cnt[ql], 1);     // < C: a buffer past C - 64 entries was shrunk to <= k before this iteration
                         buf[slot] = Cand{d, (int)row};
@@ -249,26 +257,24 @@ __global__ void __launch_bounds__(64) group_merge_kernel(const Cand * __restrict
     for (int t = lane; t < k; t += 64) O[t] = selected(bs, bi, M, t);
 }
 
-template <typename T, int QT, bool MASKED>
+template <typename T, int QT, bool MASKED, bool OWN>
 bool launch_gscan_m(const GroupScanParams & p, int n_chunks, hipStream_t stream) {
     static unsigned long long lds_done = 0;
     const size_t lds = (size_t)2 * 16 * QT * 4 + (size_t)4 * 3 * p.P * 4;
-    if (lds > 65536) opt_in_dynamic_lds(group_scan_kernel<T, QT, MASKED>, lds, lds_done);
+    if (lds > 65536) opt_in_dynamic_lds(group_scan_kernel<T, QT, MASKED, OWN>, lds, lds_done);
     const dim3 grid(n_chunks, (p.nq + 16 * QT - 1) / (16 * QT));
-    hipLaunchKernelGGL((group_scan_kernel<T, QT, MASKED>), grid, dim3(GSCAN_THREADS), lds, stream, p);
+    hipLaunchKernelGGL((group_scan_kernel<T, QT, MASKED, OWN>), grid, dim3(GSCAN_THREADS), lds, stream, p);
     return hipGetLastError() == hipSuccess;
 }
 
 template <typename T, int QT>
 bool launch_gscan_t(const GroupScanParams & p, int n_chunks, hipStream_t stream) {
-    return p.mask ? launch_gscan_m<T, QT, true>(p, n_chunks, stream) : launch_gscan_m<T, QT, false>(p, n_chunks, stream);
+    if (p.qgroup) return p.mask ? launch_gscan_m<T, QT, true, true>(p, n_chunks, stream) : launch_gscan_m<T, QT, false, true>(p, n_chunks, stream);
+    return p.mask ? launch_gscan_m<T, QT, true, false>(p, n_chunks, stream) : launch_gscan_m<T, QT, false, false>(p, n_chunks, stream);
 }
 
-}  // namespace
-
-bool launch_search_scan_grouped(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq,
-                                int qt, int k, const int * groups, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask,
-                                hipStream_t stream) {
+bool launch_gscan(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq, int qt, int k,
+                  const int * groups, const int * qgroup, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask, hipStream_t stream) {
     GroupScanParams p;
     p.rows = rows;
     p.q = q;
@@ -284,12 +290,27 @@ bool launch_search_scan_grouped(const void * rows, const float * rinv, int64_t n
     p.rinv = rinv;
     p.qinv = qinv;
     p.mask = mask;
+    p.qgroup = qgroup;
     return with_search_type(dtype, [&](auto t) {
         using T = decltype(t);
         if (qt == 4) return launch_gscan_t<T, 4>(p, n_chunks, stream);
         if (qt == 2) return launch_gscan_t<T, 2>(p, n_chunks, stream);
         return launch_gscan_t<T, 1>(p, n_chunks, stream);
     });
+}
+
+}  // namespace
+
+bool launch_search_scan_grouped(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq,
+                                int qt, int k, const int * groups, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask,
+                                hipStream_t stream) {
+    return launch_gscan(rows, rinv, n, Dpad, dtype, q, qinv, nq, qt, k, groups, nullptr, cand, n_chunks, rows_per_chunk, mask, stream);
+}
+
+bool launch_search_scan_grouped_own(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq,
+                                    int qt, int k, const int * groups, const int * qgroup, void * cand, int n_chunks, int64_t rows_per_chunk,
+                                    const uint32_t * mask, hipStream_t stream) {
+    return launch_gscan(rows, rinv, n, Dpad, dtype, q, qinv, nq, qt, k, groups, qgroup, cand, n_chunks, rows_per_chunk, mask, stream);
 }
 
 void launch_search_merge_grouped(const void * in, int64_t in_stride, int n_in, void * out, int nq, int k, const int * groups, hipStream_t stream) {

@@ -332,6 +332,20 @@ bool launch_search_scan_grouped(const void * rows, const float * rinv, int64_t n
                                 int qt, int k, const int * groups, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask,
                                 hipStream_t stream);
 void launch_search_merge_grouped(const void * in, int64_t in_stride, int n_in, void * out, int nq, int k, const int * groups, hipStream_t stream);
+// The grouped scan with own-group exclusion: qgroup [nq rounded up to 16 qt] (device) is each query's own group; a row of that group is
+// never a candidate of the query (-1: no row is excluded).
+bool launch_search_scan_grouped_own(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq,
+                                    int qt, int k, const int * groups, const int * qgroup, void * cand, int n_chunks, int64_t rows_per_chunk,
+                                    const uint32_t * mask, hipStream_t stream);
+// Query sets (k_sets.hip).  fill: count result slots empty (+inf / -1 / -1).  qgroup: qgroup[t] = groups[qself[t]], -1 where qself[t] < 0
+// (qself as launch_search_gather leaves it).  fold: for the n_fold sets from s_lo on of lims (device; row numbers of the call, the pass
+// holding rows q0 ... q0 + m - 1 as one sorted list of k (score, id) pairs each, `stride` pairs apart), result slot s (dist / ids / qrows
+// + s k) := the best k distinct keys (groups[id]; groups NULL: id) over that slot's entries and the lists of the set's rows in the pass,
+// ordered by distance, id, query row; a reported query row is qrow_base + its row number.
+void launch_sets_fill(float * dist, int64_t * ids, int * qrows, int64_t count, hipStream_t stream);
+void launch_sets_qgroup(const int * groups, const int * qself, int * qgroup, int64_t n_rows, hipStream_t stream);
+void launch_sets_fold(const void * lists, int64_t stride, int64_t q0, int m, const int64_t * lims, int64_t s_lo, int64_t n_fold, int k,
+                      const int * groups, float * dist, int64_t * ids, int * qrows, int64_t qrow_base, hipStream_t stream);
 // Searches by id.  gather: query t of n_rows (the padded count) := stored row ids[t] (device; NULL: row first + t) for t < n_ids, bit for bit
 // (i8: qinv[t] := rinv of that row), qself[t] := that id; an id outside [0, n) or with a cleared bit in live, and every t >= n_ids, gives the
 // zero row and qself -1.  launch_search_scan with qself != NULL never makes row qself[query] a candidate of that query; launch_search_finish

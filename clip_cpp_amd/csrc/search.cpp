@@ -1,6 +1,7 @@
 // search.cpp — the exact nearest-neighbour index of include/clip_amd.h (clip_amd_index_*): device-resident rows, argument checking,
 // query chunking, the scan -> merge tree -> finish launch sequence of k_search.hip, searches by id, the k-NN graph and the search of one
 // index with the rows of another (the gather kernel in front of the same sequence, or the tiled kernel of k_graph.hip in the scan's place),
+// searches with query sets (the set fold of k_sets.hip in the finish's place),
 // appending one index to another, the count -> lims -> scatter -> sort -> finish sequence of
 // range search and pairs (k_join.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
 // Replaces the usearch index of the reference's examples/image-search (build.cpp / search.cpp) with an exact search on the GPU.
@@ -60,6 +61,10 @@ struct clip_amd_index {
     Buf idbuf;                     // ids of a search by id copied from the host
     Buf qself;                     // searches by id: [nq_pad] the stored row each query is, -1 for a flagged one
     Buf gbuf;                      // groups of a grouped search copied from the host
+    Buf qgroup;                    // query sets with exclude_own: [nq_pad] the group of the stored row each query is
+    Buf slims;                     // query sets: set_lims of the call (of one query block of a host form) on the device
+    Buf souts;                     // query sets, host forms: ids + distances + query rows of one query block's sets
+    int64_t sets_block = 0;        // clip_amd_test_index_sets_block: query rows per block of the host forms, 0 automatic
     int knn_route = 0;             // clip_amd_test_index_knn_route: 0 automatic, 1 scan, 2 tiled
     int cross_route = 0;           // clip_amd_test_index_cross_route: the same for clip_amd_index_search_index
     // range search / pairs
@@ -272,14 +277,14 @@ bool gather_queries(clip_amd_index * ix, const QuerySource & src, int q0, int64_
     return true;
 }
 
-// the merge tree over the chunks' lists of m queries and the finish into d_dist / d_ids ([m][k]); d_groups: the grouped merge of k_group.hip
-bool merge_and_finish(clip_amd_index * ix, int n_chunks, int m, int k, const int * qself, float * d_dist, int64_t * d_ids,
-                      const int * d_groups = nullptr) {
+// the merge tree over the chunks' lists of m queries: afterwards query q's sorted k entries are at in + q * stride pairs; d_groups: the
+// grouped merge of k_group.hip
+bool merge_tree(clip_amd_index * ix, int n_chunks, int m, int k, const int * d_groups, const void *& in, int64_t & stride) {
     hipStream_t st = stream_of(ix);
     const size_t mb = (size_t)((n_chunks + 1) / 2) * m * k * 8;
     if (n_chunks > 1 && (!ensure(ix, ix->mbuf[0], mb) || !ensure(ix, ix->mbuf[1], mb))) return false;
-    const void * in = ix->cand.p;
-    int64_t stride = search_candidate_capacity(k);
+    in = ix->cand.p;
+    stride = search_candidate_capacity(k);
     int lists = n_chunks, t = 0;
     while (lists > 1) {
         if (d_groups) launch_search_merge_grouped(in, stride, lists, ix->mbuf[t].p, m, k, d_groups, st);
@@ -289,16 +294,42 @@ bool merge_and_finish(clip_amd_index * ix, int n_chunks, int m, int k, const int
         stride = k;
         lists = (lists + 1) / 2;
     }
-    launch_search_finish(in, stride, m, k, d_dist, d_ids, qself, st);
     return true;
 }
 
-// d_groups (vector queries only): one group per stored row, the grouped scan and merge in the place of the plain ones
+// the merge tree and the finish into d_dist / d_ids ([m][k])
+bool merge_and_finish(clip_amd_index * ix, int n_chunks, int m, int k, const int * qself, float * d_dist, int64_t * d_ids,
+                      const int * d_groups = nullptr) {
+    const void * in = nullptr;
+    int64_t stride = 0;
+    if (!merge_tree(ix, n_chunks, m, k, d_groups, in, stride)) return false;
+    launch_search_finish(in, stride, m, k, d_dist, d_ids, qself, stream_of(ix));
+    return true;
+}
+
+// What a search over query sets puts in the place of the finish: the fold of k_sets.hip over the sets that have rows in the pass.  lims
+// (host) / d_lims (device) [n_sets + 1]: the sets as row numbers of the call; the results ([n_sets][k] each) accumulate in d_dist / d_ids
+// / d_qrows, which the caller filled empty; a reported query row is qrow_base + its row number.  own (stored-row queries with groups
+// only): the scan excludes each query's own group.
+struct SetFold {
+    const int64_t * lims = nullptr;
+    const int64_t * d_lims = nullptr;
+    int64_t n_sets = 0;
+    float * d_dist = nullptr;
+    int64_t * d_ids = nullptr;
+    int * d_qrows = nullptr;
+    int64_t qrow_base = 0;
+    bool own = false;
+};
+
+// d_groups (vector queries, or query sets): one group per stored row, the grouped scan and merge in the place of the plain ones.  fold
+// (query sets): every pass ends in the set fold instead of the finish, and d_dist / d_ids are not used.
 bool search_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, int k, const uint32_t * d_allow, float * d_dist, int64_t * d_ids,
-                        const int * d_groups = nullptr) {
+                        const int * d_groups = nullptr, const SetFold * fold = nullptr) {
     hipStream_t st = stream_of(ix);
     if (nq == 0) return true;
     if (ix->n == 0) {
+        if (fold) return true;      // every set's result stays empty
         launch_search_finish(nullptr, 0, nq, k, d_dist, d_ids, nullptr, st);
         return hipGetLastError() == hipSuccess;
     }
@@ -316,8 +347,15 @@ bool search_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, in
         if (!(src.by_id ? gather_queries(ix, src, q0, m, m_pad) : prepare_queries(ix, src.d_q + (size_t)q0 * ix->dim, m, m_pad))) return false;
         if (!ensure(ix, ix->cand, (size_t)n_chunks * m * C * 8)) return false;
         const int * qself = src.by_id ? (const int *)ix->qself.p : nullptr;
+        const bool own = fold && fold->own;
+        if (own) {
+            if (!ensure(ix, ix->qgroup, (size_t)m_pad * sizeof(int))) return false;
+            launch_sets_qgroup(d_groups, qself, (int *)ix->qgroup.p, m_pad, st);
+        }
         const bool launched =
-            d_groups ? launch_search_scan_grouped(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, ix->qbuf.p, (const float *)ix->qinv.p, m,
+            own      ? launch_search_scan_grouped_own(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, ix->qbuf.p, (const float *)ix->qinv.p,
+                                                      m, qt, k, d_groups, (const int *)ix->qgroup.p, ix->cand.p, n_chunks, rpc, mask, st)
+            : d_groups ? launch_search_scan_grouped(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, ix->qbuf.p, (const float *)ix->qinv.p, m,
                                                   qt, k, d_groups, ix->cand.p, n_chunks, rpc, mask, st)
                      : launch_search_scan(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, ix->qbuf.p, (const float *)ix->qinv.p, m, qt, k,
                                           ix->cand.p, n_chunks, rpc, mask, src.exclude_self ? qself : nullptr, st);
@@ -325,7 +363,19 @@ bool search_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, in
             fprintf(stderr, "clip_amd_index_search: scan launch failed\n");
             return false;
         }
-        if (!merge_and_finish(ix, n_chunks, m, k, qself, d_dist + (size_t)q0 * k, d_ids + (size_t)q0 * k, d_groups)) return false;
+        if (fold) {
+            // the sets with a row in [q0, q0 + m): from the first that ends after q0 to the last that starts before q0 + m
+            const int64_t * L = fold->lims;
+            const int64_t s_lo = std::upper_bound(L + 1, L + fold->n_sets + 1, (int64_t)q0) - (L + 1);
+            const int64_t s_hi = std::lower_bound(L, L + fold->n_sets, (int64_t)q0 + m) - L;      // one past the last
+            const void * in = nullptr;
+            int64_t stride = 0;
+            if (!merge_tree(ix, n_chunks, m, k, d_groups, in, stride)) return false;
+            launch_sets_fold(in, stride, q0, m, fold->d_lims, s_lo, s_hi - s_lo, k, d_groups, fold->d_dist, fold->d_ids, fold->d_qrows,
+                             fold->qrow_base, st);
+        } else if (!merge_and_finish(ix, n_chunks, m, k, qself, d_dist + (size_t)q0 * k, d_ids + (size_t)q0 * k, d_groups)) {
+            return false;
+        }
         if (hipGetLastError() != hipSuccess) {
             fprintf(stderr, "clip_amd_index_search: launch failed\n");
             return false;
@@ -481,6 +531,146 @@ bool check_search_args(const clip_amd_index * ix, const void * q, int nq, int k,
     if (nq < 0) { fprintf(stderr, "%s: n_queries %d < 0\n", fn, nq); return false; }
     if (k < 1 || k > MAX_K) { fprintf(stderr, "%s: k = %d outside 1 ... %d\n", fn, k, MAX_K); return false; }
     if (nq > 0 && (!q || !dist || !ids)) { fprintf(stderr, "%s: NULL queries or result pointer\n", fn); return false; }
+    return true;
+}
+
+// what the query-set entry points ask beyond check_search_args: set_lims [n_sets + 1] starts at 0, never decreases and ends at nq
+bool check_set_args(int64_t nq, const int64_t * lims, int64_t n_sets, const void * qrows, const char * fn) {
+    if (n_sets < 0 || n_sets > MAX_ROWS) { fprintf(stderr, "%s: n_sets %lld outside 0 ... %lld\n", fn, (long long)n_sets, (long long)MAX_ROWS); return false; }
+    if (!lims) { fprintf(stderr, "%s: set_lims is NULL\n", fn); return false; }
+    if (n_sets > 0 && !qrows) { fprintf(stderr, "%s: NULL queries or result pointer\n", fn); return false; }
+    if (lims[0] != 0) { fprintf(stderr, "%s: set_lims[0] = %lld, not 0\n", fn, (long long)lims[0]); return false; }
+    for (int64_t s = 0; s < n_sets; s++)
+        if (lims[s + 1] < lims[s]) {
+            fprintf(stderr, "%s: set_lims decreases at entry %lld (%lld after %lld)\n", fn, (long long)s + 1, (long long)lims[s + 1], (long long)lims[s]);
+            return false;
+        }
+    if (lims[n_sets] != nq) {
+        fprintf(stderr, "%s: set_lims ends at %lld, not at the %lld query rows\n", fn, (long long)lims[n_sets], (long long)nq);
+        return false;
+    }
+    return true;
+}
+
+// Query sets on the device: the nq query rows of src in the n_sets sets of lims (host, [n_sets + 1], row numbers of src), results into
+// d_dist / d_ids / d_qrows ([n_sets][k], device).  first_kept: slot 0 already holds the result so far of set 0 (a set that began in an
+// earlier block of a host form) and is folded on; every other slot starts empty.  lims is read before the call returns.
+bool sets_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, const int64_t * lims, int64_t n_sets, int k, const int * d_groups,
+                      bool own, const uint32_t * d_allow, float * d_dist, int64_t * d_ids, int * d_qrows, int64_t qrow_base, bool first_kept) {
+    hipStream_t st = stream_of(ix);
+    if (n_sets == 0) return true;
+    const int64_t skip = first_kept ? 1 : 0;
+    launch_sets_fill(d_dist + skip * k, d_ids + skip * k, d_qrows + skip * k, (n_sets - skip) * k, st);
+    if (hipGetLastError() != hipSuccess) { fprintf(stderr, "clip_amd_index_search_sets: launch failed\n"); return false; }
+    if (nq == 0 || ix->n == 0) return true;
+    if (!ensure(ix, ix->slims, (size_t)(n_sets + 1) * 8)) return false;
+    if (hipMemcpyAsync(ix->slims.p, lims, (size_t)(n_sets + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess) {
+        fprintf(stderr, "clip_amd_index_search_sets: the upload of set_lims failed: %s\n", hipGetErrorString(hipGetLastError()));
+        return false;
+    }
+    SetFold f;
+    f.lims = lims;
+    f.d_lims = (const int64_t *)ix->slims.p;
+    f.n_sets = n_sets;
+    f.d_dist = d_dist;
+    f.d_ids = d_ids;
+    f.d_qrows = d_qrows;
+    f.qrow_base = qrow_base;
+    f.own = own;
+    return search_device_impl(ix, src, nq, k, d_allow, nullptr, nullptr, d_groups, &f);
+}
+
+// The host forms of the query-set searches: the nq query rows are f32 vectors (queries) or stored rows (ids), both on the host.  Query
+// blocks of a fixed size, as in knn_graph_impl, one after another; a block's rows are staged, searched as the sets (and parts of sets) they
+// hold, and the sets that end in the block are copied out.  A set that goes on into the next block keeps its result so far on the device:
+// it moves to slot 0 of the block's result workspace and the next block folds on.  Nothing on the device grows with nq, n_sets or their
+// product with k: empty sets never reach it (their results are written here).
+bool sets_host_impl(clip_amd_index * ix, const float * queries, const int64_t * ids, int64_t nq, const int64_t * lims, int64_t n_sets, int k,
+                    bool own, const int32_t * groups, const uint64_t * allow, float * distances, int64_t * out_ids, int32_t * qrows, const char * fn) {
+    hipStream_t st = stream_of(ix);
+    for (int64_t i = 0; i < n_sets * k; i++) {
+        distances[i] = INFINITY;
+        out_ids[i] = -1;
+        qrows[i] = -1;
+    }
+    if (nq == 0 || ix->n == 0) return true;
+    const uint32_t * d_allow = nullptr;
+    if (allow) {
+        const size_t ab = (size_t)search_allow_words(ix->n) * 4;
+        if (!ensure(ix, ix->abuf, ab)) return false;
+        (void)hipMemcpyAsync(ix->abuf.p, allow, ab, hipMemcpyHostToDevice, st);
+        d_allow = (const uint32_t *)ix->abuf.p;
+    }
+    if (groups) {
+        if (!ensure(ix, ix->gbuf, (size_t)ix->n * sizeof(int32_t))) return false;
+        if (hipMemcpyAsync(ix->gbuf.p, groups, (size_t)ix->n * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) {
+            fprintf(stderr, "%s: the upload of groups failed: %s\n", fn, hipGetErrorString(hipGetLastError()));
+            return false;
+        }
+    }
+    const int * d_groups = groups ? (const int *)ix->gbuf.p : nullptr;
+    std::vector<int64_t> sets;                             // the sets that hold rows, ascending: together they cover every row in order
+    for (int64_t s = 0; s < n_sets; s++)
+        if (lims[s + 1] > lims[s]) sets.push_back(s);
+    const int C = search_candidate_capacity(k);
+    int64_t block = std::min<int64_t>({(nq + 127) / 128 * 128, GRAPH_BLOCK_MAX, (int64_t)(GRAPH_OUT_BUDGET / ((size_t)k * 16)) / 128 * 128,
+                                       (int64_t)(CAND_BUDGET / ((size_t)C * 8)) / 128 * 128});
+    if (ix->sets_block > 0) block = ix->sets_block;
+    const size_t slots = (size_t)block * k;                // a block of m rows holds at most m sets
+    if (!ensure(ix, ix->souts, slots * 16) || (ids ? !ensure(ix, ix->idbuf, (size_t)block * 8) : !ensure(ix, ix->stage, (size_t)block * ix->dim * 4)))
+        return false;
+    int64_t * d_out = (int64_t *)ix->souts.p;
+    float * d_dist = (float *)((char *)ix->souts.p + slots * 8);
+    int * d_qrows = (int *)((char *)ix->souts.p + slots * 12);
+    std::vector<int64_t> local;
+    size_t j_lo = 0;
+    int64_t carried = -1;                                  // slot of the previous block that holds the result so far of this block's first set
+    for (int64_t r0 = 0; r0 < nq; r0 += block) {
+        const int m = (int)std::min(block, nq - r0);
+        size_t j_hi = j_lo;                                // one past the last set with a row in [r0, r0 + m)
+        local.assign(1, 0);
+        while (j_hi < sets.size() && lims[sets[j_hi]] < r0 + m) {
+            local.push_back(std::min(lims[sets[j_hi] + 1], r0 + m) - r0);
+            j_hi++;
+        }
+        const int64_t ns = (int64_t)(j_hi - j_lo);
+        const bool first_kept = lims[sets[j_lo]] < r0;
+        if (first_kept && carried > 0) {
+            (void)hipMemcpyAsync(d_out, d_out + carried * k, (size_t)k * 8, hipMemcpyDeviceToDevice, st);
+            (void)hipMemcpyAsync(d_dist, d_dist + carried * k, (size_t)k * 4, hipMemcpyDeviceToDevice, st);
+            (void)hipMemcpyAsync(d_qrows, d_qrows + carried * k, (size_t)k * 4, hipMemcpyDeviceToDevice, st);
+        }
+        QuerySource qs;
+        if (ids) {
+            (void)hipMemcpyAsync(ix->idbuf.p, ids + r0, (size_t)m * 8, hipMemcpyHostToDevice, st);
+            qs = stored_rows((const int64_t *)ix->idbuf.p, 0, false);
+        } else {
+            (void)hipMemcpyAsync(ix->stage.p, queries + (size_t)r0 * ix->dim, (size_t)m * ix->dim * 4, hipMemcpyHostToDevice, st);
+            qs = vectors((const float *)ix->stage.p);
+        }
+        if (!sets_device_impl(ix, qs, m, local.data(), ns, k, d_groups, own, d_allow, d_dist, d_out, d_qrows, r0, first_kept)) return false;
+        const bool last_open = lims[sets[j_hi - 1] + 1] > r0 + m;      // the block's last set goes on in the next block
+        const size_t j_done = last_open ? j_hi - 1 : j_hi;
+        for (size_t j = j_lo; j < j_done;) {                // one copy per run of consecutive sets
+            size_t e = j + 1;
+            while (e < j_done && sets[e] == sets[e - 1] + 1) e++;
+            const size_t from = (j - j_lo) * k, to = (size_t)sets[j] * k, cnt = (e - j) * k;
+            (void)hipMemcpyAsync(out_ids + to, d_out + from, cnt * 8, hipMemcpyDeviceToHost, st);
+            (void)hipMemcpyAsync(distances + to, d_dist + from, cnt * 4, hipMemcpyDeviceToHost, st);
+            (void)hipMemcpyAsync(qrows + to, d_qrows + from, cnt * 4, hipMemcpyDeviceToHost, st);
+            j = e;
+        }
+        if (!stream_done(ix, fn, hipGetLastError())) return false;      // (the staging buffers and `local` are reused by the next block)
+        carried = last_open ? ns - 1 : -1;
+        j_lo = j_done;
+    }
+    return true;
+}
+
+// the groups of a query-set host form: each of the n >= 0 (NULL: no groups)
+bool check_set_groups(const clip_amd_index * ix, const int32_t * groups, const char * fn) {
+    for (int64_t r = 0; groups && r < ix->n; r++)
+        if (groups[r] < 0) { fprintf(stderr, "%s: groups[%lld] = %d is negative\n", fn, (long long)r, (int)groups[r]); return false; }
     return true;
 }
 
@@ -774,6 +964,117 @@ bool clip_amd_index_search_grouped(struct clip_amd_index * ix, const float * que
         float * d_dist = (float *)((char *)ix->outs.p + count * 8);
         return search_device_impl(ix, vectors(d_q), n_queries, k, d_allow, d_dist, d_ids, (const int *)ix->gbuf.p) &&
                copy_results(ix, d_dist, d_ids, count, distances, ids, fn);
+    });
+}
+
+bool clip_amd_index_search_sets_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, const int64_t * set_lims, int64_t n_sets,
+                                       int k, const int32_t * d_groups, const uint64_t * d_allow, float * d_distances, int64_t * d_ids,
+                                       int32_t * d_qrows) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_search_args(ix, d_queries, n_queries, k, d_distances, d_ids, fn)) return false;
+        if (!check_set_args(n_queries, set_lims, n_sets, d_qrows, fn)) return false;
+        if (n_sets > 0 && (!d_distances || !d_ids)) { fprintf(stderr, "%s: NULL queries or result pointer\n", fn); return false; }
+        (void)hipSetDevice(ix->device);
+        return sets_device_impl(ix, vectors(d_queries), n_queries, set_lims, n_sets, k, (const int *)d_groups, false, (const uint32_t *)d_allow,
+                                d_distances, d_ids, d_qrows, 0, false);
+    });
+}
+
+bool clip_amd_index_search_sets(struct clip_amd_index * ix, const float * queries, int n_queries, const int64_t * set_lims, int64_t n_sets, int k,
+                                const int32_t * groups, const uint64_t * allow, float * distances, int64_t * ids, int32_t * qrows) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_search_args(ix, queries, n_queries, k, distances, ids, fn)) return false;
+        if (!check_set_args(n_queries, set_lims, n_sets, qrows, fn)) return false;
+        if (n_sets > 0 && (!distances || !ids)) { fprintf(stderr, "%s: NULL queries or result pointer\n", fn); return false; }
+        if (!check_set_groups(ix, groups, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return sets_host_impl(ix, queries, nullptr, n_queries, set_lims, n_sets, k, false, groups, allow, distances, ids, qrows, fn);
+    });
+}
+
+bool clip_amd_index_search_ids_sets(struct clip_amd_index * ix, const int64_t * ids, int64_t n_ids, const int64_t * set_lims, int64_t n_sets, int k,
+                                    int exclude_own, const int32_t * groups, const uint64_t * allow, float * distances, int64_t * out_ids,
+                                    int32_t * qrows) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+        if (n_ids < 0 || n_ids > MAX_ROWS) { fprintf(stderr, "%s: n_ids %lld outside 0 ... %lld\n", fn, (long long)n_ids, (long long)MAX_ROWS); return false; }
+        if (!check_search_args(ix, ids, (int)n_ids, k, distances, out_ids, fn)) return false;
+        if (!check_set_args(n_ids, set_lims, n_sets, qrows, fn)) return false;
+        if (n_sets > 0 && (!distances || !out_ids)) { fprintf(stderr, "%s: NULL queries or result pointer\n", fn); return false; }
+        if (exclude_own && !groups) {
+            fprintf(stderr, "%s: exclude_own needs groups: without them a set has no own group to exclude\n", fn);
+            return false;
+        }
+        if (!check_set_groups(ix, groups, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        std::vector<uint32_t> live;                        // only when rows were removed: every in-range id is live otherwise
+        if (ix->removed > 0 && n_ids > 0) {
+            live.resize(live_bytes(ix->n) / 4);
+            if (!stream_done(ix, fn, hipMemcpyAsync(live.data(), ix->store.live, live.size() * 4, hipMemcpyDeviceToHost, stream_of(ix)))) return false;
+        }
+        for (int64_t t = 0; t < n_ids; t++) {
+            const int64_t id = ids[t];
+            if (id < 0 || id >= ix->n) {
+                fprintf(stderr, "%s: id %lld (entry %lld) outside 0 ... %lld: nothing searched\n", fn, (long long)id, (long long)t, (long long)ix->n - 1);
+                return false;
+            }
+            if (!live.empty() && !((live[(size_t)(id >> 5)] >> (int)(id & 31)) & 1u)) {
+                fprintf(stderr, "%s: id %lld (entry %lld) was removed: nothing searched\n", fn, (long long)id, (long long)t);
+                return false;
+            }
+        }
+        return sets_host_impl(ix, nullptr, ids, n_ids, set_lims, n_sets, k, exclude_own != 0, groups, allow, distances, out_ids, qrows, fn);
+    });
+}
+
+int64_t clip_amd_test_index_sets_block(struct clip_amd_index * ix, int64_t rows) {
+    if (!ix || rows < 0 || rows > GRAPH_BLOCK_MAX) return -1;
+    ix->sets_block = rows;
+    return rows;
+}
+
+float clip_amd_bench_search_sets(int dtype, int64_t n, int dim, int n_sets, int set_size, int k, int group_size, int iters) {
+    return guarded(__func__, -4.f, [&](const char *) {
+        const bool args_ok = n_sets >= 1 && set_size >= 1 && (int64_t)n_sets * set_size <= (1 << 20) && k >= 1 && k <= MAX_K && group_size >= 0;
+        const int nq = args_ok ? n_sets * set_size : 0;
+        return bench_on_gallery(dtype, n, dim, nq, iters, args_ok, false, [&](clip_amd_index * ix, float * src) {
+            const size_t count = (size_t)n_sets * k;
+            float * d_dist = nullptr;
+            int64_t * d_ids = nullptr;
+            int * d_qrows = nullptr, * d_groups = nullptr;
+            std::vector<int64_t> lims((size_t)n_sets + 1);
+            for (int s = 0; s <= n_sets; s++) lims[(size_t)s] = (int64_t)s * set_size;
+            float us = -4.f;
+            bool ok = (group_size < 1 || hipMalloc((void **)&d_groups, (size_t)n * 4) == hipSuccess) && hipMalloc(&d_dist, count * 4) == hipSuccess &&
+                      hipMalloc(&d_ids, count * 8) == hipSuccess && hipMalloc((void **)&d_qrows, count * 4) == hipSuccess;
+            const auto call = [&]() {
+                return sets_device_impl(ix, vectors(src), nq, lims.data(), n_sets, k, d_groups, false, nullptr, d_dist, d_ids, d_qrows, 0, false);
+            };
+            if (ok) {
+                launch_search_fill_random(src, (int64_t)nq * dim, 0xC0FFEEull, nullptr);
+                if (d_groups) {
+                    std::vector<int> g((size_t)n);
+                    for (int64_t r = 0; r < n; r++) g[(size_t)r] = (int)(r / group_size);
+                    ok = hipMemcpy(d_groups, g.data(), (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess;
+                }
+                ok = ok && call() && hipDeviceSynchronize() == hipSuccess;
+            }
+            if (ok) {
+                hipEvent_t e0, e1;
+                (void)hipEventCreate(&e0);
+                (void)hipEventCreate(&e1);
+                (void)hipEventRecord(e0, nullptr);
+                for (int i = 0; ok && i < iters; i++) ok = call();
+                (void)hipEventRecord(e1, nullptr);
+                float ms = -1.f;
+                if (ok && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) us = ms * 1000.f / iters;
+                (void)hipEventDestroy(e0);
+                (void)hipEventDestroy(e1);
+            }
+            for (void * p : {(void *)d_dist, (void *)d_ids, (void *)d_qrows, (void *)d_groups})
+                if (p) (void)hipFree(p);
+            return us;
+        });
     });
 }
 

@@ -9,6 +9,7 @@ build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.In
     python -m clip_cpp_amd.image_search neighbors [-m MODEL] [-v N] [--db DIR] [-n N]
     python -m clip_cpp_amd.image_search label  [-m MODEL] [-v N] [-t N] [--db DIR] [-n N] LABEL [LABEL ...]
     python -m clip_cpp_amd.image_search merge  [-m MODEL] [-v N] --db DIR --from DIR2 [--from DIR3 ...] [-d R]
+    python -m clip_cpp_amd.image_search match  [-m MODEL] [-v N] [-t N] [--db DIR] [-n N] [INDEXED/IMAGE/PATH or /path/to/query/image]
 
 `build` writes DIR/images.index (the CLIPIDX1 file of clip_amd_index_save) and DIR/images.paths (the reference's layout: the model path
 on the first line, then one image path per id).  `search` prints the reference's output: "search results:" / "distance path" at
@@ -41,6 +42,17 @@ images.paths keeps one line per image; DIR/images.regions holds "grid G" and the
 such a database ranks images by their best row (Index.search_grouped with group = image): each image is printed once, with its best row's
 distance and, when that row is a tile, " [x,y,w,h]" behind the path; a query image is encoded whole; --in selects the rows of the matching
 images.  update, merge, dedup, neighbors, label and search --like / -d do not support a database built with --grid yet and say so.
+
+`match` asks a gridded database which other images contain what an image contains: both sides are images made of 1 + G * G rows, and two
+images match through their best pair of regions, one from each (query sets: Index.search_ids_sets / Index.search_sets with group = image).
+`match PATH` with a path that equals a line of images.paths lists the -n (default 5) nearest OTHER images of that indexed image: its
+stored rows are the query set, nothing is decoded or encoded and no tower is needed (the model is loaded only to place the index on its
+device), and the image never matches itself through its own rows.  `match FILE` with any other image file encodes it with
+Clip.encode_image_files(grid=G), G from images.regions, into one set of 1 + G * G vectors.  Each hit is "  %f %s" (distance, path),
+then " [x,y,w,h]" when the stored row of the best pair is a tile (the suffix of `search`), then " <- [x,y,w,h]" when the query row is a
+tile of the query image.  `match` without a path prints every image's matches (Index.knn_graph_grouped, one call) in the output shape of
+`neighbors`: "matches:" at verbosity > 0, per image its path and its hits, images separated by a blank line, and "main: %d images, %d
+matches each".  On a plain database `match` stops before any model is loaded and points to `search --like` / `neighbors`.
 """
 import ctypes as C
 import os
@@ -79,16 +91,16 @@ def _err(msg):
     print(msg, file=sys.stderr, flush=True)
 
 
-def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False, merge=False):
+def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False, merge=False, match=False):
     """Reference-style option parsing (examples/image-search/{build,search}.cpp my_app_params_parse); `dedup`, `neighbors` and `merge` take
     no positional arguments; `update` takes build's directories, but neither a default model nor --dtype (both come from the database);
-    `label` takes the labels; `merge` needs --from at least once."""
+    `label` takes the labels; `merge` needs --from at least once; `match` takes at most one image path."""
     p = dict(threads=4, verbose=1, db=".", dtype="f16", results=1 if label else 5, max_distance=DEDUP_RADIUS if dedup else None,
              model="../models/ggml-model-f16.bin" if build else "", rest=[], like=None)
     p["in"] = []
     if merge:
         p["from"] = []
-    search = not (build or dedup or update or neighbors or label or merge)
+    search = not (build or dedup or update or neighbors or label or merge or match)
     seen = set()
     i = 0
     while i < len(argv):
@@ -99,7 +111,7 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         if build:
             takes["--dtype"] = "dtype"
             takes["--grid"] = "grid"
-        elif neighbors or label:
+        elif neighbors or label or match:
             takes.update({"-n": "results", "--results": "results"})
         elif merge:
             takes.update({"-d": "max_distance", "--max-distance": "max_distance", "--from": "from"})
@@ -132,7 +144,7 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
                 print("main: --grid takes 1 ... %d (1: whole images only), not %d" % (MAX_GRID, p[key]))
                 return None
         elif a in ("-h", "--help"):
-            _help(build, p, dedup, update, neighbors, label, merge)
+            _help(build, p, dedup, update, neighbors, label, merge, match)
             sys.exit(0)
         elif a.startswith("-"):
             print("main: unrecognized argument: %s" % a)
@@ -140,7 +152,7 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         elif dedup or neighbors or merge:
             print("main: unexpected argument: %s" % a)
             return None
-        elif build or update or label:
+        elif build or update or label or match:
             p["rest"].append(a)
         else:
             p["rest"] = argv[i:]     # the query: everything from here on
@@ -150,9 +162,12 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         if p["rest"] or "max_distance" in seen:
             print("main: --like cannot be combined with a query or with -d: it lists the -n nearest images of an indexed one")
             return None
-    elif (not p["rest"] and not (dedup or neighbors or merge)) or (build and p["dtype"] not in ("f16", "f32", "i8")):
+    elif (not p["rest"] and not (dedup or neighbors or merge or match)) or (build and p["dtype"] not in ("f16", "f32", "i8")):
         return None
     if merge and not p["from"]:
+        return None
+    if match and len(p["rest"]) > 1:
+        print("main: match takes one image path, or none for every indexed image")
         return None
     if {"results", "max_distance"} <= seen:
         print("main: -n and -d cannot be combined: -n N prints the N nearest, -d R every image within R")
@@ -160,10 +175,23 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
     return p
 
 
-def _help(build, p, dedup=False, update=False, neighbors=False, label=False, merge=False):
+def _help(build, p, dedup=False, update=False, neighbors=False, label=False, merge=False, match=False):
     radius = ("  -d R, --max-distance R: %s within cosine distance R (<= R). Default: %s. %g is a starting point for embeddings of near-identical"
               " images, not a tuned value: check a few groups of your collection and adjust R")
-    if label:
+    if match:
+        print("Usage: python -m clip_cpp_amd.image_search match [options] [indexed/image/path or /path/to/query/image]")
+        print("\nOn a database built with `build --grid G`: the other images that contain what an image contains. Two images match through")
+        print("their best pair of regions, one from each. A path that equals a line of %s is an indexed image (nothing is decoded or" % PATHS_FILE)
+        print("encoded); any other path is an image file, encoded as its 1 + G*G regions; without a path, every indexed image's matches.")
+        print("\nOptions:")
+        print("  -h, --help: Show this message and exit")
+        print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default (an indexed image needs no tower: the"
+              " model is loaded only to place the index on its device; an image file needs the vision encoder).")
+        print("  -t N, --threads N: Number of host threads that read and decode a query image file. Default: %d" % p["threads"])
+        print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
+        print("  --db <dir>: directory holding %s, %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, REGIONS_FILE, p["db"]))
+        print("  -n N, --results N: Number of matching images per image (at most %d). Default: %d" % (MAX_K, p["results"]))
+    elif label:
         print("Usage: python -m clip_cpp_amd.image_search label [options] LABEL [LABEL ...]")
         print("\nPrints, for every image of an index built by `build`, the labels that fit it best. The labels are encoded as written (no prompt")
         print("template); no image is decoded or encoded again.")
@@ -838,15 +866,98 @@ def merge(argv):
     return 0
 
 
+def _tile_suffix(rows, whole, r, arrow=""):
+    """" [x,y,w,h]" of index row r when it is a tile, "" when it is the whole image"""
+    return "" if whole[r] else "%s [%d,%d,%d,%d]" % ((arrow,) + tuple(rows[r, 1:]))
+
+
+def match(argv):
+    import clip_cpp_amd
+    p = _parse(argv, build=False, match=True)
+    if p is None:
+        _help(False, dict(threads=4, verbose=1, db=".", results=5), match=True)
+        return 1
+    try:
+        regions = read_regions(p["db"])
+    except ValueError as e:
+        _err("main: %s" % e)
+        return 1
+    if regions is None:
+        _err("main: the database in '%s' was not built with --grid (it holds no %s): `match` compares images region by region; on a plain "
+             "database use `search --like PATH` for one image or `neighbors` for all" % (p["db"], REGIONS_FILE))
+        return 1
+    image_paths = _read_db(p, regions)
+    if image_paths is None:
+        return 1
+    grid, rows = regions
+    groups = rows[:, 0]
+    whole = np.ones(len(rows), dtype=np.bool_)
+    whole[1:] = groups[1:] != groups[:-1]          # an image's first row is the whole image, the tiles follow
+    query = p["rest"][0] if p["rest"] else None
+    like_id = image_paths.index(query) if query in image_paths else None
+    try:
+        clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])
+    except RuntimeError:
+        print("main: Unable to load model from %s" % p["model"])
+        return 1
+    k = max(1, min(p["results"], MAX_K))
+    vecs = boxes = None
+    if query is not None and like_id is None:      # an image file: its 1 + G * G regions are the query set
+        if clip.vision_config["n_layer"] <= 0:
+            _err("main: the model at %s has no vision encoder: image queries need a vision or two-tower model" % p["model"])
+            return 1
+        vecs, ok, _, boxes = clip.encode_image_files([query], normalize=True, n_threads=p["threads"], grid=grid)
+        if not len(ok) or not ok[0]:
+            _err("main: failed to load image from '%s'" % query)
+            return 1
+    index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
+    if vecs is not None and index.dim != vecs.shape[1]:
+        _err("main: the index holds %d-dimensional embeddings, the model makes %d" % (index.dim, vecs.shape[1]))
+        return 1
+
+    def show(dist, ids, qsuffix):
+        for t, (d, r) in enumerate(zip(dist, ids)):
+            if r >= 0 and p["results"] > 0:
+                print("  %f %s%s%s" % (d, image_paths[groups[r]], _tile_suffix(rows, whole, r), qsuffix(t)))
+
+    if query is None:                              # every image's nearest other images, by best region pair
+        labels, dist, ids, qids = index.knn_graph_grouped(k, groups)
+        if p["verbose"] > 0:
+            print("matches:")
+        for i, img in enumerate(labels):
+            if i:
+                print()
+            print(image_paths[img])
+            show(dist[i], ids[i], lambda t: _tile_suffix(rows, whole, qids[i, t], " <-"))
+        print("main: %d images, %d matches each" % (len(labels), k if p["results"] > 0 else 0))
+    else:
+        if like_id is not None:
+            own = np.flatnonzero(groups == like_id)
+            dist, ids, qrows = index.search_ids_sets(own, [0, len(own)], k, groups=groups, exclude_own=True)
+            qsuffix = lambda t: _tile_suffix(rows, whole, own[qrows[0, t]], " <-")
+        else:
+            dist, ids, qrows = index.search_sets(vecs, [0, len(vecs)], k, groups=groups)
+            qsuffix = lambda t: "" if qrows[0, t] == 0 else " <- [%d,%d,%d,%d]" % tuple(boxes[qrows[0, t]])
+        if p["verbose"] > 0:
+            print("search results:")
+            print("distance path")
+        show(dist[0], ids[0], qsuffix)
+    sys.stdout.flush()
+    index.close()
+    clip.close()
+    return 0
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
-    commands = {"build": build, "update": update, "search": search, "dedup": dedup, "neighbors": neighbors, "label": label, "merge": merge}
+    commands = {"build": build, "update": update, "search": search, "dedup": dedup, "neighbors": neighbors, "label": label, "merge": merge, "match": match}
     if not argv or argv[0] not in commands:
         print("Usage: python -m clip_cpp_amd.image_search {build|search|dedup} [options] ...  (-h after the command for its options)")
         print("       python -m clip_cpp_amd.image_search update [options] dir [more dirs]  (an existing database brought in line with the disk)")
         print("       python -m clip_cpp_amd.image_search neighbors [options]  (every indexed image's nearest other images; search --like PATH for one)")
         print("       python -m clip_cpp_amd.image_search label [options] LABEL [LABEL ...]  (every indexed image's best-fitting labels)")
         print("       python -m clip_cpp_amd.image_search merge [options] --db DIR --from DIR2 [--from DIR3 ...]  (append databases, nothing encoded twice)")
+        print("       python -m clip_cpp_amd.image_search match [options] [IMAGE]  (a --grid database: the images that share a region with IMAGE, or with each other)")
         return 1
     return commands[argv[0]](argv[1:])
 

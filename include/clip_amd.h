@@ -261,6 +261,40 @@ float clip_amd_bench_search(int dtype, int64_t n, int dim, int n_queries, int k,
 /* The same for clip_amd_index_search_grouped_device over the same seeded rows and queries, row r in group r / group_size (group_size >= 1).
  * Used by scripts/regions_bench.py. */
 float clip_amd_bench_search_grouped(int dtype, int64_t n, int dim, int n_queries, int k, int group_size, int iters);
+/* Query sets: a set of query rows stands for one thing (the regions of one image) and its result is the best stored rows over all of its
+ * rows, each key at most once, with the query row that matched.  set_lims: host int64 [n_sets + 1], starting at 0, non-decreasing and
+ * ending at n_queries, in the style of the lims of range_search; set s is the query rows set_lims[s] ... set_lims[s + 1] - 1; an empty set
+ * is legal and gives an all-empty result.  groups as for search_grouped, or NULL: every row is its own key.
+ * For set s take every pair (query row q of the set, eligible stored row r), eligible as for search_subset, ordered by distance ascending,
+ * then r, then q; a pair is kept when the key of r (groups[r]; NULL groups: r) has not been seen earlier in the set's walk; the walk stops
+ * at k kept pairs.  Per set: distances [k] f32, ids [k] int64 (the stored row), qrows [k] int32 (the query row's index within the call);
+ * the tail is +INFINITY / -1 / -1.  A distance is, bit for bit, what clip_amd_index_search reports for that (query, row) pair: with every
+ * set of size one the result is search_grouped's (NULL groups: search_subset's) and qrows counts up.  A set's result does not depend on
+ * the other sets of the call or on how the call is cut into passes internally.  1 <= k <= 1024, 0 <= n_sets < 2^31.
+ * Host form: host arrays, synchronous; device memory beyond the index is the fixed workspace of knn_graph (query blocks one after
+ * another), whatever n_queries and n_sets.  Device form: queries, groups, allow and the three outputs in HBM (groups and allow trusted),
+ * asynchronous on the context's stream; set_lims stays a host array because it shapes the launches and is read before the call returns.
+ * search_ids_sets: the query rows are the stored rows ids[0 ... n_ids), gathered bit for bit as search_ids does (a row is not excluded as
+ * "self"); exclude_own != 0: a pair (q, r) is not eligible when groups[r] == groups[ids[q]], so a group never matches itself through any
+ * pair of its own rows; it needs groups.  An id out of range or removed returns false, names the id, launches nothing and leaves the
+ * outputs untouched, as for search_ids.
+ * Checked before any launch, outputs untouched: set_lims not starting at 0, decreasing or not ending at the number of query rows; a
+ * negative group (host forms); exclude_own with NULL groups; k out of range; NULL pointers; everything search refuses. */
+bool clip_amd_index_search_sets(struct clip_amd_index * ix, const float * queries, int n_queries, const int64_t * set_lims, int64_t n_sets, int k,
+                                const int32_t * groups, const uint64_t * allow, float * distances, int64_t * ids, int32_t * qrows);
+bool clip_amd_index_search_sets_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, const int64_t * set_lims, int64_t n_sets,
+                                       int k, const int32_t * d_groups, const uint64_t * d_allow, float * d_distances, int64_t * d_ids,
+                                       int32_t * d_qrows);
+bool clip_amd_index_search_ids_sets(struct clip_amd_index * ix, const int64_t * ids, int64_t n_ids, const int64_t * set_lims, int64_t n_sets, int k,
+                                    int exclude_own, const int32_t * groups, const uint64_t * allow, float * distances, int64_t * out_ids,
+                                    int32_t * qrows);
+/* test hook: the query rows per block of the two host forms above on this index from now on (1 ... 65408; 0: automatic), so that a test
+ * can make small sets straddle blocks.  Returns the value set, -1 for a NULL index or another value. */
+int64_t clip_amd_test_index_sets_block(struct clip_amd_index * ix, int64_t rows);
+/* Average device time (microseconds, HIP events) of one clip_amd_index_search_sets_device of n_sets sets of set_size seeded random query
+ * rows each over the seeded rows of clip_amd_bench_search, row r in group r / group_size (0: no groups); < 0 on error.  Used by
+ * scripts/sets_bench.py. */
+float clip_amd_bench_search_sets(int dtype, int64_t n, int dim, int n_sets, int set_size, int k, int group_size, int iters);
 /* The same with an allowed set over the same seeded rows and queries (clip_amd_index_search_subset_device): allowed_fraction in [0, 1] of
  * the ids, a seeded random selection or, contiguous != 0, one id range in the middle of the index.  Used by scripts/subset_bench.py. */
 float clip_amd_bench_search_subset(int dtype, int64_t n, int dim, int n_queries, int k, float allowed_fraction, int contiguous, int iters);
