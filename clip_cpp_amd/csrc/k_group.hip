@@ -21,51 +21,31 @@
 //                         k_search.hip cannot drop a group that both lists hold.)  A chunk's list is enough: if the best row of group g is
 //                         among the k best groups overall, fewer than k groups rank above it inside its own chunk too.
 // Selection (wave_group_select, one wave, three LDS arrays of the sort size): load (distance, id) and look the group up by row id (groups
-// are not carried in the candidate buffers); bitonic sort by (group, distance, id); every entry whose predecessor has the same group
-// becomes an empty slot; bitonic sort by (distance, id).  Both orders are strict total orders over the real entries (ids are unique), so
+// are not carried in the candidate buffers); bitonic sort by (group, distance, id) (wave_sort of search_common.h with group_first); every
+// entry whose predecessor has the same group becomes an empty slot (wave_blank_repeats, shared with k_sets.hip); bitonic sort by (distance,
+// id).  Both orders are strict total orders over the real entries (ids are unique), so
 // the outcome does not depend on the sort size or on how the buffer was filled.  The sorts run over the power of two that holds the
 // entries present, not the whole buffer.
-// LDS per scan workgroup: 2 * 16 QT * 4 + 4 waves * 3 arrays * P * 4 bytes, P = search_sort_size(k) <= 2048: 96.5 KB at k > 512 (one
-// workgroup per CU, through the opt-in for more than 64 KB as the plain scan's), 24.5 KB up to k = 256.  The merge needs 3 * 4 * (power of
+// LDS per scan workgroup (scan_lds_bytes of search_scan.h, three arrays): 96.5 KB at k > 512 (one workgroup per CU, through the opt-in for more than
+// 64 KB as the plain scan's), 24.5 KB up to k = 256.  The merge needs 3 * 4 * (power of
 // two >= 2 k) <= 24 KB.  search_finish_kernel of k_search.hip turns the last list into distances and int64 ids.
 
 #include <cfloat>
 #include <climits>
 
-#include "search_common.h"
+#include "search_scan.h"
 
 namespace clipamd {
 
 namespace {
 
-constexpr int GSCAN_THREADS = 256;
-constexpr int GROWS_PER_ITER = 64;     // 4 waves x 16 rows
-
-// strict total order (group ascending, then `better`); empty slots carry group INT_MAX, distance +inf, id INT_MAX and sort last
-__device__ __forceinline__ bool group_first(int ga, float da, int ia, int gb, float db, int ib) {
-    return ga < gb || (ga == gb && better(da, ia, db, ib));
-}
-
-// wave_sort of search_common.h with the group as the leading key, over three arrays
-__device__ void wave_sort_grouped(float * bs, int * bi, int * bg, int P, int lane) {
-    for (int kk = 2; kk <= P; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int t = lane; t < (P >> 1); t += 64) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i + j;
-                const float sa = bs[i], sb = bs[l];
-                const int ia = bi[i], ib = bi[l];
-                const int ga = bg[i], gb = bg[l];
-                const bool first_half = (i & kk) == 0;
-                const bool sw = first_half ? group_first(gb, sb, ib, ga, sa, ia) : group_first(ga, sa, ia, gb, sb, ib);
-                if (sw) {
-                    bs[i] = sb; bi[i] = ib; bg[i] = gb;
-                    bs[l] = sa; bi[l] = ia; bg[l] = ga;
-                }
-            }
-            wave_lds_sync();
-        }
+// strict total order (group ascending, then `better`) of slots (distance, id, group); empty slots carry distance +inf, id INT_MAX, group
+// INT_MAX and sort last
+struct group_first {
+    __device__ __forceinline__ bool operator()(float da, int ia, int ga, float db, int ib, int gb) const {
+        return ga < gb || (ga == gb && better(da, ia, db, ib));
     }
-}
+};
 
 // The grouped selection over the cnt <= cap entries load(0 ... cnt - 1) (cap a power of two >= 64): afterwards bs / bi hold, sorted by
 // `better`, the best row of every distinct group among them, then empty slots, over [0, M), M = the power of two >= max(cnt, 64) that was
@@ -82,15 +62,8 @@ __device__ int wave_group_select(Load load, int cnt, int cap, const int * __rest
         bg[i] = c.id == INT_MAX ? INT_MAX : groups[c.id];
     }
     wave_lds_sync();
-    wave_sort_grouped(bs, bi, bg, M, lane);
-    // bg is only read here and bs / bi only written, each slot by the lane that owns it
-    for (int i = lane; i < M; i += 64) {
-        if (i > 0 && bg[i] == bg[i - 1]) {
-            bs[i] = INFINITY;
-            bi[i] = INT_MAX;
-        }
-    }
-    wave_lds_sync();
+    wave_sort(group_first(), M, lane, bs, bi, bg);
+    wave_blank_repeats(bg, M, lane, bs, bi);
     wave_sort(bs, bi, M, lane);
     return M;
 }
@@ -127,7 +100,7 @@ struct GroupScanParams {
 };
 
 template <typename T, int QT, bool MASKED, bool OWN>
-__global__ void __launch_bounds__(GSCAN_THREADS) group_scan_kernel(const GroupScanParams p) {
+__global__ void __launch_bounds__(SCAN_THREADS) group_scan_kernel(const GroupScanParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int QB = 16 * QT;
     int * cnt = (int *)smem;                              // [QB]
@@ -142,7 +115,7 @@ __global__ void __launch_bounds__(GSCAN_THREADS) group_scan_kernel(const GroupSc
     const int q0 = blockIdx.y * QB;
     const int64_t lo = (int64_t)chunk * p.rows_per_chunk;
     const int64_t hi = lo + p.rows_per_chunk < p.n ? lo + p.rows_per_chunk : p.n;
-    for (int i = threadIdx.x; i < QB; i += GSCAN_THREADS) {
+    for (int i = threadIdx.x; i < QB; i += SCAN_THREADS) {
         cnt[i] = 0;
         thr[i] = INFINITY;
     }
@@ -151,10 +124,10 @@ __global__ void __launch_bounds__(GSCAN_THREADS) group_scan_kernel(const GroupSc
     const T * qrow[QT];
 #pragma unroll
     for (int j = 0; j < QT; j++) qrow[j] = (const T *)p.q + (size_t)(q0 + j * 16 + frow) * p.Dpad;
-    const int nit = (int)((hi - lo + GROWS_PER_ITER - 1) / GROWS_PER_ITER);
+    const int nit = (int)((hi - lo + ROWS_PER_ITER - 1) / ROWS_PER_ITER);
 
     for (int it = 0; it < nit; it++) {
-        const int64_t r0 = lo + (int64_t)it * GROWS_PER_ITER + wave * 16;
+        const int64_t r0 = lo + (int64_t)it * ROWS_PER_ITER + wave * 16;
         unsigned mbits = 0xffffu;                                             // the wave's 16 rows: 16 aligned bits of one mask word
         if constexpr (MASKED) mbits = r0 < hi ? (p.mask[r0 >> 5] >> (int)(r0 & 16)) & 0xffffu : 0u;
         if (r0 < hi && mbits != 0) {
@@ -212,7 +185,7 @@ __global__ void __launch_bounds__(GSCAN_THREADS) group_scan_kernel(const GroupSc
         if (it + 1 < nit) {
             for (int ql = wave; ql < QB; ql += 4) {
                 const int c = cnt[ql];
-                if (q0 + ql < p.nq && c > p.C - GROWS_PER_ITER) {
+                if (q0 + ql < p.nq && c > p.C - ROWS_PER_ITER) {
                     Cand * buf = p.cand + ((size_t)chunk * p.nq + q0 + ql) * p.C;
                     const int M = wave_group_select([&](int i) { return buf[i]; }, c, p.P, p.groups, bs, bi, bg, lane);
                     const int nc = wave_count_real(bi, M, p.k, lane);
@@ -236,6 +209,34 @@ __global__ void __launch_bounds__(GSCAN_THREADS) group_scan_kernel(const GroupSc
     }
 }
 
+// what the launch path of search_scan.h needs to know of this scan
+struct GroupScan {
+    typedef GroupScanParams Params;
+    static constexpr int ARRAYS = 3;      // LDS arrays of P entries per wave: distances, ids, groups
+    template <typename T, int QT, bool MASKED, bool OWN>
+    static auto kernel() { return group_scan_kernel<T, QT, MASKED, OWN>; }
+    static bool flag(const GroupScanParams & p) { return p.qgroup != nullptr; }
+    static GroupScanParams params(const ScanArgs & a) {
+        GroupScanParams p;
+        p.rows = a.rows;
+        p.q = a.q;
+        p.cand = (Cand *)a.cand;
+        p.groups = a.groups;
+        p.n = a.n;
+        p.Dpad = a.Dpad;
+        p.nq = a.nq;
+        p.k = a.k;
+        p.C = search_candidate_capacity(a.k);
+        p.P = search_sort_size(a.k);
+        p.rows_per_chunk = a.rows_per_chunk;
+        p.rinv = a.rinv;
+        p.qinv = a.qinv;
+        p.mask = a.mask;
+        p.qgroup = a.qgroup;
+        return p;
+    }
+};
+
 // out list i of query q = grouped selection over in lists 2i and 2i + 1 (list 2i alone when it has no partner).  One wave per workgroup;
 // LDS: 3 arrays of P2 = the power of two >= max(2 k, 64).
 __global__ void __launch_bounds__(64) group_merge_kernel(const Cand * __restrict__ in, int64_t in_stride, int n_in, Cand * __restrict__ out,
@@ -257,61 +258,9 @@ __global__ void __launch_bounds__(64) group_merge_kernel(const Cand * __restrict
     for (int t = lane; t < k; t += 64) O[t] = selected(bs, bi, M, t);
 }
 
-template <typename T, int QT, bool MASKED, bool OWN>
-bool launch_gscan_m(const GroupScanParams & p, int n_chunks, hipStream_t stream) {
-    static unsigned long long lds_done = 0;
-    const size_t lds = (size_t)2 * 16 * QT * 4 + (size_t)4 * 3 * p.P * 4;
-    if (lds > 65536) opt_in_dynamic_lds(group_scan_kernel<T, QT, MASKED, OWN>, lds, lds_done);
-    const dim3 grid(n_chunks, (p.nq + 16 * QT - 1) / (16 * QT));
-    hipLaunchKernelGGL((group_scan_kernel<T, QT, MASKED, OWN>), grid, dim3(GSCAN_THREADS), lds, stream, p);
-    return hipGetLastError() == hipSuccess;
-}
-
-template <typename T, int QT>
-bool launch_gscan_t(const GroupScanParams & p, int n_chunks, hipStream_t stream) {
-    if (p.qgroup) return p.mask ? launch_gscan_m<T, QT, true, true>(p, n_chunks, stream) : launch_gscan_m<T, QT, false, true>(p, n_chunks, stream);
-    return p.mask ? launch_gscan_m<T, QT, true, false>(p, n_chunks, stream) : launch_gscan_m<T, QT, false, false>(p, n_chunks, stream);
-}
-
-bool launch_gscan(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq, int qt, int k,
-                  const int * groups, const int * qgroup, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask, hipStream_t stream) {
-    GroupScanParams p;
-    p.rows = rows;
-    p.q = q;
-    p.cand = (Cand *)cand;
-    p.groups = groups;
-    p.n = n;
-    p.Dpad = Dpad;
-    p.nq = nq;
-    p.k = k;
-    p.C = search_candidate_capacity(k);
-    p.P = search_sort_size(k);
-    p.rows_per_chunk = rows_per_chunk;
-    p.rinv = rinv;
-    p.qinv = qinv;
-    p.mask = mask;
-    p.qgroup = qgroup;
-    return with_search_type(dtype, [&](auto t) {
-        using T = decltype(t);
-        if (qt == 4) return launch_gscan_t<T, 4>(p, n_chunks, stream);
-        if (qt == 2) return launch_gscan_t<T, 2>(p, n_chunks, stream);
-        return launch_gscan_t<T, 1>(p, n_chunks, stream);
-    });
-}
-
 }  // namespace
 
-bool launch_search_scan_grouped(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq,
-                                int qt, int k, const int * groups, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask,
-                                hipStream_t stream) {
-    return launch_gscan(rows, rinv, n, Dpad, dtype, q, qinv, nq, qt, k, groups, nullptr, cand, n_chunks, rows_per_chunk, mask, stream);
-}
-
-bool launch_search_scan_grouped_own(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq,
-                                    int qt, int k, const int * groups, const int * qgroup, void * cand, int n_chunks, int64_t rows_per_chunk,
-                                    const uint32_t * mask, hipStream_t stream) {
-    return launch_gscan(rows, rinv, n, Dpad, dtype, q, qinv, nq, qt, k, groups, qgroup, cand, n_chunks, rows_per_chunk, mask, stream);
-}
+bool launch_group_scan(const ScanArgs & a, hipStream_t stream) { return launch_scan<GroupScan>(a, stream); }
 
 void launch_search_merge_grouped(const void * in, int64_t in_stride, int n_in, void * out, int nq, int k, const int * groups, hipStream_t stream) {
     int P2 = 64;

@@ -60,20 +60,19 @@
 //   search_fill_allow_kernel benchmark data: an allowed set of a given fraction, seeded random or one contiguous id range.
 // Plain launches on the caller's stream, no LDS past 64 KB but the sort buffers of k > 512 (compact_ids_kernel: 16 KB static; the mask needs
 // none), no scratch.  The score chain (ld_step, mfma_step,
-// scan_distance), the candidate order and wave_sort live in search_common.h, shared with k_join.hip (range search / pairs).
+// scan_distance), the candidate order and wave_sort live in search_common.h, shared with k_join.hip (range search / pairs); the scan's
+// launch path (dtype x QT x MASKED x flag, the LDS size and its opt-in) in search_scan.h, shared with group_scan_kernel of k_group.hip,
+// which is this file's search_scan_kernel with another selection: a change to the loop of one belongs in the other as well.
 
 #include <algorithm>
 #include <cfloat>
 #include <climits>
 
-#include "search_common.h"
+#include "search_scan.h"
 
 namespace clipamd {
 
 namespace {
-
-constexpr int SCAN_THREADS = 256;
-constexpr int ROWS_PER_ITER = 64;     // 4 waves x 16 rows
 
 template <typename T>
 __global__ void __launch_bounds__(256) search_normalize_kernel(const float * __restrict__ src, int64_t n_src, int64_t n_rows, int dim, int Dpad,
@@ -282,6 +281,33 @@ __global__ void __launch_bounds__(SCAN_THREADS) search_scan_kernel(const ScanPar
     }
 }
 
+// what the launch path of search_scan.h needs to know of this scan
+struct PlainScan {
+    typedef ScanParams Params;
+    static constexpr int ARRAYS = 2;      // LDS arrays of P entries per wave: distances, ids
+    template <typename T, int QT, bool MASKED, bool SELF>
+    static auto kernel() { return search_scan_kernel<T, QT, MASKED, SELF>; }
+    static bool flag(const ScanParams & p) { return p.qself != nullptr; }
+    static ScanParams params(const ScanArgs & a) {
+        ScanParams p;
+        p.mask = a.mask;
+        p.qself = a.qself;
+        p.rows = a.rows;
+        p.q = a.q;
+        p.rinv = a.rinv;
+        p.qinv = a.qinv;
+        p.cand = (Cand *)a.cand;
+        p.n = a.n;
+        p.Dpad = a.Dpad;
+        p.nq = a.nq;
+        p.k = a.k;
+        p.C = search_candidate_capacity(a.k);
+        p.P = search_sort_size(a.k);
+        p.rows_per_chunk = a.rows_per_chunk;
+        return p;
+    }
+};
+
 // number of entries of the sorted list L[0..k) that are better than (s, id)
 __device__ __forceinline__ int rank_in(const Cand * L, int k, float s, int id) {
     int a = 0, b = k;
@@ -336,22 +362,6 @@ __global__ void __launch_bounds__(256) search_fill_random_kernel(float * __restr
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     z ^= z >> 31;
     x[i] = (float)(z >> 40) * (1.0f / 8388608.0f) - 1.0f;
-}
-
-template <typename T, int QT, bool MASKED, bool SELF>
-bool launch_scan_m(const ScanParams & p, int n_chunks, hipStream_t stream) {
-    static unsigned long long lds_done = 0;
-    const size_t lds = (size_t)2 * 16 * QT * 4 + (size_t)4 * 2 * p.P * 4;
-    if (lds > 65536) opt_in_dynamic_lds(search_scan_kernel<T, QT, MASKED, SELF>, lds, lds_done);
-    const dim3 grid(n_chunks, (p.nq + 16 * QT - 1) / (16 * QT));
-    hipLaunchKernelGGL((search_scan_kernel<T, QT, MASKED, SELF>), grid, dim3(SCAN_THREADS), lds, stream, p);
-    return hipGetLastError() == hipSuccess;
-}
-
-template <typename T, int QT>
-bool launch_scan_t(const ScanParams & p, int n_chunks, hipStream_t stream) {
-    if (p.qself) return p.mask ? launch_scan_m<T, QT, true, true>(p, n_chunks, stream) : launch_scan_m<T, QT, false, true>(p, n_chunks, stream);
-    return p.mask ? launch_scan_m<T, QT, true, false>(p, n_chunks, stream) : launch_scan_m<T, QT, false, false>(p, n_chunks, stream);
 }
 
 __global__ void __launch_bounds__(256) live_set_kernel(uint32_t * __restrict__ live, int64_t lo, int64_t hi) {
@@ -537,29 +547,8 @@ void launch_search_row_inv(const void * rows, int64_t n, int Dpad, float * inv, 
     hipLaunchKernelGGL(search_row_inv_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, (const int8_t *)rows, n, Dpad, inv);
 }
 
-bool launch_search_scan(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq, int qt,
-                        int k, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask, const int * qself, hipStream_t stream) {
-    ScanParams p;
-    p.mask = mask;
-    p.qself = qself;
-    p.rows = rows;
-    p.q = q;
-    p.rinv = rinv;
-    p.qinv = qinv;
-    p.cand = (Cand *)cand;
-    p.n = n;
-    p.Dpad = Dpad;
-    p.nq = nq;
-    p.k = k;
-    p.C = search_candidate_capacity(k);
-    p.P = search_sort_size(k);
-    p.rows_per_chunk = rows_per_chunk;
-    return with_search_type(dtype, [&](auto t) {
-        using T = decltype(t);
-        if (qt == 4) return launch_scan_t<T, 4>(p, n_chunks, stream);
-        if (qt == 2) return launch_scan_t<T, 2>(p, n_chunks, stream);
-        return launch_scan_t<T, 1>(p, n_chunks, stream);
-    });
+bool launch_search_scan(const ScanArgs & a, hipStream_t stream) {
+    return a.groups ? launch_group_scan(a, stream) : launch_scan<PlainScan>(a, stream);
 }
 
 void launch_search_merge(const void * in, int64_t in_stride, int n_in, void * out, int nq, int k, hipStream_t stream) {

@@ -13,8 +13,9 @@
 //   sets_fold_kernel      one wave per set: the set's result so far (read from the outputs, where the previous pass or the fill left it) is
 //                         the accumulator; it is merged with the sorted k-entry lists of the set's rows of this pass, as many rows per step
 //                         as fit beside the accumulator in the sort buffer (at least one: P2 >= 2 k), by the selection of
-//                         wave_group_select (k_group.hip) with the query row carried along as a fourth array and as the last key of
-//                         both orders: bitonic sort by (key, distance, id, query row); every entry whose predecessor has the same key
+//                         wave_group_select (k_group.hip; the same wave_sort and wave_blank_repeats of search_common.h) with the query
+//                         row carried along as a fourth array and as the last key of both orders: bitonic sort by (key, distance, id, query
+//                         row); every entry whose predecessor has the same key
 //                         becomes an empty slot; bitonic sort by (distance, id, query row).  A (query row, stored row) pair enters once, so
 //                         both orders are strict total orders over the real entries and the outcome does not depend on how a set's rows
 //                         were cut into steps, passes or calls.  Between steps the accumulator stays in LDS; the final distances, int64
@@ -38,34 +39,14 @@ __device__ __forceinline__ bool pair_first(float da, int ia, int qa, float db, i
     return better(da, ia, db, ib) || (da == db && ia == ib && qa < qb);
 }
 
+// slots (distance, id, key, query row); KEYED: the key leads the order
 template <bool KEYED>
-__device__ __forceinline__ bool entry_first(int ga, float da, int ia, int qa, int gb, float db, int ib, int qb) {
-    if constexpr (KEYED) return ga < gb || (ga == gb && pair_first(da, ia, qa, db, ib, qb));
-    return pair_first(da, ia, qa, db, ib, qb);
-}
-
-// wave_sort of search_common.h over four arrays; KEYED: the key leads the order
-template <bool KEYED>
-__device__ void wave_sort_sets(float * bs, int * bi, int * bg, int * bq, int P, int lane) {
-    for (int kk = 2; kk <= P; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int t = lane; t < (P >> 1); t += 64) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i + j;
-                const float sa = bs[i], sb = bs[l];
-                const int ia = bi[i], ib = bi[l];
-                const int ga = bg[i], gb = bg[l];
-                const int qa = bq[i], qb = bq[l];
-                const bool first_half = (i & kk) == 0;
-                const bool sw = first_half ? entry_first<KEYED>(gb, sb, ib, qb, ga, sa, ia, qa) : entry_first<KEYED>(ga, sa, ia, qa, gb, sb, ib, qb);
-                if (sw) {
-                    bs[i] = sb; bi[i] = ib; bg[i] = gb; bq[i] = qb;
-                    bs[l] = sa; bi[l] = ia; bg[l] = ga; bq[l] = qa;
-                }
-            }
-            wave_lds_sync();
-        }
+struct entry_first {
+    __device__ __forceinline__ bool operator()(float da, int ia, int ga, int qa, float db, int ib, int gb, int qb) const {
+        if constexpr (KEYED) return ga < gb || (ga == gb && pair_first(da, ia, qa, db, ib, qb));
+        return pair_first(da, ia, qa, db, ib, qb);
     }
-}
+};
 
 __global__ void __launch_bounds__(256) sets_fill_kernel(float * __restrict__ dist, int64_t * __restrict__ ids, int * __restrict__ qrows, int64_t count) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) {
@@ -131,17 +112,9 @@ __global__ void __launch_bounds__(64) sets_fold_kernel(const Cand * __restrict__
             bg[i] = id == INT_MAX ? INT_MAX : (groups ? groups[id] : id);
         }
         wave_lds_sync();
-        wave_sort_sets<true>(bs, bi, bg, bq, M, lane);
-        // bg is only read here and the others only written, each slot by the lane that owns it
-        for (int i = lane; i < M; i += 64) {
-            if (i > 0 && bg[i] == bg[i - 1]) {
-                bs[i] = INFINITY;
-                bi[i] = INT_MAX;
-                bq[i] = INT_MAX;
-            }
-        }
-        wave_lds_sync();
-        wave_sort_sets<false>(bs, bi, bg, bq, M, lane);      // the best k are the accumulator of the next step, in place
+        wave_sort(entry_first<true>(), M, lane, bs, bi, bg, bq);
+        wave_blank_repeats(bg, M, lane, bs, bi, bq);
+        wave_sort(entry_first<false>(), M, lane, bs, bi, bg, bq);      // the best k are the accumulator of the next step, in place
     }
     for (int i = lane; i < k; i += 64) {
         const bool empty = bi[i] == INT_MAX;

@@ -321,22 +321,32 @@ int search_sort_size(int k);
 void launch_search_prepare(const float * src, int64_t n_src, int64_t n_rows, int dim, int Dpad, int dtype, void * dst, float * inv,
                            hipStream_t stream);
 void launch_search_row_inv(const void * rows, int64_t n, int Dpad, float * inv, hipStream_t stream);
-bool launch_search_scan(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq, int qt,
-                        int k, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask, const int * qself, hipStream_t stream);
+// The scan (search_scan.h; kernels in k_search.hip and, with groups, k_group.hip): nq queries (q / qinv, padded to 16 qt) against the n
+// stored rows in n_chunks chunks of rows_per_chunk.  qself != NULL: row qself[query] is never a candidate of that query.  groups != NULL
+// ([n], device, each >= 0): the grouped scan, which leaves per (chunk, query) the best row of each of the chunk's best k distinct groups,
+// sorted, in the same layout, for launch_search_merge_grouped; with qgroup != NULL ([nq rounded up to 16 qt], device, each query's own
+// group, -1: none) a row of the query's own group is never a candidate either.
+struct ScanArgs {
+    const void * rows = nullptr;
+    const float * rinv = nullptr;
+    int64_t n = 0;
+    int Dpad = 0, dtype = 0;
+    const void * q = nullptr;
+    const float * qinv = nullptr;
+    int nq = 0, qt = 1, k = 0;
+    void * cand = nullptr;
+    int n_chunks = 0;
+    int64_t rows_per_chunk = 0;
+    const uint32_t * mask = nullptr;
+    const int * qself = nullptr;
+    const int * groups = nullptr;
+    const int * qgroup = nullptr;
+};
+bool launch_search_scan(const ScanArgs & a, hipStream_t stream);
 void launch_search_merge(const void * in, int64_t in_stride, int n_in, void * out, int nq, int k, hipStream_t stream);
 void launch_search_finish(const void * in, int64_t in_stride, int nq, int k, float * dist, int64_t * ids, const int * qself, hipStream_t stream);
-// Grouped search (k_group.hip): groups [n] (device, each >= 0) names every row's group; the scan leaves, per (chunk, query), the best row of
-// each of the chunk's best k distinct groups, sorted, in the layout of launch_search_scan (same cand workspace, chunks and mask), and the
-// merge runs the same selection over two lists.  launch_search_finish ends the tree.
-bool launch_search_scan_grouped(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq,
-                                int qt, int k, const int * groups, void * cand, int n_chunks, int64_t rows_per_chunk, const uint32_t * mask,
-                                hipStream_t stream);
+// Grouped search (k_group.hip): the merge runs the grouped selection over two lists of the grouped scan.  launch_search_finish ends the tree.
 void launch_search_merge_grouped(const void * in, int64_t in_stride, int n_in, void * out, int nq, int k, const int * groups, hipStream_t stream);
-// The grouped scan with own-group exclusion: qgroup [nq rounded up to 16 qt] (device) is each query's own group; a row of that group is
-// never a candidate of the query (-1: no row is excluded).
-bool launch_search_scan_grouped_own(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const void * q, const float * qinv, int nq,
-                                    int qt, int k, const int * groups, const int * qgroup, void * cand, int n_chunks, int64_t rows_per_chunk,
-                                    const uint32_t * mask, hipStream_t stream);
 // Query sets (k_sets.hip).  fill: count result slots empty (+inf / -1 / -1).  qgroup: qgroup[t] = groups[qself[t]], -1 where qself[t] < 0
 // (qself as launch_search_gather leaves it).  fold: for the n_fold sets from s_lo on of lims (device; row numbers of the call, the pass
 // holding rows q0 ... q0 + m - 1 as one sorted list of k (score, id) pairs each, `stride` pairs apart), result slot s (dist / ids / qrows

@@ -5,6 +5,9 @@
 // appending one index to another, the count -> lims -> scatter -> sort -> finish sequence of
 // range search and pairs (k_join.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
 // Replaces the usearch index of the reference's examples/image-search (build.cpp / search.cpp) with an exact search on the GPU.
+// Single owners: search_device_impl (the passes of a search: one ScanArgs per scan launch, whatever the selection), search_blocks and
+// query_block (the blocked host forms of stored-row queries), upload_allow / upload_groups / stage_inputs (a call's inputs on the device),
+// check_groups / check_stored_ids (host arguments), time_device / time_wall (the timed part of the benchmark hooks).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -205,19 +208,38 @@ bool effective_mask(clip_amd_index * ix, const uint32_t * d_allow, const uint32_
     return true;
 }
 
-// A host form's inputs on the device: the f32 queries in the staging workspace and, if given, the caller's allowed set (host words; NULL
-// stays NULL)
-bool stage_inputs(clip_amd_index * ix, const float * queries, int nq, const uint64_t * allow, const float *& d_q, const uint32_t *& d_allow) {
-    const size_t qb = (size_t)nq * ix->dim * 4, ab = (size_t)search_allow_words(ix->n) * 4;
+// The caller's allowed set (host words) in its workspace on the device; NULL stays NULL, and an empty index has no set
+bool upload_allow(clip_amd_index * ix, const uint64_t * allow, const uint32_t *& d_allow) {
+    const size_t ab = (size_t)search_allow_words(ix->n) * 4;
     d_allow = nullptr;
-    if (!ensure(ix, ix->stage, qb)) return false;
-    (void)hipMemcpyAsync(ix->stage.p, queries, qb, hipMemcpyHostToDevice, stream_of(ix));
-    d_q = (const float *)ix->stage.p;
     if (!allow || ix->n == 0) return true;
     if (!ensure(ix, ix->abuf, ab)) return false;
     (void)hipMemcpyAsync(ix->abuf.p, allow, ab, hipMemcpyHostToDevice, stream_of(ix));
     d_allow = (const uint32_t *)ix->abuf.p;
     return true;
+}
+
+// The caller's groups (host, one per stored row; NULL stays NULL, and an empty index has none) in their workspace on the device
+bool upload_groups(clip_amd_index * ix, const int32_t * groups, const char * fn, const int *& d_groups) {
+    d_groups = nullptr;
+    if (!groups || ix->n == 0) return true;
+    if (!ensure(ix, ix->gbuf, (size_t)ix->n * sizeof(int32_t))) return false;
+    if (hipMemcpyAsync(ix->gbuf.p, groups, (size_t)ix->n * sizeof(int32_t), hipMemcpyHostToDevice, stream_of(ix)) != hipSuccess) {
+        fprintf(stderr, "%s: the upload of groups failed: %s\n", fn, hipGetErrorString(hipGetLastError()));
+        return false;
+    }
+    d_groups = (const int *)ix->gbuf.p;
+    return true;
+}
+
+// A host form's inputs on the device: the f32 queries in the staging workspace and, if given, the caller's allowed set
+bool stage_inputs(clip_amd_index * ix, const float * queries, int nq, const uint64_t * allow, const float *& d_q, const uint32_t *& d_allow) {
+    const size_t qb = (size_t)nq * ix->dim * 4;
+    d_allow = nullptr;
+    if (!ensure(ix, ix->stage, qb)) return false;
+    (void)hipMemcpyAsync(ix->stage.p, queries, qb, hipMemcpyHostToDevice, stream_of(ix));
+    d_q = (const float *)ix->stage.p;
+    return upload_allow(ix, allow, d_allow);
 }
 
 bool valid_dim(int dim) { return dim >= 4 && dim <= 4096 && dim % 4 == 0; }
@@ -352,13 +374,25 @@ bool search_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, in
             if (!ensure(ix, ix->qgroup, (size_t)m_pad * sizeof(int))) return false;
             launch_sets_qgroup(d_groups, qself, (int *)ix->qgroup.p, m_pad, st);
         }
-        const bool launched =
-            own      ? launch_search_scan_grouped_own(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, ix->qbuf.p, (const float *)ix->qinv.p,
-                                                      m, qt, k, d_groups, (const int *)ix->qgroup.p, ix->cand.p, n_chunks, rpc, mask, st)
-            : d_groups ? launch_search_scan_grouped(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, ix->qbuf.p, (const float *)ix->qinv.p, m,
-                                                  qt, k, d_groups, ix->cand.p, n_chunks, rpc, mask, st)
-                     : launch_search_scan(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, ix->qbuf.p, (const float *)ix->qinv.p, m, qt, k,
-                                          ix->cand.p, n_chunks, rpc, mask, src.exclude_self ? qself : nullptr, st);
+        ScanArgs a;
+        a.rows = ix->store.rows;
+        a.rinv = ix->store.rinv;
+        a.n = ix->n;
+        a.Dpad = ix->Dpad;
+        a.dtype = ix->dtype;
+        a.q = ix->qbuf.p;
+        a.qinv = (const float *)ix->qinv.p;
+        a.nq = m;
+        a.qt = qt;
+        a.k = k;
+        a.cand = ix->cand.p;
+        a.n_chunks = n_chunks;
+        a.rows_per_chunk = rpc;
+        a.mask = mask;
+        a.qself = src.exclude_self ? qself : nullptr;
+        a.groups = d_groups;
+        a.qgroup = own ? (const int *)ix->qgroup.p : nullptr;
+        const bool launched = launch_search_scan(a, st);
         if (!launched) {
             fprintf(stderr, "clip_amd_index_search: scan launch failed\n");
             return false;
@@ -422,30 +456,32 @@ void tiled_chunks(int64_t n, int64_t block, int k, int64_t & rpc, int & n_chunks
     n_chunks = (int)((n + rpc - 1) / rpc);
 }
 
-// The k-NN graph on the host: query blocks of a fixed size, one after another, each scored (scan route: the self-excluding scan over the
-// gathered rows; tiled route: graph_kernel straight from the store), merged, finished into the block's result workspace and copied out.
-bool knn_graph_impl(clip_amd_index * ix, int k, float * distances, int64_t * ids, const char * fn) {
-    hipStream_t st = stream_of(ix);
-    const int64_t n = ix->n;
-    if (n == 0) return true;
-    const bool tiled = ix->knn_route ? ix->knn_route == 2 : n >= KNN_TILED_MIN_ROWS;
-    const uint32_t * mask = ix->removed > 0 ? ix->store.live : nullptr;
+// Query rows per block of a blocked host form whose results take slot_bytes per (row, k) slot on the device: the padded count, within the
+// grids' 16-bit tile counts, the result budget and one chunk's candidate budget, in whole tiles of 128
+int64_t query_block(int64_t nq, int k, size_t slot_bytes) {
     const int C = search_candidate_capacity(k);
-    int64_t block = std::min<int64_t>({(n + 127) / 128 * 128, GRAPH_BLOCK_MAX, (int64_t)(GRAPH_OUT_BUDGET / ((size_t)k * 12)) / 128 * 128,
-                                       (int64_t)(CAND_BUDGET / ((size_t)C * 8)) / 128 * 128});
-    int n_chunks = 1;
-    int64_t rpc = (n + 127) / 128 * 128;
-    if (tiled) tiled_chunks(n, block, k, rpc, n_chunks);
+    return std::min<int64_t>({(nq + 127) / 128 * 128, GRAPH_BLOCK_MAX, (int64_t)(GRAPH_OUT_BUDGET / ((size_t)k * slot_bytes)) / 128 * 128,
+                              (int64_t)(CAND_BUDGET / ((size_t)C * 8)) / 128 * 128});
+}
+
+// "nq stored-row queries, results to the host" (the k-NN graph, the search of one index with the rows of another): query blocks of
+// `block` rows, one after another, each scored, merged, finished into the block's result workspace and copied out.  Scan route: the scan
+// over the rows source(q0, m) names (a QuerySource), under d_allow.  Tiled route: launch(q0, m) runs a kernel of k_graph.hip over n_chunks
+// chunks straight from the stores.
+template <typename Source, typename Launch>
+bool search_blocks(clip_amd_index * ix, int64_t nq, int k, int64_t block, bool tiled, int n_chunks, const uint32_t * d_allow, float * distances,
+                   int64_t * ids, const char * fn, Source && source, Launch && launch) {
+    const int C = search_candidate_capacity(k);
     if (!ensure(ix, ix->outs, (size_t)block * k * 12)) return false;
     int64_t * d_ids = (int64_t *)ix->outs.p;
     float * d_dist = (float *)((char *)ix->outs.p + (size_t)block * k * 8);
-    for (int64_t q0 = 0; q0 < n; q0 += block) {
-        const int m = (int)std::min(block, n - q0);
+    for (int64_t q0 = 0; q0 < nq; q0 += block) {
+        const int m = (int)std::min(block, nq - q0);
         if (!tiled) {
-            if (!search_device_impl(ix, stored_rows(nullptr, q0, true), m, k, nullptr, d_dist, d_ids)) return false;
+            if (!search_device_impl(ix, source(q0, m), m, k, d_allow, d_dist, d_ids)) return false;
         } else {
             if (!ensure(ix, ix->cand, (size_t)n_chunks * m * C * 8)) return false;
-            if (!launch_graph(ix->store.rows, ix->store.rinv, n, q0, m, ix->Dpad, ix->dtype, k, ix->cand.p, n_chunks, rpc, mask, st)) {
+            if (!launch(q0, m)) {
                 fprintf(stderr, "%s: graph launch failed\n", fn);
                 return false;
             }
@@ -457,6 +493,25 @@ bool knn_graph_impl(clip_amd_index * ix, int k, float * distances, int64_t * ids
     return true;
 }
 
+// The k-NN graph on the host, by search_blocks (scan route: the self-excluding scan over the gathered rows; tiled route: graph_kernel
+// straight from the store).
+bool knn_graph_impl(clip_amd_index * ix, int k, float * distances, int64_t * ids, const char * fn) {
+    hipStream_t st = stream_of(ix);
+    const int64_t n = ix->n;
+    if (n == 0) return true;
+    const bool tiled = ix->knn_route ? ix->knn_route == 2 : n >= KNN_TILED_MIN_ROWS;
+    const uint32_t * mask = ix->removed > 0 ? ix->store.live : nullptr;
+    const int64_t block = query_block(n, k, 12);
+    int n_chunks = 1;
+    int64_t rpc = (n + 127) / 128 * 128;
+    if (tiled) tiled_chunks(n, block, k, rpc, n_chunks);
+    return search_blocks(
+        ix, n, k, block, tiled, n_chunks, nullptr, distances, ids, fn, [&](int64_t q0, int) { return stored_rows(nullptr, q0, true); },
+        [&](int64_t q0, int m) {
+            return launch_graph(ix->store.rows, ix->store.rinv, n, q0, m, ix->Dpad, ix->dtype, k, ix->cand.p, n_chunks, rpc, mask, st);
+        });
+}
+
 // Queries from which the automatic route of clip_amd_index_search_index takes the tiled kernel (ids == NULL only); below, the scan route.
 // Measured (profiles/cross_bench.txt, "crossover"; MI355X, dim 512): the smallest swept query count from which on the tiled route's median
 // wall time is below the scan route's on every dtype is 2048 over an index of 256 and of 1024 rows (a call of the tiled route costs about
@@ -464,24 +519,16 @@ bool knn_graph_impl(clip_amd_index * ix, int k, float * distances, int64_t * ids
 // constant is the largest of the three, so the automatic route never takes the slower kernel of a label-sized index.
 constexpr int64_t CROSS_TILED_MIN_QUERIES = 2048;
 
-// clip_amd_index_search_index on the host: the nq queries are the rows ids[0 ... nq) of src (host ids) or, ids NULL, its rows 0 ... nq - 1.
-// Query blocks as in knn_graph_impl, one after another: scored (scan route: the scan over rows gathered from src's store; tiled route:
-// the CROSS graph_kernel straight from both stores), merged, finished into the block's result workspace and copied out.
+// clip_amd_index_search_index on the host: the nq queries are the rows ids[0 ... nq) of src (host ids) or, ids NULL, its rows 0 ... nq - 1,
+// by search_blocks (scan route: the scan over rows gathered from src's store; tiled route: the CROSS graph_kernel straight from both stores).
 bool search_index_impl(clip_amd_index * ix, const clip_amd_index * src, const int64_t * ids, int64_t nq, int k, const uint64_t * allow,
                        float * distances, int64_t * out_ids, const char * fn) {
     hipStream_t st = stream_of(ix);
     if (nq == 0) return true;
     const bool tiled = !ids && ix->n > 0 && (ix->cross_route ? ix->cross_route == 2 : nq >= CROSS_TILED_MIN_QUERIES);
-    const int C = search_candidate_capacity(k);
-    const int64_t block = std::min<int64_t>({(nq + 127) / 128 * 128, GRAPH_BLOCK_MAX, (int64_t)(GRAPH_OUT_BUDGET / ((size_t)k * 12)) / 128 * 128,
-                                             (int64_t)(CAND_BUDGET / ((size_t)C * 8)) / 128 * 128});
+    const int64_t block = query_block(nq, k, 12);
     const uint32_t * d_allow = nullptr;
-    if (allow && ix->n > 0) {
-        const size_t ab = (size_t)search_allow_words(ix->n) * 4;
-        if (!ensure(ix, ix->abuf, ab)) return false;
-        (void)hipMemcpyAsync(ix->abuf.p, allow, ab, hipMemcpyHostToDevice, st);
-        d_allow = (const uint32_t *)ix->abuf.p;
-    }
+    if (!upload_allow(ix, allow, d_allow)) return false;
     const uint32_t * mask = nullptr;
     int n_chunks = 1;
     int64_t rpc = 128;
@@ -489,28 +536,17 @@ bool search_index_impl(clip_amd_index * ix, const clip_amd_index * src, const in
         if (!effective_mask(ix, d_allow, mask)) return false;
         tiled_chunks(ix->n, block, k, rpc, n_chunks);
     }
-    if (!ensure(ix, ix->outs, (size_t)block * k * 12) || (ids && !ensure(ix, ix->idbuf, (size_t)block * 8))) return false;
-    int64_t * d_out = (int64_t *)ix->outs.p;
-    float * d_dist = (float *)((char *)ix->outs.p + (size_t)block * k * 8);
-    for (int64_t q0 = 0; q0 < nq; q0 += block) {
-        const int m = (int)std::min(block, nq - q0);
-        if (!tiled) {
+    if (ids && !ensure(ix, ix->idbuf, (size_t)block * 8)) return false;
+    return search_blocks(
+        ix, nq, k, block, tiled, n_chunks, d_allow, distances, out_ids, fn,
+        [&](int64_t q0, int m) {
             if (ids) (void)hipMemcpyAsync(ix->idbuf.p, ids + q0, (size_t)m * 8, hipMemcpyHostToDevice, st);
-            const QuerySource qs = stored_rows(ids ? (const int64_t *)ix->idbuf.p : nullptr, ids ? 0 : q0, false, src);
-            if (!search_device_impl(ix, qs, m, k, d_allow, d_dist, d_out)) return false;
-        } else {
-            if (!ensure(ix, ix->cand, (size_t)n_chunks * m * C * 8)) return false;
-            if (!launch_graph_cross(ix->store.rows, ix->store.rinv, ix->n, src->store.rows, src->store.rinv, src->n, q0, m, ix->Dpad, ix->dtype, k,
-                                    ix->cand.p, n_chunks, rpc, mask, st)) {
-                fprintf(stderr, "%s: graph launch failed\n", fn);
-                return false;
-            }
-            if (!merge_and_finish(ix, n_chunks, m, k, nullptr, d_dist, d_out)) return false;
-            if (hipGetLastError() != hipSuccess) { fprintf(stderr, "%s: launch failed\n", fn); return false; }
-        }
-        if (!copy_results(ix, d_dist, d_out, (size_t)m * k, distances + (size_t)q0 * k, out_ids + (size_t)q0 * k, fn)) return false;
-    }
-    return true;
+            return stored_rows(ids ? (const int64_t *)ix->idbuf.p : nullptr, ids ? 0 : q0, false, src);
+        },
+        [&](int64_t q0, int m) {
+            return launch_graph_cross(ix->store.rows, ix->store.rinv, ix->n, src->store.rows, src->store.rinv, src->n, q0, m, ix->Dpad, ix->dtype, k,
+                                      ix->cand.p, n_chunks, rpc, mask, st);
+        });
 }
 
 // what clip_amd_index_search_index and clip_amd_index_append ask of their two indexes
@@ -595,26 +631,12 @@ bool sets_host_impl(clip_amd_index * ix, const float * queries, const int64_t * 
     }
     if (nq == 0 || ix->n == 0) return true;
     const uint32_t * d_allow = nullptr;
-    if (allow) {
-        const size_t ab = (size_t)search_allow_words(ix->n) * 4;
-        if (!ensure(ix, ix->abuf, ab)) return false;
-        (void)hipMemcpyAsync(ix->abuf.p, allow, ab, hipMemcpyHostToDevice, st);
-        d_allow = (const uint32_t *)ix->abuf.p;
-    }
-    if (groups) {
-        if (!ensure(ix, ix->gbuf, (size_t)ix->n * sizeof(int32_t))) return false;
-        if (hipMemcpyAsync(ix->gbuf.p, groups, (size_t)ix->n * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) {
-            fprintf(stderr, "%s: the upload of groups failed: %s\n", fn, hipGetErrorString(hipGetLastError()));
-            return false;
-        }
-    }
-    const int * d_groups = groups ? (const int *)ix->gbuf.p : nullptr;
+    const int * d_groups = nullptr;
+    if (!upload_allow(ix, allow, d_allow) || !upload_groups(ix, groups, fn, d_groups)) return false;
     std::vector<int64_t> sets;                             // the sets that hold rows, ascending: together they cover every row in order
     for (int64_t s = 0; s < n_sets; s++)
         if (lims[s + 1] > lims[s]) sets.push_back(s);
-    const int C = search_candidate_capacity(k);
-    int64_t block = std::min<int64_t>({(nq + 127) / 128 * 128, GRAPH_BLOCK_MAX, (int64_t)(GRAPH_OUT_BUDGET / ((size_t)k * 16)) / 128 * 128,
-                                       (int64_t)(CAND_BUDGET / ((size_t)C * 8)) / 128 * 128});
+    int64_t block = query_block(nq, k, 16);
     if (ix->sets_block > 0) block = ix->sets_block;
     const size_t slots = (size_t)block * k;                // a block of m rows holds at most m sets
     if (!ensure(ix, ix->souts, slots * 16) || (ids ? !ensure(ix, ix->idbuf, (size_t)block * 8) : !ensure(ix, ix->stage, (size_t)block * ix->dim * 4)))
@@ -667,10 +689,32 @@ bool sets_host_impl(clip_amd_index * ix, const float * queries, const int64_t * 
     return true;
 }
 
-// the groups of a query-set host form: each of the n >= 0 (NULL: no groups)
-bool check_set_groups(const clip_amd_index * ix, const int32_t * groups, const char * fn) {
+// the groups of a host form: each of the n >= 0 (NULL: no groups)
+bool check_groups(const clip_amd_index * ix, const int32_t * groups, const char * fn) {
     for (int64_t r = 0; groups && r < ix->n; r++)
         if (groups[r] < 0) { fprintf(stderr, "%s: groups[%lld] = %d is negative\n", fn, (long long)r, (int)groups[r]); return false; }
+    return true;
+}
+
+// the host ids of a search by id: each a stored row that was not removed (the live bitmap is fetched only when rows were removed: every
+// in-range id is live otherwise)
+bool check_stored_ids(clip_amd_index * ix, const int64_t * ids, int64_t n, const char * fn) {
+    std::vector<uint32_t> live;
+    if (ix->removed > 0 && n > 0) {
+        live.resize(live_bytes(ix->n) / 4);
+        if (!stream_done(ix, fn, hipMemcpyAsync(live.data(), ix->store.live, live.size() * 4, hipMemcpyDeviceToHost, stream_of(ix)))) return false;
+    }
+    for (int64_t t = 0; t < n; t++) {
+        const int64_t id = ids[t];
+        if (id < 0 || id >= ix->n) {
+            fprintf(stderr, "%s: id %lld (entry %lld) outside 0 ... %lld: nothing searched\n", fn, (long long)id, (long long)t, (long long)ix->n - 1);
+            return false;
+        }
+        if (!live.empty() && !((live[(size_t)(id >> 5)] >> (int)(id & 31)) & 1u)) {
+            fprintf(stderr, "%s: id %lld (entry %lld) was removed: nothing searched\n", fn, (long long)id, (long long)t);
+            return false;
+        }
+    }
     return true;
 }
 
@@ -802,6 +846,36 @@ float bench_on_gallery(int dtype, int64_t n, int dim, int n_queries, int iters, 
     return us;
 }
 
+// The timed part of the benchmark hooks: microseconds per call over iters calls (call() false: a failure), -4 when anything failed.
+// time_device: device time between two HIP events on the default stream around asynchronous calls (the hook made its warm call).
+template <typename F>
+float time_device(int iters, F && call) {
+    bool ok = true;
+    float us = -4.f;
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    (void)hipEventRecord(e0, nullptr);
+    for (int i = 0; ok && i < iters; i++) ok = call();
+    (void)hipEventRecord(e1, nullptr);
+    float ms = -1.f;
+    if (ok && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) us = ms * 1000.f / iters;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return us;
+}
+
+// time_wall: wall time of synchronous calls, after one warm call
+template <typename F>
+float time_wall(int iters, F && call) {
+    bool ok = call();
+    if (!ok) return -4.f;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int i = 0; ok && i < iters; i++) ok = call();
+    const auto t1 = std::chrono::steady_clock::now();
+    return ok ? (float)(std::chrono::duration<double, std::micro>(t1 - t0).count() / iters) : -4.f;
+}
+
 // the body of clip_amd_bench_search (fraction < 0: no allowed set), clip_amd_bench_search_subset and, group_size >= 1,
 // clip_amd_bench_search_grouped (row r in group r / group_size)
 float bench_search_impl(int dtype, int64_t n, int dim, int n_queries, int k, float fraction, bool contiguous, int iters, int group_size = 0) {
@@ -812,6 +886,7 @@ float bench_search_impl(int dtype, int64_t n, int dim, int n_queries, int k, flo
         uint32_t * d_allow = nullptr;
         int * d_groups = nullptr;
         float us = -4.f;
+        const auto call = [&]() { return search_device_impl(ix, vectors(src), n_queries, k, d_allow, d_dist, d_ids, d_groups); };
         bool ok = (fraction < 0.f || hipMalloc((void **)&d_allow, (size_t)search_allow_words(n) * 4) == hipSuccess) &&
                   (group_size < 1 || hipMalloc((void **)&d_groups, (size_t)n * 4) == hipSuccess) && hipMalloc(&d_dist, (size_t)n_queries * k * 4) == hipSuccess && hipMalloc(&d_ids, (size_t)n_queries * k * 8) == hipSuccess;
         if (ok) {
@@ -822,20 +897,9 @@ float bench_search_impl(int dtype, int64_t n, int dim, int n_queries, int k, flo
                 for (int64_t r = 0; r < n; r++) g[(size_t)r] = (int)(r / group_size);
                 ok = hipMemcpy(d_groups, g.data(), (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess;
             }
-            ok = ok && search_device_impl(ix, vectors(src), n_queries, k, d_allow, d_dist, d_ids, d_groups) && hipDeviceSynchronize() == hipSuccess;
+            ok = ok && call() && hipDeviceSynchronize() == hipSuccess;
         }
-        if (ok) {
-            hipEvent_t e0, e1;
-            (void)hipEventCreate(&e0);
-            (void)hipEventCreate(&e1);
-            (void)hipEventRecord(e0, nullptr);
-            for (int i = 0; ok && i < iters; i++) ok = search_device_impl(ix, vectors(src), n_queries, k, d_allow, d_dist, d_ids, d_groups);
-            (void)hipEventRecord(e1, nullptr);
-            float ms = -1.f;
-            if (ok && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) us = ms * 1000.f / iters;
-            (void)hipEventDestroy(e0);
-            (void)hipEventDestroy(e1);
-        }
+        if (ok) us = time_device(iters, call);
         for (void * p : {(void *)d_dist, (void *)d_ids, (void *)d_allow, (void *)d_groups})
             if (p) (void)hipFree(p);
         return us;
@@ -946,23 +1010,18 @@ bool clip_amd_index_search_grouped(struct clip_amd_index * ix, const float * que
     return guarded(__func__, false, [&](const char * fn) {
         if (!check_search_args(ix, queries, n_queries, k, distances, ids, fn)) return false;
         if (!groups && ix->n > 0) { fprintf(stderr, "%s: groups is NULL\n", fn); return false; }
-        for (int64_t r = 0; r < ix->n; r++)
-            if (groups[r] < 0) { fprintf(stderr, "%s: groups[%lld] = %d is negative\n", fn, (long long)r, (int)groups[r]); return false; }
+        if (!check_groups(ix, groups, fn)) return false;
         if (n_queries == 0) return true;
         (void)hipSetDevice(ix->device);
         const float * d_q = nullptr;
         const uint32_t * d_allow = nullptr;
+        const int * d_groups = nullptr;
         const size_t count = (size_t)n_queries * k;
-        if (!stage_inputs(ix, queries, n_queries, allow, d_q, d_allow) || !ensure(ix, ix->outs, count * 12) ||
-            !ensure(ix, ix->gbuf, (size_t)ix->n * sizeof(int32_t)))
+        if (!stage_inputs(ix, queries, n_queries, allow, d_q, d_allow) || !ensure(ix, ix->outs, count * 12) || !upload_groups(ix, groups, fn, d_groups))
             return false;
-        if (ix->n > 0 && hipMemcpyAsync(ix->gbuf.p, groups, (size_t)ix->n * sizeof(int32_t), hipMemcpyHostToDevice, stream_of(ix)) != hipSuccess) {
-            fprintf(stderr, "%s: the upload of groups failed: %s\n", fn, hipGetErrorString(hipGetLastError()));
-            return false;
-        }
         int64_t * d_ids = (int64_t *)ix->outs.p;
         float * d_dist = (float *)((char *)ix->outs.p + count * 8);
-        return search_device_impl(ix, vectors(d_q), n_queries, k, d_allow, d_dist, d_ids, (const int *)ix->gbuf.p) &&
+        return search_device_impl(ix, vectors(d_q), n_queries, k, d_allow, d_dist, d_ids, d_groups) &&
                copy_results(ix, d_dist, d_ids, count, distances, ids, fn);
     });
 }
@@ -986,7 +1045,7 @@ bool clip_amd_index_search_sets(struct clip_amd_index * ix, const float * querie
         if (!check_search_args(ix, queries, n_queries, k, distances, ids, fn)) return false;
         if (!check_set_args(n_queries, set_lims, n_sets, qrows, fn)) return false;
         if (n_sets > 0 && (!distances || !ids)) { fprintf(stderr, "%s: NULL queries or result pointer\n", fn); return false; }
-        if (!check_set_groups(ix, groups, fn)) return false;
+        if (!check_groups(ix, groups, fn)) return false;
         (void)hipSetDevice(ix->device);
         return sets_host_impl(ix, queries, nullptr, n_queries, set_lims, n_sets, k, false, groups, allow, distances, ids, qrows, fn);
     });
@@ -1005,24 +1064,9 @@ bool clip_amd_index_search_ids_sets(struct clip_amd_index * ix, const int64_t * 
             fprintf(stderr, "%s: exclude_own needs groups: without them a set has no own group to exclude\n", fn);
             return false;
         }
-        if (!check_set_groups(ix, groups, fn)) return false;
+        if (!check_groups(ix, groups, fn)) return false;
         (void)hipSetDevice(ix->device);
-        std::vector<uint32_t> live;                        // only when rows were removed: every in-range id is live otherwise
-        if (ix->removed > 0 && n_ids > 0) {
-            live.resize(live_bytes(ix->n) / 4);
-            if (!stream_done(ix, fn, hipMemcpyAsync(live.data(), ix->store.live, live.size() * 4, hipMemcpyDeviceToHost, stream_of(ix)))) return false;
-        }
-        for (int64_t t = 0; t < n_ids; t++) {
-            const int64_t id = ids[t];
-            if (id < 0 || id >= ix->n) {
-                fprintf(stderr, "%s: id %lld (entry %lld) outside 0 ... %lld: nothing searched\n", fn, (long long)id, (long long)t, (long long)ix->n - 1);
-                return false;
-            }
-            if (!live.empty() && !((live[(size_t)(id >> 5)] >> (int)(id & 31)) & 1u)) {
-                fprintf(stderr, "%s: id %lld (entry %lld) was removed: nothing searched\n", fn, (long long)id, (long long)t);
-                return false;
-            }
-        }
+        if (!check_stored_ids(ix, ids, n_ids, fn)) return false;
         return sets_host_impl(ix, nullptr, ids, n_ids, set_lims, n_sets, k, exclude_own != 0, groups, allow, distances, out_ids, qrows, fn);
     });
 }
@@ -1059,18 +1103,7 @@ float clip_amd_bench_search_sets(int dtype, int64_t n, int dim, int n_sets, int 
                 }
                 ok = ok && call() && hipDeviceSynchronize() == hipSuccess;
             }
-            if (ok) {
-                hipEvent_t e0, e1;
-                (void)hipEventCreate(&e0);
-                (void)hipEventCreate(&e1);
-                (void)hipEventRecord(e0, nullptr);
-                for (int i = 0; ok && i < iters; i++) ok = call();
-                (void)hipEventRecord(e1, nullptr);
-                float ms = -1.f;
-                if (ok && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) us = ms * 1000.f / iters;
-                (void)hipEventDestroy(e0);
-                (void)hipEventDestroy(e1);
-            }
+            if (ok) us = time_device(iters, call);
             for (void * p : {(void *)d_dist, (void *)d_ids, (void *)d_qrows, (void *)d_groups})
                 if (p) (void)hipFree(p);
             return us;
@@ -1300,31 +1333,12 @@ bool clip_amd_index_search_ids(struct clip_amd_index * ix, const int64_t * ids, 
         if (n_ids == 0) return true;
         (void)hipSetDevice(ix->device);
         hipStream_t st = stream_of(ix);
-        std::vector<uint32_t> live;                        // only when rows were removed: every in-range id is live otherwise
-        if (ix->removed > 0) {
-            live.resize(live_bytes(ix->n) / 4);
-            if (!stream_done(ix, fn, hipMemcpyAsync(live.data(), ix->store.live, live.size() * 4, hipMemcpyDeviceToHost, st))) return false;
-        }
-        for (int t = 0; t < n_ids; t++) {
-            const int64_t id = ids[t];
-            if (id < 0 || id >= ix->n) {
-                fprintf(stderr, "%s: id %lld (entry %d) outside 0 ... %lld: nothing searched\n", fn, (long long)id, t, (long long)ix->n - 1);
-                return false;
-            }
-            if (!live.empty() && !((live[(size_t)(id >> 5)] >> (int)(id & 31)) & 1u)) {
-                fprintf(stderr, "%s: id %lld (entry %d) was removed: nothing searched\n", fn, (long long)id, t);
-                return false;
-            }
-        }
-        const size_t count = (size_t)n_ids * k, ab = (size_t)search_allow_words(ix->n) * 4;
+        if (!check_stored_ids(ix, ids, n_ids, fn)) return false;
+        const size_t count = (size_t)n_ids * k;
         const uint32_t * d_allow = nullptr;
         if (!ensure(ix, ix->idbuf, (size_t)n_ids * 8) || !ensure(ix, ix->outs, count * 12)) return false;
         (void)hipMemcpyAsync(ix->idbuf.p, ids, (size_t)n_ids * 8, hipMemcpyHostToDevice, st);
-        if (allow) {
-            if (!ensure(ix, ix->abuf, ab)) return false;
-            (void)hipMemcpyAsync(ix->abuf.p, allow, ab, hipMemcpyHostToDevice, st);
-            d_allow = (const uint32_t *)ix->abuf.p;
-        }
+        if (!upload_allow(ix, allow, d_allow)) return false;
         int64_t * d_out = (int64_t *)ix->outs.p;
         float * d_dist = (float *)((char *)ix->outs.p + count * 8);
         return search_device_impl(ix, stored_rows((const int64_t *)ix->idbuf.p, 0, exclude_self != 0), n_ids, k, d_allow, d_dist, d_out) &&
@@ -1407,13 +1421,8 @@ float clip_amd_bench_cross(int dtype, int64_t n_rows, int64_t n_queries, int dim
                 std::vector<float> dist((size_t)n_queries * k);
                 std::vector<int64_t> out((size_t)n_queries * k);
                 ix->cross_route = route;
-                ok = hipDeviceSynchronize() == hipSuccess && search_index_impl(ix, src, nullptr, n_queries, k, nullptr, dist.data(), out.data(), fn);   // a warm call
-                if (ok) {
-                    const auto t0 = std::chrono::steady_clock::now();
-                    for (int i = 0; ok && i < iters; i++) ok = search_index_impl(ix, src, nullptr, n_queries, k, nullptr, dist.data(), out.data(), fn);
-                    const auto t1 = std::chrono::steady_clock::now();
-                    if (ok) us = (float)(std::chrono::duration<double, std::micro>(t1 - t0).count() / iters);
-                }
+                if (hipDeviceSynchronize() == hipSuccess)
+                    us = time_wall(iters, [&]() { return search_index_impl(ix, src, nullptr, n_queries, k, nullptr, dist.data(), out.data(), fn); });
             }
             (void)hipDeviceSynchronize();
             free_index(src);
@@ -1435,15 +1444,8 @@ float clip_amd_bench_knn(int dtype, int64_t n, int dim, int k, int route, int it
             std::vector<float> dist((size_t)n * k);
             std::vector<int64_t> ids((size_t)n * k);
             ix->knn_route = route;
-            float us = -4.f;
-            bool ok = hipDeviceSynchronize() == hipSuccess && knn_graph_impl(ix, k, dist.data(), ids.data(), fn);      // a warm call
-            if (ok) {
-                const auto t0 = std::chrono::steady_clock::now();
-                for (int i = 0; ok && i < iters; i++) ok = knn_graph_impl(ix, k, dist.data(), ids.data(), fn);
-                const auto t1 = std::chrono::steady_clock::now();
-                if (ok) us = (float)(std::chrono::duration<double, std::micro>(t1 - t0).count() / iters);
-            }
-            return us;
+            if (hipDeviceSynchronize() != hipSuccess) return -4.f;
+            return time_wall(iters, [&]() { return knn_graph_impl(ix, k, dist.data(), ids.data(), fn); });
         });
     });
 }
@@ -1478,13 +1480,10 @@ float clip_amd_bench_range(int dtype, int64_t n, int dim, int n_queries, float r
             int64_t tot = hipDeviceSynchronize() == hipSuccess ? join_impl(ix, d_q, n_queries, pairs, radius, nullptr, lims.data(), nullptr, nullptr, 0, fn) : -1;
             std::vector<float> dist((size_t)std::max<int64_t>(tot, 1));
             std::vector<int64_t> ids(dist.size());
-            if (tot >= 0) tot = join_impl(ix, d_q, n_queries, pairs, radius, nullptr, lims.data(), dist.data(), ids.data(), tot, fn);
             if (tot >= 0) {
-                const auto t0 = std::chrono::steady_clock::now();
-                for (int i = 0; tot >= 0 && i < iters; i++)
-                    tot = join_impl(ix, d_q, n_queries, pairs, radius, nullptr, lims.data(), dist.data(), ids.data(), (int64_t)dist.size(), fn);
-                const auto t1 = std::chrono::steady_clock::now();
-                if (tot >= 0) us = (float)(std::chrono::duration<double, std::micro>(t1 - t0).count() / iters);
+                us = time_wall(iters, [&]() {
+                    return join_impl(ix, d_q, n_queries, pairs, radius, nullptr, lims.data(), dist.data(), ids.data(), (int64_t)dist.size(), fn) >= 0;
+                });
             }
             return us;
         });

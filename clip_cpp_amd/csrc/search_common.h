@@ -1,4 +1,5 @@
-// search_common.h — the score chain of the exact index, shared by k_search.hip (top-k scan) and k_join.hip (range search / pairs).
+// search_common.h — the score chain of the exact index, shared by the top-k scans (k_search.hip, k_group.hip) and k_join.hip
+// (range search / pairs), and the one wave sort of every selection (wave_sort; wave_blank_repeats for the keyed ones of k_group.hip, k_sets.hip).
 //
 // A (query, row) score is bit-identical in both files because both take it from here: the same 16-byte lane loads (ld_step), the same
 // MFMA per stored dtype in the same k order (mfma_step), the same f32 distance expression (scan_distance), with the gallery row as the
@@ -49,25 +50,54 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// bitonic sort of a wave's LDS buffer (P pairs, P a power of two >= 2, better first).  The buffer is private to the wave and LDS operations
-// of one wave are processed in order, so a wave-level barrier (compiler ordering) separates the stages.
-__device__ void wave_sort(float * bs, int * bi, int P, int lane) {
+// Bitonic sort of a wave's LDS buffer: P slots (a power of two >= 2), a slot being entry i of each of the arrays given, first by the strict
+// order `first`, which takes the contents of two slots in the order of the arrays (a..., b...) and says whether a goes before b.  The
+// buffer is private to the wave and LDS operations of one wave are processed in order, so a wave-level barrier (compiler ordering)
+// separates the stages.  The one text of the stage loop: the grouped selection (k_group.hip) and the set fold (k_sets.hip) sort three and
+// four arrays with orders of their own.
+template <typename V> struct SlotPair { V a, b; };      // one array's entries of the two slots a stage compares
+
+template <typename First, typename... V>
+__device__ __forceinline__ void wave_sort(First first, int P, int lane, V *... arr) {
     for (int kk = 2; kk <= P; kk <<= 1) {
         for (int j = kk >> 1; j > 0; j >>= 1) {
             for (int t = lane; t < (P >> 1); t += 64) {
                 const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i + j;   // (j is a power of two)
-                const float sa = bs[i], sb = bs[l];
-                const int ia = bi[i], ib = bi[l];
                 const bool first_half = (i & kk) == 0;
-                const bool sw = first_half ? better(sb, ib, sa, ia) : better(sa, ia, sb, ib);
-                if (sw) {
-                    bs[i] = sb; bi[i] = ib;
-                    bs[l] = sa; bi[l] = ia;
-                }
+                // (a lambda only to name the loaded values: its parameter pack expands in lock-step with arr for the compare and both stores)
+                [&](SlotPair<V>... v) __attribute__((always_inline)) {
+                    const bool sw = first_half ? first(v.b..., v.a...) : first(v.a..., v.b...);
+                    if (sw) {
+                        ((arr[i] = v.b), ...);
+                        ((arr[l] = v.a), ...);
+                    }
+                }(SlotPair<V>{arr[i], arr[l]}...);
             }
             wave_lds_sync();
         }
     }
+}
+
+struct BetterFirst {
+    __device__ __forceinline__ bool operator()(float da, int ia, float db, int ib) const { return better(da, ia, db, ib); }
+};
+
+// the sort of (distance, id) pairs, better first
+__device__ void wave_sort(float * bs, int * bi, int P, int lane) { wave_sort(BetterFirst(), P, lane, bs, bi); }
+
+// The middle step of a keyed selection over M slots sorted with the key leading (then by the order of the result): every entry whose
+// predecessor has the same key becomes an empty slot (+inf, INT_MAX, and INT_MAX in every further array given), which leaves each key's
+// best entry.  bg is only read and the others only written, each slot by the lane that owns it.  The caller sorts by the result's order next.
+template <typename... X>
+__device__ __forceinline__ void wave_blank_repeats(const int * bg, int M, int lane, float * bs, int * bi, X *... more) {
+    for (int i = lane; i < M; i += 64) {
+        if (i > 0 && bg[i] == bg[i - 1]) {
+            bs[i] = INFINITY;
+            bi[i] = INT_MAX;
+            ((more[i] = INT_MAX), ...);
+        }
+    }
+    wave_lds_sync();
 }
 
 // One k-step of a row (or query) for lane group fgrp: fp16 — 32 k per step, the lane's 8 consecutive k (16 bytes); f32 — 16 k per step,

@@ -86,6 +86,10 @@ CASES = [  # dtype, dim, N, nq, k
     ("f16", 1024, 65537, 5, 100), ("f32", 768, 65537, 64, 5), ("f16", 1280, 65537, 1, 1024), ("f16", 512, 65537, 300, 1),
     ("f32", 1024, 65537, 5, 1024), ("f16", 512, 300000, 5, 100), ("f32", 512, 300000, 1, 5), ("f16", 768, 300000, 64, 1024),
     ("f16", 36, 300, 1030, 3), ("f32", 36, 300, 1030, 3),      # two passes over the query chunks, workspaces reused
+    # k = 100 over three chunks of 448 rows: every buffer is shrunk in the middle of its chunk; 1, 2 and 4 query tiles
+    ("f16", 36, 1030, 1, 100), ("f16", 36, 1030, 17, 100), ("f16", 36, 1030, 64, 100), ("f16", 512, 1030, 1, 100), ("f16", 512, 1030, 17, 100),
+    ("f16", 512, 1030, 64, 100), ("f32", 36, 1030, 1, 100), ("f32", 36, 1030, 17, 100), ("f32", 36, 1030, 64, 100), ("f32", 512, 1030, 1, 100),
+    ("f32", 512, 1030, 17, 100), ("f32", 512, 1030, 64, 100),
 ]
 
 

@@ -212,6 +212,70 @@ def test_query_splitting_runs_and_device_form(clip, clip_lib, dtype, dim):
     ix.close()
 
 
+def full_ranking(search, n, allow):
+    """every eligible row of each query in the order of `better`, from two searches over complementary halves of the ids (k = 515 and one
+    chunk each: no selection runs before the end of the scan), merged here by (distance, id)"""
+    lo = np.arange(n) < n // 2
+    a, b = search(n // 2, lo & allow), search(n - n // 2, ~lo & allow)
+    d, i = np.concatenate([a[0], b[0]], axis=1), np.concatenate([a[1], b[1]], axis=1)
+    key = np.where(i < 0, np.iinfo(np.int64).max, i)
+    order = np.stack([np.lexsort((key[r], d[r])) for r in range(len(d))])
+    return np.take_along_axis(d, order, axis=1), np.take_along_axis(i, order, axis=1)
+
+
+def without(ranked, drop):
+    """a ranked list per query with the entries where drop[query, slot] holds taken out, padded"""
+    dist, ids = ranked
+    out_d, out_i = np.full_like(dist, np.inf), np.full_like(ids, -1)
+    for r in range(len(ids)):
+        keep = ~drop[r] & (ids[r] >= 0)
+        out_d[r, :keep.sum()], out_i[r, :keep.sum()] = dist[r][keep], ids[r][keep]
+    return out_d, out_i
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("dim", DIMS)
+def test_selection_in_the_middle_of_the_scan(clip, clip_lib, dtype, dim):
+    """The four selections of the scan kernels where they shrink a buffer before the chunk ends.  k = 100: 356 candidate slots and
+    chunks of 448 rows, so with the threshold still +inf every query's buffer is shrunk after the fifth iteration of 64 rows whatever
+    the data; n = 1030 is three chunks (the last one short, an odd merge tree); 1, 17 and 64 queries take the kernels of 1, 2 and 4 query
+    tiles.  Plain, self-excluding (search_ids), grouped and own-group (search_ids_sets over sets of one row), without a mask and with one
+    that clears an aligned group of 16 rows (not read at all) and a single row.  Groups of 8 consecutive rows leave fewer than k groups
+    in a chunk, so the grouped threshold stays +inf after a shrink; with every row its own group the grouped results must be the plain
+    ones bit for bit.  Expected: the definitions above over full_ranking."""
+    n, k = 1030, 100
+    rows, _, rng = rows_and_queries(dim, n, 1, seed=7)
+    ix = make_index(clip, clip_lib, rows, dtype)
+    g8, g1 = (np.arange(n) // 8).astype(np.int32), np.arange(n, dtype=np.int32)
+    masked = np.ones(n, dtype=bool)
+    masked[512:528] = False
+    masked[77] = False
+    for nq in (1, 17, 64):
+        q = rng.standard_normal((nq, dim), dtype=np.float32)
+        ids = rng.choice(n, nq, replace=False).astype(np.int64)
+        ids[0] = 77                                               # a query row that the mask clears
+        lims, qrow = np.arange(nq + 1), np.arange(nq)[:, None]
+        for allow in (None, masked):
+            al = np.ones(n, dtype=bool) if allow is None else allow
+            tag = (nq, allow is not None)
+            by_vec = full_ranking(lambda kk, a: ix.search(q, kk, allow=a), n, al)
+            by_id = full_ranking(lambda kk, a: ix.search_ids(ids, kk, exclude_self=False, allow=a), n, al)
+            assert np.all((by_vec[1] >= 0).sum(axis=1) == al.sum())
+            cut = lambda r: (r[0][:, :k], r[1][:, :k])
+            plain = ix.search(q, k, allow=allow)
+            assert same(plain, cut(by_vec)), tag
+            no_self = without(by_id, by_id[1] == ids[:, None])
+            assert same(ix.search_ids(ids, k, exclude_self=True, allow=allow), cut(no_self)), tag
+            assert same(ix.search_grouped(q, k, g8, allow=allow), dedup(by_vec, g8, k)), tag
+            assert same(ix.search_grouped(q, k, g1, allow=allow), plain), tag
+            for g in (g8, g1):
+                want = dedup(without(by_id, g[np.maximum(by_id[1], 0)] == g[ids][:, None]), g, k)
+                got = ix.search_ids_sets(ids, lims, k, groups=g, exclude_own=True, allow=allow)
+                assert same(got[:2], want) and np.array_equal(got[2], np.where(want[1] >= 0, qrow, -1)), tag
+            assert same(ix.search_ids_sets(ids, lims, k, groups=g1, exclude_own=True, allow=allow)[:2], cut(no_self)), tag
+    ix.close()
+
+
 def test_bad_arguments(clip, clip_lib):
     n, dim = 40, 36
     rows, q, rng = rows_and_queries(dim, n, 2, seed=6)

@@ -85,6 +85,8 @@ CASES = [  # dim, N, nq, k
     (32, 1, 1, 1), (32, 7, 5, 5), (100, 7, 64, 100), (512, 7, 1, 1024), (100, 1000, 64, 100), (512, 1000, 300, 5), (1280, 1000, 1, 1),
     (768, 65537, 5, 100), (1280, 65537, 1, 1024), (1024, 65537, 64, 5), (512, 300000, 5, 100), (768, 300000, 1, 1024),
     (36, 300, 1030, 3),      # two passes over the query chunks, workspaces reused
+    # k = 100 over three chunks of 448 rows: every buffer is shrunk in the middle of its chunk; 1, 2 and 4 query tiles
+    (36, 1030, 1, 100), (36, 1030, 17, 100), (36, 1030, 64, 100), (512, 1030, 1, 100), (512, 1030, 17, 100), (512, 1030, 64, 100),
 ]
 
 
