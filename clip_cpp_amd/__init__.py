@@ -84,6 +84,8 @@ AMD_SYMBOLS = [
     "clip_amd_image_batch_encode_memory_grid",
     "clip_amd_index_search_sets", "clip_amd_index_search_sets_device", "clip_amd_index_search_ids_sets", "clip_amd_test_index_sets_block",
     "clip_amd_bench_search_sets",
+    "clip_amd_index_search_distinct", "clip_amd_index_search_distinct_device", "clip_amd_index_search_ids_distinct",
+    "clip_amd_test_index_distinct_block", "clip_amd_bench_search_distinct",
 ]
 
 _lib = None
@@ -275,6 +277,16 @@ def lib():
     L.clip_amd_test_index_sets_block.argtypes = [vp, i64]
     L.clip_amd_bench_search_sets.restype = C.c_float
     L.clip_amd_bench_search_sets.argtypes = [i32, i64, i32, i32, i32, i32, i32, i32]
+    L.clip_amd_index_search_distinct.restype = C.c_bool
+    L.clip_amd_index_search_distinct.argtypes = [vp, f32p, i32, i32, C.c_float, i32, u64p, f32p, i64p, C.POINTER(C.c_int32)]
+    L.clip_amd_index_search_distinct_device.restype = C.c_bool
+    L.clip_amd_index_search_distinct_device.argtypes = [vp, vp, i32, i32, C.c_float, i32, vp, vp, vp, vp]
+    L.clip_amd_index_search_ids_distinct.restype = C.c_bool
+    L.clip_amd_index_search_ids_distinct.argtypes = [vp, i64p, i32, i32, C.c_float, i32, i32, u64p, f32p, i64p, C.POINTER(C.c_int32)]
+    L.clip_amd_test_index_distinct_block.restype = i32
+    L.clip_amd_test_index_distinct_block.argtypes = [vp, i32]
+    L.clip_amd_bench_search_distinct.restype = C.c_float
+    L.clip_amd_bench_search_distinct.argtypes = [i32, i64, i32, i32, i32, i32, C.c_float, i32, i32]
     L.clip_amd_bench_search_subset.restype = C.c_float
     L.clip_amd_bench_search_subset.argtypes = [i32, i64, i32, i32, i32, C.c_float, i32, i32]
     L.clip_amd_index_search_ids.restype = C.c_bool
@@ -772,7 +784,11 @@ class Index:
     regions of one image) and the result of a set holds the best stored rows over all of its rows, each group (without groups: each row)
     at most once, with the query row that matched.  search_ids_sets does the same with stored rows as the queries and can leave a set's
     own group out (two gridded images match through their best pair of regions, and no image matches itself); knn_graph_grouped is that
-    for every group of the index at once."""
+    for every group of the index at once.
+
+    search_distinct(queries, k, radius) folds near-duplicates into one hit: over the query's `pool` nearest rows, walked in search's order,
+    a row within `radius` (the distance of pairs) of an earlier kept row is dropped and counted for it; search_ids_distinct does the same
+    with stored rows as the queries.  Suppression is over the pool, not the whole index."""
 
     DTYPES = {"f32": 0, "f16": 1, "i8": 3}
 
@@ -970,6 +986,71 @@ class Index:
                                                        C.c_void_p(d_distances or None), C.c_void_p(d_ids or None), C.c_void_p(d_qrows or None)):
             raise RuntimeError("clip_amd_index_search_sets_device failed (see stderr)")
 
+    MAX_POOL = 1024
+
+    @classmethod
+    def _distinct_args(cls, k, radius, pool):
+        """(k, radius, pool) of a distinct search after the checks of the library that need no device (ValueError): 1 <= k <= pool <= 1024
+        with pool 0 standing for min(1024, max(64, 8 k)), and a radius that is a number.  The pool returned is what the caller passed."""
+        k, pool, radius = int(k), int(pool), float(radius)
+        if k < 1 or k > cls.MAX_POOL:
+            raise ValueError("k = %d outside 1 ... %d" % (k, cls.MAX_POOL))
+        if pool < 0 or pool > cls.MAX_POOL:
+            raise ValueError("pool = %d outside 1 ... %d (0: automatic)" % (pool, cls.MAX_POOL))
+        if pool and k > pool:
+            raise ValueError("k = %d exceeds pool = %d" % (k, pool))
+        if radius != radius:
+            raise ValueError("radius is NaN")
+        return k, radius, pool
+
+    def search_distinct(self, queries, k, radius, pool=0, allow=None):
+        """search with near-duplicates folded into one hit.  The pool L is search(query, pool, allow) without its empty tail; two members
+        with ids i < j are near when d(i, j) <= radius in f32, d being the distance of pairs (so exactly when pairs(radius) lists them).
+        Walking L in order, a member that an earlier kept member is near to is suppressed (and suppresses nothing itself), every other one
+        is kept, until k are kept: (distances f32 [nq, k], ids int64 [nq, k], counts int32 [nq, k]), counts[t] the pool members kept
+        member t suppressed (each counted once, for the first kept member near it; over the whole pool); +inf / -1 / 0 where fewer are
+        kept.  Suppression is over the pool, not the whole index.  1 <= k <= pool <= 1024; pool 0: min(1024, max(64, 8 k)).  radius < 0:
+        search's result with counts 0.  ValueError for a wrong shape of queries, k > pool, or a NaN radius."""
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim not in (1, 2) or q.shape[-1] != self.dim:
+            raise ValueError("queries must be [n, %d] (or one vector of %d values), not %r" % (self.dim, self.dim, q.shape))
+        q = np.ascontiguousarray(q).reshape(-1, self.dim)
+        k, radius, pool = self._distinct_args(k, radius, pool)
+        nq = q.shape[0]
+        words, wp = self._allow(allow)
+        dist = np.empty((nq, k), dtype=np.float32)
+        ids = np.empty((nq, k), dtype=np.int64)
+        counts = np.empty((nq, k), dtype=np.int32)
+        if not lib().clip_amd_index_search_distinct(self._live(), _fp(q), nq, k, radius, pool, wp, _fp(dist), ids.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    counts.ctypes.data_as(C.POINTER(C.c_int32))):
+            raise RuntimeError("clip_amd_index_search_distinct failed (see stderr)")
+        return dist, ids, counts
+
+    def search_ids_distinct(self, ids, k, radius, pool=0, exclude_self=True, allow=None):
+        """search_distinct with the stored rows `ids` (each a live id; duplicates are fine) as the queries, bit for bit as search_ids takes
+        them.  exclude_self: the query's own row is not in the pool, so it is neither a hit nor a suppressor.  Returns (distances, ids,
+        counts) as search_distinct."""
+        a = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        k, radius, pool = self._distinct_args(k, radius, pool)
+        words, wp = self._allow(allow)
+        dist = np.empty((a.size, k), dtype=np.float32)
+        out = np.empty((a.size, k), dtype=np.int64)
+        counts = np.empty((a.size, k), dtype=np.int32)
+        if not lib().clip_amd_index_search_ids_distinct(self._live(), a.ctypes.data_as(C.POINTER(C.c_int64)), a.size, k, radius, pool,
+                                                        int(bool(exclude_self)), wp, _fp(dist), out.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                        counts.ctypes.data_as(C.POINTER(C.c_int32))):
+            raise RuntimeError("clip_amd_index_search_ids_distinct failed (see stderr)")
+        return dist, out, counts
+
+    def search_distinct_device(self, d_queries, n_queries, k, radius, d_distances, d_ids, d_counts, pool=0, d_allow=None):
+        """search_distinct on device pointers (ints): queries [n, dim] f32, d_allow uint64 words (0 / None: every row) -> distances [n, k]
+        f32, ids [n, k] int64, counts [n, k] int32; asynchronous on the context's stream."""
+        k, radius, pool = self._distinct_args(k, radius, pool)
+        if not lib().clip_amd_index_search_distinct_device(self._live(), C.c_void_p(d_queries or None), int(n_queries), k, radius, pool,
+                                                           C.c_void_p(d_allow or None), C.c_void_p(d_distances or None), C.c_void_p(d_ids or None),
+                                                           C.c_void_p(d_counts or None)):
+            raise RuntimeError("clip_amd_index_search_distinct_device failed (see stderr)")
+
     def knn_graph_grouped(self, k, groups):
         """The k-NN graph of the groups (images of a gridded index): (labels, distances, ids, qids).  labels int64 [G]: the distinct groups
         of the live rows, ascending, one result row each; distances f32 / ids int64 / qids int64 [G, k]: the label's k nearest OTHER
@@ -1123,6 +1204,13 @@ def bench_search_sets(dtype, n, dim, n_sets, set_size, k, group_size, iters=10):
     r // group_size, 0: no groups (clip_amd_bench_search_sets); < 0 on error."""
     return float(lib().clip_amd_bench_search_sets(Index.DTYPES[dtype], int(n), int(dim), int(n_sets), int(set_size), int(k), int(group_size),
                                                   int(iters)))
+
+
+def bench_search_distinct(dtype, n, dim, n_queries, k, pool, radius, copies=4, iters=10):
+    """Microseconds per clip_amd_index_search_distinct_device over n seeded rows in groups of a random row and `copies` noisy copies of it
+    (clip_amd_bench_search_distinct); < 0 on error."""
+    return float(lib().clip_amd_bench_search_distinct(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(k), int(pool), float(radius),
+                                                      int(copies), int(iters)))
 
 
 def bench_search_subset(dtype, n, dim, n_queries, k, allowed_fraction, contiguous, iters=10):

@@ -401,4 +401,17 @@ void * launch_join_sort(void * buf, void * tmp, const int64_t * offs, int64_t ns
 void launch_join_finish(const void * in, int64_t total, float * dist, int64_t * ids, hipStream_t stream);
 void launch_join_plant(float * x, int64_t rows, int dim, uint64_t seed, hipStream_t stream);
 
+// Distinct search (k_distinct.hip).  A query's pool: `pool` slots of pool_dist / pool_ids ([nq][pool], device) as launch_search_finish
+// leaves them (sorted, real members first, empty slots id -1).  near: near[q][a][w], [nq][pool][distinct_near_words(pool)] 32-bit words,
+// bit b & 31 of word b >> 5 of rank a set when ranks a < b are two members at distance <= radius (the distance of pairs: row min id as
+// the query against row max id); words of tiles below the diagonal are not written, and pick does not read them.  pick: the walk over a
+// pool, k slots of dist / ids / counts per query (tail +inf / -1 / 0).  Plant: benchmark rows, x [rows][dim] holding rows first_row ...
+// of the gallery, row r with r % (copies + 1) != 0 := the group's first row + amp * uniform(-1, 1) per value.
+int distinct_near_words(int pool);
+void launch_distinct_near(const void * rows, const float * rinv, int Dpad, int dtype, const int64_t * pool_ids, int nq, int pool, float radius,
+                          uint32_t * near, hipStream_t stream);
+void launch_distinct_pick(const float * pool_dist, const int64_t * pool_ids, const uint32_t * near, int nq, int pool, int k, float * dist,
+                          int64_t * ids, int * counts, hipStream_t stream);
+void launch_distinct_plant(float * x, int64_t rows, int dim, int64_t first_row, int copies, float amp, uint64_t seed, hipStream_t stream);
+
 }  // namespace clipamd

@@ -1,7 +1,8 @@
 // search.cpp — the exact nearest-neighbour index of include/clip_amd.h (clip_amd_index_*): device-resident rows, argument checking,
 // query chunking, the scan -> merge tree -> finish launch sequence of k_search.hip, searches by id, the k-NN graph and the search of one
 // index with the rows of another (the gather kernel in front of the same sequence, or the tiled kernel of k_graph.hip in the scan's place),
-// searches with query sets (the set fold of k_sets.hip in the finish's place),
+// searches with query sets (the set fold of k_sets.hip in the finish's place), distinct searches (the pools of a search, then the near
+// bitmap and the walk of k_distinct.hip),
 // appending one index to another, the count -> lims -> scatter -> sort -> finish sequence of
 // range search and pairs (k_join.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
 // Replaces the usearch index of the reference's examples/image-search (build.cpp / search.cpp) with an exact search on the GPU.
@@ -68,6 +69,10 @@ struct clip_amd_index {
     Buf slims;                     // query sets: set_lims of the call (of one query block of a host form) on the device
     Buf souts;                     // query sets, host forms: ids + distances + query rows of one query block's sets
     int64_t sets_block = 0;        // clip_amd_test_index_sets_block: query rows per block of the host forms, 0 automatic
+    Buf dpool;                     // distinct search: distances + ids of one query block's pools
+    Buf dnear;                     // distinct search: the near bitmap of one query block
+    Buf douts;                     // distinct search, host forms: ids + distances + counts of the call
+    int distinct_block = 0;        // clip_amd_test_index_distinct_block: queries per block, 0 automatic
     int knn_route = 0;             // clip_amd_test_index_knn_route: 0 automatic, 1 scan, 2 tiled
     int cross_route = 0;           // clip_amd_test_index_cross_route: the same for clip_amd_index_search_index
     // range search / pairs
@@ -85,9 +90,13 @@ constexpr uint32_t VERSION = 1;
 constexpr int MAX_K = 1024;
 constexpr int64_t MAX_ROWS = 2147483647;
 constexpr size_t CAND_BUDGET = (size_t)512 << 20;       // bytes of candidate workspace per scan launch
+constexpr int PLANT_NONE = 0, PLANT_JOIN = -1;           // bench_on_gallery: what is planted into the seeded rows (> 0: copies per row)
+constexpr float DISTINCT_PLANT_AMP = 0.05f;             // noise amplitude of clip_amd_bench_search_distinct's copies
 constexpr int64_t HOST_CHUNK_ROWS = 65536;              // rows per staging copy (add, save, load)
 constexpr int64_t JOIN_HIT_BUDGET = (int64_t)1 << 21;    // hits the first scoring pass keeps (24 MB); more only when the caller's capacity asks
 constexpr size_t GRAPH_OUT_BUDGET = (size_t)128 << 20;  // bytes of results one query block of the k-NN graph leaves on the device
+constexpr size_t DISTINCT_NEAR_BUDGET = (size_t)64 << 20;   // bytes of near bitmap per query block of a distinct search
+constexpr int DISTINCT_BLOCK_MAX = 4096;                // queries per block of a distinct search (the near grid counts them in z)
 constexpr int64_t GRAPH_BLOCK_MAX = 65408;              // queries per block: 511 tiles of 128 (the merge and graph grids count them in 16 bits)
 
 hipStream_t stream_of(const clip_amd_index * ix) { return ix->ctx ? ix->ctx->stream : nullptr; }
@@ -689,6 +698,90 @@ bool sets_host_impl(clip_amd_index * ix, const float * queries, const int64_t * 
     return true;
 }
 
+// Queries per block of a distinct search: the near bitmap of a block within its budget (or the test hook's value)
+int distinct_block_size(const clip_amd_index * ix, int pool) {
+    if (ix->distinct_block > 0) return ix->distinct_block;
+    const size_t near_q = (size_t)pool * distinct_near_words(pool) * 4;
+    return (int)std::min<size_t>(DISTINCT_BLOCK_MAX, std::max<size_t>(1, DISTINCT_NEAR_BUDGET / near_q));
+}
+
+// Distinct search on the device: query blocks one after another, each searched with k = pool into the pool workspace (the [m][pool]
+// distances and ids after the finish), then the near bitmap over the pool's stored rows and the walk of k_distinct.hip into d_dist / d_ids
+// / d_counts ([nq][k], device).  A query's pool, bitmap and walk are its own, so the cut into blocks does not show in the result.
+bool distinct_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, int k, float radius, int pool, const uint32_t * d_allow,
+                          float * d_dist, int64_t * d_ids, int * d_counts) {
+    hipStream_t st = stream_of(ix);
+    const int block = std::min(distinct_block_size(ix, pool), nq);
+    const size_t slots = (size_t)block * pool;
+    if (!ensure(ix, ix->dpool, slots * 12) || !ensure(ix, ix->dnear, slots * distinct_near_words(pool) * 4)) return false;
+    int64_t * p_ids = (int64_t *)ix->dpool.p;
+    float * p_dist = (float *)((char *)ix->dpool.p + slots * 8);
+    for (int q0 = 0; q0 < nq; q0 += block) {
+        const int m = std::min(block, nq - q0);
+        QuerySource part = src;
+        if (!part.by_id) part.d_q += (size_t)q0 * ix->dim;
+        else if (part.d_ids) part.d_ids += q0;
+        else part.first += q0;
+        if (!search_device_impl(ix, part, m, pool, d_allow, p_dist, p_ids)) return false;
+        launch_distinct_near(ix->store.rows, ix->store.rinv, ix->Dpad, ix->dtype, p_ids, m, pool, radius, (uint32_t *)ix->dnear.p, st);
+        launch_distinct_pick(p_dist, p_ids, (const uint32_t *)ix->dnear.p, m, pool, k, d_dist + (size_t)q0 * k, d_ids + (size_t)q0 * k,
+                             d_counts + (size_t)q0 * k, st);
+        if (hipGetLastError() != hipSuccess) {
+            fprintf(stderr, "clip_amd_index_search_distinct: launch failed\n");
+            return false;
+        }
+    }
+    return true;
+}
+
+// The host forms of the distinct searches: the nq queries are f32 vectors (queries) or stored rows (ids), both on the host.  Query blocks
+// of distinct_block_size, one after another: a block's queries are staged, searched and its results copied out, so nothing on the device
+// grows with nq.
+bool distinct_host_impl(clip_amd_index * ix, const float * queries, const int64_t * ids, int nq, int k, float radius, int pool, bool exclude_self,
+                        const uint64_t * allow, float * distances, int64_t * out_ids, int32_t * counts, const char * fn) {
+    hipStream_t st = stream_of(ix);
+    const uint32_t * d_allow = nullptr;
+    if (!upload_allow(ix, allow, d_allow)) return false;
+    const int block = std::min(distinct_block_size(ix, pool), nq);
+    const size_t slots = (size_t)block * k;
+    if (!ensure(ix, ix->douts, slots * 16) || (ids ? !ensure(ix, ix->idbuf, (size_t)block * 8) : !ensure(ix, ix->stage, (size_t)block * ix->dim * 4)))
+        return false;
+    int64_t * d_out = (int64_t *)ix->douts.p;
+    float * d_dist = (float *)((char *)ix->douts.p + slots * 8);
+    int * d_counts = (int *)((char *)ix->douts.p + slots * 12);
+    for (int q0 = 0; q0 < nq; q0 += block) {
+        const int m = std::min(block, nq - q0);
+        QuerySource qs;
+        if (ids) {
+            (void)hipMemcpyAsync(ix->idbuf.p, ids + q0, (size_t)m * 8, hipMemcpyHostToDevice, st);
+            qs = stored_rows((const int64_t *)ix->idbuf.p, 0, exclude_self);
+        } else {
+            (void)hipMemcpyAsync(ix->stage.p, queries + (size_t)q0 * ix->dim, (size_t)m * ix->dim * 4, hipMemcpyHostToDevice, st);
+            qs = vectors((const float *)ix->stage.p);
+        }
+        if (!distinct_device_impl(ix, qs, m, k, radius, pool, d_allow, d_dist, d_out, d_counts)) return false;
+        const size_t cnt = (size_t)m * k;
+        (void)hipMemcpyAsync(counts + (size_t)q0 * k, d_counts, cnt * 4, hipMemcpyDeviceToHost, st);
+        if (!copy_results(ix, d_dist, d_out, cnt, distances + (size_t)q0 * k, out_ids + (size_t)q0 * k, fn)) return false;      // (the staging buffers are reused)
+    }
+    return true;
+}
+
+// the pool of a distinct search when the caller leaves it to the library
+int auto_pool(int k) { return std::min(MAX_K, std::max(64, 8 * k)); }
+
+// what the distinct searches ask beyond check_search_args; pool 0 becomes the automatic value
+bool check_distinct_args(const clip_amd_index * ix, int nq, int k, float radius, int & pool, const void * counts, const char * fn) {
+    if (nq < 1) { fprintf(stderr, "%s: n_queries %d < 1\n", fn, nq); return false; }
+    if (!counts) { fprintf(stderr, "%s: NULL queries or result pointer\n", fn); return false; }
+    if (std::isnan(radius)) { fprintf(stderr, "%s: radius is NaN\n", fn); return false; }
+    if (pool < 0 || pool > MAX_K) { fprintf(stderr, "%s: pool = %d outside 1 ... %d (0: automatic)\n", fn, pool, MAX_K); return false; }
+    if (pool == 0) pool = auto_pool(k);
+    if (k > pool) { fprintf(stderr, "%s: k = %d exceeds pool = %d\n", fn, k, pool); return false; }
+    if (ix->n == 0) { fprintf(stderr, "%s: the index is empty (0 rows)\n", fn); return false; }
+    return true;
+}
+
 // the groups of a host form: each of the n >= 0 (NULL: no groups)
 bool check_groups(const clip_amd_index * ix, const int32_t * groups, const char * fn) {
     for (int64_t r = 0; groups && r < ix->n; r++)
@@ -818,11 +911,12 @@ struct File {
 
 // The frame of the benchmark hooks: -1 without a device, -3 for arguments outside the index's limits (args_ok: the hook's own), else an
 // index on the default stream holding the seeded gallery of n rows, filled in pieces of HOST_CHUNK_ROWS (a multiple of 64: a planted row
-// and its original share a piece), each piece from its own seed and, planted, with launch_join_plant's near-duplicates.  run(ix, src)
+// and its original share a piece), each piece from its own seed and, plant < 0, with launch_join_plant's near-duplicates or, plant > 0,
+// with launch_distinct_plant's groups of a row and `plant` noisy copies.  run(ix, src)
 // times the hook and returns its microseconds; src, a device scratch of max(piece, n_queries) rows of f32, is its to fill with queries.
 // -4 when anything failed.
 template <typename F>
-float bench_on_gallery(int dtype, int64_t n, int dim, int n_queries, int iters, bool args_ok, bool planted, F && run) {
+float bench_on_gallery(int dtype, int64_t n, int dim, int n_queries, int iters, bool args_ok, int plant, F && run) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return -1.f; }
     if (!valid_dtype(dtype) || !valid_dim(dim) || n < 1 || n > MAX_ROWS || iters < 1 || !args_ok) return -3.f;
@@ -835,7 +929,8 @@ float bench_on_gallery(int dtype, int64_t n, int dim, int n_queries, int iters, 
     for (int64_t r0 = 0; ok && r0 < n; r0 += piece) {
         const int64_t m = std::min(piece, n - r0);
         launch_search_fill_random(src, m * dim, 0x5EEDull + (uint64_t)r0 * dim, nullptr);
-        if (planted) launch_join_plant(src, m, dim, 0xD0Bull + (uint64_t)r0, nullptr);
+        if (plant < 0) launch_join_plant(src, m, dim, 0xD0Bull + (uint64_t)r0, nullptr);
+        if (plant > 0) launch_distinct_plant(src, m, dim, r0, plant, DISTINCT_PLANT_AMP, 0xD157ull + (uint64_t)r0, nullptr);
         ok = add_device_impl(ix, src, m);
     }
     const float us = ok ? run(ix, src) : -4.f;
@@ -880,7 +975,7 @@ float time_wall(int iters, F && call) {
 // clip_amd_bench_search_grouped (row r in group r / group_size)
 float bench_search_impl(int dtype, int64_t n, int dim, int n_queries, int k, float fraction, bool contiguous, int iters, int group_size = 0) {
     const bool args_ok = n_queries >= 1 && k >= 1 && k <= MAX_K && fraction <= 1.0f && group_size >= 0;
-    return bench_on_gallery(dtype, n, dim, n_queries, iters, args_ok, false, [&](clip_amd_index * ix, float * src) {
+    return bench_on_gallery(dtype, n, dim, n_queries, iters, args_ok, PLANT_NONE, [&](clip_amd_index * ix, float * src) {
         float * d_dist = nullptr;
         int64_t * d_ids = nullptr;
         uint32_t * d_allow = nullptr;
@@ -1081,7 +1176,7 @@ float clip_amd_bench_search_sets(int dtype, int64_t n, int dim, int n_sets, int 
     return guarded(__func__, -4.f, [&](const char *) {
         const bool args_ok = n_sets >= 1 && set_size >= 1 && (int64_t)n_sets * set_size <= (1 << 20) && k >= 1 && k <= MAX_K && group_size >= 0;
         const int nq = args_ok ? n_sets * set_size : 0;
-        return bench_on_gallery(dtype, n, dim, nq, iters, args_ok, false, [&](clip_amd_index * ix, float * src) {
+        return bench_on_gallery(dtype, n, dim, nq, iters, args_ok, PLANT_NONE, [&](clip_amd_index * ix, float * src) {
             const size_t count = (size_t)n_sets * k;
             float * d_dist = nullptr;
             int64_t * d_ids = nullptr;
@@ -1105,6 +1200,68 @@ float clip_amd_bench_search_sets(int dtype, int64_t n, int dim, int n_sets, int 
             }
             if (ok) us = time_device(iters, call);
             for (void * p : {(void *)d_dist, (void *)d_ids, (void *)d_qrows, (void *)d_groups})
+                if (p) (void)hipFree(p);
+            return us;
+        });
+    });
+}
+
+bool clip_amd_index_search_distinct_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int k, float radius, int pool,
+                                           const uint64_t * d_allow, float * d_distances, int64_t * d_ids, int32_t * d_counts) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_search_args(ix, d_queries, n_queries, k, d_distances, d_ids, fn)) return false;
+        if (!check_distinct_args(ix, n_queries, k, radius, pool, d_counts, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return distinct_device_impl(ix, vectors(d_queries), n_queries, k, radius, pool, (const uint32_t *)d_allow, d_distances, d_ids, d_counts);
+    });
+}
+
+bool clip_amd_index_search_distinct(struct clip_amd_index * ix, const float * queries, int n_queries, int k, float radius, int pool,
+                                    const uint64_t * allow, float * distances, int64_t * ids, int32_t * counts) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_search_args(ix, queries, n_queries, k, distances, ids, fn)) return false;
+        if (!check_distinct_args(ix, n_queries, k, radius, pool, counts, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return distinct_host_impl(ix, queries, nullptr, n_queries, k, radius, pool, false, allow, distances, ids, counts, fn);
+    });
+}
+
+bool clip_amd_index_search_ids_distinct(struct clip_amd_index * ix, const int64_t * ids, int n_ids, int k, float radius, int pool, int exclude_self,
+                                        const uint64_t * allow, float * distances, int64_t * out_ids, int32_t * counts) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_search_args(ix, ids, n_ids, k, distances, out_ids, fn)) return false;
+        if (!check_distinct_args(ix, n_ids, k, radius, pool, counts, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        if (!check_stored_ids(ix, ids, n_ids, fn)) return false;
+        return distinct_host_impl(ix, nullptr, ids, n_ids, k, radius, pool, exclude_self != 0, allow, distances, out_ids, counts, fn);
+    });
+}
+
+int clip_amd_test_index_distinct_block(struct clip_amd_index * ix, int queries) {
+    if (!ix || queries < 0 || queries > DISTINCT_BLOCK_MAX) return -1;
+    ix->distinct_block = queries;
+    return queries;
+}
+
+float clip_amd_bench_search_distinct(int dtype, int64_t n, int dim, int n_queries, int k, int pool, float radius, int copies, int iters) {
+    return guarded(__func__, -4.f, [&](const char *) {
+        if (pool == 0 && k >= 1 && k <= MAX_K) pool = auto_pool(k);
+        const bool args_ok = n_queries >= 1 && k >= 1 && k <= pool && pool <= MAX_K && !std::isnan(radius) && copies >= 1 && copies < HOST_CHUNK_ROWS;
+        return bench_on_gallery(dtype, n, dim, n_queries, iters, args_ok, copies, [&](clip_amd_index * ix, float * src) {
+            const size_t count = (size_t)n_queries * k;
+            float * d_dist = nullptr;
+            int64_t * d_ids = nullptr;
+            int * d_counts = nullptr;
+            float us = -4.f;
+            const auto call = [&]() { return distinct_device_impl(ix, vectors(src), n_queries, k, radius, pool, nullptr, d_dist, d_ids, d_counts); };
+            bool ok = hipMalloc(&d_dist, count * 4) == hipSuccess && hipMalloc(&d_ids, count * 8) == hipSuccess &&
+                      hipMalloc((void **)&d_counts, count * 4) == hipSuccess;
+            if (ok) {
+                launch_search_fill_random(src, (int64_t)n_queries * dim, 0xC0FFEEull, nullptr);
+                ok = call() && hipDeviceSynchronize() == hipSuccess;
+            }
+            if (ok) us = time_device(iters, call);
+            for (void * p : {(void *)d_dist, (void *)d_ids, (void *)d_counts})
                 if (p) (void)hipFree(p);
             return us;
         });
@@ -1407,7 +1564,7 @@ int clip_amd_test_index_cross_route(struct clip_amd_index * ix, int route) {
 float clip_amd_bench_cross(int dtype, int64_t n_rows, int64_t n_queries, int dim, int k, int route, int iters) {
     return guarded(__func__, -4.f, [&](const char * fn) {
         const bool args_ok = k >= 1 && k <= MAX_K && route >= 0 && route <= 2 && n_queries >= 1 && n_queries <= MAX_ROWS;
-        return bench_on_gallery(dtype, n_rows, dim, 0, iters, args_ok, false, [&](clip_amd_index * ix, float * scratch) {
+        return bench_on_gallery(dtype, n_rows, dim, 0, iters, args_ok, PLANT_NONE, [&](clip_amd_index * ix, float * scratch) {
             // the second index: n_queries rows from seeds of their own, filled in the pieces the gallery was filled in
             clip_amd_index * src = make_index(nullptr, ix->device, dim, dtype);
             bool ok = reserve_rows(src, n_queries);
@@ -1440,7 +1597,7 @@ int clip_amd_test_index_knn_route(struct clip_amd_index * ix, int route) {
 float clip_amd_bench_knn(int dtype, int64_t n, int dim, int k, int route, int iters) {
     return guarded(__func__, -4.f, [&](const char * fn) {
         const bool args_ok = k >= 1 && k <= MAX_K && route >= 0 && route <= 2;
-        return bench_on_gallery(dtype, n, dim, 0, iters, args_ok, false, [&](clip_amd_index * ix, float *) {
+        return bench_on_gallery(dtype, n, dim, 0, iters, args_ok, PLANT_NONE, [&](clip_amd_index * ix, float *) {
             std::vector<float> dist((size_t)n * k);
             std::vector<int64_t> ids((size_t)n * k);
             ix->knn_route = route;
@@ -1471,7 +1628,7 @@ float clip_amd_bench_search_subset(int dtype, int64_t n, int dim, int n_queries,
 float clip_amd_bench_range(int dtype, int64_t n, int dim, int n_queries, float radius, int iters) {
     return guarded(__func__, -4.f, [&](const char * fn) {
         const bool pairs = n_queries == 0;
-        return bench_on_gallery(dtype, n, dim, n_queries, iters, n_queries >= 0 && !std::isnan(radius), true, [&](clip_amd_index * ix, float * src) {
+        return bench_on_gallery(dtype, n, dim, n_queries, iters, n_queries >= 0 && !std::isnan(radius), PLANT_JOIN, [&](clip_amd_index * ix, float * src) {
             float us = -4.f;
             const float * d_q = pairs ? nullptr : src;
             std::vector<int64_t> lims((size_t)(pairs ? n : n_queries) + 1);

@@ -3,8 +3,8 @@ build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.In
 
     python -m clip_cpp_amd.image_search build  [-m MODEL] [-v N] [-t N] [--db DIR] [--dtype f16|f32|i8] [--grid G] dir [more dirs]
     python -m clip_cpp_amd.image_search update [-m MODEL] [-v N] [-t N] [--db DIR] dir [more dirs]
-    python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N | -d R] [--in PREFIX]... [--db DIR] <search text or /path/to/query/image>
-    python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-n N] [--in PREFIX]... [--db DIR] --like INDEXED/IMAGE/PATH
+    python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N | -d R] [--distinct R] [--in PREFIX]... [--db DIR] <search text or /path/to/query/image>
+    python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-n N] [--distinct R] [--in PREFIX]... [--db DIR] --like INDEXED/IMAGE/PATH
     python -m clip_cpp_amd.image_search dedup  [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R]
     python -m clip_cpp_amd.image_search neighbors [-m MODEL] [-v N] [--db DIR] [-n N]
     python -m clip_cpp_amd.image_search label  [-m MODEL] [-v N] [-t N] [--db DIR] [-n N] LABEL [LABEL ...]
@@ -24,7 +24,12 @@ verbosity > 0, then per group, in order of its lowest id, "  %f %s" per member i
 groups separated by a blank line, and "main: %d groups, %d images".
 `search --like PATH` asks for "more like this one": the query is the indexed image whose line in images.paths equals PATH as written
 (Index.search_ids: its stored row, nothing is decoded or encoded, so a text-only or vision-less model is enough); the image itself is not
-listed.  It composes with -n and --in, not with a positional query or -d.  `neighbors` prints the k-NN graph (Index.knn_graph, one call):
+listed.  It composes with -n and --in, not with a positional query or -d.
+`search --distinct R` folds near-duplicates (bursts, resized copies, re-saved files) into one hit (Index.search_distinct /
+Index.search_ids_distinct): walking the ranked list, an image within distance R of an image already listed (the distance of `dedup -d R`)
+is dropped, and a listed image that stands for dropped ones gets " (+%d)", their number, behind its path.  The suppression runs over the
+pool of the max(64, 8 N) nearest eligible images (at most 1024), not over the whole index.  It works with -n, --in and --like, not with
+-d, and not on a database built with --grid.  `neighbors` prints the k-NN graph (Index.knn_graph, one call):
 "neighbours:" at verbosity > 0, then per image, in id order, its path on a line of its own and "  %f %s" per neighbour, the -n (default 5)
 nearest other images, nearest first; images separated by a blank line, and "main: %d images, %d neighbours each".
 `label` labels the whole database (the reference's zsl example applied to a collection): the labels are encoded as written, in one batch,
@@ -120,7 +125,7 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
             if not dedup:
                 takes.update({"-n": "results", "--results": "results"})
         if search:
-            takes.update({"--in": "in", "--like": "like"})
+            takes.update({"--in": "in", "--like": "like", "--distinct": "distinct"})
         if a in takes:
             i += 1
             if i >= len(argv):
@@ -135,10 +140,10 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
                 i += 1
                 continue
             try:
-                p[key] = int(argv[i]) if key in ("threads", "verbose", "results", "grid") else float(argv[i]) if key == "max_distance" else argv[i]
+                p[key] = int(argv[i]) if key in ("threads", "verbose", "results", "grid") else float(argv[i]) if key in ("max_distance", "distinct") else argv[i]
             except ValueError:
                 return None
-            if key == "max_distance" and p[key] != p[key]:      # NaN
+            if key in ("max_distance", "distinct") and p[key] != p[key]:      # NaN
                 return None
             if key == "grid" and not 1 <= p[key] <= MAX_GRID:
                 print("main: --grid takes 1 ... %d (1: whole images only), not %d" % (MAX_GRID, p[key]))
@@ -168,6 +173,9 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         return None
     if match and len(p["rest"]) > 1:
         print("main: match takes one image path, or none for every indexed image")
+        return None
+    if {"distinct", "max_distance"} <= seen:
+        print("main: --distinct and -d cannot be combined: --distinct R thins the -n nearest, -d R prints every image within R")
         return None
     if {"results", "max_distance"} <= seen:
         print("main: -n and -d cannot be combined: -n N prints the N nearest, -d R every image within R")
@@ -272,6 +280,10 @@ def _help(build, p, dedup=False, update=False, neighbors=False, label=False, mer
               " a path matching any prefix is eligible. Works with -n and with -d")
         print("  --like <path>: more like this one: the query is the indexed image whose line in %s equals <path> as written; nothing is"
               " decoded or encoded and the image itself is not listed. Works with -n and --in, not with a query or -d" % PATHS_FILE)
+        print("  --distinct R: fold near-duplicates into one hit: walking the ranked list, an image within cosine distance R (<= R, the distance"
+              " of `dedup -d R`) of an image already listed is dropped, and a listed image is followed by (+N), the number of images dropped"
+              " for it. Suppression runs over the max(64, 8 N) nearest eligible images (at most %d), not the whole index. Works with -n, --in"
+              " and --like, not with -d" % MAX_K)
         print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
 
 
@@ -561,6 +573,8 @@ def search(argv):
         _help(False, dict(threads=4, verbose=1, db=".", results=5))
         return 1
     img_path, text = classify_query(p["rest"])
+    if p.get("distinct") is not None and _refuse_gridded(p["db"], "search --distinct"):
+        return 1
     if (p["like"] is not None or p["max_distance"] is not None) and _refuse_gridded(p["db"], "search --like" if p["like"] is not None else "search -d"):
         return 1
     try:
@@ -611,6 +625,7 @@ def search(argv):
     if p["in"]:                                    # the index ranks only these rows: no host-side filtering of a longer list
         allow = np.array([path.startswith(tuple(p["in"])) for path in image_paths], dtype=np.bool_)
     boxes = {}
+    more = {}                                      # --distinct: id -> the number of images folded into that hit
     if regions is not None:                        # images ranked by their best row: group = image, each image once
         rows = regions[1]
         groups = rows[:, 0]
@@ -627,6 +642,16 @@ def search(argv):
     elif p["max_distance"] is not None:
         _, dist, ids = index.range_search(vec[None, :], p["max_distance"], allow=allow)
         hits = list(zip(dist, ids))
+    elif p.get("distinct") is not None:
+        k = max(1, min(p["results"], MAX_K))
+        if len(index) == 0:                        # (the library refuses an empty index)
+            dist, ids, counts = np.zeros((1, 0), np.float32), np.zeros((1, 0), np.int64), np.zeros((1, 0), np.int32)
+        elif like_id is not None:
+            dist, ids, counts = index.search_ids_distinct([like_id], k, p["distinct"], allow=allow)
+        else:
+            dist, ids, counts = index.search_distinct(vec[None, :], k, p["distinct"], allow=allow)
+        hits = [(d, i) for d, i in zip(dist[0], ids[0]) if i >= 0 and p["results"] > 0]
+        more = {int(i): int(c) for i, c in zip(ids[0], counts[0]) if i >= 0 and c > 0}
     else:
         k = max(1, min(p["results"], MAX_K))
         dist, ids = index.search_ids([like_id], k, allow=allow) if like_id is not None else index.search(vec[None, :], k, allow=allow)
@@ -635,7 +660,7 @@ def search(argv):
         print("search results:")
         print("distance path")
     for d, i in hits:
-        print("  %f %s%s" % (d, image_paths[i], boxes.get(i, "")))
+        print("  %f %s%s%s" % (d, image_paths[i], boxes.get(i, ""), " (+%d)" % more[i] if i in more else ""))
     sys.stdout.flush()
     index.close()
     clip.close()

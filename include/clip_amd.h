@@ -295,6 +295,45 @@ int64_t clip_amd_test_index_sets_block(struct clip_amd_index * ix, int64_t rows)
  * rows each over the seeded rows of clip_amd_bench_search, row r in group r / group_size (0: no groups); < 0 on error.  Used by
  * scripts/sets_bench.py. */
 float clip_amd_bench_search_sets(int dtype, int64_t n, int dim, int n_sets, int set_size, int k, int group_size, int iters);
+/* Distinct search: near-duplicates fold into one hit (the retrieval form of non-maximum suppression).  Inputs: a query, k, radius R, pool
+ * P and allow.
+ * Pool: L is the query's result from clip_amd_index_search_subset(ix, q, 1, P, allow): the P nearest eligible rows (live and allowed) in
+ * search's order, distance ascending, equal distances lower id first.  Empty tail slots are not members.  SUPPRESSION IS OVER THE POOL,
+ * NOT THE WHOLE INDEX: a row outside the P nearest neither suppresses nor is counted.  The pool bounds memory and time, and it makes the
+ * result a closed-form function of search's output.
+ * Near: two members a != b are near when d(min(a, b), max(a, b)) <= R, compared in f32.  d(i, j) for i < j is exactly the distance
+ * clip_amd_index_pairs defines for that pair: what search reports for row j when the query is the vector that was added as row i (row
+ * i's stored values are the prepared query; i8: inv_q := inv_r[i]).  So (a, b) are near at R exactly when pairs(R) lists the pair.
+ * Walk: walk L in order.  A member that an earlier KEPT member is near to is suppressed: it is skipped, and a suppressed member never
+ * suppresses anything.  Every other member is kept.  The walk stops at k kept members.
+ * Outputs per query: distances [k] f32 (the query-to-row bits search reports), ids [k] int64, counts [k] int32: counts[t] is the number
+ * of pool members that kept member t suppressed, each suppressed member counted once, for the first kept member (in walk order) that is
+ * near it; the count runs over the whole pool, including members ranked behind the k-th kept one.  Tail: +INFINITY / -1 / 0.
+ * Consequences: R < 0 suppresses nothing (search_subset's first k, bit for bit, all counts 0); a very large R (4, say) keeps only the
+ * pool's first member, with count = members - 1; a query's result depends neither on the other queries of the call nor on how the call is
+ * cut into blocks; results are bit-identical run to run and across save / load.
+ * Limits: 1 <= k <= pool <= 1024; pool == 0 is automatic: min(1024, max(64, 8 k)).  A NaN radius, a pool outside the range, an empty
+ * index, n_queries < 1 and everything search_subset refuses return false with a message that names the value; nothing is launched and
+ * the outputs are untouched.
+ * Host form: host arrays, synchronous; device memory beyond the index is a fixed budget (query blocks one after another: the near bitmap
+ * alone is 128 KB per query at pool 1024), whatever n_queries.  Device form: queries, allow (trusted) and the three outputs in HBM,
+ * asynchronous on the context's stream.  search_ids_distinct: the queries are the stored rows ids[0 ... n_ids), gathered bit for bit as
+ * search_ids does; an id out of range or removed returns false, names the id and leaves the outputs untouched.  exclude_self != 0: the
+ * query's own row is not in the pool, so it suppresses nothing either. */
+bool clip_amd_index_search_distinct(struct clip_amd_index * ix, const float * queries, int n_queries, int k, float radius, int pool,
+                                    const uint64_t * allow, float * distances, int64_t * ids, int32_t * counts);
+bool clip_amd_index_search_distinct_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int k, float radius, int pool,
+                                           const uint64_t * d_allow, float * d_distances, int64_t * d_ids, int32_t * d_counts);
+bool clip_amd_index_search_ids_distinct(struct clip_amd_index * ix, const int64_t * ids, int n_ids, int k, float radius, int pool, int exclude_self,
+                                        const uint64_t * allow, float * distances, int64_t * out_ids, int32_t * counts);
+/* test hook: the queries per block of the distinct searches on this index from now on (1 ... 4096; 0: automatic), so that a test can make
+ * a call straddle blocks.  Returns the value set, -1 for a NULL index or another value. */
+int clip_amd_test_index_distinct_block(struct clip_amd_index * ix, int queries);
+/* Average device time (microseconds, HIP events) of one clip_amd_index_search_distinct_device of n_queries seeded random queries over n
+ * seeded rows in groups of copies + 1: a seeded random row followed by `copies` noisy copies of it (the row + 0.05 uniform(-1, 1) per
+ * value, before normalisation: seeded random rows alone have no near pairs and the walk would never suppress anything); < 0 on error.
+ * Used by scripts/distinct_bench.py. */
+float clip_amd_bench_search_distinct(int dtype, int64_t n, int dim, int n_queries, int k, int pool, float radius, int copies, int iters);
 /* The same with an allowed set over the same seeded rows and queries (clip_amd_index_search_subset_device): allowed_fraction in [0, 1] of
  * the ids, a seeded random selection or, contiguous != 0, one id range in the middle of the index.  Used by scripts/subset_bench.py. */
 float clip_amd_bench_search_subset(int dtype, int64_t n, int dim, int n_queries, int k, float allowed_fraction, int contiguous, int iters);
