@@ -86,6 +86,8 @@ AMD_SYMBOLS = [
     "clip_amd_bench_search_sets",
     "clip_amd_index_search_distinct", "clip_amd_index_search_distinct_device", "clip_amd_index_search_ids_distinct",
     "clip_amd_test_index_distinct_block", "clip_amd_bench_search_distinct",
+    "clip_amd_index_search_compound", "clip_amd_index_search_compound_device", "clip_amd_test_index_compound_block",
+    "clip_amd_bench_search_compound",
 ]
 
 _lib = None
@@ -287,6 +289,14 @@ def lib():
     L.clip_amd_test_index_distinct_block.argtypes = [vp, i32]
     L.clip_amd_bench_search_distinct.restype = C.c_float
     L.clip_amd_bench_search_distinct.argtypes = [i32, i64, i32, i32, i32, i32, C.c_float, i32, i32]
+    L.clip_amd_index_search_compound.restype = C.c_bool
+    L.clip_amd_index_search_compound.argtypes = [vp, f32p, i64p, C.POINTER(C.c_int32), f32p, i64p, i32, i32, i32, u64p, f32p, i64p]
+    L.clip_amd_index_search_compound_device.restype = C.c_bool
+    L.clip_amd_index_search_compound_device.argtypes = [vp, vp, i64p, C.POINTER(C.c_int32), f32p, i64p, i32, i32, i32, vp, vp, vp]
+    L.clip_amd_test_index_compound_block.restype = i32
+    L.clip_amd_test_index_compound_block.argtypes = [vp, i32]
+    L.clip_amd_bench_search_compound.restype = C.c_float
+    L.clip_amd_bench_search_compound.argtypes = [i32, i64, i32, i32, i32, i32, i32]
     L.clip_amd_bench_search_subset.restype = C.c_float
     L.clip_amd_bench_search_subset.argtypes = [i32, i64, i32, i32, i32, C.c_float, i32, i32]
     L.clip_amd_index_search_ids.restype = C.c_bool
@@ -788,7 +798,11 @@ class Index:
 
     search_distinct(queries, k, radius) folds near-duplicates into one hit: over the query's `pool` nearest rows, walked in search's order,
     a row within `radius` (the distance of pairs) of an earlier kept row is dropped and counted for it; search_ids_distinct does the same
-    with stored rows as the queries.  Suppression is over the pool, not the whole index."""
+    with stored rows as the queries.  Suppression is over the pool, not the whole index.
+
+    search_compound(queries, k) takes compound queries of 1 ... 8 terms each, a term being a vector or a stored row's id with a kind: "all"
+    terms rank (a row's score is its distance to its WORST all-term), "within" / "beyond" terms keep the rows at most / more than a bound
+    away, and an "over" term keeps the rows that are farther from it than their score plus a bound ("a beach" but not "people")."""
 
     DTYPES = {"f32": 0, "f16": 1, "i8": 3}
 
@@ -1051,6 +1065,97 @@ class Index:
                                                            C.c_void_p(d_counts or None)):
             raise RuntimeError("clip_amd_index_search_distinct_device failed (see stderr)")
 
+    COMPOUND_KINDS = {"all": 0, "within": 1, "beyond": 2, "over": 3}
+    MAX_TERMS = 8
+
+    @classmethod
+    def _compound_args(cls, queries, dim):
+        """The flat arrays of a compound call after the checks of the library that need no device (ValueError): (terms f32 [total, dim],
+        term_ids int64 [total] (-1: a vector), kinds int32 [total], bounds f32 [total], term_lims int64 [nq + 1]).  `queries` is a list of
+        compound queries, each a list of 1 ... 8 terms (what, kind) or (what, kind, bound): `what` a vector of dim values or an int id,
+        `kind` "all" (at least one per query), "within", "beyond" (both need a bound) or "over" (bound 0 unless given)."""
+        terms, term_ids, kinds, bounds, lims = [], [], [], [], [0]
+        for c, query in enumerate(queries):
+            query = list(query)
+            if not query:
+                raise ValueError("query %d has no terms" % c)
+            if len(query) > cls.MAX_TERMS:
+                raise ValueError("query %d has %d terms, more than %d" % (c, len(query), cls.MAX_TERMS))
+            for term in query:
+                if not isinstance(term, (tuple, list)) or len(term) not in (2, 3):
+                    raise ValueError("a term of query %d is not (what, kind) or (what, kind, bound): %r" % (c, term))
+                what, kind = term[0], term[1]
+                if not isinstance(kind, str) or kind not in cls.COMPOUND_KINDS:
+                    raise ValueError("query %d: unknown kind %r (known: %s)" % (c, kind, ", ".join(cls.COMPOUND_KINDS)))
+                if len(term) == 3 and term[2] is not None:
+                    bound = float(term[2])
+                elif kind in ("within", "beyond"):
+                    raise ValueError("query %d: a %r term needs a bound" % (c, kind))
+                else:
+                    bound = 0.0
+                if bound != bound:
+                    raise ValueError("query %d: the bound of a %r term is NaN" % (c, kind))
+                if isinstance(what, (int, np.integer)) and not isinstance(what, (bool, np.bool_)):
+                    if int(what) < 0:
+                        raise ValueError("query %d: the id %d of a term is negative" % (c, int(what)))
+                    term_ids.append(int(what))
+                    terms.append(np.zeros(dim, dtype=np.float32))
+                else:
+                    v = np.asarray(what, dtype=np.float32)
+                    if v.shape != (dim,):
+                        raise ValueError("query %d: a term's vector must have %d values, not the shape %r" % (c, dim, v.shape))
+                    term_ids.append(-1)
+                    terms.append(v)
+                kinds.append(cls.COMPOUND_KINDS[kind])
+                bounds.append(bound)
+            if cls.COMPOUND_KINDS["all"] not in kinds[lims[-1]:]:
+                raise ValueError("query %d has no \"all\" term to rank by" % c)
+            lims.append(len(kinds))
+        if len(lims) < 2:
+            raise ValueError("no queries")
+        return (np.ascontiguousarray(np.stack(terms), dtype=np.float32), np.asarray(term_ids, dtype=np.int64), np.asarray(kinds, dtype=np.int32),
+                np.asarray(bounds, dtype=np.float32), np.asarray(lims, dtype=np.int64))
+
+    def search_compound(self, queries, k, allow=None, exclude_terms=True):
+        """Compound queries: `queries` is a list of queries, each a list of 1 ... 8 terms (what, kind) or (what, kind, bound); `what` is a
+        vector or the int id of a stored row (taken bit for bit, as search_ids takes it).  With d_t(row) the distance `search` reports for
+        (term t, row): score(row) = the max of d_t over the query's "all" terms (at least one); a "within" term keeps the rows with d_t <=
+        bound, a "beyond" term those with d_t > bound, an "over" term those with d_t > score + bound in f32 (bound 0 unless given: the
+        row is strictly nearer to what is asked for than to this term).  Eligible rows are live, in `allow` and pass every filter;
+        exclude_terms: the stored rows that are terms of a query are not eligible for it.  Returns (distances f32 [nq, k], ids int64 [nq,
+        k]): the k best eligible rows by (score, id), the distance being the score; +inf / -1 where there are fewer.  A single "all" term
+        is search's result.  ValueError for an empty query, more than 8 terms, no "all" term, a missing or NaN bound, an unknown kind or a
+        vector of the wrong length."""
+        terms, term_ids, kinds, bounds, lims = self._compound_args(queries, self.dim)
+        nq = lims.size - 1
+        words, wp = self._allow(allow)
+        dist = np.empty((nq, int(k)), dtype=np.float32)
+        ids = np.empty((nq, int(k)), dtype=np.int64)
+        if not lib().clip_amd_index_search_compound(self._live(), _fp(terms), term_ids.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    kinds.ctypes.data_as(C.POINTER(C.c_int32)), _fp(bounds), lims.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    nq, int(k), int(bool(exclude_terms)), wp, _fp(dist), ids.ctypes.data_as(C.POINTER(C.c_int64))):
+            raise RuntimeError("clip_amd_index_search_compound failed (see stderr)")
+        return dist, ids
+
+    def search_compound_device(self, d_terms, term_ids, kinds, bounds, term_lims, k, d_distances, d_ids, exclude_terms=True, d_allow=None):
+        """search_compound on device pointers (ints) in the flat form of the library: d_terms [total, dim] f32 in HBM; term_ids int64
+        [total] (>= 0: that stored row replaces the vector; None: no id terms), kinds int32 [total] (0 all, 1 within, 2 beyond, 3 over),
+        bounds f32 [total] and term_lims int64 [nq + 1] are host arrays, read before the call returns; d_allow uint64 words (0 / None:
+        every row) -> distances [nq, k] f32, ids [nq, k] int64; asynchronous on the context's stream.  An id term that is out of range or
+        removed gives an all-empty row."""
+        kinds = np.ascontiguousarray(kinds, dtype=np.int32).reshape(-1)
+        bounds = np.ascontiguousarray(bounds, dtype=np.float32).reshape(-1)
+        lims = np.ascontiguousarray(term_lims, dtype=np.int64).reshape(-1)
+        tid = None if term_ids is None else np.ascontiguousarray(term_ids, dtype=np.int64).reshape(-1)
+        if lims.size < 2 or kinds.size != int(lims[-1]) or bounds.size != kinds.size or (tid is not None and tid.size != kinds.size):
+            raise ValueError("term_lims must end at the %d terms that kinds, bounds and term_ids hold" % kinds.size)
+        if not lib().clip_amd_index_search_compound_device(self._live(), C.c_void_p(d_terms or None),
+                                                           None if tid is None else tid.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                           kinds.ctypes.data_as(C.POINTER(C.c_int32)), _fp(bounds), lims.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                           lims.size - 1, int(k), int(bool(exclude_terms)), C.c_void_p(d_allow or None),
+                                                           C.c_void_p(d_distances or None), C.c_void_p(d_ids or None)):
+            raise RuntimeError("clip_amd_index_search_compound_device failed (see stderr)")
+
     def knn_graph_grouped(self, k, groups):
         """The k-NN graph of the groups (images of a gridded index): (labels, distances, ids, qids).  labels int64 [G]: the distinct groups
         of the live rows, ascending, one result row each; distances f32 / ids int64 / qids int64 [G, k]: the label's k nearest OTHER
@@ -1211,6 +1316,12 @@ def bench_search_distinct(dtype, n, dim, n_queries, k, pool, radius, copies=4, i
     (clip_amd_bench_search_distinct); < 0 on error."""
     return float(lib().clip_amd_bench_search_distinct(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(k), int(pool), float(radius),
                                                       int(copies), int(iters)))
+
+
+def bench_search_compound(dtype, n, dim, n_queries, n_terms, k, iters=10):
+    """Microseconds per clip_amd_index_search_compound_device of n_queries compound queries of n_terms "all" terms each on the data of
+    bench_search (clip_amd_bench_search_compound); < 0 on error."""
+    return float(lib().clip_amd_bench_search_compound(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(n_terms), int(k), int(iters)))
 
 
 def bench_search_subset(dtype, n, dim, n_queries, k, allowed_fraction, contiguous, iters=10):

@@ -414,4 +414,38 @@ void launch_distinct_pick(const float * pool_dist, const int64_t * pool_ids, con
                           int64_t * ids, int * counts, hipStream_t stream);
 void launch_distinct_plant(float * x, int64_t rows, int dim, int64_t first_row, int copies, float amp, uint64_t seed, hipStream_t stream);
 
+// Compound queries (k_compound.hip).  The query workspace is term-major inside a block of 16 compound queries: workspace row
+// compound_row(c, t, tt) holds term t of query c, tt in {2, 4, 8} terms per query (absent terms: zero rows of kind -1).  Every per-row
+// array below (q, qinv, src, ids, kinds, bounds, xids) has compound_rows(nq, tt) entries in that layout.
+// place: workspace row w := stored row ids[w] bit for bit when ids[w] >= 0 (i8: qinv[w] := its rinv; xids[w] := the id), tested against n
+// and live before anything is read there: a bad id gives the zero row, xids -1 and flag[w's query] := -1 (flag [nq], zeroed by the caller);
+// else prepared row src[w] of prep / pinv (as launch_search_prepare leaves them) when src[w] >= 0; else the zero row.
+// scan: launch_search_scan's chunks, candidate layout ([n_chunks][nq][C], nq compound queries) and selection with score(row) = the max over
+// a query's kind-0 terms of the term's distance; a row is a candidate only if it passes every filter term (1: d <= bound, 2: d > bound,
+// 3: d > score + bound) and, xids != NULL, is none of the query's xids.  launch_search_merge / launch_search_finish (qself := flag) follow.
+constexpr int COMPOUND_MAX_TERMS = 8;
+enum { COMPOUND_ALL = 0, COMPOUND_WITHIN = 1, COMPOUND_BEYOND = 2, COMPOUND_OVER = 3 };
+inline int64_t compound_row(int64_t c, int t, int tt) { return (c / 16) * 16 * tt + (int64_t)t * 16 + c % 16; }
+inline int64_t compound_rows(int64_t nq, int tt) { return (nq + 15) / 16 * 16 * tt; }
+struct CompoundArgs {
+    const void * rows = nullptr;
+    const float * rinv = nullptr;
+    int64_t n = 0;
+    int Dpad = 0, dtype = 0;
+    const void * q = nullptr;
+    const float * qinv = nullptr;
+    int nq = 0, tt = 2, k = 0;
+    void * cand = nullptr;
+    int n_chunks = 0;
+    int64_t rows_per_chunk = 0;
+    const uint32_t * mask = nullptr;
+    const int * kinds = nullptr;
+    const float * bounds = nullptr;
+    const int * xids = nullptr;
+};
+void launch_compound_place(const void * rows, const float * rinv, const uint32_t * live, int64_t n, const void * prep, const float * pinv,
+                           const int * src, const int * ids, int nq, int tt, int64_t row_bytes, void * q, float * qinv, int * xids, int * flag,
+                           hipStream_t stream);
+bool launch_compound_scan(const CompoundArgs & a, hipStream_t stream);
+
 }  // namespace clipamd

@@ -2,7 +2,7 @@
 // query chunking, the scan -> merge tree -> finish launch sequence of k_search.hip, searches by id, the k-NN graph and the search of one
 // index with the rows of another (the gather kernel in front of the same sequence, or the tiled kernel of k_graph.hip in the scan's place),
 // searches with query sets (the set fold of k_sets.hip in the finish's place), distinct searches (the pools of a search, then the near
-// bitmap and the walk of k_distinct.hip),
+// bitmap and the walk of k_distinct.hip), compound queries (the placement and the scan of k_compound.hip in front of the same merge tree),
 // appending one index to another, the count -> lims -> scatter -> sort -> finish sequence of
 // range search and pairs (k_join.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
 // Replaces the usearch index of the reference's examples/image-search (build.cpp / search.cpp) with an exact search on the GPU.
@@ -73,6 +73,11 @@ struct clip_amd_index {
     Buf dnear;                     // distinct search: the near bitmap of one query block
     Buf douts;                     // distinct search, host forms: ids + distances + counts of the call
     int distinct_block = 0;        // clip_amd_test_index_distinct_block: queries per block, 0 automatic
+    Buf cprep;                     // compound queries: the vector terms of one query block in the stored form
+    Buf cpinv;                     // compound queries, i8: their inverse norms
+    Buf cmeta;                     // compound queries: source, id, kind and bound of every workspace row of one query block
+    Buf cxid;                      // compound queries: the stored row every workspace row is, or -1
+    int compound_block = 0;        // clip_amd_test_index_compound_block: compound queries per block, 0 automatic
     int knn_route = 0;             // clip_amd_test_index_knn_route: 0 automatic, 1 scan, 2 tiled
     int cross_route = 0;           // clip_amd_test_index_cross_route: the same for clip_amd_index_search_index
     // range search / pairs
@@ -1001,6 +1006,149 @@ float bench_search_impl(int dtype, int64_t n, int dim, int n_queries, int k, flo
     });
 }
 
+// What a compound call's small host arrays say, after check_compound_args: tt = the smallest of {2, 4, 8} that holds the longest query
+struct CompoundCall {
+    const int64_t * term_ids = nullptr;
+    const int32_t * kinds = nullptr;
+    const float * bounds = nullptr;
+    const int64_t * lims = nullptr;
+    int tt = 2;
+    int k = 0;
+    bool exclude = false;
+};
+
+// Compound queries per block: one scan launch within the candidate budget, as a pass of search_device_impl (or the test hook's value)
+int compound_block_size(const clip_amd_index * ix, int k) {
+    if (ix->compound_block > 0) return ix->compound_block;
+    const int64_t rpc = rows_per_chunk(ix->n, k);
+    const size_t n_chunks = (size_t)((ix->n + rpc - 1) / rpc);
+    const int max_q = (int)std::min<size_t>(1024, CAND_BUDGET / (n_chunks * search_candidate_capacity(k) * sizeof(float) * 2));
+    return std::max(16, max_q / 16 * 16);
+}
+
+// what the compound entry points ask beyond check_search_args; sets tt
+bool check_compound_args(const clip_amd_index * ix, const float * terms, const int64_t * term_ids, const int32_t * kinds, const float * bounds,
+                         const int64_t * lims, int nq, int & tt, const char * fn) {
+    if (nq < 1) { fprintf(stderr, "%s: n_queries %d < 1\n", fn, nq); return false; }
+    if (!kinds || !lims) { fprintf(stderr, "%s: NULL kinds or term_lims\n", fn); return false; }
+    if (lims[0] != 0) { fprintf(stderr, "%s: term_lims[0] = %lld, not 0\n", fn, (long long)lims[0]); return false; }
+    int64_t longest = 0;
+    for (int c = 0; c < nq; c++) {
+        const int64_t m = lims[c + 1] - lims[c];
+        if (m < 0) {
+            fprintf(stderr, "%s: term_lims decreases at entry %d (%lld after %lld)\n", fn, c + 1, (long long)lims[c + 1], (long long)lims[c]);
+            return false;
+        }
+        if (m < 1 || m > COMPOUND_MAX_TERMS) {
+            fprintf(stderr, "%s: query %d has %lld terms, outside 1 ... %d\n", fn, c, (long long)m, COMPOUND_MAX_TERMS);
+            return false;
+        }
+        longest = std::max(longest, m);
+        bool scoring = false;
+        for (int64_t t = lims[c]; t < lims[c + 1]; t++) {
+            const int kind = kinds[t];
+            if (kind < COMPOUND_ALL || kind > COMPOUND_OVER) { fprintf(stderr, "%s: term %lld has the unknown kind %d\n", fn, (long long)t, kind); return false; }
+            scoring = scoring || kind == COMPOUND_ALL;
+            if (kind != COMPOUND_ALL && !bounds) { fprintf(stderr, "%s: term %lld is a filter (kind %d) and bounds is NULL\n", fn, (long long)t, kind); return false; }
+            if (kind != COMPOUND_ALL && std::isnan(bounds[t])) { fprintf(stderr, "%s: the bound of term %lld is NaN\n", fn, (long long)t); return false; }
+            if (!terms && !(term_ids && term_ids[t] >= 0)) { fprintf(stderr, "%s: term %lld is a vector and terms is NULL\n", fn, (long long)t); return false; }
+        }
+        if (!scoring) { fprintf(stderr, "%s: query %d has no all-term (kind 0) to rank by\n", fn, c); return false; }
+    }
+    if (ix->n == 0) { fprintf(stderr, "%s: the index is empty (0 rows)\n", fn); return false; }
+    tt = longest <= 2 ? 2 : (longest <= 4 ? 4 : 8);
+    return true;
+}
+
+// Compound queries c_lo ... c_lo + nq - 1 of a call on the device, results into d_dist / d_ids ([nq][k], device).  d_terms: the f32 term
+// vectors on the device from term `origin` of the call on (NULL: every term is a stored row).  Query blocks of compound_block_size, one
+// after another: the block's vector terms are normalised / quantised into the staging array, the placement kernel lays the term-major
+// workspace out of them and of the gathered id terms, then the compound scan, the merge tree and the finish (a query whose id term is
+// out of range or removed: all empty).  A query's workspace rows, candidates and result are its own, so the cut into blocks does not show.
+bool compound_device_impl(clip_amd_index * ix, const float * d_terms, int64_t origin, const CompoundCall & cc, int c_lo, int nq,
+                          const uint32_t * d_allow, float * d_dist, int64_t * d_ids) {
+    hipStream_t st = stream_of(ix);
+    const uint32_t * mask = nullptr;
+    if (!effective_mask(ix, d_allow, mask)) return false;
+    const bool i8 = ix->dtype == SEARCH_I8;
+    const int64_t rpc = rows_per_chunk(ix->n, cc.k);
+    const int n_chunks = (int)((ix->n + rpc - 1) / rpc);
+    const int C = search_candidate_capacity(cc.k);
+    const int block = compound_block_size(ix, cc.k);
+    // the workspace rows of every block, in their layout: source (term number inside the block's vector terms), id, kind, bound.  Built
+    // once and never changed afterwards: the uploads read it
+    std::vector<std::vector<int>> metas;
+    for (int c0 = 0; c0 < nq; c0 += block) {
+        const int m = std::min(block, nq - c0);
+        const int64_t W = compound_rows(m, cc.tt);
+        const int64_t T0 = cc.lims[c_lo + c0];
+        std::vector<int> meta((size_t)(4 * W), -1);
+        std::fill(meta.begin() + 3 * W, meta.end(), 0);
+        for (int c = 0; c < m; c++) {
+            const int64_t f0 = cc.lims[c_lo + c0 + c], f1 = cc.lims[c_lo + c0 + c + 1];
+            for (int64_t f = f0; f < f1; f++) {
+                const int64_t w = compound_row(c, (int)(f - f0), cc.tt);
+                const int64_t id = cc.term_ids ? cc.term_ids[f] : -1;
+                if (id >= 0) meta[(size_t)(W + w)] = (int)std::min<int64_t>(id, MAX_ROWS);      // (MAX_ROWS is never a stored row: flagged)
+                else meta[(size_t)w] = (int)(f - T0);
+                meta[(size_t)(2 * W + w)] = cc.kinds[f];
+                if (cc.kinds[f] != COMPOUND_ALL) memcpy(&meta[(size_t)(3 * W + w)], &cc.bounds[f], 4);
+            }
+        }
+        metas.push_back(std::move(meta));
+    }
+    for (int c0 = 0, b = 0; c0 < nq; c0 += block, b++) {
+        const int m = std::min(block, nq - c0);
+        const int64_t W = compound_rows(m, cc.tt);
+        const int64_t T0 = cc.lims[c_lo + c0], cnt = cc.lims[c_lo + c0 + m] - T0;
+        if (!ensure(ix, ix->cmeta, (size_t)W * 16) || !ensure(ix, ix->cxid, (size_t)W * 4) || !ensure(ix, ix->qself, (size_t)(m + 15) / 16 * 16 * 4) ||
+            !ensure(ix, ix->qbuf, (size_t)W * row_stride(ix)) || (i8 && !ensure(ix, ix->qinv, (size_t)W * sizeof(float))) ||
+            !ensure(ix, ix->cand, (size_t)n_chunks * m * C * 8))
+            return false;
+        if (hipMemcpyAsync(ix->cmeta.p, metas[(size_t)b].data(), (size_t)W * 16, hipMemcpyHostToDevice, st) != hipSuccess) {
+            fprintf(stderr, "clip_amd_index_search_compound: the upload of the terms' kinds failed: %s\n", hipGetErrorString(hipGetLastError()));
+            return false;
+        }
+        if (d_terms) {
+            if (!ensure(ix, ix->cprep, (size_t)cnt * row_stride(ix)) || (i8 && !ensure(ix, ix->cpinv, (size_t)cnt * sizeof(float)))) return false;
+            launch_search_prepare(d_terms + (size_t)(T0 - origin) * ix->dim, cnt, cnt, ix->dim, ix->Dpad, ix->dtype, ix->cprep.p, (float *)ix->cpinv.p, st);
+        }
+        const int * d_meta = (const int *)ix->cmeta.p;
+        int * flag = (int *)ix->qself.p;
+        (void)hipMemsetAsync(flag, 0, (size_t)(m + 15) / 16 * 16 * 4, st);
+        launch_compound_place(ix->store.rows, ix->store.rinv, ix->store.live, ix->n, ix->cprep.p, (const float *)ix->cpinv.p, d_meta, d_meta + W, m, cc.tt,
+                              (int64_t)row_stride(ix), ix->qbuf.p, i8 ? (float *)ix->qinv.p : nullptr, (int *)ix->cxid.p, flag, st);
+        CompoundArgs a;
+        a.rows = ix->store.rows;
+        a.rinv = ix->store.rinv;
+        a.n = ix->n;
+        a.Dpad = ix->Dpad;
+        a.dtype = ix->dtype;
+        a.q = ix->qbuf.p;
+        a.qinv = (const float *)ix->qinv.p;
+        a.nq = m;
+        a.tt = cc.tt;
+        a.k = cc.k;
+        a.cand = ix->cand.p;
+        a.n_chunks = n_chunks;
+        a.rows_per_chunk = rpc;
+        a.mask = mask;
+        a.kinds = d_meta + 2 * W;
+        a.bounds = (const float *)(d_meta + 3 * W);
+        a.xids = cc.exclude ? (const int *)ix->cxid.p : nullptr;
+        if (hipGetLastError() != hipSuccess || !launch_compound_scan(a, st)) {
+            fprintf(stderr, "clip_amd_index_search_compound: scan launch failed\n");
+            return false;
+        }
+        if (!merge_and_finish(ix, n_chunks, m, cc.k, flag, d_dist + (size_t)c0 * cc.k, d_ids + (size_t)c0 * cc.k)) return false;
+        if (hipGetLastError() != hipSuccess) {
+            fprintf(stderr, "clip_amd_index_search_compound: launch failed\n");
+            return false;
+        }
+    }
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1262,6 +1410,102 @@ float clip_amd_bench_search_distinct(int dtype, int64_t n, int dim, int n_querie
             }
             if (ok) us = time_device(iters, call);
             for (void * p : {(void *)d_dist, (void *)d_ids, (void *)d_counts})
+                if (p) (void)hipFree(p);
+            return us;
+        });
+    });
+}
+
+bool clip_amd_index_search_compound_device(struct clip_amd_index * ix, const float * d_terms, const int64_t * term_ids, const int32_t * kinds,
+                                           const float * bounds, const int64_t * term_lims, int n_queries, int k, int exclude_terms,
+                                           const uint64_t * d_allow, float * d_distances, int64_t * d_ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_search_args(ix, kinds, n_queries, k, d_distances, d_ids, fn)) return false;
+        CompoundCall cc;
+        if (!check_compound_args(ix, d_terms, term_ids, kinds, bounds, term_lims, n_queries, cc.tt, fn)) return false;
+        cc.term_ids = term_ids;
+        cc.kinds = kinds;
+        cc.bounds = bounds;
+        cc.lims = term_lims;
+        cc.k = k;
+        cc.exclude = exclude_terms != 0;
+        (void)hipSetDevice(ix->device);
+        return compound_device_impl(ix, d_terms, 0, cc, 0, n_queries, (const uint32_t *)d_allow, d_distances, d_ids);
+    });
+}
+
+bool clip_amd_index_search_compound(struct clip_amd_index * ix, const float * terms, const int64_t * term_ids, const int32_t * kinds,
+                                    const float * bounds, const int64_t * term_lims, int n_queries, int k, int exclude_terms,
+                                    const uint64_t * allow, float * distances, int64_t * ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_search_args(ix, kinds, n_queries, k, distances, ids, fn)) return false;
+        CompoundCall cc;
+        if (!check_compound_args(ix, terms, term_ids, kinds, bounds, term_lims, n_queries, cc.tt, fn)) return false;
+        cc.term_ids = term_ids;
+        cc.kinds = kinds;
+        cc.bounds = bounds;
+        cc.lims = term_lims;
+        cc.k = k;
+        cc.exclude = exclude_terms != 0;
+        (void)hipSetDevice(ix->device);
+        hipStream_t st = stream_of(ix);
+        const int64_t total = term_lims[n_queries];
+        std::vector<int64_t> stored;                           // the id terms: each a stored row that was not removed
+        for (int64_t t = 0; term_ids && t < total; t++)
+            if (term_ids[t] >= 0) stored.push_back(term_ids[t]);
+        if (!check_stored_ids(ix, stored.data(), (int64_t)stored.size(), fn)) return false;
+        const uint32_t * d_allow = nullptr;
+        if (!upload_allow(ix, allow, d_allow)) return false;
+        // query blocks one after another: a block's terms are staged, searched and its results copied out, so nothing on the device grows
+        // with n_queries
+        const int block = std::min(compound_block_size(ix, k), n_queries);
+        const size_t slots = (size_t)block * k;
+        if (!ensure(ix, ix->outs, slots * 12)) return false;
+        if (terms && !ensure(ix, ix->stage, (size_t)std::min<int64_t>(total, (int64_t)block * COMPOUND_MAX_TERMS) * ix->dim * 4)) return false;
+        int64_t * d_out = (int64_t *)ix->outs.p;
+        float * d_dist = (float *)((char *)ix->outs.p + slots * 8);
+        for (int c0 = 0; c0 < n_queries; c0 += block) {
+            const int m = std::min(block, n_queries - c0);
+            const int64_t T0 = term_lims[c0], cnt = term_lims[c0 + m] - T0;
+            if (terms) (void)hipMemcpyAsync(ix->stage.p, terms + (size_t)T0 * ix->dim, (size_t)cnt * ix->dim * 4, hipMemcpyHostToDevice, st);
+            if (!compound_device_impl(ix, terms ? (const float *)ix->stage.p : nullptr, T0, cc, c0, m, d_allow, d_dist, d_out)) return false;
+            if (!copy_results(ix, d_dist, d_out, (size_t)m * k, distances + (size_t)c0 * k, ids + (size_t)c0 * k, fn)) return false;      // (the stage is reused)
+        }
+        return true;
+    });
+}
+
+int clip_amd_test_index_compound_block(struct clip_amd_index * ix, int queries) {
+    if (!ix || queries < 0 || queries > 1024) return -1;
+    ix->compound_block = queries;
+    return queries;
+}
+
+float clip_amd_bench_search_compound(int dtype, int64_t n, int dim, int n_queries, int n_terms, int k, int iters) {
+    return guarded(__func__, -4.f, [&](const char *) {
+        const bool args_ok = n_queries >= 1 && n_queries <= (1 << 17) && n_terms >= 1 && n_terms <= COMPOUND_MAX_TERMS && k >= 1 && k <= MAX_K;
+        const int total = args_ok ? n_queries * n_terms : 0;
+        return bench_on_gallery(dtype, n, dim, total, iters, args_ok, PLANT_NONE, [&](clip_amd_index * ix, float * src) {
+            const size_t count = (size_t)n_queries * k;
+            float * d_dist = nullptr;
+            int64_t * d_ids = nullptr;
+            std::vector<int64_t> lims((size_t)n_queries + 1);
+            for (int c = 0; c <= n_queries; c++) lims[(size_t)c] = (int64_t)c * n_terms;
+            const std::vector<int32_t> kinds((size_t)total, COMPOUND_ALL);
+            CompoundCall cc;
+            cc.kinds = kinds.data();
+            cc.lims = lims.data();
+            cc.tt = n_terms <= 2 ? 2 : (n_terms <= 4 ? 4 : 8);
+            cc.k = k;
+            float us = -4.f;
+            const auto call = [&]() { return compound_device_impl(ix, src, 0, cc, 0, n_queries, nullptr, d_dist, d_ids); };
+            bool ok = hipMalloc(&d_dist, count * 4) == hipSuccess && hipMalloc(&d_ids, count * 8) == hipSuccess;
+            if (ok) {
+                launch_search_fill_random(src, (int64_t)total * dim, 0xC0FFEEull, nullptr);
+                ok = call() && hipDeviceSynchronize() == hipSuccess;
+            }
+            if (ok) us = time_device(iters, call);
+            for (void * p : {(void *)d_dist, (void *)d_ids})
                 if (p) (void)hipFree(p);
             return us;
         });

@@ -5,6 +5,7 @@ build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.In
     python -m clip_cpp_amd.image_search update [-m MODEL] [-v N] [-t N] [--db DIR] dir [more dirs]
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N | -d R] [--distinct R] [--in PREFIX]... [--db DIR] <search text or /path/to/query/image>
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-n N] [--distinct R] [--in PREFIX]... [--db DIR] --like INDEXED/IMAGE/PATH
+    python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N] [--in PREFIX]... [--db DIR] [--and TERM]... [--not TERM]... [--not-margin M] <query or --like PATH>
     python -m clip_cpp_amd.image_search dedup  [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R]
     python -m clip_cpp_amd.image_search neighbors [-m MODEL] [-v N] [--db DIR] [-n N]
     python -m clip_cpp_amd.image_search label  [-m MODEL] [-v N] [-t N] [--db DIR] [-n N] LABEL [LABEL ...]
@@ -29,7 +30,15 @@ listed.  It composes with -n and --in, not with a positional query or -d.
 Index.search_ids_distinct): walking the ranked list, an image within distance R of an image already listed (the distance of `dedup -d R`)
 is dropped, and a listed image that stands for dropped ones gets " (+%d)", their number, behind its path.  The suppression runs over the
 pool of the max(64, 8 N) nearest eligible images (at most 1024), not over the whole index.  It works with -n, --in and --like, not with
--d, and not on a database built with --grid.  `neighbors` prints the k-NN graph (Index.knn_graph, one call):
+-d, and not on a database built with --grid.
+`search --and TERM` / `--not TERM` (both repeatable, up to 8 terms with the main query) ask compound questions (Index.search_compound):
+"a dog" --and "on a beach", --like PATH --and "at night", "a beach" --not "people".  A TERM with an image extension is an image: one that
+equals a line of images.paths is that indexed image (its stored row: nothing is decoded or encoded, and it is not listed itself), any
+other is a file to load and encode; everything else is text.  The main query and every --and term rank together: --and ranks by the
+WORST term, an image's distance column is its largest distance to any of them, so only an image near all of them comes first.  A --not
+term keeps only the images that are strictly nearer to all of what is asked for than to that term: its distance must exceed the printed
+distance by more than --not-margin M (default 0).  The options go in front of the query; they work with -n, --in and --like, not with -d
+or --distinct, and not on a database built with --grid.  `neighbors` prints the k-NN graph (Index.knn_graph, one call):
 "neighbours:" at verbosity > 0, then per image, in id order, its path on a line of its own and "  %f %s" per neighbour, the -n (default 5)
 nearest other images, nearest first; images separated by a blank line, and "main: %d images, %d neighbours each".
 `label` labels the whole database (the reference's zsl example applied to a collection): the labels are encoded as written, in one batch,
@@ -74,6 +83,7 @@ MAX_GRID = 8
 BATCH = 64          # images decoded and encoded per call
 MAX_K = 1024
 DEDUP_RADIUS = 0.05
+MAX_TERMS = 8       # terms of a compound search: the main query, every --and and every --not
 
 
 def is_image_file_extension(path):
@@ -125,7 +135,7 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
             if not dedup:
                 takes.update({"-n": "results", "--results": "results"})
         if search:
-            takes.update({"--in": "in", "--like": "like", "--distinct": "distinct"})
+            takes.update({"--in": "in", "--like": "like", "--distinct": "distinct", "--and": "and", "--not": "not", "--not-margin": "not_margin"})
         if a in takes:
             i += 1
             if i >= len(argv):
@@ -135,15 +145,15 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
                 print("main: --like takes one indexed image: it cannot be given twice")
                 return None
             seen.add(key)
-            if key in ("in", "from"):
-                p[key].append(argv[i])
+            if key in ("in", "from", "and", "not"):
+                p.setdefault(key, []).append(argv[i])
                 i += 1
                 continue
             try:
-                p[key] = int(argv[i]) if key in ("threads", "verbose", "results", "grid") else float(argv[i]) if key in ("max_distance", "distinct") else argv[i]
+                p[key] = int(argv[i]) if key in ("threads", "verbose", "results", "grid") else float(argv[i]) if key in ("max_distance", "distinct", "not_margin") else argv[i]
             except ValueError:
                 return None
-            if key in ("max_distance", "distinct") and p[key] != p[key]:      # NaN
+            if key in ("max_distance", "distinct", "not_margin") and p[key] != p[key]:      # NaN
                 return None
             if key == "grid" and not 1 <= p[key] <= MAX_GRID:
                 print("main: --grid takes 1 ... %d (1: whole images only), not %d" % (MAX_GRID, p[key]))
@@ -174,6 +184,17 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
     if match and len(p["rest"]) > 1:
         print("main: match takes one image path, or none for every indexed image")
         return None
+    if seen & {"and", "not", "not_margin"}:
+        if "max_distance" in seen or "distinct" in seen:
+            print("main: --and / --not cannot be combined with -d or --distinct: they rank the -n nearest images by their worst term")
+            return None
+        if "not_margin" in seen and "not" not in seen:
+            print("main: --not-margin is the margin of the --not terms: it needs at least one --not")
+            return None
+        if 1 + len(p.get("and", [])) + len(p.get("not", [])) > MAX_TERMS:
+            print("main: a compound search takes at most %d terms (the query, every --and and every --not), not %d"
+                  % (MAX_TERMS, 1 + len(p.get("and", [])) + len(p.get("not", []))))
+            return None
     if {"distinct", "max_distance"} <= seen:
         print("main: --distinct and -d cannot be combined: --distinct R thins the -n nearest, -d R prints every image within R")
         return None
@@ -284,6 +305,14 @@ def _help(build, p, dedup=False, update=False, neighbors=False, label=False, mer
               " of `dedup -d R`) of an image already listed is dropped, and a listed image is followed by (+N), the number of images dropped"
               " for it. Suppression runs over the max(64, 8 N) nearest eligible images (at most %d), not the whole index. Works with -n, --in"
               " and --like, not with -d" % MAX_K)
+        print("  --and <term>: a compound search: rank by the WORST term, an image's distance is its largest distance to the query and to every"
+              " --and term, so only an image near all of them comes first; may be repeated. A term with an image extension is an image: one"
+              " that equals a line of %s is that indexed image (its stored row; it is not listed itself), any other is a file to load and"
+              " encode; everything else is text. Works with -n, --in and --like, not with -d or --distinct; options go in front of the query"
+              % PATHS_FILE)
+        print("  --not <term>: only images strictly nearer to the query (and every --and term) than to this term; may be repeated. At most %d"
+              " terms in all: the query, every --and and every --not" % MAX_TERMS)
+        print("  --not-margin M: the distance to a --not term must exceed the printed distance by more than M. Default: 0")
         print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
 
 
@@ -575,6 +604,9 @@ def search(argv):
     img_path, text = classify_query(p["rest"])
     if p.get("distinct") is not None and _refuse_gridded(p["db"], "search --distinct"):
         return 1
+    compound = bool(p.get("and") or p.get("not"))
+    if compound and _refuse_gridded(p["db"], "search --and / --not"):
+        return 1
     if (p["like"] is not None or p["max_distance"] is not None) and _refuse_gridded(p["db"], "search --like" if p["like"] is not None else "search -d"):
         return 1
     try:
@@ -596,6 +628,8 @@ def search(argv):
     except RuntimeError:
         print("main: Unable to load model from %s" % p["model"])
         return 1
+    if compound:
+        return _search_compound(clip_cpp_amd, clip, p, image_paths, like_id, img_path, text)
     vec = None
     if like_id is not None:
         pass                                       # the query is a stored row: no tower is needed
@@ -661,6 +695,76 @@ def search(argv):
         print("distance path")
     for d, i in hits:
         print("  %f %s%s%s" % (d, image_paths[i], boxes.get(i, ""), " (+%d)" % more[i] if i in more else ""))
+    sys.stdout.flush()
+    index.close()
+    clip.close()
+    return 0
+
+
+def compound_terms(p, image_paths, like_id, img_path, text):
+    """The terms of a compound search as (source, value, kind): source "id" (an indexed image: value its id), "file" (an image file to load
+    and encode) or "text"; kind "all" for the main query and every --and, "over" for every --not.  The main query is --like's indexed
+    image, the positional image file or the positional text, as in a plain search; a --and / --not TERM with an image extension is an
+    image, indexed when it equals a line of images.paths, and everything else is text."""
+    terms = [("id", like_id, "all") if like_id is not None else ("file", img_path, "all") if img_path else ("text", text, "all")]
+    for key, kind in (("and", "all"), ("not", "over")):
+        for term in p.get(key, []):
+            if is_image_file_extension(term):
+                terms.append(("id", image_paths.index(term), kind) if term in image_paths else ("file", term, kind))
+            else:
+                terms.append(("text", term, kind))
+    return terms
+
+
+def _search_compound(clip_cpp_amd, clip, p, image_paths, like_id, img_path, text):
+    """`search` with --and / --not: one Index.search_compound over the main query and the terms.  Every text term is encoded in one
+    encode_texts call and every image file in one batch; an indexed image is its stored row."""
+    terms = compound_terms(p, image_paths, like_id, img_path, text)
+    texts = [value for source, value, _ in terms if source == "text"]
+    files = [value for source, value, _ in terms if source == "file"]
+    if files and clip.vision_config["n_layer"] <= 0:
+        _err("main: the model at %s has no vision encoder: image queries need a vision or two-tower model" % p["model"])
+        return 1
+    if texts and clip.text_config["n_layer"] <= 0:
+        _err("main: the model at %s has no text encoder: text queries need a two-tower model" % p["model"])
+        return 1
+    vecs = {}
+    if texts:
+        enc = np.asarray(clip.encode_texts([clip.tokenize(t) for t in texts], normalize=True), dtype=np.float32)
+        vecs.update((("text", t), v) for t, v in zip(texts, enc))
+    if files:
+        L = clip_cpp_amd.lib()
+        imgs = []
+        try:
+            for path in files:
+                imgs.append(L.clip_image_u8_make())
+                if not L.clip_image_load_from_file(os.fsencode(path), imgs[-1]):
+                    _err("main: failed to load image from '%s'" % path)
+                    return 1
+            vecs.update((("file", f), v) for f, v in zip(files, _encode_batch(clip, L, imgs)))
+        finally:
+            for im in imgs:
+                L.clip_image_u8_free(im)
+    index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
+    for v in vecs.values():
+        if index.dim != v.size:
+            _err("main: the index holds %d-dimensional embeddings, the model makes %d" % (index.dim, v.size))
+            return 1
+    allow = None
+    if p["in"]:
+        allow = np.array([path.startswith(tuple(p["in"])) for path in image_paths], dtype=np.bool_)
+    margin = p.get("not_margin", 0.0)
+    query = [(value if source == "id" else vecs[(source, value)], kind) + ((margin,) if kind == "over" else ()) for source, value, kind in terms]
+    k = max(1, min(p["results"], MAX_K))
+    hits = []
+    if len(index) > 0:                             # (the library refuses an empty index)
+        dist, ids = index.search_compound([query], k, allow=allow, exclude_terms=True)
+        hits = [(d, i) for d, i in zip(dist[0], ids[0]) if i >= 0 and p["results"] > 0]
+    if p["verbose"] > 0:
+        print("search results:")
+        print("distance path")
+    for d, i in hits:
+        print("  %f %s" % (d, image_paths[i]))
     sys.stdout.flush()
     index.close()
     clip.close()

@@ -334,6 +334,45 @@ int clip_amd_test_index_distinct_block(struct clip_amd_index * ix, int queries);
  * value, before normalisation: seeded random rows alone have no near pairs and the walk would never suppress anything); < 0 on error.
  * Used by scripts/distinct_bench.py. */
 float clip_amd_bench_search_distinct(int dtype, int64_t n, int dim, int n_queries, int k, int pool, float radius, int copies, int iters);
+/* Compound queries: a query is several terms ("a dog" and "on a beach"; like this stored picture and "at night"; "a beach" but not
+ * "people"; ranked by A but only within R of image B).  A call holds n_queries compound queries; query c is the terms term_lims[c] ...
+ * term_lims[c + 1] - 1 (term_lims: host int64 [n_queries + 1], starting at 0 and increasing, like set_lims), 1 ... 8 of them.
+ * A term is a vector and a kind and, for the filter kinds, a bound (f32): terms [total][dim] f32 holds the vectors; term_ids [total] (or
+ * NULL) replaces a term's vector by a stored row where term_ids[t] >= 0 (the row's stored values bit for bit, as search_ids gathers them;
+ * i8: its inverse norm comes along; the vector is then not used); kinds [total] int32 and bounds [total] f32 (read for kinds 1 ... 3 only).
+ * d_t(row) is the distance clip_amd_index_search reports for (term t, row), bit for bit.
+ *   kind 0 "all"     scoring term: score(row) = the max over the query's all-terms of d_t(row); at least one per query
+ *   kind 1 "within"  the row is eligible only if d_t(row) <= bound (range_search's comparison)
+ *   kind 2 "beyond"  the row is eligible only if d_t(row) > bound (its complement)
+ *   kind 3 "over"    the row is eligible only if d_t(row) > score(row) + bound, one f32 addition and then the compare; with bound 0 the
+ *                    row is strictly nearer to what is asked for than to this term
+ * Eligible rows are live, set in allow (as for search_subset; NULL = every row) and pass every filter term; with exclude_terms != 0 the
+ * rows named as id terms of that query are not eligible either.  The result is the k best eligible rows by (score ascending, id
+ * ascending), search's order; the tail is +INFINITY / -1.  The reported distance is the score: bit for bit one of the all-terms' distances.
+ * Consequences: a query of a single all-term is search_subset bit for bit; with exclude_terms and an id term it is search_ids with
+ * exclude_self; a result depends neither on the other queries of the call, nor on how terms are padded, nor on how the call is cut into
+ * blocks; results are bit-identical run to run, across save / load and however rows were split across add calls.
+ * Any-of (the union of the terms' top-k lists) and weighted means (one query vector) compose exactly from the other calls and are not
+ * offered here; per-hit term distances are not returned (range_search at radius 4 with allow set to the hits gives them).
+ * Limits: 1 <= k <= 1024, 1 <= terms per query <= 8.  A NaN bound of a filter term, an unknown kind, a query without an all-term or with
+ * 0 or more than 8 terms, term_lims not starting at 0 or decreasing, an empty index, n_queries < 1 and everything search_subset refuses
+ * return false with a message that names the value; nothing is launched and the outputs are untouched.
+ * Host form: host arrays, synchronous; an id term out of range or removed returns false, names the id and leaves the outputs untouched,
+ * as search_ids does; device memory beyond the index is a fixed budget (query blocks one after another), whatever n_queries.  Device
+ * form: terms, allow (trusted) and the two outputs in HBM, the small arrays (term_ids, kinds, bounds, term_lims) on the host and read
+ * before the call returns; asynchronous on the context's stream; a bad id term yields an all-empty result row, as search_ids_device does. */
+bool clip_amd_index_search_compound(struct clip_amd_index * ix, const float * terms, const int64_t * term_ids, const int32_t * kinds,
+                                    const float * bounds, const int64_t * term_lims, int n_queries, int k, int exclude_terms,
+                                    const uint64_t * allow, float * distances, int64_t * ids);
+bool clip_amd_index_search_compound_device(struct clip_amd_index * ix, const float * d_terms, const int64_t * term_ids, const int32_t * kinds,
+                                           const float * bounds, const int64_t * term_lims, int n_queries, int k, int exclude_terms,
+                                           const uint64_t * d_allow, float * d_distances, int64_t * d_ids);
+/* test hook: the compound queries per block of the two forms above on this index from now on (1 ... 1024; 0: automatic), so that a test
+ * can make a call straddle blocks.  Returns the value set, -1 for a NULL index or another value. */
+int clip_amd_test_index_compound_block(struct clip_amd_index * ix, int queries);
+/* Average device time (microseconds, HIP events) of one clip_amd_index_search_compound_device of n_queries compound queries of n_terms
+ * all-terms each (seeded random vectors) over the seeded rows of clip_amd_bench_search; < 0 on error.  Used by scripts/compound_bench.py. */
+float clip_amd_bench_search_compound(int dtype, int64_t n, int dim, int n_queries, int n_terms, int k, int iters);
 /* The same with an allowed set over the same seeded rows and queries (clip_amd_index_search_subset_device): allowed_fraction in [0, 1] of
  * the ids, a seeded random selection or, contiguous != 0, one id range in the middle of the index.  Used by scripts/subset_bench.py. */
 float clip_amd_bench_search_subset(int dtype, int64_t n, int dim, int n_queries, int k, float allowed_fraction, int contiguous, int iters);
