@@ -88,6 +88,7 @@ AMD_SYMBOLS = [
     "clip_amd_test_index_distinct_block", "clip_amd_bench_search_distinct",
     "clip_amd_index_search_compound", "clip_amd_index_search_compound_device", "clip_amd_test_index_compound_block",
     "clip_amd_bench_search_compound",
+    "clip_amd_index_components", "clip_amd_index_components_device", "clip_amd_bench_components",
 ]
 
 _lib = None
@@ -263,6 +264,12 @@ def lib():
     L.clip_amd_index_search_subset_device.argtypes = [vp, vp, i32, i32, vp, vp, vp]
     L.clip_amd_index_range_search_subset.restype = i64
     L.clip_amd_index_range_search_subset.argtypes = [vp, f32p, i32, C.c_float, u64p, i64p, f32p, i64p, i64]
+    L.clip_amd_index_components.restype = i64
+    L.clip_amd_index_components.argtypes = [vp, C.c_float, u64p, i64p, f32p, i64p]
+    L.clip_amd_index_components_device.restype = C.c_bool
+    L.clip_amd_index_components_device.argtypes = [vp, C.c_float, vp, vp, vp, vp]
+    L.clip_amd_bench_components.restype = C.c_float
+    L.clip_amd_bench_components.argtypes = [i32, i64, i32, C.c_float, i32]
     L.clip_amd_index_search_grouped.restype = C.c_bool
     L.clip_amd_index_search_grouped.argtypes = [vp, f32p, i32, i32, C.POINTER(C.c_int32), u64p, f32p, i64p]
     L.clip_amd_index_search_grouped_device.restype = C.c_bool
@@ -770,6 +777,9 @@ class Index:
     exactly 1 to everything).  Distance = 1 - (float)dot * inv_q * inv_r with dot the exact int32 sum q_i r_i and inv = 1 / sqrtf(sum
     v_i^2) (0 for the zero vector): the cosine distance of the stored integer vectors, bit-reproducible like the other dtypes.
 
+    components(radius) groups near-duplicates at any density: the connected components of the pairs graph as one label per row (the
+    lowest id of the row's group) and every row's nearest near row, computed on the device; no pair list is ever made.
+
     remove(ids) marks rows as removed: no search, range_search or pairs returns them again, ids are not renumbered and len() keeps
     counting every id ever given (`live` = len minus the removed rows); compact() drops them from device memory and renumbers the
     survivors.  search and range_search take `allow`, a bool mask of length len(index) or an array of ids: only those rows (and of those
@@ -1189,6 +1199,29 @@ class Index:
         lims, dist, j = self._join(call, n + 1, 4 * n + 1024, "clip_amd_index_pairs")
         return np.repeat(np.arange(n, dtype=np.int64), np.diff(lims)), j, dist
 
+    def components(self, radius, allow=None):
+        """Connected components of the graph whose edges are the pairs of `pairs(radius)`, without the pairs ever leaving the device:
+        (labels int64 [n], nearest_distance f32 [n], nearest_id int64 [n]).  labels[x] is the lowest id of x's component (x itself when no
+        row is near it, -1 for a removed or not allowed row); nearest_distance[x] / nearest_id[x] are the smallest distance of a pair x
+        is in and the other row of that pair (the lower id among equal distances), +inf / -1 without one.  `allow` (bool mask [len] or
+        ids): only those rows are eligible.  The components of two or more rows are the roots (labels[x] == x) with a nearest id."""
+        n = len(self)
+        words, wp = self._allow(allow)
+        labels = np.empty(n, dtype=np.int64)
+        dist = np.empty(n, dtype=np.float32)
+        ids = np.empty(n, dtype=np.int64)
+        if lib().clip_amd_index_components(self._live(), float(radius), wp, labels.ctypes.data_as(C.POINTER(C.c_int64)), _fp(dist),
+                                           ids.ctypes.data_as(C.POINTER(C.c_int64))) < 0:
+            raise RuntimeError("clip_amd_index_components failed (see stderr)")
+        return labels, dist, ids
+
+    def components_device(self, radius, d_labels, d_nearest_distance=None, d_nearest_id=None, d_allow=None):
+        """components on device pointers (ints): labels [n] int64, nearest_distance [n] f32 and nearest_id [n] int64 (0 / None: not
+        wanted); d_allow: uint64 words on the device (0 / None: every row); asynchronous on the context's stream."""
+        if not lib().clip_amd_index_components_device(self._live(), float(radius), C.c_void_p(d_allow or None), C.c_void_p(d_labels),
+                                                      C.c_void_p(d_nearest_distance or None), C.c_void_p(d_nearest_id or None)):
+            raise RuntimeError("clip_amd_index_components_device failed (see stderr)")
+
     @staticmethod
     def _join(call, n_lims, guess, name):
         """(lims, distances, ids) of a range-search / pairs call: a guessed capacity first, the exact total again when it did not fit"""
@@ -1335,6 +1368,11 @@ def bench_range(dtype, n, dim, n_queries, radius, iters=10):
     """Microseconds per clip_amd_index_range_search of n_queries queries, or per clip_amd_index_pairs when n_queries == 0, on seeded random
     rows with planted near-duplicates (clip_amd_bench_range); < 0 on error."""
     return float(lib().clip_amd_bench_range(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), float(radius), int(iters)))
+
+
+def bench_components(dtype, n, dim, radius, iters=3):
+    """Microseconds per clip_amd_index_components (host form) over the seeded rows of bench_range (clip_amd_bench_components); < 0 on error."""
+    return float(lib().clip_amd_bench_components(Index.DTYPES[dtype], int(n), int(dim), float(radius), int(iters)))
 
 
 def bench_knn(dtype, n, dim, k, route=0, iters=3):

@@ -401,6 +401,15 @@ void * launch_join_sort(void * buf, void * tmp, const int64_t * offs, int64_t ns
 void launch_join_finish(const void * in, int64_t total, float * dist, int64_t * ids, hipStream_t stream);
 void launch_join_plant(float * x, int64_t rows, int dim, uint64_t seed, hipStream_t stream);
 
+// Connected components of the pairs graph (k_components.hip): two eligible rows (mask as for launch_join with pairs: both sides) are joined
+// when launch_join's pairs would report them at `radius`.  Workspaces: parent [2 n] i32, nearest [n] u64 (both initialised here).
+// labels [n] i64: the lowest id of the row's component, -1 for a row that is not eligible; nearest_distance [n] f32 / nearest_id [n] i64
+// (either may be NULL): the row's nearest near row, lower id first among equal distances, +inf / -1 without one; *groups (may be NULL;
+// zero it first) receives the number of components of two or more rows.  Everything on the device, n < 2^31.
+bool launch_components(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, float radius, const uint32_t * mask, int * parent,
+                       unsigned long long * nearest, int64_t * labels, float * nearest_distance, int64_t * nearest_id, unsigned long long * groups,
+                       hipStream_t stream);
+
 // Distinct search (k_distinct.hip).  A query's pool: `pool` slots of pool_dist / pool_ids ([nq][pool], device) as launch_search_finish
 // leaves them (sorted, real members first, empty slots id -1).  near: near[q][a][w], [nq][pool][distinct_near_words(pool)] 32-bit words,
 // bit b & 31 of word b >> 5 of rank a set when ranks a < b are two members at distance <= radius (the distance of pairs: row min id as

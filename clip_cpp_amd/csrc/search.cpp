@@ -4,7 +4,7 @@
 // searches with query sets (the set fold of k_sets.hip in the finish's place), distinct searches (the pools of a search, then the near
 // bitmap and the walk of k_distinct.hip), compound queries (the placement and the scan of k_compound.hip in front of the same merge tree),
 // appending one index to another, the count -> lims -> scatter -> sort -> finish sequence of
-// range search and pairs (k_join.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
+// range search and pairs (k_join.hip), connected components (the link -> flatten -> finish sequence of k_components.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
 // Replaces the usearch index of the reference's examples/image-search (build.cpp / search.cpp) with an exact search on the GPU.
 // Single owners: search_device_impl (the passes of a search: one ScanArgs per scan launch, whatever the selection), search_blocks and
 // query_block (the blocked host forms of stored-row queries), upload_allow / upload_groups / stage_inputs (a call's inputs on the device),
@@ -86,6 +86,10 @@ struct clip_amd_index {
     Buf joffs;                     // segment offsets (= lims) on the device
     Buf jsort;                     // two (distance, id) buffers of the results
     Buf jouts;                     // ids (int64) + distances of the results
+    // connected components
+    Buf cparent;                   // the union-find: two [n] i32 arrays (the passes that flatten it go from one to the other)
+    Buf cnear;                     // [n] nearest keys (u64)
+    Buf couts;                     // host form: group count (u64), labels + nearest ids (int64), nearest distances
 };
 
 namespace {
@@ -887,6 +891,49 @@ bool check_join_args(const clip_amd_index * ix, float radius, const int64_t * li
     if (capacity < 0) { fprintf(stderr, "%s: capacity %lld < 0\n", fn, (long long)capacity); return false; }
     if (capacity > 0 && (!dist || !ids)) { fprintf(stderr, "%s: NULL result pointer with capacity %lld\n", fn, (long long)capacity); return false; }
     return true;
+}
+
+// Connected components on the device: labels and, where asked for, the nearest near row of every row; d_groups (may be NULL): the number
+// of components of two or more rows.  Queues the launches and returns; ix->n > 0.
+bool components_impl(clip_amd_index * ix, float radius, const uint32_t * d_allow, int64_t * d_labels, float * d_ndist, int64_t * d_nid,
+                     unsigned long long * d_groups, const char * fn) {
+    const uint32_t * mask = nullptr;
+    if (!effective_mask(ix, d_allow, mask)) return false;
+    if (!ensure(ix, ix->cparent, (size_t)ix->n * 2 * sizeof(int)) || !ensure(ix, ix->cnear, (size_t)ix->n * 8)) return false;
+    if (d_groups) (void)hipMemsetAsync(d_groups, 0, 8, stream_of(ix));
+    if (!launch_components(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, radius, mask, (int *)ix->cparent.p,
+                           (unsigned long long *)ix->cnear.p, d_labels, d_ndist, d_nid, d_groups, stream_of(ix))) {
+        fprintf(stderr, "%s: launch failed\n", fn);
+        return false;
+    }
+    return true;
+}
+
+bool check_components_args(const clip_amd_index * ix, float radius, const void * labels, const char * fn) {
+    if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+    if (!labels) { fprintf(stderr, "%s: labels is NULL\n", fn); return false; }
+    if (std::isnan(radius)) { fprintf(stderr, "%s: radius is NaN\n", fn); return false; }
+    return true;
+}
+
+// The host form: the outputs in their workspace, then copied out with the group count.  Returns that count or -1.
+int64_t components_host(clip_amd_index * ix, float radius, const uint64_t * allow, int64_t * labels, float * ndist, int64_t * nid, const char * fn) {
+    if (ix->n == 0) return 0;
+    hipStream_t st = stream_of(ix);
+    const size_t n = (size_t)ix->n;
+    const uint32_t * d_allow = nullptr;
+    if (!upload_allow(ix, allow, d_allow) || !ensure(ix, ix->couts, 8 + n * 20)) return -1;
+    unsigned long long * d_groups = (unsigned long long *)ix->couts.p;
+    int64_t * d_labels = (int64_t *)((char *)ix->couts.p + 8);
+    int64_t * d_nid = d_labels + n;
+    float * d_ndist = (float *)(d_nid + n);
+    if (!components_impl(ix, radius, d_allow, d_labels, ndist ? d_ndist : nullptr, nid ? d_nid : nullptr, d_groups, fn)) return -1;
+    unsigned long long groups = 0;
+    (void)hipMemcpyAsync(&groups, d_groups, 8, hipMemcpyDeviceToHost, st);
+    (void)hipMemcpyAsync(labels, d_labels, n * 8, hipMemcpyDeviceToHost, st);
+    if (ndist) (void)hipMemcpyAsync(ndist, d_ndist, n * 4, hipMemcpyDeviceToHost, st);
+    if (nid) (void)hipMemcpyAsync(nid, d_nid, n * 8, hipMemcpyDeviceToHost, st);
+    return stream_done(ix, fn) ? (int64_t)groups : -1;
 }
 
 bool add_device_impl(clip_amd_index * ix, const float * d_vecs, int64_t n) {
@@ -1718,6 +1765,25 @@ int64_t clip_amd_index_pairs(struct clip_amd_index * ix, float radius, int64_t *
     });
 }
 
+int64_t clip_amd_index_components(struct clip_amd_index * ix, float radius, const uint64_t * allow, int64_t * labels, float * nearest_distance,
+                                  int64_t * nearest_id) {
+    return guarded(__func__, (int64_t)-1, [&](const char * fn) -> int64_t {
+        if (!check_components_args(ix, radius, labels, fn)) return -1;
+        (void)hipSetDevice(ix->device);
+        return components_host(ix, radius, allow, labels, nearest_distance, nearest_id, fn);
+    });
+}
+
+bool clip_amd_index_components_device(struct clip_amd_index * ix, float radius, const uint64_t * d_allow, int64_t * d_labels,
+                                      float * d_nearest_distance, int64_t * d_nearest_id) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_components_args(ix, radius, d_labels, fn)) return false;
+        if (ix->n == 0) return true;
+        (void)hipSetDevice(ix->device);
+        return components_impl(ix, radius, (const uint32_t *)d_allow, d_labels, d_nearest_distance, d_nearest_id, nullptr, fn);
+    });
+}
+
 bool clip_amd_index_search_ids_device(struct clip_amd_index * ix, const int64_t * d_ids, int n_ids, int k, int exclude_self,
                                       const uint64_t * d_allow, float * d_distances, int64_t * d_out_ids) {
     return guarded(__func__, false, [&](const char * fn) {
@@ -1887,6 +1953,17 @@ float clip_amd_bench_range(int dtype, int64_t n, int dim, int n_queries, float r
                 });
             }
             return us;
+        });
+    });
+}
+
+float clip_amd_bench_components(int dtype, int64_t n, int dim, float radius, int iters) {
+    return guarded(__func__, -4.f, [&](const char * fn) {
+        return bench_on_gallery(dtype, n, dim, 0, iters, !std::isnan(radius), PLANT_JOIN, [&](clip_amd_index * ix, float *) {
+            std::vector<int64_t> labels((size_t)n), nid((size_t)n);
+            std::vector<float> ndist((size_t)n);
+            if (hipDeviceSynchronize() != hipSuccess || components_host(ix, radius, nullptr, labels.data(), ndist.data(), nid.data(), fn) < 0) return -4.f;
+            return time_wall(iters, [&]() { return components_host(ix, radius, nullptr, labels.data(), ndist.data(), nid.data(), fn) >= 0; });
         });
     });
 }

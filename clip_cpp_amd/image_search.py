@@ -6,7 +6,7 @@ build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.In
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N | -d R] [--distinct R] [--in PREFIX]... [--db DIR] <search text or /path/to/query/image>
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-n N] [--distinct R] [--in PREFIX]... [--db DIR] --like INDEXED/IMAGE/PATH
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N] [--in PREFIX]... [--db DIR] [--and TERM]... [--not TERM]... [--not-margin M] <query or --like PATH>
-    python -m clip_cpp_amd.image_search dedup  [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R]
+    python -m clip_cpp_amd.image_search dedup  [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R] [--prune]
     python -m clip_cpp_amd.image_search neighbors [-m MODEL] [-v N] [--db DIR] [-n N]
     python -m clip_cpp_amd.image_search label  [-m MODEL] [-v N] [-t N] [--db DIR] [-n N] LABEL [LABEL ...]
     python -m clip_cpp_amd.image_search merge  [-m MODEL] [-v N] --db DIR --from DIR2 [--from DIR3 ...] [-d R]
@@ -20,9 +20,13 @@ verbosity > 0, then "  %f %s" per hit, nearest first: the -n nearest, or with -d
 removed from the index (Index.remove + Index.compact), the files under the given dirs that are not indexed yet are encoded and appended,
 and both files are rewritten: the survivors in their old order, then the new files in scan order; it prints "main: %d added, %d removed,
 %d kept".  `dedup` prints
-the groups of near-duplicate images (connected components of the pairs within distance R, clip_amd_index_pairs): "duplicate groups:" at
+the groups of near-duplicate images (connected components of the pairs within distance R, computed on the device by Index.components: one
+label per image at any number of pairs): "duplicate groups:" at
 verbosity > 0, then per group, in order of its lowest id, "  %f %s" per member in id order (the distance to its nearest other member),
-groups separated by a blank line, and "main: %d groups, %d images".
+groups separated by a blank line, and "main: %d groups, %d images".  `dedup --prune` de-duplicates the database: of every group only the
+lowest id stays, the others leave the index (Index.remove + Index.compact) and images.paths, both files are rewritten as `update` rewrites
+them, and no image file on disk is touched; it prints the groups at verbosity > 0, then "main: %d removed, %d kept", and rewrites nothing
+when there is nothing to remove.
 `search --like PATH` asks for "more like this one": the query is the indexed image whose line in images.paths equals PATH as written
 (Index.search_ids: its stored row, nothing is decoded or encoded, so a text-only or vision-less model is enough); the image itself is not
 listed.  It composes with -n and --in, not with a positional query or -d.
@@ -158,6 +162,8 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
             if key == "grid" and not 1 <= p[key] <= MAX_GRID:
                 print("main: --grid takes 1 ... %d (1: whole images only), not %d" % (MAX_GRID, p[key]))
                 return None
+        elif dedup and a == "--prune":
+            p["prune"] = True
         elif a in ("-h", "--help"):
             _help(build, p, dedup, update, neighbors, label, merge, match)
             sys.exit(0)
@@ -256,13 +262,17 @@ def _help(build, p, dedup=False, update=False, neighbors=False, label=False, mer
         print("  -n N, --results N: Number of neighbours per image (at most %d). Default: %d" % (MAX_K, p["results"]))
     elif dedup:
         print("Usage: python -m clip_cpp_amd.image_search dedup [options]")
-        print("\nPrints the groups of near-duplicate images of an index built by `build` (connected components of the image pairs within R).")
+        print("\nPrints the groups of near-duplicate images of an index built by `build` (connected components of the image pairs within R),")
+        print("or with --prune removes all but one image of every group from the database.")
         print("\nOptions:")
         print("  -h, --help: Show this message and exit")
         print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default (loaded only to place the index on its device).")
         print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
         print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
         print(radius % ("pair images", DEDUP_RADIUS, DEDUP_RADIUS))
+        print("  --prune: de-duplicate the database: of every group only the first image (the lowest id) stays in %s and %s, both"
+              " rewritten under temporary names and renamed into place; image files on disk are never touched. Prints the groups at"
+              " verbosity > 0, then the number of images removed and kept" % (INDEX_FILE, PATHS_FILE))
     elif update:
         print("Usage: python -m clip_cpp_amd.image_search update [options] dir/with/pictures [more/dirs]")
         print("\nBrings a database made by `build` in line with the disk: indexed paths that no longer exist are removed, image files under the")
@@ -797,6 +807,17 @@ def duplicate_groups(i, j, d):
     return [groups[r] for r in sorted(groups)]
 
 
+def component_groups(labels, nearest_distance):
+    """The groups of Index.components' output in the structure of duplicate_groups: a list, in order of each group's lowest id, of
+    [(id, distance to its nearest other member), ...] in id order, over the rows that have a near row (a finite nearest distance)."""
+    labels = np.asarray(labels, dtype=np.int64)
+    dist = np.asarray(nearest_distance, dtype=np.float32).astype(np.float64)
+    ids = np.flatnonzero(np.isfinite(dist) & (labels >= 0))
+    order = ids[np.argsort(labels[ids], kind="stable")]          # by group (its label is its lowest id), ids ascending within one
+    cuts = np.flatnonzero(np.diff(labels[order])) + 1
+    return [list(zip(g.tolist(), dist[g].tolist())) for g in np.split(order, cuts) if g.size]
+
+
 def dedup(argv):
     import clip_cpp_amd
     p = _parse(argv, build=False, dedup=True)
@@ -814,15 +835,27 @@ def dedup(argv):
         print("main: Unable to load model from %s" % p["model"])
         return 1
     index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
-    groups = duplicate_groups(*index.pairs(p["max_distance"]))
-    if p["verbose"] > 0:
-        print("duplicate groups:")
-    for g, members in enumerate(groups):
-        if g:
-            print()
-        for i, d in members:
-            print("  %f %s" % (d, image_paths[i]))
-    print("main: %d groups, %d images" % (len(groups), sum(len(m) for m in groups)))
+    prune = p.get("prune", False)                  # (the key exists only when --prune was given)
+    labels, nearest, _ = index.components(p["max_distance"])
+    groups = component_groups(labels, nearest)
+    if p["verbose"] > 0 or not prune:
+        if p["verbose"] > 0:
+            print("duplicate groups:")
+        for g, members in enumerate(groups):
+            if g:
+                print()
+            for i, d in members:
+                print("  %f %s" % (d, image_paths[i]))
+    if prune:
+        removed = [i for members in groups for i, _ in members[1:]]      # every member but the group's lowest id
+        if removed:
+            gone = set(removed)
+            index.remove(removed)
+            index.compact()
+            _write_db(p, index, [path for i, path in enumerate(image_paths) if i not in gone])
+        print("main: %d removed, %d kept" % (len(removed), len(image_paths) - len(removed)))
+    else:
+        print("main: %d groups, %d images" % (len(groups), sum(len(m) for m in groups)))
     sys.stdout.flush()
     index.close()
     clip.close()

@@ -461,6 +461,28 @@ int64_t clip_amd_index_range_search_subset(struct clip_amd_index * ix, const flo
  * against n seeded random rows of which every 64th is a small perturbation of an earlier one (sparse, non-empty output at small radii), on
  * the current device (dtype as clip_amd_index_create); < 0 on error.  Used by scripts/pairs_bench.py. */
 float clip_amd_bench_range(int dtype, int64_t n, int dim, int n_queries, float radius, int iters);
+/* Connected components of the graph "distance <= radius": the groups of near-duplicates as one label per row, whatever the number of near
+ * pairs (a burst of m copies is m (m - 1) / 2 pairs for clip_amd_index_pairs and m labels here; no pair ever leaves the device).
+ * Near pairs: two eligible rows i < j (live and set in allow, layout as live_mask, NULL = every live row) are near when d(i, j) <= radius,
+ * compared in f32, d(i, j) being exactly the distance clip_amd_index_pairs defines for that pair: they are near at R exactly when pairs(R)
+ * over the eligible rows lists them.
+ * labels [size] int64: the lowest id of the row's component; the row itself for a row without a near row; -1 for a removed or not allowed
+ * row.  nearest_distance [size] f32: the smallest d over the near pairs the row takes part in, on either side (as i or as j), the bits pairs
+ * reports; nearest_id [size] int64: the other row of that pair, the lower id among equal distances; +INFINITY / -1 when the row has no
+ * near row (and for a row that is not eligible).  Either of the two, or both, may be NULL.
+ * The host form returns the number of components with at least two rows: exactly the roots (labels[x] == x) that have a nearest id; 0 for
+ * an empty index (nothing is written); -1 on error.  Results are bit-identical run to run, however rows were split across add calls and
+ * across save / load; over the eligible rows they are those of an index to which only those rows were ever added (ids mapped in order).
+ * -1 / false with a message on stderr, nothing launched, for a NULL index, NULL labels or a NaN radius.
+ * Host form: host arrays, synchronous on the ctx stream.  Device form: allow (trusted) and the outputs in HBM, asynchronous on the ctx
+ * stream, synchronises with nothing on the host.  Device memory beyond the index: 16 bytes per row (the host form 20 more for its results). */
+int64_t clip_amd_index_components(struct clip_amd_index * ix, float radius, const uint64_t * allow, int64_t * labels, float * nearest_distance,
+                                  int64_t * nearest_id);
+bool clip_amd_index_components_device(struct clip_amd_index * ix, float radius, const uint64_t * d_allow, int64_t * d_labels,
+                                      float * d_nearest_distance, int64_t * d_nearest_id);
+/* Average wall time (microseconds) of one clip_amd_index_components (host form, all three outputs) over the seeded rows of
+ * clip_amd_bench_range; < 0 on error.  Used by scripts/components_bench.py. */
+float clip_amd_bench_components(int dtype, int64_t n, int dim, float radius, int iters);
 
 /* ---- kernel-level test hooks (used by tests/ only; host pointers, synchronous) ----
  * Y[M,N] = X[M,K] . W[N,K]^T (+bias) through the production dequant-GEMM kernel.
