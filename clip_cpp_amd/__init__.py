@@ -68,7 +68,7 @@ AMD_SYMBOLS = [
     "clip_amd_zero_shot_score_device", "clip_amd_zero_shot_label_images",
     "clip_amd_synchronize", "clip_amd_profile_enable", "clip_amd_profile_read", "clip_amd_profile_report",
     "clip_amd_test_gemm", "clip_amd_test_gemm_ex", "clip_amd_test_gemm_tile", "clip_amd_test_gemm_tile_ex", "clip_amd_test_skinny", "clip_amd_test_layernorm", "clip_amd_test_attention", "clip_amd_bench_gemm",
-    "clip_amd_test_attention_ex", "clip_amd_bench_attention",
+    "clip_amd_test_attention_ex", "clip_amd_bench_attention", "clip_amd_test_attention_ragged",
     "clip_amd_test_layernorm_ex", "clip_amd_test_text_embed", "clip_amd_test_im2col", "clip_amd_test_layernorm_prep", "clip_amd_test_rows",
     "clip_amd_index_create", "clip_amd_index_add", "clip_amd_index_add_device", "clip_amd_index_size", "clip_amd_index_dim",
     "clip_amd_index_search", "clip_amd_index_search_device", "clip_amd_index_save", "clip_amd_index_load", "clip_amd_index_free",
@@ -220,6 +220,8 @@ def lib():
     L.clip_amd_test_attention_ex.argtypes = [f32p, i32, i32, i32, i32, i32, f32p, i32]
     L.clip_amd_bench_attention.restype = C.c_float
     L.clip_amd_bench_attention.argtypes = [i32, i32, i32, i32, i32, i32, i32]
+    L.clip_amd_test_attention_ragged.restype = i32
+    L.clip_amd_test_attention_ragged.argtypes = [f32p, C.c_int64, i32p, i32, i32, i32, i32, i32, f32p, i32]
     i64, i64p = C.c_int64, C.POINTER(C.c_int64)
     L.clip_amd_index_create.restype = vp
     L.clip_amd_index_create.argtypes = [vp, i32, i32]

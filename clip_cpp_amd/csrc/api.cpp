@@ -1396,6 +1396,50 @@ int clip_amd_test_attention(const float * qkv, int nseq, int T, int h, int n_hea
     return clip_amd_test_attention_ex(qkv, nseq, T, h, n_head, causal, out, 0);
 }
 
+// Ragged batches through one kernel (clip_amd.h): seq_start goes to the device as the layers pass it, rows outside
+// [seq_start[0], seq_start[nseq]) are guard rows, and `out` travels up before the launch so that a row no kernel wrote comes back as the caller left it.
+// Every argument is checked on the host before anything is allocated or launched: the kernels clamp to row len - 1 and trust their offsets.
+int clip_amd_test_attention_ragged(const float * qkv, int64_t rows_total, const int32_t * seq_start, int nseq, int max_len,
+                                   int h, int n_head, int causal, float * out, int kernel) {
+    if (!qkv || !out || rows_total <= 0 || rows_total > (int64_t)1 << 24 || nseq < 1 || max_len < 1 || h <= 0 || n_head <= 0 || h % n_head) return -3;
+    if (kernel < 0 || kernel > 3) return -3;
+    if (seq_start) {
+        if (seq_start[0] < 0 || (int64_t)seq_start[nseq] > rows_total) return -3;
+        for (int i = 0; i < nseq; i++) {
+            const int64_t len = (int64_t)seq_start[i + 1] - seq_start[i];      // (decreasing offsets: len < 1)
+            if (len < 1 || len > max_len) return -3;
+        }
+    } else if ((int64_t)nseq * max_len > rows_total) return -3;
+    if (!test_device()) return -1;
+    const size_t rows = (size_t)rows_total, nq = rows * 3 * h, no = rows * h;
+    const bool f32 = kernel == 3;
+    DBuf q32(nq * 4), q16(f32 ? 0 : nq * 2), o32(no * 4), o16(f32 ? 0 : no * 2), ds(seq_start ? ((size_t)nseq + 1) * 4 : 0);
+    if (!q32.p || !q16.p || !o32.p || !o16.p || !ds.p) return -1;
+    upload(q32, qkv, nq * 4);
+    upload(o32, out, no * 4);
+    if (seq_start) upload(ds, seq_start, ((size_t)nseq + 1) * 4);
+    const int * dstart = seq_start ? (const int *)ds.p : nullptr;
+    bool ok = false;
+    if (f32) {
+        ok = launch_attention_f32((const float *)q32.p, (float *)o32.p, nseq, max_len, dstart, max_len, h, n_head, causal != 0, nullptr);
+    } else {
+        launch_f32_to_f16((const float *)q32.p, 3 * h, (half_t *)q16.p, 3 * h, (int)rows, 3 * h, 3 * h, nullptr);
+        launch_f32_to_f16((const float *)o32.p, h, (half_t *)o16.p, h, (int)rows, h, h, nullptr);
+        const half_t * q = (const half_t *)q16.p;
+        half_t * o = (half_t *)o16.p;
+        switch (kernel) {
+        case 0: ok = launch_attention(q, o, nseq, max_len, dstart, max_len, h, n_head, causal != 0, nullptr); break;
+        case 1: ok = launch_attention_whole_row(q, o, nseq, max_len, dstart, max_len, h, n_head, causal != 0, nullptr); break;
+        case 2: ok = launch_attention_long(q, o, nseq, max_len, dstart, max_len, h, n_head, causal != 0, nullptr); break;
+        }
+        if (ok) launch_f16_to_f32((const half_t *)o16.p, h, (float *)o32.p, h, (int)rows, h, nullptr);
+    }
+    if (!test_sync()) return -4;
+    if (!ok) return -2;
+    download(out, o32, no * 4);
+    return 0;
+}
+
 // Micro-benchmark of one attention shape (seeded random q / k / v, q at the scale of a pre-scaled projection): average kernel time in
 // microseconds over `iters` launches (HIP events, after one warm-up launch), < 0 on error (-2: the chosen kernel does not take the shape).
 float clip_amd_bench_attention(int nseq, int T, int h, int n_head, int causal, int kernel, int iters) {

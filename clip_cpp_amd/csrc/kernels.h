@@ -226,6 +226,9 @@ void launch_layernorm_prep(const float * x, int ldx, const float * w, const floa
 // Multi-head self-attention softmax(QK^T)V (reference clip.cpp:1382-1388; causal for text :1101).
 // qkv: [rows][3h] fp16 with Q pre-scaled; sequences given by seq_start[nseq+1] (device) or, when
 // seq_start == nullptr, uniform length T.  out: [rows][h] fp16.
+// Precondition: every sequence has 1 <= len <= max_len.  The kernels read padded queries and keys from the clamped row len - 1, so an empty
+// sequence (len == 0) would read row -1; callers never pass one (a text is at least its start token, an image its class token).  max_len only
+// picks the instantiation and the grid: it may exceed the longest sequence (the text graphs bucket it by 16-key tiles).
 // Sequences up to attention_whole_row_max_len(d_head) (592 for d_head 64, 288 otherwise) run the whole-row kernel of k_attn.hip,
 // longer ones the streaming kernel of k_attn_long.hip; the two are also callable on their own (test / measurement hooks), and
 // launch_attention_whole_row returns false past its limit.

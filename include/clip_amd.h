@@ -577,6 +577,16 @@ int clip_amd_test_attention(const float * qkv, int nseq, int T, int h, int n_hea
 /* ... with the kernel chosen: 0 = automatic (what the layers run), 1 = the whole-row kernel (d_head 64: T <= 592, other head sizes:
  * T <= 288), 2 = the streaming kernel (any T).  Returns -2 when the chosen kernel does not take the shape. */
 int clip_amd_test_attention_ex(const float * qkv, int nseq, int T, int h, int n_head, int causal, float * out, int kernel);
+/* Ragged batches: qkv [rows_total][3h] (q pre-scaled), seq_start[nseq + 1] row offsets (uploaded to the device as the layers pass them), max_len the
+ * launch's key bound (>= every length; it may be larger than the longest sequence).  Rows before seq_start[0] and from seq_start[nseq] on are guard
+ * rows no kernel may read or write.  seq_start == NULL: nseq sequences of max_len rows each, from row 0.  kernel: 0 = automatic, 1 = whole-row,
+ * 2 = streaming (these three on fp16 copies of qkv and out), 3 = the f32 kernel (qkv and out stay f32 end to end).  out [rows_total][h] is in and
+ * out: it is uploaded before the launch and downloaded after it, so a row that no kernel wrote comes back with the caller's value.
+ * Checked on the host before anything launches: nseq >= 1, 0 <= seq_start[0], seq_start[nseq] <= rows_total, offsets non-decreasing, every length in
+ * [1, max_len] (the kernels clamp to row len - 1: an empty sequence is outside their contract), h % n_head == 0.
+ * Returns 0; -1 no device; -2 the chosen kernel does not take the shape; -3 a check failed (nothing launched, out untouched); -4 HIP error. */
+int clip_amd_test_attention_ragged(const float * qkv, int64_t rows_total, const int32_t * seq_start, int nseq, int max_len,
+                                   int h, int n_head, int causal, float * out /* in and out */, int kernel);
 /* Average device time (microseconds, HIP events) of one attention launch on seeded random q / k / v, kernel as
  * clip_amd_test_attention_ex; < 0 on error (-2: the kernel does not take the shape).  Used by scripts/attn_bench.py. */
 float clip_amd_bench_attention(int nseq, int T, int h, int n_head, int causal, int kernel, int iters);

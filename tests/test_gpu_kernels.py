@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import attention_common as ac
 from oracle import ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -269,17 +270,8 @@ def test_layernorm_vs_oracle(L, h):
 
 
 def attention_ref(qkv, nseq, T, h, nh, causal):
-    qkv = _h(qkv).astype(np.float64).reshape(nseq, T, 3, nh, h // nh)
-    q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
-    s = np.einsum("bqhd,bkhd->bhqk", q, k)
-    if causal:
-        mask = np.triu(np.ones((T, T), dtype=bool), 1)
-        s = np.where(mask, -np.inf, s)
-    s = s - s.max(-1, keepdims=True)
-    p = np.exp(s)
-    p /= p.sum(-1, keepdims=True)
-    o = np.einsum("bhqk,bkhd->bqhd", p, v)
-    return o.reshape(nseq * T, h)
+    """the float64 definition on the fp16-rounded inputs and what its element-wise fp16 bound is made of (tests/attention_common.py)"""
+    return ac.attention_ref_ragged(qkv, ac.uniform_starts(nseq, T), h, nh, causal, True)
 
 
 @pytest.mark.parametrize("cfg", [(3, 17, 64, 2, 0), (2, 50, 768, 12, 0), (2, 257, 1024, 16, 0), (1, 257, 1280, 16, 0),
@@ -290,15 +282,19 @@ def attention_ref(qkv, nseq, T, h, nh, causal):
 def test_attention_vs_reference(L, cfg):
     nseq, T, h, nh, causal = cfg
     rng = np.random.default_rng(sum(cfg))
-    qkv = (rng.standard_normal((nseq * T, 3 * h)) * 0.7).astype(np.float32)
-    qkv[:, :h] *= 1.0 / np.sqrt(h // nh)   # q arrives pre-scaled
-    out = np.full((nseq * T, h), np.nan, dtype=np.float32)
-    rc = L.clip_amd_test_attention(_fp(qkv), nseq, T, h, nh, causal, _fp(out))
-    assert rc == 0, rc
-    want = attention_ref(qkv, nseq, T, h, nh, causal)
-    assert np.all(np.isfinite(out))
-    err = np.abs(out - want).max()
-    assert err < 4e-3, (cfg, err)
+    flat = (rng.standard_normal((nseq * T, 3 * h)) * 0.7).astype(np.float32)
+    flat[:, :h] *= 1.0 / np.sqrt(h // nh)   # q arrives pre-scaled
+    peaked = ac.make_ragged_qkv([T] * nseq, h, nh, 6, sum(cfg), guard=0)[0]      # score scale 6 and one dominant key per sequence
+    for what, qkv in (("flat", flat), ("peaked", peaked)):
+        out = np.full((nseq * T, h), np.nan, dtype=np.float32)
+        rc = L.clip_amd_test_attention(_fp(qkv), nseq, T, h, nh, causal, _fp(out))
+        assert rc == 0, rc
+        defn = attention_ref(qkv, nseq, T, h, nh, causal)
+        assert np.all(np.isfinite(out))
+        err = np.abs(out - defn.want).max()
+        assert err < 4e-3, (cfg, what, err)
+        r = ac.err_over_bound(out, defn, ac.fp16_bound(defn))
+        assert r <= 1.0, (cfg, what, "max err / element-wise fp16 bound", r)
 
 
 def run_gemm_ex(L, tid, raw, N, K, X, bias=None, epi=0, tile=0, qcols=0, qscale=1.0, Np=0, T=0, pos=None, y=None):

@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import attention_common as ac
 from oracle import fixtures, ref
 
 pytestmark = pytest.mark.gpu
@@ -17,10 +18,6 @@ TOL = {"f32": 1e-6, "f16": 1e-4, "q4_0": 1e-3, "q5_1": 1e-3}
 
 def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
-
-
-def _h(x):
-    return np.asarray(x, dtype=np.float32).astype(np.float16).astype(np.float32)
 
 
 def one_minus_cos(a, b):
@@ -37,16 +34,9 @@ def L(clip_lib):
 
 
 def attention_ref(qkv, nseq, T, h, nh, causal):
-    """softmax(Q K^T) V in float64 on the fp16-rounded inputs; qkv [nseq*T][3h] with Q pre-scaled."""
-    x = _h(qkv).astype(np.float64).reshape(nseq, T, 3, nh, h // nh)
-    q, k, v = (x[:, :, i].transpose(0, 2, 1, 3) for i in range(3))          # [nseq][nh][T][dh]
-    s = q @ k.transpose(0, 1, 3, 2)
-    if causal:
-        s = np.where(np.triu(np.ones((T, T), dtype=bool), 1), -np.inf, s)
-    s -= s.max(-1, keepdims=True)
-    p = np.exp(s)
-    p /= p.sum(-1, keepdims=True)
-    return (p @ v).transpose(0, 2, 1, 3).reshape(nseq * T, h)
+    """softmax(Q K^T) V in float64 on the fp16-rounded inputs; qkv [nseq*T][3h] with Q pre-scaled: the definition and what its element-wise
+    fp16 bound is made of (tests/attention_common.py)"""
+    return ac.attention_ref_ragged(qkv, ac.uniform_starts(nseq, T), h, nh, causal, True)
 
 
 def make_qkv(cfg, seed=None):
@@ -88,22 +78,16 @@ LONG_SHAPES = [
 @pytest.mark.parametrize("cfg", LONG_SHAPES)
 def test_long_attention_vs_reference(L, cfg):
     nseq, T, h, nh, causal = cfg
-    qkv = make_qkv(cfg)
-    rc, out = run(L, qkv, cfg)
-    assert rc == 0, rc
-    assert np.all(np.isfinite(out))
-    err = np.abs(out - attention_ref(qkv, nseq, T, h, nh, causal)).max()
-    assert err < 4e-3, (cfg, err)
-
-
-def _ulps_at_row_scale(a, b, h, nh):
-    """|a - b| in fp16 ulps of the largest magnitude of the (query, head) row it belongs to: the two kernels round different fp16
-    probabilities (the streaming one against the running maximum), so an output that nearly cancels can differ by many ulps of its own."""
-    dh = h // nh
-    a3, b3 = a.reshape(-1, nh, dh), b.reshape(-1, nh, dh)
-    scale = np.maximum(np.abs(a3).max(-1, keepdims=True), np.abs(b3).max(-1, keepdims=True))
-    ulp = np.spacing(scale.astype(np.float16)).astype(np.float32)
-    return (np.abs(a3 - b3) / ulp).max()
+    peaked = ac.make_ragged_qkv([T] * nseq, h, nh, 6, sum(cfg), guard=0)[0]      # score scale 6 and one dominant key per sequence
+    for what, qkv in (("flat", make_qkv(cfg)), ("peaked", peaked)):
+        rc, out = run(L, qkv, cfg)
+        assert rc == 0, rc
+        assert np.all(np.isfinite(out))
+        defn = attention_ref(qkv, nseq, T, h, nh, causal)
+        err = np.abs(out - defn.want).max()
+        assert err < 4e-3, (cfg, what, err)
+        r = ac.err_over_bound(out, defn, ac.fp16_bound(defn))
+        assert r <= 1.0, (cfg, what, "max err / element-wise fp16 bound", r)
 
 
 AGREE_SHAPES = [(2, T, 2 * dh, 2, 0) for T in (17, 257, 288) for dh in (32, 64, 80, 88, 96, 104)]
@@ -127,9 +111,9 @@ def test_kernels_agree_where_both_apply(L, cfg):
         return
     assert rc_row == 0, rc_row
     assert np.array_equal(auto, whole), "automatic dispatch left the whole-row kernel at T = %d" % T
-    u = _ulps_at_row_scale(whole, stream, h, nh)
+    u = ac.ulps_at_row_scale(whole, stream, h, nh)
     assert u <= 2.0, (cfg, u)
-    assert np.abs(stream - attention_ref(qkv, nseq, T, h, nh, causal)).max() < 4e-3
+    assert np.abs(stream - attention_ref(qkv, nseq, T, h, nh, causal).want).max() < 4e-3
 
 
 @pytest.mark.parametrize("cfg", [(2, 730, 1280, 16, 0), (4, 1025, 1024, 16, 0), (1, 1025, 208, 2, 1)])
