@@ -89,6 +89,7 @@ AMD_SYMBOLS = [
     "clip_amd_index_search_compound", "clip_amd_index_search_compound_device", "clip_amd_test_index_compound_block",
     "clip_amd_bench_search_compound",
     "clip_amd_index_components", "clip_amd_index_components_device", "clip_amd_bench_components",
+    "clip_amd_index_modes", "clip_amd_index_modes_device", "clip_amd_bench_modes",
 ]
 
 _lib = None
@@ -272,6 +273,12 @@ def lib():
     L.clip_amd_index_components_device.argtypes = [vp, C.c_float, vp, vp, vp, vp]
     L.clip_amd_bench_components.restype = C.c_float
     L.clip_amd_bench_components.argtypes = [i32, i64, i32, C.c_float, i32]
+    L.clip_amd_index_modes.restype = i64
+    L.clip_amd_index_modes.argtypes = [vp, C.c_float, C.c_float, u64p, i64p, i64p, f32p, C.POINTER(C.c_int32)]
+    L.clip_amd_index_modes_device.restype = C.c_bool
+    L.clip_amd_index_modes_device.argtypes = [vp, C.c_float, C.c_float, vp, vp, vp, vp, vp]
+    L.clip_amd_bench_modes.restype = C.c_float
+    L.clip_amd_bench_modes.argtypes = [i32, i64, i32, C.c_float, C.c_float, i32, i32]
     L.clip_amd_index_search_grouped.restype = C.c_bool
     L.clip_amd_index_search_grouped.argtypes = [vp, f32p, i32, i32, C.POINTER(C.c_int32), u64p, f32p, i64p]
     L.clip_amd_index_search_grouped_device.restype = C.c_bool
@@ -782,6 +789,10 @@ class Index:
     components(radius) groups near-duplicates at any density: the connected components of the pairs graph as one label per row (the
     lowest id of the row's group) and every row's nearest near row, computed on the device; no pair list is ever made.
 
+    modes(radius, link) organises a collection into albums, each with a cover: every row points to its nearest row of higher local density
+    (density = its number of rows within `radius`; the parent is looked for within `link`), the roots of that forest are the modes, the
+    most typical rows, and every tree is an album.  Exact and deterministic like everything else here.
+
     remove(ids) marks rows as removed: no search, range_search or pairs returns them again, ids are not renumbered and len() keeps
     counting every id ever given (`live` = len minus the removed rows); compact() drops them from device memory and renumbers the
     survivors.  search and range_search take `allow`, a bool mask of length len(index) or an array of ids: only those rows (and of those
@@ -1225,6 +1236,43 @@ class Index:
             raise RuntimeError("clip_amd_index_components_device failed (see stderr)")
 
     @staticmethod
+    def _modes_scales(radius, link):
+        """(radius, link) as the f32 values the library compares with; link None: radius.  ValueError for a NaN, before any call."""
+        radius = float(np.float32(radius))
+        link = radius if link is None else float(np.float32(link))
+        if radius != radius or link != link:
+            raise ValueError("radius and link must not be NaN")
+        return radius, link
+
+    def modes(self, radius, link=None, allow=None):
+        """Density modes: (labels int64 [n], parent int64 [n], parent_distance f32 [n], density int32 [n]).  density[x] is the number of other
+        eligible rows within `radius` of x (the distance and the <= of `pairs`).  y outranks x when density[y] > density[x], or the
+        densities are equal and y < x.  parent[x] is the nearest row within `link` (default: radius) among those that outrank x, the lower
+        id among equal distances, -1 when there is none; parent_distance[x] the distance to it, the bits `pairs` reports, +inf without a
+        parent; labels[x] the root reached by following parent: the cover of x's album.  A removed or not allowed row gets -1, -1, +inf,
+        -1.  The modes are the rows with labels[x] == x, singletons included.  `allow` (bool mask [len] or ids): only those rows are
+        eligible; the result over them is that of an index that only ever held them.  ValueError for a NaN or a malformed allow."""
+        radius, link = self._modes_scales(radius, link)
+        n = len(self)
+        words, wp = self._allow(allow)
+        labels = np.empty(n, dtype=np.int64)
+        parent = np.empty(n, dtype=np.int64)
+        dist = np.empty(n, dtype=np.float32)
+        density = np.empty(n, dtype=np.int32)
+        if lib().clip_amd_index_modes(self._live(), radius, link, wp, labels.ctypes.data_as(C.POINTER(C.c_int64)),
+                                      parent.ctypes.data_as(C.POINTER(C.c_int64)), _fp(dist), density.ctypes.data_as(C.POINTER(C.c_int32))) < 0:
+            raise RuntimeError("clip_amd_index_modes failed (see stderr)")
+        return labels, parent, dist, density
+
+    def modes_device(self, radius, d_labels, link=None, d_parent=None, d_parent_distance=None, d_density=None, d_allow=None):
+        """modes on device pointers (ints): labels [n] int64, parent [n] int64, parent_distance [n] f32 and density [n] int32 (0 / None: not
+        wanted); d_allow: uint64 words on the device (0 / None: every row); asynchronous on the context's stream."""
+        radius, link = self._modes_scales(radius, link)
+        if not lib().clip_amd_index_modes_device(self._live(), radius, link, C.c_void_p(d_allow or None), C.c_void_p(d_labels),
+                                                 C.c_void_p(d_parent or None), C.c_void_p(d_parent_distance or None), C.c_void_p(d_density or None)):
+            raise RuntimeError("clip_amd_index_modes_device failed (see stderr)")
+
+    @staticmethod
     def _join(call, n_lims, guess, name):
         """(lims, distances, ids) of a range-search / pairs call: a guessed capacity first, the exact total again when it did not fit"""
         lims = np.zeros(n_lims, dtype=np.int64)
@@ -1375,6 +1423,13 @@ def bench_range(dtype, n, dim, n_queries, radius, iters=10):
 def bench_components(dtype, n, dim, radius, iters=3):
     """Microseconds per clip_amd_index_components (host form) over the seeded rows of bench_range (clip_amd_bench_components); < 0 on error."""
     return float(lib().clip_amd_bench_components(Index.DTYPES[dtype], int(n), int(dim), float(radius), int(iters)))
+
+
+def bench_modes(dtype, n, dim, radius, link=None, copies=0, iters=3):
+    """Microseconds per clip_amd_index_modes (host form); copies 0: the seeded rows of bench_range, copies > 0: groups of a row and that
+    many noisy copies (clip_amd_bench_modes); < 0 on error."""
+    return float(lib().clip_amd_bench_modes(Index.DTYPES[dtype], int(n), int(dim), float(radius), float(radius if link is None else link), int(copies),
+                                            int(iters)))
 
 
 def bench_knn(dtype, n, dim, k, route=0, iters=3):

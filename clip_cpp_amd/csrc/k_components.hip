@@ -14,28 +14,22 @@
 //                             returned, and every step moves one side to a strictly smaller id.  No waits, flags or fences, and no path
 //                             compression inside the launch.  Two walks that end at one id: already connected, loads only.
 //                             Nearest: key = (order-preserving bits of d) << 32 | other id, folded into both endpoints with a 64-bit
-//                             atomicMin behind a plain load (keys only fall: a stale value is an upper bound, "my key >= what I read"
-//                             skips the atomic safely).  The minimum of a set does not depend on the order either.
-//   components_jump_kernel    one pass of pointer doubling, out[i] = in[in[i]]: ceil(log2 n) passes in launches of their own (later
-//                             launches of the stream see the link launch's atomics) flatten every tree, a path of n rows included
+//                             atomicMin behind a plain load (fold_nearest of nearest_key.h: keys only fall, a stale value is an upper
+//                             bound, "my key >= what I read" skips the atomic safely).  The minimum of a set does not depend on the
+//                             order either.
+//   flatten_forest            (nearest_key.h, shared with k_modes.hip) pointer doubling, out[i] = in[in[i]]: ceil(log2 n) passes in launches
+//                             of their own (later launches of the stream see the link launch's atomics) flatten every tree, a path of
+//                             n rows included
 //   components_finish_kernel  labels (int64; -1 for a row that is not eligible), the nearest keys decoded to f32 distance and int64 id
 //                             (+inf / -1: no near row), and the number of roots with a nearest id = components of two or more rows
 // Plain launches on the caller's stream; the link kernel's LDS is join_tile.h's 72 KB; no scratch.
 
 #include "join_tile.h"
+#include "nearest_key.h"
 
 namespace clipamd {
 
 namespace {
-
-constexpr unsigned long long NO_KEY = ~0ull;
-
-// f32 bits -> u32 in the order of the values (d may be a tiny negative number), and back
-__device__ __forceinline__ uint32_t ordered_bits(float d) {
-    const uint32_t u = __float_as_uint(d);
-    return (u & 0x80000000u) ? ~u : u | 0x80000000u;
-}
-__device__ __forceinline__ float ordered_value(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? u & 0x7fffffffu : ~u); }
 
 // up from x while the loaded parent differs: every value ever stored in parent[x] is x or a smaller id of x's component, so whatever
 // age the loaded values have, the walk descends and ends at an ancestor of x (agent-scope loads: past the L1, only for fresher values)
@@ -45,10 +39,6 @@ __device__ __forceinline__ int walk_up(const int * parent, int x) {
         if (t == x) return x;
         x = t;
     }
-}
-
-__device__ __forceinline__ void fold_nearest(unsigned long long * nearest, int x, unsigned long long key) {
-    if (key < nearest[x]) atomicMin(nearest + x, key);
 }
 
 __device__ __forceinline__ void link_pair(int * parent, unsigned long long * nearest, int a, int b, float d) {
@@ -78,11 +68,6 @@ __global__ void __launch_bounds__(256) components_init_kernel(int * __restrict__
 template <typename T, bool MASKED>
 __global__ void __launch_bounds__(JOIN_THREADS) components_link_kernel(const JoinParams p, int * parent, unsigned long long * nearest) {
     join_tiles<T, 4, 4, 2, MASKED>(p, [&](int64_t qi, int64_t row, float d) { link_pair(parent, nearest, (int)qi, (int)row, d); });
-}
-
-__global__ void __launch_bounds__(256) components_jump_kernel(const int * __restrict__ in, int * __restrict__ out, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = in[in[i]];
 }
 
 __global__ void __launch_bounds__(256) components_finish_kernel(const int * __restrict__ root, const unsigned long long * __restrict__ nearest,
@@ -134,13 +119,8 @@ bool launch_components(const void * rows, const float * rinv, int64_t n, int Dpa
         return mask ? launch_link_m<T, true>(p, parent, nearest, stream) : launch_link_m<T, false>(p, parent, nearest, stream);
     });
     if (!ok) return false;
-    int * cur = parent;                                        // a pointer reaches 2^t steps up after t passes; a tree is at most n - 1 deep
-    for (int64_t reach = 1; reach < n - 1; reach *= 2) {
-        int * next = cur == parent ? parent + n : parent;
-        hipLaunchKernelGGL(components_jump_kernel, dim3(grid), dim3(256), 0, stream, (const int *)cur, next, n);
-        cur = next;
-    }
-    hipLaunchKernelGGL(components_finish_kernel, dim3(grid), dim3(256), 0, stream, (const int *)cur, (const unsigned long long *)nearest, mask, n, labels,
+    const int * root = flatten_forest(parent, n, stream);
+    hipLaunchKernelGGL(components_finish_kernel, dim3(grid), dim3(256), 0, stream, root, (const unsigned long long *)nearest, mask, n, labels,
                        nearest_distance, nearest_id, groups);
     return hipGetLastError() == hipSuccess;
 }

@@ -413,6 +413,16 @@ bool launch_components(const void * rows, const float * rinv, int64_t n, int Dpa
                        unsigned long long * nearest, int64_t * labels, float * nearest_distance, int64_t * nearest_id, unsigned long long * groups,
                        hipStream_t stream);
 
+// Density modes over the same pairs (k_modes.hip): density = a row's near rows at `radius`; a row's parent = its nearest row within `link`
+// among those that outrank it (higher density, or equal density and lower id), lower id first among equal distances.  Workspaces: count
+// [n] u32, key [n] u64, parent [2 n] i32 (all initialised here).  labels [n] i64: the root of the row's tree, -1 for a row that is not
+// eligible; parent_id [n] i64 / parent_distance [n] f32 / density [n] i32 (each may be NULL): -1 / +inf for a root, density -1 for a row
+// that is not eligible; *modes (may be NULL; zero it first) receives the number of eligible rows without a parent.  Everything on the
+// device, n < 2^31.
+bool launch_modes(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, float radius, float link, const uint32_t * mask,
+                  uint32_t * count, unsigned long long * key, int * parent, int64_t * labels, int64_t * parent_id, float * parent_distance,
+                  int * density, unsigned long long * modes, hipStream_t stream);
+
 // Distinct search (k_distinct.hip).  A query's pool: `pool` slots of pool_dist / pool_ids ([nq][pool], device) as launch_search_finish
 // leaves them (sorted, real members first, empty slots id -1).  near: near[q][a][w], [nq][pool][distinct_near_words(pool)] 32-bit words,
 // bit b & 31 of word b >> 5 of rank a set when ranks a < b are two members at distance <= radius (the distance of pairs: row min id as

@@ -4,7 +4,7 @@
 // searches with query sets (the set fold of k_sets.hip in the finish's place), distinct searches (the pools of a search, then the near
 // bitmap and the walk of k_distinct.hip), compound queries (the placement and the scan of k_compound.hip in front of the same merge tree),
 // appending one index to another, the count -> lims -> scatter -> sort -> finish sequence of
-// range search and pairs (k_join.hip), connected components (the link -> flatten -> finish sequence of k_components.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
+// range search and pairs (k_join.hip), connected components (the link -> flatten -> finish sequence of k_components.hip), density modes (k_modes.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
 // Replaces the usearch index of the reference's examples/image-search (build.cpp / search.cpp) with an exact search on the GPU.
 // Single owners: search_device_impl (the passes of a search: one ScanArgs per scan launch, whatever the selection), search_blocks and
 // query_block (the blocked host forms of stored-row queries), upload_allow / upload_groups / stage_inputs (a call's inputs on the device),
@@ -90,6 +90,9 @@ struct clip_amd_index {
     Buf cparent;                   // the union-find: two [n] i32 arrays (the passes that flatten it go from one to the other)
     Buf cnear;                     // [n] nearest keys (u64)
     Buf couts;                     // host form: group count (u64), labels + nearest ids (int64), nearest distances
+    // density modes (the forest goes through cparent, the keys through cnear)
+    Buf mcount;                    // [n] near rows of every row (u32)
+    Buf mouts;                     // host form: mode count (u64), labels + parents (int64), parent distances, densities
 };
 
 namespace {
@@ -934,6 +937,55 @@ int64_t components_host(clip_amd_index * ix, float radius, const uint64_t * allo
     if (ndist) (void)hipMemcpyAsync(ndist, d_ndist, n * 4, hipMemcpyDeviceToHost, st);
     if (nid) (void)hipMemcpyAsync(nid, d_nid, n * 8, hipMemcpyDeviceToHost, st);
     return stream_done(ix, fn) ? (int64_t)groups : -1;
+}
+
+// Density modes on the device: labels and, where asked for, every row's parent, the distance to it and its density; d_modes (may be NULL):
+// the number of modes.  Queues the launches and returns; ix->n > 0.
+bool modes_impl(clip_amd_index * ix, float radius, float link, const uint32_t * d_allow, int64_t * d_labels, int64_t * d_parent, float * d_pdist,
+                int * d_density, unsigned long long * d_modes, const char * fn) {
+    const uint32_t * mask = nullptr;
+    if (!effective_mask(ix, d_allow, mask)) return false;
+    if (!ensure(ix, ix->cparent, (size_t)ix->n * 2 * sizeof(int)) || !ensure(ix, ix->cnear, (size_t)ix->n * 8) ||
+        !ensure(ix, ix->mcount, (size_t)ix->n * 4))
+        return false;
+    if (d_modes) (void)hipMemsetAsync(d_modes, 0, 8, stream_of(ix));
+    if (!launch_modes(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, radius, link, mask, (uint32_t *)ix->mcount.p,
+                      (unsigned long long *)ix->cnear.p, (int *)ix->cparent.p, d_labels, d_parent, d_pdist, d_density, d_modes, stream_of(ix))) {
+        fprintf(stderr, "%s: launch failed\n", fn);
+        return false;
+    }
+    return true;
+}
+
+bool check_modes_args(const clip_amd_index * ix, float radius, float link, const void * labels, const char * fn) {
+    if (!check_components_args(ix, radius, labels, fn)) return false;
+    if (std::isnan(link)) { fprintf(stderr, "%s: link is NaN\n", fn); return false; }
+    return true;
+}
+
+// The host form: the outputs in their workspace, then copied out with the mode count.  Returns that count or -1.
+int64_t modes_host(clip_amd_index * ix, float radius, float link, const uint64_t * allow, int64_t * labels, int64_t * parent, float * pdist,
+                   int * density, const char * fn) {
+    if (ix->n == 0) return 0;
+    hipStream_t st = stream_of(ix);
+    const size_t n = (size_t)ix->n;
+    const uint32_t * d_allow = nullptr;
+    if (!upload_allow(ix, allow, d_allow) || !ensure(ix, ix->mouts, 8 + n * 24)) return -1;
+    unsigned long long * d_modes = (unsigned long long *)ix->mouts.p;
+    int64_t * d_labels = (int64_t *)((char *)ix->mouts.p + 8);
+    int64_t * d_parent = d_labels + n;
+    float * d_pdist = (float *)(d_parent + n);
+    int * d_density = (int *)(d_pdist + n);
+    if (!modes_impl(ix, radius, link, d_allow, d_labels, parent ? d_parent : nullptr, pdist ? d_pdist : nullptr, density ? d_density : nullptr,
+                    d_modes, fn))
+        return -1;
+    unsigned long long modes = 0;
+    (void)hipMemcpyAsync(&modes, d_modes, 8, hipMemcpyDeviceToHost, st);
+    (void)hipMemcpyAsync(labels, d_labels, n * 8, hipMemcpyDeviceToHost, st);
+    if (parent) (void)hipMemcpyAsync(parent, d_parent, n * 8, hipMemcpyDeviceToHost, st);
+    if (pdist) (void)hipMemcpyAsync(pdist, d_pdist, n * 4, hipMemcpyDeviceToHost, st);
+    if (density) (void)hipMemcpyAsync(density, d_density, n * 4, hipMemcpyDeviceToHost, st);
+    return stream_done(ix, fn) ? (int64_t)modes : -1;
 }
 
 bool add_device_impl(clip_amd_index * ix, const float * d_vecs, int64_t n) {
@@ -1784,6 +1836,25 @@ bool clip_amd_index_components_device(struct clip_amd_index * ix, float radius, 
     });
 }
 
+int64_t clip_amd_index_modes(struct clip_amd_index * ix, float radius, float link, const uint64_t * allow, int64_t * labels, int64_t * parent,
+                             float * parent_distance, int32_t * density) {
+    return guarded(__func__, (int64_t)-1, [&](const char * fn) -> int64_t {
+        if (!check_modes_args(ix, radius, link, labels, fn)) return -1;
+        (void)hipSetDevice(ix->device);
+        return modes_host(ix, radius, link, allow, labels, parent, parent_distance, density, fn);
+    });
+}
+
+bool clip_amd_index_modes_device(struct clip_amd_index * ix, float radius, float link, const uint64_t * d_allow, int64_t * d_labels,
+                                 int64_t * d_parent, float * d_parent_distance, int32_t * d_density) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_modes_args(ix, radius, link, d_labels, fn)) return false;
+        if (ix->n == 0) return true;
+        (void)hipSetDevice(ix->device);
+        return modes_impl(ix, radius, link, (const uint32_t *)d_allow, d_labels, d_parent, d_parent_distance, d_density, nullptr, fn);
+    });
+}
+
 bool clip_amd_index_search_ids_device(struct clip_amd_index * ix, const int64_t * d_ids, int n_ids, int k, int exclude_self,
                                       const uint64_t * d_allow, float * d_distances, int64_t * d_out_ids) {
     return guarded(__func__, false, [&](const char * fn) {
@@ -1964,6 +2035,20 @@ float clip_amd_bench_components(int dtype, int64_t n, int dim, float radius, int
             std::vector<float> ndist((size_t)n);
             if (hipDeviceSynchronize() != hipSuccess || components_host(ix, radius, nullptr, labels.data(), ndist.data(), nid.data(), fn) < 0) return -4.f;
             return time_wall(iters, [&]() { return components_host(ix, radius, nullptr, labels.data(), ndist.data(), nid.data(), fn) >= 0; });
+        });
+    });
+}
+
+float clip_amd_bench_modes(int dtype, int64_t n, int dim, float radius, float link, int copies, int iters) {
+    return guarded(__func__, -4.f, [&](const char * fn) {
+        const bool args_ok = !std::isnan(radius) && !std::isnan(link) && copies >= 0;
+        return bench_on_gallery(dtype, n, dim, 0, iters, args_ok, copies > 0 ? copies : PLANT_JOIN, [&](clip_amd_index * ix, float *) {
+            std::vector<int64_t> labels((size_t)n), parent((size_t)n);
+            std::vector<float> pdist((size_t)n);
+            std::vector<int> density((size_t)n);
+            auto call = [&]() { return modes_host(ix, radius, link, nullptr, labels.data(), parent.data(), pdist.data(), density.data(), fn) >= 0; };
+            if (hipDeviceSynchronize() != hipSuccess || !call()) return -4.f;
+            return time_wall(iters, call);
         });
     });
 }

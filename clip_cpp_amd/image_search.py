@@ -7,6 +7,7 @@ build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.In
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-n N] [--distinct R] [--in PREFIX]... [--db DIR] --like INDEXED/IMAGE/PATH
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N] [--in PREFIX]... [--db DIR] [--and TERM]... [--not TERM]... [--not-margin M] <query or --like PATH>
     python -m clip_cpp_amd.image_search dedup  [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R] [--prune]
+    python -m clip_cpp_amd.image_search albums [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R] [--link T] [--min N] [-n COUNT]
     python -m clip_cpp_amd.image_search neighbors [-m MODEL] [-v N] [--db DIR] [-n N]
     python -m clip_cpp_amd.image_search label  [-m MODEL] [-v N] [-t N] [--db DIR] [-n N] LABEL [LABEL ...]
     python -m clip_cpp_amd.image_search merge  [-m MODEL] [-v N] --db DIR --from DIR2 [--from DIR3 ...] [-d R]
@@ -27,6 +28,12 @@ groups separated by a blank line, and "main: %d groups, %d images".  `dedup --pr
 lowest id stays, the others leave the index (Index.remove + Index.compact) and images.paths, both files are rewritten as `update` rewrites
 them, and no image file on disk is touched; it prints the groups at verbosity > 0, then "main: %d removed, %d kept", and rewrites nothing
 when there is nothing to remove.
+`albums` organises the database by content (Index.modes, one call; nothing is encoded): every image points to its nearest image of higher
+local density (density = the images within distance R of it, -d as in `dedup`; the parent is looked for within --link T, default R), so
+every tree is an album and its root, the most typical image, the cover.  It prints "albums:" at verbosity > 0, then the albums of at
+least --min N images (default 2), largest first, equal sizes in order of the cover's id, at most -n COUNT of them: the cover's path on a
+line of its own, then "  %f %s" per other member in id order (the distance to its parent), albums separated by a blank line, and
+"main: %d albums, %d images".  Among exact copies the lowest id is the cover, the image `dedup --prune` keeps.
 `search --like PATH` asks for "more like this one": the query is the indexed image whose line in images.paths equals PATH as written
 (Index.search_ids: its stored row, nothing is decoded or encoded, so a text-only or vision-less model is enough); the image itself is not
 listed.  It composes with -n and --in, not with a positional query or -d.
@@ -59,7 +66,7 @@ grid (Clip.encode_image_files(grid=G)), so a small object that hardly moves the 
 images.paths keeps one line per image; DIR/images.regions holds "grid G" and then one line "image x y w h" per index row.  `search` on
 such a database ranks images by their best row (Index.search_grouped with group = image): each image is printed once, with its best row's
 distance and, when that row is a tile, " [x,y,w,h]" behind the path; a query image is encoded whole; --in selects the rows of the matching
-images.  update, merge, dedup, neighbors, label and search --like / -d do not support a database built with --grid yet and say so.
+images.  update, merge, dedup, albums, neighbors, label and search --like / -d do not support a database built with --grid yet and say so.
 
 `match` asks a gridded database which other images contain what an image contains: both sides are images made of 1 + G * G rows, and two
 images match through their best pair of regions, one from each (query sets: Index.search_ids_sets / Index.search_sets with group = image).
@@ -110,22 +117,24 @@ def _err(msg):
     print(msg, file=sys.stderr, flush=True)
 
 
-def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False, merge=False, match=False):
-    """Reference-style option parsing (examples/image-search/{build,search}.cpp my_app_params_parse); `dedup`, `neighbors` and `merge` take
-    no positional arguments; `update` takes build's directories, but neither a default model nor --dtype (both come from the database);
+def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False, merge=False, match=False, albums=False):
+    """Reference-style option parsing (examples/image-search/{build,search}.cpp my_app_params_parse); `dedup`, `albums`, `neighbors` and `merge`
+    take no positional arguments; `update` takes build's directories, but neither a default model nor --dtype (both come from the database);
     `label` takes the labels; `merge` needs --from at least once; `match` takes at most one image path."""
-    p = dict(threads=4, verbose=1, db=".", dtype="f16", results=1 if label else 5, max_distance=DEDUP_RADIUS if dedup else None,
+    p = dict(threads=4, verbose=1, db=".", dtype="f16", results=1 if label else 5, max_distance=DEDUP_RADIUS if dedup or albums else None,
              model="../models/ggml-model-f16.bin" if build else "", rest=[], like=None)
     p["in"] = []
     if merge:
         p["from"] = []
-    search = not (build or dedup or update or neighbors or label or merge or match)
+    if albums:
+        p.update(results=None, link=None, min_size=2)      # every album; link = the radius
+    search = not (build or dedup or update or neighbors or label or merge or match or albums)
     seen = set()
     i = 0
     while i < len(argv):
         a = argv[i]
         takes = {"-m": "model", "--model": "model", "-v": "verbose", "--verbose": "verbose", "--db": "db"}
-        if not (dedup or neighbors or merge):
+        if not (dedup or neighbors or merge or albums):
             takes.update({"-t": "threads", "--threads": "threads"})
         if build:
             takes["--dtype"] = "dtype"
@@ -134,6 +143,9 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
             takes.update({"-n": "results", "--results": "results"})
         elif merge:
             takes.update({"-d": "max_distance", "--max-distance": "max_distance", "--from": "from"})
+        elif albums:
+            takes.update({"-d": "max_distance", "--max-distance": "max_distance", "--link": "link", "--min": "min_size", "-n": "results",
+                          "--results": "results"})
         elif not update:
             takes.update({"-d": "max_distance", "--max-distance": "max_distance"})
             if not dedup:
@@ -154,10 +166,10 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
                 i += 1
                 continue
             try:
-                p[key] = int(argv[i]) if key in ("threads", "verbose", "results", "grid") else float(argv[i]) if key in ("max_distance", "distinct", "not_margin") else argv[i]
+                p[key] = int(argv[i]) if key in ("threads", "verbose", "results", "grid", "min_size") else float(argv[i]) if key in ("max_distance", "distinct", "not_margin", "link") else argv[i]
             except ValueError:
                 return None
-            if key in ("max_distance", "distinct", "not_margin") and p[key] != p[key]:      # NaN
+            if key in ("max_distance", "distinct", "not_margin", "link") and p[key] != p[key]:      # NaN
                 return None
             if key == "grid" and not 1 <= p[key] <= MAX_GRID:
                 print("main: --grid takes 1 ... %d (1: whole images only), not %d" % (MAX_GRID, p[key]))
@@ -165,12 +177,12 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         elif dedup and a == "--prune":
             p["prune"] = True
         elif a in ("-h", "--help"):
-            _help(build, p, dedup, update, neighbors, label, merge, match)
+            _help(build, p, dedup, update, neighbors, label, merge, match, albums)
             sys.exit(0)
         elif a.startswith("-"):
             print("main: unrecognized argument: %s" % a)
             return None
-        elif dedup or neighbors or merge:
+        elif dedup or neighbors or merge or albums:
             print("main: unexpected argument: %s" % a)
             return None
         elif build or update or label or match:
@@ -183,7 +195,7 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         if p["rest"] or "max_distance" in seen:
             print("main: --like cannot be combined with a query or with -d: it lists the -n nearest images of an indexed one")
             return None
-    elif (not p["rest"] and not (dedup or neighbors or merge or match)) or (build and p["dtype"] not in ("f16", "f32", "i8")):
+    elif (not p["rest"] and not (dedup or neighbors or merge or match or albums)) or (build and p["dtype"] not in ("f16", "f32", "i8")):
         return None
     if merge and not p["from"]:
         return None
@@ -204,16 +216,30 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
     if {"distinct", "max_distance"} <= seen:
         print("main: --distinct and -d cannot be combined: --distinct R thins the -n nearest, -d R prints every image within R")
         return None
-    if {"results", "max_distance"} <= seen:
+    if {"results", "max_distance"} <= seen and not albums:         # (albums: -n counts albums, -d is the density radius)
         print("main: -n and -d cannot be combined: -n N prints the N nearest, -d R every image within R")
         return None
     return p
 
 
-def _help(build, p, dedup=False, update=False, neighbors=False, label=False, merge=False, match=False):
+def _help(build, p, dedup=False, update=False, neighbors=False, label=False, merge=False, match=False, albums=False):
     radius = ("  -d R, --max-distance R: %s within cosine distance R (<= R). Default: %s. %g is a starting point for embeddings of near-identical"
               " images, not a tuned value: check a few groups of your collection and adjust R")
-    if match:
+    if albums:
+        print("Usage: python -m clip_cpp_amd.image_search albums [options]")
+        print("\nGroups the images of an index built by `build` into albums, each with a cover: every image points to its nearest image of higher")
+        print("local density, every tree of that forest is an album and its root, the most typical image, the cover. Nothing is encoded.")
+        print("\nOptions:")
+        print("  -h, --help: Show this message and exit")
+        print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default (loaded only to place the index on its device).")
+        print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
+        print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
+        print(radius % ("an image's density is the number of images", DEDUP_RADIUS, DEDUP_RADIUS))
+        print("  --link T: an image joins the album of its nearest image of higher density (equal density: lower id) within cosine distance T"
+              " (<= T). Default: R. A larger T gives fewer, larger albums")
+        print("  --min N: print only the albums of at least N images. Default: 2 (1: single images too)")
+        print("  -n COUNT, --results COUNT: print at most COUNT albums, the largest. Default: all")
+    elif match:
         print("Usage: python -m clip_cpp_amd.image_search match [options] [indexed/image/path or /path/to/query/image]")
         print("\nOn a database built with `build --grid G`: the other images that contain what an image contains. Two images match through")
         print("their best pair of regions, one from each. A path that equals a line of %s is an indexed image (nothing is decoded or" % PATHS_FILE)
@@ -295,7 +321,7 @@ def _help(build, p, dedup=False, update=False, neighbors=False, label=False, mer
         print("  --db <dir>: directory that receives %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
         print("  --dtype f16|f32|i8: stored precision of the index (i8: int8 rows, half of f16's memory). Default: %s" % p["dtype"])
         print("  --grid G: index regions as well: every image gives 1 + G*G rows, the whole image and the tiles of a G x G grid, and `search`"
-              " ranks images by their best row (2 ... %d; update, merge, dedup, neighbors, label and search --like / -d do not support such"
+              " ranks images by their best row (2 ... %d; update, merge, dedup, albums, neighbors, label and search --like / -d do not support such"
               " a database yet). Default: 1, whole images only" % MAX_GRID)
     else:
         print("Usage: python -m clip_cpp_amd.image_search search [options] <search string or /path/to/query/image>")
@@ -818,6 +844,56 @@ def component_groups(labels, nearest_distance):
     return [list(zip(g.tolist(), dist[g].tolist())) for g in np.split(order, cuts) if g.size]
 
 
+def album_groups(labels, parent_distance, min_size=2):
+    """The albums of Index.modes' output: a list of (cover id, [(id, distance to its parent), ...] the other members in id order) over the
+    albums of at least min_size rows (the cover counts), largest first, equal sizes in order of the cover's id.  Rows with label -1 are in
+    no album."""
+    labels = np.asarray(labels, dtype=np.int64)
+    dist = np.asarray(parent_distance, dtype=np.float32).astype(np.float64)
+    ids = np.flatnonzero(labels >= 0)
+    order = ids[np.argsort(labels[ids], kind="stable")]          # by album (its label is its cover), ids ascending within one
+    cuts = np.flatnonzero(np.diff(labels[order])) + 1
+    albums = [(int(labels[g[0]]), g[g != labels[g[0]]]) for g in np.split(order, cuts) if g.size >= max(int(min_size), 1)]
+    albums.sort(key=lambda a: (-a[1].size, a[0]))
+    return [(cover, list(zip(g.tolist(), dist[g].tolist()))) for cover, g in albums]
+
+
+def albums(argv):
+    import clip_cpp_amd
+    p = _parse(argv, build=False, albums=True)
+    if p is None:
+        _help(False, dict(verbose=1, db="."), albums=True)
+        return 1
+    if _refuse_gridded(p["db"], "albums"):
+        return 1
+    image_paths = _read_db(p)
+    if image_paths is None:
+        return 1
+    try:
+        clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])      # only the index's device: no image is encoded
+    except RuntimeError:
+        print("main: Unable to load model from %s" % p["model"])
+        return 1
+    index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
+    labels, _, parent_distance, _ = index.modes(p["max_distance"], p["link"])
+    groups = album_groups(labels, parent_distance, p["min_size"])
+    if p["results"] is not None:
+        groups = groups[:max(p["results"], 0)]
+    if p["verbose"] > 0:
+        print("albums:")
+    for g, (cover, members) in enumerate(groups):
+        if g:
+            print()
+        print(image_paths[cover])
+        for i, d in members:
+            print("  %f %s" % (d, image_paths[i]))
+    print("main: %d albums, %d images" % (len(groups), sum(1 + len(m) for _, m in groups)))
+    sys.stdout.flush()
+    index.close()
+    clip.close()
+    return 0
+
+
 def dedup(argv):
     import clip_cpp_amd
     p = _parse(argv, build=False, dedup=True)
@@ -1112,10 +1188,12 @@ def match(argv):
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
-    commands = {"build": build, "update": update, "search": search, "dedup": dedup, "neighbors": neighbors, "label": label, "merge": merge, "match": match}
+    commands = {"build": build, "update": update, "search": search, "dedup": dedup, "neighbors": neighbors, "label": label, "merge": merge, "match": match,
+                "albums": albums}
     if not argv or argv[0] not in commands:
         print("Usage: python -m clip_cpp_amd.image_search {build|search|dedup} [options] ...  (-h after the command for its options)")
         print("       python -m clip_cpp_amd.image_search update [options] dir [more dirs]  (an existing database brought in line with the disk)")
+        print("       python -m clip_cpp_amd.image_search albums [options]  (the database grouped by content: albums, each with its most typical image as the cover)")
         print("       python -m clip_cpp_amd.image_search neighbors [options]  (every indexed image's nearest other images; search --like PATH for one)")
         print("       python -m clip_cpp_amd.image_search label [options] LABEL [LABEL ...]  (every indexed image's best-fitting labels)")
         print("       python -m clip_cpp_amd.image_search merge [options] --db DIR --from DIR2 [--from DIR3 ...]  (append databases, nothing encoded twice)")

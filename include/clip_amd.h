@@ -483,6 +483,32 @@ bool clip_amd_index_components_device(struct clip_amd_index * ix, float radius, 
 /* Average wall time (microseconds) of one clip_amd_index_components (host form, all three outputs) over the seeded rows of
  * clip_amd_bench_range; < 0 on error.  Used by scripts/components_bench.py. */
 float clip_amd_bench_components(int dtype, int64_t n, int dim, float radius, int iters);
+/* Density modes: the index grouped into albums, each with a cover.  Every row points to its nearest row of higher local density; the roots
+ * of that forest are the modes (the most typical rows, not outliers), every tree is an album and its root the cover.
+ * E is the set of eligible rows (live and set in allow, layout as live_mask, NULL = every live row); for a pair {x, y} of E, d(x, y) is
+ * the distance clip_amd_index_pairs reports for (min, max), the same bits from the same chain.  radius and link are compared in f32.
+ * density [size] int32: the number of y in E, y != x, with d(x, y) <= radius.
+ * y OUTRANKS x when density[y] > density[x], or the densities are equal and y < x.
+ * parent [size] int64: the y that minimises (d(x, y), y) over the rows of E that outrank x and have d(x, y) <= link; -1 when there is none.
+ * parent_distance [size] f32: that distance, the bits pairs reports; +INFINITY without a parent.
+ * labels [size] int64: the root reached from x by following parent (rank rises strictly along every step: no cycle).
+ * A row outside E gets label -1, parent -1, distance +INFINITY and density -1.  parent, parent_distance and density may each be NULL.
+ * The host form returns the number of modes: the rows of E without a parent, singletons included; 0 for an empty index (nothing is
+ * written); -1 on error.  Among exact copies the lowest id is the root.  Results are bit-identical run to run, however rows were split
+ * across add calls and across save / load, and do not depend on the order of any atomic; over E they are those of an index to which only
+ * the rows of E were ever added (ids mapped in order).
+ * -1 / false with a message on stderr, nothing launched, for a NULL index, NULL labels or a NaN radius or link (pass link = radius for one
+ * scale; link = INFINITY leaves only the top-ranked row as a root).
+ * Host form: host arrays, synchronous on the ctx stream.  Device form: allow (trusted) and the outputs in HBM, asynchronous on the ctx
+ * stream, synchronises with nothing on the host.  Device memory beyond the index: 20 bytes per row (the host form 24 more for its results). */
+int64_t clip_amd_index_modes(struct clip_amd_index * ix, float radius, float link, const uint64_t * allow, int64_t * labels, int64_t * parent,
+                             float * parent_distance, int32_t * density);
+bool clip_amd_index_modes_device(struct clip_amd_index * ix, float radius, float link, const uint64_t * d_allow, int64_t * d_labels,
+                                 int64_t * d_parent, float * d_parent_distance, int32_t * d_density);
+/* Average wall time (microseconds) of one clip_amd_index_modes (host form, all four outputs); copies == 0: over the seeded rows of
+ * clip_amd_bench_range (sparse), copies > 0: over the groups of a row and `copies` noisy copies of clip_amd_bench_search_distinct (dense);
+ * < 0 on error.  Used by scripts/modes_bench.py. */
+float clip_amd_bench_modes(int dtype, int64_t n, int dim, float radius, float link, int copies, int iters);
 
 /* ---- kernel-level test hooks (used by tests/ only; host pointers, synchronous) ----
  * Y[M,N] = X[M,K] . W[N,K]^T (+bias) through the production dequant-GEMM kernel.
