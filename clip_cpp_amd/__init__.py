@@ -90,6 +90,7 @@ AMD_SYMBOLS = [
     "clip_amd_bench_search_compound",
     "clip_amd_index_components", "clip_amd_index_components_device", "clip_amd_bench_components",
     "clip_amd_index_modes", "clip_amd_index_modes_device", "clip_amd_bench_modes",
+    "clip_amd_index_spread", "clip_amd_index_spread_device", "clip_amd_bench_spread",
 ]
 
 _lib = None
@@ -279,6 +280,12 @@ def lib():
     L.clip_amd_index_modes_device.argtypes = [vp, C.c_float, C.c_float, vp, vp, vp, vp, vp]
     L.clip_amd_bench_modes.restype = C.c_float
     L.clip_amd_bench_modes.argtypes = [i32, i64, i32, C.c_float, C.c_float, i32, i32]
+    L.clip_amd_index_spread.restype = i64
+    L.clip_amd_index_spread.argtypes = [vp, i64, C.c_float, i64p, i64, u64p, i64p, f32p, i64p, f32p, f32p]
+    L.clip_amd_index_spread_device.restype = C.c_bool
+    L.clip_amd_index_spread_device.argtypes = [vp, i64, C.c_float, i64p, i64, vp, vp, vp, vp, vp, vp, vp]
+    L.clip_amd_bench_spread.restype = C.c_float
+    L.clip_amd_bench_spread.argtypes = [i32, i64, i32, i64, i32, i32]
     L.clip_amd_index_search_grouped.restype = C.c_bool
     L.clip_amd_index_search_grouped.argtypes = [vp, f32p, i32, i32, C.POINTER(C.c_int32), u64p, f32p, i64p]
     L.clip_amd_index_search_grouped_device.restype = C.c_bool
@@ -793,6 +800,12 @@ class Index:
     (density = its number of rows within `radius`; the parent is looked for within `link`), the roots of that forest are the modes, the
     most typical rows, and every tree is an album.  Exact and deterministic like everything else here.
 
+    spread(n) answers "show me n rows that between them cover everything in here": greedy farthest-first selection (k-center).  From the
+    seeds, or the lowest id, the row farthest from everything chosen so far is taken next, until n rows are chosen or nothing is farther
+    than `radius` from a chosen one.  It needs no radius, returns exactly n rows (when there are that many), every prefix of them is
+    within a factor 2 of the best possible cover, and reach[t] is the coverage radius of the t rows before it.  With `allow` it is the
+    diverse-subset step after a search: ids of the 1000 nearest rows in, 20 of them spread apart out (spread(20, allow=ids)).
+
     remove(ids) marks rows as removed: no search, range_search or pairs returns them again, ids are not renumbered and len() keeps
     counting every id ever given (`live` = len minus the removed rows); compact() drops them from device memory and renumbers the
     survivors.  search and range_search take `allow`, a bool mask of length len(index) or an array of ids: only those rows (and of those
@@ -1273,6 +1286,75 @@ class Index:
             raise RuntimeError("clip_amd_index_modes_device failed (see stderr)")
 
     @staticmethod
+    def _spread_args(n, radius, seeds):
+        """(n, stop radius as the f32 the library compares with, seeds int64 [s]); radius None: never stop.  ValueError for a NaN and for
+        n < max(1, len(seeds)), before any call."""
+        n = int(n)
+        stop = float("-inf") if radius is None else float(np.float32(radius))
+        if stop != stop:
+            raise ValueError("radius must not be NaN")
+        seeds = np.ascontiguousarray([] if seeds is None else seeds, dtype=np.int64).reshape(-1)
+        if n < max(1, seeds.size):
+            raise ValueError("n = %d: at least 1 and at least the %d seeds" % (n, seeds.size))
+        return n, stop, seeds
+
+    def _check_seeds(self, seeds, eligible):
+        """ValueError for a seed that is out of range, repeated or not eligible (eligible: bool [len])"""
+        if seeds.size == 0:
+            return
+        if seeds.min() < 0 or seeds.max() >= len(self):
+            raise ValueError("seeds must be ids of the index (0 ... %d)" % (len(self) - 1))
+        if np.unique(seeds).size != seeds.size:
+            raise ValueError("a seed is given twice")
+        if not eligible[seeds].all():
+            raise ValueError("seed %d is removed or not allowed" % int(seeds[~eligible[seeds]][0]))
+
+    def spread(self, n, radius=None, seeds=None, allow=None):
+        """Farthest-first selection: (centres int64 [m], reach f32 [m], owner int64 [len], owner_distance f32 [len], cover_radius).  The
+        first centres are `seeds` in order (default: the lowest eligible id), with reach +inf; then, while fewer than n are chosen, the
+        eligible row with the largest distance to its nearest centre (the distances and bits of `pairs`; the lowest id among equals)
+        becomes the next centre and that distance its reach, unless it is <= radius (default: never), which ends the traversal.  m <= n
+        is the number chosen.  owner[x] is the centre nearest to x, the earliest chosen among equals, owner_distance[x] the distance to
+        it; a centre owns itself at 0.0; a removed or not allowed row gets -1 / +inf.  cover_radius = the largest owner_distance of an
+        eligible row.  `allow` (bool mask [len] or ids): only those rows are eligible; the result over them is that of an index that
+        only ever held them.  ValueError for a NaN, n < max(1, len(seeds)), a seed that is not eligible or repeated, a malformed allow."""
+        n, stop, seeds = self._spread_args(n, radius, seeds)
+        size = len(self)
+        words, wp = self._allow(allow)
+        if seeds.size:
+            eligible = self.live_mask()
+            if words is not None:
+                eligible &= np.unpackbits(words.astype("<u8").view(np.uint8), bitorder="little")[:size].astype(np.bool_)
+            self._check_seeds(seeds, eligible)
+        cap = min(n, max(size, 1))
+        centres = np.empty(cap, dtype=np.int64)
+        reach = np.empty(cap, dtype=np.float32)
+        owner = np.empty(size, dtype=np.int64)
+        dist = np.empty(size, dtype=np.float32)
+        cover = C.c_float(0.0)
+        i64 = C.POINTER(C.c_int64)
+        m = lib().clip_amd_index_spread(self._live(), cap, stop, seeds.ctypes.data_as(i64) if seeds.size else None, seeds.size, wp,
+                                        centres.ctypes.data_as(i64), _fp(reach), owner.ctypes.data_as(i64), _fp(dist), C.byref(cover))
+        if m < 0:
+            raise RuntimeError("clip_amd_index_spread failed (see stderr)")
+        return centres[:m].copy(), reach[:m].copy(), owner, dist, float(cover.value)
+
+    def spread_device(self, n, d_centres, radius=None, seeds=None, d_reach=None, d_owner=None, d_owner_distance=None, d_cover_radius=None,
+                      d_count=None, d_allow=None):
+        """spread on device pointers (ints): centres [n] int64, reach [n] f32, owner [len] int64, owner_distance [len] f32, cover_radius
+        [1] f32 and count [1] int64 (0 / None: not wanted, not written); seeds: host ids; d_allow: uint64 words on the device (0 /
+        None: every row); asynchronous on the context's stream.  ValueError as for spread, but a seed's eligibility is the library's to
+        test (RuntimeError)."""
+        n, stop, seeds = self._spread_args(n, radius, seeds)
+        if seeds.size and (seeds.min() < 0 or seeds.max() >= len(self) or np.unique(seeds).size != seeds.size):
+            raise ValueError("seeds must be distinct ids of the index")
+        if not lib().clip_amd_index_spread_device(self._live(), n, stop, seeds.ctypes.data_as(C.POINTER(C.c_int64)) if seeds.size else None,
+                                                  seeds.size, C.c_void_p(d_allow or None), C.c_void_p(d_centres), C.c_void_p(d_reach or None),
+                                                  C.c_void_p(d_owner or None), C.c_void_p(d_owner_distance or None),
+                                                  C.c_void_p(d_cover_radius or None), C.c_void_p(d_count or None)):
+            raise RuntimeError("clip_amd_index_spread_device failed (see stderr)")
+
+    @staticmethod
     def _join(call, n_lims, guess, name):
         """(lims, distances, ids) of a range-search / pairs call: a guessed capacity first, the exact total again when it did not fit"""
         lims = np.zeros(n_lims, dtype=np.int64)
@@ -1430,6 +1512,12 @@ def bench_modes(dtype, n, dim, radius, link=None, copies=0, iters=3):
     many noisy copies (clip_amd_bench_modes); < 0 on error."""
     return float(lib().clip_amd_bench_modes(Index.DTYPES[dtype], int(n), int(dim), float(radius), float(radius if link is None else link), int(copies),
                                             int(iters)))
+
+
+def bench_spread(dtype, n, dim, n_max, copies=0, iters=3):
+    """Microseconds of device time per clip_amd_index_spread_device of n_max centres, no seeds, no stop radius; the data of bench_modes
+    (clip_amd_bench_spread); < 0 on error."""
+    return float(lib().clip_amd_bench_spread(Index.DTYPES[dtype], int(n), int(dim), int(n_max), int(copies), int(iters)))
 
 
 def bench_knn(dtype, n, dim, k, route=0, iters=3):

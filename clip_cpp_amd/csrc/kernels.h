@@ -423,6 +423,22 @@ bool launch_modes(const void * rows, const float * rinv, int64_t n, int Dpad, in
                   uint32_t * count, unsigned long long * key, int * parent, int64_t * labels, int64_t * parent_id, float * parent_distance,
                   int * density, unsigned long long * modes, hipStream_t stream);
 
+// Farthest-first selection (k_spread.hip).  Workspaces: gap [n] f32, opos [n] i32, slot [n_slots] u64 (slot t: the key of the centre at
+// position t, 0 = empty).  init: zeroes the slots, sets gap / opos from the mask and writes the seeds' keys (seeds: device ids), or, with
+// n_seeds == 0, the lowest eligible id's into slot 0.  sweep: one pass over the gallery against the centres of slots first ... first +
+// count - 1 (count <= 16); greedy: exits when slot `first` is empty or holds a reach <= stop; pick: the farthest row's key goes to slot
+// first + count.  grid: spread_sweep_grid(n).  finish: centres [n_max] i64 / reach [n_max] f32 (-1 / +inf past the count; n_first: the
+// slots that are centres whatever their reach), owner [n] i64, owner_distance [n] f32, cover_radius, count (each may be NULL but centres).
+int64_t spread_sweep_grid(int64_t n);
+void launch_spread_init(const uint32_t * mask, int64_t n, const int64_t * seeds, int n_seeds, float * gap, int * opos, unsigned long long * slot,
+                        int64_t n_slots, hipStream_t stream);
+bool launch_spread_sweep(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const uint32_t * mask, int first, int count,
+                         bool greedy, bool pick, float stop, float * gap, int * opos, unsigned long long * slot, int64_t grid,
+                         hipStream_t stream);
+bool launch_spread_finish(const unsigned long long * slot, int64_t n_slots, int n_first, float stop, const float * gap, const int * opos, int64_t n,
+                          int64_t n_max, int64_t * centres, float * reach, int64_t * owner, float * owner_distance, float * cover_radius,
+                          int64_t * count, hipStream_t stream);
+
 // Distinct search (k_distinct.hip).  A query's pool: `pool` slots of pool_dist / pool_ids ([nq][pool], device) as launch_search_finish
 // leaves them (sorted, real members first, empty slots id -1).  near: near[q][a][w], [nq][pool][distinct_near_words(pool)] 32-bit words,
 // bit b & 31 of word b >> 5 of rank a set when ranks a < b are two members at distance <= radius (the distance of pairs: row min id as

@@ -4,7 +4,7 @@
 // searches with query sets (the set fold of k_sets.hip in the finish's place), distinct searches (the pools of a search, then the near
 // bitmap and the walk of k_distinct.hip), compound queries (the placement and the scan of k_compound.hip in front of the same merge tree),
 // appending one index to another, the count -> lims -> scatter -> sort -> finish sequence of
-// range search and pairs (k_join.hip), connected components (the link -> flatten -> finish sequence of k_components.hip), density modes (k_modes.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
+// range search and pairs (k_join.hip), connected components (the link -> flatten -> finish sequence of k_components.hip), density modes (k_modes.hip), farthest-first selection (k_spread.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
 // Replaces the usearch index of the reference's examples/image-search (build.cpp / search.cpp) with an exact search on the GPU.
 // Single owners: search_device_impl (the passes of a search: one ScanArgs per scan launch, whatever the selection), search_blocks and
 // query_block (the blocked host forms of stored-row queries), upload_allow / upload_groups / stage_inputs (a call's inputs on the device),
@@ -93,6 +93,12 @@ struct clip_amd_index {
     // density modes (the forest goes through cparent, the keys through cnear)
     Buf mcount;                    // [n] near rows of every row (u32)
     Buf mouts;                     // host form: mode count (u64), labels + parents (int64), parent distances, densities
+    // farthest-first selection
+    Buf sgap;                      // [n] distance to the nearest centre so far (f32)
+    Buf sopos;                     // [n] position of that centre (i32)
+    Buf sslot;                     // [centres + 1] the centres' keys (u64)
+    Buf sseeds;                    // the seed ids copied from the host
+    Buf spouts;                    // host form: count (int64), cover radius, centres + owners (int64), reaches + owner distances
 };
 
 namespace {
@@ -988,6 +994,124 @@ int64_t modes_host(clip_amd_index * ix, float radius, float link, const uint64_t
     return stream_done(ix, fn) ? (int64_t)modes : -1;
 }
 
+// reach of a key slot of k_spread.hip on the host (nearest_key.h's ordered_value)
+float spread_slot_reach(unsigned long long key) {
+    uint32_t u = (uint32_t)(key >> 32);
+    u = (u & 0x80000000u) ? u & 0x7fffffffu : ~u;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
+bool check_spread_args(const clip_amd_index * ix, int64_t n_max, float stop, const int64_t * seeds, int64_t n_seeds, const void * centres,
+                       const char * fn) {
+    if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+    if (!centres) { fprintf(stderr, "%s: centres is NULL\n", fn); return false; }
+    if (std::isnan(stop)) { fprintf(stderr, "%s: stop_radius is NaN\n", fn); return false; }
+    if (n_seeds < 0 || (n_seeds > 0 && !seeds)) { fprintf(stderr, "%s: %lld seeds without ids\n", fn, (long long)n_seeds); return false; }
+    if (n_max < 1 || n_max < n_seeds) {
+        fprintf(stderr, "%s: n_max %lld with %lld seeds (at least 1 and at least the seeds)\n", fn, (long long)n_max, (long long)n_seeds);
+        return false;
+    }
+    std::vector<int64_t> sorted(seeds, seeds + n_seeds);
+    std::sort(sorted.begin(), sorted.end());
+    for (int64_t i = 0; i < n_seeds; i++) {
+        if (sorted[i] < 0 || sorted[i] >= ix->n) { fprintf(stderr, "%s: seed %lld is not a row of the index\n", fn, (long long)sorted[i]); return false; }
+        if (i > 0 && sorted[i] == sorted[i - 1]) { fprintf(stderr, "%s: seed %lld is given twice\n", fn, (long long)sorted[i]); return false; }
+    }
+    return true;
+}
+
+// Farthest-first selection on the device (arguments checked).  Queues the launches and returns: one sweep per 16 seeds, one per greedy
+// step, the finish.  A call with seeds first reads the effective mask back to test them (one wait, before anything is written); poll
+// (the host form): every 64 steps the next slot is read back and the steps that would find the traversal ended are not queued.
+bool spread_impl(clip_amd_index * ix, int64_t n_max, float stop, const int64_t * seeds, int64_t n_seeds, const uint32_t * d_allow,
+                 int64_t * d_centres, float * d_reach, int64_t * d_owner, float * d_odist, float * d_cover, int64_t * d_count, bool poll,
+                 const char * fn) {
+    hipStream_t st = stream_of(ix);
+    const int64_t n = ix->n;
+    const uint32_t * mask = nullptr;
+    if (!effective_mask(ix, d_allow, mask)) return false;
+    if (n_seeds > 0 && mask) {
+        std::vector<uint32_t> bits(live_bytes(n) / 4);
+        if (hipMemcpyAsync(bits.data(), mask, bits.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess || !stream_done(ix, fn)) return false;
+        for (int64_t i = 0; i < n_seeds; i++) {
+            if (!((bits[seeds[i] >> 5] >> (int)(seeds[i] & 31)) & 1u)) {
+                fprintf(stderr, "%s: seed %lld is removed or not allowed\n", fn, (long long)seeds[i]);
+                return false;
+            }
+        }
+    }
+    const int64_t c = std::min(n_max, n);                      // centres there can be
+    const int n_first = (int)std::max<int64_t>(n_seeds, 1);
+    if (!ensure(ix, ix->sgap, (size_t)n * 4) || !ensure(ix, ix->sopos, (size_t)n * 4) || !ensure(ix, ix->sslot, (size_t)(c + 1) * 8) ||
+        !ensure(ix, ix->sseeds, (size_t)n_seeds * 8))
+        return false;
+    float * gap = (float *)ix->sgap.p;
+    int * opos = (int *)ix->sopos.p;
+    unsigned long long * slot = (unsigned long long *)ix->sslot.p;
+    if (n_seeds > 0) (void)hipMemcpyAsync(ix->sseeds.p, seeds, (size_t)n_seeds * 8, hipMemcpyHostToDevice, st);
+    launch_spread_init(mask, n, (const int64_t *)ix->sseeds.p, (int)n_seeds, gap, opos, slot, c + 1, st);
+    bool ok = hipGetLastError() == hipSuccess;
+    const int64_t grid = n > 0 ? spread_sweep_grid(n) : 0;
+    const auto sweep = [&](int64_t first, int count, bool greedy) {
+        return launch_spread_sweep(ix->store.rows, ix->store.rinv, n, ix->Dpad, ix->dtype, mask, (int)first, count, greedy,
+                                   first + count >= n_first && first + count < c, stop, gap, opos, slot, grid, st);
+    };
+    if (n > 0) {
+        for (int64_t s0 = 0; ok && s0 < n_first; s0 += 16) ok = sweep(s0, (int)std::min<int64_t>(16, n_first - s0), false);
+        for (int64_t t = n_first; ok && t < c; t++) {
+            ok = sweep(t, 1, true);
+            if (poll && ok && (t - n_first) % 64 == 63 && t + 1 < c) {
+                unsigned long long next = 0;
+                if (hipMemcpyAsync(&next, slot + t + 1, 8, hipMemcpyDeviceToHost, st) != hipSuccess || !stream_done(ix, fn)) return false;
+                if (next == 0 || spread_slot_reach(next) <= stop) break;
+            }
+        }
+    }
+    ok = ok && launch_spread_finish(slot, c + 1, n_first, stop, gap, opos, n, n_max, d_centres, d_reach, d_owner, d_odist, d_cover, d_count, st);
+    if (!ok) fprintf(stderr, "%s: launch failed\n", fn);
+    return ok;
+}
+
+// The host form: the outputs in their workspace, then copied out with the count.  Returns that count or -1.
+int64_t spread_host(clip_amd_index * ix, int64_t n_max, float stop, const int64_t * seeds, int64_t n_seeds, const uint64_t * allow, int64_t * centres,
+                    float * reach, int64_t * owner, float * odist, float * cover, const char * fn) {
+    const size_t n = (size_t)ix->n, c = (size_t)std::min<int64_t>(n_max, ix->n);
+    int64_t m = 0;
+    if (n > 0) {
+        hipStream_t st = stream_of(ix);
+        const uint32_t * d_allow = nullptr;
+        if (!upload_allow(ix, allow, d_allow) || !ensure(ix, ix->spouts, 16 + c * 12 + n * 12)) return -1;
+        int64_t * d_count = (int64_t *)ix->spouts.p;
+        float * d_cover = (float *)(d_count + 1);
+        int64_t * d_centres = d_count + 2;
+        int64_t * d_owner = d_centres + c;
+        float * d_reach = (float *)(d_owner + n);
+        float * d_odist = d_reach + c;
+        if (!spread_impl(ix, (int64_t)c, stop, seeds, n_seeds, d_allow, d_centres, reach ? d_reach : nullptr, owner ? d_owner : nullptr,
+                         odist ? d_odist : nullptr, cover ? d_cover : nullptr, d_count, true, fn))
+            return -1;
+        std::vector<int64_t> h_centres(c);                     // the caller's arrays stay untouched when the stream fails
+        (void)hipMemcpyAsync(&m, d_count, 8, hipMemcpyDeviceToHost, st);
+        (void)hipMemcpyAsync(h_centres.data(), d_centres, c * 8, hipMemcpyDeviceToHost, st);
+        if (!stream_done(ix, fn)) return -1;
+        std::copy(h_centres.begin(), h_centres.end(), centres);
+        if (reach) (void)hipMemcpyAsync(reach, d_reach, c * 4, hipMemcpyDeviceToHost, st);
+        if (owner) (void)hipMemcpyAsync(owner, d_owner, n * 8, hipMemcpyDeviceToHost, st);
+        if (odist) (void)hipMemcpyAsync(odist, d_odist, n * 4, hipMemcpyDeviceToHost, st);
+        if (cover) (void)hipMemcpyAsync(cover, d_cover, 4, hipMemcpyDeviceToHost, st);
+        if (!stream_done(ix, fn)) return -1;
+    } else if (cover) {
+        *cover = 0.f;
+    }
+    for (int64_t i = (int64_t)c; i < n_max; i++) {
+        centres[i] = -1;
+        if (reach) reach[i] = INFINITY;
+    }
+    return m;
+}
+
 bool add_device_impl(clip_amd_index * ix, const float * d_vecs, int64_t n) {
     if (!reserve_rows(ix, ix->n + n)) return false;
     const RowStore & s = ix->store;
@@ -1855,6 +1979,27 @@ bool clip_amd_index_modes_device(struct clip_amd_index * ix, float radius, float
     });
 }
 
+int64_t clip_amd_index_spread(struct clip_amd_index * ix, int64_t n_max, float stop_radius, const int64_t * seeds, int64_t n_seeds,
+                              const uint64_t * allow, int64_t * centres, float * reach, int64_t * owner, float * owner_distance,
+                              float * cover_radius) {
+    return guarded(__func__, (int64_t)-1, [&](const char * fn) -> int64_t {
+        if (!check_spread_args(ix, n_max, stop_radius, seeds, n_seeds, centres, fn)) return -1;
+        (void)hipSetDevice(ix->device);
+        return spread_host(ix, n_max, stop_radius, seeds, n_seeds, allow, centres, reach, owner, owner_distance, cover_radius, fn);
+    });
+}
+
+bool clip_amd_index_spread_device(struct clip_amd_index * ix, int64_t n_max, float stop_radius, const int64_t * seeds, int64_t n_seeds,
+                                  const uint64_t * d_allow, int64_t * d_centres, float * d_reach, int64_t * d_owner,
+                                  float * d_owner_distance, float * d_cover_radius, int64_t * d_count) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_spread_args(ix, n_max, stop_radius, seeds, n_seeds, d_centres, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return spread_impl(ix, n_max, stop_radius, seeds, n_seeds, ix->n > 0 ? (const uint32_t *)d_allow : nullptr, d_centres, d_reach, d_owner,
+                           d_owner_distance, d_cover_radius, d_count, false, fn);
+    });
+}
+
 bool clip_amd_index_search_ids_device(struct clip_amd_index * ix, const int64_t * d_ids, int n_ids, int k, int exclude_self,
                                       const uint64_t * d_allow, float * d_distances, int64_t * d_out_ids) {
     return guarded(__func__, false, [&](const char * fn) {
@@ -2049,6 +2194,28 @@ float clip_amd_bench_modes(int dtype, int64_t n, int dim, float radius, float li
             auto call = [&]() { return modes_host(ix, radius, link, nullptr, labels.data(), parent.data(), pdist.data(), density.data(), fn) >= 0; };
             if (hipDeviceSynchronize() != hipSuccess || !call()) return -4.f;
             return time_wall(iters, call);
+        });
+    });
+}
+
+float clip_amd_bench_spread(int dtype, int64_t n, int dim, int64_t n_max, int copies, int iters) {
+    return guarded(__func__, -4.f, [&](const char * fn) {
+        const bool args_ok = n_max >= 1 && copies >= 0;
+        return bench_on_gallery(dtype, n, dim, 0, iters, args_ok, copies > 0 ? copies : PLANT_JOIN, [&](clip_amd_index * ix, float *) {
+            Buf out;                                           // centres + owners (int64), reaches + owner distances, cover radius, count
+            const size_t c = (size_t)n_max, rows = (size_t)n;
+            if (!ensure(ix, out, (c + rows) * 12 + 16)) return -4.f;
+            int64_t * d_centres = (int64_t *)out.p;
+            int64_t * d_owner = d_centres + c;
+            int64_t * d_count = d_owner + rows;
+            float * d_reach = (float *)(d_count + 1);
+            float * d_odist = d_reach + c;
+            float * d_cover = d_odist + rows;
+            auto call = [&]() {
+                return spread_impl(ix, n_max, -INFINITY, nullptr, 0, nullptr, d_centres, d_reach, d_owner, d_odist, d_cover, d_count, false, fn);
+            };
+            if (!call() || hipDeviceSynchronize() != hipSuccess) return -4.f;
+            return time_device(iters, call);
         });
     });
 }

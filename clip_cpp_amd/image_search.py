@@ -8,6 +8,7 @@ build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.In
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N] [--in PREFIX]... [--db DIR] [--and TERM]... [--not TERM]... [--not-margin M] <query or --like PATH>
     python -m clip_cpp_amd.image_search dedup  [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R] [--prune]
     python -m clip_cpp_amd.image_search albums [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R] [--link T] [--min N] [-n COUNT]
+    python -m clip_cpp_amd.image_search spread [-m MODEL] [-v N] [--db DIR] -n N [-d R] [--in PREFIX]... [--from INDEXED/IMAGE/PATH]...
     python -m clip_cpp_amd.image_search neighbors [-m MODEL] [-v N] [--db DIR] [-n N]
     python -m clip_cpp_amd.image_search label  [-m MODEL] [-v N] [-t N] [--db DIR] [-n N] LABEL [LABEL ...]
     python -m clip_cpp_amd.image_search merge  [-m MODEL] [-v N] --db DIR --from DIR2 [--from DIR3 ...] [-d R]
@@ -34,6 +35,13 @@ every tree is an album and its root, the most typical image, the cover.  It prin
 least --min N images (default 2), largest first, equal sizes in order of the cover's id, at most -n COUNT of them: the cover's path on a
 line of its own, then "  %f %s" per other member in id order (the distance to its parent), albums separated by a blank line, and
 "main: %d albums, %d images".  Among exact copies the lowest id is the cover, the image `dedup --prune` keeps.
+`spread -n N` answers "show me N images that between them cover everything in here" (Index.spread, one call; nothing is encoded, nothing
+on disk changes): the first indexed image, or the --from images in order, then again and again the image farthest from everything picked
+so far, until N are picked or, with -d R, every image is within R of a picked one.  It prints "spread:" at verbosity > 0, then the picks
+in order, "%f %s (+K)": the distance at which the image was picked (inf for the first and for --from images; each is the coverage radius
+of the picks before it), its path and the number of other images nearer to it than to any other pick; then
+"main: %d images, every other image within %f of one of them".  --in PREFIX restricts both the picks and what they cover.  To spread the
+results of a search, use the library: Index.search, then Index.spread(n, allow=ids).
 `search --like PATH` asks for "more like this one": the query is the indexed image whose line in images.paths equals PATH as written
 (Index.search_ids: its stored row, nothing is decoded or encoded, so a text-only or vision-less model is enough); the image itself is not
 listed.  It composes with -n and --in, not with a positional query or -d.
@@ -66,7 +74,7 @@ grid (Clip.encode_image_files(grid=G)), so a small object that hardly moves the 
 images.paths keeps one line per image; DIR/images.regions holds "grid G" and then one line "image x y w h" per index row.  `search` on
 such a database ranks images by their best row (Index.search_grouped with group = image): each image is printed once, with its best row's
 distance and, when that row is a tile, " [x,y,w,h]" behind the path; a query image is encoded whole; --in selects the rows of the matching
-images.  update, merge, dedup, albums, neighbors, label and search --like / -d do not support a database built with --grid yet and say so.
+images.  update, merge, dedup, albums, spread, neighbors, label and search --like / -d do not support a database built with --grid yet and say so.
 
 `match` asks a gridded database which other images contain what an image contains: both sides are images made of 1 + G * G rows, and two
 images match through their best pair of regions, one from each (query sets: Index.search_ids_sets / Index.search_sets with group = image).
@@ -117,24 +125,26 @@ def _err(msg):
     print(msg, file=sys.stderr, flush=True)
 
 
-def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False, merge=False, match=False, albums=False):
-    """Reference-style option parsing (examples/image-search/{build,search}.cpp my_app_params_parse); `dedup`, `albums`, `neighbors` and `merge`
-    take no positional arguments; `update` takes build's directories, but neither a default model nor --dtype (both come from the database);
+def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False, merge=False, match=False, albums=False, spread=False):
+    """Reference-style option parsing (examples/image-search/{build,search}.cpp my_app_params_parse); `dedup`, `albums`, `spread`, `neighbors`
+    and `merge` take no positional arguments; `spread` needs -n; `update` takes build's directories, but neither a default model nor --dtype (both come from the database);
     `label` takes the labels; `merge` needs --from at least once; `match` takes at most one image path."""
     p = dict(threads=4, verbose=1, db=".", dtype="f16", results=1 if label else 5, max_distance=DEDUP_RADIUS if dedup or albums else None,
              model="../models/ggml-model-f16.bin" if build else "", rest=[], like=None)
     p["in"] = []
-    if merge:
+    if merge or spread:
         p["from"] = []
+    if spread:
+        p.update(results=None)                             # -n has no default: it is the question
     if albums:
         p.update(results=None, link=None, min_size=2)      # every album; link = the radius
-    search = not (build or dedup or update or neighbors or label or merge or match or albums)
+    search = not (build or dedup or update or neighbors or label or merge or match or albums or spread)
     seen = set()
     i = 0
     while i < len(argv):
         a = argv[i]
         takes = {"-m": "model", "--model": "model", "-v": "verbose", "--verbose": "verbose", "--db": "db"}
-        if not (dedup or neighbors or merge or albums):
+        if not (dedup or neighbors or merge or albums or spread):
             takes.update({"-t": "threads", "--threads": "threads"})
         if build:
             takes["--dtype"] = "dtype"
@@ -143,6 +153,9 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
             takes.update({"-n": "results", "--results": "results"})
         elif merge:
             takes.update({"-d": "max_distance", "--max-distance": "max_distance", "--from": "from"})
+        elif spread:
+            takes.update({"-d": "max_distance", "--max-distance": "max_distance", "-n": "results", "--results": "results", "--in": "in",
+                          "--from": "from"})
         elif albums:
             takes.update({"-d": "max_distance", "--max-distance": "max_distance", "--link": "link", "--min": "min_size", "-n": "results",
                           "--results": "results"})
@@ -177,12 +190,12 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         elif dedup and a == "--prune":
             p["prune"] = True
         elif a in ("-h", "--help"):
-            _help(build, p, dedup, update, neighbors, label, merge, match, albums)
+            _help(build, p, dedup, update, neighbors, label, merge, match, albums, spread)
             sys.exit(0)
         elif a.startswith("-"):
             print("main: unrecognized argument: %s" % a)
             return None
-        elif dedup or neighbors or merge or albums:
+        elif dedup or neighbors or merge or albums or spread:
             print("main: unexpected argument: %s" % a)
             return None
         elif build or update or label or match:
@@ -195,10 +208,19 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         if p["rest"] or "max_distance" in seen:
             print("main: --like cannot be combined with a query or with -d: it lists the -n nearest images of an indexed one")
             return None
-    elif (not p["rest"] and not (dedup or neighbors or merge or match or albums)) or (build and p["dtype"] not in ("f16", "f32", "i8")):
+    elif (not p["rest"] and not (dedup or neighbors or merge or match or albums or spread)) or (build and p["dtype"] not in ("f16", "f32", "i8")):
         return None
     if merge and not p["from"]:
         return None
+    if spread:
+        if p["results"] is None:
+            return None
+        if len(set(p["from"])) != len(p["from"]):
+            print("main: --from names the first images to take: each can be given once")
+            return None
+        if p["results"] < max(1, len(p["from"])):
+            print("main: -n %d: spread picks at least one image and at least the %d given with --from" % (p["results"], len(p["from"])))
+            return None
     if match and len(p["rest"]) > 1:
         print("main: match takes one image path, or none for every indexed image")
         return None
@@ -216,16 +238,32 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
     if {"distinct", "max_distance"} <= seen:
         print("main: --distinct and -d cannot be combined: --distinct R thins the -n nearest, -d R prints every image within R")
         return None
-    if {"results", "max_distance"} <= seen and not albums:         # (albums: -n counts albums, -d is the density radius)
+    if {"results", "max_distance"} <= seen and not (albums or spread):     # (albums: -n counts albums, -d is the density radius; spread: both end it)
         print("main: -n and -d cannot be combined: -n N prints the N nearest, -d R every image within R")
         return None
     return p
 
 
-def _help(build, p, dedup=False, update=False, neighbors=False, label=False, merge=False, match=False, albums=False):
+def _help(build, p, dedup=False, update=False, neighbors=False, label=False, merge=False, match=False, albums=False, spread=False):
     radius = ("  -d R, --max-distance R: %s within cosine distance R (<= R). Default: %s. %g is a starting point for embeddings of near-identical"
               " images, not a tuned value: check a few groups of your collection and adjust R")
-    if albums:
+    if spread:
+        print("Usage: python -m clip_cpp_amd.image_search spread [options] -n N")
+        print("\nPicks N images of an index built by `build` that between them cover the collection: the first indexed image (or the --from")
+        print("images), then again and again the image farthest from everything picked so far. Nothing is encoded, nothing on disk changes.")
+        print("Each line is the distance at which the image was picked (how far the farthest image was from the picks before it), its path and")
+        print("the number of other images that are nearer to it than to any other pick.")
+        print("\nOptions:")
+        print("  -h, --help: Show this message and exit")
+        print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default (loaded only to place the index on its device).")
+        print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
+        print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
+        print("  -n N, --results N: pick N images (fewer when there are fewer, or when -d ends it). Required")
+        print("  -d R, --max-distance R: stop once every image is within cosine distance R (<= R) of a picked one. Default: never")
+        print("  --in <prefix>: only images whose indexed path starts with <prefix> are picked from and covered; may be repeated")
+        print("  --from <indexed/image/path>: start from this image, as written in %s; may be repeated: they are taken first, in order."
+              " Default: the first indexed image" % PATHS_FILE)
+    elif albums:
         print("Usage: python -m clip_cpp_amd.image_search albums [options]")
         print("\nGroups the images of an index built by `build` into albums, each with a cover: every image points to its nearest image of higher")
         print("local density, every tree of that forest is an album and its root, the most typical image, the cover. Nothing is encoded.")
@@ -894,6 +932,57 @@ def albums(argv):
     return 0
 
 
+def spread_lines(centres, reach, owner, paths):
+    """The lines of `spread` for Index.spread's output: one per centre in pick order, "%f %s (+K)": the reach (inf for a seed or the first
+    centre), the path and K, the number of other rows the centre owns."""
+    centres = np.asarray(centres, dtype=np.int64)
+    owner = np.asarray(owner, dtype=np.int64)
+    owned = np.bincount(owner[owner >= 0], minlength=len(paths)) if owner.size else np.zeros(len(paths), dtype=np.int64)
+    return ["%f %s (+%d)" % (float(r), paths[int(c)], int(owned[c]) - 1) for c, r in zip(centres.tolist(), np.asarray(reach, dtype=np.float32).tolist())]
+
+
+def spread(argv):
+    import clip_cpp_amd
+    p = _parse(argv, build=False, spread=True)
+    if p is None:
+        _help(False, dict(verbose=1, db="."), spread=True)
+        return 1
+    if _refuse_gridded(p["db"], "spread"):
+        return 1
+    image_paths = _read_db(p)
+    if image_paths is None:
+        return 1
+    seeds = []
+    for path in p["from"]:
+        if path not in image_paths:
+            _err("main: '%s' is not in the database (paths are compared as written in %s)" % (path, PATHS_FILE))
+            return 1
+        seeds.append(image_paths.index(path))
+    allow = None
+    if p["in"]:
+        allow = np.array([path.startswith(tuple(p["in"])) for path in image_paths], dtype=np.bool_)
+        outside = [image_paths[i] for i in seeds if not allow[i]]
+        if outside:
+            _err("main: '%s' does not start with an --in prefix: a --from image must be one of the images picked from" % outside[0])
+            return 1
+    try:
+        clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])      # only the index's device: no image is encoded
+    except RuntimeError:
+        print("main: Unable to load model from %s" % p["model"])
+        return 1
+    index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
+    centres, reach, owner, _, cover = index.spread(p["results"], p["max_distance"], seeds or None, allow=allow)
+    if p["verbose"] > 0:
+        print("spread:")
+    for line in spread_lines(centres, reach, owner, image_paths):
+        print(line)
+    print("main: %d images, every other image within %f of one of them" % (len(centres), cover))
+    sys.stdout.flush()
+    index.close()
+    clip.close()
+    return 0
+
+
 def dedup(argv):
     import clip_cpp_amd
     p = _parse(argv, build=False, dedup=True)
@@ -1189,11 +1278,12 @@ def match(argv):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     commands = {"build": build, "update": update, "search": search, "dedup": dedup, "neighbors": neighbors, "label": label, "merge": merge, "match": match,
-                "albums": albums}
+                "albums": albums, "spread": spread}
     if not argv or argv[0] not in commands:
         print("Usage: python -m clip_cpp_amd.image_search {build|search|dedup} [options] ...  (-h after the command for its options)")
         print("       python -m clip_cpp_amd.image_search update [options] dir [more dirs]  (an existing database brought in line with the disk)")
         print("       python -m clip_cpp_amd.image_search albums [options]  (the database grouped by content: albums, each with its most typical image as the cover)")
+        print("       python -m clip_cpp_amd.image_search spread [options] -n N  (N images that between them cover the database: farthest-first selection)")
         print("       python -m clip_cpp_amd.image_search neighbors [options]  (every indexed image's nearest other images; search --like PATH for one)")
         print("       python -m clip_cpp_amd.image_search label [options] LABEL [LABEL ...]  (every indexed image's best-fitting labels)")
         print("       python -m clip_cpp_amd.image_search merge [options] --db DIR --from DIR2 [--from DIR3 ...]  (append databases, nothing encoded twice)")

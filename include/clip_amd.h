@@ -509,6 +509,42 @@ bool clip_amd_index_modes_device(struct clip_amd_index * ix, float radius, float
  * clip_amd_bench_range (sparse), copies > 0: over the groups of a row and `copies` noisy copies of clip_amd_bench_search_distinct (dense);
  * < 0 on error.  Used by scripts/modes_bench.py. */
 float clip_amd_bench_modes(int dtype, int64_t n, int dim, float radius, float link, int copies, int iters);
+/* Farthest-first selection (greedy k-center): n_max rows that between them cover the index, each picked as the row farthest from
+ * everything chosen before it.  Every prefix of the result is a 2-approximate k-center solution, and reach[t] is the coverage radius of
+ * the prefix before position t, so one call gives the table of "how many rows" against "how far is everything else".
+ * E is the set of eligible rows (live and set in allow, layout as live_mask, NULL = every live row); for a pair {x, y} of E, d(x, y) is
+ * the distance clip_amd_index_pairs reports for (min, max), the same bits from the same chain.  Every comparison is in f32 on those bits.
+ * seeds [n_seeds] (host ids in both forms): the first centres, in order; each must be in E and they must be distinct.  n_seeds == 0: the
+ * first centre is the lowest id of E.  Then, while fewer than n_max centres are chosen and E holds a row that is not a centre: with
+ * gap(x) = min d(c, x) over the centres so far, take the x of largest gap, the lowest id among equals; if gap(x) <= stop_radius the
+ * traversal stops without it (stop_radius = -INFINITY never stops), else x is the next centre, at position t, with reach[t] = gap(x).
+ * n_max above the size of E is fine: the traversal ends when every row of E is a centre.
+ * centres [n_max] int64: the centres in pick order, -1 past the count.  reach [n_max] f32: +INFINITY for the seeds (and the automatic
+ * first centre) and past the count, else the gap at which the centre was picked (non-increasing).  owner [size] int64 / owner_distance
+ * [size] f32: the centre that minimises (d(c, x), position of c), so the earliest chosen among equals; a centre owns itself at exactly
+ * 0; a row outside E gets -1 / +INFINITY.  cover_radius: one float, the maximum of owner_distance over E (0 when every row of E is a
+ * centre).  Every output but centres may be NULL.
+ * The host form returns the number of centres m (0: E is empty; only centres, reach and cover_radius are written); the device form writes
+ * it to d_count (int64, may be NULL).  Results are bit-identical run to run, however rows were split across add calls and across save /
+ * load, and do not depend on the order of any atomic; over E they are those of an index to which only the rows of E were ever added (ids
+ * mapped in order).
+ * -1 / false with a message on stderr, no output written, for a NULL index, NULL centres, a NaN stop_radius, n_max < 1, n_max < n_seeds, or
+ * a seed that is out of range, removed, not allowed or repeated.
+ * Host form: host arrays, synchronous on the ctx stream; it reads one slot back every 64 steps and stops queueing once the traversal
+ * has ended.  Device form: allow (trusted) and the outputs in HBM, asynchronous on the ctx stream, all min(n_max, size) steps queued (a step
+ * after the end exits at once); with seeds and a mask to test them against it waits once for the stream, before anything is written.
+ * One launch per 16 seeds and one per further centre, each reading the eligible rows once.  Device memory beyond the index: 8 bytes per
+ * row and 8 per centre (the host form 12 more of each for its results). */
+int64_t clip_amd_index_spread(struct clip_amd_index * ix, int64_t n_max, float stop_radius, const int64_t * seeds, int64_t n_seeds,
+                              const uint64_t * allow, int64_t * centres, float * reach, int64_t * owner, float * owner_distance,
+                              float * cover_radius);
+bool clip_amd_index_spread_device(struct clip_amd_index * ix, int64_t n_max, float stop_radius, const int64_t * seeds, int64_t n_seeds,
+                                  const uint64_t * d_allow, int64_t * d_centres, float * d_reach, int64_t * d_owner,
+                                  float * d_owner_distance, float * d_cover_radius, int64_t * d_count);
+/* Device time (microseconds, HIP events) of one clip_amd_index_spread_device of n_max centres without seeds or stop radius, all outputs;
+ * copies == 0: over the seeded rows of clip_amd_bench_range, copies > 0: over the groups of clip_amd_bench_search_distinct; < 0 on error.
+ * Used by scripts/spread_bench.py. */
+float clip_amd_bench_spread(int dtype, int64_t n, int dim, int64_t n_max, int copies, int iters);
 
 /* ---- kernel-level test hooks (used by tests/ only; host pointers, synchronous) ----
  * Y[M,N] = X[M,K] . W[N,K]^T (+bias) through the production dequant-GEMM kernel.
