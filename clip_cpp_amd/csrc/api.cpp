@@ -1167,6 +1167,75 @@ static bool test_rows_ok(const int32_t * in_rows, int64_t in_row_mul, int64_t ro
 }
 static bool test_sync() { return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess; }
 
+// k_gemm_f32.hip as an f32 file runs it (clip_amd.h): f32 weight (ggml type 0) through the production repack, and with act_f32 != 0 the activations as
+// f32 rows [M][Kpad] — exactly M rows, columns K .. Kpad - 1 zero as the layer chain's rows are — behind the half_t pointer, GemmParams::act_f32 set and the
+// fp16-output epilogues read back as the f32 they store (gemm_f32_kernel<EPI, true>, epilogue_f32_out).  act_f32 == 0: the fp16-activation form of
+// clip_amd_test_gemm_ex on the same buffers.  y travels up before the launch and all of it comes back: what no kernel wrote is the caller's fill.
+// Every argument is checked on the host before the device is looked for.  The epilogues load and store 4 columns per lane and decide n < N and
+// n < qcols per group of 4: N % 4 == 0 and qcols % 4 == 0 (kernel_limits of load.cpp holds a model to the same multiple — projection_dim % 4, and the
+// head sizes it admits are multiples of 8 — and to no coarser one).
+int clip_amd_test_gemm_f32(const void * w, int64_t N, int64_t K, const float * x, int64_t M, const float * bias, const float * resid, int epilogue,
+                           int qcols, float qscale, int Np, int T, const float * pos, int act_f32, int guard_rows, float * y) {
+    if (!w || !x || !y || N <= 0 || K <= 0 || M <= 0 || M > (int64_t)1 << 24 || N > (int64_t)1 << 20 || K > (int64_t)1 << 20) return -3;
+    if (N % 4 || qcols < 0 || qcols > N || qcols % 4 || epilogue < 0 || epilogue > 5 || (act_f32 != 0 && act_f32 != 1) || guard_rows < 0 || guard_rows > 1024) return -3;
+    if (epilogue == 4 && !resid) return -3;
+    if (epilogue == 5 && (act_f32 || Np <= 0 || T < Np + 1 || M % Np || !pos)) return -3;      // (production's patch GEMM reads the fp16 im2col rows)
+    if (!test_device()) return -1;
+    DevWeight W;
+    void * wbase = nullptr;
+    if (!repack_for_test(0, w, N, K, W, &wbase)) return -2;
+    const int Kpad = W.Kpad;
+    const bool f16_out = !act_f32 && epilogue >= 1 && epilogue <= 3;
+    const size_t rows = epilogue == 5 ? (size_t)(M / Np) * T : (size_t)M, n_out = (rows + guard_rows) * (size_t)N;
+    DBuf dx32((size_t)M * Kpad * 4), dx16(act_f32 ? 0 : (size_t)M * Kpad * 2), dbias((size_t)N * 4), dout32(n_out * 4), dout16(f16_out ? n_out * 2 : 0),
+        dpos(epilogue == 5 ? (size_t)T * N * 4 : 0);
+    int rc = 0;
+    if (!dx32.p || !dx16.p || !dbias.p || !dout32.p || !dout16.p || !dpos.p) rc = -1;
+    hipStream_t s = nullptr;
+    if (rc == 0) {
+        (void)hipMemset(dx32.p, 0, (size_t)M * Kpad * 4);
+        (void)hipMemcpy2D(dx32.p, (size_t)Kpad * 4, x, (size_t)K * 4, (size_t)K * 4, (size_t)M, hipMemcpyHostToDevice);
+        upload(dbias, bias, (size_t)N * 4);
+        upload(dout32, y, n_out * 4);
+        GemmParams p;
+        p.lda = Kpad; p.M = (int)M; p.W = W; p.bias = bias ? (const float *)dbias.p : nullptr; p.ldc = (int)N; p.out = dout32.p;
+        if (act_f32) {
+            p.A = (const half_t *)dx32.p;
+            p.act_f32 = true;
+        } else {
+            launch_f32_to_f16((const float *)dx32.p, Kpad, (half_t *)dx16.p, Kpad, (int)M, (int)K, Kpad, s);
+            p.A = (const half_t *)dx16.p;
+        }
+        if (f16_out) {      // the caller's fill in fp16 under the fp16 rows (a fill that fp16 holds exactly comes back bit for bit)
+            launch_f32_to_f16((const float *)dout32.p, (int)N, (half_t *)dout16.p, (int)N, (int)(rows + guard_rows), (int)N, (int)N, s);
+            p.out = dout16.p;
+        }
+        int epi = EPI_F32;
+        switch (epilogue) {
+        case 0: epi = EPI_F32; break;
+        case 1: epi = EPI_F16; p.qscale = qscale; p.qcols = qcols; break;
+        case 2: epi = EPI_GELU_F16; break;
+        case 3: epi = EPI_QGELU_F16; break;
+        case 4:             // x += A W^T + bias: resid and out are one buffer (forward.cpp resid_linear)
+            epi = EPI_RESID_F32;
+            upload(dout32, resid, (size_t)M * N * 4);
+            p.resid = (const float *)dout32.p;
+            break;
+        case 5:
+            epi = EPI_PATCH_F32;
+            upload(dpos, pos, (size_t)T * N * 4);
+            p.Np = Np; p.T = T; p.pos = (const float *)dpos.p; p.bias = nullptr;
+            break;
+        }
+        launch_gemm(p, epi, 0, s);
+        if (f16_out) launch_f16_to_f32((const half_t *)dout16.p, (int)N, (float *)dout32.p, (int)N, (int)(rows + guard_rows), (int)N, s);
+        if (!test_sync()) rc = -4;
+        else download(y, dout32, n_out * 4);
+    }
+    (void)hipFree(wbase);
+    return rc;
+}
+
 int clip_amd_test_layernorm_ex(const float * x, int64_t x_rows, int ldx, const int32_t * in_rows, int in_row_mul, const float * w, const float * b, float eps,
                                int rows, int h, uint16_t * out16, int ld16, float * out32, int ld32) {
     if (!test_device()) return -1;

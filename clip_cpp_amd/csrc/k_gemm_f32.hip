@@ -1,6 +1,6 @@
 // k_gemm_f32.hip — weight GEMM for f32 GGUF files on the exact-f32 matrix instruction of gfx950 (v_mfma_f32_16x16x4_f32).
 //
-//   out[M][N] = epilogue( X[M][K] (fp16 activations, widened exactly to f32) · W[N][K]^T (f32, as the file holds it) + bias )
+//   out[M][N] = epilogue( X[M][K] (f32 activations, or fp16 ones widened exactly to f32) · W[N][K]^T (f32, as the file holds it) + bias )
 //
 // Reference: ggml multiplies an f32 weight with its f32 vec_dot (type dispatch behind ggml_mul_mat, clip.cpp:1360-1380, 1392, 1407, 1416,
 // 1443; text :1079-1160).  Until round 4 the loader rounded f32 linear weights to fp16 (load.cpp) — narrower than the reference for that
@@ -8,7 +8,8 @@
 // here: products and sums in f32 (the MFMA is an fmaf chain, bit for bit: MI355X_MICROARCH.md), 1/16 of the fp16 matrix rate — an f32 file
 // is a debugging / reference format, not a benchmarked configuration.  Since round 6 the ACTIVATIONS of such a model are f32 too
 // (GemmParams::act_f32: LayerNorm output, q/k/v, attention output, GELU output — forward.cpp): f32 x f32 as in ggml, nothing narrower than the
-// reference anywhere for this file type; the fp16-activation form (AF32 = false) remains for callers that hand in fp16 rows (kernel test hooks).
+// reference anywhere for this file type; the fp16-activation form (AF32 = false) remains for callers that hand in fp16 rows: the patch embedding of an f32
+// file (EPI_PATCH_F32 on the fp16 im2col rows) and the kernel test hooks.  tests/test_gpu_gemm_f32.py holds both forms to each other and to float64.
 //
 // Mapping: workgroup = 64 weight rows x 64 activation rows, 4 waves; wave w owns weight rows 16 w ... 16 w + 15 against all 64 activation
 // rows = 1 x 4 accumulator fragments in the layout of the other GEMM kernels (weight = MFMA "A" operand: a lane ends up with 4 consecutive

@@ -561,6 +561,20 @@ int clip_amd_test_gemm(int type, const void * w_raw, int64_t N, int64_t K, const
 int clip_amd_test_gemm_ex(int type, const void * w_raw, int64_t N, int64_t K, const float * x, int64_t M,
                           const float * bias, const float * resid, float * y, int epilogue, int tile,
                           int qcols, float qscale, int Np, int T, const float * pos);
+/* The GEMM of an f32 file (k_gemm_f32.hip) in the form the layers run it.  w is f32 [N][K] (ggml type 0), x f32 [M][K]; bias [N] and resid [M][N] may be
+ * NULL (resid is required by epilogue 4); epilogue, qcols / qscale, Np / T / pos as for clip_amd_test_gemm_ex.
+ * act_f32 = 1: the activations go up as f32 rows [M][Kpad] (exactly M rows, columns K .. Kpad - 1 zero), GemmParams::act_f32 is set, and epilogues 1-3
+ * come back as the f32 values the kernel stores, with no fp16 step.  act_f32 = 0: x is rounded to fp16 and epilogues 1-3 store fp16 (returned widened),
+ * as clip_amd_test_gemm_ex does.  Epilogue 4 adds into the residual rows in place (resid and out are one buffer, as in the layers).
+ * y is in and out: [M + guard_rows][N], for epilogue 5 [(M / Np) * T + guard_rows][N].  It is uploaded before the launch and all of it is downloaded,
+ * so a row the kernel must not write (the guard rows, the class-token rows of epilogue 5) comes back with the caller's fill (with act_f32 = 0 and
+ * epilogues 1-3 through fp16: use a fill that fp16 holds exactly).
+ * Checked on the host before the device is looked for: N % 4 == 0 and qcols % 4 == 0 (the epilogues work on groups of 4 columns; the loader holds a
+ * model to the same multiple and to no coarser one), 0 <= qcols <= N, epilogue in 0..5, act_f32 in {0, 1}, epilogue 5 only with act_f32 = 0 (the patch GEMM
+ * always reads fp16 im2col rows) and with Np >= 1, T >= Np + 1, M % Np == 0 and pos, 0 <= guard_rows <= 1024.
+ * Returns 0; -1 no device; -2 repack failed; -3 a check failed (nothing launched, y untouched); -4 HIP error. */
+int clip_amd_test_gemm_f32(const void * w, int64_t N, int64_t K, const float * x, int64_t M, const float * bias, const float * resid, int epilogue,
+                           int qcols, float qscale, int Np, int T, const float * pos, int act_f32, int guard_rows, float * y /* in and out */);
 /* LayerNorm fold A/B (the LayerNorm launches of reference clip.cpp:1350-1355,1400-1405 folded into the GEMM epilogues around them):
  *   x1 = resid + a . W1^T + b1                       [M][h]   W1: [h][K1]  (residual epilogue)
  *   y  = epi2( LN(x1; gamma, beta, eps) . W2^T + b2 )  [M][N2]  W2: [N2][h]  (epi2: 1 f16 (+ qcols / qscale), 2 gelu, 3 quick-gelu)

@@ -377,7 +377,7 @@ def test_gemm_patch_embedding_epilogue(L, B, G, h, P):
     rng = np.random.default_rng(B * 100 + G)
     Np, T, K = G * G, G * G + 1, 3 * P * P
     Wf = (rng.standard_normal((h, K)) * 0.02).astype(np.float32)
-    raw = ref.quantize(1, Wf)                               # patch kernel is always f16
+    raw = ref.quantize(1, Wf)                               # an f16 patch kernel; the f32 one: test_gpu_gemm_f32.py
     Wd = ref.dequantize(1, raw, h, K).astype(np.float64)
     X = rng.standard_normal((B * Np, K)).astype(np.float32)
     pos = (rng.standard_normal((T, h)) * 0.02).astype(np.float32)
