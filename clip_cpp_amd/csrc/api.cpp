@@ -784,6 +784,33 @@ int clip_amd_profile_read(struct clip_ctx * ctx, float * ms, int64_t * launches,
 #define CLIPAMD_TEST_HOOKS 1
 #endif
 #if CLIPAMD_TEST_HOOKS
+// Shared by the hooks.  Output buffers are filled with a poison pattern before the launch (f32: quiet NaN, fp16: 0x7e00), so what a kernel did not
+// write comes back as NaN.  The GEMM hooks also keep GUARD_ROWS rows behind every output, poisoned like the rest (zero where the rows past M must be
+// zero), and compare them on the host after the launch: a store past row M - 1 is return code -6.
+static bool test_device() {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return false; }
+    return true;
+}
+static const uint32_t POISON32 = 0x7fc00000u, POISON16 = 0x7e00u;
+static const size_t GUARD_ROWS = 2;
+static void poison32(const DBuf & d, size_t n) { if (n) (void)hipMemsetD32((hipDeviceptr_t)d.p, (int)POISON32, n); }
+static void poison16(const DBuf & d, size_t n) { if (n) (void)hipMemsetD16((hipDeviceptr_t)d.p, (unsigned short)POISON16, n); }
+static void upload(const DBuf & d, const void * src, size_t bytes) { if (src && bytes) (void)hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice); }
+static void download(void * dst, const DBuf & d, size_t bytes) { if (dst && bytes) (void)hipMemcpy(dst, d.p, bytes, hipMemcpyDeviceToHost); }
+static bool test_sync() { return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess; }
+// elements first .. first + n - 1 of d (elem_bytes 2 or 4 each) still hold `fill`
+static bool guard_intact(const DBuf & d, size_t first, size_t n, size_t elem_bytes, uint32_t fill) {
+    std::vector<unsigned char> g(n * elem_bytes);
+    if (hipMemcpy(g.data(), (const char *)d.p + first * elem_bytes, n * elem_bytes, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    for (size_t i = 0; i < n; i++) {
+        uint32_t v = 0;
+        memcpy(&v, g.data() + i * elem_bytes, elem_bytes);
+        if (v != fill) return false;
+    }
+    return true;
+}
+
 int clip_amd_test_gemm_tile(int64_t M, int64_t N, int64_t K, int quantised) {
     const int Kpad = (int)((K + 63) / 64 * 64);
     return gemm_tile_for((int)M, (int)N, Kpad, quantised != 0);
@@ -806,18 +833,24 @@ int clip_amd_test_gemm_ex(int type, const void * w_raw, int64_t N, int64_t K, co
     void * wbase = nullptr;
     if (!repack_for_test(type, w_raw, N, K, W, &wbase)) return -2;
     const int Kpad = W.Kpad;
-    const size_t out_rows = epilogue == 5 ? (size_t)(M / Np) * T : (size_t)M;
-    DBuf dx32((size_t)M * K * 4), dx16((size_t)(M + 1) * Kpad * 2), dbias((size_t)N * 4), dres((size_t)M * N * 4), dout(out_rows * N * 4), dout32(out_rows * N * 4),
+    // outputs: poisoned, GUARD_ROWS guard rows behind them; the caller's rows (resid, the fill of epilogue 5) go over the first out_rows rows only
+    const size_t out_rows = epilogue == 5 ? (size_t)(M / Np) * T : (size_t)M, n_out = out_rows * N, n_guard = GUARD_ROWS * (size_t)N;
+    const bool f16_out = epilogue >= 1 && epilogue <= 3;
+    DBuf dx32((size_t)M * K * 4), dx16((size_t)(M + 1) * Kpad * 2), dbias((size_t)N * 4), dout((n_out + n_guard) * 2), dout32((n_out + n_guard) * 4),
         dpos(epilogue == 5 ? (size_t)T * N * 4 : 16);
     int rc = 0;
     hipStream_t s = nullptr;
     (void)hipMemcpy(dx32.p, x, (size_t)M * K * 4, hipMemcpyHostToDevice);
     if (bias) (void)hipMemcpy(dbias.p, bias, (size_t)N * 4, hipMemcpyHostToDevice);
+    poison16(dout, n_out + n_guard);
+    poison32(dout32, n_out + n_guard);
+    poison16(dx16, (size_t)(M + 1) * Kpad);          // row M: clamped or prefetching reads may touch it, no stored output may depend on it
     launch_f32_to_f16((const float *)dx32.p, (int)K, (half_t *)dx16.p, Kpad, (int)M, (int)K, Kpad, s);
     GemmParams p;
     p.A = (const half_t *)dx16.p; p.lda = Kpad; p.M = (int)M; p.W = W; p.bias = bias ? (const float *)dbias.p : nullptr; p.ldc = (int)N;
     DBuf skw((size_t)64 << 20), skc(4096 * 4);   // split-K workspace + ticket counters (as load.cpp gives the ctx)
     (void)hipMemset(skc.p, 0, 4096 * 4);
+    poison32(skw, (size_t)16 << 20);
     p.sk_ws = (float *)skw.p; p.sk_ws_floats = (size_t)16 << 20; p.sk_cnt = (unsigned *)skc.p; p.sk_cnt_n = 4096;
     DBuf panel((size_t)W.Npad * W.Kpad * 2);         // fp16 panel for the 8-wave large-M kernel (quantised weights)
     p.w16_scratch = (half_t *)panel.p; p.w16_scratch_halfs = panel.p ? (size_t)W.Npad * W.Kpad : 0;
@@ -836,17 +869,19 @@ int clip_amd_test_gemm_ex(int type, const void * w_raw, int64_t N, int64_t K, co
     case 5:
         epi = EPI_PATCH_F32;
         (void)hipMemcpy(dpos.p, pos, (size_t)T * N * 4, hipMemcpyHostToDevice);
-        (void)hipMemcpy(dout32.p, y, out_rows * N * 4, hipMemcpyHostToDevice);   // caller's fill: rows the epilogue must not touch
+        (void)hipMemcpy(dout32.p, y, n_out * 4, hipMemcpyHostToDevice);   // caller's fill: rows the epilogue must not touch
         p.out = dout32.p; p.Np = Np; p.T = T; p.pos = (const float *)dpos.p; p.bias = nullptr;
         break;
     default: rc = -3;
     }
     if (rc == 0) {
         launch_gemm(p, epi, tile, s);
-        if (epi == EPI_F16 || epi == EPI_GELU_F16 || epi == EPI_QGELU_F16)
-            launch_f16_to_f32((const half_t *)dout.p, (int)N, (float *)dout32.p, (int)N, (int)M, (int)N, s);
-        if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) rc = -4;
-        else (void)hipMemcpy(y, dout32.p, out_rows * N * 4, hipMemcpyDeviceToHost);
+        if (f16_out) launch_f16_to_f32((const half_t *)dout.p, (int)N, (float *)dout32.p, (int)N, (int)M, (int)N, s);
+        if (!test_sync()) rc = -4;
+        else {
+            (void)hipMemcpy(y, dout32.p, n_out * 4, hipMemcpyDeviceToHost);
+            if (!guard_intact(dout32, n_out, n_guard, 4, POISON32) || (f16_out && !guard_intact(dout, n_out, n_guard, 2, POISON16))) rc = -6;
+        }
     }
     (void)hipFree(wbase);
     return rc;
@@ -865,17 +900,25 @@ int clip_amd_test_lnfold(int type, const void * w1_raw, int64_t h, int64_t K1, c
     if (!repack_for_test(type, w1_raw, h, K1, W1, &w1base)) return -2;
     if (!repack_for_test(type, w2_raw, N2, h, W2, &w2base)) { (void)hipFree(w1base); return -2; }
     const int st_stride = (int)((M + 63) & ~(int64_t)63);
-    DBuf da32((size_t)M * K1 * 4), da16((size_t)(M + 1) * W1.Kpad * 2), dx((size_t)M * h * 4), dxn((size_t)(M + 1) * W2.Kpad * 2), dy16((size_t)M * N2 * 2),
-        dy32((size_t)M * N2 * 4), db1((size_t)h * 4), db2((size_t)N2 * 4), dg((size_t)h * 4), dbeta((size_t)h * 4), dc((size_t)N2 * 4), dbf((size_t)N2 * 4),
+    // outputs (dx: the residual rows in place, dxn: the LayerNorm / fold operand, dy16, dy32): poisoned, GUARD_ROWS guard rows behind each; the rows of
+    // dxn at and past M must stay zero (the consumer's row M), so its guard rows keep the zero fill
+    const size_t rows_g = (size_t)M + GUARD_ROWS;
+    DBuf da32((size_t)M * K1 * 4), da16((size_t)(M + 1) * W1.Kpad * 2), dx(rows_g * h * 4), dxn(rows_g * W2.Kpad * 2), dy16(rows_g * N2 * 2),
+        dy32(rows_g * N2 * 4), db1((size_t)h * 4), db2((size_t)N2 * 4), dg((size_t)h * 4), dbeta((size_t)h * 4), dc((size_t)N2 * 4), dbf((size_t)N2 * 4),
         dstats((size_t)(h / 16) * st_stride * 8);
     hipStream_t s = nullptr;
     (void)hipMemcpy(da32.p, a, (size_t)M * K1 * 4, hipMemcpyHostToDevice);
+    poison32(dx, rows_g * h);
+    poison16(dy16, rows_g * N2);
+    poison32(dy32, rows_g * N2);
+    poison16(da16, (size_t)(M + 1) * W1.Kpad);       // row M: as in clip_amd_test_gemm_ex
     (void)hipMemcpy(dx.p, resid, (size_t)M * h * 4, hipMemcpyHostToDevice);
     (void)hipMemcpy(db1.p, b1, (size_t)h * 4, hipMemcpyHostToDevice);
     (void)hipMemcpy(db2.p, b2, (size_t)N2 * 4, hipMemcpyHostToDevice);
     (void)hipMemcpy(dg.p, gamma, (size_t)h * 4, hipMemcpyHostToDevice);
     (void)hipMemcpy(dbeta.p, beta, (size_t)h * 4, hipMemcpyHostToDevice);
-    (void)hipMemset(dxn.p, 0, (size_t)(M + 1) * W2.Kpad * 2);
+    (void)hipMemset(dxn.p, 0, rows_g * W2.Kpad * 2);
+    poison16(dxn, (size_t)M * W2.Kpad);
     // fold == 2: the centred form (GemmParams::xg_mu / ln_mu): the offsets are the row means of the INCOMING residual rows — what the
     // previous LayerNorm's consumer leaves in the layer chain — computed here in double
     DBuf dmu((size_t)M * 4), dmu2((size_t)M * 4);
@@ -891,6 +934,17 @@ int clip_amd_test_lnfold(int type, const void * w1_raw, int64_t h, int64_t K1, c
     launch_f32_to_f16((const float *)da32.p, (int)K1, (half_t *)da16.p, W1.Kpad, (int)M, (int)K1, W1.Kpad, s);
     DBuf skw((size_t)64 << 20), skc(4096 * 4);
     (void)hipMemset(skc.p, 0, 4096 * 4);
+    poison32(skw, (size_t)16 << 20);
+    // after the last launch: y widened, both outputs down, every guard row compared
+    auto finish = [&]() {
+        launch_f16_to_f32((const half_t *)dy16.p, (int)N2, (float *)dy32.p, (int)N2, (int)M, (int)N2, s);
+        if (!test_sync()) return -4;
+        (void)hipMemcpy(x1_out, dx.p, (size_t)M * h * 4, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(y_out, dy32.p, (size_t)M * N2 * 4, hipMemcpyDeviceToHost);
+        const bool ok = guard_intact(dx, (size_t)M * h, GUARD_ROWS * (size_t)h, 4, POISON32) && guard_intact(dxn, (size_t)M * W2.Kpad, GUARD_ROWS * (size_t)W2.Kpad, 2, 0u) &&
+                        guard_intact(dy16, (size_t)M * N2, GUARD_ROWS * (size_t)N2, 2, POISON16) && guard_intact(dy32, (size_t)M * N2, GUARD_ROWS * (size_t)N2, 4, POISON32);
+        return ok ? 0 : -6;
+    };
     DBuf panel1((size_t)W1.Npad * W1.Kpad * 2), panel2((size_t)W2.Npad * W2.Kpad * 2);
     auto common = [&](GemmParams & p, const DBuf & panel, const DevWeight & W) {
         p.sk_ws = (float *)skw.p; p.sk_ws_floats = (size_t)16 << 20; p.sk_cnt = (unsigned *)skc.p; p.sk_cnt_n = 4096;
@@ -928,12 +982,7 @@ int clip_amd_test_lnfold(int type, const void * w1_raw, int64_t h, int64_t K1, c
         else {
             launch_skinny(a1, EPI_RESID_F32, s);
             launch_skinny(a2, epi, s);
-            launch_f16_to_f32((const half_t *)dy16.p, (int)N2, (float *)dy32.p, (int)N2, (int)M, (int)N2, s);
-            if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) rc2 = -4;
-            else {
-                (void)hipMemcpy(x1_out, dx.p, (size_t)M * h * 4, hipMemcpyDeviceToHost);
-                (void)hipMemcpy(y_out, dy32.p, (size_t)M * N2 * 4, hipMemcpyDeviceToHost);
-            }
+            rc2 = finish();
         }
         (void)hipFree(w1base);
         (void)hipFree(w2base);
@@ -956,13 +1005,7 @@ int clip_amd_test_lnfold(int type, const void * w1_raw, int64_t h, int64_t K1, c
         p2.bias = (const float *)db2.p;
         launch_gemm(p2, epi, tile2, s);
     }
-    launch_f16_to_f32((const half_t *)dy16.p, (int)N2, (float *)dy32.p, (int)N2, (int)M, (int)N2, s);
-    int rc = 0;
-    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) rc = -4;
-    else {
-        (void)hipMemcpy(x1_out, dx.p, (size_t)M * h * 4, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(y_out, dy32.p, (size_t)M * N2 * 4, hipMemcpyDeviceToHost);
-    }
+    const int rc = finish();
     (void)hipFree(w1base);
     (void)hipFree(w2base);
     return rc;
@@ -1098,10 +1141,15 @@ int clip_amd_test_skinny(int type, const void * w_raw, int64_t N, int64_t K, con
     void * wbase = nullptr;
     if (!repack_for_test(type, w_raw, N, K, W, &wbase)) return -2;
     const int Kpad = W.Kpad;
-    DBuf dx32((size_t)M * K * 4), dx16((size_t)(M + 1) * Kpad * 2), dbias((size_t)N * 4), dout((size_t)M * N * 4), dout32((size_t)M * N * 4), dlw((size_t)K * 4), dlb((size_t)K * 4),
+    const size_t n_out = (size_t)M * N, n_guard = GUARD_ROWS * (size_t)N;      // outputs poisoned and guarded as in clip_amd_test_gemm_ex
+    const bool f16_out = epilogue >= 1 && epilogue <= 3;
+    DBuf dx32((size_t)M * K * 4), dx16((size_t)(M + 1) * Kpad * 2), dbias((size_t)N * 4), dout((n_out + n_guard) * 2), dout32((n_out + n_guard) * 4), dlw((size_t)K * 4), dlb((size_t)K * 4),
         dst((size_t)2 * SKINNY_MAX_ROWS * 128 * 8);
     hipStream_t s = nullptr;
     (void)hipMemcpy(dx32.p, x, (size_t)M * K * 4, hipMemcpyHostToDevice);
+    poison16(dout, n_out + n_guard);
+    poison32(dout32, n_out + n_guard);
+    poison16(dx16, (size_t)(M + 1) * Kpad);
     if (bias) (void)hipMemcpy(dbias.p, bias, (size_t)N * 4, hipMemcpyHostToDevice);
     (void)hipMemset(dst.p, 0, (size_t)2 * SKINNY_MAX_ROWS * 128 * 8);
     SkinnyParams p;
@@ -1134,11 +1182,11 @@ int clip_amd_test_skinny(int type, const void * w_raw, int64_t N, int64_t K, con
     if (!skinny_supported(p, epi)) rc = -5;
     else {
         launch_skinny(p, epi, s);
-        if (epi == EPI_F16 || epi == EPI_GELU_F16 || epi == EPI_QGELU_F16)
-            launch_f16_to_f32((const half_t *)dout.p, (int)N, (float *)dout32.p, (int)N, (int)M, (int)N, s);
-        if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) rc = -4;
+        if (f16_out) launch_f16_to_f32((const half_t *)dout.p, (int)N, (float *)dout32.p, (int)N, (int)M, (int)N, s);
+        if (!test_sync()) rc = -4;
         else {
-            (void)hipMemcpy(y, dout32.p, (size_t)M * N * 4, hipMemcpyDeviceToHost);
+            (void)hipMemcpy(y, dout32.p, n_out * 4, hipMemcpyDeviceToHost);
+            if (!guard_intact(dout32, n_out, n_guard, 4, POISON32) || (f16_out && !guard_intact(dout, n_out, n_guard, 2, POISON16))) rc = -6;
             if (stats_out && epi == EPI_RESID_F32) (void)hipMemcpy(stats_out, (float2 *)dst.p + (size_t)SKINNY_MAX_ROWS * 128, (size_t)128 * 128 * 8, hipMemcpyDeviceToHost);   // (rows 0..127)
         }
     }
@@ -1149,15 +1197,6 @@ int clip_amd_test_skinny(int type, const void * w_raw, int64_t N, int64_t K, con
 // ---- the memory-bound kernels at the two ends of each tower (k_misc.hip, row_stats_kernel of k_skinny.hip) ----
 // Every hook: host pointers in, ONE launch through the launch_* entry point forward.cpp calls, synchronise, host pointers out.  Output buffers are
 // filled with a poison pattern first (f32: quiet NaN, fp16: 0x7e00), so padding and rows the kernel must not write can be checked afterwards.
-static bool test_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return false; }
-    return true;
-}
-static void poison32(const DBuf & d, size_t n) { if (n) (void)hipMemsetD32((hipDeviceptr_t)d.p, 0x7fc00000, n); }
-static void poison16(const DBuf & d, size_t n) { if (n) (void)hipMemsetD16((hipDeviceptr_t)d.p, 0x7e00, n); }
-static void upload(const DBuf & d, const void * src, size_t bytes) { if (src && bytes) (void)hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice); }
-static void download(void * dst, const DBuf & d, size_t bytes) { if (dst && bytes) (void)hipMemcpy(dst, d.p, bytes, hipMemcpyDeviceToHost); }
 // the source rows of a gather (in_rows[r], or r * in_row_mul) stay inside [0, n_src)
 static bool test_rows_ok(const int32_t * in_rows, int64_t in_row_mul, int64_t rows, int64_t n_src) {
     if (!in_rows) return in_row_mul >= 0 && (rows - 1) * in_row_mul < n_src;
@@ -1165,7 +1204,6 @@ static bool test_rows_ok(const int32_t * in_rows, int64_t in_row_mul, int64_t ro
         if (in_rows[r] < 0 || in_rows[r] >= n_src) return false;
     return true;
 }
-static bool test_sync() { return hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess; }
 
 // k_gemm_f32.hip as an f32 file runs it (clip_amd.h): f32 weight (ggml type 0) through the production repack, and with act_f32 != 0 the activations as
 // f32 rows [M][Kpad] — exactly M rows, columns K .. Kpad - 1 zero as the layer chain's rows are — behind the half_t pointer, GemmParams::act_f32 set and the

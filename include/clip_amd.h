@@ -550,14 +550,21 @@ float clip_amd_bench_spread(int dtype, int64_t n, int dim, int64_t n_max, int co
  * Y[M,N] = X[M,K] . W[N,K]^T (+bias) through the production dequant-GEMM kernel.
  * w_raw is the tensor in its GGUF/ggml block layout (type: ggml type id 0,1,2,3,6,7,8).
  * epilogue: 0 plain f32 out, 1 f16 out (returned widened to f32), 2 gelu->f16, 3 quick-gelu->f16,
- *           4 residual: Y = resid + X.W^T + bias (f32).  tile: 0 auto, else BM*1000+BN. */
+ *           4 residual: Y = resid + X.W^T + bias (f32).  tile: 0 auto, else BM*1000+BN.
+ * This hook, clip_amd_test_gemm_ex, clip_amd_test_skinny and clip_amd_test_lnfold poison every buffer a kernel stores to before the launch
+ * (f32: quiet NaN 0x7fc00000, fp16: 0x7e00; also the split-K workspace and the extra activation row M that clamped or prefetching reads may
+ * touch), so an output element that no kernel wrote arrives in y as NaN, never as what an earlier call left in device memory.  Two guard
+ * rows lie behind each output (poisoned too; behind the fold's fp16(x gamma) operand they are zero, as rows at and past M must be) and are
+ * compared on the host after the launch.
+ * Returns 0; -1 no device; -2 repack failed; -3 bad arguments; -4 HIP error; -5 (skinny / lnfold) combination not covered;
+ * -6 a guard row changed: a kernel stored past row M - 1 (y is still returned). */
 int clip_amd_test_gemm(int type, const void * w_raw, int64_t N, int64_t K, const float * x, int64_t M,
                        const float * bias, const float * resid, float * y, int epilogue, int tile);
 /* Same, plus the two epilogue features the plain hook cannot reach: epilogue 1 with qcols / qscale (columns n < qcols
  * are multiplied by qscale AFTER the bias: the 1/sqrt(d_head) Q scale of the fused q/k/v projection, reference
  * clip.cpp:1363) and epilogue 5 = patch embedding (reference clip.cpp:1309-1331): GEMM row m -> output row
- * (m / Np) * T + 1 + m % Np with pos[1 + m % Np] added, no bias; y is [(M / Np) * T][N] and is uploaded first so that
- * untouched rows (the class-token rows) keep the caller's fill; pos is [T][N]. */
+ * (m / Np) * T + 1 + m % Np with pos[1 + m % Np] added, no bias; y is [(M / Np) * T][N] and is uploaded first (over the poison, not over
+ * the guard rows) so that untouched rows (the class-token rows) keep the caller's fill; pos is [T][N]. */
 int clip_amd_test_gemm_ex(int type, const void * w_raw, int64_t N, int64_t K, const float * x, int64_t M,
                           const float * bias, const float * resid, float * y, int epilogue, int tile,
                           int qcols, float qscale, int Np, int T, const float * pos);
@@ -583,7 +590,7 @@ int clip_amd_test_gemm_f32(const void * w, int64_t N, int64_t K, const float * x
  * x1_out [M][h] f32, y_out [M][N2] (fp16 widened).  h % 64 == 0.  tile1 < 0: both GEMMs on the small-M kernels (k_skinny.hip, M <= 128; fold = 0
  * is then the LayerNorm fused on the operand, fold = 1 the folded form).  fold = 2: the folded form with the operand CENTRED (the default of
  * the layer chain since round 4): fp16((x1 - mu) gamma) with mu_m = the mean of row m of `resid` (what the previous LayerNorm's consumer
- * leaves), and rstd (acc - (mean - mu) c) + b' in the consumer. */
+ * leaves), and rstd (acc - (mean - mu) c) + b' in the consumer.  Poison, guard rows and return codes as for clip_amd_test_gemm. */
 int clip_amd_test_lnfold(int type, const void * w1_raw, int64_t h, int64_t K1, const void * w2_raw, int64_t N2, const float * a, int64_t M,
                          const float * b1, const float * resid, const float * gamma, const float * beta, float eps, const float * b2,
                          int epi2, int tile1, int tile2, int fold, int qcols, float qscale, float * x1_out, float * y_out);
@@ -598,7 +605,7 @@ float clip_amd_bench_gemm(int type, int64_t N, int64_t K, int64_t M, int epilogu
  * != NULL — A = LayerNorm(x) fused into the kernel.  epilogue 0 f32, 1 f16 (+ qcols / qscale), 2 gelu, 3 quick-gelu, 4 residual
  * (stats_out, if not NULL, receives the [128 rows][128 slots][2] partial row statistics the epilogue leaves for the next LayerNorm:
  * slot j of a row = its (sum, sum of squares) over output columns 16 j .. 16 j + 15).
- * Returns -5 when the combination is not covered by this path. */
+ * Returns -5 when the combination is not covered by this path; poison, guard rows and the other return codes as for clip_amd_test_gemm. */
 int clip_amd_test_skinny(int type, const void * w_raw, int64_t N, int64_t K, const float * x, int64_t M, const float * bias,
                          const float * resid, const float * ln_w, const float * ln_b, float eps, float * y, int epilogue,
                          int qcols, float qscale, float * stats_out);

@@ -31,8 +31,16 @@ def run_gemm(L, tid, raw, N, K, X, bias=None, resid=None, epi=0, tile=0):
     y = np.full((M, N), np.nan, dtype=np.float32)
     rc = L.clip_amd_test_gemm(tid, raw.ctypes.data_as(C.c_void_p), N, K, _fp(X), M,
                               _fp(bias) if bias is not None else None, _fp(resid) if resid is not None else None, _fp(y), epi, tile)
-    assert rc == 0, "clip_amd_test_gemm rc=%d" % rc
+    assert rc == 0, "clip_amd_test_gemm rc=%d" % rc          # -6: a guard row behind the output changed
+    _assert_written(y, "clip_amd_test_gemm")
     return y
+
+
+def _assert_written(y, what):
+    """the hooks poison their output buffers (include/clip_amd.h): an element no kernel wrote comes back as NaN."""
+    bad = np.argwhere(~np.isfinite(y))
+    assert np.all(np.isfinite(y)), "%s: %d/%d elements not finite / not written, first %s, rows %d..%d cols %d..%d" % (
+        what, len(bad), y.size, bad[0].tolist(), bad[:, 0].min(), bad[:, 0].max(), bad[:, 1].min(), bad[:, 1].max())
 
 
 def _diff_report(base, y):
@@ -304,6 +312,7 @@ def run_gemm_ex(L, tid, raw, N, K, X, bias=None, epi=0, tile=0, qcols=0, qscale=
     rc = L.clip_amd_test_gemm_ex(tid, raw.ctypes.data_as(C.c_void_p), N, K, _fp(X), M, _fp(bias) if bias is not None else None, None,
                                  _fp(y), epi, tile, qcols, qscale, Np, T, _fp(pos) if pos is not None else None)
     assert rc == 0, "clip_amd_test_gemm_ex rc=%d" % rc
+    _assert_written(y, "clip_amd_test_gemm_ex")
     return y
 
 
@@ -474,6 +483,7 @@ def run_skinny(L, tid, raw, N, K, X, bias=None, resid=None, ln=None, epi=0, qcol
                                 _fp(resid) if resid is not None else None, _fp(lw) if lw is not None else None,
                                 _fp(lb) if lb is not None else None, eps, _fp(y), epi, qcols, qscale, _fp(stats) if stats is not None else None)
     assert rc == 0, "clip_amd_test_skinny rc=%d" % rc
+    _assert_written(y, "clip_amd_test_skinny")
     return y
 
 
@@ -550,6 +560,8 @@ def run_lnfold(L, tid, raw1, h, K1, raw2, N2, A, b1, resid, g, beta, b2, epi2, t
     rc = L.clip_amd_test_lnfold(tid, raw1.ctypes.data_as(C.c_void_p), h, K1, raw2.ctypes.data_as(C.c_void_p), N2, _fp(A), M, _fp(b1), _fp(resid),
                                 _fp(g), _fp(beta), eps, _fp(b2), epi2, tile1, tile2, fold, qcols, qscale, _fp(x1), _fp(y))
     assert rc == 0, "clip_amd_test_lnfold rc=%d" % rc
+    _assert_written(x1, "clip_amd_test_lnfold x1")
+    _assert_written(y, "clip_amd_test_lnfold y")
     return x1, y
 
 
