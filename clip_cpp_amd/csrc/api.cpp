@@ -820,18 +820,19 @@ int clip_amd_test_gemm_tile_ex(int64_t M, int64_t N, int64_t K, int quantised, i
     return gemm_tile_for((int)M, (int)N, Kpad, quantised != 0, shared_device != 0);
 }
 
-// Extended form: qcols / qscale (EPI_F16 Q-scale path, clip.cpp:1363) and epilogue 5 = EPI_PATCH_F32 (patch embedding:
-// row m of the GEMM lands in output row (m / Np) * T + 1 + m % Np and gets pos[1 + m % Np] added; no bias; the class-token
-// rows (b * T) are left untouched).  For epilogue 5, y is [(M / Np) * T][N] and pos is [T][N].
-int clip_amd_test_gemm_ex(int type, const void * w_raw, int64_t N, int64_t K, const float * x, int64_t M, const float * bias, const float * resid,
-                          float * y, int epilogue, int tile, int qcols, float qscale, int Np, int T, const float * pos) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); fprintf(stderr, "clip_amd_test_gemm: no HIP device\n"); return -1; }
-    if (epilogue == 5 && (Np <= 0 || T < Np + 1 || M % Np || !pos)) return -3;
+// Shared body of clip_amd_test_gemm_ex and clip_amd_test_gemm_panel: how launch_gemm comes by the fp16 panel of a block-quantised weight.
+enum { PANEL_NONE = 0, PANEL_PRE = 1, PANEL_SCRATCH = 2 };
+// PANEL_SCRATCH: w16_scratch is given and launch_gemm fills it when it picks a panel kernel (what every other hook does).  PANEL_PRE: the panel of
+// w_raw is built here by ONE launch_dequant of lead + 1 jobs (the last feeds the GEMM, the others are further copies of the weight into panels of
+// their own) and handed over as w16_pre without a scratch; the DevWeight itself comes from w_planes_raw when that is given.  PANEL_NONE: neither.
+static int test_gemm_body(int type, const void * w_raw, const void * w_planes_raw, int64_t N, int64_t K, const float * x, int64_t M, const float * bias,
+                          const float * resid, float * y, int epilogue, int tile, int qcols, float qscale, int Np, int T, const float * pos, int panel_mode,
+                          int lead) {
     // the weight goes through the production repack path (load.cpp)
-    DevWeight W;
-    void * wbase = nullptr;
-    if (!repack_for_test(type, w_raw, N, K, W, &wbase)) return -2;
+    DevWeight W, Wd;
+    void * wbase = nullptr, * wdbase = nullptr;
+    if (!repack_for_test(type, panel_mode == PANEL_PRE && w_planes_raw ? w_planes_raw : w_raw, N, K, W, &wbase)) return -2;
+    if (panel_mode == PANEL_PRE && !repack_for_test(type, w_raw, N, K, Wd, &wdbase)) { (void)hipFree(wbase); return -2; }
     const int Kpad = W.Kpad;
     // outputs: poisoned, GUARD_ROWS guard rows behind them; the caller's rows (resid, the fill of epilogue 5) go over the first out_rows rows only
     const size_t out_rows = epilogue == 5 ? (size_t)(M / Np) * T : (size_t)M, n_out = out_rows * N, n_guard = GUARD_ROWS * (size_t)N;
@@ -852,8 +853,21 @@ int clip_amd_test_gemm_ex(int type, const void * w_raw, int64_t N, int64_t K, co
     (void)hipMemset(skc.p, 0, 4096 * 4);
     poison32(skw, (size_t)16 << 20);
     p.sk_ws = (float *)skw.p; p.sk_ws_floats = (size_t)16 << 20; p.sk_cnt = (unsigned *)skc.p; p.sk_cnt_n = 4096;
-    DBuf panel((size_t)W.Npad * W.Kpad * 2);         // fp16 panel for the 8-wave large-M kernel (quantised weights)
-    p.w16_scratch = (half_t *)panel.p; p.w16_scratch_halfs = panel.p ? (size_t)W.Npad * W.Kpad : 0;
+    const size_t panel_halfs = (size_t)W.Npad * W.Kpad, n_panels = panel_mode == PANEL_PRE ? (size_t)lead + 1 : panel_mode == PANEL_SCRATCH ? 1 : 0;
+    DBuf panel(n_panels * panel_halfs * 2);          // fp16 panel for the 8-wave large-M kernel (quantised weights)
+    if (panel_mode == PANEL_SCRATCH) {
+        p.w16_scratch = (half_t *)panel.p; p.w16_scratch_halfs = panel.p ? panel_halfs : 0;
+    } else if (panel_mode == PANEL_PRE) {
+        if (!panel.p) rc = -4;
+        else {
+            poison16(panel, n_panels * panel_halfs);
+            const DevWeight * ws[4];
+            half_t * outs[4];
+            for (int i = 0; i <= lead; i++) { ws[i] = &Wd; outs[i] = (half_t *)panel.p + (size_t)i * panel_halfs; }
+            launch_dequant(ws, outs, lead + 1, s);
+            p.w16_pre = outs[lead];
+        }
+    }
     int epi = EPI_F32;
     switch (epilogue) {
     case 0: epi = EPI_F32; p.out = dout32.p; break;
@@ -881,6 +895,107 @@ int clip_amd_test_gemm_ex(int type, const void * w_raw, int64_t N, int64_t K, co
         else {
             (void)hipMemcpy(y, dout32.p, n_out * 4, hipMemcpyDeviceToHost);
             if (!guard_intact(dout32, n_out, n_guard, 4, POISON32) || (f16_out && !guard_intact(dout, n_out, n_guard, 2, POISON16))) rc = -6;
+        }
+    }
+    (void)hipFree(wbase);
+    if (wdbase) (void)hipFree(wdbase);
+    return rc;
+}
+
+// Extended form: qcols / qscale (EPI_F16 Q-scale path, clip.cpp:1363) and epilogue 5 = EPI_PATCH_F32 (patch embedding:
+// row m of the GEMM lands in output row (m / Np) * T + 1 + m % Np and gets pos[1 + m % Np] added; no bias; the class-token
+// rows (b * T) are left untouched).  For epilogue 5, y is [(M / Np) * T][N] and pos is [T][N].
+int clip_amd_test_gemm_ex(int type, const void * w_raw, int64_t N, int64_t K, const float * x, int64_t M, const float * bias, const float * resid,
+                          float * y, int epilogue, int tile, int qcols, float qscale, int Np, int T, const float * pos) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); fprintf(stderr, "clip_amd_test_gemm: no HIP device\n"); return -1; }
+    if (epilogue == 5 && (Np <= 0 || T < Np + 1 || M % Np || !pos)) return -3;
+    return test_gemm_body(type, w_raw, nullptr, N, K, x, M, bias, resid, y, epilogue, tile, qcols, qscale, Np, T, pos, PANEL_SCRATCH, 0);
+}
+
+static bool test_type_quantised(int type) { return type == GT_Q4_0 || type == GT_Q4_1 || type == GT_Q5_0 || type == GT_Q5_1 || type == GT_Q8_0; }
+
+// clip_amd_test_gemm_ex without epilogue 5, with the panel supplied by the caller of launch_gemm (panel_mode 1: GemmParams::w16_pre out of one
+// launch_dequant of lead + 1 jobs) or withheld (panel_mode 0: no w16_pre, no w16_scratch).  See include/clip_amd.h.
+int clip_amd_test_gemm_panel(int type, const void * w_raw, const void * w_planes_raw, int64_t N, int64_t K, const float * x, int64_t M, const float * bias,
+                             const float * resid, float * y, int epilogue, int tile, int qcols, float qscale, int panel_mode, int lead) {
+    if (!w_raw || !x || !y || N <= 0 || K <= 0 || M <= 0 || M > (int64_t)1 << 24 || N > (int64_t)1 << 20 || K > (int64_t)1 << 20) return -3;
+    if (epilogue < 0 || epilogue > 4 || (epilogue == 4 && !resid) || tile < 0 || qcols < 0 || qcols > N) return -3;
+    if (type != GT_F16 && !test_type_quantised(type)) return -3;
+    if (panel_mode == PANEL_PRE ? (!test_type_quantised(type) || lead < 0 || lead > 3) : (panel_mode != PANEL_NONE || lead != 0 || w_planes_raw)) return -3;
+    if (!test_device()) return -1;
+    return test_gemm_body(type, w_raw, w_planes_raw, N, K, x, M, bias, resid, y, epilogue, tile, qcols, qscale, 0, 0, nullptr, panel_mode, lead);
+}
+
+// launch_dequant as dequant_layer of forward.cpp calls it: n weights, their panels back to back in ONE buffer, ONE call.  See include/clip_amd.h.
+int clip_amd_test_dequant_panels(int n, const int * types, const void * const * w_raw, const int64_t * N, const int64_t * K, uint16_t * const * panels_out,
+                                 int * guard_ok) {
+    const int MAX_PANELS = 8;
+    const size_t GUARD = 4096;                       // halfs before the first panel and behind the last
+    if (n < 1 || n > MAX_PANELS || !types || !w_raw || !N || !K || !panels_out) return -3;
+    for (int i = 0; i < n; i++)
+        if (!w_raw[i] || !panels_out[i] || N[i] <= 0 || K[i] <= 0 || N[i] > (int64_t)1 << 20 || K[i] > (int64_t)1 << 20 ||
+            (types[i] != GT_F16 && !test_type_quantised(types[i])))
+            return -3;
+    if (!test_device()) return -1;
+    DevWeight W[MAX_PANELS];
+    void * base[MAX_PANELS] = {};
+    size_t off[MAX_PANELS + 1] = {};
+    int rc = 0;
+    for (int i = 0; i < n && rc == 0; i++) {
+        if (!repack_for_test(types[i], w_raw[i], N[i], K[i], W[i], &base[i])) rc = -2;
+        else off[i + 1] = off[i] + (size_t)W[i].Npad * W[i].Kpad;
+    }
+    if (rc == 0) {
+        const size_t total = off[n];
+        DBuf buf((GUARD + total + GUARD) * 2);
+        if (!buf.p) rc = -4;
+        else {
+            poison16(buf, GUARD + total + GUARD);
+            const DevWeight * ws[MAX_PANELS];
+            half_t * outs[MAX_PANELS];
+            for (int i = 0; i < n; i++) { ws[i] = &W[i]; outs[i] = (half_t *)buf.p + GUARD + off[i]; }
+            launch_dequant(ws, outs, n, nullptr);
+            if (!test_sync()) rc = -4;
+            else {
+                for (int i = 0; i < n; i++)
+                    (void)hipMemcpy(panels_out[i], outs[i], (off[i + 1] - off[i]) * 2, hipMemcpyDeviceToHost);
+                const bool ok = guard_intact(buf, 0, GUARD, 2, POISON16) && guard_intact(buf, GUARD + total, GUARD, 2, POISON16);
+                if (guard_ok) *guard_ok = ok ? 1 : 0;
+                if (!ok) rc = -6;
+            }
+        }
+    }
+    for (int i = 0; i < n; i++)
+        if (base[i]) (void)hipFree(base[i]);
+    return rc;
+}
+
+// ONE launch_fold_vectors (k_fold.hip) on host data.  See include/clip_amd.h.
+int clip_amd_test_fold_vectors(int type, const void * w_raw, int64_t N, int64_t K, const float * gamma, const float * beta, const float * bias,
+                               float * c_out, float * b_out) {
+    const size_t GUARD = 64;                         // floats behind c and behind b'
+    if (!w_raw || !gamma || !beta || !c_out || !b_out || N <= 0 || K <= 0 || N > (int64_t)1 << 20 || K > (int64_t)1 << 20) return -3;
+    if (type != GT_F16 && !test_type_quantised(type)) return -3;
+    if (!test_device()) return -1;
+    DevWeight W;
+    void * wbase = nullptr;
+    if (!repack_for_test(type, w_raw, N, K, W, &wbase)) return -2;
+    DBuf dg((size_t)K * 4), dbeta((size_t)K * 4), dbias((size_t)N * 4), dc(((size_t)N + GUARD) * 4), db(((size_t)N + GUARD) * 4);
+    int rc = 0;
+    if (!dg.p || !dbeta.p || !dbias.p || !dc.p || !db.p) rc = -4;
+    else {
+        upload(dg, gamma, (size_t)K * 4);
+        upload(dbeta, beta, (size_t)K * 4);
+        upload(dbias, bias, (size_t)N * 4);
+        poison32(dc, (size_t)N + GUARD);
+        poison32(db, (size_t)N + GUARD);
+        launch_fold_vectors(W, (const float *)dg.p, (const float *)dbeta.p, bias ? (const float *)dbias.p : nullptr, (float *)dc.p, (float *)db.p, nullptr);
+        if (!test_sync()) rc = -4;
+        else {
+            download(c_out, dc, (size_t)N * 4);
+            download(b_out, db, (size_t)N * 4);
+            if (!guard_intact(dc, (size_t)N, GUARD, 4, POISON32) || !guard_intact(db, (size_t)N, GUARD, 4, POISON32)) rc = -6;
         }
     }
     (void)hipFree(wbase);

@@ -568,7 +568,32 @@ int clip_amd_test_gemm(int type, const void * w_raw, int64_t N, int64_t K, const
 int clip_amd_test_gemm_ex(int type, const void * w_raw, int64_t N, int64_t K, const float * x, int64_t M,
                           const float * bias, const float * resid, float * y, int epilogue, int tile,
                           int qcols, float qscale, int Np, int T, const float * pos);
-/* The GEMM of an f32 file (k_gemm_f32.hip) in the form the layers run it.  w is f32 [N][K] (ggml type 0), x f32 [M][K]; bias [N] and resid [M][N] may be
+/* clip_amd_test_gemm_ex without epilogue 5, with the fp16 panel of a block-quantised weight supplied the way the layer chain supplies it, or withheld.
+ * panel_mode = 1 (quantised types only): the panel of w_raw is built by ONE launch_dequant call of lead + 1 jobs, lead in 0..3 — jobs 0 .. lead - 1 are
+ * further copies of the weight into panels of their own, the last job feeds the GEMM — and is passed as GemmParams::w16_pre; w16_scratch is NULL.  The
+ * DevWeight given to launch_gemm is repacked from w_planes_raw when that is not NULL: a second weight of the same type and shape with other values.
+ * By the contract of w16_pre (kernels.h) every kernel multiplies the panel, so y must be the product with w_raw whatever w_planes_raw holds.
+ * panel_mode = 0 (lead = 0, w_planes_raw = NULL): neither w16_pre nor w16_scratch; for a panel tile code and a quantised weight launch_gemm must fall
+ * back to the fused 4-wave kernel.
+ * Checked on the host before the device is looked for: pointers, N, K, M >= 1, epilogue in 0..4 (4 needs resid), tile >= 0, 0 <= qcols <= N, type f16 or
+ * block-quantised, panel_mode / lead / type as above.  Poison, guard rows and return codes as for clip_amd_test_gemm. */
+int clip_amd_test_gemm_panel(int type, const void * w_raw, const void * w_planes_raw, int64_t N, int64_t K, const float * x, int64_t M,
+                             const float * bias, const float * resid, float * y, int epilogue, int tile, int qcols, float qscale,
+                             int panel_mode, int lead);
+/* launch_dequant (k_gemm8.hip) as dequant_layer of forward.cpp calls it: n <= 8 weights (types[i], w_raw[i], N[i] x K[i]; f16 or block-quantised), each
+ * through the production repack; ONE device buffer holds the n fp16 panels [Npad_i][Kpad_i] back to back in the caller's order (Npad = N rounded up to
+ * 128, Kpad = K rounded up to 64), with 4096 guard halfs before the first and behind the last; all of it is poisoned with 0x7e00, then ONE
+ * launch_dequant(ws, outs, n) runs.  panels_out[i] receives panel i whole (Npad_i * Kpad_i raw fp16 bits).  An f16 entry is legal: launch_dequant
+ * skips it and its panel comes back all poison.  *guard_ok (may be NULL) = 1 when the guard halfs still hold the poison, else 0 and the return code
+ * is -6.  Returns 0; -1 no device; -2 repack failed; -3 bad arguments (checked before the device is looked for); -4 HIP error; -6. */
+int clip_amd_test_dequant_panels(int n, const int * types, const void * const * w_raw, const int64_t * N, const int64_t * K,
+                                 uint16_t * const * panels_out, int * guard_ok);
+/* ONE launch_fold_vectors (k_fold.hip): c_out[n] = sum_k gamma[k] W[n][k], b_out[n] = sum_k beta[k] W[n][k] + bias[n] (bias may be NULL: no bias),
+ * W [N][K] of ggml type `type` (f16 or block-quantised) as the GEMM kernels dequantise it.  c and b' are device buffers of N + 64 floats, poisoned; the
+ * 64 floats behind each are compared after the launch (-6).  Return codes as for clip_amd_test_dequant_panels. */
+int clip_amd_test_fold_vectors(int type, const void * w_raw, int64_t N, int64_t K, const float * gamma, const float * beta, const float * bias,
+                               float * c_out, float * b_out);
+/* The GEMM of an f32 file (k_gemm_f32.hip) in the form the layers run it. w is f32 [N][K] (ggml type 0), x f32 [M][K]; bias [N] and resid [M][N] may be
  * NULL (resid is required by epilogue 4); epilogue, qcols / qscale, Np / T / pos as for clip_amd_test_gemm_ex.
  * act_f32 = 1: the activations go up as f32 rows [M][Kpad] (exactly M rows, columns K .. Kpad - 1 zero), GemmParams::act_f32 is set, and epilogues 1-3
  * come back as the f32 values the kernel stores, with no fp16 step.  act_f32 = 0: x is rounded to fp16 and epilogues 1-3 store fp16 (returned widened),
