@@ -70,7 +70,7 @@ AMD_SYMBOLS = [
     "clip_amd_test_gemm", "clip_amd_test_gemm_ex", "clip_amd_test_gemm_f32", "clip_amd_test_gemm_tile", "clip_amd_test_gemm_tile_ex", "clip_amd_test_skinny", "clip_amd_test_layernorm", "clip_amd_test_attention", "clip_amd_bench_gemm",
     "clip_amd_test_attention_ex", "clip_amd_bench_attention", "clip_amd_test_attention_ragged",
     "clip_amd_test_layernorm_ex", "clip_amd_test_text_embed", "clip_amd_test_im2col", "clip_amd_test_layernorm_prep", "clip_amd_test_rows",
-    "clip_amd_test_gemm_panel", "clip_amd_test_dequant_panels", "clip_amd_test_fold_vectors",
+    "clip_amd_test_gemm_panel", "clip_amd_test_dequant_panels", "clip_amd_test_fold_vectors", "clip_amd_test_fold_producer", "clip_amd_test_fold_consumer",
     "clip_amd_index_create", "clip_amd_index_add", "clip_amd_index_add_device", "clip_amd_index_size", "clip_amd_index_dim",
     "clip_amd_index_search", "clip_amd_index_search_device", "clip_amd_index_save", "clip_amd_index_load", "clip_amd_index_free",
     "clip_amd_bench_search", "clip_amd_index_range_search", "clip_amd_index_pairs", "clip_amd_bench_range",
@@ -204,6 +204,11 @@ def lib():
     L.clip_amd_test_lnfold.restype = i32
     L.clip_amd_test_lnfold.argtypes = [i32, vp, C.c_int64, C.c_int64, vp, C.c_int64, f32p, C.c_int64, f32p, f32p, f32p, f32p, C.c_float, f32p,
                                        i32, i32, i32, i32, i32, C.c_float, f32p, f32p]
+    L.clip_amd_test_fold_producer.restype = i32
+    L.clip_amd_test_fold_producer.argtypes = [i32, vp, C.c_int64, C.c_int64, f32p, C.c_int64, f32p, f32p, f32p, f32p, i32, C.c_int64, f32p, vp, f32p, C.POINTER(i32)]
+    L.clip_amd_test_fold_consumer.restype = i32
+    L.clip_amd_test_fold_consumer.argtypes = [i32, vp, C.c_int64, C.c_int64, vp, C.c_int64, f32p, i32, i32, f32p, f32p, f32p, C.c_float, i32, i32, C.c_float,
+                                              i32, f32p, f32p]
     L.clip_amd_test_gemm_tile.restype = i32
     L.clip_amd_test_gemm_tile.argtypes = [C.c_int64, C.c_int64, C.c_int64, i32]
     L.clip_amd_test_gemm_tile_ex.restype = i32

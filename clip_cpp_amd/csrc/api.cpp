@@ -1037,6 +1037,8 @@ int clip_amd_test_lnfold(int type, const void * w1_raw, int64_t h, int64_t K1, c
     // fold == 2: the centred form (GemmParams::xg_mu / ln_mu): the offsets are the row means of the INCOMING residual rows — what the
     // previous LayerNorm's consumer leaves in the layer chain — computed here in double
     DBuf dmu((size_t)M * 4), dmu2((size_t)M * 4);
+    poison32(dstats, (size_t)(h / 16) * st_stride * 2);   // a statistics slot or a row mean that a consumer reads and no producer wrote is a NaN in y
+    poison32(dmu2, (size_t)M);
     if (fold == 2) {
         std::vector<float> mu((size_t)M);
         for (int64_t m = 0; m < M; m++) {
@@ -1122,6 +1124,160 @@ int clip_amd_test_lnfold(int type, const void * w1_raw, int64_t h, int64_t K1, c
     }
     const int rc = finish();
     (void)hipFree(w1base);
+    (void)hipFree(w2base);
+    return rc;
+}
+
+// The two halves of the LayerNorm fold on their own (gemm_common.h resid_fold_tail / ln_row_final + ln_apply, k_skinny.hip).  See include/clip_amd.h.
+static bool test_fold_tile_ok(int tile, int64_t M, int64_t N) {
+    if (tile < -1) return false;
+    if (tile <= 0) return true;
+    const int bn = tile % 1000;
+    // 258 / 260: the whole-rounds split (a second launch on a tile of launch_gemm's choosing) is not what these hooks are for
+    if (bn == 258 || bn == 260) return ((M + 255) / 256) * ((N + 255) / 256) < 256;
+    return true;
+}
+
+int clip_amd_test_fold_producer(int type, const void * w_raw, int64_t h, int64_t K1, const float * a, int64_t M, const float * b1, const float * resid,
+                                const float * gamma_next, const float * xg_mu, int tile1, int64_t ldxg, float * x1_out, uint16_t * xg_out,
+                                float * stats_out, int * slotw_out) {
+    if (!w_raw || !a || !b1 || !resid || !gamma_next || !x1_out || !xg_out || !stats_out || !slotw_out) return -3;
+    if (h <= 0 || h % 64 || h > (int64_t)1 << 20 || K1 <= 0 || K1 > (int64_t)1 << 20 || M <= 0 || M > (int64_t)1 << 20) return -3;
+    if (type != GT_F16 && !test_type_quantised(type)) return -3;
+    if (ldxg < h || ldxg % 8 || ldxg > h + 4096) return -3;
+    if (!test_fold_tile_ok(tile1, M, h) || (tile1 == -1 && M > 128)) return -3;
+    if (!test_device()) return -1;
+    DevWeight W1;
+    void * w1base = nullptr;
+    if (!repack_for_test(type, w_raw, h, K1, W1, &w1base)) return -2;
+    const int st_stride = (int)((M + 63) & ~(int64_t)63);
+    const int t1 = tile1 > 0 ? tile1 : tile1 == 0 ? gemm_tile_for((int)M, (int)h, W1.Kpad, W1.wtype != W_F16) : 0;
+    const int slotw = tile1 < 0 ? 16 : gemm_fold_slotw(t1);
+    // the buffer is sized for the narrowest slots any producer writes (16 columns), whatever slotw says; what lies behind the slots of this launch is guard
+    const size_t slots = (size_t)h / slotw, n_stats = slots * st_stride * 2, g_stats = ((size_t)h / 16 + 1) * st_stride * 2 - n_stats;
+    const size_t rows_g = (size_t)M + GUARD_ROWS;
+    DBuf da32((size_t)M * K1 * 4), da16((size_t)(M + 1) * W1.Kpad * 2), dx(rows_g * h * 4), dxg(rows_g * ldxg * 2), db1((size_t)h * 4), dg((size_t)h * 4),
+        dmu((size_t)M * 4), dstats((n_stats + g_stats) * 4), skw((size_t)64 << 20), skc(4096 * 4), panel((size_t)W1.Npad * W1.Kpad * 2);
+    int rc = 0;
+    if (!da32.p || !da16.p || !dx.p || !dxg.p || !db1.p || !dg.p || !dmu.p || !dstats.p || !skw.p || !skc.p) rc = -4;
+    hipStream_t s = nullptr;
+    if (rc == 0) {
+        upload(da32, a, (size_t)M * K1 * 4);
+        poison16(da16, (size_t)(M + 1) * W1.Kpad);
+        poison32(dx, rows_g * h);
+        upload(dx, resid, (size_t)M * h * 4);
+        poison16(dxg, rows_g * ldxg);
+        poison32(dstats, n_stats + g_stats);
+        upload(db1, b1, (size_t)h * 4);
+        upload(dg, gamma_next, (size_t)h * 4);
+        upload(dmu, xg_mu, (size_t)M * 4);
+        (void)hipMemset(skc.p, 0, 4096 * 4);
+        poison32(skw, (size_t)16 << 20);
+        launch_f32_to_f16((const float *)da32.p, (int)K1, (half_t *)da16.p, W1.Kpad, (int)M, (int)K1, W1.Kpad, s);
+        if (tile1 < 0) {
+            SkinnyParams a1;
+            a1.A16 = (const half_t *)da16.p; a1.lda = W1.Kpad; a1.M = (int)M; a1.W = W1; a1.bias = (const float *)db1.p; a1.out = dx.p; a1.ldc = (int)h;
+            a1.resid = (const float *)dx.p; a1.xg_out = (half_t *)dxg.p; a1.ldxg = (int)ldxg; a1.xg_gamma = (const float *)dg.p;
+            a1.fstats_out = (float2 *)dstats.p; a1.fstride_out = st_stride;
+            if (xg_mu) a1.xg_mu = (const float *)dmu.p;
+            if (!skinny_supported(a1, EPI_RESID_F32)) rc = -5;
+            else launch_skinny(a1, EPI_RESID_F32, s);
+        } else {
+            GemmParams p1;
+            p1.A = (const half_t *)da16.p; p1.lda = W1.Kpad; p1.M = (int)M; p1.W = W1; p1.bias = (const float *)db1.p; p1.out = dx.p; p1.ldc = (int)h;
+            p1.resid = (const float *)dx.p;
+            p1.sk_ws = (float *)skw.p; p1.sk_ws_floats = (size_t)16 << 20; p1.sk_cnt = (unsigned *)skc.p; p1.sk_cnt_n = 4096;
+            p1.w16_scratch = (half_t *)panel.p; p1.w16_scratch_halfs = panel.p ? (size_t)W1.Npad * W1.Kpad : 0;
+            p1.xg_out = (half_t *)dxg.p; p1.ldxg = (int)ldxg; p1.xg_gamma = (const float *)dg.p; p1.stats_out = (float2 *)dstats.p; p1.stats_stride = st_stride;
+            if (xg_mu) p1.xg_mu = (const float *)dmu.p;
+            launch_gemm(p1, EPI_RESID_F32, tile1, s);
+        }
+    }
+    if (rc == 0) {
+        if (!test_sync()) rc = -4;
+        else {
+            download(x1_out, dx, (size_t)M * h * 4);
+            download(xg_out, dxg, (size_t)M * ldxg * 2);
+            download(stats_out, dstats, n_stats * 4);
+            *slotw_out = slotw;
+            const bool ok = guard_intact(dx, (size_t)M * h, GUARD_ROWS * (size_t)h, 4, POISON32) &&
+                            guard_intact(dxg, (size_t)M * ldxg, GUARD_ROWS * (size_t)ldxg, 2, POISON16) && guard_intact(dstats, n_stats, g_stats, 4, POISON32);
+            if (!ok) rc = -6;
+        }
+    }
+    (void)hipFree(w1base);
+    return rc;
+}
+
+int clip_amd_test_fold_consumer(int type, const void * w_raw, int64_t N2, int64_t h, const uint16_t * xg, int64_t M, const float * stats, int slots,
+                                int slotw, const float * ln_mu, const float * c, const float * b_fold, float eps, int epi2, int qcols, float qscale,
+                                int tile2, float * y_out, float * mu_out) {
+    const size_t MU_GUARD = 64;                      // floats behind mu_out
+    if (!w_raw || !xg || !stats || !c || !b_fold || !y_out || !mu_out) return -3;
+    if (h <= 0 || h % 64 || h > (int64_t)1 << 20 || N2 <= 0 || N2 % 4 || N2 > (int64_t)1 << 20 || M <= 0 || M > (int64_t)1 << 20) return -3;
+    if (type != GT_F16 && !test_type_quantised(type)) return -3;
+    if (epi2 < 1 || epi2 > 3 || qcols < 0 || qcols > N2 || qcols % 4) return -3;
+    if (slots <= 0 || slotw <= 0 || (int64_t)slots * slotw != h || (slotw == 32 && (slots & 1))) return -3;
+    if (!test_fold_tile_ok(tile2, M, N2) || (tile2 == -1 && M > 128)) return -3;
+    if (tile2 >= 0 && (slotw == 32 ? slots >> 1 : slots) > 32) return -3;       // ln_row_final: two chunks of 16 units
+    if (!test_device()) return -1;
+    DevWeight W2;
+    void * w2base = nullptr;
+    if (!repack_for_test(type, w_raw, N2, h, W2, &w2base)) return -2;
+    const int st_stride = (int)((M + 63) & ~(int64_t)63);
+    const size_t rows_g = (size_t)M + GUARD_ROWS, n_stats = (size_t)slots * st_stride * 2;
+    DBuf dxg(rows_g * W2.Kpad * 2), dstats(n_stats * 4), dmu((size_t)M * 4), dmu2(((size_t)st_stride + MU_GUARD) * 4), dc((size_t)N2 * 4), dbf((size_t)N2 * 4),
+        dy16(rows_g * N2 * 2), dy32(rows_g * N2 * 4), skw((size_t)64 << 20), skc(4096 * 4), panel((size_t)W2.Npad * W2.Kpad * 2);
+    int rc = 0;
+    if (!dxg.p || !dstats.p || !dmu.p || !dmu2.p || !dc.p || !dbf.p || !dy16.p || !dy32.p || !skw.p || !skc.p) rc = -4;
+    hipStream_t s = nullptr;
+    const int epi = epi2 == 1 ? EPI_F16 : epi2 == 2 ? EPI_GELU_F16 : EPI_QGELU_F16;
+    if (rc == 0) {
+        (void)hipMemset(dxg.p, 0, rows_g * W2.Kpad * 2);          // rows at and past M, columns past h: zero, as the layer chain keeps them
+        if (hipMemcpy2D(dxg.p, (size_t)W2.Kpad * 2, xg, (size_t)h * 2, (size_t)h * 2, (size_t)M, hipMemcpyHostToDevice) != hipSuccess) rc = -4;
+        upload(dstats, stats, n_stats * 4);
+        upload(dmu, ln_mu, (size_t)M * 4);
+        upload(dc, c, (size_t)N2 * 4);
+        upload(dbf, b_fold, (size_t)N2 * 4);
+        poison32(dmu2, (size_t)st_stride + MU_GUARD);
+        poison16(dy16, rows_g * N2);
+        poison32(dy32, rows_g * N2);
+        (void)hipMemset(skc.p, 0, 4096 * 4);
+        poison32(skw, (size_t)16 << 20);
+    }
+    if (rc == 0) {
+        if (tile2 < 0) {
+            SkinnyParams a2;
+            a2.A16 = (const half_t *)dxg.p; a2.lda = W2.Kpad; a2.M = (int)M; a2.W = W2; a2.bias = (const float *)dbf.p; a2.out = dy16.p; a2.ldc = (int)N2;
+            a2.qcols = qcols; a2.qscale = qscale; a2.eps = eps; a2.ln_c = (const float *)dc.p; a2.fstats = (const float2 *)dstats.p; a2.fslots = slots;
+            a2.fslotw = slotw; a2.fstride = st_stride; a2.mu_out = (float *)dmu2.p;
+            if (ln_mu) a2.ln_mu = (const float *)dmu.p;
+            if (!skinny_supported(a2, epi)) rc = -5;
+            else launch_skinny(a2, epi, s);
+        } else {
+            GemmParams p2;
+            p2.A = (const half_t *)dxg.p; p2.lda = W2.Kpad; p2.M = (int)M; p2.W = W2; p2.bias = (const float *)dbf.p; p2.out = dy16.p; p2.ldc = (int)N2;
+            p2.qcols = qcols; p2.qscale = qscale;
+            p2.sk_ws = (float *)skw.p; p2.sk_ws_floats = (size_t)16 << 20; p2.sk_cnt = (unsigned *)skc.p; p2.sk_cnt_n = 4096;
+            p2.w16_scratch = (half_t *)panel.p; p2.w16_scratch_halfs = panel.p ? (size_t)W2.Npad * W2.Kpad : 0;
+            p2.ln_c = (const float *)dc.p; p2.ln_stats = (const float2 *)dstats.p; p2.ln_slotw = slotw; p2.ln_slots = slots; p2.ln_stride = st_stride;
+            p2.ln_eps = eps; p2.mu_out = (float *)dmu2.p;
+            if (ln_mu) p2.ln_mu = (const float *)dmu.p;
+            launch_gemm(p2, epi, tile2, s);
+        }
+    }
+    if (rc == 0) {
+        launch_f16_to_f32((const half_t *)dy16.p, (int)N2, (float *)dy32.p, (int)N2, (int)M, (int)N2, s);
+        if (!test_sync()) rc = -4;
+        else {
+            download(y_out, dy32, (size_t)M * N2 * 4);
+            download(mu_out, dmu2, (size_t)st_stride * 4);
+            const bool ok = guard_intact(dy16, (size_t)M * N2, GUARD_ROWS * (size_t)N2, 2, POISON16) &&
+                            guard_intact(dy32, (size_t)M * N2, GUARD_ROWS * (size_t)N2, 4, POISON32) &&
+                            guard_intact(dmu2, (size_t)st_stride, MU_GUARD, 4, POISON32);
+            if (!ok) rc = -6;
+        }
+    }
     (void)hipFree(w2base);
     return rc;
 }

@@ -615,10 +615,34 @@ int clip_amd_test_gemm_f32(const void * w, int64_t N, int64_t K, const float * x
  * x1_out [M][h] f32, y_out [M][N2] (fp16 widened).  h % 64 == 0.  tile1 < 0: both GEMMs on the small-M kernels (k_skinny.hip, M <= 128; fold = 0
  * is then the LayerNorm fused on the operand, fold = 1 the folded form).  fold = 2: the folded form with the operand CENTRED (the default of
  * the layer chain since round 4): fp16((x1 - mu) gamma) with mu_m = the mean of row m of `resid` (what the previous LayerNorm's consumer
- * leaves), and rstd (acc - (mean - mu) c) + b' in the consumer.  Poison, guard rows and return codes as for clip_amd_test_gemm. */
+ * leaves), and rstd (acc - (mean - mu) c) + b' in the consumer.  Poison, guard rows and return codes as for clip_amd_test_gemm; the statistics
+ * buffer between the two launches and the consumer's mu_out are poisoned too: a slot that a consumer reads and no producer wrote is a NaN in y. */
 int clip_amd_test_lnfold(int type, const void * w1_raw, int64_t h, int64_t K1, const void * w2_raw, int64_t N2, const float * a, int64_t M,
                          const float * b1, const float * resid, const float * gamma, const float * beta, float eps, const float * b2,
                          int epi2, int tile1, int tile2, int fold, int qcols, float qscale, float * x1_out, float * y_out);
+/* The two halves of the fold on their own, so that what passes between them — the operand, the partial statistics, the row means — is seen, not only y.
+ * Producer: ONE EPI_RESID_F32 launch with xg_out set.  x1 = resid + a . W^T + b1 ([M][h], W [h][K1] of ggml type `type`, f16 or block-quantised),
+ * xg = fp16((x1 - xg_mu_m) gamma_next) as raw bits [M][ldxg] (xg_mu NULL: the uncentred form; ldxg >= h, a multiple of 8: the columns past h are
+ * never written and come back as the poison 0x7e00), and the WHOLE statistics buffer [h / slotw][st_stride][2] f32, st_stride = M rounded up to 64
+ * (rows M .. st_stride - 1 must still hold the poison 0x7fc00000), with *slotw_out = the slot width the launch used: gemm_fold_slotw(tile), 16 for the
+ * small-M kernel.  stats_out must hold (h / 16) * st_stride * 2 floats.  tile1: as `tile` of clip_amd_test_gemm (launch_gemm with stats_out /
+ * stats_stride), -1 = launch_skinny (fstats_out / fstride_out; M <= 128).  Guard rows: two behind x1 and xg; the device
+ * statistics buffer holds h / 16 + 1 slots, and all of it behind the h / slotw slots of this launch is guard.
+ * Consumer: ONE launch with ln_c set on an operand and statistics of the caller's making.  y = epi2(q (rstd_m (xg . W^T - (mean_m - ln_mu_m) c) + b_fold))
+ * ([M][N2] fp16, widened; W [N2][h]; epi2, qcols / qscale as for clip_amd_test_lnfold; ln_mu may be NULL), (mean_m, rstd_m) merged by the kernel from
+ * stats [slots][st_stride][2] (slots * slotw == h; rows >= M are uploaded as given and must not matter).  The operand's rows at and past M are zero.
+ * mu_out [st_stride] is poisoned before the launch and comes back whole: rows < M hold the kernel's row means, the rest the poison; 64 guard floats
+ * lie behind it.  tile2: as tile1; a panel scratch is provided, so the panel tile codes reach their kernels.
+ * Checked on the host before the device is looked for (-3, nothing written): pointers, h % 64 == 0, sizes >= 1, type f16 or block-quantised, tile >= -1,
+ * M <= 128 with tile -1, the whole-rounds codes 258 / 260 only where they do not split; producer: ldxg; consumer: N2 % 4 == 0, epi2 in 1..3,
+ * 0 <= qcols <= N2 and qcols % 4 == 0, slots * slotw == h, an even slot count with slotw == 32, at most 32 merge units (slots, or pairs of 32-column
+ * slots) unless tile2 == -1.  Other return codes as for clip_amd_test_gemm (-5: skinny_supported refuses). */
+int clip_amd_test_fold_producer(int type, const void * w_raw, int64_t h, int64_t K1, const float * a, int64_t M, const float * b1, const float * resid,
+                                const float * gamma_next, const float * xg_mu, int tile1, int64_t ldxg, float * x1_out, uint16_t * xg_out,
+                                float * stats_out, int * slotw_out);
+int clip_amd_test_fold_consumer(int type, const void * w_raw, int64_t N2, int64_t h, const uint16_t * xg, int64_t M, const float * stats, int slots,
+                                int slotw, const float * ln_mu, const float * c, const float * b_fold, float eps, int epi2, int qcols, float qscale,
+                                int tile2, float * y_out, float * mu_out);
 /* The tile the heuristic of launch_gemm picks for an [M][K] x [N][K]^T problem (pure host arithmetic, no device needed):
  * BM * 1000 + BN; BM = 65: the mid-M ring kernel on 64-row tiles (k_gemm_ring.hip), BN = 256 / 258-260: the large-M panel kernels. */
 int clip_amd_test_gemm_tile(int64_t M, int64_t N, int64_t K, int quantised);
