@@ -92,6 +92,8 @@ AMD_SYMBOLS = [
     "clip_amd_index_components", "clip_amd_index_components_device", "clip_amd_bench_components",
     "clip_amd_index_modes", "clip_amd_index_modes_device", "clip_amd_bench_modes",
     "clip_amd_index_spread", "clip_amd_index_spread_device", "clip_amd_bench_spread",
+    "clip_amd_index_linkage", "clip_amd_index_linkage_device", "clip_amd_bench_linkage", "clip_amd_bench_linkage_rounds",
+    "clip_amd_test_index_linkage_rounds",
 ]
 
 _lib = None
@@ -294,6 +296,16 @@ def lib():
     L.clip_amd_index_modes_device.argtypes = [vp, C.c_float, C.c_float, vp, vp, vp, vp, vp]
     L.clip_amd_bench_modes.restype = C.c_float
     L.clip_amd_bench_modes.argtypes = [i32, i64, i32, C.c_float, C.c_float, i32, i32]
+    L.clip_amd_index_linkage.restype = i64
+    L.clip_amd_index_linkage.argtypes = [vp, C.c_float, u64p, i64p, i64p, f32p]
+    L.clip_amd_index_linkage_device.restype = C.c_bool
+    L.clip_amd_index_linkage_device.argtypes = [vp, C.c_float, vp, vp, vp, vp, vp]
+    L.clip_amd_bench_linkage.restype = C.c_float
+    L.clip_amd_bench_linkage.argtypes = [i32, i64, i32, i32, i32]
+    L.clip_amd_bench_linkage_rounds.restype = i32
+    L.clip_amd_bench_linkage_rounds.argtypes = []
+    L.clip_amd_test_index_linkage_rounds.restype = i32
+    L.clip_amd_test_index_linkage_rounds.argtypes = [vp]
     L.clip_amd_index_spread.restype = i64
     L.clip_amd_index_spread.argtypes = [vp, i64, C.c_float, i64p, i64, u64p, i64p, f32p, i64p, f32p, f32p]
     L.clip_amd_index_spread_device.restype = C.c_bool
@@ -820,6 +832,11 @@ class Index:
     within a factor 2 of the best possible cover, and reach[t] is the coverage radius of the t rows before it.  With `allow` it is the
     diverse-subset step after a search: ids of the 1000 nearest rows in, 20 of them spread apart out (spread(20, allow=ids)).
 
+    linkage() answers for every radius at once: the minimum spanning tree of the rows under the index's distances, the single-linkage
+    dendrogram.  cut_linkage(..., radius=R) on its edges gives the labels of components(R), cut_linkage(..., n_groups=N) exactly N
+    groups, and the sorted edge distances are the table of radius against number of groups.  The edge order (d, lo, hi) is total, so the
+    tree is unique, exact and bit-reproducible.
+
     remove(ids) marks rows as removed: no search, range_search or pairs returns them again, ids are not renumbered and len() keeps
     counting every id ever given (`live` = len minus the removed rows); compact() drops them from device memory and renumbers the
     survivors.  search and range_search take `allow`, a bool mask of length len(index) or an array of ids: only those rows (and of those
@@ -1300,6 +1317,46 @@ class Index:
             raise RuntimeError("clip_amd_index_modes_device failed (see stderr)")
 
     @staticmethod
+    def _linkage_link(link):
+        """link as the f32 the library compares with; None: +inf, the whole tree.  ValueError for a NaN, before any call."""
+        link = float("inf") if link is None else float(np.float32(link))
+        if link != link:
+            raise ValueError("link must not be NaN")
+        return link
+
+    def linkage(self, link=None, allow=None):
+        """The single-linkage tree: (lo int64 [e], hi int64 [e], d f32 [e]), the edges of the minimum spanning forest of the graph
+        "distance <= link" (default: no limit, the whole tree) over the eligible rows, lo < hi, sorted by (d, lo, hi): that is the order
+        of the edges, it is total, and an edge is in the forest exactly when strictly smaller edges do not connect its ends.  d are the
+        distances and bits of `pairs`.  e = eligible rows - components at link.  cut_linkage turns the edges into labels for any radius
+        or any number of groups.  `allow` (bool mask [len] or ids): only those rows are eligible; the result over them is that of an
+        index that only ever held them.  ValueError for a NaN or a malformed allow."""
+        link = self._linkage_link(link)
+        cap = max(len(self) - 1, 1)
+        words, wp = self._allow(allow)
+        lo = np.empty(cap, dtype=np.int64)
+        hi = np.empty(cap, dtype=np.int64)
+        dist = np.empty(cap, dtype=np.float32)
+        i64 = C.POINTER(C.c_int64)
+        m = lib().clip_amd_index_linkage(self._live(), link, wp, lo.ctypes.data_as(i64), hi.ctypes.data_as(i64), _fp(dist))
+        if m < 0:
+            raise RuntimeError("clip_amd_index_linkage failed (see stderr)")
+        return lo[:m].copy(), hi[:m].copy(), dist[:m].copy()
+
+    def linkage_rounds(self):
+        """The rounds that did work in the last `linkage` call of this index: sweeps over the pairs that ran (for measurements)"""
+        return int(lib().clip_amd_test_index_linkage_rounds(self._live()))
+
+    def linkage_device(self, d_lo, d_hi, d_distances, d_count, link=None, d_allow=None):
+        """linkage on device pointers (ints): lo [len - 1] int64, hi [len - 1] int64, distances [len - 1] f32 and count [1] int64, the
+        same edges as the host form in an order that is not specified but the same run to run; d_allow: uint64 words on the device
+        (0 / None: every row); asynchronous on the context's stream."""
+        link = self._linkage_link(link)
+        if not lib().clip_amd_index_linkage_device(self._live(), link, C.c_void_p(d_allow or None), C.c_void_p(d_lo or None),
+                                                   C.c_void_p(d_hi or None), C.c_void_p(d_distances or None), C.c_void_p(d_count or None)):
+            raise RuntimeError("clip_amd_index_linkage_device failed (see stderr)")
+
+    @staticmethod
     def _spread_args(n, radius, seeds):
         """(n, stop radius as the f32 the library compares with, seeds int64 [s]); radius None: never stop.  ValueError for a NaN and for
         n < max(1, len(seeds)), before any call."""
@@ -1516,6 +1573,63 @@ def bench_range(dtype, n, dim, n_queries, radius, iters=10):
     return float(lib().clip_amd_bench_range(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), float(radius), int(iters)))
 
 
+def cut_linkage(size, lo, hi, d, radius=None, n_groups=None, eligible=None):
+    """Labels from the edges of Index.linkage, with the conventions of Index.components: labels int64 [size], the lowest id of the row's
+    group, the row itself for a singleton, -1 for a row outside `eligible` (bool [size]; None: every row).  radius: the edges with
+    d <= radius (compared in f32) are kept, which gives exactly the labels of components(radius) when the edges reach that far (link >=
+    radius).  n_groups: the longest edges in the order (d, lo, hi) are dropped until exactly n_groups groups are left, singletons
+    included.  Neither: every edge is kept.  Host code, a union-find.  ValueError for both at once, a NaN radius, an edge that touches a
+    row outside `eligible`, or an n_groups that the edges cannot give (more than the eligible rows, fewer than the trees of the forest)."""
+    size = int(size)
+    lo = np.ascontiguousarray(lo, dtype=np.int64).reshape(-1)
+    hi = np.ascontiguousarray(hi, dtype=np.int64).reshape(-1)
+    d = np.ascontiguousarray(d, dtype=np.float32).reshape(-1)
+    if not (lo.size == hi.size == d.size):
+        raise ValueError("lo, hi and d must have one length")
+    if radius is not None and n_groups is not None:
+        raise ValueError("radius and n_groups exclude each other")
+    if eligible is None:
+        eligible = np.ones(size, dtype=np.bool_)
+    else:
+        eligible = np.ascontiguousarray(eligible, dtype=np.bool_).reshape(-1)
+        if eligible.size != size:
+            raise ValueError("eligible must have one entry per row")
+    if lo.size and (lo.min() < 0 or hi.max() >= size or (lo >= hi).any() or not (eligible[lo].all() and eligible[hi].all())):
+        raise ValueError("edges must join two eligible rows lo < hi of the index")
+    order = np.lexsort((hi, lo, d))
+    if radius is not None:
+        r = np.float32(radius)
+        if r != r:
+            raise ValueError("radius must not be NaN")
+        order = order[d[order] <= r]
+    if n_groups is not None:
+        m = int(eligible.sum())
+        keep = m - int(n_groups)
+        if int(n_groups) < 1 or keep < 0 or keep > order.size:
+            raise ValueError("n_groups = %d with %d eligible rows in %d trees" % (int(n_groups), m, m - order.size))
+        order = order[:keep]
+    parent = list(range(size))
+    for a, b in zip(lo[order].tolist(), hi[order].tolist()):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        while parent[b] != b:
+            parent[b] = parent[parent[b]]
+            b = parent[b]
+        if a < b:
+            parent[b] = a
+        elif b < a:
+            parent[a] = b
+    labels = np.asarray(parent, dtype=np.int64)
+    for _ in range(64):                                    # a root is the lowest id of its group: pointer jumping ends at it
+        up = labels[labels]
+        if (up == labels).all():
+            break
+        labels = up
+    labels[~eligible] = -1
+    return labels
+
+
 def bench_components(dtype, n, dim, radius, iters=3):
     """Microseconds per clip_amd_index_components (host form) over the seeded rows of bench_range (clip_amd_bench_components); < 0 on error."""
     return float(lib().clip_amd_bench_components(Index.DTYPES[dtype], int(n), int(dim), float(radius), int(iters)))
@@ -1526,6 +1640,13 @@ def bench_modes(dtype, n, dim, radius, link=None, copies=0, iters=3):
     many noisy copies (clip_amd_bench_modes); < 0 on error."""
     return float(lib().clip_amd_bench_modes(Index.DTYPES[dtype], int(n), int(dim), float(radius), float(radius if link is None else link), int(copies),
                                             int(iters)))
+
+
+def bench_linkage(dtype, n, dim, copies=0, iters=3):
+    """(microseconds per clip_amd_index_linkage, host form, the whole tree; rounds that did work) over the data of bench_modes
+    (clip_amd_bench_linkage); a time < 0 on error."""
+    us = float(lib().clip_amd_bench_linkage(Index.DTYPES[dtype], int(n), int(dim), int(copies), int(iters)))
+    return us, int(lib().clip_amd_bench_linkage_rounds())
 
 
 def bench_spread(dtype, n, dim, n_max, copies=0, iters=3):

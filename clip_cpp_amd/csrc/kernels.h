@@ -423,6 +423,18 @@ bool launch_modes(const void * rows, const float * rinv, int64_t n, int Dpad, in
                   uint32_t * count, unsigned long long * key, int * parent, int64_t * labels, int64_t * parent_id, float * parent_distance,
                   int * density, unsigned long long * modes, hipStream_t stream);
 
+// The single-linkage tree over the same pairs (k_linkage.hip): the minimum spanning forest of the graph "distance <= link" (link may be
+// +inf) under the edge order (d, lo, hi), lo < hi, by Boruvka rounds.  Workspaces: parent [2 n] i32, key [n] u64, work
+// [linkage_work_bytes(n)] (all initialised here).  lo / hi [n - 1] i64 and distances [n - 1] f32 receive the edges in ascending order of
+// the row that was hooked with the edge, *count (i64) their number.  Queues linkage_rounds(n) = ceil(log2 n) rounds; linkage_stat(work, n)
+// [2 rounds + 2] u32: {components hooked, eligible roots left} ahead of every round, a round having run when both allowed it (> 0, > 1).
+// Everything on the device, n < 2^31.
+int linkage_rounds(int64_t n);
+size_t linkage_work_bytes(int64_t n);
+const uint32_t * linkage_stat(const void * work, int64_t n);
+bool launch_linkage(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, float link, const uint32_t * mask, int * parent,
+                    unsigned long long * key, void * work, int64_t * lo, int64_t * hi, float * distances, int64_t * count, hipStream_t stream);
+
 // Farthest-first selection (k_spread.hip).  Workspaces: gap [n] f32, opos [n] i32, slot [n_slots] u64 (slot t: the key of the centre at
 // position t, 0 = empty).  init: zeroes the slots, sets gap / opos from the mask and writes the seeds' keys (seeds: device ids), or, with
 // n_seeds == 0, the lowest eligible id's into slot 0.  sweep: one pass over the gallery against the centres of slots first ... first +

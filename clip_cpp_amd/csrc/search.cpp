@@ -4,7 +4,7 @@
 // searches with query sets (the set fold of k_sets.hip in the finish's place), distinct searches (the pools of a search, then the near
 // bitmap and the walk of k_distinct.hip), compound queries (the placement and the scan of k_compound.hip in front of the same merge tree),
 // appending one index to another, the count -> lims -> scatter -> sort -> finish sequence of
-// range search and pairs (k_join.hip), connected components (the link -> flatten -> finish sequence of k_components.hip), density modes (k_modes.hip), farthest-first selection (k_spread.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
+// range search and pairs (k_join.hip), connected components (the link -> flatten -> finish sequence of k_components.hip), density modes (k_modes.hip), the single-linkage tree (k_linkage.hip), farthest-first selection (k_spread.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
 // Replaces the usearch index of the reference's examples/image-search (build.cpp / search.cpp) with an exact search on the GPU.
 // Single owners: search_device_impl (the passes of a search: one ScanArgs per scan launch, whatever the selection), search_blocks and
 // query_block (the blocked host forms of stored-row queries), upload_allow / upload_groups / stage_inputs (a call's inputs on the device),
@@ -93,6 +93,10 @@ struct clip_amd_index {
     // density modes (the forest goes through cparent, the keys through cnear)
     Buf mcount;                    // [n] near rows of every row (u32)
     Buf mouts;                     // host form: mode count (u64), labels + parents (int64), parent distances, densities
+    // single-linkage tree (the forest goes through cparent, the keys through cnear)
+    Buf lwork;                     // labels, per-root edges, round statistics and block counts (linkage_work_bytes)
+    Buf louts;                     // host form: count (int64), lo + hi (int64), distances
+    int linkage_rounds = 0;        // clip_amd_test_index_linkage_rounds: the rounds that ran in the last host-form call
     // farthest-first selection
     Buf sgap;                      // [n] distance to the nearest centre so far (f32)
     Buf sopos;                     // [n] position of that centre (i32)
@@ -992,6 +996,74 @@ int64_t modes_host(clip_amd_index * ix, float radius, float link, const uint64_t
     if (pdist) (void)hipMemcpyAsync(pdist, d_pdist, n * 4, hipMemcpyDeviceToHost, st);
     if (density) (void)hipMemcpyAsync(density, d_density, n * 4, hipMemcpyDeviceToHost, st);
     return stream_done(ix, fn) ? (int64_t)modes : -1;
+}
+
+// The single-linkage tree on the device: the edges and their number.  Queues the launches and returns.
+bool linkage_impl(clip_amd_index * ix, float link, const uint32_t * d_allow, int64_t * d_lo, int64_t * d_hi, float * d_dist, int64_t * d_count,
+                  const char * fn) {
+    const uint32_t * mask = nullptr;
+    if (ix->n > 1) {
+        if (!effective_mask(ix, d_allow, mask)) return false;
+        if (!ensure(ix, ix->cparent, (size_t)ix->n * 2 * sizeof(int)) || !ensure(ix, ix->cnear, (size_t)ix->n * 8) ||
+            !ensure(ix, ix->lwork, linkage_work_bytes(ix->n)))
+            return false;
+    }
+    if (!launch_linkage(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, link, mask, (int *)ix->cparent.p,
+                        (unsigned long long *)ix->cnear.p, ix->lwork.p, d_lo, d_hi, d_dist, d_count, stream_of(ix))) {
+        fprintf(stderr, "%s: launch failed\n", fn);
+        return false;
+    }
+    return true;
+}
+
+bool check_linkage_args(const clip_amd_index * ix, float link, const void * lo, const void * hi, const void * dist, const char * fn) {
+    if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+    if (!lo || !hi || !dist) { fprintf(stderr, "%s: NULL result pointer\n", fn); return false; }
+    if (std::isnan(link)) { fprintf(stderr, "%s: link is NaN\n", fn); return false; }
+    return true;
+}
+
+// The host form: the edges in their workspace, copied out and sorted by (d, lo, hi).  Returns their number or -1.
+int64_t linkage_host(clip_amd_index * ix, float link, const uint64_t * allow, int64_t * lo, int64_t * hi, float * dist, const char * fn) {
+    ix->linkage_rounds = 0;
+    if (ix->n <= 1) return 0;
+    hipStream_t st = stream_of(ix);
+    const size_t cap = (size_t)ix->n - 1;
+    const uint32_t * d_allow = nullptr;
+    if (!upload_allow(ix, allow, d_allow) || !ensure(ix, ix->louts, 8 + cap * 20)) return -1;
+    int64_t * d_count = (int64_t *)ix->louts.p;
+    int64_t * d_lo = d_count + 1;
+    int64_t * d_hi = d_lo + cap;
+    float * d_dist = (float *)(d_hi + cap);
+    if (!linkage_impl(ix, link, d_allow, d_lo, d_hi, d_dist, d_count, fn)) return -1;
+    int64_t m = 0;
+    std::vector<uint32_t> stat((size_t)2 * linkage_rounds(ix->n));
+    (void)hipMemcpyAsync(&m, d_count, 8, hipMemcpyDeviceToHost, st);
+    (void)hipMemcpyAsync(stat.data(), linkage_stat(ix->lwork.p, ix->n), stat.size() * 4, hipMemcpyDeviceToHost, st);
+    if (!stream_done(ix, fn)) return -1;
+    if (m < 0 || (size_t)m > cap) { fprintf(stderr, "%s: %lld edges for %lld rows\n", fn, (long long)m, (long long)ix->n); return -1; }
+    for (size_t r = 0; 2 * r < stat.size(); r++) ix->linkage_rounds += stat[2 * r] > 0 && stat[2 * r + 1] > 1;
+    std::vector<int64_t> h_lo((size_t)m), h_hi((size_t)m);     // the caller's arrays stay untouched when the stream fails
+    std::vector<float> h_dist((size_t)m);
+    if (m > 0) {
+        (void)hipMemcpyAsync(h_lo.data(), d_lo, (size_t)m * 8, hipMemcpyDeviceToHost, st);
+        (void)hipMemcpyAsync(h_hi.data(), d_hi, (size_t)m * 8, hipMemcpyDeviceToHost, st);
+        (void)hipMemcpyAsync(h_dist.data(), d_dist, (size_t)m * 4, hipMemcpyDeviceToHost, st);
+        if (!stream_done(ix, fn)) return -1;
+    }
+    std::vector<int64_t> order((size_t)m);
+    for (int64_t e = 0; e < m; e++) order[(size_t)e] = e;
+    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+        if (h_dist[(size_t)a] != h_dist[(size_t)b]) return h_dist[(size_t)a] < h_dist[(size_t)b];
+        if (h_lo[(size_t)a] != h_lo[(size_t)b]) return h_lo[(size_t)a] < h_lo[(size_t)b];
+        return h_hi[(size_t)a] < h_hi[(size_t)b];
+    });
+    for (int64_t e = 0; e < m; e++) {
+        lo[e] = h_lo[(size_t)order[(size_t)e]];
+        hi[e] = h_hi[(size_t)order[(size_t)e]];
+        dist[e] = h_dist[(size_t)order[(size_t)e]];
+    }
+    return m;
 }
 
 // reach of a key slot of k_spread.hip on the host (nearest_key.h's ordered_value)
@@ -1979,6 +2051,24 @@ bool clip_amd_index_modes_device(struct clip_amd_index * ix, float radius, float
     });
 }
 
+int64_t clip_amd_index_linkage(struct clip_amd_index * ix, float link, const uint64_t * allow, int64_t * lo, int64_t * hi, float * distances) {
+    return guarded(__func__, (int64_t)-1, [&](const char * fn) -> int64_t {
+        if (!check_linkage_args(ix, link, lo, hi, distances, fn)) return -1;
+        (void)hipSetDevice(ix->device);
+        return linkage_host(ix, link, allow, lo, hi, distances, fn);
+    });
+}
+
+bool clip_amd_index_linkage_device(struct clip_amd_index * ix, float link, const uint64_t * d_allow, int64_t * d_lo, int64_t * d_hi,
+                                   float * d_distances, int64_t * d_count) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_linkage_args(ix, link, d_lo, d_hi, d_distances, fn)) return false;
+        if (!d_count) { fprintf(stderr, "%s: d_count is NULL\n", fn); return false; }
+        (void)hipSetDevice(ix->device);
+        return linkage_impl(ix, link, (const uint32_t *)d_allow, d_lo, d_hi, d_distances, d_count, fn);
+    });
+}
+
 int64_t clip_amd_index_spread(struct clip_amd_index * ix, int64_t n_max, float stop_radius, const int64_t * seeds, int64_t n_seeds,
                               const uint64_t * allow, int64_t * centres, float * reach, int64_t * owner, float * owner_distance,
                               float * cover_radius) {
@@ -2197,6 +2287,27 @@ float clip_amd_bench_modes(int dtype, int64_t n, int dim, float radius, float li
         });
     });
 }
+
+static int bench_linkage_rounds = 0;
+
+float clip_amd_bench_linkage(int dtype, int64_t n, int dim, int copies, int iters) {
+    return guarded(__func__, -4.f, [&](const char * fn) {
+        return bench_on_gallery(dtype, n, dim, 0, iters, copies >= 0, copies > 0 ? copies : PLANT_JOIN, [&](clip_amd_index * ix, float *) {
+            const size_t cap = (size_t)std::max<int64_t>(n - 1, 1);
+            std::vector<int64_t> lo(cap), hi(cap);
+            std::vector<float> dist(cap);
+            auto call = [&]() { return linkage_host(ix, INFINITY, nullptr, lo.data(), hi.data(), dist.data(), fn) >= 0; };
+            if (hipDeviceSynchronize() != hipSuccess || !call()) return -4.f;
+            const float us = time_wall(iters, call);
+            bench_linkage_rounds = ix->linkage_rounds;
+            return us;
+        });
+    });
+}
+
+int clip_amd_bench_linkage_rounds(void) { return bench_linkage_rounds; }
+
+int clip_amd_test_index_linkage_rounds(struct clip_amd_index * ix) { return ix ? ix->linkage_rounds : -1; }
 
 float clip_amd_bench_spread(int dtype, int64_t n, int dim, int64_t n_max, int copies, int iters) {
     return guarded(__func__, -4.f, [&](const char * fn) {

@@ -9,6 +9,8 @@ build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.In
     python -m clip_cpp_amd.image_search dedup  [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R] [--prune]
     python -m clip_cpp_amd.image_search albums [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R] [--link T] [--min N] [-n COUNT]
     python -m clip_cpp_amd.image_search spread [-m MODEL] [-v N] [--db DIR] -n N [-d R] [--in PREFIX]... [--from INDEXED/IMAGE/PATH]...
+    python -m clip_cpp_amd.image_search groups [-m MODEL] [-v N] [--db DIR] -n N [--in PREFIX]... [--min M]
+    python -m clip_cpp_amd.image_search levels [-m MODEL] [-v N] [--db DIR] [--in PREFIX]... [-n ROWS]
     python -m clip_cpp_amd.image_search neighbors [-m MODEL] [-v N] [--db DIR] [-n N]
     python -m clip_cpp_amd.image_search label  [-m MODEL] [-v N] [-t N] [--db DIR] [-n N] LABEL [LABEL ...]
     python -m clip_cpp_amd.image_search merge  [-m MODEL] [-v N] --db DIR --from DIR2 [--from DIR3 ...] [-d R]
@@ -42,6 +44,16 @@ in order, "%f %s (+K)": the distance at which the image was picked (inf for the 
 of the picks before it), its path and the number of other images nearer to it than to any other pick; then
 "main: %d images, every other image within %f of one of them".  --in PREFIX restricts both the picks and what they cover.  To spread the
 results of a search, use the library: Index.search, then Index.spread(n, allow=ids).
+`groups -n N` and `levels` need no distance at all: both read the single-linkage tree of the database (Index.linkage, one call: the minimum
+spanning tree of the images under the index's distances; nothing is encoded, nothing on disk changes).  `groups -n N` splits the database
+into exactly N groups, single images included: the tree without its N - 1 longest links.  It prints "groups:" at verbosity > 0, then the
+groups of at least --min M images (default 2) in the format of `dedup`, largest first, equal sizes in order of the lowest id, and
+"main: %d groups, %d of them with at least %d images, %d images in those; longest link kept %f, cut at %f": `dedup -d R` finds the same
+groups for every R from the first distance up to, not including, the second.  `levels` answers "which -d do I give `dedup`?": the table of
+distance against groups from the sorted links of the tree.  It prints "levels:" and "distance groups images largest" at verbosity > 0, then
+-n ROWS rows (default 20) evenly spaced over the merges, each moved to the end of its run of equal distances, "  %f %d %d %d": a distance,
+the groups of two or more images `dedup` finds at it, the images in them and the size of the largest group; the last row is the distance
+at which everything is one group; then "main: %d images, %d levels".  --in PREFIX restricts both commands to the matching images.
 `search --like PATH` asks for "more like this one": the query is the indexed image whose line in images.paths equals PATH as written
 (Index.search_ids: its stored row, nothing is decoded or encoded, so a text-only or vision-less model is enough); the image itself is not
 listed.  It composes with -n and --in, not with a positional query or -d.
@@ -74,7 +86,7 @@ grid (Clip.encode_image_files(grid=G)), so a small object that hardly moves the 
 images.paths keeps one line per image; DIR/images.regions holds "grid G" and then one line "image x y w h" per index row.  `search` on
 such a database ranks images by their best row (Index.search_grouped with group = image): each image is printed once, with its best row's
 distance and, when that row is a tile, " [x,y,w,h]" behind the path; a query image is encoded whole; --in selects the rows of the matching
-images.  update, merge, dedup, albums, spread, neighbors, label and search --like / -d do not support a database built with --grid yet and say so.
+images.  update, merge, dedup, albums, spread, groups, levels, neighbors, label and search --like / -d do not support a database built with --grid yet and say so.
 
 `match` asks a gridded database which other images contain what an image contains: both sides are images made of 1 + G * G rows, and two
 images match through their best pair of regions, one from each (query sets: Index.search_ids_sets / Index.search_sets with group = image).
@@ -103,6 +115,7 @@ BATCH = 64          # images decoded and encoded per call
 MAX_K = 1024
 DEDUP_RADIUS = 0.05
 MAX_TERMS = 8       # terms of a compound search: the main query, every --and and every --not
+LEVEL_ROWS = 20     # rows of the `levels` table
 
 
 def is_image_file_extension(path):
@@ -125,10 +138,12 @@ def _err(msg):
     print(msg, file=sys.stderr, flush=True)
 
 
-def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False, merge=False, match=False, albums=False, spread=False):
+def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False, merge=False, match=False, albums=False, spread=False,
+           groups=False, levels=False):
     """Reference-style option parsing (examples/image-search/{build,search}.cpp my_app_params_parse); `dedup`, `albums`, `spread`, `neighbors`
     and `merge` take no positional arguments; `spread` needs -n; `update` takes build's directories, but neither a default model nor --dtype (both come from the database);
-    `label` takes the labels; `merge` needs --from at least once; `match` takes at most one image path."""
+    `label` takes the labels; `merge` needs --from at least once; `match` takes at most one image path; `groups` and `levels` take no
+    positional arguments either, `groups` needs -n."""
     p = dict(threads=4, verbose=1, db=".", dtype="f16", results=1 if label else 5, max_distance=DEDUP_RADIUS if dedup or albums else None,
              model="../models/ggml-model-f16.bin" if build else "", rest=[], like=None)
     p["in"] = []
@@ -138,19 +153,28 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         p.update(results=None)                             # -n has no default: it is the question
     if albums:
         p.update(results=None, link=None, min_size=2)      # every album; link = the radius
-    search = not (build or dedup or update or neighbors or label or merge or match or albums or spread)
+    if groups:
+        p.update(results=None, min_size=2)                 # -n has no default: it is the question
+    if levels:
+        p.update(results=LEVEL_ROWS)
+    tree = groups or levels
+    search = not (build or dedup or update or neighbors or label or merge or match or albums or spread or tree)
     seen = set()
     i = 0
     while i < len(argv):
         a = argv[i]
         takes = {"-m": "model", "--model": "model", "-v": "verbose", "--verbose": "verbose", "--db": "db"}
-        if not (dedup or neighbors or merge or albums or spread):
+        if not (dedup or neighbors or merge or albums or spread or tree):
             takes.update({"-t": "threads", "--threads": "threads"})
         if build:
             takes["--dtype"] = "dtype"
             takes["--grid"] = "grid"
         elif neighbors or label or match:
             takes.update({"-n": "results", "--results": "results"})
+        elif tree:
+            takes.update({"-n": "results", "--results": "results", "--in": "in"})
+            if groups:
+                takes["--min"] = "min_size"
         elif merge:
             takes.update({"-d": "max_distance", "--max-distance": "max_distance", "--from": "from"})
         elif spread:
@@ -190,12 +214,12 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         elif dedup and a == "--prune":
             p["prune"] = True
         elif a in ("-h", "--help"):
-            _help(build, p, dedup, update, neighbors, label, merge, match, albums, spread)
+            _help(build, p, dedup, update, neighbors, label, merge, match, albums, spread, groups, levels)
             sys.exit(0)
         elif a.startswith("-"):
             print("main: unrecognized argument: %s" % a)
             return None
-        elif dedup or neighbors or merge or albums or spread:
+        elif dedup or neighbors or merge or albums or spread or tree:
             print("main: unexpected argument: %s" % a)
             return None
         elif build or update or label or match:
@@ -208,7 +232,7 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         if p["rest"] or "max_distance" in seen:
             print("main: --like cannot be combined with a query or with -d: it lists the -n nearest images of an indexed one")
             return None
-    elif (not p["rest"] and not (dedup or neighbors or merge or match or albums or spread)) or (build and p["dtype"] not in ("f16", "f32", "i8")):
+    elif (not p["rest"] and not (dedup or neighbors or merge or match or albums or spread or tree)) or (build and p["dtype"] not in ("f16", "f32", "i8")):
         return None
     if merge and not p["from"]:
         return None
@@ -221,6 +245,15 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         if p["results"] < max(1, len(p["from"])):
             print("main: -n %d: spread picks at least one image and at least the %d given with --from" % (p["results"], len(p["from"])))
             return None
+    if groups:
+        if p["results"] is None:
+            return None
+        if p["results"] < 1:
+            print("main: -n %d: groups makes at least one group" % p["results"])
+            return None
+    if levels and p["results"] < 1:
+        print("main: -n %d: levels prints at least one row" % p["results"])
+        return None
     if match and len(p["rest"]) > 1:
         print("main: match takes one image path, or none for every indexed image")
         return None
@@ -244,10 +277,33 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
     return p
 
 
-def _help(build, p, dedup=False, update=False, neighbors=False, label=False, merge=False, match=False, albums=False, spread=False):
+def _help(build, p, dedup=False, update=False, neighbors=False, label=False, merge=False, match=False, albums=False, spread=False,
+          groups=False, levels=False):
     radius = ("  -d R, --max-distance R: %s within cosine distance R (<= R). Default: %s. %g is a starting point for embeddings of near-identical"
               " images, not a tuned value: check a few groups of your collection and adjust R")
-    if spread:
+    if groups or levels:
+        if groups:
+            print("Usage: python -m clip_cpp_amd.image_search groups [options] -n N")
+            print("\nSplits the images of an index built by `build` into exactly N groups: the single-linkage tree of the index (its minimum")
+            print("spanning tree) without its N - 1 longest links. No distance has to be guessed. Nothing is encoded, nothing on disk changes.")
+            print("Groups are printed as `dedup` prints them, the largest first; the last line states the distance at which the tree was cut.")
+        else:
+            print("Usage: python -m clip_cpp_amd.image_search levels [options]")
+            print("\nPrints the table of distance against groups for an index built by `build`: what `dedup -d R` would find at each R, from one")
+            print("pass over the single-linkage tree of the index. Each row: a distance, the groups of two or more images at it, the images in")
+            print("them and the size of the largest group. Nothing is encoded, nothing on disk changes.")
+        print("\nOptions:")
+        print("  -h, --help: Show this message and exit")
+        print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default (loaded only to place the index on its device).")
+        print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
+        print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
+        if groups:
+            print("  -n N, --results N: make exactly N groups, single images included. Required")
+            print("  --min M: print only the groups of at least M images. Default: 2 (1: single images too)")
+        else:
+            print("  -n ROWS, --results ROWS: rows of the table, evenly spaced over the merges of the tree. Default: %d" % LEVEL_ROWS)
+        print("  --in <prefix>: only images whose indexed path starts with <prefix> take part; may be repeated")
+    elif spread:
         print("Usage: python -m clip_cpp_amd.image_search spread [options] -n N")
         print("\nPicks N images of an index built by `build` that between them cover the collection: the first indexed image (or the --from")
         print("images), then again and again the image farthest from everything picked so far. Nothing is encoded, nothing on disk changes.")
@@ -983,6 +1039,136 @@ def spread(argv):
     return 0
 
 
+def tree_groups(size, lo, hi, d, n_groups, eligible=None, min_size=2):
+    """Exactly n_groups groups from the edges of Index.linkage (the whole tree, sorted): the tree without its n_groups - 1 longest edges.
+    Returns (groups, longest edge kept, shortest edge dropped): groups in the structure of component_groups, [(id, distance to its
+    nearest other member), ...] in id order (inf for a single image), only those of at least min_size images, largest first, equal sizes
+    in order of the lowest id; the two distances are -inf / inf when no edge is kept / dropped.  Every `dedup -d R` with R from the first
+    up to, but not including, the second finds these groups.  ValueError when the edges cannot give n_groups."""
+    import clip_cpp_amd
+    lo, hi = np.asarray(lo, dtype=np.int64), np.asarray(hi, dtype=np.int64)
+    d = np.asarray(d, dtype=np.float32)
+    labels = clip_cpp_amd.cut_linkage(size, lo, hi, d, n_groups=n_groups, eligible=eligible)
+    kept = int(np.count_nonzero(labels >= 0)) - int(n_groups)
+    nearest = np.full(size, np.inf, dtype=np.float64)
+    np.minimum.at(nearest, lo[:kept], d[:kept].astype(np.float64))
+    np.minimum.at(nearest, hi[:kept], d[:kept].astype(np.float64))
+    ids = np.flatnonzero(labels >= 0)
+    order = ids[np.argsort(labels[ids], kind="stable")]
+    cuts = np.flatnonzero(np.diff(labels[order])) + 1
+    groups = [g for g in np.split(order, cuts) if g.size >= max(int(min_size), 1)]
+    groups.sort(key=lambda g: (-g.size, int(g[0])))
+    return ([list(zip(g.tolist(), nearest[g].tolist())) for g in groups], float(d[kept - 1]) if kept > 0 else float("-inf"),
+            float(d[kept]) if kept < d.size else float("inf"))
+
+
+def level_rows(size, d_sorted_lo, d_sorted_hi, d, rows=LEVEL_ROWS):
+    """The table of `levels` from the edges of Index.linkage (sorted): up to `rows` positions evenly spaced over the merges, the last merge
+    among them, each moved to the end of its run of equal distances, so that a row says what the cut at its distance gives: (distance,
+    groups of two or more rows, rows in them, size of the largest group)."""
+    lo, hi = np.asarray(d_sorted_lo, dtype=np.int64).tolist(), np.asarray(d_sorted_hi, dtype=np.int64).tolist()
+    d = np.asarray(d, dtype=np.float32)
+    e = d.size
+    if e == 0:
+        return []
+    rows = max(1, min(int(rows), e))
+    ends = sorted({int(np.searchsorted(d, d[(e * (r + 1)) // rows - 1], side="right")) for r in range(rows)})
+    parent, size_of = list(range(size)), [1] * size
+    groups = images = largest = 0
+    out, done = [], 0
+    for end in ends:
+        for t in range(done, end):
+            a, b = lo[t], hi[t]
+            while parent[a] != a:
+                parent[a] = parent[parent[a]]
+                a = parent[a]
+            while parent[b] != b:
+                parent[b] = parent[parent[b]]
+                b = parent[b]
+            if a == b:
+                continue
+            if a > b:
+                a, b = b, a
+            groups += 1 - (size_of[a] > 1) - (size_of[b] > 1)
+            images += (size_of[a] == 1) + (size_of[b] == 1)
+            parent[b] = a
+            size_of[a] += size_of[b]
+            largest = max(largest, size_of[a])
+        done = end
+        out.append((float(d[end - 1]), groups, images, largest))
+    return out
+
+
+def _load_tree(p, command):
+    """What `groups` and `levels` share: (paths, eligible or None, (lo, hi, d)) of the database's tree, or None after a message"""
+    import clip_cpp_amd
+    if _refuse_gridded(p["db"], command):
+        return None
+    image_paths = _read_db(p)
+    if image_paths is None:
+        return None
+    allow = None
+    if p["in"]:
+        allow = np.array([path.startswith(tuple(p["in"])) for path in image_paths], dtype=np.bool_)
+    m = len(image_paths) if allow is None else int(allow.sum())
+    if command == "groups" and p["results"] > m:
+        _err("main: -n %d: there are only %d images to group" % (p["results"], m))
+        return None
+    try:
+        clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])      # only the index's device: no image is encoded
+    except RuntimeError:
+        print("main: Unable to load model from %s" % p["model"])
+        return None
+    index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
+    edges = index.linkage(allow=allow)
+    index.close()
+    clip.close()
+    return image_paths, allow, edges
+
+
+def groups(argv):
+    p = _parse(argv, build=False, groups=True)
+    if p is None:
+        _help(False, dict(verbose=1, db="."), groups=True)
+        return 1
+    loaded = _load_tree(p, "groups")
+    if loaded is None:
+        return 1
+    image_paths, allow, (lo, hi, d) = loaded
+    found, kept, cut = tree_groups(len(image_paths), lo, hi, d, p["results"], allow, p["min_size"])
+    if p["verbose"] > 0:
+        print("groups:")
+    for g, members in enumerate(found):
+        if g:
+            print()
+        for i, dist in members:
+            print("  %f %s" % (dist, image_paths[i]))
+    print("main: %d groups, %d of them with at least %d images, %d images in those; longest link kept %f, cut at %f"
+          % (p["results"], len(found), max(p["min_size"], 1), sum(len(g) for g in found), kept, cut))
+    sys.stdout.flush()
+    return 0
+
+
+def levels(argv):
+    p = _parse(argv, build=False, levels=True)
+    if p is None:
+        _help(False, dict(verbose=1, db="."), levels=True)
+        return 1
+    loaded = _load_tree(p, "levels")
+    if loaded is None:
+        return 1
+    image_paths, allow, (lo, hi, d) = loaded
+    table = level_rows(len(image_paths), lo, hi, d, p["results"])
+    if p["verbose"] > 0:
+        print("levels:")
+        print("distance groups images largest")
+    for dist, n_groups, images, largest in table:
+        print("  %f %d %d %d" % (dist, n_groups, images, largest))
+    print("main: %d images, %d levels" % (len(image_paths) if allow is None else int(allow.sum()), len(table)))
+    sys.stdout.flush()
+    return 0
+
+
 def dedup(argv):
     import clip_cpp_amd
     p = _parse(argv, build=False, dedup=True)
@@ -1278,12 +1464,14 @@ def match(argv):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     commands = {"build": build, "update": update, "search": search, "dedup": dedup, "neighbors": neighbors, "label": label, "merge": merge, "match": match,
-                "albums": albums, "spread": spread}
+                "albums": albums, "spread": spread, "groups": groups, "levels": levels}
     if not argv or argv[0] not in commands:
         print("Usage: python -m clip_cpp_amd.image_search {build|search|dedup} [options] ...  (-h after the command for its options)")
         print("       python -m clip_cpp_amd.image_search update [options] dir [more dirs]  (an existing database brought in line with the disk)")
         print("       python -m clip_cpp_amd.image_search albums [options]  (the database grouped by content: albums, each with its most typical image as the cover)")
         print("       python -m clip_cpp_amd.image_search spread [options] -n N  (N images that between them cover the database: farthest-first selection)")
+        print("       python -m clip_cpp_amd.image_search groups [options] -n N  (the database split into exactly N groups: the single-linkage tree, cut)")
+        print("       python -m clip_cpp_amd.image_search levels [options]  (the table of distance against groups: which -d to give dedup)")
         print("       python -m clip_cpp_amd.image_search neighbors [options]  (every indexed image's nearest other images; search --like PATH for one)")
         print("       python -m clip_cpp_amd.image_search label [options] LABEL [LABEL ...]  (every indexed image's best-fitting labels)")
         print("       python -m clip_cpp_amd.image_search merge [options] --db DIR --from DIR2 [--from DIR3 ...]  (append databases, nothing encoded twice)")

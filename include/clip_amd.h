@@ -509,6 +509,37 @@ bool clip_amd_index_modes_device(struct clip_amd_index * ix, float radius, float
  * clip_amd_bench_range (sparse), copies > 0: over the groups of a row and `copies` noisy copies of clip_amd_bench_search_distinct (dense);
  * < 0 on error.  Used by scripts/modes_bench.py. */
 float clip_amd_bench_modes(int dtype, int64_t n, int dim, float radius, float link, int copies, int iters);
+/* The single-linkage tree: the minimum spanning tree of the eligible rows under the index's own distances.  Its edges, sorted, are the
+ * single-linkage dendrogram: cutting the tree at any R (dropping the edges with d > R) leaves exactly the groups clip_amd_index_components
+ * gives at R, dropping its N - 1 longest edges leaves exactly N groups, and the sorted distances are the table of radius against number
+ * of groups.  One call answers for every radius.
+ * E is the set of eligible rows (live and set in allow, layout as live_mask, NULL = every live row), m its size; for x < y in E, d(x, y) is
+ * the distance clip_amd_index_pairs reports for that pair, the same bits from the same chain.  Every comparison is in f32 on those bits.
+ * Edges are ordered by (d, lo, hi), lo < hi, lexicographically: a total order.  The result is the minimum spanning forest of the graph
+ * "d <= link" under that order: an edge belongs to it exactly when its endpoints are not connected by strictly smaller edges.  So the
+ * forest is unique.  link = INFINITY gives the whole tree, m - 1 edges; a finite link gives m - c edges, c being the number of components
+ * at link, singletons included, and those edges are the first m - c of the whole tree.
+ * Host form: lo, hi [size - 1] int64 and distances [size - 1] f32 receive the edges in ascending edge order; returns their number, 0 when
+ * m <= 1 (nothing is written), -1 on error.  Device form: the same set of edges into HBM arrays of the same capacity and their number into
+ * d_count (int64); their order is not specified, but it is the same, byte for byte, run to run.
+ * Results are bit-identical run to run, however rows were split across add calls and across save / load, and do not depend on the order
+ * of any atomic; over E they are those of an index to which only the rows of E were ever added (ids mapped in order).
+ * -1 / false with a message on stderr, nothing launched and no output written, for a NULL index, a NULL output or a NaN link.
+ * Host form: host arrays, synchronous on the ctx stream.  Device form: allow (trusted) and the outputs in HBM, asynchronous on the ctx
+ * stream, synchronises with nothing on the host: it queues ceil(log2 size) rounds, each one sweep over the pairs of E plus O(size) work,
+ * and a round after the tree is complete exits at once.  Device memory beyond the index: 32 bytes per row (the host form 20 more for its
+ * results). */
+int64_t clip_amd_index_linkage(struct clip_amd_index * ix, float link, const uint64_t * allow, int64_t * lo, int64_t * hi, float * distances);
+bool clip_amd_index_linkage_device(struct clip_amd_index * ix, float link, const uint64_t * d_allow, int64_t * d_lo, int64_t * d_hi,
+                                   float * d_distances, int64_t * d_count);
+/* Average wall time (microseconds) of one clip_amd_index_linkage (host form, link = INFINITY) over the rows of clip_amd_bench_modes
+ * (copies == 0: sparse, copies > 0: groups of a row and `copies` noisy copies); < 0 on error.  clip_amd_bench_linkage_rounds: the rounds
+ * that did work in the last call of it.  Used by scripts/linkage_bench.py. */
+float clip_amd_bench_linkage(int dtype, int64_t n, int dim, int copies, int iters);
+int clip_amd_bench_linkage_rounds(void);
+/* The rounds that did work in the index's last clip_amd_index_linkage (host form): sweeps over the pairs that ran; -1 for a NULL index.
+ * Used by scripts/linkage_bench.py and tests/. */
+int clip_amd_test_index_linkage_rounds(struct clip_amd_index * ix);
 /* Farthest-first selection (greedy k-center): n_max rows that between them cover the index, each picked as the row farthest from
  * everything chosen before it.  Every prefix of the result is a 2-approximate k-center solution, and reach[t] is the coverage radius of
  * the prefix before position t, so one call gives the table of "how many rows" against "how far is everything else".
