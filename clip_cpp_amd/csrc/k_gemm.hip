@@ -40,10 +40,6 @@
 
 #include "gemm_common.h"
 
-#ifndef CLIPAMD_TEST_HOOKS
-#define CLIPAMD_TEST_HOOKS 1
-#endif
-
 namespace clipamd {
 
 namespace {

@@ -10,6 +10,12 @@
 
 #include "jpeg_stages.h"
 
+// Kernel test and micro-benchmark hooks (test_hooks.cpp) and the tuning aids that go with them (k_gemm.hip tile_override): on unless the
+// build says -DCLIPAMD_TEST_HOOKS=0 (`make hooks=0`).  This is the only place that gives the default.
+#ifndef CLIPAMD_TEST_HOOKS
+#define CLIPAMD_TEST_HOOKS 1
+#endif
+
 namespace clipamd {
 
 typedef _Float16 half_t;

@@ -215,6 +215,16 @@ struct RelaxCapture {
     RelaxCapture & operator=(const RelaxCapture &) = delete;
 };
 
+// RAII device buffer (api.cpp's batched zero-shot, the kernel test hooks of test_hooks.cpp); p stays null when the allocation fails.
+// Hidden: a helper of two translation units, not a symbol of the library.
+struct __attribute__((visibility("hidden"))) DBuf {
+    void * p = nullptr;
+    explicit DBuf(size_t n) { if (hipMalloc(&p, n ? n : 16) != hipSuccess) p = nullptr; }
+    ~DBuf() { if (p) (void)hipFree(p); }
+    DBuf(const DBuf &) = delete;
+    DBuf & operator=(const DBuf &) = delete;
+};
+
 // load.cpp
 clip_ctx * load_model(const char * fname, int verbosity, int device);
 clip_ctx * sibling_context(clip_ctx * owner, int index = 0);     // owner->sibling (index 0) / more_siblings[index - 1], created on first use (nullptr on failure)
