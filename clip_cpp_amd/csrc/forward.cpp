@@ -173,6 +173,17 @@ bool ensure_panel(clip_ctx * ctx, size_t halfs) {
     return true;
 }
 
+// Which of a layer's four GEMMs (i = 0 q/k/v, 1 out, 2 FFN-up, 3 FFN-down) multiplies a RESIDENT fp16 panel of its block-quantised weight: a
+// function of the row count, the weight and device_shared(ctx) alone.  resident_panels() builds what it names and dequant_layer() uses
+// what it names — a panel that an earlier batch left behind but this row count does not want is ignored, so that the kernels of a call do not
+// depend on the calls before it.  The reasons for each line are with resident_panels().
+bool wants_resident_panel(const clip_ctx * ctx, const DevWeight & w, int i, int rows) {
+    if (w.wtype == W_F16 || w.wtype == W_F32) return false;
+    if (i == 3) return rows >= 4096 && gemm_tile_uses_panel(gemm_tile_for(rows, w.N, w.Kpad, false));
+    if (i == 1) return rows >= 4096 && rows < 32768 && gemm_tile_uses_panel(gemm_tile_for(rows, w.N, w.Kpad, false));
+    return rows >= 32768 && gemm_tile_for(rows, w.N, w.Kpad, false, device_shared(ctx)) % 1000 == 261;
+}
+
 // res: this layer's four entries of the resident-panel table (resident_panels below), or null
 LayerPanels dequant_layer(clip_ctx * ctx, const DevLayer & l, int rows, const half_t * const * res = nullptr) {
     LayerPanels lp;
@@ -184,10 +195,10 @@ LayerPanels dequant_layer(clip_ctx * ctx, const DevLayer & l, int rows, const ha
     size_t need = 0;
     bool todo[4];
     for (int i = 0; i < 4; i++) {
-        // kept from the first large batch: nothing to dequantise.  (A q/k/v or FFN-up panel exists for the 32 x 32 x 16 kernel only: where the
-        // heuristic does not pick that kernel — device shared with the other tower, another row count — the fused kernels multiply the quantised planes)
-        const bool for32 = i == 0 || i == 2;
-        if (res && res[i] && (!for32 || gemm_tile_for(rows, ws[i]->N, ws[i]->Kpad, false, device_shared(ctx)) % 1000 == 261)) { *slot[i] = res[i]; todo[i] = false; continue; }
+        // a resident panel that THIS row count wants (wants_resident_panel: what a fresh context would have built for this call): nothing to
+        // dequantise.  One that only another row count or another device_shared state wants stays unused here — the call runs what it would
+        // run without it: the per-layer panel below or the fused kernels on the quantised planes
+        if (res && res[i] && wants_resident_panel(ctx, *ws[i], i, rows)) { *slot[i] = res[i]; todo[i] = false; continue; }
         todo[i] = ws[i]->wtype != W_F16 && ws[i]->wtype != W_F32 && gemm_tile_uses_panel(gemm_tile_for(rows, ws[i]->N, ws[i]->Kpad, true));
         if (todo[i]) need += (size_t)ws[i]->Npad * ws[i]->Kpad;
     }
@@ -271,48 +282,54 @@ const half_t * const * resident_panels(clip_ctx * ctx, const DevTower & tw, int 
         clip_ctx * o = ctx->owner;
         return (o->res_panel_mask[which] && o->res_panels[which].size() == 4 * tw.layers.size()) ? o->res_panels[which].data() : nullptr;
     }
-    const DevLayer & l0 = tw.layers[0];
-    unsigned want = 0;
-    if (l0.ff2.wtype != W_F16 && l0.ff2.wtype != W_F32 && rows >= 4096 && gemm_tile_uses_panel(gemm_tile_for(rows, l0.ff2.N, l0.ff2.Kpad, false))) want |= 8u;
-    if (l0.o.wtype != W_F16 && l0.o.wtype != W_F32 && rows >= 4096 && rows < 32768 && gemm_tile_uses_panel(gemm_tile_for(rows, l0.o.N, l0.o.Kpad, false))) want |= 2u;
+    // what this call wants (wants_resident_panel — the same predicate decides in dequant_layer which entries the call uses):
+    // FFN-down and, below 32768 rows, the out-projection where their fp16 form runs on a panel kernel (rounds 4 and 6);
     // round 6: q/k/v and FFN-up where the 32 x 32 x 16 kernel (k_gemm32.hip: fp16 x fp16) takes the shape (ViT-B/32 at batch 256: 99 MB per tower)
     // ... from 32768 rows only (ViT-L/14 / H/14 batches, where the alternative is a per-layer dequantisation launch + the 256 x 256 kernel).  Below that
     // (ViT-B/32-class batches) the fused-dequant two-per-CU kernels, after the instruction trims of round 6, are ahead of the 32 x 32 x 16 kernel on 99 MB of
     // resident panels for block-quantised files: 80.5-80.6 k against 79.0-79.3 k img/s, texts 161 k against 163 k (profiles/r06_experiments.txt section 19);
-    // f16 files, which need no panel, keep that kernel (+2 %).
-    if (rows >= 32768 && l0.qkv.wtype != W_F16 && l0.qkv.wtype != W_F32 && gemm_tile_for(rows, l0.qkv.N, l0.qkv.Kpad, false, device_shared(ctx)) % 1000 == 261) want |= 1u;
-    if (rows >= 32768 && l0.ff1.wtype != W_F16 && l0.ff1.wtype != W_F32 && gemm_tile_for(rows, l0.ff1.N, l0.ff1.Kpad, false, device_shared(ctx)) % 1000 == 261) want |= 4u;
+    // f16 files, which need no panel, keep that kernel (+2 %).  A q/k/v or FFN-up panel that a 32768-row batch has left is NOT used by a smaller
+    // batch afterwards: that call runs the fused kernels, as it would on a fresh context.
+    const DevLayer & l0 = tw.layers[0];
+    const DevWeight * w0[4] = {&l0.qkv, &l0.o, &l0.ff1, &l0.ff2};
+    unsigned want = 0;
+    for (int i = 0; i < 4; i++) if (wants_resident_panel(ctx, *w0[i], i, rows)) want |= 1u << i;
     if (!want) return nullptr;
     auto & tab = ctx->res_panels[which];
-    if ((ctx->res_panel_mask[which] & want) == want && tab.size() == 4 * tw.layers.size()) return tab.data();
+    if (tab.size() != 4 * tw.layers.size()) return nullptr;    // (sized at load: load.cpp)
+    const unsigned have = ctx->res_panel_mask[which];
+    if ((have & want) == want) return tab.data();
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(ctx->stream, &cs);
-    if (cs != hipStreamCaptureStatusNone) return (ctx->res_panel_mask[which] && tab.size() == 4 * tw.layers.size()) ? tab.data() : nullptr;
-    want |= ctx->res_panel_mask[which];
-    (void)hipStreamSynchronize(ctx->stream);                   // (re)build: nothing may still read the old table
-    if (ctx->res_panel_buf[which]) (void)hipFree(ctx->res_panel_buf[which]);
-    ctx->res_panel_buf[which] = nullptr;
-    ctx->res_panel_mask[which] = 0;
-    tab.clear();
+    if (cs != hipStreamCaptureStatusNone) return have ? tab.data() : nullptr;
+    // Grow: the missing panels go into a buffer of their own.  Nothing that exists is freed, moved or rewritten — graphs captured earlier hold the
+    // addresses of the old entries in their kernel nodes and siblings read this table in place on their own streams — and a new entry is
+    // published only when the dequantisation that fills it has completed.
+    const unsigned add = want & ~have;
     size_t halfs = 0;
     for (const DevLayer & l : tw.layers) {
         const DevWeight * ws[4] = {&l.qkv, &l.o, &l.ff1, &l.ff2};
-        for (int i = 0; i < 4; i++) if (want >> i & 1) halfs += (size_t)ws[i]->Npad * ws[i]->Kpad;
+        for (int i = 0; i < 4; i++) if (add >> i & 1) halfs += (size_t)ws[i]->Npad * ws[i]->Kpad;
     }
-    if (hipMalloc((void **)&ctx->res_panel_buf[which], halfs * sizeof(half_t)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    half_t * buf = nullptr;
+    if (hipMalloc((void **)&buf, halfs * sizeof(half_t)) != hipSuccess) { (void)hipGetLastError(); return have ? tab.data() : nullptr; }
+    ctx->res_panel_bufs[which].push_back(buf);
+    std::vector<half_t *> fresh(tab.size(), nullptr);
     size_t off = 0;
-    for (const DevLayer & l : tw.layers) {
+    for (size_t li = 0; li < tw.layers.size(); li++) {
+        const DevLayer & l = tw.layers[li];
         const DevWeight * ws[4] = {&l.qkv, &l.o, &l.ff1, &l.ff2};
         for (int i = 0; i < 4; i++) {
-            if (!(want >> i & 1)) { tab.push_back(nullptr); continue; }
-            half_t * o = ctx->res_panel_buf[which] + off;
+            if (!(add >> i & 1)) continue;
+            half_t * o = buf + off;
             launch_dequant(&ws[i], &o, 1, ctx->stream);
-            tab.push_back(o);
+            fresh[4 * li + i] = o;
             off += (size_t)ws[i]->Npad * ws[i]->Kpad;
         }
     }
-    (void)hipStreamSynchronize(ctx->stream);                   // one-time build: siblings read the table on their own streams (borrowed above)
-    ctx->res_panel_mask[which] = want;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return have ? tab.data() : nullptr;      // (the buffer stays listed for the teardown)
+    for (size_t k = 0; k < tab.size(); k++) if (fresh[k] && !tab[k]) tab[k] = fresh[k];
+    ctx->res_panel_mask[which] = have | add;
     return tab.data();
 }
 
@@ -770,9 +787,12 @@ bool vision_forward_device(clip_ctx * ctx, const float * d_imgs, int B, float * 
     // (looked up again after every vision_forward_launch: growing a sibling's workspace drops this context's graphs — ensure_workspace).
     // The sibling's state is part of the key: the split decision differs with it, so each form has its own entry — first sighting
     // eager, second captured — and a caller that alternates pair calls and plain calls still reaches its captures.
+    // So is device_shared(ctx), which also holds the caller's own flag (clip_amd_set_device_shared): the GEMM heuristic picks other kernels
+    // when it flips (gemm_tile_for), and a capture replays the kernels of the setting it was taken under.
+    const bool shared = device_shared(ctx);
     auto find = [&]() -> clip_ctx::GraphEntry * {
         for (auto & g : ctx->vgraphs)
-            if (g.B == B && g.in == d_imgs && g.out == d_out && g.norm == normalize && g.in_f16 == ctx->input_f16 && g.busy_seen == ctx->sibling_busy) return &g;
+            if (g.B == B && g.in == d_imgs && g.out == d_out && g.norm == normalize && g.in_f16 == ctx->input_f16 && g.busy_seen == ctx->sibling_busy && g.shared_seen == shared) return &g;
         return nullptr;
     };
     clip_ctx::GraphEntry * e = find();
@@ -784,7 +804,7 @@ bool vision_forward_device(clip_ctx * ctx, const float * d_imgs, int B, float * 
     }
     if (!e) {   // first sighting: run eagerly (allocates the workspace, sets kernel attributes)
         if (ctx->vgraphs.size() >= 16) drop_graphs(ctx);
-        ctx->vgraphs.push_back({B, d_imgs, d_out, normalize, ctx->input_f16, 1, nullptr, nullptr, false, ctx->sibling_busy});
+        ctx->vgraphs.push_back({B, d_imgs, d_out, normalize, ctx->input_f16, 1, nullptr, nullptr, false, ctx->sibling_busy, shared});
         return vision_forward_launch(ctx, d_imgs, B, d_out, normalize);
     }
     // second sighting: capture
@@ -1026,18 +1046,21 @@ bool text_forward_device(clip_ctx * ctx, const int32_t * d_ids, const int32_t * 
     };
     // Small token counts are launch-bound (~90 dependent launches): capture the chain on the second sighting of a signature and
     // replay it afterwards.  The kernels read the sequence offsets from device memory (uploaded above), so a graph only depends on
-    // (texts, token rows, attention key-tile bucket, pointers) — not on the individual lengths.  The bucket also fixes which attention
+    // (texts, token rows, attention key-tile bucket, pointers, device_shared(ctx)) — not on the individual lengths.  The bucket also fixes which attention
     // kernel runs (the whole-row limits 592 / 288 are whole tiles) and the streaming kernel's grid (whole blocks of 64 / 128 queries).
     const int nt_bucket = (P.max_len + 15) / 16;
     if (ctx->graphs_enabled && !ctx->profiling && rows <= 1024 && !guard_mode()) {
         clip_ctx::TextGraphEntry * e = nullptr;
         const void * ids_key = d_ids + h_offsets[0];
+        // (device_shared: no kernel choice depends on it at <= 1024 rows today — every such branch of the tile heuristic starts at 8192 — but the
+        //  launches carry the flag, so the key does too, as the vision key does)
+        const bool shared = device_shared(ctx);
         for (auto & g : ctx->tgraphs)
-            if (g.n_texts == n_texts && g.rows == rows && g.nt == nt_bucket && g.ids == ids_key && g.out == d_out && g.norm == normalize) { e = &g; break; }
+            if (g.n_texts == n_texts && g.rows == rows && g.nt == nt_bucket && g.ids == ids_key && g.out == d_out && g.norm == normalize && g.shared_seen == shared) { e = &g; break; }
         if (e && e->exec) return hipGraphLaunch(e->exec, s) == hipSuccess;
         if (!e) {
             if (ctx->tgraphs.size() >= 96) drop_graphs(ctx);
-            ctx->tgraphs.push_back({n_texts, rows, nt_bucket, ids_key, d_out, normalize, 1, nullptr, nullptr});
+            ctx->tgraphs.push_back({n_texts, rows, nt_bucket, ids_key, d_out, normalize, 1, nullptr, nullptr, shared});
         } else if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
             break_capture_for_test();
             const bool ok = launch_all();

@@ -628,6 +628,9 @@ clip_ctx * load_model(const char * fname, int verbosity, int device) {
         ctx->ln_fold_force = e && e[0] == '2';       // tuning: fold even where forward.cpp fold_pays() says the LayerNorm launches are cheaper
         const char * e2 = getenv("CLIP_AMD_RESIDENT_PANELS");
         ctx->resident_panels_on = !(e2 && e2[0] == '0');
+        // the resident-panel tables (forward.cpp resident_panels): every entry null, sized here once and never again — siblings read them in place
+        ctx->res_panels[0].assign(4 * ctx->vision.layers.size(), nullptr);
+        ctx->res_panels[1].assign(4 * ctx->text.layers.size(), nullptr);
         const char * ef = getenv("CLIP_AMD_F32_ACTS");
         ctx->f32_acts = !(ef && ef[0] == '0');
         const char * ep = getenv("CLIP_AMD_PRUNE_LAST");
@@ -713,7 +716,7 @@ void free_model(clip_ctx * ctx) {
         if (ctx->pre_buf) (void)hipFree(ctx->pre_buf);
         free_preprocess_slots(ctx);
         if (ctx->w16_panel) (void)hipFree(ctx->w16_panel);
-        for (auto * b : ctx->res_panel_buf) if (b) (void)hipFree(b);
+        for (auto & bufs : ctx->res_panel_bufs) for (auto * b : bufs) if (b) (void)hipFree(b);
         if (ctx->sk_stats) (void)hipFree(ctx->sk_stats);
         if (ctx->sk_ws) (void)hipFree(ctx->sk_ws);
         if (ctx->sk_cnt) (void)hipFree(ctx->sk_cnt);

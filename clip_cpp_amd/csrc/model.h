@@ -166,7 +166,10 @@ struct clip_ctx {
     size_t w16_panel_halfs = 0;
     // RESIDENT fp16 panels of block-quantised weights (forward.cpp resident_panels; round 4), per tower ([0] vision, [1] text): built on the
     // first batch that wants them, entry 4 * layer + {0 q/k/v, 1 out, 2 FFN-up, 3 FFN-down}, null = multiply the quantised planes.
-    clipamd::half_t * res_panel_buf[2] = {nullptr, nullptr};
+    // The table has its 4 * layers entries from load to teardown (load.cpp) and an entry, once set, keeps its value: captured graphs hold
+    // panel addresses in their kernel nodes and siblings read the table itself.  A later batch that wants more weights adds a buffer
+    // with the missing panels to res_panel_bufs; all of them are freed with the context.
+    std::vector<clipamd::half_t *> res_panel_bufs[2];
     std::vector<const clipamd::half_t *> res_panels[2];
     unsigned res_panel_mask[2] = {0, 0};      // which of the four weights the table holds (bit = index above)
     bool resident_panels_on = true;           // CLIP_AMD_RESIDENT_PANELS=0: per-layer dequantisation launches / fused kernels only (A/B)
@@ -181,12 +184,13 @@ struct clip_ctx {
     // second time the same (batch, input pointer, output pointer, normalize) signature is seen and replayed afterwards.
     // split: the capture holds kernel nodes on the sibling context (batch split over two streams) — such a graph must not be replayed
     // while the sibling carries something else (sibling_busy); busy_seen: sibling_busy at the last eager sighting — a capture happens
-    // only behind an eager run that took the same split decision, so every workspace the captured form needs already has its size
-    struct GraphEntry { int B; const void * in; void * out; bool norm; bool in_f16; int seen; hipGraph_t graph; hipGraphExec_t exec; bool split; bool busy_seen; };
+    // only behind an eager run that took the same split decision, so every workspace the captured form needs already has its size;
+    // shared_seen: forward.cpp device_shared(ctx) at that sighting — the GEMM heuristic picks other kernels when it flips, so it is part of the key
+    struct GraphEntry { int B; const void * in; void * out; bool norm; bool in_f16; int seen; hipGraph_t graph; hipGraphExec_t exec; bool split; bool busy_seen; bool shared_seen; };
     std::vector<GraphEntry> vgraphs;
     // ... and for the text forward at small token counts (single texts, short label lists): keyed on (texts, token rows,
-    // attention key-tile bucket, pointers); the per-call sequence offsets live in device memory and are uploaded before the replay
-    struct TextGraphEntry { int n_texts, rows, nt; const void * ids; void * out; bool norm; int seen; hipGraph_t graph; hipGraphExec_t exec; };
+    // attention key-tile bucket, pointers, device_shared(ctx)); the per-call sequence offsets live in device memory and are uploaded before the replay
+    struct TextGraphEntry { int n_texts, rows, nt; const void * ids; void * out; bool norm; int seen; hipGraph_t graph; hipGraphExec_t exec; bool shared_seen; };
     std::vector<TextGraphEntry> tgraphs;
     bool graphs_enabled = true;      // CLIP_AMD_GRAPHS=0 disables
 

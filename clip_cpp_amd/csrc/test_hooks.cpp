@@ -283,6 +283,23 @@ int clip_amd_test_gemm_tile_ex(int64_t M, int64_t N, int64_t K, int quantised, i
     return gemm_tile_for((int)M, (int)N, Kpad, quantised != 0, shared_device != 0);
 }
 
+// What a context carries from one call to the next (model.h), for the call-history tests: fields are read, nothing else — no HIP call, so
+// a host-only context answers too.
+int clip_amd_test_ctx_state(struct clip_ctx * ctx, int which, int64_t * head, uint64_t * panels, int panels_cap) {
+    if (!ctx || (which != 0 && which != 1) || !head || panels_cap < 0 || (!panels && panels_cap > 0)) return -3;
+    const auto & tab = ctx->res_panels[which];
+    int64_t vg = 0, tg = 0;
+    for (const auto & g : ctx->vgraphs) vg += g.exec != nullptr;
+    for (const auto & g : ctx->tgraphs) tg += g.exec != nullptr;
+    head[0] = (int64_t)ctx->res_panel_mask[which];
+    head[1] = (int64_t)tab.size();
+    head[2] = vg;
+    head[3] = tg;
+    head[4] = (int64_t)ctx->ws.bytes;
+    for (size_t k = 0; k < tab.size() && k < (size_t)panels_cap; k++) panels[k] = (uint64_t)(uintptr_t)tab[k];
+    return (int)tab.size();
+}
+
 // Extended form: qcols / qscale (EPI_F16 Q-scale path, clip.cpp:1363) and epilogue 5 = EPI_PATCH_F32 (patch embedding:
 // row m of the GEMM lands in output row (m / Np) * T + 1 + m % Np and gets pos[1 + m % Np] added; no bias; the class-token
 // rows (b * T) are left untouched).  For epilogue 5, y is [(M / Np) * T][N] and pos is [T][N].

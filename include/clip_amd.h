@@ -79,7 +79,17 @@ void clip_amd_set_stream(struct clip_ctx * ctx, void * hip_stream);
  * on a second context / stream.  The GEMM heuristic then keeps to kernels that share a compute unit (two workgroups per CU); with
  * shared == 0 (the default: one encoder call at a time, as every reference caller does) the wide q/k/v and FFN-up GEMMs of a large batch
  * run on kernels that take a whole CU each (k_gemm32.hip).  Results agree within fp16 output rounding either way.  The two-tower
- * multi-GPU entry point (clip_amd_encode_pair_device_multi) knows by itself. */
+ * multi-GPU entry point (clip_amd_encode_pair_device_multi) knows by itself.
+ *
+ * WHAT THE BITS OF AN ENCODE DEPEND ON.  The embeddings a call returns are a function of
+ *   - the model file,
+ *   - the inputs of the call and how they are batched (which items share a call, in which order: kernels are chosen by row count),
+ *   - `normalize`,
+ *   - this flag and the sibling state AT THE CALL (the other tower of a pair call running next to it),
+ *   - the environment switches the library read when the context was loaded (CLIP_AMD_*),
+ * and of nothing else (a call made while clip_amd_profile_enable is on is a different call in this sense: it runs unsplit and uncaptured).  The calls a context has served before — other batch sizes, the other tower, captured and replayed graphs, resident
+ * panels built for a larger batch, a workspace that has grown, profiling switched on and off, this flag set and set back — are NOT on the
+ * list: a context with a history returns bit for bit what a freshly loaded one returns for the same call (tests/test_gpu_call_history.py). */
 void clip_amd_set_device_shared(struct clip_ctx * ctx, int shared);
 
 /* Device-resident form of clip_image_batch_encode (reference clip.cpp:1247-1523):
@@ -678,6 +688,14 @@ int clip_amd_test_fold_consumer(int type, const void * w_raw, int64_t N2, int64_
  * BM * 1000 + BN; BM = 65: the mid-M ring kernel on 64-row tiles (k_gemm_ring.hip), BN = 256 / 258-260: the large-M panel kernels. */
 int clip_amd_test_gemm_tile(int64_t M, int64_t N, int64_t K, int quantised);
 int clip_amd_test_gemm_tile_ex(int64_t M, int64_t N, int64_t K, int quantised, int shared_device);   /* ... with clip_amd_set_device_shared's flag */
+/* The state a context keeps between calls, read-only (fields are read; no HIP call, so a host-only context answers too).  which: 0 the vision
+ * tower, 1 the text tower.  head[5], in this order: the resident-panel mask of that tower (bit i: weight i of every layer has a resident fp16
+ * panel; 0 q/k/v, 1 out-projection, 2 FFN-up, 3 FFN-down), the number of entries of its panel table (4 x layers on a context with a device,
+ * 0 on a host-only one), the number of vision graph entries that hold an instantiated graph, the same for the text graphs, the bytes of the
+ * activation workspace.  panels: the first min(panels_cap, entries) table entries as integers — entry 4 * layer + i is the device address of
+ * that panel, 0 where there is none; may be NULL with panels_cap == 0.  Returns the number of table entries, or -3 (nothing written): ctx or
+ * head NULL, which outside {0, 1}, panels_cap < 0, panels NULL with panels_cap > 0. */
+int clip_amd_test_ctx_state(struct clip_ctx * ctx, int which, int64_t * head, uint64_t * panels, int panels_cap);
 /* Average device time (microseconds, HIP events) of one GEMM shape through the production kernel on random
  * weights of ggml type `type`; < 0 on error.  Used by scripts/gemm_bench.py for kernel A/B work. */
 float clip_amd_bench_gemm(int type, int64_t N, int64_t K, int64_t M, int epilogue, int tile, int iters);
