@@ -67,7 +67,7 @@ AMD_SYMBOLS = [
     "clip_amd_image_batch_preprocess_device", "clip_amd_image_batch_encode_u8",
     "clip_amd_zero_shot_score_device", "clip_amd_zero_shot_label_images",
     "clip_amd_synchronize", "clip_amd_profile_enable", "clip_amd_profile_read", "clip_amd_profile_report",
-    "clip_amd_test_gemm", "clip_amd_test_gemm_ex", "clip_amd_test_gemm_f32", "clip_amd_test_gemm_tile", "clip_amd_test_gemm_tile_ex", "clip_amd_test_ctx_state", "clip_amd_test_skinny", "clip_amd_test_layernorm", "clip_amd_test_attention", "clip_amd_bench_gemm",
+    "clip_amd_test_gemm", "clip_amd_test_gemm_ex", "clip_amd_test_gemm_f32", "clip_amd_test_gemm_tile", "clip_amd_test_gemm_tile_ex", "clip_amd_test_ctx_state", "clip_amd_test_tower_plan", "clip_amd_test_skinny", "clip_amd_test_layernorm", "clip_amd_test_attention", "clip_amd_bench_gemm",
     "clip_amd_test_attention_ex", "clip_amd_bench_attention", "clip_amd_test_attention_ragged",
     "clip_amd_test_layernorm_ex", "clip_amd_test_text_embed", "clip_amd_test_im2col", "clip_amd_test_layernorm_prep", "clip_amd_test_rows",
     "clip_amd_test_gemm_panel", "clip_amd_test_dequant_panels", "clip_amd_test_fold_vectors", "clip_amd_test_fold_producer", "clip_amd_test_fold_consumer",
@@ -217,6 +217,8 @@ def lib():
     L.clip_amd_test_gemm_tile_ex.argtypes = [C.c_int64, C.c_int64, C.c_int64, i32, i32]
     L.clip_amd_test_ctx_state.restype = i32
     L.clip_amd_test_ctx_state.argtypes = [vp, i32, C.POINTER(C.c_int64), C.POINTER(C.c_uint64), i32]
+    L.clip_amd_test_tower_plan.restype = i32
+    L.clip_amd_test_tower_plan.argtypes = [C.c_int64, i32, i32, i32, i32, i32, C.c_int64, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), i32, C.POINTER(C.c_int64)]
     L.clip_amd_test_skinny.restype = i32
     L.clip_amd_test_skinny.argtypes = [i32, vp, C.c_int64, C.c_int64, f32p, C.c_int64, f32p, f32p, f32p, f32p, C.c_float, f32p, i32, i32, C.c_float, f32p]
     L.clip_amd_bench_gemm.restype = C.c_float

@@ -37,16 +37,18 @@ struct Carver {
     size_t off = 0;
     std::vector<size_t> * gaps = nullptr;       // guard mode: offsets of the canary blocks
     explicit Carver(void * b, std::vector<size_t> * g = nullptr) : base((uint8_t *)b), gaps(g) { if (gaps) gaps->clear(); }
-    template <typename T> T * take(size_t n) {
+    size_t take_bytes(size_t bytes) {           // the offset of the buffer
         off = (off + 255) & ~(size_t)255;
-        T * p = base ? (T *)(base + off) : nullptr;
-        off += n * sizeof(T);
+        const size_t at = off;
+        off += bytes;
         if (guard_mode()) {
             if (gaps) gaps->push_back(off);
             off += kGuardBytes;
         }
-        return p;
+        return at;
     }
+    template <typename T> T * at(size_t o) const { return base ? (T *)(base + o) : nullptr; }
+    template <typename T> T * take(size_t n) { return at<T>(take_bytes(n * sizeof(T))); }
 };
 
 bool guard_arm(clip_ctx * ctx) {
@@ -545,23 +547,64 @@ bool launch_ok(const char * who) {
     return true;
 }
 
-// The buffers both towers need, for `rows` token rows of `n` sequences
-void carve_tower(Carver & c, TowerBufs & b, int rows, int n, int h, int ff, int proj, bool f32) {
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// Bytes of the storage that qkv, att, mid and the im2col matrix share (carve_tower, alias): qkv with att behind it, or mid, or col
+size_t shared_region_bytes(size_t rows, int h, int ff, bool f32, size_t col_halfs) {
+    const size_t ab = f32 ? 4 : 2;                            // f32 file: the activation buffers hold float rows
+    return std::max({ab * rows * ff, align256(ab * rows * 3 * h) + ab * rows * h, col_halfs * sizeof(half_t)});
+}
+
+// The buffers both towers need, for `rows` token rows of `n` sequences, and the vision tower's im2col matrix of col_halfs elements (0: none; col
+// may then be null).  plan, where not null, receives the offsets.
+//
+// alias: buffers that are never live together share one region, so that the activations of a step cycle through fewer bytes of cache.
+// Liveness (run_layers, pooled_tail, vision_stage_patch):
+//   col   im2col .. patch GEMM, before the first layer (every copy piece's patch stage runs before vision_stage_finish on the same stream)
+//   qkv   q/k/v GEMM .. attention
+//   att   attention .. out-projection (last layer, pruned: .. gather_pooled)
+//   mid   FFN-up .. FFN-down
+// qkv and att are live together, mid with neither, col with none of the three: qkv and mid and col start at the region's base, att
+// behind qkv (3 h + h = ff in every CLIP shape, so qkv + att fill mid's bytes exactly).  x, xn, stats and mu live across all of these and the
+// pooled buffers are written while att and x are read (pooled_tail), so they keep storage of their own.  A consumer must find its
+// producer's bytes in everything it reads, because the region holds the previous producer's bytes where separate buffers held nothing
+// (guard mode: NaN patterns): the GEMMs clamp their A rows to M - 1 and the attention kernels their query / key rows to the sequence's last,
+// both on row widths without padding, and im2col writes the zero columns K .. Kpad - 1 itself (k_misc.hip).  One read is not covered by a producer,
+// here as with separate buffers: where K is no multiple of the 64-wide K-step a GEMM reads the Kpad - K elements behind a row against
+// zero weights — of the last row, behind the buffer (finite fp16 of a neighbour or canary bytes).
+void carve_tower(Carver & c, TowerBufs & b, half_t ** col, TowerPlan * plan, int rows, int n, int h, int ff, int proj, bool f32, size_t col_halfs, bool alias) {
+    TowerPlan pl;
+    auto take = [&](int what, size_t bytes) { pl.bytes[what] = bytes; pl.off[what] = c.take_bytes(bytes); return pl.off[what]; };
+    auto sub = [&](int what, size_t bytes, size_t at) { pl.bytes[what] = bytes; pl.off[what] = at; return at; };
+    const size_t ab = f32 ? 4 : 2;                            // f32 file: the activation buffers hold float rows
+    const size_t R = (size_t)rows;
     b.st_stride = (rows + 63) & ~63;
-    b.stats = c.take<float2>((size_t)(h / 16) * b.st_stride);
-    b.mu = c.take<float>((size_t)2 * b.st_stride);
-    b.x = c.take<float>((size_t)rows * h);
-    const size_t aw = f32 ? 2 : 1;                            // f32 file: the activation buffers hold float rows
-    b.xn = c.take<half_t>(aw * rows * h);
-    b.qkv = c.take<half_t>(aw * rows * 3 * h);
-    b.att = c.take<half_t>(aw * rows * h);
-    b.mid = c.take<half_t>(aw * rows * ff);
-    b.pooled = c.take<half_t>(aw * n * h);
-    b.emb = c.take<float>((size_t)n * proj);
-    b.xp = c.take<float>((size_t)n * h);
-    b.ap = c.take<half_t>(aw * n * h);
-    b.xnp = c.take<half_t>(aw * n * h);
-    b.midp = c.take<half_t>(aw * n * ff);
+    b.stats = c.at<float2>(take(TowerPlan::STATS, (size_t)(h / 16) * b.st_stride * sizeof(float2)));
+    b.mu = c.at<float>(take(TowerPlan::MU, (size_t)2 * b.st_stride * sizeof(float)));
+    b.x = c.at<float>(take(TowerPlan::X, R * h * sizeof(float)));
+    b.xn = c.at<half_t>(take(TowerPlan::XN, ab * R * h));
+    half_t * colp = nullptr;
+    if (alias) {
+        const size_t base = take(TowerPlan::REGION, shared_region_bytes(R, h, ff, f32, col_halfs));
+        b.qkv = c.at<half_t>(sub(TowerPlan::QKV, ab * R * 3 * h, base));
+        b.att = c.at<half_t>(sub(TowerPlan::ATT, ab * R * h, base + align256(ab * R * 3 * h)));
+        b.mid = c.at<half_t>(sub(TowerPlan::MID, ab * R * ff, base));
+        if (col_halfs) colp = c.at<half_t>(sub(TowerPlan::COL, col_halfs * sizeof(half_t), base));
+    } else {
+        b.qkv = c.at<half_t>(take(TowerPlan::QKV, ab * R * 3 * h));
+        b.att = c.at<half_t>(take(TowerPlan::ATT, ab * R * h));
+        b.mid = c.at<half_t>(take(TowerPlan::MID, ab * R * ff));
+    }
+    b.pooled = c.at<half_t>(take(TowerPlan::POOLED, ab * n * h));
+    b.emb = c.at<float>(take(TowerPlan::EMB, (size_t)n * proj * sizeof(float)));
+    b.xp = c.at<float>(take(TowerPlan::XP, (size_t)n * h * sizeof(float)));
+    b.ap = c.at<half_t>(take(TowerPlan::AP, ab * n * h));
+    b.xnp = c.at<half_t>(take(TowerPlan::XNP, ab * n * h));
+    b.midp = c.at<half_t>(take(TowerPlan::MIDP, ab * n * ff));
+    if (!alias && col_halfs) colp = c.at<half_t>(take(TowerPlan::COL, col_halfs * sizeof(half_t)));
+    if (col) *col = colp;
+    pl.total = c.off;
+    if (plan) *plan = pl;
 }
 
 // carve(Carver &) runs twice: over a null base to size the workspace, then over the workspace itself
@@ -599,6 +642,12 @@ bool run_tower(clip_ctx * ctx, TowerPass & P, float * d_out, bool normalize) {
 }
 
 }  // namespace
+
+void tower_plan(TowerPlan & plan, int rows, int nseq, int h, int ff, int proj, bool f32, size_t col_halfs, bool alias) {
+    Carver sizer(nullptr);
+    TowerBufs b;
+    carve_tower(sizer, b, nullptr, &plan, rows, nseq, h, ff, proj, f32, col_halfs, alias);
+}
 
 void drop_graphs(clip_ctx * ctx) {
     for (auto & g : ctx->vgraphs) {
@@ -851,8 +900,7 @@ bool vision_stage_begin(clip_ctx * ctx, int Bc, VisionStage & st) {
     const int rows = Bc * T;
     st.Bc = Bc;
     return carve_workspace(ctx, [&](Carver & c) {
-        carve_tower(c, st.b, rows, Bc, h, ff, proj, acts_f32(ctx, V));
-        st.col = c.take<half_t>((size_t)Bc * Np * V.patch.Kpad);
+        carve_tower(c, st.b, &st.col, nullptr, rows, Bc, h, ff, proj, acts_f32(ctx, V), (size_t)Bc * Np * V.patch.Kpad, ctx->ws_alias);
     });
 }
 
@@ -909,8 +957,10 @@ int vision_max_chunk(const clip_ctx * ctx) {
     const int S = hp.image_size, P = hp.patch_size, G = S / P, Np = G * G, T = Np + 1;
     const int h = hp.hidden_size, ff = hp.n_intermediate;
     // images are processed in chunks so that the workspace stays bounded (<= ~6 GB even for ViT-H)
-    const size_t aw = acts_f32(ctx, ctx->vision) ? 2 : 1;
-    const size_t per_img = (size_t)T * ((size_t)h * 4 + aw * ((size_t)h * 2 * 2 + (size_t)3 * h * 2 + (size_t)ff * 2)) + (size_t)Np * ctx->vision.patch.Kpad * 2;
+    const bool f32 = acts_f32(ctx, ctx->vision);
+    const size_t aw = f32 ? 2 : 1, col_halfs = (size_t)Np * ctx->vision.patch.Kpad;
+    const size_t per_img = ctx->ws_alias ? (size_t)T * ((size_t)h * 4 + aw * (size_t)h * 2) + shared_region_bytes(T, h, ff, f32, col_halfs)      // x, xn, the shared region (carve_tower)
+                                         : (size_t)T * ((size_t)h * 4 + aw * ((size_t)h * 2 * 2 + (size_t)3 * h * 2 + (size_t)ff * 2)) + col_halfs * 2;
     return (int)std::min<size_t>(1024, std::max<size_t>(1, ((size_t)6 << 30) / per_img));
 }
 
@@ -962,7 +1012,7 @@ bool text_forward_device(clip_ctx * ctx, const int32_t * d_ids, const int32_t * 
     const int rows = P.rows, h = P.h;
     int * seq = nullptr, * last = nullptr;                     // device copies of the sequence offsets [n_texts + 1] and the last-token rows [n_texts]
     if (!carve_workspace(ctx, [&](Carver & c) {
-            carve_tower(c, P.b, rows, n_texts, h, P.ff, P.proj, acts_f32(ctx, Tw));
+            carve_tower(c, P.b, nullptr, nullptr, rows, n_texts, h, P.ff, P.proj, acts_f32(ctx, Tw), 0, ctx->ws_alias);
             seq = c.take<int>((size_t)n_texts + 1);
             last = c.take<int>((size_t)n_texts);
         })) return false;

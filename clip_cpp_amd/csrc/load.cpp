@@ -637,6 +637,8 @@ clip_ctx * load_model(const char * fname, int verbosity, int device) {
         ctx->prune_last = !(ep && ep[0] == '0');
         const char * ec = getenv("CLIP_AMD_LNFOLD_CENTRE");
         ctx->ln_fold_centre = !(ec && ec[0] == '0');  // A/B: the r03 form, fp16(x gamma) without the per-row offset
+        const char * ea = getenv("CLIP_AMD_WS_ALIAS");
+        ctx->ws_alias = !(ea && ea[0] == '0');        // A/B: every activation buffer with storage of its own (forward.cpp carve_tower)
     }
     if (verbosity >= 1) printf("\n%s: %zu MB of HBM allocated for weights on device %d\n", "clip_model_load", ctx->weights_bytes / 1024 / 1024, device);
     return ctx;
@@ -670,7 +672,7 @@ clip_ctx * sibling_context(clip_ctx * owner, int index) {
     c->weights_borrowed = true;
     c->owner = owner;
     c->ln_fold = owner->ln_fold; c->ln_fold_force = owner->ln_fold_force; c->ln_fold_centre = owner->ln_fold_centre; c->prune_last = owner->prune_last;
-    c->f32_acts = owner->f32_acts;
+    c->f32_acts = owner->f32_acts; c->ws_alias = owner->ws_alias;
     c->resident_panels_on = owner->resident_panels_on;           // (the table itself is the OWNER's: forward.cpp resident_panels — read-only, same device)
     c->graphs_enabled = false;                                   // (its launches are captured into the OWNER's graphs)
     c->split_min = c->split_max = 0;                             // (a sibling never splits)

@@ -160,6 +160,7 @@ struct clip_ctx {
     bool ln_fold_force = false;      // CLIP_AMD_LNFOLD=2
     bool prune_last = true;          // the last layer's out-projection + FFN run on the pooled rows only (forward.cpp pooled_tail; CLIP_AMD_PRUNE_LAST=0: every row, for A/B)
     bool ln_fold_centre = true;      // the folded operand is built about the row's mean at the previous LayerNorm (kernels.h GemmParams::xg_mu; CLIP_AMD_LNFOLD_CENTRE=0: the r03 form, for A/B)
+    bool ws_alias = true;            // activation buffers that are never live together share storage (forward.cpp carve_tower; CLIP_AMD_WS_ALIAS=0: one buffer each, for A/B)
     bool ln_fold = true;             // LayerNorm folded into the GEMM epilogues for > 64 rows (CLIP_AMD_LNFOLD=0: the two-launch form, for A/B)
     // fp16 panels of one layer's block-quantised weights for the large-M GEMM (k_gemm8.hip); grown on demand, re-filled per layer
     clipamd::half_t * w16_panel = nullptr;
@@ -255,6 +256,14 @@ struct VisionStage {
     int Bc = 0;
     half_t * col = nullptr;
 };
+// Where carve_tower puts the buffers of a tower pass, as byte offsets from a 256-byte aligned start (pure arithmetic: no context, no device).
+// REGION is the storage that qkv, att, mid and col share when alias is on (then their offsets lie inside it); bytes 0 = no such buffer.
+struct TowerPlan {
+    enum { STATS, MU, X, XN, QKV, ATT, MID, COL, POOLED, EMB, XP, AP, XNP, MIDP, REGION, N };
+    size_t off[N] = {}, bytes[N] = {};
+    size_t total = 0;                // the end of the last buffer (and of its canary block in guard mode)
+};
+void tower_plan(TowerPlan & plan, int rows, int nseq, int h, int ff, int proj, bool f32, size_t col_halfs, bool alias);
 bool vision_stage_begin(clip_ctx * ctx, int Bc, VisionStage & st);
 bool vision_stage_patch(clip_ctx * ctx, const VisionStage & st, const void * imgs, int i0, int n);
 bool vision_stage_finish(clip_ctx * ctx, const VisionStage & st, float * d_out, bool normalize);

@@ -300,6 +300,17 @@ int clip_amd_test_ctx_state(struct clip_ctx * ctx, int which, int64_t * head, ui
     return (int)tab.size();
 }
 
+// Where forward.cpp carve_tower puts the activation buffers of a tower pass (model.h TowerPlan): arithmetic only, no context and no device.
+int clip_amd_test_tower_plan(int64_t rows, int nseq, int h, int ff, int proj, int f32, int64_t col_halfs, int alias, int64_t * off, int64_t * bytes, int cap,
+                             int64_t * total) {
+    if (rows < 1 || rows > INT32_MAX || nseq < 1 || nseq > rows || h < 16 || h % 16 || ff < 1 || proj < 1 || col_halfs < 0 || !off || !bytes || cap < 0) return -3;
+    TowerPlan pl;
+    tower_plan(pl, (int)rows, nseq, h, ff, proj, f32 != 0, (size_t)col_halfs, alias != 0);
+    for (int i = 0; i < TowerPlan::N && i < cap; i++) { off[i] = (int64_t)pl.off[i]; bytes[i] = (int64_t)pl.bytes[i]; }
+    if (total) *total = (int64_t)pl.total;
+    return TowerPlan::N;
+}
+
 // Extended form: qcols / qscale (EPI_F16 Q-scale path, clip.cpp:1363) and epilogue 5 = EPI_PATCH_F32 (patch embedding:
 // row m of the GEMM lands in output row (m / Np) * T + 1 + m % Np and gets pos[1 + m % Np] added; no bias; the class-token
 // rows (b * T) are left untouched).  For epilogue 5, y is [(M / Np) * T][N] and pos is [T][N].

@@ -696,6 +696,14 @@ int clip_amd_test_gemm_tile_ex(int64_t M, int64_t N, int64_t K, int quantised, i
  * that panel, 0 where there is none; may be NULL with panels_cap == 0.  Returns the number of table entries, or -3 (nothing written): ctx or
  * head NULL, which outside {0, 1}, panels_cap < 0, panels NULL with panels_cap > 0. */
 int clip_amd_test_ctx_state(struct clip_ctx * ctx, int which, int64_t * head, uint64_t * panels, int panels_cap);
+/* The layout of a tower pass's activation buffers in the workspace (forward.cpp carve_tower; pure host arithmetic, no context, no device) for rows token
+ * rows of nseq sequences, hidden width h, FFN width ff, projection proj, f32 != 0: float activations (f32 file), col_halfs: elements of the vision
+ * tower's im2col matrix (0: none), alias: the value of CLIP_AMD_WS_ALIAS.  off / bytes [min(cap, 15)]: byte offset from the 256-byte aligned start
+ * and size of, in this order, stats, mu, x, xn, qkv, att, mid, col, pooled, emb, xp, ap, xnp, midp and the region that qkv, att, mid and col
+ * share when alias != 0 (size 0 otherwise, as for col when col_halfs == 0).  total, if not NULL: the end of the last buffer.  With CLIP_AMD_GUARD=1
+ * in the environment the offsets include the canary blocks.  Returns 15, or -3 (nothing written) on arguments no tower can have. */
+int clip_amd_test_tower_plan(int64_t rows, int nseq, int h, int ff, int proj, int f32, int64_t col_halfs, int alias, int64_t * off, int64_t * bytes, int cap,
+                             int64_t * total);
 /* Average device time (microseconds, HIP events) of one GEMM shape through the production kernel on random
  * weights of ggml type `type`; < 0 on error.  Used by scripts/gemm_bench.py for kernel A/B work. */
 float clip_amd_bench_gemm(int type, int64_t N, int64_t K, int64_t M, int epilogue, int tile, int iters);
