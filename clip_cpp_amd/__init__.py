@@ -94,6 +94,7 @@ AMD_SYMBOLS = [
     "clip_amd_index_spread", "clip_amd_index_spread_device", "clip_amd_bench_spread",
     "clip_amd_index_linkage", "clip_amd_index_linkage_device", "clip_amd_bench_linkage", "clip_amd_bench_linkage_rounds",
     "clip_amd_test_index_linkage_rounds",
+    "clip_amd_index_extents", "clip_amd_index_extents_device", "clip_amd_bench_extents", "clip_amd_test_index_extents_route",
 ]
 
 _lib = None
@@ -308,6 +309,14 @@ def lib():
     L.clip_amd_bench_linkage.argtypes = [i32, i64, i32, i32, i32]
     L.clip_amd_bench_linkage_rounds.restype = i32
     L.clip_amd_bench_linkage_rounds.argtypes = []
+    L.clip_amd_index_extents.restype = i64
+    L.clip_amd_index_extents.argtypes = [vp, i64p, u64p, i64p, f32p, f32p, f32p, i64p]
+    L.clip_amd_index_extents_device.restype = C.c_bool
+    L.clip_amd_index_extents_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.clip_amd_bench_extents.restype = C.c_float
+    L.clip_amd_bench_extents.argtypes = [i32, i64, i32, i32, i32, i32]
+    L.clip_amd_test_index_extents_route.restype = i64
+    L.clip_amd_test_index_extents_route.argtypes = [vp, i32]
     L.clip_amd_test_index_linkage_rounds.restype = i32
     L.clip_amd_test_index_linkage_rounds.argtypes = [vp]
     L.clip_amd_index_spread.restype = i64
@@ -841,6 +850,10 @@ class Index:
     groups, and the sorted edge distances are the table of radius against number of groups.  The edge order (d, lo, hi) is total, so the
     tree is unique, exact and bit-reproducible.
 
+    extents(labels) measures any of these groupings: how far every row's own group reaches from it, and per group the minimax centre (the
+    member whose farthest other member is nearest: a cover for groups that have none), the radius around it and the diameter, the largest
+    distance inside the group.  It tells a tight burst of copies from a chain whose ends are far apart.
+
     remove(ids) marks rows as removed: no search, range_search or pairs returns them again, ids are not renumbered and len() keeps
     counting every id ever given (`live` = len minus the removed rows); compact() drops them from device memory and renumbers the
     survivors.  search and range_search take `allow`, a bool mask of length len(index) or an array of ids: only those rows (and of those
@@ -1360,6 +1373,63 @@ class Index:
                                                    C.c_void_p(d_hi or None), C.c_void_p(d_distances or None), C.c_void_p(d_count or None)):
             raise RuntimeError("clip_amd_index_linkage_device failed (see stderr)")
 
+    def _extents_labels(self, labels, words=None):
+        """labels as int64 [len]; ValueError for another length, or a label >= len on a row of the allowed set (words of _allow; None:
+        on any row), before the library is reached"""
+        size = len(self)
+        a = np.asarray(labels)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("labels must be integers, not %s" % a.dtype)
+        a = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+        if a.size != size:
+            raise ValueError("labels holds %d entries, the index %d rows" % (a.size, size))
+        checked = a if words is None else a[np.unpackbits(words.astype("<u8").view(np.uint8), bitorder="little")[:size].astype(np.bool_)]
+        if checked.size and int(checked.max()) >= size:
+            raise ValueError("labels holds %d: a label is negative (not a member) or an id of the index (0 ... %d)" % (int(checked.max()), size - 1))
+        return a
+
+    def extents(self, labels, allow=None):
+        """Extents of a labelling: (centre int64 [n], radius f32 [n], diameter f32 [n], reach f32 [n], far int64 [n]).  `labels` int64
+        [len]: row x is a member when it is eligible and labels[x] >= 0; its group is the members that carry its label (the labels of
+        components, modes, cut_linkage and spread's owner all qualify; a label must be < len and need not be a member of its group).
+        reach[x] is the largest distance (the distances and bits of `pairs`) from x to a member of its group and far[x] the member that
+        attains it, the lowest id among equals; 0 / -1 for the only member of a group.  centre[x] is the member c of x's group that
+        minimises (reach[c], c), radius[x] = reach[centre[x]] and diameter[x] the largest reach of the group, its largest pairwise
+        distance: equal across a group.  A row that is not a member gets -1 / +inf.  `allow` (bool mask [len] or ids): only those rows
+        are eligible; the result over them is that of an index that only ever held them.  ValueError for labels of another length, a
+        label >= len (on a row of `allow`, when it is given) or a malformed allow, before the library is reached.  Re-centring a k-centre cover:
+        owner = ix.spread(n)[2]; centre, radius = ix.extents(owner)[:2]."""
+        words, wp = self._allow(allow)
+        lab = self._extents_labels(labels, words)
+        n = lab.size
+        centre = np.empty(n, dtype=np.int64)
+        far = np.empty(n, dtype=np.int64)
+        radius = np.empty(n, dtype=np.float32)
+        diameter = np.empty(n, dtype=np.float32)
+        reach = np.empty(n, dtype=np.float32)
+        i64 = C.POINTER(C.c_int64)
+        if lib().clip_amd_index_extents(self._live(), lab.ctypes.data_as(i64), wp, centre.ctypes.data_as(i64), _fp(radius), _fp(diameter),
+                                        _fp(reach), far.ctypes.data_as(i64)) < 0:
+            raise RuntimeError("clip_amd_index_extents failed (see stderr)")
+        return centre, radius, diameter, reach, far
+
+    def extents_device(self, d_labels, d_centre, d_radius=None, d_diameter=None, d_reach=None, d_far=None, d_count=None, d_allow=None):
+        """extents on device pointers (ints): labels [len] int64 in (trusted: a label >= len makes its row no member); centre [len] int64,
+        radius / diameter / reach [len] f32, far [len] int64 and count [1] int64 (the groups with a member) out (0 / None: not wanted);
+        d_allow: uint64 words on the device (0 / None: every row); asynchronous on the context's stream."""
+        if not lib().clip_amd_index_extents_device(self._live(), C.c_void_p(d_labels or None), C.c_void_p(d_allow or None),
+                                                   C.c_void_p(d_centre or None), C.c_void_p(d_radius or None), C.c_void_p(d_diameter or None),
+                                                   C.c_void_p(d_reach or None), C.c_void_p(d_far or None), C.c_void_p(d_count or None)):
+            raise RuntimeError("clip_amd_index_extents_device failed (see stderr)")
+
+    def extents_route(self, route=0):
+        """Test hook: route 0 skips the tile pairs that hold no two rows of one group, route 1 computes them all (the same result);
+        returns the tile pairs the last extents call of this index computed"""
+        r = int(lib().clip_amd_test_index_extents_route(self._live(), int(route)))
+        if r < 0:
+            raise ValueError("route must be 0 or 1")
+        return r
+
     @staticmethod
     def _spread_args(n, radius, seeds):
         """(n, stop radius as the f32 the library compares with, seeds int64 [s]); radius None: never stop.  ValueError for a NaN and for
@@ -1644,6 +1714,12 @@ def bench_modes(dtype, n, dim, radius, link=None, copies=0, iters=3):
     many noisy copies (clip_amd_bench_modes); < 0 on error."""
     return float(lib().clip_amd_bench_modes(Index.DTYPES[dtype], int(n), int(dim), float(radius), float(radius if link is None else link), int(copies),
                                             int(iters)))
+
+
+def bench_extents(dtype, n, dim, group_size, sorted=True, iters=3):
+    """Microseconds per clip_amd_index_extents (host form) over bursts of group_size rows labelled by burst, the labels following the row
+    order (sorted) or scattered over the index (clip_amd_bench_extents); < 0 on error."""
+    return float(lib().clip_amd_bench_extents(Index.DTYPES[dtype], int(n), int(dim), int(group_size), int(bool(sorted)), int(iters)))
 
 
 def bench_linkage(dtype, n, dim, copies=0, iters=3):

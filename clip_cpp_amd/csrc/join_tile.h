@@ -16,6 +16,9 @@
 //                             skipped before anything is loaded, and the near condition tests the row's bit; pairs test the same mask
 //                             on the query side too (p.qmask: a removed row is neither i nor j) and skip a query tile without a set bit.
 //                             The distances still come from the same chain.
+//                             Tile predicate (template parameter Skip, argument skip; default: none, compiled to nothing): a tile that
+//                             survived the masks is skipped, before anything is loaded, when skip(row tile, query tile) says that no
+//                             pair of it can reach the ending (k_extents.hip: the two tiles hold no label in common).
 //   join_grid                 the tile counts of a launch and its grid: the resident workgroups, pairs in whole groups of 8
 // LDS: 41 KB (BN 16) / 72 KB (BN 128), dynamic; no scratch.
 #pragma once
@@ -56,8 +59,13 @@ __device__ __forceinline__ void tri_index(int64_t t, int64_t & a, int64_t & b) {
     b = t - x * (x + 1) / 2;
 }
 
-template <typename T, int WR, int WQ, int WQS, bool MASKED, typename Near>
-__device__ __forceinline__ void join_tiles(const JoinParams & p, Near && near) {
+// the default tile predicate of join_tiles: no tile is skipped, and nothing is compiled for it
+struct KeepEveryTile {
+    __device__ __forceinline__ bool operator()(int64_t, int64_t) const { return false; }
+};
+
+template <typename T, int WR, int WQ, int WQS, bool MASKED, typename Near, typename Skip = KeepEveryTile>
+__device__ __forceinline__ void join_tiles(const JoinParams & p, Near && near, Skip skip = Skip()) {
     constexpr int WRS = 4 / WQS;
     static_assert(WRS * WQS == 4 && WRS * WR * 16 == JOIN_BM, "four waves cover 128 rows");
     constexpr int BN = WQS * WQ * 16;
@@ -99,6 +107,7 @@ __device__ __forceinline__ void join_tiles(const JoinParams & p, Near && near) {
                 if ((mq[0] | mq[1] | mq[2] | mq[3]) == 0) continue;
             }
         }
+        if (skip(ti, tj)) continue;                            // the caller's predicate (row tile, query tile): nothing of this tile can matter
         Acc acc[WR][WQ];
 #pragma unroll
         for (int i = 0; i < WR; i++)

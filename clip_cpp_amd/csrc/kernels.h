@@ -441,6 +441,20 @@ const uint32_t * linkage_stat(const void * work, int64_t n);
 bool launch_linkage(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, float link, const uint32_t * mask, int * parent,
                     unsigned long long * key, void * work, int64_t * lo, int64_t * hi, float * distances, int64_t * count, hipStream_t stream);
 
+// Extents of a labelling over the same pairs (k_extents.hip): labels [n] i64 on the device; row x is a member when it is eligible (mask as
+// for launch_components) and 0 <= labels[x] < n.  Workspace: work [extents_work_bytes(n)] (initialised here; 24 bytes per row and 24 per
+// tile of 128 rows).  centre [n] i64: the member of the row's group that minimises (reach, id); radius / diameter / reach [n] f32 and far
+// [n] i64 (each may be NULL): the centre's reach, the largest reach of the group, the row's largest distance to a member of its group and
+// the member that attains it (lower id first among equal distances; 0 / -1 for the only member of a group); -1 / +inf for a row that is
+// not a member.  *count (may be NULL; zero it first) receives the number of groups with a member.  skip != 0: a tile pair whose label
+// ranges do not intersect is not computed (the same result, bit for bit); extents_tiles_computed(work): the tile pairs the last launch
+// computed (u64, device).  Everything on the device, n < 2^31.
+size_t extents_work_bytes(int64_t n);
+const unsigned long long * extents_tiles_computed(const void * work);
+bool launch_extents(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, const int64_t * labels, const uint32_t * mask,
+                    void * work, int skip, int64_t * centre, float * radius, float * diameter, float * reach, int64_t * far,
+                    unsigned long long * count, hipStream_t stream);
+
 // Farthest-first selection (k_spread.hip).  Workspaces: gap [n] f32, opos [n] i32, slot [n_slots] u64 (slot t: the key of the centre at
 // position t, 0 = empty).  init: zeroes the slots, sets gap / opos from the mask and writes the seeds' keys (seeds: device ids), or, with
 // n_seeds == 0, the lowest eligible id's into slot 0.  sweep: one pass over the gallery against the centres of slots first ... first +

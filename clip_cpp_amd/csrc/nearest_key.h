@@ -5,6 +5,8 @@
 //   fold_nearest              key = ordered_bits(d) << 32 | other id into nearest[x]: a 64-bit atomicMin behind a plain load (keys only fall:
 //                             a stale value is an upper bound, "my key >= what I read" skips the atomic safely).  The minimum of a set does
 //                             not depend on the order of the atomics.
+//   fold_farthest             the same turned around for k_extents.hip: a 64-bit atomicMax behind a plain load (keys only rise: a stale
+//                             value is a lower bound, "my key <= what I read" skips the atomic safely); 0 = no key
 //   forest_jump_kernel        one pass of pointer doubling, out[i] = in[in[i]] (a root points to itself)
 //   flatten_forest            ceil(log2 (n - 1)) such passes in launches of their own, between the two halves of parent [2 n]: every tree,
 //                             a path of n rows included, ends flat; returns the half that holds the roots
@@ -29,6 +31,11 @@ __device__ __forceinline__ float ordered_value(uint32_t u) { return __uint_as_fl
 
 __device__ __forceinline__ void fold_nearest(unsigned long long * nearest, int x, unsigned long long key) {
     if (key < nearest[x]) atomicMin(nearest + x, key);
+}
+
+// fold_nearest turned around: the maximum of the keys (0: no key yet).  Keys only rise, a stale value is a lower bound.
+__device__ __forceinline__ void fold_farthest(unsigned long long * farthest, int x, unsigned long long key) {
+    if (key > farthest[x]) atomicMax(farthest + x, key);
 }
 
 __global__ void __launch_bounds__(256) forest_jump_kernel(const int * __restrict__ in, int * __restrict__ out, int64_t n) {

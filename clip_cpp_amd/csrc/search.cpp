@@ -4,7 +4,7 @@
 // searches with query sets (the set fold of k_sets.hip in the finish's place), distinct searches (the pools of a search, then the near
 // bitmap and the walk of k_distinct.hip), compound queries (the placement and the scan of k_compound.hip in front of the same merge tree),
 // appending one index to another, the count -> lims -> scatter -> sort -> finish sequence of
-// range search and pairs (k_join.hip), connected components (the link -> flatten -> finish sequence of k_components.hip), density modes (k_modes.hip), the single-linkage tree (k_linkage.hip), farthest-first selection (k_spread.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
+// range search and pairs (k_join.hip), connected components (the link -> flatten -> finish sequence of k_components.hip), density modes (k_modes.hip), the single-linkage tree (k_linkage.hip), the extents of a labelling (k_extents.hip), farthest-first selection (k_spread.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
 // Replaces the usearch index of the reference's examples/image-search (build.cpp / search.cpp) with an exact search on the GPU.
 // Single owners: search_device_impl (the passes of a search: one ScanArgs per scan launch, whatever the selection), search_blocks and
 // query_block (the blocked host forms of stored-row queries), upload_allow / upload_groups / stage_inputs (a call's inputs on the device),
@@ -97,6 +97,10 @@ struct clip_amd_index {
     Buf lwork;                     // labels, per-root edges, round statistics and block counts (linkage_work_bytes)
     Buf louts;                     // host form: count (int64), lo + hi (int64), distances
     int linkage_rounds = 0;        // clip_amd_test_index_linkage_rounds: the rounds that ran in the last host-form call
+    // extents of a labelling
+    Buf ework;                     // member bitmap, label ranges, reach keys, per-label slots and i32 labels (extents_work_bytes)
+    Buf eouts;                     // host form: group count (u64), labels + centres + far ids (int64), radii, diameters, reaches
+    int extents_route = 0;         // clip_amd_test_index_extents_route: 0 tile skip on, 1 every tile pair computed
     // farthest-first selection
     Buf sgap;                      // [n] distance to the nearest centre so far (f32)
     Buf sopos;                     // [n] position of that centre (i32)
@@ -1064,6 +1068,70 @@ int64_t linkage_host(clip_amd_index * ix, float link, const uint64_t * allow, in
         dist[e] = h_dist[(size_t)order[(size_t)e]];
     }
     return m;
+}
+
+// Extents of a labelling on the device: d_labels [n] int64 in, centre and, where asked for, radius, diameter, reach and far out; d_count
+// (may be NULL): the number of groups with a member.  Queues the launches and returns; ix->n > 0.
+bool extents_impl(clip_amd_index * ix, const int64_t * d_labels, const uint32_t * d_allow, int64_t * d_centre, float * d_radius, float * d_diameter,
+                  float * d_reach, int64_t * d_far, unsigned long long * d_count, const char * fn) {
+    const uint32_t * mask = nullptr;
+    if (!effective_mask(ix, d_allow, mask) || !ensure(ix, ix->ework, extents_work_bytes(ix->n))) return false;
+    if (d_count) (void)hipMemsetAsync(d_count, 0, 8, stream_of(ix));
+    if (!launch_extents(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, d_labels, mask, ix->ework.p, ix->extents_route == 0, d_centre,
+                        d_radius, d_diameter, d_reach, d_far, d_count, stream_of(ix))) {
+        fprintf(stderr, "%s: launch failed\n", fn);
+        return false;
+    }
+    return true;
+}
+
+bool check_extents_args(const clip_amd_index * ix, const void * labels, const void * centre, const char * fn) {
+    if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+    if (!labels) { fprintf(stderr, "%s: labels is NULL\n", fn); return false; }
+    if (!centre) { fprintf(stderr, "%s: centre is NULL\n", fn); return false; }
+    return true;
+}
+
+// The host form: a member's label >= size is refused before anything is queued; then the labels go up, the outputs into their workspace
+// and out with the group count.  Returns that count or -1.
+int64_t extents_host(clip_amd_index * ix, const int64_t * labels, const uint64_t * allow, int64_t * centre, float * radius, float * diameter,
+                     float * reach, int64_t * far, const char * fn) {
+    if (ix->n == 0) return 0;
+    hipStream_t st = stream_of(ix);
+    const size_t n = (size_t)ix->n;
+    std::vector<uint64_t> live;                                // only read when rows were removed
+    if (ix->removed > 0) {
+        live.resize((size_t)search_allow_words(ix->n) / 2);
+        if (!stream_done(ix, fn, hipMemcpyAsync(live.data(), ix->store.live, live.size() * 8, hipMemcpyDeviceToHost, st))) return -1;
+    }
+    for (size_t x = 0; x < n; x++) {
+        if (labels[x] < (int64_t)n) continue;
+        if ((live.empty() || ((live[x >> 6] >> (x & 63)) & 1u)) && (!allow || ((allow[x >> 6] >> (x & 63)) & 1u))) {
+            fprintf(stderr, "%s: label %lld of row %zu outside 0 ... %zu: nothing computed\n", fn, (long long)labels[x], x, n - 1);
+            return -1;
+        }
+    }
+    const uint32_t * d_allow = nullptr;
+    if (!upload_allow(ix, allow, d_allow) || !ensure(ix, ix->eouts, 8 + n * 36)) return -1;
+    unsigned long long * d_count = (unsigned long long *)ix->eouts.p;
+    int64_t * d_labels = (int64_t *)((char *)ix->eouts.p + 8);
+    int64_t * d_centre = d_labels + n;
+    int64_t * d_far = d_centre + n;
+    float * d_radius = (float *)(d_far + n);
+    float * d_diameter = d_radius + n;
+    float * d_reach = d_diameter + n;
+    (void)hipMemcpyAsync(d_labels, labels, n * 8, hipMemcpyHostToDevice, st);
+    if (!extents_impl(ix, d_labels, d_allow, d_centre, radius ? d_radius : nullptr, diameter ? d_diameter : nullptr, reach ? d_reach : nullptr,
+                      far ? d_far : nullptr, d_count, fn))
+        return -1;
+    unsigned long long groups = 0;
+    (void)hipMemcpyAsync(&groups, d_count, 8, hipMemcpyDeviceToHost, st);
+    (void)hipMemcpyAsync(centre, d_centre, n * 8, hipMemcpyDeviceToHost, st);
+    if (radius) (void)hipMemcpyAsync(radius, d_radius, n * 4, hipMemcpyDeviceToHost, st);
+    if (diameter) (void)hipMemcpyAsync(diameter, d_diameter, n * 4, hipMemcpyDeviceToHost, st);
+    if (reach) (void)hipMemcpyAsync(reach, d_reach, n * 4, hipMemcpyDeviceToHost, st);
+    if (far) (void)hipMemcpyAsync(far, d_far, n * 8, hipMemcpyDeviceToHost, st);
+    return stream_done(ix, fn) ? (int64_t)groups : -1;
 }
 
 // reach of a key slot of k_spread.hip on the host (nearest_key.h's ordered_value)
@@ -2069,6 +2137,40 @@ bool clip_amd_index_linkage_device(struct clip_amd_index * ix, float link, const
     });
 }
 
+int64_t clip_amd_index_extents(struct clip_amd_index * ix, const int64_t * labels, const uint64_t * allow, int64_t * centre, float * radius,
+                               float * diameter, float * reach, int64_t * far) {
+    return guarded(__func__, (int64_t)-1, [&](const char * fn) -> int64_t {
+        if (!check_extents_args(ix, labels, centre, fn)) return -1;
+        (void)hipSetDevice(ix->device);
+        return extents_host(ix, labels, allow, centre, radius, diameter, reach, far, fn);
+    });
+}
+
+bool clip_amd_index_extents_device(struct clip_amd_index * ix, const int64_t * d_labels, const uint64_t * d_allow, int64_t * d_centre,
+                                   float * d_radius, float * d_diameter, float * d_reach, int64_t * d_far, int64_t * d_count) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_extents_args(ix, d_labels, d_centre, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        if (ix->n == 0) {
+            if (d_count) (void)hipMemsetAsync(d_count, 0, 8, stream_of(ix));
+            return true;
+        }
+        return extents_impl(ix, d_labels, (const uint32_t *)d_allow, d_centre, d_radius, d_diameter, d_reach, d_far, (unsigned long long *)d_count, fn);
+    });
+}
+
+int64_t clip_amd_test_index_extents_route(struct clip_amd_index * ix, int route) {
+    return guarded(__func__, (int64_t)-1, [&](const char * fn) -> int64_t {
+        if (!ix || route < 0 || route > 1) return -1;
+        ix->extents_route = route;
+        if (ix->n == 0 || !ix->ework.p) return 0;             // no call yet
+        (void)hipSetDevice(ix->device);
+        unsigned long long computed = 0;
+        if (!stream_done(ix, fn, hipMemcpyAsync(&computed, extents_tiles_computed(ix->ework.p), 8, hipMemcpyDeviceToHost, stream_of(ix)))) return -1;
+        return (int64_t)computed;
+    });
+}
+
 int64_t clip_amd_index_spread(struct clip_amd_index * ix, int64_t n_max, float stop_radius, const int64_t * seeds, int64_t n_seeds,
                               const uint64_t * allow, int64_t * centres, float * reach, int64_t * owner, float * owner_distance,
                               float * cover_radius) {
@@ -2283,6 +2385,34 @@ float clip_amd_bench_modes(int dtype, int64_t n, int dim, float radius, float li
             std::vector<int> density((size_t)n);
             auto call = [&]() { return modes_host(ix, radius, link, nullptr, labels.data(), parent.data(), pdist.data(), density.data(), fn) >= 0; };
             if (hipDeviceSynchronize() != hipSuccess || !call()) return -4.f;
+            return time_wall(iters, call);
+        });
+    });
+}
+
+float clip_amd_bench_extents(int dtype, int64_t n, int dim, int group_size, int sorted, int iters) {
+    return guarded(__func__, -4.f, [&](const char * fn) {
+        // bursts of group_size rows (launch_distinct_plant's row and group_size - 1 noisy copies), labelled by burst: row r carries the
+        // label r / group_size.  Not sorted: row r carries the label of row pi(r), pi a fixed permutation of the rows, so the groups keep
+        // their sizes but lie scattered over the index and every tile of 128 rows holds labels from the whole range (the time does not
+        // depend on which rows a group holds, only on where they lie)
+        return bench_on_gallery(dtype, n, dim, 0, iters, group_size >= 1, group_size > 1 ? group_size - 1 : PLANT_NONE, [&](clip_amd_index * ix, float *) {
+            std::vector<int64_t> labels((size_t)n), centre((size_t)n), far((size_t)n);
+            std::vector<float> radius((size_t)n), diameter((size_t)n), reach((size_t)n);
+            for (int64_t r = 0; r < n; r++) labels[(size_t)r] = r / group_size;
+            if (!sorted) {                                     // pi: an odd factor modulo a power of two >= n, walked until it lands below n
+                uint64_t m = 1;
+                while ((int64_t)m < n) m *= 2;
+                for (int64_t r = 0; r < n; r++) {
+                    uint64_t v = (uint64_t)r;
+                    do v = (v * 0x9E3779B1ull + 12345ull) & (m - 1); while ((int64_t)v >= n);
+                    labels[(size_t)r] = (int64_t)v / group_size;
+                }
+            }
+            auto call = [&]() {
+                return extents_host(ix, labels.data(), nullptr, centre.data(), radius.data(), diameter.data(), reach.data(), far.data(), fn) >= 0;
+            };
+            if (hipDeviceSynchronize() != hipSuccess) return -4.f;
             return time_wall(iters, call);
         });
     });

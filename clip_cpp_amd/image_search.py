@@ -6,10 +6,10 @@ build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.In
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N | -d R] [--distinct R] [--in PREFIX]... [--db DIR] <search text or /path/to/query/image>
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-n N] [--distinct R] [--in PREFIX]... [--db DIR] --like INDEXED/IMAGE/PATH
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N] [--in PREFIX]... [--db DIR] [--and TERM]... [--not TERM]... [--not-margin M] <query or --like PATH>
-    python -m clip_cpp_amd.image_search dedup  [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R] [--prune]
+    python -m clip_cpp_amd.image_search dedup  [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R] [--prune] [--extents]
     python -m clip_cpp_amd.image_search albums [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R] [--link T] [--min N] [-n COUNT]
     python -m clip_cpp_amd.image_search spread [-m MODEL] [-v N] [--db DIR] -n N [-d R] [--in PREFIX]... [--from INDEXED/IMAGE/PATH]...
-    python -m clip_cpp_amd.image_search groups [-m MODEL] [-v N] [--db DIR] -n N [--in PREFIX]... [--min M]
+    python -m clip_cpp_amd.image_search groups [-m MODEL] [-v N] [--db DIR] -n N [--in PREFIX]... [--min M] [--extents]
     python -m clip_cpp_amd.image_search levels [-m MODEL] [-v N] [--db DIR] [--in PREFIX]... [-n ROWS]
     python -m clip_cpp_amd.image_search neighbors [-m MODEL] [-v N] [--db DIR] [-n N]
     python -m clip_cpp_amd.image_search label  [-m MODEL] [-v N] [-t N] [--db DIR] [-n N] LABEL [LABEL ...]
@@ -31,6 +31,13 @@ groups separated by a blank line, and "main: %d groups, %d images".  `dedup --pr
 lowest id stays, the others leave the index (Index.remove + Index.compact) and images.paths, both files are rewritten as `update` rewrites
 them, and no image file on disk is touched; it prints the groups at verbosity > 0, then "main: %d removed, %d kept", and rewrites nothing
 when there is nothing to remove.
+`dedup --extents` and `groups --extents` measure the groups they print (Index.extents over the labels, one call): a group from a chain of
+near pairs may be a tight burst of copies or reach far from end to end, and its lowest id is only the first file on disk.  Every group is
+printed with its centre first, the member from which the farthest other member is nearest (the lowest id among equals), as
+"  %f %f %s": radius (the centre's distance to its farthest member), diameter (the largest distance between two members) and path; the
+other members follow in id order as "  %f %s", the distance to their farthest member.  The groups and their order are those without the
+flag, and the closing line ends with ", largest diameter %f" (`groups`: "; largest diameter %f").  `dedup --prune --extents` keeps each
+group's centre instead of its lowest id.  Without the flag both commands print exactly what they printed before.
 `albums` organises the database by content (Index.modes, one call; nothing is encoded): every image points to its nearest image of higher
 local density (density = the images within distance R of it, -d as in `dedup`; the parent is looked for within --link T, default R), so
 every tree is an album and its root, the most typical image, the cover.  It prints "albums:" at verbosity > 0, then the albums of at
@@ -116,6 +123,12 @@ MAX_K = 1024
 DEDUP_RADIUS = 0.05
 MAX_TERMS = 8       # terms of a compound search: the main query, every --and and every --not
 LEVEL_ROWS = 20     # rows of the `levels` table
+
+
+EXTENTS_HELP = ("  --extents: measure every group (Index.extents): its centre, the image from which the farthest other member is nearest, comes"
+                " first as `radius diameter path` (the distance from the centre to its farthest member, and the largest distance between two"
+                " members: a tight burst of copies has a small diameter, a chain of near pairs a large one); the other members follow with"
+                " the distance to their farthest member. The last line adds the largest diameter found.%s")
 
 
 def is_image_file_extension(path):
@@ -213,6 +226,8 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
                 return None
         elif dedup and a == "--prune":
             p["prune"] = True
+        elif (dedup or groups) and a == "--extents":
+            p["extents"] = True
         elif a in ("-h", "--help"):
             _help(build, p, dedup, update, neighbors, label, merge, match, albums, spread, groups, levels)
             sys.exit(0)
@@ -303,6 +318,8 @@ def _help(build, p, dedup=False, update=False, neighbors=False, label=False, mer
         else:
             print("  -n ROWS, --results ROWS: rows of the table, evenly spaced over the merges of the tree. Default: %d" % LEVEL_ROWS)
         print("  --in <prefix>: only images whose indexed path starts with <prefix> take part; may be repeated")
+        if groups:
+            print(EXTENTS_HELP % "")
     elif spread:
         print("Usage: python -m clip_cpp_amd.image_search spread [options] -n N")
         print("\nPicks N images of an index built by `build` that between them cover the collection: the first indexed image (or the --from")
@@ -393,6 +410,7 @@ def _help(build, p, dedup=False, update=False, neighbors=False, label=False, mer
         print("  --prune: de-duplicate the database: of every group only the first image (the lowest id) stays in %s and %s, both"
               " rewritten under temporary names and renamed into place; image files on disk are never touched. Prints the groups at"
               " verbosity > 0, then the number of images removed and kept" % (INDEX_FILE, PATHS_FILE))
+        print(EXTENTS_HELP % " With --prune the centre is the image that stays, not the lowest id.")
     elif update:
         print("Usage: python -m clip_cpp_amd.image_search update [options] dir/with/pictures [more/dirs]")
         print("\nBrings a database made by `build` in line with the disk: indexed paths that no longer exist are removed, image files under the")
@@ -938,6 +956,39 @@ def component_groups(labels, nearest_distance):
     return [list(zip(g.tolist(), dist[g].tolist())) for g in np.split(order, cuts) if g.size]
 
 
+def extent_groups(labels, centre, radius, diameter, reach, min_size=2, largest_first=False):
+    """The groups of Index.extents' output over `labels`: a list of (centre id, radius, diameter, [(id, distance to its farthest member),
+    ...] the other members in id order) over the groups of at least min_size members (the centre counts), in order of each group's lowest
+    id, or, largest_first, largest first and equal sizes in order of the lowest id.  Rows with centre -1 are members of no group."""
+    labels = np.asarray(labels, dtype=np.int64)
+    centre = np.asarray(centre, dtype=np.int64)
+    radius = np.asarray(radius, dtype=np.float32).astype(np.float64)
+    diameter = np.asarray(diameter, dtype=np.float32).astype(np.float64)
+    reach = np.asarray(reach, dtype=np.float32).astype(np.float64)
+    ids = np.flatnonzero(centre >= 0)
+    order = ids[np.argsort(labels[ids], kind="stable")]          # by group, ids ascending within one
+    cuts = np.flatnonzero(np.diff(labels[order])) + 1
+    found = [g for g in np.split(order, cuts) if g.size >= max(int(min_size), 1)]
+    found.sort(key=lambda g: (-g.size if largest_first else 0, int(g[0])))
+    out = []
+    for g in found:
+        c = int(centre[g[0]])
+        rest = g[g != c]
+        out.append((c, float(radius[c]), float(diameter[c]), list(zip(rest.tolist(), reach[rest].tolist()))))
+    return out
+
+
+def _print_extent_groups(found, image_paths):
+    """`groups --extents` / `dedup --extents`: every group with its centre first; returns the largest diameter (0 without a group)"""
+    for g, (c, radius, diameter, members) in enumerate(found):
+        if g:
+            print()
+        print("  %f %f %s" % (radius, diameter, image_paths[c]))
+        for i, d in members:
+            print("  %f %s" % (d, image_paths[i]))
+    return max([diameter for _, _, diameter, _ in found], default=0.0)
+
+
 def album_groups(labels, parent_distance, min_size=2):
     """The albums of Index.modes' output: a list of (cover id, [(id, distance to its parent), ...] the other members in id order) over the
     albums of at least min_size rows (the cover counts), largest first, equal sizes in order of the cover's id.  Rows with label -1 are in
@@ -1100,7 +1151,8 @@ def level_rows(size, d_sorted_lo, d_sorted_hi, d, rows=LEVEL_ROWS):
 
 
 def _load_tree(p, command):
-    """What `groups` and `levels` share: (paths, eligible or None, (lo, hi, d)) of the database's tree, or None after a message"""
+    """What `groups` and `levels` share: (paths, eligible or None, (lo, hi, d), extents) of the database's tree, or None after a message;
+    extents: None, or with `groups --extents` (labels,) + Index.extents(labels) of the cut into -n groups"""
     import clip_cpp_amd
     if _refuse_gridded(p["db"], command):
         return None
@@ -1121,9 +1173,13 @@ def _load_tree(p, command):
         return None
     index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
     edges = index.linkage(allow=allow)
+    extents = None
+    if p.get("extents"):
+        labels = clip_cpp_amd.cut_linkage(len(image_paths), *edges, n_groups=p["results"], eligible=allow)
+        extents = (labels,) + index.extents(labels, allow=allow)
     index.close()
     clip.close()
-    return image_paths, allow, edges
+    return image_paths, allow, edges, extents
 
 
 def groups(argv):
@@ -1134,17 +1190,23 @@ def groups(argv):
     loaded = _load_tree(p, "groups")
     if loaded is None:
         return 1
-    image_paths, allow, (lo, hi, d) = loaded
+    image_paths, allow, (lo, hi, d), extents = loaded
     found, kept, cut = tree_groups(len(image_paths), lo, hi, d, p["results"], allow, p["min_size"])
     if p["verbose"] > 0:
         print("groups:")
-    for g, members in enumerate(found):
-        if g:
-            print()
-        for i, dist in members:
-            print("  %f %s" % (dist, image_paths[i]))
-    print("main: %d groups, %d of them with at least %d images, %d images in those; longest link kept %f, cut at %f"
-          % (p["results"], len(found), max(p["min_size"], 1), sum(len(g) for g in found), kept, cut))
+    closing = ("main: %d groups, %d of them with at least %d images, %d images in those; longest link kept %f, cut at %f"
+               % (p["results"], len(found), max(p["min_size"], 1), sum(len(g) for g in found), kept, cut))
+    if extents is not None:                        # the same groups in the same order, each with its centre first
+        labels, centre, radius, diameter, reach, _ = extents
+        closing += "; largest diameter %f" % _print_extent_groups(
+            extent_groups(labels, centre, radius, diameter, reach, p["min_size"], largest_first=True), image_paths)
+    else:
+        for g, members in enumerate(found):
+            if g:
+                print()
+            for i, dist in members:
+                print("  %f %s" % (dist, image_paths[i]))
+    print(closing)
     sys.stdout.flush()
     return 0
 
@@ -1157,7 +1219,7 @@ def levels(argv):
     loaded = _load_tree(p, "levels")
     if loaded is None:
         return 1
-    image_paths, allow, (lo, hi, d) = loaded
+    image_paths, allow, (lo, hi, d), _ = loaded
     table = level_rows(len(image_paths), lo, hi, d, p["results"])
     if p["verbose"] > 0:
         print("levels:")
@@ -1189,24 +1251,35 @@ def dedup(argv):
     prune = p.get("prune", False)                  # (the key exists only when --prune was given)
     labels, nearest, _ = index.components(p["max_distance"])
     groups = component_groups(labels, nearest)
+    found, tail = None, ""
+    if p.get("extents"):                           # the same groups in the same order, each with its centre first
+        centre, radius, diameter, reach, _ = index.extents(labels)
+        found = extent_groups(labels, centre, radius, diameter, reach, 2)
+        tail = ", largest diameter %f" % max([g[2] for g in found], default=0.0)
     if p["verbose"] > 0 or not prune:
         if p["verbose"] > 0:
             print("duplicate groups:")
-        for g, members in enumerate(groups):
-            if g:
-                print()
-            for i, d in members:
-                print("  %f %s" % (d, image_paths[i]))
+        if found is not None:
+            _print_extent_groups(found, image_paths)
+        else:
+            for g, members in enumerate(groups):
+                if g:
+                    print()
+                for i, d in members:
+                    print("  %f %s" % (d, image_paths[i]))
     if prune:
-        removed = [i for members in groups for i, _ in members[1:]]      # every member but the group's lowest id
+        if found is not None:
+            removed = sorted(i for _, _, _, members in found for i, _ in members)      # every member but the group's centre
+        else:
+            removed = [i for members in groups for i, _ in members[1:]]      # every member but the group's lowest id
         if removed:
             gone = set(removed)
             index.remove(removed)
             index.compact()
             _write_db(p, index, [path for i, path in enumerate(image_paths) if i not in gone])
-        print("main: %d removed, %d kept" % (len(removed), len(image_paths) - len(removed)))
+        print("main: %d removed, %d kept%s" % (len(removed), len(image_paths) - len(removed), tail))
     else:
-        print("main: %d groups, %d images" % (len(groups), sum(len(m) for m in groups)))
+        print("main: %d groups, %d images%s" % (len(groups), sum(len(m) for m in groups), tail))
     sys.stdout.flush()
     index.close()
     clip.close()

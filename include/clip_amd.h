@@ -550,6 +550,47 @@ int clip_amd_bench_linkage_rounds(void);
 /* The rounds that did work in the index's last clip_amd_index_linkage (host form): sweeps over the pairs that ran; -1 for a NULL index.
  * Used by scripts/linkage_bench.py and tests/. */
 int clip_amd_test_index_linkage_rounds(struct clip_amd_index * ix);
+/* Extents of a labelling: given one label per row (from clip_amd_index_components, a cut of the linkage tree, clip_amd_index_modes, the
+ * owner of clip_amd_index_spread, or anything else), how far every row's own group reaches from it, and for every group its minimax
+ * centre, its radius and its diameter.  It tells a tight burst of copies from a chain whose two ends are far apart, and gives every
+ * group a cover: the member from which the farthest other member is nearest.
+ * E is the set of eligible rows (live and set in allow, layout as live_mask, NULL = every live row); for a pair {x, y} of E, d(x, y) is
+ * the distance clip_amd_index_pairs reports for (min, max), the same bits from the same chain for every stored dtype.  A pair whose
+ * distance is NaN is not a pair, as in pairs.  Every comparison is in f32 on those bits.
+ * labels [size] int64.  Row x is a MEMBER when x is in E and labels[x] >= 0.  Every member's label must be < size (the labels of
+ * components, modes, a tree cut and spread's owner are); the label need not be a member of its own group, or eligible.  G(x) is the set
+ * of members that carry x's label.
+ * reach [size] f32: the maximum of d(x, y) over y in G(x), y != x.  far [size] int64: the y that attains it, the lowest id among equals.
+ * The only member of a group (and a member without a pair) gets reach 0 and far -1.
+ * centre [size] int64: the member c of G(x) that minimises (reach[c], c).  radius [size] f32: reach[centre[x]].  diameter [size] f32: the
+ * maximum of reach over G(x), which is the largest pairwise distance in the group.  These three are equal across a group; they are
+ * written per row, so the output is O(size) and needs no table of groups.
+ * A row that is not a member gets -1 for the ids and +INFINITY for the floats.  Every output but centre may be NULL.
+ * The host form returns the number of groups with at least one member (0 for an empty index: nothing is written; -1 on error); the
+ * device form writes it to d_count (int64, may be NULL).  Results are bit-identical run to run, however rows were split across add calls
+ * and across save / load, and do not depend on the order of any atomic (every output is a maximum or minimum of integer keys; there is
+ * no float sum); over E they are those of an index to which only the rows of E were ever added (ids and labels mapped in order).
+ * -1 / false with a message on stderr, nothing launched and no output written, for a NULL index, labels or centre and, in the host form,
+ * for a member whose label is >= size.
+ * Host form: host arrays, synchronous on the ctx stream.  Device form: labels, allow (both trusted; a row whose label is >= size is
+ * treated as not a member) and the outputs in HBM, asynchronous on the ctx stream, synchronises with nothing on the host.
+ * Cost: one sweep over the tile pairs (128 x 128 rows) that can hold two rows of one group: a tile pair is skipped when the label ranges
+ * of its two tiles do not intersect, so labels that follow the row order cost little more than the diagonal, and shuffled labels one
+ * sweep over all pairs of members.  Device memory beyond the index: 24 bytes per row (the host form 36 more for the labels and its
+ * results). */
+int64_t clip_amd_index_extents(struct clip_amd_index * ix, const int64_t * labels, const uint64_t * allow, int64_t * centre, float * radius,
+                               float * diameter, float * reach, int64_t * far);
+bool clip_amd_index_extents_device(struct clip_amd_index * ix, const int64_t * d_labels, const uint64_t * d_allow, int64_t * d_centre,
+                                   float * d_radius, float * d_diameter, float * d_reach, int64_t * d_far, int64_t * d_count);
+/* Average wall time (microseconds) of one clip_amd_index_extents (host form, all five outputs) over n rows in bursts of group_size (a row
+ * and group_size - 1 noisy copies, as clip_amd_bench_search_distinct plants them), row r labelled r / group_size; sorted == 0: row r
+ * carries the label of row pi(r) instead, pi a fixed permutation, so the groups keep their sizes but lie scattered over the index;
+ * < 0 on error.  Used by scripts/extents_bench.py. */
+float clip_amd_bench_extents(int dtype, int64_t n, int dim, int group_size, int sorted, int iters);
+/* Test hook: route 0 (the default) skips the tile pairs whose label ranges do not intersect, route 1 computes every tile pair of members;
+ * the results are the same, bit for bit.  Returns the number of tile pairs the index's last clip_amd_index_extents call (either form; the
+ * stream is waited for) computed, 0 before the first; -1 for a NULL index or another route.  Used by tests/. */
+int64_t clip_amd_test_index_extents_route(struct clip_amd_index * ix, int route);
 /* Farthest-first selection (greedy k-center): n_max rows that between them cover the index, each picked as the row farthest from
  * everything chosen before it.  Every prefix of the result is a 2-approximate k-center solution, and reach[t] is the coverage radius of
  * the prefix before position t, so one call gives the table of "how many rows" against "how far is everything else".
