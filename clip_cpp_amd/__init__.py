@@ -94,6 +94,7 @@ AMD_SYMBOLS = [
     "clip_amd_index_spread", "clip_amd_index_spread_device", "clip_amd_bench_spread",
     "clip_amd_index_linkage", "clip_amd_index_linkage_device", "clip_amd_bench_linkage", "clip_amd_bench_linkage_rounds",
     "clip_amd_test_index_linkage_rounds",
+    "clip_amd_index_linkage_core", "clip_amd_index_linkage_core_device", "clip_amd_bench_linkage_core", "clip_amd_bench_linkage_core_parts",
     "clip_amd_index_extents", "clip_amd_index_extents_device", "clip_amd_bench_extents", "clip_amd_test_index_extents_route",
 ]
 
@@ -305,6 +306,14 @@ def lib():
     L.clip_amd_index_linkage.argtypes = [vp, C.c_float, u64p, i64p, i64p, f32p]
     L.clip_amd_index_linkage_device.restype = C.c_bool
     L.clip_amd_index_linkage_device.argtypes = [vp, C.c_float, vp, vp, vp, vp, vp]
+    L.clip_amd_index_linkage_core.restype = i64
+    L.clip_amd_index_linkage_core.argtypes = [vp, i32, C.c_float, u64p, i64p, i64p, f32p, f32p]
+    L.clip_amd_index_linkage_core_device.restype = C.c_bool
+    L.clip_amd_index_linkage_core_device.argtypes = [vp, i32, C.c_float, vp, vp, vp, vp, vp, vp]
+    L.clip_amd_bench_linkage_core.restype = C.c_float
+    L.clip_amd_bench_linkage_core.argtypes = [i32, i64, i32, i32, i32, i32]
+    L.clip_amd_bench_linkage_core_parts.restype = None
+    L.clip_amd_bench_linkage_core_parts.argtypes = [f32p]
     L.clip_amd_bench_linkage.restype = C.c_float
     L.clip_amd_bench_linkage.argtypes = [i32, i64, i32, i32, i32]
     L.clip_amd_bench_linkage_rounds.restype = i32
@@ -1373,6 +1382,48 @@ class Index:
                                                    C.c_void_p(d_hi or None), C.c_void_p(d_distances or None), C.c_void_p(d_count or None)):
             raise RuntimeError("clip_amd_index_linkage_device failed (see stderr)")
 
+    @staticmethod
+    def _core_k(k):
+        """k of linkage_core as an int; ValueError outside 0 ... 1024, before any call"""
+        k = int(k)
+        if k < 0 or k > 1024:
+            raise ValueError("k = %d outside 0 ... 1024" % k)
+        return k
+
+    def linkage_core(self, k, link=None, allow=None):
+        """The mutual-reachability tree (robust single linkage): (lo int64 [e], hi int64 [e], w f32 [e], core f32 [len]).  core[x] is the
+        distance from x to its k-th nearest other eligible row, the bits search_ids(x, k, exclude_self=True, allow=...) reports (-inf for
+        k = 0, inf with fewer than k other rows and for every row that is not eligible); w(x, y) = max(d(x, y), core[x], core[y]); the
+        edges are the minimum spanning forest of the graph "w <= link" under the order (w, lo, hi), sorted by it.  A stray row between two
+        dense groups has a large core distance, so it no longer chains them together.  k = 0 is `linkage`.  cut_linkage(..., radius=R)
+        gives DBSCAN* at R with min_pts = k + 1: the rows with core <= R labelled as components(R, allow=core <= R) labels them, every
+        other eligible row on its own; cut_linkage_sized picks the radius from a number of groups.  ValueError for a k outside 0 ... 1024,
+        a NaN link or a malformed allow."""
+        k = self._core_k(k)
+        link = self._linkage_link(link)
+        cap = max(len(self) - 1, 1)
+        words, wp = self._allow(allow)
+        lo = np.empty(cap, dtype=np.int64)
+        hi = np.empty(cap, dtype=np.int64)
+        w = np.empty(cap, dtype=np.float32)
+        core = np.empty(max(len(self), 1), dtype=np.float32)
+        i64 = C.POINTER(C.c_int64)
+        m = lib().clip_amd_index_linkage_core(self._live(), k, link, wp, lo.ctypes.data_as(i64), hi.ctypes.data_as(i64), _fp(w), _fp(core))
+        if m < 0:
+            raise RuntimeError("clip_amd_index_linkage_core failed (see stderr)")
+        return lo[:m].copy(), hi[:m].copy(), w[:m].copy(), core[:len(self)].copy()
+
+    def linkage_core_device(self, k, d_lo, d_hi, d_weights, d_count, d_core=None, link=None, d_allow=None):
+        """linkage_core on device pointers (ints): lo [len - 1] int64, hi [len - 1] int64, weights [len - 1] f32, count [1] int64 and,
+        if wanted, core [len] f32; the same edges as the host form in an order that is not specified but the same run to run; d_allow:
+        uint64 words on the device (0 / None: every row); asynchronous on the context's stream."""
+        k = self._core_k(k)
+        link = self._linkage_link(link)
+        if not lib().clip_amd_index_linkage_core_device(self._live(), k, link, C.c_void_p(d_allow or None), C.c_void_p(d_lo or None),
+                                                        C.c_void_p(d_hi or None), C.c_void_p(d_weights or None), C.c_void_p(d_core or None),
+                                                        C.c_void_p(d_count or None)):
+            raise RuntimeError("clip_amd_index_linkage_core_device failed (see stderr)")
+
     def _extents_labels(self, labels, words=None):
         """labels as int64 [len]; ValueError for another length, or a label >= len on a row of the allowed set (words of _allow; None:
         on any row), before the library is reached"""
@@ -1704,6 +1755,46 @@ def cut_linkage(size, lo, hi, d, radius=None, n_groups=None, eligible=None):
     return labels
 
 
+def cut_linkage_sized(size, lo, hi, d, n_groups, min_size=2, eligible=None):
+    """(labels, radius): the cut of a tree of Index.linkage or Index.linkage_core at the largest of its distances at which it has exactly
+    n_groups groups of at least min_size rows; labels as cut_linkage(..., radius=radius) gives them (smaller groups and single rows keep
+    their own labels: with a tree of linkage_core those are the rows left unfiled).  One union-find sweep over the sorted edges, the
+    count read at the end of every run of equal distances.  ValueError, naming the counts that do occur, when no distance gives exactly
+    n_groups; for the rest as cut_linkage."""
+    size, n_groups, min_size = int(size), int(n_groups), max(int(min_size), 1)
+    labels = cut_linkage(size, lo, hi, d, eligible=eligible)      # (the checks of the edges)
+    lo = np.ascontiguousarray(lo, dtype=np.int64).reshape(-1)
+    hi = np.ascontiguousarray(hi, dtype=np.int64).reshape(-1)
+    d = np.ascontiguousarray(d, dtype=np.float32).reshape(-1)
+    order = np.lexsort((hi, lo, d))
+    los, his, ds = lo[order].tolist(), hi[order].tolist(), d[order]
+    parent, size_of = list(range(size)), [1] * size
+    big = int(np.count_nonzero(labels >= 0)) if min_size == 1 else 0
+    seen, best = set(), None
+    for t in range(len(los)):
+        a, b = los[t], his[t]
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        while parent[b] != b:
+            parent[b] = parent[parent[b]]
+            b = parent[b]
+        if a != b:
+            if a > b:
+                a, b = b, a
+            big += (size_of[a] + size_of[b] >= min_size) - (size_of[a] >= min_size) - (size_of[b] >= min_size)
+            parent[b] = a
+            size_of[a] += size_of[b]
+        if t + 1 == len(los) or ds[t + 1] != ds[t]:
+            seen.add(big)
+            if big == n_groups:
+                best = ds[t]
+    if best is None:
+        raise ValueError("no distance of the tree gives %d groups of at least %d rows; the counts that occur: %s"
+                         % (n_groups, min_size, ", ".join(str(c) for c in sorted(seen)) or "none"))
+    return cut_linkage(size, lo, hi, d, radius=best, eligible=eligible), float(best)
+
+
 def bench_components(dtype, n, dim, radius, iters=3):
     """Microseconds per clip_amd_index_components (host form) over the seeded rows of bench_range (clip_amd_bench_components); < 0 on error."""
     return float(lib().clip_amd_bench_components(Index.DTYPES[dtype], int(n), int(dim), float(radius), int(iters)))
@@ -1727,6 +1818,17 @@ def bench_linkage(dtype, n, dim, copies=0, iters=3):
     (clip_amd_bench_linkage); a time < 0 on error."""
     us = float(lib().clip_amd_bench_linkage(Index.DTYPES[dtype], int(n), int(dim), int(copies), int(iters)))
     return us, int(lib().clip_amd_bench_linkage_rounds())
+
+
+def bench_linkage_core(dtype, n, dim, k, copies=0, iters=3):
+    """Microseconds per call, all on one index in one run, interleaved (clip_amd_bench_linkage_core): a dict with linkage_core (host form,
+    the whole tree), knn_graph (k), linkage, core_column (the neighbour search with its device-side sink alone), rounds and
+    linkage_rounds (the rounds that did work in either tree); linkage_core < 0 on error."""
+    us = float(lib().clip_amd_bench_linkage_core(Index.DTYPES[dtype], int(n), int(dim), int(k), int(copies), int(iters)))
+    parts = np.zeros(5, dtype=np.float32)
+    lib().clip_amd_bench_linkage_core_parts(_fp(parts))
+    return dict(linkage_core=us, knn_graph=float(parts[0]), linkage=float(parts[1]), core_column=float(parts[2]), rounds=int(parts[3]),
+                linkage_rounds=int(parts[4]))
 
 
 def bench_spread(dtype, n, dim, n_max, copies=0, iters=3):

@@ -9,17 +9,28 @@
 // is live when both say that work may be left (hooked > 0, roots > 1; round 0 always), and every kernel of a round that is not live exits
 // at once, the tile sweep included (the flatten passes, shared code, then only run over the forest of the last live round again).
 //
+// The mutual-reachability tree (clip_amd_index_linkage_core; core != NULL in launch_linkage) is the same rounds over the weight
+// w(x, y) = max(d(x, y), core[x], core[y]) in the place of d, core one f32 per row (launch_linkage_core writes it from the finished k-NN
+// results of a query block, on the device).  w is a maximum of three f32 values, none a NaN: exact.  The order (w, lo, hi) is total too,
+// but under it ties are the rule: every row closer to x than core[x] is at the same weight from x.
+//
 // Kernels of a round:
 //   linkage_outward_kernel<T> join_tiles (pairs: 128 x 128 tiles, row tile >= query tile, the masks and the score chain of pairs) at `link`
 //                             (may be +inf).  A near pair (a, b) whose labels differ folds (ordered_bits(d) << 32 | b) into key[a] and the
 //                             mirror into key[b]: fold_nearest, the minimum of a set.  The labels are loaded once per fragment: the query's
 //                             when the lane's query column changes, the four rows of a lane's fragment in one 16-byte load.  The query
 //                             side's minimum is kept in a register and folded when the column changes.
+//                             CORE instantiation: the core distances are loaded exactly where the labels are (the query's when the column
+//                             changes, the fragment's four in one 16-byte load next to the labels: both arrays are padded to whole groups
+//                             of four rows); the labels are tested first, then w is formed and ordered_bits(w) is folded.  The tile loop
+//                             kept d <= link, which w <= link needs but does not give: the ending tests w <= link itself.
 //   linkage_min_kernel        cmin[comp[x]] = min of the ordered distance of key[x]: 32-bit atomicMin
 //   linkage_edge_kernel       a later launch, so cmin is final: of the rows that attain it, cedge[comp[x]] = min of (lo << 32 | hi), 64-bit
 //                             atomicMin.  The smallest outgoing edge (d, lo, hi) of a component is among these candidates: at its endpoint x
 //                             inside, key[x] = (d, lowest outside id at d), and a lower outside id at d than the edge's own would give a
 //                             smaller (lo, hi) with the same x.  Every candidate is an outgoing edge, so the minimum is that edge.
+//                             With core distances the argument is the same with w for d: it uses only that key[x] is the minimum of
+//                             (weight, outside id) over the outgoing edges at x and that the edge order is total, not what the weight is.
 //   linkage_hook_kernel       root r with an edge: t = the component at the other end.  parent[r] = t, unless t took the same edge (the only
 //                             cycles a total order allows are these mutual picks) and r < t: then r stays the root.  A root that is hooked
 //                             is never a root again, so its cmin / cedge hold the edge it brought for good: every tree edge is stored once,
@@ -32,6 +43,11 @@
 // A launch reads another workgroup's data only if an earlier launch wrote it (the load ahead of an atomicMin is only an upper bound, as in
 // fold_nearest): no waits, flags or fences inside a launch.  Plain launches on the caller's stream; the tile kernel's LDS is join_tile.h's
 // 72 KB; no scratch.
+// Registers of the CORE instantiations (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; profiles/linkage_kernel_resources.txt),
+// unmasked / masked: fp16 200 / 215 VGPRs, f32 200 / 215, i8 202 / 219, each with 128 AGPRs; scratch 0 bytes per lane and no VGPR spill in
+// any of the six (the masked ones park 12 / 12 / 16 SGPRs in VGPR lanes, as the masked plain ones park 8 / 8 / 12); one wave per SIMD, one
+// workgroup per CU, as before.  The plain instantiations keep their registers (196 / 209, i8 196 / 213) and their instructions: next to
+// the parent's assembly only the offset of one hidden kernel argument differs, which lies behind the new pointer.
 
 #include "join_tile.h"
 #include "nearest_key.h"
@@ -56,34 +72,56 @@ __global__ void __launch_bounds__(256) linkage_init_kernel(int * __restrict__ co
     cedge[i] = NO_KEY;
 }
 
-template <typename T, bool MASKED>
+template <typename T, bool MASKED, bool CORE>
 __global__ void __launch_bounds__(JOIN_THREADS) linkage_outward_kernel(const JoinParams p, const uint32_t * __restrict__ stat, int round,
-                                                                       const int * __restrict__ comp, unsigned long long * key) {
+                                                                       const int * __restrict__ comp, unsigned long long * key,
+                                                                       const float * __restrict__ core) {
     if (!round_live(stat, round)) return;
     int64_t col = -1, rbase = -1;                              // the query column whose minimum is held; the four rows whose labels are
     int clab = 0;
     unsigned long long ckey = NO_KEY;
     i4 rlab = {0, 0, 0, 0};
+    float ccore = 0.0f;                                        // CORE: the core distances, held exactly as the labels are
+    f4 rcore = {0.0f, 0.0f, 0.0f, 0.0f};
     join_tiles<T, 4, 4, 2, MASKED>(p, [&](int64_t qi, int64_t row, float d) {                  // qi < row
         if (qi != col) {
             if (ckey != NO_KEY) fold_nearest(key, (int)col, ckey);
             col = qi;
             ckey = NO_KEY;
             clab = comp[qi];
+            if constexpr (CORE) ccore = core[qi];
         }
         if ((row & ~(int64_t)3) != rbase) {
             rbase = row & ~(int64_t)3;
             rlab = *(const i4 *)(comp + rbase);
+            if constexpr (CORE) rcore = *(const f4 *)(core + rbase);
         }
         const int sub = (int)(row & 3);
         const int lab = sub == 0 ? rlab[0] : sub == 1 ? rlab[1] : sub == 2 ? rlab[2] : rlab[3];
         if (lab == clab) return;
-        const unsigned long long hi_bits = (unsigned long long)ordered_bits(d) << 32;
+        float w = d;
+        if constexpr (CORE) {                                  // the tile loop kept d <= link, which w <= link needs but does not give
+            const float rc = sub == 0 ? rcore[0] : sub == 1 ? rcore[1] : sub == 2 ? rcore[2] : rcore[3];
+            w = fmaxf(d, fmaxf(ccore, rc));                    // (no operand is a NaN: exact, whatever the order)
+            if (!(w <= p.radius)) return;
+        }
+        const unsigned long long hi_bits = (unsigned long long)ordered_bits(w) << 32;
         const unsigned long long kq = hi_bits | (unsigned)row;
         if (kq < ckey) ckey = kq;
         fold_nearest(key, (int)row, hi_bits | (unsigned)qi);
     });
     if (ckey != NO_KEY) fold_nearest(key, (int)col, ckey);
+}
+
+// The core column of the mutual-reachability tree from a query block's finished k-NN results (dist [m][k], sorted): core[q0 + q] = the
+// k-th distance of an eligible row, +inf for every other row.  dist NULL: `value` in the place of the k-th distance.
+__global__ void __launch_bounds__(256) linkage_core_kernel(const float * __restrict__ dist, int64_t q0, int m, int k, float value,
+                                                           const uint32_t * __restrict__ mask, float * __restrict__ core) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= m) return;
+    const int64_t x = q0 + q;
+    const bool in = !mask || ((mask[x >> 5] >> (int)(x & 31)) & 1u);
+    core[x] = !in ? INFINITY : dist ? dist[(size_t)q * k + k - 1] : value;
 }
 
 __global__ void __launch_bounds__(256) linkage_min_kernel(const uint32_t * __restrict__ stat, int round, const int * __restrict__ comp,
@@ -214,12 +252,13 @@ __global__ void __launch_bounds__(256) linkage_emit_kernel(const int * __restric
     dist[pos] = ordered_value(cmin[i]);
 }
 
-template <typename T, bool MASKED>
-bool launch_outward_m(JoinParams p, const uint32_t * stat, int round, const int * comp, unsigned long long * key, hipStream_t stream) {
+template <typename T, bool MASKED, bool CORE>
+bool launch_outward_m(JoinParams p, const uint32_t * stat, int round, const int * comp, unsigned long long * key, const float * core,
+                      hipStream_t stream) {
     static unsigned long long lds_done = 0;
-    const int64_t grid = join_grid(p, linkage_outward_kernel<T, MASKED>, JOIN_BM, lds_done);
-    hipLaunchKernelGGL((linkage_outward_kernel<T, MASKED>), dim3((unsigned)grid), dim3(JOIN_THREADS), (size_t)(JOIN_BM + JOIN_BM) * JOIN_LROW, stream, p,
-                       stat, round, comp, key);
+    const int64_t grid = join_grid(p, linkage_outward_kernel<T, MASKED, CORE>, JOIN_BM, lds_done);
+    hipLaunchKernelGGL((linkage_outward_kernel<T, MASKED, CORE>), dim3((unsigned)grid), dim3(JOIN_THREADS), (size_t)(JOIN_BM + JOIN_BM) * JOIN_LROW,
+                       stream, p, stat, round, comp, key, core);
     return hipGetLastError() == hipSuccess;
 }
 
@@ -235,6 +274,13 @@ int linkage_rounds(int64_t n) {
 }
 
 // work: comp [n rounded up to 4] i32 (first: its 16-byte loads), cedge [n] u64, bsum [blocks of 256 rows] i64, stat, cmin [n] u32
+size_t linkage_core_bytes(int64_t n) { return (size_t)comp_rows(n) * 4; }
+
+void launch_linkage_core(const float * dist, int64_t q0, int m, int k, float value, const uint32_t * mask, float * core, hipStream_t stream) {
+    if (m <= 0) return;
+    hipLaunchKernelGGL(linkage_core_kernel, dim3((unsigned)(((int64_t)m + 255) / 256)), dim3(256), 0, stream, dist, q0, m, k, value, mask, core);
+}
+
 size_t linkage_work_bytes(int64_t n) {
     return (size_t)comp_rows(n) * 4 + (size_t)n * 8 + (size_t)count_blocks(n) * 8 + (size_t)2 * (LINKAGE_MAX_ROUNDS + 1) * 4 + (size_t)n * 4;
 }
@@ -243,8 +289,8 @@ const uint32_t * linkage_stat(const void * work, int64_t n) {
     return (const uint32_t *)((const char *)work + (size_t)comp_rows(n) * 4 + (size_t)n * 8 + (size_t)count_blocks(n) * 8);
 }
 
-bool launch_linkage(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, float link, const uint32_t * mask, int * parent,
-                    unsigned long long * key, void * work, int64_t * lo, int64_t * hi, float * distances, int64_t * count, hipStream_t stream) {
+bool launch_linkage(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, float link, const uint32_t * mask, const float * core,
+                    int * parent, unsigned long long * key, void * work, int64_t * lo, int64_t * hi, float * distances, int64_t * count, hipStream_t stream) {
     if (n <= 1) {
         (void)hipMemsetAsync(count, 0, 8, stream);
         return hipGetLastError() == hipSuccess;
@@ -273,7 +319,11 @@ bool launch_linkage(const void * rows, const float * rinv, int64_t n, int Dpad, 
     for (int r = 0; r < rounds; r++) {
         const bool ok = with_search_type(dtype, [&](auto t) {
             using T = decltype(t);
-            return mask ? launch_outward_m<T, true>(p, stat, r, comp, key, stream) : launch_outward_m<T, false>(p, stat, r, comp, key, stream);
+            if (core)
+                return mask ? launch_outward_m<T, true, true>(p, stat, r, comp, key, core, stream)
+                            : launch_outward_m<T, false, true>(p, stat, r, comp, key, core, stream);
+            return mask ? launch_outward_m<T, true, false>(p, stat, r, comp, key, nullptr, stream)
+                        : launch_outward_m<T, false, false>(p, stat, r, comp, key, nullptr, stream);
         });
         if (!ok) return false;
         hipLaunchKernelGGL(linkage_min_kernel, dim3(grid), dim3(256), 0, stream, (const uint32_t *)stat, r, (const int *)comp,

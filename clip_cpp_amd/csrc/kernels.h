@@ -435,11 +435,18 @@ bool launch_modes(const void * rows, const float * rinv, int64_t n, int Dpad, in
 // the row that was hooked with the edge, *count (i64) their number.  Queues linkage_rounds(n) = ceil(log2 n) rounds; linkage_stat(work, n)
 // [2 rounds + 2] u32: {components hooked, eligible roots left} ahead of every round, a round having run when both allowed it (> 0, > 1).
 // Everything on the device, n < 2^31.
+// core != NULL ([linkage_core_bytes(n)] f32, device: one core distance per row, padded to whole groups of four rows; none a NaN): the
+// mutual-reachability tree, every distance d(x, y) replaced by w = max(d, core[x], core[y]) and the graph by "w <= link"; `distances`
+// receives w.  launch_linkage_core fills that column from a query block's finished k-NN results (dist [m][k] f32, sorted, device):
+// core[q0 + q] = dist[q][k - 1] for an eligible row (mask, NULL: every row), +inf for any other; dist NULL: `value` for an eligible row.
 int linkage_rounds(int64_t n);
 size_t linkage_work_bytes(int64_t n);
+size_t linkage_core_bytes(int64_t n);
 const uint32_t * linkage_stat(const void * work, int64_t n);
-bool launch_linkage(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, float link, const uint32_t * mask, int * parent,
-                    unsigned long long * key, void * work, int64_t * lo, int64_t * hi, float * distances, int64_t * count, hipStream_t stream);
+void launch_linkage_core(const float * dist, int64_t q0, int m, int k, float value, const uint32_t * mask, float * core, hipStream_t stream);
+bool launch_linkage(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, float link, const uint32_t * mask, const float * core,
+                    int * parent, unsigned long long * key, void * work, int64_t * lo, int64_t * hi, float * distances, int64_t * count,
+                    hipStream_t stream);
 
 // Extents of a labelling over the same pairs (k_extents.hip): labels [n] i64 on the device; row x is a member when it is eligible (mask as
 // for launch_components) and 0 <= labels[x] < n.  Workspace: work [extents_work_bytes(n)] (initialised here; 24 bytes per row and 24 per

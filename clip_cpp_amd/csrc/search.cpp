@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstring>
 #include <exception>
+#include <functional>
 #include <vector>
 
 #include "../../include/clip_amd.h"
@@ -96,6 +97,7 @@ struct clip_amd_index {
     // single-linkage tree (the forest goes through cparent, the keys through cnear)
     Buf lwork;                     // labels, per-root edges, round statistics and block counts (linkage_work_bytes)
     Buf louts;                     // host form: count (int64), lo + hi (int64), distances
+    Buf lcore;                     // mutual-reachability tree: [n rounded up to 4] core distances (f32)
     int linkage_rounds = 0;        // clip_amd_test_index_linkage_rounds: the rounds that ran in the last host-form call
     // extents of a labelling
     Buf ework;                     // member bitmap, label ranges, reach keys, per-label slots and i32 labels (extents_work_bytes)
@@ -499,13 +501,15 @@ int64_t query_block(int64_t nq, int k, size_t slot_bytes) {
                               (int64_t)(CAND_BUDGET / ((size_t)C * 8)) / 128 * 128});
 }
 
-// "nq stored-row queries, results to the host" (the k-NN graph, the search of one index with the rows of another): query blocks of
-// `block` rows, one after another, each scored, merged, finished into the block's result workspace and copied out.  Scan route: the scan
-// over the rows source(q0, m) names (a QuerySource), under d_allow.  Tiled route: launch(q0, m) runs a kernel of k_graph.hip over n_chunks
-// chunks straight from the stores.
-template <typename Source, typename Launch>
-bool search_blocks(clip_amd_index * ix, int64_t nq, int k, int64_t block, bool tiled, int n_chunks, const uint32_t * d_allow, float * distances,
-                   int64_t * ids, const char * fn, Source && source, Launch && launch) {
+// "nq stored-row queries" (the k-NN graph, the search of one index with the rows of another, the core distances of the mutual-reachability
+// tree): query blocks of `block` rows, one after another, each scored, merged, finished into the block's result workspace and handed to
+// sink(q0, m, d_dist, d_ids), which takes what it wants of the block's results ([m][k], device) before the next block reuses them on the
+// same stream: block_to_host copies them out, the tree keeps one column on the device.  Scan route: the scan over the rows source(q0, m)
+// names (a QuerySource), under d_allow.  Tiled route: launch(q0, m) runs a kernel of k_graph.hip over n_chunks chunks straight from the
+// stores.
+template <typename Source, typename Launch, typename Sink>
+bool search_blocks(clip_amd_index * ix, int64_t nq, int k, int64_t block, bool tiled, int n_chunks, const uint32_t * d_allow, const char * fn,
+                   Source && source, Launch && launch, Sink && sink) {
     const int C = search_candidate_capacity(k);
     if (!ensure(ix, ix->outs, (size_t)block * k * 12)) return false;
     int64_t * d_ids = (int64_t *)ix->outs.p;
@@ -523,9 +527,16 @@ bool search_blocks(clip_amd_index * ix, int64_t nq, int k, int64_t block, bool t
             if (!merge_and_finish(ix, n_chunks, m, k, nullptr, d_dist, d_ids)) return false;
             if (hipGetLastError() != hipSuccess) { fprintf(stderr, "%s: launch failed\n", fn); return false; }
         }
-        if (!copy_results(ix, d_dist, d_ids, (size_t)m * k, distances + (size_t)q0 * k, ids + (size_t)q0 * k, fn)) return false;
+        if (!sink(q0, m, (const float *)d_dist, (const int64_t *)d_ids)) return false;
     }
     return true;
+}
+
+// the sink of search_blocks that copies every block's results to the caller's host arrays ([nq][k]) and waits for the stream
+auto block_to_host(const clip_amd_index * ix, int k, float * distances, int64_t * ids, const char * fn) {
+    return [=](int64_t q0, int m, const float * d_dist, const int64_t * d_ids) {
+        return copy_results(ix, d_dist, d_ids, (size_t)m * k, distances + (size_t)q0 * k, ids + (size_t)q0 * k, fn);
+    };
 }
 
 // The k-NN graph on the host, by search_blocks (scan route: the self-excluding scan over the gathered rows; tiled route: graph_kernel
@@ -541,9 +552,37 @@ bool knn_graph_impl(clip_amd_index * ix, int k, float * distances, int64_t * ids
     int64_t rpc = (n + 127) / 128 * 128;
     if (tiled) tiled_chunks(n, block, k, rpc, n_chunks);
     return search_blocks(
-        ix, n, k, block, tiled, n_chunks, nullptr, distances, ids, fn, [&](int64_t q0, int) { return stored_rows(nullptr, q0, true); },
+        ix, n, k, block, tiled, n_chunks, nullptr, fn, [&](int64_t q0, int) { return stored_rows(nullptr, q0, true); },
         [&](int64_t q0, int m) {
             return launch_graph(ix->store.rows, ix->store.rinv, n, q0, m, ix->Dpad, ix->dtype, k, ix->cand.p, n_chunks, rpc, mask, st);
+        },
+        block_to_host(ix, k, distances, ids, fn));
+}
+
+// The core distances of the mutual-reachability tree (clip_amd_index_linkage_core): core [linkage_core_bytes(n)] on the device, per row of
+// E (mask: live & allow, NULL every row) the distance to its k-th nearest other row of E, +inf with fewer than k of them and for every
+// row outside E; k == 0: -inf over E.  The neighbour search of knn_graph_impl on both of its routes, under the mask, with
+// launch_linkage_core as the sink: nothing visits the host.  d_allow: the caller's allowed set behind mask (the scan route applies it).
+bool core_column(clip_amd_index * ix, int k, const uint32_t * d_allow, const uint32_t * mask, float * d_core, const char * fn) {
+    hipStream_t st = stream_of(ix);
+    const int64_t n = ix->n;
+    if (k == 0 || n == 1) {                                    // (a single row has no other row)
+        launch_linkage_core(nullptr, 0, (int)n, 1, k == 0 ? -INFINITY : INFINITY, mask, d_core, st);
+        return hipGetLastError() == hipSuccess;
+    }
+    const bool tiled = ix->knn_route ? ix->knn_route == 2 : n >= KNN_TILED_MIN_ROWS;
+    const int64_t block = query_block(n, k, 12);
+    int n_chunks = 1;
+    int64_t rpc = (n + 127) / 128 * 128;
+    if (tiled) tiled_chunks(n, block, k, rpc, n_chunks);
+    return search_blocks(
+        ix, n, k, block, tiled, n_chunks, d_allow, fn, [&](int64_t q0, int) { return stored_rows(nullptr, q0, true); },
+        [&](int64_t q0, int m) {
+            return launch_graph(ix->store.rows, ix->store.rinv, n, q0, m, ix->Dpad, ix->dtype, k, ix->cand.p, n_chunks, rpc, mask, st);
+        },
+        [&](int64_t q0, int m, const float * d_dist, const int64_t *) {
+            launch_linkage_core(d_dist, q0, m, k, 0.0f, mask, d_core, st);
+            return hipGetLastError() == hipSuccess;
         });
 }
 
@@ -573,7 +612,7 @@ bool search_index_impl(clip_amd_index * ix, const clip_amd_index * src, const in
     }
     if (ids && !ensure(ix, ix->idbuf, (size_t)block * 8)) return false;
     return search_blocks(
-        ix, nq, k, block, tiled, n_chunks, d_allow, distances, out_ids, fn,
+        ix, nq, k, block, tiled, n_chunks, d_allow, fn,
         [&](int64_t q0, int m) {
             if (ids) (void)hipMemcpyAsync(ix->idbuf.p, ids + q0, (size_t)m * 8, hipMemcpyHostToDevice, st);
             return stored_rows(ids ? (const int64_t *)ix->idbuf.p : nullptr, ids ? 0 : q0, false, src);
@@ -581,7 +620,8 @@ bool search_index_impl(clip_amd_index * ix, const clip_amd_index * src, const in
         [&](int64_t q0, int m) {
             return launch_graph_cross(ix->store.rows, ix->store.rinv, ix->n, src->store.rows, src->store.rinv, src->n, q0, m, ix->Dpad, ix->dtype, k,
                                       ix->cand.p, n_chunks, rpc, mask, st);
-        });
+        },
+        block_to_host(ix, k, distances, out_ids, fn));
 }
 
 // what clip_amd_index_search_index and clip_amd_index_append ask of their two indexes
@@ -1002,17 +1042,25 @@ int64_t modes_host(clip_amd_index * ix, float radius, float link, const uint64_t
     return stream_done(ix, fn) ? (int64_t)modes : -1;
 }
 
-// The single-linkage tree on the device: the edges and their number.  Queues the launches and returns.
-bool linkage_impl(clip_amd_index * ix, float link, const uint32_t * d_allow, int64_t * d_lo, int64_t * d_hi, float * d_dist, int64_t * d_count,
-                  const char * fn) {
+// The single-linkage tree on the device: the edges and their number.  Queues the launches and returns.  k >= 0: the mutual-reachability
+// tree of clip_amd_index_linkage_core instead; the core distances go to the core workspace first (core_column) and from there to d_core
+// ([size], may be NULL).  k == 0 runs the plain kernels: every core distance is -inf, so w is d.
+bool linkage_impl(clip_amd_index * ix, int k, float link, const uint32_t * d_allow, int64_t * d_lo, int64_t * d_hi, float * d_dist, float * d_core,
+                  int64_t * d_count, const char * fn) {
     const uint32_t * mask = nullptr;
+    const float * core = nullptr;
+    if (ix->n > 0 && (ix->n > 1 || k >= 0) && !effective_mask(ix, d_allow, mask)) return false;
+    if (ix->n > 0 && k >= 0) {
+        if (!ensure(ix, ix->lcore, linkage_core_bytes(ix->n)) || !core_column(ix, k, d_allow, mask, (float *)ix->lcore.p, fn)) return false;
+        if (d_core) (void)hipMemcpyAsync(d_core, ix->lcore.p, (size_t)ix->n * 4, hipMemcpyDeviceToDevice, stream_of(ix));
+        if (k > 0) core = (const float *)ix->lcore.p;
+    }
     if (ix->n > 1) {
-        if (!effective_mask(ix, d_allow, mask)) return false;
         if (!ensure(ix, ix->cparent, (size_t)ix->n * 2 * sizeof(int)) || !ensure(ix, ix->cnear, (size_t)ix->n * 8) ||
             !ensure(ix, ix->lwork, linkage_work_bytes(ix->n)))
             return false;
     }
-    if (!launch_linkage(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, link, mask, (int *)ix->cparent.p,
+    if (!launch_linkage(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, link, mask, core, (int *)ix->cparent.p,
                         (unsigned long long *)ix->cnear.p, ix->lwork.p, d_lo, d_hi, d_dist, d_count, stream_of(ix))) {
         fprintf(stderr, "%s: launch failed\n", fn);
         return false;
@@ -1027,10 +1075,18 @@ bool check_linkage_args(const clip_amd_index * ix, float link, const void * lo, 
     return true;
 }
 
-// The host form: the edges in their workspace, copied out and sorted by (d, lo, hi).  Returns their number or -1.
-int64_t linkage_host(clip_amd_index * ix, float link, const uint64_t * allow, int64_t * lo, int64_t * hi, float * dist, const char * fn) {
+// what clip_amd_index_linkage_core asks of k beyond check_linkage_args
+bool check_core_k(int k, const char * fn) {
+    if (k < 0 || k > MAX_K) { fprintf(stderr, "%s: k = %d outside 0 ... %d\n", fn, k, MAX_K); return false; }
+    return true;
+}
+
+// The host form: the edges in their workspace, copied out and sorted by (d, lo, hi).  Returns their number or -1.  k as for linkage_impl;
+// k >= 0: core ([size], may be NULL) receives the core distances, which a single row has too.
+int64_t linkage_host(clip_amd_index * ix, int k, float link, const uint64_t * allow, int64_t * lo, int64_t * hi, float * dist, float * core,
+                     const char * fn) {
     ix->linkage_rounds = 0;
-    if (ix->n <= 1) return 0;
+    if (ix->n <= (k >= 0 ? 0 : 1)) return 0;
     hipStream_t st = stream_of(ix);
     const size_t cap = (size_t)ix->n - 1;
     const uint32_t * d_allow = nullptr;
@@ -1039,12 +1095,15 @@ int64_t linkage_host(clip_amd_index * ix, float link, const uint64_t * allow, in
     int64_t * d_lo = d_count + 1;
     int64_t * d_hi = d_lo + cap;
     float * d_dist = (float *)(d_hi + cap);
-    if (!linkage_impl(ix, link, d_allow, d_lo, d_hi, d_dist, d_count, fn)) return -1;
+    if (!linkage_impl(ix, k, link, d_allow, d_lo, d_hi, d_dist, nullptr, d_count, fn)) return -1;
     int64_t m = 0;
     std::vector<uint32_t> stat((size_t)2 * linkage_rounds(ix->n));
+    std::vector<float> h_core(k >= 0 && core ? (size_t)ix->n : 0);      // (the caller's array stays untouched when the stream fails)
     (void)hipMemcpyAsync(&m, d_count, 8, hipMemcpyDeviceToHost, st);
-    (void)hipMemcpyAsync(stat.data(), linkage_stat(ix->lwork.p, ix->n), stat.size() * 4, hipMemcpyDeviceToHost, st);
+    if (!stat.empty()) (void)hipMemcpyAsync(stat.data(), linkage_stat(ix->lwork.p, ix->n), stat.size() * 4, hipMemcpyDeviceToHost, st);
+    if (!h_core.empty()) (void)hipMemcpyAsync(h_core.data(), ix->lcore.p, h_core.size() * 4, hipMemcpyDeviceToHost, st);
     if (!stream_done(ix, fn)) return -1;
+    if (!h_core.empty()) memcpy(core, h_core.data(), h_core.size() * 4);
     if (m < 0 || (size_t)m > cap) { fprintf(stderr, "%s: %lld edges for %lld rows\n", fn, (long long)m, (long long)ix->n); return -1; }
     for (size_t r = 0; 2 * r < stat.size(); r++) ix->linkage_rounds += stat[2 * r] > 0 && stat[2 * r + 1] > 1;
     std::vector<int64_t> h_lo((size_t)m), h_hi((size_t)m);     // the caller's arrays stay untouched when the stream fails
@@ -2123,7 +2182,7 @@ int64_t clip_amd_index_linkage(struct clip_amd_index * ix, float link, const uin
     return guarded(__func__, (int64_t)-1, [&](const char * fn) -> int64_t {
         if (!check_linkage_args(ix, link, lo, hi, distances, fn)) return -1;
         (void)hipSetDevice(ix->device);
-        return linkage_host(ix, link, allow, lo, hi, distances, fn);
+        return linkage_host(ix, -1, link, allow, lo, hi, distances, nullptr, fn);
     });
 }
 
@@ -2133,7 +2192,26 @@ bool clip_amd_index_linkage_device(struct clip_amd_index * ix, float link, const
         if (!check_linkage_args(ix, link, d_lo, d_hi, d_distances, fn)) return false;
         if (!d_count) { fprintf(stderr, "%s: d_count is NULL\n", fn); return false; }
         (void)hipSetDevice(ix->device);
-        return linkage_impl(ix, link, (const uint32_t *)d_allow, d_lo, d_hi, d_distances, d_count, fn);
+        return linkage_impl(ix, -1, link, (const uint32_t *)d_allow, d_lo, d_hi, d_distances, nullptr, d_count, fn);
+    });
+}
+
+int64_t clip_amd_index_linkage_core(struct clip_amd_index * ix, int k, float link, const uint64_t * allow, int64_t * lo, int64_t * hi,
+                                    float * weights, float * core) {
+    return guarded(__func__, (int64_t)-1, [&](const char * fn) -> int64_t {
+        if (!check_linkage_args(ix, link, lo, hi, weights, fn) || !check_core_k(k, fn)) return -1;
+        (void)hipSetDevice(ix->device);
+        return linkage_host(ix, k, link, allow, lo, hi, weights, core, fn);
+    });
+}
+
+bool clip_amd_index_linkage_core_device(struct clip_amd_index * ix, int k, float link, const uint64_t * d_allow, int64_t * d_lo, int64_t * d_hi,
+                                        float * d_weights, float * d_core, int64_t * d_count) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_linkage_args(ix, link, d_lo, d_hi, d_weights, fn) || !check_core_k(k, fn)) return false;
+        if (!d_count) { fprintf(stderr, "%s: d_count is NULL\n", fn); return false; }
+        (void)hipSetDevice(ix->device);
+        return linkage_impl(ix, k, link, (const uint32_t *)d_allow, d_lo, d_hi, d_weights, d_core, d_count, fn);
     });
 }
 
@@ -2426,7 +2504,7 @@ float clip_amd_bench_linkage(int dtype, int64_t n, int dim, int copies, int iter
             const size_t cap = (size_t)std::max<int64_t>(n - 1, 1);
             std::vector<int64_t> lo(cap), hi(cap);
             std::vector<float> dist(cap);
-            auto call = [&]() { return linkage_host(ix, INFINITY, nullptr, lo.data(), hi.data(), dist.data(), fn) >= 0; };
+            auto call = [&]() { return linkage_host(ix, -1, INFINITY, nullptr, lo.data(), hi.data(), dist.data(), nullptr, fn) >= 0; };
             if (hipDeviceSynchronize() != hipSuccess || !call()) return -4.f;
             const float us = time_wall(iters, call);
             bench_linkage_rounds = ix->linkage_rounds;
@@ -2438,6 +2516,48 @@ float clip_amd_bench_linkage(int dtype, int64_t n, int dim, int copies, int iter
 int clip_amd_bench_linkage_rounds(void) { return bench_linkage_rounds; }
 
 int clip_amd_test_index_linkage_rounds(struct clip_amd_index * ix) { return ix ? ix->linkage_rounds : -1; }
+
+static float bench_core_parts[5] = {-4.f, -4.f, -4.f, 0.f, 0.f};
+
+float clip_amd_bench_linkage_core(int dtype, int64_t n, int dim, int k, int copies, int iters) {
+    return guarded(__func__, -4.f, [&](const char * fn) {
+        const bool args_ok = copies >= 0 && k >= 1 && k <= MAX_K;
+        return bench_on_gallery(dtype, n, dim, 0, iters, args_ok, copies > 0 ? copies : PLANT_JOIN, [&](clip_amd_index * ix, float *) {
+            const size_t cap = (size_t)std::max<int64_t>(n - 1, 1);
+            std::vector<int64_t> lo(cap), hi(cap), ids((size_t)n * k);
+            std::vector<float> dist(cap), core((size_t)n), kd((size_t)n * k);
+            // the four calls of an iteration one after another on the one index, each timed on its own: wall time, synchronous calls
+            const std::function<bool()> calls[4] = {
+                [&]() { return linkage_host(ix, k, INFINITY, nullptr, lo.data(), hi.data(), dist.data(), core.data(), fn) >= 0; },
+                [&]() { return knn_graph_impl(ix, k, kd.data(), ids.data(), fn); },
+                [&]() { return linkage_host(ix, -1, INFINITY, nullptr, lo.data(), hi.data(), dist.data(), nullptr, fn) >= 0; },
+                [&]() {
+                    return ensure(ix, ix->lcore, linkage_core_bytes(ix->n)) && core_column(ix, k, nullptr, nullptr, (float *)ix->lcore.p, fn) &&
+                           stream_done(ix, fn);
+                }};
+            double sum[4] = {0, 0, 0, 0};
+            int rounds[2] = {0, 0};
+            if (hipDeviceSynchronize() != hipSuccess) return -4.f;
+            for (int i = -1; i < iters; i++)                   // (iteration -1 warms every call up)
+                for (int c = 0; c < 4; c++) {
+                    const auto t0 = std::chrono::steady_clock::now();
+                    if (!calls[c]()) return -4.f;
+                    if (i >= 0) sum[c] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+                    if (c == 0 || c == 2) rounds[c / 2] = ix->linkage_rounds;
+                }
+            bench_core_parts[0] = (float)(sum[1] / iters);
+            bench_core_parts[1] = (float)(sum[2] / iters);
+            bench_core_parts[2] = (float)(sum[3] / iters);
+            bench_core_parts[3] = (float)rounds[0];
+            bench_core_parts[4] = (float)rounds[1];
+            return (float)(sum[0] / iters);
+        });
+    });
+}
+
+void clip_amd_bench_linkage_core_parts(float * parts) {
+    if (parts) memcpy(parts, bench_core_parts, sizeof(bench_core_parts));
+}
 
 float clip_amd_bench_spread(int dtype, int64_t n, int dim, int64_t n_max, int copies, int iters) {
     return guarded(__func__, -4.f, [&](const char * fn) {

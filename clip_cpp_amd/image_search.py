@@ -9,8 +9,8 @@ build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.In
     python -m clip_cpp_amd.image_search dedup  [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R] [--prune] [--extents]
     python -m clip_cpp_amd.image_search albums [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R] [--link T] [--min N] [-n COUNT]
     python -m clip_cpp_amd.image_search spread [-m MODEL] [-v N] [--db DIR] -n N [-d R] [--in PREFIX]... [--from INDEXED/IMAGE/PATH]...
-    python -m clip_cpp_amd.image_search groups [-m MODEL] [-v N] [--db DIR] -n N [--in PREFIX]... [--min M] [--extents]
-    python -m clip_cpp_amd.image_search levels [-m MODEL] [-v N] [--db DIR] [--in PREFIX]... [-n ROWS]
+    python -m clip_cpp_amd.image_search groups [-m MODEL] [-v N] [--db DIR] -n N [--in PREFIX]... [--min M] [--extents] [--core K]
+    python -m clip_cpp_amd.image_search levels [-m MODEL] [-v N] [--db DIR] [--in PREFIX]... [-n ROWS] [--core K]
     python -m clip_cpp_amd.image_search neighbors [-m MODEL] [-v N] [--db DIR] [-n N]
     python -m clip_cpp_amd.image_search label  [-m MODEL] [-v N] [-t N] [--db DIR] [-n N] LABEL [LABEL ...]
     python -m clip_cpp_amd.image_search merge  [-m MODEL] [-v N] --db DIR --from DIR2 [--from DIR3 ...] [-d R]
@@ -61,6 +61,16 @@ distance against groups from the sorted links of the tree.  It prints "levels:" 
 -n ROWS rows (default 20) evenly spaced over the merges, each moved to the end of its run of equal distances, "  %f %d %d %d": a distance,
 the groups of two or more images `dedup` finds at it, the images in them and the size of the largest group; the last row is the distance
 at which everything is one group; then "main: %d images, %d levels".  --in PREFIX restricts both commands to the matching images.
+`groups --core K` and `levels --core K` read the mutual-reachability tree instead (Index.linkage_core, one call): every distance d(x, y)
+is raised to max(d, core(x), core(y)), core being the distance to an image's K-th nearest other image, so an image in a sparse region is
+far from everything and a few stray images between two albums no longer chain them into one (the cut at R is DBSCAN* at R with
+min_pts = K + 1).  `groups --core K -n N` then asks for exactly N groups of at least --min M images (default 2), at the largest distance
+of the tree that gives them (clip_cpp_amd.cut_linkage_sized); smaller groups and single images are left unfiled.  The groups are printed
+as without the flag, and the closing line is
+"main: %d groups of at least %d images, %d images in those; cut at radius %f, %d images left unfiled"
+(--extents adds "; largest diameter %f" as before).  When no distance gives exactly N such groups it prints
+"main: -n %d: ..." with the counts that do occur and exits with status 1.  `levels --core K` prints the same table from that tree.
+Without --core both commands print exactly what they printed before.
 `search --like PATH` asks for "more like this one": the query is the indexed image whose line in images.paths equals PATH as written
 (Index.search_ids: its stored row, nothing is decoded or encoded, so a text-only or vision-less model is enough); the image itself is not
 listed.  It composes with -n and --in, not with a positional query or -d.
@@ -123,6 +133,7 @@ MAX_K = 1024
 DEDUP_RADIUS = 0.05
 MAX_TERMS = 8       # terms of a compound search: the main query, every --and and every --not
 LEVEL_ROWS = 20     # rows of the `levels` table
+MAX_CORE = 1024     # --core K of `groups` and `levels`: the k of Index.linkage_core
 
 
 EXTENTS_HELP = ("  --extents: measure every group (Index.extents): its centre, the image from which the farthest other member is nearest, comes"
@@ -160,6 +171,8 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
     p = dict(threads=4, verbose=1, db=".", dtype="f16", results=1 if label else 5, max_distance=DEDUP_RADIUS if dedup or albums else None,
              model="../models/ggml-model-f16.bin" if build else "", rest=[], like=None)
     p["in"] = []
+    if groups or levels:
+        p["core"] = None                                   # --core K: the mutual-reachability tree
     if merge or spread:
         p["from"] = []
     if spread:
@@ -185,7 +198,7 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         elif neighbors or label or match:
             takes.update({"-n": "results", "--results": "results"})
         elif tree:
-            takes.update({"-n": "results", "--results": "results", "--in": "in"})
+            takes.update({"-n": "results", "--results": "results", "--in": "in", "--core": "core"})
             if groups:
                 takes["--min"] = "min_size"
         elif merge:
@@ -216,7 +229,7 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
                 i += 1
                 continue
             try:
-                p[key] = int(argv[i]) if key in ("threads", "verbose", "results", "grid", "min_size") else float(argv[i]) if key in ("max_distance", "distinct", "not_margin", "link") else argv[i]
+                p[key] = int(argv[i]) if key in ("threads", "verbose", "results", "grid", "min_size", "core") else float(argv[i]) if key in ("max_distance", "distinct", "not_margin", "link") else argv[i]
             except ValueError:
                 return None
             if key in ("max_distance", "distinct", "not_margin", "link") and p[key] != p[key]:      # NaN
@@ -266,6 +279,9 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         if p["results"] < 1:
             print("main: -n %d: groups makes at least one group" % p["results"])
             return None
+    if (groups or levels) and p["core"] is not None and not 0 <= p["core"] <= MAX_CORE:
+        print("main: --core takes 0 ... %d (0: the single-linkage tree), not %d" % (MAX_CORE, p["core"]))
+        return None
     if levels and p["results"] < 1:
         print("main: -n %d: levels prints at least one row" % p["results"])
         return None
@@ -315,8 +331,12 @@ def _help(build, p, dedup=False, update=False, neighbors=False, label=False, mer
         if groups:
             print("  -n N, --results N: make exactly N groups, single images included. Required")
             print("  --min M: print only the groups of at least M images. Default: 2 (1: single images too)")
+            print("  --core K: read the mutual-reachability tree (distances raised to the distance of either image's K-th nearest other image), so a")
+            print("    few stray images between two groups do not chain them together. -n N then asks for exactly N groups of at least --min M images;")
+            print("    smaller groups and single images are left unfiled. Exits with status 1 when no distance gives exactly N such groups")
         else:
             print("  -n ROWS, --results ROWS: rows of the table, evenly spaced over the merges of the tree. Default: %d" % LEVEL_ROWS)
+            print("  --core K: the table of the mutual-reachability tree (see `groups --core K`): what `groups --core K` finds at each distance")
         print("  --in <prefix>: only images whose indexed path starts with <prefix> take part; may be repeated")
         if groups:
             print(EXTENTS_HELP % "")
@@ -1101,16 +1121,37 @@ def tree_groups(size, lo, hi, d, n_groups, eligible=None, min_size=2):
     d = np.asarray(d, dtype=np.float32)
     labels = clip_cpp_amd.cut_linkage(size, lo, hi, d, n_groups=n_groups, eligible=eligible)
     kept = int(np.count_nonzero(labels >= 0)) - int(n_groups)
-    nearest = np.full(size, np.inf, dtype=np.float64)
-    np.minimum.at(nearest, lo[:kept], d[:kept].astype(np.float64))
-    np.minimum.at(nearest, hi[:kept], d[:kept].astype(np.float64))
+    return (_label_groups(labels, lo[:kept], hi[:kept], d[:kept], min_size), float(d[kept - 1]) if kept > 0 else float("-inf"),
+            float(d[kept]) if kept < d.size else float("inf"))
+
+
+def _label_groups(labels, lo, hi, d, min_size):
+    """The groups of a cut in the structure of component_groups: labels of the cut and the edges it kept -> [(id, distance of its
+    shortest kept edge), ...] per group in id order (inf for a single row), only the groups of at least min_size rows, largest first,
+    equal sizes in order of the lowest id"""
+    nearest = np.full(labels.size, np.inf, dtype=np.float64)
+    np.minimum.at(nearest, lo, d.astype(np.float64))
+    np.minimum.at(nearest, hi, d.astype(np.float64))
     ids = np.flatnonzero(labels >= 0)
     order = ids[np.argsort(labels[ids], kind="stable")]
     cuts = np.flatnonzero(np.diff(labels[order])) + 1
     groups = [g for g in np.split(order, cuts) if g.size >= max(int(min_size), 1)]
     groups.sort(key=lambda g: (-g.size, int(g[0])))
-    return ([list(zip(g.tolist(), nearest[g].tolist())) for g in groups], float(d[kept - 1]) if kept > 0 else float("-inf"),
-            float(d[kept]) if kept < d.size else float("inf"))
+    return [list(zip(g.tolist(), nearest[g].tolist())) for g in groups]
+
+
+def sized_groups(size, lo, hi, w, n_groups, eligible=None, min_size=2):
+    """`groups --core K`: exactly n_groups groups of at least min_size rows from the edges of Index.linkage_core (sorted), cut at the
+    largest weight that gives them (clip_cpp_amd.cut_linkage_sized).  Returns (groups, radius, unfiled): groups in the structure and
+    order of tree_groups, a member's distance being the smallest kept weight at it; unfiled: the eligible rows in no such group.
+    ValueError when no weight gives n_groups."""
+    import clip_cpp_amd
+    lo, hi = np.asarray(lo, dtype=np.int64), np.asarray(hi, dtype=np.int64)
+    w = np.asarray(w, dtype=np.float32)
+    labels, radius = clip_cpp_amd.cut_linkage_sized(size, lo, hi, w, n_groups, min_size=min_size, eligible=eligible)
+    kept = w <= np.float32(radius)
+    groups = _label_groups(labels, lo[kept], hi[kept], w[kept], min_size)
+    return groups, radius, int(np.count_nonzero(labels >= 0)) - sum(len(g) for g in groups)
 
 
 def level_rows(size, d_sorted_lo, d_sorted_hi, d, rows=LEVEL_ROWS):
@@ -1172,13 +1213,24 @@ def _load_tree(p, command):
         print("main: Unable to load model from %s" % p["model"])
         return None
     index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
-    edges = index.linkage(allow=allow)
-    extents = None
-    if p.get("extents"):
+    core = p.get("core")
+    edges = index.linkage(allow=allow) if core is None else index.linkage_core(core, allow=allow)[:3]
+    extents, labels, refused = None, None, None
+    if command == "groups" and core is not None:
+        try:
+            labels = clip_cpp_amd.cut_linkage_sized(len(image_paths), *edges, n_groups=p["results"], min_size=p["min_size"], eligible=allow)[0]
+        except ValueError as e:
+            refused = "main: -n %d: %s" % (p["results"], e)
+    elif p.get("extents"):
         labels = clip_cpp_amd.cut_linkage(len(image_paths), *edges, n_groups=p["results"], eligible=allow)
+    if p.get("extents") and labels is not None:
         extents = (labels,) + index.extents(labels, allow=allow)
     index.close()
     clip.close()
+    if refused:
+        print(refused)
+        sys.stdout.flush()
+        return None
     return image_paths, allow, edges, extents
 
 
@@ -1191,11 +1243,16 @@ def groups(argv):
     if loaded is None:
         return 1
     image_paths, allow, (lo, hi, d), extents = loaded
-    found, kept, cut = tree_groups(len(image_paths), lo, hi, d, p["results"], allow, p["min_size"])
+    if p["core"] is None:
+        found, kept, cut = tree_groups(len(image_paths), lo, hi, d, p["results"], allow, p["min_size"])
+        closing = ("main: %d groups, %d of them with at least %d images, %d images in those; longest link kept %f, cut at %f"
+                   % (p["results"], len(found), max(p["min_size"], 1), sum(len(g) for g in found), kept, cut))
+    else:                                          # (_load_tree has made sure that the cut exists)
+        found, radius, unfiled = sized_groups(len(image_paths), lo, hi, d, p["results"], allow, p["min_size"])
+        closing = ("main: %d groups of at least %d images, %d images in those; cut at radius %f, %d images left unfiled"
+                   % (len(found), max(p["min_size"], 1), sum(len(g) for g in found), radius, unfiled))
     if p["verbose"] > 0:
         print("groups:")
-    closing = ("main: %d groups, %d of them with at least %d images, %d images in those; longest link kept %f, cut at %f"
-               % (p["results"], len(found), max(p["min_size"], 1), sum(len(g) for g in found), kept, cut))
     if extents is not None:                        # the same groups in the same order, each with its centre first
         labels, centre, radius, diameter, reach, _ = extents
         closing += "; largest diameter %f" % _print_extent_groups(

@@ -550,6 +550,42 @@ int clip_amd_bench_linkage_rounds(void);
 /* The rounds that did work in the index's last clip_amd_index_linkage (host form): sweeps over the pairs that ran; -1 for a NULL index.
  * Used by scripts/linkage_bench.py and tests/. */
 int clip_amd_test_index_linkage_rounds(struct clip_amd_index * ix);
+/* The mutual-reachability tree (robust single linkage, the tree of DBSCAN* / HDBSCAN): the single-linkage tree above with every distance
+ * replaced by w(x, y) = max(d(x, y), core(x), core(y)).  A row in a sparse region is pushed away from everything, so a bridge of a few
+ * stray rows no longer joins two dense groups.  Cut at any R, the tree is DBSCAN* at radius R with min_pts = k + 1: one call answers for
+ * every radius.
+ * E, m and d(x, y) are exactly those of clip_amd_index_linkage.  0 <= k <= 1024.  core(x) for x in E: -INFINITY when k == 0; else entry
+ * k - 1 of the distances clip_amd_index_search_ids(x, k, exclude_self = 1, allow = E) returns, bit for bit: the distance to the row's
+ * k-th nearest other eligible row, +INFINITY when E holds fewer than k other rows.  w is the maximum of the three in f32; no operand is
+ * ever a NaN, so it is exact and the order of its evaluation does not matter.  Edges are ordered by (w, lo, hi), lo < hi: a total order.
+ * The result is the minimum spanning forest of the graph "w <= link" over E under that order: an edge belongs to it exactly when its
+ * endpoints are not connected by strictly smaller edges.  weights receives w.  core ([size] f32, may be NULL) receives core(x) for x in
+ * E and +INFINITY for every other row; it is written whenever size > 0, also when no edge is.
+ * Output forms, capacities (size - 1), order and return values are those of clip_amd_index_linkage: the host form sorted by the edge
+ * order, the device form unordered but byte-identical run to run, 0 when m <= 1.  +INFINITY weights are legal: they occur when E holds
+ * at most k rows, are in the graph only at link == INFINITY and are then ordered by (lo, hi).
+ * Consequences: k == 0 gives, byte for byte, the result of clip_amd_index_linkage.  A finite link gives a prefix of the whole tree.  Cut
+ * at R, the rows with core <= R carry exactly the labels of clip_amd_index_components(R, allow = {x in E : core(x) <= R}) and every
+ * other eligible row is a group of its own.  Results are bit-identical run to run, however rows were split across add calls, across
+ * save / load and on both routes of the neighbour search (clip_amd_index_knn_graph's), and do not depend on the order of any atomic;
+ * over E they are those of an index to which only the rows of E were ever added (ids mapped in order).
+ * -1 / false with a message on stderr, nothing launched and no output written, for a NULL index, a NULL lo / hi / weights, a NaN link
+ * or a k outside 0 ... 1024.
+ * Host form: host arrays, synchronous on the ctx stream.  Device form: allow (trusted) and the outputs in HBM, asynchronous on the ctx
+ * stream, synchronises with nothing on the host; the core distances never visit the host.  Device memory beyond the index: that of
+ * clip_amd_index_linkage plus 4 bytes per row (padded to four rows) and the fixed workspace of clip_amd_index_knn_graph. */
+int64_t clip_amd_index_linkage_core(struct clip_amd_index * ix, int k, float link, const uint64_t * allow, int64_t * lo, int64_t * hi,
+                                    float * weights, float * core);
+bool clip_amd_index_linkage_core_device(struct clip_amd_index * ix, int k, float link, const uint64_t * d_allow, int64_t * d_lo, int64_t * d_hi,
+                                        float * d_weights, float * d_core, int64_t * d_count);
+/* Average wall times (microseconds) over the rows of clip_amd_bench_modes, taken on one index in one run, the calls of an iteration one
+ * after another: returns that of one clip_amd_index_linkage_core (host form, link = INFINITY, core wanted); < 0 on error.
+ * clip_amd_bench_linkage_core_parts: parts [5] of the last call of it: clip_amd_index_knn_graph(k), clip_amd_index_linkage, the core
+ * column alone (the neighbour search with its device-side sink), the rounds that did work in the mutual-reachability tree and in the
+ * single-linkage tree.  clip_amd_test_index_linkage_rounds counts the rounds of clip_amd_index_linkage_core's host form as well.  Used by
+ * scripts/linkage_core_bench.py. */
+float clip_amd_bench_linkage_core(int dtype, int64_t n, int dim, int k, int copies, int iters);
+void clip_amd_bench_linkage_core_parts(float * parts);
 /* Extents of a labelling: given one label per row (from clip_amd_index_components, a cut of the linkage tree, clip_amd_index_modes, the
  * owner of clip_amd_index_spread, or anything else), how far every row's own group reaches from it, and for every group its minimax
  * centre, its radius and its diameter.  It tells a tight burst of copies from a chain whose two ends are far apart, and gives every
