@@ -155,6 +155,11 @@ void gemm(clip_ctx * ctx, const char * what, const GemmParams & p0, int epi) {
     else if (panel && tile % 1000 >= 259) snprintf(fam, sizeof fam, "gemm4_kernel<%d>/%s", epi, what);   // (+ a short second launch for the rows past the whole rounds)
     else if (panel) snprintf(fam, sizeof fam, "gemm8_kernel<%d,%d>/%s", tile / 32000, epi, what);
     else if (gemm_tile_is_ring(tile)) snprintf(fam, sizeof fam, "gemm_ring_kernel<%d,%d,4,%d,%d>/%s", wt, tile % 1000, tile % 1000 >= 128 ? 4 : 2, epi, what);
+    else if (gemm_tile_is_wide(tile)) {        // the 256-column fused tile carries fp16-output epilogues on block-quantised weights (q5_0 / q8_0: 128 rows); else launch_gemm re-picks
+        const bool wide = wt != W_F16 && (epi == EPI_F16 || epi == EPI_GELU_F16 || epi == EPI_QGELU_F16) && !p.xg_out;
+        const int t = wide ? tile : gemm_tile_for_narrow(p.M, p.W.N, p.W.Kpad, wt != W_F16, p.shared_device);
+        snprintf(fam, sizeof fam, "gemm_dma_kernel<%d,%d,%d,%d>/%s", wt, wide ? ((wt == W_Q5_0 || wt == W_Q8_0) ? 128 : tile / 1000) : gemm_tile_uses_panel(t) ? 160 : t / 1000, wide ? 256 : gemm_tile_uses_panel(t) ? 128 : t % 1000, epi, what);
+    }
     else snprintf(fam, sizeof fam, "gemm_dma_kernel<%d,%d,%d,%d>/%s", wt, gemm_tile_uses_panel(tile) ? 160 : tile / 1000, gemm_tile_uses_panel(tile) ? 128 : tile % 1000, epi, what);
     ProfScope ps(ctx, fam, p.M, p.W.N, p.W.K, fl, by);
     launch_gemm(p, epi, 0, ctx->stream);

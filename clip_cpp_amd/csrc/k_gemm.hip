@@ -29,6 +29,8 @@
 //     iglp_opt) clumps that work after the MFMA chain (+4-7 % from the explicit interleave, profiles/);
 //   * workgroup -> tile mapping: XCD-contiguous chunks, n fastest, so the workgroups that share an activation
 //     row-panel run back to back on one XCD/L2 (measured: L2 hit rate 32 % -> 85 %, HBM traffic = algorithmic).
+//   * 256-column tiles for block-quantised weights and fp16 outputs (gemm_wide.h, tile codes 128257 / 160257): ONE LDS image of W rotated by
+//     k-slice, so two workgroups still share a CU; 41 % fewer L2 -> CU operand bytes per FLOP.
 //
 // Roofline: compute (MFMA fp16, 2.5 PFLOP/s dense) for M >= ~256; HBM (weight bytes) for M <= 64.
 // Measured (r01, MI355X): 0.65-0.93 PFLOP/s on the ViT-B/32 / L/14 shapes (hipBLASLt, plain f16, no epilogue:
@@ -39,6 +41,7 @@
 #include <vector>
 
 #include "gemm_common.h"
+#include "gemm_wide.h"
 
 namespace clipamd {
 
@@ -58,11 +61,20 @@ constexpr int NTHREADS = 256;
 // item 1 —: slower on every text-tower shape, and the extra code cost the split-free FFN-up launch 25 % (49.9 -> 62.6 us); removed again,
 // the implementation is in commit 8f8234b, the numbers in profiles/r03_lnfold_and_text_tiles.txt section 6.)
 constexpr bool gemm_tile_splits_k(int bm, int bn) { return bm == 64 && bn > 0; }
+// the 256-column tiles of gemm_wide.h (tile codes 128257 / 160257): block-quantised weights and fp16 outputs, ONE rotated LDS image of W -> two workgroups per CU
+constexpr bool gemm_tile_is_wide_inst(int wt, int bm, int bn, int epi) { return bn == WIDE_BN && wt != W_F16 && gemm_wide_bm_fits(wt, bm) && gemm_wide_epilogue(epi); }
+constexpr size_t gemm_dma_lds_bytes(int wt, int bm, int bn, int epi) {
+    return gemm_tile_is_wide_inst(wt, bm, bn, epi) ? gemm_wide_lds_bytes(bm) : (size_t)2 * (bm + bn) * BK * sizeof(half_t);
+}
 
 // ---------------------------------------------------------------------------------------------
 template <int WT, int BM, int BN, int EPI>
-__global__ void __launch_bounds__(NTHREADS, ((BM + BN) * BK * 4 <= 80 * 1024 ? 2 : 1)) gemm_dma_kernel(const GemmParams p) {
+__global__ void __launch_bounds__(NTHREADS, (gemm_dma_lds_bytes(WT, BM, BN, EPI) <= 80 * 1024 ? 2 : 1)) gemm_dma_kernel(const GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    if constexpr (gemm_tile_is_wide_inst(WT, BM, BN, EPI)) {
+        gemm_wide_body<WT, BM, EPI>(p, smem_raw);
+        return;
+    } else {
     half_t * Xs = (half_t *)smem_raw;                 // [2][BM*BK]
     half_t * Ws = Xs + 2 * BM * BK;                   // [2][BN*BK]
     constexpr int TN = BN / 32, TM = BM / 32;
@@ -378,12 +390,13 @@ __global__ void __launch_bounds__(NTHREADS, ((BM + BN) * BK * 4 <= 80 * 1024 ? 2
         }
     }
     gemm_epilogue<EPI, TN, TM>(p, acc, n0 + wn * (BN / 2), m0 + wm * (BM / 2), frow, fgrp, ln, rs_lane);
+    }
 }
 
 template <int WT, int BM, int BN, int EPI>
 void launch_dma(const GemmParams & p, hipStream_t stream) {
     const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.W.N + BN - 1) / BN;
-    constexpr size_t smem = (size_t)2 * (BM + BN) * BK * sizeof(half_t);
+    constexpr size_t smem = gemm_dma_lds_bytes(WT, BM, BN, EPI);
     static unsigned long long lds_ok = 0;
     if (smem > 64 * 1024) opt_in_dynamic_lds(gemm_dma_kernel<WT, BM, BN, EPI>, smem, lds_ok);
     int grid = tiles_m * tiles_n;
@@ -398,6 +411,13 @@ void launch_tile(const GemmParams & p, int tile, hipStream_t stream) {
     case 128128: launch_dma<WT, 128, 128, EPI>(p, stream); break;
     case 160128: launch_dma<WT, 160, 128, EPI>(p, stream); break;
     case 192128: launch_dma<WT, 192, 128, EPI>(p, stream); break;
+    // gemm_wide.h: launch_gemm sends only block-quantised weights and fp16-output epilogues here
+    case 128257: if constexpr (gemm_tile_is_wide_inst(WT, 128, 256, EPI)) launch_dma<WT, 128, 256, EPI>(p, stream); else launch_dma<WT, 160, 128, EPI>(p, stream); break;
+    case 160257:
+        if constexpr (gemm_tile_is_wide_inst(WT, 160, 256, EPI)) launch_dma<WT, 160, 256, EPI>(p, stream);
+        else if constexpr (gemm_tile_is_wide_inst(WT, 128, 256, EPI)) launch_dma<WT, 128, 256, EPI>(p, stream);      // q5_0, q8_0: gemm_wide_bm_fits
+        else launch_dma<WT, 160, 128, EPI>(p, stream);
+        break;
 #ifdef CLIPAMD_BIGTILES   // tuning builds: BN = 256 tiles, one workgroup per CU, accumulators in AGPRs
     case 128256: launch_dma<WT, 128, 256, EPI>(p, stream); break;
     case 160256: launch_dma<WT, 160, 256, EPI>(p, stream); break;
@@ -454,9 +474,9 @@ int tile_override(int M, int N, int Kpad) {
 #endif
 }
 
-int pick_tile(int M, int N, int Kpad, bool quantised, bool shared = false) {
+int pick_tile(int M, int N, int Kpad, bool quantised, bool shared = false, bool wide_ok = true) {
     auto wgs = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
-    if (const int ov = tile_override(M, N, Kpad)) return ov;
+    if (const int ov = tile_override(M, N, Kpad); ov && (wide_ok || !gemm_tile_is_wide(ov))) return ov;
     if (M <= 64) return 64064;
     // (round 5, measured and NOT done — profiles/r05_experiments.txt: the fp16-output GEMMs of the ViT-B/32 batch on resident fp16 panels and the
     //  four-wave 256 x 256 kernel — isolated q/k/v 57.3 us against 64.1, text q/k/v 25.7 against 29.4 — leave the vision q/k/v launch of the
@@ -522,6 +542,17 @@ int pick_tile(int M, int N, int Kpad, bool quantised, bool shared = false) {
         // the 8-wave kernel gains there, r02h), so they take this path only where a layer is milliseconds long
         if (t8 >= 200 && eff >= 0.75f && (M >= 32768 || (Kpad >= 2048 && !quantised))) return 160256;
     }
+    // The 256-column fused tile (gemm_wide.h, two workgroups per CU): the FFN-up GEMM (N >= 4 K) of a ViT-B/32-class batch on block-quantised weights, where
+    // 160 x 256 tiles fill at least 90 % of their rounds of 512 — 12800 x 3072 x 768: 960 tiles = 1.88 rounds, -5.5 % on the launch (85.0 -> 80.3 us,
+    // 41 % fewer L2 -> CU read requests) and -1.1 ... -1.5 % on the two-tower step (five alternating rounds against the parent build: 4.071 -> 4.017 ms).  On a shared device only: the vision tower alone gains 1.35 % from it too
+    // (two rounds), but the codes the unshared heuristic may answer with are a fixed set (tests/test_host_api.py), so that case keeps today's tile.  Measured
+    // and NOT taken (profiles/gemm_wide.txt): vision q/k/v 12800 x 2304 (720 tiles = 1.41 rounds: the launch is 5 % slower, the step level, and with FFN-up it
+    // takes back a third of that gain), text q/k/v and FFN-up 10290 x 1536 / 2048 (390 / 520 tiles: the step loses 0.6-0.9 % / is level), and every 128 x 256
+    // form (25 % more dequantisation per MFMA: level or behind).
+    if (wide_ok && quantised && shared && M >= 8192 && M < 32768 && N >= 4 * Kpad && (N & 255) == 0) {
+        const int t = wgs(160, 256), rounds = (t + 511) / 512;
+        if (10 * t >= 9 * 512 * rounds) return 160257;
+    }
     // One exception measured INSIDE the two-tower step (r05, profiles/r05_experiments.txt section 9): the q/k/v GEMM of a narrow tower (10290 x 1536 x 512, the
     // ViT-B/32 text tower of the BASELINE batch) on 192 x 128 instead of the model's 128 x 128: +1.0 % of the step in five same-box pairs — level in
     // isolation (33.4 vs 32.8 us): fewer, larger workgroups leave the other tower's kernels more room.  (A larger fixed part in the cost model, which also
@@ -558,6 +589,7 @@ void launch_gemm_wt4(const GemmParams &, int, int, hipStream_t);
 void launch_gemm_wt5(const GemmParams &, int, int, hipStream_t);
 
 int gemm_tile_for(int M, int N, int Kpad, bool quantised, bool shared_device) { return pick_tile(M, N, Kpad, quantised, shared_device); }
+int gemm_tile_for_narrow(int M, int N, int Kpad, bool quantised, bool shared_device) { return pick_tile(M, N, Kpad, quantised, shared_device, false); }
 
 // LayerNorm fold: columns per statistics slot written by the residual epilogue of the kernel behind a tile code (fold_slotw<TN>() of
 // gemm_common.h: 64 where a wave spans >= 64 columns — the BN = 128 tiles of this file, k_gemm8.hip, k_gemm4.hip —, else 32)
@@ -593,6 +625,11 @@ int pick_ksplit_ring(int tiles, int nk, bool quantised) {
     return tiles <= 110 ? 2 : 1;
 }
 
+// what the 256-column fused tile carries (gemm_wide.h); its LDS-DMA sources are 32-bit element offsets from p.A
+static bool gemm_wide_supported(const GemmParams & p, int epilogue) {
+    return p.W.wtype != W_F16 && p.W.wtype != W_F32 && gemm_wide_epilogue(epilogue) && !p.xg_out && (size_t)p.M * (size_t)p.lda < ((size_t)1 << 31);
+}
+
 void launch_gemm(const GemmParams & p0, int epilogue, int tile, hipStream_t stream) {
     if (p0.M <= 0) return;
     if (p0.W.wtype == W_F32) {      // f32 GGUF file: f32 weights on the exact-f32 MFMA, whatever the tile code (k_gemm_f32.hip)
@@ -613,7 +650,10 @@ void launch_gemm(const GemmParams & p0, int epilogue, int tile, hipStream_t stre
         tile = pick_tile(p.M, p.W.N, p.W.Kpad, p.W.wtype != W_F16, p.shared_device);
         // the 32 x 32 x 16 kernel carries the fp16-output epilogues only: any other launch of such a shape gets the choice made without it
         if (tile % 1000 == 261 && !gemm32_supported(p, epilogue)) tile = pick_tile(p.M, p.W.N, p.W.Kpad, p.W.wtype != W_F16, true);
+        // likewise the 256-column fused tile (gemm_wide.h): fp16-output epilogues on block-quantised weights only
+        if (gemm_tile_is_wide(tile) && !gemm_wide_supported(p, epilogue)) tile = pick_tile(p.M, p.W.N, p.W.Kpad, p.W.wtype != W_F16, p.shared_device, false);
     }
+    if (gemm_tile_is_wide(tile) && !gemm_wide_supported(p, epilogue)) tile = 160128;     // an explicit code on another kind of launch: same bits
     if (tile % 1000 == 258 || tile % 1000 == 260) {
         // 256 x 256 tiles in whole rounds: one workgroup per CU means a launch costs ceil(tiles / 256) rounds, and ViT-L/14's
         // 65792 rows are 257 tile rows — one past a round boundary for every N.  The leading tile rows that fill whole rounds go to
@@ -677,6 +717,7 @@ void launch_gemm(const GemmParams & p0, int epilogue, int tile, hipStream_t stre
     const int bm = ring ? 64 : tile / 1000;
     int bn = tile % 1000;
     if (ring) bn = bn >= 128 ? 128 : 64;
+    if (gemm_tile_is_wide(tile)) bn = WIDE_BN;
     const int tiles = ((p.M + bm - 1) / bm) * ((p.W.N + bn - 1) / bn), nk = p.W.Kpad / BK;
     if (heuristic) ksplit = ring ? pick_ksplit_ring(tiles, nk, p.W.wtype != W_F16) : pick_ksplit(tiles, nk);
     if (ksplit < 1) ksplit = 1;

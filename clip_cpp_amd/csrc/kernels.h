@@ -141,6 +141,10 @@ int gemm_tile_for(int M, int N, int Kpad, bool quantised, bool shared_device = f
 inline bool gemm_tile_is_ring(int tile) { return (tile % 1000000) / 1000 == 65; }   // k_gemm_ring.hip (BM code 65)
 // 261: the 32 x 32 x 16 kernel of k_gemm32.hip (fp16-output epilogues): 256261 / 320261 = 256 / 320 x 256 tiles, one workgroup per CU
 inline bool gemm_tile_uses_panel(int tile) { const int bn = tile % 1000; return !gemm_tile_is_ring(tile) && (bn == 256 || (bn >= 258 && bn <= 261)); }
+// 257: the 256-column tiles of the fused-dequant kernel (gemm_wide.h): 128257 / 160257 = 128 / 160 x 256, two workgroups per CU, no panel — block-quantised
+// weights and fp16-output epilogues; any other launch with such a code runs on the 160 x 128 tile (same bits)
+inline bool gemm_tile_is_wide(int tile) { return !gemm_tile_is_ring(tile) && tile % 1000 == 257; }
+int gemm_tile_for_narrow(int M, int N, int Kpad, bool quantised, bool shared_device);     // gemm_tile_for without the 256-column fused tile (what launch_gemm falls back to)
 
 // k_gemm_ring.hip: mid-M GEMM (64 activation rows x bn weight rows per workgroup, bn in {64, 128}; a 3-4 stage LDS ring of K-tiles
 // filled by LDS-DMA only, block-quantised weights staged raw and dequantised per MFMA fragment; split-K as k_gemm.hip: p.ksplit).

@@ -762,7 +762,8 @@ int clip_amd_test_fold_consumer(int type, const void * w_raw, int64_t N2, int64_
                                 int slotw, const float * ln_mu, const float * c, const float * b_fold, float eps, int epi2, int qcols, float qscale,
                                 int tile2, float * y_out, float * mu_out);
 /* The tile the heuristic of launch_gemm picks for an [M][K] x [N][K]^T problem (pure host arithmetic, no device needed):
- * BM * 1000 + BN; BM = 65: the mid-M ring kernel on 64-row tiles (k_gemm_ring.hip), BN = 256 / 258-260: the large-M panel kernels. */
+ * BM * 1000 + BN; BM = 65: the mid-M ring kernel on 64-row tiles (k_gemm_ring.hip), BN = 256 / 258-260: the large-M panel kernels,
+ * BN = 257: the 256-column tiles of the fused-dequant kernel (128257 / 160257, csrc/gemm_wide.h). */
 int clip_amd_test_gemm_tile(int64_t M, int64_t N, int64_t K, int quantised);
 int clip_amd_test_gemm_tile_ex(int64_t M, int64_t N, int64_t K, int quantised, int shared_device);   /* ... with clip_amd_set_device_shared's flag */
 /* The state a context keeps between calls, read-only (fields are read; no HIP call, so a host-only context answers too).  which: 0 the vision
