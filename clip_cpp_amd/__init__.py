@@ -834,6 +834,9 @@ class Index:
     stored in f16 (default) or f32; search returns (distances f32 [nq, k], ids int64 [nq, k]) sorted by ascending 1 - cosine, equal
     distances lower id first, -1 / +inf past the index size.  range_search (every row within a radius of each query) and pairs (every pair
     of rows within a radius: near-duplicates) report the same distances, bit for bit.  Keep the `Clip` alive while the index is in use.
+    A row or query with a NaN or an infinity is the zero vector (distance exactly 1 to everything); a finite one is normalised
+    independently of its scale (x and x * 2**e store the same bits, from subnormals to values near the f32 maximum), so what the f32 /
+    f16 index stores is always finite and within 1 in magnitude; load() refuses a file that holds anything else.
 
     "i8" (dtype code 3) stores each row as int8, a quarter of f32's bytes: in f32, amax = max |x|, q = rint((x / amax) * 127) (half to
     even; numpy: np.rint((x / amax).astype(np.float32) * np.float32(127))), no L2 normalisation first (the mapping is scale-invariant).

@@ -9,8 +9,11 @@
 //             i8: the exact i32 dot on v_mfma_i32_16x16x64_i8, score = (float)dot * qinv * rinv
 //
 // Kernels:
-//   search_normalize_kernel  one wave per row: f32 sum of squares (fixed lane order + butterfly), x / sqrt(ss) (zero rows stay zero),
-//                            written in the stored dtype with the zero padding; rows past the source count are written as zeros.
+//   search_normalize_kernel  one wave per row: max |x| and a non-finite flag (a row with amax 0 or any NaN / inf is the zero row), the row
+//                            scaled by the power of two that brings amax into [0.5, 1) (exact), its f32 sum of squares (fixed lane order +
+//                            butterfly), x / sqrt(ss), written in the stored dtype with the zero padding; rows past the source count are
+//                            written as zeros.  The stored row is finite, of magnitude <= 1 and the same for x and x 2^e; without the
+//                            scaling step the bits are the same wherever its sum of squares neither overflows nor underflows.
 //   search_quantize_kernel   the i8 form: one wave per row: max |x| and a non-finite flag (a row with amax 0 or any NaN / inf is the zero
 //                            row), rint(x / amax * 127) packed 4 per lane store with the zero padding, the exact integer sum of squares
 //                            -> inv; rows past the source count are written as zeros (inv 0).
@@ -86,13 +89,34 @@ __global__ void __launch_bounds__(256) search_normalize_kernel(const float * __r
         return;
     }
     const float * s = src + row * dim;
+    float amax = 0.f;
+    int bad = 0;
+    for (int i = lane; i < dim; i += 64) {
+        const float a = fabsf(s[i]);
+        bad |= !(a <= FLT_MAX);                                // NaN or inf (fmaxf alone would skip a NaN)
+        amax = fmaxf(amax, a);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        amax = fmaxf(amax, __shfl_xor(amax, off, 64));
+        bad |= __shfl_xor(bad, off, 64);
+    }
+    const bool zero = bad || !(amax > 0.f);
+    // amax = m 2^e with m in [0.5, 1): x 2^-e is exact unless an element 2^-125 below the row's largest loses bits as a subnormal, and
+    // the squares of the scaled row can neither overflow (ss <= dim) nor vanish (ss >= 0.25).  Scaling by a power of two commutes with
+    // every rounding below while nothing overflows or underflows, so such rows keep the bits of x / sqrtf(sum x^2).
+    int e = 0;
+    if (!zero) (void)frexpf(amax, &e);
     float ss = 0.f;
-    for (int i = lane; i < dim; i += 64) ss += s[i] * s[i];
+    for (int i = lane; i < dim; i += 64) {
+        const float x = ldexpf(s[i], -e);
+        ss += x * x;
+    }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
     const float nrm = sqrtf(ss);
     for (int i = lane; i < Dpad; i += 64) {
-        const float v = (i < dim && ss > 0.f) ? s[i] / nrm : 0.f;
+        const float v = (i < dim && !zero) ? ldexpf(s[i], -e) / nrm : 0.f;
         d[i] = (T)v;
     }
 }

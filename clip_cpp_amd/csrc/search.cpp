@@ -282,6 +282,28 @@ bool stage_inputs(clip_amd_index * ix, const float * queries, int nq, const uint
 bool valid_dim(int dim) { return dim >= 4 && dim <= 4096 && dim % 4 == 0; }
 bool valid_dtype(int64_t dtype) { return dtype == SEARCH_F32 || dtype == SEARCH_F16 || dtype == SEARCH_I8; }
 
+// An f32 / fp16 store holds only finite values of magnitude <= 1: the normalising kernel writes nothing else (sqrtf(fl(sum x^2)) >= |x_i|
+// by the monotonicity of rounding), and the strict order of candidates and the ordered-bits atomic folds of the join, extents, spread and
+// linkage kernels rest on it.  True when count values of a file keep to that (the bits of |v| against those of 1.0: a NaN or an
+// infinity compares above); every i8 byte is a legal value.
+bool stored_values_valid(const unsigned char * p, size_t count, int dtype) {
+    size_t out = 0;
+    if (dtype == SEARCH_F32) {
+        for (size_t i = 0; i < count; i++) {
+            uint32_t b;
+            memcpy(&b, p + 4 * i, 4);
+            out += (b & 0x7fffffffu) > 0x3f800000u;
+        }
+    } else if (dtype == SEARCH_F16) {
+        for (size_t i = 0; i < count; i++) {
+            uint16_t b;
+            memcpy(&b, p + 2 * i, 2);
+            out += (b & 0x7fffu) > 0x3c00u;
+        }
+    }
+    return out == 0;
+}
+
 clip_amd_index * make_index(clip_ctx * ctx, int device, int dim, int dtype) {
     clip_amd_index * ix = new clip_amd_index;
     ix->ctx = ctx;
@@ -2081,12 +2103,22 @@ struct clip_amd_index * clip_amd_index_load(struct clip_ctx * ctx, const char * 
         if (ok && n) launch_live_set(s.live, 0, (int64_t)n, st);
         const size_t row_bytes = (size_t)dim * es;
         std::vector<unsigned char> buf((size_t)std::min<uint64_t>(HOST_CHUNK_ROWS, std::max<uint64_t>(n, 1)) * row_bytes);
+        bool valid = true;
         for (int64_t r0 = 0; ok && r0 < (int64_t)n; r0 += HOST_CHUNK_ROWS) {
             const int64_t m = std::min<int64_t>(HOST_CHUNK_ROWS, (int64_t)n - r0);
-            ok = fread(buf.data(), row_bytes, (size_t)m, in.f) == (size_t)m &&
-                 hipMemcpy2DAsync((char *)s.rows + (size_t)r0 * row_stride(ix), row_stride(ix), buf.data(), row_bytes, row_bytes, (size_t)m,
-                                  hipMemcpyHostToDevice, st) == hipSuccess &&
+            ok = fread(buf.data(), row_bytes, (size_t)m, in.f) == (size_t)m;
+            if (ok && !stored_values_valid(buf.data(), (size_t)m * dim, (int)dtype)) {
+                valid = ok = false;
+                break;
+            }
+            ok = ok && hipMemcpy2DAsync((char *)s.rows + (size_t)r0 * row_stride(ix), row_stride(ix), buf.data(), row_bytes, row_bytes, (size_t)m,
+                                        hipMemcpyHostToDevice, st) == hipSuccess &&
                  hipStreamSynchronize(st) == hipSuccess;
+        }
+        if (!valid) {
+            fprintf(stderr, "%s: '%s' holds a value that is not finite or of magnitude above 1: not rows that an index stored\n", fn, path);
+            free_index(ix);
+            return nullptr;
         }
         if (ok && ix->dtype == SEARCH_I8) {          // the file holds the rows only: their inverse norms again, the same integer arithmetic
             launch_search_row_inv(s.rows, (int64_t)n, ix->Dpad, s.rinv, st);

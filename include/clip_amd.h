@@ -193,6 +193,19 @@ int clip_amd_profile_report(struct clip_ctx * ctx, char * buf, int cap, bool res
  * index for the same job) ----
  * Cosine distance d = 1 - <q/|q|, g/|g|>: rows are L2-normalised in f32 when added, queries when searched (a zero vector stays zero:
  * distance exactly 1), both stored in the index dtype (0 = f32, 1 = f16: the normalised values rounded to fp16), dot products in f32.
+ * The f32 / f16 store holds only finite values of magnitude <= 1; every kernel that orders or folds distances relies on it, and add,
+ * the query path and load each keep it:
+ *   1. a row or query with any NaN or +-inf element is the zero vector (distance exactly 1 to everything, lowest ids first), as for i8;
+ *      an add never fails over its values (the device-pointer forms are asynchronous);
+ *   2. for finite input the stored vector does not depend on a power-of-two scale of the input: x and x 2^e give the same stored bits
+ *      whenever x 2^e is computed exactly (no element overflows or loses bits to underflow), rows of subnormals included.  In f32, in
+ *      this order, without FMA contraction: amax = max_i |x_i| = m 2^e with m in [0.5, 1), y_i = x_i 2^-e (exact), ss = sum_i y_i^2
+ *      (lane i % 64 adds its values in ascending i, then the xor butterfly 32 ... 1 over the 64 lanes), stored_i = y_i / sqrtf(ss);
+ *   3. wherever the sum of squares of the unscaled row neither overflows nor underflows these are the bits of x_i / sqrtf(sum_i x_i^2)
+ *      in the same order, which is what every earlier version stored: saved indexes keep searching identically;
+ *   4. clip_amd_index_load returns NULL, with a message, for an f32 or f16 file that holds a non-finite value or one of magnitude
+ *      above 1 (add cannot write either: sqrtf(fl(ss)) >= |y_i|); rows that are finite and within 1 but not of unit length are not
+ *      looked for.  i8 files are unaffected: every byte is a legal value and the inverse norms are recomputed.
  * dtype 3 = i8 (2 is reserved): each row when added and each query when searched is quantised in f32, in this order, without FMA
  * contraction: amax = max_i |x_i|, q_i = (int8) rintf((x_i / amax) * 127.0f) (half to even; |x_i / amax| <= 1, no clamp); no L2
  * normalisation first (the mapping is scale-invariant).  A vector with amax == 0 or any NaN / inf is stored as the zero vector
