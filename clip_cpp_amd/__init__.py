@@ -96,6 +96,8 @@ AMD_SYMBOLS = [
     "clip_amd_test_index_linkage_rounds",
     "clip_amd_index_linkage_core", "clip_amd_index_linkage_core_device", "clip_amd_bench_linkage_core", "clip_amd_bench_linkage_core_parts",
     "clip_amd_index_extents", "clip_amd_index_extents_device", "clip_amd_bench_extents", "clip_amd_test_index_extents_route",
+    "clip_amd_index_vote", "clip_amd_index_vote_device", "clip_amd_index_vote_ids", "clip_amd_index_vote_graph", "clip_amd_index_vote_graph_device",
+    "clip_amd_test_index_vote_block", "clip_amd_bench_vote_graph",
 ]
 
 _lib = None
@@ -380,6 +382,20 @@ def lib():
     L.clip_amd_test_index_knn_route.argtypes = [vp, i32]
     L.clip_amd_bench_knn.restype = C.c_float
     L.clip_amd_bench_knn.argtypes = [i32, i64, i32, i32, i32, i32]
+    L.clip_amd_index_vote.restype = C.c_bool
+    L.clip_amd_index_vote.argtypes = [vp, f32p, i32, i32, i32, i32p, u64p, i32p, i32p, f32p, i64p]
+    L.clip_amd_index_vote_device.restype = C.c_bool
+    L.clip_amd_index_vote_device.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.clip_amd_index_vote_ids.restype = C.c_bool
+    L.clip_amd_index_vote_ids.argtypes = [vp, i64p, i64, i32, i32, i32, i32p, u64p, i32p, i32p, f32p, i64p]
+    L.clip_amd_index_vote_graph.restype = C.c_bool
+    L.clip_amd_index_vote_graph.argtypes = [vp, i32, i32, i32p, u64p, i32p, i32p, f32p, i64p]
+    L.clip_amd_index_vote_graph_device.restype = C.c_bool
+    L.clip_amd_index_vote_graph_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.clip_amd_test_index_vote_block.restype = i64
+    L.clip_amd_test_index_vote_block.argtypes = [vp, i64]
+    L.clip_amd_bench_vote_graph.restype = C.c_float
+    L.clip_amd_bench_vote_graph.argtypes = [i32, i64, i32, i32, i32, i32, i32, i32]
     L.clip_amd_index_search_index.restype = C.c_bool
     L.clip_amd_index_search_index.argtypes = [vp, vp, i64p, i64, i32, u64p, f32p, i64p]
     L.clip_amd_index_append.restype = i64
@@ -891,6 +907,10 @@ class Index:
     at most once, with the query row that matched.  search_ids_sets does the same with stored rows as the queries and can leave a set's
     own group out (two gridded images match through their best pair of regions, and no image matches itself); knn_graph_grouped is that
     for every group of the index at once.
+
+    vote(queries, k, labels, m) files queries by example: `labels` gives every row a class (-1: unlabelled), the k nearest labelled rows
+    vote, and the m best classes come back by votes, then by their nearest member, each with that member's distance and id; vote_ids takes
+    stored rows as the queries and vote_graph every row at once, itself excluded: the audit of a labelling (clip_amd_index_vote*).
 
     search_distinct(queries, k, radius) folds near-duplicates into one hit: over the query's `pool` nearest rows, walked in search's order,
     a row within `radius` (the distance of pairs) of an earlier kept row is dropped and counted for it; search_ids_distinct does the same
@@ -1598,6 +1618,100 @@ class Index:
             raise RuntimeError("clip_amd_index_knn_graph failed (see stderr)")
         return dist, ids
 
+    def _labels(self, labels):
+        """(keep-alive int32 array, pointer) of one label per row for the votes: >= 0 a class, -1 unlabelled (ValueError for None, a wrong
+        length, a non-integer or a label outside -1 ... 2^31 - 1).  Pure numpy: needs no device."""
+        if labels is None:
+            raise ValueError("labels must be integers, not None")
+        a = np.asarray(labels)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("labels must be integers, not %s" % a.dtype)
+        a = a.reshape(-1)
+        if a.size != len(self):
+            raise ValueError("labels must have one entry per row: %d, not %d" % (len(self), a.size))
+        if a.size and (int(a.min()) < -1 or int(a.max()) > 2 ** 31 - 1):
+            raise ValueError("labels must lie in -1 ... 2^31 - 1 (-1: unlabelled), not %d ... %d" % (int(a.min()), int(a.max())))
+        a = np.zeros(a.size + 1, dtype=np.int32)[:a.size] if a.size == 0 else np.ascontiguousarray(a, dtype=np.int32)
+        return a, a.ctypes.data_as(C.POINTER(C.c_int32))
+
+    @staticmethod
+    def _vote_km(k, m):
+        """(k, m) as ints after the check 1 <= m <= k <= 1024 (ValueError)"""
+        k, m = int(k), int(m)
+        if not 1 <= m <= k <= 1024:
+            raise ValueError("a vote needs 1 <= m <= k <= 1024, not m = %d, k = %d" % (m, k))
+        return k, m
+
+    @staticmethod
+    def _vote_outputs(n, m):
+        out = (np.empty((n, m), dtype=np.int32), np.empty((n, m), dtype=np.int32), np.empty((n, m), dtype=np.float32),
+               np.empty((n, m), dtype=np.int64))
+        i32p, i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        return out, (out[0].ctypes.data_as(i32p), out[1].ctypes.data_as(i32p), _fp(out[2]), out[3].ctypes.data_as(i64p))
+
+    def vote(self, queries, k, labels, m=1, allow=None):
+        """k-NN vote over labelled rows: `labels` (int [len]) is every row's class (>= 0, any numbering) or -1 for an unlabelled row; the
+        voters are the live, allowed, labelled rows.  Per query, L = its k nearest voters in search's order (search(..., allow=voters));
+        the classes of L by votes (entries in L) descending, then by the rank of the class's nearest entry, cut to m.  Returns (classes
+        int32 [nq, m], votes int32 [nq, m], distances f32 [nq, m], ids int64 [nq, m]): per class its number, its votes, and the distance
+        (search's bits) and row of its nearest voter; -1 / 0 / +inf / -1 where L holds fewer classes.  k = 1: nearest-neighbour
+        classification.  ValueError unless 1 <= m <= k <= 1024 and the labels are right."""
+        k, m = self._vote_km(k, m)
+        lab, lp = self._labels(labels)
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        words, wp = self._allow(allow)
+        out, ptrs = self._vote_outputs(q.shape[0], m)
+        if not lib().clip_amd_index_vote(self._live(), _fp(q), q.shape[0], k, m, lp, wp, *ptrs):
+            raise RuntimeError("clip_amd_index_vote failed (see stderr)")
+        return out
+
+    def vote_ids(self, ids, k, labels, m=1, exclude_self=True, allow=None):
+        """vote with the stored rows `ids` (each a live id) as the queries, bit for bit as search_ids takes them; exclude_self: a row does
+        not vote for itself.  The query rows need not be labelled or allowed."""
+        k, m = self._vote_km(k, m)
+        lab, lp = self._labels(labels)
+        a = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        words, wp = self._allow(allow)
+        out, ptrs = self._vote_outputs(a.size, m)
+        if not lib().clip_amd_index_vote_ids(self._live(), a.ctypes.data_as(C.POINTER(C.c_int64)), a.size, k, m, int(bool(exclude_self)), lp, wp, *ptrs):
+            raise RuntimeError("clip_amd_index_vote_ids failed (see stderr)")
+        return out
+
+    def vote_graph(self, k, labels, m=1, allow=None):
+        """vote for every row at once, each row excluded from its own vote (leave-one-out): [len, m] arrays as vote's; row i equals
+        vote_ids([i], ...) bit for bit for a live row, and is empty for a removed one.  On the routes of knn_graph."""
+        k, m = self._vote_km(k, m)
+        lab, lp = self._labels(labels)
+        words, wp = self._allow(allow)
+        out, ptrs = self._vote_outputs(len(self), m)
+        if not lib().clip_amd_index_vote_graph(self._live(), k, m, lp, wp, *ptrs):
+            raise RuntimeError("clip_amd_index_vote_graph failed (see stderr)")
+        return out
+
+    def vote_device(self, d_queries, n_queries, k, d_labels, d_classes, d_votes, d_distances, d_ids, m=1, d_allow=None):
+        """vote on device pointers (ints): queries [n, dim] f32, labels [len] int32 (trusted: any negative value is unlabelled), d_allow
+        uint64 words (0 / None: every row) -> classes / votes int32, distances f32, ids int64, [n, m] each; asynchronous on the context's
+        stream."""
+        k, m = self._vote_km(k, m)
+        if not lib().clip_amd_index_vote_device(self._live(), C.c_void_p(d_queries), int(n_queries), k, m, C.c_void_p(d_labels or None),
+                                                C.c_void_p(d_allow or None), C.c_void_p(d_classes), C.c_void_p(d_votes), C.c_void_p(d_distances),
+                                                C.c_void_p(d_ids)):
+            raise RuntimeError("clip_amd_index_vote_device failed (see stderr)")
+
+    def vote_graph_device(self, k, d_labels, d_classes, d_votes, d_distances, d_ids, m=1, d_allow=None):
+        """vote_graph on device pointers (ints), outputs [len, m] each: no result visits the host"""
+        k, m = self._vote_km(k, m)
+        if not lib().clip_amd_index_vote_graph_device(self._live(), k, m, C.c_void_p(d_labels or None), C.c_void_p(d_allow or None),
+                                                      C.c_void_p(d_classes), C.c_void_p(d_votes), C.c_void_p(d_distances), C.c_void_p(d_ids)):
+            raise RuntimeError("clip_amd_index_vote_graph_device failed (see stderr)")
+
+    def vote_block(self, rows=0):
+        """test hook: query rows per block of the votes from now on (0: automatic); returns the value set"""
+        r = int(lib().clip_amd_test_index_vote_block(self._live(), int(rows)))
+        if r < 0:
+            raise ValueError("vote_block: rows must lie in 0 ... 65408, not %d" % int(rows))
+        return r
+
     def search_index(self, src, k, ids=None, allow=None):
         """This index searched with the stored rows of `src` (an Index of the same Clip, dim and dtype without removed rows): every row in
         id order, or the rows `ids` (duplicates and any order are fine).  (distances f32 [n, k], ids int64 [n, k]) as `search` gives them
@@ -1838,6 +1952,12 @@ def bench_spread(dtype, n, dim, n_max, copies=0, iters=3):
     """Microseconds of device time per clip_amd_index_spread_device of n_max centres, no seeds, no stop radius; the data of bench_modes
     (clip_amd_bench_spread); < 0 on error."""
     return float(lib().clip_amd_bench_spread(Index.DTYPES[dtype], int(n), int(dim), int(n_max), int(copies), int(iters)))
+
+
+def bench_vote_graph(dtype, n, dim, k, m=1, classes=64, route=0, iters=3):
+    """Microseconds (wall) per clip_amd_index_vote_graph over the n seeded random rows of bench_knn, a row's label a seeded hash of its
+    number modulo `classes`; route as bench_knn (clip_amd_bench_vote_graph); < 0 on error."""
+    return float(lib().clip_amd_bench_vote_graph(Index.DTYPES[dtype], int(n), int(dim), int(k), int(m), int(classes), int(route), int(iters)))
 
 
 def bench_knn(dtype, n, dim, k, route=0, iters=3):

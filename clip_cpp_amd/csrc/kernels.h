@@ -369,6 +369,17 @@ void launch_sets_fill(float * dist, int64_t * ids, int * qrows, int64_t count, h
 void launch_sets_qgroup(const int * groups, const int * qself, int * qgroup, int64_t n_rows, hipStream_t stream);
 void launch_sets_fold(const void * lists, int64_t stride, int64_t q0, int m, const int64_t * lims, int64_t s_lo, int64_t n_fold, int k,
                       const int * groups, float * dist, int64_t * ids, int * qrows, int64_t qrow_base, hipStream_t stream);
+// k-NN voting (k_vote.hip).  voters: the voter bitmap of `words` 32-bit words (layout of mask above; live has as many):
+// voters[w] = live[w] & allow[w] & {labels[32 w + b] >= 0}, allow NULL: every row, its words at w >= allow_words read as 0; labels (device,
+// one per stored row) are read only under a live bit.  *mixed (device, zeroed by the caller) := 1 when some live row is no voter.
+// fold: for each of nq queries its finished list (dist / ids [nq][k] as launch_search_finish leaves them) becomes the m best classes of
+// the list: classes / votes / odist / oids [nq][m], by votes descending, then the rank of the class's nearest entry, whose distance and id
+// are reported; -1 / 0 / +inf / -1 behind the last class.  ids NULL: every slot empty.  only_voters != NULL: query q is stored row
+// row0 + q and is folded only when that row is live (live, never NULL then) and no voter; the slots of any other query are not touched.
+void launch_vote_voters(const uint32_t * live, const uint32_t * allow, int64_t allow_words, const int * labels, uint32_t * voters, int64_t words,
+                        uint32_t * mixed, hipStream_t stream);
+void launch_vote_fold(const float * dist, const int64_t * ids, int64_t nq, int k, const int * labels, int m, int64_t row0, const uint32_t * live,
+                      const uint32_t * only_voters, int * classes, int * votes, float * odist, int64_t * oids, hipStream_t stream);
 // Searches by id.  gather: query t of n_rows (the padded count) := stored row ids[t] (device; NULL: row first + t) for t < n_ids, bit for bit
 // (i8: qinv[t] := rinv of that row), qself[t] := that id; an id outside [0, n) or with a cleared bit in live, and every t >= n_ids, gives the
 // zero row and qself -1.  launch_search_scan with qself != NULL never makes row qself[query] a candidate of that query; launch_search_finish

@@ -4,7 +4,7 @@
 // searches with query sets (the set fold of k_sets.hip in the finish's place), distinct searches (the pools of a search, then the near
 // bitmap and the walk of k_distinct.hip), compound queries (the placement and the scan of k_compound.hip in front of the same merge tree),
 // appending one index to another, the count -> lims -> scatter -> sort -> finish sequence of
-// range search and pairs (k_join.hip), connected components (the link -> flatten -> finish sequence of k_components.hip), density modes (k_modes.hip), the single-linkage tree (k_linkage.hip), the extents of a labelling (k_extents.hip), farthest-first selection (k_spread.hip), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
+// range search and pairs (k_join.hip), connected components (the link -> flatten -> finish sequence of k_components.hip), density modes (k_modes.hip), the single-linkage tree (k_linkage.hip), the extents of a labelling (k_extents.hip), farthest-first selection (k_spread.hip), k-NN voting over labelled rows (the voter bitmap and the fold of k_vote.hip as the sink of search_blocks), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
 // Replaces the usearch index of the reference's examples/image-search (build.cpp / search.cpp) with an exact search on the GPU.
 // Single owners: search_device_impl (the passes of a search: one ScanArgs per scan launch, whatever the selection), search_blocks and
 // query_block (the blocked host forms of stored-row queries), upload_allow / upload_groups / stage_inputs (a call's inputs on the device),
@@ -109,6 +109,11 @@ struct clip_amd_index {
     Buf sslot;                     // [centres + 1] the centres' keys (u64)
     Buf sseeds;                    // the seed ids copied from the host
     Buf spouts;                    // host form: count (int64), cover radius, centres + owners (int64), reaches + owner distances
+    // k-NN voting
+    Buf vvoters;                   // the voter bitmap (live & allow & labelled) and, behind it, the "some live row is no voter" word
+    Buf vlabels;                   // labels of a host form copied from the host
+    Buf vouts;                     // host forms: ids (int64) + classes + votes + distances of one query block
+    int64_t vote_block = 0;        // clip_amd_test_index_vote_block: query rows per block, 0 automatic
 };
 
 namespace {
@@ -644,6 +649,173 @@ bool search_index_impl(clip_amd_index * ix, const clip_amd_index * src, const in
                                       ix->cand.p, n_chunks, rpc, mask, st);
         },
         block_to_host(ix, k, distances, out_ids, fn));
+}
+
+// The four result arrays of a vote ([rows][m] each), on the device or on the host
+struct VoteOut {
+    int32_t * classes = nullptr;
+    int32_t * votes = nullptr;
+    float * dist = nullptr;
+    int64_t * ids = nullptr;
+};
+
+int64_t vote_block_size(const clip_amd_index * ix, int64_t nq, int k) { return ix->vote_block > 0 ? ix->vote_block : query_block(nq, k, 12); }
+
+// k-NN voting on the device (clip_amd_index_vote*): nq queries in blocks, each block searched with the voter bitmap of k_vote.hip as the
+// allowed set and folded by launch_vote_fold, the sink of search_blocks, into dest(q0) (device, [m_block][m]); done(q0, m_block) follows
+// every block (the host forms copy it out there).  source(q0, m_block) names a block's queries for the scan.  graph: the queries are the
+// stored rows 0 ... nq - 1 (nq == size), each excluded from its own list, on either route of knn_graph_impl.  The tiled kernel of
+// k_graph.hip scores only queries whose own bit stands in its mask, which is right for removed rows and wrong for a live row that is no
+// voter (unlabelled, or outside allow): such a row still asks.  So the route reads back one word, "some live row is no voter".  Without one
+// the voters are the live rows and the launch is knn_graph_impl's; with one, a block runs launch_graph under the voter bitmap for the
+// queries that vote, then launch_graph_cross of the store against itself under the same bitmap, folded only into the rows that are live
+// and no voter (such a row is not in the bitmap, so it cannot meet itself): two tile passes, the price of leaving k_graph.hip alone.
+template <typename Source, typename Dest, typename Done>
+bool vote_impl(clip_amd_index * ix, int64_t nq, int k, int m, bool graph, const int * d_labels, const uint32_t * d_allow, const char * fn,
+               Source && source, Dest && dest, Done && done) {
+    hipStream_t st = stream_of(ix);
+    const int64_t n = ix->n;
+    if (nq == 0) return true;
+    const int64_t block = vote_block_size(ix, nq, k);
+    uint32_t * voters = nullptr;
+    bool tiled = false, mixed = false;
+    if (n > 0) {
+        const size_t vb = live_bytes(n);
+        if (!ensure(ix, ix->vvoters, vb + 16)) return false;
+        voters = (uint32_t *)ix->vvoters.p;
+        uint32_t * d_mixed = (uint32_t *)((char *)ix->vvoters.p + vb);
+        (void)hipMemsetAsync(d_mixed, 0, 4, st);
+        launch_vote_voters(ix->store.live, d_allow, search_allow_words(n), d_labels, voters, (int64_t)(vb / 4), d_mixed, st);
+        if (hipGetLastError() != hipSuccess) { fprintf(stderr, "%s: launch failed\n", fn); return false; }
+        tiled = graph && (ix->knn_route ? ix->knn_route == 2 : n >= KNN_TILED_MIN_ROWS);
+        if (tiled) {
+            uint32_t h = 0;
+            if (!stream_done(ix, fn, hipMemcpyAsync(&h, d_mixed, 4, hipMemcpyDeviceToHost, st))) return false;
+            mixed = h != 0;
+        }
+    }
+    int n_chunks = 1;
+    int64_t rpc = (n + 127) / 128 * 128;
+    if (tiled) tiled_chunks(n, (block + 127) / 128 * 128, k, rpc, n_chunks);
+    const uint32_t * graph_mask = mixed ? voters : (ix->removed > 0 ? ix->store.live : nullptr);
+    for (int64_t q0 = 0; q0 < nq; q0 += block) {
+        const int mb = (int)std::min(block, nq - q0);
+        const VoteOut o = dest(q0);
+        const auto fold = [&](bool rest) {
+            return [&, rest](int64_t, int mm, const float * d_dist, const int64_t * d_ids) {
+                launch_vote_fold(d_dist, d_ids, mm, k, d_labels, m, q0, ix->store.live, rest ? voters : nullptr, o.classes, o.votes, o.dist, o.ids, st);
+                return hipGetLastError() == hipSuccess;
+            };
+        };
+        const auto no_source = [](int64_t, int) { return QuerySource(); };
+        const auto no_launch = [](int64_t, int) { return false; };
+        if (n == 0) {
+            launch_vote_fold(nullptr, nullptr, mb, k, nullptr, m, 0, nullptr, nullptr, o.classes, o.votes, o.dist, o.ids, st);
+            if (hipGetLastError() != hipSuccess) { fprintf(stderr, "%s: launch failed\n", fn); return false; }
+        } else if (!tiled) {
+            if (!search_blocks(ix, mb, k, block, false, 1, voters, fn, [&](int64_t, int) { return source(q0, mb); }, no_launch, fold(false))) return false;
+        } else {
+            if (!search_blocks(ix, mb, k, block, true, n_chunks, nullptr, fn, no_source,
+                               [&](int64_t, int mm) {
+                                   return launch_graph(ix->store.rows, ix->store.rinv, n, q0, mm, ix->Dpad, ix->dtype, k, ix->cand.p, n_chunks, rpc, graph_mask, st);
+                               },
+                               fold(false)))
+                return false;
+            if (mixed && !search_blocks(ix, mb, k, block, true, n_chunks, nullptr, fn, no_source,
+                                        [&](int64_t, int mm) {
+                                            return launch_graph_cross(ix->store.rows, ix->store.rinv, n, ix->store.rows, ix->store.rinv, n, q0, mm, ix->Dpad,
+                                                                      ix->dtype, k, ix->cand.p, n_chunks, rpc, voters, st);
+                                        },
+                                        fold(true)))
+                return false;
+        }
+        if (!done(q0, mb)) return false;
+    }
+    return true;
+}
+
+// The host forms of the votes: the queries are f32 vectors (queries), stored rows (ids), both on the host, or, with neither, every stored
+// row with itself excluded (the graph form).  Labels and the allowed set go up once; a block's queries are staged, its folded results
+// ([m_block][m]) land in the vouts workspace and are copied out before the next block, so nothing on the device grows with nq x k.
+bool vote_host(clip_amd_index * ix, const float * queries, const int64_t * ids, int64_t nq, int k, int m, bool exclude_self, const int32_t * labels,
+               const uint64_t * allow, const VoteOut & out, const char * fn) {
+    hipStream_t st = stream_of(ix);
+    if (nq == 0) return true;
+    const uint32_t * d_allow = nullptr;
+    const int * d_labels = nullptr;
+    if (!upload_allow(ix, allow, d_allow)) return false;
+    if (ix->n > 0) {
+        if (!ensure(ix, ix->vlabels, (size_t)ix->n * sizeof(int32_t))) return false;
+        if (hipMemcpyAsync(ix->vlabels.p, labels, (size_t)ix->n * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) {
+            fprintf(stderr, "%s: the upload of labels failed: %s\n", fn, hipGetErrorString(hipGetLastError()));
+            return false;
+        }
+        d_labels = (const int *)ix->vlabels.p;
+    }
+    const int64_t block = vote_block_size(ix, nq, k);
+    const size_t slots = (size_t)block * m;
+    if (!ensure(ix, ix->vouts, slots * 20)) return false;
+    if (ids ? !ensure(ix, ix->idbuf, (size_t)block * 8) : (queries && !ensure(ix, ix->stage, (size_t)block * ix->dim * 4))) return false;
+    VoteOut d;
+    d.ids = (int64_t *)ix->vouts.p;
+    d.classes = (int32_t *)((char *)ix->vouts.p + slots * 8);
+    d.votes = (int32_t *)((char *)ix->vouts.p + slots * 12);
+    d.dist = (float *)((char *)ix->vouts.p + slots * 16);
+    return vote_impl(
+        ix, nq, k, m, !ids && !queries, d_labels, d_allow, fn,
+        [&](int64_t q0, int mb) {
+            if (ids) {
+                (void)hipMemcpyAsync(ix->idbuf.p, ids + q0, (size_t)mb * 8, hipMemcpyHostToDevice, st);
+                return stored_rows((const int64_t *)ix->idbuf.p, 0, exclude_self);
+            }
+            if (queries) {
+                (void)hipMemcpyAsync(ix->stage.p, queries + (size_t)q0 * ix->dim, (size_t)mb * ix->dim * 4, hipMemcpyHostToDevice, st);
+                return vectors((const float *)ix->stage.p);
+            }
+            return stored_rows(nullptr, q0, true);
+        },
+        [&](int64_t) { return d; },
+        [&](int64_t q0, int mb) {
+            const size_t to = (size_t)q0 * m, cnt = (size_t)mb * m;
+            (void)hipMemcpyAsync(out.classes + to, d.classes, cnt * 4, hipMemcpyDeviceToHost, st);
+            (void)hipMemcpyAsync(out.votes + to, d.votes, cnt * 4, hipMemcpyDeviceToHost, st);
+            (void)hipMemcpyAsync(out.dist + to, d.dist, cnt * 4, hipMemcpyDeviceToHost, st);
+            (void)hipMemcpyAsync(out.ids + to, d.ids, cnt * 8, hipMemcpyDeviceToHost, st);
+            return stream_done(ix, fn, hipGetLastError());      // (the staging buffers and the block's results are reused)
+        });
+}
+
+// The device forms: queries, labels and allowed set on the device, results straight into the caller's arrays
+bool vote_device(clip_amd_index * ix, const float * d_queries, int64_t nq, int k, int m, const int * d_labels, const uint32_t * d_allow,
+                 const VoteOut & out, const char * fn) {
+    return vote_impl(
+        ix, nq, k, m, !d_queries, d_labels, ix->n > 0 ? d_allow : nullptr, fn,
+        [&](int64_t q0, int) { return d_queries ? vectors(d_queries + (size_t)q0 * ix->dim) : stored_rows(nullptr, q0, true); },
+        [&](int64_t q0) {
+            const size_t to = (size_t)q0 * m;
+            VoteOut o;
+            o.classes = out.classes + to;
+            o.votes = out.votes + to;
+            o.dist = out.dist + to;
+            o.ids = out.ids + to;
+            return o;
+        },
+        [](int64_t, int) { return true; });
+}
+
+// what the votes ask beyond the index and k: 1 <= m <= k, result pointers when there is a row to write, labels when there is a row to
+// label; host_labels: each of them >= -1
+bool check_vote_args(const clip_amd_index * ix, int k, int m, bool any_rows, const int32_t * labels, bool host_labels, const VoteOut & o,
+                     const char * fn) {
+    if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+    if (k < 1 || k > MAX_K) { fprintf(stderr, "%s: k = %d outside 1 ... %d\n", fn, k, MAX_K); return false; }
+    if (m < 1) { fprintf(stderr, "%s: m = %d < 1\n", fn, m); return false; }
+    if (m > k) { fprintf(stderr, "%s: m = %d exceeds k = %d\n", fn, m, k); return false; }
+    if (any_rows && (!o.classes || !o.votes || !o.dist || !o.ids)) { fprintf(stderr, "%s: NULL result pointer\n", fn); return false; }
+    if (!labels && ix->n > 0) { fprintf(stderr, "%s: labels is NULL\n", fn); return false; }
+    for (int64_t r = 0; host_labels && labels && r < ix->n; r++)
+        if (labels[r] < -1) { fprintf(stderr, "%s: labels[%lld] = %d is below -1 (unlabelled)\n", fn, (long long)r, (int)labels[r]); return false; }
+    return true;
 }
 
 // what clip_amd_index_search_index and clip_amd_index_append ask of their two indexes
@@ -2338,6 +2510,97 @@ bool clip_amd_index_knn_graph(struct clip_amd_index * ix, int k, float * distanc
         if (ix->n > 0 && (!distances || !ids)) { fprintf(stderr, "%s: NULL result pointer\n", fn); return false; }
         (void)hipSetDevice(ix->device);
         return knn_graph_impl(ix, k, distances, ids, fn);
+    });
+}
+
+static VoteOut vote_out(int32_t * classes, int32_t * votes, float * distances, int64_t * ids) {
+    VoteOut o;
+    o.classes = classes;
+    o.votes = votes;
+    o.dist = distances;
+    o.ids = ids;
+    return o;
+}
+
+bool clip_amd_index_vote(struct clip_amd_index * ix, const float * queries, int n_queries, int k, int m, const int32_t * labels,
+                         const uint64_t * allow, int32_t * classes, int32_t * votes, float * distances, int64_t * ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        const VoteOut out = vote_out(classes, votes, distances, ids);
+        if (!check_search_args(ix, queries, n_queries, k, distances, ids, fn)) return false;
+        if (!check_vote_args(ix, k, m, n_queries > 0, labels, true, out, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return vote_host(ix, queries, nullptr, n_queries, k, m, false, labels, allow, out, fn);
+    });
+}
+
+bool clip_amd_index_vote_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int k, int m, const int32_t * d_labels,
+                                const uint64_t * d_allow, int32_t * d_classes, int32_t * d_votes, float * d_distances, int64_t * d_ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        const VoteOut out = vote_out(d_classes, d_votes, d_distances, d_ids);
+        if (!check_search_args(ix, d_queries, n_queries, k, d_distances, d_ids, fn)) return false;
+        if (!check_vote_args(ix, k, m, n_queries > 0, d_labels, false, out, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return vote_device(ix, d_queries, n_queries, k, m, (const int *)d_labels, (const uint32_t *)d_allow, out, fn);
+    });
+}
+
+bool clip_amd_index_vote_ids(struct clip_amd_index * ix, const int64_t * ids, int64_t n_ids, int k, int m, int exclude_self, const int32_t * labels,
+                             const uint64_t * allow, int32_t * classes, int32_t * votes, float * distances, int64_t * out_ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        const VoteOut out = vote_out(classes, votes, distances, out_ids);
+        if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+        if (n_ids < 0 || n_ids > MAX_ROWS) { fprintf(stderr, "%s: n_ids %lld outside 0 ... %lld\n", fn, (long long)n_ids, (long long)MAX_ROWS); return false; }
+        if (!check_search_args(ix, ids, (int)n_ids, k, distances, out_ids, fn)) return false;
+        if (!check_vote_args(ix, k, m, n_ids > 0, labels, true, out, fn)) return false;
+        if (n_ids == 0) return true;
+        (void)hipSetDevice(ix->device);
+        if (!check_stored_ids(ix, ids, n_ids, fn)) return false;
+        return vote_host(ix, nullptr, ids, n_ids, k, m, exclude_self != 0, labels, allow, out, fn);
+    });
+}
+
+bool clip_amd_index_vote_graph(struct clip_amd_index * ix, int k, int m, const int32_t * labels, const uint64_t * allow, int32_t * classes,
+                               int32_t * votes, float * distances, int64_t * ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_vote_args(ix, k, m, ix && ix->n > 0, labels, true, vote_out(classes, votes, distances, ids), fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return vote_host(ix, nullptr, nullptr, ix->n, k, m, true, labels, allow, vote_out(classes, votes, distances, ids), fn);
+    });
+}
+
+bool clip_amd_index_vote_graph_device(struct clip_amd_index * ix, int k, int m, const int32_t * d_labels, const uint64_t * d_allow,
+                                      int32_t * d_classes, int32_t * d_votes, float * d_distances, int64_t * d_ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_vote_args(ix, k, m, ix && ix->n > 0, d_labels, false, vote_out(d_classes, d_votes, d_distances, d_ids), fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return vote_device(ix, nullptr, ix->n, k, m, (const int *)d_labels, (const uint32_t *)d_allow, vote_out(d_classes, d_votes, d_distances, d_ids), fn);
+    });
+}
+
+int64_t clip_amd_test_index_vote_block(struct clip_amd_index * ix, int64_t rows) {
+    if (!ix || rows < 0 || rows > GRAPH_BLOCK_MAX) return -1;
+    ix->vote_block = rows;
+    return rows;
+}
+
+float clip_amd_bench_vote_graph(int dtype, int64_t n, int dim, int k, int m, int classes, int route, int iters) {
+    return guarded(__func__, -4.f, [&](const char * fn) {
+        const bool args_ok = k >= 1 && k <= MAX_K && m >= 1 && m <= k && classes >= 1 && route >= 0 && route <= 2;
+        return bench_on_gallery(dtype, n, dim, 0, iters, args_ok, PLANT_NONE, [&](clip_amd_index * ix, float *) {
+            std::vector<int32_t> labels((size_t)n), cls((size_t)n * m), votes((size_t)n * m);
+            std::vector<float> dist((size_t)n * m);
+            std::vector<int64_t> ids((size_t)n * m);
+            for (int64_t r = 0; r < n; r++) {                  // splitmix64 of the row number under a fixed seed
+                uint64_t z = 0x707E5ull + (uint64_t)r * 0x9E3779B97F4A7C15ull;
+                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+                z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+                labels[(size_t)r] = (int32_t)((z ^ (z >> 31)) % (uint64_t)classes);
+            }
+            ix->knn_route = route;
+            if (hipDeviceSynchronize() != hipSuccess) return -4.f;
+            const VoteOut out = vote_out(cls.data(), votes.data(), dist.data(), ids.data());
+            return time_wall(iters, [&]() { return vote_host(ix, nullptr, nullptr, n, k, m, true, labels.data(), nullptr, out, fn); });
+        });
     });
 }
 

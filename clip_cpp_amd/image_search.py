@@ -15,6 +15,8 @@ build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.In
     python -m clip_cpp_amd.image_search label  [-m MODEL] [-v N] [-t N] [--db DIR] [-n N] LABEL [LABEL ...]
     python -m clip_cpp_amd.image_search merge  [-m MODEL] [-v N] --db DIR --from DIR2 [--from DIR3 ...] [-d R]
     python -m clip_cpp_amd.image_search match  [-m MODEL] [-v N] [-t N] [--db DIR] [-n N] [INDEXED/IMAGE/PATH or /path/to/query/image]
+    python -m clip_cpp_amd.image_search file   [-m MODEL] [-v N] [-t N] [--db DIR] [-k K] [-n N] [--labels FILE] [--in PREFIX]... IMAGE [IMAGE ...]
+    python -m clip_cpp_amd.image_search audit  [-m MODEL] [-v N] [--db DIR] [-k K] [--labels FILE] [--in PREFIX]...
 
 `build` writes DIR/images.index (the CLIPIDX1 file of clip_amd_index_save) and DIR/images.paths (the reference's layout: the model path
 on the first line, then one image path per id).  `search` prints the reference's output: "search results:" / "distance path" at
@@ -115,6 +117,20 @@ then " [x,y,w,h]" when the stored row of the best pair is a tile (the suffix of 
 tile of the query image.  `match` without a path prints every image's matches (Index.knn_graph_grouped, one call) in the output shape of
 `neighbors`: "matches:" at verbosity > 0, per image its path and its hits, images separated by a blank line, and "main: %d images, %d
 matches each".  On a plain database `match` stops before any model is loaded and points to `search --like` / `neighbors`.
+
+`file` and `audit` use the labels a library already carries, its folders, through a k-nearest-neighbour vote over the stored rows
+(Index.vote / Index.vote_ids / Index.vote_graph): an image's class is the directory part of its line in images.paths, as written, or with
+--labels FILE (lines "label<TAB>path") the label listed for its path; an image the file does not list is unlabelled: it may be asked about
+but never votes, and a path in the file that is not indexed is an error that names it.  --in PREFIX lets only the matching images vote.
+`file IMAGE...` answers "into which of my folders does this picture go?": an IMAGE that equals a line of images.paths is that stored row
+(nothing is decoded, and the row itself does not vote), any other is a file to load and encode.  The -k K (default 10) nearest voters
+vote; it prints "filing:" at verbosity > 0, then per image its path on a line of its own and, for each of the -n N (default 3) best
+classes, "  %d/%d %f %s ~ %s": votes, voters counted, the distance of the class's nearest member, the class and that member's path; images
+are separated by a blank line, and the last line is "main: %d images, %d voters each".  `audit` is the leave-one-out twin, "which
+pictures lie in the wrong folder?" (one Index.vote_graph call; no image is decoded or encoded): "misfiled:" at verbosity > 0, then for
+every labelled image whose winning class is not its own, in id order, "  %d/%d %f %s -> %s ~ %s": the winner's votes, voters counted, the
+distance of the winner's nearest member, the image's path, the winning class and that member's path; then
+"main: %d labelled images, %d filed against their neighbours, %d with no voter".  Neither supports a database built with --grid.
 """
 import ctypes as C
 import os
@@ -1378,6 +1394,236 @@ def neighbors(argv):
     return 0
 
 
+VOTE_K = 10         # -k of `file` and `audit`: the voters counted per image
+FILE_CLASSES = 3    # -n of `file`: the classes printed per image
+
+
+def _parse_vote(argv, file):
+    """The options of `file` (file=True: -t, -n and the images as well) and `audit`; None when they do not parse."""
+    p = dict(threads=4, verbose=1, db=".", model="", k=VOTE_K, results=FILE_CLASSES, labels=None, rest=[])
+    p["in"] = []
+    takes = {"-m": "model", "--model": "model", "-v": "verbose", "--verbose": "verbose", "--db": "db", "-k": "k", "--labels": "labels", "--in": "in"}
+    if file:
+        takes.update({"-t": "threads", "--threads": "threads", "-n": "results", "--results": "results"})
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a in takes:
+            i += 1
+            if i >= len(argv):
+                return None
+            key = takes[a]
+            if key == "in":
+                p["in"].append(argv[i])
+            else:
+                try:
+                    p[key] = int(argv[i]) if key in ("threads", "verbose", "k", "results") else argv[i]
+                except ValueError:
+                    return None
+        elif a in ("-h", "--help"):
+            _help_vote(file, p)
+            sys.exit(0)
+        elif a.startswith("-"):
+            print("main: unrecognized argument: %s" % a)
+            return None
+        elif not file:
+            print("main: unexpected argument: %s" % a)
+            return None
+        else:
+            p["rest"].append(a)
+        i += 1
+    if file and not p["rest"]:
+        return None
+    if not 1 <= p["k"] <= MAX_K:
+        print("main: -k takes 1 ... %d, not %d" % (MAX_K, p["k"]))
+        return None
+    if p["results"] < 1:
+        print("main: -n %d: file prints at least one class" % p["results"])
+        return None
+    return p
+
+
+def _help_vote(file, p):
+    if file:
+        print("Usage: python -m clip_cpp_amd.image_search file [options] IMAGE [IMAGE ...]")
+        print("\nFiles images by example: into which of your folders does each IMAGE go? The K nearest labelled images of an index built by")
+        print("`build` vote with their folder (Index.vote); per IMAGE the N best folders are printed as `votes/voters distance folder ~ nearest")
+        print("member`. An IMAGE that equals a line of %s is that indexed image: nothing is decoded, and it does not vote for itself." % PATHS_FILE)
+    else:
+        print("Usage: python -m clip_cpp_amd.image_search audit [options]")
+        print("\nLists the images of an index built by `build` that lie in the wrong folder: every labelled image is filed by the vote of its K")
+        print("nearest other labelled images (Index.vote_graph, one call; nothing is decoded or encoded), and those whose winning folder is not")
+        print("their own are printed as `votes/voters distance path -> winning folder ~ nearest member of it`.")
+    print("\nOptions:")
+    print("  -h, --help: Show this message and exit")
+    print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default.")
+    print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
+    if file:
+        print("  -t N, --threads N: Number of threads to use for inference. Default: %d" % p["threads"])
+        print("  -n N, --results N: classes printed per image. Default: %d" % p["results"])
+    print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
+    print("  -k K: voters counted per image (1 ... %d). Default: %d" % (MAX_K, p["k"]))
+    print("  --labels FILE: lines `label<TAB>path` instead of the folders: the listed images carry that label, every other image is unlabelled")
+    print("      (it may be asked about, it never votes). A path that is not in the database is an error.")
+    print("  --in PREFIX: only images whose path starts with PREFIX vote%s. Repeatable." % ("" if file else " and are audited"))
+
+
+def read_labels(image_paths, labels_file=None):
+    """(labels int32 [n], names): the class of every indexed image and the classes' names, numbered in order of first appearance.  Without
+    a file an image's class is the directory part of its line in images.paths, as written.  With one (lines `label<TAB>path`) the listed
+    paths carry that label and every other image is unlabelled (-1); ValueError for a malformed line or a path that is not indexed."""
+    names, number = [], {}
+    labels = np.full(len(image_paths), -1, dtype=np.int32)
+
+    def class_of(name):
+        if name not in number:
+            number[name] = len(names)
+            names.append(name)
+        return number[name]
+
+    if labels_file is None:
+        for i, path in enumerate(image_paths):
+            labels[i] = class_of(os.path.dirname(path))
+        return labels, names
+    ids = {path: i for i, path in enumerate(image_paths)}
+    with open(labels_file) as f:
+        for n, line in enumerate(f.read().split("\n")):
+            if not line:
+                continue
+            name, tab, path = line.partition("\t")
+            if not tab:
+                raise ValueError("%s line %d: expected `label<TAB>path`, not '%s'" % (labels_file, n + 1, line))
+            if path not in ids:
+                raise ValueError("%s line %d: '%s' is not in the database (paths are compared as written in %s)" % (labels_file, n + 1, path, PATHS_FILE))
+            labels[ids[path]] = class_of(name)
+    return labels, names
+
+
+def _open_votes(p, command):
+    """What `file` and `audit` share up to the index: (image paths, labels, class names, allowed set or None), or None with the message
+    printed.  Nothing here loads a model."""
+    if _refuse_gridded(p["db"], command):
+        return None
+    image_paths = _read_db(p)
+    if image_paths is None:
+        return None
+    try:
+        labels, names = read_labels(image_paths, p["labels"])
+    except (OSError, ValueError) as e:
+        _err("main: %s" % e)
+        return None
+    allow = None
+    if p["in"]:
+        allow = np.array([path.startswith(tuple(p["in"])) for path in image_paths], dtype=np.bool_)
+    return image_paths, labels, names, allow
+
+
+def vote_lines(classes, votes, dist, ids, counted, names, image_paths):
+    """the lines of one image's vote: `  votes/voters distance class ~ nearest member` per class"""
+    return ["  %d/%d %f %s ~ %s" % (v, counted, d, names[c], image_paths[j]) for c, v, d, j in zip(classes, votes, dist, ids) if c >= 0]
+
+
+def file_images(argv):
+    import clip_cpp_amd
+    p = _parse_vote(argv, file=True)
+    if p is None:
+        _help_vote(True, dict(threads=4, verbose=1, db=".", k=VOTE_K, results=FILE_CLASSES))
+        return 1
+    opened = _open_votes(p, "file")
+    if opened is None:
+        return 1
+    image_paths, labels, names, allow = opened
+    try:
+        clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])
+    except RuntimeError:
+        print("main: Unable to load model from %s" % p["model"])
+        return 1
+    row_of = {path: i for i, path in enumerate(image_paths)}
+    outside = [a for a in p["rest"] if a not in row_of]
+    vecs = {}
+    if outside:
+        if clip.vision_config["n_layer"] <= 0:
+            _err("main: the model at %s has no vision encoder: filing an image file needs a vision or two-tower model" % p["model"])
+            return 1
+        L = clip_cpp_amd.lib()
+        for a in outside:
+            im = L.clip_image_u8_make()
+            try:
+                if not L.clip_image_load_from_file(os.fsencode(a), im):
+                    _err("main: failed to load image from '%s'" % a)
+                    return 1
+                vecs[a] = _encode_batch(clip, L, [im])[0]
+            finally:
+                L.clip_image_u8_free(im)
+    index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
+    if vecs and index.dim != next(iter(vecs.values())).size:
+        _err("main: the index holds %d-dimensional embeddings, the model makes %d" % (index.dim, next(iter(vecs.values())).size))
+        return 1
+    k, m = p["k"], min(p["results"], p["k"])
+    voter = labels >= 0 if allow is None else (labels >= 0) & allow
+    n_voters = int(voter.sum())
+    stored = [row_of[a] for a in p["rest"] if a in row_of]
+    res_stored = index.vote_ids(stored, k, labels, m=m, allow=allow) if stored else None
+    res_out = index.vote(np.stack([vecs[a] for a in outside]), k, labels, m=m, allow=allow) if outside else None
+    if p["verbose"] > 0:
+        print("filing:")
+    si = oi = 0
+    for t, a in enumerate(p["rest"]):
+        if t:
+            print()
+        print(a)
+        if a in row_of:
+            res, r, si = res_stored, si, si + 1
+            counted = min(k, n_voters - int(voter[row_of[a]]))      # the image itself does not vote
+        else:
+            res, r, oi = res_out, oi, oi + 1
+            counted = min(k, n_voters)
+        for line in vote_lines(res[0][r], res[1][r], res[2][r], res[3][r], counted, names, image_paths):
+            print(line)
+    print("main: %d images, %d voters each" % (len(p["rest"]), k))
+    sys.stdout.flush()
+    index.close()
+    clip.close()
+    return 0
+
+
+def audit(argv):
+    import clip_cpp_amd
+    p = _parse_vote(argv, file=False)
+    if p is None:
+        _help_vote(False, dict(verbose=1, db=".", k=VOTE_K))
+        return 1
+    opened = _open_votes(p, "audit")
+    if opened is None:
+        return 1
+    image_paths, labels, names, allow = opened
+    try:
+        clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])      # only the index's device: no image is encoded
+    except RuntimeError:
+        print("main: Unable to load model from %s" % p["model"])
+        return 1
+    index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
+    k = p["k"]
+    classes, votes, dist, ids = index.vote_graph(k, labels, m=1, allow=allow)
+    voter = labels >= 0 if allow is None else (labels >= 0) & allow
+    n_voters = int(voter.sum())
+    if p["verbose"] > 0:
+        print("misfiled:")
+    against = lonely = 0
+    for i in np.flatnonzero(voter):                            # the audited images are the voters: labelled and, with --in, selected
+        c = int(classes[i, 0])
+        if c < 0:
+            lonely += 1
+        elif c != int(labels[i]):
+            against += 1
+            print("  %d/%d %f %s -> %s ~ %s" % (votes[i, 0], min(k, n_voters - 1), dist[i, 0], image_paths[i], names[c], image_paths[ids[i, 0]]))
+    print("main: %d labelled images, %d filed against their neighbours, %d with no voter" % (n_voters, against, lonely))
+    sys.stdout.flush()
+    index.close()
+    clip.close()
+    return 0
+
+
 DTYPE_NAMES = {0: "f32", 1: "f16", 3: "i8"}       # the dtype codes of a CLIPIDX1 header
 
 
@@ -1594,7 +1840,7 @@ def match(argv):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     commands = {"build": build, "update": update, "search": search, "dedup": dedup, "neighbors": neighbors, "label": label, "merge": merge, "match": match,
-                "albums": albums, "spread": spread, "groups": groups, "levels": levels}
+                "albums": albums, "spread": spread, "groups": groups, "levels": levels, "file": file_images, "audit": audit}
     if not argv or argv[0] not in commands:
         print("Usage: python -m clip_cpp_amd.image_search {build|search|dedup} [options] ...  (-h after the command for its options)")
         print("       python -m clip_cpp_amd.image_search update [options] dir [more dirs]  (an existing database brought in line with the disk)")
@@ -1606,6 +1852,8 @@ def main(argv=None):
         print("       python -m clip_cpp_amd.image_search label [options] LABEL [LABEL ...]  (every indexed image's best-fitting labels)")
         print("       python -m clip_cpp_amd.image_search merge [options] --db DIR --from DIR2 [--from DIR3 ...]  (append databases, nothing encoded twice)")
         print("       python -m clip_cpp_amd.image_search match [options] [IMAGE]  (a --grid database: the images that share a region with IMAGE, or with each other)")
+        print("       python -m clip_cpp_amd.image_search file [options] IMAGE [IMAGE ...]  (into which of your folders each IMAGE goes: its nearest labelled images vote)")
+        print("       python -m clip_cpp_amd.image_search audit [options]  (the indexed images that lie in the wrong folder, by the vote of their neighbours)")
         return 1
     return commands[argv[0]](argv[1:])
 

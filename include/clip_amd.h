@@ -431,6 +431,54 @@ int clip_amd_test_index_knn_route(struct clip_amd_index * ix, int route);
 /* Average wall time (microseconds) of one clip_amd_index_knn_graph over n seeded random rows on the current device (results copied to the
  * host included), route as above; < 0 on error.  Used by scripts/knn_bench.py. */
 float clip_amd_bench_knn(int dtype, int64_t n, int dim, int k, int route, int iters);
+/* k-NN voting: "which of MY classes does this belong to?", answered from labelled stored rows.  File a new picture into the folder most
+ * of its neighbours sit in (vote), or find the pictures that sit in the wrong folder (vote_graph, the leave-one-out form).
+ * labels: one int32 per row id, [size]: >= 0 the class of a labelled row (any numbering up to 2^31 - 1), -1 unlabelled.  Labels are an
+ * argument of the call, not index state, like groups.  A row is a VOTER when it is live, allowed (allow as for
+ * clip_amd_index_search_subset, NULL = every row) and labelled.  For one query, with 1 <= m <= k <= 1024:
+ *   1. L is the first k voters in search's order (distance ascending, equal distances lower id first): bit for bit,
+ *      clip_amd_index_search_subset with the voter bitmap as allow;
+ *   2. for each class c that occurs in L, votes(c) is the number of its entries in L and first(c) the rank of its nearest entry;
+ *   3. the classes are ordered by votes descending, then first ascending (ranks are distinct, so the order is total, and k = 1 is
+ *      nearest-neighbour classification);
+ *   4. the query's outputs are classes [m] int32, votes [m] int32, distances [m] f32 (the distance of the class's nearest voter, the bits
+ *      search reports for that pair) and ids [m] int64 (that voter's row);
+ *   5. the tail is -1 / 0 / +INFINITY / -1.
+ * With all labels distinct and m == k the result is search_subset's with votes all 1; fewer than k voters make L shorter; no voter at all
+ * gives an all-empty row, and so does an empty index.  A query's result does not depend on the other queries, on how queries are split
+ * across calls or blocks, or on the route: it is made of integers and of distances search reports, so it is as exact and bit-reproducible
+ * as search.  Votes are plain counts: distance-weighted votes are out of scope (a float sum would need an order of its own, and the
+ * tie-break on the nearest member already carries most of the benefit).
+ * vote: n_queries f32 vectors [n_queries][dim], results [n_queries][m].
+ * vote_ids: the stored rows ids[0 ... n_ids) as the queries, each bit for bit as in clip_amd_index_search_ids; with exclude_self != 0 a row
+ * is no voter for its own query.  The query row need not be labelled or allowed.  A bad id: as clip_amd_index_search_ids (false, the id
+ * named, outputs untouched).
+ * vote_graph: every row as the query, itself excluded: results [size][m]; row i is vote_ids(i, exclude_self = 1) for a live row i, bit
+ * for bit, the row of a removed id is empty, size == 0 succeeds and writes nothing.  The routes are clip_amd_index_knn_graph's, chosen as
+ * there (clip_amd_test_index_knn_route); on the tiled route one 4-byte word is read back before the first block ("is some live row no
+ * voter?"): if so every block takes a second tile pass for those rows, if not the pass is knn_graph's own.
+ * Host forms refuse, before any launch, with a message that names the value and with the outputs untouched: a label < -1, NULL labels
+ * with size > 0, m < 1, m > k, k outside 1 ... 1024, NULL pointers and everything search_subset refuses.  Device forms trust d_labels: any
+ * negative value counts as unlabelled.  Device memory beyond the index: the workspaces of the search, the voter bitmap (one bit per row),
+ * the labels of a host form and one query block's results; nothing grows with size x k. */
+bool clip_amd_index_vote(struct clip_amd_index * ix, const float * queries, int n_queries, int k, int m, const int32_t * labels,
+                         const uint64_t * allow, int32_t * classes, int32_t * votes, float * distances, int64_t * ids);   /* host, synchronous */
+bool clip_amd_index_vote_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int k, int m, const int32_t * d_labels,
+                                const uint64_t * d_allow, int32_t * d_classes, int32_t * d_votes, float * d_distances,
+                                int64_t * d_ids);                                                                        /* HBM, asynchronous */
+bool clip_amd_index_vote_ids(struct clip_amd_index * ix, const int64_t * ids, int64_t n_ids, int k, int m, int exclude_self,
+                             const int32_t * labels, const uint64_t * allow, int32_t * classes, int32_t * votes, float * distances,
+                             int64_t * out_ids);                                                                         /* host, synchronous */
+bool clip_amd_index_vote_graph(struct clip_amd_index * ix, int k, int m, const int32_t * labels, const uint64_t * allow, int32_t * classes,
+                               int32_t * votes, float * distances, int64_t * ids);                                       /* host, synchronous */
+bool clip_amd_index_vote_graph_device(struct clip_amd_index * ix, int k, int m, const int32_t * d_labels, const uint64_t * d_allow,
+                                      int32_t * d_classes, int32_t * d_votes, float * d_distances, int64_t * d_ids);    /* results stay in HBM */
+/* test hook: query rows per block of the votes on this index from now on (0: automatic), as clip_amd_test_index_sets_block.  Returns the
+ * value set, -1 for a NULL index or a value outside 0 ... 65408. */
+int64_t clip_amd_test_index_vote_block(struct clip_amd_index * ix, int64_t rows);
+/* Average wall time (microseconds) of one clip_amd_index_vote_graph over the n seeded random rows of clip_amd_bench_knn, the label of a row
+ * a seeded hash of its number modulo `classes`, route as clip_amd_bench_knn; < 0 on error.  Used by scripts/vote_bench.py. */
+float clip_amd_bench_vote_graph(int dtype, int64_t n, int dim, int k, int m, int classes, int route, int iters);
 /* One index searched with the rows of another, and one index appended to another: label every image of a database with a small index of
  * captions, find which images of B a database A already holds (k = 1), merge two databases without encoding anything twice.
  * search_index: the queries are stored rows of src: ids[0 ... n_ids) (host), or with ids == NULL every row 0 ... size(src) - 1 (n_ids is
