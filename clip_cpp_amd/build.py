@@ -22,7 +22,7 @@ GGML_STUB = os.path.join(HERE, "libggml.so")
 ARCH = "gfx950"
 
 HOST_SOURCES = ["gguf.cpp", "quant.cpp", "load.cpp", "forward.cpp", "tokenizer.cpp", "preprocess.cpp", "image_io.cpp", "image_formats.cpp",
-                "jpeg_decode.cpp", "host_pipeline.cpp", "files_pipeline.cpp", "api.cpp", "test_hooks.cpp", "search.cpp"]
+                "jpeg_decode.cpp", "host_pipeline.cpp", "files_pipeline.cpp", "api.cpp", "test_hooks.cpp", "search.cpp", "search_bench.cpp"]
 HIP_SOURCES = ["k_attn.hip", "k_attn_long.hip", "k_attn_f32.hip", "k_misc.hip", "k_preproc.hip", "k_jpeg.hip", "k_gemm.hip", "k_gemm8.hip", "k_gemm4.hip", "k_gemm32.hip", "k_gemm_f32.hip", "k_skinny.hip", "k_gemm_ring.hip", "k_fold.hip", "k_search.hip", "k_join.hip", "k_graph.hip", "k_group.hip", "k_sets.hip", "k_distinct.hip", "k_compound.hip", "k_components.hip", "k_modes.hip", "k_linkage.hip", "k_spread.hip", "k_extents.hip", "k_vote.hip"]
 GEMM_WTYPES = [0, 1, 2, 3, 4, 5]
 # Per-file flags.  The f32-file kernels (a correctness path, not a tuned one) are built without the SLP vectoriser: packed f32 instructions that

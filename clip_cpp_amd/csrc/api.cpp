@@ -2,7 +2,7 @@
 // the MI355X extensions of include/clip_amd.h.  Thin shim: argument checking, host<->HBM staging,
 // then forward.cpp.  Nothing here throws across the ABI: every entry point that parses a file or allocates in
 // proportion to caller input is a function-try-block that turns an exception (bad_alloc, length_error, ...) into NULL / false.
-// The kernel test and micro-benchmark hooks of clip_amd.h (clip_amd_test_*, clip_amd_bench_*) are not here: test_hooks.cpp, and search.cpp for the index.
+// The kernel test and micro-benchmark hooks of clip_amd.h (clip_amd_test_*, clip_amd_bench_*) are not here: test_hooks.cpp, and search_bench.cpp for the index.
 #include <algorithm>
 #include <chrono>
 #include <cmath>

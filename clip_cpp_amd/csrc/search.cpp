@@ -1,155 +1,50 @@
-// search.cpp — the exact nearest-neighbour index of include/clip_amd.h (clip_amd_index_*): device-resident rows, argument checking,
-// query chunking, the scan -> merge tree -> finish launch sequence of k_search.hip, searches by id, the k-NN graph and the search of one
-// index with the rows of another (the gather kernel in front of the same sequence, or the tiled kernel of k_graph.hip in the scan's place),
-// searches with query sets (the set fold of k_sets.hip in the finish's place), distinct searches (the pools of a search, then the near
-// bitmap and the walk of k_distinct.hip), compound queries (the placement and the scan of k_compound.hip in front of the same merge tree),
-// appending one index to another, the count -> lims -> scatter -> sort -> finish sequence of
-// range search and pairs (k_join.hip), connected components (the link -> flatten -> finish sequence of k_components.hip), density modes (k_modes.hip), the single-linkage tree (k_linkage.hip), the extents of a labelling (k_extents.hip), farthest-first selection (k_spread.hip), k-NN voting over labelled rows (the voter bitmap and the fold of k_vote.hip as the sink of search_blocks), the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
-// Replaces the usearch index of the reference's examples/image-search (build.cpp / search.cpp) with an exact search on the GPU.
+// search.cpp — the exact nearest-neighbour index of include/clip_amd.h (clip_amd_index_*): device-resident rows, argument checking and
+// query chunking around the kernels' launchers.  Replaces the usearch index of the reference's examples/image-search (build.cpp /
+// search.cpp) with an exact search on the GPU.  What is here, by kernel file:
+//   k_search.hip    the scan -> merge tree -> finish launch sequence of a search; searches by id (the gather kernel in front of it)
+//   k_graph.hip     the k-NN graph and the search of one index with the rows of another (the tiled kernel in the scan's place)
+//   k_sets.hip      searches with query sets (the set fold in the finish's place)
+//   k_distinct.hip  distinct searches (the pools of a search, then the near bitmap and the walk)
+//   k_compound.hip  compound queries (the placement and the scan in front of the same merge tree)
+//   k_join.hip      range search and pairs (count -> lims -> scatter -> sort -> finish)
+//   k_components.hip, k_modes.hip, k_linkage.hip, k_extents.hip, k_spread.hip
+//                   connected components (link -> flatten -> finish), density modes, the single-linkage tree, the extents of a
+//                   labelling, farthest-first selection
+//   k_vote.hip      k-NN voting over labelled rows (the voter bitmap and the fold, as the sink of search_blocks)
+// and appending one index to another, the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
+// The benchmark and test hooks are in search_bench.cpp; search_impl.h holds what the two files share.
 // Single owners: search_device_impl (the passes of a search: one ScanArgs per scan launch, whatever the selection), search_blocks and
-// query_block (the blocked host forms of stored-row queries), upload_allow / upload_groups / stage_inputs (a call's inputs on the device),
-// check_groups / check_stored_ids (host arguments), time_device / time_wall (the timed part of the benchmark hooks).
+// query_block (the blocked host forms of stored-row queries), graph_plan / launch_graph_block (the route of the k-NN graph, the core
+// distances and the vote graph), Arena (search_impl.h: the device results of every host form and their way back), reserve_stage /
+// stage_block / advance (a block's queries on the device), upload_allow / upload_groups / stage_inputs (a call's other inputs),
+// check_index / check_k / check_groups / check_stored_ids (host arguments), launched (the message of a failed launch).
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cstdio>
 #include <cstring>
-#include <exception>
-#include <functional>
 #include <vector>
 
-#include "../../include/clip_amd.h"
-#include "kernels.h"
-#include "model.h"
+#include "search_impl.h"
 
 using namespace clipamd;
-
-namespace {
-
-// A device workspace, grown on demand by ensure() and released with its owner.  Every workspace of an index is one member of this type:
-// a new one is a single declaration.
-struct Buf {
-    void * p = nullptr;
-    size_t bytes = 0;
-    Buf() = default;
-    Buf(const Buf &) = delete;
-    Buf & operator=(const Buf &) = delete;
-    ~Buf() { if (p) (void)hipFree(p); }
-};
-
-// The stored rows and what is kept per row, allocated (alloc_store) and released (release_store) as one.
-struct RowStore {
-    void * rows = nullptr;         // [cap][Dpad]
-    float * rinv = nullptr;        // i8: [cap rounded up to 64] row inverse norms (the scan reads them 4 at a time)
-    uint32_t * live = nullptr;     // [cap rounded up to 128 bits] one bit per row: 1 = live; zeros at positions >= n
-    int64_t cap = 0;               // rows allocated
-};
-
-}  // namespace
-
-struct clip_amd_index {
-    clip_ctx * ctx = nullptr;      // NULL: benchmark index on the default stream
-    int device = 0;
-    int dim = 0, Dpad = 0, dtype = 1;
-    size_t es = 2;                 // bytes per stored value
-    int64_t n = 0;                 // rows stored
-    RowStore store;
-    int64_t removed = 0;           // rows < n whose bit is 0
-    Buf abuf;                      // allowed set copied from the host / ids of a remove call / new ids of compact
-    Buf mask;                      // effective mask of a subset search: live & allow
-    Buf stage;                     // f32 rows / queries copied from the host
-    Buf qbuf;                      // normalised queries [nq_pad][Dpad]
-    Buf qinv;                      // i8: query inverse norms [nq_pad]
-    Buf cand;                      // [n_chunks][nq][C] candidates
-    Buf mbuf[2];                   // merge levels
-    Buf outs;                      // distances + ids of the host search form / of one query block of the k-NN graph
-    Buf idbuf;                     // ids of a search by id copied from the host
-    Buf qself;                     // searches by id: [nq_pad] the stored row each query is, -1 for a flagged one
-    Buf gbuf;                      // groups of a grouped search copied from the host
-    Buf qgroup;                    // query sets with exclude_own: [nq_pad] the group of the stored row each query is
-    Buf slims;                     // query sets: set_lims of the call (of one query block of a host form) on the device
-    Buf souts;                     // query sets, host forms: ids + distances + query rows of one query block's sets
-    int64_t sets_block = 0;        // clip_amd_test_index_sets_block: query rows per block of the host forms, 0 automatic
-    Buf dpool;                     // distinct search: distances + ids of one query block's pools
-    Buf dnear;                     // distinct search: the near bitmap of one query block
-    Buf douts;                     // distinct search, host forms: ids + distances + counts of the call
-    int distinct_block = 0;        // clip_amd_test_index_distinct_block: queries per block, 0 automatic
-    Buf cprep;                     // compound queries: the vector terms of one query block in the stored form
-    Buf cpinv;                     // compound queries, i8: their inverse norms
-    Buf cmeta;                     // compound queries: source, id, kind and bound of every workspace row of one query block
-    Buf cxid;                      // compound queries: the stored row every workspace row is, or -1
-    int compound_block = 0;        // clip_amd_test_index_compound_block: compound queries per block, 0 automatic
-    int knn_route = 0;             // clip_amd_test_index_knn_route: 0 automatic, 1 scan, 2 tiled
-    int cross_route = 0;           // clip_amd_test_index_cross_route: the same for clip_amd_index_search_index
-    // range search / pairs
-    Buf jcnt;                      // total (u64) + per-segment counts, reused as the scatter cursors
-    Buf hits;                      // hit list
-    Buf joffs;                     // segment offsets (= lims) on the device
-    Buf jsort;                     // two (distance, id) buffers of the results
-    Buf jouts;                     // ids (int64) + distances of the results
-    // connected components
-    Buf cparent;                   // the union-find: two [n] i32 arrays (the passes that flatten it go from one to the other)
-    Buf cnear;                     // [n] nearest keys (u64)
-    Buf couts;                     // host form: group count (u64), labels + nearest ids (int64), nearest distances
-    // density modes (the forest goes through cparent, the keys through cnear)
-    Buf mcount;                    // [n] near rows of every row (u32)
-    Buf mouts;                     // host form: mode count (u64), labels + parents (int64), parent distances, densities
-    // single-linkage tree (the forest goes through cparent, the keys through cnear)
-    Buf lwork;                     // labels, per-root edges, round statistics and block counts (linkage_work_bytes)
-    Buf louts;                     // host form: count (int64), lo + hi (int64), distances
-    Buf lcore;                     // mutual-reachability tree: [n rounded up to 4] core distances (f32)
-    int linkage_rounds = 0;        // clip_amd_test_index_linkage_rounds: the rounds that ran in the last host-form call
-    // extents of a labelling
-    Buf ework;                     // member bitmap, label ranges, reach keys, per-label slots and i32 labels (extents_work_bytes)
-    Buf eouts;                     // host form: group count (u64), labels + centres + far ids (int64), radii, diameters, reaches
-    int extents_route = 0;         // clip_amd_test_index_extents_route: 0 tile skip on, 1 every tile pair computed
-    // farthest-first selection
-    Buf sgap;                      // [n] distance to the nearest centre so far (f32)
-    Buf sopos;                     // [n] position of that centre (i32)
-    Buf sslot;                     // [centres + 1] the centres' keys (u64)
-    Buf sseeds;                    // the seed ids copied from the host
-    Buf spouts;                    // host form: count (int64), cover radius, centres + owners (int64), reaches + owner distances
-    // k-NN voting
-    Buf vvoters;                   // the voter bitmap (live & allow & labelled) and, behind it, the "some live row is no voter" word
-    Buf vlabels;                   // labels of a host form copied from the host
-    Buf vouts;                     // host forms: ids (int64) + classes + votes + distances of one query block
-    int64_t vote_block = 0;        // clip_amd_test_index_vote_block: query rows per block, 0 automatic
-};
+using namespace clipamd::idx;
 
 namespace {
 
 constexpr char MAGIC[8] = {'C', 'L', 'I', 'P', 'I', 'D', 'X', '1'};
 constexpr uint32_t VERSION = 1;
-constexpr int MAX_K = 1024;
-constexpr int64_t MAX_ROWS = 2147483647;
 constexpr size_t CAND_BUDGET = (size_t)512 << 20;       // bytes of candidate workspace per scan launch
-constexpr int PLANT_NONE = 0, PLANT_JOIN = -1;           // bench_on_gallery: what is planted into the seeded rows (> 0: copies per row)
-constexpr float DISTINCT_PLANT_AMP = 0.05f;             // noise amplitude of clip_amd_bench_search_distinct's copies
 constexpr int64_t HOST_CHUNK_ROWS = 65536;              // rows per staging copy (add, save, load)
 constexpr int64_t JOIN_HIT_BUDGET = (int64_t)1 << 21;    // hits the first scoring pass keeps (24 MB); more only when the caller's capacity asks
 constexpr size_t GRAPH_OUT_BUDGET = (size_t)128 << 20;  // bytes of results one query block of the k-NN graph leaves on the device
 constexpr size_t DISTINCT_NEAR_BUDGET = (size_t)64 << 20;   // bytes of near bitmap per query block of a distinct search
-constexpr int DISTINCT_BLOCK_MAX = 4096;                // queries per block of a distinct search (the near grid counts them in z)
-constexpr int64_t GRAPH_BLOCK_MAX = 65408;              // queries per block: 511 tiles of 128 (the merge and graph grids count them in 16 bits)
 
-hipStream_t stream_of(const clip_amd_index * ix) { return ix->ctx ? ix->ctx->stream : nullptr; }
 size_t row_stride(const clip_amd_index * ix) { return (size_t)ix->Dpad * ix->es; }      // bytes from one stored row to the next
 
-// Runs an entry point's body, handing it the entry point's name for its messages; an exception ends the call with "<name>: <what>" and
-// the entry point's failure value.
-template <typename R, typename F>
-R guarded(const char * fn, R fail, F && body) {
-    try {
-        return body(fn);
-    } catch (const std::exception & e) {
-        fprintf(stderr, "%s: %s\n", fn, e.what());
-        return fail;
-    }
-}
+}  // namespace
 
 // b holds at least need bytes afterwards (contents are not kept when it grows).  Work queued on the index's stream may still use the old
 // block, so the stream is waited for before it is freed; an empty workspace is still a valid pointer (16 bytes).
-bool ensure(const clip_amd_index * ix, Buf & b, size_t need) {
+bool idx::ensure(const clip_amd_index * ix, Buf & b, size_t need) {
     if (need <= b.bytes && b.p) return true;
     if (b.p) {
         (void)hipStreamSynchronize(stream_of(ix));
@@ -167,6 +62,33 @@ bool ensure(const clip_amd_index * ix, Buf & b, size_t need) {
     return true;
 }
 
+// false, with the runtime's message under the entry point's name, when a launch (pass hipGetLastError()) or the stream's work failed
+bool idx::stream_done(const clip_amd_index * ix, const char * fn, hipError_t launched) {
+    if (launched == hipSuccess && hipStreamSynchronize(stream_of(ix)) == hipSuccess) return true;
+    fprintf(stderr, "%s: %s\n", fn, hipGetErrorString(hipGetLastError()));
+    return false;
+}
+
+namespace {
+
+// the argument checks every entry point shares, and the message of a launcher that returned false or left an error behind
+bool check_index(const void * ix, const char * fn) {
+    if (!ix) fprintf(stderr, "%s: index is NULL\n", fn);
+    return ix != nullptr;
+}
+
+bool check_k(int k, int lo, const char * fn) {
+    if (k >= lo && k <= MAX_K) return true;
+    fprintf(stderr, "%s: k = %d outside %d ... %d\n", fn, k, lo, MAX_K);
+    return false;
+}
+
+bool launched(bool ok, const char * fn) {
+    if (ok && hipGetLastError() == hipSuccess) return true;
+    fprintf(stderr, "%s: launch failed\n", fn);
+    return false;
+}
+
 // "a counter followed by an array" in one workspace: an 8-byte counter at its start, count items of T behind it
 template <typename T>
 bool ensure_counted(const clip_amd_index * ix, Buf & b, size_t count, unsigned long long *& counter, T *& items) {
@@ -174,13 +96,6 @@ bool ensure_counted(const clip_amd_index * ix, Buf & b, size_t count, unsigned l
     counter = (unsigned long long *)b.p;
     items = (T *)((char *)b.p + 8);
     return true;
-}
-
-// false, with the runtime's message under the entry point's name, when a launch (pass hipGetLastError()) or the stream's work failed
-bool stream_done(const clip_amd_index * ix, const char * fn, hipError_t launched = hipSuccess) {
-    if (launched == hipSuccess && hipStreamSynchronize(stream_of(ix)) == hipSuccess) return true;
-    fprintf(stderr, "%s: %s\n", fn, hipGetErrorString(hipGetLastError()));
-    return false;
 }
 
 // results of a host form back to the caller: count distances and ids, then the stream is waited for
@@ -216,7 +131,9 @@ bool alloc_store(const clip_amd_index * ix, int64_t cap, RowStore & s, const cha
     return true;
 }
 
-bool reserve_rows(clip_amd_index * ix, int64_t need) {
+}  // namespace
+
+bool idx::reserve_rows(clip_amd_index * ix, int64_t need) {
     RowStore & cur = ix->store;
     if (need <= cur.cap) return true;
     int64_t cap = std::max<int64_t>({need, cur.cap * 2, 1024});
@@ -234,6 +151,26 @@ bool reserve_rows(clip_amd_index * ix, int64_t need) {
     cur = fresh;
     return true;
 }
+
+clip_amd_index * idx::make_index(clip_ctx * ctx, int device, int dim, int dtype) {
+    clip_amd_index * ix = new clip_amd_index;
+    ix->ctx = ctx;
+    ix->device = device;
+    ix->dim = dim;
+    ix->Dpad = search_dpad(dtype, dim);
+    ix->dtype = dtype;
+    ix->es = search_elem_size(dtype);
+    return ix;
+}
+
+void idx::free_index(clip_amd_index * ix) {
+    (void)hipSetDevice(ix->device);
+    (void)hipStreamSynchronize(stream_of(ix));
+    release_store(ix->store);
+    delete ix;      // the workspaces go with it
+}
+
+namespace {
 
 // The mask a scan or join honours: NULL (every row, the unmasked kernels) when nothing was removed and no allowed set was given, the live
 // bitmap when only rows were removed, else live & allow in the mask workspace (bits of allow at positions >= n meet live's zeros).
@@ -274,19 +211,6 @@ bool upload_groups(clip_amd_index * ix, const int32_t * groups, const char * fn,
     return true;
 }
 
-// A host form's inputs on the device: the f32 queries in the staging workspace and, if given, the caller's allowed set
-bool stage_inputs(clip_amd_index * ix, const float * queries, int nq, const uint64_t * allow, const float *& d_q, const uint32_t *& d_allow) {
-    const size_t qb = (size_t)nq * ix->dim * 4;
-    d_allow = nullptr;
-    if (!ensure(ix, ix->stage, qb)) return false;
-    (void)hipMemcpyAsync(ix->stage.p, queries, qb, hipMemcpyHostToDevice, stream_of(ix));
-    d_q = (const float *)ix->stage.p;
-    return upload_allow(ix, allow, d_allow);
-}
-
-bool valid_dim(int dim) { return dim >= 4 && dim <= 4096 && dim % 4 == 0; }
-bool valid_dtype(int64_t dtype) { return dtype == SEARCH_F32 || dtype == SEARCH_F16 || dtype == SEARCH_I8; }
-
 // An f32 / fp16 store holds only finite values of magnitude <= 1: the normalising kernel writes nothing else (sqrtf(fl(sum x^2)) >= |x_i|
 // by the monotonicity of rounding), and the strict order of candidates and the ordered-bits atomic folds of the join, extents, spread and
 // linkage kernels rest on it.  True when count values of a file keep to that (the bits of |v| against those of 1.0: a NaN or an
@@ -309,17 +233,6 @@ bool stored_values_valid(const unsigned char * p, size_t count, int dtype) {
     return out == 0;
 }
 
-clip_amd_index * make_index(clip_ctx * ctx, int device, int dim, int dtype) {
-    clip_amd_index * ix = new clip_amd_index;
-    ix->ctx = ctx;
-    ix->device = device;
-    ix->dim = dim;
-    ix->Dpad = search_dpad(dtype, dim);
-    ix->dtype = dtype;
-    ix->es = search_elem_size(dtype);
-    return ix;
-}
-
 // n_src f32 queries on the device -> the query workspaces in the stored form, n_rows (the padded count) rows
 bool prepare_queries(clip_amd_index * ix, const float * d_q, int64_t n_src, int64_t n_rows) {
     if (!ensure(ix, ix->qbuf, (size_t)n_rows * row_stride(ix))) return false;
@@ -328,30 +241,11 @@ bool prepare_queries(clip_amd_index * ix, const float * d_q, int64_t n_src, int6
     return true;
 }
 
-void free_index(clip_amd_index * ix) {
-    (void)hipSetDevice(ix->device);
-    (void)hipStreamSynchronize(stream_of(ix));
-    release_store(ix->store);
-    delete ix;      // the workspaces go with it
-}
-
 // rows of a search: every chunk at least 256 rows and 4 k (its k best are a small part of it), at most ~1024 chunks
 int64_t rows_per_chunk(int64_t n, int k) {
     int64_t r = std::max<int64_t>({256, 4 * (int64_t)k, (n + 1023) / 1024});
     return (r + 63) / 64 * 64;
 }
-
-// Where the queries of a search come from: f32 vectors on the device (normalised / quantised into the query workspace), or stored rows by
-// id (gathered bit for bit): d_ids on the device or, NULL, the rows first, first + 1, ...; rows of `from` (same dim, dtype and stream),
-// NULL: of the searched index itself
-struct QuerySource {
-    const float * d_q = nullptr;
-    bool by_id = false;
-    const clip_amd_index * from = nullptr;
-    const int64_t * d_ids = nullptr;
-    int64_t first = 0;
-    bool exclude_self = false;
-};
 
 // n_src stored rows by id -> the query workspaces, n_rows (the padded count) rows, and qself
 bool gather_queries(clip_amd_index * ix, const QuerySource & src, int q0, int64_t n_src, int64_t n_rows) {
@@ -393,11 +287,13 @@ bool merge_and_finish(clip_amd_index * ix, int n_chunks, int m, int k, const int
     return true;
 }
 
+}  // namespace
+
 // What a search over query sets puts in the place of the finish: the fold of k_sets.hip over the sets that have rows in the pass.  lims
 // (host) / d_lims (device) [n_sets + 1]: the sets as row numbers of the call; the results ([n_sets][k] each) accumulate in d_dist / d_ids
 // / d_qrows, which the caller filled empty; a reported query row is qrow_base + its row number.  own (stored-row queries with groups
 // only): the scan excludes each query's own group.
-struct SetFold {
+struct idx::SetFold {
     const int64_t * lims = nullptr;
     const int64_t * d_lims = nullptr;
     int64_t n_sets = 0;
@@ -410,8 +306,8 @@ struct SetFold {
 
 // d_groups (vector queries, or query sets): one group per stored row, the grouped scan and merge in the place of the plain ones.  fold
 // (query sets): every pass ends in the set fold instead of the finish, and d_dist / d_ids are not used.
-bool search_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, int k, const uint32_t * d_allow, float * d_dist, int64_t * d_ids,
-                        const int * d_groups = nullptr, const SetFold * fold = nullptr) {
+bool idx::search_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, int k, const uint32_t * d_allow, float * d_dist, int64_t * d_ids,
+                             const int * d_groups, const SetFold * fold) {
     hipStream_t st = stream_of(ix);
     if (nq == 0) return true;
     if (ix->n == 0) {
@@ -456,8 +352,7 @@ bool search_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, in
         a.qself = src.exclude_self ? qself : nullptr;
         a.groups = d_groups;
         a.qgroup = own ? (const int *)ix->qgroup.p : nullptr;
-        const bool launched = launch_search_scan(a, st);
-        if (!launched) {
+        if (!launch_search_scan(a, st)) {
             fprintf(stderr, "clip_amd_index_search: scan launch failed\n");
             return false;
         }
@@ -474,19 +369,12 @@ bool search_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, in
         } else if (!merge_and_finish(ix, n_chunks, m, k, qself, d_dist + (size_t)q0 * k, d_ids + (size_t)q0 * k, d_groups)) {
             return false;
         }
-        if (hipGetLastError() != hipSuccess) {
-            fprintf(stderr, "clip_amd_index_search: launch failed\n");
-            return false;
-        }
+        if (!launched(true, "clip_amd_index_search")) return false;
     }
     return true;
 }
 
-QuerySource vectors(const float * d_q) {
-    QuerySource s;
-    s.d_q = d_q;
-    return s;
-}
+namespace {
 
 QuerySource stored_rows(const int64_t * d_ids, int64_t first, bool exclude_self, const clip_amd_index * from = nullptr) {
     QuerySource s;
@@ -496,6 +384,41 @@ QuerySource stored_rows(const int64_t * d_ids, int64_t first, bool exclude_self,
     s.first = first;
     s.exclude_self = exclude_self;
     return s;
+}
+
+// src from its query q0 on (the device forms cut their queries into blocks)
+QuerySource advance(QuerySource src, int64_t q0, int dim) {
+    if (!src.by_id) src.d_q += (size_t)q0 * dim;
+    else if (src.d_ids) src.d_ids += q0;
+    else src.first += q0;
+    return src;
+}
+
+// The staging workspaces for blocks of up to `block` host queries: ids (stored rows) or f32 rows; with neither, the queries are the
+// stored rows in order and nothing is staged
+bool reserve_stage(clip_amd_index * ix, const float * queries, const int64_t * ids, int64_t block) {
+    return ids ? ensure(ix, ix->idbuf, (size_t)block * 8) : (!queries || ensure(ix, ix->stage, (size_t)block * ix->dim * 4));
+}
+
+// One block's queries on the device: the m ids or f32 rows from q0 on go up into their workspace (which the next block reuses: the
+// caller waits for the stream in between); with neither, the stored rows q0, q0 + 1, ... of `from`
+QuerySource stage_block(clip_amd_index * ix, const float * queries, const int64_t * ids, int64_t q0, int64_t m, bool exclude_self,
+                        const clip_amd_index * from = nullptr) {
+    if (ids) {
+        (void)hipMemcpyAsync(ix->idbuf.p, ids + q0, (size_t)m * 8, hipMemcpyHostToDevice, stream_of(ix));
+        return stored_rows((const int64_t *)ix->idbuf.p, 0, exclude_self, from);
+    }
+    if (!queries) return stored_rows(nullptr, q0, exclude_self, from);
+    (void)hipMemcpyAsync(ix->stage.p, queries + (size_t)q0 * ix->dim, (size_t)m * ix->dim * 4, hipMemcpyHostToDevice, stream_of(ix));
+    return vectors((const float *)ix->stage.p);
+}
+
+// A host form's inputs on the device: its nq f32 queries as one block and, if given, the caller's allowed set
+bool stage_inputs(clip_amd_index * ix, const float * queries, int nq, const uint64_t * allow, const float *& d_q, const uint32_t *& d_allow) {
+    d_allow = nullptr;
+    if (!reserve_stage(ix, queries, nullptr, nq)) return false;
+    d_q = stage_block(ix, queries, nullptr, 0, nq, false).d_q;
+    return upload_allow(ix, allow, d_allow);
 }
 
 // Rows from which the automatic route of clip_amd_index_knn_graph takes the tiled kernel of k_graph.hip; below, the scan route.
@@ -528,31 +451,69 @@ int64_t query_block(int64_t nq, int k, size_t slot_bytes) {
                               (int64_t)(CAND_BUDGET / ((size_t)C * 8)) / 128 * 128});
 }
 
+// The route of a blocked search of stored rows, the arithmetic knn_graph_impl, core_column, vote_impl and search_index_impl share:
+// block = queries per block; tiled = the kernel of k_graph.hip over n_chunks chunks of rpc candidate rows in the scan's place
+struct GraphPlan {
+    bool tiled = false;
+    int64_t block = 0;
+    int n_chunks = 1;
+    int64_t rpc = 0;
+};
+
+// route: the test hook's override (0: automatic, which takes the tiled kernel when auto_tiled; 1 scan; 2 tiled).  grid_block: the block
+// the tiled grid is sized for, a multiple of 128.  The graph, the core distances and the cross search pass their block, which
+// query_block made one.  The votes' block can be any count the vote_block hook sets, so they pass it rounded up to whole tiles;
+// query_block's automatic value is already whole tiles, so the two agree wherever no hook is set and nothing depends on the difference.
+GraphPlan graph_plan(const clip_amd_index * ix, int k, int route, bool auto_tiled, int64_t block, int64_t grid_block) {
+    GraphPlan p;
+    p.tiled = route ? route == 2 : auto_tiled;
+    p.block = block;
+    p.rpc = (ix->n + 127) / 128 * 128;
+    if (p.tiled) tiled_chunks(ix->n, grid_block, k, p.rpc, p.n_chunks);
+    return p;
+}
+
+// The tiled kernel for the stored rows q0 ... q0 + m - 1 as the queries, straight from the store, under mask (which also decides
+// which of those rows ask)
+bool launch_graph_block(clip_amd_index * ix, const GraphPlan & p, int k, int64_t q0, int m, const uint32_t * mask) {
+    return launch_graph(ix->store.rows, ix->store.rinv, ix->n, q0, m, ix->Dpad, ix->dtype, k, ix->cand.p, p.n_chunks, p.rpc, mask, stream_of(ix));
+}
+
+bool knn_auto_tiled(const clip_amd_index * ix) { return ix->n >= KNN_TILED_MIN_ROWS; }
+
+// The block results workspace for `slots` (row, k) entries: ids first, distances behind them.  search_blocks and the plain host
+// searches own it; a host form's Arena is live next to it (vote_host, linkage_host through core_column, the distinct forms).
+bool block_outs(clip_amd_index * ix, size_t slots, float *& d_dist, int64_t *& d_ids) {
+    if (!ensure(ix, ix->outs, slots * 12)) return false;
+    d_ids = (int64_t *)ix->outs.p;
+    d_dist = (float *)((char *)ix->outs.p + slots * 8);
+    return true;
+}
+
 // "nq stored-row queries" (the k-NN graph, the search of one index with the rows of another, the core distances of the mutual-reachability
-// tree): query blocks of `block` rows, one after another, each scored, merged, finished into the block's result workspace and handed to
+// tree): query blocks of p.block rows, one after another, each scored, merged, finished into the block's result workspace and handed to
 // sink(q0, m, d_dist, d_ids), which takes what it wants of the block's results ([m][k], device) before the next block reuses them on the
 // same stream: block_to_host copies them out, the tree keeps one column on the device.  Scan route: the scan over the rows source(q0, m)
-// names (a QuerySource), under d_allow.  Tiled route: launch(q0, m) runs a kernel of k_graph.hip over n_chunks chunks straight from the
-// stores.
+// names (a QuerySource), under d_allow.  Tiled route: launch(q0, m) runs a kernel of k_graph.hip over p.n_chunks chunks straight from
+// the stores.
 template <typename Source, typename Launch, typename Sink>
-bool search_blocks(clip_amd_index * ix, int64_t nq, int k, int64_t block, bool tiled, int n_chunks, const uint32_t * d_allow, const char * fn,
-                   Source && source, Launch && launch, Sink && sink) {
+bool search_blocks(clip_amd_index * ix, int64_t nq, int k, const GraphPlan & p, const uint32_t * d_allow, const char * fn, Source && source,
+                   Launch && launch, Sink && sink) {
     const int C = search_candidate_capacity(k);
-    if (!ensure(ix, ix->outs, (size_t)block * k * 12)) return false;
-    int64_t * d_ids = (int64_t *)ix->outs.p;
-    float * d_dist = (float *)((char *)ix->outs.p + (size_t)block * k * 8);
-    for (int64_t q0 = 0; q0 < nq; q0 += block) {
-        const int m = (int)std::min(block, nq - q0);
-        if (!tiled) {
+    float * d_dist = nullptr;
+    int64_t * d_ids = nullptr;
+    if (!block_outs(ix, (size_t)p.block * k, d_dist, d_ids)) return false;
+    for (int64_t q0 = 0; q0 < nq; q0 += p.block) {
+        const int m = (int)std::min(p.block, nq - q0);
+        if (!p.tiled) {
             if (!search_device_impl(ix, source(q0, m), m, k, d_allow, d_dist, d_ids)) return false;
         } else {
-            if (!ensure(ix, ix->cand, (size_t)n_chunks * m * C * 8)) return false;
+            if (!ensure(ix, ix->cand, (size_t)p.n_chunks * m * C * 8)) return false;
             if (!launch(q0, m)) {
                 fprintf(stderr, "%s: graph launch failed\n", fn);
                 return false;
             }
-            if (!merge_and_finish(ix, n_chunks, m, k, nullptr, d_dist, d_ids)) return false;
-            if (hipGetLastError() != hipSuccess) { fprintf(stderr, "%s: launch failed\n", fn); return false; }
+            if (!merge_and_finish(ix, p.n_chunks, m, k, nullptr, d_dist, d_ids) || !launched(true, fn)) return false;
         }
         if (!sink(q0, m, (const float *)d_dist, (const int64_t *)d_ids)) return false;
     }
@@ -566,53 +527,6 @@ auto block_to_host(const clip_amd_index * ix, int k, float * distances, int64_t 
     };
 }
 
-// The k-NN graph on the host, by search_blocks (scan route: the self-excluding scan over the gathered rows; tiled route: graph_kernel
-// straight from the store).
-bool knn_graph_impl(clip_amd_index * ix, int k, float * distances, int64_t * ids, const char * fn) {
-    hipStream_t st = stream_of(ix);
-    const int64_t n = ix->n;
-    if (n == 0) return true;
-    const bool tiled = ix->knn_route ? ix->knn_route == 2 : n >= KNN_TILED_MIN_ROWS;
-    const uint32_t * mask = ix->removed > 0 ? ix->store.live : nullptr;
-    const int64_t block = query_block(n, k, 12);
-    int n_chunks = 1;
-    int64_t rpc = (n + 127) / 128 * 128;
-    if (tiled) tiled_chunks(n, block, k, rpc, n_chunks);
-    return search_blocks(
-        ix, n, k, block, tiled, n_chunks, nullptr, fn, [&](int64_t q0, int) { return stored_rows(nullptr, q0, true); },
-        [&](int64_t q0, int m) {
-            return launch_graph(ix->store.rows, ix->store.rinv, n, q0, m, ix->Dpad, ix->dtype, k, ix->cand.p, n_chunks, rpc, mask, st);
-        },
-        block_to_host(ix, k, distances, ids, fn));
-}
-
-// The core distances of the mutual-reachability tree (clip_amd_index_linkage_core): core [linkage_core_bytes(n)] on the device, per row of
-// E (mask: live & allow, NULL every row) the distance to its k-th nearest other row of E, +inf with fewer than k of them and for every
-// row outside E; k == 0: -inf over E.  The neighbour search of knn_graph_impl on both of its routes, under the mask, with
-// launch_linkage_core as the sink: nothing visits the host.  d_allow: the caller's allowed set behind mask (the scan route applies it).
-bool core_column(clip_amd_index * ix, int k, const uint32_t * d_allow, const uint32_t * mask, float * d_core, const char * fn) {
-    hipStream_t st = stream_of(ix);
-    const int64_t n = ix->n;
-    if (k == 0 || n == 1) {                                    // (a single row has no other row)
-        launch_linkage_core(nullptr, 0, (int)n, 1, k == 0 ? -INFINITY : INFINITY, mask, d_core, st);
-        return hipGetLastError() == hipSuccess;
-    }
-    const bool tiled = ix->knn_route ? ix->knn_route == 2 : n >= KNN_TILED_MIN_ROWS;
-    const int64_t block = query_block(n, k, 12);
-    int n_chunks = 1;
-    int64_t rpc = (n + 127) / 128 * 128;
-    if (tiled) tiled_chunks(n, block, k, rpc, n_chunks);
-    return search_blocks(
-        ix, n, k, block, tiled, n_chunks, d_allow, fn, [&](int64_t q0, int) { return stored_rows(nullptr, q0, true); },
-        [&](int64_t q0, int m) {
-            return launch_graph(ix->store.rows, ix->store.rinv, n, q0, m, ix->Dpad, ix->dtype, k, ix->cand.p, n_chunks, rpc, mask, st);
-        },
-        [&](int64_t q0, int m, const float * d_dist, const int64_t *) {
-            launch_linkage_core(d_dist, q0, m, k, 0.0f, mask, d_core, st);
-            return hipGetLastError() == hipSuccess;
-        });
-}
-
 // Queries from which the automatic route of clip_amd_index_search_index takes the tiled kernel (ids == NULL only); below, the scan route.
 // Measured (profiles/cross_bench.txt, "crossover"; MI355X, dim 512): the smallest swept query count from which on the tiled route's median
 // wall time is below the scan route's on every dtype is 2048 over an index of 256 and of 1024 rows (a call of the tiled route costs about
@@ -620,44 +534,63 @@ bool core_column(clip_amd_index * ix, int k, const uint32_t * d_allow, const uin
 // constant is the largest of the three, so the automatic route never takes the slower kernel of a label-sized index.
 constexpr int64_t CROSS_TILED_MIN_QUERIES = 2048;
 
+}  // namespace
+
+// The k-NN graph on the host, by search_blocks (scan route: the self-excluding scan over the gathered rows; tiled route: graph_kernel
+// straight from the store).
+bool idx::knn_graph_impl(clip_amd_index * ix, int k, float * distances, int64_t * ids, const char * fn) {
+    if (ix->n == 0) return true;
+    const uint32_t * mask = ix->removed > 0 ? ix->store.live : nullptr;
+    const int64_t block = query_block(ix->n, k, 12);
+    const GraphPlan p = graph_plan(ix, k, ix->knn_route, knn_auto_tiled(ix), block, block);
+    return search_blocks(
+        ix, ix->n, k, p, nullptr, fn, [&](int64_t q0, int) { return stored_rows(nullptr, q0, true); },
+        [&](int64_t q0, int m) { return launch_graph_block(ix, p, k, q0, m, mask); }, block_to_host(ix, k, distances, ids, fn));
+}
+
+// The core distances of the mutual-reachability tree (clip_amd_index_linkage_core): core [linkage_core_bytes(n)] on the device, per row of
+// E (mask: live & allow, NULL every row) the distance to its k-th nearest other row of E, +inf with fewer than k of them and for every
+// row outside E; k == 0: -inf over E.  The neighbour search of knn_graph_impl on both of its routes, under the mask, with
+// launch_linkage_core as the sink: nothing visits the host.  d_allow: the caller's allowed set behind mask (the scan route applies it).
+bool idx::core_column(clip_amd_index * ix, int k, const uint32_t * d_allow, const uint32_t * mask, float * d_core, const char * fn) {
+    hipStream_t st = stream_of(ix);
+    const int64_t n = ix->n;
+    if (k == 0 || n == 1) {                                    // (a single row has no other row)
+        launch_linkage_core(nullptr, 0, (int)n, 1, k == 0 ? -INFINITY : INFINITY, mask, d_core, st);
+        return hipGetLastError() == hipSuccess;
+    }
+    const int64_t block = query_block(n, k, 12);
+    const GraphPlan p = graph_plan(ix, k, ix->knn_route, knn_auto_tiled(ix), block, block);
+    return search_blocks(
+        ix, n, k, p, d_allow, fn, [&](int64_t q0, int) { return stored_rows(nullptr, q0, true); },
+        [&](int64_t q0, int m) { return launch_graph_block(ix, p, k, q0, m, mask); },
+        [&](int64_t q0, int m, const float * d_dist, const int64_t *) {
+            launch_linkage_core(d_dist, q0, m, k, 0.0f, mask, d_core, st);
+            return hipGetLastError() == hipSuccess;
+        });
+}
+
 // clip_amd_index_search_index on the host: the nq queries are the rows ids[0 ... nq) of src (host ids) or, ids NULL, its rows 0 ... nq - 1,
 // by search_blocks (scan route: the scan over rows gathered from src's store; tiled route: the CROSS graph_kernel straight from both stores).
-bool search_index_impl(clip_amd_index * ix, const clip_amd_index * src, const int64_t * ids, int64_t nq, int k, const uint64_t * allow,
-                       float * distances, int64_t * out_ids, const char * fn) {
-    hipStream_t st = stream_of(ix);
+bool idx::search_index_impl(clip_amd_index * ix, const clip_amd_index * src, const int64_t * ids, int64_t nq, int k, const uint64_t * allow,
+                            float * distances, int64_t * out_ids, const char * fn) {
     if (nq == 0) return true;
-    const bool tiled = !ids && ix->n > 0 && (ix->cross_route ? ix->cross_route == 2 : nq >= CROSS_TILED_MIN_QUERIES);
     const int64_t block = query_block(nq, k, 12);
+    // (the tiled kernel reads src's rows in order and needs a row to score: with ids, or over an empty index, the route is the scan's, 1)
+    const GraphPlan p = graph_plan(ix, k, !ids && ix->n > 0 ? ix->cross_route : 1, nq >= CROSS_TILED_MIN_QUERIES, block, block);
     const uint32_t * d_allow = nullptr;
-    if (!upload_allow(ix, allow, d_allow)) return false;
     const uint32_t * mask = nullptr;
-    int n_chunks = 1;
-    int64_t rpc = 128;
-    if (tiled) {
-        if (!effective_mask(ix, d_allow, mask)) return false;
-        tiled_chunks(ix->n, block, k, rpc, n_chunks);
-    }
-    if (ids && !ensure(ix, ix->idbuf, (size_t)block * 8)) return false;
+    if (!upload_allow(ix, allow, d_allow) || (p.tiled && !effective_mask(ix, d_allow, mask)) || !reserve_stage(ix, nullptr, ids, block)) return false;
     return search_blocks(
-        ix, nq, k, block, tiled, n_chunks, d_allow, fn,
-        [&](int64_t q0, int m) {
-            if (ids) (void)hipMemcpyAsync(ix->idbuf.p, ids + q0, (size_t)m * 8, hipMemcpyHostToDevice, st);
-            return stored_rows(ids ? (const int64_t *)ix->idbuf.p : nullptr, ids ? 0 : q0, false, src);
-        },
+        ix, nq, k, p, d_allow, fn, [&](int64_t q0, int m) { return stage_block(ix, nullptr, ids, q0, m, false, src); },
         [&](int64_t q0, int m) {
             return launch_graph_cross(ix->store.rows, ix->store.rinv, ix->n, src->store.rows, src->store.rinv, src->n, q0, m, ix->Dpad, ix->dtype, k,
-                                      ix->cand.p, n_chunks, rpc, mask, st);
+                                      ix->cand.p, p.n_chunks, p.rpc, mask, stream_of(ix));
         },
         block_to_host(ix, k, distances, out_ids, fn));
 }
 
-// The four result arrays of a vote ([rows][m] each), on the device or on the host
-struct VoteOut {
-    int32_t * classes = nullptr;
-    int32_t * votes = nullptr;
-    float * dist = nullptr;
-    int64_t * ids = nullptr;
-};
+namespace {
 
 int64_t vote_block_size(const clip_amd_index * ix, int64_t nq, int k) { return ix->vote_block > 0 ? ix->vote_block : query_block(nq, k, 12); }
 
@@ -676,9 +609,10 @@ bool vote_impl(clip_amd_index * ix, int64_t nq, int k, int m, bool graph, const 
     hipStream_t st = stream_of(ix);
     const int64_t n = ix->n;
     if (nq == 0) return true;
-    const int64_t block = vote_block_size(ix, nq, k);
+    GraphPlan p;                                               // (an empty index: blocks only)
+    p.block = vote_block_size(ix, nq, k);
     uint32_t * voters = nullptr;
-    bool tiled = false, mixed = false;
+    bool mixed = false;
     if (n > 0) {
         const size_t vb = live_bytes(n);
         if (!ensure(ix, ix->vvoters, vb + 16)) return false;
@@ -686,20 +620,17 @@ bool vote_impl(clip_amd_index * ix, int64_t nq, int k, int m, bool graph, const 
         uint32_t * d_mixed = (uint32_t *)((char *)ix->vvoters.p + vb);
         (void)hipMemsetAsync(d_mixed, 0, 4, st);
         launch_vote_voters(ix->store.live, d_allow, search_allow_words(n), d_labels, voters, (int64_t)(vb / 4), d_mixed, st);
-        if (hipGetLastError() != hipSuccess) { fprintf(stderr, "%s: launch failed\n", fn); return false; }
-        tiled = graph && (ix->knn_route ? ix->knn_route == 2 : n >= KNN_TILED_MIN_ROWS);
-        if (tiled) {
+        if (!launched(true, fn)) return false;
+        p = graph_plan(ix, k, graph ? ix->knn_route : 1, knn_auto_tiled(ix), p.block, (p.block + 127) / 128 * 128);
+        if (p.tiled) {
             uint32_t h = 0;
             if (!stream_done(ix, fn, hipMemcpyAsync(&h, d_mixed, 4, hipMemcpyDeviceToHost, st))) return false;
             mixed = h != 0;
         }
     }
-    int n_chunks = 1;
-    int64_t rpc = (n + 127) / 128 * 128;
-    if (tiled) tiled_chunks(n, (block + 127) / 128 * 128, k, rpc, n_chunks);
     const uint32_t * graph_mask = mixed ? voters : (ix->removed > 0 ? ix->store.live : nullptr);
-    for (int64_t q0 = 0; q0 < nq; q0 += block) {
-        const int mb = (int)std::min(block, nq - q0);
+    for (int64_t q0 = 0; q0 < nq; q0 += p.block) {
+        const int mb = (int)std::min(p.block, nq - q0);
         const VoteOut o = dest(q0);
         const auto fold = [&](bool rest) {
             return [&, rest](int64_t, int mm, const float * d_dist, const int64_t * d_ids) {
@@ -711,20 +642,17 @@ bool vote_impl(clip_amd_index * ix, int64_t nq, int k, int m, bool graph, const 
         const auto no_launch = [](int64_t, int) { return false; };
         if (n == 0) {
             launch_vote_fold(nullptr, nullptr, mb, k, nullptr, m, 0, nullptr, nullptr, o.classes, o.votes, o.dist, o.ids, st);
-            if (hipGetLastError() != hipSuccess) { fprintf(stderr, "%s: launch failed\n", fn); return false; }
-        } else if (!tiled) {
-            if (!search_blocks(ix, mb, k, block, false, 1, voters, fn, [&](int64_t, int) { return source(q0, mb); }, no_launch, fold(false))) return false;
+            if (!launched(true, fn)) return false;
+        } else if (!p.tiled) {
+            if (!search_blocks(ix, mb, k, p, voters, fn, [&](int64_t, int) { return source(q0, mb); }, no_launch, fold(false))) return false;
         } else {
-            if (!search_blocks(ix, mb, k, block, true, n_chunks, nullptr, fn, no_source,
-                               [&](int64_t, int mm) {
-                                   return launch_graph(ix->store.rows, ix->store.rinv, n, q0, mm, ix->Dpad, ix->dtype, k, ix->cand.p, n_chunks, rpc, graph_mask, st);
-                               },
+            if (!search_blocks(ix, mb, k, p, nullptr, fn, no_source, [&](int64_t, int mm) { return launch_graph_block(ix, p, k, q0, mm, graph_mask); },
                                fold(false)))
                 return false;
-            if (mixed && !search_blocks(ix, mb, k, block, true, n_chunks, nullptr, fn, no_source,
+            if (mixed && !search_blocks(ix, mb, k, p, nullptr, fn, no_source,
                                         [&](int64_t, int mm) {
                                             return launch_graph_cross(ix->store.rows, ix->store.rinv, n, ix->store.rows, ix->store.rinv, n, q0, mm, ix->Dpad,
-                                                                      ix->dtype, k, ix->cand.p, n_chunks, rpc, voters, st);
+                                                                      ix->dtype, k, ix->cand.p, p.n_chunks, p.rpc, voters, st);
                                         },
                                         fold(true)))
                 return false;
@@ -734,10 +662,12 @@ bool vote_impl(clip_amd_index * ix, int64_t nq, int k, int m, bool graph, const 
     return true;
 }
 
+}  // namespace
+
 // The host forms of the votes: the queries are f32 vectors (queries), stored rows (ids), both on the host, or, with neither, every stored
 // row with itself excluded (the graph form).  Labels and the allowed set go up once; a block's queries are staged, its folded results
-// ([m_block][m]) land in the vouts workspace and are copied out before the next block, so nothing on the device grows with nq x k.
-bool vote_host(clip_amd_index * ix, const float * queries, const int64_t * ids, int64_t nq, int k, int m, bool exclude_self, const int32_t * labels,
+// ([m_block][m]) land in the results arena and are copied out before the next block, so nothing on the device grows with nq x k.
+bool idx::vote_host(clip_amd_index * ix, const float * queries, const int64_t * ids, int64_t nq, int k, int m, bool exclude_self, const int32_t * labels,
                const uint64_t * allow, const VoteOut & out, const char * fn) {
     hipStream_t st = stream_of(ix);
     if (nq == 0) return true;
@@ -754,43 +684,33 @@ bool vote_host(clip_amd_index * ix, const float * queries, const int64_t * ids, 
     }
     const int64_t block = vote_block_size(ix, nq, k);
     const size_t slots = (size_t)block * m;
-    if (!ensure(ix, ix->vouts, slots * 20)) return false;
-    if (ids ? !ensure(ix, ix->idbuf, (size_t)block * 8) : (queries && !ensure(ix, ix->stage, (size_t)block * ix->dim * 4))) return false;
+    Arena a(ix);
+    const auto o_ids = a.add(out.ids, slots);
+    const auto o_classes = a.add(out.classes, slots), o_votes = a.add(out.votes, slots);
+    const auto o_dist = a.add(out.dist, slots);
+    if (!a.ready() || !reserve_stage(ix, queries, ids, block)) return false;
     VoteOut d;
-    d.ids = (int64_t *)ix->vouts.p;
-    d.classes = (int32_t *)((char *)ix->vouts.p + slots * 8);
-    d.votes = (int32_t *)((char *)ix->vouts.p + slots * 12);
-    d.dist = (float *)((char *)ix->vouts.p + slots * 16);
+    d.ids = a.dev(o_ids);
+    d.classes = a.dev(o_classes);
+    d.votes = a.dev(o_votes);
+    d.dist = a.dev(o_dist);
     return vote_impl(
-        ix, nq, k, m, !ids && !queries, d_labels, d_allow, fn,
-        [&](int64_t q0, int mb) {
-            if (ids) {
-                (void)hipMemcpyAsync(ix->idbuf.p, ids + q0, (size_t)mb * 8, hipMemcpyHostToDevice, st);
-                return stored_rows((const int64_t *)ix->idbuf.p, 0, exclude_self);
-            }
-            if (queries) {
-                (void)hipMemcpyAsync(ix->stage.p, queries + (size_t)q0 * ix->dim, (size_t)mb * ix->dim * 4, hipMemcpyHostToDevice, st);
-                return vectors((const float *)ix->stage.p);
-            }
-            return stored_rows(nullptr, q0, true);
-        },
+        ix, nq, k, m, !ids && !queries, d_labels, d_allow, fn, [&](int64_t q0, int mb) { return stage_block(ix, queries, ids, q0, mb, exclude_self); },
         [&](int64_t) { return d; },
         [&](int64_t q0, int mb) {
-            const size_t to = (size_t)q0 * m, cnt = (size_t)mb * m;
-            (void)hipMemcpyAsync(out.classes + to, d.classes, cnt * 4, hipMemcpyDeviceToHost, st);
-            (void)hipMemcpyAsync(out.votes + to, d.votes, cnt * 4, hipMemcpyDeviceToHost, st);
-            (void)hipMemcpyAsync(out.dist + to, d.dist, cnt * 4, hipMemcpyDeviceToHost, st);
-            (void)hipMemcpyAsync(out.ids + to, d.ids, cnt * 8, hipMemcpyDeviceToHost, st);
+            a.queue(0, a.n, 0, (size_t)q0 * m, (size_t)mb * m);
             return stream_done(ix, fn, hipGetLastError());      // (the staging buffers and the block's results are reused)
         });
 }
 
+namespace {
+
 // The device forms: queries, labels and allowed set on the device, results straight into the caller's arrays
 bool vote_device(clip_amd_index * ix, const float * d_queries, int64_t nq, int k, int m, const int * d_labels, const uint32_t * d_allow,
                  const VoteOut & out, const char * fn) {
+    const QuerySource src = d_queries ? vectors(d_queries) : stored_rows(nullptr, 0, true);
     return vote_impl(
-        ix, nq, k, m, !d_queries, d_labels, ix->n > 0 ? d_allow : nullptr, fn,
-        [&](int64_t q0, int) { return d_queries ? vectors(d_queries + (size_t)q0 * ix->dim) : stored_rows(nullptr, q0, true); },
+        ix, nq, k, m, !d_queries, d_labels, ix->n > 0 ? d_allow : nullptr, fn, [&](int64_t q0, int) { return advance(src, q0, ix->dim); },
         [&](int64_t q0) {
             const size_t to = (size_t)q0 * m;
             VoteOut o;
@@ -807,8 +727,8 @@ bool vote_device(clip_amd_index * ix, const float * d_queries, int64_t nq, int k
 // label; host_labels: each of them >= -1
 bool check_vote_args(const clip_amd_index * ix, int k, int m, bool any_rows, const int32_t * labels, bool host_labels, const VoteOut & o,
                      const char * fn) {
-    if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
-    if (k < 1 || k > MAX_K) { fprintf(stderr, "%s: k = %d outside 1 ... %d\n", fn, k, MAX_K); return false; }
+    if (!check_index(ix, fn)) return false;
+    if (!check_k(k, 1, fn)) return false;
     if (m < 1) { fprintf(stderr, "%s: m = %d < 1\n", fn, m); return false; }
     if (m > k) { fprintf(stderr, "%s: m = %d exceeds k = %d\n", fn, m, k); return false; }
     if (any_rows && (!o.classes || !o.votes || !o.dist || !o.ids)) { fprintf(stderr, "%s: NULL result pointer\n", fn); return false; }
@@ -832,9 +752,9 @@ bool check_pair(const clip_amd_index * ix, const clip_amd_index * src, const cha
 }
 
 bool check_search_args(const clip_amd_index * ix, const void * q, int nq, int k, const void * dist, const void * ids, const char * fn) {
-    if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+    if (!check_index(ix, fn)) return false;
     if (nq < 0) { fprintf(stderr, "%s: n_queries %d < 0\n", fn, nq); return false; }
-    if (k < 1 || k > MAX_K) { fprintf(stderr, "%s: k = %d outside 1 ... %d\n", fn, k, MAX_K); return false; }
+    if (!check_k(k, 1, fn)) return false;
     if (nq > 0 && (!q || !dist || !ids)) { fprintf(stderr, "%s: NULL queries or result pointer\n", fn); return false; }
     return true;
 }
@@ -857,16 +777,18 @@ bool check_set_args(int64_t nq, const int64_t * lims, int64_t n_sets, const void
     return true;
 }
 
+}  // namespace
+
 // Query sets on the device: the nq query rows of src in the n_sets sets of lims (host, [n_sets + 1], row numbers of src), results into
 // d_dist / d_ids / d_qrows ([n_sets][k], device).  first_kept: slot 0 already holds the result so far of set 0 (a set that began in an
 // earlier block of a host form) and is folded on; every other slot starts empty.  lims is read before the call returns.
-bool sets_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, const int64_t * lims, int64_t n_sets, int k, const int * d_groups,
+bool idx::sets_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, const int64_t * lims, int64_t n_sets, int k, const int * d_groups,
                       bool own, const uint32_t * d_allow, float * d_dist, int64_t * d_ids, int * d_qrows, int64_t qrow_base, bool first_kept) {
     hipStream_t st = stream_of(ix);
     if (n_sets == 0) return true;
     const int64_t skip = first_kept ? 1 : 0;
     launch_sets_fill(d_dist + skip * k, d_ids + skip * k, d_qrows + skip * k, (n_sets - skip) * k, st);
-    if (hipGetLastError() != hipSuccess) { fprintf(stderr, "clip_amd_index_search_sets: launch failed\n"); return false; }
+    if (!launched(true, "clip_amd_index_search_sets")) return false;
     if (nq == 0 || ix->n == 0) return true;
     if (!ensure(ix, ix->slims, (size_t)(n_sets + 1) * 8)) return false;
     if (hipMemcpyAsync(ix->slims.p, lims, (size_t)(n_sets + 1) * 8, hipMemcpyHostToDevice, st) != hipSuccess) {
@@ -884,6 +806,8 @@ bool sets_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, cons
     f.own = own;
     return search_device_impl(ix, src, nq, k, d_allow, nullptr, nullptr, d_groups, &f);
 }
+
+namespace {
 
 // The host forms of the query-set searches: the nq query rows are f32 vectors (queries) or stored rows (ids), both on the host.  Query
 // blocks of a fixed size, as in knn_graph_impl, one after another; a block's rows are staged, searched as the sets (and parts of sets) they
@@ -908,11 +832,14 @@ bool sets_host_impl(clip_amd_index * ix, const float * queries, const int64_t * 
     int64_t block = query_block(nq, k, 16);
     if (ix->sets_block > 0) block = ix->sets_block;
     const size_t slots = (size_t)block * k;                // a block of m rows holds at most m sets
-    if (!ensure(ix, ix->souts, slots * 16) || (ids ? !ensure(ix, ix->idbuf, (size_t)block * 8) : !ensure(ix, ix->stage, (size_t)block * ix->dim * 4)))
-        return false;
-    int64_t * d_out = (int64_t *)ix->souts.p;
-    float * d_dist = (float *)((char *)ix->souts.p + slots * 8);
-    int * d_qrows = (int *)((char *)ix->souts.p + slots * 12);
+    Arena a(ix);                                           // (laid out once: the carried set stays in its slot from block to block)
+    const auto o_ids = a.add(out_ids, slots);
+    const auto o_dist = a.add(distances, slots);
+    const auto o_qrows = a.add(qrows, slots);
+    if (!a.ready() || !reserve_stage(ix, queries, ids, block)) return false;
+    int64_t * d_out = a.dev(o_ids);
+    float * d_dist = a.dev(o_dist);
+    int * d_qrows = a.dev(o_qrows);
     std::vector<int64_t> local;
     size_t j_lo = 0;
     int64_t carried = -1;                                  // slot of the previous block that holds the result so far of this block's first set
@@ -931,24 +858,14 @@ bool sets_host_impl(clip_amd_index * ix, const float * queries, const int64_t * 
             (void)hipMemcpyAsync(d_dist, d_dist + carried * k, (size_t)k * 4, hipMemcpyDeviceToDevice, st);
             (void)hipMemcpyAsync(d_qrows, d_qrows + carried * k, (size_t)k * 4, hipMemcpyDeviceToDevice, st);
         }
-        QuerySource qs;
-        if (ids) {
-            (void)hipMemcpyAsync(ix->idbuf.p, ids + r0, (size_t)m * 8, hipMemcpyHostToDevice, st);
-            qs = stored_rows((const int64_t *)ix->idbuf.p, 0, false);
-        } else {
-            (void)hipMemcpyAsync(ix->stage.p, queries + (size_t)r0 * ix->dim, (size_t)m * ix->dim * 4, hipMemcpyHostToDevice, st);
-            qs = vectors((const float *)ix->stage.p);
-        }
+        const QuerySource qs = stage_block(ix, queries, ids, r0, m, false);
         if (!sets_device_impl(ix, qs, m, local.data(), ns, k, d_groups, own, d_allow, d_dist, d_out, d_qrows, r0, first_kept)) return false;
         const bool last_open = lims[sets[j_hi - 1] + 1] > r0 + m;      // the block's last set goes on in the next block
         const size_t j_done = last_open ? j_hi - 1 : j_hi;
         for (size_t j = j_lo; j < j_done;) {                // one copy per run of consecutive sets
             size_t e = j + 1;
             while (e < j_done && sets[e] == sets[e - 1] + 1) e++;
-            const size_t from = (j - j_lo) * k, to = (size_t)sets[j] * k, cnt = (e - j) * k;
-            (void)hipMemcpyAsync(out_ids + to, d_out + from, cnt * 8, hipMemcpyDeviceToHost, st);
-            (void)hipMemcpyAsync(distances + to, d_dist + from, cnt * 4, hipMemcpyDeviceToHost, st);
-            (void)hipMemcpyAsync(qrows + to, d_qrows + from, cnt * 4, hipMemcpyDeviceToHost, st);
+            a.queue(0, a.n, (j - j_lo) * k, (size_t)sets[j] * k, (e - j) * k);
             j = e;
         }
         if (!stream_done(ix, fn, hipGetLastError())) return false;      // (the staging buffers and `local` are reused by the next block)
@@ -965,10 +882,12 @@ int distinct_block_size(const clip_amd_index * ix, int pool) {
     return (int)std::min<size_t>(DISTINCT_BLOCK_MAX, std::max<size_t>(1, DISTINCT_NEAR_BUDGET / near_q));
 }
 
+}  // namespace
+
 // Distinct search on the device: query blocks one after another, each searched with k = pool into the pool workspace (the [m][pool]
 // distances and ids after the finish), then the near bitmap over the pool's stored rows and the walk of k_distinct.hip into d_dist / d_ids
 // / d_counts ([nq][k], device).  A query's pool, bitmap and walk are its own, so the cut into blocks does not show in the result.
-bool distinct_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, int k, float radius, int pool, const uint32_t * d_allow,
+bool idx::distinct_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, int k, float radius, int pool, const uint32_t * d_allow,
                           float * d_dist, int64_t * d_ids, int * d_counts) {
     hipStream_t st = stream_of(ix);
     const int block = std::min(distinct_block_size(ix, pool), nq);
@@ -978,57 +897,42 @@ bool distinct_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, 
     float * p_dist = (float *)((char *)ix->dpool.p + slots * 8);
     for (int q0 = 0; q0 < nq; q0 += block) {
         const int m = std::min(block, nq - q0);
-        QuerySource part = src;
-        if (!part.by_id) part.d_q += (size_t)q0 * ix->dim;
-        else if (part.d_ids) part.d_ids += q0;
-        else part.first += q0;
-        if (!search_device_impl(ix, part, m, pool, d_allow, p_dist, p_ids)) return false;
+        if (!search_device_impl(ix, advance(src, q0, ix->dim), m, pool, d_allow, p_dist, p_ids)) return false;
         launch_distinct_near(ix->store.rows, ix->store.rinv, ix->Dpad, ix->dtype, p_ids, m, pool, radius, (uint32_t *)ix->dnear.p, st);
         launch_distinct_pick(p_dist, p_ids, (const uint32_t *)ix->dnear.p, m, pool, k, d_dist + (size_t)q0 * k, d_ids + (size_t)q0 * k,
                              d_counts + (size_t)q0 * k, st);
-        if (hipGetLastError() != hipSuccess) {
-            fprintf(stderr, "clip_amd_index_search_distinct: launch failed\n");
-            return false;
-        }
+        if (!launched(true, "clip_amd_index_search_distinct")) return false;
     }
     return true;
 }
+
+// the pool of a distinct search when the caller leaves it to the library
+int idx::auto_pool(int k) { return std::min(MAX_K, std::max(64, 8 * k)); }
+
+namespace {
 
 // The host forms of the distinct searches: the nq queries are f32 vectors (queries) or stored rows (ids), both on the host.  Query blocks
 // of distinct_block_size, one after another: a block's queries are staged, searched and its results copied out, so nothing on the device
 // grows with nq.
 bool distinct_host_impl(clip_amd_index * ix, const float * queries, const int64_t * ids, int nq, int k, float radius, int pool, bool exclude_self,
                         const uint64_t * allow, float * distances, int64_t * out_ids, int32_t * counts, const char * fn) {
-    hipStream_t st = stream_of(ix);
     const uint32_t * d_allow = nullptr;
-    if (!upload_allow(ix, allow, d_allow)) return false;
     const int block = std::min(distinct_block_size(ix, pool), nq);
     const size_t slots = (size_t)block * k;
-    if (!ensure(ix, ix->douts, slots * 16) || (ids ? !ensure(ix, ix->idbuf, (size_t)block * 8) : !ensure(ix, ix->stage, (size_t)block * ix->dim * 4)))
-        return false;
-    int64_t * d_out = (int64_t *)ix->douts.p;
-    float * d_dist = (float *)((char *)ix->douts.p + slots * 8);
-    int * d_counts = (int *)((char *)ix->douts.p + slots * 12);
+    Arena a(ix);
+    const auto o_ids = a.add(out_ids, slots);
+    const auto o_dist = a.add(distances, slots);
+    const auto o_counts = a.add(counts, slots);
+    if (!upload_allow(ix, allow, d_allow) || !a.ready() || !reserve_stage(ix, queries, ids, block)) return false;
     for (int q0 = 0; q0 < nq; q0 += block) {
         const int m = std::min(block, nq - q0);
-        QuerySource qs;
-        if (ids) {
-            (void)hipMemcpyAsync(ix->idbuf.p, ids + q0, (size_t)m * 8, hipMemcpyHostToDevice, st);
-            qs = stored_rows((const int64_t *)ix->idbuf.p, 0, exclude_self);
-        } else {
-            (void)hipMemcpyAsync(ix->stage.p, queries + (size_t)q0 * ix->dim, (size_t)m * ix->dim * 4, hipMemcpyHostToDevice, st);
-            qs = vectors((const float *)ix->stage.p);
-        }
-        if (!distinct_device_impl(ix, qs, m, k, radius, pool, d_allow, d_dist, d_out, d_counts)) return false;
-        const size_t cnt = (size_t)m * k;
-        (void)hipMemcpyAsync(counts + (size_t)q0 * k, d_counts, cnt * 4, hipMemcpyDeviceToHost, st);
-        if (!copy_results(ix, d_dist, d_out, cnt, distances + (size_t)q0 * k, out_ids + (size_t)q0 * k, fn)) return false;      // (the staging buffers are reused)
+        const QuerySource qs = stage_block(ix, queries, ids, q0, m, exclude_self);
+        if (!distinct_device_impl(ix, qs, m, k, radius, pool, d_allow, a.dev(o_dist), a.dev(o_ids), a.dev(o_counts))) return false;
+        a.queue(0, a.n, 0, (size_t)q0 * k, (size_t)m * k);
+        if (!stream_done(ix, fn)) return false;                // (the staging buffers and the block's results are reused)
     }
     return true;
 }
-
-// the pool of a distinct search when the caller leaves it to the library
-int auto_pool(int k) { return std::min(MAX_K, std::max(64, 8 * k)); }
 
 // what the distinct searches ask beyond check_search_args; pool 0 becomes the automatic value
 bool check_distinct_args(const clip_amd_index * ix, int nq, int k, float radius, int & pool, const void * counts, const char * fn) {
@@ -1071,11 +975,13 @@ bool check_stored_ids(clip_amd_index * ix, const int64_t * ids, int64_t n, const
     return true;
 }
 
+}  // namespace
+
 // Range search (d_q: nq f32 queries on the device) or pairs (d_q NULL, the rows against the rows, row > query): one scoring pass counts
 // every segment and keeps up to min(capacity, JOIN_HIT_BUDGET) hits; a second pass runs only when the total fits the caller's capacity
 // but not that list.  lims [segments + 1] is always written; when total <= capacity the hits are placed in their segments, sorted and
 // copied out.  Returns the total or -1.
-int64_t join_impl(clip_amd_index * ix, const float * d_q, int nq, bool pairs, float radius, const uint32_t * d_allow, int64_t * lims,
+int64_t idx::join_impl(clip_amd_index * ix, const float * d_q, int nq, bool pairs, float radius, const uint32_t * d_allow, int64_t * lims,
                   float * distances, int64_t * ids, int64_t capacity, const char * fn) {
     hipStream_t st = stream_of(ix);
     const uint32_t * mask = nullptr;
@@ -1117,26 +1023,25 @@ int64_t join_impl(clip_amd_index * ix, const float * d_q, int nq, bool pairs, fl
     }
     const int64_t tot = lims[nseg];
     if (tot > capacity || tot == 0) return tot;
-    if (!ensure(ix, ix->joffs, (size_t)(nseg + 1) * 8) || !ensure(ix, ix->jsort, (size_t)tot * 16) || !ensure(ix, ix->jouts, (size_t)tot * 12))
-        return -1;
+    Arena a(ix);
+    const auto o_ids = a.add(ids, (size_t)tot);
+    const auto o_dist = a.add(distances, (size_t)tot);
+    if (!ensure(ix, ix->joffs, (size_t)(nseg + 1) * 8) || !ensure(ix, ix->jsort, (size_t)tot * 16) || !a.ready()) return -1;
     const int64_t * d_offs = (const int64_t *)ix->joffs.p;
     (void)hipMemcpyAsync(ix->joffs.p, lims, (size_t)(nseg + 1) * 8, hipMemcpyHostToDevice, st);
     (void)hipMemsetAsync(d_count, 0, (size_t)nseg * 4, st);
     launch_join_scatter(ix->hits.p, tot, d_offs, d_count, ix->jsort.p, st);
     const void * sorted = launch_join_sort(ix->jsort.p, (char *)ix->jsort.p + (size_t)tot * 8, d_offs, nseg, tot, longest, st);
-    int64_t * d_ids = (int64_t *)ix->jouts.p;
-    float * d_dist = (float *)((char *)ix->jouts.p + (size_t)tot * 8);
-    launch_join_finish(sorted, tot, d_dist, d_ids, st);
-    if (hipGetLastError() != hipSuccess) {
-        fprintf(stderr, "%s: launch failed\n", fn);
-        return -1;
-    }
-    return copy_results(ix, d_dist, d_ids, (size_t)tot, distances, ids, fn) ? tot : -1;
+    launch_join_finish(sorted, tot, a.dev(o_dist), a.dev(o_ids), st);
+    if (!launched(true, fn)) return -1;
+    return a.fetch(fn) ? tot : -1;
 }
+
+namespace {
 
 bool check_join_args(const clip_amd_index * ix, float radius, const int64_t * lims, const void * dist, const void * ids, int64_t capacity,
                      const char * fn) {
-    if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+    if (!check_index(ix, fn)) return false;
     if (!lims) { fprintf(stderr, "%s: lims is NULL\n", fn); return false; }
     if (std::isnan(radius)) { fprintf(stderr, "%s: radius is NaN\n", fn); return false; }
     if (capacity < 0) { fprintf(stderr, "%s: capacity %lld < 0\n", fn, (long long)capacity); return false; }
@@ -1152,40 +1057,35 @@ bool components_impl(clip_amd_index * ix, float radius, const uint32_t * d_allow
     if (!effective_mask(ix, d_allow, mask)) return false;
     if (!ensure(ix, ix->cparent, (size_t)ix->n * 2 * sizeof(int)) || !ensure(ix, ix->cnear, (size_t)ix->n * 8)) return false;
     if (d_groups) (void)hipMemsetAsync(d_groups, 0, 8, stream_of(ix));
-    if (!launch_components(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, radius, mask, (int *)ix->cparent.p,
-                           (unsigned long long *)ix->cnear.p, d_labels, d_ndist, d_nid, d_groups, stream_of(ix))) {
-        fprintf(stderr, "%s: launch failed\n", fn);
-        return false;
-    }
-    return true;
+    return launched(launch_components(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, radius, mask, (int *)ix->cparent.p,
+                           (unsigned long long *)ix->cnear.p, d_labels, d_ndist, d_nid, d_groups, stream_of(ix)), fn);
 }
 
 bool check_components_args(const clip_amd_index * ix, float radius, const void * labels, const char * fn) {
-    if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+    if (!check_index(ix, fn)) return false;
     if (!labels) { fprintf(stderr, "%s: labels is NULL\n", fn); return false; }
     if (std::isnan(radius)) { fprintf(stderr, "%s: radius is NaN\n", fn); return false; }
     return true;
 }
 
-// The host form: the outputs in their workspace, then copied out with the group count.  Returns that count or -1.
-int64_t components_host(clip_amd_index * ix, float radius, const uint64_t * allow, int64_t * labels, float * ndist, int64_t * nid, const char * fn) {
+}  // namespace
+
+// The host form: the outputs in the results arena, then copied out with the group count.  Returns that count or -1.
+int64_t idx::components_host(clip_amd_index * ix, float radius, const uint64_t * allow, int64_t * labels, float * ndist, int64_t * nid, const char * fn) {
     if (ix->n == 0) return 0;
-    hipStream_t st = stream_of(ix);
     const size_t n = (size_t)ix->n;
     const uint32_t * d_allow = nullptr;
-    if (!upload_allow(ix, allow, d_allow) || !ensure(ix, ix->couts, 8 + n * 20)) return -1;
-    unsigned long long * d_groups = (unsigned long long *)ix->couts.p;
-    int64_t * d_labels = (int64_t *)((char *)ix->couts.p + 8);
-    int64_t * d_nid = d_labels + n;
-    float * d_ndist = (float *)(d_nid + n);
-    if (!components_impl(ix, radius, d_allow, d_labels, ndist ? d_ndist : nullptr, nid ? d_nid : nullptr, d_groups, fn)) return -1;
     unsigned long long groups = 0;
-    (void)hipMemcpyAsync(&groups, d_groups, 8, hipMemcpyDeviceToHost, st);
-    (void)hipMemcpyAsync(labels, d_labels, n * 8, hipMemcpyDeviceToHost, st);
-    if (ndist) (void)hipMemcpyAsync(ndist, d_ndist, n * 4, hipMemcpyDeviceToHost, st);
-    if (nid) (void)hipMemcpyAsync(nid, d_nid, n * 8, hipMemcpyDeviceToHost, st);
-    return stream_done(ix, fn) ? (int64_t)groups : -1;
+    Arena a(ix);
+    const auto o_groups = a.add(&groups, 1);
+    const auto o_labels = a.add(labels, n), o_nid = a.add(nid, n);
+    const auto o_ndist = a.add(ndist, n);
+    if (!upload_allow(ix, allow, d_allow) || !a.ready()) return -1;
+    if (!components_impl(ix, radius, d_allow, a.dev(o_labels), a.dev(o_ndist), a.dev(o_nid), a.dev(o_groups), fn)) return -1;
+    return a.fetch(fn) ? (int64_t)groups : -1;
 }
+
+namespace {
 
 // Density modes on the device: labels and, where asked for, every row's parent, the distance to it and its density; d_modes (may be NULL):
 // the number of modes.  Queues the launches and returns; ix->n > 0.
@@ -1197,12 +1097,8 @@ bool modes_impl(clip_amd_index * ix, float radius, float link, const uint32_t * 
         !ensure(ix, ix->mcount, (size_t)ix->n * 4))
         return false;
     if (d_modes) (void)hipMemsetAsync(d_modes, 0, 8, stream_of(ix));
-    if (!launch_modes(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, radius, link, mask, (uint32_t *)ix->mcount.p,
-                      (unsigned long long *)ix->cnear.p, (int *)ix->cparent.p, d_labels, d_parent, d_pdist, d_density, d_modes, stream_of(ix))) {
-        fprintf(stderr, "%s: launch failed\n", fn);
-        return false;
-    }
-    return true;
+    return launched(launch_modes(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, radius, link, mask, (uint32_t *)ix->mcount.p,
+                      (unsigned long long *)ix->cnear.p, (int *)ix->cparent.p, d_labels, d_parent, d_pdist, d_density, d_modes, stream_of(ix)), fn);
 }
 
 bool check_modes_args(const clip_amd_index * ix, float radius, float link, const void * labels, const char * fn) {
@@ -1211,30 +1107,26 @@ bool check_modes_args(const clip_amd_index * ix, float radius, float link, const
     return true;
 }
 
-// The host form: the outputs in their workspace, then copied out with the mode count.  Returns that count or -1.
-int64_t modes_host(clip_amd_index * ix, float radius, float link, const uint64_t * allow, int64_t * labels, int64_t * parent, float * pdist,
-                   int * density, const char * fn) {
+}  // namespace
+
+// The host form: the outputs in the results arena, then copied out with the mode count.  Returns that count or -1.
+int64_t idx::modes_host(clip_amd_index * ix, float radius, float link, const uint64_t * allow, int64_t * labels, int64_t * parent, float * pdist,
+                        int * density, const char * fn) {
     if (ix->n == 0) return 0;
-    hipStream_t st = stream_of(ix);
     const size_t n = (size_t)ix->n;
     const uint32_t * d_allow = nullptr;
-    if (!upload_allow(ix, allow, d_allow) || !ensure(ix, ix->mouts, 8 + n * 24)) return -1;
-    unsigned long long * d_modes = (unsigned long long *)ix->mouts.p;
-    int64_t * d_labels = (int64_t *)((char *)ix->mouts.p + 8);
-    int64_t * d_parent = d_labels + n;
-    float * d_pdist = (float *)(d_parent + n);
-    int * d_density = (int *)(d_pdist + n);
-    if (!modes_impl(ix, radius, link, d_allow, d_labels, parent ? d_parent : nullptr, pdist ? d_pdist : nullptr, density ? d_density : nullptr,
-                    d_modes, fn))
-        return -1;
     unsigned long long modes = 0;
-    (void)hipMemcpyAsync(&modes, d_modes, 8, hipMemcpyDeviceToHost, st);
-    (void)hipMemcpyAsync(labels, d_labels, n * 8, hipMemcpyDeviceToHost, st);
-    if (parent) (void)hipMemcpyAsync(parent, d_parent, n * 8, hipMemcpyDeviceToHost, st);
-    if (pdist) (void)hipMemcpyAsync(pdist, d_pdist, n * 4, hipMemcpyDeviceToHost, st);
-    if (density) (void)hipMemcpyAsync(density, d_density, n * 4, hipMemcpyDeviceToHost, st);
-    return stream_done(ix, fn) ? (int64_t)modes : -1;
+    Arena a(ix);
+    const auto o_modes = a.add(&modes, 1);
+    const auto o_labels = a.add(labels, n), o_parent = a.add(parent, n);
+    const auto o_pdist = a.add(pdist, n);
+    const auto o_density = a.add(density, n);
+    if (!upload_allow(ix, allow, d_allow) || !a.ready()) return -1;
+    if (!modes_impl(ix, radius, link, d_allow, a.dev(o_labels), a.dev(o_parent), a.dev(o_pdist), a.dev(o_density), a.dev(o_modes), fn)) return -1;
+    return a.fetch(fn) ? (int64_t)modes : -1;
 }
+
+namespace {
 
 // The single-linkage tree on the device: the edges and their number.  Queues the launches and returns.  k >= 0: the mutual-reachability
 // tree of clip_amd_index_linkage_core instead; the core distances go to the core workspace first (core_column) and from there to d_core
@@ -1254,46 +1146,38 @@ bool linkage_impl(clip_amd_index * ix, int k, float link, const uint32_t * d_all
             !ensure(ix, ix->lwork, linkage_work_bytes(ix->n)))
             return false;
     }
-    if (!launch_linkage(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, link, mask, core, (int *)ix->cparent.p,
-                        (unsigned long long *)ix->cnear.p, ix->lwork.p, d_lo, d_hi, d_dist, d_count, stream_of(ix))) {
-        fprintf(stderr, "%s: launch failed\n", fn);
-        return false;
-    }
-    return true;
+    return launched(launch_linkage(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, link, mask, core, (int *)ix->cparent.p,
+                        (unsigned long long *)ix->cnear.p, ix->lwork.p, d_lo, d_hi, d_dist, d_count, stream_of(ix)), fn);
 }
 
 bool check_linkage_args(const clip_amd_index * ix, float link, const void * lo, const void * hi, const void * dist, const char * fn) {
-    if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+    if (!check_index(ix, fn)) return false;
     if (!lo || !hi || !dist) { fprintf(stderr, "%s: NULL result pointer\n", fn); return false; }
     if (std::isnan(link)) { fprintf(stderr, "%s: link is NaN\n", fn); return false; }
     return true;
 }
 
-// what clip_amd_index_linkage_core asks of k beyond check_linkage_args
-bool check_core_k(int k, const char * fn) {
-    if (k < 0 || k > MAX_K) { fprintf(stderr, "%s: k = %d outside 0 ... %d\n", fn, k, MAX_K); return false; }
-    return true;
-}
+}  // namespace
 
 // The host form: the edges in their workspace, copied out and sorted by (d, lo, hi).  Returns their number or -1.  k as for linkage_impl;
 // k >= 0: core ([size], may be NULL) receives the core distances, which a single row has too.
-int64_t linkage_host(clip_amd_index * ix, int k, float link, const uint64_t * allow, int64_t * lo, int64_t * hi, float * dist, float * core,
+int64_t idx::linkage_host(clip_amd_index * ix, int k, float link, const uint64_t * allow, int64_t * lo, int64_t * hi, float * dist, float * core,
                      const char * fn) {
     ix->linkage_rounds = 0;
     if (ix->n <= (k >= 0 ? 0 : 1)) return 0;
     hipStream_t st = stream_of(ix);
     const size_t cap = (size_t)ix->n - 1;
     const uint32_t * d_allow = nullptr;
-    if (!upload_allow(ix, allow, d_allow) || !ensure(ix, ix->louts, 8 + cap * 20)) return -1;
-    int64_t * d_count = (int64_t *)ix->louts.p;
-    int64_t * d_lo = d_count + 1;
-    int64_t * d_hi = d_lo + cap;
-    float * d_dist = (float *)(d_hi + cap);
-    if (!linkage_impl(ix, k, link, d_allow, d_lo, d_hi, d_dist, nullptr, d_count, fn)) return -1;
     int64_t m = 0;
+    Arena a(ix);                                               // the count, then the edges, which are staged once the count is known
+    const auto o_count = a.add(&m, 1);
+    const auto o_lo = a.add<int64_t>(nullptr, cap), o_hi = a.add<int64_t>(nullptr, cap);
+    const auto o_dist = a.add<float>(nullptr, cap);
+    if (!upload_allow(ix, allow, d_allow) || !a.ready()) return -1;
+    if (!linkage_impl(ix, k, link, d_allow, a.dev(o_lo, true), a.dev(o_hi, true), a.dev(o_dist, true), nullptr, a.dev(o_count), fn)) return -1;
     std::vector<uint32_t> stat((size_t)2 * linkage_rounds(ix->n));
     std::vector<float> h_core(k >= 0 && core ? (size_t)ix->n : 0);      // (the caller's array stays untouched when the stream fails)
-    (void)hipMemcpyAsync(&m, d_count, 8, hipMemcpyDeviceToHost, st);
+    a.queue(o_count.i, o_count.i + 1);
     if (!stat.empty()) (void)hipMemcpyAsync(stat.data(), linkage_stat(ix->lwork.p, ix->n), stat.size() * 4, hipMemcpyDeviceToHost, st);
     if (!h_core.empty()) (void)hipMemcpyAsync(h_core.data(), ix->lcore.p, h_core.size() * 4, hipMemcpyDeviceToHost, st);
     if (!stream_done(ix, fn)) return -1;
@@ -1302,18 +1186,17 @@ int64_t linkage_host(clip_amd_index * ix, int k, float link, const uint64_t * al
     for (size_t r = 0; 2 * r < stat.size(); r++) ix->linkage_rounds += stat[2 * r] > 0 && stat[2 * r + 1] > 1;
     std::vector<int64_t> h_lo((size_t)m), h_hi((size_t)m);     // the caller's arrays stay untouched when the stream fails
     std::vector<float> h_dist((size_t)m);
-    if (m > 0) {
-        (void)hipMemcpyAsync(h_lo.data(), d_lo, (size_t)m * 8, hipMemcpyDeviceToHost, st);
-        (void)hipMemcpyAsync(h_hi.data(), d_hi, (size_t)m * 8, hipMemcpyDeviceToHost, st);
-        (void)hipMemcpyAsync(h_dist.data(), d_dist, (size_t)m * 4, hipMemcpyDeviceToHost, st);
-        if (!stream_done(ix, fn)) return -1;
-    }
+    a.to(o_lo, h_lo.data(), (size_t)m);
+    a.to(o_hi, h_hi.data(), (size_t)m);
+    a.to(o_dist, h_dist.data(), (size_t)m);
+    a.queue(o_lo.i, o_dist.i + 1);
+    if (m > 0 && !stream_done(ix, fn)) return -1;
     std::vector<int64_t> order((size_t)m);
     for (int64_t e = 0; e < m; e++) order[(size_t)e] = e;
-    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
-        if (h_dist[(size_t)a] != h_dist[(size_t)b]) return h_dist[(size_t)a] < h_dist[(size_t)b];
-        if (h_lo[(size_t)a] != h_lo[(size_t)b]) return h_lo[(size_t)a] < h_lo[(size_t)b];
-        return h_hi[(size_t)a] < h_hi[(size_t)b];
+    std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) {
+        if (h_dist[(size_t)x] != h_dist[(size_t)y]) return h_dist[(size_t)x] < h_dist[(size_t)y];
+        if (h_lo[(size_t)x] != h_lo[(size_t)y]) return h_lo[(size_t)x] < h_lo[(size_t)y];
+        return h_hi[(size_t)x] < h_hi[(size_t)y];
     });
     for (int64_t e = 0; e < m; e++) {
         lo[e] = h_lo[(size_t)order[(size_t)e]];
@@ -1323,6 +1206,8 @@ int64_t linkage_host(clip_amd_index * ix, int k, float link, const uint64_t * al
     return m;
 }
 
+namespace {
+
 // Extents of a labelling on the device: d_labels [n] int64 in, centre and, where asked for, radius, diameter, reach and far out; d_count
 // (may be NULL): the number of groups with a member.  Queues the launches and returns; ix->n > 0.
 bool extents_impl(clip_amd_index * ix, const int64_t * d_labels, const uint32_t * d_allow, int64_t * d_centre, float * d_radius, float * d_diameter,
@@ -1330,24 +1215,22 @@ bool extents_impl(clip_amd_index * ix, const int64_t * d_labels, const uint32_t 
     const uint32_t * mask = nullptr;
     if (!effective_mask(ix, d_allow, mask) || !ensure(ix, ix->ework, extents_work_bytes(ix->n))) return false;
     if (d_count) (void)hipMemsetAsync(d_count, 0, 8, stream_of(ix));
-    if (!launch_extents(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, d_labels, mask, ix->ework.p, ix->extents_route == 0, d_centre,
-                        d_radius, d_diameter, d_reach, d_far, d_count, stream_of(ix))) {
-        fprintf(stderr, "%s: launch failed\n", fn);
-        return false;
-    }
-    return true;
+    return launched(launch_extents(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, d_labels, mask, ix->ework.p, ix->extents_route == 0, d_centre,
+                        d_radius, d_diameter, d_reach, d_far, d_count, stream_of(ix)), fn);
 }
 
 bool check_extents_args(const clip_amd_index * ix, const void * labels, const void * centre, const char * fn) {
-    if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+    if (!check_index(ix, fn)) return false;
     if (!labels) { fprintf(stderr, "%s: labels is NULL\n", fn); return false; }
     if (!centre) { fprintf(stderr, "%s: centre is NULL\n", fn); return false; }
     return true;
 }
 
+}  // namespace
+
 // The host form: a member's label >= size is refused before anything is queued; then the labels go up, the outputs into their workspace
 // and out with the group count.  Returns that count or -1.
-int64_t extents_host(clip_amd_index * ix, const int64_t * labels, const uint64_t * allow, int64_t * centre, float * radius, float * diameter,
+int64_t idx::extents_host(clip_amd_index * ix, const int64_t * labels, const uint64_t * allow, int64_t * centre, float * radius, float * diameter,
                      float * reach, int64_t * far, const char * fn) {
     if (ix->n == 0) return 0;
     hipStream_t st = stream_of(ix);
@@ -1365,27 +1248,21 @@ int64_t extents_host(clip_amd_index * ix, const int64_t * labels, const uint64_t
         }
     }
     const uint32_t * d_allow = nullptr;
-    if (!upload_allow(ix, allow, d_allow) || !ensure(ix, ix->eouts, 8 + n * 36)) return -1;
-    unsigned long long * d_count = (unsigned long long *)ix->eouts.p;
-    int64_t * d_labels = (int64_t *)((char *)ix->eouts.p + 8);
-    int64_t * d_centre = d_labels + n;
-    int64_t * d_far = d_centre + n;
-    float * d_radius = (float *)(d_far + n);
-    float * d_diameter = d_radius + n;
-    float * d_reach = d_diameter + n;
-    (void)hipMemcpyAsync(d_labels, labels, n * 8, hipMemcpyHostToDevice, st);
-    if (!extents_impl(ix, d_labels, d_allow, d_centre, radius ? d_radius : nullptr, diameter ? d_diameter : nullptr, reach ? d_reach : nullptr,
-                      far ? d_far : nullptr, d_count, fn))
-        return -1;
     unsigned long long groups = 0;
-    (void)hipMemcpyAsync(&groups, d_count, 8, hipMemcpyDeviceToHost, st);
-    (void)hipMemcpyAsync(centre, d_centre, n * 8, hipMemcpyDeviceToHost, st);
-    if (radius) (void)hipMemcpyAsync(radius, d_radius, n * 4, hipMemcpyDeviceToHost, st);
-    if (diameter) (void)hipMemcpyAsync(diameter, d_diameter, n * 4, hipMemcpyDeviceToHost, st);
-    if (reach) (void)hipMemcpyAsync(reach, d_reach, n * 4, hipMemcpyDeviceToHost, st);
-    if (far) (void)hipMemcpyAsync(far, d_far, n * 8, hipMemcpyDeviceToHost, st);
-    return stream_done(ix, fn) ? (int64_t)groups : -1;
+    Arena a(ix);
+    const auto o_count = a.add(&groups, 1);
+    const auto i_labels = a.add<int64_t>(nullptr, n);         // an input: it goes up and does not come back
+    const auto o_centre = a.add(centre, n), o_far = a.add(far, n);
+    const auto o_radius = a.add(radius, n), o_diameter = a.add(diameter, n), o_reach = a.add(reach, n);
+    if (!upload_allow(ix, allow, d_allow) || !a.ready()) return -1;
+    (void)hipMemcpyAsync(a.dev(i_labels, true), labels, n * 8, hipMemcpyHostToDevice, st);
+    if (!extents_impl(ix, a.dev(i_labels, true), d_allow, a.dev(o_centre), a.dev(o_radius), a.dev(o_diameter), a.dev(o_reach), a.dev(o_far),
+                      a.dev(o_count), fn))
+        return -1;
+    return a.fetch(fn) ? (int64_t)groups : -1;
 }
+
+namespace {
 
 // reach of a key slot of k_spread.hip on the host (nearest_key.h's ordered_value)
 float spread_slot_reach(unsigned long long key) {
@@ -1398,7 +1275,7 @@ float spread_slot_reach(unsigned long long key) {
 
 bool check_spread_args(const clip_amd_index * ix, int64_t n_max, float stop, const int64_t * seeds, int64_t n_seeds, const void * centres,
                        const char * fn) {
-    if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+    if (!check_index(ix, fn)) return false;
     if (!centres) { fprintf(stderr, "%s: centres is NULL\n", fn); return false; }
     if (std::isnan(stop)) { fprintf(stderr, "%s: stop_radius is NaN\n", fn); return false; }
     if (n_seeds < 0 || (n_seeds > 0 && !seeds)) { fprintf(stderr, "%s: %lld seeds without ids\n", fn, (long long)n_seeds); return false; }
@@ -1415,10 +1292,12 @@ bool check_spread_args(const clip_amd_index * ix, int64_t n_max, float stop, con
     return true;
 }
 
+}  // namespace
+
 // Farthest-first selection on the device (arguments checked).  Queues the launches and returns: one sweep per 16 seeds, one per greedy
 // step, the finish.  A call with seeds first reads the effective mask back to test them (one wait, before anything is written); poll
 // (the host form): every 64 steps the next slot is read back and the steps that would find the traversal ended are not queued.
-bool spread_impl(clip_amd_index * ix, int64_t n_max, float stop, const int64_t * seeds, int64_t n_seeds, const uint32_t * d_allow,
+bool idx::spread_impl(clip_amd_index * ix, int64_t n_max, float stop, const int64_t * seeds, int64_t n_seeds, const uint32_t * d_allow,
                  int64_t * d_centres, float * d_reach, int64_t * d_owner, float * d_odist, float * d_cover, int64_t * d_count, bool poll,
                  const char * fn) {
     hipStream_t st = stream_of(ix);
@@ -1463,9 +1342,10 @@ bool spread_impl(clip_amd_index * ix, int64_t n_max, float stop, const int64_t *
         }
     }
     ok = ok && launch_spread_finish(slot, c + 1, n_first, stop, gap, opos, n, n_max, d_centres, d_reach, d_owner, d_odist, d_cover, d_count, st);
-    if (!ok) fprintf(stderr, "%s: launch failed\n", fn);
-    return ok;
+    return launched(ok, fn);
 }
+
+namespace {
 
 // The host form: the outputs in their workspace, then copied out with the count.  Returns that count or -1.
 int64_t spread_host(clip_amd_index * ix, int64_t n_max, float stop, const int64_t * seeds, int64_t n_seeds, const uint64_t * allow, int64_t * centres,
@@ -1473,27 +1353,21 @@ int64_t spread_host(clip_amd_index * ix, int64_t n_max, float stop, const int64_
     const size_t n = (size_t)ix->n, c = (size_t)std::min<int64_t>(n_max, ix->n);
     int64_t m = 0;
     if (n > 0) {
-        hipStream_t st = stream_of(ix);
         const uint32_t * d_allow = nullptr;
-        if (!upload_allow(ix, allow, d_allow) || !ensure(ix, ix->spouts, 16 + c * 12 + n * 12)) return -1;
-        int64_t * d_count = (int64_t *)ix->spouts.p;
-        float * d_cover = (float *)(d_count + 1);
-        int64_t * d_centres = d_count + 2;
-        int64_t * d_owner = d_centres + c;
-        float * d_reach = (float *)(d_owner + n);
-        float * d_odist = d_reach + c;
-        if (!spread_impl(ix, (int64_t)c, stop, seeds, n_seeds, d_allow, d_centres, reach ? d_reach : nullptr, owner ? d_owner : nullptr,
-                         odist ? d_odist : nullptr, cover ? d_cover : nullptr, d_count, true, fn))
-            return -1;
         std::vector<int64_t> h_centres(c);                     // the caller's arrays stay untouched when the stream fails
-        (void)hipMemcpyAsync(&m, d_count, 8, hipMemcpyDeviceToHost, st);
-        (void)hipMemcpyAsync(h_centres.data(), d_centres, c * 8, hipMemcpyDeviceToHost, st);
+        Arena a(ix);
+        const auto o_count = a.add(&m, 1), o_centres = a.add(h_centres.data(), c);      // the first copies: these two
+        const auto o_cover = a.add(cover, 1);
+        const auto o_owner = a.add(owner, n);
+        const auto o_reach = a.add(reach, c), o_odist = a.add(odist, n);
+        if (!upload_allow(ix, allow, d_allow) || !a.ready()) return -1;
+        if (!spread_impl(ix, (int64_t)c, stop, seeds, n_seeds, d_allow, a.dev(o_centres), a.dev(o_reach), a.dev(o_owner), a.dev(o_odist),
+                         a.dev(o_cover), a.dev(o_count), true, fn))
+            return -1;
+        a.queue(o_count.i, o_centres.i + 1);
         if (!stream_done(ix, fn)) return -1;
         std::copy(h_centres.begin(), h_centres.end(), centres);
-        if (reach) (void)hipMemcpyAsync(reach, d_reach, c * 4, hipMemcpyDeviceToHost, st);
-        if (owner) (void)hipMemcpyAsync(owner, d_owner, n * 8, hipMemcpyDeviceToHost, st);
-        if (odist) (void)hipMemcpyAsync(odist, d_odist, n * 4, hipMemcpyDeviceToHost, st);
-        if (cover) (void)hipMemcpyAsync(cover, d_cover, 4, hipMemcpyDeviceToHost, st);
+        a.queue(o_cover.i, a.n);
         if (!stream_done(ix, fn)) return -1;
     } else if (cover) {
         *cover = 0.f;
@@ -1505,20 +1379,24 @@ int64_t spread_host(clip_amd_index * ix, int64_t n_max, float stop, const int64_
     return m;
 }
 
-bool add_device_impl(clip_amd_index * ix, const float * d_vecs, int64_t n) {
+}  // namespace
+
+bool idx::add_device_impl(clip_amd_index * ix, const float * d_vecs, int64_t n) {
     if (!reserve_rows(ix, ix->n + n)) return false;
     const RowStore & s = ix->store;
     launch_search_prepare(d_vecs, n, n, ix->dim, ix->Dpad, ix->dtype, (char *)s.rows + (size_t)ix->n * row_stride(ix), s.rinv ? s.rinv + ix->n : nullptr,
                           stream_of(ix));
-    if (hipGetLastError() != hipSuccess) { fprintf(stderr, "clip_amd_index_add: launch failed\n"); return false; }
+    if (!launched(true, "clip_amd_index_add")) return false;
     launch_live_set(s.live, ix->n, ix->n + n, stream_of(ix));      // only for rows that count: live holds zeros at positions >= n
-    if (hipGetLastError() != hipSuccess) { fprintf(stderr, "clip_amd_index_add: launch failed\n"); return false; }   // not launched: no bit set
+    if (!launched(true, "clip_amd_index_add")) return false;   // not launched: no bit set
     ix->n += n;
     return true;
 }
 
+namespace {
+
 bool check_add_args(const clip_amd_index * ix, const float * v, int64_t n, const char * fn) {
-    if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+    if (!check_index(ix, fn)) return false;
     if (n < 0 || n > MAX_ROWS - ix->n) { fprintf(stderr, "%s: %lld rows would take the index past %lld rows\n", fn, (long long)n, (long long)MAX_ROWS); return false; }
     if (n > 0 && !v) { fprintf(stderr, "%s: NULL rows\n", fn); return false; }
     return true;
@@ -1530,109 +1408,6 @@ struct File {
     ~File() { if (f) fclose(f); }
 };
 
-// The frame of the benchmark hooks: -1 without a device, -3 for arguments outside the index's limits (args_ok: the hook's own), else an
-// index on the default stream holding the seeded gallery of n rows, filled in pieces of HOST_CHUNK_ROWS (a multiple of 64: a planted row
-// and its original share a piece), each piece from its own seed and, plant < 0, with launch_join_plant's near-duplicates or, plant > 0,
-// with launch_distinct_plant's groups of a row and `plant` noisy copies.  run(ix, src)
-// times the hook and returns its microseconds; src, a device scratch of max(piece, n_queries) rows of f32, is its to fill with queries.
-// -4 when anything failed.
-template <typename F>
-float bench_on_gallery(int dtype, int64_t n, int dim, int n_queries, int iters, bool args_ok, int plant, F && run) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return -1.f; }
-    if (!valid_dtype(dtype) || !valid_dim(dim) || n < 1 || n > MAX_ROWS || iters < 1 || !args_ok) return -3.f;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    clip_amd_index * ix = make_index(nullptr, dev, dim, dtype);
-    float * src = nullptr;
-    const int64_t piece = HOST_CHUNK_ROWS;
-    bool ok = hipMalloc(&src, (size_t)std::max<int64_t>(piece, n_queries) * dim * 4) == hipSuccess && reserve_rows(ix, n);
-    for (int64_t r0 = 0; ok && r0 < n; r0 += piece) {
-        const int64_t m = std::min(piece, n - r0);
-        launch_search_fill_random(src, m * dim, 0x5EEDull + (uint64_t)r0 * dim, nullptr);
-        if (plant < 0) launch_join_plant(src, m, dim, 0xD0Bull + (uint64_t)r0, nullptr);
-        if (plant > 0) launch_distinct_plant(src, m, dim, r0, plant, DISTINCT_PLANT_AMP, 0xD157ull + (uint64_t)r0, nullptr);
-        ok = add_device_impl(ix, src, m);
-    }
-    const float us = ok ? run(ix, src) : -4.f;
-    (void)hipGetLastError();
-    (void)hipDeviceSynchronize();
-    if (src) (void)hipFree(src);
-    free_index(ix);
-    return us;
-}
-
-// The timed part of the benchmark hooks: microseconds per call over iters calls (call() false: a failure), -4 when anything failed.
-// time_device: device time between two HIP events on the default stream around asynchronous calls (the hook made its warm call).
-template <typename F>
-float time_device(int iters, F && call) {
-    bool ok = true;
-    float us = -4.f;
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, nullptr);
-    for (int i = 0; ok && i < iters; i++) ok = call();
-    (void)hipEventRecord(e1, nullptr);
-    float ms = -1.f;
-    if (ok && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) us = ms * 1000.f / iters;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return us;
-}
-
-// time_wall: wall time of synchronous calls, after one warm call
-template <typename F>
-float time_wall(int iters, F && call) {
-    bool ok = call();
-    if (!ok) return -4.f;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int i = 0; ok && i < iters; i++) ok = call();
-    const auto t1 = std::chrono::steady_clock::now();
-    return ok ? (float)(std::chrono::duration<double, std::micro>(t1 - t0).count() / iters) : -4.f;
-}
-
-// the body of clip_amd_bench_search (fraction < 0: no allowed set), clip_amd_bench_search_subset and, group_size >= 1,
-// clip_amd_bench_search_grouped (row r in group r / group_size)
-float bench_search_impl(int dtype, int64_t n, int dim, int n_queries, int k, float fraction, bool contiguous, int iters, int group_size = 0) {
-    const bool args_ok = n_queries >= 1 && k >= 1 && k <= MAX_K && fraction <= 1.0f && group_size >= 0;
-    return bench_on_gallery(dtype, n, dim, n_queries, iters, args_ok, PLANT_NONE, [&](clip_amd_index * ix, float * src) {
-        float * d_dist = nullptr;
-        int64_t * d_ids = nullptr;
-        uint32_t * d_allow = nullptr;
-        int * d_groups = nullptr;
-        float us = -4.f;
-        const auto call = [&]() { return search_device_impl(ix, vectors(src), n_queries, k, d_allow, d_dist, d_ids, d_groups); };
-        bool ok = (fraction < 0.f || hipMalloc((void **)&d_allow, (size_t)search_allow_words(n) * 4) == hipSuccess) &&
-                  (group_size < 1 || hipMalloc((void **)&d_groups, (size_t)n * 4) == hipSuccess) && hipMalloc(&d_dist, (size_t)n_queries * k * 4) == hipSuccess && hipMalloc(&d_ids, (size_t)n_queries * k * 8) == hipSuccess;
-        if (ok) {
-            launch_search_fill_random(src, (int64_t)n_queries * dim, 0xC0FFEEull, nullptr);
-            if (d_allow) launch_search_fill_allow(d_allow, n, fraction, contiguous, 0xA110ull, nullptr);
-            if (d_groups) {
-                std::vector<int> g((size_t)n);
-                for (int64_t r = 0; r < n; r++) g[(size_t)r] = (int)(r / group_size);
-                ok = hipMemcpy(d_groups, g.data(), (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess;
-            }
-            ok = ok && call() && hipDeviceSynchronize() == hipSuccess;
-        }
-        if (ok) us = time_device(iters, call);
-        for (void * p : {(void *)d_dist, (void *)d_ids, (void *)d_allow, (void *)d_groups})
-            if (p) (void)hipFree(p);
-        return us;
-    });
-}
-
-// What a compound call's small host arrays say, after check_compound_args: tt = the smallest of {2, 4, 8} that holds the longest query
-struct CompoundCall {
-    const int64_t * term_ids = nullptr;
-    const int32_t * kinds = nullptr;
-    const float * bounds = nullptr;
-    const int64_t * lims = nullptr;
-    int tt = 2;
-    int k = 0;
-    bool exclude = false;
-};
-
 // Compound queries per block: one scan launch within the candidate budget, as a pass of search_device_impl (or the test hook's value)
 int compound_block_size(const clip_amd_index * ix, int k) {
     if (ix->compound_block > 0) return ix->compound_block;
@@ -1640,6 +1415,18 @@ int compound_block_size(const clip_amd_index * ix, int k) {
     const size_t n_chunks = (size_t)((ix->n + rpc - 1) / rpc);
     const int max_q = (int)std::min<size_t>(1024, CAND_BUDGET / (n_chunks * search_candidate_capacity(k) * sizeof(float) * 2));
     return std::max(16, max_q / 16 * 16);
+}
+
+// a compound entry point's arguments as one (tt: check_compound_args sets it)
+CompoundCall compound_call(const int64_t * term_ids, const int32_t * kinds, const float * bounds, const int64_t * lims, int k, int exclude) {
+    CompoundCall cc;
+    cc.term_ids = term_ids;
+    cc.kinds = kinds;
+    cc.bounds = bounds;
+    cc.lims = lims;
+    cc.k = k;
+    cc.exclude = exclude != 0;
+    return cc;
 }
 
 // what the compound entry points ask beyond check_search_args; sets tt
@@ -1676,12 +1463,14 @@ bool check_compound_args(const clip_amd_index * ix, const float * terms, const i
     return true;
 }
 
+}  // namespace
+
 // Compound queries c_lo ... c_lo + nq - 1 of a call on the device, results into d_dist / d_ids ([nq][k], device).  d_terms: the f32 term
 // vectors on the device from term `origin` of the call on (NULL: every term is a stored row).  Query blocks of compound_block_size, one
 // after another: the block's vector terms are normalised / quantised into the staging array, the placement kernel lays the term-major
 // workspace out of them and of the gathered id terms, then the compound scan, the merge tree and the finish (a query whose id term is
 // out of range or removed: all empty).  A query's workspace rows, candidates and result are its own, so the cut into blocks does not show.
-bool compound_device_impl(clip_amd_index * ix, const float * d_terms, int64_t origin, const CompoundCall & cc, int c_lo, int nq,
+bool idx::compound_device_impl(clip_amd_index * ix, const float * d_terms, int64_t origin, const CompoundCall & cc, int c_lo, int nq,
                           const uint32_t * d_allow, float * d_dist, int64_t * d_ids) {
     hipStream_t st = stream_of(ix);
     const uint32_t * mask = nullptr;
@@ -1757,15 +1546,10 @@ bool compound_device_impl(clip_amd_index * ix, const float * d_terms, int64_t or
             return false;
         }
         if (!merge_and_finish(ix, n_chunks, m, cc.k, flag, d_dist + (size_t)c0 * cc.k, d_ids + (size_t)c0 * cc.k)) return false;
-        if (hipGetLastError() != hipSuccess) {
-            fprintf(stderr, "clip_amd_index_search_compound: launch failed\n");
-            return false;
-        }
+        if (!launched(true, "clip_amd_index_search_compound")) return false;
     }
     return true;
 }
-
-}  // namespace
 
 extern "C" {
 
@@ -1838,9 +1622,9 @@ static bool search_call(struct clip_amd_index * ix, const float * queries, int n
         const float * d_q = nullptr;
         const uint32_t * d_allow = nullptr;
         const size_t count = (size_t)n_queries * k;
-        if (!stage_inputs(ix, queries, n_queries, allow, d_q, d_allow) || !ensure(ix, ix->outs, count * 12)) return false;
-        int64_t * d_ids = (int64_t *)ix->outs.p;
-        float * d_dist = (float *)((char *)ix->outs.p + count * 8);
+        float * d_dist = nullptr;
+        int64_t * d_ids = nullptr;
+        if (!stage_inputs(ix, queries, n_queries, allow, d_q, d_allow) || !block_outs(ix, count, d_dist, d_ids)) return false;
         return search_device_impl(ix, vectors(d_q), n_queries, k, d_allow, d_dist, d_ids) && copy_results(ix, d_dist, d_ids, count, distances, ids, fn);
     });
 }
@@ -1876,10 +1660,10 @@ bool clip_amd_index_search_grouped(struct clip_amd_index * ix, const float * que
         const uint32_t * d_allow = nullptr;
         const int * d_groups = nullptr;
         const size_t count = (size_t)n_queries * k;
-        if (!stage_inputs(ix, queries, n_queries, allow, d_q, d_allow) || !ensure(ix, ix->outs, count * 12) || !upload_groups(ix, groups, fn, d_groups))
+        float * d_dist = nullptr;
+        int64_t * d_ids = nullptr;
+        if (!stage_inputs(ix, queries, n_queries, allow, d_q, d_allow) || !block_outs(ix, count, d_dist, d_ids) || !upload_groups(ix, groups, fn, d_groups))
             return false;
-        int64_t * d_ids = (int64_t *)ix->outs.p;
-        float * d_dist = (float *)((char *)ix->outs.p + count * 8);
         return search_device_impl(ix, vectors(d_q), n_queries, k, d_allow, d_dist, d_ids, d_groups) &&
                copy_results(ix, d_dist, d_ids, count, distances, ids, fn);
     });
@@ -1914,7 +1698,7 @@ bool clip_amd_index_search_ids_sets(struct clip_amd_index * ix, const int64_t * 
                                     int exclude_own, const int32_t * groups, const uint64_t * allow, float * distances, int64_t * out_ids,
                                     int32_t * qrows) {
     return guarded(__func__, false, [&](const char * fn) {
-        if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+        if (!check_index(ix, fn)) return false;
         if (n_ids < 0 || n_ids > MAX_ROWS) { fprintf(stderr, "%s: n_ids %lld outside 0 ... %lld\n", fn, (long long)n_ids, (long long)MAX_ROWS); return false; }
         if (!check_search_args(ix, ids, (int)n_ids, k, distances, out_ids, fn)) return false;
         if (!check_set_args(n_ids, set_lims, n_sets, qrows, fn)) return false;
@@ -1927,46 +1711,6 @@ bool clip_amd_index_search_ids_sets(struct clip_amd_index * ix, const int64_t * 
         (void)hipSetDevice(ix->device);
         if (!check_stored_ids(ix, ids, n_ids, fn)) return false;
         return sets_host_impl(ix, nullptr, ids, n_ids, set_lims, n_sets, k, exclude_own != 0, groups, allow, distances, out_ids, qrows, fn);
-    });
-}
-
-int64_t clip_amd_test_index_sets_block(struct clip_amd_index * ix, int64_t rows) {
-    if (!ix || rows < 0 || rows > GRAPH_BLOCK_MAX) return -1;
-    ix->sets_block = rows;
-    return rows;
-}
-
-float clip_amd_bench_search_sets(int dtype, int64_t n, int dim, int n_sets, int set_size, int k, int group_size, int iters) {
-    return guarded(__func__, -4.f, [&](const char *) {
-        const bool args_ok = n_sets >= 1 && set_size >= 1 && (int64_t)n_sets * set_size <= (1 << 20) && k >= 1 && k <= MAX_K && group_size >= 0;
-        const int nq = args_ok ? n_sets * set_size : 0;
-        return bench_on_gallery(dtype, n, dim, nq, iters, args_ok, PLANT_NONE, [&](clip_amd_index * ix, float * src) {
-            const size_t count = (size_t)n_sets * k;
-            float * d_dist = nullptr;
-            int64_t * d_ids = nullptr;
-            int * d_qrows = nullptr, * d_groups = nullptr;
-            std::vector<int64_t> lims((size_t)n_sets + 1);
-            for (int s = 0; s <= n_sets; s++) lims[(size_t)s] = (int64_t)s * set_size;
-            float us = -4.f;
-            bool ok = (group_size < 1 || hipMalloc((void **)&d_groups, (size_t)n * 4) == hipSuccess) && hipMalloc(&d_dist, count * 4) == hipSuccess &&
-                      hipMalloc(&d_ids, count * 8) == hipSuccess && hipMalloc((void **)&d_qrows, count * 4) == hipSuccess;
-            const auto call = [&]() {
-                return sets_device_impl(ix, vectors(src), nq, lims.data(), n_sets, k, d_groups, false, nullptr, d_dist, d_ids, d_qrows, 0, false);
-            };
-            if (ok) {
-                launch_search_fill_random(src, (int64_t)nq * dim, 0xC0FFEEull, nullptr);
-                if (d_groups) {
-                    std::vector<int> g((size_t)n);
-                    for (int64_t r = 0; r < n; r++) g[(size_t)r] = (int)(r / group_size);
-                    ok = hipMemcpy(d_groups, g.data(), (size_t)n * 4, hipMemcpyHostToDevice) == hipSuccess;
-                }
-                ok = ok && call() && hipDeviceSynchronize() == hipSuccess;
-            }
-            if (ok) us = time_device(iters, call);
-            for (void * p : {(void *)d_dist, (void *)d_ids, (void *)d_qrows, (void *)d_groups})
-                if (p) (void)hipFree(p);
-            return us;
-        });
     });
 }
 
@@ -2001,50 +1745,13 @@ bool clip_amd_index_search_ids_distinct(struct clip_amd_index * ix, const int64_
     });
 }
 
-int clip_amd_test_index_distinct_block(struct clip_amd_index * ix, int queries) {
-    if (!ix || queries < 0 || queries > DISTINCT_BLOCK_MAX) return -1;
-    ix->distinct_block = queries;
-    return queries;
-}
-
-float clip_amd_bench_search_distinct(int dtype, int64_t n, int dim, int n_queries, int k, int pool, float radius, int copies, int iters) {
-    return guarded(__func__, -4.f, [&](const char *) {
-        if (pool == 0 && k >= 1 && k <= MAX_K) pool = auto_pool(k);
-        const bool args_ok = n_queries >= 1 && k >= 1 && k <= pool && pool <= MAX_K && !std::isnan(radius) && copies >= 1 && copies < HOST_CHUNK_ROWS;
-        return bench_on_gallery(dtype, n, dim, n_queries, iters, args_ok, copies, [&](clip_amd_index * ix, float * src) {
-            const size_t count = (size_t)n_queries * k;
-            float * d_dist = nullptr;
-            int64_t * d_ids = nullptr;
-            int * d_counts = nullptr;
-            float us = -4.f;
-            const auto call = [&]() { return distinct_device_impl(ix, vectors(src), n_queries, k, radius, pool, nullptr, d_dist, d_ids, d_counts); };
-            bool ok = hipMalloc(&d_dist, count * 4) == hipSuccess && hipMalloc(&d_ids, count * 8) == hipSuccess &&
-                      hipMalloc((void **)&d_counts, count * 4) == hipSuccess;
-            if (ok) {
-                launch_search_fill_random(src, (int64_t)n_queries * dim, 0xC0FFEEull, nullptr);
-                ok = call() && hipDeviceSynchronize() == hipSuccess;
-            }
-            if (ok) us = time_device(iters, call);
-            for (void * p : {(void *)d_dist, (void *)d_ids, (void *)d_counts})
-                if (p) (void)hipFree(p);
-            return us;
-        });
-    });
-}
-
 bool clip_amd_index_search_compound_device(struct clip_amd_index * ix, const float * d_terms, const int64_t * term_ids, const int32_t * kinds,
                                            const float * bounds, const int64_t * term_lims, int n_queries, int k, int exclude_terms,
                                            const uint64_t * d_allow, float * d_distances, int64_t * d_ids) {
     return guarded(__func__, false, [&](const char * fn) {
         if (!check_search_args(ix, kinds, n_queries, k, d_distances, d_ids, fn)) return false;
-        CompoundCall cc;
+        CompoundCall cc = compound_call(term_ids, kinds, bounds, term_lims, k, exclude_terms);
         if (!check_compound_args(ix, d_terms, term_ids, kinds, bounds, term_lims, n_queries, cc.tt, fn)) return false;
-        cc.term_ids = term_ids;
-        cc.kinds = kinds;
-        cc.bounds = bounds;
-        cc.lims = term_lims;
-        cc.k = k;
-        cc.exclude = exclude_terms != 0;
         (void)hipSetDevice(ix->device);
         return compound_device_impl(ix, d_terms, 0, cc, 0, n_queries, (const uint32_t *)d_allow, d_distances, d_ids);
     });
@@ -2055,14 +1762,8 @@ bool clip_amd_index_search_compound(struct clip_amd_index * ix, const float * te
                                     const uint64_t * allow, float * distances, int64_t * ids) {
     return guarded(__func__, false, [&](const char * fn) {
         if (!check_search_args(ix, kinds, n_queries, k, distances, ids, fn)) return false;
-        CompoundCall cc;
+        CompoundCall cc = compound_call(term_ids, kinds, bounds, term_lims, k, exclude_terms);
         if (!check_compound_args(ix, terms, term_ids, kinds, bounds, term_lims, n_queries, cc.tt, fn)) return false;
-        cc.term_ids = term_ids;
-        cc.kinds = kinds;
-        cc.bounds = bounds;
-        cc.lims = term_lims;
-        cc.k = k;
-        cc.exclude = exclude_terms != 0;
         (void)hipSetDevice(ix->device);
         hipStream_t st = stream_of(ix);
         const int64_t total = term_lims[n_queries];
@@ -2075,11 +1776,10 @@ bool clip_amd_index_search_compound(struct clip_amd_index * ix, const float * te
         // query blocks one after another: a block's terms are staged, searched and its results copied out, so nothing on the device grows
         // with n_queries
         const int block = std::min(compound_block_size(ix, k), n_queries);
-        const size_t slots = (size_t)block * k;
-        if (!ensure(ix, ix->outs, slots * 12)) return false;
+        float * d_dist = nullptr;
+        int64_t * d_out = nullptr;
+        if (!block_outs(ix, (size_t)block * k, d_dist, d_out)) return false;
         if (terms && !ensure(ix, ix->stage, (size_t)std::min<int64_t>(total, (int64_t)block * COMPOUND_MAX_TERMS) * ix->dim * 4)) return false;
-        int64_t * d_out = (int64_t *)ix->outs.p;
-        float * d_dist = (float *)((char *)ix->outs.p + slots * 8);
         for (int c0 = 0; c0 < n_queries; c0 += block) {
             const int m = std::min(block, n_queries - c0);
             const int64_t T0 = term_lims[c0], cnt = term_lims[c0 + m] - T0;
@@ -2091,48 +1791,11 @@ bool clip_amd_index_search_compound(struct clip_amd_index * ix, const float * te
     });
 }
 
-int clip_amd_test_index_compound_block(struct clip_amd_index * ix, int queries) {
-    if (!ix || queries < 0 || queries > 1024) return -1;
-    ix->compound_block = queries;
-    return queries;
-}
-
-float clip_amd_bench_search_compound(int dtype, int64_t n, int dim, int n_queries, int n_terms, int k, int iters) {
-    return guarded(__func__, -4.f, [&](const char *) {
-        const bool args_ok = n_queries >= 1 && n_queries <= (1 << 17) && n_terms >= 1 && n_terms <= COMPOUND_MAX_TERMS && k >= 1 && k <= MAX_K;
-        const int total = args_ok ? n_queries * n_terms : 0;
-        return bench_on_gallery(dtype, n, dim, total, iters, args_ok, PLANT_NONE, [&](clip_amd_index * ix, float * src) {
-            const size_t count = (size_t)n_queries * k;
-            float * d_dist = nullptr;
-            int64_t * d_ids = nullptr;
-            std::vector<int64_t> lims((size_t)n_queries + 1);
-            for (int c = 0; c <= n_queries; c++) lims[(size_t)c] = (int64_t)c * n_terms;
-            const std::vector<int32_t> kinds((size_t)total, COMPOUND_ALL);
-            CompoundCall cc;
-            cc.kinds = kinds.data();
-            cc.lims = lims.data();
-            cc.tt = n_terms <= 2 ? 2 : (n_terms <= 4 ? 4 : 8);
-            cc.k = k;
-            float us = -4.f;
-            const auto call = [&]() { return compound_device_impl(ix, src, 0, cc, 0, n_queries, nullptr, d_dist, d_ids); };
-            bool ok = hipMalloc(&d_dist, count * 4) == hipSuccess && hipMalloc(&d_ids, count * 8) == hipSuccess;
-            if (ok) {
-                launch_search_fill_random(src, (int64_t)total * dim, 0xC0FFEEull, nullptr);
-                ok = call() && hipDeviceSynchronize() == hipSuccess;
-            }
-            if (ok) us = time_device(iters, call);
-            for (void * p : {(void *)d_dist, (void *)d_ids})
-                if (p) (void)hipFree(p);
-            return us;
-        });
-    });
-}
-
 int64_t clip_amd_index_live(const struct clip_amd_index * ix) { return ix ? ix->n - ix->removed : 0; }
 
 int64_t clip_amd_index_remove(struct clip_amd_index * ix, const int64_t * ids, int64_t n) {
     return guarded(__func__, (int64_t)-1, [&](const char * fn) -> int64_t {
-        if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return -1; }
+        if (!check_index(ix, fn)) return -1;
         if (n < 0) { fprintf(stderr, "%s: n %lld < 0\n", fn, (long long)n); return -1; }
         if (n > 0 && !ids) { fprintf(stderr, "%s: NULL ids\n", fn); return -1; }
         for (int64_t i = 0; i < n; i++)
@@ -2159,7 +1822,7 @@ int64_t clip_amd_index_remove(struct clip_amd_index * ix, const int64_t * ids, i
 
 bool clip_amd_index_live_mask(struct clip_amd_index * ix, uint64_t * bits) {
     return guarded(__func__, false, [&](const char * fn) {
-        if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+        if (!check_index(ix, fn)) return false;
         if (ix->n == 0) return true;
         if (!bits) { fprintf(stderr, "%s: bits is NULL\n", fn); return false; }
         (void)hipSetDevice(ix->device);
@@ -2169,7 +1832,7 @@ bool clip_amd_index_live_mask(struct clip_amd_index * ix, uint64_t * bits) {
 
 int64_t clip_amd_index_compact(struct clip_amd_index * ix, int64_t * new_ids) {
     return guarded(__func__, (int64_t)-1, [&](const char * fn) -> int64_t {
-        if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return -1; }
+        if (!check_index(ix, fn)) return -1;
         if (ix->removed == 0) {                                   // nothing to drop: every id stays
             for (int64_t i = 0; new_ids && i < ix->n; i++) new_ids[i] = i;
             return ix->n;
@@ -2403,7 +2066,7 @@ bool clip_amd_index_linkage_device(struct clip_amd_index * ix, float link, const
 int64_t clip_amd_index_linkage_core(struct clip_amd_index * ix, int k, float link, const uint64_t * allow, int64_t * lo, int64_t * hi,
                                     float * weights, float * core) {
     return guarded(__func__, (int64_t)-1, [&](const char * fn) -> int64_t {
-        if (!check_linkage_args(ix, link, lo, hi, weights, fn) || !check_core_k(k, fn)) return -1;
+        if (!check_linkage_args(ix, link, lo, hi, weights, fn) || !check_k(k, 0, fn)) return -1;
         (void)hipSetDevice(ix->device);
         return linkage_host(ix, k, link, allow, lo, hi, weights, core, fn);
     });
@@ -2412,7 +2075,7 @@ int64_t clip_amd_index_linkage_core(struct clip_amd_index * ix, int k, float lin
 bool clip_amd_index_linkage_core_device(struct clip_amd_index * ix, int k, float link, const uint64_t * d_allow, int64_t * d_lo, int64_t * d_hi,
                                         float * d_weights, float * d_core, int64_t * d_count) {
     return guarded(__func__, false, [&](const char * fn) {
-        if (!check_linkage_args(ix, link, d_lo, d_hi, d_weights, fn) || !check_core_k(k, fn)) return false;
+        if (!check_linkage_args(ix, link, d_lo, d_hi, d_weights, fn) || !check_k(k, 0, fn)) return false;
         if (!d_count) { fprintf(stderr, "%s: d_count is NULL\n", fn); return false; }
         (void)hipSetDevice(ix->device);
         return linkage_impl(ix, k, link, (const uint32_t *)d_allow, d_lo, d_hi, d_weights, d_core, d_count, fn);
@@ -2438,18 +2101,6 @@ bool clip_amd_index_extents_device(struct clip_amd_index * ix, const int64_t * d
             return true;
         }
         return extents_impl(ix, d_labels, (const uint32_t *)d_allow, d_centre, d_radius, d_diameter, d_reach, d_far, (unsigned long long *)d_count, fn);
-    });
-}
-
-int64_t clip_amd_test_index_extents_route(struct clip_amd_index * ix, int route) {
-    return guarded(__func__, (int64_t)-1, [&](const char * fn) -> int64_t {
-        if (!ix || route < 0 || route > 1) return -1;
-        ix->extents_route = route;
-        if (ix->n == 0 || !ix->ework.p) return 0;             // no call yet
-        (void)hipSetDevice(ix->device);
-        unsigned long long computed = 0;
-        if (!stream_done(ix, fn, hipMemcpyAsync(&computed, extents_tiles_computed(ix->ework.p), 8, hipMemcpyDeviceToHost, stream_of(ix)))) return -1;
-        return (int64_t)computed;
     });
 }
 
@@ -2489,24 +2140,21 @@ bool clip_amd_index_search_ids(struct clip_amd_index * ix, const int64_t * ids, 
         if (!check_search_args(ix, ids, n_ids, k, distances, out_ids, fn)) return false;
         if (n_ids == 0) return true;
         (void)hipSetDevice(ix->device);
-        hipStream_t st = stream_of(ix);
         if (!check_stored_ids(ix, ids, n_ids, fn)) return false;
         const size_t count = (size_t)n_ids * k;
         const uint32_t * d_allow = nullptr;
-        if (!ensure(ix, ix->idbuf, (size_t)n_ids * 8) || !ensure(ix, ix->outs, count * 12)) return false;
-        (void)hipMemcpyAsync(ix->idbuf.p, ids, (size_t)n_ids * 8, hipMemcpyHostToDevice, st);
-        if (!upload_allow(ix, allow, d_allow)) return false;
-        int64_t * d_out = (int64_t *)ix->outs.p;
-        float * d_dist = (float *)((char *)ix->outs.p + count * 8);
-        return search_device_impl(ix, stored_rows((const int64_t *)ix->idbuf.p, 0, exclude_self != 0), n_ids, k, d_allow, d_dist, d_out) &&
+        float * d_dist = nullptr;
+        int64_t * d_out = nullptr;
+        if (!reserve_stage(ix, nullptr, ids, n_ids) || !block_outs(ix, count, d_dist, d_out) || !upload_allow(ix, allow, d_allow)) return false;
+        return search_device_impl(ix, stage_block(ix, nullptr, ids, 0, n_ids, exclude_self != 0), n_ids, k, d_allow, d_dist, d_out) &&
                copy_results(ix, d_dist, d_out, count, distances, out_ids, fn);
     });
 }
 
 bool clip_amd_index_knn_graph(struct clip_amd_index * ix, int k, float * distances, int64_t * ids) {
     return guarded(__func__, false, [&](const char * fn) {
-        if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
-        if (k < 1 || k > MAX_K) { fprintf(stderr, "%s: k = %d outside 1 ... %d\n", fn, k, MAX_K); return false; }
+        if (!check_index(ix, fn)) return false;
+        if (!check_k(k, 1, fn)) return false;
         if (ix->n > 0 && (!distances || !ids)) { fprintf(stderr, "%s: NULL result pointer\n", fn); return false; }
         (void)hipSetDevice(ix->device);
         return knn_graph_impl(ix, k, distances, ids, fn);
@@ -2548,7 +2196,7 @@ bool clip_amd_index_vote_ids(struct clip_amd_index * ix, const int64_t * ids, in
                              const uint64_t * allow, int32_t * classes, int32_t * votes, float * distances, int64_t * out_ids) {
     return guarded(__func__, false, [&](const char * fn) {
         const VoteOut out = vote_out(classes, votes, distances, out_ids);
-        if (!ix) { fprintf(stderr, "%s: index is NULL\n", fn); return false; }
+        if (!check_index(ix, fn)) return false;
         if (n_ids < 0 || n_ids > MAX_ROWS) { fprintf(stderr, "%s: n_ids %lld outside 0 ... %lld\n", fn, (long long)n_ids, (long long)MAX_ROWS); return false; }
         if (!check_search_args(ix, ids, (int)n_ids, k, distances, out_ids, fn)) return false;
         if (!check_vote_args(ix, k, m, n_ids > 0, labels, true, out, fn)) return false;
@@ -2577,38 +2225,11 @@ bool clip_amd_index_vote_graph_device(struct clip_amd_index * ix, int k, int m, 
     });
 }
 
-int64_t clip_amd_test_index_vote_block(struct clip_amd_index * ix, int64_t rows) {
-    if (!ix || rows < 0 || rows > GRAPH_BLOCK_MAX) return -1;
-    ix->vote_block = rows;
-    return rows;
-}
-
-float clip_amd_bench_vote_graph(int dtype, int64_t n, int dim, int k, int m, int classes, int route, int iters) {
-    return guarded(__func__, -4.f, [&](const char * fn) {
-        const bool args_ok = k >= 1 && k <= MAX_K && m >= 1 && m <= k && classes >= 1 && route >= 0 && route <= 2;
-        return bench_on_gallery(dtype, n, dim, 0, iters, args_ok, PLANT_NONE, [&](clip_amd_index * ix, float *) {
-            std::vector<int32_t> labels((size_t)n), cls((size_t)n * m), votes((size_t)n * m);
-            std::vector<float> dist((size_t)n * m);
-            std::vector<int64_t> ids((size_t)n * m);
-            for (int64_t r = 0; r < n; r++) {                  // splitmix64 of the row number under a fixed seed
-                uint64_t z = 0x707E5ull + (uint64_t)r * 0x9E3779B97F4A7C15ull;
-                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-                z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-                labels[(size_t)r] = (int32_t)((z ^ (z >> 31)) % (uint64_t)classes);
-            }
-            ix->knn_route = route;
-            if (hipDeviceSynchronize() != hipSuccess) return -4.f;
-            const VoteOut out = vote_out(cls.data(), votes.data(), dist.data(), ids.data());
-            return time_wall(iters, [&]() { return vote_host(ix, nullptr, nullptr, n, k, m, true, labels.data(), nullptr, out, fn); });
-        });
-    });
-}
-
 bool clip_amd_index_search_index(struct clip_amd_index * ix, struct clip_amd_index * src, const int64_t * ids, int64_t n_ids, int k,
                                  const uint64_t * allow, float * distances, int64_t * out_ids) {
     return guarded(__func__, false, [&](const char * fn) {
         if (!check_pair(ix, src, fn)) return false;
-        if (k < 1 || k > MAX_K) { fprintf(stderr, "%s: k = %d outside 1 ... %d\n", fn, k, MAX_K); return false; }
+        if (!check_k(k, 1, fn)) return false;
         if (ids && n_ids < 0) { fprintf(stderr, "%s: n_ids %lld < 0\n", fn, (long long)n_ids); return false; }
         const int64_t nq = ids ? n_ids : src->n;
         if (nq > 0 && (!distances || !out_ids)) { fprintf(stderr, "%s: NULL result pointer\n", fn); return false; }
@@ -2643,236 +2264,6 @@ int64_t clip_amd_index_append(struct clip_amd_index * ix, struct clip_amd_index 
         }
         for (int64_t i = 0; new_ids && i < m; i++) new_ids[i] = n + i;
         return m;
-    });
-}
-
-int clip_amd_test_index_cross_route(struct clip_amd_index * ix, int route) {
-    if (!ix || route < 0 || route > 2) return -1;
-    ix->cross_route = route;
-    return route;
-}
-
-float clip_amd_bench_cross(int dtype, int64_t n_rows, int64_t n_queries, int dim, int k, int route, int iters) {
-    return guarded(__func__, -4.f, [&](const char * fn) {
-        const bool args_ok = k >= 1 && k <= MAX_K && route >= 0 && route <= 2 && n_queries >= 1 && n_queries <= MAX_ROWS;
-        return bench_on_gallery(dtype, n_rows, dim, 0, iters, args_ok, PLANT_NONE, [&](clip_amd_index * ix, float * scratch) {
-            // the second index: n_queries rows from seeds of their own, filled in the pieces the gallery was filled in
-            clip_amd_index * src = make_index(nullptr, ix->device, dim, dtype);
-            bool ok = reserve_rows(src, n_queries);
-            for (int64_t r0 = 0; ok && r0 < n_queries; r0 += HOST_CHUNK_ROWS) {
-                const int64_t m = std::min(HOST_CHUNK_ROWS, n_queries - r0);
-                launch_search_fill_random(scratch, m * dim, 0xC0FFEEull + (uint64_t)r0 * dim, nullptr);
-                ok = add_device_impl(src, scratch, m);
-            }
-            float us = -4.f;
-            if (ok) {
-                std::vector<float> dist((size_t)n_queries * k);
-                std::vector<int64_t> out((size_t)n_queries * k);
-                ix->cross_route = route;
-                if (hipDeviceSynchronize() == hipSuccess)
-                    us = time_wall(iters, [&]() { return search_index_impl(ix, src, nullptr, n_queries, k, nullptr, dist.data(), out.data(), fn); });
-            }
-            (void)hipDeviceSynchronize();
-            free_index(src);
-            return us;
-        });
-    });
-}
-
-int clip_amd_test_index_knn_route(struct clip_amd_index * ix, int route) {
-    if (!ix || route < 0 || route > 2) return -1;
-    ix->knn_route = route;
-    return route;
-}
-
-float clip_amd_bench_knn(int dtype, int64_t n, int dim, int k, int route, int iters) {
-    return guarded(__func__, -4.f, [&](const char * fn) {
-        const bool args_ok = k >= 1 && k <= MAX_K && route >= 0 && route <= 2;
-        return bench_on_gallery(dtype, n, dim, 0, iters, args_ok, PLANT_NONE, [&](clip_amd_index * ix, float *) {
-            std::vector<float> dist((size_t)n * k);
-            std::vector<int64_t> ids((size_t)n * k);
-            ix->knn_route = route;
-            if (hipDeviceSynchronize() != hipSuccess) return -4.f;
-            return time_wall(iters, [&]() { return knn_graph_impl(ix, k, dist.data(), ids.data(), fn); });
-        });
-    });
-}
-
-float clip_amd_bench_search(int dtype, int64_t n, int dim, int n_queries, int k, int iters) {
-    return guarded(__func__, -4.f, [&](const char *) { return bench_search_impl(dtype, n, dim, n_queries, k, -1.f, false, iters); });
-}
-
-float clip_amd_bench_search_grouped(int dtype, int64_t n, int dim, int n_queries, int k, int group_size, int iters) {
-    return guarded(__func__, -4.f, [&](const char *) {
-        if (group_size < 1) return -3.f;
-        return bench_search_impl(dtype, n, dim, n_queries, k, -1.0f, false, iters, group_size);
-    });
-}
-
-float clip_amd_bench_search_subset(int dtype, int64_t n, int dim, int n_queries, int k, float allowed_fraction, int contiguous, int iters) {
-    return guarded(__func__, -4.f, [&](const char *) {
-        if (!(allowed_fraction >= 0.f)) return -3.f;
-        return bench_search_impl(dtype, n, dim, n_queries, k, allowed_fraction, contiguous != 0, iters);
-    });
-}
-
-float clip_amd_bench_range(int dtype, int64_t n, int dim, int n_queries, float radius, int iters) {
-    return guarded(__func__, -4.f, [&](const char * fn) {
-        const bool pairs = n_queries == 0;
-        return bench_on_gallery(dtype, n, dim, n_queries, iters, n_queries >= 0 && !std::isnan(radius), PLANT_JOIN, [&](clip_amd_index * ix, float * src) {
-            float us = -4.f;
-            const float * d_q = pairs ? nullptr : src;
-            std::vector<int64_t> lims((size_t)(pairs ? n : n_queries) + 1);
-            // queries: the gallery's first rows before planting (each finds itself, some a planted copy as well)
-            launch_search_fill_random(src, (int64_t)n_queries * dim, 0x5EEDull, nullptr);
-            int64_t tot = hipDeviceSynchronize() == hipSuccess ? join_impl(ix, d_q, n_queries, pairs, radius, nullptr, lims.data(), nullptr, nullptr, 0, fn) : -1;
-            std::vector<float> dist((size_t)std::max<int64_t>(tot, 1));
-            std::vector<int64_t> ids(dist.size());
-            if (tot >= 0) {
-                us = time_wall(iters, [&]() {
-                    return join_impl(ix, d_q, n_queries, pairs, radius, nullptr, lims.data(), dist.data(), ids.data(), (int64_t)dist.size(), fn) >= 0;
-                });
-            }
-            return us;
-        });
-    });
-}
-
-float clip_amd_bench_components(int dtype, int64_t n, int dim, float radius, int iters) {
-    return guarded(__func__, -4.f, [&](const char * fn) {
-        return bench_on_gallery(dtype, n, dim, 0, iters, !std::isnan(radius), PLANT_JOIN, [&](clip_amd_index * ix, float *) {
-            std::vector<int64_t> labels((size_t)n), nid((size_t)n);
-            std::vector<float> ndist((size_t)n);
-            if (hipDeviceSynchronize() != hipSuccess || components_host(ix, radius, nullptr, labels.data(), ndist.data(), nid.data(), fn) < 0) return -4.f;
-            return time_wall(iters, [&]() { return components_host(ix, radius, nullptr, labels.data(), ndist.data(), nid.data(), fn) >= 0; });
-        });
-    });
-}
-
-float clip_amd_bench_modes(int dtype, int64_t n, int dim, float radius, float link, int copies, int iters) {
-    return guarded(__func__, -4.f, [&](const char * fn) {
-        const bool args_ok = !std::isnan(radius) && !std::isnan(link) && copies >= 0;
-        return bench_on_gallery(dtype, n, dim, 0, iters, args_ok, copies > 0 ? copies : PLANT_JOIN, [&](clip_amd_index * ix, float *) {
-            std::vector<int64_t> labels((size_t)n), parent((size_t)n);
-            std::vector<float> pdist((size_t)n);
-            std::vector<int> density((size_t)n);
-            auto call = [&]() { return modes_host(ix, radius, link, nullptr, labels.data(), parent.data(), pdist.data(), density.data(), fn) >= 0; };
-            if (hipDeviceSynchronize() != hipSuccess || !call()) return -4.f;
-            return time_wall(iters, call);
-        });
-    });
-}
-
-float clip_amd_bench_extents(int dtype, int64_t n, int dim, int group_size, int sorted, int iters) {
-    return guarded(__func__, -4.f, [&](const char * fn) {
-        // bursts of group_size rows (launch_distinct_plant's row and group_size - 1 noisy copies), labelled by burst: row r carries the
-        // label r / group_size.  Not sorted: row r carries the label of row pi(r), pi a fixed permutation of the rows, so the groups keep
-        // their sizes but lie scattered over the index and every tile of 128 rows holds labels from the whole range (the time does not
-        // depend on which rows a group holds, only on where they lie)
-        return bench_on_gallery(dtype, n, dim, 0, iters, group_size >= 1, group_size > 1 ? group_size - 1 : PLANT_NONE, [&](clip_amd_index * ix, float *) {
-            std::vector<int64_t> labels((size_t)n), centre((size_t)n), far((size_t)n);
-            std::vector<float> radius((size_t)n), diameter((size_t)n), reach((size_t)n);
-            for (int64_t r = 0; r < n; r++) labels[(size_t)r] = r / group_size;
-            if (!sorted) {                                     // pi: an odd factor modulo a power of two >= n, walked until it lands below n
-                uint64_t m = 1;
-                while ((int64_t)m < n) m *= 2;
-                for (int64_t r = 0; r < n; r++) {
-                    uint64_t v = (uint64_t)r;
-                    do v = (v * 0x9E3779B1ull + 12345ull) & (m - 1); while ((int64_t)v >= n);
-                    labels[(size_t)r] = (int64_t)v / group_size;
-                }
-            }
-            auto call = [&]() {
-                return extents_host(ix, labels.data(), nullptr, centre.data(), radius.data(), diameter.data(), reach.data(), far.data(), fn) >= 0;
-            };
-            if (hipDeviceSynchronize() != hipSuccess) return -4.f;
-            return time_wall(iters, call);
-        });
-    });
-}
-
-static int bench_linkage_rounds = 0;
-
-float clip_amd_bench_linkage(int dtype, int64_t n, int dim, int copies, int iters) {
-    return guarded(__func__, -4.f, [&](const char * fn) {
-        return bench_on_gallery(dtype, n, dim, 0, iters, copies >= 0, copies > 0 ? copies : PLANT_JOIN, [&](clip_amd_index * ix, float *) {
-            const size_t cap = (size_t)std::max<int64_t>(n - 1, 1);
-            std::vector<int64_t> lo(cap), hi(cap);
-            std::vector<float> dist(cap);
-            auto call = [&]() { return linkage_host(ix, -1, INFINITY, nullptr, lo.data(), hi.data(), dist.data(), nullptr, fn) >= 0; };
-            if (hipDeviceSynchronize() != hipSuccess || !call()) return -4.f;
-            const float us = time_wall(iters, call);
-            bench_linkage_rounds = ix->linkage_rounds;
-            return us;
-        });
-    });
-}
-
-int clip_amd_bench_linkage_rounds(void) { return bench_linkage_rounds; }
-
-int clip_amd_test_index_linkage_rounds(struct clip_amd_index * ix) { return ix ? ix->linkage_rounds : -1; }
-
-static float bench_core_parts[5] = {-4.f, -4.f, -4.f, 0.f, 0.f};
-
-float clip_amd_bench_linkage_core(int dtype, int64_t n, int dim, int k, int copies, int iters) {
-    return guarded(__func__, -4.f, [&](const char * fn) {
-        const bool args_ok = copies >= 0 && k >= 1 && k <= MAX_K;
-        return bench_on_gallery(dtype, n, dim, 0, iters, args_ok, copies > 0 ? copies : PLANT_JOIN, [&](clip_amd_index * ix, float *) {
-            const size_t cap = (size_t)std::max<int64_t>(n - 1, 1);
-            std::vector<int64_t> lo(cap), hi(cap), ids((size_t)n * k);
-            std::vector<float> dist(cap), core((size_t)n), kd((size_t)n * k);
-            // the four calls of an iteration one after another on the one index, each timed on its own: wall time, synchronous calls
-            const std::function<bool()> calls[4] = {
-                [&]() { return linkage_host(ix, k, INFINITY, nullptr, lo.data(), hi.data(), dist.data(), core.data(), fn) >= 0; },
-                [&]() { return knn_graph_impl(ix, k, kd.data(), ids.data(), fn); },
-                [&]() { return linkage_host(ix, -1, INFINITY, nullptr, lo.data(), hi.data(), dist.data(), nullptr, fn) >= 0; },
-                [&]() {
-                    return ensure(ix, ix->lcore, linkage_core_bytes(ix->n)) && core_column(ix, k, nullptr, nullptr, (float *)ix->lcore.p, fn) &&
-                           stream_done(ix, fn);
-                }};
-            double sum[4] = {0, 0, 0, 0};
-            int rounds[2] = {0, 0};
-            if (hipDeviceSynchronize() != hipSuccess) return -4.f;
-            for (int i = -1; i < iters; i++)                   // (iteration -1 warms every call up)
-                for (int c = 0; c < 4; c++) {
-                    const auto t0 = std::chrono::steady_clock::now();
-                    if (!calls[c]()) return -4.f;
-                    if (i >= 0) sum[c] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-                    if (c == 0 || c == 2) rounds[c / 2] = ix->linkage_rounds;
-                }
-            bench_core_parts[0] = (float)(sum[1] / iters);
-            bench_core_parts[1] = (float)(sum[2] / iters);
-            bench_core_parts[2] = (float)(sum[3] / iters);
-            bench_core_parts[3] = (float)rounds[0];
-            bench_core_parts[4] = (float)rounds[1];
-            return (float)(sum[0] / iters);
-        });
-    });
-}
-
-void clip_amd_bench_linkage_core_parts(float * parts) {
-    if (parts) memcpy(parts, bench_core_parts, sizeof(bench_core_parts));
-}
-
-float clip_amd_bench_spread(int dtype, int64_t n, int dim, int64_t n_max, int copies, int iters) {
-    return guarded(__func__, -4.f, [&](const char * fn) {
-        const bool args_ok = n_max >= 1 && copies >= 0;
-        return bench_on_gallery(dtype, n, dim, 0, iters, args_ok, copies > 0 ? copies : PLANT_JOIN, [&](clip_amd_index * ix, float *) {
-            Buf out;                                           // centres + owners (int64), reaches + owner distances, cover radius, count
-            const size_t c = (size_t)n_max, rows = (size_t)n;
-            if (!ensure(ix, out, (c + rows) * 12 + 16)) return -4.f;
-            int64_t * d_centres = (int64_t *)out.p;
-            int64_t * d_owner = d_centres + c;
-            int64_t * d_count = d_owner + rows;
-            float * d_reach = (float *)(d_count + 1);
-            float * d_odist = d_reach + c;
-            float * d_cover = d_odist + rows;
-            auto call = [&]() {
-                return spread_impl(ix, n_max, -INFINITY, nullptr, 0, nullptr, d_centres, d_reach, d_owner, d_odist, d_cover, d_count, false, fn);
-            };
-            if (!call() || hipDeviceSynchronize() != hipSuccess) return -4.f;
-            return time_device(iters, call);
-        });
     });
 }
 

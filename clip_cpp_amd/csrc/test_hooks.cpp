@@ -1,7 +1,7 @@
 // test_hooks.cpp — the kernel-level test and micro-benchmark hooks of include/clip_amd.h (clip_amd_test_*, clip_amd_bench_gemm,
 // clip_amd_bench_attention, clip_amd_bench_jpeg_kernels): host pointers in, the launch_* entry points forward.cpp calls, host pointers out.
 // Nothing here is on a product path; the whole file compiles to nothing with -DCLIPAMD_TEST_HOOKS=0 (`make hooks=0`).  The hooks of the
-// exact index live in search.cpp, next to the private state they reach into.
+// exact index live in search_bench.cpp, next to search.cpp, whose internals they time.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
