@@ -98,6 +98,8 @@ AMD_SYMBOLS = [
     "clip_amd_index_extents", "clip_amd_index_extents_device", "clip_amd_bench_extents", "clip_amd_test_index_extents_route",
     "clip_amd_index_vote", "clip_amd_index_vote_device", "clip_amd_index_vote_ids", "clip_amd_index_vote_graph", "clip_amd_index_vote_graph_device",
     "clip_amd_test_index_vote_block", "clip_amd_bench_vote_graph",
+    "clip_amd_index_rank", "clip_amd_index_rank_ids", "clip_amd_index_rank_device", "clip_amd_index_count", "clip_amd_index_count_device",
+    "clip_amd_bench_rank", "clip_amd_bench_rank_parts",
 ]
 
 _lib = None
@@ -396,6 +398,20 @@ def lib():
     L.clip_amd_test_index_vote_block.argtypes = [vp, i64]
     L.clip_amd_bench_vote_graph.restype = C.c_float
     L.clip_amd_bench_vote_graph.argtypes = [i32, i64, i32, i32, i32, i32, i32, i32]
+    L.clip_amd_index_rank.restype = C.c_bool
+    L.clip_amd_index_rank.argtypes = [vp, f32p, i32, i64p, i64p, u64p, i64p, f32p]
+    L.clip_amd_index_rank_ids.restype = C.c_bool
+    L.clip_amd_index_rank_ids.argtypes = [vp, i64p, i64, i64p, i64p, i32, u64p, i64p, f32p]
+    L.clip_amd_index_rank_device.restype = C.c_bool
+    L.clip_amd_index_rank_device.argtypes = [vp, vp, i32, vp, i64p, vp, vp, vp]
+    L.clip_amd_index_count.restype = C.c_bool
+    L.clip_amd_index_count.argtypes = [vp, f32p, i32, f32p, u64p, i64p]
+    L.clip_amd_index_count_device.restype = C.c_bool
+    L.clip_amd_index_count_device.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.clip_amd_bench_rank.restype = C.c_float
+    L.clip_amd_bench_rank.argtypes = [i32, i64, i32, i32, i32]
+    L.clip_amd_bench_rank_parts.restype = None
+    L.clip_amd_bench_rank_parts.argtypes = [f32p]
     L.clip_amd_index_search_index.restype = C.c_bool
     L.clip_amd_index_search_index.argtypes = [vp, vp, i64p, i64, i32, u64p, f32p, i64p]
     L.clip_amd_index_append.restype = i64
@@ -911,6 +927,11 @@ class Index:
     vote(queries, k, labels, m) files queries by example: `labels` gives every row a class (-1: unlabelled), the k nearest labelled rows
     vote, and the m best classes come back by votes, then by their nearest member, each with that member's distance and id; vote_ids takes
     stored rows as the queries and vote_graph every row at once, itself excluded: the audit of a labelling (clip_amd_index_vote*).
+
+    rank(queries, targets) answers "where does THIS row stand for that query?" at any depth: the number of eligible rows search orders
+    before the target (the slot it holds in the full ranking) and search's distance for the pair, with no list made and no k; rank_ids
+    takes stored rows as the queries.  count(queries, radius) is the number of rows range_search would return, without the rows.  Both
+    are one pass of the scan's score chain with a compare and an integer add per row (clip_amd_index_rank* / _count*).
 
     search_distinct(queries, k, radius) folds near-duplicates into one hit: over the query's `pool` nearest rows, walked in search's order,
     a row within `radius` (the distance of pairs) of an earlier kept row is dropped and counted for it; search_ids_distinct does the same
@@ -1712,6 +1733,100 @@ class Index:
             raise ValueError("vote_block: rows must lie in 0 ... 65408, not %d" % int(rows))
         return r
 
+    @staticmethod
+    def _rank_targets(targets, target_lims, nq):
+        """(targets int64 [columns], lims int64 [nq + 1] or None, result shape) of a rank call.  Without target_lims, `targets` holds one
+        target per query ([nq]) or the same number for every query ([nq, t]); with it, query i owns targets[target_lims[i] :
+        target_lims[i + 1]] (ValueError unless it starts at 0, never decreases and ends at the number of targets).  Pure numpy."""
+        t = np.asarray(targets)
+        if t.size and not np.issubdtype(t.dtype, np.integer):
+            raise ValueError("targets must be integers, not %s" % t.dtype)
+        if target_lims is not None:
+            flat = np.ascontiguousarray(t.reshape(-1), dtype=np.int64)
+            lims = Index._set_lims(target_lims, flat.size)
+            if lims.size != nq + 1:
+                raise ValueError("target_lims must have one entry per query and one more: %d, not %d" % (nq + 1, lims.size))
+            return flat, lims, (flat.size,)
+        if t.ndim == 2 and t.shape[0] == nq:
+            flat = np.ascontiguousarray(t.reshape(-1), dtype=np.int64)
+            return flat, np.arange(nq + 1, dtype=np.int64) * t.shape[1], t.shape
+        if t.size != nq:
+            raise ValueError("targets must hold one id per query ([%d]) or as many for each ([%d, t]), not shape %r" % (nq, nq, t.shape))
+        return np.ascontiguousarray(t.reshape(-1), dtype=np.int64), None, (nq,)
+
+    @staticmethod
+    def _rank_outputs(flat, lims, shape):
+        ranks = np.empty(max(flat.size, 1), dtype=np.int64)[:flat.size]      # (never a NULL pointer)
+        dist = np.empty(max(flat.size, 1), dtype=np.float32)[:flat.size]
+        i64p = C.POINTER(C.c_int64)
+        return ranks, dist, (flat.ctypes.data_as(i64p), None if lims is None else lims.ctypes.data_as(i64p)), shape
+
+    def rank(self, queries, targets, target_lims=None, allow=None):
+        """Where the stored rows `targets` stand for their queries: (ranks int64, distances f32), shaped like targets (see _rank_targets: one
+        per query, [nq, t], or CSR through target_lims).  ranks = the number of eligible rows `search` orders before the target (smaller
+        distance, or equal distance and lower id): the slot it holds in search(q, everything, allow), or, for a live target outside
+        `allow`, the slot it would be inserted at.  distances = the bits search reports for the pair.  A target out of range or removed:
+        -1 / +inf.  No k: exact at any depth, in one pass over the rows."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        flat, lims, shape = self._rank_targets(targets, target_lims, q.shape[0])
+        ranks, dist, (tp, lp), shape = self._rank_outputs(flat, lims, shape)
+        words, wp = self._allow(allow)
+        if not lib().clip_amd_index_rank(self._live(), _fp(q), q.shape[0], tp, lp, wp, ranks.ctypes.data_as(C.POINTER(C.c_int64)), _fp(dist)):
+            raise RuntimeError("clip_amd_index_rank failed (see stderr)")
+        return ranks.reshape(shape), dist.reshape(shape)
+
+    def rank_ids(self, ids, targets, target_lims=None, exclude_self=True, allow=None):
+        """rank with the stored rows `ids` as the queries, bit for bit as search_ids takes them; exclude_self: a query's own row is never
+        counted, so the ranks are slots of search_ids(..., exclude_self=True).  A query id out of range or removed gives -1 / +inf in all
+        its columns (no error: a rank call reports per column)."""
+        a = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        a = np.zeros(1, dtype=np.int64)[:0] if a.size == 0 else a
+        flat, lims, shape = self._rank_targets(targets, target_lims, a.size)
+        ranks, dist, (tp, lp), shape = self._rank_outputs(flat, lims, shape)
+        words, wp = self._allow(allow)
+        if not lib().clip_amd_index_rank_ids(self._live(), a.ctypes.data_as(C.POINTER(C.c_int64)), a.size, tp, lp, int(bool(exclude_self)), wp,
+                                             ranks.ctypes.data_as(C.POINTER(C.c_int64)), _fp(dist)):
+            raise RuntimeError("clip_amd_index_rank_ids failed (see stderr)")
+        return ranks.reshape(shape), dist.reshape(shape)
+
+    def rank_device(self, d_queries, n_queries, d_targets, d_ranks, d_distances=None, target_lims=None, d_allow=None):
+        """rank on device pointers (ints): queries [n, dim] f32, targets int64 [columns] -> ranks int64, distances f32 (0 / None: not
+        wanted), [columns] each; target_lims stays a host array ([n + 1], None: one target per query); d_allow uint64 words (0 / None:
+        every row).  Asynchronous on the context's stream."""
+        lp = None
+        if target_lims is not None:
+            lims = np.ascontiguousarray(target_lims, dtype=np.int64)
+            if lims.ndim != 1 or lims.size != int(n_queries) + 1:
+                raise ValueError("target_lims must have one entry per query and one more: %d" % (int(n_queries) + 1))
+            lp = lims.ctypes.data_as(C.POINTER(C.c_int64))
+        if not lib().clip_amd_index_rank_device(self._live(), C.c_void_p(d_queries or None), int(n_queries), C.c_void_p(d_targets or None), lp,
+                                                C.c_void_p(d_allow or None), C.c_void_p(d_ranks or None), C.c_void_p(d_distances or None)):
+            raise RuntimeError("clip_amd_index_rank_device failed (see stderr)")
+
+    def count(self, queries, radius, allow=None):
+        """int64 [nq]: how many eligible rows lie within `radius` (a scalar, or one per query) of each query, d <= radius in f32: the
+        lengths of range_search's segments at that radius, without the rows.  ValueError for a NaN radius."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        nq = q.shape[0]
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float32), (nq,)) if np.ndim(radius) == 0
+                                 else np.asarray(radius, dtype=np.float32).reshape(-1))
+        if r.size != nq:
+            raise ValueError("radius must be a scalar or hold one value per query: %d, not %d" % (nq, r.size))
+        if bool(np.isnan(r).any()):
+            raise ValueError("radius is NaN")
+        r = np.zeros(1, dtype=np.float32)[:0] if nq == 0 else r
+        words, wp = self._allow(allow)
+        counts = np.empty(max(nq, 1), dtype=np.int64)[:nq]
+        if not lib().clip_amd_index_count(self._live(), _fp(q), nq, _fp(r), wp, counts.ctypes.data_as(C.POINTER(C.c_int64))):
+            raise RuntimeError("clip_amd_index_count failed (see stderr)")
+        return counts
+
+    def count_device(self, d_queries, n_queries, d_radii, d_counts, d_allow=None):
+        """count on device pointers (ints): queries [n, dim] f32, radii f32 [n] -> counts int64 [n]; asynchronous on the context's stream"""
+        if not lib().clip_amd_index_count_device(self._live(), C.c_void_p(d_queries or None), int(n_queries), C.c_void_p(d_radii or None),
+                                                 C.c_void_p(d_allow or None), C.c_void_p(d_counts or None)):
+            raise RuntimeError("clip_amd_index_count_device failed (see stderr)")
+
     def search_index(self, src, k, ids=None, allow=None):
         """This index searched with the stored rows of `src` (an Index of the same Clip, dim and dtype without removed rows): every row in
         id order, or the rows `ids` (duplicates and any order are fine).  (distances f32 [n, k], ids int64 [n, k]) as `search` gives them
@@ -1958,6 +2073,18 @@ def bench_vote_graph(dtype, n, dim, k, m=1, classes=64, route=0, iters=3):
     """Microseconds (wall) per clip_amd_index_vote_graph over the n seeded random rows of bench_knn, a row's label a seeded hash of its
     number modulo `classes`; route as bench_knn (clip_amd_bench_vote_graph); < 0 on error."""
     return float(lib().clip_amd_bench_vote_graph(Index.DTYPES[dtype], int(n), int(dim), int(k), int(m), int(classes), int(route), int(iters)))
+
+
+def bench_rank(dtype, n, dim, n_queries, iters=10, parts=False):
+    """Microseconds (device time) per clip_amd_index_rank_device of n_queries seeded random queries, one seeded target each, over the n
+    seeded random rows of bench_search (clip_amd_bench_rank); < 0 on error.  parts: (that, the key kernel alone in device microseconds,
+    one host-form rank of one query in wall microseconds)."""
+    us = float(lib().clip_amd_bench_rank(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(iters)))
+    if not parts:
+        return us
+    p = (C.c_float * 2)()
+    lib().clip_amd_bench_rank_parts(p)
+    return us, float(p[0]), float(p[1])
 
 
 def bench_knn(dtype, n, dim, k, route=0, iters=3):

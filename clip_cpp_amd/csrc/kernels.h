@@ -380,6 +380,37 @@ void launch_vote_voters(const uint32_t * live, const uint32_t * allow, int64_t a
                         uint32_t * mixed, hipStream_t stream);
 void launch_vote_fold(const float * dist, const int64_t * ids, int64_t nq, int k, const int * labels, int m, int64_t row0, const uint32_t * live,
                       const uint32_t * only_voters, int * classes, int * votes, float * odist, int64_t * oids, hipStream_t stream);
+// Rank and count queries (k_rank.hip).  A column c is the prepared query row qof[c] (device; NULL: row c) with a key (kd[c], kid[c]); its
+// count is the number of stored rows that are eligible (mask as above; qself != NULL: row qself[query row] is not, as in the scan) and
+// come before the key in the candidate order: d < kd, or d == kd and row < kid (kid NULL: INT_MAX, which makes it d <= kd).
+// key: kd[c] / kid[c] := the distance of (query row qof[c], stored row targets[c]) with the scan's bits and that row's id; a target
+// outside [0, n) or with a cleared bit in live, or a query row with qself < 0 (qself may be NULL), gives +inf / -1, and nothing is read at
+// such a target.  count: part [n_chunks][ncols] := each chunk's count of every column (rows_per_chunk from rank_rows_per_chunk; qt in
+// {1, 2, 4}: column tiles per workgroup; nothing is launched for n == 0).  finish: out[c] := the sum of the column's n_chunks partials, -1
+// where kid[c] < 0 (kid may be NULL) or `none`; dist != NULL: dist[c] := kd[c], +inf with `none` (kd and kid are not read then).
+struct RankArgs {
+    const void * rows = nullptr;
+    const float * rinv = nullptr;
+    int64_t n = 0;
+    int Dpad = 0, dtype = 0;
+    const void * q = nullptr;
+    const float * qinv = nullptr;
+    const int * qof = nullptr;
+    const float * kd = nullptr;
+    const int * kid = nullptr;
+    const int * qself = nullptr;
+    int ncols = 0, qt = 1;
+    int * part = nullptr;
+    int n_chunks = 0;
+    int64_t rows_per_chunk = 0;
+    const uint32_t * mask = nullptr;
+};
+int64_t rank_rows_per_chunk(int64_t n);
+void launch_rank_key(const void * rows, const float * rinv, const uint32_t * live, int64_t n, int Dpad, int dtype, const void * q, const float * qinv,
+                     const int * qof, const int * qself, const int64_t * targets, int ncols, float * kd, int * kid, hipStream_t stream);
+bool launch_rank_count(const RankArgs & a, hipStream_t stream);
+void launch_rank_finish(const int * part, int n_chunks, int ncols, const int * kid, const float * kd, bool none, int64_t * out, float * dist,
+                        hipStream_t stream);
 // Searches by id.  gather: query t of n_rows (the padded count) := stored row ids[t] (device; NULL: row first + t) for t < n_ids, bit for bit
 // (i8: qinv[t] := rinv of that row), qself[t] := that id; an id outside [0, n) or with a cleared bit in live, and every t >= n_ids, gives the
 // zero row and qself -1.  launch_search_scan with qself != NULL never makes row qself[query] a candidate of that query; launch_search_finish

@@ -11,6 +11,7 @@
 //                   connected components (link -> flatten -> finish), density modes, the single-linkage tree, the extents of a
 //                   labelling, farthest-first selection
 //   k_vote.hip      k-NN voting over labelled rows (the voter bitmap and the fold, as the sink of search_blocks)
+//   k_rank.hip      rank and count queries (rank_blocks: key -> count -> finish per block of columns; the host arithmetic in rank_host.h)
 // and appending one index to another, the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
 // The benchmark and test hooks are in search_bench.cpp; search_impl.h holds what the two files share.
 // Single owners: search_device_impl (the passes of a search: one ScanArgs per scan launch, whatever the selection), search_blocks and
@@ -1551,7 +1552,202 @@ bool idx::compound_device_impl(clip_amd_index * ix, const float * d_terms, int64
     return true;
 }
 
+namespace {
+
+// Rank and count queries (k_rank.hip) over nq query rows whose columns lims names (rank_host.h; NULL: one column per query), in blocks of
+// at most RANK_BLOCK columns and query rows, one after another on the stream.  source(q_lo, mq) names a block's queries for
+// prepare_queries / gather_queries; keys(c0, m) hands out the block's keys on the device: ranked, the int64 targets of its columns (the
+// key kernel turns them into (distance, id) keys and flags); else the f32 radii of its queries, which are the key distances as they
+// stand.  dest(c0, out, dist) names where the block's int64 results and, ranked and wanted, key distances go (device); done(c0, m)
+// follows every block (the host forms copy it out there).  An empty index: rank -1 / +inf, count 0, from the finish alone.
+template <typename Source, typename Keys, typename Dest, typename Done>
+bool rank_blocks(clip_amd_index * ix, int64_t nq, const int64_t * lims, bool ranked, const uint32_t * d_allow, const char * fn, Source && source,
+                 Keys && keys, Dest && dest, Done && done) {
+    hipStream_t st = stream_of(ix);
+    const int64_t ncols = rank_columns(nq, lims), n = ix->n;
+    if (ncols == 0) return true;
+    const uint32_t * mask = nullptr;
+    if (!effective_mask(ix, d_allow, mask)) return false;
+    const int64_t rpc = rank_rows_per_chunk(n);
+    const int n_chunks = (int)((n + rpc - 1) / rpc);
+    const size_t B = (size_t)std::min(ncols, RANK_BLOCK);
+    if (!ensure(ix, ix->rcols, B * 12) || !ensure(ix, ix->rpart, (size_t)n_chunks * B * sizeof(int))) return false;
+    float * kd = (float *)ix->rcols.p;
+    int * kid = (int *)(kd + B);
+    int * d_qof = kid + B;
+    std::vector<int> qof(lims ? (size_t)ncols : 0);            // (the whole call's: a block's part is never rewritten while its copy may be pending)
+    for (int64_t c0 = 0; c0 < ncols;) {
+        const RankBlock b = rank_block_at(nq, lims, c0);
+        const int m = (int)(b.c1 - b.c0), mq = (int)(b.q_hi - b.q_lo);
+        const QuerySource src = source(b.q_lo, mq);
+        const void * key = keys(b.c0, m);
+        int64_t * d_out = nullptr;
+        float * d_dist = nullptr;
+        dest(b.c0, d_out, d_dist);
+        if (!ranked) d_dist = nullptr;
+        if (n == 0) {
+            launch_rank_finish(nullptr, 0, m, nullptr, nullptr, ranked, d_out, d_dist, st);
+        } else {
+            if (!(src.by_id ? gather_queries(ix, src, 0, mq, mq) : prepare_queries(ix, src.d_q, mq, mq))) return false;
+            const int * qself = src.by_id ? (const int *)ix->qself.p : nullptr;
+            if (lims) {
+                rank_expand(lims, b, qof.data() + b.c0);
+                if (hipMemcpyAsync(d_qof, qof.data() + b.c0, (size_t)m * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) {
+                    fprintf(stderr, "%s: the upload of a block's columns failed: %s\n", fn, hipGetErrorString(hipGetLastError()));
+                    return false;
+                }
+            }
+            RankArgs a;
+            a.rows = ix->store.rows;
+            a.rinv = ix->store.rinv;
+            a.n = n;
+            a.Dpad = ix->Dpad;
+            a.dtype = ix->dtype;
+            a.q = ix->qbuf.p;
+            a.qinv = (const float *)ix->qinv.p;
+            a.qof = lims ? d_qof : nullptr;
+            a.kd = ranked ? kd : (const float *)key;
+            a.kid = ranked ? kid : nullptr;
+            a.qself = src.exclude_self ? qself : nullptr;
+            a.ncols = m;
+            a.qt = m >= 64 ? 4 : (m > 16 ? 2 : 1);
+            a.part = (int *)ix->rpart.p;
+            a.n_chunks = n_chunks;
+            a.rows_per_chunk = rpc;
+            a.mask = mask;
+            if (ranked)
+                launch_rank_key(a.rows, a.rinv, ix->store.live, n, a.Dpad, a.dtype, a.q, a.qinv, a.qof, qself, (const int64_t *)key, m, kd, kid, st);
+            if (!launch_rank_count(a, st)) {
+                fprintf(stderr, "%s: count launch failed\n", fn);
+                return false;
+            }
+            launch_rank_finish(a.part, n_chunks, m, a.kid, a.kd, false, d_out, d_dist, st);
+        }
+        if (!launched(true, fn) || !done(b.c0, m)) return false;
+        c0 = b.c1;
+    }
+    return true;
+}
+
+// The host forms: the queries are f32 vectors (queries) or stored rows (ids); radii == NULL: ranks of `targets` under lims, else counts
+// within radii (one column per query).  The allowed set goes up once; a block's queries and keys are staged, its results land in the
+// results arena and are copied out before the next block, so nothing on the device grows with the call.
+bool rank_host(clip_amd_index * ix, const float * queries, const int64_t * ids, int64_t nq, const int64_t * targets, const int64_t * lims,
+               const float * radii, bool exclude_self, const uint64_t * allow, int64_t * out, float * distances, const char * fn) {
+    hipStream_t st = stream_of(ix);
+    const int64_t ncols = rank_columns(nq, lims);
+    if (ncols == 0) return true;
+    const uint32_t * d_allow = nullptr;
+    const size_t B = (size_t)std::min(ncols, RANK_BLOCK);
+    Arena a(ix);
+    const auto o_out = a.add(out, B);
+    const auto o_dist = a.add(distances, B);
+    if (!upload_allow(ix, allow, d_allow) || !a.ready() || !reserve_stage(ix, queries, ids, std::min(nq, RANK_BLOCK)) || !ensure(ix, ix->rin, B * 8))
+        return false;
+    return rank_blocks(
+        ix, nq, lims, !radii, d_allow, fn, [&](int64_t q_lo, int mq) { return stage_block(ix, queries, ids, q_lo, mq, exclude_self); },
+        [&](int64_t c0, int m) -> const void * {
+            if (radii) (void)hipMemcpyAsync(ix->rin.p, radii + c0, (size_t)m * 4, hipMemcpyHostToDevice, st);
+            else (void)hipMemcpyAsync(ix->rin.p, targets + c0, (size_t)m * 8, hipMemcpyHostToDevice, st);
+            return ix->rin.p;
+        },
+        [&](int64_t, int64_t *& d_out, float *& d_dist) {
+            d_out = a.dev(o_out);
+            d_dist = a.dev(o_dist);
+        },
+        [&](int64_t c0, int m) {
+            a.queue(0, a.n, 0, (size_t)c0, (size_t)m);
+            return stream_done(ix, fn, hipGetLastError());      // (the staging buffers and the block's results are reused)
+        });
+}
+
+// what the rank entry points ask: the index, n >= 0, target_lims in order, and pointers wherever there is something to read or write
+bool check_rank_args(const clip_amd_index * ix, const void * q, int64_t nq, const void * targets, const int64_t * lims, const void * ranks,
+                     const char * fn) {
+    if (!check_index(ix, fn)) return false;
+    if (nq < 0 || nq > MAX_ROWS) { fprintf(stderr, "%s: %lld queries outside 0 ... %lld\n", fn, (long long)nq, (long long)MAX_ROWS); return false; }
+    if (nq > 0 && !q) { fprintf(stderr, "%s: NULL queries\n", fn); return false; }
+    if (!check_rank_lims(nq, lims, fn)) return false;
+    if (rank_columns(nq, lims) > 0 && (!targets || !ranks)) { fprintf(stderr, "%s: NULL targets or result pointer\n", fn); return false; }
+    return true;
+}
+
+bool check_count_args(const clip_amd_index * ix, const void * q, int nq, const void * radii, const void * counts, const char * fn) {
+    if (!check_index(ix, fn)) return false;
+    if (nq < 0) { fprintf(stderr, "%s: n_queries %d < 0\n", fn, nq); return false; }
+    if (nq > 0 && (!q || !radii || !counts)) { fprintf(stderr, "%s: NULL queries, radii or result pointer\n", fn); return false; }
+    return true;
+}
+
+}  // namespace
+
+// The device forms: queries, keys and allowed set on the device (lims on the host), results straight into the caller's arrays
+bool idx::rank_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, const int64_t * lims, const int64_t * d_targets, const uint32_t * d_allow,
+                           int64_t * d_ranks, float * d_dist, const char * fn) {
+    return rank_blocks(
+        ix, nq, lims, true, ix->n > 0 ? d_allow : nullptr, fn, [&](int64_t q_lo, int) { return vectors(d_q + (size_t)q_lo * ix->dim); },
+        [&](int64_t c0, int) -> const void * { return d_targets + c0; },
+        [&](int64_t c0, int64_t *& o, float *& d) {
+            o = d_ranks + c0;
+            d = d_dist ? d_dist + c0 : nullptr;
+        },
+        [](int64_t, int) { return true; });
+}
+
+bool idx::count_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, const float * d_radii, const uint32_t * d_allow, int64_t * d_counts,
+                            const char * fn) {
+    return rank_blocks(
+        ix, nq, nullptr, false, ix->n > 0 ? d_allow : nullptr, fn, [&](int64_t q_lo, int) { return vectors(d_q + (size_t)q_lo * ix->dim); },
+        [&](int64_t c0, int) -> const void * { return d_radii + c0; }, [&](int64_t c0, int64_t *& o, float *&) { o = d_counts + c0; },
+        [](int64_t, int) { return true; });
+}
+
 extern "C" {
+
+bool clip_amd_index_rank(struct clip_amd_index * ix, const float * queries, int n_queries, const int64_t * targets, const int64_t * target_lims,
+                         const uint64_t * allow, int64_t * ranks, float * distances) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_rank_args(ix, queries, n_queries, targets, target_lims, ranks, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return rank_host(ix, queries, nullptr, n_queries, targets, target_lims, nullptr, false, allow, ranks, distances, fn);
+    });
+}
+
+bool clip_amd_index_rank_ids(struct clip_amd_index * ix, const int64_t * ids, int64_t n_ids, const int64_t * targets, const int64_t * target_lims,
+                             int exclude_self, const uint64_t * allow, int64_t * ranks, float * distances) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_rank_args(ix, ids, n_ids, targets, target_lims, ranks, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return rank_host(ix, nullptr, ids, n_ids, targets, target_lims, nullptr, exclude_self != 0, allow, ranks, distances, fn);
+    });
+}
+
+bool clip_amd_index_rank_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, const int64_t * d_targets,
+                                const int64_t * target_lims, const uint64_t * d_allow, int64_t * d_ranks, float * d_distances) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_rank_args(ix, d_queries, n_queries, d_targets, target_lims, d_ranks, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return rank_device_impl(ix, d_queries, n_queries, target_lims, d_targets, (const uint32_t *)d_allow, d_ranks, d_distances, fn);
+    });
+}
+
+bool clip_amd_index_count(struct clip_amd_index * ix, const float * queries, int n_queries, const float * radii, const uint64_t * allow,
+                          int64_t * counts) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_count_args(ix, queries, n_queries, radii, counts, fn) || !check_radii(radii, n_queries, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return rank_host(ix, queries, nullptr, n_queries, nullptr, nullptr, radii, false, allow, counts, nullptr, fn);
+    });
+}
+
+bool clip_amd_index_count_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, const float * d_radii, const uint64_t * d_allow,
+                                 int64_t * d_counts) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_count_args(ix, d_queries, n_queries, d_radii, d_counts, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return count_device_impl(ix, d_queries, n_queries, d_radii, (const uint32_t *)d_allow, d_counts, fn);
+    });
+}
 
 struct clip_amd_index * clip_amd_index_create(struct clip_ctx * ctx, int dim, int dtype) {
     return guarded(__func__, (clip_amd_index *)nullptr, [&](const char * fn) -> clip_amd_index * {

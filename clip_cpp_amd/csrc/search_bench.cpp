@@ -119,6 +119,7 @@ T set_hook(clip_amd_index * ix, T clip_amd_index::*field, T value, T max) {
 
 int bench_linkage_rounds = 0;
 float bench_core_parts[5] = {-4.f, -4.f, -4.f, 0.f, 0.f};
+float bench_rank_parts[2] = {-4.f, -4.f};      // of the last clip_amd_bench_rank: the key kernel (device), the host form at one query (wall)
 
 }  // namespace
 
@@ -429,6 +430,46 @@ float clip_amd_bench_spread(int dtype, int64_t n, int dim, int64_t n_max, int co
             });
         });
     });
+}
+
+float clip_amd_bench_rank(int dtype, int64_t n, int dim, int n_queries, int iters) {
+    return guarded(__func__, -4.f, [&](const char * fn) {
+        return bench_on_gallery(dtype, n, dim, n_queries, iters, n_queries >= 1, PLANT_NONE, [&](clip_amd_index * ix, float * src) {
+            Buf own;
+            Arena a(ix, own);
+            const auto o_ranks = a.add<int64_t>(nullptr, (size_t)n_queries), o_targets = a.add<int64_t>(nullptr, (size_t)n_queries);
+            const auto o_dist = a.add<float>(nullptr, (size_t)n_queries), o_kd = a.add<float>(nullptr, (size_t)n_queries);
+            const auto o_kid = a.add<int>(nullptr, (size_t)n_queries);
+            if (!a.ready()) return -4.f;
+            std::vector<int64_t> targets((size_t)n_queries), ranks((size_t)n_queries);
+            for (int i = 0; i < n_queries; i++) {              // splitmix64 of the query number under a fixed seed
+                uint64_t z = 0x7A26E7ull + (uint64_t)i * 0x9E3779B97F4A7C15ull;
+                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+                z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+                targets[(size_t)i] = (int64_t)((z ^ (z >> 31)) % (uint64_t)n);
+            }
+            if (hipMemcpy(a.dev(o_targets, true), targets.data(), (size_t)n_queries * 8, hipMemcpyHostToDevice) != hipSuccess) return -4.f;
+            launch_search_fill_random(src, (int64_t)n_queries * dim, 0xC0FFEEull, nullptr);
+            const float us = time_device(iters, [&]() {
+                return rank_device_impl(ix, src, n_queries, nullptr, a.dev(o_targets, true), nullptr, a.dev(o_ranks, true), a.dev(o_dist, true), fn);
+            });
+            // the key kernel on its own over the queries the last call left prepared, and the host form at one query
+            bench_rank_parts[0] = time_device(iters, [&]() {
+                launch_rank_key(ix->store.rows, ix->store.rinv, ix->store.live, ix->n, ix->Dpad, ix->dtype, ix->qbuf.p, (const float *)ix->qinv.p, nullptr,
+                                nullptr, a.dev(o_targets, true), std::min<int>(n_queries, (int)RANK_BLOCK), a.dev(o_kd, true), a.dev(o_kid, true),
+                                nullptr);
+                return hipGetLastError() == hipSuccess;
+            });
+            std::vector<float> q((size_t)dim);
+            if (hipMemcpy(q.data(), src, (size_t)dim * 4, hipMemcpyDeviceToHost) != hipSuccess) return -4.f;
+            bench_rank_parts[1] = time_wall(iters, [&]() { return clip_amd_index_rank(ix, q.data(), 1, targets.data(), nullptr, nullptr, ranks.data(), nullptr); });
+            return us;
+        });
+    });
+}
+
+void clip_amd_bench_rank_parts(float * parts) {
+    if (parts) memcpy(parts, bench_rank_parts, sizeof(bench_rank_parts));
 }
 
 }  // extern "C"

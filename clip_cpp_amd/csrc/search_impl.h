@@ -9,6 +9,7 @@
 #include "../../include/clip_amd.h"
 #include "kernels.h"
 #include "model.h"
+#include "rank_host.h"
 
 namespace clipamd {
 namespace idx {
@@ -93,6 +94,10 @@ struct clip_amd_index {
     Buf vvoters;                   // the voter bitmap (live & allow & labelled) and, behind it, the "some live row is no voter" word
     Buf vlabels;                   // labels of a host form copied from the host
     int64_t vote_block = 0;        // clip_amd_test_index_vote_block: query rows per block, 0 automatic
+    // rank and count queries
+    Buf rin;                       // one block's targets (i64) or radii (f32) copied from the host
+    Buf rcols;                     // one block's columns: key distances (f32), key ids (i32), query rows (i32)
+    Buf rpart;                     // one block's partial counts [n_chunks][columns] (i32)
 };
 
 namespace clipamd {
@@ -238,6 +243,10 @@ bool knn_graph_impl(clip_amd_index * ix, int k, float * distances, int64_t * ids
 bool core_column(clip_amd_index * ix, int k, const uint32_t * d_allow, const uint32_t * mask, float * d_core, const char * fn);
 bool search_index_impl(clip_amd_index * ix, const clip_amd_index * src, const int64_t * ids, int64_t nq, int k, const uint64_t * allow,
                        float * distances, int64_t * out_ids, const char * fn);
+bool rank_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, const int64_t * lims, const int64_t * d_targets, const uint32_t * d_allow,
+                      int64_t * d_ranks, float * d_dist, const char * fn);
+bool count_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, const float * d_radii, const uint32_t * d_allow, int64_t * d_counts,
+                       const char * fn);
 bool vote_host(clip_amd_index * ix, const float * queries, const int64_t * ids, int64_t nq, int k, int m, bool exclude_self, const int32_t * labels,
                const uint64_t * allow, const VoteOut & out, const char * fn);
 int64_t join_impl(clip_amd_index * ix, const float * d_q, int nq, bool pairs, float radius, const uint32_t * d_allow, int64_t * lims,

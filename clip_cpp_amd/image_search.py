@@ -1624,6 +1624,137 @@ def audit(argv):
     return 0
 
 
+EVAL_BATCH = 256    # captions per pass of the text tower in `eval`
+
+
+def _parse_eval(argv):
+    """The options of `eval`; None when they do not parse."""
+    p = dict(verbose=1, db=".", model="", results=0, rest=[])
+    p["in"] = []
+    takes = {"-m": "model", "--model": "model", "-v": "verbose", "--verbose": "verbose", "--db": "db", "-n": "results", "--results": "results",
+             "--in": "in"}
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a in takes:
+            i += 1
+            if i >= len(argv):
+                return None
+            key = takes[a]
+            if key == "in":
+                p["in"].append(argv[i])
+            else:
+                try:
+                    p[key] = int(argv[i]) if key in ("verbose", "results") else argv[i]
+                except ValueError:
+                    return None
+        elif a in ("-h", "--help"):
+            _help_eval(p)
+            sys.exit(0)
+        elif a.startswith("-"):
+            print("main: unrecognized argument: %s" % a)
+            return None
+        else:
+            p["rest"].append(a)
+        i += 1
+    if len(p["rest"]) != 1 or p["results"] < 0:
+        return None
+    return p
+
+
+def _help_eval(p):
+    print("Usage: python -m clip_cpp_amd.image_search eval [options] PAIRS")
+    print("\nMeasures retrieval over an index built by `build`: PAIRS holds lines `caption<TAB>indexed/path`; every caption goes through the")
+    print("text tower and is ranked against its image among all indexed images (Index.rank: exact at any depth, no list is made). Prints the")
+    print("number of pairs, recall@1 / @5 / @10, the median rank (1-based) and the mean reciprocal rank: the figures by which a weight format")
+    print("or an index dtype is judged good enough.")
+    print("\nOptions:")
+    print("  -h, --help: Show this message and exit")
+    print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default.")
+    print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
+    print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
+    print("  -n N, --results N: also print the N worst-placed pairs as `rank distance path caption`. Default: %d" % p["results"])
+    print("  --in PREFIX: rank among the images whose path starts with PREFIX only (a pair's own image need not be one). Repeatable.")
+    print("  PAIRS: a path may occur on several lines; a path that is not in the database is an error.")
+
+
+def read_pairs(image_paths, pairs_file):
+    """(captions, targets int64) of a PAIRS file (lines `caption<TAB>path`, a path compared as written in images.paths and free to occur on
+    several lines); ValueError naming the line for a malformed line or a path that is not indexed."""
+    ids = {path: i for i, path in enumerate(image_paths)}
+    captions, targets = [], []
+    with open(pairs_file) as f:
+        for n, line in enumerate(f.read().split("\n")):
+            if not line:
+                continue
+            caption, tab, path = line.partition("\t")
+            if not tab:
+                raise ValueError("%s line %d: expected `caption<TAB>path`, not '%s'" % (pairs_file, n + 1, line))
+            if path not in ids:
+                raise ValueError("%s line %d: '%s' is not in the database (paths are compared as written in %s)" % (pairs_file, n + 1, path, PATHS_FILE))
+            captions.append(caption)
+            targets.append(ids[path])
+    return captions, np.array(targets, dtype=np.int64)
+
+
+def eval_figures(ranks):
+    """(recall@1, recall@5, recall@10, median rank 1-based, mean reciprocal rank) of 0-based integer ranks, in float64"""
+    r = np.asarray(ranks, dtype=np.int64).astype(np.float64) + 1.0
+    return tuple(float(np.mean(r <= k)) for k in (1, 5, 10)) + (float(np.median(r)), float(np.mean(1.0 / r)))
+
+
+def evaluate(argv):
+    import clip_cpp_amd
+    p = _parse_eval(argv)
+    if p is None:
+        _help_eval(dict(verbose=1, db=".", results=0))
+        return 1
+    if _refuse_gridded(p["db"], "eval"):
+        return 1
+    image_paths = _read_db(p)
+    if image_paths is None:
+        return 1
+    try:
+        captions, targets = read_pairs(image_paths, p["rest"][0])
+    except (OSError, ValueError) as e:
+        _err("main: %s" % e)
+        return 1
+    _, dim, _, _ = read_index_header(os.path.join(p["db"], INDEX_FILE))
+    try:
+        clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])
+    except RuntimeError:
+        print("main: Unable to load model from %s" % p["model"])
+        return 1
+    if clip.text_config["n_layer"] <= 0:
+        _err("main: the model at %s has no text encoder: captions need a two-tower model" % p["model"])
+        return 1
+    if dim != clip.text_config["projection_dim"]:
+        _err("main: the index holds %d-dimensional embeddings, the model makes %d" % (dim, clip.text_config["projection_dim"]))
+        return 1
+    index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
+    allow = np.array([path.startswith(tuple(p["in"])) for path in image_paths], dtype=np.bool_) if p["in"] else None
+    ranks = np.empty(len(captions), dtype=np.int64)
+    dist = np.empty(len(captions), dtype=np.float32)
+    for b in range(0, len(captions), EVAL_BATCH):
+        vecs = clip.encode_texts([clip.tokenize(t) for t in captions[b:b + EVAL_BATCH]], normalize=True)      # as written: no prompt template
+        ranks[b:b + EVAL_BATCH], dist[b:b + EVAL_BATCH] = index.rank(vecs, targets[b:b + EVAL_BATCH], allow=allow)
+    if p["verbose"] > 0:
+        print("retrieval:")
+    if len(captions):
+        r1, r5, r10, median, mrr = eval_figures(ranks)
+        print("  recall@1 %f recall@5 %f recall@10 %f" % (r1, r5, r10))
+        print("  median rank %.1f mean reciprocal rank %f" % (median, mrr))
+    if p["results"] > 0 and len(captions):
+        print("worst placed:")
+        for i in np.lexsort((np.arange(len(ranks)), -ranks))[:p["results"]]:      # rank descending, then the order of PAIRS
+            print("  %d %f %s %s" % (ranks[i] + 1, dist[i], image_paths[targets[i]], captions[i]))
+    print("main: %d pairs ranked among %d images" % (len(captions), len(image_paths) if allow is None else int(allow.sum())))
+    sys.stdout.flush()
+    index.close()
+    clip.close()
+    return 0
+
+
 DTYPE_NAMES = {0: "f32", 1: "f16", 3: "i8"}       # the dtype codes of a CLIPIDX1 header
 
 
@@ -1840,7 +1971,7 @@ def match(argv):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     commands = {"build": build, "update": update, "search": search, "dedup": dedup, "neighbors": neighbors, "label": label, "merge": merge, "match": match,
-                "albums": albums, "spread": spread, "groups": groups, "levels": levels, "file": file_images, "audit": audit}
+                "albums": albums, "spread": spread, "groups": groups, "levels": levels, "file": file_images, "audit": audit, "eval": evaluate}
     if not argv or argv[0] not in commands:
         print("Usage: python -m clip_cpp_amd.image_search {build|search|dedup} [options] ...  (-h after the command for its options)")
         print("       python -m clip_cpp_amd.image_search update [options] dir [more dirs]  (an existing database brought in line with the disk)")
@@ -1854,6 +1985,7 @@ def main(argv=None):
         print("       python -m clip_cpp_amd.image_search match [options] [IMAGE]  (a --grid database: the images that share a region with IMAGE, or with each other)")
         print("       python -m clip_cpp_amd.image_search file [options] IMAGE [IMAGE ...]  (into which of your folders each IMAGE goes: its nearest labelled images vote)")
         print("       python -m clip_cpp_amd.image_search audit [options]  (the indexed images that lie in the wrong folder, by the vote of their neighbours)")
+        print("       python -m clip_cpp_amd.image_search eval [options] PAIRS  (recall@K, median rank and MRR of caption<TAB>path pairs: is this model file good enough?)")
         return 1
     return commands[argv[0]](argv[1:])
 

@@ -479,6 +479,47 @@ int64_t clip_amd_test_index_vote_block(struct clip_amd_index * ix, int64_t rows)
 /* Average wall time (microseconds) of one clip_amd_index_vote_graph over the n seeded random rows of clip_amd_bench_knn, the label of a row
  * a seeded hash of its number modulo `classes`, route as clip_amd_bench_knn; < 0 on error.  Used by scripts/vote_bench.py. */
 float clip_amd_bench_vote_graph(int dtype, int64_t n, int dim, int k, int m, int classes, int route, int iters);
+/* Rank and count queries: "where does THIS row stand for that query?" and "how many rows lie within R?", answered without listing
+ * anything.  Evaluating a model file or an index dtype is the first: for (caption, image) pairs, the rank at which the right image comes
+ * back, at any depth (search stops at k = 1024); the second sizes a range search before it is made.  Both run the scan's score chain
+ * with the selection taken out (k_rank.hip): per (query, row) a compare and an integer add, no candidate buffer, sort or merge.
+ * A row is ELIGIBLE when it is live and set in allow (as for clip_amd_index_search_subset; NULL = every live row).
+ * rank: query i owns the targets targets[target_lims[i] ... target_lims[i + 1]) (target_lims host, [n + 1], starting at 0 and never
+ * decreasing; NULL: one target per query, targets[i]); results are laid out like targets.  For a (query, target) column c:
+ *   ranks[c]      the number of eligible rows that search orders before the target: rows at a smaller distance, and rows at the same
+ *                 distance with a lower id.  It is the slot the target holds in clip_amd_index_search_subset(q, k = everything, allow)
+ *                 when the target is itself eligible, and the slot at which it would be inserted when it is live but not in allow.
+ *   distances[c]  the bits search reports for that (query, row) pair; distances may be NULL.
+ * A target outside [0, size) or removed gives rank -1 and distance +INFINITY; nothing is read at such an id.
+ * rank_ids: the stored rows ids[0 ... n_ids) as the queries, bit for bit as in clip_amd_index_search_ids; with exclude_self != 0 a query's
+ * own row is never counted, so the ranks are the slots of search_ids(..., exclude_self = 1).  A query id outside [0, size) or removed gives -1 / +INFINITY in all its columns; unlike search_ids the host form does
+ * not refuse it: a rank call reports per column.
+ * count: counts[i] is the number of eligible rows with d <= radii[i] (radii [n_queries]): lims[i + 1] - lims[i] of
+ * clip_amd_index_range_search_subset at that radius, without the hits.  +INFINITY counts every eligible row; a negative radius counts
+ * what range search reports there: nothing, unless it lies within the rounding of an exact match (a distance can be as low as -1.2e-7).
+ * Results are integers and search's own distances: exact, independent of how queries, targets and rows are split, bit-reproducible.
+ * Refused before any launch, with a message and the outputs untouched: a NULL index, a negative count, NULL pointers where there is
+ * something to read or write, target_lims that does not start at 0 or decreases and, host form, a NaN radius (the device form cannot
+ * see it: such a query counts 0).  Zero queries, zero targets and an empty index succeed: nothing, or -1 / +INFINITY (rank) and 0 (count).
+ * Device memory beyond the index: one block of 4096 columns at a time (its queries, keys and at most 1024 x 4096 partial counts);
+ * nothing grows with the call. */
+bool clip_amd_index_rank(struct clip_amd_index * ix, const float * queries, int n_queries, const int64_t * targets, const int64_t * target_lims,
+                         const uint64_t * allow, int64_t * ranks, float * distances);                        /* host, synchronous */
+bool clip_amd_index_rank_ids(struct clip_amd_index * ix, const int64_t * ids, int64_t n_ids, const int64_t * targets, const int64_t * target_lims,
+                             int exclude_self, const uint64_t * allow, int64_t * ranks, float * distances);   /* host, synchronous */
+bool clip_amd_index_rank_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, const int64_t * d_targets,
+                                const int64_t * target_lims, const uint64_t * d_allow, int64_t * d_ranks,
+                                float * d_distances);                                 /* HBM (target_lims: host), asynchronous */
+bool clip_amd_index_count(struct clip_amd_index * ix, const float * queries, int n_queries, const float * radii, const uint64_t * allow,
+                          int64_t * counts);                                                                  /* host, synchronous */
+bool clip_amd_index_count_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, const float * d_radii,
+                                 const uint64_t * d_allow, int64_t * d_counts);                               /* HBM, asynchronous */
+/* Average device time (microseconds) of one clip_amd_index_rank_device of n_queries seeded random queries with one seeded target each over
+ * the n seeded random rows of clip_amd_bench_search on the current device; < 0 on error.  clip_amd_bench_rank_parts: of the last such
+ * call, parts[0] the key kernel alone (device time) and parts[1] one host-form clip_amd_index_rank of one query (wall time).  Used by
+ * scripts/rank_bench.py. */
+float clip_amd_bench_rank(int dtype, int64_t n, int dim, int n_queries, int iters);
+void clip_amd_bench_rank_parts(float * parts);
 /* One index searched with the rows of another, and one index appended to another: label every image of a database with a small index of
  * captions, find which images of B a database A already holds (k = 1), merge two databases without encoding anything twice.
  * search_index: the queries are stored rows of src: ids[0 ... n_ids) (host), or with ids == NULL every row 0 ... size(src) - 1 (n_ids is
