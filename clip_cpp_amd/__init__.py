@@ -100,6 +100,7 @@ AMD_SYMBOLS = [
     "clip_amd_test_index_vote_block", "clip_amd_bench_vote_graph",
     "clip_amd_index_rank", "clip_amd_index_rank_ids", "clip_amd_index_rank_device", "clip_amd_index_count", "clip_amd_index_count_device",
     "clip_amd_bench_rank", "clip_amd_bench_rank_parts",
+    "clip_amd_index_softmax", "clip_amd_index_softmax_device", "clip_amd_index_softmax_ids", "clip_amd_index_softmax_index", "clip_amd_bench_softmax",
 ]
 
 _lib = None
@@ -412,6 +413,16 @@ def lib():
     L.clip_amd_bench_rank.argtypes = [i32, i64, i32, i32, i32]
     L.clip_amd_bench_rank_parts.restype = None
     L.clip_amd_bench_rank_parts.argtypes = [f32p]
+    L.clip_amd_index_softmax.restype = C.c_bool
+    L.clip_amd_index_softmax.argtypes = [vp, f32p, i32, i32, C.c_float, u64p, f32p, i64p, f32p, f32p]
+    L.clip_amd_index_softmax_device.restype = C.c_bool
+    L.clip_amd_index_softmax_device.argtypes = [vp, vp, i32, i32, C.c_float, vp, vp, vp, vp, vp]
+    L.clip_amd_index_softmax_ids.restype = C.c_bool
+    L.clip_amd_index_softmax_ids.argtypes = [vp, i64p, i64, i32, C.c_float, i32, u64p, f32p, i64p, f32p, f32p]
+    L.clip_amd_index_softmax_index.restype = C.c_bool
+    L.clip_amd_index_softmax_index.argtypes = [vp, vp, i64p, i64, i32, C.c_float, u64p, f32p, i64p, f32p, f32p]
+    L.clip_amd_bench_softmax.restype = C.c_float
+    L.clip_amd_bench_softmax.argtypes = [i32, i64, i32, i32, i32, i32]
     L.clip_amd_index_search_index.restype = C.c_bool
     L.clip_amd_index_search_index.argtypes = [vp, vp, i64p, i64, i32, u64p, f32p, i64p]
     L.clip_amd_index_append.restype = i64
@@ -697,6 +708,22 @@ class Clip:
             raise RuntimeError("clip_amd_zero_shot_label_images failed (see stderr)")
         return scores, idx
 
+    def zero_shot_top(self, images, labels, top=5, scale=100.0):
+        """Zero-shot labelling over ANY number of labels: list of uint8 [ny,nx,3] images x list of label strings -> (probs f32 [B, top],
+        indices int64 [B, top], log_z f32 [B]), each image's `top` best labels with their probabilities under the softmax of scale * cosine
+        similarity over all labels.  The labels are encoded once into an f32 Index of their own, the images go through encode_images_u8,
+        and one Index.softmax call follows; zero_shot_label_images (the reference's arithmetic, at most 8192 labels) is another path."""
+        names = list(labels)
+        dim = self.text_config["projection_dim"]
+        ix = Index(self, dim, "f32")
+        try:
+            for b in range(0, len(names), 1024):
+                ix.add(self.encode_texts([self.tokenize(t) for t in names[b:b + 1024]], normalize=True))
+            _, ids, probs, log_z = ix.softmax(self.encode_images_u8(images), max(1, min(int(top), 1024)), scale=scale)
+        finally:
+            ix.close()
+        return probs, ids, log_z
+
     def preprocess_device(self, images, d_out_ptr):
         """list of uint8 [ny,nx,3] raw images -> [n,S,S,3] float32 at device address d_out_ptr (asynchronous)."""
         keep, arr, B = self._u8_array(images)
@@ -932,6 +959,10 @@ class Index:
     before the target (the slot it holds in the full ranking) and search's distance for the pair, with no list made and no k; rank_ids
     takes stored rows as the queries.  count(queries, radius) is the number of rows range_search would return, without the rows.  Both
     are one pass of the scan's score chain with a compare and an integer add per row (clip_amd_index_rank* / _count*).
+
+    softmax(queries, k, scale) answers "how sure is this hit?": search's k nearest rows with, for each, its probability under the softmax
+    of -scale * distance over EVERY eligible row, and the query's log Z; softmax_ids and softmax_index take stored rows of this or of
+    another index as the queries.  The search plus one sweep of the rows that sums exp instead of ranking (clip_amd_index_softmax*).
 
     search_distinct(queries, k, radius) folds near-duplicates into one hit: over the query's `pool` nearest rows, walked in search's order,
     a row within `radius` (the distance of pairs) of an earlier kept row is dropped and counted for it; search_ids_distinct does the same
@@ -1827,6 +1858,61 @@ class Index:
                                                  C.c_void_p(d_allow or None), C.c_void_p(d_counts or None)):
             raise RuntimeError("clip_amd_index_count_device failed (see stderr)")
 
+    @staticmethod
+    def _softmax_outputs(n, k):
+        """(distances, ids, probs, log_z) to be filled and their four pointers (never NULL, also for n == 0)"""
+        outs = (np.empty((n + 1, k), dtype=np.float32)[:n], np.empty((n + 1, k), dtype=np.int64)[:n], np.empty((n + 1, k), dtype=np.float32)[:n],
+                np.empty(n + 1, dtype=np.float32)[:n])
+        return outs, (_fp(outs[0]), outs[1].ctypes.data_as(C.POINTER(C.c_int64)), _fp(outs[2]), _fp(outs[3]))
+
+    def softmax(self, queries, k, scale=100.0, allow=None):
+        """(distances f32 [nq, k], ids int64 [nq, k], probs f32 [nq, k], log_z f32 [nq]): distances and ids are search(queries, k, allow) bit
+        for bit; probs[i, j] = exp(-scale (d_ij - m_i)) / S_i with m_i the query's smallest distance and S_i the sum of exp(-scale (d - m_i))
+        over EVERY eligible row, so a query's probs sum to 1 when k covers its eligible rows; log_z = -scale m + log S.  scale: finite and
+        > 0 (100: CLIP's logit scale).  Empty slots: prob 0; no eligible row: log_z -inf.  probs / log_z are bit-identical run to run for
+        the same index, queries and call, not across other splits of the queries or index sizes."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        words, wp = self._allow(allow)
+        outs, ptrs = self._softmax_outputs(q.shape[0], int(k))
+        if not lib().clip_amd_index_softmax(self._live(), _fp(q), q.shape[0], int(k), float(scale), wp, *ptrs):
+            raise RuntimeError("clip_amd_index_softmax failed (see stderr)")
+        return outs
+
+    def softmax_ids(self, ids, k, scale=100.0, exclude_self=True, allow=None):
+        """softmax with the stored rows `ids` as the queries, as search_ids takes them; exclude_self: a row is neither its own neighbour nor
+        a term of its own sum."""
+        a = np.zeros(np.size(ids) + 1, dtype=np.int64)[:np.size(ids)]
+        a[:] = np.asarray(ids, dtype=np.int64).reshape(-1)
+        words, wp = self._allow(allow)
+        outs, ptrs = self._softmax_outputs(a.size, int(k))
+        if not lib().clip_amd_index_softmax_ids(self._live(), a.ctypes.data_as(C.POINTER(C.c_int64)), a.size, int(k), float(scale),
+                                                int(bool(exclude_self)), wp, *ptrs):
+            raise RuntimeError("clip_amd_index_softmax_ids failed (see stderr)")
+        return outs
+
+    def softmax_index(self, src, k, scale=100.0, ids=None, allow=None):
+        """softmax with the stored rows of `src` as the queries (every row in id order, or the rows `ids`), as search_index takes them:
+        with labels in this index and images in `src`, every image's k best labels and their probabilities over all labels."""
+        a, ap = None, None
+        n = len(src)
+        if ids is not None:
+            a = np.zeros(np.size(ids) + 1, dtype=np.int64)[:np.size(ids)]      # (no ids is still an array, not the NULL of "every row")
+            a[:] = np.asarray(ids, dtype=np.int64).reshape(-1)
+            ap, n = a.ctypes.data_as(C.POINTER(C.c_int64)), a.size
+        words, wp = self._allow(allow)
+        outs, ptrs = self._softmax_outputs(n, int(k))
+        if not lib().clip_amd_index_softmax_index(self._live(), src._live(), ap, n, int(k), float(scale), wp, *ptrs):
+            raise RuntimeError("clip_amd_index_softmax_index failed (see stderr)")
+        return outs
+
+    def softmax_device(self, d_queries, n_queries, k, d_distances, d_ids, d_probs, d_log_z, scale=100.0, d_allow=None):
+        """softmax on device pointers (ints): queries [n, dim] f32 -> distances, probs [n, k] f32, ids [n, k] int64, log_z [n] f32; d_allow
+        uint64 words (0 / None: every row).  Asynchronous on the context's stream."""
+        if not lib().clip_amd_index_softmax_device(self._live(), C.c_void_p(d_queries or None), int(n_queries), int(k), float(scale),
+                                                   C.c_void_p(d_allow or None), C.c_void_p(d_distances or None), C.c_void_p(d_ids or None),
+                                                   C.c_void_p(d_probs or None), C.c_void_p(d_log_z or None)):
+            raise RuntimeError("clip_amd_index_softmax_device failed (see stderr)")
+
     def search_index(self, src, k, ids=None, allow=None):
         """This index searched with the stored rows of `src` (an Index of the same Clip, dim and dtype without removed rows): every row in
         id order, or the rows `ids` (duplicates and any order are fine).  (distances f32 [n, k], ids int64 [n, k]) as `search` gives them
@@ -2085,6 +2171,12 @@ def bench_rank(dtype, n, dim, n_queries, iters=10, parts=False):
     p = (C.c_float * 2)()
     lib().clip_amd_bench_rank_parts(p)
     return us, float(p[0]), float(p[1])
+
+
+def bench_softmax(dtype, n, dim, n_queries, k=10, iters=10):
+    """Microseconds (device time) per clip_amd_index_softmax_device of n_queries seeded random queries at scale 100 over the n seeded random
+    rows of bench_search (clip_amd_bench_softmax); < 0 on error."""
+    return float(lib().clip_amd_bench_softmax(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(k), int(iters)))
 
 
 def bench_knn(dtype, n, dim, k, route=0, iters=3):

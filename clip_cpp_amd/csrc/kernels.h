@@ -411,6 +411,31 @@ void launch_rank_key(const void * rows, const float * rinv, const uint32_t * liv
 bool launch_rank_count(const RankArgs & a, hipStream_t stream);
 void launch_rank_finish(const int * part, int n_chunks, int ncols, const int * kid, const float * kd, bool none, int64_t * out, float * dist,
                         hipStream_t stream);
+// Softmax over every eligible row (k_softmax.hip).  Column c is the prepared query row c; kd [ncols][k] holds the distances the search
+// reported for it, so kd[c * k] is its minimum m over the eligible rows (mask and qself as for rank above: qself != NULL, row qself[c]
+// is not eligible).  sweep: part [n_chunks][ncols] := each chunk's sum of exp(-beta (d - m)) over its eligible rows, every term <= 1
+// (rows_per_chunk from rank_rows_per_chunk; qt in {1, 2, 4}; nothing is launched for n == 0).  finish: S := the column's partials added
+// in chunk order in double; dist / ids [ncols][k] := din / iin bit for bit, probs[c][j] := exp(-beta (d_j - m)) / S (0 for an empty
+// slot), log_z[c] := -beta m + log S; a column whose first slot is empty (iin < 0), and every column with n_chunks == 0: -inf and zeros.
+struct SoftmaxArgs {
+    const void * rows = nullptr;
+    const float * rinv = nullptr;
+    int64_t n = 0;
+    int Dpad = 0, dtype = 0;
+    const void * q = nullptr;
+    const float * qinv = nullptr;
+    const float * kd = nullptr;
+    const int * qself = nullptr;
+    int ncols = 0, qt = 1, k = 1;
+    float beta = 1.f;
+    float * part = nullptr;
+    int n_chunks = 0;
+    int64_t rows_per_chunk = 0;
+    const uint32_t * mask = nullptr;
+};
+bool launch_softmax_sweep(const SoftmaxArgs & a, hipStream_t stream);
+void launch_softmax_finish(const float * part, int n_chunks, int ncols, int k, float beta, const float * din, const int64_t * iin, float * dist,
+                           int64_t * ids, float * probs, float * log_z, hipStream_t stream);
 // Searches by id.  gather: query t of n_rows (the padded count) := stored row ids[t] (device; NULL: row first + t) for t < n_ids, bit for bit
 // (i8: qinv[t] := rinv of that row), qself[t] := that id; an id outside [0, n) or with a cleared bit in live, and every t >= n_ids, gives the
 // zero row and qself -1.  launch_search_scan with qself != NULL never makes row qself[query] a candidate of that query; launch_search_finish

@@ -12,6 +12,7 @@
 //                   labelling, farthest-first selection
 //   k_vote.hip      k-NN voting over labelled rows (the voter bitmap and the fold, as the sink of search_blocks)
 //   k_rank.hip      rank and count queries (rank_blocks: key -> count -> finish per block of columns; the host arithmetic in rank_host.h)
+//   k_softmax.hip   softmax over every eligible row (softmax_blocks: the sweep and its finish as the sink of search_blocks)
 // and appending one index to another, the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
 // The benchmark and test hooks are in search_bench.cpp; search_impl.h holds what the two files share.
 // Single owners: search_device_impl (the passes of a search: one ScanArgs per scan launch, whatever the selection), search_blocks and
@@ -1702,7 +1703,195 @@ bool idx::count_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, 
         [](int64_t, int) { return true; });
 }
 
+namespace {
+
+constexpr int64_t SOFTMAX_BLOCK = 4096;       // queries per block: the partial sums of a block are at most 1024 x 4096 floats
+
+// the four result arrays of a softmax call: dist / ids / probs [rows][k], log_z [rows], on the device or on the host
+struct SoftmaxOut {
+    float * dist = nullptr;
+    int64_t * ids = nullptr;
+    float * probs = nullptr;
+    float * log_z = nullptr;
+};
+
+// queries per block of a softmax call: query_block's, at most SOFTMAX_BLOCK (whole tiles of 128 either way)
+int64_t softmax_block(int64_t nq, int k) { return std::min(query_block(nq, k, 12), SOFTMAX_BLOCK); }
+
+// Softmax over every eligible row (k_softmax.hip) as the sink of search_blocks: a block of queries is searched on route p exactly as
+// the search entry points search it, which leaves its k nearest rows and so its minimum distance; then the block's queries are
+// prepared (or gathered) once more as one run of rows, the sweep sums exp(-beta (d - m)) over the eligible rows into one float per
+// (chunk, column), and the finish writes distances, ids, probs and log_z to dest(q0) (device); done(q0, m) follows every block (the host
+// forms copy it out there).  source(q0, m) names a block's queries; launch(q0, m) is the tiled route's kernel.  An empty index: the
+// search's empty slots, probs 0 and log_z -inf, from the finish alone.
+template <typename Source, typename Launch, typename Dest, typename Done>
+bool softmax_blocks(clip_amd_index * ix, int64_t nq, int k, float beta, const GraphPlan & p, const uint32_t * d_allow, const char * fn,
+                    Source && source, Launch && launch, Dest && dest, Done && done) {
+    hipStream_t st = stream_of(ix);
+    const int64_t n = ix->n;
+    if (nq == 0) return true;
+    const int64_t rpc = rank_rows_per_chunk(n);
+    const int n_chunks = (int)((n + rpc - 1) / rpc);
+    if (!ensure(ix, ix->spart, (size_t)n_chunks * (size_t)std::min(nq, p.block) * sizeof(float))) return false;
+    QuerySource cur;
+    return search_blocks(
+        ix, nq, k, p, d_allow, fn, [&](int64_t q0, int m) { return cur = source(q0, m); }, launch,
+        [&](int64_t q0, int m, const float * d_dist, const int64_t * d_ids) {
+            const SoftmaxOut o = dest(q0);
+            if (n > 0) {
+                if (p.tiled) cur = source(q0, m);                  // (the tiled kernel read the stores itself: nothing was staged yet)
+                const uint32_t * mask = nullptr;                   // (after the search: the scan left the same words in the same workspace)
+                if (!effective_mask(ix, d_allow, mask)) return false;
+                if (!(cur.by_id ? gather_queries(ix, cur, 0, m, m) : prepare_queries(ix, cur.d_q, m, m))) return false;
+                SoftmaxArgs a;
+                a.rows = ix->store.rows;
+                a.rinv = ix->store.rinv;
+                a.n = n;
+                a.Dpad = ix->Dpad;
+                a.dtype = ix->dtype;
+                a.q = ix->qbuf.p;
+                a.qinv = (const float *)ix->qinv.p;
+                a.kd = d_dist;
+                a.qself = cur.exclude_self ? (const int *)ix->qself.p : nullptr;
+                a.ncols = m;
+                a.qt = m >= 64 ? 4 : (m > 16 ? 2 : 1);
+                a.k = k;
+                a.beta = beta;
+                a.part = (float *)ix->spart.p;
+                a.n_chunks = n_chunks;
+                a.rows_per_chunk = rpc;
+                a.mask = mask;
+                if (!launch_softmax_sweep(a, st)) {
+                    fprintf(stderr, "%s: sweep launch failed\n", fn);
+                    return false;
+                }
+            }
+            launch_softmax_finish((const float *)ix->spart.p, n > 0 ? n_chunks : 0, m, k, beta, d_dist, d_ids, o.dist, o.ids, o.probs, o.log_z, st);
+            return launched(true, fn) && done(q0, m);
+        });
+}
+
+// The host forms: the queries are f32 vectors (queries), stored rows of the index (ids) or stored rows of `from` (ids, or NULL: every
+// row in order), on the routes of the searches of the same name.  The allowed set goes up once; a block's queries are staged, its
+// results land in the results arena and are copied out before the next block, so nothing on the device grows with the call.
+bool softmax_host(clip_amd_index * ix, const float * queries, const int64_t * ids, const clip_amd_index * from, int64_t nq, int k, float beta,
+                  bool exclude_self, const uint64_t * allow, const SoftmaxOut & out, const char * fn) {
+    if (nq == 0) return true;
+    const int64_t block = softmax_block(nq, k);
+    // (the tiled kernel reads from's rows in order and needs a row to score: search_index_impl's choice)
+    const GraphPlan p = graph_plan(ix, k, from && !ids && ix->n > 0 ? ix->cross_route : 1, nq >= CROSS_TILED_MIN_QUERIES, block, block);
+    const uint32_t * d_allow = nullptr;
+    const uint32_t * mask = nullptr;
+    const size_t slots = (size_t)block * k;
+    Arena a(ix);
+    const auto o_ids = a.add(out.ids, slots);
+    const auto o_dist = a.add(out.dist, slots), o_probs = a.add(out.probs, slots);
+    const auto o_logz = a.add(out.log_z, (size_t)block);
+    if (!upload_allow(ix, allow, d_allow) || (p.tiled && !effective_mask(ix, d_allow, mask)) || !a.ready() || !reserve_stage(ix, queries, ids, block))
+        return false;
+    SoftmaxOut d;
+    d.dist = a.dev(o_dist);
+    d.ids = a.dev(o_ids);
+    d.probs = a.dev(o_probs);
+    d.log_z = a.dev(o_logz);
+    return softmax_blocks(
+        ix, nq, k, beta, p, d_allow, fn, [&](int64_t q0, int m) { return stage_block(ix, queries, ids, q0, m, exclude_self, from); },
+        [&](int64_t q0, int m) {
+            return launch_graph_cross(ix->store.rows, ix->store.rinv, ix->n, from->store.rows, from->store.rinv, from->n, q0, m, ix->Dpad, ix->dtype, k,
+                                      ix->cand.p, p.n_chunks, p.rpc, mask, stream_of(ix));
+        },
+        [&](int64_t) { return d; },
+        [&](int64_t q0, int m) {
+            a.queue(0, 3, 0, (size_t)q0 * k, (size_t)m * k);
+            a.queue(3, 4, 0, (size_t)q0, (size_t)m);
+            return stream_done(ix, fn, hipGetLastError());      // (the staging buffers and the block's results are reused)
+        });
+}
+
+// what every softmax entry point asks beyond its search: k, a usable scale, and all four result arrays when there is a row to write
+bool check_softmax_args(int64_t nq, int k, float beta, const void * dist, const void * ids, const void * probs, const void * log_z, const char * fn) {
+    if (nq < 0 || nq > MAX_ROWS) { fprintf(stderr, "%s: %lld queries outside 0 ... %lld\n", fn, (long long)nq, (long long)MAX_ROWS); return false; }
+    if (!check_k(k, 1, fn)) return false;
+    if (!(beta > 0.f) || std::isinf(beta)) { fprintf(stderr, "%s: scale %g is not a finite value > 0\n", fn, (double)beta); return false; }
+    if (nq > 0 && (!dist || !ids || !probs || !log_z)) { fprintf(stderr, "%s: NULL result pointer\n", fn); return false; }
+    return true;
+}
+
+}  // namespace
+
+// The device form: queries and allowed set on the device, results straight into the caller's arrays, on the scan route
+bool idx::softmax_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, int k, float beta, const uint32_t * d_allow, float * d_dist,
+                              int64_t * d_ids, float * d_probs, float * d_log_z, const char * fn) {
+    if (nq == 0) return true;
+    const int64_t block = softmax_block(nq, k);
+    const GraphPlan p = graph_plan(ix, k, 1, false, block, block);
+    return softmax_blocks(
+        ix, nq, k, beta, p, ix->n > 0 ? d_allow : nullptr, fn, [&](int64_t q0, int) { return vectors(d_q + (size_t)q0 * ix->dim); },
+        [](int64_t, int) { return false; },
+        [&](int64_t q0) {
+            SoftmaxOut o;
+            o.dist = d_dist + (size_t)q0 * k;
+            o.ids = d_ids + (size_t)q0 * k;
+            o.probs = d_probs + (size_t)q0 * k;
+            o.log_z = d_log_z + q0;
+            return o;
+        },
+        [](int64_t, int) { return true; });
+}
+
 extern "C" {
+
+bool clip_amd_index_softmax(struct clip_amd_index * ix, const float * queries, int n_queries, int k, float scale, const uint64_t * allow,
+                            float * distances, int64_t * ids, float * probs, float * log_z) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_index(ix, fn) || !check_softmax_args(n_queries, k, scale, distances, ids, probs, log_z, fn)) return false;
+        if (n_queries > 0 && !queries) { fprintf(stderr, "%s: NULL queries\n", fn); return false; }
+        (void)hipSetDevice(ix->device);
+        SoftmaxOut o{distances, ids, probs, log_z};
+        return softmax_host(ix, queries, nullptr, nullptr, n_queries, k, scale, false, allow, o, fn);
+    });
+}
+
+bool clip_amd_index_softmax_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int k, float scale, const uint64_t * d_allow,
+                                   float * d_distances, int64_t * d_ids, float * d_probs, float * d_log_z) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_index(ix, fn) || !check_softmax_args(n_queries, k, scale, d_distances, d_ids, d_probs, d_log_z, fn)) return false;
+        if (n_queries > 0 && !d_queries) { fprintf(stderr, "%s: NULL queries\n", fn); return false; }
+        (void)hipSetDevice(ix->device);
+        return softmax_device_impl(ix, d_queries, n_queries, k, scale, (const uint32_t *)d_allow, d_distances, d_ids, d_probs, d_log_z, fn);
+    });
+}
+
+bool clip_amd_index_softmax_ids(struct clip_amd_index * ix, const int64_t * ids, int64_t n_ids, int k, float scale, int exclude_self,
+                                const uint64_t * allow, float * distances, int64_t * out_ids, float * probs, float * log_z) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_index(ix, fn) || !check_softmax_args(n_ids, k, scale, distances, out_ids, probs, log_z, fn)) return false;
+        if (n_ids > 0 && !ids) { fprintf(stderr, "%s: NULL ids\n", fn); return false; }
+        (void)hipSetDevice(ix->device);
+        if (!check_stored_ids(ix, ids, n_ids, fn)) return false;
+        SoftmaxOut o{distances, out_ids, probs, log_z};
+        return softmax_host(ix, nullptr, ids, nullptr, n_ids, k, scale, exclude_self != 0, allow, o, fn);
+    });
+}
+
+bool clip_amd_index_softmax_index(struct clip_amd_index * ix, struct clip_amd_index * src, const int64_t * ids, int64_t n_ids, int k, float scale,
+                                  const uint64_t * allow, float * distances, int64_t * out_ids, float * probs, float * log_z) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_pair(ix, src, fn)) return false;
+        if (ids && n_ids < 0) { fprintf(stderr, "%s: n_ids %lld < 0\n", fn, (long long)n_ids); return false; }
+        const int64_t nq = ids ? n_ids : src->n;
+        if (!check_softmax_args(nq, k, scale, distances, out_ids, probs, log_z, fn)) return false;
+        for (int64_t t = 0; ids && t < nq; t++)
+            if (ids[t] < 0 || ids[t] >= src->n) {
+                fprintf(stderr, "%s: id %lld (entry %lld) outside 0 ... %lld of src: nothing searched\n", fn, (long long)ids[t], (long long)t,
+                        (long long)src->n - 1);
+                return false;
+            }
+        (void)hipSetDevice(ix->device);
+        SoftmaxOut o{distances, out_ids, probs, log_z};
+        return softmax_host(ix, nullptr, ids, src, nq, k, scale, false, allow, o, fn);
+    });
+}
 
 bool clip_amd_index_rank(struct clip_amd_index * ix, const float * queries, int n_queries, const int64_t * targets, const int64_t * target_lims,
                          const uint64_t * allow, int64_t * ranks, float * distances) {

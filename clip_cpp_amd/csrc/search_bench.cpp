@@ -472,4 +472,22 @@ void clip_amd_bench_rank_parts(float * parts) {
     if (parts) memcpy(parts, bench_rank_parts, sizeof(bench_rank_parts));
 }
 
+float clip_amd_bench_softmax(int dtype, int64_t n, int dim, int n_queries, int k, int iters) {
+    return guarded(__func__, -4.f, [&](const char * fn) {
+        return bench_on_gallery(dtype, n, dim, n_queries, iters, n_queries >= 1 && k >= 1 && k <= MAX_K, PLANT_NONE, [&](clip_amd_index * ix, float * src) {
+            Buf own;
+            Arena a(ix, own);
+            const auto o_dist = a.add<float>(nullptr, (size_t)n_queries * k), o_probs = a.add<float>(nullptr, (size_t)n_queries * k);
+            const auto o_ids = a.add<int64_t>(nullptr, (size_t)n_queries * k);
+            const auto o_logz = a.add<float>(nullptr, (size_t)n_queries);
+            if (!a.ready()) return -4.f;
+            launch_search_fill_random(src, (int64_t)n_queries * dim, 0xC0FFEEull, nullptr);
+            return time_device(iters, [&]() {
+                return softmax_device_impl(ix, src, n_queries, k, 100.f, nullptr, a.dev(o_dist, true), a.dev(o_ids, true), a.dev(o_probs, true),
+                                           a.dev(o_logz, true), fn);
+            });
+        });
+    });
+}
+
 }  // extern "C"

@@ -98,6 +98,8 @@ struct clip_amd_index {
     Buf rin;                       // one block's targets (i64) or radii (f32) copied from the host
     Buf rcols;                     // one block's columns: key distances (f32), key ids (i32), query rows (i32)
     Buf rpart;                     // one block's partial counts [n_chunks][columns] (i32)
+    // softmax over every eligible row
+    Buf spart;                     // one block's partial sums [n_chunks][columns] (f32)
 };
 
 namespace clipamd {
@@ -247,6 +249,8 @@ bool rank_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, const 
                       int64_t * d_ranks, float * d_dist, const char * fn);
 bool count_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, const float * d_radii, const uint32_t * d_allow, int64_t * d_counts,
                        const char * fn);
+bool softmax_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, int k, float beta, const uint32_t * d_allow, float * d_dist,
+                         int64_t * d_ids, float * d_probs, float * d_log_z, const char * fn);
 bool vote_host(clip_amd_index * ix, const float * queries, const int64_t * ids, int64_t nq, int k, int m, bool exclude_self, const int32_t * labels,
                const uint64_t * allow, const VoteOut & out, const char * fn);
 int64_t join_impl(clip_amd_index * ix, const float * d_q, int nq, bool pairs, float radius, const uint32_t * d_allow, int64_t * lims,

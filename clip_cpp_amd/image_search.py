@@ -81,6 +81,10 @@ Index.search_ids_distinct): walking the ranked list, an image within distance R 
 is dropped, and a listed image that stands for dropped ones gets " (+%d)", their number, behind its path.  The suppression runs over the
 pool of the max(64, 8 N) nearest eligible images (at most 1024), not over the whole index.  It works with -n, --in and --like, not with
 -d, and not on a database built with --grid.
+`search --prob [--scale S]` and `label --prob [--scale S]` say how sure a hit is (Index.softmax / softmax_ids / softmax_index): the same
+hits in the same order, each line "  %f %f %s" = distance, probability, path (or label), the probability being the softmax of -S * distance
+over EVERY eligible image (every label), not over the printed ones; `search` ends with "main: log Z %f at scale %g".  S defaults to 100,
+the logit scale CLIP is trained to.  --prob works with -n, --in and --like, not with -d, --distinct, --and / --not or a --grid database.
 `search --and TERM` / `--not TERM` (both repeatable, up to 8 terms with the main query) ask compound questions (Index.search_compound):
 "a dog" --and "on a beach", --like PATH --and "at night", "a beach" --not "people".  A TERM with an image extension is an image: one that
 equals a line of images.paths is that indexed image (its stored row: nothing is decoded or encoded, and it is not listed itself), any
@@ -231,6 +235,8 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
                 takes.update({"-n": "results", "--results": "results"})
         if search:
             takes.update({"--in": "in", "--like": "like", "--distinct": "distinct", "--and": "and", "--not": "not", "--not-margin": "not_margin"})
+        if search or label:
+            takes["--scale"] = "scale"
         if a in takes:
             i += 1
             if i >= len(argv):
@@ -245,14 +251,19 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
                 i += 1
                 continue
             try:
-                p[key] = int(argv[i]) if key in ("threads", "verbose", "results", "grid", "min_size", "core") else float(argv[i]) if key in ("max_distance", "distinct", "not_margin", "link") else argv[i]
+                p[key] = int(argv[i]) if key in ("threads", "verbose", "results", "grid", "min_size", "core") else float(argv[i]) if key in ("max_distance", "distinct", "not_margin", "link", "scale") else argv[i]
             except ValueError:
                 return None
-            if key in ("max_distance", "distinct", "not_margin", "link") and p[key] != p[key]:      # NaN
+            if key in ("max_distance", "distinct", "not_margin", "link", "scale") and p[key] != p[key]:      # NaN
+                return None
+            if key == "scale" and not 0.0 < p[key] < float("inf"):
+                print("main: --scale takes a finite value > 0 (100: the logit scale CLIP is trained to), not %s" % argv[i])
                 return None
             if key == "grid" and not 1 <= p[key] <= MAX_GRID:
                 print("main: --grid takes 1 ... %d (1: whole images only), not %d" % (MAX_GRID, p[key]))
                 return None
+        elif (search or label) and a == "--prob":
+            p["prob"] = True
         elif dedup and a == "--prune":
             p["prune"] = True
         elif (dedup or groups) and a == "--extents":
@@ -315,6 +326,12 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
             print("main: a compound search takes at most %d terms (the query, every --and and every --not), not %d"
                   % (MAX_TERMS, 1 + len(p.get("and", [])) + len(p.get("not", []))))
             return None
+    if "scale" in seen and not p.get("prob"):
+        print("main: --scale is the scale of --prob: it needs --prob")
+        return None
+    if p.get("prob") and seen & {"max_distance", "distinct", "and", "not", "not_margin"}:
+        print("main: --prob cannot be combined with -d, --distinct, --and or --not: it prints the probabilities of the -n nearest images")
+        return None
     if {"distinct", "max_distance"} <= seen:
         print("main: --distinct and -d cannot be combined: --distinct R thins the -n nearest, -d R prints every image within R")
         return None
@@ -410,6 +427,8 @@ def _help(build, p, dedup=False, update=False, neighbors=False, label=False, mer
         print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
         print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
         print("  -n N, --results N: Number of labels per image, nearest first (at most %d). Default: %d" % (MAX_K, p["results"]))
+        print("  --prob: print every label's probability (softmax of -scale * distance over ALL labels) behind its distance")
+        print("  --scale S: the scale of --prob, finite and > 0. Default: 100")
     elif merge:
         print("Usage: python -m clip_cpp_amd.image_search merge [options] --db <dir> --from <dir2> [--from <dir3> ...]")
         print("\nAppends the databases given with --from to the one at --db without encoding anything twice. Images whose path the target")
@@ -485,6 +504,8 @@ def _help(build, p, dedup=False, update=False, neighbors=False, label=False, mer
               " a path matching any prefix is eligible. Works with -n and with -d")
         print("  --like <path>: more like this one: the query is the indexed image whose line in %s equals <path> as written; nothing is"
               " decoded or encoded and the image itself is not listed. Works with -n and --in, not with a query or -d" % PATHS_FILE)
+        print("  --prob: print every hit's probability (softmax of -scale * distance over ALL eligible images) and the query's log Z; with -n, --in, --like")
+        print("  --scale S: the scale of --prob, finite and > 0. Default: 100")
         print("  --distinct R: fold near-duplicates into one hit: walking the ranked list, an image within cosine distance R (<= R, the distance"
               " of `dedup -d R`) of an image already listed is dropped, and a listed image is followed by (+N), the number of images dropped"
               " for it. Suppression runs over the max(64, 8 N) nearest eligible images (at most %d), not the whole index. Works with -n, --in"
@@ -788,6 +809,8 @@ def search(argv):
     img_path, text = classify_query(p["rest"])
     if p.get("distinct") is not None and _refuse_gridded(p["db"], "search --distinct"):
         return 1
+    if p.get("prob") and _refuse_gridded(p["db"], "search --prob"):
+        return 1
     compound = bool(p.get("and") or p.get("not"))
     if compound and _refuse_gridded(p["db"], "search --and / --not"):
         return 1
@@ -870,15 +893,29 @@ def search(argv):
             dist, ids, counts = index.search_distinct(vec[None, :], k, p["distinct"], allow=allow)
         hits = [(d, i) for d, i in zip(dist[0], ids[0]) if i >= 0 and p["results"] > 0]
         more = {int(i): int(c) for i, c in zip(ids[0], counts[0]) if i >= 0 and c > 0}
+    elif p.get("prob"):                            # the same hits in the same order, each with its probability over every eligible image
+        k = max(1, min(p["results"], MAX_K))
+        scale = p.get("scale", PROB_SCALE)
+        if like_id is not None:
+            dist, ids, probs, log_z = index.softmax_ids([like_id], k, scale=scale, allow=allow)
+        else:
+            dist, ids, probs, log_z = index.softmax(vec[None, :], k, scale=scale, allow=allow)
+        hits = [(d, i) for d, i in zip(dist[0], ids[0]) if i >= 0 and p["results"] > 0]
+        prob = {int(i): float(pr) for pr, i in zip(probs[0], ids[0]) if i >= 0}
     else:
         k = max(1, min(p["results"], MAX_K))
         dist, ids = index.search_ids([like_id], k, allow=allow) if like_id is not None else index.search(vec[None, :], k, allow=allow)
         hits = [(d, i) for d, i in zip(dist[0], ids[0]) if i >= 0 and p["results"] > 0]
     if p["verbose"] > 0:
         print("search results:")
-        print("distance path")
+        print("distance probability path" if p.get("prob") else "distance path")
     for d, i in hits:
-        print("  %f %s%s%s" % (d, image_paths[i], boxes.get(i, ""), " (+%d)" % more[i] if i in more else ""))
+        if p.get("prob"):
+            print("  %f %f %s" % (d, prob[int(i)], image_paths[i]))
+        else:
+            print("  %f %s%s%s" % (d, image_paths[i], boxes.get(i, ""), " (+%d)" % more[i] if i in more else ""))
+    if p.get("prob"):
+        print("main: log Z %f at scale %g" % (float(log_z[0]), scale))
     sys.stdout.flush()
     index.close()
     clip.close()
@@ -1756,6 +1793,7 @@ def evaluate(argv):
 
 
 DTYPE_NAMES = {0: "f32", 1: "f16", 3: "i8"}       # the dtype codes of a CLIPIDX1 header
+PROB_SCALE = 100.0                                # --prob without --scale: the logit scale CLIP is trained to
 
 
 def label(argv):
@@ -1786,16 +1824,19 @@ def label(argv):
     labels.add(clip.encode_texts([clip.tokenize(t) for t in names], normalize=True))      # as written: no prompt template
     index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
     k = max(1, min(p["results"], len(names), MAX_K))
-    dist, ids = labels.search_index(index, k)      # every image's stored row against the labels
+    if p.get("prob"):                              # the same labels in the same order, each with its probability over all labels
+        dist, ids, probs, _ = labels.softmax_index(index, k, scale=p.get("scale", PROB_SCALE))
+    else:
+        dist, ids = labels.search_index(index, k)      # every image's stored row against the labels
     if p["verbose"] > 0:
         print("labels:")
     for i, path in enumerate(image_paths):
         if i:
             print()
         print(path)
-        for d, j in zip(dist[i], ids[i]):
+        for t, (d, j) in enumerate(zip(dist[i], ids[i])):
             if j >= 0 and p["results"] > 0:
-                print("  %f %s" % (d, names[j]))
+                print("  %f %f %s" % (d, probs[i, t], names[j]) if p.get("prob") else "  %f %s" % (d, names[j]))
     print("main: %d images, %d labels each" % (len(image_paths), k if p["results"] > 0 else 0))
     sys.stdout.flush()
     index.close()

@@ -520,6 +520,48 @@ bool clip_amd_index_count_device(struct clip_amd_index * ix, const float * d_que
  * scripts/rank_bench.py. */
 float clip_amd_bench_rank(int dtype, int64_t n, int dim, int n_queries, int iters);
 void clip_amd_bench_rank_parts(float * parts);
+/* Softmax probabilities over every eligible row: "how sure is this hit?".  A search answers in distances; a probability needs the
+ * normaliser over ALL rows, which a top-k scan never sees.  The call runs the search and then one more sweep of the rows without
+ * selection (k_softmax.hip), which sums exp of the distances instead of ranking them.  Labels in a small index and images as the
+ * queries make it zero-shot classification over any number of labels.
+ * A row is ELIGIBLE when it is live and set in allow (as for clip_amd_index_search_subset; NULL = every live row) and, softmax_ids with
+ * exclude_self != 0, is not the query's own row.  d(q, r) is the f32 distance search reports for the pair, with the same bits.  scale
+ * (beta) is an f32 > 0 and finite: 100 is the logit scale CLIP is trained to, 1 the weighting of the reference's zsl example.  With
+ *   m(q)     = the smallest d(q, r) over the eligible rows: search's first distance,
+ *   S(q)     = the sum over the eligible rows of exp(-scale (d(q, r) - m(q))): every term <= 1 and the nearest row's term 1, so S >= 1
+ *              and no scale over- or underflows,
+ * the call returns per query
+ *   distances[k], ids[k]  the k nearest eligible rows, bit for bit what clip_amd_index_search_subset / _search_ids / _search_index return,
+ *   probs[k]              exp(-scale (distances[j] - m)) / S; 0 in the empty slots (+INFINITY / -1) behind the last eligible row,
+ *   log_z                 -scale m + log S, the log of the sum of exp(-scale d): what compares a query's confidence across databases.
+ * A query without an eligible row (and every query over an empty index): log_z -INFINITY, probs 0.
+ * softmax_ids: the stored rows ids[0 ... n_ids) are the queries, as in clip_amd_index_search_ids (a bad id is refused in the same way).
+ * softmax_index: the stored rows of src are the queries, ids[0 ... n_ids) or, ids == NULL, every row in order: the same requirements,
+ * routes and bits as clip_amd_index_search_index.
+ * What the bits depend on.  distances and ids are exact and bit-reproducible, as everywhere in the index.  probs and log_z are
+ * floating-point sums added in a fixed order (f32 within a chunk of rows, double across chunks): they are bit-identical from run to run
+ * for the same index, the same queries and the same call.  They are NOT promised to be independent of how the queries are split across
+ * calls (a query's place in its tile of 16 ... 64 selects the kernel variant) nor of the index size (which sets the chunks); such
+ * results agree to rounding (profiles/softmax_accuracy.txt), not to the bit.
+ * Refused before any launch, with a message that names the value and the outputs untouched: a NULL index, a negative count, NULL
+ * pointers where there is something to read or write, k outside 1 ... 1024, a scale that is NaN, infinite or <= 0, a bad id (host ids
+ * forms).  Zero queries succeed and write nothing.
+ * Device memory beyond the index: one block of at most 4096 queries at a time (its queries, its results and n_chunks x queries partial
+ * sums, n_chunks <= 1024); nothing grows with the call. */
+bool clip_amd_index_softmax(struct clip_amd_index * ix, const float * queries, int n_queries, int k, float scale, const uint64_t * allow,
+                            float * distances, int64_t * ids, float * probs, float * log_z);                  /* host, synchronous */
+bool clip_amd_index_softmax_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int k, float scale,
+                                   const uint64_t * d_allow, float * d_distances, int64_t * d_ids, float * d_probs,
+                                   float * d_log_z);                                                           /* HBM, asynchronous */
+bool clip_amd_index_softmax_ids(struct clip_amd_index * ix, const int64_t * ids, int64_t n_ids, int k, float scale, int exclude_self,
+                                const uint64_t * allow, float * distances, int64_t * out_ids, float * probs,
+                                float * log_z);                                                                /* host, synchronous */
+bool clip_amd_index_softmax_index(struct clip_amd_index * ix, struct clip_amd_index * src, const int64_t * ids, int64_t n_ids, int k,
+                                  float scale, const uint64_t * allow, float * distances, int64_t * out_ids, float * probs,
+                                  float * log_z);                                                              /* host, synchronous */
+/* Average device time (microseconds) of one clip_amd_index_softmax_device of n_queries seeded random queries over the n seeded random
+ * rows of clip_amd_bench_search on the current device, scale 100; < 0 on error.  Used by scripts/softmax_bench.py. */
+float clip_amd_bench_softmax(int dtype, int64_t n, int dim, int n_queries, int k, int iters);
 /* One index searched with the rows of another, and one index appended to another: label every image of a database with a small index of
  * captions, find which images of B a database A already holds (k = 1), merge two databases without encoding anything twice.
  * search_index: the queries are stored rows of src: ids[0 ... n_ids) (host), or with ids == NULL every row 0 ... size(src) - 1 (n_ids is
