@@ -96,6 +96,7 @@ AMD_SYMBOLS = [
     "clip_amd_test_index_linkage_rounds",
     "clip_amd_index_linkage_core", "clip_amd_index_linkage_core_device", "clip_amd_bench_linkage_core", "clip_amd_bench_linkage_core_parts",
     "clip_amd_index_extents", "clip_amd_index_extents_device", "clip_amd_bench_extents", "clip_amd_test_index_extents_route",
+    "clip_amd_index_closest_pairs", "clip_amd_index_closest_pairs_device",
     "clip_amd_index_vote", "clip_amd_index_vote_device", "clip_amd_index_vote_ids", "clip_amd_index_vote_graph", "clip_amd_index_vote_graph_device",
     "clip_amd_test_index_vote_block", "clip_amd_bench_vote_graph",
     "clip_amd_index_rank", "clip_amd_index_rank_ids", "clip_amd_index_rank_device", "clip_amd_index_count", "clip_amd_index_count_device",
@@ -331,6 +332,10 @@ def lib():
     L.clip_amd_bench_extents.argtypes = [i32, i64, i32, i32, i32, i32]
     L.clip_amd_test_index_extents_route.restype = i64
     L.clip_amd_test_index_extents_route.argtypes = [vp, i32]
+    L.clip_amd_index_closest_pairs.restype = i64
+    L.clip_amd_index_closest_pairs.argtypes = [vp, i32, u64p, i64p, f32p, i64, i64, f32p, i64p, i64p]
+    L.clip_amd_index_closest_pairs_device.restype = C.c_bool
+    L.clip_amd_index_closest_pairs_device.argtypes = [vp, i32, vp, vp, f32p, i64, i64, vp, vp, vp, vp]
     L.clip_amd_test_index_linkage_rounds.restype = i32
     L.clip_amd_test_index_linkage_rounds.argtypes = [vp]
     L.clip_amd_index_spread.restype = i64
@@ -1547,6 +1552,59 @@ class Index:
                                                    C.c_void_p(d_centre or None), C.c_void_p(d_radius or None), C.c_void_p(d_diameter or None),
                                                    C.c_void_p(d_reach or None), C.c_void_p(d_far or None), C.c_void_p(d_count or None)):
             raise RuntimeError("clip_amd_index_extents_device failed (see stderr)")
+
+    def _closest_args(self, n, after):
+        """(n_pairs, after_distance pointer or NULL, after_lo, after_hi); ValueError for n outside 1 ... 1024 or an `after` that is no
+        (distance, lo, hi) with a distance that is not NaN and 0 <= lo < hi < len, before the library is reached"""
+        n = int(n)
+        if n < 1 or n > 1024:
+            raise ValueError("n = %d outside 1 ... 1024" % n)
+        if after is None:
+            return n, None, 0, 0
+        d, lo, hi = float(np.float32(after[0])), int(after[1]), int(after[2])
+        if d != d or not 0 <= lo < hi < len(self):
+            raise ValueError("after must be (distance, lo, hi) with 0 <= lo < hi < %d and a distance that is not NaN" % len(self))
+        return n, C.byref(C.c_float(d)), lo, hi
+
+    def closest_pairs(self, n, allow=None, labels=None, after=None):
+        """The n (1 ... 1024) closest pairs of the index: (lo int64 [m], hi int64 [m], distances f32 [m]), m <= n, the fields of `pairs`.
+        The candidates are the pairs lo < hi of eligible rows (`allow`: bool mask [len] or ids, None: every live row) with the distance
+        and bits `pairs` reports, in the order (distance, lo, hi); the result is the first n of them.  `labels` (int64 [len], each below
+        2^31): a row with a negative label is not eligible, and only pairs whose two labels differ are candidates ("the most similar
+        pictures in different folders").  `after` = (distance, lo, hi): only candidates strictly after it in that order, so the last
+        triple of one call gives the next page.  No radius is needed and nothing but the n pairs leaves the device.  ValueError for a
+        bad n, after, allow or labels before the library is reached."""
+        n, ad, alo, ahi = self._closest_args(n, after)
+        words, wp = self._allow(allow)
+        lab = None
+        if labels is not None:
+            lab = np.asarray(labels)
+            if lab.size and not np.issubdtype(lab.dtype, np.integer):
+                raise ValueError("labels must be integers, not %s" % lab.dtype)
+            lab = np.ascontiguousarray(lab, dtype=np.int64).reshape(-1)
+            if lab.size != len(self):
+                raise ValueError("labels holds %d entries, the index %d rows" % (lab.size, len(self)))
+            if lab.size and int(lab.max()) >= 2 ** 31:
+                raise ValueError("labels holds %d: a label must be below 2^31" % int(lab.max()))
+        lo = np.empty(n, dtype=np.int64)
+        hi = np.empty(n, dtype=np.int64)
+        dist = np.empty(n, dtype=np.float32)
+        i64 = C.POINTER(C.c_int64)
+        m = lib().clip_amd_index_closest_pairs(self._live(), n, wp, lab.ctypes.data_as(i64) if lab is not None else None, ad, alo, ahi, _fp(dist),
+                                               lo.ctypes.data_as(i64), hi.ctypes.data_as(i64))
+        if m < 0:
+            raise RuntimeError("clip_amd_index_closest_pairs failed (see stderr)")
+        return lo[:m].copy(), hi[:m].copy(), dist[:m].copy()
+
+    def closest_pairs_device(self, n, d_lo, d_hi, d_distances, d_count, d_allow=None, d_labels=None, after=None):
+        """closest_pairs on torch tensors on the device: lo [n] int64, hi [n] int64, distances [n] f32 (tail -1 / -1 / +inf) and count [1]
+        int64 out; d_allow: uint64 words as an int64 tensor, d_labels: int64 [len] (both trusted; None: not given); `after` as for
+        closest_pairs (host values); asynchronous on the context's stream."""
+        n, ad, alo, ahi = self._closest_args(n, after)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        if not lib().clip_amd_index_closest_pairs_device(self._live(), n, ptr(d_allow), ptr(d_labels), ad, alo, ahi, ptr(d_distances), ptr(d_lo),
+                                                         ptr(d_hi), ptr(d_count)):
+            raise RuntimeError("clip_amd_index_closest_pairs_device failed (see stderr)")
 
     def extents_route(self, route=0):
         """Test hook: route 0 skips the tile pairs that hold no two rows of one group, route 1 computes them all (the same result);

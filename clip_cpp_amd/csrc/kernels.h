@@ -533,6 +533,18 @@ bool launch_extents(const void * rows, const float * rinv, int64_t n, int Dpad, 
                     void * work, int skip, int64_t * centre, float * radius, float * diameter, float * reach, int64_t * far,
                     unsigned long long * count, hipStream_t stream);
 
+// Closest pairs over the same pairs (k_closest.hip): the first n_pairs (1 ... 1024) candidates (lo < hi, both eligible: mask as for
+// launch_components and, with labels, label >= 0; with labels [n] i64 on the device, each < 2^31: of different labels) in the order
+// (d, lo, hi); after_distance (host, may be NULL): only candidates strictly after (*after_distance, after_lo, after_hi).  distances
+// [n_pairs] f32, lo / hi [n_pairs] i64 (tail +inf / -1 / -1) and *count (may be NULL) on the device.  Workspace: work
+// [closest_work_bytes(n, dtype, n_pairs, masked)], masked = a mask or labels are given (initialised here; 4 bytes per row, 24 per tile
+// of 128 rows and, per resident workgroup of the link kernel, 4 + 12 n_pairs bytes of list and 192 KB of overflow).  n == 0 writes the
+// tail and a count of 0.  n < 2^31.
+size_t closest_work_bytes(int64_t n, int dtype, int n_pairs, bool masked);
+bool launch_closest(const void * rows, const float * rinv, int64_t n, int Dpad, int dtype, int n_pairs, const int64_t * labels,
+                    const uint32_t * mask, const float * after_distance, int64_t after_lo, int64_t after_hi, void * work, float * distances,
+                    int64_t * lo, int64_t * hi, int64_t * count, hipStream_t stream);
+
 // Farthest-first selection (k_spread.hip).  Workspaces: gap [n] f32, opos [n] i32, slot [n_slots] u64 (slot t: the key of the centre at
 // position t, 0 = empty).  init: zeroes the slots, sets gap / opos from the mask and writes the seeds' keys (seeds: device ids), or, with
 // n_seeds == 0, the lowest eligible id's into slot 0.  sweep: one pass over the gallery against the centres of slots first ... first +

@@ -7,9 +7,9 @@
 //   k_distinct.hip  distinct searches (the pools of a search, then the near bitmap and the walk)
 //   k_compound.hip  compound queries (the placement and the scan in front of the same merge tree)
 //   k_join.hip      range search and pairs (count -> lims -> scatter -> sort -> finish)
-//   k_components.hip, k_modes.hip, k_linkage.hip, k_extents.hip, k_spread.hip
+//   k_components.hip, k_modes.hip, k_linkage.hip, k_extents.hip, k_spread.hip, k_closest.hip
 //                   connected components (link -> flatten -> finish), density modes, the single-linkage tree, the extents of a
-//                   labelling, farthest-first selection
+//                   labelling, farthest-first selection, the closest pairs (prep -> link -> merge)
 //   k_vote.hip      k-NN voting over labelled rows (the voter bitmap and the fold, as the sink of search_blocks)
 //   k_rank.hip      rank and count queries (rank_blocks: key -> count -> finish per block of columns; the host arithmetic in rank_host.h)
 //   k_softmax.hip   softmax over every eligible row (softmax_blocks: the sweep and its finish as the sink of search_blocks)
@@ -1266,6 +1266,66 @@ int64_t idx::extents_host(clip_amd_index * ix, const int64_t * labels, const uin
 
 namespace {
 
+// Closest pairs on the device: d_labels [n] int64 or NULL in, n_pairs distances / lo / hi and, d_count != NULL, the count out.  Queues the
+// launches and returns; an empty index gets the tail and a count of 0.
+bool closest_impl(clip_amd_index * ix, int n_pairs, const uint32_t * d_allow, const int64_t * d_labels, const float * after_distance, int64_t after_lo,
+                  int64_t after_hi, float * d_dist, int64_t * d_lo, int64_t * d_hi, int64_t * d_count, const char * fn) {
+    const uint32_t * mask = nullptr;
+    if (!effective_mask(ix, d_allow, mask)) return false;
+    if (!ensure(ix, ix->kwork, closest_work_bytes(ix->n, ix->dtype, n_pairs, mask != nullptr || d_labels != nullptr))) return false;
+    return launched(launch_closest(ix->store.rows, ix->store.rinv, ix->n, ix->Dpad, ix->dtype, n_pairs, d_labels, mask, after_distance, after_lo,
+                                   after_hi, ix->kwork.p, d_dist, d_lo, d_hi, d_count, stream_of(ix)), fn);
+}
+
+bool check_closest_args(const clip_amd_index * ix, int n_pairs, const float * after_distance, int64_t after_lo, int64_t after_hi, const void * dist,
+                        const void * lo, const void * hi, const char * fn) {
+    if (!check_index(ix, fn)) return false;
+    if (!dist || !lo || !hi) { fprintf(stderr, "%s: distances, lo or hi is NULL\n", fn); return false; }
+    if (n_pairs < 1 || n_pairs > MAX_K) { fprintf(stderr, "%s: n_pairs = %d outside 1 ... %d\n", fn, n_pairs, MAX_K); return false; }
+    if (!after_distance) return true;
+    if (std::isnan(*after_distance)) { fprintf(stderr, "%s: after_distance is NaN\n", fn); return false; }
+    if (after_lo < 0 || after_lo >= after_hi || after_hi >= ix->n) {
+        fprintf(stderr, "%s: after (%lld, %lld) is no pair lo < hi of rows 0 ... %lld\n", fn, (long long)after_lo, (long long)after_hi, (long long)ix->n - 1);
+        return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+// The host form: a label >= 2^31 is refused before anything is queued (the kernels compare labels as i32); then the labels go up, the
+// results into their workspace and out with the count.  Returns that count or -1.
+int64_t idx::closest_host(clip_amd_index * ix, int n_pairs, const uint64_t * allow, const int64_t * labels, const float * after_distance,
+                          int64_t after_lo, int64_t after_hi, float * distances, int64_t * lo, int64_t * hi, const char * fn) {
+    const size_t n = (size_t)ix->n;
+    for (size_t x = 0; labels && x < n; x++) {
+        if (labels[x] <= INT32_MAX) continue;
+        fprintf(stderr, "%s: label %lld of row %zu is not below 2^31: nothing computed\n", fn, (long long)labels[x], x);
+        return -1;
+    }
+    if (n == 0) {                                              // no candidate: only the tail
+        std::fill(distances, distances + n_pairs, INFINITY);
+        std::fill(lo, lo + n_pairs, (int64_t)-1);
+        std::fill(hi, hi + n_pairs, (int64_t)-1);
+        return 0;
+    }
+    const uint32_t * d_allow = nullptr;
+    int64_t count = 0;
+    Arena a(ix);
+    const auto o_count = a.add(&count, 1);
+    const auto i_labels = a.add<int64_t>(nullptr, labels ? n : 0);      // an input: it goes up and does not come back
+    const auto o_dist = a.add(distances, (size_t)n_pairs);
+    const auto o_lo = a.add(lo, (size_t)n_pairs), o_hi = a.add(hi, (size_t)n_pairs);
+    if (!upload_allow(ix, allow, d_allow) || !a.ready()) return -1;
+    if (labels) (void)hipMemcpyAsync(a.dev(i_labels, true), labels, n * 8, hipMemcpyHostToDevice, stream_of(ix));
+    if (!closest_impl(ix, n_pairs, d_allow, labels ? a.dev(i_labels, true) : nullptr, after_distance, after_lo, after_hi, a.dev(o_dist), a.dev(o_lo),
+                      a.dev(o_hi), a.dev(o_count), fn))
+        return -1;
+    return a.fetch(fn) ? count : -1;
+}
+
+namespace {
+
 // reach of a key slot of k_spread.hip on the host (nearest_key.h's ordered_value)
 float spread_slot_reach(unsigned long long key) {
     uint32_t u = (uint32_t)(key >> 32);
@@ -2486,6 +2546,26 @@ bool clip_amd_index_extents_device(struct clip_amd_index * ix, const int64_t * d
             return true;
         }
         return extents_impl(ix, d_labels, (const uint32_t *)d_allow, d_centre, d_radius, d_diameter, d_reach, d_far, (unsigned long long *)d_count, fn);
+    });
+}
+
+int64_t clip_amd_index_closest_pairs(struct clip_amd_index * ix, int n_pairs, const uint64_t * allow, const int64_t * labels,
+                                     const float * after_distance, int64_t after_lo, int64_t after_hi, float * distances, int64_t * lo, int64_t * hi) {
+    return guarded(__func__, (int64_t)-1, [&](const char * fn) -> int64_t {
+        if (!check_closest_args(ix, n_pairs, after_distance, after_lo, after_hi, distances, lo, hi, fn)) return -1;
+        (void)hipSetDevice(ix->device);
+        return closest_host(ix, n_pairs, allow, labels, after_distance, after_lo, after_hi, distances, lo, hi, fn);
+    });
+}
+
+bool clip_amd_index_closest_pairs_device(struct clip_amd_index * ix, int n_pairs, const uint64_t * d_allow, const int64_t * d_labels,
+                                         const float * after_distance, int64_t after_lo, int64_t after_hi, float * d_distances, int64_t * d_lo,
+                                         int64_t * d_hi, int64_t * d_count) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_closest_args(ix, n_pairs, after_distance, after_lo, after_hi, d_distances, d_lo, d_hi, fn)) return false;
+        if (!d_count) { fprintf(stderr, "%s: d_count is NULL\n", fn); return false; }
+        (void)hipSetDevice(ix->device);
+        return closest_impl(ix, n_pairs, (const uint32_t *)d_allow, d_labels, after_distance, after_lo, after_hi, d_distances, d_lo, d_hi, d_count, fn);
     });
 }
 

@@ -85,6 +85,8 @@ struct clip_amd_index {
     // extents of a labelling
     Buf ework;                     // member bitmap, label ranges, reach keys, per-label slots and i32 labels (extents_work_bytes)
     int extents_route = 0;         // clip_amd_test_index_extents_route: 0 tile skip on, 1 every tile pair computed
+    // closest pairs
+    Buf kwork;                     // bound, eligibility bitmap, label ranges, i32 labels, per-workgroup lists and overflow (closest_work_bytes)
     // farthest-first selection
     Buf sgap;                      // [n] distance to the nearest centre so far (f32)
     Buf sopos;                     // [n] position of that centre (i32)
@@ -262,6 +264,8 @@ int64_t linkage_host(clip_amd_index * ix, int k, float link, const uint64_t * al
                      const char * fn);
 int64_t extents_host(clip_amd_index * ix, const int64_t * labels, const uint64_t * allow, int64_t * centre, float * radius, float * diameter,
                      float * reach, int64_t * far, const char * fn);
+int64_t closest_host(clip_amd_index * ix, int n_pairs, const uint64_t * allow, const int64_t * labels, const float * after_distance, int64_t after_lo,
+                     int64_t after_hi, float * distances, int64_t * lo, int64_t * hi, const char * fn);
 bool spread_impl(clip_amd_index * ix, int64_t n_max, float stop, const int64_t * seeds, int64_t n_seeds, const uint32_t * d_allow,
                  int64_t * d_centres, float * d_reach, int64_t * d_owner, float * d_odist, float * d_cover, int64_t * d_count, bool poll,
                  const char * fn);

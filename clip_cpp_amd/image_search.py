@@ -17,6 +17,7 @@ build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.In
     python -m clip_cpp_amd.image_search match  [-m MODEL] [-v N] [-t N] [--db DIR] [-n N] [INDEXED/IMAGE/PATH or /path/to/query/image]
     python -m clip_cpp_amd.image_search file   [-m MODEL] [-v N] [-t N] [--db DIR] [-k K] [-n N] [--labels FILE] [--in PREFIX]... IMAGE [IMAGE ...]
     python -m clip_cpp_amd.image_search audit  [-m MODEL] [-v N] [--db DIR] [-k K] [--labels FILE] [--in PREFIX]...
+    python -m clip_cpp_amd.image_search closest [-m MODEL] [-v N] [--db DIR] [-n N] [--in PREFIX]... [--across] [--labels FILE]
 
 `build` writes DIR/images.index (the CLIPIDX1 file of clip_amd_index_save) and DIR/images.paths (the reference's layout: the model path
 on the first line, then one image path per id).  `search` prints the reference's output: "search results:" / "distance path" at
@@ -135,6 +136,13 @@ pictures lie in the wrong folder?" (one Index.vote_graph call; no image is decod
 every labelled image whose winning class is not its own, in id order, "  %d/%d %f %s -> %s ~ %s": the winner's votes, voters counted, the
 distance of the winner's nearest member, the image's path, the winning class and that member's path; then
 "main: %d labelled images, %d filed against their neighbours, %d with no voter".  Neither supports a database built with --grid.
+
+`closest` answers "which are the most similar pairs of images I have?" without a radius (Index.closest_pairs; nothing is decoded or
+encoded): "closest:" at verbosity > 0, then the -n N (default 50) closest pairs, nearest first, as "%f<TAB>%s<TAB>%s": the distance and
+the two paths, the image indexed first on the left; then "main: %d pairs".  --in PREFIX restricts it to the matching images.  --across
+(implied by --labels FILE) lists only pairs from different folders, with the labelling of `file` / `audit`: the directory part of a path,
+or the label the file gives it; an image the file does not list takes no part.  N above 1024 is served in pages of 1024 (each call
+continues after the last pair of the one before).  It does not support a database built with --grid.
 """
 import ctypes as C
 import os
@@ -1661,6 +1669,98 @@ def audit(argv):
     return 0
 
 
+CLOSEST_PAIRS = 50  # pairs `closest` prints by default
+
+
+def _help_closest(p):
+    print("Usage: python -m clip_cpp_amd.image_search closest [options]")
+    print("\nLists the most similar pairs of images of an index built by `build`, nearest first, as `distance<TAB>path<TAB>path`: no radius")
+    print("to guess (Index.closest_pairs, a selection over all pairs on the GPU; no image is decoded or encoded).")
+    print("\nOptions:")
+    print("  -h, --help: Show this message and exit")
+    print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default.")
+    print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
+    print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
+    print("  -n N, --results N: pairs printed. Default: %d" % p["results"])
+    print("  --in PREFIX: only images whose path starts with PREFIX take part. Repeatable.")
+    print("  --across: only pairs of images from different folders (the directory part of their paths)")
+    print("  --labels FILE: lines `label<TAB>path` instead of the folders (implies --across): only pairs of listed images with different labels.")
+    print("      A path that is not in the database is an error.")
+
+
+def _parse_closest(argv):
+    """The options of `closest`; None when they do not parse."""
+    p = dict(verbose=1, db=".", model="", results=CLOSEST_PAIRS, labels=None, across=False)
+    p["in"] = []
+    takes = {"-m": "model", "--model": "model", "-v": "verbose", "--verbose": "verbose", "--db": "db", "-n": "results", "--results": "results",
+             "--labels": "labels", "--in": "in"}
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a in takes:
+            i += 1
+            if i >= len(argv):
+                return None
+            key = takes[a]
+            if key == "in":
+                p["in"].append(argv[i])
+            else:
+                try:
+                    p[key] = int(argv[i]) if key in ("verbose", "results") else argv[i]
+                except ValueError:
+                    return None
+        elif a == "--across":
+            p["across"] = True
+        elif a in ("-h", "--help"):
+            _help_closest(p)
+            sys.exit(0)
+        else:
+            print("main: %s argument: %s" % ("unrecognized" if a.startswith("-") else "unexpected", a))
+            return None
+        i += 1
+    if p["results"] < 1:
+        print("main: -n %d: closest prints at least one pair" % p["results"])
+        return None
+    return p
+
+
+def closest(argv):
+    import clip_cpp_amd
+    p = _parse_closest(argv)
+    if p is None:
+        _help_closest(dict(verbose=1, db=".", results=CLOSEST_PAIRS))
+        return 1
+    opened = _open_votes(p, "closest")
+    if opened is None:
+        return 1
+    image_paths, labels, _, allow = opened
+    if not p["across"] and p["labels"] is None:
+        labels = None
+    try:
+        clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])      # only the index's device: no image is encoded
+    except RuntimeError:
+        print("main: Unable to load model from %s" % p["model"])
+        return 1
+    index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
+    if p["verbose"] > 0:
+        print("closest:")
+    printed, after = 0, None
+    while printed < p["results"]:                              # pages of at most MAX_K pairs, each after the last pair of the one before
+        want = min(MAX_K, p["results"] - printed)
+        lo, hi, d = index.closest_pairs(want, allow=allow, labels=labels, after=after)
+        for a, b, dist in zip(lo, hi, d):
+            print("%f\t%s\t%s" % (dist, image_paths[a], image_paths[b]))
+        printed += len(lo)
+        if len(lo) < want:
+            break
+        after = (d[-1], lo[-1], hi[-1])
+    print("main: %d pairs" % printed)
+    sys.stdout.flush()
+    index.close()
+    clip.close()
+    return 0
+
+
 EVAL_BATCH = 256    # captions per pass of the text tower in `eval`
 
 
@@ -2012,7 +2112,8 @@ def match(argv):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     commands = {"build": build, "update": update, "search": search, "dedup": dedup, "neighbors": neighbors, "label": label, "merge": merge, "match": match,
-                "albums": albums, "spread": spread, "groups": groups, "levels": levels, "file": file_images, "audit": audit, "eval": evaluate}
+                "albums": albums, "spread": spread, "groups": groups, "levels": levels, "file": file_images, "audit": audit, "eval": evaluate,
+                "closest": closest}
     if not argv or argv[0] not in commands:
         print("Usage: python -m clip_cpp_amd.image_search {build|search|dedup} [options] ...  (-h after the command for its options)")
         print("       python -m clip_cpp_amd.image_search update [options] dir [more dirs]  (an existing database brought in line with the disk)")
@@ -2026,6 +2127,7 @@ def main(argv=None):
         print("       python -m clip_cpp_amd.image_search match [options] [IMAGE]  (a --grid database: the images that share a region with IMAGE, or with each other)")
         print("       python -m clip_cpp_amd.image_search file [options] IMAGE [IMAGE ...]  (into which of your folders each IMAGE goes: its nearest labelled images vote)")
         print("       python -m clip_cpp_amd.image_search audit [options]  (the indexed images that lie in the wrong folder, by the vote of their neighbours)")
+        print("       python -m clip_cpp_amd.image_search closest [options]  (the most similar pairs of indexed images, nearest first; --across: from different folders)")
         print("       python -m clip_cpp_amd.image_search eval [options] PAIRS  (recall@K, median rank and MRR of caption<TAB>path pairs: is this model file good enough?)")
         return 1
     return commands[argv[0]](argv[1:])

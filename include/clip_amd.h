@@ -771,6 +771,34 @@ float clip_amd_bench_extents(int dtype, int64_t n, int dim, int group_size, int 
  * the results are the same, bit for bit.  Returns the number of tile pairs the index's last clip_amd_index_extents call (either form; the
  * stream is waited for) computed, 0 before the first; -1 for a NULL index or another route.  Used by tests/. */
 int64_t clip_amd_test_index_extents_route(struct clip_amd_index * ix, int route);
+/* The closest pairs of the index: "the n_pairs most similar pairs of images I have", with no radius to guess and nothing but the answer
+ * leaving the device.
+ * A row is ELIGIBLE when it is live and set in allow (layout as live_mask, NULL = every live row) and, with labels, its label is >= 0.
+ * labels [size] int64, may be NULL; every label must be < 2^31.  A CANDIDATE is a pair (lo, hi), lo < hi, of eligible rows; with labels
+ * only when labels[lo] != labels[hi] ("pictures in different folders").  d(lo, hi) is bit for bit the distance clip_amd_index_pairs
+ * reports for that pair; a pair whose distance is NaN is not a pair, as in pairs.  Candidates are ordered by (d, lo, hi) ascending, a total
+ * order.  The result is the first n_pairs (1 ... 1024, the limit of search's k) candidates in that order; with after_distance != NULL
+ * (a host value in both forms) only candidates strictly after (*after_distance, after_lo, after_hi) count, which is the next page.
+ * distances / lo / hi [n_pairs].  The host form returns the number of pairs written, m <= n_pairs; slots m ... n_pairs - 1 hold
+ * +INFINITY / -1 / -1.  An empty index, or one with no candidate, returns 0 and writes only that tail.  The device form writes m to
+ * d_count (int64).
+ * -1 / false with a message on stderr, nothing launched and no output written, for a NULL index, a NULL output (the device form: d_count
+ * too), n_pairs outside 1 ... 1024, a NaN *after_distance, after_lo >= after_hi or either outside [0, size) when after_distance is given
+ * and, in the host form, a label >= 2^31.
+ * Results are bit-identical run to run, however rows were split across add calls and across save / load, and do not depend on the order
+ * of any atomic or on which workgroup computed which tile (a shared bound only ever removes pairs that cannot be in the answer; there is
+ * no float sum); over the eligible rows they are those of an index to which only those rows were ever added, with ids mapped in order.
+ * Equivalently: pairs(4.0) restricted to eligible rows and by labels, sorted by (d, lo, hi) and cut to n_pairs.
+ * Host form: host arrays, synchronous on the ctx stream.  Device form: allow, labels (both trusted) and the outputs in HBM, asynchronous
+ * on the ctx stream, synchronises with nothing on the host.
+ * Cost: one sweep over the tile pairs (128 x 128 rows) of eligible rows; with labels a tile pair whose two tiles hold one and the same
+ * single label is skipped.  Device memory beyond the index: 4 bytes per row and, per CU, 12 n_pairs bytes + 192 KB. */
+int64_t clip_amd_index_closest_pairs(struct clip_amd_index * ix, int n_pairs, const uint64_t * allow, const int64_t * labels,
+                                     const float * after_distance, int64_t after_lo, int64_t after_hi, float * distances, int64_t * lo,
+                                     int64_t * hi);
+bool clip_amd_index_closest_pairs_device(struct clip_amd_index * ix, int n_pairs, const uint64_t * d_allow, const int64_t * d_labels,
+                                         const float * after_distance, int64_t after_lo, int64_t after_hi, float * d_distances, int64_t * d_lo,
+                                         int64_t * d_hi, int64_t * d_count);
 /* Farthest-first selection (greedy k-center): n_max rows that between them cover the index, each picked as the row farthest from
  * everything chosen before it.  Every prefix of the result is a 2-approximate k-center solution, and reach[t] is the coverage radius of
  * the prefix before position t, so one call gives the table of "how many rows" against "how far is everything else".
