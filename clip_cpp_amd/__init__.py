@@ -102,6 +102,8 @@ AMD_SYMBOLS = [
     "clip_amd_index_rank", "clip_amd_index_rank_ids", "clip_amd_index_rank_device", "clip_amd_index_count", "clip_amd_index_count_device",
     "clip_amd_bench_rank", "clip_amd_bench_rank_parts",
     "clip_amd_index_softmax", "clip_amd_index_softmax_device", "clip_amd_index_softmax_ids", "clip_amd_index_softmax_index", "clip_amd_bench_softmax",
+    "clip_amd_index_search_biased", "clip_amd_index_search_biased_device", "clip_amd_index_search_ids_biased", "clip_amd_index_hubness",
+    "clip_amd_index_hubness_device", "clip_amd_bench_search_biased",
 ]
 
 _lib = None
@@ -428,6 +430,18 @@ def lib():
     L.clip_amd_index_softmax_index.argtypes = [vp, vp, i64p, i64, i32, C.c_float, u64p, f32p, i64p, f32p, f32p]
     L.clip_amd_bench_softmax.restype = C.c_float
     L.clip_amd_bench_softmax.argtypes = [i32, i64, i32, i32, i32, i32]
+    L.clip_amd_index_search_biased.restype = C.c_bool
+    L.clip_amd_index_search_biased.argtypes = [vp, f32p, i32, i32, f32p, u64p, f32p, f32p, i64p]
+    L.clip_amd_index_search_biased_device.restype = C.c_bool
+    L.clip_amd_index_search_biased_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.clip_amd_index_search_ids_biased.restype = C.c_bool
+    L.clip_amd_index_search_ids_biased.argtypes = [vp, i64p, i32, i32, i32, f32p, u64p, f32p, f32p, i64p]
+    L.clip_amd_index_hubness.restype = C.c_bool
+    L.clip_amd_index_hubness.argtypes = [vp, vp, i32, i32, C.c_float, u64p, f32p]
+    L.clip_amd_index_hubness_device.restype = C.c_bool
+    L.clip_amd_index_hubness_device.argtypes = [vp, vp, i32, i32, C.c_float, vp, vp]
+    L.clip_amd_bench_search_biased.restype = C.c_float
+    L.clip_amd_bench_search_biased.argtypes = [i32, i64, i32, i32, i32, i32]
     L.clip_amd_index_search_index.restype = C.c_bool
     L.clip_amd_index_search_index.argtypes = [vp, vp, i64p, i64, i32, u64p, f32p, i64p]
     L.clip_amd_index_append.restype = i64
@@ -1997,6 +2011,69 @@ class Index:
             raise RuntimeError("clip_amd_index_append failed (see stderr)")
         return new_ids
 
+    def _bias(self, bias):
+        """(keep-alive array, pointer) of a bias column float32 [len]; (None, NULL) for None"""
+        if bias is None:
+            return None, None
+        b = np.ascontiguousarray(bias, dtype=np.float32).reshape(-1)
+        if b.size != len(self):
+            raise ValueError("bias holds %d values, the index %d rows" % (b.size, len(self)))
+        return b, _fp(b)
+
+    def search_biased(self, queries, k, bias, allow=None):
+        """(distances f32 [nq, k], scores f32 [nq, k], ids int64 [nq, k]): the k best rows by score = distance + bias[row] (one f32 add on
+        search's distance), equal scores lower id first; `bias` float32 [len] (None: zeros, then this is search and scores == distances),
+        finite at every live row.  distances are the plain distances of the reported pairs, with search's bits.  With the column of
+        `hubness` this is CSLS / inverted-softmax retrieval; any per-row prior works the same way."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        nq = q.shape[0]
+        words, wp = self._allow(allow)
+        b, bp = self._bias(bias)
+        dist = np.empty((nq, k), dtype=np.float32)
+        scores = np.empty((nq, k), dtype=np.float32)
+        ids = np.empty((nq, k), dtype=np.int64)
+        if not lib().clip_amd_index_search_biased(self._live(), _fp(q), nq, int(k), bp, wp, _fp(dist), _fp(scores), ids.ctypes.data_as(C.POINTER(C.c_int64))):
+            raise RuntimeError("clip_amd_index_search_biased failed (see stderr)")
+        return dist, scores, ids
+
+    def search_ids_biased(self, ids, k, bias, exclude_self=True, allow=None):
+        """search_biased with the stored rows `ids` as the queries, as search_ids takes them"""
+        a = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        words, wp = self._allow(allow)
+        b, bp = self._bias(bias)
+        dist = np.empty((a.size, k), dtype=np.float32)
+        scores = np.empty((a.size, k), dtype=np.float32)
+        out = np.empty((a.size, k), dtype=np.int64)
+        if not lib().clip_amd_index_search_ids_biased(self._live(), a.ctypes.data_as(C.POINTER(C.c_int64)), a.size, int(k), int(bool(exclude_self)), bp, wp,
+                                                      _fp(dist), _fp(scores), out.ctypes.data_as(C.POINTER(C.c_int64))):
+            raise RuntimeError("clip_amd_index_search_ids_biased failed (see stderr)")
+        return dist, scores, out
+
+    def search_biased_device(self, d_queries, n_queries, k, d_bias, d_distances, d_scores, d_ids, d_allow=None):
+        """search_biased on device pointers (ints): queries [n, dim] f32, bias [len] f32 (0 / None: zeros; not checked: +inf drops a row) ->
+        distances, scores [n, k] f32, ids [n, k] int64; asynchronous on the context's stream."""
+        if not lib().clip_amd_index_search_biased_device(self._live(), C.c_void_p(d_queries), int(n_queries), int(k), C.c_void_p(d_bias or None),
+                                                         C.c_void_p(d_allow or None), C.c_void_p(d_distances), C.c_void_p(d_scores), C.c_void_p(d_ids)):
+            raise RuntimeError("clip_amd_index_search_biased_device failed (see stderr)")
+
+    HUBNESS_MODES = {"csls": 0, "softmax": 1}
+
+    def hubness(self, bank, mode="csls", k=10, scale=100.0, allow=None):
+        """The bias column float32 [len] that corrects hubness, from `bank`, an Index (same Clip, dim, dtype) of typical queries.  "csls":
+        -1/2 the mean distance of a row to its k nearest bank rows; "softmax": log Z of the row over the bank at `scale`, / scale (the
+        inverted softmax of Querybank Normalisation).  Rows removed or outside `allow` get 0; an empty bank gives zeros."""
+        words, wp = self._allow(allow)
+        bias = np.empty(len(self) + 1, dtype=np.float32)[:len(self)]
+        if not lib().clip_amd_index_hubness(self._live(), bank._live(), self.HUBNESS_MODES[mode], int(k), float(scale), wp, _fp(bias)):
+            raise RuntimeError("clip_amd_index_hubness failed (see stderr)")
+        return bias
+
+    def hubness_device(self, bank, d_bias, mode="csls", k=10, scale=100.0, d_allow=None):
+        """hubness into the f32 [len] at device address d_bias; d_allow uint64 words (0 / None: every row); asynchronous on the context's stream."""
+        if not lib().clip_amd_index_hubness_device(self._live(), bank._live(), self.HUBNESS_MODES[mode], int(k), float(scale), C.c_void_p(d_allow or None),
+                                                   C.c_void_p(d_bias or None)):
+            raise RuntimeError("clip_amd_index_hubness_device failed (see stderr)")
+
     def search_device(self, d_queries, n_queries, k, d_distances, d_ids):
         """Device pointers (ints): queries [n, dim] f32 -> distances [n, k] f32, ids [n, k] int64; asynchronous on the context's stream."""
         if not lib().clip_amd_index_search_device(self._live(), C.c_void_p(d_queries), int(n_queries), int(k), C.c_void_p(d_distances),
@@ -2033,6 +2110,12 @@ class Index:
 def bench_search(dtype, n, dim, n_queries, k, iters=10):
     """Microseconds per clip_amd_index_search_device on seeded random data (clip_amd_bench_search); < 0 on error."""
     return float(lib().clip_amd_bench_search(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(k), int(iters)))
+
+
+def bench_search_biased(dtype, n, dim, n_queries, k, iters=10):
+    """Microseconds per biased search on the data of bench_search with a seeded random bias in [-0.3, 0.3), the column already on the
+    device (clip_amd_bench_search_biased); < 0 on error."""
+    return float(lib().clip_amd_bench_search_biased(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(k), int(iters)))
 
 
 def bench_search_grouped(dtype, n, dim, n_queries, k, group_size, iters=10):

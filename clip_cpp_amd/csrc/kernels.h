@@ -354,6 +354,7 @@ struct ScanArgs {
     const int * qself = nullptr;
     const int * groups = nullptr;
     const int * qgroup = nullptr;
+    const float * bias = nullptr;      // launch_bias_scan only: [n rounded up to 64] one f32 per stored row
 };
 bool launch_search_scan(const ScanArgs & a, hipStream_t stream);
 void launch_search_merge(const void * in, int64_t in_stride, int n_in, void * out, int nq, int k, hipStream_t stream);
@@ -436,6 +437,20 @@ struct SoftmaxArgs {
 bool launch_softmax_sweep(const SoftmaxArgs & a, hipStream_t stream);
 void launch_softmax_finish(const float * part, int n_chunks, int ncols, int k, float beta, const float * din, const int64_t * iin, float * dist,
                            int64_t * ids, float * probs, float * log_z, hipStream_t stream);
+// Biased search (k_bias.hip).  scan: launch_search_scan's plain scan (groups / qgroup unused) ranking by distance + a.bias[row], one f32
+// addition; the candidates hold (score, id), so launch_search_merge follows unchanged.  finish: the merge tree's lists (in, `in_stride` pairs
+// apart; nq * k >= 1 slots, the index not empty) -> scores / dist / ids [nq][k]: the score as ranked, the plain distance of the pair computed
+// again on the MFMA from the stored rows and the pass's prepared queries q / qinv (search's bits), ids widened; empty slots and every slot
+// of a query flagged qself < 0: +inf / +inf / -1.  fold: the bias column of the gallery rows row0 ... row0 + m - 1 from a block of bank
+// results (mode 0: dist / ids [m][k], -0.5 x the mean of the present slots, 0 without one; mode 1: log_z [m] / scale); a row whose bit in
+// mask (NULL: every row) is clear gets 0.  zero: x[lo ... hi) := 0.
+bool launch_bias_scan(const ScanArgs & a, hipStream_t stream);
+void launch_bias_finish(const void * in, int64_t in_stride, int nq, int k, const void * rows, const float * rinv, int Dpad, int dtype,
+                        const void * q, const float * qinv, const int * qself, float * scores, float * dist, int64_t * ids,
+                        hipStream_t stream);
+void launch_bias_fold(int mode, const float * dist, const int64_t * ids, const float * log_z, int64_t row0, int m, int k, float scale,
+                      const uint32_t * mask, float * bias, hipStream_t stream);
+void launch_bias_zero(float * x, int64_t lo, int64_t hi, hipStream_t stream);
 // Searches by id.  gather: query t of n_rows (the padded count) := stored row ids[t] (device; NULL: row first + t) for t < n_ids, bit for bit
 // (i8: qinv[t] := rinv of that row), qself[t] := that id; an id outside [0, n) or with a cleared bit in live, and every t >= n_ids, gives the
 // zero row and qself -1.  launch_search_scan with qself != NULL never makes row qself[query] a candidate of that query; launch_search_finish

@@ -307,9 +307,11 @@ struct idx::SetFold {
 };
 
 // d_groups (vector queries, or query sets): one group per stored row, the grouped scan and merge in the place of the plain ones.  fold
-// (query sets): every pass ends in the set fold instead of the finish, and d_dist / d_ids are not used.
+// (query sets): every pass ends in the set fold instead of the finish, and d_dist / d_ids are not used.  biased (plain searches only):
+// the scan and the finish of k_bias.hip in the place of the plain ones, ranking by distance + bias; the scores go to biased->d_scores
+// (never with an empty index: biased_device sends that to the plain search).
 bool idx::search_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, int k, const uint32_t * d_allow, float * d_dist, int64_t * d_ids,
-                             const int * d_groups, const SetFold * fold) {
+                             const int * d_groups, const SetFold * fold, const BiasedCall * biased) {
     hipStream_t st = stream_of(ix);
     if (nq == 0) return true;
     if (ix->n == 0) {
@@ -354,11 +356,18 @@ bool idx::search_device_impl(clip_amd_index * ix, const QuerySource & src, int n
         a.qself = src.exclude_self ? qself : nullptr;
         a.groups = d_groups;
         a.qgroup = own ? (const int *)ix->qgroup.p : nullptr;
-        if (!launch_search_scan(a, st)) {
+        a.bias = biased ? biased->d_bias : nullptr;
+        if (!(biased ? launch_bias_scan(a, st) : launch_search_scan(a, st))) {
             fprintf(stderr, "clip_amd_index_search: scan launch failed\n");
             return false;
         }
-        if (fold) {
+        if (biased) {
+            const void * in = nullptr;
+            int64_t stride = 0;
+            if (!merge_tree(ix, n_chunks, m, k, nullptr, in, stride)) return false;
+            launch_bias_finish(in, stride, m, k, a.rows, a.rinv, a.Dpad, a.dtype, a.q, a.qinv, qself, biased->d_scores + (size_t)q0 * k,
+                               d_dist + (size_t)q0 * k, d_ids + (size_t)q0 * k, st);
+        } else if (fold) {
             // the sets with a row in [q0, q0 + m): from the first that ends after q0 to the last that starts before q0 + m
             const int64_t * L = fold->lims;
             const int64_t s_lo = std::upper_bound(L + 1, L + fold->n_sets + 1, (int64_t)q0) - (L + 1);
@@ -2706,6 +2715,182 @@ bool clip_amd_index_search_index(struct clip_amd_index * ix, struct clip_amd_ind
             }
         (void)hipSetDevice(ix->device);
         return search_index_impl(ix, src, ids, nq, k, allow, distances, out_ids, fn);
+    });
+}
+
+}  // extern "C"
+
+// The call's bias column in the index's padded workspace (n rounded up to 64 floats, as rinv is kept: the scan loads four at a time
+// without a bounds test): bias [n] from the host or the device, the padding zeroed.  d_bias: the workspace.
+bool idx::stage_bias(clip_amd_index * ix, const float * bias, bool on_host, const float *& d_bias) {
+    const int64_t padded = (ix->n + 63) / 64 * 64;
+    if (!ensure(ix, ix->bias, (size_t)padded * sizeof(float))) return false;
+    (void)hipMemcpyAsync(ix->bias.p, bias, (size_t)ix->n * sizeof(float), on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream_of(ix));
+    launch_bias_zero((float *)ix->bias.p, ix->n, padded, stream_of(ix));
+    d_bias = (const float *)ix->bias.p;
+    return hipGetLastError() == hipSuccess;
+}
+
+namespace {
+
+// A host bias column may hold no NaN and no infinity at a live row (a removed row's entry is never read as a candidate's)
+bool check_host_bias(clip_amd_index * ix, const float * bias, const char * fn) {
+    std::vector<uint32_t> live;
+    if (ix->removed > 0) {
+        live.resize(live_bytes(ix->n) / 4);
+        if (!stream_done(ix, fn, hipMemcpyAsync(live.data(), ix->store.live, live.size() * 4, hipMemcpyDeviceToHost, stream_of(ix)))) return false;
+    }
+    for (int64_t r = 0; r < ix->n; r++)
+        if (!std::isfinite(bias[r]) && (live.empty() || ((live[(size_t)(r >> 5)] >> (int)(r & 31)) & 1u))) {
+            fprintf(stderr, "%s: bias[%lld] = %g is not finite: nothing searched\n", fn, (long long)r, (double)bias[r]);
+            return false;
+        }
+    return true;
+}
+
+// The biased searches on the device, all of them: src names the queries, bias (NULL: all zeros) is [n] on the host or on the device.
+// NULL runs the plain search and copies its distances: search_subset's bits, scores == distances.
+bool biased_device(clip_amd_index * ix, const QuerySource & src, int nq, int k, const float * bias, bool bias_on_host, const uint32_t * d_allow,
+                   float * d_dist, float * d_scores, int64_t * d_ids) {
+    if (!bias || ix->n == 0) {
+        if (!search_device_impl(ix, src, nq, k, d_allow, d_dist, d_ids)) return false;
+        return hipMemcpyAsync(d_scores, d_dist, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToDevice, stream_of(ix)) == hipSuccess;
+    }
+    BiasedCall b;
+    b.d_scores = d_scores;
+    return stage_bias(ix, bias, bias_on_host, b.d_bias) && search_device_impl(ix, src, nq, k, d_allow, d_dist, d_ids, nullptr, nullptr, &b);
+}
+
+// The host forms: queries (f32 rows) or ids (stored rows) staged as one block, the three results through the results arena
+bool biased_host(clip_amd_index * ix, const float * queries, const int64_t * ids, int nq, int k, bool exclude_self, const float * bias,
+                 const uint64_t * allow, float * distances, float * scores, int64_t * out_ids, const char * fn) {
+    if (nq == 0) return true;
+    if (ids && !check_stored_ids(ix, ids, nq, fn)) return false;
+    if (bias && !check_host_bias(ix, bias, fn)) return false;
+    const size_t count = (size_t)nq * k;
+    const uint32_t * d_allow = nullptr;
+    Arena a(ix);
+    const auto o_ids = a.add(out_ids, count);
+    const auto o_dist = a.add(distances, count), o_scores = a.add(scores, count);
+    if (!reserve_stage(ix, queries, ids, nq) || !a.ready() || !upload_allow(ix, allow, d_allow)) return false;
+    return biased_device(ix, stage_block(ix, queries, ids, 0, nq, exclude_self), nq, k, bias, true, d_allow, a.dev(o_dist), a.dev(o_scores),
+                         a.dev(o_ids)) &&
+           a.fetch(fn);
+}
+
+bool check_biased_args(const clip_amd_index * ix, const void * q, int nq, int k, const void * dist, const void * scores, const void * ids,
+                       const char * fn) {
+    if (!check_search_args(ix, q, nq, k, dist, ids, fn)) return false;
+    if (nq > 0 && !scores) { fprintf(stderr, "%s: NULL queries or result pointer\n", fn); return false; }
+    return true;
+}
+
+// The bias column of clip_amd_index_hubness on the device: every row of ix, in blocks, as the queries of a search of `bank` on the routes
+// of clip_amd_index_search_index (mode 0) / clip_amd_index_softmax_index (mode 1), each block ending in launch_bias_fold, which writes 0
+// for a row of ix that is removed or outside d_allow whatever the block holds for it.  d_out [n].
+bool hubness_impl(clip_amd_index * ix, clip_amd_index * bank, int mode, int k, float scale, const uint32_t * d_allow, float * d_out, const char * fn) {
+    hipStream_t st = stream_of(ix);
+    const int64_t n = ix->n;
+    if (n == 0) return true;
+    if (bank->n - bank->removed == 0) {                        // an empty bank: no neighbour, no sum
+        launch_bias_zero(d_out, 0, n, st);
+        return launched(true, fn);
+    }
+    const uint32_t * gmask = nullptr;                          // the rows of ix that get a value
+    const uint32_t * bmask = nullptr;                          // the rows of the bank the tiled kernel may score
+    if (!effective_mask(ix, d_allow, gmask) || !effective_mask(bank, nullptr, bmask)) return false;
+    const int kk = mode == 0 ? k : 1;
+    const int64_t block = mode == 0 ? query_block(n, kk, 12) : softmax_block(n, kk);
+    const GraphPlan p = graph_plan(bank, kk, bank->cross_route, n >= CROSS_TILED_MIN_QUERIES, block, block);
+    const auto source = [&](int64_t q0, int) { return stored_rows(nullptr, q0, false, ix); };
+    const auto tiled = [&](int64_t q0, int m) {
+        return launch_graph_cross(bank->store.rows, bank->store.rinv, bank->n, ix->store.rows, ix->store.rinv, n, q0, m, bank->Dpad, bank->dtype, kk,
+                                  bank->cand.p, p.n_chunks, p.rpc, bmask, st);
+    };
+    if (mode == 0)
+        return search_blocks(bank, n, kk, p, nullptr, fn, source, tiled, [&](int64_t q0, int m, const float * d_dist, const int64_t * d_ids) {
+            launch_bias_fold(0, d_dist, d_ids, nullptr, q0, m, kk, 0.f, gmask, d_out, st);
+            return launched(true, fn);
+        });
+    Arena a(bank);
+    const auto o_ids = a.add<int64_t>(nullptr, (size_t)block);
+    const auto o_dist = a.add<float>(nullptr, (size_t)block), o_probs = a.add<float>(nullptr, (size_t)block), o_logz = a.add<float>(nullptr, (size_t)block);
+    if (!a.ready()) return false;
+    SoftmaxOut d;
+    d.dist = a.dev(o_dist, true);
+    d.ids = a.dev(o_ids, true);
+    d.probs = a.dev(o_probs, true);
+    d.log_z = a.dev(o_logz, true);
+    return softmax_blocks(
+        bank, n, kk, scale, p, nullptr, fn, source, tiled, [&](int64_t) { return d; },
+        [&](int64_t q0, int m) {
+            launch_bias_fold(1, nullptr, nullptr, d.log_z, q0, m, kk, scale, gmask, d_out, st);
+            return launched(true, fn);
+        });
+}
+
+bool check_hubness_args(const clip_amd_index * ix, const clip_amd_index * bank, int mode, int k, float scale, const void * bias, const char * fn) {
+    if (!ix || !bank) { fprintf(stderr, "%s: %s is NULL\n", fn, ix ? "bank" : "index"); return false; }
+    if (ix->ctx != bank->ctx) { fprintf(stderr, "%s: the two indexes belong to different contexts (%p and %p)\n", fn, (void *)ix->ctx, (void *)bank->ctx); return false; }
+    if (ix->dim != bank->dim) { fprintf(stderr, "%s: bank holds %d-dimensional rows, the index %d-dimensional ones\n", fn, bank->dim, ix->dim); return false; }
+    if (ix->dtype != bank->dtype) { fprintf(stderr, "%s: bank has dtype %d, the index dtype %d\n", fn, bank->dtype, ix->dtype); return false; }
+    if (mode != 0 && mode != 1) { fprintf(stderr, "%s: mode %d is neither 0 (CSLS) nor 1 (inverted softmax)\n", fn, mode); return false; }
+    if (mode == 0 && !check_k(k, 1, fn)) return false;
+    if (mode == 1 && (!(scale > 0.f) || std::isinf(scale))) { fprintf(stderr, "%s: scale %g is not a finite value > 0\n", fn, (double)scale); return false; }
+    if (ix->n > 0 && !bias) { fprintf(stderr, "%s: NULL result pointer\n", fn); return false; }
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+bool clip_amd_index_search_biased(struct clip_amd_index * ix, const float * queries, int n_queries, int k, const float * bias, const uint64_t * allow,
+                                  float * distances, float * scores, int64_t * ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_biased_args(ix, queries, n_queries, k, distances, scores, ids, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return biased_host(ix, queries, nullptr, n_queries, k, false, bias, allow, distances, scores, ids, fn);
+    });
+}
+
+bool clip_amd_index_search_biased_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int k, const float * d_bias,
+                                         const uint64_t * d_allow, float * d_distances, float * d_scores, int64_t * d_ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_biased_args(ix, d_queries, n_queries, k, d_distances, d_scores, d_ids, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return n_queries == 0 ||
+               biased_device(ix, vectors(d_queries), n_queries, k, d_bias, false, (const uint32_t *)d_allow, d_distances, d_scores, d_ids);
+    });
+}
+
+bool clip_amd_index_search_ids_biased(struct clip_amd_index * ix, const int64_t * ids, int n_ids, int k, int exclude_self, const float * bias,
+                                      const uint64_t * allow, float * distances, float * scores, int64_t * ids_out) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_biased_args(ix, ids, n_ids, k, distances, scores, ids_out, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return biased_host(ix, nullptr, ids, n_ids, k, exclude_self != 0, bias, allow, distances, scores, ids_out, fn);
+    });
+}
+
+bool clip_amd_index_hubness(struct clip_amd_index * ix, struct clip_amd_index * bank, int mode, int k, float scale, const uint64_t * allow, float * bias) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_hubness_args(ix, bank, mode, k, scale, bias, fn)) return false;
+        if (ix->n == 0) return true;
+        (void)hipSetDevice(ix->device);
+        const uint32_t * d_allow = nullptr;
+        if (!upload_allow(ix, allow, d_allow) || !ensure(ix, ix->bias, (size_t)ix->n * sizeof(float))) return false;
+        if (!hubness_impl(ix, bank, mode, k, scale, d_allow, (float *)ix->bias.p, fn)) return false;
+        return stream_done(ix, fn, hipMemcpyAsync(bias, ix->bias.p, (size_t)ix->n * sizeof(float), hipMemcpyDeviceToHost, stream_of(ix)));
+    });
+}
+
+bool clip_amd_index_hubness_device(struct clip_amd_index * ix, struct clip_amd_index * bank, int mode, int k, float scale, const uint64_t * d_allow,
+                                   float * d_bias) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_hubness_args(ix, bank, mode, k, scale, d_bias, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return hubness_impl(ix, bank, mode, k, scale, ix->n > 0 ? (const uint32_t *)d_allow : nullptr, d_bias, fn);
     });
 }
 

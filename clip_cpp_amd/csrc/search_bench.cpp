@@ -490,4 +490,30 @@ float clip_amd_bench_softmax(int dtype, int64_t n, int dim, int n_queries, int k
     });
 }
 
+float clip_amd_bench_search_biased(int dtype, int64_t n, int dim, int n_queries, int k, int iters) {
+    return guarded(__func__, -4.f, [&](const char *) {
+        return bench_on_gallery(dtype, n, dim, n_queries, iters, n_queries >= 1 && k >= 1 && k <= MAX_K, PLANT_NONE, [&](clip_amd_index * ix, float * src) {
+            Buf own;
+            Arena a(ix, own);
+            const auto o_dist = a.add<float>(nullptr, (size_t)n_queries * k), o_scores = a.add<float>(nullptr, (size_t)n_queries * k);
+            const auto o_ids = a.add<int64_t>(nullptr, (size_t)n_queries * k);
+            if (!a.ready()) return -4.f;
+            std::vector<float> bias((size_t)n);
+            for (int64_t r = 0; r < n; r++) {                  // splitmix64 of the row number under a fixed seed -> [-0.3, 0.3)
+                uint64_t z = 0xB1A5ull + (uint64_t)r * 0x9E3779B97F4A7C15ull;
+                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+                z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+                bias[(size_t)r] = ((float)((z ^ (z >> 31)) >> 40) * (1.0f / 8388608.0f) - 1.0f) * 0.3f;
+            }
+            BiasedCall b;
+            b.d_scores = a.dev(o_scores, true);
+            if (!stage_bias(ix, bias.data(), true, b.d_bias) || hipDeviceSynchronize() != hipSuccess) return -4.f;
+            launch_search_fill_random(src, (int64_t)n_queries * dim, 0xC0FFEEull, nullptr);
+            return time_device(iters, [&]() {
+                return search_device_impl(ix, vectors(src), n_queries, k, nullptr, a.dev(o_dist, true), a.dev(o_ids, true), nullptr, nullptr, &b);
+            });
+        });
+    });
+}
+
 }  // extern "C"

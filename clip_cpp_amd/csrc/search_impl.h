@@ -102,6 +102,8 @@ struct clip_amd_index {
     Buf rpart;                     // one block's partial counts [n_chunks][columns] (i32)
     // softmax over every eligible row
     Buf spart;                     // one block's partial sums [n_chunks][columns] (f32)
+    // biased search
+    Buf bias;                      // [n rounded up to 64] the call's bias column, padded as rinv is (the scan reads it 4 at a time)
 };
 
 namespace clipamd {
@@ -229,6 +231,13 @@ struct CompoundCall {
 
 struct SetFold;
 
+// What makes a search a biased one: the padded column stage_bias left on the device and where the scores go ([nq][k], device); the
+// distances of the same slots go to the search's d_dist
+struct BiasedCall {
+    const float * d_bias = nullptr;
+    float * d_scores = nullptr;
+};
+
 // the internals the benchmark hooks build their gallery with and time; each is described at its definition in search.cpp
 clip_amd_index * make_index(clip_ctx * ctx, int device, int dim, int dtype);
 void free_index(clip_amd_index * ix);
@@ -236,7 +245,8 @@ bool reserve_rows(clip_amd_index * ix, int64_t need);
 bool add_device_impl(clip_amd_index * ix, const float * d_vecs, int64_t n);
 int auto_pool(int k);
 bool search_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, int k, const uint32_t * d_allow, float * d_dist, int64_t * d_ids,
-                        const int * d_groups = nullptr, const SetFold * fold = nullptr);
+                        const int * d_groups = nullptr, const SetFold * fold = nullptr, const BiasedCall * biased = nullptr);
+bool stage_bias(clip_amd_index * ix, const float * bias, bool on_host, const float *& d_bias);
 bool sets_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, const int64_t * lims, int64_t n_sets, int k, const int * d_groups,
                       bool own, const uint32_t * d_allow, float * d_dist, int64_t * d_ids, int * d_qrows, int64_t qrow_base, bool first_kept);
 bool distinct_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, int k, float radius, int pool, const uint32_t * d_allow,

@@ -86,6 +86,13 @@ pool of the max(64, 8 N) nearest eligible images (at most 1024), not over the wh
 hits in the same order, each line "  %f %f %s" = distance, probability, path (or label), the probability being the softmax of -S * distance
 over EVERY eligible image (every label), not over the printed ones; `search` ends with "main: log Z %f at scale %g".  S defaults to 100,
 the logit scale CLIP is trained to.  --prob works with -n, --in and --like, not with -d, --distinct, --and / --not or a --grid database.
+`debias --db DIR [--mode csls|softmax] [-k K] [--scale S] QUERIES` corrects hubness, a few images that sit close to very many text queries
+and crowd every list: the lines of the text file QUERIES (typical searches, captions) are encoded into a bank index, Index.hubness makes
+one f32 per image from it (csls: -1/2 the mean distance to the image's K nearest bank queries, K default 10; softmax: log Z of the image
+over the bank at scale S / S, S default 100) and DIR/images.bias holds it ("CLIPBIAS", mode, k, scale and row count, then f32).  `search
+--debias` (with -n, --in, --like) then ranks by distance + bias (Index.search_biased / search_ids_biased) and prints "  %f %f %s" = score,
+distance, path; it refuses when images.bias is missing or of another row count.  `eval --debias` prints its recall line twice, plain and
+then "  debiased recall@1 ..." from search_biased at k = 10.  update, dedup --prune and merge remove a now stale images.bias and say so.
 `search --and TERM` / `--not TERM` (both repeatable, up to 8 terms with the main query) ask compound questions (Index.search_compound):
 "a dog" --and "on a beach", --like PATH --and "at night", "a beach" --not "people".  A TERM with an image extension is an image: one that
 equals a line of images.paths is that indexed image (its stored row: nothing is decoded or encoded, and it is not listed itself), any
@@ -155,6 +162,7 @@ IMAGE_EXTENSIONS = (".jpg", ".JPG", ".jpeg", ".JPEG", ".gif", ".GIF", ".png", ".
 INDEX_FILE = "images.index"
 PATHS_FILE = "images.paths"
 REGIONS_FILE = "images.regions"
+BIAS_FILE = "images.bias"
 MAX_GRID = 8
 BATCH = 64          # images decoded and encoded per call
 MAX_K = 1024
@@ -272,6 +280,8 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
                 return None
         elif (search or label) and a == "--prob":
             p["prob"] = True
+        elif search and a == "--debias":
+            p["debias"] = True
         elif dedup and a == "--prune":
             p["prune"] = True
         elif (dedup or groups) and a == "--extents":
@@ -339,6 +349,9 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         return None
     if p.get("prob") and seen & {"max_distance", "distinct", "and", "not", "not_margin"}:
         print("main: --prob cannot be combined with -d, --distinct, --and or --not: it prints the probabilities of the -n nearest images")
+        return None
+    if p.get("debias") and (p.get("prob") or seen & {"max_distance", "distinct", "and", "not", "not_margin"}):
+        print("main: --debias cannot be combined with -d, --distinct, --prob, --and or --not: it ranks the -n nearest images by distance + bias")
         return None
     if {"distinct", "max_distance"} <= seen:
         print("main: --distinct and -d cannot be combined: --distinct R thins the -n nearest, -d R prints every image within R")
@@ -513,6 +526,8 @@ def _help(build, p, dedup=False, update=False, neighbors=False, label=False, mer
         print("  --like <path>: more like this one: the query is the indexed image whose line in %s equals <path> as written; nothing is"
               " decoded or encoded and the image itself is not listed. Works with -n and --in, not with a query or -d" % PATHS_FILE)
         print("  --prob: print every hit's probability (softmax of -scale * distance over ALL eligible images) and the query's log Z; with -n, --in, --like")
+        print("  --debias: rank by distance + the hubness correction `debias` wrote to %s (Index.search_biased) and print `score distance path`;"
+              " with -n, --in, --like" % BIAS_FILE)
         print("  --scale S: the scale of --prob, finite and > 0. Default: 100")
         print("  --distinct R: fold near-duplicates into one hit: walking the ranked list, an image within cosine distance R (<= R, the distance"
               " of `dedup -d R`) of an image already listed is dropped, and a listed image is followed by (+N), the number of images dropped"
@@ -600,6 +615,38 @@ def _write_db(p, index, paths, regions=None):
         os.replace(regions_file + ".tmp", regions_file)
     elif os.path.exists(regions_file):
         os.remove(regions_file)
+
+
+def write_bias(db, mode, k, scale, bias):
+    """DIR/images.bias: "CLIPBIAS", mode (0 csls, 1 softmax) u32, k u32, scale f32, rows u64, then the column in f32, all little-endian"""
+    path = os.path.join(db, BIAS_FILE)
+    with open(path + ".tmp", "wb") as f:
+        f.write(struct.pack("<8sIIfQ", b"CLIPBIAS", mode, k, scale, len(bias)))
+        f.write(np.ascontiguousarray(bias, dtype="<f4").tobytes())
+    os.replace(path + ".tmp", path)
+
+
+def read_bias(db, rows):
+    """The column of DIR/images.bias for an index of `rows` rows; ValueError when the file is missing, malformed or of another row count"""
+    path = os.path.join(db, BIAS_FILE)
+    try:
+        with open(path, "rb") as f:
+            h, body = f.read(28), f.read()
+    except OSError:
+        raise ValueError("'%s' is missing: run `python -m clip_cpp_amd.image_search debias` first" % path)
+    if len(h) != 28 or h[:8] != b"CLIPBIAS" or len(body) != 4 * struct.unpack("<8sIIfQ", h)[4]:
+        raise ValueError("'%s' is not a bias file" % path)
+    if len(body) != 4 * rows:
+        raise ValueError("'%s' holds %d rows, the index %d: run `debias` again" % (path, len(body) // 4, rows))
+    return np.frombuffer(body, dtype="<f4").astype(np.float32)
+
+
+def _drop_stale_bias(db):
+    """after the rows of a database changed: a bias column computed for the old rows goes away, in one line"""
+    path = os.path.join(db, BIAS_FILE)
+    if os.path.exists(path):
+        os.remove(path)
+        print("main: removed %s, computed for the rows before this change: run `debias` again" % path)
 
 
 def read_regions(db):
@@ -744,6 +791,7 @@ def update(argv):
         _encode_dirs(clip, L, index, p, paths, scans)
     if removed or len(paths) > n_kept:
         _write_db(p, index, paths)
+        _drop_stale_bias(p["db"])
     index.close()
     clip.close()
     print("main: %d added, %d removed, %d kept" % (len(paths) - n_kept, len(removed), n_kept), flush=True)
@@ -819,6 +867,8 @@ def search(argv):
         return 1
     if p.get("prob") and _refuse_gridded(p["db"], "search --prob"):
         return 1
+    if p.get("debias") and _refuse_gridded(p["db"], "search --debias"):
+        return 1
     compound = bool(p.get("and") or p.get("not"))
     if compound and _refuse_gridded(p["db"], "search --and / --not"):
         return 1
@@ -832,6 +882,13 @@ def search(argv):
     image_paths = _read_db(p, regions)
     if image_paths is None:
         return 1
+    bias = None
+    if p.get("debias"):
+        try:
+            bias = read_bias(p["db"], len(image_paths))
+        except ValueError as e:
+            _err("main: %s" % e)
+            return 1
     like_id = None
     if p["like"] is not None:
         if p["like"] not in image_paths:
@@ -910,16 +967,26 @@ def search(argv):
             dist, ids, probs, log_z = index.softmax(vec[None, :], k, scale=scale, allow=allow)
         hits = [(d, i) for d, i in zip(dist[0], ids[0]) if i >= 0 and p["results"] > 0]
         prob = {int(i): float(pr) for pr, i in zip(probs[0], ids[0]) if i >= 0}
+    elif bias is not None:                         # ranked by distance + bias; the score is printed in front of the distance
+        k = max(1, min(p["results"], MAX_K))
+        if like_id is not None:
+            dist, scores, ids = index.search_ids_biased([like_id], k, bias, allow=allow)
+        else:
+            dist, scores, ids = index.search_biased(vec[None, :], k, bias, allow=allow)
+        hits = [(d, i) for d, i in zip(dist[0], ids[0]) if i >= 0 and p["results"] > 0]
+        score = {int(i): float(s) for s, i in zip(scores[0], ids[0]) if i >= 0}
     else:
         k = max(1, min(p["results"], MAX_K))
         dist, ids = index.search_ids([like_id], k, allow=allow) if like_id is not None else index.search(vec[None, :], k, allow=allow)
         hits = [(d, i) for d, i in zip(dist[0], ids[0]) if i >= 0 and p["results"] > 0]
     if p["verbose"] > 0:
         print("search results:")
-        print("distance probability path" if p.get("prob") else "distance path")
+        print("distance probability path" if p.get("prob") else "score distance path" if bias is not None else "distance path")
     for d, i in hits:
         if p.get("prob"):
             print("  %f %f %s" % (d, prob[int(i)], image_paths[i]))
+        elif bias is not None:
+            print("  %f %f %s" % (score[int(i)], d, image_paths[i]))
         else:
             print("  %f %s%s%s" % (d, image_paths[i], boxes.get(i, ""), " (+%d)" % more[i] if i in more else ""))
     if p.get("prob"):
@@ -1395,6 +1462,7 @@ def dedup(argv):
             index.remove(removed)
             index.compact()
             _write_db(p, index, [path for i, path in enumerate(image_paths) if i not in gone])
+            _drop_stale_bias(p["db"])
         print("main: %d removed, %d kept%s" % (len(removed), len(image_paths) - len(removed), tail))
     else:
         print("main: %d groups, %d images%s" % (len(groups), sum(len(m) for m in groups), tail))
@@ -1785,6 +1853,8 @@ def _parse_eval(argv):
                     p[key] = int(argv[i]) if key in ("verbose", "results") else argv[i]
                 except ValueError:
                     return None
+        elif a == "--debias":
+            p["debias"] = True
         elif a in ("-h", "--help"):
             _help_eval(p)
             sys.exit(0)
@@ -1812,6 +1882,8 @@ def _help_eval(p):
     print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
     print("  -n N, --results N: also print the N worst-placed pairs as `rank distance path caption`. Default: %d" % p["results"])
     print("  --in PREFIX: rank among the images whose path starts with PREFIX only (a pair's own image need not be one). Repeatable.")
+    print("  --debias: print a second recall line, `debiased recall@1 ... @5 ... @10 ...`, from Index.search_biased at k = 10 with the column of %s;"
+          " median rank and mean reciprocal rank stay plain" % BIAS_FILE)
     print("  PAIRS: a path may occur on several lines; a path that is not in the database is an error.")
 
 
@@ -1857,6 +1929,13 @@ def evaluate(argv):
         _err("main: %s" % e)
         return 1
     _, dim, _, _ = read_index_header(os.path.join(p["db"], INDEX_FILE))
+    bias = None
+    if p.get("debias"):
+        try:
+            bias = read_bias(p["db"], len(image_paths))
+        except ValueError as e:
+            _err("main: %s" % e)
+            return 1
     try:
         clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])
     except RuntimeError:
@@ -1872,14 +1951,20 @@ def evaluate(argv):
     allow = np.array([path.startswith(tuple(p["in"])) for path in image_paths], dtype=np.bool_) if p["in"] else None
     ranks = np.empty(len(captions), dtype=np.int64)
     dist = np.empty(len(captions), dtype=np.float32)
+    place = np.full(len(captions), 10, dtype=np.int64)          # --debias: the target's slot in the debiased top 10, 10 when it is not there
     for b in range(0, len(captions), EVAL_BATCH):
         vecs = clip.encode_texts([clip.tokenize(t) for t in captions[b:b + EVAL_BATCH]], normalize=True)      # as written: no prompt template
         ranks[b:b + EVAL_BATCH], dist[b:b + EVAL_BATCH] = index.rank(vecs, targets[b:b + EVAL_BATCH], allow=allow)
+        if bias is not None:
+            hit = index.search_biased(vecs, 10, bias, allow=allow)[2] == targets[b:b + EVAL_BATCH, None]
+            place[b:b + EVAL_BATCH] = np.where(hit.any(1), hit.argmax(1), 10)
     if p["verbose"] > 0:
         print("retrieval:")
     if len(captions):
         r1, r5, r10, median, mrr = eval_figures(ranks)
         print("  recall@1 %f recall@5 %f recall@10 %f" % (r1, r5, r10))
+        if bias is not None:
+            print("  debiased recall@1 %f recall@5 %f recall@10 %f" % tuple(float(np.mean(place < k)) for k in (1, 5, 10)))
         print("  median rank %.1f mean reciprocal rank %f" % (median, mrr))
     if p["results"] > 0 and len(captions):
         print("worst placed:")
@@ -1887,6 +1972,93 @@ def evaluate(argv):
             print("  %d %f %s %s" % (ranks[i] + 1, dist[i], image_paths[targets[i]], captions[i]))
     print("main: %d pairs ranked among %d images" % (len(captions), len(image_paths) if allow is None else int(allow.sum())))
     sys.stdout.flush()
+    index.close()
+    clip.close()
+    return 0
+
+
+def _parse_debias(argv):
+    """The options of `debias`; None when they do not parse."""
+    p = dict(verbose=1, db=".", model="", mode="csls", k=10, scale=PROB_SCALE, rest=[])
+    takes = {"-m": "model", "--model": "model", "-v": "verbose", "--verbose": "verbose", "--db": "db", "--mode": "mode", "-k": "k", "--scale": "scale"}
+    i = 0
+    while i < len(argv):
+        a = argv[i]
+        if a in takes:
+            i += 1
+            if i >= len(argv):
+                return None
+            key = takes[a]
+            try:
+                p[key] = int(argv[i]) if key in ("verbose", "k") else float(argv[i]) if key == "scale" else argv[i]
+            except ValueError:
+                return None
+        elif a in ("-h", "--help"):
+            _help_debias(p)
+            sys.exit(0)
+        elif a.startswith("-"):
+            print("main: unrecognized argument: %s" % a)
+            return None
+        else:
+            p["rest"].append(a)
+        i += 1
+    if len(p["rest"]) != 1 or p["mode"] not in ("csls", "softmax") or not 1 <= p["k"] <= MAX_K or not 0.0 < p["scale"] < float("inf"):
+        return None
+    return p
+
+
+def _help_debias(p):
+    print("Usage: python -m clip_cpp_amd.image_search debias [options] QUERIES")
+    print("\nCorrects hubness (a few images close to very many text queries, crowding every result list) in an index built by `build`: the lines")
+    print("of the text file QUERIES, typical searches or captions, go through the text tower into a bank index, Index.hubness makes one value per")
+    print("image from it, and `search --debias` / `eval --debias` rank by distance + that value. Writes %s next to the index." % BIAS_FILE)
+    print("\nOptions:")
+    print("  -h, --help: Show this message and exit")
+    print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default. The model needs a text encoder.")
+    print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
+    print("  --db <dir>: directory holding %s and %s. Default: %s" % (INDEX_FILE, PATHS_FILE, p["db"]))
+    print("  --mode csls|softmax: csls (local scaling): -1/2 the mean distance of an image to its K nearest bank queries; softmax (the inverted")
+    print("      softmax of Querybank Normalisation): log Z of the image over the bank at scale S, divided by S. Default: %s" % p["mode"])
+    print("  -k K: the K of csls, 1 ... %d. Default: %d" % (MAX_K, p["k"]))
+    print("  --scale S: the S of softmax, finite and > 0. Default: %g" % p["scale"])
+
+
+def debias(argv):
+    import clip_cpp_amd
+    p = _parse_debias(argv)
+    if p is None:
+        _help_debias(dict(verbose=1, db=".", mode="csls", k=10, scale=PROB_SCALE))
+        return 1
+    if _refuse_gridded(p["db"], "debias"):
+        return 1
+    image_paths = _read_db(p)
+    if image_paths is None:
+        return 1
+    try:
+        with open(p["rest"][0]) as f:
+            queries = [line for line in f.read().split("\n") if line]
+    except OSError as e:
+        _err("main: %s" % e)
+        return 1
+    _, dim, dtype, _ = read_index_header(os.path.join(p["db"], INDEX_FILE))
+    try:
+        clip = clip_cpp_amd.Clip(p["model"], verbosity=p["verbose"])
+    except RuntimeError:
+        print("main: Unable to load model from %s" % p["model"])
+        return 1
+    if clip.text_config["n_layer"] <= 0:
+        _err("main: the model at %s has no text encoder: the query bank needs a two-tower model" % p["model"])
+        return 1
+    if dim != clip.text_config["projection_dim"]:
+        _err("main: the index holds %d-dimensional embeddings, the model makes %d" % (dim, clip.text_config["projection_dim"]))
+        return 1
+    index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
+    bank = clip_cpp_amd.Index(clip, dim, DTYPE_NAMES[dtype])
+    for b in range(0, len(queries), EVAL_BATCH):
+        bank.add(clip.encode_texts([clip.tokenize(t) for t in queries[b:b + EVAL_BATCH]], normalize=True))      # as written: no prompt template
+    write_bias(p["db"], 0 if p["mode"] == "csls" else 1, p["k"], p["scale"], index.hubness(bank, mode=p["mode"], k=p["k"], scale=p["scale"]))
+    print("main: %s written for %d images from %d queries (%s)" % (BIAS_FILE, len(image_paths), len(queries), p["mode"]), flush=True)
+    bank.close()
     index.close()
     clip.close()
     return 0
@@ -2021,6 +2193,7 @@ def merge(argv):
         source.close()
     if added:
         _write_db(p, target, paths)
+        _drop_stale_bias(p["db"])
     target.close()
     clip.close()
     print("main: %d added, %d already present, %d near duplicates skipped" % (added, present, near), flush=True)
@@ -2113,7 +2286,7 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     commands = {"build": build, "update": update, "search": search, "dedup": dedup, "neighbors": neighbors, "label": label, "merge": merge, "match": match,
                 "albums": albums, "spread": spread, "groups": groups, "levels": levels, "file": file_images, "audit": audit, "eval": evaluate,
-                "closest": closest}
+                "closest": closest, "debias": debias}
     if not argv or argv[0] not in commands:
         print("Usage: python -m clip_cpp_amd.image_search {build|search|dedup} [options] ...  (-h after the command for its options)")
         print("       python -m clip_cpp_amd.image_search update [options] dir [more dirs]  (an existing database brought in line with the disk)")
@@ -2129,6 +2302,7 @@ def main(argv=None):
         print("       python -m clip_cpp_amd.image_search audit [options]  (the indexed images that lie in the wrong folder, by the vote of their neighbours)")
         print("       python -m clip_cpp_amd.image_search closest [options]  (the most similar pairs of indexed images, nearest first; --across: from different folders)")
         print("       python -m clip_cpp_amd.image_search eval [options] PAIRS  (recall@K, median rank and MRR of caption<TAB>path pairs: is this model file good enough?)")
+        print("       python -m clip_cpp_amd.image_search debias [options] QUERIES  (the hubness correction from a file of typical queries: search --debias, eval --debias)")
         return 1
     return commands[argv[0]](argv[1:])
 

@@ -562,6 +562,38 @@ bool clip_amd_index_softmax_index(struct clip_amd_index * ix, struct clip_amd_in
 /* Average device time (microseconds) of one clip_amd_index_softmax_device of n_queries seeded random queries over the n seeded random
  * rows of clip_amd_bench_search on the current device, scale 100; < 0 on error.  Used by scripts/softmax_bench.py. */
 float clip_amd_bench_softmax(int dtype, int64_t n, int dim, int n_queries, int k, int iters);
+/* Biased search: the k best rows by score = d + bias[row], with d the distance clip_amd_index_search reports for the pair (same bits) and
+ * bias one f32 per stored row, float[size(ix)] (host for the host forms, device for the _device form; NULL = all zeros).  The addition is
+ * one f32 addition, rounded once.  Results are ordered by (score ascending, id ascending), a total order, so they are exact and do not
+ * depend on how queries are split across calls.  scores / distances / ids are [n][k]: the score as ranked, the pair's plain distance (not
+ * score - bias: search's bits) and the id; empty slots +inf / +inf / -1.  Eligible rows, allow, the limits (1 <= k <= 1024) and every
+ * refusal are clip_amd_index_search_subset's; search_ids_biased takes its queries as clip_amd_index_search_ids does.  With bias NULL the
+ * result is search_subset's (search_ids') bit for bit and scores == distances.  A row whose score is NaN or +inf is never reported.  The
+ * host forms refuse, before any launch and naming the row, a bias entry of a live row that is NaN or infinite; the device form trusts the
+ * array (-inf puts a row first, +inf drops it).
+ * hubness makes the column that corrects hubness in cross-modal retrieval from `bank`, another index of the same context, dim and dtype
+ * holding typical queries (past searches, captions): every row of ix that is live and set in allow is searched against the live rows of
+ * bank on the routes of clip_amd_index_search_index / _softmax_index, and
+ *   mode 0 (CSLS / local scaling, 1 <= k <= 1024)  bias = -0.5f / count * (its k nearest bank distances added in f32, nearest first),
+ *                                                  count = min(k, live rows of bank);
+ *   mode 1 (inverted softmax, scale finite > 0)    bias = log_z / scale, log_z as clip_amd_index_softmax_index(bank, ix, ...) reports it.
+ * k is ignored in mode 1 and scale in mode 0.  Rows of ix that are removed or outside allow get 0 (their searches' results are not
+ * used); a bank without live rows gives an all-zero column.  bias: float[size(ix)], host (device for the _device form, as d_allow). */
+bool clip_amd_index_search_biased(struct clip_amd_index * ix, const float * queries, int n_queries, int k, const float * bias,
+                                  const uint64_t * allow, float * distances, float * scores, int64_t * ids);   /* host, synchronous */
+bool clip_amd_index_search_biased_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int k, const float * d_bias,
+                                         const uint64_t * d_allow, float * d_distances, float * d_scores,
+                                         int64_t * d_ids);                                    /* asynchronous on the context's stream */
+bool clip_amd_index_search_ids_biased(struct clip_amd_index * ix, const int64_t * ids, int n_ids, int k, int exclude_self, const float * bias,
+                                      const uint64_t * allow, float * distances, float * scores, int64_t * ids_out);   /* host, synchronous */
+bool clip_amd_index_hubness(struct clip_amd_index * ix, struct clip_amd_index * bank, int mode, int k, float scale, const uint64_t * allow,
+                            float * bias);                                                                     /* host, synchronous */
+bool clip_amd_index_hubness_device(struct clip_amd_index * ix, struct clip_amd_index * bank, int mode, int k, float scale,
+                                   const uint64_t * d_allow, float * d_bias);                 /* asynchronous on the context's stream */
+/* Average device time (microseconds) of one biased search on the data of clip_amd_bench_search with a seeded random bias in [-0.3, 0.3),
+ * the column already on the device in its padded form (search_biased_device copies it there first, 4 bytes per row); < 0 on error.  Used
+ * by scripts/bias_bench.py. */
+float clip_amd_bench_search_biased(int dtype, int64_t n, int dim, int n_queries, int k, int iters);
 /* One index searched with the rows of another, and one index appended to another: label every image of a database with a small index of
  * captions, find which images of B a database A already holds (k = 1), merge two databases without encoding anything twice.
  * search_index: the queries are stored rows of src: ids[0 ... n_ids) (host), or with ids == NULL every row 0 ... size(src) - 1 (n_ids is
