@@ -101,6 +101,7 @@ AMD_SYMBOLS = [
     "clip_amd_test_index_vote_block", "clip_amd_bench_vote_graph",
     "clip_amd_index_rank", "clip_amd_index_rank_ids", "clip_amd_index_rank_device", "clip_amd_index_count", "clip_amd_index_count_device",
     "clip_amd_bench_rank", "clip_amd_bench_rank_parts",
+    "clip_amd_index_select", "clip_amd_index_select_device", "clip_amd_index_search_page", "clip_amd_index_search_page_device",
     "clip_amd_index_softmax", "clip_amd_index_softmax_device", "clip_amd_index_softmax_ids", "clip_amd_index_softmax_index", "clip_amd_bench_softmax",
     "clip_amd_index_search_biased", "clip_amd_index_search_biased_device", "clip_amd_index_search_ids_biased", "clip_amd_index_hubness",
     "clip_amd_index_hubness_device", "clip_amd_bench_search_biased",
@@ -416,6 +417,14 @@ def lib():
     L.clip_amd_index_count.argtypes = [vp, f32p, i32, f32p, u64p, i64p]
     L.clip_amd_index_count_device.restype = C.c_bool
     L.clip_amd_index_count_device.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.clip_amd_index_select.restype = C.c_bool
+    L.clip_amd_index_select.argtypes = [vp, f32p, i32, i64p, u64p, f32p, i64p]
+    L.clip_amd_index_select_device.restype = C.c_bool
+    L.clip_amd_index_select_device.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.clip_amd_index_search_page.restype = C.c_bool
+    L.clip_amd_index_search_page.argtypes = [vp, f32p, i32, i64, i32, u64p, f32p, i64p]
+    L.clip_amd_index_search_page_device.restype = C.c_bool
+    L.clip_amd_index_search_page_device.argtypes = [vp, vp, i32, i64, i32, vp, vp, vp]
     L.clip_amd_bench_rank.restype = C.c_float
     L.clip_amd_bench_rank.argtypes = [i32, i64, i32, i32, i32]
     L.clip_amd_bench_rank_parts.restype = None
@@ -1929,6 +1938,54 @@ class Index:
         if not lib().clip_amd_index_count_device(self._live(), C.c_void_p(d_queries or None), int(n_queries), C.c_void_p(d_radii or None),
                                                  C.c_void_p(d_allow or None), C.c_void_p(d_counts or None)):
             raise RuntimeError("clip_amd_index_count_device failed (see stderr)")
+
+    def select(self, queries, ranks, allow=None):
+        """The eligible row at place `ranks` (0-based; a scalar, or one per query) of each query's full ranking: (distances f32 [nq], ids
+        int64 [nq]), the entry search would list there at any depth; +inf / -1 for a rank at or past the number of eligible rows.  The
+        inverse of rank; a percentile threshold is select(q, eligible // 100)[0].  ValueError for a negative rank."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        nq = q.shape[0]
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(ranks, dtype=np.int64), (nq,)) if np.ndim(ranks) == 0
+                                 else np.asarray(ranks, dtype=np.int64).reshape(-1))
+        if r.size != nq:
+            raise ValueError("ranks must be a scalar or hold one value per query: %d, not %d" % (nq, r.size))
+        if bool((r < 0).any()):
+            raise ValueError("a rank is negative")
+        r = np.zeros(1, dtype=np.int64)[:0] if nq == 0 else r
+        words, wp = self._allow(allow)
+        dist = np.empty(max(nq, 1), dtype=np.float32)[:nq]
+        ids = np.empty(max(nq, 1), dtype=np.int64)[:nq]
+        i64p = C.POINTER(C.c_int64)
+        if not lib().clip_amd_index_select(self._live(), _fp(q), nq, r.ctypes.data_as(i64p), wp, _fp(dist), ids.ctypes.data_as(i64p)):
+            raise RuntimeError("clip_amd_index_select failed (see stderr)")
+        return dist, ids
+
+    def select_device(self, d_queries, n_queries, d_ranks, d_distances, d_ids, d_allow=None):
+        """select on device pointers (ints): queries [n, dim] f32, ranks int64 [n] -> distances f32 [n], ids int64 [n]; asynchronous on
+        the context's stream"""
+        if not lib().clip_amd_index_select_device(self._live(), C.c_void_p(d_queries or None), int(n_queries), C.c_void_p(d_ranks or None),
+                                                  C.c_void_p(d_allow or None), C.c_void_p(d_distances or None), C.c_void_p(d_ids or None)):
+            raise RuntimeError("clip_amd_index_select_device failed (see stderr)")
+
+    def search_page(self, queries, k, offset=0, allow=None):
+        """Places offset ... offset + k - 1 of every query's full ranking: (distances f32 [nq, k], ids int64 [nq, k]), sorted, +inf / -1
+        past the eligible rows.  offset 0 is search bit for bit; the pages at 0, k, 2 k, ... concatenate to the full ranking with every
+        row exactly once, also across runs of equal distances.  1 <= k <= 1024, any offset >= 0."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        nq = q.shape[0]
+        words, wp = self._allow(allow)
+        dist = np.empty((nq, max(int(k), 1)), dtype=np.float32)
+        ids = np.empty((nq, max(int(k), 1)), dtype=np.int64)
+        if not lib().clip_amd_index_search_page(self._live(), _fp(q), nq, int(offset), int(k), wp, _fp(dist), ids.ctypes.data_as(C.POINTER(C.c_int64))):
+            raise RuntimeError("clip_amd_index_search_page failed (see stderr)")
+        return dist, ids
+
+    def search_page_device(self, d_queries, n_queries, k, d_distances, d_ids, offset=0, d_allow=None):
+        """search_page on device pointers (ints): queries [n, dim] f32 -> distances [n, k] f32, ids [n, k] int64; asynchronous on the
+        context's stream"""
+        if not lib().clip_amd_index_search_page_device(self._live(), C.c_void_p(d_queries or None), int(n_queries), int(offset), int(k),
+                                                       C.c_void_p(d_allow or None), C.c_void_p(d_distances or None), C.c_void_p(d_ids or None)):
+            raise RuntimeError("clip_amd_index_search_page_device failed (see stderr)")
 
     @staticmethod
     def _softmax_outputs(n, k):

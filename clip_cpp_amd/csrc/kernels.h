@@ -412,6 +412,42 @@ void launch_rank_key(const void * rows, const float * rinv, const uint32_t * liv
 bool launch_rank_count(const RankArgs & a, hipStream_t stream);
 void launch_rank_finish(const int * part, int n_chunks, int ncols, const int * kid, const float * kd, bool none, int64_t * out, float * dist,
                         hipStream_t stream);
+// Selection of an order statistic (k_select.hip): a radix select over the keys K = (okey(distance) << 32) | row of the eligible rows
+// (mask as above), 8 bits a pass.  nq prepared query rows carry nr rank columns each (1: select; 2: a page, columns q and nq + q the
+// ranks lo and hi); the columns' state and histograms live behind one pointer of select_state_bytes(nq, nr) bytes, laid out by
+// select_state_at (which fills the state pointers of a).  init: rem := ranks[c] (device, nr == 1) or lo / hi, prefix := 0, bins and page
+// counters := 0; a negative rank, and with `none` every column, is flagged.  Then, for pass = 0 ... select_passes(n) - 1 and shift =
+// select_shift(n, pass): sweep (collect false; rows_per_chunk from rank_rows_per_chunk; qt in {1, 2}) and pick (first: pass 0, which
+// flags a rank at or past the number of eligible rows and clamps a page's hi to the last).  Nothing is launched for n == 0.  A page
+// then sweeps once more with collect (the keys between the two selected ones -> page [nq][k], cnt [nq]).  finish: nr == 1: dist / ids
+// [nq] := the selected pair, +inf / -1 for a flagged column; nr == 2: dist / ids [nq][k] := the page sorted, +inf / -1 behind its end.
+struct SelectArgs {
+    const void * rows = nullptr;
+    const float * rinv = nullptr;
+    int64_t n = 0;
+    int Dpad = 0, dtype = 0;
+    const void * q = nullptr;
+    const float * qinv = nullptr;
+    int nq = 0, qt = 1, nr = 1, k = 1;
+    int n_chunks = 0;
+    int64_t rows_per_chunk = 0;
+    const uint32_t * mask = nullptr;
+    uint64_t * prefix = nullptr;      // [nr][nq]
+    uint64_t * pmask = nullptr;       // [nr][nq]
+    int64_t * rem = nullptr;          // [nr][nq]
+    int * flag = nullptr;             // [nr][nq]
+    unsigned * hist = nullptr;        // [nr][nq][256]
+    unsigned * cnt = nullptr;         // [nq]
+    uint64_t * page = nullptr;        // nr == 2: [nq][k]
+};
+int select_passes(int64_t n);
+int select_shift(int64_t n, int pass);
+size_t select_state_bytes(int64_t nq, int nr);
+void select_state_at(void * base, int64_t nq, int nr, SelectArgs & a);
+void launch_select_init(const SelectArgs & a, const int64_t * ranks, int64_t lo, int64_t hi, bool none, hipStream_t stream);
+bool launch_select_sweep(const SelectArgs & a, int shift, bool collect, hipStream_t stream);
+void launch_select_pick(const SelectArgs & a, int shift, bool first, hipStream_t stream);
+void launch_select_finish(const SelectArgs & a, float * dist, int64_t * ids, hipStream_t stream);
 // Softmax over every eligible row (k_softmax.hip).  Column c is the prepared query row c; kd [ncols][k] holds the distances the search
 // reported for it, so kd[c * k] is its minimum m over the eligible rows (mask and qself as for rank above: qself != NULL, row qself[c]
 // is not eligible).  sweep: part [n_chunks][ncols] := each chunk's sum of exp(-beta (d - m)) over its eligible rows, every term <= 1

@@ -12,6 +12,7 @@
 //                   labelling, farthest-first selection, the closest pairs (prep -> link -> merge)
 //   k_vote.hip      k-NN voting over labelled rows (the voter bitmap and the fold, as the sink of search_blocks)
 //   k_rank.hip      rank and count queries (rank_blocks: key -> count -> finish per block of columns; the host arithmetic in rank_host.h)
+//   k_select.hip    selection of an order statistic and pages at any depth (select_blocks: init -> (sweep -> pick) per digit -> collect -> finish)
 //   k_softmax.hip   softmax over every eligible row (softmax_blocks: the sweep and its finish as the sink of search_blocks)
 // and appending one index to another, the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
 // The benchmark and test hooks are in search_bench.cpp; search_impl.h holds what the two files share.
@@ -1774,7 +1775,133 @@ bool idx::count_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, 
 
 namespace {
 
-constexpr int64_t SOFTMAX_BLOCK = 4096;       // queries per block: the partial sums of a block are at most 1024 x 4096 floats
+constexpr int64_t SELECT_BLOCK = 1024;        // queries per block: a page's two columns hold 2 MB of histograms, its keys at k = 1024 8 MB
+
+// Selection of an order statistic (k_select.hip) for nq queries, in blocks of at most SELECT_BLOCK, one after another on the stream.
+// page: ranks offset ... offset + k - 1 of every query, [k] results each; else one rank per query, which ranks(q0, m) hands out on the
+// device (int64), one result each.  source(q0, m) names a block's queries for prepare_queries; dest(q0, dist, ids) names where the
+// block's results go (device); done(q0, m) follows every block (the host forms copy it out there).  All passes of a block are enqueued
+// without a sync: their number depends on the size of the index alone.  An empty index: +inf / -1 from init and finish alone.
+template <typename Source, typename Ranks, typename Dest, typename Done>
+bool select_blocks(clip_amd_index * ix, int64_t nq, bool page, int64_t offset, int k, const uint32_t * d_allow, const char * fn, Source && source,
+                   Ranks && ranks, Dest && dest, Done && done) {
+    hipStream_t st = stream_of(ix);
+    if (nq == 0) return true;
+    const int64_t n = ix->n;
+    const uint32_t * mask = nullptr;
+    if (!effective_mask(ix, d_allow, mask)) return false;
+    const int64_t rpc = rank_rows_per_chunk(n);
+    const int64_t B = std::min(nq, SELECT_BLOCK);
+    const int nr = page ? 2 : 1;
+    if (!ensure(ix, ix->selstate, select_state_bytes(B, nr)) || (page && !ensure(ix, ix->selpage, (size_t)B * k * 8))) return false;
+    const int64_t hi = offset > INT64_MAX - k ? INT64_MAX : offset + k - 1;
+    const int passes = select_passes(n);
+    for (int64_t q0 = 0; q0 < nq; q0 += B) {
+        const int m = (int)std::min(B, nq - q0);
+        SelectArgs a;
+        a.rows = ix->store.rows;
+        a.rinv = ix->store.rinv;
+        a.n = n;
+        a.Dpad = ix->Dpad;
+        a.dtype = ix->dtype;
+        a.nq = m;
+        a.qt = m > 16 ? 2 : 1;
+        a.nr = nr;
+        a.k = k;
+        a.n_chunks = (int)((n + rpc - 1) / rpc);
+        a.rows_per_chunk = rpc;
+        a.mask = mask;
+        select_state_at(ix->selstate.p, m, nr, a);
+        a.page = (uint64_t *)ix->selpage.p;
+        float * d_dist = nullptr;
+        int64_t * d_ids = nullptr;
+        dest(q0, d_dist, d_ids);
+        const int64_t * d_ranks = page ? nullptr : ranks(q0, m);
+        if (n > 0) {
+            if (!prepare_queries(ix, source(q0, m).d_q, m, m)) return false;
+            a.q = ix->qbuf.p;
+            a.qinv = (const float *)ix->qinv.p;
+        }
+        launch_select_init(a, d_ranks, offset, hi, n == 0, st);
+        for (int pass = 0; n > 0 && pass < passes; pass++) {
+            const int shift = select_shift(n, pass);
+            if (!launch_select_sweep(a, shift, false, st)) {
+                fprintf(stderr, "%s: sweep launch failed\n", fn);
+                return false;
+            }
+            launch_select_pick(a, shift, pass == 0, st);
+        }
+        if (page && n > 0 && !launch_select_sweep(a, 0, true, st)) {
+            fprintf(stderr, "%s: collect launch failed\n", fn);
+            return false;
+        }
+        launch_select_finish(a, d_dist, d_ids, st);
+        if (!launched(true, fn) || !done(q0, m)) return false;
+    }
+    return true;
+}
+
+// The host forms: ranks != NULL: select, else the page at offset.  The allowed set goes up once; a block's queries and ranks are
+// staged, its results land in the results arena and are copied out before the next block.
+bool select_host(clip_amd_index * ix, const float * queries, int64_t nq, const int64_t * ranks, int64_t offset, int k, const uint64_t * allow,
+                 float * distances, int64_t * ids, const char * fn) {
+    hipStream_t st = stream_of(ix);
+    if (nq == 0) return true;
+    const uint32_t * d_allow = nullptr;
+    const size_t B = (size_t)std::min(nq, SELECT_BLOCK), per = ranks ? 1 : (size_t)k;
+    Arena a(ix);
+    const auto o_ids = a.add(ids, B * per);
+    const auto o_dist = a.add(distances, B * per);
+    if (!upload_allow(ix, allow, d_allow) || !a.ready() || !reserve_stage(ix, queries, nullptr, (int64_t)B) || (ranks && !ensure(ix, ix->rin, B * 8)))
+        return false;
+    return select_blocks(
+        ix, nq, !ranks, offset, k, d_allow, fn, [&](int64_t q0, int m) { return stage_block(ix, queries, nullptr, q0, m, false); },
+        [&](int64_t q0, int m) {
+            (void)hipMemcpyAsync(ix->rin.p, ranks + q0, (size_t)m * 8, hipMemcpyHostToDevice, st);
+            return (const int64_t *)ix->rin.p;
+        },
+        [&](int64_t, float *& d_dist, int64_t *& d_ids) {
+            d_dist = a.dev(o_dist);
+            d_ids = a.dev(o_ids);
+        },
+        [&](int64_t q0, int m) {
+            a.queue(0, a.n, 0, (size_t)q0 * per, (size_t)m * per);
+            return stream_done(ix, fn, hipGetLastError());      // (the staging buffers and the block's results are reused)
+        });
+}
+
+// what the select and page entry points ask: the index, n >= 0, and pointers wherever there is something to read or write
+bool check_select_args(const clip_amd_index * ix, const void * q, int nq, const void * ranks, const void * dist, const void * ids, const char * fn) {
+    if (!check_index(ix, fn)) return false;
+    if (nq < 0) { fprintf(stderr, "%s: n_queries %d < 0\n", fn, nq); return false; }
+    if (nq > 0 && (!q || !ranks || !dist || !ids)) { fprintf(stderr, "%s: NULL queries, ranks or result pointer\n", fn); return false; }
+    return true;
+}
+
+bool check_offset(int64_t offset, const char * fn) {
+    if (offset < 0) fprintf(stderr, "%s: offset %lld < 0\n", fn, (long long)offset);
+    return offset >= 0;
+}
+
+}  // namespace
+
+// The device form: queries, ranks (select; NULL: the page at offset) and allowed set on the device, results straight into the caller's arrays
+bool idx::select_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, const int64_t * d_ranks, int64_t offset, int k, const uint32_t * d_allow,
+                             float * d_dist, int64_t * d_ids, const char * fn) {
+    const size_t per = d_ranks ? 1 : (size_t)k;
+    return select_blocks(
+        ix, nq, !d_ranks, offset, k, ix->n > 0 ? d_allow : nullptr, fn, [&](int64_t q0, int) { return vectors(d_q + (size_t)q0 * ix->dim); },
+        [&](int64_t q0, int) { return d_ranks + q0; },
+        [&](int64_t q0, float *& d, int64_t *& o) {
+            d = d_dist + (size_t)q0 * per;
+            o = d_ids + (size_t)q0 * per;
+        },
+        [](int64_t, int) { return true; });
+}
+
+namespace {
+
+constexpr int64_t SOFTMAX_BLOCK = 4096;      // queries per block: the partial sums of a block are at most 1024 x 4096 floats
 
 // the four result arrays of a softmax call: dist / ids / probs [rows][k], log_z [rows], on the device or on the host
 struct SoftmaxOut {
@@ -2004,6 +2131,44 @@ bool clip_amd_index_count_device(struct clip_amd_index * ix, const float * d_que
         if (!check_count_args(ix, d_queries, n_queries, d_radii, d_counts, fn)) return false;
         (void)hipSetDevice(ix->device);
         return count_device_impl(ix, d_queries, n_queries, d_radii, (const uint32_t *)d_allow, d_counts, fn);
+    });
+}
+
+bool clip_amd_index_select(struct clip_amd_index * ix, const float * queries, int n_queries, const int64_t * ranks, const uint64_t * allow,
+                           float * distances, int64_t * ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_select_args(ix, queries, n_queries, ranks, distances, ids, fn)) return false;
+        for (int i = 0; i < n_queries; i++)
+            if (ranks[i] < 0) { fprintf(stderr, "%s: ranks[%d] = %lld < 0\n", fn, i, (long long)ranks[i]); return false; }
+        (void)hipSetDevice(ix->device);
+        return select_host(ix, queries, n_queries, ranks, 0, 1, allow, distances, ids, fn);
+    });
+}
+
+bool clip_amd_index_select_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, const int64_t * d_ranks,
+                                  const uint64_t * d_allow, float * d_distances, int64_t * d_ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_select_args(ix, d_queries, n_queries, d_ranks, d_distances, d_ids, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return select_device_impl(ix, d_queries, n_queries, d_ranks, 0, 1, (const uint32_t *)d_allow, d_distances, d_ids, fn);
+    });
+}
+
+bool clip_amd_index_search_page(struct clip_amd_index * ix, const float * queries, int n_queries, int64_t offset, int k, const uint64_t * allow,
+                                float * distances, int64_t * ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_search_args(ix, queries, n_queries, k, distances, ids, fn) || !check_offset(offset, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return select_host(ix, queries, n_queries, nullptr, offset, k, allow, distances, ids, fn);
+    });
+}
+
+bool clip_amd_index_search_page_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int64_t offset, int k,
+                                       const uint64_t * d_allow, float * d_distances, int64_t * d_ids) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_search_args(ix, d_queries, n_queries, k, d_distances, d_ids, fn) || !check_offset(offset, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return select_device_impl(ix, d_queries, n_queries, nullptr, offset, k, (const uint32_t *)d_allow, d_distances, d_ids, fn);
     });
 }
 

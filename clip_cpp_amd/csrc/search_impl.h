@@ -100,8 +100,11 @@ struct clip_amd_index {
     Buf rin;                       // one block's targets (i64) or radii (f32) copied from the host
     Buf rcols;                     // one block's columns: key distances (f32), key ids (i32), query rows (i32)
     Buf rpart;                     // one block's partial counts [n_chunks][columns] (i32)
+    // selection of an order statistic
+    Buf selstate;                  // one block's rank columns: histograms, prefixes, masks, remaining ranks, flags, page counters
+    Buf selpage;                   // one block's collected page keys [queries][k] (u64)
     // softmax over every eligible row
-    Buf spart;                     // one block's partial sums [n_chunks][columns] (f32)
+    Buf spart;                    // one block's partial sums [n_chunks][columns] (f32)
     // biased search
     Buf bias;                      // [n rounded up to 64] the call's bias column, padded as rinv is (the scan reads it 4 at a time)
 };
@@ -261,6 +264,8 @@ bool rank_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, const 
                       int64_t * d_ranks, float * d_dist, const char * fn);
 bool count_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, const float * d_radii, const uint32_t * d_allow, int64_t * d_counts,
                        const char * fn);
+bool select_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, const int64_t * d_ranks, int64_t offset, int k, const uint32_t * d_allow,
+                        float * d_dist, int64_t * d_ids, const char * fn);
 bool softmax_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, int k, float beta, const uint32_t * d_allow, float * d_dist,
                          int64_t * d_ids, float * d_probs, float * d_log_z, const char * fn);
 bool vote_host(clip_amd_index * ix, const float * queries, const int64_t * ids, int64_t nq, int k, int m, bool exclude_self, const int32_t * labels,

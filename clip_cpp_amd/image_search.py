@@ -3,7 +3,7 @@ build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.In
 
     python -m clip_cpp_amd.image_search build  [-m MODEL] [-v N] [-t N] [--db DIR] [--dtype f16|f32|i8] [--grid G] dir [more dirs]
     python -m clip_cpp_amd.image_search update [-m MODEL] [-v N] [-t N] [--db DIR] dir [more dirs]
-    python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N | -d R] [--distinct R] [--in PREFIX]... [--db DIR] <search text or /path/to/query/image>
+    python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N [--offset O] | -d R] [--distinct R] [--in PREFIX]... [--db DIR] <search text or /path/to/query/image>
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-n N] [--distinct R] [--in PREFIX]... [--db DIR] --like INDEXED/IMAGE/PATH
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N] [--in PREFIX]... [--db DIR] [--and TERM]... [--not TERM]... [--not-margin M] <query or --like PATH>
     python -m clip_cpp_amd.image_search dedup  [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R] [--prune] [--extents]
@@ -77,6 +77,10 @@ Without --core both commands print exactly what they printed before.
 `search --like PATH` asks for "more like this one": the query is the indexed image whose line in images.paths equals PATH as written
 (Index.search_ids: its stored row, nothing is decoded or encoded, so a text-only or vision-less model is enough); the image itself is not
 listed.  It composes with -n and --in, not with a positional query or -d.
+`search -n N` with a text or image query takes any N: past the first 1024 hits (Index.search) it prints pages of 1024 from
+Index.search_page, which selects places at any depth on the device; `search --offset O` skips the O nearest (places O ... O + N - 1 of the
+full ranking).  Both work with --in.  With --like, --distinct, --debias, --prob, --and / --not and on a database built with --grid at most
+1024 images are displayed (the command says so on stderr when N is larger) and --offset is refused.
 `search --distinct R` folds near-duplicates (bursts, resized copies, re-saved files) into one hit (Index.search_distinct /
 Index.search_ids_distinct): walking the ranked list, an image within distance R of an image already listed (the distance of `dedup -d R`)
 is dropped, and a listed image that stands for dropped ones gets " (+%d)", their number, behind its path.  The suppression runs over the
@@ -250,7 +254,8 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
             if not dedup:
                 takes.update({"-n": "results", "--results": "results"})
         if search:
-            takes.update({"--in": "in", "--like": "like", "--distinct": "distinct", "--and": "and", "--not": "not", "--not-margin": "not_margin"})
+            takes.update({"--in": "in", "--like": "like", "--distinct": "distinct", "--and": "and", "--not": "not", "--not-margin": "not_margin",
+                          "--offset": "offset"})
         if search or label:
             takes["--scale"] = "scale"
         if a in takes:
@@ -267,7 +272,7 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
                 i += 1
                 continue
             try:
-                p[key] = int(argv[i]) if key in ("threads", "verbose", "results", "grid", "min_size", "core") else float(argv[i]) if key in ("max_distance", "distinct", "not_margin", "link", "scale") else argv[i]
+                p[key] = int(argv[i]) if key in ("threads", "verbose", "results", "grid", "min_size", "core", "offset") else float(argv[i]) if key in ("max_distance", "distinct", "not_margin", "link", "scale") else argv[i]
             except ValueError:
                 return None
             if key in ("max_distance", "distinct", "not_margin", "link", "scale") and p[key] != p[key]:      # NaN
@@ -352,6 +357,11 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         return None
     if p.get("debias") and (p.get("prob") or seen & {"max_distance", "distinct", "and", "not", "not_margin"}):
         print("main: --debias cannot be combined with -d, --distinct, --prob, --and or --not: it ranks the -n nearest images by distance + bias")
+        return None
+    if "offset" in seen and (p["offset"] < 0 or p["like"] is not None or p.get("prob") or p.get("debias") or
+                             seen & {"max_distance", "distinct", "and", "not", "not_margin"}):
+        print("main: --offset O skips the O nearest images of a text or image query (O >= 0): it works with -n and --in, not with --like, -d,"
+              " --distinct, --prob, --debias, --and or --not")
         return None
     if {"distinct", "max_distance"} <= seen:
         print("main: --distinct and -d cannot be combined: --distinct R thins the -n nearest, -d R prints every image within R")
@@ -519,7 +529,11 @@ def _help(build, p, dedup=False, update=False, neighbors=False, label=False, mer
         print("  -m <path>, --model <path>: overwrite path to model. Read from images.paths by default.")
         print("  -t N, --threads N: Number of threads to use for inference. Default: %d" % p["threads"])
         print("  -v <level>, --verbose <level>: Control the level of verbosity. 0 = minimum, 2 = maximum. Default: %d" % p["verbose"])
-        print("  -n N, --results N: Number of results to display. Default: %d" % p["results"])
+        print("  -n N, --results N: Number of results to display. Default: %d. A text or image query takes any N (Index.search_page, pages of %d);"
+              " with --like, --distinct, --debias, --prob, --and / --not and on a --grid database at most %d are displayed, and the command says so"
+              % (p["results"], MAX_K, MAX_K))
+        print("  --offset O: skip the O nearest images: display places O ... O + N - 1 of the full ranking, at any depth. Works with -n and --in,"
+              " not with --like, -d, --distinct, --prob, --debias, --and / --not or a --grid database")
         print("  -d R, --max-distance R: display every indexed image within cosine distance R (<= R), nearest first, instead of the -n nearest (not with -n)")
         print("  --in <prefix>: only images whose indexed path starts with <prefix> are eligible (one directory, one album); may be repeated:"
               " a path matching any prefix is eligible. Works with -n and with -d")
@@ -869,9 +883,16 @@ def search(argv):
         return 1
     if p.get("debias") and _refuse_gridded(p["db"], "search --debias"):
         return 1
+    if p.get("offset") is not None and _refuse_gridded(p["db"], "search --offset"):
+        return 1
     compound = bool(p.get("and") or p.get("not"))
     if compound and _refuse_gridded(p["db"], "search --and / --not"):
         return 1
+    capped = [w for w, on in (("--like", p["like"] is not None), ("--distinct", p.get("distinct") is not None), ("--debias", p.get("debias")),
+                              ("--prob", p.get("prob")), ("--and / --not", compound),
+                              ("a --grid database", os.path.exists(os.path.join(p["db"], REGIONS_FILE)))) if on]
+    if p["results"] > MAX_K and capped and p["max_distance"] is None:
+        _err("main: -n %d: with %s at most %d images are displayed" % (p["results"], capped[0], MAX_K))
     if (p["like"] is not None or p["max_distance"] is not None) and _refuse_gridded(p["db"], "search --like" if p["like"] is not None else "search -d"):
         return 1
     try:
@@ -975,10 +996,20 @@ def search(argv):
             dist, scores, ids = index.search_biased(vec[None, :], k, bias, allow=allow)
         hits = [(d, i) for d, i in zip(dist[0], ids[0]) if i >= 0 and p["results"] > 0]
         score = {int(i): float(s) for s, i in zip(scores[0], ids[0]) if i >= 0}
-    else:
+    elif like_id is not None:
         k = max(1, min(p["results"], MAX_K))
-        dist, ids = index.search_ids([like_id], k, allow=allow) if like_id is not None else index.search(vec[None, :], k, allow=allow)
+        dist, ids = index.search_ids([like_id], k, allow=allow)
         hits = [(d, i) for d, i in zip(dist[0], ids[0]) if i >= 0 and p["results"] > 0]
+    else:                                          # any depth: pages of at most MAX_K from --offset on, until -n hits or the ranking ends
+        hits, at = [], p.get("offset") or 0
+        while len(hits) < p["results"]:
+            k = min(p["results"] - len(hits), MAX_K)
+            # (the first page of the ranking is search's own scan: the same bits in one sweep of the rows)
+            dist, ids = index.search(vec[None, :], k, allow=allow) if at == 0 else index.search_page(vec[None, :], k, offset=at, allow=allow)
+            hits += [(d, i) for d, i in zip(dist[0], ids[0]) if i >= 0]
+            at += k
+            if ids[0, -1] < 0:
+                break
     if p["verbose"] > 0:
         print("search results:")
         print("distance probability path" if p.get("prob") else "score distance path" if bias is not None else "distance path")

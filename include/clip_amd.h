@@ -514,6 +514,36 @@ bool clip_amd_index_count(struct clip_amd_index * ix, const float * queries, int
                           int64_t * counts);                                                                  /* host, synchronous */
 bool clip_amd_index_count_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, const float * d_radii,
                                  const uint64_t * d_allow, int64_t * d_counts);                               /* HBM, asynchronous */
+/* Selection at any depth: "which row stands at place R of this query's ranking, and at what distance?" and "hits offset ... offset + k - 1
+ * of it".  The inverse of rank: a percentile threshold (the distance that keeps the nearest 1 %), the bounds of a page, result 1025
+ * and beyond (search stops at k = 1024).  Exact selection of an order statistic on the device (k_select.hip), without moving or
+ * storing the distances of the index.
+ * Every ELIGIBLE row r of a query q (live and, with allow, allowed, as for clip_amd_index_search_subset) has the 64-bit key
+ *   K(q, r) = (okey(d) << 32) | (uint32)r
+ * where d is the f32 distance with search's bits and okey the order-preserving map of f32 bits to u32: all bits of a negative value
+ * flipped, the sign bit of a non-negative one set.  Stored values are finite by the index's contract, so d is never a NaN, and 1 - x
+ * never yields -0; the calls rely on both: ascending K is exactly search's order (distance ascending, then id ascending), and it is total.
+ * select: distances[i] / ids[i] = the eligible row at place ranks[i] (int64, 0-based) of query i's full ranking; a rank at or past the
+ * number of eligible rows gives +INFINITY / -1.
+ * search_page: distances / ids [n_queries][k] = places offset ... offset + k - 1 of every query's full ranking (offset int64 >= 0, one
+ * for the call; 1 <= k <= 1024), sorted; the tail past the eligible rows holds +INFINITY / -1, exactly as search pads.  offset == 0 is
+ * clip_amd_index_search_subset bit for bit; the pages at offsets 0, k, 2 k, ... concatenate to the full ranking, every row exactly once,
+ * also where a page boundary falls inside a run of equal distances.
+ * The results are integers and search's own distances: exact, independent of the order of any atomic, bit-reproducible.
+ * Cost: 4 + ceil(bits(size - 1) / 8) sweeps of the rows (one per 8-bit digit of K; each about a rank call's sweep), for a page one more.
+ * Refused before any launch, with a message and the outputs untouched: a NULL index, n_queries < 0, NULL pointers where there is
+ * something to read or write, a negative rank (host form) or offset, k outside 1 ... 1024.  The device forms trust their pointers; a
+ * negative rank on the device gives +INFINITY / -1.  Zero queries and an empty index succeed: nothing, or +INFINITY / -1.
+ * Device memory beyond the index: one block of 1024 queries at a time (its queries, 1 KB of histogram per rank column, k keys per
+ * query of a page); nothing grows with the call or with the depth. */
+bool clip_amd_index_select(struct clip_amd_index * ix, const float * queries, int n_queries, const int64_t * ranks, const uint64_t * allow,
+                           float * distances, int64_t * ids);                                                  /* host, synchronous */
+bool clip_amd_index_select_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, const int64_t * d_ranks,
+                                  const uint64_t * d_allow, float * d_distances, int64_t * d_ids);             /* HBM, asynchronous */
+bool clip_amd_index_search_page(struct clip_amd_index * ix, const float * queries, int n_queries, int64_t offset, int k,
+                                const uint64_t * allow, float * distances, int64_t * ids);                     /* host, synchronous */
+bool clip_amd_index_search_page_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int64_t offset, int k,
+                                       const uint64_t * d_allow, float * d_distances, int64_t * d_ids);        /* HBM, asynchronous */
 /* Average device time (microseconds) of one clip_amd_index_rank_device of n_queries seeded random queries with one seeded target each over
  * the n seeded random rows of clip_amd_bench_search on the current device; < 0 on error.  clip_amd_bench_rank_parts: of the last such
  * call, parts[0] the key kernel alone (device time) and parts[1] one host-form clip_amd_index_rank of one query (wall time).  Used by
