@@ -87,6 +87,8 @@ AMD_SYMBOLS = [
     "clip_amd_bench_search_sets",
     "clip_amd_index_search_distinct", "clip_amd_index_search_distinct_device", "clip_amd_index_search_ids_distinct",
     "clip_amd_test_index_distinct_block", "clip_amd_bench_search_distinct",
+    "clip_amd_index_search_mmr", "clip_amd_index_search_mmr_device", "clip_amd_index_search_ids_mmr",
+    "clip_amd_test_index_mmr_route", "clip_amd_bench_search_mmr",
     "clip_amd_index_search_compound", "clip_amd_index_search_compound_device", "clip_amd_test_index_compound_block",
     "clip_amd_bench_search_compound",
     "clip_amd_index_components", "clip_amd_index_components_device", "clip_amd_bench_components",
@@ -373,6 +375,16 @@ def lib():
     L.clip_amd_test_index_distinct_block.argtypes = [vp, i32]
     L.clip_amd_bench_search_distinct.restype = C.c_float
     L.clip_amd_bench_search_distinct.argtypes = [i32, i64, i32, i32, i32, i32, C.c_float, i32, i32]
+    L.clip_amd_index_search_mmr.restype = C.c_bool
+    L.clip_amd_index_search_mmr.argtypes = [vp, f32p, i32, i32, C.c_float, i32, u64p, f32p, i64p, f32p]
+    L.clip_amd_index_search_mmr_device.restype = C.c_bool
+    L.clip_amd_index_search_mmr_device.argtypes = [vp, vp, i32, i32, C.c_float, i32, vp, vp, vp, vp]
+    L.clip_amd_index_search_ids_mmr.restype = C.c_bool
+    L.clip_amd_index_search_ids_mmr.argtypes = [vp, i64p, i32, i32, C.c_float, i32, i32, u64p, f32p, i64p, f32p]
+    L.clip_amd_test_index_mmr_route.restype = i32
+    L.clip_amd_test_index_mmr_route.argtypes = [vp, i32]
+    L.clip_amd_bench_search_mmr.restype = C.c_float
+    L.clip_amd_bench_search_mmr.argtypes = [i32, i64, i32, i32, i32, i32, C.c_float, i32, i32]
     L.clip_amd_index_search_compound.restype = C.c_bool
     L.clip_amd_index_search_compound.argtypes = [vp, f32p, i64p, C.POINTER(C.c_int32), f32p, i64p, i32, i32, i32, u64p, f32p, i64p]
     L.clip_amd_index_search_compound_device.restype = C.c_bool
@@ -996,6 +1008,10 @@ class Index:
     a row within `radius` (the distance of pairs) of an earlier kept row is dropped and counted for it; search_ids_distinct does the same
     with stored rows as the queries.  Suppression is over the pool, not the whole index.
 
+    search_mmr(queries, k, lam) diversifies the result (maximal marginal relevance): over the query's `pool` nearest rows, greedily the row
+    of the lowest lam * (distance to the query) - (1 - lam) * (distance of pairs to the nearest row already picked); search_ids_mmr does
+    the same with stored rows as the queries.  One fused kernel per call (k_mmr.hip); selection is over the pool, not the whole index.
+
     search_compound(queries, k) takes compound queries of 1 ... 8 terms each, a term being a vector or a stored row's id with a kind: "all"
     terms rank (a row's score is its distance to its WORST all-term), "within" / "beyond" terms keep the rows at most / more than a bound
     away, and an "over" term keeps the rows that are farther from it than their score plus a bound ("a beach" but not "people")."""
@@ -1260,6 +1276,65 @@ class Index:
                                                            C.c_void_p(d_allow or None), C.c_void_p(d_distances or None), C.c_void_p(d_ids or None),
                                                            C.c_void_p(d_counts or None)):
             raise RuntimeError("clip_amd_index_search_distinct_device failed (see stderr)")
+
+    @classmethod
+    def _mmr_args(cls, k, lam, pool):
+        """(k, lam, pool) of a diversified search after the checks of the library that need no device (ValueError): k and pool as
+        _distinct_args, and lam a number in [0, 1]."""
+        k, _, pool = cls._distinct_args(k, 0.0, pool)
+        lam = float(lam)
+        if lam != lam:
+            raise ValueError("lambda is NaN")
+        if lam < 0.0 or lam > 1.0:
+            raise ValueError("lambda = %g outside 0 ... 1" % lam)
+        return k, lam, pool
+
+    def search_mmr(self, queries, k, lam, pool=0, allow=None):
+        """Diversified search (maximal marginal relevance).  The pool L is search(query, pool, allow) without its empty tail.  Greedy: with
+        S the members picked so far, the next pick is the unpicked member x of the lowest score = lam * dq(x) - (1 - lam) * m(x), dq the
+        query distance search reports, m(x) the least distance of pairs between x and a member of S (0 at the first pick), in f32 with a
+        rounding per operation and mu = float32(1) - float32(lam); equal scores: the lower pool rank.  Returns (distances f32 [nq, k]: dq of
+        the picks, ids int64 [nq, k], gaps f32 [nq, k]: m at the moment of the pick, +inf for the first); +inf / -1 / +inf where the pool
+        has fewer than k members.  Selection is over the pool, not the whole index.  lam = 1: search's first k; lam = 0: farthest-first
+        over the pool from the nearest member.  1 <= k <= pool <= 1024; pool 0: min(1024, max(64, 8 k)).  ValueError for a wrong shape of
+        queries, k > pool, or a lam that is NaN or outside [0, 1]."""
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim not in (1, 2) or q.shape[-1] != self.dim:
+            raise ValueError("queries must be [n, %d] (or one vector of %d values), not %r" % (self.dim, self.dim, q.shape))
+        q = np.ascontiguousarray(q).reshape(-1, self.dim)
+        k, lam, pool = self._mmr_args(k, lam, pool)
+        nq = q.shape[0]
+        words, wp = self._allow(allow)
+        dist = np.empty((nq, k), dtype=np.float32)
+        ids = np.empty((nq, k), dtype=np.int64)
+        gaps = np.empty((nq, k), dtype=np.float32)
+        if not lib().clip_amd_index_search_mmr(self._live(), _fp(q), nq, k, lam, pool, wp, _fp(dist), ids.ctypes.data_as(C.POINTER(C.c_int64)),
+                                               _fp(gaps)):
+            raise RuntimeError("clip_amd_index_search_mmr failed (see stderr)")
+        return dist, ids, gaps
+
+    def search_ids_mmr(self, ids, k, lam, pool=0, exclude_self=True, allow=None):
+        """search_mmr with the stored rows `ids` (each a live id; duplicates are fine) as the queries, bit for bit as search_ids takes
+        them.  exclude_self: the query's own row is not in the pool.  Returns (distances, ids, gaps) as search_mmr."""
+        a = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        k, lam, pool = self._mmr_args(k, lam, pool)
+        words, wp = self._allow(allow)
+        dist = np.empty((a.size, k), dtype=np.float32)
+        out = np.empty((a.size, k), dtype=np.int64)
+        gaps = np.empty((a.size, k), dtype=np.float32)
+        if not lib().clip_amd_index_search_ids_mmr(self._live(), a.ctypes.data_as(C.POINTER(C.c_int64)), a.size, k, lam, pool,
+                                                   int(bool(exclude_self)), wp, _fp(dist), out.ctypes.data_as(C.POINTER(C.c_int64)), _fp(gaps)):
+            raise RuntimeError("clip_amd_index_search_ids_mmr failed (see stderr)")
+        return dist, out, gaps
+
+    def search_mmr_device(self, d_queries, n_queries, k, lam, d_distances, d_ids, d_gaps, pool=0, d_allow=None):
+        """search_mmr on device pointers (ints): queries [n, dim] f32, d_allow uint64 words (0 / None: every row) -> distances [n, k] f32,
+        ids [n, k] int64, gaps [n, k] f32; asynchronous on the context's stream."""
+        k, lam, pool = self._mmr_args(k, lam, pool)
+        if not lib().clip_amd_index_search_mmr_device(self._live(), C.c_void_p(d_queries or None), int(n_queries), k, lam, pool,
+                                                      C.c_void_p(d_allow or None), C.c_void_p(d_distances or None), C.c_void_p(d_ids or None),
+                                                      C.c_void_p(d_gaps or None)):
+            raise RuntimeError("clip_amd_index_search_mmr_device failed (see stderr)")
 
     COMPOUND_KINDS = {"all": 0, "within": 1, "beyond": 2, "over": 3}
     MAX_TERMS = 8
@@ -2186,6 +2261,13 @@ def bench_search_sets(dtype, n, dim, n_sets, set_size, k, group_size, iters=10):
     r // group_size, 0: no groups (clip_amd_bench_search_sets); < 0 on error."""
     return float(lib().clip_amd_bench_search_sets(Index.DTYPES[dtype], int(n), int(dim), int(n_sets), int(set_size), int(k), int(group_size),
                                                   int(iters)))
+
+
+def bench_search_mmr(dtype, n, dim, n_queries, k, pool, lam, copies=4, iters=10):
+    """Microseconds per clip_amd_index_search_mmr_device over the gallery of bench_search_distinct (clip_amd_bench_search_mmr); < 0 on
+    error."""
+    return float(lib().clip_amd_bench_search_mmr(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(k), int(pool), float(lam),
+                                                 int(copies), int(iters)))
 
 
 def bench_search_distinct(dtype, n, dim, n_queries, k, pool, radius, copies=4, iters=10):

@@ -625,6 +625,16 @@ void launch_distinct_pick(const float * pool_dist, const int64_t * pool_ids, con
                           int64_t * ids, int * counts, hipStream_t stream);
 void launch_distinct_plant(float * x, int64_t rows, int dim, int64_t first_row, int copies, float amp, uint64_t seed, hipStream_t stream);
 
+// Diversified search (k_mmr.hip).  The pools as for the distinct search; one launch walks every query's pool: k times the unpicked member
+// of the lowest lambda * dq - mu * m (three f32 roundings; m: the least pair distance to a picked member, 0 at the first pick; ties to the
+// lower rank) into dist / ids / gaps ([nq][k], tail +inf / -1 / +inf; gaps: m at the pick, +inf for the first).  resident: the pool's rows
+// are gathered into LDS once (only where mmr_resident_fits says so: launch_mmr returns false otherwise); else every pick reads them from
+// the store.  Both give the same bits.  mmr_lds_bytes: the dynamic LDS of a launch.
+size_t mmr_lds_bytes(int pool, int64_t row_bytes, bool resident);
+bool mmr_resident_fits(int pool, int64_t row_bytes);
+bool launch_mmr(const void * rows, const float * rinv, int Dpad, int dtype, const float * pool_dist, const int64_t * pool_ids, int nq, int pool,
+                int k, float lambda, float mu, bool resident, float * dist, int64_t * ids, float * gaps, hipStream_t stream);
+
 // Compound queries (k_compound.hip).  The query workspace is term-major inside a block of 16 compound queries: workspace row
 // compound_row(c, t, tt) holds term t of query c, tt in {2, 4, 8} terms per query (absent terms: zero rows of kind -1).  Every per-row
 // array below (q, qinv, src, ids, kinds, bounds, xids) has compound_rows(nq, tt) entries in that layout.

@@ -5,6 +5,7 @@
 //   k_graph.hip     the k-NN graph and the search of one index with the rows of another (the tiled kernel in the scan's place)
 //   k_sets.hip      searches with query sets (the set fold in the finish's place)
 //   k_distinct.hip  distinct searches (the pools of a search, then the near bitmap and the walk)
+//   k_mmr.hip       diversified searches (the pools of a search, then one fused greedy walk per query)
 //   k_compound.hip  compound queries (the placement and the scan in front of the same merge tree)
 //   k_join.hip      range search and pairs (count -> lims -> scatter -> sort -> finish)
 //   k_components.hip, k_modes.hip, k_linkage.hip, k_extents.hip, k_spread.hip, k_closest.hip
@@ -40,6 +41,7 @@ constexpr int64_t HOST_CHUNK_ROWS = 65536;              // rows per staging copy
 constexpr int64_t JOIN_HIT_BUDGET = (int64_t)1 << 21;    // hits the first scoring pass keeps (24 MB); more only when the caller's capacity asks
 constexpr size_t GRAPH_OUT_BUDGET = (size_t)128 << 20;  // bytes of results one query block of the k-NN graph leaves on the device
 constexpr size_t DISTINCT_NEAR_BUDGET = (size_t)64 << 20;   // bytes of near bitmap per query block of a distinct search
+constexpr int MMR_BLOCK = 1024;                             // queries per block of a diversified search (12 MB of pools at pool 1024)
 
 size_t row_stride(const clip_amd_index * ix) { return (size_t)ix->Dpad * ix->es; }      // bytes from one stored row to the next
 
@@ -894,6 +896,17 @@ int distinct_block_size(const clip_amd_index * ix, int pool) {
     return (int)std::min<size_t>(DISTINCT_BLOCK_MAX, std::max<size_t>(1, DISTINCT_NEAR_BUDGET / near_q));
 }
 
+// The route of a diversified search (k_mmr.hip): the pool's rows resident in LDS when they fit next to the walk state, unless the test
+// hook asks for streaming; streaming otherwise.  The hook's "resident" is a demand: false (refused) for a pool that cannot fit, so a
+// call that succeeds under it ran the resident kernel.
+bool mmr_route(const clip_amd_index * ix, int pool, bool & resident) {
+    resident = ix->mmr_route != 2 && mmr_resident_fits(pool, (int64_t)ix->Dpad * (int64_t)ix->es);
+    if (ix->mmr_route != 1 || resident) return true;
+    fprintf(stderr, "clip_amd_index_search_mmr: the resident route was asked for (test hook), but pool = %d rows of %lld bytes do not fit the LDS\n",
+            pool, (long long)ix->Dpad * (long long)ix->es);
+    return false;
+}
+
 }  // namespace
 
 // Distinct search on the device: query blocks one after another, each searched with k = pool into the pool workspace (the [m][pool]
@@ -914,6 +927,30 @@ bool idx::distinct_device_impl(clip_amd_index * ix, const QuerySource & src, int
         launch_distinct_pick(p_dist, p_ids, (const uint32_t *)ix->dnear.p, m, pool, k, d_dist + (size_t)q0 * k, d_ids + (size_t)q0 * k,
                              d_counts + (size_t)q0 * k, st);
         if (!launched(true, "clip_amd_index_search_distinct")) return false;
+    }
+    return true;
+}
+
+// Diversified search on the device: query blocks one after another, each searched with k = pool into the pool workspace of the distinct
+// search, then the walk of k_mmr.hip into d_dist / d_ids / d_gaps ([nq][k], device).  A query's pool and walk are its own, so the cut into
+// blocks does not show in the result.
+bool idx::mmr_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, int k, float lambda, int pool, const uint32_t * d_allow,
+                          float * d_dist, int64_t * d_ids, float * d_gaps) {
+    hipStream_t st = stream_of(ix);
+    const int block = std::min(MMR_BLOCK, nq);
+    const size_t slots = (size_t)block * pool;
+    if (!ensure(ix, ix->dpool, slots * 12)) return false;
+    int64_t * p_ids = (int64_t *)ix->dpool.p;
+    float * p_dist = (float *)((char *)ix->dpool.p + slots * 8);
+    const float mu = 1.0f - lambda;
+    bool resident = false;
+    if (!mmr_route(ix, pool, resident)) return false;
+    for (int q0 = 0; q0 < nq; q0 += block) {
+        const int m = std::min(block, nq - q0);
+        if (!search_device_impl(ix, advance(src, q0, ix->dim), m, pool, d_allow, p_dist, p_ids)) return false;
+        const bool ok = launch_mmr(ix->store.rows, ix->store.rinv, ix->Dpad, ix->dtype, p_dist, p_ids, m, pool, k, lambda, mu, resident,
+                                   d_dist + (size_t)q0 * k, d_ids + (size_t)q0 * k, d_gaps + (size_t)q0 * k, st);
+        if (!launched(ok, "clip_amd_index_search_mmr")) return false;
     }
     return true;
 }
@@ -946,6 +983,27 @@ bool distinct_host_impl(clip_amd_index * ix, const float * queries, const int64_
     return true;
 }
 
+// The host forms of the diversified searches, block by block as distinct_host_impl
+bool mmr_host_impl(clip_amd_index * ix, const float * queries, const int64_t * ids, int nq, int k, float lambda, int pool, bool exclude_self,
+                   const uint64_t * allow, float * distances, int64_t * out_ids, float * gaps, const char * fn) {
+    const uint32_t * d_allow = nullptr;
+    const int block = std::min(MMR_BLOCK, nq);
+    const size_t slots = (size_t)block * k;
+    Arena a(ix);
+    const auto o_ids = a.add(out_ids, slots);
+    const auto o_dist = a.add(distances, slots);
+    const auto o_gaps = a.add(gaps, slots);
+    if (!upload_allow(ix, allow, d_allow) || !a.ready() || !reserve_stage(ix, queries, ids, block)) return false;
+    for (int q0 = 0; q0 < nq; q0 += block) {
+        const int m = std::min(block, nq - q0);
+        const QuerySource qs = stage_block(ix, queries, ids, q0, m, exclude_self);
+        if (!mmr_device_impl(ix, qs, m, k, lambda, pool, d_allow, a.dev(o_dist), a.dev(o_ids), a.dev(o_gaps))) return false;
+        a.queue(0, a.n, 0, (size_t)q0 * k, (size_t)m * k);
+        if (!stream_done(ix, fn)) return false;                // (the staging buffers and the block's results are reused)
+    }
+    return true;
+}
+
 // what the distinct searches ask beyond check_search_args; pool 0 becomes the automatic value
 bool check_distinct_args(const clip_amd_index * ix, int nq, int k, float radius, int & pool, const void * counts, const char * fn) {
     if (nq < 1) { fprintf(stderr, "%s: n_queries %d < 1\n", fn, nq); return false; }
@@ -956,6 +1014,13 @@ bool check_distinct_args(const clip_amd_index * ix, int nq, int k, float radius,
     if (k > pool) { fprintf(stderr, "%s: k = %d exceeds pool = %d\n", fn, k, pool); return false; }
     if (ix->n == 0) { fprintf(stderr, "%s: the index is empty (0 rows)\n", fn); return false; }
     return true;
+}
+
+// the same for the diversified searches: lambda in [0, 1] in the radius's place
+bool check_mmr_args(const clip_amd_index * ix, int nq, int k, float lambda, int & pool, const void * gaps, const char * fn) {
+    if (std::isnan(lambda)) { fprintf(stderr, "%s: lambda is NaN\n", fn); return false; }
+    if (lambda < 0.f || lambda > 1.f) { fprintf(stderr, "%s: lambda = %g outside 0 ... 1\n", fn, (double)lambda); return false; }
+    return check_distinct_args(ix, nq, k, 0.f, pool, gaps, fn);
 }
 
 // the groups of a host form: each of the n >= 0 (NULL: no groups)
@@ -2361,6 +2426,37 @@ bool clip_amd_index_search_ids_distinct(struct clip_amd_index * ix, const int64_
         (void)hipSetDevice(ix->device);
         if (!check_stored_ids(ix, ids, n_ids, fn)) return false;
         return distinct_host_impl(ix, nullptr, ids, n_ids, k, radius, pool, exclude_self != 0, allow, distances, out_ids, counts, fn);
+    });
+}
+
+bool clip_amd_index_search_mmr_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int k, float lambda, int pool,
+                                      const uint64_t * d_allow, float * d_distances, int64_t * d_ids, float * d_gaps) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_search_args(ix, d_queries, n_queries, k, d_distances, d_ids, fn)) return false;
+        if (!check_mmr_args(ix, n_queries, k, lambda, pool, d_gaps, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return mmr_device_impl(ix, vectors(d_queries), n_queries, k, lambda, pool, (const uint32_t *)d_allow, d_distances, d_ids, d_gaps);
+    });
+}
+
+bool clip_amd_index_search_mmr(struct clip_amd_index * ix, const float * queries, int n_queries, int k, float lambda, int pool,
+                               const uint64_t * allow, float * distances, int64_t * ids, float * gaps) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_search_args(ix, queries, n_queries, k, distances, ids, fn)) return false;
+        if (!check_mmr_args(ix, n_queries, k, lambda, pool, gaps, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        return mmr_host_impl(ix, queries, nullptr, n_queries, k, lambda, pool, false, allow, distances, ids, gaps, fn);
+    });
+}
+
+bool clip_amd_index_search_ids_mmr(struct clip_amd_index * ix, const int64_t * ids, int n_ids, int k, float lambda, int pool, int exclude_self,
+                                   const uint64_t * allow, float * distances, int64_t * out_ids, float * gaps) {
+    return guarded(__func__, false, [&](const char * fn) {
+        if (!check_search_args(ix, ids, n_ids, k, distances, out_ids, fn)) return false;
+        if (!check_mmr_args(ix, n_ids, k, lambda, pool, gaps, fn)) return false;
+        (void)hipSetDevice(ix->device);
+        if (!check_stored_ids(ix, ids, n_ids, fn)) return false;
+        return mmr_host_impl(ix, nullptr, ids, n_ids, k, lambda, pool, exclude_self != 0, allow, distances, out_ids, gaps, fn);
     });
 }
 

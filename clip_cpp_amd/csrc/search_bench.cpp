@@ -127,6 +127,7 @@ extern "C" {
 
 int64_t clip_amd_test_index_sets_block(struct clip_amd_index * ix, int64_t rows) { return set_hook(ix, &clip_amd_index::sets_block, rows, GRAPH_BLOCK_MAX); }
 int clip_amd_test_index_distinct_block(struct clip_amd_index * ix, int queries) { return set_hook(ix, &clip_amd_index::distinct_block, queries, DISTINCT_BLOCK_MAX); }
+int clip_amd_test_index_mmr_route(struct clip_amd_index * ix, int route) { return set_hook(ix, &clip_amd_index::mmr_route, route, 2); }
 int clip_amd_test_index_compound_block(struct clip_amd_index * ix, int queries) { return set_hook(ix, &clip_amd_index::compound_block, queries, 1024); }
 int64_t clip_amd_test_index_vote_block(struct clip_amd_index * ix, int64_t rows) { return set_hook(ix, &clip_amd_index::vote_block, rows, GRAPH_BLOCK_MAX); }
 int clip_amd_test_index_cross_route(struct clip_amd_index * ix, int route) { return set_hook(ix, &clip_amd_index::cross_route, route, 2); }
@@ -202,6 +203,27 @@ float clip_amd_bench_search_distinct(int dtype, int64_t n, int dim, int n_querie
             return time_device(iters, [&]() {
                 return distinct_device_impl(ix, vectors(src), n_queries, k, radius, pool, nullptr, a.dev(o_dist, true), a.dev(o_ids, true),
                                             a.dev(o_counts, true));
+            });
+        });
+    });
+}
+
+float clip_amd_bench_search_mmr(int dtype, int64_t n, int dim, int n_queries, int k, int pool, float lambda, int copies, int iters) {
+    return guarded(__func__, -4.f, [&](const char *) {
+        if (pool == 0 && k >= 1 && k <= MAX_K) pool = auto_pool(k);
+        const bool args_ok = n_queries >= 1 && k >= 1 && k <= pool && pool <= MAX_K && lambda >= 0.f && lambda <= 1.f && copies >= 1 &&
+                             copies < GALLERY_PIECE_ROWS;
+        return bench_on_gallery(dtype, n, dim, n_queries, iters, args_ok, copies, [&](clip_amd_index * ix, float * src) {
+            Buf own;
+            Arena a(ix, own);
+            const auto o_dist = a.add<float>(nullptr, (size_t)n_queries * k);
+            const auto o_ids = a.add<int64_t>(nullptr, (size_t)n_queries * k);
+            const auto o_gaps = a.add<float>(nullptr, (size_t)n_queries * k);
+            if (!a.ready()) return -4.f;
+            launch_search_fill_random(src, (int64_t)n_queries * dim, 0xC0FFEEull, nullptr);
+            return time_device(iters, [&]() {
+                return mmr_device_impl(ix, vectors(src), n_queries, k, lambda, pool, nullptr, a.dev(o_dist, true), a.dev(o_ids, true),
+                                       a.dev(o_gaps, true));
             });
         });
     });

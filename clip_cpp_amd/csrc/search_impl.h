@@ -63,6 +63,7 @@ struct clip_amd_index {
     Buf dpool;                     // distinct search: distances + ids of one query block's pools
     Buf dnear;                     // distinct search: the near bitmap of one query block
     int distinct_block = 0;        // clip_amd_test_index_distinct_block: queries per block, 0 automatic
+    int mmr_route = 0;             // clip_amd_test_index_mmr_route: 0 automatic, 1 resident (a pool that does not fit the LDS is refused), 2 streaming
     Buf cprep;                     // compound queries: the vector terms of one query block in the stored form
     Buf cpinv;                     // compound queries, i8: their inverse norms
     Buf cmeta;                     // compound queries: source, id, kind and bound of every workspace row of one query block
@@ -254,6 +255,8 @@ bool sets_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, cons
                       bool own, const uint32_t * d_allow, float * d_dist, int64_t * d_ids, int * d_qrows, int64_t qrow_base, bool first_kept);
 bool distinct_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, int k, float radius, int pool, const uint32_t * d_allow,
                           float * d_dist, int64_t * d_ids, int * d_counts);
+bool mmr_device_impl(clip_amd_index * ix, const QuerySource & src, int nq, int k, float lambda, int pool, const uint32_t * d_allow, float * d_dist,
+                     int64_t * d_ids, float * d_gaps);
 bool compound_device_impl(clip_amd_index * ix, const float * d_terms, int64_t origin, const CompoundCall & cc, int c_lo, int nq,
                           const uint32_t * d_allow, float * d_dist, int64_t * d_ids);
 bool knn_graph_impl(clip_amd_index * ix, int k, float * distances, int64_t * ids, const char * fn);

@@ -5,6 +5,7 @@ build.cpp / search.cpp) on the exact GPU index of this library (`clip_cpp_amd.In
     python -m clip_cpp_amd.image_search update [-m MODEL] [-v N] [-t N] [--db DIR] dir [more dirs]
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N [--offset O] | -d R] [--distinct R] [--in PREFIX]... [--db DIR] <search text or /path/to/query/image>
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-n N] [--distinct R] [--in PREFIX]... [--db DIR] --like INDEXED/IMAGE/PATH
+    python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N] --diverse L [--in PREFIX]... [--db DIR] <query or --like PATH>
     python -m clip_cpp_amd.image_search search [-m MODEL] [-v N] [-t N] [-n N] [--in PREFIX]... [--db DIR] [--and TERM]... [--not TERM]... [--not-margin M] <query or --like PATH>
     python -m clip_cpp_amd.image_search dedup  [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R] [--prune] [--extents]
     python -m clip_cpp_amd.image_search albums [-m MODEL] [-v N] [--db DIR] [-d R | --max-distance R] [--link T] [--min N] [-n COUNT]
@@ -86,6 +87,12 @@ Index.search_ids_distinct): walking the ranked list, an image within distance R 
 is dropped, and a listed image that stands for dropped ones gets " (+%d)", their number, behind its path.  The suppression runs over the
 pool of the max(64, 8 N) nearest eligible images (at most 1024), not over the whole index.  It works with -n, --in and --like, not with
 -d, and not on a database built with --grid.
+`search --diverse L` (L in 0 ... 1) diversifies the list (Index.search_mmr / Index.search_ids_mmr, maximal marginal relevance): among the
+pool of the max(64, 8 N) nearest eligible images (at most 1024), again and again the image of the lowest L * (distance to the query) -
+(1 - L) * (distance to the nearest image already listed), so twelve frames of one burst no longer fill the first screen.  L = 1 is the
+plain search, L = 0 farthest-first over the pool.  Each line is "%f<TAB>%f<TAB>%s" = distance, gap, path ("distance<TAB>gap<TAB>path" is
+the heading), the gap being the distance to the nearest image listed above it (inf for the first).  It works with -n (at most 1024), --in
+and --like, not with -d, --distinct, --debias, --prob, --and / --not, --offset or a database built with --grid.
 `search --prob [--scale S]` and `label --prob [--scale S]` say how sure a hit is (Index.softmax / softmax_ids / softmax_index): the same
 hits in the same order, each line "  %f %f %s" = distance, probability, path (or label), the probability being the softmax of -S * distance
 over EVERY eligible image (every label), not over the printed ones; `search` ends with "main: log Z %f at scale %g".  S defaults to 100,
@@ -254,7 +261,7 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
             if not dedup:
                 takes.update({"-n": "results", "--results": "results"})
         if search:
-            takes.update({"--in": "in", "--like": "like", "--distinct": "distinct", "--and": "and", "--not": "not", "--not-margin": "not_margin",
+            takes.update({"--in": "in", "--like": "like", "--distinct": "distinct", "--diverse": "diverse", "--and": "and", "--not": "not", "--not-margin": "not_margin",
                           "--offset": "offset"})
         if search or label:
             takes["--scale"] = "scale"
@@ -272,10 +279,13 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
                 i += 1
                 continue
             try:
-                p[key] = int(argv[i]) if key in ("threads", "verbose", "results", "grid", "min_size", "core", "offset") else float(argv[i]) if key in ("max_distance", "distinct", "not_margin", "link", "scale") else argv[i]
+                p[key] = int(argv[i]) if key in ("threads", "verbose", "results", "grid", "min_size", "core", "offset") else float(argv[i]) if key in ("max_distance", "distinct", "diverse", "not_margin", "link", "scale") else argv[i]
             except ValueError:
                 return None
-            if key in ("max_distance", "distinct", "not_margin", "link", "scale") and p[key] != p[key]:      # NaN
+            if key in ("max_distance", "distinct", "diverse", "not_margin", "link", "scale") and p[key] != p[key]:      # NaN
+                return None
+            if key == "diverse" and not 0.0 <= p[key] <= 1.0:
+                print("main: --diverse takes L in 0 ... 1 (1: relevance only, 0: diversity only), not %s" % argv[i])
                 return None
             if key == "scale" and not 0.0 < p[key] < float("inf"):
                 print("main: --scale takes a finite value > 0 (100: the logit scale CLIP is trained to), not %s" % argv[i])
@@ -337,6 +347,11 @@ def _parse(argv, build, dedup=False, update=False, neighbors=False, label=False,
         return None
     if match and len(p["rest"]) > 1:
         print("main: match takes one image path, or none for every indexed image")
+        return None
+    if "diverse" in seen and (p.get("prob") or p.get("debias") or p["results"] > MAX_K or
+                              seen & {"max_distance", "distinct", "and", "not", "not_margin", "offset"}):
+        print("main: --diverse L re-ranks the -n nearest images (n <= %d) of a query or of --like: it works with -n and --in, not with -d,"
+              " --distinct, --debias, --prob, --and, --not or --offset" % MAX_K)
         return None
     if seen & {"and", "not", "not_margin"}:
         if "max_distance" in seen or "distinct" in seen:
@@ -547,6 +562,10 @@ def _help(build, p, dedup=False, update=False, neighbors=False, label=False, mer
               " of `dedup -d R`) of an image already listed is dropped, and a listed image is followed by (+N), the number of images dropped"
               " for it. Suppression runs over the max(64, 8 N) nearest eligible images (at most %d), not the whole index. Works with -n, --in"
               " and --like, not with -d" % MAX_K)
+        print("  --diverse L: diversify the list (maximal marginal relevance, L in 0 ... 1): among the max(64, 8 N) nearest eligible images (at"
+              " most %d), again and again the image of the lowest L * distance - (1 - L) * gap, the gap being the distance to the nearest image"
+              " already listed; prints `distance<TAB>gap<TAB>path`. L = 1: the plain search. Works with -n (<= %d), --in and --like, not with"
+              " -d, --distinct, --debias, --prob, --and / --not, --offset or a --grid database" % (MAX_K, MAX_K))
         print("  --and <term>: a compound search: rank by the WORST term, an image's distance is its largest distance to the query and to every"
               " --and term, so only an image near all of them comes first; may be repeated. A term with an image extension is an image: one"
               " that equals a line of %s is that indexed image (its stored row; it is not listed itself), any other is a file to load and"
@@ -879,6 +898,8 @@ def search(argv):
     img_path, text = classify_query(p["rest"])
     if p.get("distinct") is not None and _refuse_gridded(p["db"], "search --distinct"):
         return 1
+    if p.get("diverse") is not None and _refuse_gridded(p["db"], "search --diverse"):
+        return 1
     if p.get("prob") and _refuse_gridded(p["db"], "search --prob"):
         return 1
     if p.get("debias") and _refuse_gridded(p["db"], "search --debias"):
@@ -979,6 +1000,16 @@ def search(argv):
             dist, ids, counts = index.search_distinct(vec[None, :], k, p["distinct"], allow=allow)
         hits = [(d, i) for d, i in zip(dist[0], ids[0]) if i >= 0 and p["results"] > 0]
         more = {int(i): int(c) for i, c in zip(ids[0], counts[0]) if i >= 0 and c > 0}
+    elif p.get("diverse") is not None:             # maximal marginal relevance over the pool of the nearest (n <= MAX_K: _parse)
+        k = max(1, p["results"])
+        if len(index) == 0:                        # (the library refuses an empty index)
+            dist, ids, gaps = np.zeros((1, 0), np.float32), np.zeros((1, 0), np.int64), np.zeros((1, 0), np.float32)
+        elif like_id is not None:
+            dist, ids, gaps = index.search_ids_mmr([like_id], k, p["diverse"], allow=allow)
+        else:
+            dist, ids, gaps = index.search_mmr(vec[None, :], k, p["diverse"], allow=allow)
+        hits = [(d, i) for d, i in zip(dist[0], ids[0]) if i >= 0 and p["results"] > 0]
+        gap = {int(i): float(g) for g, i in zip(gaps[0], ids[0]) if i >= 0}
     elif p.get("prob"):                            # the same hits in the same order, each with its probability over every eligible image
         k = max(1, min(p["results"], MAX_K))
         scale = p.get("scale", PROB_SCALE)
@@ -1012,9 +1043,12 @@ def search(argv):
                 break
     if p["verbose"] > 0:
         print("search results:")
-        print("distance probability path" if p.get("prob") else "score distance path" if bias is not None else "distance path")
+        print("distance probability path" if p.get("prob") else "score distance path" if bias is not None else
+              "distance\tgap\tpath" if p.get("diverse") is not None else "distance path")
     for d, i in hits:
-        if p.get("prob"):
+        if p.get("diverse") is not None:
+            print("%f\t%f\t%s" % (d, gap[int(i)], image_paths[i]))
+        elif p.get("prob"):
             print("  %f %f %s" % (d, prob[int(i)], image_paths[i]))
         elif bias is not None:
             print("  %f %f %s" % (score[int(i)], d, image_paths[i]))

@@ -357,6 +357,46 @@ int clip_amd_test_index_distinct_block(struct clip_amd_index * ix, int queries);
  * value, before normalisation: seeded random rows alone have no near pairs and the walk would never suppress anything); < 0 on error.
  * Used by scripts/distinct_bench.py. */
 float clip_amd_bench_search_distinct(int dtype, int64_t n, int dim, int n_queries, int k, int pool, float radius, int copies, int iters);
+/* Diversified search: maximal marginal relevance (MMR), a result list that trades relevance against redundancy with one dial.  Inputs: a
+ * query, k, lambda in [0, 1], pool P and allow.
+ * Pool: L is the query's result from clip_amd_index_search_subset(ix, q, 1, P, allow), exactly the pool of the distinct search: the P
+ * nearest eligible rows in search's order; empty tail slots are not members.  SELECTION IS OVER THE POOL, NOT THE WHOLE INDEX.
+ * Selection: greedy.  With S the members picked so far, the next pick is the unpicked member x of the lowest
+ *     score(x) = lambda * dq(x) - mu * m(x)
+ * dq(x): the query-to-row distance, the bits search reports.  mu: the f32 value 1.0f - lambda, computed once on the host.  m(x): the
+ * minimum over s in S of d(min(x, s), max(x, s)), d(i, j) for i < j being exactly the distance clip_amd_index_pairs defines for that pair
+ * (as in the distinct search); for the first pick m(x) = 0.  The score is three f32 operations with a rounding each and no FMA
+ * contraction: round(round(lambda * dq) - round(mu * m)).  Equal scores: the lower pool rank first.  The order is total, so the result is
+ * exact, bit-reproducible, and independent of the other queries of the call and of how the call is cut into blocks.
+ * Outputs per query: distances [k] f32 (dq of the pick), ids [k] int64, gaps [k] f32: m(x) at the moment of the pick, +INFINITY for the
+ * first pick (its score used 0).  The score of a pick is recomputable from the three.  A pool with fewer than k members ends the list
+ * early.  Tail: +INFINITY / -1 / +INFINITY.
+ * Consequences: lambda = 1 gives search_subset's first k, bit for bit; lambda = 0 gives farthest-first over the pool, starting at the
+ * nearest member; a duplicate of an already picked row has gap 0 (up to the rounding of 1 - dot of the stored values) and sinks: its diversity
+ * term is 0, so it competes on lambda * dq alone.
+ * Limits: 1 <= k <= pool <= 1024; pool == 0 is automatic: min(1024, max(64, 8 k)).  A NaN lambda, a lambda outside [0, 1], a pool outside
+ * the range, an empty index, n_queries < 1 and everything search_subset refuses return false with a message that names the value; nothing
+ * is launched and the outputs are untouched.
+ * Host form: host arrays, synchronous, query blocks one after another (device memory beyond the index does not grow with n_queries).
+ * Device form: queries, allow (trusted) and the three outputs in HBM, asynchronous on the context's stream.  search_ids_mmr: the queries
+ * are the stored rows ids[0 ... n_ids), gathered bit for bit as search_ids does; an id out of range or removed returns false, names the id
+ * and leaves the outputs untouched.  exclude_self != 0: the query's own row is not in the pool. */
+bool clip_amd_index_search_mmr(struct clip_amd_index * ix, const float * queries, int n_queries, int k, float lambda, int pool,
+                               const uint64_t * allow, float * distances, int64_t * ids, float * gaps);
+bool clip_amd_index_search_mmr_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, int k, float lambda, int pool,
+                                      const uint64_t * d_allow, float * d_distances, int64_t * d_ids, float * d_gaps);
+bool clip_amd_index_search_ids_mmr(struct clip_amd_index * ix, const int64_t * ids, int n_ids, int k, float lambda, int pool, int exclude_self,
+                                   const uint64_t * allow, float * distances, int64_t * out_ids, float * gaps);
+/* test hook: the route of the diversified searches on this index from now on: 0 automatic (the pool's rows resident in LDS when they fit
+ * next to the walk state, else streamed from the store at every pick), 1 resident (a demand: a diversified search whose pool does not
+ * fit then returns false with a message and launches nothing, so a call that succeeds ran the resident kernel), 2 streaming.  Both routes
+ * give the same bits.  Returns the value set, -1 for a NULL index or another value. */
+int clip_amd_test_index_mmr_route(struct clip_amd_index * ix, int route);
+/* Average device time (microseconds, HIP events) of one clip_amd_index_search_mmr_device of n_queries seeded random queries over the
+ * gallery of clip_amd_bench_search_distinct (groups of a seeded random row and `copies` noisy copies); < 0 on error (-3: an argument
+ * outside the limits of search_mmr).  scripts/mmr_bench.py times whole calls on an index of its own instead; the hook is for quick
+ * device-time checks and is run by tests/test_gpu_search_mmr.py. */
+float clip_amd_bench_search_mmr(int dtype, int64_t n, int dim, int n_queries, int k, int pool, float lambda, int copies, int iters);
 /* Compound queries: a query is several terms ("a dog" and "on a beach"; like this stored picture and "at night"; "a beach" but not
  * "people"; ranked by A but only within R of image B).  A call holds n_queries compound queries; query c is the terms term_lims[c] ...
  * term_lims[c + 1] - 1 (term_lims: host int64 [n_queries + 1], starting at 0 and increasing, like set_lims), 1 ... 8 of them.
