@@ -13,7 +13,7 @@ SRC     := clip_cpp_amd/csrc
 OUT     := clip_cpp_amd/build
 CXXFLAGS := -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -Wno-unused-result -Wno-inline-asm -Wno-bitwise-instead-of-logical -Iinclude --offload-arch=$(ARCH) -DCLIPAMD_TEST_HOOKS=$(hooks)
 HOST    := gguf quant load forward tokenizer preprocess image_io image_formats jpeg_decode host_pipeline files_pipeline api test_hooks search search_bench
-KERNELS := k_attn k_attn_long k_attn_f32 k_misc k_preproc k_jpeg k_gemm k_gemm8 k_gemm4 k_gemm32 k_gemm_f32 k_skinny k_gemm_ring k_fold k_search k_join k_graph k_group k_sets k_distinct k_mmr k_compound k_components k_modes k_linkage k_spread k_extents k_closest k_vote k_rank k_softmax k_bias k_select
+KERNELS := k_attn k_attn_long k_attn_f32 k_misc k_preproc k_jpeg k_gemm k_gemm8 k_gemm4 k_gemm32 k_gemm_f32 k_skinny k_gemm_ring k_fold k_search k_join k_graph k_group k_sets k_distinct k_mmr k_compound k_components k_modes k_linkage k_spread k_extents k_closest k_vote k_rank k_softmax k_bias k_select k_classes
 WTS     := 0 1 2 3 4 5
 OBJS    := $(HOST:%=$(OUT)/%.cpp.o) $(KERNELS:%=$(OUT)/%.hip.o) $(WTS:%=$(OUT)/k_gemm_wt%.o) $(WTS:%=$(OUT)/k_skinny_wt%.o) $(WTS:%=$(OUT)/k_gemm_ring_wt%.o)
 
@@ -26,8 +26,8 @@ $(OUT)/%.cpp.o: $(SRC)/%.cpp $(wildcard $(SRC)/*.h) include/clip.h include/clip_
 	$(HIPCC) -x hip -fwrapv $(CXXFLAGS) -c $< -o $@
 # (the online-softmax attention kernels and the f32-file GEMM without the SLP vectoriser: same per-file flags as clip_cpp_amd/build.py EXTRA_FLAGS, which says why)
 $(OUT)/k_attn_f32.hip.o $(OUT)/k_attn_long.hip.o $(OUT)/k_gemm_f32.hip.o: CXXFLAGS += -fno-slp-vectorize
-# (the rank / count, softmax, closest-pairs and select kernels without packed f32 instructions: same flags as clip_cpp_amd/build.py NO_PACKED_F32, which says why)
-$(OUT)/k_rank.hip.o $(OUT)/k_softmax.hip.o $(OUT)/k_closest.hip.o $(OUT)/k_select.hip.o: CXXFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+# (the rank / count, softmax, closest-pairs, select and class-probability kernels without packed f32 instructions: same flags as clip_cpp_amd/build.py NO_PACKED_F32, which says why)
+$(OUT)/k_rank.hip.o $(OUT)/k_softmax.hip.o $(OUT)/k_closest.hip.o $(OUT)/k_select.hip.o $(OUT)/k_classes.hip.o: CXXFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 $(OUT)/%.hip.o: $(SRC)/%.hip $(wildcard $(SRC)/*.h) | $(OUT)
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@
 $(OUT)/k_gemm_wt%.o: $(SRC)/k_gemm.hip $(wildcard $(SRC)/*.h) | $(OUT)

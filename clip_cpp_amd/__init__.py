@@ -107,6 +107,7 @@ AMD_SYMBOLS = [
     "clip_amd_index_softmax", "clip_amd_index_softmax_device", "clip_amd_index_softmax_ids", "clip_amd_index_softmax_index", "clip_amd_bench_softmax",
     "clip_amd_index_search_biased", "clip_amd_index_search_biased_device", "clip_amd_index_search_ids_biased", "clip_amd_index_hubness",
     "clip_amd_index_hubness_device", "clip_amd_bench_search_biased",
+    "clip_amd_index_class_probs", "clip_amd_index_class_probs_ids", "clip_amd_index_class_probs_device", "clip_amd_bench_class_probs",
 ]
 
 _lib = None
@@ -451,6 +452,14 @@ def lib():
     L.clip_amd_index_softmax_index.argtypes = [vp, vp, i64p, i64, i32, C.c_float, u64p, f32p, i64p, f32p, f32p]
     L.clip_amd_bench_softmax.restype = C.c_float
     L.clip_amd_bench_softmax.argtypes = [i32, i64, i32, i32, i32, i32]
+    L.clip_amd_index_class_probs.restype = C.c_bool
+    L.clip_amd_index_class_probs.argtypes = [vp, f32p, i32, i32p, i32, i32, C.c_float, u64p, i32p, f32p, f32p, f32p]
+    L.clip_amd_index_class_probs_ids.restype = C.c_bool
+    L.clip_amd_index_class_probs_ids.argtypes = [vp, i64p, i64, i32p, i32, i32, C.c_float, i32, u64p, i32p, f32p, f32p, f32p]
+    L.clip_amd_index_class_probs_device.restype = C.c_bool
+    L.clip_amd_index_class_probs_device.argtypes = [vp, vp, i32, vp, i32, i32, C.c_float, vp, vp, vp, vp, vp]
+    L.clip_amd_bench_class_probs.restype = C.c_float
+    L.clip_amd_bench_class_probs.argtypes = [i32, i64, i32, i32, i32, i32]
     L.clip_amd_index_search_biased.restype = C.c_bool
     L.clip_amd_index_search_biased.argtypes = [vp, f32p, i32, i32, f32p, u64p, f32p, f32p, i64p]
     L.clip_amd_index_search_biased_device.restype = C.c_bool
@@ -2117,6 +2126,74 @@ class Index:
                                                    C.c_void_p(d_probs or None), C.c_void_p(d_log_z or None)):
             raise RuntimeError("clip_amd_index_softmax_device failed (see stderr)")
 
+    @staticmethod
+    def _class_args(m, scale, n_classes):
+        """(m, scale) of a class-probability call after the checks of the library that need no device (ValueError): 1 <= n_classes <=
+        65536, 1 <= m <= min(n_classes, 1024), scale a finite number > 0."""
+        m, scale = int(m), float(scale)
+        if not 1 <= n_classes <= 65536:
+            raise ValueError("class probabilities need 1 <= n_classes <= 65536, not %d (the largest label + 1)" % n_classes)
+        if not 1 <= m <= min(n_classes, 1024):
+            raise ValueError("class probabilities need 1 <= m <= min(n_classes, 1024), not m = %d, n_classes = %d" % (m, n_classes))
+        if scale != scale:
+            raise ValueError("scale is NaN")
+        if not 0.0 < scale < float("inf"):
+            raise ValueError("scale = %g is not a finite value > 0" % scale)
+        return m, scale
+
+    def _class_call(self, labels, m, scale, n, full):
+        """(labels kept alive, its pointer, n_classes, m, scale, outputs, their pointers) of a host class-probability call of n queries"""
+        lab, lp = self._labels(labels)
+        n_classes = max(int(lab.max()) + 1, 1) if lab.size else 1
+        m, scale = self._class_args(m, scale, n_classes)
+        outs = [np.empty((n + 1, m), dtype=np.int32)[:n], np.empty((n + 1, m), dtype=np.float32)[:n], np.empty(n + 1, dtype=np.float32)[:n]]
+        if full:
+            outs.append(np.empty((n + 1, n_classes), dtype=np.float32)[:n])
+        ptrs = [outs[0].ctypes.data_as(C.POINTER(C.c_int32))] + [_fp(o) for o in outs[1:]] + ([] if full else [None])
+        return lab, lp, n_classes, m, scale, tuple(outs), ptrs
+
+    def class_probs(self, queries, labels, m=1, scale=100.0, allow=None, full=False):
+        """Class probabilities over labelled rows, the soft form of `vote` (no k): `labels` (int [len]) is every row's class in 0 ...
+        n_classes - 1 or -1 for an unlabelled row, n_classes = labels.max() + 1 (1 when no row is labelled); the eligible rows are the live,
+        allowed, labelled ones.  p(c | q) = sum over the eligible rows of class c of exp(-scale d) / the same sum over every eligible row,
+        d search's distance.  Returns (classes int32 [nq, m], probs f32 [nq, m], log_z f32 [nq]): the m most probable classes by
+        (probability descending, class ascending), -1 / 0 behind the last class of probability > 0, and the log of the normaliser; with
+        full=True also the matrix f32 [nq, n_classes].  No eligible row: -1, 0, log_z -inf.  Bit-identical run to run for the same index,
+        labels, queries and call, not across other splits of the queries or index sizes.  ValueError unless 1 <= n_classes <= 65536,
+        1 <= m <= min(n_classes, 1024), scale is finite and > 0 and the labels are right."""
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim not in (1, 2) or q.shape[-1] != self.dim:
+            raise ValueError("queries must be [n, %d] (or one vector of %d values), not %r" % (self.dim, self.dim, q.shape))
+        q = np.ascontiguousarray(q).reshape(-1, self.dim)
+        lab, lp, n_classes, m, scale, outs, ptrs = self._class_call(labels, m, scale, q.shape[0], full)
+        words, wp = self._allow(allow)
+        if not lib().clip_amd_index_class_probs(self._live(), _fp(q), q.shape[0], lp, n_classes, m, scale, wp, *ptrs):
+            raise RuntimeError("clip_amd_index_class_probs failed (see stderr)")
+        return outs
+
+    def class_probs_ids(self, ids, labels, m=1, scale=100.0, exclude_self=True, allow=None, full=False):
+        """class_probs with the stored rows `ids` (each a live id) as the queries, bit for bit as search_ids takes them; exclude_self: a
+        row contributes nothing to its own probabilities (leave-one-out).  The query rows need not be labelled or allowed."""
+        a = np.zeros(np.size(ids) + 1, dtype=np.int64)[:np.size(ids)]
+        a[:] = np.asarray(ids, dtype=np.int64).reshape(-1)
+        lab, lp, n_classes, m, scale, outs, ptrs = self._class_call(labels, m, scale, a.size, full)
+        words, wp = self._allow(allow)
+        if not lib().clip_amd_index_class_probs_ids(self._live(), a.ctypes.data_as(C.POINTER(C.c_int64)), a.size, lp, n_classes, m, scale,
+                                                    int(bool(exclude_self)), wp, *ptrs):
+            raise RuntimeError("clip_amd_index_class_probs_ids failed (see stderr)")
+        return outs
+
+    def class_probs_device(self, d_queries, n_queries, d_labels, n_classes, d_classes, d_probs, d_log_z, m=1, scale=100.0, d_allow=None,
+                           d_all_probs=None):
+        """class_probs on device pointers (ints): queries [n, dim] f32, labels [len] int32 (a value outside 0 ... n_classes - 1 counts as
+        unlabelled), d_allow uint64 words (0 / None: every row) -> classes int32 / probs f32 [n, m], log_z f32 [n] and, unless 0 /
+        None, all_probs f32 [n, n_classes]; asynchronous on the context's stream."""
+        m, scale = self._class_args(m, scale, int(n_classes))
+        if not lib().clip_amd_index_class_probs_device(self._live(), C.c_void_p(d_queries or None), int(n_queries), C.c_void_p(d_labels or None),
+                                                       int(n_classes), m, scale, C.c_void_p(d_allow or None), C.c_void_p(d_classes or None),
+                                                       C.c_void_p(d_probs or None), C.c_void_p(d_log_z or None), C.c_void_p(d_all_probs or None)):
+            raise RuntimeError("clip_amd_index_class_probs_device failed (see stderr)")
+
     def search_index(self, src, k, ids=None, allow=None):
         """This index searched with the stored rows of `src` (an Index of the same Clip, dim and dtype without removed rows): every row in
         id order, or the rows `ids` (duplicates and any order are fine).  (distances f32 [n, k], ids int64 [n, k]) as `search` gives them
@@ -2457,6 +2534,12 @@ def bench_softmax(dtype, n, dim, n_queries, k=10, iters=10):
     """Microseconds (device time) per clip_amd_index_softmax_device of n_queries seeded random queries at scale 100 over the n seeded random
     rows of bench_search (clip_amd_bench_softmax); < 0 on error."""
     return float(lib().clip_amd_bench_softmax(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(k), int(iters)))
+
+
+def bench_class_probs(dtype, n, dim, n_queries, n_classes, iters=10):
+    """Microseconds (device time) per clip_amd_index_class_probs_device (m = 1, no matrix) of n_queries seeded random queries at scale 100
+    over the n seeded random rows of bench_search, row labels a seeded hash modulo n_classes (clip_amd_bench_class_probs); < 0 on error."""
+    return float(lib().clip_amd_bench_class_probs(Index.DTYPES[dtype], int(n), int(dim), int(n_queries), int(n_classes), int(iters)))
 
 
 def bench_knn(dtype, n, dim, k, route=0, iters=3):

@@ -473,6 +473,41 @@ struct SoftmaxArgs {
 bool launch_softmax_sweep(const SoftmaxArgs & a, hipStream_t stream);
 void launch_softmax_finish(const float * part, int n_chunks, int ncols, int k, float beta, const float * din, const int64_t * iin, float * dist,
                            int64_t * ids, float * probs, float * log_z, hipStream_t stream);
+// Class probabilities (k_classes.hip).  Column c is the prepared query row c; kd [ncols] holds the smallest distance the search (k = 1)
+// found for it over the eligible labelled rows, which are the set bits of mask (the voter bitmap of k_vote.hip, never NULL; qself as for
+// softmax above).  labels: device, [n rounded up to 16] int32, read as 16-byte groups; a value outside 0 ... n_classes - 1 adds nothing.
+// sweep: part [n_chunks][ncols][W] := each chunk's sum of exp(-beta (d - m)) per class c0 ... c0 + W - 1, W = min(n_classes - c0,
+// CLASS_WINDOW) (rows_per_chunk from class_rows_per_chunk, which keeps n_chunks x ncols x W floats within 128 MB; nothing is launched
+// for n == 0).  fold: sums [ncols][n_classes] (double) := per column and class of the window the partials added in chunk order.
+// finish (after every window's fold): Z := the column's sums added in class order; log_z[c] := -beta kd[c] + log Z; all_probs (NULL: not
+// wanted) [ncols][n_classes] := S / Z; classes / probs [ncols][m] := the m best classes by (probability descending, class ascending), -1
+// / 0 behind the last class of probability > 0; a column with kid[c] < 0, and with `none` every column (sums, kd, kid not read): -inf,
+// zeros and -1.  1 <= m <= 1024.
+constexpr int CLASS_WINDOW = 512;
+struct ClassArgs {
+    const void * rows = nullptr;
+    const float * rinv = nullptr;
+    int64_t n = 0;
+    int Dpad = 0, dtype = 0;
+    const void * q = nullptr;
+    const float * qinv = nullptr;
+    const float * kd = nullptr;
+    const int * qself = nullptr;
+    const int * labels = nullptr;
+    int ncols = 0, n_classes = 1, c0 = 0;
+    float beta = 1.f;
+    float * part = nullptr;
+    int n_chunks = 0;
+    int64_t rows_per_chunk = 0;
+    const uint32_t * mask = nullptr;
+};
+int64_t class_rows_per_chunk(int64_t n, int ncols, int n_classes);
+// labels: dst [n_pad] := src [n] (both device) with every value outside 0 ... n_classes - 1, and the padding, as -1
+void launch_class_labels(const int * src, int64_t n, int64_t n_pad, int n_classes, int * dst, hipStream_t stream);
+bool launch_class_sweep(const ClassArgs & a, hipStream_t stream);
+void launch_class_fold(const float * part, int n_chunks, int ncols, int c0, int n_classes, double * sums, hipStream_t stream);
+void launch_class_finish(const double * sums, int ncols, int n_classes, int m, float beta, const float * kd, const int64_t * kid, bool none, int * classes,
+                         float * probs, float * log_z, float * all_probs, hipStream_t stream);
 // Biased search (k_bias.hip).  scan: launch_search_scan's plain scan (groups / qgroup unused) ranking by distance + a.bias[row], one f32
 // addition; the candidates hold (score, id), so launch_search_merge follows unchanged.  finish: the merge tree's lists (in, `in_stride` pairs
 // apart; nq * k >= 1 slots, the index not empty) -> scores / dist / ids [nq][k]: the score as ranked, the plain distance of the pair computed

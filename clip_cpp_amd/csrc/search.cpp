@@ -15,6 +15,7 @@
 //   k_rank.hip      rank and count queries (rank_blocks: key -> count -> finish per block of columns; the host arithmetic in rank_host.h)
 //   k_select.hip    selection of an order statistic and pages at any depth (select_blocks: init -> (sweep -> pick) per digit -> collect -> finish)
 //   k_softmax.hip   softmax over every eligible row (softmax_blocks: the sweep and its finish as the sink of search_blocks)
+//   k_classes.hip   class probabilities over labelled rows (class_blocks: per window of classes the sweep and its fold, then the finish)
 // and appending one index to another, the live bitmap behind row removal, compaction and subset search, and the CLIPIDX1 file format.
 // The benchmark and test hooks are in search_bench.cpp; search_impl.h holds what the two files share.
 // Single owners: search_device_impl (the passes of a search: one ScanArgs per scan launch, whatever the selection), search_blocks and
@@ -2151,6 +2152,233 @@ bool clip_amd_index_softmax_index(struct clip_amd_index * ix, struct clip_amd_in
         (void)hipSetDevice(ix->device);
         SoftmaxOut o{distances, out_ids, probs, log_z};
         return softmax_host(ix, nullptr, ids, src, nq, k, scale, false, allow, o, fn);
+    });
+}
+
+}  // extern "C"
+
+namespace {
+
+constexpr int MAX_CLASSES = 65536;
+constexpr int64_t CLASS_BLOCK = 1024;                      // queries per block: at 512 classes a chunk's partials are 2 MB, so 64 chunks fit
+constexpr size_t CLASS_SUMS_BUDGET = (size_t)64 << 20;     // bytes of per-class sums (f64) one query block leaves on the device
+
+// queries per block of a class-probability call: whole workgroup column blocks of 64, at most CLASS_BLOCK, and as many as keep the
+// block's [queries][n_classes] sums within their budget (128 at 65 536 classes)
+int64_t class_block(int64_t nq, int n_classes) {
+    const int64_t fit = (int64_t)(CLASS_SUMS_BUDGET / ((size_t)n_classes * sizeof(double))) / 64 * 64;
+    return std::min<int64_t>({(nq + 63) / 64 * 64, CLASS_BLOCK, fit});
+}
+
+// A call's labels (one per stored row, on the host or on the device) in their workspace, padded to the 16-byte groups the sweep of
+// k_classes.hip reads; an empty index has none.  The host forms checked their labels; the device form's go through launch_class_labels,
+// which makes a value outside 0 ... n_classes - 1 unlabelled, so such a row is no voter and cannot set a query's minimum.
+bool stage_labels(clip_amd_index * ix, const int32_t * labels, bool on_host, int n_classes, const char * fn, const int *& d_labels) {
+    d_labels = nullptr;
+    if (ix->n == 0) return true;
+    const int64_t n_pad = (ix->n + 15) / 16 * 16;
+    if (!ensure(ix, ix->vlabels, (size_t)n_pad * sizeof(int32_t))) return false;
+    if (!on_host) {
+        launch_class_labels((const int *)labels, ix->n, n_pad, n_classes, (int *)ix->vlabels.p, stream_of(ix));
+        if (!launched(true, fn)) return false;
+    } else if (hipMemcpyAsync(ix->vlabels.p, labels, (size_t)ix->n * sizeof(int32_t), hipMemcpyHostToDevice, stream_of(ix)) != hipSuccess) {
+        fprintf(stderr, "%s: the upload of labels failed: %s\n", fn, hipGetErrorString(hipGetLastError()));
+        return false;
+    }
+    d_labels = (const int *)ix->vlabels.p;
+    return true;
+}
+
+// Class probabilities (k_classes.hip) as the sink of search_blocks.  The eligible labelled rows are the voter bitmap of k_vote.hip
+// (live & allow & labelled), built once per call; a block of queries is searched under it with k = 1 on the scan route, which leaves
+// its minimum distance; then the block's queries are prepared (or gathered) once more as one run of rows and, per window of CLASS_WINDOW
+// classes, the sweep sums exp(-beta (d - m)) per (chunk, column, class) and the fold adds the chunks into the block's sums; the finish
+// writes classes, probs, log_z and, where wanted, the whole matrix to dest(q0) (device); done(q0, m_block) follows every block.
+// d_labels: stage_labels'.  An empty index: -1, zeros and -inf from the finish alone.
+template <typename Source, typename Dest, typename Done>
+bool class_blocks(clip_amd_index * ix, int64_t nq, const int * d_labels, int n_classes, int m, float beta, const uint32_t * d_allow, const char * fn,
+                  Source && source, Dest && dest, Done && done) {
+    hipStream_t st = stream_of(ix);
+    const int64_t n = ix->n;
+    if (nq == 0) return true;
+    const int64_t block = class_block(nq, n_classes);
+    if (n == 0) {
+        for (int64_t q0 = 0; q0 < nq; q0 += block) {
+            const int mb = (int)std::min(block, nq - q0);
+            const ClassOut o = dest(q0);
+            launch_class_finish(nullptr, mb, n_classes, m, beta, nullptr, nullptr, true, o.classes, o.probs, o.log_z, o.all, st);
+            if (!launched(true, fn) || !done(q0, mb)) return false;
+        }
+        return true;
+    }
+    const size_t vb = live_bytes(n);
+    if (!ensure(ix, ix->vvoters, vb + 16)) return false;
+    uint32_t * voters = (uint32_t *)ix->vvoters.p;
+    uint32_t * d_mixed = (uint32_t *)((char *)ix->vvoters.p + vb);
+    (void)hipMemsetAsync(d_mixed, 0, 4, st);
+    launch_vote_voters(ix->store.live, d_allow, search_allow_words(n), d_labels, voters, (int64_t)(vb / 4), d_mixed, st);
+    if (!launched(true, fn)) return false;
+    const int cols = (int)std::min(nq, block);
+    const int64_t rpc = class_rows_per_chunk(n, cols, n_classes);
+    const int n_chunks = (int)((n + rpc - 1) / rpc);
+    if (!ensure(ix, ix->cpart, (size_t)n_chunks * cols * std::min(n_classes, CLASS_WINDOW) * sizeof(float)) ||
+        !ensure(ix, ix->csums, (size_t)cols * n_classes * sizeof(double)))
+        return false;
+    const GraphPlan p = graph_plan(ix, 1, 1, false, block, block);
+    QuerySource cur;
+    return search_blocks(
+        ix, nq, 1, p, voters, fn, [&](int64_t q0, int mb) { return cur = source(q0, mb); }, [](int64_t, int) { return false; },
+        [&](int64_t q0, int mb, const float * d_dist, const int64_t * d_ids) {
+            const ClassOut o = dest(q0);
+            if (!(cur.by_id ? gather_queries(ix, cur, 0, mb, mb) : prepare_queries(ix, cur.d_q, mb, mb))) return false;
+            ClassArgs a;
+            a.rows = ix->store.rows;
+            a.rinv = ix->store.rinv;
+            a.n = n;
+            a.Dpad = ix->Dpad;
+            a.dtype = ix->dtype;
+            a.q = ix->qbuf.p;
+            a.qinv = (const float *)ix->qinv.p;
+            a.kd = d_dist;
+            a.qself = cur.exclude_self ? (const int *)ix->qself.p : nullptr;
+            a.labels = d_labels;
+            a.ncols = mb;
+            a.n_classes = n_classes;
+            a.beta = beta;
+            a.part = (float *)ix->cpart.p;
+            a.n_chunks = n_chunks;
+            a.rows_per_chunk = rpc;
+            a.mask = voters;
+            for (a.c0 = 0; a.c0 < n_classes; a.c0 += CLASS_WINDOW) {
+                if (!launch_class_sweep(a, st)) {
+                    fprintf(stderr, "%s: sweep launch failed\n", fn);
+                    return false;
+                }
+                launch_class_fold(a.part, n_chunks, mb, a.c0, n_classes, (double *)ix->csums.p, st);
+            }
+            launch_class_finish((const double *)ix->csums.p, mb, n_classes, m, beta, d_dist, d_ids, false, o.classes, o.probs, o.log_z, o.all, st);
+            return launched(true, fn) && done(q0, mb);
+        });
+}
+
+// The host forms: the queries are f32 vectors (queries) or stored rows (ids).  Labels and the allowed set go up once; a block's queries
+// are staged, its results land in the results arena and are copied out before the next block, so nothing on the device grows with the call.
+bool class_host(clip_amd_index * ix, const float * queries, const int64_t * ids, int64_t nq, const int32_t * labels, int n_classes, int m, float beta,
+                bool exclude_self, const uint64_t * allow, const ClassOut & out, const char * fn) {
+    if (nq == 0) return true;
+    const uint32_t * d_allow = nullptr;
+    const int * d_labels = nullptr;
+    if (!upload_allow(ix, allow, d_allow) || !stage_labels(ix, labels, true, n_classes, fn, d_labels)) return false;
+    const int64_t block = class_block(nq, n_classes);
+    Arena a(ix);
+    const auto o_classes = a.add(out.classes, (size_t)block * m);
+    const auto o_probs = a.add(out.probs, (size_t)block * m);
+    const auto o_logz = a.add(out.log_z, (size_t)block);
+    const auto o_all = a.add(out.all, out.all ? (size_t)block * n_classes : 0);      // (the matrix takes room only when it is wanted)
+    if (!a.ready() || !reserve_stage(ix, queries, ids, block)) return false;
+    ClassOut d;
+    d.classes = a.dev(o_classes);
+    d.probs = a.dev(o_probs);
+    d.log_z = a.dev(o_logz);
+    d.all = a.dev(o_all);
+    return class_blocks(
+        ix, nq, d_labels, n_classes, m, beta, d_allow, fn, [&](int64_t q0, int mb) { return stage_block(ix, queries, ids, q0, mb, exclude_self); },
+        [&](int64_t) { return d; },
+        [&](int64_t q0, int mb) {
+            a.queue(0, 2, 0, (size_t)q0 * m, (size_t)mb * m);
+            a.queue(2, 3, 0, (size_t)q0, (size_t)mb);
+            a.queue(3, 4, 0, (size_t)q0 * n_classes, (size_t)mb * n_classes);
+            return stream_done(ix, fn, hipGetLastError());      // (the staging buffers and the block's results are reused)
+        });
+}
+
+// what every class-probability entry point asks: the index, 1 <= n_classes <= 65 536, 1 <= m <= min(n_classes, 1024), a usable scale,
+// the three result arrays when there is a row to write, labels when there is a row to label; host_labels: each in -1 ... n_classes - 1
+bool check_class_args(const clip_amd_index * ix, int64_t nq, const int32_t * labels, bool host_labels, int n_classes, int m, float beta,
+                      const ClassOut & o, const char * fn) {
+    if (!check_index(ix, fn)) return false;
+    if (nq < 0 || nq > MAX_ROWS) { fprintf(stderr, "%s: %lld queries outside 0 ... %lld\n", fn, (long long)nq, (long long)MAX_ROWS); return false; }
+    if (n_classes < 1 || n_classes > MAX_CLASSES) { fprintf(stderr, "%s: n_classes = %d outside 1 ... %d\n", fn, n_classes, MAX_CLASSES); return false; }
+    if (m < 1 || m > std::min(n_classes, MAX_K)) {
+        fprintf(stderr, "%s: m = %d outside 1 ... min(n_classes, %d) = %d\n", fn, m, MAX_K, std::min(n_classes, MAX_K));
+        return false;
+    }
+    if (!(beta > 0.f) || std::isinf(beta)) { fprintf(stderr, "%s: scale %g is not a finite value > 0\n", fn, (double)beta); return false; }
+    if (nq > 0 && (!o.classes || !o.probs || !o.log_z)) { fprintf(stderr, "%s: NULL result pointer\n", fn); return false; }
+    if (!labels && ix->n > 0) { fprintf(stderr, "%s: labels is NULL\n", fn); return false; }
+    for (int64_t r = 0; host_labels && labels && r < ix->n; r++)
+        if (labels[r] < -1 || labels[r] >= n_classes) {
+            fprintf(stderr, "%s: labels[%lld] = %d outside -1 (unlabelled) ... %d\n", fn, (long long)r, (int)labels[r], n_classes - 1);
+            return false;
+        }
+    return true;
+}
+
+ClassOut class_out(int32_t * classes, float * probs, float * log_z, float * all_probs) {
+    ClassOut o;
+    o.classes = classes;
+    o.probs = probs;
+    o.log_z = log_z;
+    o.all = all_probs;
+    return o;
+}
+
+}  // namespace
+
+// The device form: queries, labels and allowed set on the device, results straight into the caller's arrays
+bool idx::class_probs_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, const int * d_labels, int n_classes, int m, float beta,
+                                  const uint32_t * d_allow, const ClassOut & out, const char * fn) {
+    if (nq == 0) return true;
+    const int * labels = nullptr;
+    if (!stage_labels(ix, d_labels, false, n_classes, fn, labels)) return false;
+    return class_blocks(
+        ix, nq, labels, n_classes, m, beta, ix->n > 0 ? d_allow : nullptr, fn, [&](int64_t q0, int) { return vectors(d_q + (size_t)q0 * ix->dim); },
+        [&](int64_t q0) {
+            ClassOut o;
+            o.classes = out.classes + (size_t)q0 * m;
+            o.probs = out.probs + (size_t)q0 * m;
+            o.log_z = out.log_z + q0;
+            o.all = out.all ? out.all + (size_t)q0 * n_classes : nullptr;
+            return o;
+        },
+        [](int64_t, int) { return true; });
+}
+
+extern "C" {
+
+bool clip_amd_index_class_probs(struct clip_amd_index * ix, const float * queries, int n_queries, const int32_t * labels, int n_classes, int m, float scale,
+                                const uint64_t * allow, int32_t * classes, float * probs, float * log_z, float * all_probs) {
+    return guarded(__func__, false, [&](const char * fn) {
+        const ClassOut o = class_out(classes, probs, log_z, all_probs);
+        if (!check_class_args(ix, n_queries, labels, true, n_classes, m, scale, o, fn)) return false;
+        if (n_queries > 0 && !queries) { fprintf(stderr, "%s: NULL queries\n", fn); return false; }
+        (void)hipSetDevice(ix->device);
+        return class_host(ix, queries, nullptr, n_queries, labels, n_classes, m, scale, false, allow, o, fn);
+    });
+}
+
+bool clip_amd_index_class_probs_ids(struct clip_amd_index * ix, const int64_t * ids, int64_t n_ids, const int32_t * labels, int n_classes, int m,
+                                    float scale, int exclude_self, const uint64_t * allow, int32_t * classes, float * probs, float * log_z,
+                                    float * all_probs) {
+    return guarded(__func__, false, [&](const char * fn) {
+        const ClassOut o = class_out(classes, probs, log_z, all_probs);
+        if (!check_class_args(ix, n_ids, labels, true, n_classes, m, scale, o, fn)) return false;
+        if (n_ids > 0 && !ids) { fprintf(stderr, "%s: NULL ids\n", fn); return false; }
+        (void)hipSetDevice(ix->device);
+        if (!check_stored_ids(ix, ids, n_ids, fn)) return false;
+        return class_host(ix, nullptr, ids, n_ids, labels, n_classes, m, scale, exclude_self != 0, allow, o, fn);
+    });
+}
+
+bool clip_amd_index_class_probs_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, const int32_t * d_labels, int n_classes,
+                                       int m, float scale, const uint64_t * d_allow, int32_t * d_classes, float * d_probs, float * d_log_z,
+                                       float * d_all_probs) {
+    return guarded(__func__, false, [&](const char * fn) {
+        const ClassOut o = class_out(d_classes, d_probs, d_log_z, d_all_probs);
+        if (!check_class_args(ix, n_queries, d_labels, false, n_classes, m, scale, o, fn)) return false;
+        if (n_queries > 0 && !d_queries) { fprintf(stderr, "%s: NULL queries\n", fn); return false; }
+        (void)hipSetDevice(ix->device);
+        return class_probs_device_impl(ix, d_queries, n_queries, (const int *)d_labels, n_classes, m, scale, (const uint32_t *)d_allow, o, fn);
     });
 }
 

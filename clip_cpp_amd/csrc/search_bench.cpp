@@ -512,6 +512,36 @@ float clip_amd_bench_softmax(int dtype, int64_t n, int dim, int n_queries, int k
     });
 }
 
+float clip_amd_bench_class_probs(int dtype, int64_t n, int dim, int n_queries, int n_classes, int iters) {
+    return guarded(__func__, -4.f, [&](const char * fn) {
+        const bool args_ok = n_queries >= 1 && n_classes >= 1 && n_classes <= 65536;
+        return bench_on_gallery(dtype, n, dim, n_queries, iters, args_ok, PLANT_NONE, [&](clip_amd_index * ix, float * src) {
+            Buf own;
+            Arena a(ix, own);
+            const auto o_classes = a.add<int32_t>(nullptr, (size_t)n_queries);
+            const auto o_probs = a.add<float>(nullptr, (size_t)n_queries), o_logz = a.add<float>(nullptr, (size_t)n_queries);
+            const auto o_labels = a.add<int32_t>(nullptr, (size_t)n);
+            if (!a.ready()) return -4.f;
+            std::vector<int32_t> labels((size_t)n);
+            for (int64_t r = 0; r < n; r++) {                  // splitmix64 of the row number under a fixed seed
+                uint64_t z = 0xC1A55ull + (uint64_t)r * 0x9E3779B97F4A7C15ull;
+                z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+                z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+                labels[(size_t)r] = (int32_t)((z ^ (z >> 31)) % (uint64_t)n_classes);
+            }
+            if (hipMemcpy(a.dev(o_labels, true), labels.data(), (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) return -4.f;
+            launch_search_fill_random(src, (int64_t)n_queries * dim, 0xC0FFEEull, nullptr);
+            ClassOut o;
+            o.classes = a.dev(o_classes, true);
+            o.probs = a.dev(o_probs, true);
+            o.log_z = a.dev(o_logz, true);
+            return time_device(iters, [&]() {
+                return class_probs_device_impl(ix, src, n_queries, a.dev(o_labels, true), n_classes, 1, 100.f, nullptr, o, fn);
+            });
+        });
+    });
+}
+
 float clip_amd_bench_search_biased(int dtype, int64_t n, int dim, int n_queries, int k, int iters) {
     return guarded(__func__, -4.f, [&](const char *) {
         return bench_on_gallery(dtype, n, dim, n_queries, iters, n_queries >= 1 && k >= 1 && k <= MAX_K, PLANT_NONE, [&](clip_amd_index * ix, float * src) {

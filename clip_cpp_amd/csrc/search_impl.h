@@ -106,6 +106,9 @@ struct clip_amd_index {
     Buf selpage;                   // one block's collected page keys [queries][k] (u64)
     // softmax over every eligible row
     Buf spart;                    // one block's partial sums [n_chunks][columns] (f32)
+    // class probabilities
+    Buf cpart;                     // one block's partial sums [n_chunks][columns][classes of a window] (f32)
+    Buf csums;                     // one block's sums [columns][n_classes] (f64)
     // biased search
     Buf bias;                      // [n rounded up to 64] the call's bias column, padded as rinv is (the scan reads it 4 at a time)
 };
@@ -222,6 +225,15 @@ struct VoteOut {
     int64_t * ids = nullptr;
 };
 
+// The result arrays of a class-probability call: classes / probs [rows][m], log_z [rows], all [rows][n_classes] (NULL: not wanted), on the
+// device or on the host
+struct ClassOut {
+    int32_t * classes = nullptr;
+    float * probs = nullptr;
+    float * log_z = nullptr;
+    float * all = nullptr;
+};
+
 // What a compound call's small host arrays say, after check_compound_args: tt = the smallest of {2, 4, 8} that holds the longest query
 struct CompoundCall {
     const int64_t * term_ids = nullptr;
@@ -271,6 +283,8 @@ bool select_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, cons
                         float * d_dist, int64_t * d_ids, const char * fn);
 bool softmax_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, int k, float beta, const uint32_t * d_allow, float * d_dist,
                          int64_t * d_ids, float * d_probs, float * d_log_z, const char * fn);
+bool class_probs_device_impl(clip_amd_index * ix, const float * d_q, int64_t nq, const int * d_labels, int n_classes, int m, float beta,
+                             const uint32_t * d_allow, const ClassOut & out, const char * fn);
 bool vote_host(clip_amd_index * ix, const float * queries, const int64_t * ids, int64_t nq, int k, int m, bool exclude_self, const int32_t * labels,
                const uint64_t * allow, const VoteOut & out, const char * fn);
 int64_t join_impl(clip_amd_index * ix, const float * d_q, int nq, bool pairs, float radius, const uint32_t * d_allow, int64_t * lims,

@@ -154,6 +154,12 @@ pictures lie in the wrong folder?" (one Index.vote_graph call; no image is decod
 every labelled image whose winning class is not its own, in id order, "  %d/%d %f %s -> %s ~ %s": the winner's votes, voters counted, the
 distance of the winner's nearest member, the image's path, the winning class and that member's path; then
 "main: %d labelled images, %d filed against their neighbours, %d with no voter".  Neither supports a database built with --grid.
+`file --prob [--scale S]` and `audit --prob [--scale S]` put class probabilities in the votes' place (Index.class_probs / class_probs_ids:
+every labelled image contributes exp(-S * distance) to its folder, S 100 by default; no K, so -k is refused): `file` prints per image
+"%f\t%s" = probability, folder for its -n most probable folders and ends "main: %d images, scale %g"; `audit` prints, for every labelled
+image whose own folder is not the most probable one (itself excluded), lowest own-folder probability first, "%f\t%s\t%s\t%f" = own
+probability, path, best folder, its probability, then "main: %d labelled images, %d more probably in another folder, %d with no other
+labelled image".
 
 `closest` answers "which are the most similar pairs of images I have?" without a radius (Index.closest_pairs; nothing is decoded or
 encoded): "closest:" at verbosity > 0, then the -n N (default 50) closest pairs, nearest first, as "%f<TAB>%s<TAB>%s": the distance and
@@ -1574,6 +1580,9 @@ def neighbors(argv):
 
 VOTE_K = 10         # -k of `file` and `audit`: the voters counted per image
 FILE_CLASSES = 3    # -n of `file`: the classes printed per image
+PROB_MAX_CLASSES = 65536    # the classes Index.class_probs takes
+AUDIT_PROB_BLOCK = 4096     # images per Index.class_probs_ids call of `audit --prob` at most, and
+AUDIT_PROB_BYTES = 64 << 20     # the bytes of the [images, classes] f32 matrix that comes back to the host per call at most
 
 
 def _parse_vote(argv, file):
@@ -1583,6 +1592,8 @@ def _parse_vote(argv, file):
     takes = {"-m": "model", "--model": "model", "-v": "verbose", "--verbose": "verbose", "--db": "db", "-k": "k", "--labels": "labels", "--in": "in"}
     if file:
         takes.update({"-t": "threads", "--threads": "threads", "-n": "results", "--results": "results"})
+    takes["--scale"] = "scale"
+    seen = set()
     i = 0
     while i < len(argv):
         a = argv[i]
@@ -1591,13 +1602,16 @@ def _parse_vote(argv, file):
             if i >= len(argv):
                 return None
             key = takes[a]
+            seen.add(key)
             if key == "in":
                 p["in"].append(argv[i])
             else:
                 try:
-                    p[key] = int(argv[i]) if key in ("threads", "verbose", "k", "results") else argv[i]
+                    p[key] = int(argv[i]) if key in ("threads", "verbose", "k", "results") else float(argv[i]) if key == "scale" else argv[i]
                 except ValueError:
                     return None
+        elif a == "--prob":
+            p["prob"] = True
         elif a in ("-h", "--help"):
             _help_vote(file, p)
             sys.exit(0)
@@ -1617,6 +1631,15 @@ def _parse_vote(argv, file):
         return None
     if p["results"] < 1:
         print("main: -n %d: file prints at least one class" % p["results"])
+        return None
+    if "scale" in seen and not p.get("prob"):
+        print("main: --scale is the scale of --prob: it needs --prob")
+        return None
+    if p.get("prob") and "k" in seen:
+        print("main: --prob cannot be combined with -k: every labelled image contributes to a class's probability, there is no k to pick")
+        return None
+    if "scale" in seen and not 0.0 < p["scale"] < float("inf"):
+        print("main: --scale takes a finite value > 0, not %s" % p["scale"])
         return None
     return p
 
@@ -1644,6 +1667,14 @@ def _help_vote(file, p):
     print("  --labels FILE: lines `label<TAB>path` instead of the folders: the listed images carry that label, every other image is unlabelled")
     print("      (it may be asked about, it never votes). A path that is not in the database is an error.")
     print("  --in PREFIX: only images whose path starts with PREFIX vote%s. Repeatable." % ("" if file else " and are audited"))
+    if file:
+        print("  --prob: class probabilities in the votes' place (Index.class_probs: every labelled image contributes exp(-scale * distance) to its")
+        print("      folder, no K): per IMAGE the N most probable folders as `probability<TAB>folder`. Not with -k.")
+    else:
+        print("  --prob: class probabilities in the votes' place (Index.class_probs_ids, each image itself excluded): the images whose own folder is")
+        print("      not the most probable one, lowest own-folder probability first, as `own probability<TAB>path<TAB>best folder<TAB>its")
+        print("      probability`. Not with -k.")
+    print("  --scale S: the scale of --prob, finite and > 0. Default: %g" % PROB_SCALE)
 
 
 def read_labels(image_paths, labels_file=None):
@@ -1689,6 +1720,9 @@ def _open_votes(p, command):
         labels, names = read_labels(image_paths, p["labels"])
     except (OSError, ValueError) as e:
         _err("main: %s" % e)
+        return None
+    if p.get("prob") and len(names) > PROB_MAX_CLASSES:
+        _err("main: %s --prob takes at most %d folders (labels), this database has %d" % (command, PROB_MAX_CLASSES, len(names)))
         return None
     allow = None
     if p["in"]:
@@ -1737,10 +1771,33 @@ def file_images(argv):
     if vecs and index.dim != next(iter(vecs.values())).size:
         _err("main: the index holds %d-dimensional embeddings, the model makes %d" % (index.dim, next(iter(vecs.values())).size))
         return 1
+    stored = [row_of[a] for a in p["rest"] if a in row_of]
+    if p.get("prob"):                              # class probabilities in the votes' place: `probability<TAB>folder` per reported class
+        m, scale = min(p["results"], max(len(names), 1), MAX_K), p.get("scale", PROB_SCALE)
+        res_stored = index.class_probs_ids(stored, labels, m=m, scale=scale, allow=allow) if stored else None
+        res_out = index.class_probs(np.stack([vecs[a] for a in outside]), labels, m=m, scale=scale, allow=allow) if outside else None
+        if p["verbose"] > 0:
+            print("filing:")
+        si = oi = 0
+        for t, a in enumerate(p["rest"]):
+            if t:
+                print()
+            print(a)
+            if a in row_of:
+                res, r, si = res_stored, si, si + 1
+            else:
+                res, r, oi = res_out, oi, oi + 1
+            for c, pr in zip(res[0][r], res[1][r]):
+                if c >= 0:
+                    print("%f\t%s" % (pr, names[c]))
+        print("main: %d images, scale %g" % (len(p["rest"]), scale))
+        sys.stdout.flush()
+        index.close()
+        clip.close()
+        return 0
     k, m = p["k"], min(p["results"], p["k"])
     voter = labels >= 0 if allow is None else (labels >= 0) & allow
     n_voters = int(voter.sum())
-    stored = [row_of[a] for a in p["rest"] if a in row_of]
     res_stored = index.vote_ids(stored, k, labels, m=m, allow=allow) if stored else None
     res_out = index.vote(np.stack([vecs[a] for a in outside]), k, labels, m=m, allow=allow) if outside else None
     if p["verbose"] > 0:
@@ -1781,10 +1838,31 @@ def audit(argv):
         print("main: Unable to load model from %s" % p["model"])
         return 1
     index = clip_cpp_amd.Index.load(clip, os.path.join(p["db"], INDEX_FILE))
-    k = p["k"]
-    classes, votes, dist, ids = index.vote_graph(k, labels, m=1, allow=allow)
     voter = labels >= 0 if allow is None else (labels >= 0) & allow
     n_voters = int(voter.sum())
+    if p.get("prob"):                              # every audited image's probability for its own folder, itself excluded
+        scale = p.get("scale", PROB_SCALE)
+        audited = np.flatnonzero(voter)
+        found, lonely = [], 0
+        block = max(1, min(AUDIT_PROB_BLOCK, AUDIT_PROB_BYTES // (4 * max(len(names), 1))))
+        for b0 in range(0, audited.size, block):
+            rows = audited[b0:b0 + block]
+            classes, probs, _, full = index.class_probs_ids(rows, labels, m=1, scale=scale, allow=allow, full=True)
+            own = full[np.arange(rows.size), labels[rows]]
+            lonely += int((classes[:, 0] < 0).sum())
+            found += [(float(own[t]), int(rows[t]), int(classes[t, 0]), float(probs[t, 0]))
+                      for t in np.flatnonzero((classes[:, 0] >= 0) & (classes[:, 0] != labels[rows]))]
+        if p["verbose"] > 0:
+            print("misfiled:")
+        for own_p, i, c, best_p in sorted(found):
+            print("%f\t%s\t%s\t%f" % (own_p, image_paths[i], names[c], best_p))
+        print("main: %d labelled images, %d more probably in another folder, %d with no other labelled image" % (n_voters, len(found), lonely))
+        sys.stdout.flush()
+        index.close()
+        clip.close()
+        return 0
+    k = p["k"]
+    classes, votes, dist, ids = index.vote_graph(k, labels, m=1, allow=allow)
     if p["verbose"] > 0:
         print("misfiled:")
     against = lonely = 0

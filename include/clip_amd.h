@@ -632,6 +632,46 @@ bool clip_amd_index_softmax_index(struct clip_amd_index * ix, struct clip_amd_in
 /* Average device time (microseconds) of one clip_amd_index_softmax_device of n_queries seeded random queries over the n seeded random
  * rows of clip_amd_bench_search on the current device, scale 100; < 0 on error.  Used by scripts/softmax_bench.py. */
 float clip_amd_bench_softmax(int dtype, int64_t n, int dim, int n_queries, int k, int iters);
+/* Class probabilities over labelled rows: "into which folder does this picture go, and how surely?".  The soft form of the votes: no k,
+ * every labelled row of a class contributes (the cache model of Tip-Adapter, a Parzen / soft nearest-neighbour classifier).  labels is
+ * int32[size(ix)]: -1 = unlabelled (such a row may ask but contributes nothing, as in the votes), else a class in 0 ... n_classes - 1.
+ * A row is ELIGIBLE when it is live, set in allow (NULL = every live row), labelled and, class_probs_ids with exclude_self != 0, not the
+ * query's own row.  d(q, r) is the f32 distance search reports for the pair, with the same bits.  With
+ *   m(q)     = the smallest d(q, r) over the eligible rows (the call searches them with k = 1 first),
+ *   S_c(q)   = the sum over the eligible rows of class c of exp(-scale (d(q, r) - m(q))): every term <= 1, the nearest row's term 1,
+ *   Z(q)     = the sum of S_c over the classes in ascending order,
+ * the call returns per query
+ *   all_probs[n_classes]  p(c | q) = S_c / Z; the array may be NULL when only the best classes are wanted,
+ *   classes[m], probs[m]  the m best classes by (probability descending, class ascending) and their probabilities; a class of
+ *                         probability 0 is not reported: -1 / 0 behind the last class of probability > 0,
+ *   log_z                 -scale m + log Z: the log of the sum of exp(-scale d) over the eligible rows.
+ * A query without an eligible row (and every query over an empty index): log_z -INFINITY, probabilities 0, classes -1.
+ * Limits: 1 <= n_classes <= 65536; 1 <= m <= min(n_classes, 1024); scale finite and > 0.  One sweep of the rows (k_classes.hip) serves
+ * a window of 512 classes, whose sums it keeps in the LDS: n_classes above 512 costs ceil(n_classes / 512) sweeps.
+ * What the bits depend on.  Every sum has a fixed order and no atomics (f32 within a chunk of rows per class, double across chunks, double
+ * across classes), so the outputs are bit-identical from run to run for the same index, labels, queries and call.  As for softmax they
+ * are NOT promised to be independent of how the queries are split across calls, of the index size, or of n_classes (which bound the
+ * chunks); such results agree to rounding (profiles/class_probs_accuracy.txt), not to the bit.
+ * Refused before any launch, with a message and the outputs untouched: a NULL index, a negative count, n_classes, m or scale outside
+ * the limits, NULL queries / ids / labels / classes / probs / log_z where there is something to read or write, a bad id (ids form), and
+ * in the host forms a label outside -1 ... n_classes - 1 (the device form does not read its labels on the host: there such a value counts as -1, unlabelled).  Zero
+ * queries succeed and write nothing.
+ * Device memory beyond the index, for one block of B <= 1024 queries at a time: the voter bitmap, a padded copy of the labels, the
+ * partial sums n_chunks x B x min(n_classes, 512) x 4 bytes with n_chunks bounded so that they stay within 128 MB, the sums
+ * B x n_classes x 8 bytes with B bounded so that they stay within 64 MB (B = 128 at 65536 classes), and the block's results. */
+bool clip_amd_index_class_probs(struct clip_amd_index * ix, const float * queries, int n_queries, const int32_t * labels, int n_classes,
+                                int m, float scale, const uint64_t * allow, int32_t * classes, float * probs, float * log_z,
+                                float * all_probs);                                                          /* host, synchronous */
+bool clip_amd_index_class_probs_ids(struct clip_amd_index * ix, const int64_t * ids, int64_t n_ids, const int32_t * labels, int n_classes,
+                                    int m, float scale, int exclude_self, const uint64_t * allow, int32_t * classes, float * probs,
+                                    float * log_z, float * all_probs);                                       /* host, synchronous */
+bool clip_amd_index_class_probs_device(struct clip_amd_index * ix, const float * d_queries, int n_queries, const int32_t * d_labels,
+                                       int n_classes, int m, float scale, const uint64_t * d_allow, int32_t * d_classes, float * d_probs,
+                                       float * d_log_z, float * d_all_probs);                                /* HBM, asynchronous */
+/* Average device time (microseconds) of one clip_amd_index_class_probs_device (m = 1, no matrix) of n_queries seeded random queries over
+ * the n seeded random rows of clip_amd_bench_search on the current device, the label of a row a seeded hash of its number modulo
+ * n_classes, scale 100; < 0 on error.  Used by scripts/classes_bench.py (its "device" column). */
+float clip_amd_bench_class_probs(int dtype, int64_t n, int dim, int n_queries, int n_classes, int iters);
 /* Biased search: the k best rows by score = d + bias[row], with d the distance clip_amd_index_search reports for the pair (same bits) and
  * bias one f32 per stored row, float[size(ix)] (host for the host forms, device for the _device form; NULL = all zeros).  The addition is
  * one f32 addition, rounded once.  Results are ordered by (score ascending, id ascending), a total order, so they are exact and do not
